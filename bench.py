@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- cell-updates/s of the MI355X-native AWFL dycore step (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--scaling weak|strong] [--nens E]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--scaling weak|strong] [--nens E] [--dump-outputs DIR]
 
 A "step" is one `Dycore::timeStep` (Dycore.h:107) over the whole resident ensemble: coupler->dycore conversion,
 CFL reduction, `ncycles` SSPRK3 sub-steps (3 tendency evaluations each) and dycore->coupler conversion, with the
@@ -38,6 +38,12 @@ Extra objects on the JSON line:
                 timed on this host on a bounded sample of the same workload (rank 0, N=1 only).
   other_configs C3 / C4 throughput on this GPU (N=1, default run only), measured the same way with fewer steps, each with its
                 own `roofline` (+ `traffic` from profiles/r03_c{3,4}_traffic.json) and `kernel_rooflines`.
+
+--dump-outputs DIR: after the K timed steps (before any un-timed pass), the coupler fields the last timed step left behind --
+what a caller of `Dycore::timeStep` reads back: density_dry, uvel, vvel, wvel, temp and every tracer -- go to DIR/<name>.npy as
+float64: whole, or, when all of them would exceed DUMP_BYTES, the same fixed, seeded sample of flat indices of every field
+(dump_sample).  The inputs are deterministic, so two builds run with the same arguments can be compared file for file.
+With N > 1 ranks it is rank 0's shard of the ensemble.
 """
 import argparse
 import copy
@@ -68,6 +74,40 @@ CONFIGS = {
             50, "uniform20km", 128000.0),
 }
 STAGE_KERNELS = ("flux", "xupd", "xtr1", "xtr2", "ptail", "trfix", "fct_mult", "update")
+OUTPUT_FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp")       # + the tracers, in registration order
+DUMP_BYTES = 60 << 20         # --dump-outputs: data bytes of all files together (below 64 MB with the .npy headers)
+DUMP_SEED = 20240607
+
+
+def dump_sample(numel, nfields):
+    """sorted flat indices of the elements --dump-outputs writes of each field (None: all); depends on the two sizes alone"""
+    per = DUMP_BYTES // (8 * nfields)
+    if numel <= per:
+        return None
+    import numpy as np
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(numel, per, replace=False))
+
+
+def dump_outputs(fields, out_dir):
+    """fields: name -> torch tensor or numpy array, one output field each, all of one size -> out_dir/<name>.npy (float64)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    first = next(iter(fields.values()))
+    idx = dump_sample(first.numel() if hasattr(first, "numel") else np.asarray(first).size, len(fields))
+    idx_dev = None
+    for name, a in fields.items():
+        if hasattr(a, "numel"):                           # a device tensor: gather the sample there, copy only that
+            import torch
+            flat = a.detach().reshape(-1)
+            if idx is not None:
+                if idx_dev is None:
+                    idx_dev = torch.from_numpy(idx).to(flat.device)
+                flat = flat.index_select(0, idx_dev)
+            out = flat.cpu().numpy()
+        else:
+            flat = np.asarray(a).reshape(-1)
+            out = flat if idx is None else flat[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(out, dtype=np.float64))
 
 
 def csrc_hash():
@@ -152,10 +192,17 @@ def launch_cpp(args):
                 fh.write(f[k].astype("<f8").tobytes())
             for t in range(len(tracers)):
                 fh.write(f["tracers"][t].astype("<f8").tobytes())
+        outp = os.path.join(td, "out.bin") if args.dump_outputs else "-"
         r = subprocess.run([driver, "--gpus", str(args.gpus), "--tile", str(nens_total // nens_gen), "--bench", str(args.steps),
-                            str(args.warmup), inp, "-"], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise SystemExit("bench.py --launcher cpp: examples/driver failed: %s" % r.stderr[-2000:])
+                            str(args.warmup), inp, outp], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise SystemExit("bench.py --launcher cpp: examples/driver failed: %s" % r.stderr[-2000:])
+        if args.dump_outputs:
+            # the driver's output file: every field (nz, ny, nx, nens_total) in float64, OUTPUT_FIELDS then the tracers
+            fields = list(OUTPUT_FIELDS) + list(names)
+            raw = np.memmap(outp, dtype="<f8", mode="r", shape=(len(fields), nz * ny * nx * nens_total))
+            dump_outputs(dict(zip(fields, raw)), args.dump_outputs)
+            del raw
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     updates = float(nens_total) * nz * ny * nx * d["substeps"]
     out = {"metric": "cell-updates/sec (AWFL dycore step)", "value": updates / d["seconds"], "unit": "cell-updates/s",
@@ -397,6 +444,11 @@ class Job:
         dycore.declare_current_profile_as_hydrostatic(coupler)
         torch.cuda.synchronize()
         self.coupler, self.dycore = coupler, dycore
+
+    def outputs(self):
+        """the coupler fields a caller of timeStep reads back (device tensors, (nz, ny, nx, nens) each)"""
+        names = list(OUTPUT_FIELDS) + list(self.coupler.get_tracer_names())
+        return {n: self.coupler.dm.get(n, readonly=True) for n in names}
 
     def one_step(self):
         if self.world > 1 or getattr(self, "sharded", False):
@@ -889,6 +941,8 @@ def worker(args):
     job = Job(args.config, args, dev, rank, world, args.nens)
     job.sharded = dd is not None
     updates, elapsed, substeps = job.timed(args.steps, args.warmup, dd, backend, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job.outputs(), args.dump_outputs)
     value = updates / elapsed
     fct_rows = job.dycore.debug_fct_rows()      # rows the LAST stage's limiter flagged / all rows
     cells = job.nens * job.nz * job.ny * job.nx
@@ -1044,6 +1098,8 @@ def build_parser():
     ap.add_argument("--cpu-worker", default="", help=argparse.SUPPRESS)
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the fields the last timed step computed to DIR/<name>.npy (float64; a fixed, seeded sample when large)")
     return ap
 
 
@@ -1059,6 +1115,8 @@ def main():
         return
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.launcher == "cpp":
         if "WORLD_SIZE" in os.environ and int(os.environ.get("RANK", "0")) != 0:
             return                      # under torch.distributed.run: rank 0 alone drives every device through the C++ path

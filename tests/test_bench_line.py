@@ -12,6 +12,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -138,6 +139,68 @@ def test_bench_py_cpp_launcher_line():
     d, _ = _run_bench("--launcher", "cpp", "--nens", "32")
     _check_contract(d, nens_per_gpu=32, need_roofline=False)
     assert "examples/driver" in d["config"]["launcher"] and d["config"]["ranks_seen"] == 1 and d["roofline"] is None
+
+
+def _dump_run(tmp_path, tag, *extra):
+    out = str(tmp_path / tag)
+    d, _ = _run_bench("--nens", "32", "--no-kernel-timing", "--dump-outputs", out, *extra)
+    return d, {n[:-4]: np.load(os.path.join(out, n)) for n in sorted(os.listdir(out))}
+
+
+@pytest.mark.gpu
+def test_bench_py_dump_outputs_of_both_launchers(tmp_path):
+    """--dump-outputs writes the coupler fields after the last timed step; the Python and the C++ launcher run the same workload
+    on the same inputs, so their files agree"""
+    d, py = _dump_run(tmp_path, "py")
+    assert sorted(py) == ["density_dry", "temp", "uvel", "vvel", "water_vapor", "wvel"]
+    # six fields of 32 x 32 x 32 x 60 doubles (15.7 MB each) exceed the budget: the seeded sample, the same on both launchers
+    n = _bench_module().dump_sample(60 * 32 * 32 * 32, 6).size
+    assert n < 60 * 32 * 32 * 32
+    for name, a in py.items():
+        assert a.dtype == np.float64 and a.shape == (n,) and np.isfinite(a).all(), name
+    assert py["density_dry"].min() > 0 and 150.0 < py["temp"].min() and py["temp"].max() < 350.0
+    assert d["steps"] == 1
+    _, cpp = _dump_run(tmp_path, "cpp", "--launcher", "cpp")
+    assert sorted(cpp) == sorted(py)
+    for name in py:
+        np.testing.assert_allclose(cpp[name], py[name], rtol=1e-12, atol=1e-12 * np.abs(py[name]).max(), err_msg=name)
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_dump_outputs_samples_large_fields_and_stays_below_64mb(tmp_path):
+    b = _bench_module()
+    # C2's fields: 1024 x 32 x 32 x 60 doubles each, far above the budget -> one seeded sample, the same for every field
+    n, nf = 1024 * 32 * 32 * 60, 6
+    idx = b.dump_sample(n, nf)
+    assert idx is not None and np.array_equal(idx, b.dump_sample(n, nf)) and (np.diff(idx) > 0).all() and idx[-1] < n
+    assert nf * idx.size * 8 <= b.DUMP_BYTES < 64e6
+    assert b.dump_sample(1000, nf) is None                  # small outputs are written whole
+    m = 3 * b.DUMP_BYTES // 8 // nf                         # fields of three times the per-field share (one array, 31 MB)
+    base = np.arange(m, dtype=np.float64).reshape(-1, 8)
+    b.dump_outputs({"f%d" % k: base for k in range(nf)}, str(tmp_path / "d"))
+    files = sorted(os.listdir(tmp_path / "d"))
+    assert files == ["f%d.npy" % k for k in range(nf)]
+    assert sum(os.path.getsize(tmp_path / "d" / f) for f in files) < 64e6
+    sample = b.dump_sample(m, nf)
+    for k in range(nf):
+        a = np.load(tmp_path / "d" / ("f%d.npy" % k))
+        assert a.dtype == np.float64 and np.array_equal(a, sample.astype(np.float64))
+    b.dump_outputs({"g": np.ones((3, 4), dtype=np.float32)}, str(tmp_path / "e"))
+    g = np.load(tmp_path / "e" / "g.npy")
+    assert g.dtype == np.float64 and g.shape == (12,) and (g == 1).all()
+
+
+def test_bench_py_refuses_zero_steps():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+    assert _bench_module().parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
 
 
 def test_compact_line_of_a_large_detail_object_stays_below_the_limit():

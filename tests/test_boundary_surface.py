@@ -4,10 +4,13 @@ DataManager that PAM's own headers lack, and expose the reference `Dycore`'s sig
 YAKL is absent, so the headers cannot be compiled against the reference's pam_core here; instead
   * every `coupler.X(` / `dm.X(` member used by the host-side C++ sources is looked up in the member lists of
     pam_core/pam_coupler.h and pam_core/DataManager.h.  The lists below are DATA extracted from those headers (names
-    only); where the reference tree is mounted they are re-extracted live and must agree;
+    only); they must agree with the names `extract` read from the headers into tests/golden/reference_extract.json;
   * the same members must exist in the work-alike pam_amd/csrc/host/pam_coupler.h this repository compiles against;
-  * the Dycore member signatures are compared with the reference's own lines (live) and with their recorded form;
+  * the Dycore member signatures are compared with their recorded form and with digests of the reference's own lines
+    (the same fixture: SHA-256 of each line, whitespace removed, up to its opening brace);
   * INTEGRATION.md section 2 must be the shipped header, verbatim."""
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -17,7 +20,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-REF = "/root/reference"
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_extract.json")
 
 # member names of pam::PamCoupler (pam_core/pam_coupler.h) and pam::DataManager (pam_core/DataManager.h)
 REF_COUPLER = {"add_option", "add_tracer", "allocate_coupler_state", "delete_option", "finalize",
@@ -79,10 +82,9 @@ def test_workalike_declares_nothing_under_an_invented_name():
     assert names and names <= REF_DM, sorted(names - REF_DM)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 def test_recorded_member_lists_match_the_reference_headers():
-    pc = _declared(os.path.join(REF, "pam_core", "pam_coupler.h"))
-    dm = _declared(os.path.join(REF, "pam_core", "DataManager.h"))
+    rec = json.load(open(GOLDEN))["boundary_surface"]
+    pc, dm = set(rec["pam_coupler_h_names"]), set(rec["datamanager_h_names"])
     assert REF_COUPLER <= pc, sorted(REF_COUPLER - pc)
     assert REF_DM <= dm, sorted(REF_DM - dm)
     for invented in ("unregister", "deallocate_entry"):
@@ -115,6 +117,23 @@ def _norm(s):
     return re.sub(r"\s+", "", s).replace("pam::", "")
 
 
+def _digest(s):
+    return hashlib.sha256(s.encode()).hexdigest()
+
+
+def extract(ref):
+    """what the tests of this module record of the reference tree at `ref` (tests/golden/extract_reference.py stores it)"""
+    out = {"pam_coupler_h_names": sorted(_declared(os.path.join(ref, "pam_core", "pam_coupler.h"))),
+           "datamanager_h_names": sorted(_declared(os.path.join(ref, "pam_core", "DataManager.h"))), "signature_sha256": {}}
+    for which, sigs in (("awfl", AWFL_SIGNATURES), ("spam", SPAM_SIGNATURES)):
+        lines = open(os.path.join(ref, "dynamics", which, "Dycore.h")).read().split("\n")
+        rec = out["signature_sha256"][which] = {}
+        for ln in sorted(sigs.values()):
+            got = _norm(" ".join(lines[ln - 1:ln + 2]))      # a signature may wrap
+            rec[str(ln)] = _digest(got[:got.index("{")])
+    return out
+
+
 def test_awfl_amd_dycore_has_the_reference_signatures():
     text = _norm(_strip_comments(open(os.path.join(HOST, "dynamics", "awfl_amd", "Dycore.h")).read()))
     for sig in AWFL_SIGNATURES:
@@ -127,14 +146,13 @@ def test_spam_surface_dycore_has_spams_signatures():
         assert _norm(sig) + "{" in text, sig
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 @pytest.mark.parametrize("which", ["awfl", "spam"])
 def test_recorded_signatures_are_the_reference_lines(which):
     sigs = AWFL_SIGNATURES if which == "awfl" else SPAM_SIGNATURES
-    lines = open(os.path.join(REF, "dynamics", which, "Dycore.h")).read().split("\n")
+    rec = json.load(open(GOLDEN))["boundary_surface"]["signature_sha256"][which]
+    assert sorted(rec, key=int) == [str(ln) for ln in sorted(sigs.values())]
     for sig, ln in sigs.items():
-        got = _norm(" ".join(lines[ln - 1:ln + 2]))      # a signature may wrap
-        assert got.startswith(_norm(sig)), (sig, lines[ln - 1])
+        assert _digest(_norm(sig)) == rec[str(ln)], (sig, ln)
 
 
 def test_integration_md_lists_the_shipped_header():
