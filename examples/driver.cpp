@@ -42,6 +42,8 @@
 #include "modules/sponge_layer.h"
 #include "modules/broadcast_initial_gcm_column.h"
 #include "modules/perturb_temperature.h"
+#include "modules/saturation_adjustment.h"
+#include "modules/surface_friction.h"
 #include "physics/micro/kessler_amd/Microphysics.h"
 
 #include <map>
@@ -229,7 +231,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-//   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] <output.bin | ->
+//   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
 // out_freq, vcoords [, crm_nz, zlen, idealized, apply_sponge, initData].  What runs, in the reference's order:
@@ -295,7 +297,13 @@ static void initialize_from_supercell_column(std::vector<real> const &zint_in, p
 
 #ifndef PAMC_DYCORE
 struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };      // bisection switches (tools/repro_ci_run.py has the Python twin)
-static int run_yaml(const std::string &file, int nens_override, int steps_limit, bool check, const std::string &outfile, YamlDebug dbg = YamlDebug()) {
+// opt-in modules of the CRM step (off: the run is the one above, byte for byte):
+//   --sat-adjust               modules::saturation_adjustment after micro
+//   --surface-friction TAU BFLX  modules::surface_friction_init once (every member: tau = TAU, bflx = BFLX), then
+//                              modules::compute_surface_friction every CRM step after the sponge layer
+struct YamlModules { bool sat_adjust = false, surface_friction = false; double tau = 0, bflx = 0; };
+static int run_yaml(const std::string &file, int nens_override, int steps_limit, bool check, const std::string &outfile, YamlDebug dbg = YamlDebug(),
+                    YamlModules mods = YamlModules()) {
   auto kv = read_flat_yaml(file);
   auto has = [&](char const *k) { return kv.count(k) > 0; };
   auto num = [&](char const *k, double dflt, bool required = false) {
@@ -353,6 +361,15 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     if (!idealized) initialize_from_supercell_column(zint, coupler);        // driver.cpp:220-222
     if (check) dycore.set_debug_conservation(true);
     auto &dm = coupler.get_data_manager_device_readwrite();
+    double *sf_in = nullptr;                                                 // tau_in, bflx_in of surface_friction_init: (2, nens)
+    if (mods.surface_friction) {
+      std::vector<real> h((size_t)2 * nens);
+      for (int e = 0; e < nens; e++) { h[e] = mods.tau; h[nens + e] = mods.bflx; }
+      if (hipMalloc((void **)&sf_in, h.size() * sizeof(real)) != hipSuccess ||
+          hipMemcpy(sf_in, h.data(), h.size() * sizeof(real), hipMemcpyHostToDevice) != hipSuccess) endrun("hipMalloc");
+      realConst1d tau_in(sf_in, {nens}), bflx_in(sf_in + nens, {nens});
+      coupler.run_module("surface_friction_init", [&](pam::PamCoupler &c) { modules::surface_friction_init(c, tau_in, bflx_in); });
+    }
     const size_t ncell = (size_t)crm_nz * crm_ny * crm_nx * nens;
     std::vector<real> buf(ncell);
     auto fetch = [&](std::string const &name) {
@@ -374,8 +391,10 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         }
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         if (apply_sponge && !dbg.no_sponge) coupler.run_module("sponge_layer", modules::sponge_layer);         // driver.cpp:249-251
+        if (mods.surface_friction) coupler.run_module("surface_friction", modules::compute_surface_friction);
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         if (!dbg.no_micro) coupler.run_module("micro", [&](pam::PamCoupler &c) { micro.timeStep(c); });         // driver.cpp:253
+        if (mods.sat_adjust) coupler.run_module("saturation_adjustment", modules::saturation_adjustment);
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         crm_steps++;
         etime_gcm = step_gcm * dt_gcm + (step_crm_phys + 1) * dt_crm_phys;  // driver.cpp:255
@@ -395,7 +414,23 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       }
     }
     if (hipDeviceSynchronize() != hipSuccess) endrun("device error");
+    if (sf_in) (void)hipFree(sf_in);
     std::printf("Simulation Time: %g\n", etime_gcm);
+    if (mods.surface_friction) {                                             // the fluxes SHOC would read (not consumed here)
+      const size_t n2 = (size_t)crm_ny * crm_nx * nens;
+      std::vector<real> fu(n2), fv(n2), z0(nens);
+      if (hipMemcpy(fu.data(), dm.get<real const, 3>("sfc_mom_flx_u").data(), n2 * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess ||
+          hipMemcpy(fv.data(), dm.get<real const, 3>("sfc_mom_flx_v").data(), n2 * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess ||
+          hipMemcpy(z0.data(), dm.get<real const, 1>("z0").data(), nens * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess) endrun("memcpy");
+      double fmax = 0, z0min = INFINITY, z0max = -INFINITY;
+      bool ffin = true;
+      for (size_t c = 0; c < n2; c++) {
+        if (!std::isfinite(fu[c]) || !std::isfinite(fv[c])) ffin = false;
+        fmax = std::max(fmax, std::max(std::fabs(fu[c]), std::fabs(fv[c])));
+      }
+      for (real z : z0) { z0min = std::min(z0min, (double)z); z0max = std::max(z0max, (double)z); }
+      std::printf("surface friction: finite %s, max |sfc_mom_flx| %.9g, z0 [%.9g, %.9g]\n", ffin ? "true" : "false", fmax, z0min, z0max);
+    }
     // statistics of the final state + the output file (same layout as the binary mode: the fields, then precl)
     std::vector<std::string> names = {"density_dry", "uvel", "vvel", "wvel", "temp"};
     for (auto &n : coupler.get_tracer_names()) names.push_back(n);
@@ -446,6 +481,7 @@ int main(int argc, char **argv) {
     int nens_override = 0, steps_limit = 0, b = 3;
     bool check = false;
     YamlDebug dbg;
+    YamlModules mods;
     for (; b < argc - 1; b++) {
       const std::string o(argv[b]);
       if (o == "--nens" && b + 1 < argc - 1) nens_override = std::atoi(argv[++b]);
@@ -454,9 +490,15 @@ int main(int argc, char **argv) {
       else if (o == "--no-micro") dbg.no_micro = true;
       else if (o == "--no-sponge") dbg.no_sponge = true;
       else if (o == "--sync") dbg.sync = true;
-      else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] <output.bin | ->");
+      else if (o == "--sat-adjust") mods.sat_adjust = true;
+      else if (o == "--surface-friction" && b + 2 < argc - 1) {
+        mods.surface_friction = true;
+        mods.tau = std::atof(argv[++b]);
+        mods.bflx = std::atof(argv[++b]);
+      }
+      else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] <output.bin | ->");
     }
-    return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg);
+    return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }
 #endif
   Job J;

@@ -96,6 +96,38 @@ int pam_amd_supercell_init(int nz, const double *vert_interface, double R_d, dou
                            double *uvel_col, double *vvel_col, double *wvel_col, double *temp_col, double *rho_v_col,
                            void *stream);
 
+/* modules::saturation_adjustment(coupler)  (pam_core/modules/saturation_adjustment.h:116-147): instantaneous condensation of
+ * super-saturation / evaporation of cloud towards saturation, by bisection, in every cell.  DEVICE arrays (nz,ny,nx,nens):
+ *   rho_d       "density_dry" (in)
+ *   rho_v       "water_vapor", rho_c the cloud condensate ("cloud_liquid" for option micro = kessler, "cloud_water" for p3),
+ *               temp "temp": in/out; a cell in neither branch is not written
+ *   massy       host array of num_massy DEVICE pointers: every tracer that adds mass, in registration order (rho_v and rho_c
+ *               among them); rho = rho_d + their sum
+ *   R_v, cp_d, cp_v  the coupler's options; cp_l the reference's 4188
+ * The bisection stops after 2048 iterations where the reference's would not end (infinite or absurd densities). */
+int pam_amd_saturation_adjustment(int nens, int nx, int ny, int nz, const double *rho_d, double *rho_v, double *rho_c, double *temp,
+                                  int num_massy, const double *const *massy, double R_v, double cp_d, double cp_v, double cp_l,
+                                  void *stream);
+
+/* modules::surface_friction_init(coupler, tau_in, bflx_in)  (pam_core/modules/surface_friction.h:66-104).  DEVICE arrays:
+ *   rho_d, rho_v        "density_dry", "water_vapor" (nz,ny,nx,nens): level 0 gives the horizontal-mean surface density
+ *   zmid                "vertical_midpoint_height" (nz,nens); gcm_uvel, gcm_vvel "gcm_uvel", "gcm_vvel" (nz,nens)
+ *   tau_in, bflx_in     (nens): surface stress and buoyancy flux of the GCM
+ *   z0, sfc_bflx        (nens) out: momentum roughness height (clipped to [1e-5, 1] m) and a copy of bflx_in
+ *   sfc_mom_flx_u/v     (ny,nx,nens) out: zeroed */
+int pam_amd_surface_friction_init(int nens, int nx, int ny, int nz, const double *rho_d, const double *rho_v, const double *zmid,
+                                  const double *gcm_uvel, const double *gcm_vvel, const double *tau_in, const double *bflx_in,
+                                  double *z0, double *sfc_bflx, double *sfc_mom_flx_u, double *sfc_mom_flx_v, void *stream);
+
+/* modules::compute_surface_friction(coupler)  (surface_friction.h:107-167; every CRM step): the surface momentum flux SHOC reads,
+ * -(u - mean u) / max(1,|u|) * rho_mean ustar^2, in [m2/s2] (* rho_sfc / dz).  DEVICE arrays: rho_d, rho_v, uvel, vvel
+ * (nz,ny,nx,nens); zmid (nz,nens); zint "vertical_interface_height" (nz+1,nens); z0, sfc_bflx (nens) from the init;
+ * sfc_mom_flx_u/v (ny,nx,nens) out.  nz >= 3 (the surface density is extrapolated from levels 0-2).  The horizontal means are
+ * summed in a fixed order (the reference: atomicAdd) in the launch that writes the fluxes. */
+int pam_amd_surface_friction_compute(int nens, int nx, int ny, int nz, const double *rho_d, const double *rho_v, const double *uvel,
+                                     const double *vvel, const double *zmid, const double *zint, const double *z0,
+                                     const double *sfc_bflx, double *sfc_mom_flx_u, double *sfc_mom_flx_v, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,10 @@ MODULE_SYMBOLS = {
     "pam_amd_supercell_init": (C.c_int, [C.c_int, C.c_void_p] + [C.c_double] * 3 + [C.c_void_p] * 6 + [C.c_void_p]),
     "pam_amd_kessler_max_stable_dt": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_double, C.c_void_p, C.c_void_p,
                                                                                    C.POINTER(C.c_double)]),
+    "pam_amd_saturation_adjustment": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.POINTER(C.c_void_p)] + [C.c_double] * 4
+                                      + [C.c_void_p]),
+    "pam_amd_surface_friction_init": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 11 + [C.c_void_p]),
+    "pam_amd_surface_friction_compute": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 10 + [C.c_void_p]),
 }
 
 

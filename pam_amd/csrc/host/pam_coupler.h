@@ -44,6 +44,7 @@ class DeviceView {
 // pam_const.h:30-55: YAKL device arrays by rank; here every rank is the same non-owning view
 typedef pam::DeviceView<real> real5d;
 typedef pam::DeviceView<real const> realConst5d;
+typedef pam::DeviceView<real const> realConst1d;
 typedef pam::DeviceView<int> int1d;
 typedef pam::DeviceView<int const> intConst1d;
 namespace pam {

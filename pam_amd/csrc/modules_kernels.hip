@@ -1,5 +1,6 @@
 // modules_kernels.hip -- gfx950 kernels of the coupler modules around the dycore (include/pam_amd_modules.h).
 // sponge_layer: pam_core/modules/sponge_layer.h:8-95.  Both kernels are tiny and HBM-bound (top 5 of 60 levels).
+// saturation_adjustment, surface_friction_init / compute_surface_friction: at the end of the file.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -12,6 +13,7 @@
 #include "awfl_device.h"       // pow_pos_fast + its tables (the step's own x^y for positive bases)
 #include "awfl_vertical.h"     // build_pow_tab
 #include "supercell_sounding.h"
+#include "moist_surface_device.h"  // saturation adjustment, surface friction: per-cell bodies shared with the host emulation
 
 namespace {
 
@@ -872,6 +874,176 @@ extern "C" int pam_amd_supercell_init(int nz, const double *vert_interface, doub
     return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "supercell_init: cannot raise the LDS limit");
   hipLaunchKernelGGL(supercell_init_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, nz, vert_interface, R_d, R_v, grav,
                      rho_d_col, uvel_col, vvel_col, wvel_col, temp_col, rho_v_col);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, hipGetErrorString(err));
+  return PAM_AMD_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// modules::saturation_adjustment and modules::surface_friction_init / compute_surface_friction
+// (pam_core/modules/saturation_adjustment.h, surface_friction.h).  The per-cell arithmetic lives in moist_surface_device.h, which the
+// host emulation of the tests compiles too.
+namespace {
+using namespace pama::moist;
+struct MassyPtrs { const double *p[MAX_FIELDS]; };
+
+// saturation_adjustment.h:142-146: one thread per cell of the collapsed (nz,ny,nx,nens) arrays, nens fastest.  rho = rho_d + every
+// tracer that adds mass, in registration order (rho_v and rho_c among them, read before the update).  A cell in neither branch of the
+// adjustment is not written.
+__global__ void __launch_bounds__(256) saturation_adjustment_kernel(long long ncell, const double *__restrict__ rho_d, double *rho_v,
+                                                                    double *rho_c, double *temp, int num_massy, MassyPtrs M,
+                                                                    double R_v, double cp_d, double cp_v, double cp_l) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ncell) return;
+  const double rd = rho_d[i];
+  double rho = rd;
+  for (int tr = 0; tr < num_massy; tr++) rho += M.p[tr][i];
+  double rv = rho_v[i], rc = rho_c[i], t = temp[i];
+  if (compute_adjusted_state(rho, rd, rv, rc, t, R_v, cp_d, cp_v, cp_l) == 0) return;
+  rho_v[i] = rv;
+  rho_c[i] = rc;
+  temp[i] = t;
+}
+
+// surface_friction_init (surface_friction.h:66-104) in one launch: a workgroup = (block of up to 64 members) x MOD_NS slots sums
+// its members' level-0 density (rho_d + rho_v) * r_nx_ny in the fixed slot order of the other modules, zeroes their surface fluxes on
+// the way, and lane (member, slot 0) derives sfc_bflx and z0.  The mean starts from zero (the reference's atomicAdd target is never set).
+__global__ void __launch_bounds__(64 * MOD_NS) surface_friction_init_kernel(int nens, int ncol, const double *__restrict__ rho_d,
+                                                                           const double *__restrict__ rho_v, const double *__restrict__ zmid,
+                                                                           const double *__restrict__ gcm_u, const double *__restrict__ gcm_v,
+                                                                           const double *__restrict__ tau, const double *__restrict__ bflx,
+                                                                           double *__restrict__ z0, double *__restrict__ sfc_bflx,
+                                                                           double *__restrict__ flx_u, double *__restrict__ flx_v) {
+  PAMA_NO_CONTRACT      // every product is rounded before it is added, as in the reference's atomicAdd
+  __shared__ double red[MOD_NS * 64];
+  const int ME = blockDim.x, slot = threadIdx.y;
+  const int e0 = (int)blockIdx.x * ME + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1;
+  const double r_nx_ny = 1.0 / ncol;
+  double h[1] = {0.0};
+  for (int c = slot; c < ncol; c += MOD_NS) {
+    const long long o = (long long)c * nens + e;
+    h[0] += (rho_d[o] + rho_v[o]) * r_nx_ny;
+    if (ok) { flx_u[o] = 0; flx_v[o] = 0; }
+  }
+  slot_reduce<1>(h, red);
+  if (!ok || slot != 0) return;
+  const double b = bflx[e];
+  sfc_bflx[e] = b;
+  z0[e] = surface_friction_z0(zmid[e], b, gcm_u[(long long)e], gcm_v[(long long)e], tau[e], h[0]);
+}
+
+// compute_surface_friction (surface_friction.h:107-167) in one launch: grid (member blocks, column chunks).  Every workgroup sums its
+// members' level-0 means of u, v and rho_d + rho_v over ALL columns -- the fixed-order slot sums of sponge_layer and gcm_forcing, so
+// every chunk holds the same bits -- and then writes the columns of its chunk (levels 1-2 of the densities for the surface
+// extrapolation).  No scratch, no atomics.  The chunks exist for the per-column work (diag_ustar: ~2400 VALU instructions per column
+// with a buoyancy flux): one workgroup per member block alone would leave most of the chip idle; the repeated level-0 reads of the
+// chunks come out of the caches.
+__global__ void __launch_bounds__(64 * MOD_NS) surface_friction_kernel(int nens, int ncol, const double *__restrict__ rho_d,
+                                                                      const double *__restrict__ rho_v, const double *__restrict__ uvel,
+                                                                      const double *__restrict__ vvel, const double *__restrict__ zmid,
+                                                                      const double *__restrict__ zint, const double *__restrict__ z0,
+                                                                      const double *__restrict__ sfc_bflx, double *__restrict__ flx_u,
+                                                                      double *__restrict__ flx_v) {
+  PAMA_NO_CONTRACT
+  __shared__ double red[3 * MOD_NS * 64];
+  const int ME = blockDim.x, slot = threadIdx.y;
+  const int e0 = (int)blockIdx.x * ME + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1;
+  const double r_nx_ny = 1.0 / ncol;
+  double h[3] = {0.0, 0.0, 0.0};
+  for (int c = slot; c < ncol; c += MOD_NS) {
+    const long long o = (long long)c * nens + e;
+    h[0] += uvel[o] * r_nx_ny;
+    h[1] += vvel[o] * r_nx_ny;
+    h[2] += (rho_d[o] + rho_v[o]) * r_nx_ny;
+  }
+  slot_reduce<3>(h, red);
+  if (!ok) return;
+  const double zm0 = zmid[e], b = sfc_bflx[e], z0e = z0[e];
+  const double dz = zint[(long long)nens + e] - zint[e];
+  const long long lev = (long long)ncol * nens;
+  const int chunk = (ncol + (int)gridDim.y - 1) / (int)gridDim.y, c1 = min(ncol, ((int)blockIdx.y + 1) * chunk);
+  for (int c = (int)blockIdx.y * chunk + slot; c < c1; c += MOD_NS) {
+    const long long o = (long long)c * nens + e;
+    const double r0 = rho_d[o] + rho_v[o], r1 = rho_d[o + lev] + rho_v[o + lev], r2 = rho_d[o + 2 * lev] + rho_v[o + 2 * lev];
+    double fu, fv;
+    surface_friction_cell(uvel[o], vvel[o], h[0], h[1], h[2], zm0, b, z0e, r0, r1, r2, dz, fu, fv);
+    flx_u[o] = fu;
+    flx_v[o] = fv;
+  }
+}
+
+int moist_surface_device_check(const char *who) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": no HIP device available (this library has no CPU path)").c_str());
+  return PAM_AMD_OK;
+}
+}  // namespace
+
+extern "C" int pam_amd_saturation_adjustment(int nens, int nx, int ny, int nz, const double *rho_d, double *rho_v, double *rho_c,
+                                             double *temp, int num_massy, const double *const *massy, double R_v, double cp_d,
+                                             double cp_v, double cp_l, void *stream) {
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1 || !rho_d || !rho_v || !rho_c || !temp || (num_massy > 0 && !massy))
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "saturation_adjustment: bad dimensions or null pointer");
+  if (num_massy < 0 || num_massy > MAX_FIELDS)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "saturation_adjustment: num_massy must be in [0, 55]");
+  if (!(R_v > 0) || !(cp_d > 0) || !(cp_v > 0) || !(cp_l > 0))
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "saturation_adjustment: R_v, cp_d, cp_v and cp_l must be positive");
+  MassyPtrs M;
+  for (int i = 0; i < MAX_FIELDS; i++) M.p[i] = nullptr;
+  for (int i = 0; i < num_massy; i++) {
+    if (!massy[i]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "saturation_adjustment: null tracer pointer");
+    M.p[i] = massy[i];
+  }
+  if (int rc = moist_surface_device_check("saturation_adjustment")) return rc;
+  const long long ncell = (long long)nz * ny * nx * nens;
+  hipLaunchKernelGGL(saturation_adjustment_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ncell, rho_d,
+                     rho_v, rho_c, temp, num_massy, M, R_v, cp_d, cp_v, cp_l);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, hipGetErrorString(err));
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_surface_friction_init(int nens, int nx, int ny, int nz, const double *rho_d, const double *rho_v,
+                                             const double *zmid, const double *gcm_uvel, const double *gcm_vvel, const double *tau_in,
+                                             const double *bflx_in, double *z0, double *sfc_bflx, double *sfc_mom_flx_u,
+                                             double *sfc_mom_flx_v, void *stream) {
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1 || !rho_d || !rho_v || !zmid || !gcm_uvel || !gcm_vvel || !tau_in || !bflx_in || !z0 ||
+      !sfc_bflx || !sfc_mom_flx_u || !sfc_mom_flx_v)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "surface_friction_init: bad dimensions or null pointer");
+  if (int rc = moist_surface_device_check("surface_friction_init")) return rc;
+  const int ME = nens < 64 ? nens : 64;
+  hipLaunchKernelGGL(surface_friction_init_kernel, dim3((unsigned)((nens + ME - 1) / ME)), dim3((unsigned)ME, (unsigned)MOD_NS), 0,
+                     (hipStream_t)stream, nens, nx * ny, rho_d, rho_v, zmid, gcm_uvel, gcm_vvel, tau_in, bflx_in, z0, sfc_bflx,
+                     sfc_mom_flx_u, sfc_mom_flx_v);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, hipGetErrorString(err));
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_surface_friction_compute(int nens, int nx, int ny, int nz, const double *rho_d, const double *rho_v,
+                                                const double *uvel, const double *vvel, const double *zmid, const double *zint,
+                                                const double *z0, const double *sfc_bflx, double *sfc_mom_flx_u,
+                                                double *sfc_mom_flx_v, void *stream) {
+  if (nens < 1 || nx < 1 || ny < 1 || !rho_d || !rho_v || !uvel || !vvel || !zmid || !zint || !z0 || !sfc_bflx || !sfc_mom_flx_u ||
+      !sfc_mom_flx_v)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "compute_surface_friction: bad dimensions or null pointer");
+  if (nz < 3)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "compute_surface_friction: nz >= 3 required (the surface density is extrapolated from levels 0-2)");
+  if (int rc = moist_surface_device_check("compute_surface_friction")) return rc;
+  const int ME = nens < 64 ? nens : 64, nblk = (nens + ME - 1) / ME, ncol = nx * ny;
+  // column chunks: ~512 workgroups in all (two per CU), each chunk at least 64 columns (four per slot)
+  int nchunk = (512 + nblk - 1) / nblk;
+  if (nchunk > (ncol + 63) / 64) nchunk = (ncol + 63) / 64;
+  if (nchunk < 1) nchunk = 1;
+  hipLaunchKernelGGL(surface_friction_kernel, dim3((unsigned)nblk, (unsigned)nchunk), dim3((unsigned)ME, (unsigned)MOD_NS), 0,
+                     (hipStream_t)stream, nens, nx * ny, rho_d, rho_v, uvel, vvel, zmid, zint, z0, sfc_bflx, sfc_mom_flx_u,
+                     sfc_mom_flx_v);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, hipGetErrorString(err));
   return PAM_AMD_OK;

@@ -135,3 +135,70 @@ def supercell_init(vert_interface, R_d, R_v, grav):
         check(lib.pam_amd_supercell_init(nz, z.data_ptr(), float(R_d), float(R_v), float(grav), *[c.data_ptr() for c in cols],
                                          torch.cuda.current_stream(z.device).cuda_stream))
     return tuple(cols)
+
+
+SATURATION_CONDENSATE = {"kessler": "cloud_liquid", "p3": "cloud_water"}     # saturation_adjustment.h:126-129
+
+
+def saturation_adjustment(coupler):
+    """modules::saturation_adjustment(coupler)  (pam_core/modules/saturation_adjustment.h:116-147): condenses super-saturation,
+    evaporates cloud towards saturation.  Options "micro" (kessler | p3), "R_v", "cp_d", "cp_v"; cp_l = 4188."""
+    from .coupler import endrun
+    lib = capi.load()
+    nz, ny, nx, nens = coupler.get_nz(), coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+    dm = coupler.get_data_manager_device_readwrite()
+    rho_d, temp, rho_v = dm.get("density_dry"), dm.get("temp"), dm.get("water_vapor")
+    micro = coupler.get_option("micro")
+    if micro not in SATURATION_CONDENSATE:
+        endrun("ERROR: saturation_adjustment.h only currently supports kessler and p3 microphysics")
+    rho_c = dm.get(SATURATION_CONDENSATE[micro])
+    massy = [dm.get(n) for n in coupler.get_tracer_names() if coupler.get_tracer_info(n)[3]]    # :130-137, registration order
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_saturation_adjustment(nens, nx, ny, nz, rho_d.data_ptr(), rho_v.data_ptr(), rho_c.data_ptr(), temp.data_ptr(),
+                                                len(massy), _ptr_table(massy), float(coupler.get_option("R_v")),
+                                                float(coupler.get_option("cp_d")), float(coupler.get_option("cp_v")), 4188.0,
+                                                torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+def _member_array(coupler, x, what):
+    from .coupler import endrun
+    nens = coupler.get_nens()
+    t = torch.as_tensor(x, dtype=torch.float64, device=coupler.device).contiguous()
+    if t.dim() != 1 or t.numel() != nens:
+        endrun("ERROR: surface_friction_init: %s needs nens values" % what)
+    return t
+
+
+def surface_friction_init(coupler, tau, bflx):
+    """modules::surface_friction_init(coupler, tau_in, bflx_in)  (pam_core/modules/surface_friction.h:66-104); tau, bflx: one value
+    per member.  Registers "z0" and "sfc_bflx" (nens) as the reference does, and "sfc_mom_flx_u/v" (ny,nx,nens) when no SGS scheme
+    has (SHOC registers them in PAM, SGS.h:119-120)."""
+    lib = capi.load()
+    nz, ny, nx, nens = coupler.get_nz(), coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+    tau, bflx = _member_array(coupler, tau, "tau"), _member_array(coupler, bflx, "bflx")
+    dm = coupler.get_data_manager_device_readwrite()
+    dm.register_and_allocate("z0", "Momentum roughness height [m]", (nens,), ("nens",))
+    dm.register_and_allocate("sfc_bflx", "large-scale sfc buoyancy flux [K m/s]", (nens,), ("nens",))
+    for n in ("sfc_mom_flx_u", "sfc_mom_flx_v"):
+        if not dm.entry_exists(n):
+            dm.register_and_allocate(n, "surface momentum flux", (ny, nx, nens), ("y", "x", "nens"))
+    args = [dm.get(n) for n in ("density_dry", "water_vapor", "vertical_midpoint_height", "gcm_uvel", "gcm_vvel")]
+    args += [tau, bflx] + [dm.get(n) for n in ("z0", "sfc_bflx", "sfc_mom_flx_u", "sfc_mom_flx_v")]
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_surface_friction_init(nens, nx, ny, nz, *[a.data_ptr() for a in args],
+                                                torch.cuda.current_stream(coupler.device).cuda_stream))
+    return tau, bflx   # keep the inputs alive until the caller drops them (the launch is asynchronous)
+
+
+def compute_surface_friction(coupler):
+    """modules::compute_surface_friction(coupler)  (pam_core/modules/surface_friction.h:107-167): "sfc_mom_flx_u/v" from the
+    level-0 winds, the roughness height and buoyancy flux of the init, in [m2/s2]."""
+    lib = capi.load()
+    nz, ny, nx, nens = coupler.get_nz(), coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+    dm = coupler.get_data_manager_device_readwrite()
+    args = [dm.get(n, readonly=True) for n in ("density_dry", "water_vapor", "uvel", "vvel", "vertical_midpoint_height",
+                                                 "vertical_interface_height")]
+    args += [dm.get(n) for n in ("z0", "sfc_bflx", "sfc_mom_flx_u", "sfc_mom_flx_v")]
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_surface_friction_compute(nens, nx, ny, nz, *[a.data_ptr() for a in args],
+                                                   torch.cuda.current_stream(coupler.device).cuda_stream))

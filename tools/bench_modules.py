@@ -1,4 +1,5 @@
-"""The coupler-module timings of bench.py alone (Kessler, sponge layer, GCM forcing at the C2 grid): one JSON object on stdout.
+"""The coupler-module timings of bench.py alone (Kessler, sponge layer, GCM forcing at the C2 grid), then saturation_adjustment and
+surface_friction_init / compute_surface_friction at the same grid: one JSON object on stdout.
 Run on the GPU box:  python tools/bench_modules.py"""
 import json
 import os
@@ -9,7 +10,109 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 
+# FP64 issue: 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz lane-instructions per second (bench.FP64_VALU_PEAK_TFLOPS counts an FMA as 2)
+LANE_ISSUE_PER_S = bench.FP64_VALU_PEAK_TFLOPS * 1e12 / 2
+SATADJ_VALU_PER_ITER = 117      # VALU instructions of one bisection iteration (gfx950 ISA: 103 FP64 -- five divisions, one exp)
+SFC_VALU_PER_COLUMN = 113 + 8 * 288   # compute_surface_friction per column with a buoyancy flux: 8 diag_ustar iterations, both branches
+
+
+def _events(fn, restore=None, n=5):
+    """ms of each of n calls, each on a fresh copy of the state when `restore` is given (the adjustment changes what the next call does)"""
+    ts = []
+    if restore is None:
+        fn()                            # warm-up
+    for _ in range(n):
+        if restore is not None:
+            restore()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return sorted(ts)[len(ts) // 2]
+
+
+def _satadj_work(dm, rho_c_name, R_v):
+    """cells that iterate and the wave-level iteration count of the launch: a bracket of width w halves to tol = 1e-6 in
+    max(1, ceil(log2(w / tol))) iterations, and a wavefront (64 consecutive cells) runs as long as its slowest lane"""
+    rv, rc, t = dm.get("water_vapor", readonly=True), dm.get(rho_c_name, readonly=True), dm.get("temp", readonly=True)
+    tc = t - 273.15
+    svp = 610.94 * torch.exp(17.625 * tc / (243.04 + tc))
+    pv = rv * R_v * t
+    cond, evap = pv > svp, (pv < svp) & (rc > 0)
+    width = torch.where(cond, rv, torch.where(evap, rc, torch.zeros_like(rv))).flatten()
+    it = torch.where(width > 0, torch.clamp(torch.ceil(torch.log2(width / 1e-6)), min=1), torch.zeros_like(width))
+    n = it.numel()
+    pad = torch.zeros((-n) % 64, dtype=it.dtype, device=it.device)
+    wave = torch.cat([it, pad]).view(-1, 64).amax(dim=1)
+    return int((cond | evap).sum()), float(it.sum()), float(wave.sum() * 64)
+
+
+def moist_surface_timing(dev):
+    from pam_amd import PamCoupler, Microphysics, modules, idealized as idz
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    cells, ncol = nens * nx * ny * nz, nens * nx * ny
+    zint = idz.l60_interfaces()
+    f = idz.supercell_fields(16, nx, ny, nz, zint, tracers=(("water_vapor", True, True),), magnitude=0.5)
+    c = PamCoupler(dev)
+    c.set_option("crm_dt", 2.0)
+    c.allocate_coupler_state(nz, ny, nx, nens)
+    c.set_grid(nx * 1000.0, ny * 1000.0, zint)
+    micro = Microphysics()
+    micro.init(c)          # Kessler: water_vapor, cloud_liquid, precip_liquid (all add mass); options micro, R_v, cp_d, cp_v
+    dm = c.get_data_manager_device_readwrite()
+    for k in ("density_dry", "uvel", "vvel", "wvel", "temp"):
+        dm.get(k).copy_(torch.from_numpy(f[k]).to(dev).repeat(1, 1, 1, nens // 16))
+    rv0 = torch.from_numpy(f["tracers"][0]).to(dev).repeat(1, 1, 1, nens // 16)
+    out = {"grid": "1024 x 32x32x60 (C2)", "unit": "ms per call (median of 5)", "hbm_peak_GBps": bench.HBM_PEAK_GBS,
+           "fp64_issue_peak_lane_instr_per_s": LANE_ISSUE_PER_S}
+    R_v = c.get_option("R_v")
+    # two states: the supercell sounding's vapour x 1.05 without cloud (no cell reaches saturation: the 5-read floor of the launch), and
+    # every cell 30 % super-saturated with a little cloud (every cell iterates)
+    for label, scale, cloud in (("saturation_adjustment_unsaturated", 1.05, 0.0), ("saturation_adjustment_all_cells", 1.3, 1e-4)):
+        saved = {"water_vapor": rv0 * scale, "cloud_liquid": dm.get("density_dry") * cloud, "temp": dm.get("temp").clone()}
+
+        def restore():
+            for k, v in saved.items():
+                dm.get(k).copy_(v)
+        restore()
+        n_iter_cells, lane_iters, wave_iters = _satadj_work(dm, "cloud_liquid", R_v)
+        t = _events(lambda: modules.saturation_adjustment(c), restore)
+        # every cell: rho_d, the three tracers that add mass (rho_v and rho_c among them) and T read; rho_v, rho_c, T written where it
+        # iterates
+        nbytes = cells * 5 * 8.0 + n_iter_cells * 3 * 8.0
+        issue_s = wave_iters * SATADJ_VALU_PER_ITER / LANE_ISSUE_PER_S
+        out[label] = {"ms": t, "bytes": nbytes, "GBps": nbytes / t / 1e6, "hbm_frac": nbytes / t / 1e6 / bench.HBM_PEAK_GBS,
+                      "cells_iterating": n_iter_cells, "cell_fraction": n_iter_cells / cells,
+                      "iterations_per_iterating_cell": lane_iters / max(n_iter_cells, 1),
+                      "fp64_issue_floor_ms": issue_s * 1e3, "fp64_issue_frac": issue_s * 1e3 / t}
+        del saved
+    dm.get("water_vapor").copy_(rv0)
+    tau = torch.full((nens,), 0.1, dtype=torch.float64, device=dev)
+    bflx = torch.full((nens,), 0.01, dtype=torch.float64, device=dev)
+    dm.get("gcm_uvel").copy_(dm.get("uvel").mean(dim=(1, 2)))
+    dm.get("gcm_vvel").copy_(dm.get("vvel").mean(dim=(1, 2)))
+    modules.surface_friction_init(c, tau, bflx)
+    t = _events(lambda: (dm.unregister_and_deallocate("z0"), dm.unregister_and_deallocate("sfc_bflx"),
+                         modules.surface_friction_init(c, tau, bflx)))
+    nbytes = ncol * 4 * 8.0             # level 0 of rho_d, rho_v read; both fluxes zeroed
+    out["surface_friction_init"] = {"ms": t, "bytes": nbytes, "GBps": nbytes / t / 1e6, "hbm_frac": nbytes / t / 1e6 / bench.HBM_PEAK_GBS,
+                                    "note": "includes the host-side re-registration of z0 / sfc_bflx (the init registers them)"}
+    t = _events(lambda: modules.compute_surface_friction(c))
+    nbytes = ncol * 10 * 8.0            # levels 0-2 of rho_d, rho_v and level 0 of u, v read; both fluxes written
+    issue_s = ncol * SFC_VALU_PER_COLUMN / LANE_ISSUE_PER_S
+    out["compute_surface_friction"] = {"ms": t, "bytes": nbytes, "GBps": nbytes / t / 1e6,
+                                       "hbm_frac": nbytes / t / 1e6 / bench.HBM_PEAK_GBS, "fp64_issue_floor_ms": issue_s * 1e3,
+                                       "fp64_issue_frac": issue_s * 1e3 / t, "bflx": 0.01}
+    del micro, dm, c
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
     out = bench.modules_timing(torch, dev)
+    out.update(moist_surface_timing(dev))
     print(json.dumps({k: ({kk: vv for kk, vv in v.items() if kk != "note"} if isinstance(v, dict) else v) for k, v in out.items()}))
