@@ -10,12 +10,12 @@
  * (E3SM-Project/PAM @ 2025-03-03).  Each function cites the reference lines it follows.
  * Build with -ffp-contract=off so that no FMA contraction changes the rounding.
  *
- * PINNING STATUS: "parity unpinned" by reference-owned fixtures -- the reference holds no golden
- * vector or numeric assertion for this path and cannot be built here (YAKL, its
- * array/launch library, is an absent un-vendored submodule; stand-in builds are not made).  The oracle
- * is checked instead against the reference-arithmetic probe values recorded in SURVEY.md Appendix B
- * (tests/test_oracle_kat.py) and against analytic properties (hydrostatic balance, conservation,
- * WENO order, uniform-grid identity of the variable matrices).
+ * PINNING STATUS: pinned to the reference's own source text for the dycore path and the modules.  The reference holds
+ * no golden vector for it and its array/launch library YAKL is an absent submodule,
+ * so `make -C oracle` compiles the reference headers serially against the project's YAKL stand-in
+ * (oracle/ref/) into oracle/_ref/libpam_ref.so; tests/test_reference_pin.py requires this file to
+ * reproduce it bit for bit (live, and through the committed fixtures tests/golden/ref_*.npz).  Unpinned:
+ * YAKL's own semantics (matinv_ge, D3; device atomicAdd order; minval).
  *
  * Deliberate deviations from the reference (documented in DESIGN.md):
  *   D1 vertical-ghost kernel: the reference reads the potential-temperature ghost of

@@ -1,0 +1,320 @@
+#!/usr/bin/env python3
+"""Generate the REFERENCE-COMPUTED fixtures tests/golden/ref_*.npz and their provenance tests/golden/ref_provenance.json.
+
+Unlike case_*.npz (outputs of our own oracle, make_golden.py), these are outputs of the reference's own source text: the AWFL
+Dycore, PamCoupler and DataManager headers compiled serially with g++ at IEEE fp64 (-O2 -ffp-contract=off) against the project's
+YAKL stand-in (oracle/ref/, built by `make -C oracle` into oracle/_ref/libpam_ref.so, loaded by oracle/pam_ref.py).  Stand-in
+settings: new allocations filled with NaN, and the D1 replay of the vertical boundary kernel.
+
+Each fixture holds the inputs (the same deterministic generator as make_golden.py), the hydrostatic outputs of
+declare_current_profile_as_hydrostatic, the vertical reconstruction matrices of init, compute_time_step on the inputs, and the
+coupler fields after every Dycore::timeStep with its sub-cycle count and length.  ref_mod_*.npz hold the inputs and outputs of the
+coupler modules (MODULE_CASES) run by the reference on the module tests' own inputs.  The provenance file records, as data only, the
+SHA-256 of every reference header the harness compiled, of the stand-in and harness, and the compiler version.  No source text.
+
+Usage:  python tests/golden/make_ref_golden.py            (needs the reference tree: PAM_REF, see oracle/Makefile)
+        python tests/golden/make_ref_golden.py --check    (regenerates and compares bit for bit; exit status 1 on a difference)
+"""
+import hashlib
+import importlib.util
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))      # tests/: the module tests' own case builders
+
+from oracle import pam_ref      # noqa: E402
+from pam_amd import idealized as idz   # noqa: E402
+
+_spec = importlib.util.spec_from_file_location("make_golden", os.path.join(HERE, "make_golden.py"))
+mg = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(mg)
+
+# the three oracle cases of make_golden.py, and a per-member grid in balance mode B
+CASES = dict(mg.CASES)
+CASES["case_3d_nt4_perens_B"] = dict(nens=3, nx=5, ny=4, nz=9, tr="kessler_shoc", grid=("stretched", 14000.0), mode_a=False,
+                                     nsteps=2, crm_dt=3.0, consts="p3", per_ens=True)
+PROVENANCE = os.path.join(HERE, "ref_provenance.json")
+STANDIN_FILES = ("oracle/ref/YAKL.h", "oracle/ref/YAKL_netcdf.h", "oracle/ref/YAKL_tridiagonal.h", "oracle/ref/ref_harness.cpp")
+
+
+def fixture_path(name):
+    return os.path.join(HERE, "ref_" + name[len("case_"):] + ".npz")
+
+
+def run_reference(c):
+    """The reference on the inputs of case `c`: a dict of arrays (the fixture's content)."""
+    tr, consts, zi, xlen, ylen, f = mg.build_case(c)
+    names, pos, mass, idwv = idz.tracer_flags(tr)
+    r = pam_ref.RefDycore(c["nens"], c["nx"], c["ny"], c["nz"], xlen, ylen, np.diff(zi, axis=0), pos, mass, idwv, consts=consts,
+                          names=names)
+    r.set_grav_balance(c["mode_a"])
+    out = {"in_" + k: v.copy() for k, v in f.items()}
+    out["dt_cfl"] = np.array(r.compute_time_step(f))
+    r.declare_current_profile_as_hydrostatic(f)
+    if c["mode_a"]:
+        out["variable_gravity"] = r.variable_gravity
+    else:
+        out["hy_dens_cells"] = r.hy_dens_cells
+        out["hy_pressure_cells"] = r.hy_pressure_cells
+    out["vert_sten_to_coefs"] = r.vert_sten_to_coefs
+    out["vert_weno_recon_lower"] = r.vert_weno_recon_lower
+    ncyc, dts = [], []
+    pam_ref.reset_replay_count()
+    for _ in range(c["nsteps"]):
+        n, dt = r.time_step(f, c["crm_dt"])
+        ncyc.append(n)
+        dts.append(dt)
+    out["ncycles"] = np.array(ncyc)
+    out["dt_dyn"] = np.array(dts)
+    out["replays"] = np.array(pam_ref.replay_count())
+    out.update({"out_" + k: v for k, v in f.items()})
+    return out
+
+
+# ---- coupler modules ----------------------------------------------------------------------------------------------------
+# Each module case: `inputs(**kw)` -> dict of input arrays (and scalars), `run_module_reference(name, kw, inp)` -> outputs.
+FIELD5 = ("density_dry", "uvel", "vvel", "wvel", "temp")
+GCM_KW = {"plain": {}, "starve_level": {"starve_level": True}, "starve_liquid": {"starve_liquid": True}}
+MODULE_CASES = {
+    "sponge": ("sponge", dict(nens=3, nx=5, ny=4, nz=12)),
+    **{"gcm_" + k: ("gcm", dict(nens=3, nx=5, ny=2, nz=8, **v)) for k, v in GCM_KW.items()},
+    "broadcast": ("broadcast", dict(nens=3, nx=4, ny=2, nz=6)),
+    "satadj_kessler": ("satadj", dict(micro="kessler", nens=3, nx=3, ny=2, nz=5)),
+    "satadj_p3": ("satadj", dict(micro="p3", nens=3, nx=3, ny=2, nz=5)),
+    "friction": ("friction", dict(nens=3, nx=3, ny=2, nz=5)),
+    "kessler_one_cycle": ("kessler", dict(nens=3, nx=6, ny=2, nz=30, heavy_rain=False, dt=5.0)),
+    "kessler_subcycled": ("kessler", dict(nens=3, nx=6, ny=2, nz=30, heavy_rain=True, dt=60.0)),
+    "supercell_L60": ("supercell", {}),
+}
+SATADJ_CONSTS = {"R_v": 461.0, "cp_d": 1003.0, "cp_v": 1859.0}      # the Kessler scheme's constants (pam_amd/micro.py)
+GCM_DT, GCM_CRM_DT, GCM_APPLICATIONS = 1200.0, 300.0, 4
+
+
+def module_fixture_path(name):
+    return os.path.join(HERE, "ref_mod_" + name + ".npz")
+
+
+def module_inputs(kind, kw):
+    """the inputs of a module case, built by the module tests' own generators (deterministic)"""
+    if kind == "sponge":
+        import test_modules as tm
+        zint, zi, zm, f = tm._case(kw["nens"], kw["nx"], kw["ny"], kw["nz"])
+        return dict({k: f[k] for k in FIELD5}, tracers=f["tracers"], zint=zi)
+    if kind == "gcm":
+        import test_modules as tm
+        extra = {k: v for k, v in kw.items() if k.startswith("starve")}
+        crm, gcm, dz = tm._gcm_case(kw["nens"], kw["nx"], kw["ny"], kw["nz"], **extra)
+        zint = np.concatenate([np.zeros((1, kw["nens"])), np.cumsum(dz, axis=0)], axis=0)
+        return dict(crm, **gcm, zint=zint)
+    if kind == "broadcast":
+        rng = np.random.default_rng(5)
+        nz, nens = kw["nz"], kw["nens"]
+        from oracle import awfl_oracle as ao
+        inp = {n: rng.uniform(0.5, 1.5, (nz, nens)) for n in ao.BROADCAST_GCM}
+        inp["zint"] = idz.uniform_interfaces(nz, 6000.0)[:, None] * np.ones((1, nens))
+        return inp
+    if kind == "satadj":
+        import test_moist_surface_modules as tms
+        f = tms.moist_state(tms.TRACER_SETS[kw["micro"]], kw["nens"], kw["nx"], kw["ny"], kw["nz"], seed=3)
+        return dict(f, zint=idz.stretched_interfaces(kw["nz"], 12000.0)[:, None] * np.ones((1, kw["nens"])))
+    if kind == "friction":
+        import test_moist_surface_modules as tms
+        tr, f, tau, bflx, zi = tms._friction_state(kw["nens"], kw["nx"], kw["ny"], kw["nz"], seed=4)
+        return dict(f, tau=tau, bflx=bflx, zint=zi)
+    if kind == "kessler":
+        import test_micro_kessler as tk
+        zint, zi, zm, st = tk._case(kw["nens"], kw["nx"], kw["ny"], kw["nz"], heavy_rain=kw["heavy_rain"])
+        return dict(st, zint=zi)
+    if kind == "supercell":
+        return {"zint": np.asarray(idz.l60_interfaces(), dtype=np.float64)}
+    raise ValueError(kind)
+
+
+def _ref_coupler(inp, shape, tracers):
+    nz, ny, nx, nens = shape
+    return pam_ref.RefCoupler(nz, ny, nx, nens, nx * 500.0, ny * 500.0, inp["zint"], tracers)
+
+
+def run_module_reference(kind, kw, inp):
+    """the reference module on the inputs `inp`: dict of output arrays"""
+    from oracle import awfl_oracle as ao
+    if kind == "supercell":
+        return dict(zip(("rho_d", "uvel", "vvel", "wvel", "temp", "rho_v"), pam_ref.supercell_init(inp["zint"], idz.CONSTS_DEFAULT)))
+    if kind == "kessler":
+        shape = inp["temp"].shape
+        c = _ref_coupler(inp, shape, ())
+        c.run("kessler_init")
+        c.set_option("crm_dt", kw["dt"])
+        names = (("water_vapor", "rho_v"), ("cloud_liquid", "rho_c"), ("precip_liquid", "rho_r"), ("density_dry", "rho_dry"),
+                 ("temp", "temp"))
+        for name, key in names:
+            c.write(name, inp[key])
+        c.run("kessler_timeStep")
+        out = {key: c.read(name, shape) for name, key in names if key != "rho_dry"}
+        out["precl"] = c.read("precl", shape[1:])
+        return out
+    if kind == "broadcast":
+        nz, nens = inp["gcm_density_dry"].shape
+        shape = (nz, kw["ny"], kw["nx"], nens)
+        c = _ref_coupler(inp, shape, idz.TRACERS_NONE)
+        for n in ao.BROADCAST_GCM:
+            c.write(n, inp[n])
+        c.run("broadcast_initial_gcm_column_dry_density")
+        out = {"dry_" + n: c.read(n, shape) for n in ("density_dry",)}
+        c.run("broadcast_initial_gcm_column")
+        out.update({n: c.read(n, shape) for n in ao.BROADCAST_CRM})
+        return out
+    shape = inp["density_dry"].shape
+    if kind == "sponge":
+        tr = idz.TRACERS_KESSLER_SHOC
+        c = _ref_coupler(inp, shape, tr)
+        c.set_option("crm_dt", 2.0)
+        c.set_option("sponge_num_layers", 4)
+        c.set_option("sponge_time_scale", 30.0)
+        for k in FIELD5:
+            c.write(k, inp[k])
+        for t, (n, _, _) in enumerate(tr):
+            c.write(n, inp["tracers"][t])
+        c.run("sponge_layer")
+        out = {k: c.read(k, shape) for k in FIELD5}
+        out["tracers"] = np.stack([c.read(n, shape) for n, _, _ in tr])
+        return out
+    if kind == "gcm":
+        c = _ref_coupler(inp, shape, idz.TRACERS_P3_SHOC)
+        c.set_option("crm_dt", GCM_CRM_DT)
+        c.set_option("gcm_physics_dt", GCM_DT)
+        for k in ("cp_d", "grav"):         # read by the module, like latvap / latice used only in its commented-out lines
+            c.set_option(k, idz.CONSTS_P3[k])
+        c.set_option("latvap", 2.5e6)
+        c.set_option("latice", 3.34e5)
+        for n in ao.GCM_FORCING_CRM + ao.GCM_FORCING_GCM:
+            c.write(n, inp[n])
+        c.run("compute_gcm_forcing_tendencies")
+        # (the rho_v / rho_l / rho_i tendencies are left unwritten by compute -- fresh memory -- and diagnosed by apply)
+        out = {"computed_" + n: c.read(n, shape[::3]) for n in ao.GCM_FORCING_TEND if n[-5:] not in ("rho_v", "rho_l", "rho_i")}
+        for _ in range(GCM_APPLICATIONS):
+            c.run("apply_gcm_forcing_tendencies")
+        out.update({n: c.read(n, shape) for n in ao.GCM_FORCING_CRM})
+        out.update({n: c.read(n, shape[::3]) for n in ao.GCM_FORCING_TEND})
+        return out
+    if kind == "satadj":
+        import test_moist_surface_modules as tms
+        tr = tms.TRACER_SETS[kw["micro"]]
+        c = _ref_coupler(inp, shape, tr)
+        c.set_option("crm_dt", 2.0)
+        c.set_option("micro", kw["micro"])
+        for k, v in SATADJ_CONSTS.items():
+            c.set_option(k, v)
+        names = ["density_dry", "temp"] + [n for n, _, _ in tr]
+        for n in names:
+            c.write(n, inp[n])
+        c.run("saturation_adjustment")
+        return {n: c.read(n, shape) for n in names}
+    if kind == "friction":
+        import test_moist_surface_modules as tms
+        nz, ny, nx, nens = shape
+        c = _ref_coupler(inp, shape, tms.TRACER_SETS["kessler"])
+        for n in ("sfc_mom_flx_u", "sfc_mom_flx_v"):
+            c.register(n, [ny, nx, nens])
+        for n in ("density_dry", "uvel", "vvel", "water_vapor", "gcm_uvel", "gcm_vvel"):
+            c.write(n, inp[n])
+        # surface_friction_init sums the mean density into a FRESH array: the one path that needs zero-filled memory
+        pam_ref.alloc_fill(zero=True)
+        try:
+            c.run("surface_friction_init", inp["tau"], inp["bflx"])
+        finally:
+            pam_ref.alloc_fill(zero=False)
+        out = {"init_" + n: c.read(n, s) for n, s in (("z0", (nens,)), ("sfc_bflx", (nens,)), ("sfc_mom_flx_u", (ny, nx, nens)),
+                                                     ("sfc_mom_flx_v", (ny, nx, nens)))}
+        c.run("compute_surface_friction")
+        out.update({n: c.read(n, (ny, nx, nens)) for n in ("sfc_mom_flx_u", "sfc_mom_flx_v")})
+        return out
+    raise ValueError(kind)
+
+
+def sha256(path):
+    with open(path, "rb") as fh:
+        return hashlib.sha256(fh.read()).hexdigest()
+
+
+def _compiled_headers():
+    deps = open(os.path.join(ROOT, "oracle", "_ref", "libpam_ref.d")).read().replace("\\\n", " ").splitlines()[0].split(":", 1)[1].split()
+    return [os.path.realpath(os.path.join(ROOT, "oracle", d)) for d in deps]
+
+
+def reference_tree():
+    """the reference tree oracle/_ref/ was compiled from, or None where it is absent (the library may travel without it)"""
+    if not pam_ref.available() or not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libpam_ref.d")):
+        return None
+    dycore = [d for d in _compiled_headers() if d.endswith(os.path.join("dynamics", "awfl", "Dycore.h"))]
+    return os.path.dirname(os.path.dirname(os.path.dirname(dycore[0]))) if dycore and os.path.exists(dycore[0]) else None
+
+
+def provenance():
+    """headers the harness compiled (the compiler's dependency list of oracle/_ref/libpam_ref.so), inside the reference tree"""
+    deps = _compiled_headers()
+    ref = reference_tree()
+    headers = {}
+    for p in deps:
+        if p.startswith(ref + os.sep):
+            headers[os.path.relpath(p, ref)] = sha256(p)
+    cxx = os.environ.get("CXX", "g++")
+    version = subprocess.run([cxx, "--version"], capture_output=True, text=True, check=True).stdout.splitlines()[0]
+    return {"reference_headers_sha256": dict(sorted(headers.items())),
+            "standin_sha256": {f: sha256(os.path.join(ROOT, f)) for f in STANDIN_FILES},
+            "compiler": version,
+            "flags": "-std=c++17 -O2 -ffp-contract=off -fno-fast-math",
+            "standin_settings": {"alloc_fill": "nan", "d1_replay_label": pam_ref.D1_REPLAY_LABEL}}
+
+
+def main(check=False):
+    if reference_tree() is None:
+        sys.exit("needs oracle/_ref/libpam_ref.so and the reference tree it was built from: `make -C oracle` (PAM_REF)")
+    bad = []
+    for name, c in CASES.items():
+        got = run_reference(c)
+        path = fixture_path(name)
+        if check:
+            old = np.load(path)
+            if sorted(old.files) != sorted(got) or any(not np.array_equal(old[k], got[k]) for k in got):
+                bad.append(name)
+            print(name, "differs" if name in bad else "identical")
+        else:
+            np.savez_compressed(path, **got)
+            print(name, "ncycles", list(got["ncycles"]), "bytes", os.path.getsize(path))
+    for name, (kind, kw) in MODULE_CASES.items():
+        inp = module_inputs(kind, kw)
+        got = dict({"in_" + k: np.asarray(v) for k, v in inp.items()}, **{"out_" + k: v for k, v in run_module_reference(kind, kw, inp).items()})
+        path = module_fixture_path(name)
+        if check:
+            old = np.load(path)
+            if sorted(old.files) != sorted(got) or any(not np.array_equal(old[k], got[k]) for k in got):
+                bad.append(name)
+            print(name, "differs" if name in bad else "identical")
+        else:
+            np.savez_compressed(path, **got)
+            print(name, "bytes", os.path.getsize(path))
+    if check:
+        # the arrays decide; of the provenance, the header and stand-in hashes must match too.  The compiler is recorded, not
+        # compared: another g++ that reproduces every array bit for bit is no difference.
+        old, prov = json.load(open(PROVENANCE)), provenance()
+        if any(old[k] != prov[k] for k in ("reference_headers_sha256", "standin_sha256")):
+            bad.append("ref_provenance.json")
+            print("ref_provenance.json differs (reference headers or stand-in)")
+    else:
+        prov = provenance()
+        with open(PROVENANCE, "w") as fh:
+            json.dump(prov, fh, indent=1)
+            fh.write("\n")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(check="--check" in sys.argv))

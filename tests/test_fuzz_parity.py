@@ -129,11 +129,39 @@ def run_case(c):
         # members 60+ of a per-member case sit on a grid 1.6 ... 2.3 x the base grid: with 4-5 levels over 15 km the reference's own
         # arithmetic leaves the numbers there (top layers of > 7 km: the extrapolated ghost pressure of declare_current_profile_as_
         # hydrostatic is not positive -- NaN in variable_gravity; seeds 2634, 3494, 3980).  Such a case says nothing about parity.
+        # The case is skipped only if every checker agrees that it cannot run: the oracle, the reference itself where oracle/_ref/
+        # travelled, and the device (non-finite, or an error such as its refusal of a non-finite CFL step).
+        def finite(fields):
+            return all(np.isfinite(fields[k]).all() for k in ("density_dry", "uvel", "vvel", "wvel", "temp"))
         probe = copy.deepcopy(f)
         oracle_run(probe)
-        if not all(np.isfinite(probe[k]).all() for k in ("density_dry", "uvel", "vvel", "wvel", "temp")):
+        if not finite(probe):
+            from oracle import pam_ref
+            if pam_ref.available():
+                ref = pam_ref.RefDycore(nens, nx, ny, nz, xlen, ylen, dz, pos, mass, idwv, consts=consts, names=names)
+                ref.set_grav_balance(c["mode_a"])
+                rprobe = copy.deepcopy(f)
+                try:
+                    ref.declare_current_profile_as_hydrostatic(rprobe)
+                    for _ in range(c["nsteps"]):
+                        ref.time_step(rprobe, c["crm_dt"])
+                except RuntimeError:
+                    pass
+                assert not finite(rprobe), "the oracle is not finite where the reference is"
+            if not c["mode_a"]:
+                coupler.set_option("balance_hydrostasis_with_gravity", False)
+            try:
+                dycore.declare_current_profile_as_hydrostatic(coupler)
+                for _ in range(c["nsteps"]):
+                    dycore.timeStep(coupler)
+                torch.cuda.synchronize()
+                device_finite = finite(coupler.dump_fields())
+            except PamAmdError:
+                device_finite = False
             dycore.finalize(coupler)
-            raise IllPosedCase("the oracle itself is not finite on this grid")
+            assert not device_finite, "the device run is finite where the oracle is not"
+            raise IllPosedCase("the oracle itself is not finite on this grid" +
+                               (", nor is the reference" if pam_ref.available() else "") + ", nor is the device run")
     if not c["mode_a"]:
         coupler.set_option("balance_hydrostasis_with_gravity", False)
     dycore.declare_current_profile_as_hydrostatic(coupler)
@@ -166,6 +194,15 @@ def run_case(c):
         for k in over:
             assert worst[k] <= 4.0 * floor[k], (k, worst[k], "gate", loose, "4 x oracle's own noise response", 4.0 * floor[k], worst)
     return nsub, mapping, applied, {k: (worst[k], loose, floor[k]) for k in over}
+
+
+def test_ill_posed_seed_is_skipped_only_when_every_checker_agrees():
+    """seed 3980 (130 members on per-member grids up to 2.3 x the base grid, 4 levels over 15 km) is a draw the oracle cannot
+    run: the branch that skips such cases must find the reference (where present) and the device non-finite as well"""
+    c = draw_case(3980)
+    assert c["per_ens"] and c["nens"] > 60
+    with pytest.raises(IllPosedCase):
+        run_case(c)
 
 
 @pytest.mark.parametrize("seed", range(NSEEDS))
