@@ -9,7 +9,8 @@ device) -> per GCM step { declare_current_profile_as_hydrostatic; per CRM step {
 SHOC (the CI build's micro / sgs) and the GCM forcing that works on P3's tracer set are outside this repository's scope; Kessler
 is the microphysics.  What is asserted goes beyond "no crash": bounds on the final state, the reference's own runtime invariant
 (Dycore.h:224-251: the mass of every variable, per member and timeStep, within 1e-10) through the opt-in check of the C ABI, the
-first CRM steps against the oracle, and the member-lane mapping (64 members) reproducing the one-member run bit for bit."""
+first CRM steps against the oracle (at their noise floor, tests/parity_gate.py), and the member-lane mapping (64 members) reproducing the one-member run bit for bit."""
+import copy
 import json
 import os
 import subprocess
@@ -17,7 +18,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from parity_gate import compare
+from parity_gate import compare, noise_floor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "examples", "driver")
@@ -78,19 +79,25 @@ def test_first_crm_steps_of_the_ci_run_match_the_oracle(tmp_path):
     f = {k: crm[k] for k in ("density_dry", "uvel", "vvel", "wvel", "temp")}
     f["tracers"] = np.zeros((3, NZ, NY, NX, nens))
     f["tracers"][0] = crm["water_vapor"]
-    o = ao.OracleDycore(nens, NX, NY, NZ, XLEN, YLEN, np.diff(zint), [True] * 3, [True] * 3, 0, consts=CONSTS)
-    o.declare_current_profile_as_hydrostatic(f)
-    nsub = 0
-    for _ in range(nsteps):
-        nsub += o.time_step(f, CRM_DT)[0]
-        ao.sponge_layer(f, zi, zm, CRM_DT)
-        trc = [np.ascontiguousarray(f["tracers"][t]) for t in range(3)]
-        ao.kessler(trc[0], trc[1], trc[2], f["density_dry"], f["temp"], zm, CRM_DT, CONSTS)
-        for t in range(3):
-            f["tracers"][t] = trc[t]
+
+    def crm_loop(ff):                   # dycore -> sponge -> Kessler, nsteps times
+        o = ao.OracleDycore(nens, NX, NY, NZ, XLEN, YLEN, np.diff(zint), [True] * 3, [True] * 3, 0, consts=CONSTS)
+        o.declare_current_profile_as_hydrostatic(ff)
+        n = 0
+        for _ in range(nsteps):
+            n += o.time_step(ff, CRM_DT)[0]
+            ao.sponge_layer(ff, zi, zm, CRM_DT)
+            trc = [np.ascontiguousarray(ff["tracers"][t]) for t in range(3)]
+            ao.kessler(trc[0], trc[1], trc[2], ff["density_dry"], ff["temp"], zm, CRM_DT, CONSTS)
+            for t in range(3):
+                ff["tracers"][t] = trc[t]
+        return n
+    f0 = copy.deepcopy(f)
+    nsub = crm_loop(f)
     assert nsub == stats["substeps"], (nsub, stats["substeps"])
     g = {"density_dry": got[0], "uvel": got[1], "vvel": got[2], "wvel": got[3], "temp": got[4], "tracers": got[5:]}
-    compare(g, f, ["water_vapor", "cloud_liquid", "precip_liquid"], nsub)      # tests/parity_gate.py
+    names = ["water_vapor", "cloud_liquid", "precip_liquid"]
+    compare(g, f, names, nsub, floor=noise_floor(crm_loop, f0, names, 0, base=f))      # tests/parity_gate.py: the floor gate
 
 
 def test_member_lanes_reproduce_the_one_member_ci_run_bit_for_bit(tmp_path):
@@ -142,18 +149,25 @@ def test_yaml_driver_idealized_run_fills_the_state_on_the_device_and_matches_the
     f["tracers"] = np.zeros((3, nz, ny, nx, nens))
     o = ao.OracleDycore(nens, nx, ny, nz, xlen, ylen, np.diff(zint), [True] * 3, [True] * 3, 0, consts=CONSTS)
     o.init_idealized(f, "thermal", zint)
-    o.declare_current_profile_as_hydrostatic(f)
-    nsub = 0
-    for _ in range(2):
-        nsub += o.time_step(f, dt)[0]
-        trc = [np.ascontiguousarray(f["tracers"][t]) for t in range(3)]
-        ao.kessler(trc[0], trc[1], trc[2], f["density_dry"], f["temp"], zm, dt, CONSTS)
-        for t in range(3):
-            f["tracers"][t] = trc[t]
+
+    def run(ff):                        # dycore -> Kessler, twice (no sponge layer)
+        o = ao.OracleDycore(nens, nx, ny, nz, xlen, ylen, np.diff(zint), [True] * 3, [True] * 3, 0, consts=CONSTS)
+        o.declare_current_profile_as_hydrostatic(ff)
+        n = 0
+        for _ in range(2):
+            n += o.time_step(ff, dt)[0]
+            trc = [np.ascontiguousarray(ff["tracers"][t]) for t in range(3)]
+            ao.kessler(trc[0], trc[1], trc[2], ff["density_dry"], ff["temp"], zm, dt, CONSTS)
+            for t in range(3):
+                ff["tracers"][t] = trc[t]
+        return n
+    f0 = copy.deepcopy(f)
+    nsub = run(f)
     assert nsub == stats["substeps"]
     raw = np.fromfile(outp, dtype="<f8")
     ncell = nz * ny * nx * nens
     got = raw[:8 * ncell].reshape(8, nz, ny, nx, nens)
     g = {"density_dry": got[0], "uvel": got[1], "vvel": got[2], "wvel": got[3], "temp": got[4], "tracers": got[5:]}
     assert 190.0 < g["temp"].min() and g["temp"].max() < 305.0 and g["wvel"].max() > 0.0     # a warm bubble in a theta = 300 K atmosphere (T = 200 K at 10 km), rising
-    compare(g, f, ["water_vapor", "cloud_liquid", "precip_liquid"], nsub)
+    names = ["water_vapor", "cloud_liquid", "precip_liquid"]
+    compare(g, f, names, nsub, floor=noise_floor(run, f0, names, 0, base=f))
