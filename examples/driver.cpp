@@ -44,6 +44,8 @@
 #include "modules/perturb_temperature.h"
 #include "modules/saturation_adjustment.h"
 #include "modules/surface_friction.h"
+#include "modules/horizontal_average.h"
+#include "modules/time_average.h"
 #include "physics/micro/kessler_amd/Microphysics.h"
 
 #include <map>
@@ -231,7 +233,8 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-//   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] <output.bin | ->
+//   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--stats PATH]
+//          <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
 // out_freq, vcoords [, crm_nz, zlen, idealized, apply_sponge, initData].  What runs, in the reference's order:
@@ -301,7 +304,21 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //   --sat-adjust               modules::saturation_adjustment after micro
 //   --surface-friction TAU BFLX  modules::surface_friction_init once (every member: tau = TAU, bflx = BFLX), then
 //                              modules::compute_surface_friction every CRM step after the sponge layer
-struct YamlModules { bool sat_adjust = false, surface_friction = false; double tau = 0, bflx = 0; };
+//   --stats PATH               the CRM -> GCM statistics of E3SM's MMF loop: modules::time_average_init at the start of every GCM
+//                              step on the state, the tracers and precl; modules::time_average_accumulate after the last module of
+//                              every CRM step; modules::horizontal_average of the "<var>_time_average" entries at the end of every
+//                              GCM step (and of a run cut short by --steps).  The (nz,nens) profiles go to PATH as JSON, every value
+//                              printed with %.17g (exact round trip); nothing else of the run changes.
+struct YamlModules { bool sat_adjust = false, surface_friction = false; double tau = 0, bflx = 0; std::string stats; };
+
+// one JSON number that Python's json module reads back exactly (NaN / Infinity for the non-finite)
+static void stats_json_number(std::string &o, double v) {
+  char t[40];
+  if (std::isnan(v)) std::snprintf(t, sizeof(t), "NaN");
+  else if (std::isinf(v)) std::snprintf(t, sizeof(t), v > 0 ? "Infinity" : "-Infinity");
+  else std::snprintf(t, sizeof(t), "%.17g", v);
+  o += t;
+}
 static int run_yaml(const std::string &file, int nens_override, int steps_limit, bool check, const std::string &outfile, YamlDebug dbg = YamlDebug(),
                     YamlModules mods = YamlModules()) {
   auto kv = read_flat_yaml(file);
@@ -375,13 +392,23 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     auto fetch = [&](std::string const &name) {
       if (hipMemcpy(buf.data(), dm.get<real const, 4>(name).data(), ncell * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess) endrun("memcpy");
     };
+    // --stats: the fields averaged over each GCM step, and their profiles as JSON
+    const bool stats = !mods.stats.empty();
+    std::vector<std::string> stat_names = {"density_dry", "uvel", "vvel", "wvel", "temp"};
+    for (auto &n : coupler.get_tracer_names()) stat_names.push_back(n);
+    stat_names.push_back("precl");
+    std::vector<std::tuple<std::string, bool>> stat_havg;
+    for (auto &n : stat_names) stat_havg.emplace_back(n + "_time_average", n != "precl");
+    std::string stats_steps;
     double etime_gcm = 0, maxw_all = 0, cons_max_rel = 0;
     int num_out = 0, crm_steps = 0;
     long substeps = 0, cons_violations = 0;
     bool stop = false;
     std::string maxw_series;
     for (int step_gcm = 0; step_gcm < nsteps_gcm && !stop; ++step_gcm) {
+      if (stats) coupler.run_module("time_average_init", [&](pam::PamCoupler &c) { modules::time_average_init(c, stat_names); });
       dycore.declare_current_profile_as_hydrostatic(coupler);               // (E3SM's MMF driver: once per GCM step)
+      int crm_steps_gcm = 0;
       for (int step_crm_phys = 0; step_crm_phys < nsteps_crm_phys && !stop; ++step_crm_phys) {
         coupler.run_module("dycore", [&](pam::PamCoupler &c) { dycore.timeStep(c); });       // driver.cpp:248
         substeps += dycore.last_ncycles();
@@ -395,8 +422,10 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         if (!dbg.no_micro) coupler.run_module("micro", [&](pam::PamCoupler &c) { micro.timeStep(c); });         // driver.cpp:253
         if (mods.sat_adjust) coupler.run_module("saturation_adjustment", modules::saturation_adjustment);
+        if (stats) coupler.run_module("time_average_accumulate", [&](pam::PamCoupler &c) { modules::time_average_accumulate(c, stat_names); });
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         crm_steps++;
+        crm_steps_gcm++;
         etime_gcm = step_gcm * dt_gcm + (step_crm_phys + 1) * dt_crm_phys;  // driver.cpp:255
         if (out_freq >= 0. && etime_gcm / out_freq >= num_out + 1) {        // driver.cpp:257-271 (the netCDF output itself: out of scope)
           fetch("wvel");
@@ -412,6 +441,43 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         }
         if (steps_limit > 0 && crm_steps >= steps_limit) stop = true;
       }
+      if (stats) {                                                            // the GCM step's profiles
+        coupler.run_module("horizontal_average", [&](pam::PamCoupler &c) { modules::horizontal_average(c, stat_havg); });
+        char t[96];
+        std::snprintf(t, sizeof(t), "%s{\"gcm_step\": %d, \"crm_steps\": %d, \"profiles\": {", stats_steps.empty() ? "" : ", ", step_gcm,
+                      crm_steps_gcm);
+        stats_steps += t;
+        for (size_t f = 0; f < stat_names.size(); f++) {
+          const int pnz = stat_names[f] == "precl" ? 1 : crm_nz;
+          std::vector<real> prof((size_t)pnz * nens);
+          if (hipMemcpy(prof.data(), dm.get<real const, 2>(stat_names[f] + "_time_average_horizontal_average").data(),
+                        prof.size() * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess) endrun("memcpy");
+          stats_steps += (f ? ", \"" : "\"") + stat_names[f] + "\": [";
+          for (int k = 0; k < pnz; k++) {
+            stats_steps += k ? ", [" : "[";
+            for (int e = 0; e < nens; e++) {
+              if (e) stats_steps += ", ";
+              stats_json_number(stats_steps, prof[(size_t)k * nens + e]);
+            }
+            stats_steps += "]";
+          }
+          stats_steps += "]";
+        }
+        stats_steps += "}}";
+      }
+    }
+    if (stats) {
+      std::string o = "{\"nens\": " + std::to_string(nens) + ", \"nz\": " + std::to_string(crm_nz) + ", \"crm_dt\": ";
+      stats_json_number(o, dt_crm_phys);
+      o += ", \"gcm_physics_dt\": ";
+      stats_json_number(o, dt_gcm);
+      o += ", \"fields\": [";
+      for (size_t f = 0; f < stat_names.size(); f++) o += (f ? ", \"" : "\"") + stat_names[f] + "\"";
+      o += "], \"gcm_steps\": [" + stats_steps + "]}\n";
+      std::ofstream so(mods.stats);
+      if (!so) endrun("cannot open the --stats file");
+      so << o;
+      if (!so) endrun("cannot write the --stats file");
     }
     if (hipDeviceSynchronize() != hipSuccess) endrun("device error");
     if (sf_in) (void)hipFree(sf_in);
@@ -496,7 +562,9 @@ int main(int argc, char **argv) {
         mods.tau = std::atof(argv[++b]);
         mods.bflx = std::atof(argv[++b]);
       }
-      else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] <output.bin | ->");
+      else if (o == "--stats" && b + 1 < argc - 1) mods.stats = argv[++b];
+      else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
+               "[--stats PATH] <output.bin | ->");
     }
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }

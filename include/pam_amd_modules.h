@@ -128,6 +128,29 @@ int pam_amd_surface_friction_compute(int nens, int nx, int ny, int nz, const dou
                                      const double *vvel, const double *zmid, const double *zint, const double *z0,
                                      const double *sfc_bflx, double *sfc_mom_flx_u, double *sfc_mom_flx_v, void *stream);
 
+/* The CRM statistics of the CRM -> GCM direction.  Each entry point takes a LIST of fields: host arrays of num_fields values / DEVICE
+ * pointers, num_fields >= 1; 32 fields travel per launch and a longer list is split (the results do not depend on the split).  Every
+ * argument is checked before the first HIP call, so an EINVAL return has written nothing.
+ *
+ * modules::horizontal_average(coupler, var_list)  (pam_core/modules/horizontal_average.h:25-75): one profile per member.
+ *   nz, ncol   per field, >= 1: the field is (nz, ncol, nens) with nens fastest ((ny,nx) collapse to ncol = ny*nx; a field without a
+ *              vertical dimension has nz = 1)
+ *   in         DEVICE (nz,ncol,nens) fields; out  DEVICE (nz,nens) "<var>_horizontal_average"
+ * out(k,e) = sum over i = 0 .. ncol-1, in ascending order, of in(k,i,e) * (1/ncol), every product rounded before it is added: the
+ * reference's serial order, bit for bit. */
+int pam_amd_horizontal_average(int nens, int num_fields, const int *nz, const int *ncol, const double *const *in, double *const *out,
+                               void *stream);
+
+/* modules::time_average_init(coupler, names)  (pam_core/modules/time_average.h:8-36): zeroes the DEVICE "<var>_time_average"
+ * arrays tavg[f] of size[f] >= 1 elements. */
+int pam_amd_time_average_zero(int num_fields, const long long *size, double *const *tavg, void *stream);
+
+/* modules::time_average_accumulate(coupler, names)  (time_average.h:39-72; every CRM step): tavg[f][i] += var[f][i] * factor element
+ * by element, the product rounded before the add.  var, tavg: DEVICE arrays of size[f] >= 1 elements; factor = crm_dt /
+ * gcm_physics_dt (options "crm_dt", "gcm_physics_dt"), finite. */
+int pam_amd_time_average_accumulate(int num_fields, const long long *size, const double *const *var, double *const *tavg, double factor,
+                                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

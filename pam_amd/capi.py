@@ -109,6 +109,10 @@ MODULE_SYMBOLS = {
                                       + [C.c_void_p]),
     "pam_amd_surface_friction_init": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 11 + [C.c_void_p]),
     "pam_amd_surface_friction_compute": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 10 + [C.c_void_p]),
+    "pam_amd_horizontal_average": (C.c_int, [C.c_int] * 2 + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_void_p)] * 2 + [C.c_void_p]),
+    "pam_amd_time_average_zero": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_void_p), C.c_void_p]),
+    "pam_amd_time_average_accumulate": (C.c_int, [C.c_int, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_void_p)] * 2
+                                        + [C.c_double, C.c_void_p]),
 }
 
 

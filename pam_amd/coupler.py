@@ -93,6 +93,16 @@ class DataManager:
             self._e[name]["dirty"] = True                                                           # DataManager.h:306
         return self._e[name]["data"]
 
+    def get_collapsed(self, name, readonly=False):
+        """DataManager.h:363-402: the entry as one dimension (a view of the same storage)"""
+        return self.get(name, readonly).view(-1)
+
+    def get_shape(self, name):
+        """DataManager.h:405"""
+        if name not in self._e:
+            endrun(f"ERROR: Could not find entry {name}")
+        return list(self._e[name]["dims"])
+
     def get_dimension_size(self, name):
         return self._dims.get(name, -1)
 

@@ -130,6 +130,25 @@ class DataManager {
     return DeviceView<T>((T *)it->second.ptr, it->second.dims);
   }
 
+  // DataManager.h:363-402: every dimension collapsed into one (the storage order kept); T const -> read-only, T -> read-write
+  template <class T>
+  DeviceView<T> get_collapsed(std::string name) {
+    auto it = entries.find(name);
+    if (it == entries.end()) endrun("ERROR: Could not find entry " + name);
+    if (it->second.elem != sizeof(T)) endrun("ERROR: type mismatch for entry " + name);
+    if (!std::is_const<T>::value) it->second.dirty = true;
+    size_t n = 1;
+    for (int d : it->second.dims) n *= d;
+    return DeviceView<T>((T *)it->second.ptr, {(int)n});
+  }
+
+  // DataManager.h:405
+  std::vector<int> get_shape(std::string name) const {
+    auto it = entries.find(name);
+    if (it == entries.end()) endrun("ERROR: Could not find entry " + name);
+    return it->second.dims;
+  }
+
   int get_dimension_size(std::string name) const {
     auto it = dimensions.find(name);
     return it == dimensions.end() ? -1 : it->second;

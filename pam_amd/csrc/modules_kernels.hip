@@ -1,8 +1,10 @@
 // modules_kernels.hip -- gfx950 kernels of the coupler modules around the dycore (include/pam_amd_modules.h).
 // sponge_layer: pam_core/modules/sponge_layer.h:8-95.  Both kernels are tiny and HBM-bound (top 5 of 60 levels).
-// saturation_adjustment, surface_friction_init / compute_surface_friction: at the end of the file.
+// saturation_adjustment, surface_friction_init / compute_surface_friction, then the statistics modules (horizontal_average,
+// time_average_*): at the end of the file.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <mutex>
 #include <string>
@@ -14,6 +16,7 @@
 #include "awfl_vertical.h"     // build_pow_tab
 #include "supercell_sounding.h"
 #include "moist_surface_device.h"  // saturation adjustment, surface friction: per-cell bodies shared with the host emulation
+#include "statistics_device.h"     // horizontal_average, time_average_*: the same, for the statistics modules
 
 namespace {
 
@@ -1047,4 +1050,179 @@ extern "C" int pam_amd_surface_friction_compute(int nens, int nx, int ny, int nz
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, hipGetErrorString(err));
   return PAM_AMD_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// The CRM statistics modules: modules::horizontal_average and modules::time_average_init / time_average_accumulate
+// (pam_core/modules/horizontal_average.h, time_average.h).  Each call takes a list of fields; up to STATS_TABLE of them travel in one
+// kernarg table, and a longer list is split into several launches (every output element is computed by one thread from its own
+// inputs alone, so the bits do not depend on the split).  No scratch, no atomics.  The arithmetic lives in statistics_device.h.
+namespace {
+using namespace pama::stats;
+constexpr int STATS_TABLE = 32;
+constexpr int HAVG_UNROLL = 16;   // rows of the walk in flight ahead of the in-order adds
+constexpr int TAVG_UNROLL = 4;    // elements per thread and pass of the element-wise launches
+
+struct HavgTable { const double *in[STATS_TABLE]; double *out[STATS_TABLE]; int nz[STATS_TABLE]; int ncol[STATS_TABLE]; };
+struct TavgTable { const double *var[STATS_TABLE]; double *tavg[STATS_TABLE]; long long size[STATS_TABLE]; };
+
+// horizontal_average.h:67-73.  grid (member blocks x levels, fields of the table), one wavefront per workgroup: lane = member, so
+// every step of the walk over the columns is one coalesced row of up to 64 members.  One thread owns one (field, level, member) and
+// adds its column values in ascending order, each product rounded first (havg_add): the reference's serial order, not slot_reduce's.
+// The loads of HAVG_UNROLL rows are issued before their adds.  IDX: unsigned when every field of the table is below 2^31 elements.
+template <class IDX>
+__global__ void __launch_bounds__(64) horizontal_average_kernel(int nens, int nblk, HavgTable T) {
+  const int f = (int)blockIdx.y;
+  const int k = (int)blockIdx.x / nblk;
+  const int e = ((int)blockIdx.x % nblk) * 64 + (int)threadIdx.x;
+  const int nz = T.nz[f], ncol = T.ncol[f];
+  if (k >= nz || e >= nens) return;
+  const IDX stride = (IDX)nens;
+  const double *__restrict__ p = T.in[f] + ((IDX)k * (IDX)ncol * stride + (IDX)e);
+  const double r = havg_r_ncol(ncol);
+  double acc = 0.0;
+  int i = 0;
+  for (; i + HAVG_UNROLL <= ncol; i += HAVG_UNROLL) {
+    double v[HAVG_UNROLL];
+#pragma unroll
+    for (int j = 0; j < HAVG_UNROLL; j++) v[j] = p[(IDX)(i + j) * stride];
+#pragma unroll
+    for (int j = 0; j < HAVG_UNROLL; j++) acc = havg_add(acc, v[j], r);
+  }
+  for (; i < ncol; i++) acc = havg_add(acc, p[(IDX)i * stride], r);
+  T.out[f][(IDX)k * stride + (IDX)e] = acc;
+}
+
+// time_average.h:32-34 (ZERO) and :67-70: element-wise over the collapsed fields; grid (blocks, fields of the table), each block
+// strides over its field in passes of 256 x TAVG_UNROLL elements.  IDX as above.
+template <bool ZERO, class IDX>
+__global__ void __launch_bounds__(256) time_average_kernel(TavgTable T, double factor) {
+  const int f = (int)blockIdx.y;
+  const IDX n = (IDX)T.size[f];
+  const double *__restrict__ v = T.var[f];
+  double *__restrict__ t = T.tavg[f];
+  const IDX step = (IDX)gridDim.x * (IDX)(256 * TAVG_UNROLL);
+  for (IDX base = (IDX)blockIdx.x * (IDX)(256 * TAVG_UNROLL) + (IDX)threadIdx.x; base < n; base += step) {
+    if constexpr (ZERO) {
+#pragma unroll
+      for (int j = 0; j < TAVG_UNROLL; j++) {
+        const IDX i = base + (IDX)(j * 256);
+        if (i < n) t[i] = 0.0;
+      }
+    } else {
+      double a[TAVG_UNROLL], b[TAVG_UNROLL];
+#pragma unroll
+      for (int j = 0; j < TAVG_UNROLL; j++) {
+        const IDX i = base + (IDX)(j * 256);
+        if (i < n) { a[j] = v[i]; b[j] = t[i]; }
+      }
+#pragma unroll
+      for (int j = 0; j < TAVG_UNROLL; j++) {
+        const IDX i = base + (IDX)(j * 256);
+        if (i < n) t[i] = tavg_add(b[j], a[j], factor);
+      }
+    }
+  }
+}
+
+constexpr long long IDX32_LIMIT = 1LL << 31;
+
+int stats_launch_check(const char *who) {
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": " + hipGetErrorString(err)).c_str());
+  return PAM_AMD_OK;
+}
+
+// the element-wise launches of time_average_zero / time_average_accumulate over an already validated list
+template <bool ZERO>
+int time_average_launch(const char *who, int num_fields, const long long *size, const double *const *var, double *const *tavg,
+                        double factor, void *stream) {
+  for (int f0 = 0; f0 < num_fields; f0 += STATS_TABLE) {
+    const int nf = std::min(STATS_TABLE, num_fields - f0);
+    TavgTable T;
+    long long most = 0;
+    for (int l = 0; l < STATS_TABLE; l++) {
+      const bool in = l < nf;
+      T.var[l] = (in && !ZERO) ? var[f0 + l] : nullptr;
+      T.tavg[l] = in ? tavg[f0 + l] : nullptr;
+      T.size[l] = in ? size[f0 + l] : 0;
+      most = std::max(most, T.size[l]);
+    }
+    // ~2048 workgroups of 256 in all (eight per CU), never more than the largest field needs
+    const long long per_blk = 256LL * TAVG_UNROLL, need = (most + per_blk - 1) / per_blk;
+    const unsigned gx = (unsigned)std::max(1LL, std::min(need, (long long)std::max(1, 2048 / nf)));
+    const dim3 grid(gx, (unsigned)nf);
+    if (most < IDX32_LIMIT)
+      hipLaunchKernelGGL((time_average_kernel<ZERO, unsigned>), grid, dim3(256), 0, (hipStream_t)stream, T, factor);
+    else
+      hipLaunchKernelGGL((time_average_kernel<ZERO, long long>), grid, dim3(256), 0, (hipStream_t)stream, T, factor);
+    if (int rc = stats_launch_check(who)) return rc;
+  }
+  return PAM_AMD_OK;
+}
+
+int time_average_check(const char *who, int num_fields, const long long *size, double *const *tavg) {
+  if (num_fields < 1 || !size || !tavg)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": bad num_fields or null pointer table").c_str());
+  for (int f = 0; f < num_fields; f++) {
+    if (size[f] < 1) return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": every size must be >= 1").c_str());
+    if (!tavg[f]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": null time-average pointer").c_str());
+  }
+  return PAM_AMD_OK;
+}
+}  // namespace
+
+extern "C" int pam_amd_horizontal_average(int nens, int num_fields, const int *nz, const int *ncol, const double *const *in,
+                                          double *const *out, void *stream) {
+  if (nens < 1 || num_fields < 1 || !nz || !ncol || !in || !out)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "horizontal_average: bad nens / num_fields or null pointer table");
+  const long long nblk = (nens + 63) / 64;
+  for (int f = 0; f < num_fields; f++) {
+    if (nz[f] < 1 || ncol[f] < 1) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "horizontal_average: nz and ncol must be >= 1");
+    if (!in[f] || !out[f]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "horizontal_average: null field pointer");
+    if (nblk * nz[f] > 0x7fffffffLL) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "horizontal_average: nz x member blocks exceeds the grid");
+  }
+  if (int rc = moist_surface_device_check("horizontal_average")) return rc;
+  for (int f0 = 0; f0 < num_fields; f0 += STATS_TABLE) {
+    const int nf = std::min(STATS_TABLE, num_fields - f0);
+    HavgTable T;
+    int max_nz = 1;
+    long long most = 0;
+    for (int l = 0; l < STATS_TABLE; l++) {
+      const bool use = l < nf;
+      T.in[l] = use ? in[f0 + l] : nullptr;
+      T.out[l] = use ? out[f0 + l] : nullptr;
+      T.nz[l] = use ? nz[f0 + l] : 0;
+      T.ncol[l] = use ? ncol[f0 + l] : 0;
+      if (use) {
+        max_nz = std::max(max_nz, T.nz[l]);
+        most = std::max(most, (long long)T.nz[l] * T.ncol[l] * nens);
+      }
+    }
+    const dim3 grid((unsigned)(nblk * max_nz), (unsigned)nf);
+    if (most < IDX32_LIMIT)
+      hipLaunchKernelGGL((horizontal_average_kernel<unsigned>), grid, dim3(64), 0, (hipStream_t)stream, nens, (int)nblk, T);
+    else
+      hipLaunchKernelGGL((horizontal_average_kernel<long long>), grid, dim3(64), 0, (hipStream_t)stream, nens, (int)nblk, T);
+    if (int rc = stats_launch_check("horizontal_average")) return rc;
+  }
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_time_average_zero(int num_fields, const long long *size, double *const *tavg, void *stream) {
+  if (int rc = time_average_check("time_average_zero", num_fields, size, tavg)) return rc;
+  if (int rc = moist_surface_device_check("time_average_zero")) return rc;
+  return time_average_launch<true>("time_average_zero", num_fields, size, nullptr, tavg, 0.0, stream);
+}
+
+extern "C" int pam_amd_time_average_accumulate(int num_fields, const long long *size, const double *const *var, double *const *tavg,
+                                               double factor, void *stream) {
+  if (int rc = time_average_check("time_average_accumulate", num_fields, size, tavg)) return rc;
+  if (!var) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "time_average_accumulate: null pointer table");
+  for (int f = 0; f < num_fields; f++)
+    if (!var[f]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "time_average_accumulate: null field pointer");
+  if (!std::isfinite(factor)) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "time_average_accumulate: factor must be finite");
+  if (int rc = moist_surface_device_check("time_average_accumulate")) return rc;
+  return time_average_launch<false>("time_average_accumulate", num_fields, size, var, tavg, factor, stream);
 }

@@ -202,3 +202,122 @@ def compute_surface_friction(coupler):
     with torch.cuda.device(coupler.device):
         check(lib.pam_amd_surface_friction_compute(nens, nx, ny, nz, *[a.data_ptr() for a in args],
                                                    torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+def _stats_collapse(dm, name, has_vertical_dim, nens):
+    """(nz, ncol) of a variable as horizontal_average.h:43-62 reads it; endrun on every shape the reference rejects, and (deviations,
+    DESIGN.md section 8) on a last dimension other than the coupler's nens and on a rank of 5 or more"""
+    from .coupler import endrun
+    shape = dm.get_shape(name)
+    r = len(shape)
+    if shape[-1] != nens:
+        endrun("ERROR: Last dimension must be nens (%s)" % name)
+    if r == 1:
+        endrun("ERROR: Cannot horizontally average a 1-D variable (%s)" % name)
+    if has_vertical_dim:
+        if r == 2:
+            endrun("ERROR: Cannot horizontally average a nz,nens variable (%s)" % name)
+        if r > 4:
+            endrun("ERROR: Only two horizontal dimensions allowed (%s)" % name)
+        nz, ncol = shape[0], (shape[1] if r == 3 else shape[1] * shape[2])
+    else:
+        if r > 3:
+            endrun("ERROR: Only two horizontal dimensions allowed (%s)" % name)
+        nz, ncol = 1, (shape[0] if r == 2 else shape[0] * shape[1])
+    if ncol > 0x7fffffff:
+        endrun("ERROR: horizontal_average: bad number of columns (%s)" % name)
+    return nz, ncol
+
+
+def horizontal_average(coupler, var_list):
+    """modules::horizontal_average(coupler, var_list)  (pam_core/modules/horizontal_average.h:25-75): var_list holds (name,
+    has_vertical_dim) pairs; registers "<name>_horizontal_average" (nz,nens) -- or reuses it: a second call overwrites it -- and
+    sets it to the mean over the columns, summed serially in ascending column order as the reference does.  The whole list is
+    validated before anything is registered or written."""
+    from .coupler import endrun
+    lib = capi.load()
+    nens = coupler.get_nens()
+    dm = coupler.get_data_manager_device_readwrite()
+    items = []
+    for name, has_vertical_dim in var_list:
+        nz, ncol = _stats_collapse(dm, name, bool(has_vertical_dim), nens)
+        havg = name + "_horizontal_average"
+        if dm.entry_exists(havg) and dm.get_shape(havg) != [nz, nens]:
+            endrun("ERROR: %s exists with a shape other than {nz,nens}" % havg)
+        items.append((name, havg, nz, ncol))
+    if not items:
+        return
+    for name, havg, nz, _ in items:
+        if not dm.entry_exists(havg):
+            dm.register_and_allocate(havg, "", (nz, nens))
+    ins = [dm.get_collapsed(n, readonly=True) for n, _, _, _ in items]
+    outs = [dm.get(h) for _, h, _, _ in items]
+    nzs = (C.c_int * len(items))(*[it[2] for it in items])
+    ncols = (C.c_int * len(items))(*[it[3] for it in items])
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_horizontal_average(nens, len(items), nzs, ncols, _ptr_table(ins), _ptr_table(outs),
+                                             torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+def _sizes(shapes):
+    import math
+    return (C.c_longlong * len(shapes))(*[math.prod(s) for s in shapes])
+
+
+def time_average_init(coupler, names):
+    """modules::time_average_init(coupler, names)  (pam_core/modules/time_average.h:8-36): registers "<name>_time_average" with the
+    variable's own shape -- or reuses it -- and zeroes it (once per GCM step).  The whole list is validated first."""
+    from .coupler import endrun
+    lib = capi.load()
+    dm = coupler.get_data_manager_device_readwrite()
+    names = list(names)
+    shapes = []
+    for name in names:
+        shape = dm.get_shape(name)
+        tavg = name + "_time_average"
+        if dm.entry_exists(tavg) and dm.get_shape(tavg) != shape:
+            endrun("ERROR: %s exists with a shape other than %s's" % (tavg, name))
+        shapes.append(shape)
+    if not names:
+        return
+    for name, shape in zip(names, shapes):
+        if not dm.entry_exists(name + "_time_average"):
+            dm.register_and_allocate(name + "_time_average", "", tuple(shape))
+    tavg = [dm.get_collapsed(n + "_time_average") for n in names]
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_time_average_zero(len(names), _sizes(shapes), _ptr_table(tavg),
+                                            torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+def time_average_accumulate(coupler, names):
+    """modules::time_average_accumulate(coupler, names)  (time_average.h:39-72; every CRM step): "<name>_time_average" +=
+    name * (crm_dt / gcm_physics_dt), element by element.  Options "crm_dt", "gcm_physics_dt" (> 0).  The whole list is validated
+    first: a name without its time average (no init) raises and nothing is written."""
+    import math
+    from .coupler import endrun
+    lib = capi.load()
+    crm_dt = float(coupler.get_option("crm_dt"))
+    gcm_dt = float(coupler.get_option("gcm_physics_dt"))
+    if not gcm_dt > 0:
+        endrun("ERROR: time_average_accumulate: gcm_physics_dt must be positive")
+    factor = crm_dt / gcm_dt
+    if not math.isfinite(factor):
+        endrun("ERROR: time_average_accumulate: crm_dt / gcm_physics_dt is not finite")
+    dm = coupler.get_data_manager_device_readwrite()
+    names = list(names)
+    shapes = []
+    for name in names:
+        shape = dm.get_shape(name)
+        tavg = name + "_time_average"
+        if not dm.entry_exists(tavg):
+            endrun("ERROR: %s does not exist: call time_average_init first" % tavg)
+        if dm.get_shape(tavg) != shape:
+            endrun("ERROR: %s has a shape other than %s's" % (tavg, name))
+        shapes.append(shape)
+    if not names:
+        return
+    var = [dm.get_collapsed(n, readonly=True) for n in names]
+    tavg = [dm.get_collapsed(n + "_time_average") for n in names]
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_time_average_accumulate(len(names), _sizes(shapes), _ptr_table(var), _ptr_table(tavg), factor,
+                                                  torch.cuda.current_stream(coupler.device).cuda_stream))

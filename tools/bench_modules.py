@@ -1,5 +1,6 @@
 """The coupler-module timings of bench.py alone (Kessler, sponge layer, GCM forcing at the C2 grid), then saturation_adjustment and
-surface_friction_init / compute_surface_friction at the same grid: one JSON object on stdout.
+surface_friction_init / compute_surface_friction and the statistics modules (time_average_*, horizontal_average) at the same grid:
+one JSON object on stdout.
 Run on the GPU box:  python tools/bench_modules.py"""
 import json
 import os
@@ -111,8 +112,43 @@ def moist_surface_timing(dev):
     return out
 
 
+def statistics_timing(dev):
+    """time_average_init / time_average_accumulate / horizontal_average at the C2 grid on the Kessler field set: the five state
+    fields, the three tracers and precl (what examples/driver --stats averages)"""
+    from pam_amd import PamCoupler, Microphysics, modules
+    from pam_amd import idealized as idz
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    c = PamCoupler(dev)
+    c.set_option("crm_dt", 2.0)
+    c.set_option("gcm_physics_dt", 900.0)
+    c.allocate_coupler_state(nz, ny, nx, nens)
+    c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+    micro = Microphysics()
+    micro.init(c)
+    dm = c.get_data_manager_device_readwrite()
+    names = ["density_dry", "uvel", "vvel", "wvel", "temp"] + c.get_tracer_names() + ["precl"]
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for n in names:
+        t = dm.get(n)
+        t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev))
+    elems = sum(dm.get(n, readonly=True).numel() for n in names)
+    modules.time_average_init(c, names)
+    havg = [(n + "_time_average", n != "precl") for n in names]
+    out = {}
+    for label, fn, nbytes in (("time_average_init", lambda: modules.time_average_init(c, names), elems * 8.0),
+                              ("time_average_accumulate", lambda: modules.time_average_accumulate(c, names), elems * 24.0),
+                              ("horizontal_average", lambda: modules.horizontal_average(c, havg), elems * 8.0)):
+        t = _events(fn)
+        out[label] = {"ms": t, "bytes": nbytes, "GBps": nbytes / t / 1e6, "hbm_frac": nbytes / t / 1e6 / bench.HBM_PEAK_GBS,
+                      "fields": len(names)}
+    del micro, dm, c
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
     out = bench.modules_timing(torch, dev)
     out.update(moist_surface_timing(dev))
+    out.update(statistics_timing(dev))
     print(json.dumps({k: ({kk: vv for kk, vv in v.items() if kk != "note"} if isinstance(v, dict) else v) for k, v in out.items()}))
