@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- cell-updates/s of the MI355X-native AWFL dycore step (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--scaling weak|strong] [--nens E] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--scaling weak|strong] [--nens E] [--dump-outputs DIR] [--full]
 
 A "step" is one `Dycore::timeStep` (Dycore.h:107) over the whole resident ensemble: coupler->dycore conversion,
 CFL reduction, `ncycles` SSPRK3 sub-steps (3 tendency evaluations each) and dycore->coupler conversion, with the
@@ -21,7 +21,11 @@ exchange is the 8-byte all-reduce(MIN) of the CFL time step per timeStep (RCCL; 
 the TOTAL, split over the ranks (c2: 1024 -> 128 per GPU at N=8; c4's 512 is already the per-GPU shard of nens=4096).
 When the box has fewer GPUs than ranks (rehearsal on a 1-GPU box) the ranks share device 0 and reduce over gloo.
 
-Extra objects on the JSON line:
+A plain run sets up, runs the W warm-up and K timed steps, writes --dump-outputs and prints the line; `roofline` and
+`cpu_baseline` are null on it and `other` is absent.  `--full` adds the un-timed passes after the timed steps (each one can
+still be left out with --no-kernel-timing, --no-cpu-baseline, --no-other-configs).
+
+Extra objects on the JSON line (--full):
   roofline      the dominant kernel of the stage (by device time, nothing co-running): achieved = algorithmic bytes per
                 launch / mean launch duration; one launch = one tendency stage over all cells = cells/3 cell-updates x
                 64*(5+NT) B.  Launch durations are measured live with HIP events on the stream the kernels
@@ -36,7 +40,7 @@ Extra objects on the JSON line:
                 `kernel_rooflines` lists every stage kernel with the bytes it must itself move and its FP64 work.
   cpu_baseline  the CPU oracle (a port of the reference algorithm, oracle/awfl_oracle.c, OpenMP over the flux loop)
                 timed on this host on a bounded sample of the same workload (rank 0, N=1 only).
-  other_configs C3 / C4 throughput on this GPU (N=1, default run only), measured the same way with fewer steps, each with its
+  other_configs C3 / C4 throughput on this GPU (N=1, C2 at its own nens only), measured the same way with fewer steps, each with its
                 own `roofline` (+ `traffic` from profiles/r03_c{3,4}_traffic.json) and `kernel_rooflines`.
 
 --dump-outputs DIR: after the K timed steps (before any un-timed pass), the coupler fields the last timed step left behind --
@@ -216,7 +220,7 @@ def launch_cpp(args):
                                   "doubles; no collective library)" % (args.gpus, args.gpus),
                       "collective": None, "ranks_seen": d["ranks"], "devices_seen": d["devices"], "limiter_input": args.limiter},
            "roofline": None, "cpu_baseline": None,
-           "note": "roofline / cpu_baseline are measured by the default (Python) launcher of the same library"}
+           "note": "roofline / cpu_baseline are measured by the default (Python) launcher of the same library with --full"}
     emit(out, args)
 
 
@@ -948,9 +952,9 @@ def worker(args):
     cells = job.nens * job.nz * job.ny * job.nx
     nt = job.nt
 
-    # ---- per-kernel durations (HIP events on the stream each kernel is launched on), separate un-timed passes
+    # ---- per-kernel durations (HIP events on the stream each kernel is launched on), separate un-timed passes (--full)
     roofline, kernels, kernel_rooflines = None, {}, []
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         plain = args.scaling == "weak" and not args.limiter
         pkey = args.config if (plain and args.nens == 0) else ("c2grid_nens%d" % args.nens if (plain and args.config == "c2") else None)
         if plain and args.config == "ref" and args.nens in (0, 1):
@@ -960,7 +964,7 @@ def worker(args):
         roofline, kernels, kernel_rooflines = measure_roofline(job, args, pkey)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args.config)
         except Exception as e:   # the baseline is a reported extra; never fail the bench line for it
@@ -973,9 +977,9 @@ def worker(args):
     job.close()
     del job
 
-    # ---- the other single-GPU configurations, same procedure, fewer steps (default N=1 run only)
+    # ---- the other single-GPU configurations, same procedure, fewer steps (--full, C2 at its own nens on N=1 only)
     others = None
-    if world == 1 and args.config == "c2" and args.nens == 0 and not args.no_other_configs and not args.limiter:
+    if args.full and world == 1 and args.config == "c2" and args.nens == 0 and not args.no_other_configs and not args.limiter:
         others = {}
 
         def run_other(key, cfg, nens=0, limiter=0, steps=10, note=None, profile=None, warmup=1, perens=False):
@@ -1094,10 +1098,13 @@ def build_parser():
     ap.add_argument("--fold", default="auto", choices=("auto", "on", "off"),
                     help="3-D member-lane stage: the z sweep stores the y+z part of the state's divergence (on) or its own differences (off)")
     ap.add_argument("--detail", default="bench_detail.json", help="file (beside bench.py) that receives the full measurement object")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: per-kernel HIP-event passes "
+                         "(roofline, kernel_rooflines), the CPU baseline, the other configurations and the coupler modules")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-worker", default="", help=argparse.SUPPRESS)
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the per-kernel passes")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the other configurations and module timings")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="write the fields the last timed step computed to DIR/<name>.npy (float64; a fixed, seeded sample when large)")
     return ap

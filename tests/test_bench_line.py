@@ -3,14 +3,16 @@ parses that line; round 4's 32 KB object was recorded as `parsed: null`), the me
 quoted on, `roofline` and `cpu_baseline` objects, self-consistent numbers; everything else is in the detail file beside bench.py.
 
 GPU (-m gpu): `bench.py` is RUN in a child process and what it prints is validated --
-  * once with the DRIVER's command shape (`--gpus 1 --steps 2 --warmup 1`, nothing disabled: CPU baseline, other configurations,
-    module timings), which is the line that was too long in round 4;
-  * the fast variants (one step, no CPU baseline, no other configs): default, small ensemble, C++ launcher.
+  * the driver's plain command (`--gpus 1 --steps 2 --warmup 1`): the headline figure alone, set up and printed in seconds;
+  * once with `--full` and nothing disabled (CPU baseline, other configurations, module timings), which is the line that was too
+    long in round 4;
+  * the fast variants (one step, no CPU baseline, no other configs): default and small ensemble with `--full`, C++ launcher.
 Static (runs anywhere): the committed line + detail object of the round."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -86,8 +88,8 @@ def _run_bench(*extra):
 
 @pytest.mark.gpu
 def test_bench_py_the_drivers_command_prints_a_parseable_line():
-    """`python3 bench.py --gpus 1 --steps K --warmup W` with NOTHING disabled: the command whose output the driver records"""
-    d, full = _run(["--gpus", "1", "--steps", "2", "--warmup", "1"], "bench_detail_test.json")
+    """`python3 bench.py --gpus 1 --steps K --warmup W --full` with NOTHING disabled: the longest line the benchmark prints"""
+    d, full = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full"], "bench_detail_test.json")
     _check_contract(d)
     assert d["steps"] == 2 and d["warmup"] == 1
     c = d["cpu_baseline"]
@@ -116,8 +118,22 @@ def test_bench_py_the_drivers_command_prints_a_parseable_line():
 
 
 @pytest.mark.gpu
+def test_bench_py_plain_run_measures_the_headline_alone():
+    """`python3 bench.py --gpus 1 --steps K --warmup W`: set-up, warm-up, the timed steps and the line -- no un-timed pass, and at most
+    30 s of the whole run outside its K + W steps"""
+    t0 = time.monotonic()
+    d, full = _run(["--gpus", "1", "--steps", "2", "--warmup", "1"], "bench_detail_test.json")
+    wall = time.monotonic() - t0
+    _check_contract(d, need_roofline=False)
+    assert d["steps"] == 2 and d["warmup"] == 1
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "other" not in d
+    assert full["kernels"] == {} and full["kernel_rooflines"] == [] and full["other_configs"] is None
+    assert wall - (d["steps"] + d["warmup"]) * d["ms_per_step"] * 1e-3 < 30.0, (wall, d["ms_per_step"])
+
+
+@pytest.mark.gpu
 def test_bench_py_runs_and_prints_a_valid_line():
-    d, full = _run_bench()
+    d, full = _run_bench("--full")
     _check_contract(d)
     assert d["steps"] == 1 and d["warmup"] == 0 and d["cpu_baseline"] is None and "other" not in d
     names = [k["kernel"] for k in full["kernel_rooflines"]]
@@ -128,7 +144,7 @@ def test_bench_py_runs_and_prints_a_valid_line():
 
 @pytest.mark.gpu
 def test_bench_py_small_ensemble_line_uses_flat_lanes_and_tiles():
-    d, full = _run_bench("--nens", "2")
+    d, full = _run_bench("--full", "--nens", "2")
     _check_contract(d, nens_per_gpu=2)
     m = full["config"]["lane_mapping"]
     assert m["yz_flat"] and m["x_tiles"] and m["flat_cells"] and d["config"]["lanes"] == "flat+xtile-shfl"      # (2 x 32 lanes: a line is one wavefront)
@@ -201,6 +217,11 @@ def test_bench_py_refuses_zero_steps():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
     assert _bench_module().parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
+
+
+def test_full_is_off_by_default():
+    b = _bench_module()
+    assert b.parse_args([]).full is False and b.parse_args(["--full"]).full is True
 
 
 def test_compact_line_of_a_large_detail_object_stays_below_the_limit():

@@ -3,7 +3,7 @@
 
   tools/ab.py [--rounds R] [--out FILE] --common "<bench.py args shared by all>" --variant name="<extra args>" [--variant ...]
 
-Every run is `python bench.py <common> <extra> --no-cpu-baseline --no-other-configs`; printed per variant: cell-updates/s of every round,
+Every run is `python bench.py <common> <extra> --full --no-cpu-baseline --no-other-configs`; printed per variant: cell-updates/s of every round,
 the median, and the stage kernels' ms per stage of the last round (HIP events; omitted with --no-kernel-timing in <common>).
 Replaces the one-off tools/exp_*.sh scripts of rounds 2-4 (each was this loop with the variants written out)."""
 import argparse
@@ -37,7 +37,7 @@ def main():
     for r in range(a.rounds):
         for name, extra in variants:
             cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + shlex.split(a.common) + shlex.split(extra) + [
-                "--no-cpu-baseline", "--no-other-configs", "--detail", detail]
+                "--full", "--no-cpu-baseline", "--no-other-configs", "--detail", detail]
             p = subprocess.run(cmd, capture_output=True, text=True)
             if p.returncode:
                 print("%s: FAILED: %s" % (name, p.stderr[-500:]))

@@ -9,10 +9,10 @@ set -e
 for r in 1 2 3; do
   for v in base new; do
     cp pam_amd/libpam_amd_awfl_$v.so pam_amd/libpam_amd_awfl.so
-    python bench.py $ARGS --no-cpu-baseline --no-other-configs --detail gpurun_out/abso_$v.json > /dev/null 2>&1
+    python bench.py $ARGS --full --no-cpu-baseline --no-other-configs --detail bench_detail_abso_$v.json > /dev/null 2>&1
     python - <<PY
 import json
-d=json.load(open("gpurun_out/abso_$v.json"))
+d=json.load(open("bench_detail_abso_$v.json"))
 print("round $r %-5s %.4f G  %s" % ("$v", d["value"]/1e9, " ".join("%s=%.3f"%(k["kernel"].replace("awfl_","").replace("_kernel",""),k["ms_per_stage"]) for k in d["kernel_rooflines"])))
 PY
   done

@@ -1,10 +1,10 @@
 #!/bin/bash
-# Run the plain bench under the kernel tracer until the per-member C4 shard (or C2 at 128 members) shows its slow mode; keep that run's trace.
+# Run the bench with --full under the kernel tracer until the per-member C4 shard (or C2 at 128 members) shows its slow mode; keep that run's trace.
 # usage (through gpurun, from the repo root): bash tools/probe/catch_slow_mode.sh [max runs]
 R=$PWD; mkdir -p $R/gpurun_out; cd /tmp && export TMPDIR=/tmp
 for i in $(seq 1 ${1:-6}); do
   rm -rf /tmp/kt_slow
-  timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_slow -o t -- python3 $R/bench.py --detail /tmp/slow_detail.json > /tmp/slow_line.json 2>/dev/null || { echo "run $i failed"; exit 1; }
+  timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_slow -o t -- python3 $R/bench.py --full --detail /tmp/slow_detail.json > /tmp/slow_line.json 2>/dev/null || { echo "run $i failed"; exit 1; }
   python3 - <<PY
 import json
 d=json.load(open("/tmp/slow_line.json")); o=d["other"]
