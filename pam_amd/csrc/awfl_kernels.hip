@@ -1129,8 +1129,6 @@ struct pam_amd_awfl {
   bool timing = false;
   int span_override = 0;       // 0: automatic flux-kernel span
   int chunks_requested = 0;    // 0: automatic
-  bool use_priorities = true;  // flux streams get the device's highest stream priority (see Chunk)
-  bool interleave_xy = true;
   // timeStep replayed from a captured HIP graph (launch-bound small ensembles; pam_amd_awfl_set_graph_replay)
   struct GraphEntry {
     std::vector<const void *> ptrs;   // the coupler arrays the step reads and writes
@@ -1178,8 +1176,7 @@ struct pam_amd_awfl {
   bool ftile_parts = false;              // resolved
   int ncu = 0;                           // compute units of the handle's device
   XTileGeom xg;
-  bool fused = false;          // fused x-sweep + state update (needs the third state buffer prim2)
-  bool fused_supported = false;
+  bool fused = true;           // fused x-sweep + state update (needs the third state buffer prim2)
   size_t flux_lds_floor = 0;   // tuning: dynamic LDS requested per flux workgroup (the kernel uses none: a residency cap per CU)
   long long want_units = 3072, two_phase_below = 8192, split_below = 8192;   // launch-shape thresholds (pam_amd_awfl_set_handle_launch_tuning)
   int tracers_per_wave = 0;    // further tracers swept by one wavefront of the separately launched x tracer sweeps: 0 automatic, 1, 2, 4
@@ -1377,7 +1374,7 @@ int launch_flux(pam_amd_awfl *h, const double *prim, EnsRange r, hipStream_t s, 
   G.nbx = (G.nux + FLUX_WAVES - 1) / FLUX_WAVES; G.nby = (G.nuy + FLUX_WAVES - 1) / FLUX_WAVES;
   G.nbz = (G.nuz + FLUX_WAVES - 1) / FLUX_WAVES;
   G.nbx_l = G.nby_l = 0;
-  if (!two_phase && h->interleave_xy && !P.sim2d && G.nux > 0 && G.nuy > 0 && G.nux % (FLUX_WAVES * P.nz) == 0 && G.nuy % (FLUX_WAVES * P.nz) == 0) {
+  if (!two_phase && !P.sim2d && G.nux > 0 && G.nuy > 0 && G.nux % (FLUX_WAVES * P.nz) == 0 && G.nuy % (FLUX_WAVES * P.nz) == 0) {
     G.nbx_l = G.nbx / P.nz;
     G.nby_l = G.nby / P.nz;
   }
@@ -1845,9 +1842,6 @@ void choose_flux_tiles(pam_amd_awfl *h) {
 // four loads per cell from the HBM-bound x-sweep (3.59 -> 3.31 ms at C2) into the FP64-issue-bound flux kernel, which pays the same
 // back (4.36 -> 4.59 ms for the y and z launches together): C2 2.555 -> 2.564 G, 256 members 2.548 -> 2.537, 128 members 2.466 ->
 // 2.445, the 3-D four-tracer grid at 256 members 1.416 -> 1.381.
-#ifndef PAMA_FOLD_DEFAULT
-#define PAMA_FOLD_DEFAULT 0
-#endif
 // Lane mapping of the fused stage (decided from the WHOLE ensemble; results never depend on it):
 //   flat   the y/z sweeps take 64 consecutive (x, member) items per wavefront (flat_lane) instead of 64 members of one line
 //   xtile  the x direction runs as tile kernels (a lane per cell) instead of sweeps (a wavefront per line span)
@@ -1872,7 +1866,7 @@ void resolve_lane_mapping(pam_amd_awfl *h) {
   P.flat_cells = (h->lane_mode != 1 && (long long)P.nx * P.nens < 256 && P.ncell < (1ll << 31)) ? 1 : 0;
   // the y differences of the state folded into what the z sweep stores (3-D, member-lane sweeps in y, z AND x: the tile kernels form
   // the y+z part of the divergence themselves, with the same yz_divergence -- same bits either way)
-  P.yz_fold = (!P.sim2d && !h->flat && !h->xtile && (h->fold_mode == 2 || (h->fold_mode == 0 && PAMA_FOLD_DEFAULT))) ? 1 : 0;
+  P.yz_fold = (!P.sim2d && !h->flat && !h->xtile && h->fold_mode == 2) ? 1 : 0;
   // the y/z fluxes of a flat-lane stage: ONE tile kernel (a lane per cell) while the whole ensemble is below ~2.6e5 cells -- a flat-lane
   // sweep is then a handful of wavefronts walking their lines serially -- and flat-lane sweeps above (they read every input once and
   // build no halo rows; measured on MI355X, 32x32x60: 1 member 67 -> 20 us per stage, 8 members 85 -> 82, 32 members 184 -> 320)
@@ -1978,7 +1972,7 @@ int build_chunks(pam_amd_awfl *h) {
     for (auto &c : h->chunks) {
       HIP_TRY(shared_stream(h->device, prio_low, 0, ordinal, &c.stream));
       if (one_stream_per_range) c.fstream = c.stream;
-      else HIP_TRY(shared_stream(h->device, h->use_priorities ? prio_high : prio_low, 1, ordinal, &c.fstream));
+      else HIP_TRY(shared_stream(h->device, prio_high, 1, ordinal, &c.fstream));
       ordinal++;
       HIP_TRY(hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
       HIP_TRY(hipEventCreateWithFlags(&c.flux_done, hipEventDisableTiming));
@@ -2017,6 +2011,282 @@ void free_all(pam_amd_awfl *h) {
   h->pow_tab = nullptr;
   if (h->fct_flags) (void)hipFree(h->fct_flags);
   h->fct_flags = nullptr;
+}
+
+// A mode setter's request: the new values go in, the lane mapping is resolved, and when the resolved mapping does not honour the request
+// the old values go back in (resolved again) and the setter fails with `msg`.
+template <class Honoured>
+int set_resolved(pam_amd_awfl *h, std::initializer_list<std::pair<int *, int>> modes, Honoured honoured, const char *msg) {
+  std::vector<std::pair<int *, int>> m(modes);
+  for (auto &p : m) std::swap(*p.first, p.second);     // (the pairs keep the old values)
+  resolve_lane_mapping(h);
+  if (honoured()) return PAM_AMD_OK;
+  for (auto &p : m) std::swap(*p.first, p.second);
+  resolve_lane_mapping(h);
+  return fail(PAM_AMD_EINVAL, msg);
+}
+
+// ------------------------------------------------------------------------------------------------ one timeStep, phase by phase
+// What one time_step call carries from phase to phase.
+struct StepCall {
+  const pam_amd_awfl_fields_t *f;
+  double crm_dt, dt_dyn;    // dt_dyn: the caller's hint or the CFL minimum; the length of a sub-step once settle_cycles has run
+  int ncycles;
+  bool dt_pending;          // the CFL read-back is awaited behind the conversion (enqueue_step), not before the step
+  bool forked;              // several member ranges: forked from the caller's stream and joined back into it
+  int *ncycles_out; double *dt_dyn_out;
+};
+
+// the number of cycles and their length from the dynamics step (Dycore.h:142-145)
+int settle_cycles(StepCall &s) {
+  if (!(s.dt_dyn > 0) || !std::isfinite(s.dt_dyn))
+    return fail(PAM_AMD_EINVAL, "time_step: CFL time step is not positive/finite (NaN or non-physical coupler state)");
+  s.ncycles = (int)std::ceil(s.crm_dt / s.dt_dyn);
+  s.dt_dyn = s.crm_dt / s.ncycles;
+  if (s.ncycles_out) *s.ncycles_out = s.ncycles;
+  if (s.dt_dyn_out) *s.dt_dyn_out = s.dt_dyn;
+  return PAM_AMD_OK;
+}
+
+// Dycore.h:141-145: the dynamics step comes from the COUPLER fields of every member (before any conversion).  Without a hint it comes from
+// a reduction and a read-back.  A step of ONE member range issued eagerly queues the reduction, then the conversion coupler -> dycore
+// (which does not depend on it), and only then waits for the 8 bytes (dt_pending): the device converts while the host wakes up and issues
+// the stages (A/B on one box: 32x32x60 with one member 0.669 -> 0.687 G, the reference's 250x1x50 input shape 0.1405 -> 0.1525 G).  Not
+// with several ranges: their conversions then start together instead of one host launch apart and the ranges run in lock-step (one GPU's
+// shard of C4: 0.894 -> 0.883 G; started one conversion apart: 0.871).  A replayed graph needs the cycle count before it is chosen: there
+// the wait comes first, too.
+int plan_step(pam_amd_awfl *h, StepCall &s) {
+  if (!(s.dt_dyn > 0)) {
+    if (int rc = launch_cfl(h, s.f, 0.8, h->chunks.size() <= 1)) return rc;
+    if (h->graph_mode != 2 && h->chunks.size() <= 1) s.dt_pending = true;
+    else if (int rc = finish_cfl(h, &s.dt_dyn)) return rc;
+  }
+  return s.dt_pending ? PAM_AMD_OK : settle_cycles(s);
+}
+
+// the range streams start after everything already queued on the caller's stream
+int fork_ranges(pam_amd_awfl *h) {
+  HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
+  for (auto &c : h->chunks) HIP_TRY(hipStreamWaitEvent(c.stream, h->ev_fork, 0));
+  return PAM_AMD_OK;
+}
+
+// The caller's stream continues after every range (and the shared compute stream, which every range stream follows or is followed by
+// through the stage's events) has finished.  Called whatever enqueue_step returned (`rc`), so that the caller's stream stays ordered
+// after the work already queued on the range streams; the first failure is reported.
+int join_ranges(pam_amd_awfl *h, int rc) {
+  int jrc = PAM_AMD_OK;
+  auto join_try = [&](hipError_t e) { if (e != hipSuccess && jrc == PAM_AMD_OK) jrc = fail(PAM_AMD_ENOGPU, std::string("time_step join: ") + hipGetErrorString(e)); };
+  for (auto &c : h->chunks) {
+    if (c.fstream && c.fstream != c.stream) {       // flux / compute streams: order them into the range stream first
+      join_try(hipEventRecord(c.flux_done, c.fstream));
+      join_try(hipStreamWaitEvent(c.stream, c.flux_done, 0));
+    }
+    join_try(hipEventRecord(c.done, c.stream));
+    join_try(hipStreamWaitEvent(h->stream, c.done, 0));
+  }
+  return rc == PAM_AMD_OK ? jrc : rc;
+}
+
+// f(std::integral_constant<int, st>()): the stage number of a launch as the template argument of its kernels
+template <class F>
+int by_stage(int st, F &&f) {
+  switch (st) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    default: return f(std::integral_constant<int, 3>());
+  }
+}
+
+// One tendency stage of one member range: its number, input, sub-step start (base) and output buffers (the output differs from both in
+// the fused stage), the sub-step length and the stage's share of it.
+struct StageArgs { int st; const double *in, *base; double *out; double dt_dyn, dt_stage; };
+
+// Fused stage: flux (y,z) -> x-sweeps + update of the state and of every tracer -> pressure pass + tracer fix-up pass.  The two polynomial
+// kernels run on `cs`: the range's own stream when it is alone or independent (every range runs its whole stage on its own stream -- no
+// events between ranges: launches that do not fill the chip overlap their ramp-up and drain phases with another range's kernels), else
+// chunk 0's high-priority compute stream, shared by all ranges, range after range; the range's tail then runs on its own stream beside the
+// NEXT range's flux kernel (the x-sweep is both VALU- and HBM-heavy and gets the chip to itself).
+int stage_fused(pam_amd_awfl *h, Chunk &c, hipStream_t cs, const StageArgs &a, bool forked, bool indep) {
+  int rc;
+  if (forked && !indep) HIP_TRY(hipStreamWaitEvent(cs, c.upd_done, 0));         // this range's previous tail / init
+  if ((rc = launch_flux(h, a.in, c.r, cs, 6, true))) return rc;
+  const bool allow = (cs == c.stream) && tail_fusable(h);      // (the tail as part of the phase-2 launch)
+  bool fuse_tail = false;
+  if ((rc = by_stage(a.st, [&](auto S) { return launch_xupd<S()>(h, a.in, a.base, a.out, a.dt_dyn, a.dt_stage, c.r, cs, allow, &fuse_tail); })))
+    return rc;
+  if (forked && !indep) {
+    HIP_TRY(hipEventRecord(c.flux_done, cs));
+    HIP_TRY(hipStreamWaitEvent(c.stream, c.flux_done, 0));
+  }
+  if (!fuse_tail && (rc = by_stage(a.st, [&](auto S) { return launch_tail<S()>(h, a.in, a.base, a.out, a.dt_dyn, c.r, c.stream); })))
+    return rc;
+  if (forked) HIP_TRY(hipEventRecord(c.upd_done, c.stream));
+  return PAM_AMD_OK;
+}
+
+// Three-kernel stage: flux (x,y,z) -> FCT -> update.  With several ranges the flux kernels run on each range's high-priority flux stream
+// and are chained ACROSS ranges by events (A1 -> B1 -> C1 -> A2 ...; `prev_flux` is the flux kernel launched just before): two VALU-bound
+// flux kernels never share the chip, and a range's HBM-bound FCT/update kernels run on its own stream beside the NEXT range's flux kernel.
+int stage_three_kernel(pam_amd_awfl *h, Chunk &c, const StageArgs &a, bool forked, hipEvent_t &prev_flux) {
+  int rc;
+  if (forked) {
+    HIP_TRY(hipStreamWaitEvent(c.fstream, c.upd_done, 0));               // this range's previous update / init
+    if (prev_flux) HIP_TRY(hipStreamWaitEvent(c.fstream, prev_flux, 0));
+  }
+  if ((rc = launch_flux(h, a.in, c.r, c.fstream, 7))) return rc;
+  if (forked) {
+    HIP_TRY(hipEventRecord(c.flux_done, c.fstream));
+    prev_flux = c.flux_done;
+    HIP_TRY(hipStreamWaitEvent(c.stream, c.flux_done, 0));
+  }
+  if ((rc = launch_fct(h, a.dt_stage, c.r, c.stream))) return rc;
+  if ((rc = by_stage(a.st, [&](auto S) { return launch_update<S()>(h, a.in, a.base, a.out, a.dt_dyn, c.r, c.stream); })))
+    return rc;
+  if (forked) HIP_TRY(hipEventRecord(c.upd_done, c.stream));
+  return PAM_AMD_OK;
+}
+
+// one tendency stage of one range with whichever stage structure is selected (time_step and pam_amd_awfl_debug_stage)
+int run_stage(pam_amd_awfl *h, Chunk &c, const StageArgs &a, bool forked, hipEvent_t &prev_flux) {
+  if (!h->fused) return stage_three_kernel(h, c, a, forked, prev_flux);
+  const bool indep = forked && h->independent_ranges;
+  return stage_fused(h, c, forked && !indep ? h->chunks[0].fstream : c.stream, a, forked, indep);
+}
+
+// The three stages of an SSPRK3 sub-step (Dycore.h:156-221) over the buffers A (the sub-step's start: prim0), B (prim1) and C (prim2):
+// input, base, output and the stage's share of dt_dyn.  Fused: nothing may be updated in place along a periodic line, so the buffers
+// rotate A -> B -> C -> B and the new state B becomes prim0.  Three-kernel: the pointwise update kernel updates stages 2 and 3 in place.
+struct StageSpec { int in, base, out; double dt_factor; };
+constexpr StageSpec kFusedStages[3] = {{0, 0, 1, 1.0}, {1, 0, 2, 1.0 / 4.0}, {2, 0, 1, 2.0 / 3.0}};
+constexpr StageSpec kThreeKernelStages[3] = {{0, 0, 1, 1.0}, {1, 0, 1, 1.0 / 4.0}, {1, 0, 0, 2.0 / 3.0}};
+
+// One whole step: launches are issued stage by stage, round-robin over the ranges.
+int enqueue_step(pam_amd_awfl *h, StepCall &s) {
+  int rc;
+  // Dycore.h:128-134 (per range)
+  for (auto &c : h->chunks) {
+    if ((rc = launch_init_prim(h, s.f, nullptr, !h->P.grav_balance, c.r, c.stream))) return rc;
+    if (h->debug_mass && (rc = launch_mass(h, 0, c.r, c.stream))) return rc;      // Dycore.h:136-138 (after the clipping of :130-134)
+    if (s.forked) HIP_TRY(hipEventRecord(c.upd_done, c.stream));
+  }
+  if (s.dt_pending) {
+    s.dt_pending = false;
+    if ((rc = finish_cfl(h, &s.dt_dyn))) return rc;
+    if ((rc = settle_cycles(s))) return rc;
+  }
+  const StageSpec *spec = h->fused ? kFusedStages : kThreeKernelStages;
+  hipEvent_t prev_flux = nullptr;
+  for (int ic = 0; ic < s.ncycles; ic++) {
+    double *const buf[3] = {h->prim0, h->prim1, h->prim2};
+    for (int st = 1; st <= 3; st++) {
+      const StageSpec &t = spec[st - 1];
+      const StageArgs a{st, buf[t.in], buf[t.base], buf[t.out], s.dt_dyn, t.dt_factor * s.dt_dyn};
+      if ((rc = next_fct_stage(h))) return rc;
+      for (auto &c : h->chunks)
+        if ((rc = run_stage(h, c, a, s.forked, prev_flux))) return rc;
+    }
+    if (spec[2].out == 1) std::swap(h->prim0, h->prim1);     // (the new state is in B)
+  }
+  // Dycore.h:224-251 (PAM_DEBUG), then :254 (per range)
+  for (auto &c : h->chunks) {
+    if (h->debug_mass) {
+      if (h->fault.armed && h->fault.e >= c.r.e0 && h->fault.e < c.r.e0 + c.r.ne) {
+        hipLaunchKernelGGL(awfl_poke_kernel, dim3(1), dim3(1), 0, c.stream, h->P, h->prim0, h->prim0, h->seed, h->fault.ivar, h->fault.k,
+                           h->fault.j, h->fault.i, h->fault.e, h->fault.factor);
+        HIP_TRY(hipGetLastError());
+        h->fault.armed = false;
+      }
+      if ((rc = launch_mass(h, 1, c.r, c.stream))) return rc;
+    }
+    if ((rc = launch_finalize(h, s.f, c.r, c.stream))) return rc;
+  }
+  return PAM_AMD_OK;
+}
+
+// Launch-bound ensembles: the whole step (coupler -> dycore, 3 x ncycles stages, dycore -> coupler) is captured ONCE into a HIP graph on an
+// internal stream and replayed; the only thing that changes from one step to the next -- the stage number the FCT flags are compared
+// with -- is a device word set in front of every replay (FctRows::seq_base).
+// OFF unless asked for: measured on MI355X / ROCm 7.2 (round 4, 20 steps each) a replayed step is SLOWER than the same launches issued
+// eagerly -- 32x32x60 with one member 0.907 -> 1.011 ms, two 1.134 -> 1.249, eight 3.41 -> 3.58, the 250x1x50 shape 0.364 -> 0.425 ms: the
+// gaps between DEPENDENT kernels (~2.3 us each) are the same inside a graph, and the fork / join events cost more than the host-side launch
+// calls they replace (the host is not the bottleneck: launches are issued well ahead of the device).
+int replay_step(pam_amd_awfl *h, StepCall &s) {
+  const int nstages = 3 * s.ncycles;
+  if (h->fct_seq > 0x7fffffff - nstages - 4) {      // the wrap of the stage number cannot happen inside a graph
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(h->fct_flags, 0, (h->n_fct_flags + h->n_fct_any + h->n_fct_lines) * sizeof(int)));
+    h->fct_seq = 0;
+  }
+  std::vector<const void *> ptrs = {s.f->density_dry, s.f->uvel, s.f->vvel, s.f->wvel, s.f->temp};
+  for (int t = 0; t < h->P.nt; t++) ptrs.push_back(s.f->tracers[t]);
+  pam_amd_awfl::GraphEntry *entry = nullptr;
+  for (auto &g : h->graphs)
+    if (g.gen == h->graph_gen && g.ncycles == s.ncycles && g.dt_dyn == s.dt_dyn && g.prim0_before == h->prim0 && g.ptrs == ptrs) entry = &g;
+  HIP_TRY(hipEventRecord(h->g_fork, h->stream));
+  HIP_TRY(hipStreamWaitEvent(h->gstream, h->g_fork, 0));
+  int seq0 = h->fct_seq;
+  if (!entry) {
+    if (h->graphs.size() >= 8) {                      // (a few shapes of a step recur: both buffer parities x the cycle counts met)
+      HIP_TRY(hipStreamSynchronize(h->gstream));      // an earlier replay may still be running one of them
+      for (auto &g : h->graphs) (void)hipGraphExecDestroy(g.exec);
+      h->graphs.clear();
+    }
+    pam_amd_awfl::GraphEntry e;
+    e.ptrs = ptrs; e.ncycles = s.ncycles; e.dt_dyn = s.dt_dyn; e.prim0_before = h->prim0; e.gen = h->graph_gen; e.nstages = nstages;
+    Chunk &c0 = h->chunks[0];
+    const hipStream_t s_keep = c0.stream, f_keep = c0.fstream;
+    c0.stream = c0.fstream = h->gstream;
+    h->capturing = true;
+    h->capture_seq0 = h->fct_seq;
+    // what the capture advances on the host side (stage number, buffer rotation) is put back when no graph comes out of it: no
+    // kernel has run then, and the next step must start from the same buffers
+    const int seq_keep = h->fct_seq;
+    double *const p0_keep = h->prim0, *const p1_keep = h->prim1;
+    // (test hook: pam_amd_awfl_debug_fail_next_capture makes one of the three capture calls "fail")
+    const int inject = h->fail_next_capture;
+    h->fail_next_capture = 0;
+    int rc = PAM_AMD_OK;
+    hipError_t cerr = (inject == 1) ? hipErrorUnknown : hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal);
+    if (cerr == hipSuccess) rc = enqueue_step(h, s);
+    hipGraph_t graph = nullptr;
+    hipError_t eerr = (cerr == hipSuccess) ? hipStreamEndCapture(h->gstream, &graph) : cerr;
+    if (inject == 2 && eerr == hipSuccess) eerr = hipErrorUnknown;
+    h->capturing = false;
+    c0.stream = s_keep; c0.fstream = f_keep;
+    // what failed: the launches themselves (rc: a bad argument, a HIP error of a launch -- the same call would fail eagerly too) or
+    // the capture machinery (BeginCapture / EndCapture / Instantiate: the step itself is fine)
+    std::string why;
+    if (rc == PAM_AMD_OK && eerr != hipSuccess) why = std::string("graph capture: ") + hipGetErrorString(eerr);
+    if (rc == PAM_AMD_OK && why.empty() &&
+        (inject == 3 || hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0) != hipSuccess)) why = "hipGraphInstantiate failed";
+    if (graph) (void)hipGraphDestroy(graph);
+    if (rc != PAM_AMD_OK || !why.empty()) {
+      h->fct_seq = seq_keep; h->prim0 = p0_keep; h->prim1 = p1_keep;
+      // the caller's stream was forked into gstream above: join it again
+      (void)hipEventRecord(h->g_join, h->gstream);
+      (void)hipStreamWaitEvent(h->stream, h->g_join, 0);
+      if (rc != PAM_AMD_OK) return rc;         // (its message is in last_error; nothing ran: the launches were only recorded)
+      // the capture machinery failed: drop the runtime's sticky error, run the step eagerly, say so, and stop capturing on this handle
+      (void)hipGetLastError();
+      h->graph_mode = 1;
+      const int erc = enqueue_step(h, s);
+      if (erc == PAM_AMD_OK) g_last_error = "warning: time_step: " + why + "; the step ran eagerly and graph replay is switched off for this handle";
+      return erc;
+    }
+    e.prim0_after = h->prim0; e.prim1_after = h->prim1;       // (the capture has walked the buffer rotation on the host side)
+    h->graphs.push_back(e);
+    entry = &h->graphs.back();
+  } else {
+    h->fct_seq += nstages;
+    h->prim0 = entry->prim0_after;
+    h->prim1 = entry->prim1_after;
+  }
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->seq_dev, seq0, 1, h->gstream));
+  HIP_TRY(hipGraphLaunch(entry->exec, h->gstream));
+  HIP_TRY(hipEventRecord(h->g_join, h->gstream));
+  HIP_TRY(hipStreamWaitEvent(h->stream, h->g_join, 0));
+  return PAM_AMD_OK;
 }
 
 }  // namespace
@@ -2109,9 +2379,7 @@ int pam_amd_awfl_init(const pam_amd_awfl_config_t *cfg, pam_amd_awfl_t **out) {
   INIT_TRY(hipMalloc(&h->prim0, h->n_prim * 8));
   INIT_TRY(hipMalloc(&h->prim1, h->n_prim * 8));
   // the fused x-sweep writes into a third buffer (nothing may be updated in place along a periodic line)
-  h->fused_supported = true;
-  h->fused = h->fused_supported;
-  if (h->fused_supported) INIT_TRY(hipMalloc(&h->prim2, h->n_prim * 8));
+  INIT_TRY(hipMalloc(&h->prim2, h->n_prim * 8));
   INIT_TRY(hipMalloc(&h->flux_x, h->n_flux_xy * 8));
   INIT_TRY(hipMalloc(&h->flux_y, (P.sim2d ? 8 : h->n_flux_xy) * 8));
   INIT_TRY(hipMalloc(&h->flux_z, h->n_flux_z * 8));
@@ -2359,256 +2627,12 @@ int pam_amd_awfl_time_step(pam_amd_awfl_t *h, const pam_amd_awfl_fields_t *field
   TracerPtrs tp_check;
   int rc = make_tracer_ptrs(h, fields, tp_check);
   if (rc) return rc;
-  // Dycore.h:141-145: the dynamics step comes from the COUPLER fields of every member (before any conversion)
-  double dt_dyn = dt_dyn_hint;
-  int ncycles = 0;
-  // the number of cycles and their length from the dynamics step (Dycore.h:142-145)
-  auto settle_cycles = [&]() -> int {
-    if (!(dt_dyn > 0) || !std::isfinite(dt_dyn))
-      return fail(PAM_AMD_EINVAL, "time_step: CFL time step is not positive/finite (NaN or non-physical coupler state)");
-    ncycles = (int)std::ceil(crm_dt / dt_dyn);
-    dt_dyn = crm_dt / ncycles;
-    if (ncycles_out) *ncycles_out = ncycles;
-    if (dt_dyn_out) *dt_dyn_out = dt_dyn;
-    return PAM_AMD_OK;
-  };
-  // Without a hint the step comes from a reduction and a read-back.  A step of ONE member range issued eagerly queues the reduction,
-  // then the conversion coupler -> dycore (which does not depend on it), and only then waits for the 8 bytes: the device converts
-  // while the host wakes up and issues the stages (A/B on one box: 32x32x60 with one member 0.669 -> 0.687 G, the reference's
-  // 250x1x50 input shape 0.1405 -> 0.1525 G).  Not with several ranges: their conversions then start together instead of one host
-  // launch apart and the ranges run in lock-step (one GPU's shard of C4: 0.894 -> 0.883 G; started one conversion apart: 0.871).
-  // A replayed graph needs the cycle count before it is chosen: there the wait comes first, too.
-  const bool graph_on = h->graph_mode == 2;
-  bool dt_pending = false;
-  if (!(dt_dyn > 0)) {
-    if ((rc = launch_cfl(h, fields, 0.8, h->chunks.size() <= 1))) return rc;
-    if (graph_on || h->chunks.size() > 1) {
-      if ((rc = finish_cfl(h, &dt_dyn))) return rc;
-    } else {
-      dt_pending = true;
-    }
-  }
-  if (!dt_pending && (rc = settle_cycles())) return rc;
-  const bool forked = h->chunks.size() > 1;
-  if (forked) {   // chunk streams start after everything already queued on the caller's stream
-    HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
-    for (auto &c : h->chunks) HIP_TRY(hipStreamWaitEvent(c.stream, h->ev_fork, 0));
-  }
-  // Everything between fork and join runs in a lambda: whatever fails in there (a launch, an event call), the join below
-  // still happens, so that the caller's stream stays ordered after the work already queued on the internal streams.
-  auto enqueue = [&]() -> int {
-    int rc = PAM_AMD_OK;
-    // Dycore.h:128-134 (per chunk)
-    for (auto &c : h->chunks) {
-      if ((rc = launch_init_prim(h, fields, nullptr, !h->P.grav_balance, c.r, c.stream))) return rc;
-      if (h->debug_mass && (rc = launch_mass(h, 0, c.r, c.stream))) return rc;      // Dycore.h:136-138 (after the clipping of :130-134)
-      if (forked) HIP_TRY(hipEventRecord(c.upd_done, c.stream));
-    }
-    if (dt_pending) {
-      dt_pending = false;
-      if ((rc = finish_cfl(h, &dt_dyn))) return rc;
-      if ((rc = settle_cycles())) return rc;
-    }
-    // Launches are issued stage by stage, round-robin over the chunks.  With several chunks:
-    //  * flux kernels run on each chunk's high-priority flux stream and are chained ACROSS chunks by events
-    //    (A1 -> B1 -> C1 -> A2 ...): two VALU-bound flux kernels never share the chip;
-    //  * a chunk's HBM-bound FCT/update kernels run on its normal-priority stream beside the NEXT chunk's flux kernel.
-    hipEvent_t prev_flux = nullptr;
-    // One tendency stage of one chunk.  Unfused: flux (x,y,z) -> FCT -> update.  Fused: flux (y,z) -> x-sweeps + update of the
-    // state and of every tracer -> pressure pass + tracer fix-up pass (pout differs from pin and p0).
-    auto stage = [&](Chunk &c, int st, const double *pin, const double *p0, double *pout, double dt_stage) -> int {
-      int r2;
-      if (h->fused) {
-        // Fused stage.  The two polynomial kernels (flux y,z and the fused x-sweep) of ALL chunks run back to back on ONE
-        // high-priority compute stream, chunk after chunk; a chunk's tail (pressure pass, tracer fix-up)
-        // runs on the chunk's own stream beside the NEXT chunk's flux kernel.  The x-sweep is both VALU- and HBM-heavy and
-        // gets the chip to itself.
-        // (independent_ranges: every range runs its whole stage on its own stream -- no shared compute stream, no events between
-        // ranges: launches that do not fill the chip overlap their ramp-up and drain phases with another range's kernels)
-        const bool indep = forked && h->independent_ranges;
-        hipStream_t cs = indep ? c.stream : (forked ? h->chunks[0].fstream : c.stream);
-        if (forked && !indep) HIP_TRY(hipStreamWaitEvent(cs, c.upd_done, 0));         // this chunk's previous tail / init
-        if ((r2 = launch_flux(h, pin, c.r, cs, 6, true))) return r2;
-        const bool allow = (cs == c.stream) && tail_fusable(h);      // (the tail as part of the phase-2 launch)
-        bool fuse_tail = false;
-        if (st == 1) r2 = launch_xupd<1>(h, pin, p0, pout, dt_dyn, dt_stage, c.r, cs, allow, &fuse_tail);
-        else if (st == 2) r2 = launch_xupd<2>(h, pin, p0, pout, dt_dyn, dt_stage, c.r, cs, allow, &fuse_tail);
-        else r2 = launch_xupd<3>(h, pin, p0, pout, dt_dyn, dt_stage, c.r, cs, allow, &fuse_tail);
-        if (r2) return r2;
-        if (forked && !indep) {
-          HIP_TRY(hipEventRecord(c.flux_done, cs));
-          HIP_TRY(hipStreamWaitEvent(c.stream, c.flux_done, 0));
-        }
-        if (!fuse_tail) {
-          if (st == 1) r2 = launch_tail<1>(h, pin, p0, pout, dt_dyn, c.r, c.stream);
-          else if (st == 2) r2 = launch_tail<2>(h, pin, p0, pout, dt_dyn, c.r, c.stream);
-          else r2 = launch_tail<3>(h, pin, p0, pout, dt_dyn, c.r, c.stream);
-          if (r2) return r2;
-        }
-        if (forked) HIP_TRY(hipEventRecord(c.upd_done, c.stream));
-        return PAM_AMD_OK;
-      }
-      if (forked) {
-        HIP_TRY(hipStreamWaitEvent(c.fstream, c.upd_done, 0));               // this chunk's previous update / init
-        if (prev_flux) HIP_TRY(hipStreamWaitEvent(c.fstream, prev_flux, 0));  // the flux kernel launched just before
-      }
-      if ((r2 = launch_flux(h, pin, c.r, c.fstream, 7))) return r2;
-      if (forked) {
-        HIP_TRY(hipEventRecord(c.flux_done, c.fstream));
-        prev_flux = c.flux_done;
-        HIP_TRY(hipStreamWaitEvent(c.stream, c.flux_done, 0));
-      }
-      if ((r2 = launch_fct(h, dt_stage, c.r, c.stream))) return r2;
-      if (st == 1) r2 = launch_update<1>(h, pin, p0, pout, dt_dyn, c.r, c.stream);
-      else if (st == 2) r2 = launch_update<2>(h, pin, p0, pout, dt_dyn, c.r, c.stream);
-      else r2 = launch_update<3>(h, pin, p0, pout, dt_dyn, c.r, c.stream);
-      if (r2) return r2;
-      if (forked) HIP_TRY(hipEventRecord(c.upd_done, c.stream));
-      return PAM_AMD_OK;
-    };
-    for (int ic = 0; ic < ncycles; ic++) {
-      double *A = h->prim0, *B = h->prim1, *C = h->prim2;
-      if (h->fused) {
-        // three rotating buffers: A (sub-step start) -> B -> C -> B; the new state B becomes prim0
-        if ((rc = next_fct_stage(h))) return rc;
-        for (auto &c : h->chunks)   // stage 1 (Dycore.h:156-176)
-          if ((rc = stage(c, 1, A, A, B, dt_dyn))) return rc;
-        if ((rc = next_fct_stage(h))) return rc;
-        for (auto &c : h->chunks)   // stage 2 (Dycore.h:180-200)
-          if ((rc = stage(c, 2, B, A, C, (1.0 / 4.0) * dt_dyn))) return rc;
-        if ((rc = next_fct_stage(h))) return rc;
-        for (auto &c : h->chunks)   // stage 3 (Dycore.h:204-221)
-          if ((rc = stage(c, 3, C, A, B, (2.0 / 3.0) * dt_dyn))) return rc;
-        h->prim0 = B;
-        h->prim1 = A;
-      } else {
-        // pointwise update kernel: stage 2 and 3 update in place
-        if ((rc = next_fct_stage(h))) return rc;
-        for (auto &c : h->chunks)
-          if ((rc = stage(c, 1, A, A, B, dt_dyn))) return rc;
-        if ((rc = next_fct_stage(h))) return rc;
-        for (auto &c : h->chunks)
-          if ((rc = stage(c, 2, B, A, B, (1.0 / 4.0) * dt_dyn))) return rc;
-        if ((rc = next_fct_stage(h))) return rc;
-        for (auto &c : h->chunks)
-          if ((rc = stage(c, 3, B, A, A, (2.0 / 3.0) * dt_dyn))) return rc;
-      }
-    }
-    // Dycore.h:224-251 (PAM_DEBUG), then :254 (per chunk)
-    for (auto &c : h->chunks) {
-      if (h->debug_mass) {
-        if (h->fault.armed && h->fault.e >= c.r.e0 && h->fault.e < c.r.e0 + c.r.ne) {
-          hipLaunchKernelGGL(awfl_poke_kernel, dim3(1), dim3(1), 0, c.stream, h->P, h->prim0, h->prim0, h->seed, h->fault.ivar, h->fault.k,
-                             h->fault.j, h->fault.i, h->fault.e, h->fault.factor);
-          HIP_TRY(hipGetLastError());
-          h->fault.armed = false;
-        }
-        if ((rc = launch_mass(h, 1, c.r, c.stream))) return rc;
-      }
-      if ((rc = launch_finalize(h, fields, c.r, c.stream))) return rc;
-    }
-    return PAM_AMD_OK;
-  };
-  // Launch-bound ensembles: the whole step (coupler -> dycore, 3 x ncycles stages, dycore -> coupler) is captured ONCE into a HIP
-  // graph on an internal stream and replayed; the only thing that changes from one step to the next -- the stage number the FCT
-  // flags are compared with -- is a device word set in front of every replay (FctRows::seq_base).
-  // OFF unless asked for: measured on MI355X / ROCm 7.2 (round 4, 20 steps each) a replayed step is SLOWER than the same launches
-  // issued eagerly -- 32x32x60 with one member 0.907 -> 1.011 ms, two 1.134 -> 1.249, eight 3.41 -> 3.58, the 250x1x50 shape 0.364 ->
-  // 0.425 ms: the gaps between DEPENDENT kernels (~2.3 us each) are the same inside a graph, and the fork / join events cost more
-  // than the host-side launch calls they replace (the host is not the bottleneck: launches are issued well ahead of the device).
-  if (graph_on && h->fused && !forked && !h->timing && !h->debug_mass && h->gstream) {
-    const int nstages = 3 * ncycles;
-    if (h->fct_seq > 0x7fffffff - nstages - 4) {      // the wrap of the stage number cannot happen inside a graph
-      HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(hipMemset(h->fct_flags, 0, (h->n_fct_flags + h->n_fct_any + h->n_fct_lines) * sizeof(int)));
-      h->fct_seq = 0;
-    }
-    std::vector<const void *> ptrs = {fields->density_dry, fields->uvel, fields->vvel, fields->wvel, fields->temp};
-    for (int t = 0; t < h->P.nt; t++) ptrs.push_back(fields->tracers[t]);
-    pam_amd_awfl::GraphEntry *entry = nullptr;
-    for (auto &g : h->graphs)
-      if (g.gen == h->graph_gen && g.ncycles == ncycles && g.dt_dyn == dt_dyn && g.prim0_before == h->prim0 && g.ptrs == ptrs) entry = &g;
-    HIP_TRY(hipEventRecord(h->g_fork, h->stream));
-    HIP_TRY(hipStreamWaitEvent(h->gstream, h->g_fork, 0));
-    int seq0 = h->fct_seq;
-    if (!entry) {
-      if (h->graphs.size() >= 8) {                      // (a few shapes of a step recur: both buffer parities x the cycle counts met)
-        HIP_TRY(hipStreamSynchronize(h->gstream));      // an earlier replay may still be running one of them
-        for (auto &g : h->graphs) (void)hipGraphExecDestroy(g.exec);
-        h->graphs.clear();
-      }
-      pam_amd_awfl::GraphEntry e;
-      e.ptrs = ptrs; e.ncycles = ncycles; e.dt_dyn = dt_dyn; e.prim0_before = h->prim0; e.gen = h->graph_gen; e.nstages = nstages;
-      Chunk &c0 = h->chunks[0];
-      const hipStream_t s_keep = c0.stream, f_keep = c0.fstream;
-      c0.stream = c0.fstream = h->gstream;
-      h->capturing = true;
-      h->capture_seq0 = h->fct_seq;
-      // what the capture advances on the host side (stage number, buffer rotation) is put back when no graph comes out of it: no
-      // kernel has run then, and the next step must start from the same buffers
-      const int seq_keep = h->fct_seq;
-      double *const p0_keep = h->prim0, *const p1_keep = h->prim1;
-      // (test hook: pam_amd_awfl_debug_fail_next_capture makes one of the three capture calls "fail")
-      const int inject = h->fail_next_capture;
-      h->fail_next_capture = 0;
-      hipError_t cerr = (inject == 1) ? hipErrorUnknown : hipStreamBeginCapture(h->gstream, hipStreamCaptureModeThreadLocal);
-      if (cerr == hipSuccess) rc = enqueue();
-      hipGraph_t graph = nullptr;
-      hipError_t eerr = (cerr == hipSuccess) ? hipStreamEndCapture(h->gstream, &graph) : cerr;
-      if (inject == 2 && eerr == hipSuccess) eerr = hipErrorUnknown;
-      h->capturing = false;
-      c0.stream = s_keep; c0.fstream = f_keep;
-      // what failed: the launches themselves (rc: a bad argument, a HIP error of a launch -- the same call would fail eagerly too) or
-      // the capture machinery (BeginCapture / EndCapture / Instantiate: the step itself is fine)
-      const int enqueue_rc = rc;
-      std::string why;
-      if (enqueue_rc == PAM_AMD_OK && eerr != hipSuccess) why = std::string("graph capture: ") + hipGetErrorString(eerr);
-      if (enqueue_rc == PAM_AMD_OK && why.empty() &&
-          (inject == 3 || hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0) != hipSuccess)) why = "hipGraphInstantiate failed";
-      if (graph) (void)hipGraphDestroy(graph);
-      if (enqueue_rc != PAM_AMD_OK || !why.empty()) {
-        h->fct_seq = seq_keep; h->prim0 = p0_keep; h->prim1 = p1_keep;
-        // the caller's stream was forked into gstream above: join it again
-        (void)hipEventRecord(h->g_join, h->gstream);
-        (void)hipStreamWaitEvent(h->stream, h->g_join, 0);
-        if (enqueue_rc != PAM_AMD_OK) return enqueue_rc;         // (its message is in last_error; nothing ran: the launches were only recorded)
-        // the capture machinery failed: drop the runtime's sticky error, run the step eagerly, say so, and stop capturing on this handle
-        (void)hipGetLastError();
-        h->graph_mode = 1;
-        const int erc = enqueue();
-        if (erc == PAM_AMD_OK) g_last_error = "warning: time_step: " + why + "; the step ran eagerly and graph replay is switched off for this handle";
-        return erc;
-      }
-      e.prim0_after = h->prim0; e.prim1_after = h->prim1;       // (the capture has walked the buffer rotation on the host side)
-      h->graphs.push_back(e);
-      entry = &h->graphs.back();
-    } else {
-      h->fct_seq += nstages;
-      h->prim0 = entry->prim0_after;
-      h->prim1 = entry->prim1_after;
-    }
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->seq_dev, seq0, 1, h->gstream));
-    HIP_TRY(hipGraphLaunch(entry->exec, h->gstream));
-    HIP_TRY(hipEventRecord(h->g_join, h->gstream));
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->g_join, 0));
-    return PAM_AMD_OK;
-  }
-  rc = enqueue();
-  // join: the caller's stream continues after every chunk (and the shared compute stream, which every chunk stream follows
-  // or is followed by through the events above) has finished -- also on the error path
-  if (forked) {
-    int jrc = PAM_AMD_OK;
-    auto join_try = [&](hipError_t e) { if (e != hipSuccess && jrc == PAM_AMD_OK) jrc = fail(PAM_AMD_ENOGPU, std::string("time_step join: ") + hipGetErrorString(e)); };
-    for (auto &c : h->chunks) {
-      if (c.fstream && c.fstream != c.stream) {       // flux / compute streams: order them into the chunk stream first
-        join_try(hipEventRecord(c.flux_done, c.fstream));
-        join_try(hipStreamWaitEvent(c.stream, c.flux_done, 0));
-      }
-      join_try(hipEventRecord(c.done, c.stream));
-      join_try(hipStreamWaitEvent(h->stream, c.done, 0));
-    }
-    if (rc == PAM_AMD_OK) rc = jrc;
-  }
+  StepCall s{fields, crm_dt, dt_dyn_hint, 0, false, h->chunks.size() > 1, ncycles_out, dt_dyn_out};
+  if ((rc = plan_step(h, s))) return rc;
+  if (s.forked && (rc = fork_ranges(h))) return rc;
+  if (h->graph_mode == 2 && h->fused && !s.forked && !h->timing && !h->debug_mass && h->gstream) return replay_step(h, s);
+  rc = enqueue_step(h, s);
+  if (s.forked) rc = join_ranges(h, rc);      // (also on the error path)
   if (rc == PAM_AMD_OK && h->debug_mass) rc = evaluate_mass(h);
   return rc;
 }
@@ -2714,15 +2738,10 @@ int pam_amd_awfl_set_lane_mapping(pam_amd_awfl_t *h, int yz_lanes, int x_kernels
   if (yz_lanes < 0 || yz_lanes > 2 || x_kernels < 0 || x_kernels > 2)
     return fail(PAM_AMD_EINVAL, "set_lane_mapping: 0 = automatic, 1 = member lanes / sweep kernels, 2 = flat lanes / tile kernels");
   USE_DEVICE(h);
-  const int old_l = h->lane_mode, old_x = h->xtile_mode;
-  h->lane_mode = yz_lanes;
-  h->xtile_mode = x_kernels;
-  resolve_lane_mapping(h);
-  if ((yz_lanes == 2 && !h->flat) || (x_kernels == 2 && !h->xtile)) {
-    h->lane_mode = old_l; h->xtile_mode = old_x;
-    resolve_lane_mapping(h);
-    return fail(PAM_AMD_EINVAL, "set_lane_mapping: flat lanes / tile kernels need every field below 2^28 doubles (32-bit lane offsets)");
-  }
+  if (int rc = set_resolved(h, {{&h->lane_mode, yz_lanes}, {&h->xtile_mode, x_kernels}},
+                            [&] { return (yz_lanes != 2 || h->flat) && (x_kernels != 2 || h->xtile); },
+                            "set_lane_mapping: flat lanes / tile kernels need every field below 2^28 doubles (32-bit lane offsets)"))
+    return rc;
   return build_chunks(h);
 }
 
@@ -2734,29 +2753,18 @@ int pam_amd_awfl_set_x_tile(pam_amd_awfl_t *h, int row_lanes, int cells_per_tile
   USE_DEVICE(h);
   // the LDS bound is that of the launch (launch_xupd): it applies when the x tile kernels run AND exchange through LDS -- the shuffle
   // form stages nothing -- so the candidate geometry is resolved first and rolled back if the launch would refuse it
-  const int old_w = h->xt_w, old_tc = h->xt_tc, old_lpb = h->xt_lpb;
-  h->xt_w = row_lanes; h->xt_tc = cells_per_tile; h->xt_lpb = lines_per_group;
-  resolve_lane_mapping(h);       // (may switch the x kernels: the ranges are rebuilt like set_lane_mapping does)
-  if (h->xtile && !h->xshuf && (size_t)XT_NS * (xtile_threads(h->xg) + xtile_stage_elems(h->xg)) * sizeof(double) > 160 * 1024) {
-    h->xt_w = old_w; h->xt_tc = old_tc; h->xt_lpb = old_lpb;
-    resolve_lane_mapping(h);
-    return fail(PAM_AMD_EINVAL, "set_x_tile: the staged tile does not fit the 160 KB of LDS");
-  }
-  return build_chunks(h);
+  if (int rc = set_resolved(h, {{&h->xt_w, row_lanes}, {&h->xt_tc, cells_per_tile}, {&h->xt_lpb, lines_per_group}},
+                            [&] { return !h->xtile || h->xshuf || (size_t)XT_NS * (xtile_threads(h->xg) + xtile_stage_elems(h->xg)) * sizeof(double) <= 160 * 1024; },
+                            "set_x_tile: the staged tile does not fit the 160 KB of LDS"))
+    return rc;
+  return build_chunks(h);        // (the resolution may switch the x kernels: the ranges are rebuilt like set_lane_mapping does)
 }
 
 int pam_amd_awfl_set_x_exchange(pam_amd_awfl_t *h, int mode) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
   if (mode < 0 || mode > 2) return fail(PAM_AMD_EINVAL, "set_x_exchange: 0 = automatic, 1 = through LDS, 2 = wavefront shuffles");
-  const int old = h->xshuf_mode;
-  h->xshuf_mode = mode;
-  resolve_lane_mapping(h);
-  if (mode == 2 && !h->xshuf) {
-    h->xshuf_mode = old;
-    resolve_lane_mapping(h);
-    return fail(PAM_AMD_EINVAL, "set_x_exchange: wavefront shuffles need x tile kernels whose whole periodic line lies inside one wavefront (nx * row lanes divides 64)");
-  }
-  return PAM_AMD_OK;
+  return set_resolved(h, {{&h->xshuf_mode, mode}}, [&] { return mode != 2 || h->xshuf; },
+                      "set_x_exchange: wavefront shuffles need x tile kernels whose whole periodic line lies inside one wavefront (nx * row lanes divides 64)");
 }
 
 int pam_amd_awfl_set_flux_tile(pam_amd_awfl_t *h, int enable, int cells_per_y_tile, int levels_per_z_tile) {
@@ -2899,15 +2907,8 @@ int pam_amd_awfl_set_yz_fold(pam_amd_awfl_t *h, int mode) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
   if (mode < 0 || mode > 2) return fail(PAM_AMD_EINVAL, "set_yz_fold: 0 = automatic, 1 = off (the x-sweep loads the y and the z differences), 2 = on");
   USE_DEVICE(h);
-  const int old = h->fold_mode;
-  h->fold_mode = mode;
-  resolve_lane_mapping(h);
-  if (mode == 2 && !h->P.yz_fold) {
-    h->fold_mode = old;
-    resolve_lane_mapping(h);
-    return fail(PAM_AMD_EINVAL, "set_yz_fold: the fold exists for 3-D grids swept with member lanes (y, z and x sweep kernels)");
-  }
-  return PAM_AMD_OK;
+  return set_resolved(h, {{&h->fold_mode, mode}}, [&] { return mode != 2 || h->P.yz_fold; },
+                      "set_yz_fold: the fold exists for 3-D grids swept with member lanes (y, z and x sweep kernels)");
 }
 
 int pam_amd_awfl_set_range_schedule(pam_amd_awfl_t *h, int independent) {
@@ -2919,7 +2920,6 @@ int pam_amd_awfl_set_range_schedule(pam_amd_awfl_t *h, int independent) {
 
 int pam_amd_awfl_set_fused_stage(pam_amd_awfl_t *h, int enable) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
-  if (enable && !h->fused_supported) return fail(PAM_AMD_EINVAL, "set_fused_stage: not available on this handle");
   const bool changed = h->fused != (enable != 0);
   h->fused = enable != 0;
   if (changed) {   // the automatic range count and the streams a range needs depend on the stage structure
@@ -2984,21 +2984,17 @@ int pam_amd_awfl_debug_weno(pam_amd_awfl_t *h, int level, const double *stencils
 }
 
 // One tendency stage on its own: stage 1 of a sub-step of length dt_dyn from the resident state (a forward-Euler step
-// prim0 -> new prim0; the FCT seed is left as stage 1 leaves it), with whichever stage structure is selected.
+// prim0 -> new prim0; the FCT seed is left as stage 1 leaves it), with whichever stage structure is selected: time_step's own stage
+// path, with the whole ensemble as one range on the handle's stream.
 int pam_amd_awfl_debug_stage(pam_amd_awfl_t *h, double dt_dyn) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
   if (!h->hydro_declared) return fail(PAM_AMD_ESTATE, "debug_stage: declare_current_profile_as_hydrostatic first");
   USE_DEVICE(h);
-  const EnsRange r = full_range(h->P);
+  Chunk whole{full_range(h->P), h->stream, h->stream};
+  hipEvent_t prev_flux = nullptr;
   int rc;
   if ((rc = next_fct_stage(h))) return rc;
-  if ((rc = launch_flux(h, h->prim0, r, h->stream, h->fused ? 6 : 7, h->fused))) return rc;
-  bool fuse_tail = false;
-  if (h->fused && (rc = launch_xupd<1>(h, h->prim0, h->prim0, h->prim1, dt_dyn, dt_dyn, r, h->stream, tail_fusable(h), &fuse_tail))) return rc;
-  if (!h->fused && (rc = launch_fct(h, dt_dyn, r, h->stream))) return rc;
-  if (h->fused) rc = fuse_tail ? PAM_AMD_OK : launch_tail<1>(h, h->prim0, h->prim0, h->prim1, dt_dyn, r, h->stream);
-  else rc = launch_update<1>(h, h->prim0, h->prim0, h->prim1, dt_dyn, r, h->stream);
-  if (rc) return rc;
+  if ((rc = run_stage(h, whole, StageArgs{1, h->prim0, h->prim0, h->prim1, dt_dyn, dt_dyn}, false, prev_flux))) return rc;
   std::swap(h->prim0, h->prim1);
   return PAM_AMD_OK;
 }
