@@ -244,9 +244,10 @@ struct WenoLin {
   double k2, k4, k2s;    // vertical only: even-part factors of the level (see weno5_blend); k2s = k2 / sqrt(13/3) goes with the scaled a2
 };
 
-// Non-linear part (WenoLimiter.h:141-180: TV, sigma blend, weights, convexify, map, convexify, weighted sum).
+// Non-linear part (WenoLimiter.h:141-180: TV, sigma blend, weights, convexify, map, convexify, weighted sum): weno5_blend (vertical)
+// and weno5_const (uniform grid) form the TVs, both end in weno5_tail.
 // UNIFORM (constant-matrix directions): the x^2 coefficient of every lower candidate is half the second difference, so
-// p.a2 holds the second difference itself and the factor 1/4 moves into the TV constant.
+// a2 holds the second difference itself and the factor 1/4 moves into the TV constant.
 // Every multiply-add below has an explicit rounding point (fma = one rounding; nothing else is contracted): the same
 // source must give the same bits in every kernel it is inlined into (x/y/z sweeps, the fused x-sweep, the KAT hook), and the
 // backend's own contraction choices depend on the surrounding code (seen on gfx950: tv*tv + 1e-20 fused in one kernel and
@@ -263,45 +264,41 @@ constexpr double csqrt_(double v) {      // compile-time square root (Newton; v 
   for (int i = 0; i < 200; i++) x = 0.5 * (x + v / x);
   return x;
 }
-constexpr double WENO_K2U = 0.25 * AWFL_TV3_A2A2;            // uniform grid: p.a2 holds the second difference = 2 a2
+constexpr double WENO_K2U = 0.25 * AWFL_TV3_A2A2;            // uniform grid: a2 holds the second difference = 2 a2
 constexpr double WENO_SQRT_K2U = csqrt_(WENO_K2U), WENO_RSQRT_K2U = 1.0 / WENO_SQRT_K2U;
-template <bool UNIFORM>
-PAMA_D void weno5_blend(double u2, const WenoLin &p, const WenoConsts &wc, double &left, double &right) {
+// Weights with the ideal weights folded into the denominators: w_i = idl_i/d_i / (sum_k idl_k/d_k + eps) is unchanged when every
+// idl_k/d_k is replaced by idl_0/d_k' with d_k' = d_k idl_k/idl_0 and the eps by eps/idl_0.  idl_0 == idl_2 (checked below), so only
+// d_1' and d_3' carry a factor, and it rides on the tv^2 term of their multiply-add (tv (tv r) + eps r): two multiplies instead of
+// the four idl_i x_i products.
+constexpr double weno_idl_c(int i) {
+  constexpr double raw[4] = AWFL_WENO_IDL_INIT;
+  return raw[i] / ((((raw[0] + raw[1]) + raw[2]) + raw[3]) + 1.0e-20);   // the same arithmetic as weno_consts
+}
+constexpr double WENO_R1 = weno_idl_c(0) / weno_idl_c(1), WENO_R3 = weno_idl_c(0) / weno_idl_c(3);
+static_assert(weno_idl_c(0) == weno_idl_c(2), "weights 0 and 2 share their ideal weight");
+constexpr double WENO_BLEND_LO = (1.0 - AWFL_WENO_SIGMA) / 3.0;   // tv3 = lo_avg + (tv3 - lo_avg) sigma = LO (tv0+tv1+tv2) + sigma tv3
+
+// The tail of every polynomial: from the four (folded) denominators d_i' to the two edge values.
+//   w_i = x_i / (x_0 + x_1 + x_2 + x_3 + eps' d_0'd_1'd_2'd_3'),  x_i = prod_{k != i} d_k'   (one reciprocal, WenoLimiter.h:163-166);
+//   the eps term is x_3 d_3' eps', added as x_3 (1 + eps' d_3').  The eps added to the SUM matters when the TVs are large (pressure
+//   stencils: sum ~ 1e-17), so it is kept.
+//   map_weights (WenoLimiter.h:11-19) then convexify, again with one reciprocal; the normalisation 1/sum(m) is applied to the two
+//   weighted sums instead of to the four weights.
+//   lo_e / lo_o: the lower candidates' even / odd parts (sum_i m_i a2_i, sum_i m_i a1_i); e3 / o3: those of the upper polynomial,
+//   each multiplied by m3; kse: the factor of lo_e in the even part; codd: the factor of the odd part.
+PAMA_D void weno5_tail(double u2, double d0, double d1, double d2, double d3, double eps_sum, const double (&a1)[3],
+                       const double (&a2)[3], double e3, double o3, double kse, double codd, const WenoConsts &wc, double &left,
+                       double &right) {
 #pragma clang fp contract(off)
-  constexpr double K13 = AWFL_TV5_A1A3 / AWFL_TV5_SQRT_A3A3, K24 = AWFL_TV5_A2A4 / AWFL_TV5_SQRT_A4A4;
-  constexpr double EPS_TV = UNIFORM ? 1.0e-20 / (WENO_K2U * WENO_K2U) : 1.0e-20;      // added to tv^2
-  constexpr double EPS_SUM = UNIFORM ? 1.0e-20 * (WENO_K2U * WENO_K2U) : 1.0e-20;     // added to the sum of the unnormalised weights
-  constexpr double UNSCALE = UNIFORM ? WENO_SQRT_K2U : 1.0;                           // scaled x coefficients -> true ones
-  double tv[4];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    tv[i] = fma(p.a1[i], p.a1[i], p.a2[i] * p.a2[i]);   // (vertical: the table delivers a2 times sqrt(13/3), see weno5_table)
-  }
-  // coefs_to_tv<5> (TransformMatrices.h:871-876) grouped as h1 (h1 + .5 h3) + h2 (c2 h2 + 4.2 h4) + c3 h3^2 + c4 h4^2, with
-  // h3, h4 carried pre-scaled by sqrt(c3), sqrt(c4)
-  {
-    const double t1 = fma(K13, p.h3, p.h1), t2 = fma(K24, p.h4, AWFL_TV5_A2A2 * p.h2);
-    tv[3] = fma(p.h4, p.h4, fma(p.h3, p.h3, fma(p.h2, t2, p.h1 * t1)));
-  }
-  // tv3 = lo_avg + (tv3 - lo_avg) sigma  (WenoLimiter.h:150-151)
-  tv[3] = fma((1.0 - AWFL_WENO_SIGMA) / 3.0, (tv[0] + tv[1]) + tv[2], wc.sigma * tv[3]);
-  // w_i = idl_i/(tv_i^2+eps), then convexify: w_i /= (sum_k w_k + eps) (WenoLimiter.h:163-166).  One reciprocal,
-  // through products of the denominators d_i.  The eps added to the SUM matters when the TVs are large (pressure
-  // stencils: sum ~ 1e-17), so it is kept: numerator and denominator are both scaled by d0*d1*d2*d3.
-  const double d0 = fma(tv[0], tv[0], EPS_TV), d1 = fma(tv[1], tv[1], EPS_TV);
-  const double d2 = fma(tv[2], tv[2], EPS_TV), d3 = fma(tv[3], tv[3], EPS_TV);
   const double p01 = d0 * d1, p23 = d2 * d3;
   const double x0 = d1 * p23, x1 = d0 * p23, x2 = d3 * p01, x3 = d2 * p01;
-  const double n0 = wc.idl[0] * x0, n1 = wc.idl[1] * x1, n2 = wc.idl[2] * x2, n3 = wc.idl[3] * x3;
-  const double rs = weno_rcp(fma(EPS_SUM, p01 * p23, fma(wc.idl[3], x3, fma(wc.idl[2], x2, fma(wc.idl[0], x0, n1)))));
-  // map_weights (WenoLimiter.h:11-19) then convexify, again with one reciprocal; the normalisation 1/sum(m) is applied
-  // to the two weighted sums instead of to the four weights
-  const double nn[4] = {n0, n1, n2, n3};
+  const double rs = weno_rcp(fma(x3, fma(eps_sum, d3, 1.0), (x0 + x1) + x2));
+  const double xx[4] = {x0, x1, x2, x3};
   double num[4], den[4];
 #pragma unroll
   for (int i = 0; i < 4; i++) {
-    const double w = nn[i] * rs;
-    num[i] = w * fma(w, fma(nn[i], rs, -wc.idl3x[i]), wc.c0[i]);     // w (c0 + w (w - 3 idl))
+    const double w = xx[i] * rs;
+    num[i] = w * fma(w, fma(xx[i], rs, -wc.idl3x[i]), wc.c0[i]);     // w (c0 + w (w - 3 idl))
     den[i] = fma(wc.c1[i], w, wc.c2[i]);
   }
   const double q01 = den[0] * den[1], q23 = den[2] * den[3];
@@ -311,17 +308,38 @@ PAMA_D void weno5_blend(double u2, const WenoLin &p, const WenoConsts &wc, doubl
   // even part.  Every candidate reproduces the average of the centre cell, which in the candidates' coordinate is centred
   // at 0 with width w (1 on the uniform grid; dz(k)/dz(k-1) in the vertical, whose matrices are normalised by the cell
   // below): a0 + a2 w^2/12 (+ a4 w^4/80) = u2.  Its value at x = +-1/2 minus u2 is therefore
-  // a2 (1/4 - w^2/12) (+ a4 (1/16 - w^4/80)) and needs no coefficients of its own.  (UNIFORM: p.a2 holds 2 a2.)
-  const double lo_e = fma(m0, p.a2[0], fma(m1, p.a2[1], m2 * p.a2[2]));
-  double se;
-  if (UNIFORM) se = fma(1.0 / 12.0, lo_e, m3 * fma(p.h4, UNSCALE * 0.05 / AWFL_TV5_SQRT_A4A4, p.h2 * (UNSCALE / 6.0)));
-  else se = fma(p.k2s, lo_e, m3 * fma(p.h4, p.k4, p.h2 * p.k2));
-  // odd part: a1/2 (+ a3/8 for the upper polynomial); h3 is carried times sqrt(c3)
-  const double so = fma(m3, fma(0.25 / AWFL_TV5_SQRT_A3A3, p.h3, p.h1), fma(m0, p.a1[0], fma(m1, p.a1[1], m2 * p.a1[2])));
-  const double even = fma(rm, se, u2);
-  const double odd = ((0.5 * UNSCALE) * rm) * so;
-  left = even - odd;
-  right = even + odd;
+  // a2 (1/4 - w^2/12) (+ a4 (1/16 - w^4/80)) and needs no coefficients of its own.
+  const double lo_e = fma(m0, a2[0], fma(m1, a2[1], m2 * a2[2]));
+  const double se = fma(kse, lo_e, m3 * e3);
+  // odd part: a1/2 (+ a3/8 for the upper polynomial); left / right = u2 + (se -+ codd so) / sum(m)
+  const double so = fma(m3, o3, fma(m0, a1[0], fma(m1, a1[1], m2 * a1[2])));
+  left = fma(rm, fma(-codd, so, se), u2);
+  right = fma(rm, fma(codd, so, se), u2);
+}
+
+// Vertical direction (general quadratic forms): the table delivers every coefficient (see weno5_table).
+PAMA_D void weno5_blend(double u2, const WenoLin &p, const WenoConsts &wc, double &left, double &right) {
+#pragma clang fp contract(off)
+  constexpr double K13 = AWFL_TV5_A1A3 / AWFL_TV5_SQRT_A3A3, K24 = AWFL_TV5_A2A4 / AWFL_TV5_SQRT_A4A4;
+  constexpr double EPS_TV = 1.0e-20;    // added to tv^2
+  double tv[4];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    tv[i] = fma(p.a1[i], p.a1[i], p.a2[i] * p.a2[i]);   // (the table delivers a2 times sqrt(13/3), see weno5_table)
+  }
+  // coefs_to_tv<5> (TransformMatrices.h:871-876) grouped as h1 (h1 + .5 h3) + h2 (c2 h2 + 4.2 h4) + c3 h3^2 + c4 h4^2, with
+  // h3, h4 carried pre-scaled by sqrt(c3), sqrt(c4)
+  {
+    const double t1 = fma(K13, p.h3, p.h1), t2 = fma(K24, p.h4, AWFL_TV5_A2A2 * p.h2);
+    tv[3] = fma(p.h4, p.h4, fma(p.h3, p.h3, fma(p.h2, t2, p.h1 * t1)));
+  }
+  // tv3 = lo_avg + (tv3 - lo_avg) sigma  (WenoLimiter.h:150-151), formed divided by sigma: the 1/sigma^2 moves into d3's factor
+  const double tv3s = fma(WENO_BLEND_LO / AWFL_WENO_SIGMA, (tv[0] + tv[1]) + tv[2], tv[3]);
+  constexpr double R3S = WENO_R3 * (AWFL_WENO_SIGMA * AWFL_WENO_SIGMA);
+  const double d0 = fma(tv[0], tv[0], EPS_TV), d1 = fma(tv[1], tv[1] * WENO_R1, EPS_TV * WENO_R1);
+  const double d2 = fma(tv[2], tv[2], EPS_TV), d3 = fma(tv3s, tv3s * R3S, EPS_TV * WENO_R3);
+  weno5_tail(u2, d0, d1, d2, d3, 1.0e-20 / weno_idl_c(0), p.a1, p.a2, fma(p.h4, p.k4, p.h2 * p.k2),
+             fma(0.25 / AWFL_TV5_SQRT_A3A3, p.h3, p.h1), p.k2s, 0.5, wc, left, right);
 }
 
 // Difference-form coefficient tables.  Lower candidate i uses (d_{i+1}, d_{i+2}); the upper polynomial uses d_1..d_4.
@@ -404,10 +422,68 @@ constexpr bool uniform_even_identity_holds() {
 static_assert(uniform_even_identity_holds(), "uniform-grid candidates must reproduce the centre cell average");
 
 // Horizontal directions: constant matrices (uniform grid).  All coefficients are compile-time literals, and the mirror
-// symmetry of the uniform stencil (checked below, exactly) lets the four upper-polynomial coefficients share the sums
-// and differences of the outer and inner first differences:
-//   h1 = a (d0+d3) + b (d1+d2)      h3 = g ((d0+d3) - (d1+d2))
-//   h2 = c (d0-d3) + e (d2-d1)      h4 = q ((d3-d0) - 3 (d2-d1))          (h3, h4 times sqrt of their TV weights)
+// symmetry of the uniform stencil (u_m -> u_{4-m}, i.e. d0 <-> -d3, d1 <-> -d2) splits every form of the polynomial into the sums
+// and differences of the outer and inner first differences, s03 = d0+d3, s12 = d1+d2 (odd under the mirror) and t03 = d3-d0,
+// a2_1 = d2-d1 (even).  The upper polynomial enters the step only through
+//   * its blended TV  tvb = LO (tv0+tv1+tv2) + sigma tv3 (WenoLimiter.h:141-151), a quadratic form of d invariant under the mirror, so
+//     without cross terms between (s03, s12) and (t03, a2_1): two 2x2 forms, each a sum of two squares (Cholesky).  Scaled by a
+//     constant LAM (its 1/LAM^2 moves into d3's factor), and with the one-variable squares matched to tv1 = (S/2)^2 s12^2 + a2_1^2:
+//         LAM tvb = l1^2 + l3^2 + tv1 + ETA a2_1^2,   l1 = A1 s03 + B1 s12,   l3 = A3 t03 + B3 a2_1
+//     -- with l1, l3 seven instructions, where forming h1..h4, their TV and the blend took 19;
+//   * its even and odd parts in the weighted sums: X = (h2 / 6 + a4 / 16 (scaled)) (t03, a2_1) and H = (h1 / 2 + h3 / 8) (s03, s12).
+struct UniformUpper { double lam, a1, b1, a3, b3, eta, xt, xa, hs, hc, cross; };
+constexpr UniformUpper make_uniform_upper() {
+  constexpr DTable T = make_const_dtable();
+  constexpr double S = WENO_RSQRT_K2U, K13 = AWFL_TV5_A1A3 / AWFL_TV5_SQRT_A3A3, K24 = AWFL_TV5_A2A4 / AWFL_TV5_SQRT_A4A4;
+  // the quadratic form of tvb on d (every x coefficient divided by sqrt(K2U), a2 doubled: the scaling of the lower TVs)
+  double Q[4][4] = {};
+  for (int i = 0; i < 3; i++) {
+    double va[4] = {}, vb[4] = {};
+    va[i] = S * T.lo1[i][0]; va[i + 1] = S * T.lo1[i][1];
+    vb[i] = -1.0; vb[i + 1] = 1.0;
+    for (int r = 0; r < 4; r++)
+      for (int c = 0; c < 4; c++) Q[r][c] += WENO_BLEND_LO * (va[r] * va[c] + vb[r] * vb[c]);
+  }
+  double h[4][4] = {};
+  for (int q = 0; q < 4; q++)
+    for (int m = 0; m < 4; m++) h[q][m] = S * T.hi[q][m];
+  for (int r = 0; r < 4; r++)
+    for (int c = 0; c < 4; c++)
+      Q[r][c] += AWFL_WENO_SIGMA * (h[0][r] * h[0][c] + 0.5 * K13 * (h[0][r] * h[2][c] + h[2][r] * h[0][c]) +
+                                    AWFL_TV5_A2A2 * h[1][r] * h[1][c] + 0.5 * K24 * (h[1][r] * h[3][c] + h[3][r] * h[1][c]) +
+                                    h[2][r] * h[2][c] + h[3][r] * h[3][c]);
+  // to the basis (s03, s12, t03, a2_1): d = P b
+  const double P[4][4] = {{0.5, 0, -0.5, 0}, {0, 0.5, 0, -0.5}, {0, 0.5, 0, 0.5}, {0.5, 0, 0.5, 0}};
+  double M[4][4] = {};
+  for (int r = 0; r < 4; r++)
+    for (int c = 0; c < 4; c++)
+      for (int a = 0; a < 4; a++)
+        for (int b = 0; b < 4; b++) M[r][c] += P[a][r] * Q[a][b] * P[b][c];
+  UniformUpper U{};
+  const double ce = M[1][1] - M[0][1] * M[0][1] / M[0][0], co = M[3][3] - M[2][3] * M[2][3] / M[2][2];
+  U.lam = 0.25 * S * S / ce;
+  U.a1 = csqrt_(U.lam * M[0][0]); U.b1 = U.lam * M[0][1] / U.a1;
+  U.a3 = csqrt_(U.lam * M[2][2]); U.b3 = U.lam * M[2][3] / U.a3;
+  U.eta = U.lam * co - 1.0;
+  // X = h2/6 + 0.05 h4/sqrt(c4) and H = h1 + 0.25 h3/sqrt(c3) (true coefficients; H then times S, the scale of the lower a1)
+  double x[4] = {}, hh[4] = {};
+  for (int m = 0; m < 4; m++) {
+    x[m] = T.hi[1][m] / 6.0 + 0.05 * T.hi[3][m] / AWFL_TV5_SQRT_A4A4;
+    hh[m] = S * (T.hi[0][m] + 0.25 * T.hi[2][m] / AWFL_TV5_SQRT_A3A3);
+  }
+  U.xt = x[3]; U.xa = x[2];     // X = xt t03 + xa a2_1 (antisymmetric)
+  U.hs = hh[0]; U.hc = hh[1];   // H = hs s03 + hc s12  (symmetric)
+  for (int r = 0; r < 2; r++)
+    for (int c = 2; c < 4; c++) U.cross = cabs_(M[r][c]) > U.cross ? cabs_(M[r][c]) : U.cross;
+  return U;
+}
+constexpr bool uniform_upper_ok() {
+  // the blocks of tvb do not couple (mirror symmetry), and the odd block's residual square is positive
+  constexpr UniformUpper U = make_uniform_upper();
+  return U.cross < 1e-15 && U.lam > 0.0 && U.eta > -1.0 && U.a1 > 0.0 && U.a3 > 0.0;
+}
+static_assert(uniform_upper_ok(), "uniform-grid blended TV: positive definite blocks");
+
 PAMA_D void weno5_const(const double u[5], const WenoConsts &wc, double &left, double &right) {
 #pragma clang fp contract(off)
   constexpr DTable T = make_const_dtable();
@@ -420,22 +496,28 @@ PAMA_D void weno5_const(const double u[5], const WenoConsts &wc, double &left, d
   // on the uniform grid every lower candidate has a2 = (d_{i+1} - d_i)/2 exactly
   static_assert(T.lo2[0][0] == -0.5 && T.lo2[0][1] == 0.5 && T.lo2[1][0] == -0.5 && T.lo2[1][1] == 0.5 &&
                 T.lo2[2][0] == -0.5 && T.lo2[2][1] == 0.5, "uniform-grid x^2 coefficients are half second differences");
+  constexpr UniformUpper U = make_uniform_upper();
+  constexpr double EPS_TV = 1.0e-20 / (WENO_K2U * WENO_K2U);      // added to tv^2 (the TVs are divided by K2U, see above weno5_blend)
+  constexpr double EPS_SUM = 1.0e-20 * (WENO_K2U * WENO_K2U);     // added to the sum of the unnormalised weights
   const double d[4] = {u[1] - u[0], u[2] - u[1], u[3] - u[2], u[4] - u[3]};
-  WenoLin p;
   const double s03 = d[0] + d[3], s12 = d[1] + d[2], t03 = d[3] - d[0];
-  p.a2[0] = d[1] - d[0];
-  p.a2[1] = d[2] - d[1];
-  p.a2[2] = d[3] - d[2];
-  constexpr double S = WENO_RSQRT_K2U;     // every x coefficient is delivered divided by sqrt(K2U) (see weno5_blend)
-  p.a1[0] = fma(S * T.lo1[0][1], d[1], (S * T.lo1[0][0]) * d[0]);
-  p.a1[1] = (S * 0.5) * s12;
-  p.a1[2] = fma(S * T.lo1[2][1], d[3], (S * T.lo1[2][0]) * d[2]);
-  p.h1 = fma(S * T.hi[0][1], s12, (S * T.hi[0][0]) * s03);
-  p.h2 = fma(-S * T.hi[1][0], t03, (S * T.hi[1][2]) * p.a2[1]);
-  p.h3 = (S * T.hi[2][0]) * (s03 - s12);
-  p.h4 = (S * T.hi[3][3]) * fma(-3.0, p.a2[1], t03);
-  p.k2 = p.k4 = p.k2s = 0.0;   // unused on the uniform grid (weno5_blend<true>)
-  weno5_blend<true>(u[2], p, wc, left, right);
+  double a1[3], a2[3];
+  a2[0] = d[1] - d[0];
+  a2[1] = d[2] - d[1];
+  a2[2] = d[3] - d[2];
+  constexpr double S = WENO_RSQRT_K2U;     // every x coefficient is delivered divided by sqrt(K2U) (see above weno5_blend)
+  a1[0] = fma(S * T.lo1[0][1], d[1], (S * T.lo1[0][0]) * d[0]);
+  a1[1] = (S * 0.5) * s12;
+  a1[2] = fma(S * T.lo1[2][1], d[3], (S * T.lo1[2][0]) * d[2]);
+  const double sq1 = a2[1] * a2[1];
+  const double tv0 = fma(a1[0], a1[0], a2[0] * a2[0]), tv1 = fma(a1[1], a1[1], sq1), tv2 = fma(a1[2], a1[2], a2[2] * a2[2]);
+  const double l1 = fma(U.a1, s03, U.b1 * s12), l3 = fma(U.a3, t03, U.b3 * a2[1]);
+  const double tvb = fma(l1, l1, fma(l3, l3, fma(U.eta, sq1, tv1)));      // LAM x the blended TV of the upper polynomial
+  constexpr double R3L = WENO_R3 / (U.lam * U.lam);
+  const double d0 = fma(tv0, tv0, EPS_TV), d1 = fma(tv1, tv1 * WENO_R1, EPS_TV * WENO_R1);
+  const double d2 = fma(tv2, tv2, EPS_TV), d3 = fma(tvb, tvb * R3L, EPS_TV * WENO_R3);
+  weno5_tail(u[2], d0, d1, d2, d3, EPS_SUM / weno_idl_c(0), a1, a2, fma(U.xt, t03, U.xa * a2[1]), fma(U.hs, s03, U.hc * s12),
+             1.0 / 12.0, 0.5 * WENO_SQRT_K2U, wc, left, right);
 }
 
 // Vertical direction: per-level difference-form table built at init from the cell-edge locations
@@ -459,7 +541,7 @@ PAMA_D void weno5_table(const double u[5], TabPtr tab, long long ts, const WenoC
   p.k2 = tab[28 * ts];
   p.k4 = tab[29 * ts];
   p.k2s = tab[30 * ts];
-  weno5_blend<false>(u[2], p, wc, left, right);
+  weno5_blend(u[2], p, wc, left, right);
 }
 
 // ------------------------------------------------------------------------------------------------
