@@ -56,7 +56,7 @@ constexpr int FLUX_WAVES = FLUX_THREADS / 64;
 #endif
 constexpr int FLUX_NF = PAMA_FLUX_NF;   // advected fields swept together (independent polynomial chains per iteration)
 constexpr int FLUX_MAX_SPAN = 64; // longest span one wavefront sweeps without a cut (a 61-face column, a 64-cell line)
-constexpr int VZ_STRIDE = 31;  // per-level vertical table in difference form (struct DTable + one derived factor)
+constexpr int VZ_STRIDE = 31;  // per-level vertical table in difference form (struct VTable)
 
 enum PrimField { P_RHO = 0, P_PRES = 1, P_U = 2, P_V = 3, P_W = 4, P_THETA = 5, P_TR0 = 6 };
 
@@ -238,13 +238,7 @@ PAMA_D WenoConsts weno_consts() {
 //      even = u2 + sum_i w_i E_i ,  odd = sum_i w_i O_i ,  left = even - odd ,  right = even + odd
 // with E_i = (a0_i - u2) + a2_i/4 (+ a4/16), O_i = a1_i/2 (+ a3/8).  The bridge polynomial (WenoLimiter.h:128-136) is
 // linear in the stencil and is folded into the upper-polynomial coefficients.
-struct WenoLin {
-  double a1[3], a2[3];   // lower candidates: x coefficient; x^2 coefficient (UNIFORM: the second difference d_{i+1}-d_i = 2 a2)
-  double h1, h2, h3, h4; // bridged upper polynomial: x, x^2 coefficients; x^3, x^4 coefficients times sqrt of their TV weight
-  double k2, k4, k2s;    // vertical only: even-part factors of the level (see weno5_blend); k2s = k2 / sqrt(13/3) goes with the scaled a2
-};
-
-// Non-linear part (WenoLimiter.h:141-180: TV, sigma blend, weights, convexify, map, convexify, weighted sum): weno5_blend (vertical)
+// Non-linear part (WenoLimiter.h:141-180: TV, sigma blend, weights, convexify, map, convexify, weighted sum): weno5_table (vertical)
 // and weno5_const (uniform grid) form the TVs, both end in weno5_tail.
 // UNIFORM (constant-matrix directions): the x^2 coefficient of every lower candidate is half the second difference, so
 // a2 holds the second difference itself and the factor 1/4 moves into the TV constant.
@@ -317,39 +311,12 @@ PAMA_D void weno5_tail(double u2, double d0, double d1, double d2, double d3, do
   right = fma(rm, fma(codd, so, se), u2);
 }
 
-// Vertical direction (general quadratic forms): the table delivers every coefficient (see weno5_table).
-PAMA_D void weno5_blend(double u2, const WenoLin &p, const WenoConsts &wc, double &left, double &right) {
-#pragma clang fp contract(off)
-  constexpr double K13 = AWFL_TV5_A1A3 / AWFL_TV5_SQRT_A3A3, K24 = AWFL_TV5_A2A4 / AWFL_TV5_SQRT_A4A4;
-  constexpr double EPS_TV = 1.0e-20;    // added to tv^2
-  double tv[4];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    tv[i] = fma(p.a1[i], p.a1[i], p.a2[i] * p.a2[i]);   // (the table delivers a2 times sqrt(13/3), see weno5_table)
-  }
-  // coefs_to_tv<5> (TransformMatrices.h:871-876) grouped as h1 (h1 + .5 h3) + h2 (c2 h2 + 4.2 h4) + c3 h3^2 + c4 h4^2, with
-  // h3, h4 carried pre-scaled by sqrt(c3), sqrt(c4)
-  {
-    const double t1 = fma(K13, p.h3, p.h1), t2 = fma(K24, p.h4, AWFL_TV5_A2A2 * p.h2);
-    tv[3] = fma(p.h4, p.h4, fma(p.h3, p.h3, fma(p.h2, t2, p.h1 * t1)));
-  }
-  // tv3 = lo_avg + (tv3 - lo_avg) sigma  (WenoLimiter.h:150-151), formed divided by sigma: the 1/sigma^2 moves into d3's factor
-  const double tv3s = fma(WENO_BLEND_LO / AWFL_WENO_SIGMA, (tv[0] + tv[1]) + tv[2], tv[3]);
-  constexpr double R3S = WENO_R3 * (AWFL_WENO_SIGMA * AWFL_WENO_SIGMA);
-  const double d0 = fma(tv[0], tv[0], EPS_TV), d1 = fma(tv[1], tv[1] * WENO_R1, EPS_TV * WENO_R1);
-  const double d2 = fma(tv[2], tv[2], EPS_TV), d3 = fma(tv3s, tv3s * R3S, EPS_TV * WENO_R3);
-  weno5_tail(u2, d0, d1, d2, d3, 1.0e-20 / weno_idl_c(0), p.a1, p.a2, fma(p.h4, p.k4, p.h2 * p.k2),
-             fma(0.25 / AWFL_TV5_SQRT_A3A3, p.h3, p.h1), p.k2s, 0.5, wc, left, right);
-}
-
 // Difference-form coefficient tables.  Lower candidate i uses (d_{i+1}, d_{i+2}); the upper polynomial uses d_1..d_4.
 //   lo1[i][2], lo2[i][2]      x and x^2 coefficients of candidate i
 //   hi[p-1][4]   p=1..4       bridged upper coefficients; the x^3 and x^4 rows are scaled by sqrt(39.1125), sqrt(625.8)
-//                             (their weights in coefs_to_tv<5>), see weno5_blend
+//                             (their weights in coefs_to_tv<5>)
 //   k2, k4                    even-part factors 1/4 - w^2/12 and (1/16 - w^4/80)/sqrt(625.8), w = width of the centre cell
-// VZ_STRIDE doubles per level in this order, then k2 / sqrt(13/3).  In the STORED vertical tables (awfl_vertical.h) the lo2 rows
-// are multiplied by sqrt(13/3), the weight of a2^2 in coefs_to_tv<3> (TransformMatrices.h:188-193): the candidates' TV is then
-// a1^2 + a2'^2 -- one multiply and one fma instead of two multiplies and an fma -- and the even part, linear in a2', takes k2s.
+// The vertical tables store the factored form of this (VTable, make_vtable); the uniform grid uses it through make_uniform_upper.
 struct DTable { double lo1[3][2], lo2[3][2], hi[4][4], k2, k4; };
 
 // conversion of a stencil-form linear functional  sum_s c_s u_{s0+s}  (cells s0..s0+n-1 of the 5-stencil, centre = 2)
@@ -403,7 +370,69 @@ constexpr DTable make_const_dtable() {
 }
 
 constexpr double cabs_(double x) { return x < 0 ? -x : x; }
-// compile-time proof of the cell-average identity weno5_blend relies on, on the generated uniform-grid constants:
+
+// The STORED vertical table of a level (awfl_vertical.h; VZ_STRIDE doubles in this order), made from the level's DTable:
+//   lo1, lo2   the lower candidates' rows, lo2 times sqrt(13/3), the weight of a2^2 in coefs_to_tv<3> (TransformMatrices.h:188-193):
+//              the candidates' TV is then a1^2 + a2'^2 -- one multiply and one fma -- and the even part, linear in a2', takes k2s
+//   r          the upper polynomial's blended TV.  tvb = LO (tv0+tv1+tv2) + sigma tv3 (WenoLimiter.h:141-151) is one positive
+//              definite quadratic form of the four differences (the lower TVs alone are: candidates 0 and 2 cover (d0, d1) and (d2, d3)),
+//              stored as the rows of its Cholesky factor, times sqrt(R3) so that d3 = tvb'^2 + eps R3 needs no multiply of its own:
+//                  tvb' = sqrt(R3) tvb = z0^2 + z1^2 + z2^2 + z3^2,   z0 = r0 . (d0..d3), z1 = r1 . (d1..d3), z2 = r2 . (d2, d3), z3 = r3 d3
+//              -- 14 instructions, where h1..h4 (16), their TV (7) and the blend (3) took 26.  Every term is a square: nothing cancels.
+//   e3, o3     the upper polynomial's even and odd parts, k2 h2 + k4 h4 and h1 + h3 / (4 sqrt(c3)), as rows of d
+//   k2s        k2 / sqrt(13/3), the factor of the lower candidates' even part (their a2 is scaled)
+struct VTable { double lo1[3][2], lo2[3][2], r[10], e3[4], o3[4], k2s; };
+static_assert(sizeof(VTable) == VZ_STRIDE * sizeof(double), "VTable layout");
+
+// piv: the four pivots of the factorisation (all > 0 for a positive definite form; awfl_vertical.h checks them).  root: the square
+// root used for the scale factors and the pivots (std::sqrt on the host, csqrt_ at compile time).
+template <class Root>
+constexpr VTable make_vtable(const DTable &t, Root root, double (&piv)[4]) {
+  VTable v{};
+  const double sq = root(AWFL_TV3_A2A2);
+  for (int i = 0; i < 3; i++)
+    for (int q = 0; q < 2; q++) {
+      v.lo1[i][q] = t.lo1[i][q];
+      v.lo2[i][q] = t.lo2[i][q] * sq;
+    }
+  v.k2s = t.k2 / sq;
+  constexpr double K13 = AWFL_TV5_A1A3 / AWFL_TV5_SQRT_A3A3, K24 = AWFL_TV5_A2A4 / AWFL_TV5_SQRT_A4A4;
+  // the form sqrt(R3) tvb on d: LO x the lower TVs (stored rows), sigma x coefs_to_tv<5> of h1..h4 (TransformMatrices.h:871-876)
+  const double s3 = root(WENO_R3), clo = s3 * WENO_BLEND_LO, chi = s3 * AWFL_WENO_SIGMA;
+  double Q[4][4] = {};
+  for (int i = 0; i < 3; i++) {
+    double va[4] = {}, vb[4] = {};
+    va[i] = v.lo1[i][0]; va[i + 1] = v.lo1[i][1];
+    vb[i] = v.lo2[i][0]; vb[i + 1] = v.lo2[i][1];
+    for (int a = 0; a < 4; a++)
+      for (int b = 0; b < 4; b++) Q[a][b] += clo * (va[a] * va[b] + vb[a] * vb[b]);
+  }
+  const double(&h)[4][4] = t.hi;
+  for (int a = 0; a < 4; a++)
+    for (int b = 0; b < 4; b++)
+      Q[a][b] += chi * (h[0][a] * h[0][b] + 0.5 * K13 * (h[0][a] * h[2][b] + h[2][a] * h[0][b]) + AWFL_TV5_A2A2 * h[1][a] * h[1][b] +
+                        0.5 * K24 * (h[1][a] * h[3][b] + h[3][a] * h[1][b]) + h[2][a] * h[2][b] + h[3][a] * h[3][b]);
+  // Cholesky, Q = R^T R with R upper triangular: row j of R is z_j's row
+  double R[4][4] = {};
+  for (int j = 0; j < 4; j++) {
+    piv[j] = Q[j][j];
+    const double s = piv[j] > 0.0 ? root(piv[j]) : 1.0;
+    R[j][j] = s;
+    for (int k = j + 1; k < 4; k++) R[j][k] = Q[j][k] / s;
+    for (int a = j + 1; a < 4; a++)
+      for (int b = j + 1; b < 4; b++) Q[a][b] -= R[j][a] * R[j][b];
+  }
+  int n = 0;
+  for (int j = 0; j < 4; j++)
+    for (int k = j; k < 4; k++) v.r[n++] = R[j][k];
+  for (int m = 0; m < 4; m++) {
+    v.e3[m] = t.k2 * t.hi[1][m] + t.k4 * t.hi[3][m];
+    v.o3[m] = t.hi[0][m] + (0.25 / AWFL_TV5_SQRT_A3A3) * t.hi[2][m];
+  }
+  return v;
+}
+
+// compile-time proof of the cell-average identity weno5_tail relies on, on the generated uniform-grid constants:
 // (a0 - u2) = -a2/12 for the lower candidates and -(a2/12 + a4/80) for the full quartic (stencil form, per stencil value)
 constexpr bool uniform_even_identity_holds() {
   constexpr double S5[5][5] = AWFL_STEN_TO_COEFS_INIT;
@@ -497,7 +526,7 @@ PAMA_D void weno5_const(const double u[5], const WenoConsts &wc, double &left, d
   static_assert(T.lo2[0][0] == -0.5 && T.lo2[0][1] == 0.5 && T.lo2[1][0] == -0.5 && T.lo2[1][1] == 0.5 &&
                 T.lo2[2][0] == -0.5 && T.lo2[2][1] == 0.5, "uniform-grid x^2 coefficients are half second differences");
   constexpr UniformUpper U = make_uniform_upper();
-  constexpr double EPS_TV = 1.0e-20 / (WENO_K2U * WENO_K2U);      // added to tv^2 (the TVs are divided by K2U, see above weno5_blend)
+  constexpr double EPS_TV = 1.0e-20 / (WENO_K2U * WENO_K2U);      // added to tv^2 (the TVs are divided by K2U, see above weno5_tail)
   constexpr double EPS_SUM = 1.0e-20 * (WENO_K2U * WENO_K2U);     // added to the sum of the unnormalised weights
   const double d[4] = {u[1] - u[0], u[2] - u[1], u[3] - u[2], u[4] - u[3]};
   const double s03 = d[0] + d[3], s12 = d[1] + d[2], t03 = d[3] - d[0];
@@ -505,7 +534,7 @@ PAMA_D void weno5_const(const double u[5], const WenoConsts &wc, double &left, d
   a2[0] = d[1] - d[0];
   a2[1] = d[2] - d[1];
   a2[2] = d[3] - d[2];
-  constexpr double S = WENO_RSQRT_K2U;     // every x coefficient is delivered divided by sqrt(K2U) (see above weno5_blend)
+  constexpr double S = WENO_RSQRT_K2U;     // every x coefficient is delivered divided by sqrt(K2U) (see above weno5_tail)
   a1[0] = fma(S * T.lo1[0][1], d[1], (S * T.lo1[0][0]) * d[0]);
   a1[1] = (S * 0.5) * s12;
   a1[2] = fma(S * T.lo1[2][1], d[3], (S * T.lo1[2][0]) * d[2]);
@@ -522,27 +551,44 @@ PAMA_D void weno5_const(const double u[5], const WenoConsts &wc, double &left, d
 
 // Vertical direction: per-level difference-form table built at init from the cell-edge locations
 // (Dycore.h:904-937 + TransformMatrices_variable.h -> awfl_vertical.h), used as Dycore.h:454-469.
-// tab points at VZ_STRIDE doubles with element stride `ts` (1 for the ensemble-uniform table, nens otherwise).
+// tab points at VZ_STRIDE doubles (struct VTable) with element stride `ts` (1 for the ensemble-uniform table, nens otherwise).
 template <class TabPtr>
 PAMA_D void weno5_table(const double u[5], TabPtr tab, long long ts, const WenoConsts &wc, double &left,
                         double &right) {
 #pragma clang fp contract(off)
+  constexpr double EPS_TV = 1.0e-20;    // added to tv^2
   const double d[4] = {u[1] - u[0], u[2] - u[1], u[3] - u[2], u[4] - u[3]};
-  WenoLin p;
+  double a1[3], a2[3], tv[3];
 #pragma unroll
   for (int i = 0; i < 3; i++) {
-    p.a1[i] = fma(tab[(1 + 2 * i) * ts], d[i + 1], tab[(0 + 2 * i) * ts] * d[i]);
-    p.a2[i] = fma(tab[(7 + 2 * i) * ts], d[i + 1], tab[(6 + 2 * i) * ts] * d[i]);
+    a1[i] = fma(tab[(1 + 2 * i) * ts], d[i + 1], tab[(0 + 2 * i) * ts] * d[i]);
+    a2[i] = fma(tab[(7 + 2 * i) * ts], d[i + 1], tab[(6 + 2 * i) * ts] * d[i]);
+    tv[i] = fma(a1[i], a1[i], a2[i] * a2[i]);
   }
-  p.h1 = fma(tab[12 * ts], d[0], fma(tab[13 * ts], d[1], fma(tab[14 * ts], d[2], tab[15 * ts] * d[3])));
-  p.h2 = fma(tab[16 * ts], d[0], fma(tab[17 * ts], d[1], fma(tab[18 * ts], d[2], tab[19 * ts] * d[3])));
-  p.h3 = fma(tab[20 * ts], d[0], fma(tab[21 * ts], d[1], fma(tab[22 * ts], d[2], tab[23 * ts] * d[3])));
-  p.h4 = fma(tab[24 * ts], d[0], fma(tab[25 * ts], d[1], fma(tab[26 * ts], d[2], tab[27 * ts] * d[3])));
-  p.k2 = tab[28 * ts];
-  p.k4 = tab[29 * ts];
-  p.k2s = tab[30 * ts];
-  weno5_blend(u[2], p, wc, left, right);
+  // sqrt(R3) x the blended TV of the upper polynomial, a sum of four squares (VTable)
+  const double z0 = fma(tab[12 * ts], d[0], fma(tab[13 * ts], d[1], fma(tab[14 * ts], d[2], tab[15 * ts] * d[3])));
+  const double z1 = fma(tab[16 * ts], d[1], fma(tab[17 * ts], d[2], tab[18 * ts] * d[3]));
+  const double z2 = fma(tab[19 * ts], d[2], tab[20 * ts] * d[3]);
+  const double z3 = tab[21 * ts] * d[3];
+  const double tvb = fma(z0, z0, fma(z1, z1, fma(z2, z2, z3 * z3)));
+  const double e3 = fma(tab[22 * ts], d[0], fma(tab[23 * ts], d[1], fma(tab[24 * ts], d[2], tab[25 * ts] * d[3])));
+  const double o3 = fma(tab[26 * ts], d[0], fma(tab[27 * ts], d[1], fma(tab[28 * ts], d[2], tab[29 * ts] * d[3])));
+  const double d0 = fma(tv[0], tv[0], EPS_TV), d1 = fma(tv[1], tv[1] * WENO_R1, EPS_TV * WENO_R1);
+  const double d2 = fma(tv[2], tv[2], EPS_TV), d3 = fma(tvb, tvb, EPS_TV * WENO_R3);
+  weno5_tail(u[2], d0, d1, d2, d3, 1.0e-20 / weno_idl_c(0), a1, a2, e3, o3, tab[30 * ts], 0.5, wc, left, right);
 }
+
+// The factored form of the constant (uniform-grid) table: positive pivots, and every stored coefficient finite
+constexpr bool vertical_upper_ok() {
+  double piv[4] = {};
+  const VTable v = make_vtable(make_const_dtable(), csqrt_, piv);
+  for (int j = 0; j < 4; j++)
+    if (!(piv[j] > 0.0)) return false;
+  for (int m = 0; m < 10; m++)
+    if (!(cabs_(v.r[m]) < 1e100)) return false;
+  return v.r[0] > 0.0 && v.r[4] > 0.0 && v.r[7] > 0.0 && v.r[9] > 0.0;
+}
+static_assert(vertical_upper_ok(), "vertical table: the blended TV of the uniform grid must factor with positive pivots");
 
 // ------------------------------------------------------------------------------------------------
 // Arithmetic shared by the unfused stage (flux kernel + update kernel) and the fused x-sweep (flux_x_update_body).  The two
@@ -904,20 +950,17 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
     if (DIR == 2) zt.trip_end(f0);
     double Fpn = 0.0, Fn0 = 0.0;                           // DIFF: the previous face's normal-momentum flux; face 0's
     const double *fyn = FOLD ? fold_y + (long long)(1 + ncomp - P_U) * P.ncell + fbase : nullptr;
-#pragma clang loop unroll(disable)
-    for (int c = f0; c <= cloop; c++) {                    // window = cells c-2..c+2; face c lies between cells c-1 and c
-      if (DIR == 2) zt.trip_begin(c + 1);
-      const long long on = cell_off(c + 3);                // the next cell entering the window
-      const double nn = uni(pn + on)[eu], nm = mul_rn(uni(pr + on)[eu], nn), np_ = uni(pp + on)[eu];
+    // one trip: face c between cells c-1 and c, from the windows of cell c (cells c-2..c+2, in um / up / un)
+    auto trip = [&](int c, const double (&um)[5], const double (&up)[5], const double (&un)[5]) __attribute__((always_inline)) {
       double dyv = 0.0, rdzv = 0.0;
       if (FOLD) {
         dyv = uni(fyn + (long long)fold_cell(c) * g.cs)[eu];
         rdzv = zt.rdz(P, fold_cell(c), e);
       }
       double Lm, Rm, Lp, Rp, Ln, Rn;
-      weno(wm, c, Lm, Rm);
-      weno(wp, c, Lp, Rp);
-      weno(wn, c, Ln, Rn);
+      weno(um, c, Lm, Rm);
+      weno(up, c, Lp, Rp);
+      weno(un, c, Ln, Rn);
       const bool wall = (DIR == 2) && (c == 0 || c == P.nz);   // Dycore.h:477,482,496
       double ruf, ppf;
       acoustic_face(prevR_m, Lm, prevR_p, Lp, wall, ruf, ppf);
@@ -933,10 +976,41 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
         uniw(fln + (long long)c * g.cs)[eu] = fn;
       }
       prevR_m = Rm; prevR_p = Rp; prevR_n = Rn;
+    };
+    if constexpr (DIR == 2) {
+      // z: the windows rotate their slots as in the pair sweeps below (trip r of five uses the slots (r, .. r+4) mod 5 and overwrites
+      // slot r with the cell that enters): no window is moved, and neighbouring cells of a round share their differences.  The y
+      // sweep keeps moving windows: rotated, its three windows would also share second differences and their squares, and those
+      // live ranges cost the 128-register budget 108 B of scratch (docs/experiments.md).
+#pragma clang loop unroll(disable)
+      for (int c = f0; c <= cloop;) {
 #pragma unroll
-      for (int s = 0; s < 4; s++) { wm[s] = wm[s + 1]; wp[s] = wp[s + 1]; wn[s] = wn[s + 1]; }
-      wm[4] = nm; wp[4] = np_; wn[4] = nn;
-      if (DIR == 2) zt.trip_end(c + 1);
+        for (int r = 0; r < 5; r++) {
+          if (c > cloop) break;
+          if (DIR == 2) zt.trip_begin(c + 1);
+          const long long on = cell_off(c + 3);            // the next cell entering the window
+          const double nn = uni(pn + on)[eu], nm = mul_rn(uni(pr + on)[eu], nn), np_ = uni(pp + on)[eu];
+          const double um[5] = {wm[r % 5], wm[(r + 1) % 5], wm[(r + 2) % 5], wm[(r + 3) % 5], wm[(r + 4) % 5]};
+          const double up[5] = {wp[r % 5], wp[(r + 1) % 5], wp[(r + 2) % 5], wp[(r + 3) % 5], wp[(r + 4) % 5]};
+          const double un[5] = {wn[r % 5], wn[(r + 1) % 5], wn[(r + 2) % 5], wn[(r + 3) % 5], wn[(r + 4) % 5]};
+          trip(c, um, up, un);
+          wm[r % 5] = nm; wp[r % 5] = np_; wn[r % 5] = nn;
+          if (DIR == 2) zt.trip_end(c + 1);
+          c++;
+        }
+      }
+    } else {
+#pragma clang loop unroll(disable)
+      for (int c = f0; c <= cloop; c++) {
+        if (DIR == 2) zt.trip_begin(c + 1);
+        const long long on = cell_off(c + 3);              // the next cell entering the window
+        const double nn = uni(pn + on)[eu], nm = mul_rn(uni(pr + on)[eu], nn), np_ = uni(pp + on)[eu];
+        trip(c, wm, wp, wn);
+#pragma unroll
+        for (int s = 0; s < 4; s++) { wm[s] = wm[s + 1]; wp[s] = wp[s + 1]; wn[s] = wn[s + 1]; }
+        wm[4] = nm; wp[4] = np_; wn[4] = nn;
+        if (DIR == 2) zt.trip_end(c + 1);
+      }
     }
     if (reuse0) uniw(fln + (long long)(g.n - 1) * g.cs)[eu] = Fpn - Fn0;   // the last cell: closed by face n == face 0
   }

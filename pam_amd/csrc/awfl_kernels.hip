@@ -2370,6 +2370,7 @@ int pam_amd_awfl_init(const pam_amd_awfl_config_t *cfg, pam_amd_awfl_t **out) {
   for (size_t i = 0; i < nzn; i++)
     if (!(dz_host[i] > 0)) return bail(PAM_AMD_EINVAL, "init: vertical_cell_dz must be positive (set_grid not called?)");
   VerticalTables vt = build_vertical_tables(dz_host.data(), P.nz, P.nens);
+  if (!vt.pivots_ok) return bail(PAM_AMD_EINVAL, "init: vertical WENO table: the blended TV form is not positive definite at some level");
   P.vz_per_ens = vt.per_ens ? 1 : 0;
 
   h->n_prim = (size_t)(6 + P.nt) * P.prim_fs;

@@ -6,9 +6,10 @@
 // The reference inverts with yakl::intrinsics::matinv_ge, a third-party routine absent from the tree (YAKL
 // submodule, version unpinned); here it is Gauss-Jordan elimination without pivoting, (col,row) order.
 //
-// Output per level (and per ensemble member): VZ_STRIDE = 31 doubles, the difference-form table `DTable` of
-// awfl_device.h (make_dtable): lower-candidate x / x^2 / even-edge coefficients and the bridged upper polynomial
-// (WenoLimiter.h:128-136 folded in; linear in the stencil, so exact up to rounding).
+// Output per level (and per ensemble member): VZ_STRIDE = 31 doubles, the stored table `VTable` of awfl_device.h
+// (make_dtable, then make_vtable): lower-candidate x / x^2 / even-edge coefficients and the bridged upper polynomial
+// (WenoLimiter.h:128-136 folded in; linear in the stencil, so exact up to rounding) as the Cholesky factor of its
+// blended TV and the rows of its even and odd parts.
 // The stencil-form vert_sten_to_coefs / vert_weno_recon_lower are also returned for the DataManager entries of
 // those names.
 #pragma once
@@ -78,13 +79,15 @@ inline void build_pow_tab(PowTab &T) {
 
 struct VerticalTables {
   bool per_ens;                 // false: all ensemble members share one dz column
+  bool pivots_ok = true;        // every level's blended-TV form factored with positive pivots (make_vtable)
   std::vector<double> table;    // (nz+2,VZ_STRIDE) or (nz+2,VZ_STRIDE,nens)
   std::vector<double> s2c;      // vert_sten_to_coefs    (nz+2,5,5,nens)
   std::vector<double> wrl;      // vert_weno_recon_lower (nz+2,3,3,3,nens)
 };
 
-inline void level_matrices(const double *dzcol /* stride nens */, long long stride, int nz, int k, double s2c[25],
-                           double wrl[27], double dform[VZ_STRIDE]) {
+// the level's DTable (and the stencil-form matrices it is made from)
+inline DTable level_dtable(const double *dzcol /* stride nens */, long long stride, int nz, int k, double s2c[25],
+                           double wrl[27]) {
   double dzloc[5], locs[6];
   for (int kk = 0; kk < 5; kk++) {
     int ind1 = std::min(nz - 1, std::max(0, -1 + k + kk));
@@ -111,15 +114,19 @@ inline void level_matrices(const double *dzcol /* stride nens */, long long stri
       for (int ii = 0; ii < 3; ii++) lo[i][s][ii] = wrl[(i * 3 + s) * 3 + ii];
   for (int s = 0; s < 5; s++)
     for (int ii = 0; ii < 5; ii++) hi[s][ii] = s2c[s * 5 + ii];
-  DTable t = make_dtable(lo, hi, idl, locs[3] - locs[2]);   // width of the centre cell in the matrices' coordinate
-  static_assert(sizeof(DTable) == (VZ_STRIDE - 1) * sizeof(double), "DTable layout");
-  // stored form: the x^2 rows of the lower candidates times sqrt(13/3) (their TV is then a1^2 + a2'^2), and the matching
-  // even-part factor behind the struct (awfl_device.h: DTable, weno5_blend)
-  const double sq = std::sqrt(AWFL_TV3_A2A2);
-  for (int i = 0; i < 3; i++)
-    for (int q = 0; q < 2; q++) t.lo2[i][q] *= sq;
-  std::memcpy(dform, &t, sizeof(t));
-  dform[VZ_STRIDE - 1] = t.k2 / sq;
+  return make_dtable(lo, hi, idl, locs[3] - locs[2]);   // width of the centre cell in the matrices' coordinate
+}
+
+// the level's stored table (awfl_device.h: VTable); false if its blended-TV form did not factor with positive pivots
+inline bool level_matrices(const double *dzcol /* stride nens */, long long stride, int nz, int k, double s2c[25],
+                           double wrl[27], double dform[VZ_STRIDE]) {
+  double piv[4];
+  const VTable v = make_vtable(level_dtable(dzcol, stride, nz, k, s2c, wrl), [](double x) { return std::sqrt(x); }, piv);
+  std::memcpy(dform, &v, sizeof(v));
+  bool ok = true;
+  for (int j = 0; j < 4; j++) ok = ok && piv[j] > 0.0;
+  for (int m = 0; m < VZ_STRIDE; m++) ok = ok && std::isfinite(dform[m]);
+  return ok;
 }
 
 // dz: host copy of vertical_cell_dz (nz,nens)
@@ -136,7 +143,7 @@ inline VerticalTables build_vertical_tables(const double *dz, int nz, int nens) 
   for (int k = 0; k < nl; k++) {
     double s2c[25], wrl[27], br[VZ_STRIDE];
     for (int e = 0; e < nens; e++) {
-      if (e == 0 || vt.per_ens) level_matrices(dz + e, nens, nz, k, s2c, wrl, br);
+      if (e == 0 || vt.per_ens) vt.pivots_ok = level_matrices(dz + e, nens, nz, k, s2c, wrl, br) && vt.pivots_ok;
       for (int m = 0; m < 25; m++) vt.s2c[((size_t)k * 25 + m) * nens + e] = s2c[m];
       for (int m = 0; m < 27; m++) vt.wrl[((size_t)k * 27 + m) * nens + e] = wrl[m];
       if (vt.per_ens) {

@@ -2,8 +2,9 @@
 """Per-polynomial FP64 instruction ledger of the WENO reconstruction (gfx950 device assembly, no GPU needed).
 
 usage: python tools/weno_ledger.py [awfl_kernels.s]
-  1. weno5_const and weno5_table (the wave-uniform table, as the C2 z sweep reads it), each compiled alone into a kernel that
-     reconstructs ONE polynomial: FP64 / all VALU instructions of the kernel (a handful of them are the kernel's own loads / stores).
+  1. weno5_const and weno5_table (the wave-uniform table, as the C2 z sweep reads it: struct VTable, whose upper polynomial is the
+     Cholesky rows of its blended TV and the rows of its even and odd parts), each compiled alone into a kernel that reconstructs ONE
+     polynomial: FP64 / all VALU instructions of the kernel (a handful of them are the kernel's own loads / stores).
   2. the loops of the hot kernels (tools/isa_loops.py) in the given assembly of pam_amd/csrc/awfl_kernels.hip, compiled here when no
      file is given:  awfl_flux_kernel<false,true,false,false> (C2's y + z sweeps: the pass-1 loops, then the pair loops, whose
      rows make five trips of two fields per round -- the per-polynomial column divides them by 10) and
@@ -59,7 +60,7 @@ def main():
         open(src, "w").write(SINGLE)
         subprocess.run([HIPCC] + FLAGS + ["-I", os.path.join(ROOT, "pam_amd", "csrc"), src, "-o", asm], check=True)
         print("%-44s %6s %6s" % ("one polynomial", "f64", "VALU"))
-        for k, label in (("ledger_const", "weno5_const (x, y)"), ("ledger_table", "weno5_table (z, wave-uniform table)")):
+        for k, label in (("ledger_const", "weno5_const (x, y)"), ("ledger_table", "weno5_table (z, factored wave-uniform table)")):
             f, v = kernel_counts(asm, k)
             print("%-44s %6d %6d" % (label, f, v))
         big = sys.argv[1] if len(sys.argv) > 1 else None
