@@ -1144,14 +1144,34 @@ struct pam_amd_awfl {
   int *seq_dev = nullptr;      // device word: fct_seq at the start of the replayed step
   hipStream_t gstream = nullptr;
   hipEvent_t g_fork = nullptr, g_join = nullptr;
-  int lane_mode = 0;           // 0 automatic, 1 member lanes, 2 flat (x, member) lanes (pam_amd_awfl_set_lane_mapping)
-  bool flat = false;           // resolved lane mapping of the fused stage: flat lanes over (x, member) (small ensembles)
-  bool flat_supported = false; // every lane offset fits the 28 bits of the scalar-base + lane-offset addressing
-  int xtile_mode = 0;          // 0 automatic, 1 sweep kernels (a wavefront per line span), 2 tile kernels (a lane per cell)
-  bool xtile = false;          // resolved: the x direction of the fused stage runs as tile kernels
-  int xt_w = 0, xt_tc = 0, xt_lpb = 0;   // tile geometry overrides (0 = automatic)
-  int xshuf_mode = 0;          // x tile kernels, exchange between neighbouring cells: 0 automatic, 1 through LDS, 2 wavefront shuffles
-  bool xshuf = false;          // resolved: wavefront shuffles (a whole periodic line of a tile lies inside one wavefront)
+  // What the setters asked for (0 = automatic throughout) ...
+  struct Want {
+    int lanes = 0;             // 0 automatic, 1 member lanes, 2 flat (x, member) lanes (pam_amd_awfl_set_lane_mapping)
+    int xtile = 0;             // 0 automatic, 1 sweep kernels (a wavefront per line span), 2 tile kernels (a lane per cell)
+    int xt_w = 0, xt_tc = 0, xt_lpb = 0;   // tile geometry overrides (0 = automatic)
+    int xshuf = 0;             // x tile kernels, exchange between neighbouring cells: 0 automatic, 1 through LDS, 2 wavefront shuffles
+    int tail_fuse = 0;         // NT > 1: phase 2 + pressure pass + vapour fix-up as one launch: 0 automatic (on), 1 off, 2 on
+    int fold = 0;              // y differences of the state folded into the z sweep's output (P.yz_fold): 0 automatic, 1 off, 2 on
+    int tile_pressure = 0;     // 0 automatic, 1 separate pressure pass, 2 inside the x tile kernel
+    int tile_state_parts = 0;  // 0 automatic, 1 one lane does the whole state pass, 2 three parts
+    int ftile = 0;             // 0 automatic, 1 flat-lane sweeps, 2 tile kernel
+    int ft_tc_y = 0, ft_tc_z = 0;          // cells / levels per y / z tile (0 = automatic)
+    int ftile_parts = 0;       // 0 automatic, 1 the parts of a tile behind each other (one workgroup), 2 beside each other
+  } want;
+  // ... and what resolve_lane_mapping derives from it (with P.flat_cells and P.yz_fold) for the launches to read
+  struct Use {
+    bool flat = false;           // lane mapping of the fused stage: flat lanes over (x, member) (small ensembles)
+    bool flat_supported = false; // every lane offset fits the 28 bits of the scalar-base + lane-offset addressing
+    bool xtile = false;          // the x direction of the fused stage runs as tile kernels
+    bool xshuf = false;          // wavefront shuffles (a whole periodic line of a tile lies inside one wavefront)
+    XTileGeom xg;
+    bool tile_pressure = true;   // x tile kernels: the next stage's pressure inside awfl_xupd_tile_kernel (no awfl_ptail_kernel launch)
+    bool tile_state_parts = false;        // ... and the state pass itself in three parts beside each other (XP_U / XP_VW / XP_T)
+    bool tile_tracers_parallel = false;   // ... and phase 1 of the further tracers in z slices of that launch BESIDE the state pass (idle CUs)
+    bool ftile = true;           // flat lanes: the y/z fluxes as ONE tile kernel (a lane per cell) instead of flat-lane sweeps
+    int ft_auto_y = 0, ft_auto_z = 0;     // its automatic tile sizes (choose_flux_tiles; 0 = ftile_geometry's own default)
+    bool ftile_parts = false;    // the parts of a flux tile beside each other
+  } use;
   // the reference's PAM_DEBUG conservation check as an opt-in (pam_amd_awfl_set_debug_conservation): masses before / after a timeStep
   bool debug_mass = false;
   double *mass_dev = nullptr;  // (2, nt + 2, nens): before, after
@@ -1159,23 +1179,9 @@ struct pam_amd_awfl {
   double mass_max_rel = 0.0;
   std::string mass_report;
   struct { bool armed = false; int ivar, k, j, i, e; double factor; } fault;   // one-shot test hook
-  int tail_fuse_mode = 0;      // NT > 1: phase 2 + pressure pass + vapour fix-up as one launch: 0 automatic (on), 1 off, 2 on
-  int fold_mode = 0;           // y differences of the state folded into the z sweep's output (P.yz_fold): 0 automatic, 1 off, 2 on
   double *rdz = nullptr;       // (nz, nens) fast_rcp(dz)
   bool independent_ranges = true;    // fused stage, several member ranges: each range's whole stage on its own stream
-  int tile_pressure_mode = 0;  // 0 automatic, 1 separate pressure pass, 2 inside the x tile kernel
-  bool tile_pressure = true;   // x tile kernels: the next stage's pressure inside awfl_xupd_tile_kernel (no awfl_ptail_kernel launch)
-  bool tile_state_parts = false;        // ... and the state pass itself in three parts beside each other (XP_U / XP_VW / XP_T)
-  int tile_state_parts_mode = 0;        // 0 automatic, 1 one lane does the whole state pass, 2 three parts
-  bool tile_tracers_parallel = false;   // ... and phase 1 of the further tracers in z slices of that launch BESIDE the state pass (idle CUs)
-  int ftile_mode = 0;          // 0 automatic, 1 flat-lane sweeps, 2 tile kernel
-  bool ftile = true;           // resolved -- flat lanes: the y/z fluxes as ONE tile kernel (a lane per cell) instead of flat-lane sweeps
-  int ft_tc_y = 0, ft_tc_z = 0;          // cells / levels per y / z tile (0 = automatic)
-  int ft_auto_y = 0, ft_auto_z = 0;      // ... the automatic choice (choose_flux_tiles; 0 = ftile_geometry's own default)
-  int ftile_parts_mode = 0;              // 0 automatic, 1 the parts of a tile behind each other (one workgroup), 2 beside each other
-  bool ftile_parts = false;              // resolved
   int ncu = 0;                           // compute units of the handle's device
-  XTileGeom xg;
   bool fused = true;           // fused x-sweep + state update (needs the third state buffer prim2)
   size_t flux_lds_floor = 0;   // tuning: dynamic LDS requested per flux workgroup (the kernel uses none: a residency cap per CU)
   long long want_units = 3072, two_phase_below = 8192, split_below = 8192;   // launch-shape thresholds (pam_amd_awfl_set_handle_launch_tuning)
@@ -1295,38 +1301,124 @@ static void choose_span(const pam_amd_awfl *h, int nfaces, long long nlines, int
   nspan = (nfaces + span - 1) / span;
 }
 
+// f(std::integral_constant<int, st>()): the stage number of a launch as the template argument of its kernels.  The variants of one
+// kernel template share a signature, so f returns the variant to launch as an ordinary function pointer.
+template <class F>
+auto by_stage(int st, F &&f) {
+  switch (st) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    default: return f(std::integral_constant<int, 3>());
+  }
+}
+
+// One tendency stage of one member range: its number, input, sub-step start (base) and output buffers (the output differs from both in
+// the fused stage), the sub-step length and the stage's share of it.
+struct StageArgs { int st; const double *in, *base; double *out; double dt_dyn, dt_stage; };
+
+// one launch under the timer `name`
+template <class... KParams, class... Args>
+int launch(pam_amd_awfl *h, const char *name, void (*kernel)(KParams...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args &...args) {
+  ScopedTimer st(h, name, s);
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+  HIP_TRY(hipGetLastError());
+  return PAM_AMD_OK;
+}
+
+// Launch shape of the y/z flux TILE kernel for (cells per y tile, levels per z tile; 0 = ftile_geometry's own choice): nby workgroups of
+// y tiles, then nbz of z tiles, all of T lanes -- the larger of the two tiles in whole wavefronts (at most ftile_max_threads(P))
+struct FTileShape { FTileGeom Gy, Gz; int gyx; long long nby, nbz; int T; };
+FTileShape ftile_shape(const Params &P, int tc_y, int tc_z) {
+  FTileShape S;
+  S.Gy = ftile_geometry(P, 1, tc_y); S.Gz = ftile_geometry(P, 2, tc_z);
+  S.gyx = S.Gy.nch * S.Gy.ntl;
+  S.nby = P.sim2d ? 0 : (long long)S.gyx * ((P.nz + S.Gy.lpb - 1) / S.Gy.lpb);
+  S.nbz = (long long)S.Gz.nch * S.Gz.ntl;
+  S.T = ftile_threads(S.Gz);
+  if (!P.sim2d && ftile_threads(S.Gy) > S.T) S.T = ftile_threads(S.Gy);
+  S.T = ((S.T + 63) / 64) * 64;
+  return S;
+}
+// ... with the handle's tile sizes: the ones asked for, else the automatic choice
+FTileShape ftile_shape(const pam_amd_awfl *h) {
+  return ftile_shape(h->P, h->want.ft_tc_y ? h->want.ft_tc_y : h->use.ft_auto_y, h->want.ft_tc_z ? h->want.ft_tc_z : h->use.ft_auto_z);
+}
+
+// flat lanes, small grids: the y and z fluxes as one tile kernel, a lane per cell, both directions in one launch
+int launch_flux_tiles(pam_amd_awfl *h, const double *prim, hipStream_t s) {
+  const Params &P = h->P;
+  const FTileShape S = ftile_shape(h);
+  FTileGroups Q;
+  Q.ny_groups = ftile_groups(P, 1, Q.gy, FT_MAXG);
+  Q.nz_groups = ftile_groups(P, 2, Q.gz, FT_MAXG);
+  if (S.T > ftile_max_threads(P)) return fail(PAM_AMD_EINVAL, "flux tile launch: a tile must fit a workgroup of 1024 lanes (512 with per-member vertical grids)");
+  const size_t lds = (size_t)(2 * FT_NG + 4) * S.T * sizeof(double);
+  // the parts of a tile (acoustic triple, groups of advected quantities) beside each other in workgroups of their own -- grid.y --
+  // while every workgroup still finds a CU of its own (choose: resolve_lane_mapping), else behind each other in one workgroup
+  const int maxg = Q.ny_groups > Q.nz_groups ? Q.ny_groups : Q.nz_groups;
+  const int parts = h->use.ftile_parts ? 1 : 0;
+  const dim3 grid((unsigned)(S.nby + S.nbz), parts ? (unsigned)(1 + maxg) : 1u, 1u);
+  return launch(h, "flux", P.vz_per_ens ? awfl_flux_tile_kernel<true> : awfl_flux_tile_kernel<false>, grid, dim3(S.T), lds, s, P, S.Gy, S.Gz, Q,
+                (int)S.nby, S.gyx > 0 ? S.gyx : 1, prim, h->flux_y, h->flux_z, parts);
+}
+
+// What the launches of one flux sweep call share: the spans (G), the wavefronts per sweep of one member block (ux0 / uy0 / uz0), the
+// member blocks of the range, and which form of the sweeps runs
+struct FluxSweeps {
+  FluxGrid G;
+  long long ux0, uy0, uz0, nblk;
+  int npairs;               // advected fields besides the normal velocity, two per sweep
+  bool diff, flat, two_phase, fold, pe;
+  size_t lds_bytes;
+};
+
+// One launch: the sweeps of `mask` (bit 0 x, bit 1 y, bit 2 z), whole (`part` -1), or pass 1 (0) or the pairs (1) of a two-phase sweep
+int launch_flux_part(pam_amd_awfl *h, const FluxSweeps &F, int mask, int part, const double *prim, EnsRange r, hipStream_t s) {
+  const Params &P = h->P;
+  FluxGrid G = F.G;
+  const bool zonly = (mask == 4);
+  G.part = part;
+  G.npx = G.npy = G.npz = F.npairs;
+  const long long mult = (part == 1) ? F.npairs : 1;
+  G.nux = (mask & 1) ? (int)(F.ux0 * F.nblk * mult) : 0; G.nuy = (mask & 2) ? (int)(F.uy0 * F.nblk * mult) : 0; G.nuz = (mask & 4) ? (int)(F.uz0 * F.nblk * mult) : 0;
+  G.nbx = (G.nux + FLUX_WAVES - 1) / FLUX_WAVES; G.nby = (G.nuy + FLUX_WAVES - 1) / FLUX_WAVES; G.nbz = (G.nuz + FLUX_WAVES - 1) / FLUX_WAVES;
+  G.nbx_l = G.nby_l = 0;
+  if (!F.two_phase && !P.sim2d && G.nux > 0 && G.nuy > 0 && G.nux % (FLUX_WAVES * P.nz) == 0 && G.nuy % (FLUX_WAVES * P.nz) == 0) {
+    G.nbx_l = G.nbx / P.nz;
+    G.nby_l = G.nby / P.nz;
+  }
+  if (G.nbx + G.nby + G.nbz == 0) return PAM_AMD_OK;
+  const bool fold = F.fold && zonly;
+  if (F.pe && zonly) {
+    // member-block-major workgroups of ZPE_WAVES columns each (awfl_fluxz_pe_kernel)
+    const long long ncg = ((long long)P.ny * P.nx + ZPE_WAVES - 1) / ZPE_WAVES;
+    const long long nwg = F.nblk * ncg * G.nsz * mult;
+    if (nwg > 0x3fffffffll) return fail(PAM_AMD_EINVAL, "flux launch: more than 2^30 workgroups in one launch");
+    const auto kernel = !F.diff ? awfl_fluxz_pe_kernel<false, false> : fold ? awfl_fluxz_pe_kernel<true, true> : awfl_fluxz_pe_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(64 * ZPE_WAVES), 0, s, P, r, G.spz, G.nsz, G.part, F.npairs, prim, h->flux_y, h->flux_z);
+  } else {
+    // (member lanes with per-member grids: only the z sweep reads tables, and it is not in this launch)
+    const auto kernel = F.flat  ? (P.vz_per_ens ? awfl_flux_kernel<true, true, true, false> : awfl_flux_kernel<false, true, true, false>)
+                        : fold   ? awfl_flux_kernel<false, true, false, true>
+                        : F.diff ? awfl_flux_kernel<false, true, false, false>
+                                 : awfl_flux_kernel<false, false, false, false>;
+    hipLaunchKernelGGL(kernel, dim3(G.nbx + G.nby + G.nbz), dim3(FLUX_THREADS), F.lds_bytes, s, P, G, r, prim, h->flux_x, h->flux_y, h->flux_z);
+  }
+  HIP_TRY(hipGetLastError());
+  return PAM_AMD_OK;
+}
+
 // sweeps: bit 0 x, bit 1 y, bit 2 z (the fused stage runs y and z here and x in awfl_xupd_kernel / awfl_xupd_tile_kernel)
 int launch_flux(pam_amd_awfl *h, const double *prim, EnsRange r, hipStream_t s, int sweeps = 7, bool diff = false) {
   const Params &P = h->P;
-  FluxGrid G;
+  FluxSweeps F;
+  FluxGrid &G = F.G;
   if (diff && (sweeps & 1)) return fail(PAM_AMD_EINVAL, "flux launch: the difference form has no x sweep");
   // flat lanes (small ensembles): the y/z sweeps of the fused stage take 64 consecutive items of (level | y, x, member) per
   // wavefront instead of 64 members of one line; one range = the whole ensemble
-  const bool flat = h->flat && diff;
+  const bool flat = h->use.flat && diff;
   if (flat && (r.e0 != 0 || r.ne != P.nens)) return fail(PAM_AMD_EINVAL, "flux launch: flat lanes sweep the whole ensemble in one range");
-  if (flat && h->ftile && sweeps == 6) {
-    // tile kernel: a lane per cell, both directions in one launch (small ensembles)
-    const FTileGeom Gy = ftile_geometry(P, 1, h->ft_tc_y ? h->ft_tc_y : h->ft_auto_y), Gz = ftile_geometry(P, 2, h->ft_tc_z ? h->ft_tc_z : h->ft_auto_z);
-    FTileGroups Q;
-    Q.ny_groups = ftile_groups(P, 1, Q.gy, FT_MAXG);
-    Q.nz_groups = ftile_groups(P, 2, Q.gz, FT_MAXG);
-    const int gyx = Gy.nch * Gy.ntl, nby = P.sim2d ? 0 : gyx * ((P.nz + Gy.lpb - 1) / Gy.lpb), nbz = Gz.nch * Gz.ntl;
-    int T = ftile_threads(Gz);
-    if (!P.sim2d && ftile_threads(Gy) > T) T = ftile_threads(Gy);
-    T = ((T + 63) / 64) * 64;
-    if (T > ftile_max_threads(P)) return fail(PAM_AMD_EINVAL, "flux tile launch: a tile must fit a workgroup of 1024 lanes (512 with per-member vertical grids)");
-    const size_t lds = (size_t)(2 * FT_NG + 4) * T * sizeof(double);
-    ScopedTimer st(h, "flux", s);
-    // the parts of a tile (acoustic triple, groups of advected quantities) beside each other in workgroups of their own -- grid.y --
-    // while every workgroup still finds a CU of its own (choose: resolve_lane_mapping), else behind each other in one workgroup
-    const int maxg = Q.ny_groups > Q.nz_groups ? Q.ny_groups : Q.nz_groups;
-    const int parts = h->ftile_parts ? 1 : 0;
-    const dim3 fgrid((unsigned)(nby + nbz), parts ? (unsigned)(1 + maxg) : 1u, 1u);
-    if (P.vz_per_ens) hipLaunchKernelGGL(awfl_flux_tile_kernel<true>, fgrid, dim3(T), lds, s, P, Gy, Gz, Q, nby, gyx > 0 ? gyx : 1, prim, h->flux_y, h->flux_z, parts);
-    else hipLaunchKernelGGL(awfl_flux_tile_kernel<false>, fgrid, dim3(T), lds, s, P, Gy, Gz, Q, nby, gyx > 0 ? gyx : 1, prim, h->flux_y, h->flux_z, parts);
-    HIP_TRY(hipGetLastError());
-    return PAM_AMD_OK;
-  }
+  if (flat && h->use.ftile && sweeps == 6) return launch_flux_tiles(h, prim, s);
   const long long gy = flat ? (flat_items(P, 1) + 63) / 64 : (long long)P.nz * P.nx;   // groups of 64 lanes per member block (member lanes: lines)
   const long long gz = flat ? (flat_items(P, 2) + 63) / 64 : (long long)P.ny * P.nx;
   const int ens_for_span = flat ? 1 : P.nens;
@@ -1335,74 +1427,38 @@ int launch_flux(pam_amd_awfl *h, const double *prim, EnsRange r, hipStream_t s, 
   choose_span(h, P.ny, gy, ens_for_span, P.seg, h->span_override, G.spy, G.nsy);
   choose_span(h, P.nz + 1, gz, ens_for_span, P.seg, h->span_override, G.spz, G.nsz);
   if (diff) { G.spy = P.ny; G.nsy = 1; }   // difference form: a periodic line is swept whole (its last cell needs face n == face 0)
-  const long long nblk = flat ? 1 : (r.ne + 63) / 64;     // member lanes: a wavefront = 64 consecutive members of ONE line
+  F.diff = diff; F.flat = flat;
+  F.nblk = flat ? 1 : (r.ne + 63) / 64;     // member lanes: a wavefront = 64 consecutive members of ONE line
   const long long nblk_all = flat ? 1 : (P.nens + 63) / 64;
-  const long long ux0 = (sweeps & 1) ? (long long)P.nz * P.ny * G.nsx : 0;
-  const long long uy0 = (P.sim2d || !(sweeps & 2)) ? 0 : gy * G.nsy;
-  const long long uz0 = (sweeps & 4) ? gz * G.nsz : 0;
+  F.ux0 = (sweeps & 1) ? (long long)P.nz * P.ny * G.nsx : 0;
+  F.uy0 = (P.sim2d || !(sweeps & 2)) ? 0 : gy * G.nsy;
+  F.uz0 = (sweeps & 4) ? gz * G.nsz : 0;
+  const long long units0 = F.ux0 + F.uy0 + F.uz0;
   // Small ensembles: a wavefront that sweeps its span for pass 1 and then for every pair of advected fields, one after the
   // other, is a long serial chain on a mostly empty chip.  Then pass 1 runs in a launch of its own (`part` 0) and the pairs in a
   // second one with one wavefront per (span, pair) (`part` 1); decided from the WHOLE ensemble (chunking-independent).
-  const int npairs = flux_sweep_pairs(P, diff);   // advected fields besides the normal velocity, two per sweep
+  F.npairs = flux_sweep_pairs(P, diff);
   // (round 5, measured and removed -- commit 38c84c8, profiles/r05_ab_experiments.txt: the two parts as kernels of their own, each with
   // its own register count -- pass 1 alone 127, pairs 118, one field per wavefront 86 registers -- C4 flux 0.121 -> 0.126 / 0.127 ms,
   // C3 0.411 -> 0.414 / 0.434: the whole-sweep kernel at 128 registers already runs 4 wavefronts per SIMD)
-  const bool two_phase = (ux0 + uy0 + uz0) * nblk_all < h->two_phase_below;
-  const int nphase = two_phase ? 2 : 1;
-  if ((ux0 + uy0 + uz0) * nblk * (two_phase ? npairs : 1) > 0x3fffffffll)
+  F.two_phase = units0 * nblk_all < h->two_phase_below;
+  if (units0 * F.nblk * (F.two_phase ? F.npairs : 1) > 0x3fffffffll)
     return fail(PAM_AMD_EINVAL, "flux launch: more than 2^30 wavefronts in one launch");
   // the kernel uses no LDS; a dynamic LDS request only caps its residency per CU when other kernels should co-reside
-  size_t lds_bytes = 0;
-  if (h->chunks.size() > 1) lds_bytes = h->flux_lds_floor;
+  F.lds_bytes = h->chunks.size() > 1 ? h->flux_lds_floor : 0;
   // The z sweep in a launch of its own, BEHIND the x / y sweeps, in two cases:
   //   fold   (fused stage, 3-D, member lanes: P.yz_fold) it reads the y sweep's differences of the state variables and stores the y+z part
   //          of their divergence, one field per variable, which is all the x-sweep then loads (yz_divergence in awfl_device.h);
   //   pe     per-member vertical grids with member lanes: awfl_fluxz_pe_kernel (the levels' tables staged in LDS per workgroup)
-  const bool fold = diff && P.yz_fold && !flat && (sweeps & 6) == 6;
-  const bool pe = P.vz_per_ens && !flat && (sweeps & 4);
-  const int nsub = ((fold || pe) && (sweeps & 3)) ? 2 : 1;
+  F.fold = diff && P.yz_fold && !flat && (sweeps & 6) == 6;
+  F.pe = P.vz_per_ens && !flat && (sweeps & 4);
+  const int nsub = ((F.fold || F.pe) && (sweeps & 3)) ? 2 : 1;
   ScopedTimer st(h, "flux", s);
   for (int sub = 0; sub < nsub; sub++) {
-  const int mask = nsub == 1 ? sweeps : (sub == 0 ? (sweeps & 3) : (sweeps & 4));
-  const bool zonly = (mask == 4);
-  ScopedTimer st2(h, nsub == 1 ? "flux_all" : (sub == 0 ? "flux_xy" : "flux_z"), s);
-  for (int phase = 0; phase < nphase; phase++) {
-  G.part = two_phase ? phase : -1;
-  G.npx = G.npy = G.npz = npairs;
-  const long long mult = (G.part == 1) ? npairs : 1;
-  G.nux = (mask & 1) ? (int)(ux0 * nblk * mult) : 0; G.nuy = (mask & 2) ? (int)(uy0 * nblk * mult) : 0; G.nuz = (mask & 4) ? (int)(uz0 * nblk * mult) : 0;
-  G.nbx = (G.nux + FLUX_WAVES - 1) / FLUX_WAVES; G.nby = (G.nuy + FLUX_WAVES - 1) / FLUX_WAVES;
-  G.nbz = (G.nuz + FLUX_WAVES - 1) / FLUX_WAVES;
-  G.nbx_l = G.nby_l = 0;
-  if (!two_phase && !P.sim2d && G.nux > 0 && G.nuy > 0 && G.nux % (FLUX_WAVES * P.nz) == 0 && G.nuy % (FLUX_WAVES * P.nz) == 0) {
-    G.nbx_l = G.nbx / P.nz;
-    G.nby_l = G.nby / P.nz;
-  }
-  if (G.nbx + G.nby + G.nbz == 0) continue;
-  if (pe && zonly) {
-    // member-block-major workgroups of ZPE_WAVES columns each (awfl_fluxz_pe_kernel)
-    const long long ncg = ((long long)P.ny * P.nx + ZPE_WAVES - 1) / ZPE_WAVES;
-    const long long nwg = nblk * ncg * G.nsz * mult;
-    if (nwg > 0x3fffffffll) return fail(PAM_AMD_EINVAL, "flux launch: more than 2^30 workgroups in one launch");
-    const dim3 zgrid((unsigned)nwg), zblock(64 * ZPE_WAVES);
-    const bool f = fold && zonly;
-#define PAMA_LAUNCH_ZPE(DF, FO)                                                                                         \
-  hipLaunchKernelGGL((awfl_fluxz_pe_kernel<DF, FO>), zgrid, zblock, 0, s, P, r, G.spz, G.nsz, G.part, npairs, prim, h->flux_y, h->flux_z)
-    if (!diff) PAMA_LAUNCH_ZPE(false, false); else if (f) PAMA_LAUNCH_ZPE(true, true); else PAMA_LAUNCH_ZPE(true, false);
-#undef PAMA_LAUNCH_ZPE
-    HIP_TRY(hipGetLastError());
-    continue;
-  }
-  const dim3 grid(G.nbx + G.nby + G.nbz), block(FLUX_THREADS);
-#define PAMA_LAUNCH_FLUX(VZ, DF, FL, FO)                                                                                \
-  hipLaunchKernelGGL((awfl_flux_kernel<VZ, DF, FL, FO>), grid, block, lds_bytes, s, P, G, r, prim, h->flux_x, h->flux_y, h->flux_z)
-  if (flat) { if (P.vz_per_ens) PAMA_LAUNCH_FLUX(true, true, true, false); else PAMA_LAUNCH_FLUX(false, true, true, false); }
-  else if (fold && zonly) PAMA_LAUNCH_FLUX(false, true, false, true);
-  else if (diff) PAMA_LAUNCH_FLUX(false, true, false, false);      // (per-member grids: only the z sweep reads tables, and it is not in this launch)
-  else PAMA_LAUNCH_FLUX(false, false, false, false);
-#undef PAMA_LAUNCH_FLUX
-  HIP_TRY(hipGetLastError());
-  }
+    const int mask = nsub == 1 ? sweeps : (sub == 0 ? (sweeps & 3) : (sweeps & 4));
+    ScopedTimer st2(h, nsub == 1 ? "flux_all" : (sub == 0 ? "flux_xy" : "flux_z"), s);
+    for (int phase = 0; phase < (F.two_phase ? 2 : 1); phase++)
+      if (int rc = launch_flux_part(h, F, mask, F.two_phase ? phase : -1, prim, r, s)) return rc;
   }
   return PAM_AMD_OK;
 }
@@ -1437,21 +1493,14 @@ FctRows fct_rows(const pam_amd_awfl *h, EnsRange r, bool sparse_store) {
 
 // (three-kernel stage only: in the fused stage every tracer's multiplier comes out of its x-sweep)
 int launch_fct(pam_amd_awfl *h, double dt, EnsRange r, hipStream_t s) {
-  ScopedTimer st(h, "fct_mult", s);
-  hipLaunchKernelGGL(awfl_fct_kernel, cell_grid(h->P, r), dim3(256), 0, s, h->P, r, h->flux_x, h->flux_y,
-                     h->flux_z, h->seed, h->mult, fct_rows(h, r, false), dt, 0);
-  HIP_TRY(hipGetLastError());
-  return PAM_AMD_OK;
+  return launch(h, "fct_mult", awfl_fct_kernel, cell_grid(h->P, r), dim3(256), 0, s, h->P, r, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult,
+                fct_rows(h, r, false), dt, 0);
 }
 
-template <int STAGE>
-int launch_update(pam_amd_awfl *h, const double *prim_in, const double *prim0, double *prim_out, double dt_dyn, EnsRange r,
-                  hipStream_t s) {
-  ScopedTimer st(h, "update", s);
-  hipLaunchKernelGGL(awfl_update_kernel<STAGE>, cell_grid(h->P, r), dim3(256), 0, s, h->P, r, prim_in,
-                     prim0, prim_out, h->flux_x, h->flux_y, h->flux_z, h->mult, fct_rows(h, r, false), h->seed, dt_dyn);
-  HIP_TRY(hipGetLastError());
-  return PAM_AMD_OK;
+int launch_update(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStream_t s) {
+  const auto kernel = by_stage(a.st, [](auto S) { return awfl_update_kernel<S()>; });
+  return launch(h, "update", kernel, cell_grid(h->P, r), dim3(256), 0, s, h->P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z, h->mult,
+                fct_rows(h, r, false), h->seed, a.dt_dyn);
 }
 
 // Can the last three launches of a stage -- phase 2 of the further tracers, the pressure pass, water vapour's fix-up -- go out as ONE
@@ -1459,106 +1508,110 @@ int launch_update(pam_amd_awfl *h, const double *prim_in, const double *prim0, d
 // x-sweeps and tail on the same stream.
 bool tail_fusable(const pam_amd_awfl *h) {
   const Params &P = h->P;
-  if (h->tail_fuse_mode == 1 || h->xtile || P.flat_cells || P.nt < 2) return false;
+  if (h->want.tail_fuse == 1 || h->use.xtile || P.flat_cells || P.nt < 2) return false;
   if (h->tracers_per_wave == 4 || h->tracer_prefetch) return false;
   return true;
 }
 
-template <int STAGE>
-int launch_xupd(pam_amd_awfl *h, const double *prim_in, const double *prim0, double *prim_out, double dt_dyn, double dt_stage,
-                EnsRange r, hipStream_t s, bool allow_tail_fusion = false, bool *tail_fused = nullptr) {
+// the further tracers (every tracer but water vapour) are swept two per wavefront or z slice unless asked otherwise
+inline int further_tracer_pairs(const Params &P) { return (P.nt - 1 + 1) / 2; }
+
+// LDS of an x tile kernel that exchanges through LDS: `fields` fields of the tile and of its staged rows; what the state pass asks for
+// (XT_NS fields) has to fit the 160 KB of a CU
+inline size_t xtile_lds_bytes(const XTileGeom &G, int fields) { return (size_t)fields * (xtile_threads(G) + xtile_stage_elems(G)) * sizeof(double); }
+inline bool xtile_lds_fits(const XTileGeom &G) { return xtile_lds_bytes(G, XT_NS) <= 160 * 1024; }
+
+// what launch_xupd reports: its status and whether the stage's tail went out inside its last launch (no launch_tail then)
+struct XupdResult {
+  int rc; bool tail_fused;
+  XupdResult(int rc_, bool tail_fused_ = false) : rc(rc_), tail_fused(tail_fused_) {}
+};
+
+// x direction as tile kernels: a lane per cell, the whole ensemble in one launch (small ensembles; launches the sweeps cannot fill the chip with)
+int launch_xupd_tiles(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStream_t s) {
   const Params &P = h->P;
-  if (tail_fused) *tail_fused = false;
-  if (h->xtile) {
-    // tile kernels: a lane per cell, the whole ensemble in one launch (small ensembles; launches the sweeps cannot fill the chip with)
-    if (r.e0 != 0 || r.ne != P.nens) return fail(PAM_AMD_EINVAL, "x-tile launch: the tile kernels take the whole ensemble in one range");
-    const XTileGeom &G = h->xg;
-    const int nlines = P.nz * P.ny, threads = xtile_threads(G);
-    const dim3 block((unsigned)G.W, (unsigned)xtile_rows(G), (unsigned)G.lpb);
-    const dim3 grid((unsigned)(G.ntl * G.nmb), (unsigned)((nlines + G.lpb - 1) / G.lpb), 1);
-    if (grid.y > 65535u) return fail(PAM_AMD_EINVAL, "x-tile launch: more than 65535 groups of x lines");
-    if (!h->xshuf && (size_t)XT_NS * (threads + xtile_stage_elems(G)) * sizeof(double) > 160 * 1024)
-      return fail(PAM_AMD_EINVAL, "x-tile launch: the staged tile does not fit the 160 KB of LDS");
-    // a wavefront is one row of FCT flags only when a row of the tile is exactly one 64-member block
-    const bool wave_is_row = (G.W == 64 && P.nens % 64 == 0);
-    // a whole line inside one wavefront: neighbours by wavefront shuffles (no LDS image, no barrier); else through LDS
-    const bool shuf = h->xshuf;
-    const size_t lds_state = shuf ? 0 : (size_t)XT_NS * (threads + xtile_stage_elems(G)) * sizeof(double);
-    const size_t lds_pair = shuf ? 0 : (size_t)2 * (threads + xtile_stage_elems(G)) * sizeof(double);
-    {
-      ScopedTimer st(h, "xupd", s);
-      // phase 1 of the further tracers: 0 in a launch of its own (below), 1 inline behind the state pass, 2 in z slices of this launch
-      // beside the state pass (small grids with idle CUs)
-      const int npairs_x = (P.nt - 1 + 1) / 2;
-      const int sparts = (h->tile_pressure && h->tile_state_parts) ? 1 : 0;      // (the parts exist for the fused form only)
-      const int tr_mode = h->tile_pressure ? (((h->tile_tracers_parallel || sparts) && npairs_x > 0 && npairs_x < 65535) ? 2 : 1) : 0;
-      const dim3 sgrid(grid.x, grid.y, (unsigned)((sparts ? 3 : 1) + (tr_mode == 2 ? npairs_x : 0)));
-      if (shuf)
-        hipLaunchKernelGGL((awfl_xupd_tile_kernel<STAGE, true>), sgrid, block, lds_state, s, P, G, prim_in, prim0,
-                           prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, wave_is_row), dt_dyn, dt_stage,
-                           h->tile_pressure ? 1 : 0, tr_mode, sparts);
-      else
-        hipLaunchKernelGGL((awfl_xupd_tile_kernel<STAGE, false>), sgrid, block, lds_state, s, P, G, prim_in, prim0,
-                           prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, wave_is_row), dt_dyn, dt_stage,
-                           h->tile_pressure ? 1 : 0, tr_mode, sparts);
-      HIP_TRY(hipGetLastError());
-    }
-    const int npairs = (P.nt - 1 + 1) / 2;
-    if (npairs > 65535) return fail(PAM_AMD_EINVAL, "x-tile launch: too many tracer pairs");
-    if (npairs > 0) {
-      const dim3 tgrid(grid.x, grid.y, (unsigned)npairs);
-      if (!h->tile_pressure) {       // (small ensembles: phase 1 ran inline in the state kernel, like the pressure pass)
-        ScopedTimer st(h, "xtr1", s);
-        if (shuf)
-          hipLaunchKernelGGL((awfl_xtr_tile_kernel<STAGE, 1, true>), tgrid, block, lds_pair, s, P, G, prim_in, prim0,
-                             prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, wave_is_row), dt_dyn, dt_stage, 0);
-        else
-          hipLaunchKernelGGL((awfl_xtr_tile_kernel<STAGE, 1, false>), tgrid, block, lds_pair, s, P, G, prim_in, prim0,
-                             prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, wave_is_row), dt_dyn, dt_stage, 0);
-        HIP_TRY(hipGetLastError());
-      }
-      {
-        // (small ensembles: one more z slice does water vapour's fix-up -- launch_tail then has nothing left to launch)
-        ScopedTimer st(h, "xtr2", s);
-        const dim3 tgrid2(grid.x, grid.y, (unsigned)(npairs + (h->tile_pressure ? 1 : 0)));
-        if (shuf)
-          hipLaunchKernelGGL((awfl_xtr_tile_kernel<STAGE, 2, true>), tgrid2, block, lds_pair, s, P, G, prim_in, prim0,
-                             prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, wave_is_row), dt_dyn, dt_stage,
-                             h->tile_pressure ? 1 : 0);
-        else
-          hipLaunchKernelGGL((awfl_xtr_tile_kernel<STAGE, 2, false>), tgrid2, block, lds_pair, s, P, G, prim_in, prim0,
-                             prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, wave_is_row), dt_dyn, dt_stage,
-                             h->tile_pressure ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    return PAM_AMD_OK;
+  if (r.e0 != 0 || r.ne != P.nens) return fail(PAM_AMD_EINVAL, "x-tile launch: the tile kernels take the whole ensemble in one range");
+  const XTileGeom &G = h->use.xg;
+  const dim3 block((unsigned)G.W, (unsigned)xtile_rows(G), (unsigned)G.lpb);
+  const dim3 grid((unsigned)(G.ntl * G.nmb), (unsigned)((P.nz * P.ny + G.lpb - 1) / G.lpb), 1);
+  if (grid.y > 65535u) return fail(PAM_AMD_EINVAL, "x-tile launch: more than 65535 groups of x lines");
+  // neighbours through an LDS image of the tile (SHUF false); a whole line inside one wavefront: by wavefront shuffles (no LDS, no barrier).
+  // (The variants are named exchange first, stage second: that is the order in which they are instantiated, and the compiler's code for
+  // the phase-2 tile kernels was seen to change with it.)
+  const bool lds = !h->use.xshuf;
+  if (lds && !xtile_lds_fits(G)) return fail(PAM_AMD_EINVAL, "x-tile launch: the staged tile does not fit the 160 KB of LDS");
+  const size_t lds_state = lds ? xtile_lds_bytes(G, XT_NS) : 0, lds_pair = lds ? xtile_lds_bytes(G, 2) : 0;
+  // a wavefront is one row of FCT flags only when a row of the tile is exactly one 64-member block
+  const bool wave_is_row = (G.W == 64 && P.nens % 64 == 0);
+  const int npairs = further_tracer_pairs(P), pressure = h->use.tile_pressure ? 1 : 0;
+  int rc;
+  {
+    // phase 1 of the further tracers: 0 in a launch of its own (below), 1 inline behind the state pass, 2 in z slices of this launch
+    // beside the state pass (small grids with idle CUs)
+    const int sparts = (pressure && h->use.tile_state_parts) ? 1 : 0;      // (the parts exist for the fused form only)
+    const int tr_mode = pressure ? (((h->use.tile_tracers_parallel || sparts) && npairs > 0 && npairs < 65535) ? 2 : 1) : 0;
+    const dim3 sgrid(grid.x, grid.y, (unsigned)((sparts ? 3 : 1) + (tr_mode == 2 ? npairs : 0)));
+    const auto kernel = lds ? by_stage(a.st, [](auto S) { return awfl_xupd_tile_kernel<S(), false>; })
+                            : by_stage(a.st, [](auto S) { return awfl_xupd_tile_kernel<S(), true>; });
+    if ((rc = launch(h, "xupd", kernel, sgrid, block, lds_state, s, P, G, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult,
+                     fct_rows(h, r, wave_is_row), a.dt_dyn, a.dt_stage, pressure, tr_mode, sparts)))
+      return rc;
   }
-  // wavefronts: (x line, block of 64 members, span of cells).  Normally a wavefront owns a whole line; when the ensemble alone
-  // does not fill the chip the lines are cut into spans (each recomputes its closing face) as choose_span decides from the
-  // WHOLE ensemble, so that results and schedule do not depend on the chunking
-  int span, nspan;
+  if (npairs > 65535) return fail(PAM_AMD_EINVAL, "x-tile launch: too many tracer pairs");
+  if (npairs == 0) return PAM_AMD_OK;
+  if (!pressure) {       // (small ensembles: phase 1 ran inline in the state kernel, like the pressure pass)
+    const auto kernel = lds ? by_stage(a.st, [](auto S) { return awfl_xtr_tile_kernel<S(), 1, false>; })
+                            : by_stage(a.st, [](auto S) { return awfl_xtr_tile_kernel<S(), 1, true>; });
+    if ((rc = launch(h, "xtr1", kernel, dim3(grid.x, grid.y, (unsigned)npairs), block, lds_pair, s, P, G, a.in, a.base, a.out, h->flux_x, h->flux_y,
+                     h->flux_z, h->seed, h->mult, fct_rows(h, r, wave_is_row), a.dt_dyn, a.dt_stage, 0)))
+      return rc;
+  }
+  // (small ensembles: one more z slice does water vapour's fix-up -- launch_tail then has nothing left to launch)
+  const auto kernel = lds ? by_stage(a.st, [](auto S) { return awfl_xtr_tile_kernel<S(), 2, false>; })
+                            : by_stage(a.st, [](auto S) { return awfl_xtr_tile_kernel<S(), 2, true>; });
+  return launch(h, "xtr2", kernel, dim3(grid.x, grid.y, (unsigned)(npairs + pressure)), block, lds_pair, s, P, G, a.in, a.base, a.out, h->flux_x,
+                h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, wave_is_row), a.dt_dyn, a.dt_stage, pressure);
+}
+
+// Launch shape of one phase of the further tracers' x sweeps (there are some) with `per` of them per wavefront: 1 singles, 2 pairs, 4 quads
+struct TracerSweepShape { int per, ngroups, span, nspan; long long units; };   // ngroups: wavefronts per (line, member block, span); units: of the launch
+TracerSweepShape tracer_sweep_shape(const pam_amd_awfl *h, EnsRange r, int per) {
+  const Params &P = h->P;
+  TracerSweepShape T;
+  T.per = per;
+  T.ngroups = per == 4 ? (P.nt - 1 + 3) / 4 : (per == 1 ? P.nt - 1 : further_tracer_pairs(P));
+  // (twice the wavefronts of a state sweep before the lines stay whole: the tracer launches are short, register-light kernels of two
+  // member ranges that run beside each other -- finer units pack better.  Measured on MI355X (round 5, profiles/r05_ab_experiments.txt),
+  // C4 shard, A/B on two boxes: phase 1 in half lines, phase 2 in quarter lines 0.799 -> 0.833 G and 0.822 -> 0.865 G; four times: the same;
+  // C3 and C4 whole have enough line blocks either way and keep whole lines)
+  choose_span(h, P.nx, (long long)P.nz * P.ny * T.ngroups, P.nens, P.seg, h->span_override, T.span, T.nspan, 2);
+  T.units = (long long)P.nz * P.ny * ((r.ne + 63) / 64) * T.nspan * T.ngroups;
+  return T;
+}
+
+// x direction as sweeps.  Wavefronts: (x line, block of 64 members, span of cells).  Normally a wavefront owns a whole line; when the
+// ensemble alone does not fill the chip the lines are cut into spans (each recomputes its closing face) as choose_span decides from the
+// WHOLE ensemble, so that results and schedule do not depend on the chunking
+XupdResult launch_xupd_sweeps(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStream_t s, bool allow_tail_fusion) {
+  const Params &P = h->P;
+  int span, nspan, rc;
   choose_span(h, P.nx, (long long)P.nz * P.ny, P.nens, P.seg, h->span_override, span, nspan);
-  const long long nlb = (long long)P.nz * P.ny * ((r.ne + 63) / 64);
-  const long long nunits = nlb * nspan;
+  const long long nunits = (long long)P.nz * P.ny * ((r.ne + 63) / 64) * nspan;
   // a wavefront sweeps its cells once for the state and once per pair of further tracers, one after the other: when there
   // are fewer wavefronts than the chip has slots, the tracer sweeps go to their own launch, one wavefront per pair
-  const int npairs = (P.nt - 1 + 1) / 2;
+  const int npairs = further_tracer_pairs(P);
   const bool split = npairs > 0 && (long long)P.nz * P.ny * ((P.nens + 63) / 64) * nspan < h->split_below;
   if (nunits * (npairs > 0 ? npairs : 1) > 0x3fffffffll) return fail(PAM_AMD_EINVAL, "x-sweep launch: more than 2^30 wavefronts");
   if (r.e0 % 64) return fail(PAM_AMD_EINVAL, "x-sweep launch: member ranges of the fused stage start at multiples of 64 (a wavefront is one row of FCT flags)");
+  const dim3 block(FLUX_THREADS);
   {
-    ScopedTimer st(h, "xupd", s);
-    if (P.yz_fold)      // (the z sweep has left the y+z part of the state's divergence in flux_z: no y differences to load)
-      hipLaunchKernelGGL((awfl_xupd_kernel<STAGE, true>), dim3(nblocks(nunits, FLUX_WAVES)), dim3(FLUX_THREADS), 0, s, P, r,
-                         prim_in, prim0, prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), dt_dyn,
-                         dt_stage, split ? 0 : 1, span, nspan);
-    else
-      hipLaunchKernelGGL((awfl_xupd_kernel<STAGE, false>), dim3(nblocks(nunits, FLUX_WAVES)), dim3(FLUX_THREADS), 0, s, P, r,
-                         prim_in, prim0, prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), dt_dyn,
-                         dt_stage, split ? 0 : 1, span, nspan);
-    HIP_TRY(hipGetLastError());
+    // (fold: the z sweep has left the y+z part of the state's divergence in flux_z: no y differences to load)
+    const auto kernel = by_stage(a.st, [&](auto S) { return P.yz_fold ? awfl_xupd_kernel<S(), true> : awfl_xupd_kernel<S(), false>; });
+    if ((rc = launch(h, "xupd", kernel, dim3(nblocks(nunits, FLUX_WAVES)), block, 0, s, P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z,
+                     h->seed, h->mult, fct_rows(h, r, true), a.dt_dyn, a.dt_stage, split ? 0 : 1, span, nspan)))
+      return rc;
   }
+  if (npairs == 0) return PAM_AMD_OK;
   // the tracer launches have npairs wavefronts per (line, member block, span): their lines are cut less (or not at all)
   // Further tracers per wavefront of these launches (0 = automatic; measured on MI355X, round 5, profiles/r05_ab_experiments.txt):
   //   phase 1 -- ONE: 83 instead of 119 registers (5 instead of 4 wavefronts per SIMD), and only the face mass flux is loaded twice:
@@ -1567,117 +1620,65 @@ int launch_xupd(pam_amd_awfl *h, const double *prim_in, const double *prim0, dou
   //              5.2 TB/s: C4 shard 0.123 -> 0.142 ms), except for three further tracers, where pairs are one double and one single
   //              wavefront per line and singles three equal ones (C3: 0.316 -> 0.300 ms);
   //   four per wavefront lose everywhere (2 wavefronts per SIMD: C4 shard 0.82 -> 0.75 G although 12 % fewer bytes move).
-  const int nfur = P.nt - 1;
   const int per1 = h->tracers_per_wave ? h->tracers_per_wave : 1;
-  const int per2 = h->tracers_per_wave ? h->tracers_per_wave : (nfur == 3 ? 1 : 2);
-  int tspan = span, tnspan = nspan;
-  long long tunits = 0;
-  int ngroups = npairs;
-  bool quads = false, singles = false;
-  auto shape = [&](int per) {        // the launch shape of one phase
-    quads = per == 4; singles = per == 1;
-    ngroups = quads ? (nfur + 3) / 4 : (singles ? nfur : npairs);     // wavefronts per (line, member block, span)
-    tspan = span; tnspan = nspan;
-    // (twice the wavefronts of a state sweep before the lines stay whole: the tracer launches are short, register-light kernels of two
-    // member ranges that run beside each other -- finer units pack better.  Measured on MI355X (round 5, profiles/r05_ab_experiments.txt),
-    // C4 shard, A/B on two boxes: phase 1 in half lines, phase 2 in quarter lines 0.799 -> 0.833 G and 0.822 -> 0.865 G; four times: the same;
-    // C3 and C4 whole have enough line blocks either way and keep whole lines)
-    if (npairs > 0) choose_span(h, P.nx, (long long)P.nz * P.ny * ngroups, P.nens, P.seg, h->span_override, tspan, tnspan, 2);
-    tunits = nlb * tnspan * ngroups;
-  };
+  const int per2 = h->tracers_per_wave ? h->tracers_per_wave : (P.nt - 1 == 3 ? 1 : 2);
   if (split) {     // phase 1 of the further tracers (their FCT multipliers) in a launch of its own
-    shape(per1);
-    ScopedTimer st(h, "xtr1", s);
-    if (quads)
-      hipLaunchKernelGGL((awfl_xtrn_kernel<STAGE, 1, 4>), dim3(nblocks(tunits, FLUX_WAVES)), dim3(FLUX_THREADS), 0, s, P, r, prim_in,
-                         prim0, prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), dt_dyn, dt_stage,
-                         ngroups, tspan, tnspan);
-    else if (singles)
-      hipLaunchKernelGGL((awfl_xtrn_kernel<STAGE, 1, 1>), dim3(nblocks(tunits, FLUX_WAVES)), dim3(FLUX_THREADS), 0, s, P, r, prim_in,
-                         prim0, prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), dt_dyn, dt_stage,
-                         ngroups, tspan, tnspan);
-    else
-      hipLaunchKernelGGL((awfl_xtr_kernel<STAGE, 1>), dim3(nblocks(tunits, FLUX_WAVES)), dim3(FLUX_THREADS), 0, s, P, r, prim_in,
-                         prim0, prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), dt_dyn, dt_stage,
-                         npairs, tspan, tnspan);
-    HIP_TRY(hipGetLastError());
+    const TracerSweepShape T = tracer_sweep_shape(h, r, per1);
+    const auto kernel = by_stage(a.st, [&](auto S) {
+      return T.per == 4 ? awfl_xtrn_kernel<S(), 1, 4> : T.per == 1 ? awfl_xtrn_kernel<S(), 1, 1> : awfl_xtr_kernel<S(), 1>;
+    });
+    if ((rc = launch(h, "xtr1", kernel, dim3(nblocks(T.units, FLUX_WAVES)), block, 0, s, P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z,
+                     h->seed, h->mult, fct_rows(h, r, true), a.dt_dyn, a.dt_stage, T.ngroups, T.span, T.nspan)))
+      return rc;
   }
+  const TracerSweepShape T = tracer_sweep_shape(h, r, per2);
   // Phase 2 + the pressure pass + water vapour's fix-up in one launch while the phase-2 launch of this range is less than about two
   // rounds of wavefronts (256 CUs x 4 SIMDs x 3 wavefronts of this kernel): there the two short pointwise launches and their boundaries
   // are ~5 % of the stage and hide inside phase 2's tail; on launches that fill the chip several times over the pressure pass runs
   // faster on its own (8 wavefronts per SIMD instead of 3).  Measured on MI355X (round 6, profiles/r06_ab_experiments.txt): C4 shard
   // 0.891 -> 0.905 G; C4 whole 1.0925 -> 1.075 G and C3, the 3-D four-tracer grid +-0 when forced on.
-  bool fuse_tail = false;
-  if (npairs > 0 && allow_tail_fusion) {
-    shape(per2);
-    fuse_tail = h->tail_fuse_mode == 2 || tunits < 6144;
-  }
-  if (tail_fused) *tail_fused = fuse_tail;
-  if (npairs > 0 && fuse_tail) {
-    const long long nb_xtr = nblocks(tunits, FLUX_WAVES);
+  if (allow_tail_fusion && (h->want.tail_fuse == 2 || T.units < 6144)) {
+    const long long nb_xtr = nblocks(T.units, FLUX_WAVES);
     const dim3 pg = cell_grid(P, r, (P.nz + TAIL_LEVELS - 1) / TAIL_LEVELS);
     const long long nb_pt = (long long)pg.x * pg.y * pg.z;
     const long long nb_fix = nblocks((long long)P.nz * P.ny * ((r.ne + 63) / 64), 4);
     if (nb_xtr + nb_pt + nb_fix > 0x7fffffffll) return fail(PAM_AMD_EINVAL, "tail launch: more than 2^31 workgroups");
-    ScopedTimer st(h, "xtr2", s);
-    const dim3 grid((unsigned)(nb_xtr + nb_pt + nb_fix));
-    if (singles)
-      hipLaunchKernelGGL((awfl_xtr2_tail_kernel<STAGE, true>), grid, dim3(FLUX_THREADS), 0, s, P, r, prim_in, prim0, prim_out, h->flux_x,
-                         h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), fct_rows(h, r, false), dt_dyn, dt_stage, ngroups, tspan,
-                         tnspan, (int)nb_xtr, (int)nb_pt, (int)pg.x);
-    else
-      hipLaunchKernelGGL((awfl_xtr2_tail_kernel<STAGE, false>), grid, dim3(FLUX_THREADS), 0, s, P, r, prim_in, prim0, prim_out, h->flux_x,
-                         h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), fct_rows(h, r, false), dt_dyn, dt_stage, npairs, tspan,
-                         tnspan, (int)nb_xtr, (int)nb_pt, (int)pg.x);
-    HIP_TRY(hipGetLastError());
-  } else if (npairs > 0) {   // phase 2: their complete update, one wavefront per (line, member block, span, pair)
-    shape(per2);
-    ScopedTimer st(h, "xtr2", s);
-    if (quads)
-      hipLaunchKernelGGL((awfl_xtrn_kernel<STAGE, 2, 4>), dim3(nblocks(tunits, FLUX_WAVES)), dim3(FLUX_THREADS), 0, s, P, r, prim_in,
-                         prim0, prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), dt_dyn, dt_stage,
-                         ngroups, tspan, tnspan);
-    else if (singles)
-      hipLaunchKernelGGL((awfl_xtrn_kernel<STAGE, 2, 1>), dim3(nblocks(tunits, FLUX_WAVES)), dim3(FLUX_THREADS), 0, s, P, r, prim_in,
-                         prim0, prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), dt_dyn, dt_stage,
-                         ngroups, tspan, tnspan);
-    else if (h->tracer_prefetch)      // (experiment (b): phase 2 with the next trip's loads requested one trip ahead)
-      hipLaunchKernelGGL((awfl_xtr_kernel<STAGE, 2, true>), dim3(nblocks(tunits, FLUX_WAVES)), dim3(FLUX_THREADS), 0, s, P, r, prim_in,
-                         prim0, prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), dt_dyn, dt_stage,
-                         npairs, tspan, tnspan);
-    else
-      hipLaunchKernelGGL((awfl_xtr_kernel<STAGE, 2>), dim3(nblocks(tunits, FLUX_WAVES)), dim3(FLUX_THREADS), 0, s, P, r, prim_in,
-                         prim0, prim_out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), dt_dyn, dt_stage,
-                         npairs, tspan, tnspan);
-    HIP_TRY(hipGetLastError());
+    const auto kernel = by_stage(a.st, [&](auto S) { return T.per == 1 ? awfl_xtr2_tail_kernel<S(), true> : awfl_xtr2_tail_kernel<S(), false>; });
+    rc = launch(h, "xtr2", kernel, dim3((unsigned)(nb_xtr + nb_pt + nb_fix)), block, 0, s, P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z,
+                h->seed, h->mult, fct_rows(h, r, true), fct_rows(h, r, false), a.dt_dyn, a.dt_stage, T.ngroups, T.span, T.nspan, (int)nb_xtr,
+                (int)nb_pt, (int)pg.x);
+    return XupdResult(rc, true);
   }
-  return PAM_AMD_OK;
+  // phase 2: their complete update, one wavefront per (line, member block, span, group); AHEAD is experiment (b): the next trip's loads
+  // requested one trip ahead
+  const auto kernel = by_stage(a.st, [&](auto S) {
+    return T.per == 4 ? awfl_xtrn_kernel<S(), 2, 4> : T.per == 1 ? awfl_xtrn_kernel<S(), 2, 1>
+           : h->tracer_prefetch ? awfl_xtr_kernel<S(), 2, true> : awfl_xtr_kernel<S(), 2>;
+  });
+  return launch(h, "xtr2", kernel, dim3(nblocks(T.units, FLUX_WAVES)), block, 0, s, P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z,
+                h->seed, h->mult, fct_rows(h, r, true), a.dt_dyn, a.dt_stage, T.ngroups, T.span, T.nspan);
+}
+
+// the x direction of the fused stage: the state's x-sweep and update, then the further tracers in two phases (multipliers, update)
+XupdResult launch_xupd(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStream_t s, bool allow_tail_fusion) {
+  if (h->use.xtile) return launch_xupd_tiles(h, a, r, s);
+  return launch_xupd_sweeps(h, a, r, s, allow_tail_fusion);
 }
 
 // the pointwise tail of the fused stage: pressure pass, then the tracers' fix-up pass
-template <int STAGE>
-int launch_tail(pam_amd_awfl *h, const double *prim_in, const double *prim0, double *prim_out, double dt_dyn, EnsRange r,
-                hipStream_t s) {
-  if (!(h->xtile && h->tile_pressure)) {      // (small ensembles: the x tile kernel has already made the pressure)
-    ScopedTimer st(h, "ptail", s);
-    const dim3 g = cell_grid(h->P, r, (h->P.nz + TAIL_LEVELS - 1) / TAIL_LEVELS);
-    hipLaunchKernelGGL(awfl_ptail_kernel, g, dim3(256), 0, s, h->P, r, prim_out);
-    HIP_TRY(hipGetLastError());
-  }
-  if (!(h->xtile && h->tile_pressure && h->P.nt > 1)) {    // (else: the last slice of the phase-2 tile launch has done it)
-    ScopedTimer st(h, "trfix", s);
-    if (h->P.flat_cells) {      // small ensembles: a lane per cell
-      hipLaunchKernelGGL(awfl_trfix_flat_kernel<STAGE>, cell_grid(h->P, r), dim3(256), 0, s, h->P, prim_in, prim0, prim_out,
-                         h->flux_x, h->flux_y, h->flux_z, h->mult, fct_rows(h, r, false), h->seed, dt_dyn);
-    } else {
-      const long long units = (long long)h->P.nz * h->P.ny * ((r.ne + 63) / 64);   // water vapour only (the others are complete)
-      if (units > 0x3fffffffll) return fail(PAM_AMD_EINVAL, "fix-up launch: more than 2^30 wavefronts");
-      hipLaunchKernelGGL(awfl_trfix_kernel<STAGE>, dim3(nblocks(units, 4)), dim3(256), 0, s, h->P, r, prim_in, prim0, prim_out,
-                         h->flux_x, h->flux_y, h->flux_z, h->mult, fct_rows(h, r, false), h->seed, dt_dyn);
-    }
-    HIP_TRY(hipGetLastError());
-  }
-  return PAM_AMD_OK;
+int launch_tail(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStream_t s) {
+  const Params &P = h->P;
+  const bool in_tile = h->use.xtile && h->use.tile_pressure;      // (small ensembles: the x tile kernel has already made the pressure)
+  if (!in_tile)
+    if (int rc = launch(h, "ptail", awfl_ptail_kernel, cell_grid(P, r, (P.nz + TAIL_LEVELS - 1) / TAIL_LEVELS), dim3(256), 0, s, P, r, a.out)) return rc;
+  if (in_tile && P.nt > 1) return PAM_AMD_OK;                      // (the last slice of the phase-2 tile launch has done the fix-up)
+  if (P.flat_cells)      // small ensembles: a lane per cell
+    return launch(h, "trfix", by_stage(a.st, [](auto S) { return awfl_trfix_flat_kernel<S()>; }), cell_grid(P, r), dim3(256), 0, s, P, a.in, a.base,
+                  a.out, h->flux_x, h->flux_y, h->flux_z, h->mult, fct_rows(h, r, false), h->seed, a.dt_dyn);
+  const long long units = (long long)P.nz * P.ny * ((r.ne + 63) / 64);   // water vapour only (the others are complete)
+  if (units > 0x3fffffffll) return fail(PAM_AMD_EINVAL, "fix-up launch: more than 2^30 wavefronts");
+  return launch(h, "trfix", by_stage(a.st, [](auto S) { return awfl_trfix_kernel<S()>; }), dim3(nblocks(units, 4)), dim3(256), 0, s, P, r, a.in,
+                a.base, a.out, h->flux_x, h->flux_y, h->flux_z, h->mult, fct_rows(h, r, false), h->seed, a.dt_dyn);
 }
 
 // Dycore.h:36-58 on the resident state of one member range: slot 0 = before the sub-steps, 1 = after
@@ -1813,26 +1814,22 @@ void drop_graphs(pam_amd_awfl *h) {
 // reference's 250 x 1 x 50 shape: 36 workgroups of 512 -> 100 of 256: 12.8 -> 11.3 us.
 void choose_flux_tiles(pam_amd_awfl *h) {
   const Params &P = h->P;
-  h->ft_auto_y = h->ft_auto_z = 0;
+  h->use.ft_auto_y = h->use.ft_auto_z = 0;
   if (h->ncu <= 0 || P.ncell > 262144) return;
   long long best_cost = -1, best_lanes = 0;
   for (int ty = 0; ty <= (P.sim2d ? 0 : (P.ny < 30 ? P.ny : 30)); ty++) {         // (0: ftile_geometry's own choice, e.g. whole short lines)
     if (ty == 1) continue;
     for (int tz = 2; tz <= 14; tz++) {
-      const FTileGeom Gy = ftile_geometry(P, 1, ty), Gz = ftile_geometry(P, 2, tz);
-      if (ty > 0 && Gy.tc != ty) continue;                          // (clamped: the same geometry as a smaller request)
-      if (Gz.tc != tz) continue;
-      const long long nby = P.sim2d ? 0 : (long long)Gy.nch * Gy.ntl * ((P.nz + Gy.lpb - 1) / Gy.lpb), nbz = (long long)Gz.nch * Gz.ntl;
-      int T = ftile_threads(Gz);
-      if (!P.sim2d && ftile_threads(Gy) > T) T = ftile_threads(Gy);
-      T = ((T + 63) / 64) * 64;
-      if (T > ftile_max_threads(P)) continue;
-      const long long launched = (nby + nbz) * T;
-      const long long active = (P.sim2d ? 0 : nby * ftile_threads(Gy)) + nbz * ftile_threads(Gz);
+      const FTileShape S = ftile_shape(P, ty, tz);
+      if (ty > 0 && S.Gy.tc != ty) continue;                        // (clamped: the same geometry as a smaller request)
+      if (S.Gz.tc != tz) continue;
+      if (S.T > ftile_max_threads(P)) continue;
+      const long long launched = (S.nby + S.nbz) * S.T;
+      const long long active = S.nby * ftile_threads(S.Gy) + S.nbz * ftile_threads(S.Gz);
       if (active * 5 < launched * 4) continue;
-      const long long cost = ((nby + nbz + h->ncu - 1) / h->ncu) * T;
+      const long long cost = ((S.nby + S.nbz + h->ncu - 1) / h->ncu) * S.T;
       if (best_cost < 0 || cost < best_cost || (cost == best_cost && launched < best_lanes)) {
-        best_cost = cost; best_lanes = launched; h->ft_auto_y = P.sim2d ? 0 : ty; h->ft_auto_z = tz;
+        best_cost = cost; best_lanes = launched; h->use.ft_auto_y = P.sim2d ? 0 : ty; h->use.ft_auto_z = tz;
       }
     }
   }
@@ -1849,65 +1846,63 @@ void choose_flux_tiles(pam_amd_awfl *h) {
 // Automatic: all three for ensembles of fewer than 64 members (a member-lane wavefront would be mostly idle lanes).
 void resolve_lane_mapping(pam_amd_awfl *h) {
   Params &P = h->P;
+  const pam_amd_awfl::Want &want = h->want;
+  pam_amd_awfl::Use &use = h->use;
   drop_graphs(h);
   const bool small = P.nens < 64;
-  h->flat_supported = P.prim_fs < (1ll << 28) && P.fz_fs < (1ll << 28);
+  use.flat_supported = P.prim_fs < (1ll << 28) && P.fz_fs < (1ll << 28);
   // flat y/z lanes also for RAGGED ensembles below 128 members (70 members in member lanes are two wavefronts per line, the second
   // one with 6 lanes: measured 1.53 -> 1.71 G at 70, 1.99 -> 2.09 G at 96 on 32x32x60); from 128 on the two independent member
   // ranges, which need member lanes, are worth more
   const bool ragged = P.nens % 64 != 0 && P.nens < 128;
-  h->flat = h->flat_supported && (h->lane_mode == 2 || (h->lane_mode == 0 && (small || ragged)));
-  h->xg = xtile_geometry(P, h->xt_w, h->xt_tc, h->xt_lpb, h->ncu);
+  use.flat = use.flat_supported && (want.lanes == 2 || (want.lanes == 0 && (small || ragged)));
+  use.xg = xtile_geometry(P, want.xt_w, want.xt_tc, want.xt_lpb, h->ncu);
   // (the groups of x lines are the y dimension of the tile kernels' launch grid: at most 65535)
-  const bool grid_ok = ((long long)P.nz * P.ny + h->xg.lpb - 1) / h->xg.lpb <= 65535;
-  h->xtile = xtile_supported(P) && grid_ok && (h->xtile_mode == 2 || (h->xtile_mode == 0 && small));
+  const bool grid_ok = ((long long)P.nz * P.ny + use.xg.lpb - 1) / use.xg.lpb <= 65535;
+  use.xtile = xtile_supported(P) && grid_ok && (want.xtile == 2 || (want.xtile == 0 && small));
   // neighbours by wavefront shuffles instead of an LDS image + barriers wherever a line lies inside one wavefront
-  h->xshuf = h->xtile && h->xshuf_mode != 1 && xtile_line_in_wavefront(P, h->xg);
-  P.flat_cells = (h->lane_mode != 1 && (long long)P.nx * P.nens < 256 && P.ncell < (1ll << 31)) ? 1 : 0;
+  use.xshuf = use.xtile && want.xshuf != 1 && xtile_line_in_wavefront(P, use.xg);
+  P.flat_cells = (want.lanes != 1 && (long long)P.nx * P.nens < 256 && P.ncell < (1ll << 31)) ? 1 : 0;
   // the y differences of the state folded into what the z sweep stores (3-D, member-lane sweeps in y, z AND x: the tile kernels form
   // the y+z part of the divergence themselves, with the same yz_divergence -- same bits either way)
-  P.yz_fold = (!P.sim2d && !h->flat && !h->xtile && h->fold_mode == 2) ? 1 : 0;
+  P.yz_fold = (!P.sim2d && !use.flat && !use.xtile && want.fold == 2) ? 1 : 0;
   // the y/z fluxes of a flat-lane stage: ONE tile kernel (a lane per cell) while the whole ensemble is below ~2.6e5 cells -- a flat-lane
   // sweep is then a handful of wavefronts walking their lines serially -- and flat-lane sweeps above (they read every input once and
   // build no halo rows; measured on MI355X, 32x32x60: 1 member 67 -> 20 us per stage, 8 members 85 -> 82, 32 members 184 -> 320)
-  h->ftile = h->ftile_mode == 2 || (h->ftile_mode == 0 && P.ncell <= 262144);
+  use.ftile = want.ftile == 2 || (want.ftile == 0 && P.ncell <= 262144);
   choose_flux_tiles(h);
   // the parts of a flux tile BESIDE each other while every part's workgroup can be resident at once (16 wavefronts per CU at the
   // kernel's ~110 registers); measured (round 5): the 250 x 1 x 50 shape, 100 -> 300 workgroups of 256 lanes: 12.7 -> 9.6 us; 32x32x60 with
   // one member, 248 -> 744 workgroups of 640 lanes (one per CU at a time): 16.8 -> 24.4 us
   {
-    const FTileGeom Gy = ftile_geometry(P, 1, h->ft_tc_y ? h->ft_tc_y : h->ft_auto_y), Gz = ftile_geometry(P, 2, h->ft_tc_z ? h->ft_tc_z : h->ft_auto_z);
-    const long long nby = P.sim2d ? 0 : (long long)Gy.nch * Gy.ntl * ((P.nz + Gy.lpb - 1) / Gy.lpb), nbz = (long long)Gz.nch * Gz.ntl;
-    int T = ftile_threads(Gz);
-    if (!P.sim2d && ftile_threads(Gy) > T) T = ftile_threads(Gy);
-    T = ((T + 63) / 64) * 64;
+    const FTileShape S = ftile_shape(h);
     const int nadv = 3 + P.nt - (P.sim2d ? 1 : 0), maxg = (nadv + FT_NG - 1) / FT_NG;      // groups of advected quantities per sweep
-    const long long per_cu = T > 0 ? 16 / (T / 64) : 0;
-    h->ftile_parts = h->ftile_parts_mode == 2 ||
-                     (h->ftile_parts_mode == 0 && h->ncu > 0 && per_cu > 0 && (nby + nbz) * (1 + maxg) <= (long long)h->ncu * per_cu);
+    const long long per_cu = S.T > 0 ? 16 / (S.T / 64) : 0;
+    use.ftile_parts = want.ftile_parts == 2 ||
+                      (want.ftile_parts == 0 && h->ncu > 0 && per_cu > 0 && (S.nby + S.nbz) * (1 + maxg) <= (long long)h->ncu * per_cu);
   }
   // the pressure pass inside the x tile kernel while a stage is a handful of short launches (one launch of ~10 us less); above, the
   // separate pass with the pow tables in LDS and 6 levels per lane is cheaper than the tile kernel's longer lanes
-  h->tile_pressure = h->tile_pressure_mode == 2 || h->tile_pressure_mode == 3 || (h->tile_pressure_mode == 0 && P.ncell <= 1048576);
+  use.tile_pressure = want.tile_pressure == 2 || want.tile_pressure == 3 || (want.tile_pressure == 0 && P.ncell <= 1048576);
   // phase 1 of the further tracers beside the state pass instead of behind it, while the launch's workgroups fit the chip about twice
   // over (16 wavefronts per CU at the kernel's ~120 registers; the tracer workgroups rebuild the face mass flux: two more polynomials
   // per cell on SIMDs that would be idle).  Measured (round 5, profiles/r05_ab_experiments.txt): the 250 x 1 x 50 shape with 4 tracers,
   // 50 -> 150 workgroups: x kernel 18.5 -> 13.6 us, 0.112 -> 0.127 G; 32x32x60 with 4 tracers: one member 0.450 -> 0.496 G, two 0.651 ->
   // 0.688 G; a single 2-D column set with 10 tracers (32 x 1 x 60): x kernel 20.7 -> 11.6 us
   {
-    const long long nwg = (long long)h->xg.ntl * h->xg.nmb * (((long long)P.nz * P.ny + h->xg.lpb - 1) / h->xg.lpb);
-    const int npairs_x = (P.nt - 1 + 1) / 2;
-    const int T = ((xtile_threads(h->xg) + 63) / 64) * 64;
+    const long long nwg = (long long)use.xg.ntl * use.xg.nmb * (((long long)P.nz * P.ny + use.xg.lpb - 1) / use.xg.lpb);
+    const int npairs_x = further_tracer_pairs(P);
+    const int T = ((xtile_threads(use.xg) + 63) / 64) * 64;
     const long long per_cu = 16 / (T / 64 > 0 ? T / 64 : 1);       // workgroups a CU holds at the kernel's ~120 registers (16 wavefronts)
     // the state pass itself in three parts beside each other (they rebuild the face mass flux and the new density) only while every
     // workgroup of the launch finds a CU of its OWN: the polynomials are a minority of a lane's chain (two dependent rounds of loads
     // and the launch itself are the rest), so the parts buy little -- measured (round 5): 250 x 1 x 50 with 4 tracers, 150 -> 250
     // workgroups: x kernel 13.9 -> 12.8 us (0.135 -> 0.139 G); 32x32x60 with one member, 240 -> 720 workgroups: 14.6 -> 14.8 us; two: 17.5 -> 20.0
-    h->tile_state_parts = h->tile_pressure && (h->tile_state_parts_mode == 2 ||
-                          (h->tile_state_parts_mode == 0 && h->ncu > 0 && nwg * (3 + npairs_x) <= (long long)h->ncu));
-    h->tile_tracers_parallel = h->tile_pressure && npairs_x > 0 &&
-                               (h->tile_pressure_mode == 3 ||
-                                (h->tile_pressure_mode == 0 && h->ncu > 0 && per_cu > 0 && nwg * (1 + npairs_x) <= 2 * (long long)h->ncu * per_cu));
+    use.tile_state_parts = use.tile_pressure && (want.tile_state_parts == 2 ||
+                                                 (want.tile_state_parts == 0 && h->ncu > 0 && nwg * (3 + npairs_x) <= (long long)h->ncu));
+    use.tile_tracers_parallel = use.tile_pressure && npairs_x > 0 &&
+                                (want.tile_pressure == 3 ||
+                                 (want.tile_pressure == 0 && h->ncu > 0 && per_cu > 0 && nwg * (1 + npairs_x) <= 2 * (long long)h->ncu * per_cu));
   }
 }
 
@@ -1949,7 +1944,7 @@ int build_chunks(pam_amd_awfl *h) {
     // ranges lose (C4 0.70, C3 1.83), and so do two ranges that share one compute stream (round 2's schedule: C4 0.65).
     if (h->fused) n = (nens >= 128) ? 2 : 1;
   }
-  if (h->fused && (h->flat || h->xtile)) n = 1;    // flat lanes and tile kernels take the whole ensemble in one launch
+  if (h->fused && (h->use.flat || h->use.xtile)) n = 1;    // flat lanes and tile kernels take the whole ensemble in one launch
   if (h->P.flat_cells) n = 1;                      // (pointwise kernels with a flat grid over every cell)
   const int per = (((nens + n - 1) / n + 63) / 64) * 64;
   for (int e0 = 0; e0 < nens; e0 += per) {
@@ -2088,20 +2083,6 @@ int join_ranges(pam_amd_awfl *h, int rc) {
   return rc == PAM_AMD_OK ? jrc : rc;
 }
 
-// f(std::integral_constant<int, st>()): the stage number of a launch as the template argument of its kernels
-template <class F>
-int by_stage(int st, F &&f) {
-  switch (st) {
-    case 1: return f(std::integral_constant<int, 1>());
-    case 2: return f(std::integral_constant<int, 2>());
-    default: return f(std::integral_constant<int, 3>());
-  }
-}
-
-// One tendency stage of one member range: its number, input, sub-step start (base) and output buffers (the output differs from both in
-// the fused stage), the sub-step length and the stage's share of it.
-struct StageArgs { int st; const double *in, *base; double *out; double dt_dyn, dt_stage; };
-
 // Fused stage: flux (y,z) -> x-sweeps + update of the state and of every tracer -> pressure pass + tracer fix-up pass.  The two polynomial
 // kernels run on `cs`: the range's own stream when it is alone or independent (every range runs its whole stage on its own stream -- no
 // events between ranges: launches that do not fill the chip overlap their ramp-up and drain phases with another range's kernels), else
@@ -2111,16 +2092,13 @@ int stage_fused(pam_amd_awfl *h, Chunk &c, hipStream_t cs, const StageArgs &a, b
   int rc;
   if (forked && !indep) HIP_TRY(hipStreamWaitEvent(cs, c.upd_done, 0));         // this range's previous tail / init
   if ((rc = launch_flux(h, a.in, c.r, cs, 6, true))) return rc;
-  const bool allow = (cs == c.stream) && tail_fusable(h);      // (the tail as part of the phase-2 launch)
-  bool fuse_tail = false;
-  if ((rc = by_stage(a.st, [&](auto S) { return launch_xupd<S()>(h, a.in, a.base, a.out, a.dt_dyn, a.dt_stage, c.r, cs, allow, &fuse_tail); })))
-    return rc;
+  const XupdResult x = launch_xupd(h, a, c.r, cs, (cs == c.stream) && tail_fusable(h));      // (the tail as part of the phase-2 launch)
+  if (x.rc) return x.rc;
   if (forked && !indep) {
     HIP_TRY(hipEventRecord(c.flux_done, cs));
     HIP_TRY(hipStreamWaitEvent(c.stream, c.flux_done, 0));
   }
-  if (!fuse_tail && (rc = by_stage(a.st, [&](auto S) { return launch_tail<S()>(h, a.in, a.base, a.out, a.dt_dyn, c.r, c.stream); })))
-    return rc;
+  if (!x.tail_fused && (rc = launch_tail(h, a, c.r, c.stream))) return rc;
   if (forked) HIP_TRY(hipEventRecord(c.upd_done, c.stream));
   return PAM_AMD_OK;
 }
@@ -2141,8 +2119,7 @@ int stage_three_kernel(pam_amd_awfl *h, Chunk &c, const StageArgs &a, bool forke
     HIP_TRY(hipStreamWaitEvent(c.stream, c.flux_done, 0));
   }
   if ((rc = launch_fct(h, a.dt_stage, c.r, c.stream))) return rc;
-  if ((rc = by_stage(a.st, [&](auto S) { return launch_update<S()>(h, a.in, a.base, a.out, a.dt_dyn, c.r, c.stream); })))
-    return rc;
+  if ((rc = launch_update(h, a, c.r, c.stream))) return rc;
   if (forked) HIP_TRY(hipEventRecord(c.upd_done, c.stream));
   return PAM_AMD_OK;
 }
@@ -2739,8 +2716,8 @@ int pam_amd_awfl_set_lane_mapping(pam_amd_awfl_t *h, int yz_lanes, int x_kernels
   if (yz_lanes < 0 || yz_lanes > 2 || x_kernels < 0 || x_kernels > 2)
     return fail(PAM_AMD_EINVAL, "set_lane_mapping: 0 = automatic, 1 = member lanes / sweep kernels, 2 = flat lanes / tile kernels");
   USE_DEVICE(h);
-  if (int rc = set_resolved(h, {{&h->lane_mode, yz_lanes}, {&h->xtile_mode, x_kernels}},
-                            [&] { return (yz_lanes != 2 || h->flat) && (x_kernels != 2 || h->xtile); },
+  if (int rc = set_resolved(h, {{&h->want.lanes, yz_lanes}, {&h->want.xtile, x_kernels}},
+                            [&] { return (yz_lanes != 2 || h->use.flat) && (x_kernels != 2 || h->use.xtile); },
                             "set_lane_mapping: flat lanes / tile kernels need every field below 2^28 doubles (32-bit lane offsets)"))
     return rc;
   return build_chunks(h);
@@ -2752,10 +2729,10 @@ int pam_amd_awfl_set_x_tile(pam_amd_awfl_t *h, int row_lanes, int cells_per_tile
   const XTileGeom g = xtile_geometry(h->P, row_lanes, cells_per_tile, lines_per_group, h->ncu);
   if (xtile_threads(g) > 1024 || xtile_threads(g) < 1) return fail(PAM_AMD_EINVAL, "set_x_tile: a tile must fit a workgroup of 1024 lanes");
   USE_DEVICE(h);
-  // the LDS bound is that of the launch (launch_xupd): it applies when the x tile kernels run AND exchange through LDS -- the shuffle
+  // the LDS bound is that of the launch (launch_xupd_tiles): it applies when the x tile kernels run AND exchange through LDS -- the shuffle
   // form stages nothing -- so the candidate geometry is resolved first and rolled back if the launch would refuse it
-  if (int rc = set_resolved(h, {{&h->xt_w, row_lanes}, {&h->xt_tc, cells_per_tile}, {&h->xt_lpb, lines_per_group}},
-                            [&] { return !h->xtile || h->xshuf || (size_t)XT_NS * (xtile_threads(h->xg) + xtile_stage_elems(h->xg)) * sizeof(double) <= 160 * 1024; },
+  if (int rc = set_resolved(h, {{&h->want.xt_w, row_lanes}, {&h->want.xt_tc, cells_per_tile}, {&h->want.xt_lpb, lines_per_group}},
+                            [&] { return !h->use.xtile || h->use.xshuf || xtile_lds_fits(h->use.xg); },
                             "set_x_tile: the staged tile does not fit the 160 KB of LDS"))
     return rc;
   return build_chunks(h);        // (the resolution may switch the x kernels: the ranges are rebuilt like set_lane_mapping does)
@@ -2764,7 +2741,7 @@ int pam_amd_awfl_set_x_tile(pam_amd_awfl_t *h, int row_lanes, int cells_per_tile
 int pam_amd_awfl_set_x_exchange(pam_amd_awfl_t *h, int mode) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
   if (mode < 0 || mode > 2) return fail(PAM_AMD_EINVAL, "set_x_exchange: 0 = automatic, 1 = through LDS, 2 = wavefront shuffles");
-  return set_resolved(h, {{&h->xshuf_mode, mode}}, [&] { return mode != 2 || h->xshuf; },
+  return set_resolved(h, {{&h->want.xshuf, mode}}, [&] { return mode != 2 || h->use.xshuf; },
                       "set_x_exchange: wavefront shuffles need x tile kernels whose whole periodic line lies inside one wavefront (nx * row lanes divides 64)");
 }
 
@@ -2772,9 +2749,9 @@ int pam_amd_awfl_set_flux_tile(pam_amd_awfl_t *h, int enable, int cells_per_y_ti
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
   if (cells_per_y_tile < 0 || levels_per_z_tile < 0) return fail(PAM_AMD_EINVAL, "set_flux_tile: tile sizes must be >= 0 (0 = automatic)");
   if (enable < 0 || enable > 2) return fail(PAM_AMD_EINVAL, "set_flux_tile: 0 = automatic, 1 = flat-lane sweeps, 2 = tile kernel");
-  h->ftile_mode = enable;
-  h->ft_tc_y = cells_per_y_tile;
-  h->ft_tc_z = levels_per_z_tile;
+  h->want.ftile = enable;
+  h->want.ft_tc_y = cells_per_y_tile;
+  h->want.ft_tc_z = levels_per_z_tile;
   resolve_lane_mapping(h);
   return PAM_AMD_OK;
 }
@@ -2782,7 +2759,7 @@ int pam_amd_awfl_set_flux_tile(pam_amd_awfl_t *h, int enable, int cells_per_y_ti
 int pam_amd_awfl_set_flux_tile_parts(pam_amd_awfl_t *h, int mode) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
   if (mode < 0 || mode > 2) return fail(PAM_AMD_EINVAL, "set_flux_tile_parts: 0 = automatic, 1 = behind each other (one workgroup per tile), 2 = beside each other");
-  h->ftile_parts_mode = mode;
+  h->want.ftile_parts = mode;
   resolve_lane_mapping(h);
   return PAM_AMD_OK;
 }
@@ -2790,7 +2767,7 @@ int pam_amd_awfl_set_flux_tile_parts(pam_amd_awfl_t *h, int mode) {
 int pam_amd_awfl_set_tile_state_parts(pam_amd_awfl_t *h, int mode) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
   if (mode < 0 || mode > 2) return fail(PAM_AMD_EINVAL, "set_tile_state_parts: 0 = automatic, 1 = one lane finishes a cell's whole state, 2 = three parts beside each other");
-  h->tile_state_parts_mode = mode;
+  h->want.tile_state_parts = mode;
   resolve_lane_mapping(h);
   return PAM_AMD_OK;
 }
@@ -2799,7 +2776,7 @@ int pam_amd_awfl_set_tile_fusion(pam_amd_awfl_t *h, int mode) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
   if (mode < 0 || mode > 3)
     return fail(PAM_AMD_EINVAL, "set_tile_fusion: 0 = automatic, 1 = separate launches, 2 = inside the x tile kernel (tracer phase 1 behind the state pass), 3 = inside, tracer phase 1 in workgroups beside it");
-  h->tile_pressure_mode = mode;
+  h->want.tile_pressure = mode;
   resolve_lane_mapping(h);
   return PAM_AMD_OK;
 }
@@ -2856,11 +2833,11 @@ int pam_amd_awfl_set_tracer_grouping(pam_amd_awfl_t *h, int tracers_per_wavefron
 
 int pam_amd_awfl_get_lane_mapping(const pam_amd_awfl_t *h, int *yz_flat, int *x_tiles, int *flat_cells, int geom[6]) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
-  if (yz_flat) *yz_flat = h->flat ? (h->ftile ? 2 : 1) : 0;
-  if (x_tiles) *x_tiles = h->xtile ? 1 : 0;
+  if (yz_flat) *yz_flat = h->use.flat ? (h->use.ftile ? 2 : 1) : 0;
+  if (x_tiles) *x_tiles = h->use.xtile ? 1 : 0;
   if (flat_cells) *flat_cells = h->P.flat_cells;
-  if (x_tiles && h->xtile && h->xshuf) *x_tiles = 2;
-  if (geom) { geom[0] = h->xg.W; geom[1] = h->xg.nmb; geom[2] = h->xg.tc; geom[3] = h->xg.halo; geom[4] = h->xg.ntl; geom[5] = h->xg.lpb; }
+  if (x_tiles && h->use.xtile && h->use.xshuf) *x_tiles = 2;
+  if (geom) { geom[0] = h->use.xg.W; geom[1] = h->use.xg.nmb; geom[2] = h->use.xg.tc; geom[3] = h->use.xg.halo; geom[4] = h->use.xg.ntl; geom[5] = h->use.xg.lpb; }
   return PAM_AMD_OK;
 }
 
@@ -2900,7 +2877,7 @@ int pam_amd_awfl_set_tail_fusion(pam_amd_awfl_t *h, int mode) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
   if (mode < 0 || mode > 2) return fail(PAM_AMD_EINVAL, "set_tail_fusion: 0 = automatic, 1 = three launches, 2 = one launch");
   drop_graphs(h);
-  h->tail_fuse_mode = mode;
+  h->want.tail_fuse = mode;
   return PAM_AMD_OK;
 }
 
@@ -2908,7 +2885,7 @@ int pam_amd_awfl_set_yz_fold(pam_amd_awfl_t *h, int mode) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
   if (mode < 0 || mode > 2) return fail(PAM_AMD_EINVAL, "set_yz_fold: 0 = automatic, 1 = off (the x-sweep loads the y and the z differences), 2 = on");
   USE_DEVICE(h);
-  return set_resolved(h, {{&h->fold_mode, mode}}, [&] { return mode != 2 || h->P.yz_fold; },
+  return set_resolved(h, {{&h->want.fold, mode}}, [&] { return mode != 2 || h->P.yz_fold; },
                       "set_yz_fold: the fold exists for 3-D grids swept with member lanes (y, z and x sweep kernels)");
 }
 
