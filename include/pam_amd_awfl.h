@@ -257,7 +257,7 @@ int pam_amd_awfl_set_launch_tuning(long long want_units, long long two_phase_bel
  * defaults a handle created AFTERWARDS starts from, so that in the one-process / N-handle host path (examples/driver.cpp --gpus N)
  * tuning one handle never re-shapes the launches of another.  Drains the handle's streams and rebuilds its member ranges. */
 int pam_amd_awfl_set_handle_launch_tuning(pam_amd_awfl_t *h, long long want_units, long long two_phase_below, long long split_below);
-/* Separately launched x sweeps of the further tracers (awfl_xtr_kernel / awfl_xtrn_kernel); same bits whatever is chosen (ABI 4).
+/* Separately launched x sweeps of the further tracers (awfl_xtr_kernel<stage, phase, tracers per wavefront>); same bits whatever is chosen (ABI 4).
  *   tracers_per_wavefront   0 = automatic (measured, DESIGN.md section 6: phase 1 one tracer per wavefront -- 83 registers, five
  *                           wavefronts per SIMD; phase 2 pairs -- the densities and the face mass flux are loaded once per pair -- except
  *                           for three further tracers, where three equal wavefronts beat one double and one single); 1, 2, 4 force a

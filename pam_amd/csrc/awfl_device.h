@@ -770,6 +770,42 @@ PAMA_HD bool skip_advected_v(const Params &P, bool diff) { return diff && P.sim2
 // advected fields a sweep visits after pass 1 (everything but the normal velocity; see above), in pairs (host: launch geometry)
 PAMA_HD int flux_sweep_pairs(const Params &P, bool diff) { return (3 + P.nt - (skip_advected_v(P, diff) ? 1 : 0) + 1) / 2; }
 
+// The work units of a sweep launch, one per WAVEFRONT.  Unit u names (line, block of 64 members, span of the line, selector) with the
+// selector (a pair of advected fields, a group of tracers; nsel == 1: none) fastest, then the span, then the member block: consecutive
+// wavefronts take the selectors and the consecutive spans of the same 64 items.  The host fills one, asks it for the size of the launch
+// and checks its limit; the kernel builds the same numbers from its arguments and asks it what a wavefront works on -- the count
+// and the decode stand next to each other here and nowhere else.
+struct SweepUnits {
+  int n1, n2, ne, nblk, nspan, nsel;     // lines of the sweep: n1 x n2 (the two directions across it); members of the range and their
+                                         // blocks of 64; spans per line; selectors per span
+  struct Unit { int us, grp, sel; };     // us: (line, member block, span); grp: (line, member block)
+  struct Lane { int line, blk; };
+  PAMA_HD long long count() const { return (long long)n1 * n2 * nblk * nspan * nsel; }
+  PAMA_HD long long workgroups(int waves) const { return (count() + waves - 1) / waves; }
+  static constexpr long long MAX_UNITS = 0x3fffffffll;                  // the decode is 32-bit: at most 2^30 wavefronts per launch
+  PAMA_HD bool fits() const { return count() <= MAX_UNITS; }
+  // u, and with it every quotient, is wave-uniform: uni_int keeps them in scalar registers.  has_sel false: u carries no selector
+  PAMA_D Unit decode(int u, bool has_sel = true) const {
+    Unit w;
+    const int us = has_sel ? uni_int(u / nsel) : u;
+    w.us = us;
+    w.sel = has_sel ? u - us * nsel : 0;
+    w.grp = uni_int(us / nspan);
+    return w;
+  }
+  PAMA_D int span(const Unit &w) const { return w.us - w.grp * nspan; }
+  // the (line, member block) of group grp (whole lines without selectors: of the unit itself); the wavefront's lanes are the block's
+  // members: lane l works on member el = blk * 64 + l of the range
+  PAMA_D Lane place(int grp) const {
+    Lane m;
+    m.line = uni_int(grp / nblk);
+    m.blk = grp - m.line * nblk;
+    return m;
+  }
+  PAMA_D bool holds(const Lane &m, int el) const { return m.line < n1 * n2 && el < ne; }
+};
+PAMA_HD SweepUnits sweep_units(int n1, int n2, int ne, int nspan, int nsel) { return SweepUnits{n1, n2, ne, (ne + 63) >> 6, nspan, nsel}; }
+
 // Body of the reconstruction + flux kernel for one lane.
 //   DIR      sweep direction
 //   line     wave-uniform index of the line: x: k*ny + j, y: k*nx + i, z: j*nx + i        e   ensemble member of this lane

@@ -11,13 +11,15 @@
 //                 awfl_xupd_kernel          x sweep + update of the state and of water vapour (its own FCT multiplier + the update an
 //                                           unlimited neighbourhood gets; Dycore.h:334-386,525-584,162-221, next stage's :310-321 divide,
 //                                           :662-710 ghosts); for large ensembles also phase 1 of the further tracers' x sweeps
-//                 awfl_xtr_kernel<.,1>      (small ensembles) phase 1 of the further tracers: x fluxes -> their FCT multipliers
-//                 awfl_xtr_kernel<.,2>      phase 2: the same x fluxes again + the complete limited update (NT > 1 only)
+//                 awfl_xtr_kernel<.,1,G>    (small ensembles) phase 1 of the further tracers, G per wavefront: x fluxes -> their FCT multipliers
+//                 awfl_xtr_kernel<.,2,G>    phase 2: the same x fluxes again + the complete limited update (NT > 1 only)
 //                 awfl_ptail_kernel         next stage's pressure + density/pressure ghosts (Dycore.h:310-321,:682-709)
 //                 awfl_trfix_kernel         water vapour redone where its limiter acted (driven by line flags; leaves at once elsewhere)
 //     three-kernel stage (cross-check, every face flux and multiplier stored):
 //                 awfl_flux_kernel (x, y, z) -> awfl_fct_kernel (Dycore.h:525-550) -> awfl_update_kernel
 // All scratch is allocated once in init.
+// What the kernel entries share is written once: the work units of a sweep launch (SweepUnits, awfl_device.h: the host's counts and the
+// kernels' decode), the tracer sweeps' block (xtr_block), the exchange of the x tile passes (XExchange), and on the host `launch`.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -94,6 +96,31 @@ struct FluxGrid {
 // VZ_PER_ENS here means the FLAT lanes of small ensembles with per-member vertical grids (each lane reads its member's table from
 // global memory: 62 registers of coefficients per trip, so two wavefronts per SIMD instead of four -- no scratch); member lanes with
 // per-member grids run awfl_fluxz_pe_kernel below.
+// Wave unit u of the sweep in direction DIR (U: the member range; G.part == 1: the unit carries the pair of advected fields as its
+// selector).  (Flat lanes ask for the span where they use it, member lanes before they are placed: the compiler's schedule follows.)
+template <int DIR, bool VZ_PER_ENS, bool DIFF, bool FLAT, bool FOLD>
+__device__ __forceinline__ void flux_sweep_unit(const Params &P, const FluxGrid &G, EnsRange R, SweepUnits U, int u, int lane,
+                                                const double *__restrict__ prim, double *__restrict__ flux,
+                                                const double *__restrict__ fold_y) {
+  if (u >= (DIR == 0 ? G.nux : DIR == 1 ? G.nuy : G.nuz)) return;
+  const bool pairs = G.part == 1;
+  U.nsel = DIR == 0 ? G.npx : DIR == 1 ? G.npy : G.npz;
+  U.nspan = DIR == 0 ? G.nsx : DIR == 1 ? G.nsy : G.nsz;
+  const SweepUnits::Unit w = U.decode(u, pairs);
+  const int psel = pairs ? 1 + w.sel : G.part;
+  const int sp = DIR == 0 ? G.spx : DIR == 1 ? G.spy : G.spz;
+  if constexpr (FLAT && DIR != 0) {
+    const unsigned q = (unsigned)w.grp * 64u + (unsigned)lane;
+    if (q < (unsigned)flat_items(P, DIR)) flux_line_body<DIR, VZ_PER_ENS, DIFF>(P, prim, flux, flat_lane<DIR>(P, q), U.span(w) * sp, sp, psel);
+  } else {
+    const int span = U.span(w);
+    const SweepUnits::Lane m = U.place(w.grp);
+    const int el = m.blk * 64 + lane;
+    // (the fused stage's x sweep is awfl_xupd_kernel's)
+    if ((DIR != 0 || !DIFF) && el < R.ne)
+      flux_line_body<DIR, VZ_PER_ENS, DIFF && DIR != 0, FOLD && DIR == 2>(P, prim, flux, m.line, R.e0 + el, span * sp, sp, psel, fold_y);
+  }
+}
 template <bool VZ_PER_ENS, bool DIFF, bool FLAT, bool FOLD = false>
 __global__ void __launch_bounds__(FLUX_THREADS, VZ_PER_ENS ? 2 : 4) awfl_flux_kernel(Params P, FluxGrid G, EnsRange R,
                                                                      const double *__restrict__ prim,
@@ -103,7 +130,7 @@ __global__ void __launch_bounds__(FLUX_THREADS, VZ_PER_ENS ? 2 : 4) awfl_flux_ke
   static_assert(!FOLD || (DIFF && !FLAT), "the fold exists for the member-lane z sweep of the fused stage");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int nblk = (R.ne + 63) >> 6;          // blocks of 64 members per line
+  const SweepUnits U = sweep_units(0, 0, R.ne, 0, 0);      // (spans and selectors: the sweep's own, flux_sweep_unit)
   // Dispatch order: the z-sweep workgroups first, then the x/y sweeps.
   int b = (int)blockIdx.x - G.nbz;
   if (b < 0) b += G.nbx + G.nby + G.nbz;      // blockIdx < nbz  ->  logical index in [nbx+nby, nbx+nby+nbz)
@@ -114,46 +141,9 @@ __global__ void __launch_bounds__(FLUX_THREADS, VZ_PER_ENS ? 2 : 4) awfl_flux_ke
     const int lev = b / per, r = b % per;
     b = (r < G.nbx_l) ? lev * G.nbx_l + r : G.nbx + lev * G.nby_l + (r - G.nbx_l);
   }
-  // wave unit u of a sweep -> (group = u / nspan, span = u % nspan), group -> (line = group / nblk, member block)
-  if (b < G.nbx) {
-    const int u = b * FLUX_WAVES + wave;
-    if (u < G.nux) {
-      const int up = (G.part == 1) ? uni_int(u / G.npx) : u, psel = (G.part == 1) ? 1 + (u - up * G.npx) : G.part;
-      const int grp = uni_int(up / G.nsx), line = uni_int(grp / nblk), el = (grp - line * nblk) * 64 + lane;
-      if (!DIFF && el < R.ne)
-        flux_line_body<0, VZ_PER_ENS, false>(P, prim, fx, line, R.e0 + el, (up - grp * G.nsx) * G.spx, G.spx, psel);
-    }
-  } else if (b < G.nbx + G.nby) {
-    const int u = (b - G.nbx) * FLUX_WAVES + wave;
-    if (u < G.nuy) {
-      const int up = (G.part == 1) ? uni_int(u / G.npy) : u, psel = (G.part == 1) ? 1 + (u - up * G.npy) : G.part;
-      const int grp = uni_int(up / G.nsy);
-      if (FLAT) {
-        const unsigned q = (unsigned)grp * 64u + (unsigned)lane;
-        if (q < (unsigned)flat_items(P, 1))
-          flux_line_body<1, VZ_PER_ENS, DIFF>(P, prim, fy, flat_lane<1>(P, q), (up - grp * G.nsy) * G.spy, G.spy, psel);
-      } else {
-        const int line = uni_int(grp / nblk), el = (grp - line * nblk) * 64 + lane;
-        if (el < R.ne)
-          flux_line_body<1, VZ_PER_ENS, DIFF>(P, prim, fy, line, R.e0 + el, (up - grp * G.nsy) * G.spy, G.spy, psel);
-      }
-    }
-  } else {
-    const int u = (b - G.nbx - G.nby) * FLUX_WAVES + wave;
-    if (u < G.nuz) {
-      const int up = (G.part == 1) ? uni_int(u / G.npz) : u, psel = (G.part == 1) ? 1 + (u - up * G.npz) : G.part;
-      const int grp = uni_int(up / G.nsz);
-      if (FLAT) {
-        const unsigned q = (unsigned)grp * 64u + (unsigned)lane;
-        if (q < (unsigned)flat_items(P, 2))
-          flux_line_body<2, VZ_PER_ENS, DIFF>(P, prim, fz, flat_lane<2>(P, q), (up - grp * G.nsz) * G.spz, G.spz, psel);
-      } else {
-        const int line = uni_int(grp / nblk), el = (grp - line * nblk) * 64 + lane;
-        if (el < R.ne)
-          flux_line_body<2, VZ_PER_ENS, DIFF, FOLD>(P, prim, fz, line, R.e0 + el, (up - grp * G.nsz) * G.spz, G.spz, psel, fy);
-      }
-    }
-  }
+  if (b < G.nbx) flux_sweep_unit<0, VZ_PER_ENS, DIFF, FLAT, FOLD>(P, G, R, U, b * FLUX_WAVES + wave, lane, prim, fx, nullptr);
+  else if (b < G.nbx + G.nby) flux_sweep_unit<1, VZ_PER_ENS, DIFF, FLAT, FOLD>(P, G, R, U, (b - G.nbx) * FLUX_WAVES + wave, lane, prim, fy, nullptr);
+  else flux_sweep_unit<2, VZ_PER_ENS, DIFF, FLAT, FOLD>(P, G, R, U, (b - G.nbx - G.nby) * FLUX_WAVES + wave, lane, prim, fz, fy);
 }
 
 // The z sweep of ensembles whose members have DIFFERENT vertical grids (the coupler's general contract: set_grid(..., realConst2d),
@@ -270,89 +260,69 @@ __global__ void __launch_bounds__(FLUX_THREADS, 2) awfl_xupd_kernel(Params P, En
                                                                      double dt_stage, int tracers_inline, int span, int nspan) {
   fct_rows_resolve(rows);
   const int u = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * FLUX_WAVES + (threadIdx.x >> 6)));
-  const int nblk = (R.ne + 63) >> 6;
-  const int grp = uni_int(u / nspan), sp = u - grp * nspan;
-  const int line = uni_int(grp / nblk), blk = grp - line * nblk;
-  const int el = blk * 64 + (int)(threadIdx.x & 63);
-  if (line < P.nz * P.ny && el < R.ne)
-    flux_x_update_body<STAGE, FOLD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, line, R.e0 + el, sp * span, span,
+  const SweepUnits U = sweep_units(P.nz, P.ny, R.ne, nspan, 1);
+  const SweepUnits::Unit w = U.decode(u, false);
+  const int sp = U.span(w);
+  const SweepUnits::Lane m = U.place(w.grp);
+  const int el = m.blk * 64 + (int)(threadIdx.x & 63);
+  if (U.holds(m, el))
+    flux_x_update_body<STAGE, FOLD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span,
                                     dt_dyn, dt_stage, tracers_inline != 0);
 }
-// x sweeps of tracers 1.. (x_tracer_sweep): wave unit u -> (x line, member block, span, pair of tracers).  PHASE 1 (the cells' FCT
+// x sweeps of tracers 1.. (x_tracer_sweep): wave unit u -> (x line, member block, span, group of G tracers).  PHASE 1 (the cells' FCT
 // multipliers; only for small ensembles -- otherwise it runs inline in awfl_xupd_kernel) and PHASE 2 (the cells' complete update)
 // both follow awfl_xupd_kernel (they need the face mass flux; phase 2 also the new density and every line's multipliers).
-template <int STAGE, int PHASE, bool AHEAD = false>
-__device__ __forceinline__ void xtr_pairs_block(const Params &P, EnsRange R, const double *__restrict__ prim_in,
-                                                const double *__restrict__ prim0, double *__restrict__ prim_out,
-                                                const double *__restrict__ fx, const double *__restrict__ fy,
-                                                const double *__restrict__ fz, double *__restrict__ seed,
-                                                double *__restrict__ mult, const FctRows &rows, double dt_dyn,
-                                                double dt_stage, int npairs, int span, int nspan, int block) {
+// G further tracers per wavefront (pam_amd_awfl_set_tracer_grouping; experiment (a) of VERDICT r3 / r4 and its opposite): 2 is the
+// measured default of phase 2.  Four: half the wavefronts, the per-wavefront loads a pair shares (face mass flux, the three densities)
+// shared by four tracers -- and twice the windows in registers.  One: twice the wavefronts, each with half the registers (more wavefronts
+// per SIMD), the shared loads repeated per tracer.  Every (G, AHEAD) is an instantiation of its own, so the pair form keeps its register
+// count.  Same arithmetic per tracer: same bits.  (The last group's size is tested as `2 * g + 1 < nt - 1` for pairs and by the tracers
+// left otherwise: the compiler's scalar code follows the spelling -- docs/experiments.md.)
+template <int STAGE, int PHASE, int G, bool AHEAD = false>
+__device__ __forceinline__ void xtr_block(const Params &P, EnsRange R, const double *__restrict__ prim_in,
+                                          const double *__restrict__ prim0, double *__restrict__ prim_out,
+                                          const double *__restrict__ fx, const double *__restrict__ fy,
+                                          const double *__restrict__ fz, double *__restrict__ seed,
+                                          double *__restrict__ mult, const FctRows &rows, double dt_dyn,
+                                          double dt_stage, int ngroups, int span, int nspan, int block) {
+  static_assert(G == 1 || G == 2 || G == 4, "one, two or four tracers per wavefront");
+  static_assert(!AHEAD || G == 2, "the one-trip-ahead form exists for pairs only");
   const int u = __builtin_amdgcn_readfirstlane((int)(block * FLUX_WAVES + (threadIdx.x >> 6)));
-  const int nblk = (R.ne + 63) >> 6;
-  const int g2 = uni_int(u / npairs), pair = u - g2 * npairs;
-  const int grp = uni_int(g2 / nspan), sp = g2 - grp * nspan;
-  const int line = uni_int(grp / nblk), el = (grp - line * nblk) * 64 + (int)(threadIdx.x & 63);
-  if (line < P.nz * P.ny && el < R.ne) {
-    // advected-field indices of the pair's tracers (water vapour rides with the state pass)
-    const int fa[2] = {4 + further_tracer(P, 2 * pair), 4 + further_tracer(P, 2 * pair + 1)};
-    if (2 * pair + 1 < P.nt - 1)
-      x_tracer_sweep<2, STAGE, PHASE, AHEAD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
+  const SweepUnits U = sweep_units(P.nz, P.ny, R.ne, nspan, ngroups);
+  const SweepUnits::Unit w = U.decode(u);
+  const int sp = U.span(w);
+  const SweepUnits::Lane m = U.place(w.grp);
+  const int el = m.blk * 64 + (int)(threadIdx.x & 63);
+  if (!U.holds(m, el)) return;
+  // fa: advected-field indices of the group's tracers (water vapour rides with the state pass)
+  if constexpr (G == 2) {
+    const int fa[2] = {4 + further_tracer(P, 2 * w.sel), 4 + further_tracer(P, 2 * w.sel + 1)};
+    if (2 * w.sel + 1 < P.nt - 1)
+      x_tracer_sweep<2, STAGE, PHASE, AHEAD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
     else
-      x_tracer_sweep<1, STAGE, PHASE, AHEAD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
+      x_tracer_sweep<1, STAGE, PHASE, AHEAD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
+  } else {
+    const int first = G * w.sel, left = P.nt - 1 - first;
+    const int fa[4] = {4 + further_tracer(P, first), 4 + further_tracer(P, first + 1), 4 + further_tracer(P, first + 2), 4 + further_tracer(P, first + 3)};
+    if (G == 4 && left >= 4)
+      x_tracer_sweep<4, STAGE, PHASE, AHEAD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
+    else if (G == 4 && left == 3)
+      x_tracer_sweep<3, STAGE, PHASE, AHEAD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
+    else if (G == 4 && left == 2)
+      x_tracer_sweep<2, STAGE, PHASE, AHEAD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
+    else
+      x_tracer_sweep<1, STAGE, PHASE, AHEAD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
   }
 }
-template <int STAGE, int PHASE, bool AHEAD = false>
+template <int STAGE, int PHASE, int G, bool AHEAD = false>
 __global__ void __launch_bounds__(FLUX_THREADS) awfl_xtr_kernel(Params P, EnsRange R, const double *__restrict__ prim_in,
                                                                const double *__restrict__ prim0, double *__restrict__ prim_out,
                                                                const double *__restrict__ fx, const double *__restrict__ fy,
                                                                const double *__restrict__ fz, double *__restrict__ seed,
                                                                double *__restrict__ mult, FctRows rows, double dt_dyn,
-                                                               double dt_stage, int npairs, int span, int nspan) {
+                                                               double dt_stage, int ngroups, int span, int nspan) {
   fct_rows_resolve(rows);
-  xtr_pairs_block<STAGE, PHASE, AHEAD>(P, R, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, dt_dyn, dt_stage, npairs, span, nspan,
-                                       (int)blockIdx.x);
-}
-// The same sweeps with G = 4 or G = 1 further tracers per wavefront (pam_amd_awfl_set_tracer_grouping; experiment (a) of VERDICT r3 / r4
-// and its opposite).  Four: half the wavefronts, the per-wavefront loads a pair shares (face mass flux, the three densities) shared by
-// four tracers -- and twice the windows in registers.  One: twice the wavefronts, each with half the registers (more wavefronts per
-// SIMD), the shared loads repeated per tracer.  Kernels of their own so that the pair form keeps its register count.  Same arithmetic
-// per tracer: same bits.
-template <int STAGE, int PHASE, int G>
-__device__ __forceinline__ void xtr_groups_block(const Params &P, EnsRange R, const double *__restrict__ prim_in,
-                                                 const double *__restrict__ prim0, double *__restrict__ prim_out,
-                                                 const double *__restrict__ fx, const double *__restrict__ fy,
-                                                 const double *__restrict__ fz, double *__restrict__ seed,
-                                                 double *__restrict__ mult, const FctRows &rows, double dt_dyn,
-                                                 double dt_stage, int ngroups, int span, int nspan, int block) {
-  static_assert(G == 1 || G == 4, "groups of one or four tracers");
-  const int u = __builtin_amdgcn_readfirstlane((int)(block * FLUX_WAVES + (threadIdx.x >> 6)));
-  const int nblk = (R.ne + 63) >> 6;
-  const int g2 = uni_int(u / ngroups), grpn = u - g2 * ngroups;
-  const int grp = uni_int(g2 / nspan), sp = g2 - grp * nspan;
-  const int line = uni_int(grp / nblk), el = (grp - line * nblk) * 64 + (int)(threadIdx.x & 63);
-  if (line < P.nz * P.ny && el < R.ne) {
-    const int first = G * grpn, left = P.nt - 1 - first;
-    const int fa[4] = {4 + further_tracer(P, first), 4 + further_tracer(P, first + 1), 4 + further_tracer(P, first + 2), 4 + further_tracer(P, first + 3)};
-    if (G == 4 && left >= 4)
-      x_tracer_sweep<4, STAGE, PHASE>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
-    else if (G == 4 && left == 3)
-      x_tracer_sweep<3, STAGE, PHASE>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
-    else if (G == 4 && left == 2)
-      x_tracer_sweep<2, STAGE, PHASE>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
-    else
-      x_tracer_sweep<1, STAGE, PHASE>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, line, R.e0 + el, sp * span, span, fa, dt_dyn, dt_stage, false, 0.0);
-  }
-}
-template <int STAGE, int PHASE, int G>
-__global__ void __launch_bounds__(FLUX_THREADS) awfl_xtrn_kernel(Params P, EnsRange R, const double *__restrict__ prim_in,
-                                                                const double *__restrict__ prim0, double *__restrict__ prim_out,
-                                                                const double *__restrict__ fx, const double *__restrict__ fy,
-                                                                const double *__restrict__ fz, double *__restrict__ seed,
-                                                                double *__restrict__ mult, FctRows rows, double dt_dyn,
-                                                                double dt_stage, int ngroups, int span, int nspan) {
-  fct_rows_resolve(rows);
-  xtr_groups_block<STAGE, PHASE, G>(P, R, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, dt_dyn, dt_stage, ngroups, span, nspan,
+  xtr_block<STAGE, PHASE, G, AHEAD>(P, R, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, dt_dyn, dt_stage, ngroups, span, nspan,
                                     (int)blockIdx.x);
 }
 // Pointwise tail of the fused stage, (1): next stage's pressure + density/pressure ghosts: a pow per cell and nothing else, so few
@@ -408,11 +378,12 @@ __device__ __forceinline__ void trfix_block(const Params &P, EnsRange R, const d
                                             const double *__restrict__ fz, const double *__restrict__ mult,
                                             const FctRows &rows, double *__restrict__ seed, double dt_dyn, int block) {
   const int u = __builtin_amdgcn_readfirstlane((int)(block * 4 + (threadIdx.x >> 6)));
-  const int nblk = (R.ne + 63) >> 6;
-  const int line = uni_int(u / nblk), el = (u - line * nblk) * 64 + (int)(threadIdx.x & 63);
-  if (line >= P.nz * P.ny || el >= R.ne) return;
-  if (rows.any[(R.e0 + el) >> 6] != rows.seq) return;     // no row of this member block was flagged in this stage
-  const int k = uni_int(line / P.ny), j = line - k * P.ny;
+  const SweepUnits U = sweep_units(P.nz, P.ny, R.ne, 1, 1);      // whole lines, no selector: the unit is the (line, member block) itself
+  const SweepUnits::Lane m = U.place(u);
+  const int el = m.blk * 64 + (int)(threadIdx.x & 63);
+  if (!U.holds(m, el)) return;
+  if (rows.any[(R.e0 + el) >> 6] != rows.seq) return;   // no row of this member block was flagged in this stage
+  const int k = uni_int(m.line / P.ny), j = m.line - k * P.ny;
   tracer_fixup_line_body<STAGE>(P, prim_in, prim0, prim_out, fx, fy, fz, mult, rows, seed, dt_dyn, P.idWV, k, j, R.e0 + el);
 }
 template <int STAGE>
@@ -444,8 +415,7 @@ __global__ void __launch_bounds__(FLUX_THREADS) awfl_xtr2_tail_kernel(Params P, 
   const int b = (int)blockIdx.x;
   if (b < nb_xtr) {
     fct_rows_resolve(rows);
-    if (SINGLES) xtr_groups_block<STAGE, 2, 1>(P, R, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, dt_dyn, dt_stage, ngroups, span, nspan, b);
-    else xtr_pairs_block<STAGE, 2>(P, R, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, dt_dyn, dt_stage, ngroups, span, nspan, b);
+    xtr_block<STAGE, 2, SINGLES ? 1 : 2>(P, R, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, dt_dyn, dt_stage, ngroups, span, nspan, b);
   } else if (b < nb_xtr + nb_pt) {
     stage_pow_tab(P, &sh_tab);
     const int q = b - nb_xtr, per_level = ptx * P.ny;
@@ -470,9 +440,39 @@ __global__ void __launch_bounds__(256) awfl_trfix_flat_kernel(Params P, const do
   tracer_fixup_cell_body<STAGE>(P, prim_in, prim0, prim_out, fx, fy, fz, mult, rows, seed, dt_dyn, P.idWV, c);
 }
 
-// TILE form of the further tracers' x sweeps (one pair of tracers); have_ruf: inline in the state kernel (phase 1 only).
-// SHUF: a whole line of the tile lies inside one wavefront (xtile_line_in_wavefront): the stencil values, the right-edge values and the
-// face fluxes come from the neighbouring lanes by wavefront shuffles -- no LDS image, no workgroup barrier (XShuf, awfl_device.h)
+// How the lanes of an x tile hand values to their neighbours in the line.  A pass of the tile is ONE pipeline,
+//   stage -> polynomials -> right-edge values to the right neighbour -> face -> fluxes to the left neighbour -> finish,
+// with the exchange chosen at its exchange points:
+// SHUF false: through an LDS image of the tile -- st: the staged fields, TS elements each (later: the face fluxes, T per field); ex: the
+// right-edge values, T per field; a workgroup barrier between the steps.
+// SHUF true: a whole line of the tile lies inside one wavefront (xtile_line_in_wavefront): the stencil values, the right-edge values and
+// the face fluxes come from the neighbouring lanes by wavefront shuffles (XShuf, awfl_device.h) -- no LDS image, no barrier.
+// A shuffle must be executed by every lane of the line it serves.  Shuffle tiles are whole-line tiles, where every valid lane builds a
+// polynomial, owns a face and completes a cell; a pass states that as code, `face = SHUF ? poly : X.face` and likewise `upd`, which is
+// both the safety argument and what lets the compiler keep one region under one execution mask.
+// What stays in the pass's own text, and why (docs/experiments.md, kernel entry layer): the roles, the barriers and the exchange's loads
+// and stores.  Helpers are inlined from the kernel downwards, so a load or store inside a new helper no longer carries the no-alias
+// scopes of the pass's __restrict__ arguments, and the compiler orders the LDS traffic differently.
+template <bool SHUF>
+struct XExchange {
+  // the stage-input values of the lane's own cell in `own`; afterwards nb() serves every lane's stencils
+  template <int N>
+  static __device__ __forceinline__ void stage(const Params &P, const double *prim_in, const XLane &X, const int (&fields)[N], double *st,
+                                               int TS, double (&own)[N], unsigned fmask = ~0u) {
+    if (SHUF) {
+      xtile_load_own<N>(P, prim_in, X, fields, own, fmask);
+    } else {
+      xtile_stage<N>(P, prim_in, X, fields, st, TS, own, fmask);
+      __syncthreads();
+    }
+  }
+  // staged field f of the cell s - 2 cells to the right of the lane's (s != 2)
+  template <int N>
+  static __device__ __forceinline__ double nb(const XLane &X, const XShuf &S, const double *st, int TS, const double (&own)[N], int f, int s) {
+    return SHUF ? xtile_shfl(own[f], S.ln[s]) : st[f * TS + X.s5[s]];
+  }
+};
+// TILE form of the further tracers' x sweeps (NF tracers of one pair); have_ruf: inline in the state kernel (phase 1 only).
 template <int STAGE, int PHASE, int NF, bool SHUF>
 __device__ __forceinline__ void xtr_tile_run(const Params &P, const XLane &X, const XShuf &S, int T, int TS, const double *__restrict__ prim_in,
                                              const double *__restrict__ prim0, double *__restrict__ prim_out,
@@ -480,46 +480,36 @@ __device__ __forceinline__ void xtr_tile_run(const Params &P, const XLane &X, co
                                              const double *__restrict__ fz, double *__restrict__ seed, double *__restrict__ mult,
                                              const FctRows &rows, double dt_dyn, double dt_stage, const int *fa, double *lds,
                                              bool have_ruf, double ruf_reg) {
+  using E = XExchange<SHUF>;
   double L[NF], R[NF], cen[NF], F[NF], own[NF];
   int fields[NF];
 #pragma unroll
   for (int n = 0; n < NF; n++) fields[n] = P_U + fa[n];
-  if (SHUF) {
-    xtile_load_own<NF>(P, prim_in, X, fields, own);
-    if (X.poly) {      // (whole-line tiles: poly == face == upd; the lanes a lane shuffles with are lanes of its own line)
-      xtile_tracer_polys_from<NF>(P, [&](int n, int s) { return xtile_shfl(own[n], S.ln[s]); }, own, L, R, cen);
-#pragma unroll
-      for (int f = 0; f < NF; f++) R[f] = xtile_shfl(R[f], S.l);
-      xtile_tracer_face<NF>(P, fx, X, L, R, F, have_ruf, ruf_reg);
-      double Fhi[NF];
-#pragma unroll
-      for (int f = 0; f < NF; f++) Fhi[f] = xtile_shfl(F[f], S.r);
-      xtile_tracer_finish<NF, STAGE, PHASE>(P, prim_in, prim0, prim_out, fy, fz, seed, mult, rows, X, fa, F, Fhi, cen, dt_dyn, dt_stage);
-    }
-    return;
-  }
-  // lds: NF staged fields of TS elements (later: the face fluxes), then NF x T right-edge values
   double *st = lds, *ex = lds + NF * TS;
-  xtile_stage<NF>(P, prim_in, X, fields, st, TS, own);
-  __syncthreads();
-  if (X.poly) {
-    xtile_tracer_polys<NF>(P, X, st, TS, own, L, R, cen);
+  const bool poly = X.poly, face = SHUF ? poly : X.face, upd = SHUF ? poly : X.upd;
+  E::stage(P, prim_in, X, fields, st, TS, own);
+  if (poly) {
+    xtile_tracer_polys_from<NF>(P, [&](int n, int s) { return E::nb(X, S, st, TS, own, n, s); }, own, L, R, cen);
+    if (!SHUF) {
 #pragma unroll
-    for (int f = 0; f < NF; f++) ex[f * T + X.slot] = R[f];
+      for (int f = 0; f < NF; f++) ex[f * T + X.slot] = R[f];
+    }
   }
-  __syncthreads();
-  if (X.face) {
+  if (!SHUF) __syncthreads();
+  if (face) {
 #pragma unroll
-    for (int f = 0; f < NF; f++) R[f] = ex[f * T + X.slot_l];
+    for (int f = 0; f < NF; f++) R[f] = SHUF ? xtile_shfl(R[f], S.l) : ex[f * T + X.slot_l];
     xtile_tracer_face<NF>(P, fx, X, L, R, F, have_ruf, ruf_reg);
+    if (!SHUF) {
 #pragma unroll
-    for (int f = 0; f < NF; f++) st[f * T + X.slot] = F[f];
+      for (int f = 0; f < NF; f++) st[f * T + X.slot] = F[f];
+    }
   }
-  __syncthreads();
-  if (X.upd) {
+  if (!SHUF) __syncthreads();
+  if (upd) {
     double Fhi[NF];
 #pragma unroll
-    for (int f = 0; f < NF; f++) Fhi[f] = st[f * T + X.slot_r];
+    for (int f = 0; f < NF; f++) Fhi[f] = SHUF ? xtile_shfl(F[f], S.r) : st[f * T + X.slot_r];
     xtile_tracer_finish<NF, STAGE, PHASE>(P, prim_in, prim0, prim_out, fy, fz, seed, mult, rows, X, fa, F, Fhi, cen, dt_dyn, dt_stage);
   }
 }
@@ -535,6 +525,7 @@ __device__ __forceinline__ void xtr_tile_run_own_flux(const Params &P, const XLa
                                                       const double *__restrict__ fy, const double *__restrict__ fz,
                                                       double *__restrict__ seed, double *__restrict__ mult, const FctRows &rows,
                                                       double dt_dyn, double dt_stage, const int *fa, double *lds) {
+  using E = XExchange<SHUF>;
   constexpr int NQ = NF + 3;                         // staged: rho, p, u, the tracers
   constexpr int NE = NF + 2;                         // exchanged right-edge values: rho*u, p, the tracers
   const WenoConsts wc = weno_consts();
@@ -544,13 +535,8 @@ __device__ __forceinline__ void xtr_tile_run_own_flux(const Params &P, const XLa
   for (int n = 0; n < NF; n++) fields[3 + n] = P_U + fa[n];
   double own[NQ], L[NE], R[NE], cen[NF], F[NF];
   double *st = lds, *ex = lds + NQ * TS;
-  if (SHUF) {
-    xtile_load_own<NQ>(P, prim_in, X, fields, own);
-  } else {
-    xtile_stage<NQ>(P, prim_in, X, fields, st, TS, own);
-    __syncthreads();
-  }
-  auto nb = [&](int f, int s) -> double { return SHUF ? xtile_shfl(own[f], S.ln[s]) : st[f * TS + X.s5[s]]; };
+  E::stage(P, prim_in, X, fields, st, TS, own);
+  auto nb = [&](int f, int s) -> double { return E::nb(X, S, st, TS, own, f, s); };
   if (X.poly) {
     double r[5], u[5], w[5];
 #pragma unroll
@@ -597,7 +583,9 @@ __device__ __forceinline__ void xtr_tile_run_own_flux(const Params &P, const XLa
     xtile_tracer_finish<NF, STAGE, 1>(P, prim_in, prim0, prim_out, fy, fz, seed, mult, rows, X, fa, F, Fhi, cen, dt_dyn, dt_stage);
   }
 }
-// The state pass of a tile (or one PART of it: XP_U / XP_VW / XP_T, awfl_device.h) for the lane's cell; F: the fluxes through its left face
+// The state pass of a tile (or one PART of it: XP_U / XP_VW / XP_T, awfl_device.h) for the lane's cell; F: the fluxes through its left face.
+// (Still one pipeline per exchange: written once like the tracer passes, the LDS form of awfl_xupd_tile_kernel<., false> comes out of the
+// compiler with other code -- docs/experiments.md, kernel entry layer.)
 template <int STAGE, bool SHUF, int PART>
 __device__ __forceinline__ void xupd_tile_state(const Params &P, const XLane &X, const XShuf &S, int T, int TS, const double *__restrict__ prim_in,
                                                 const double *__restrict__ prim0, double *__restrict__ prim_out, double *__restrict__ fx,
@@ -737,14 +725,21 @@ __global__ void __launch_bounds__(1024) awfl_xtr_tile_kernel(Params P, XTileGeom
 // two ping-pong sets of FT_NG right-edge values + 4 face fluxes (the state variables' differences).
 constexpr int FT_MAXG = (4 + MAXT + FT_NG - 1) / FT_NG + 1;
 struct FTileGroups { int ny_groups, nz_groups; int gy[FT_MAXG][FT_NG], gz[FT_MAXG][FT_NG]; };
-template <int DIR, bool VZ_PER_ENS>
-__device__ __forceinline__ void flux_tile_run(const Params &P, const FTileGeom &G, int bx, int by, int T, const int (*grp)[FT_NG],
-                                              int ngroups, const double *__restrict__ prim, double *__restrict__ flux, double *lds) {
+// the lane of a flux tile kernel's 1-D workgroup (bx, by): thread -> (member of the row, row, line of the group); the lanes beyond the
+// group's lines idle
+template <int DIR>
+__device__ __forceinline__ void ftile_workgroup_lane(const Params &P, const FTileGeom &G, int bx, int by, FLane &X) {
   const int rows = ftile_rows(G), per = rows * G.W;
   const int t = (int)threadIdx.x;
   const int tz = t / per, r = t - tz * per, ty = r / G.W, tx = r - ty * G.W;
-  FLane X = ftile_lane<DIR>(P, G, bx, by, tx, ty, tz < G.lpb ? tz : 0);
+  X = ftile_lane<DIR>(P, G, bx, by, tx, ty, tz < G.lpb ? tz : 0);
   if (tz >= G.lpb) { X.poly = X.face = X.own = X.pay = false; X.slot = X.slot_l = X.slot_r = 0; }
+}
+template <int DIR, bool VZ_PER_ENS>
+__device__ __forceinline__ void flux_tile_run(const Params &P, const FTileGeom &G, int bx, int by, int T, const int (*grp)[FT_NG],
+                                              int ngroups, const double *__restrict__ prim, double *__restrict__ flux, double *lds) {
+  FLane X;
+  ftile_workgroup_lane<DIR>(P, G, bx, by, X);
   double *ldsR[2] = {lds, lds + FT_NG * T}, *ldsF = lds + 2 * FT_NG * T;
   const int ncomp_a = (DIR == 1) ? 1 : 2;
   double L[FT_NG], R[FT_NG], F[FT_NG], ruf = 0.0, fn = 0.0;
@@ -802,11 +797,8 @@ __device__ __forceinline__ void flux_tile_part(const Params &P, const FTileGeom 
                                                int ngroups, int part, const double *__restrict__ prim, double *__restrict__ flux,
                                                double *lds) {
   if (part > ngroups) return;
-  const int rows = ftile_rows(G), per = rows * G.W;
-  const int t = (int)threadIdx.x;
-  const int tz = t / per, r = t - tz * per, ty = r / G.W, tx = r - ty * G.W;
-  FLane X = ftile_lane<DIR>(P, G, bx, by, tx, ty, tz < G.lpb ? tz : 0);
-  if (tz >= G.lpb) { X.poly = X.face = X.own = X.pay = false; X.slot = X.slot_l = X.slot_r = 0; }
+  FLane X;
+  ftile_workgroup_lane<DIR>(P, G, bx, by, X);
   double *ldsA = lds, *ldsR = lds + FT_NG * T, *ldsF = lds + 2 * FT_NG * T;
   const int ncomp_a = (DIR == 1) ? 1 : 2;
   double La[FT_NG], Ra[FT_NG], L[FT_NG], R[FT_NG], F[FT_NG], ruf = 0.0, fn = 0.0;
@@ -1201,7 +1193,7 @@ struct ScopedTimer {
   KernelTimer *t = nullptr;
   hipEvent_t a = nullptr, b = nullptr;
   ScopedTimer(pam_amd_awfl *h_, const char *name, hipStream_t s_) : h(h_), s(s_) {
-    if (!h->timing) return;
+    if (!h->timing || !name) return;
     t = &h->timers[name];
     hipEventCreate(&a);
     hipEventCreate(&b);
@@ -1225,6 +1217,15 @@ void drain(KernelTimer &t) {
     hipEventDestroy(p.second);
   }
   t.pending.clear();
+}
+
+// one launch under the timer `name` (null: un-timed, or inside a timer of the caller's)
+template <class... KParams, class... Args>
+int launch(pam_amd_awfl *h, const char *name, void (*kernel)(KParams...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args &...args) {
+  ScopedTimer st(h, name, s);
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+  HIP_TRY(hipGetLastError());
+  return PAM_AMD_OK;
 }
 
 inline int nblocks(long long n, int bs) { return (int)((n + bs - 1) / bs); }
@@ -1256,22 +1257,16 @@ int launch_init_prim(pam_amd_awfl *h, const pam_amd_awfl_fields_t *f, const pam_
   } else {
     for (int i = 0; i < 5; i++) gp.p[i] = nullptr;
   }
-  ScopedTimer st(h, "init_prim", s);
-  hipLaunchKernelGGL(awfl_init_prim_kernel, cell_grid(h->P, r), dim3(256), 0, s, h->P, r,
-                     f->density_dry, f->uvel, f->vvel, f->wvel, f->temp, tp, gp, h->prim0, h->seed, subtract_hy ? 1 : 0);
-  HIP_TRY(hipGetLastError());
-  return PAM_AMD_OK;
+  return launch(h, "init_prim", awfl_init_prim_kernel, cell_grid(h->P, r), dim3(256), 0, s, h->P, r, f->density_dry, f->uvel, f->vvel, f->wvel,
+                f->temp, tp, gp, h->prim0, h->seed, subtract_hy ? 1 : 0);
 }
 
 int launch_finalize(pam_amd_awfl *h, const pam_amd_awfl_fields_t *f, EnsRange r, hipStream_t s) {
   TracerPtrs tp;
   int rc = make_tracer_ptrs(h, f, tp);
   if (rc) return rc;
-  ScopedTimer st(h, "finalize", s);
-  hipLaunchKernelGGL(awfl_finalize_kernel, cell_grid(h->P, r), dim3(256), 0, s, h->P, r, h->prim0,
-                     h->seed, f->density_dry, f->uvel, f->vvel, f->wvel, f->temp, tp);
-  HIP_TRY(hipGetLastError());
-  return PAM_AMD_OK;
+  return launch(h, "finalize", awfl_finalize_kernel, cell_grid(h->P, r), dim3(256), 0, s, h->P, r, h->prim0, h->seed, f->density_dry, f->uvel,
+                f->vvel, f->wvel, f->temp, tp);
 }
 
 // Span (faces swept by one wavefront) of one sweep: the whole line (up to FLUX_MAX_SPAN faces) if that still leaves enough
@@ -1316,15 +1311,6 @@ auto by_stage(int st, F &&f) {
 // the fused stage), the sub-step length and the stage's share of it.
 struct StageArgs { int st; const double *in, *base; double *out; double dt_dyn, dt_stage; };
 
-// one launch under the timer `name`
-template <class... KParams, class... Args>
-int launch(pam_amd_awfl *h, const char *name, void (*kernel)(KParams...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args &...args) {
-  ScopedTimer st(h, name, s);
-  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
-  HIP_TRY(hipGetLastError());
-  return PAM_AMD_OK;
-}
-
 // Launch shape of the y/z flux TILE kernel for (cells per y tile, levels per z tile; 0 = ftile_geometry's own choice): nby workgroups of
 // y tiles, then nbz of z tiles, all of T lanes -- the larger of the two tiles in whole wavefronts (at most ftile_max_threads(P))
 struct FTileShape { FTileGeom Gy, Gz; int gyx; long long nby, nbz; int T; };
@@ -1362,11 +1348,11 @@ int launch_flux_tiles(pam_amd_awfl *h, const double *prim, hipStream_t s) {
                 (int)S.nby, S.gyx > 0 ? S.gyx : 1, prim, h->flux_y, h->flux_z, parts);
 }
 
-// What the launches of one flux sweep call share: the spans (G), the wavefronts per sweep of one member block (ux0 / uy0 / uz0), the
-// member blocks of the range, and which form of the sweeps runs
+// What the launches of one flux sweep call share: the spans (G), the work units of the x / y / z sweep of the member range without
+// selectors (U; no lines: the sweep does not run), and which form of the sweeps runs
 struct FluxSweeps {
   FluxGrid G;
-  long long ux0, uy0, uz0, nblk;
+  SweepUnits U[3];
   int npairs;               // advected fields besides the normal velocity, two per sweep
   bool diff, flat, two_phase, fold, pe;
   size_t lds_bytes;
@@ -1379,9 +1365,14 @@ int launch_flux_part(pam_amd_awfl *h, const FluxSweeps &F, int mask, int part, c
   const bool zonly = (mask == 4);
   G.part = part;
   G.npx = G.npy = G.npz = F.npairs;
-  const long long mult = (part == 1) ? F.npairs : 1;
-  G.nux = (mask & 1) ? (int)(F.ux0 * F.nblk * mult) : 0; G.nuy = (mask & 2) ? (int)(F.uy0 * F.nblk * mult) : 0; G.nuz = (mask & 4) ? (int)(F.uz0 * F.nblk * mult) : 0;
-  G.nbx = (G.nux + FLUX_WAVES - 1) / FLUX_WAVES; G.nby = (G.nuy + FLUX_WAVES - 1) / FLUX_WAVES; G.nbz = (G.nuz + FLUX_WAVES - 1) / FLUX_WAVES;
+  const int mult = (part == 1) ? F.npairs : 1;
+  SweepUnits U[3] = {F.U[0], F.U[1], F.U[2]};
+  for (int d = 0; d < 3; d++) {
+    U[d].nsel = mult;
+    if (!(mask & (1 << d))) U[d].n1 = 0;
+  }
+  G.nux = (int)U[0].count(); G.nuy = (int)U[1].count(); G.nuz = (int)U[2].count();
+  G.nbx = (int)U[0].workgroups(FLUX_WAVES); G.nby = (int)U[1].workgroups(FLUX_WAVES); G.nbz = (int)U[2].workgroups(FLUX_WAVES);
   G.nbx_l = G.nby_l = 0;
   if (!F.two_phase && !P.sim2d && G.nux > 0 && G.nuy > 0 && G.nux % (FLUX_WAVES * P.nz) == 0 && G.nuy % (FLUX_WAVES * P.nz) == 0) {
     G.nbx_l = G.nbx / P.nz;
@@ -1392,20 +1383,17 @@ int launch_flux_part(pam_amd_awfl *h, const FluxSweeps &F, int mask, int part, c
   if (F.pe && zonly) {
     // member-block-major workgroups of ZPE_WAVES columns each (awfl_fluxz_pe_kernel)
     const long long ncg = ((long long)P.ny * P.nx + ZPE_WAVES - 1) / ZPE_WAVES;
-    const long long nwg = F.nblk * ncg * G.nsz * mult;
-    if (nwg > 0x3fffffffll) return fail(PAM_AMD_EINVAL, "flux launch: more than 2^30 workgroups in one launch");
+    const long long nwg = F.U[2].nblk * ncg * G.nsz * mult;
+    if (nwg > SweepUnits::MAX_UNITS) return fail(PAM_AMD_EINVAL, "flux launch: more than 2^30 workgroups in one launch");
     const auto kernel = !F.diff ? awfl_fluxz_pe_kernel<false, false> : fold ? awfl_fluxz_pe_kernel<true, true> : awfl_fluxz_pe_kernel<true, false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(64 * ZPE_WAVES), 0, s, P, r, G.spz, G.nsz, G.part, F.npairs, prim, h->flux_y, h->flux_z);
-  } else {
-    // (member lanes with per-member grids: only the z sweep reads tables, and it is not in this launch)
-    const auto kernel = F.flat  ? (P.vz_per_ens ? awfl_flux_kernel<true, true, true, false> : awfl_flux_kernel<false, true, true, false>)
-                        : fold   ? awfl_flux_kernel<false, true, false, true>
-                        : F.diff ? awfl_flux_kernel<false, true, false, false>
-                                 : awfl_flux_kernel<false, false, false, false>;
-    hipLaunchKernelGGL(kernel, dim3(G.nbx + G.nby + G.nbz), dim3(FLUX_THREADS), F.lds_bytes, s, P, G, r, prim, h->flux_x, h->flux_y, h->flux_z);
+    return launch(h, nullptr, kernel, dim3((unsigned)nwg), dim3(64 * ZPE_WAVES), 0, s, P, r, G.spz, G.nsz, G.part, F.npairs, prim, h->flux_y, h->flux_z);
   }
-  HIP_TRY(hipGetLastError());
-  return PAM_AMD_OK;
+  // (member lanes with per-member grids: only the z sweep reads tables, and it is not in this launch)
+  const auto kernel = F.flat  ? (P.vz_per_ens ? awfl_flux_kernel<true, true, true, false> : awfl_flux_kernel<false, true, true, false>)
+                      : fold   ? awfl_flux_kernel<false, true, false, true>
+                      : F.diff ? awfl_flux_kernel<false, true, false, false>
+                               : awfl_flux_kernel<false, false, false, false>;
+  return launch(h, nullptr, kernel, dim3(G.nbx + G.nby + G.nbz), dim3(FLUX_THREADS), F.lds_bytes, s, P, G, r, prim, h->flux_x, h->flux_y, h->flux_z);
 }
 
 // sweeps: bit 0 x, bit 1 y, bit 2 z (the fused stage runs y and z here and x in awfl_xupd_kernel / awfl_xupd_tile_kernel)
@@ -1428,12 +1416,17 @@ int launch_flux(pam_amd_awfl *h, const double *prim, EnsRange r, hipStream_t s, 
   choose_span(h, P.nz + 1, gz, ens_for_span, P.seg, h->span_override, G.spz, G.nsz);
   if (diff) { G.spy = P.ny; G.nsy = 1; }   // difference form: a periodic line is swept whole (its last cell needs face n == face 0)
   F.diff = diff; F.flat = flat;
-  F.nblk = flat ? 1 : (r.ne + 63) / 64;     // member lanes: a wavefront = 64 consecutive members of ONE line
-  const long long nblk_all = flat ? 1 : (P.nens + 63) / 64;
-  F.ux0 = (sweeps & 1) ? (long long)P.nz * P.ny * G.nsx : 0;
-  F.uy0 = (P.sim2d || !(sweeps & 2)) ? 0 : gy * G.nsy;
-  F.uz0 = (sweeps & 4) ? gz * G.nsz : 0;
-  const long long units0 = F.ux0 + F.uy0 + F.uz0;
+  // member lanes: a wavefront = 64 consecutive members of ONE line; flat lanes: the groups of 64 items are the lines, in one block
+  if (flat && (gy > 0x7fffffffll || gz > 0x7fffffffll)) return fail(PAM_AMD_EINVAL, "flux launch: more than 2^31 groups of flat lanes");
+  long long units = 0, units_all = 0;      // wavefronts of one pass over this range / over the whole ensemble
+  for (int d = 0; d < 3; d++) {
+    const bool runs = (sweeps & (1 << d)) && !(d == 1 && P.sim2d);
+    const int n1 = !runs ? 0 : d == 0 ? P.nz : flat ? (int)(d == 1 ? gy : gz) : (d == 1 ? P.nz : P.ny);
+    const int n2 = d == 0 ? P.ny : flat ? 1 : P.nx, nspan = d == 0 ? G.nsx : d == 1 ? G.nsy : G.nsz;
+    F.U[d] = sweep_units(n1, n2, flat ? 1 : r.ne, nspan, 1);
+    units += F.U[d].count();
+    units_all += sweep_units(n1, n2, flat ? 1 : P.nens, nspan, 1).count();
+  }
   // Small ensembles: a wavefront that sweeps its span for pass 1 and then for every pair of advected fields, one after the
   // other, is a long serial chain on a mostly empty chip.  Then pass 1 runs in a launch of its own (`part` 0) and the pairs in a
   // second one with one wavefront per (span, pair) (`part` 1); decided from the WHOLE ensemble (chunking-independent).
@@ -1441,8 +1434,8 @@ int launch_flux(pam_amd_awfl *h, const double *prim, EnsRange r, hipStream_t s, 
   // (round 5, measured and removed -- commit 38c84c8, profiles/r05_ab_experiments.txt: the two parts as kernels of their own, each with
   // its own register count -- pass 1 alone 127, pairs 118, one field per wavefront 86 registers -- C4 flux 0.121 -> 0.126 / 0.127 ms,
   // C3 0.411 -> 0.414 / 0.434: the whole-sweep kernel at 128 registers already runs 4 wavefronts per SIMD)
-  F.two_phase = units0 * nblk_all < h->two_phase_below;
-  if (units0 * F.nblk * (F.two_phase ? F.npairs : 1) > 0x3fffffffll)
+  F.two_phase = units_all < h->two_phase_below;
+  if (units * (F.two_phase ? F.npairs : 1) > SweepUnits::MAX_UNITS)
     return fail(PAM_AMD_EINVAL, "flux launch: more than 2^30 wavefronts in one launch");
   // the kernel uses no LDS; a dynamic LDS request only caps its residency per CU when other kernels should co-reside
   F.lds_bytes = h->chunks.size() > 1 ? h->flux_lds_floor : 0;
@@ -1574,19 +1567,33 @@ int launch_xupd_tiles(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStream
 }
 
 // Launch shape of one phase of the further tracers' x sweeps (there are some) with `per` of them per wavefront: 1 singles, 2 pairs, 4 quads
-struct TracerSweepShape { int per, ngroups, span, nspan; long long units; };   // ngroups: wavefronts per (line, member block, span); units: of the launch
+struct TracerSweepShape { int per, span; SweepUnits U; };   // U: the launch's work units, with the groups of `per` tracers as selectors
 TracerSweepShape tracer_sweep_shape(const pam_amd_awfl *h, EnsRange r, int per) {
   const Params &P = h->P;
   TracerSweepShape T;
   T.per = per;
-  T.ngroups = per == 4 ? (P.nt - 1 + 3) / 4 : (per == 1 ? P.nt - 1 : further_tracer_pairs(P));
+  const int ngroups = per == 4 ? (P.nt - 1 + 3) / 4 : (per == 1 ? P.nt - 1 : further_tracer_pairs(P));
+  int nspan;
   // (twice the wavefronts of a state sweep before the lines stay whole: the tracer launches are short, register-light kernels of two
   // member ranges that run beside each other -- finer units pack better.  Measured on MI355X (round 5, profiles/r05_ab_experiments.txt),
   // C4 shard, A/B on two boxes: phase 1 in half lines, phase 2 in quarter lines 0.799 -> 0.833 G and 0.822 -> 0.865 G; four times: the same;
   // C3 and C4 whole have enough line blocks either way and keep whole lines)
-  choose_span(h, P.nx, (long long)P.nz * P.ny * T.ngroups, P.nens, P.seg, h->span_override, T.span, T.nspan, 2);
-  T.units = (long long)P.nz * P.ny * ((r.ne + 63) / 64) * T.nspan * T.ngroups;
+  choose_span(h, P.nx, (long long)P.nz * P.ny * ngroups, P.nens, P.seg, h->span_override, T.span, nspan, 2);
+  T.U = sweep_units(P.nz, P.ny, r.ne, nspan, ngroups);
   return T;
+}
+
+// The kernel of one phase of the further tracers' x sweeps for `per` tracers per wavefront; ahead (experiment (b), phase 2, pairs): the
+// next trip's loads requested one trip ahead.  (The phases are named one after the other, stage by stage inside each: the order in which
+// the variants are instantiated -- launch_xupd_tiles.)
+auto xtr_kernel(int st, int phase, int per, bool ahead) {
+  const auto phase1 = by_stage(st, [&](auto S) {
+    return per == 4 ? awfl_xtr_kernel<S(), 1, 4> : per == 1 ? awfl_xtr_kernel<S(), 1, 1> : awfl_xtr_kernel<S(), 1, 2>;
+  });
+  const auto phase2 = by_stage(st, [&](auto S) {
+    return per == 4 ? awfl_xtr_kernel<S(), 2, 4> : per == 1 ? awfl_xtr_kernel<S(), 2, 1> : ahead ? awfl_xtr_kernel<S(), 2, 2, true> : awfl_xtr_kernel<S(), 2, 2>;
+  });
+  return phase == 1 ? phase1 : phase2;
 }
 
 // x direction as sweeps.  Wavefronts: (x line, block of 64 members, span of cells).  Normally a wavefront owns a whole line; when the
@@ -1596,18 +1603,18 @@ XupdResult launch_xupd_sweeps(pam_amd_awfl *h, const StageArgs &a, EnsRange r, h
   const Params &P = h->P;
   int span, nspan, rc;
   choose_span(h, P.nx, (long long)P.nz * P.ny, P.nens, P.seg, h->span_override, span, nspan);
-  const long long nunits = (long long)P.nz * P.ny * ((r.ne + 63) / 64) * nspan;
+  const SweepUnits U = sweep_units(P.nz, P.ny, r.ne, nspan, 1);
   // a wavefront sweeps its cells once for the state and once per pair of further tracers, one after the other: when there
   // are fewer wavefronts than the chip has slots, the tracer sweeps go to their own launch, one wavefront per pair
   const int npairs = further_tracer_pairs(P);
-  const bool split = npairs > 0 && (long long)P.nz * P.ny * ((P.nens + 63) / 64) * nspan < h->split_below;
-  if (nunits * (npairs > 0 ? npairs : 1) > 0x3fffffffll) return fail(PAM_AMD_EINVAL, "x-sweep launch: more than 2^30 wavefronts");
+  const bool split = npairs > 0 && sweep_units(P.nz, P.ny, P.nens, nspan, 1).count() < h->split_below;
+  if (!sweep_units(P.nz, P.ny, r.ne, nspan, npairs > 0 ? npairs : 1).fits()) return fail(PAM_AMD_EINVAL, "x-sweep launch: more than 2^30 wavefronts");
   if (r.e0 % 64) return fail(PAM_AMD_EINVAL, "x-sweep launch: member ranges of the fused stage start at multiples of 64 (a wavefront is one row of FCT flags)");
   const dim3 block(FLUX_THREADS);
   {
     // (fold: the z sweep has left the y+z part of the state's divergence in flux_z: no y differences to load)
     const auto kernel = by_stage(a.st, [&](auto S) { return P.yz_fold ? awfl_xupd_kernel<S(), true> : awfl_xupd_kernel<S(), false>; });
-    if ((rc = launch(h, "xupd", kernel, dim3(nblocks(nunits, FLUX_WAVES)), block, 0, s, P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z,
+    if ((rc = launch(h, "xupd", kernel, dim3((unsigned)U.workgroups(FLUX_WAVES)), block, 0, s, P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z,
                      h->seed, h->mult, fct_rows(h, r, true), a.dt_dyn, a.dt_stage, split ? 0 : 1, span, nspan)))
       return rc;
   }
@@ -1622,14 +1629,14 @@ XupdResult launch_xupd_sweeps(pam_amd_awfl *h, const StageArgs &a, EnsRange r, h
   //   four per wavefront lose everywhere (2 wavefronts per SIMD: C4 shard 0.82 -> 0.75 G although 12 % fewer bytes move).
   const int per1 = h->tracers_per_wave ? h->tracers_per_wave : 1;
   const int per2 = h->tracers_per_wave ? h->tracers_per_wave : (P.nt - 1 == 3 ? 1 : 2);
+  // one phase in a launch of its own, one wavefront per (line, member block, span, group of T.per tracers)
+  auto launch_tracer_sweep = [&](int phase, const TracerSweepShape &T) {
+    return launch(h, phase == 1 ? "xtr1" : "xtr2", xtr_kernel(a.st, phase, T.per, h->tracer_prefetch), dim3((unsigned)T.U.workgroups(FLUX_WAVES)),
+                  block, 0, s, P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), a.dt_dyn,
+                  a.dt_stage, T.U.nsel, T.span, T.U.nspan);
+  };
   if (split) {     // phase 1 of the further tracers (their FCT multipliers) in a launch of its own
-    const TracerSweepShape T = tracer_sweep_shape(h, r, per1);
-    const auto kernel = by_stage(a.st, [&](auto S) {
-      return T.per == 4 ? awfl_xtrn_kernel<S(), 1, 4> : T.per == 1 ? awfl_xtrn_kernel<S(), 1, 1> : awfl_xtr_kernel<S(), 1>;
-    });
-    if ((rc = launch(h, "xtr1", kernel, dim3(nblocks(T.units, FLUX_WAVES)), block, 0, s, P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z,
-                     h->seed, h->mult, fct_rows(h, r, true), a.dt_dyn, a.dt_stage, T.ngroups, T.span, T.nspan)))
-      return rc;
+    if ((rc = launch_tracer_sweep(1, tracer_sweep_shape(h, r, per1)))) return rc;
   }
   const TracerSweepShape T = tracer_sweep_shape(h, r, per2);
   // Phase 2 + the pressure pass + water vapour's fix-up in one launch while the phase-2 launch of this range is less than about two
@@ -1637,26 +1644,20 @@ XupdResult launch_xupd_sweeps(pam_amd_awfl *h, const StageArgs &a, EnsRange r, h
   // are ~5 % of the stage and hide inside phase 2's tail; on launches that fill the chip several times over the pressure pass runs
   // faster on its own (8 wavefronts per SIMD instead of 3).  Measured on MI355X (round 6, profiles/r06_ab_experiments.txt): C4 shard
   // 0.891 -> 0.905 G; C4 whole 1.0925 -> 1.075 G and C3, the 3-D four-tracer grid +-0 when forced on.
-  if (allow_tail_fusion && (h->want.tail_fuse == 2 || T.units < 6144)) {
-    const long long nb_xtr = nblocks(T.units, FLUX_WAVES);
+  if (allow_tail_fusion && (h->want.tail_fuse == 2 || T.U.count() < 6144)) {
+    const long long nb_xtr = T.U.workgroups(FLUX_WAVES);
     const dim3 pg = cell_grid(P, r, (P.nz + TAIL_LEVELS - 1) / TAIL_LEVELS);
     const long long nb_pt = (long long)pg.x * pg.y * pg.z;
-    const long long nb_fix = nblocks((long long)P.nz * P.ny * ((r.ne + 63) / 64), 4);
+    const long long nb_fix = sweep_units(P.nz, P.ny, r.ne, 1, 1).workgroups(4);
     if (nb_xtr + nb_pt + nb_fix > 0x7fffffffll) return fail(PAM_AMD_EINVAL, "tail launch: more than 2^31 workgroups");
     const auto kernel = by_stage(a.st, [&](auto S) { return T.per == 1 ? awfl_xtr2_tail_kernel<S(), true> : awfl_xtr2_tail_kernel<S(), false>; });
     rc = launch(h, "xtr2", kernel, dim3((unsigned)(nb_xtr + nb_pt + nb_fix)), block, 0, s, P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z,
-                h->seed, h->mult, fct_rows(h, r, true), fct_rows(h, r, false), a.dt_dyn, a.dt_stage, T.ngroups, T.span, T.nspan, (int)nb_xtr,
+                h->seed, h->mult, fct_rows(h, r, true), fct_rows(h, r, false), a.dt_dyn, a.dt_stage, T.U.nsel, T.span, T.U.nspan, (int)nb_xtr,
                 (int)nb_pt, (int)pg.x);
     return XupdResult(rc, true);
   }
-  // phase 2: their complete update, one wavefront per (line, member block, span, group); AHEAD is experiment (b): the next trip's loads
-  // requested one trip ahead
-  const auto kernel = by_stage(a.st, [&](auto S) {
-    return T.per == 4 ? awfl_xtrn_kernel<S(), 2, 4> : T.per == 1 ? awfl_xtrn_kernel<S(), 2, 1>
-           : h->tracer_prefetch ? awfl_xtr_kernel<S(), 2, true> : awfl_xtr_kernel<S(), 2>;
-  });
-  return launch(h, "xtr2", kernel, dim3(nblocks(T.units, FLUX_WAVES)), block, 0, s, P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z,
-                h->seed, h->mult, fct_rows(h, r, true), a.dt_dyn, a.dt_stage, T.ngroups, T.span, T.nspan);
+  // phase 2: their complete update
+  return launch_tracer_sweep(2, T);
 }
 
 // the x direction of the fused stage: the state's x-sweep and update, then the further tracers in two phases (multipliers, update)
@@ -1675,19 +1676,17 @@ int launch_tail(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStream_t s) 
   if (P.flat_cells)      // small ensembles: a lane per cell
     return launch(h, "trfix", by_stage(a.st, [](auto S) { return awfl_trfix_flat_kernel<S()>; }), cell_grid(P, r), dim3(256), 0, s, P, a.in, a.base,
                   a.out, h->flux_x, h->flux_y, h->flux_z, h->mult, fct_rows(h, r, false), h->seed, a.dt_dyn);
-  const long long units = (long long)P.nz * P.ny * ((r.ne + 63) / 64);   // water vapour only (the others are complete)
-  if (units > 0x3fffffffll) return fail(PAM_AMD_EINVAL, "fix-up launch: more than 2^30 wavefronts");
-  return launch(h, "trfix", by_stage(a.st, [](auto S) { return awfl_trfix_kernel<S()>; }), dim3(nblocks(units, 4)), dim3(256), 0, s, P, r, a.in,
+  const SweepUnits U = sweep_units(P.nz, P.ny, r.ne, 1, 1);   // whole lines of water vapour only (the others are complete)
+  if (!U.fits()) return fail(PAM_AMD_EINVAL, "fix-up launch: more than 2^30 wavefronts");
+  return launch(h, "trfix", by_stage(a.st, [](auto S) { return awfl_trfix_kernel<S()>; }), dim3((unsigned)U.workgroups(4)), dim3(256), 0, s, P, r, a.in,
                 a.base, a.out, h->flux_x, h->flux_y, h->flux_z, h->mult, fct_rows(h, r, false), h->seed, a.dt_dyn);
 }
 
 // Dycore.h:36-58 on the resident state of one member range: slot 0 = before the sub-steps, 1 = after
 int launch_mass(pam_amd_awfl *h, int slot, EnsRange r, hipStream_t s) {
   const Params &P = h->P;
-  hipLaunchKernelGGL(awfl_mass_kernel, dim3((unsigned)((r.ne + 63) / 64), (unsigned)(P.nt + 2)), dim3(256), 0, s, P, r, h->prim0, h->seed,
-                     h->mass_dev + (size_t)slot * (P.nt + 2) * P.nens);
-  HIP_TRY(hipGetLastError());
-  return PAM_AMD_OK;
+  return launch(h, nullptr, awfl_mass_kernel, dim3((unsigned)((r.ne + 63) / 64), (unsigned)(P.nt + 2)), dim3(256), 0, s, P, r, h->prim0, h->seed,
+                h->mass_dev + (size_t)slot * (P.nt + 2) * P.nens);
 }
 // Dycore.h:224-251: a (variable, member) pair is reported when its mass changed by more than 1e-10 relative AND absolute
 int evaluate_mass(pam_amd_awfl *h) {
@@ -1728,20 +1727,16 @@ int launch_cfl(pam_amd_awfl *h, const pam_amd_awfl_fields_t *f, double cfl, bool
     // whose last user has been read by then (finish_cfl)
     unsigned long long *word = h->dt_bits + (h->dt_slot & 1u), *next_word = h->dt_bits + ((h->dt_slot + 1u) & 1u);
     h->dt_slot++;
-    ScopedTimer st(h, "cfl", h->stream);
-    hipLaunchKernelGGL(awfl_cfl_kernel<true>, dim3(nb), dim3(256), 0, h->stream, h->P, f->density_dry, f->uvel, f->vvel, f->wvel,
-                       f->temp, f->tracers[h->P.idWV], cfl, word, next_word, (unsigned *)(h->dt_bits + 2), h->dt_host_dev);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch(h, "cfl", awfl_cfl_kernel<true>, dim3(nb), dim3(256), 0, h->stream, h->P, f->density_dry, f->uvel, f->vvel, f->wvel,
+                        f->temp, f->tracers[h->P.idWV], cfl, word, next_word, (unsigned *)(h->dt_bits + 2), h->dt_host_dev))
+      return rc;
   } else {
     unsigned long long *word = h->dt_bits + 3;      // (a word of its own: the two forms may alternate on one handle)
     HIP_TRY(hipMemcpyAsync(word, h->dt_host + 1, sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));   // +inf, pinned
-    {
-      ScopedTimer st(h, "cfl", h->stream);
-      hipLaunchKernelGGL(awfl_cfl_kernel<false>, dim3(nb), dim3(256), 0, h->stream, h->P, f->density_dry, f->uvel, f->vvel, f->wvel,
-                         f->temp, f->tracers[h->P.idWV], cfl, word, (unsigned long long *)nullptr, (unsigned *)nullptr,
-                         (unsigned long long *)nullptr);
-      HIP_TRY(hipGetLastError());
-    }
+    if (int rc = launch(h, "cfl", awfl_cfl_kernel<false>, dim3(nb), dim3(256), 0, h->stream, h->P, f->density_dry, f->uvel, f->vvel, f->wvel,
+                        f->temp, f->tracers[h->P.idWV], cfl, word, (unsigned long long *)nullptr, (unsigned *)nullptr,
+                        (unsigned long long *)nullptr))
+      return rc;
     HIP_TRY(hipMemcpyAsync(h->dt_host, word, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   }
   HIP_TRY(hipEventRecord(h->ev_cfl, h->stream));
@@ -2169,9 +2164,9 @@ int enqueue_step(pam_amd_awfl *h, StepCall &s) {
   for (auto &c : h->chunks) {
     if (h->debug_mass) {
       if (h->fault.armed && h->fault.e >= c.r.e0 && h->fault.e < c.r.e0 + c.r.ne) {
-        hipLaunchKernelGGL(awfl_poke_kernel, dim3(1), dim3(1), 0, c.stream, h->P, h->prim0, h->prim0, h->seed, h->fault.ivar, h->fault.k,
-                           h->fault.j, h->fault.i, h->fault.e, h->fault.factor);
-        HIP_TRY(hipGetLastError());
+        if (int rc = launch(h, nullptr, awfl_poke_kernel, dim3(1), dim3(1), 0, c.stream, h->P, h->prim0, h->prim0, h->seed, h->fault.ivar,
+                            h->fault.k, h->fault.j, h->fault.i, h->fault.e, h->fault.factor))
+          return rc;
         h->fault.armed = false;
       }
       if ((rc = launch_mass(h, 1, c.r, c.stream))) return rc;
@@ -2414,22 +2409,17 @@ int pam_amd_awfl_init(const pam_amd_awfl_config_t *cfg, pam_amd_awfl_t **out) {
   h->n_vert_s2c = vt.s2c.size(); h->n_vert_wrl = vt.wrl.size();
   INIT_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
   // (the graph-replay stream, its events and the stage-number word are created when the replay is switched on)
-  // the flux kernel may request more than the default 64 KiB of dynamic LDS (residency cap)
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_flux_kernel<false, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_flux_kernel<false, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_flux_kernel<false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  // the tile kernels stage their tiles in LDS: up to 14 doubles per lane of a 1024-lane workgroup
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_xupd_tile_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_xupd_tile_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_xupd_tile_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_xtr_tile_kernel<1, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_xtr_tile_kernel<1, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_xtr_tile_kernel<2, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_xtr_tile_kernel<2, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_xtr_tile_kernel<3, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_xtr_tile_kernel<3, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_flux_tile_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  INIT_TRY(hipFuncSetAttribute((const void *)awfl_flux_tile_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  // Kernels that may ask for more than the default 64 KiB of dynamic LDS: the flux kernel (a request that only caps its residency), and the
+  // tile kernels that stage their tiles in LDS -- up to 14 doubles per lane of a 1024-lane workgroup
+  const void *const big_lds_kernels[] = {
+      (const void *)awfl_flux_kernel<false, false, false, false>, (const void *)awfl_flux_kernel<false, true, false, false>,
+      (const void *)awfl_flux_kernel<false, true, false, true>,
+      (const void *)awfl_xupd_tile_kernel<1, false>, (const void *)awfl_xupd_tile_kernel<2, false>, (const void *)awfl_xupd_tile_kernel<3, false>,
+      (const void *)awfl_xtr_tile_kernel<1, 1, false>, (const void *)awfl_xtr_tile_kernel<1, 2, false>,
+      (const void *)awfl_xtr_tile_kernel<2, 1, false>, (const void *)awfl_xtr_tile_kernel<2, 2, false>,
+      (const void *)awfl_xtr_tile_kernel<3, 1, false>, (const void *)awfl_xtr_tile_kernel<3, 2, false>,
+      (const void *)awfl_flux_tile_kernel<false>, (const void *)awfl_flux_tile_kernel<true>};
+  for (const void *kernel : big_lds_kernels) INIT_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #undef INIT_TRY
   h->flux_lds_floor = 0;   // no residency cap by default
   h->want_units = g_want_units.load(); h->two_phase_below = g_two_phase_below.load(); h->split_below = g_split_below.load();
@@ -2537,14 +2527,13 @@ int pam_amd_awfl_declare_current_profile_as_hydrostatic(pam_amd_awfl_t *h, const
       const long long nf = h->P.fz_fs;       // (nz + 1) faces x columns
       const dim3 grid(nblocks(nf, 256)), block(256);
       const bool wide = nf >= (1ll << 32);
-      if (h->P.vz_per_ens && wide) hipLaunchKernelGGL((awfl_hydro_pint_kernel<true, unsigned long long>), grid, block, 0, h->stream, h->P, h->prim0, h->flux_z);
-      else if (h->P.vz_per_ens) hipLaunchKernelGGL((awfl_hydro_pint_kernel<true, unsigned>), grid, block, 0, h->stream, h->P, h->prim0, h->flux_z);
-      else if (wide) hipLaunchKernelGGL((awfl_hydro_pint_kernel<false, unsigned long long>), grid, block, 0, h->stream, h->P, h->prim0, h->flux_z);
-      else hipLaunchKernelGGL((awfl_hydro_pint_kernel<false, unsigned>), grid, block, 0, h->stream, h->P, h->prim0, h->flux_z);
-      hipLaunchKernelGGL(awfl_hydro_sum_kernel, dim3(nblocks(n, 64)), dim3(64), 0, h->stream, h->P, h->prim0, h->flux_z, h->act_grav_var);
-    } else
-      hipLaunchKernelGGL(awfl_hydro_kernel, dim3(nblocks(n, 64)), dim3(64), 0, h->stream, h->P, h->prim0, h->act_hy_dens, h->act_hy_pres);
-    HIP_TRY(hipGetLastError());
+      const auto pint_kernel = h->P.vz_per_ens ? (wide ? awfl_hydro_pint_kernel<true, unsigned long long> : awfl_hydro_pint_kernel<true, unsigned>)
+                                               : (wide ? awfl_hydro_pint_kernel<false, unsigned long long> : awfl_hydro_pint_kernel<false, unsigned>);
+      if (int rc = launch(h, nullptr, pint_kernel, grid, block, 0, h->stream, h->P, h->prim0, h->flux_z)) return rc;
+      if (int rc = launch(h, nullptr, awfl_hydro_sum_kernel, dim3(nblocks(n, 64)), dim3(64), 0, h->stream, h->P, h->prim0, h->flux_z, h->act_grav_var)) return rc;
+    } else if (int rc = launch(h, nullptr, awfl_hydro_kernel, dim3(nblocks(n, 64)), dim3(64), 0, h->stream, h->P, h->prim0, h->act_hy_dens, h->act_hy_pres)) {
+      return rc;
+    }
   }
   h->hydro_declared = true;
   return PAM_AMD_OK;
@@ -2575,10 +2564,8 @@ int pam_amd_awfl_convert_coupler_to_dynamics_arrays(pam_amd_awfl_t *h, const pam
   TracerPtrs tp;
   if (int rc = make_tracer_ptrs(h, fields, tp)) return rc;
   const EnsRange r = full_range(h->P);
-  hipLaunchKernelGGL(awfl_c2d_arrays_kernel, cell_grid(h->P, r), dim3(256), 0, h->stream, h->P, r, fields->density_dry, fields->uvel,
-                     fields->vvel, fields->wvel, fields->temp, tp, state, tracers);
-  HIP_TRY(hipGetLastError());
-  return PAM_AMD_OK;
+  return launch(h, nullptr, awfl_c2d_arrays_kernel, cell_grid(h->P, r), dim3(256), 0, h->stream, h->P, r, fields->density_dry, fields->uvel,
+                fields->vvel, fields->wvel, fields->temp, tp, state, tracers);
 }
 
 int pam_amd_awfl_convert_dynamics_to_coupler_arrays(pam_amd_awfl_t *h, const pam_amd_awfl_fields_t *fields, const double *state,
@@ -2588,10 +2575,8 @@ int pam_amd_awfl_convert_dynamics_to_coupler_arrays(pam_amd_awfl_t *h, const pam
   TracerPtrs tp;
   if (int rc = make_tracer_ptrs(h, fields, tp)) return rc;
   const EnsRange r = full_range(h->P);
-  hipLaunchKernelGGL(awfl_d2c_arrays_kernel, cell_grid(h->P, r), dim3(256), 0, h->stream, h->P, r, state, tracers, fields->density_dry,
-                     fields->uvel, fields->vvel, fields->wvel, fields->temp, tp);
-  HIP_TRY(hipGetLastError());
-  return PAM_AMD_OK;
+  return launch(h, nullptr, awfl_d2c_arrays_kernel, cell_grid(h->P, r), dim3(256), 0, h->stream, h->P, r, state, tracers, fields->density_dry,
+                fields->uvel, fields->vvel, fields->wvel, fields->temp, tp);
 }
 
 int pam_amd_awfl_time_step(pam_amd_awfl_t *h, const pam_amd_awfl_fields_t *fields, double crm_dt, double dt_dyn_hint,
@@ -2629,12 +2614,8 @@ int pam_amd_awfl_init_idealized(pam_amd_awfl_t *h, const pam_amd_awfl_fields_t *
   const Params &P = h->P;
   const EnsRange r = full_range(P);
   if (kind == "thermal") {
-    ScopedTimer st(h, "init_idealized", h->stream);
-    hipLaunchKernelGGL(awfl_init_thermal_kernel, cell_grid(P, r), dim3(256), 0, h->stream, P, r, h->cfg.xlen, h->cfg.ylen,
-                       h->cp_d, h->p0, vertical_midpoint_height, fields->density_dry, fields->uvel, fields->vvel, fields->wvel,
-                       fields->temp, tp);
-    HIP_TRY(hipGetLastError());
-    return PAM_AMD_OK;
+    return launch(h, "init_idealized", awfl_init_thermal_kernel, cell_grid(P, r), dim3(256), 0, h->stream, P, r, h->cfg.xlen, h->cfg.ylen,
+                  h->cp_d, h->p0, vertical_midpoint_height, fields->density_dry, fields->uvel, fields->vvel, fields->wvel, fields->temp, tp);
   }
   // supercell: integrate the sounding column on the host (once), then fill the 3-D fields on the device
   const size_t nzn = (size_t)P.nz * P.nens;
@@ -2651,13 +2632,11 @@ int pam_amd_awfl_init_idealized(pam_amd_awfl_t *h, const pam_amd_awfl_fields_t *
   HIP_TRY(hipMemcpy(d_hd, sc.hy_dens.data(), nzn * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_hp, sc.hy_pres.data(), nzn * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_dv, sc.dens_vap_gll.data(), nzn * 9 * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(awfl_init_supercell_kernel, cell_grid(P, r), dim3(256), 0, h->stream, P, r, vertical_midpoint_height,
-                     d_hd, d_hp, d_dv, fields->density_dry, fields->uvel, fields->vvel, fields->wvel, fields->temp, tp);
-  hipError_t err = hipGetLastError();
+  rc = launch(h, nullptr, awfl_init_supercell_kernel, cell_grid(P, r), dim3(256), 0, h->stream, P, r, vertical_midpoint_height,
+               d_hd, d_hp, d_dv, fields->density_dry, fields->uvel, fields->vvel, fields->wvel, fields->temp, tp);
   (void)hipStreamSynchronize(h->stream);
   (void)hipFree(d_hd); (void)hipFree(d_hp); (void)hipFree(d_dv);
-  if (err != hipSuccess) return fail(PAM_AMD_ENOGPU, hipGetErrorString(err));
-  return PAM_AMD_OK;
+  return rc;
 }
 
 int pam_amd_awfl_set_kernel_timing(pam_amd_awfl_t *h, int enable) {
@@ -2931,9 +2910,7 @@ int pam_amd_awfl_debug_pow(pam_amd_awfl_t *h, const double *x, int n, double y, 
   if (!h || !x || !out || n < 0) return fail(PAM_AMD_EINVAL, "debug_pow: bad argument");
   USE_DEVICE(h);
   if (n == 0) return PAM_AMD_OK;
-  hipLaunchKernelGGL(awfl_pow_kat_kernel, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->P, x, n, y, out);
-  HIP_TRY(hipGetLastError());
-  return PAM_AMD_OK;
+  return launch(h, nullptr, awfl_pow_kat_kernel, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->P, x, n, y, out);
 }
 
 int pam_amd_awfl_debug_fct_rows(pam_amd_awfl_t *h, long long *rows_flagged, long long *rows_total, int *any_flagged) {
@@ -2956,9 +2933,7 @@ int pam_amd_awfl_debug_weno(pam_amd_awfl_t *h, int level, const double *stencils
   if (level > h->P.nz + 1) return fail(PAM_AMD_EINVAL, "debug_weno: level must be < nz+2 (negative = uniform-grid constants)");
   USE_DEVICE(h);
   if (n == 0) return PAM_AMD_OK;
-  hipLaunchKernelGGL(awfl_weno_kat_kernel, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->P, level, stencils, n, left, right);
-  HIP_TRY(hipGetLastError());
-  return PAM_AMD_OK;
+  return launch(h, nullptr, awfl_weno_kat_kernel, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->P, level, stencils, n, left, right);
 }
 
 // One tendency stage on its own: stage 1 of a sub-step of length dt_dyn from the resident state (a forward-Euler step
