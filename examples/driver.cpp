@@ -46,6 +46,7 @@
 #include "modules/surface_friction.h"
 #include "modules/horizontal_average.h"
 #include "modules/time_average.h"
+#include "vertical_interp.h"
 #include "physics/micro/kessler_amd/Microphysics.h"
 
 #include <map>
@@ -233,7 +234,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-//   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--stats PATH]
+//   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--stats PATH] [--edges PATH]
 //          <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
@@ -309,7 +310,9 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              every CRM step; modules::horizontal_average of the "<var>_time_average" entries at the end of every
 //                              GCM step (and of a run cut short by --steps).  The (nz,nens) profiles go to PATH as JSON, every value
 //                              printed with %.17g (exact round trip); nothing else of the run changes.
-struct YamlModules { bool sat_adjust = false, surface_friction = false; double tau = 0, bflx = 0; std::string stats; };
+//   --edges PATH               at the end of the run: "temp" on the nz+1 vertical interfaces (pam::VerticalInterp<5>, zero gradient at
+//                              both ends), (nz+1,ny,nx,nens) raw fp64 to PATH; nothing else of the run changes.
+struct YamlModules { bool sat_adjust = false, surface_friction = false; double tau = 0, bflx = 0; std::string stats, edges; };
 
 // one JSON number that Python's json module reads back exactly (NaN / Infinity for the non-finite)
 static void stats_json_number(std::string &o, double v) {
@@ -479,6 +482,17 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       so << o;
       if (!so) endrun("cannot write the --stats file");
     }
+    if (!mods.edges.empty()) {
+      pam::VerticalInterp<5> vert_interp;
+      vert_interp.init(dm.get<real const, 2>("vertical_interface_height"));
+      real4d edges = vert_interp.cells_to_edges(dm.get<real const, 4>("temp"), vert_interp.BC_ZERO_GRADIENT, vert_interp.BC_ZERO_GRADIENT);
+      std::vector<real> host(edges.size());
+      if (hipMemcpy(host.data(), edges.data(), host.size() * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess) endrun("memcpy");
+      std::ofstream eo(mods.edges, std::ios::binary);
+      if (!eo) endrun("cannot open the --edges file");
+      eo.write((char *)host.data(), host.size() * sizeof(real));
+      if (!eo) endrun("cannot write the --edges file");
+    }
     if (hipDeviceSynchronize() != hipSuccess) endrun("device error");
     if (sf_in) (void)hipFree(sf_in);
     std::printf("Simulation Time: %g\n", etime_gcm);
@@ -563,8 +577,9 @@ int main(int argc, char **argv) {
         mods.bflx = std::atof(argv[++b]);
       }
       else if (o == "--stats" && b + 1 < argc - 1) mods.stats = argv[++b];
+      else if (o == "--edges" && b + 1 < argc - 1) mods.edges = argv[++b];
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
-               "[--stats PATH] <output.bin | ->");
+               "[--stats PATH] [--edges PATH] <output.bin | ->");
     }
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }

@@ -151,6 +151,33 @@ int pam_amd_time_average_zero(int num_fields, const long long *size, double *con
 int pam_amd_time_average_accumulate(int num_fields, const long long *size, const double *const *var, double *const *tavg, double factor,
                                     void *stream);
 
+/* pam::VerticalInterp<ord>  (pam_core/vertical_interp.h): a cell-centred field on its nz+1 vertical interfaces, by a WENO
+ * reconstruction of order `ord` on every member's own vertical grid.  Orders 3 and 5: the reference's sample_val for orders 7 and 9
+ * drops a `* z` (vertical_interp.h:139, :145) and is refused here.  Every argument is checked before the first HIP call.
+ *
+ * init(zint)  (:150-211).  zint: DEVICE "vertical_interface_height" (nz+1,nens), every member's interfaces finite and strictly
+ * increasing; nz, nens >= 1.  Copies zint to the host, builds the reconstruction matrices there and uploads them; synchronises
+ * `stream`.  Where every member has the same interfaces ONE shared table is kept.  *handle: to be passed to the calls below. */
+int pam_amd_vertical_interp_init(int ord, int nz, int nens, const double *zint, void *stream, void **handle);
+
+/* cells_to_edges(data, bc_lower, bc_upper)  (:54-122).  data: DEVICE (nz,ny,nx,nens); edges: DEVICE (nz+1,ny,nx,nens), a different
+ * array; ny, nx >= 1; bc_lower, bc_upper: 0 = BC_ZERO_GRADIENT, 1 = BC_ZERO_VALUE.  One launch on `stream`, no scratch, no
+ * synchronisation: edges(k) = 0.5 * (upper sample of cell k-1 + lower sample of cell k), the reference's bits. */
+int pam_amd_vertical_interp_cells_to_edges(void *handle, int ny, int nx, const double *data, int bc_lower, int bc_upper, double *edges,
+                                           void *stream);
+
+/* The matrices in use, DEVICE, owned by the handle: recon_lo (nz,hs+1,hs+1,hs+1,T) and recon_hi (nz,ord,ord,T), hs = (ord-1)/2, the
+ * reference's weno_recon_lo / weno_recon_hi; *shared = 1: T = 1 (one table for all members), 0: T = nens. */
+int pam_amd_vertical_interp_tables(void *handle, const double **recon_lo, const double **recon_hi, int *shared);
+
+/* shared = 0: use per-member tables although the members' interfaces are identical (the shared table repeated; built on the first
+ * such call, which synchronises `stream`); shared = 1: back to the shared table (EINVAL where the interfaces differ).  The results
+ * have the same bits either way. */
+int pam_amd_vertical_interp_set_table_sharing(void *handle, int shared, void *stream);
+
+/* Frees the handle and its tables (NULL: nothing to do). */
+int pam_amd_vertical_interp_finalize(void *handle);
+
 #ifdef __cplusplus
 }
 #endif

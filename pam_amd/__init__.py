@@ -9,3 +9,4 @@ from .dycore import Dycore  # noqa: F401
 from . import parallel  # noqa: F401
 from . import modules  # noqa: F401
 from .micro import Microphysics  # noqa: F401
+from .vertical_interp import VerticalInterp  # noqa: F401

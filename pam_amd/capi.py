@@ -113,6 +113,12 @@ MODULE_SYMBOLS = {
     "pam_amd_time_average_zero": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_void_p), C.c_void_p]),
     "pam_amd_time_average_accumulate": (C.c_int, [C.c_int, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_void_p)] * 2
                                         + [C.c_double, C.c_void_p]),
+    "pam_amd_vertical_interp_init": (C.c_int, [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "pam_amd_vertical_interp_cells_to_edges": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                         C.c_void_p]),
+    "pam_amd_vertical_interp_tables": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "pam_amd_vertical_interp_set_table_sharing": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "pam_amd_vertical_interp_finalize": (C.c_int, [C.c_void_p]),
 }
 
 

@@ -42,9 +42,16 @@ class DeviceView {
 
 }  // namespace pam
 // pam_const.h:30-55: YAKL device arrays by rank; here every rank is the same non-owning view
+typedef pam::DeviceView<real> real1d;
+typedef pam::DeviceView<real> real2d;
+typedef pam::DeviceView<real> real3d;
+typedef pam::DeviceView<real> real4d;
 typedef pam::DeviceView<real> real5d;
-typedef pam::DeviceView<real const> realConst5d;
 typedef pam::DeviceView<real const> realConst1d;
+typedef pam::DeviceView<real const> realConst2d;
+typedef pam::DeviceView<real const> realConst3d;
+typedef pam::DeviceView<real const> realConst4d;
+typedef pam::DeviceView<real const> realConst5d;
 typedef pam::DeviceView<int> int1d;
 typedef pam::DeviceView<int const> intConst1d;
 namespace pam {

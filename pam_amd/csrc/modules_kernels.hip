@@ -1,7 +1,7 @@
 // modules_kernels.hip -- gfx950 kernels of the coupler modules around the dycore (include/pam_amd_modules.h).
 // sponge_layer: pam_core/modules/sponge_layer.h:8-95.  Both kernels are tiny and HBM-bound (top 5 of 60 levels).
 // saturation_adjustment, surface_friction_init / compute_surface_friction, then the statistics modules (horizontal_average,
-// time_average_*): at the end of the file.
+// time_average_*), and last pam::VerticalInterp: at the end of the file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +17,7 @@
 #include "supercell_sounding.h"
 #include "moist_surface_device.h"  // saturation adjustment, surface friction: per-cell bodies shared with the host emulation
 #include "statistics_device.h"     // horizontal_average, time_average_*: the same, for the statistics modules
+#include "vertical_interp_device.h"  // pam::VerticalInterp: the same, for the cell-to-edge interpolation
 
 namespace {
 
@@ -1225,4 +1226,330 @@ extern "C" int pam_amd_time_average_accumulate(int num_fields, const long long *
   if (!std::isfinite(factor)) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "time_average_accumulate: factor must be finite");
   if (int rc = moist_surface_device_check("time_average_accumulate")) return rc;
   return time_average_launch<false>("time_average_accumulate", num_fields, size, var, tavg, factor, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// pam::VerticalInterp<ord> (pam_core/vertical_interp.h), orders 3 and 5: a cell-centred (nz,ny,nx,nens) field -> its values on the
+// nz+1 vertical interfaces, by a WENO reconstruction on every member's own vertical grid.  The arithmetic lives in
+// vertical_interp_device.h.  The matrices are built once per init on the host (as the dycore's, awfl_vertical.h) and kept on the
+// device as recon_lo (nz,hs+1,hs+1,hs+1,T) and recon_hi (nz,ord,ord,T), T = nens, or 1 where every member has the same column.
+// cells_to_edges is ONE launch: a thread marches up its column with a rolling window of `ord` values, computes each cell's polynomial
+// once, samples it at both edges and averages the upper sample of cell k-1 with the lower sample of cell k in registers -- the
+// reference's limits(2,nz+1,..) array and its second pass do not exist.  No scratch allocation, no atomics, no synchronisation.
+namespace {
+namespace vi = pama::vinterp;
+// workgroup shape of the per-member form, chosen by measurement at 1024 x 32x32x60; the macros exist for that A/B
+#ifndef PAMA_VI_WAVES
+#define PAMA_VI_WAVES 8
+#endif
+#ifndef PAMA_VI_COLS
+#define PAMA_VI_COLS 2
+#endif
+#ifndef PAMA_VI_MINWAVES
+#define PAMA_VI_MINWAVES 4
+#endif
+constexpr int VI_WAVES = PAMA_VI_WAVES;   // per-member form: wavefronts of a workgroup (threadIdx.y), each lane one member of a block of 64
+constexpr int VI_COLS = PAMA_VI_COLS;     // columns marched by one thread, so a workgroup's staged level serves VI_WAVES * VI_COLS columns
+constexpr int VI_FLAT = 256;     // shared-table form: threads of a workgroup
+
+// Per-member tables: grid (column groups, member blocks), block (64, VI_WAVES).  Lane = member, so every data row and every table row
+// is one coalesced 512 B line.  Per level, the 64 members' NTAB doubles (52 for order 5, 17 for order 3) are staged in LDS once per
+// workgroup: wavefront w fetches rows w, w + VI_WAVES, .. of the NEXT level into registers while the current level is being used.
+template <int ORD, class IDX>
+__global__ void __launch_bounds__(64 * VI_WAVES, PAMA_VI_MINWAVES) vertical_interp_member_kernel(int nz, int ncol, int nens, const double *__restrict__ data,
+                                                                               const double *__restrict__ tab_lo,
+                                                                               const double *__restrict__ tab_hi, int bc_lower,
+                                                                               int bc_upper, double *__restrict__ edges) {
+  using D = vi::Dims<ORD>;
+  constexpr int hs = D::hs, NLO = D::NLO, NHI = D::NHI, NTAB = D::NTAB, NROW = (NTAB + VI_WAVES - 1) / VI_WAVES;
+  __shared__ double tab[NTAB * 64];
+  const int lane = (int)threadIdx.x, w = (int)threadIdx.y;
+  const int e = (int)blockIdx.y * 64 + lane;
+  const bool member = e < nens;
+  const int col0 = ((int)blockIdx.x * VI_WAVES + w) * VI_COLS;
+  double idl[hs + 2];
+  vi::ideal_weights<ORD>(idl);
+
+  // this thread's rows of the staged level: row m = w + j * VI_WAVES is row m of recon_lo (m < NLO) or row m - NLO of recon_hi
+  const double *lo_k = tab_lo + e, *hi_k = tab_hi + e;   // member e of the current level's first rows
+  const auto fetch = [&](int j) {
+    const int m = w + j * VI_WAVES;
+    if (m >= NTAB || !member) return 0.0;
+    return (m < NLO) ? lo_k[(long long)m * nens] : hi_k[(long long)(m - NLO) * nens];
+  };
+  double held[NROW];
+#pragma unroll
+  for (int j = 0; j < NROW; j++) held[j] = fetch(j);
+
+  const IDX lev = (IDX)ncol * (IDX)nens;
+  bool live[VI_COLS];
+  IDX at[VI_COLS];
+  double u[VI_COLS][ORD], prev_upper[VI_COLS];
+#pragma unroll
+  for (int r = 0; r < VI_COLS; r++) {
+    live[r] = member && col0 + r < ncol;
+    at[r] = (IDX)(col0 + r) * (IDX)nens + (IDX)e;
+    prev_upper[r] = 0.0;
+    if (live[r]) {
+      u[r][hs] = data[at[r]];
+#pragma unroll
+      for (int kk = 0; kk < hs; kk++) u[r][kk] = vi::ghost_value(bc_lower, u[r][hs]);
+#pragma unroll
+      for (int kk = hs + 1; kk < ORD; kk++)
+        u[r][kk] = (kk - hs < nz) ? data[(IDX)(kk - hs) * lev + at[r]] : vi::ghost_value(bc_upper, u[r][kk - 1]);
+    }
+  }
+
+  for (int k = 0; k < nz; k++) {
+    __syncthreads();                 // level k-1 has been read by every wavefront
+#pragma unroll
+    for (int j = 0; j < NROW; j++)
+      if (w + j * VI_WAVES < NTAB) tab[(w + j * VI_WAVES) * 64 + lane] = held[j];
+    __syncthreads();
+    if (k + 1 < nz) {
+      lo_k += (long long)NLO * nens;
+      hi_k += (long long)NHI * nens;
+#pragma unroll
+      for (int j = 0; j < NROW; j++) held[j] = fetch(j);
+    }
+    double incoming[VI_COLS];
+#pragma unroll
+    for (int r = 0; r < VI_COLS; r++)
+      incoming[r] = (live[r] && k + hs + 1 < nz) ? data[(IDX)(k + hs + 1) * lev + at[r]] : 0.0;
+#pragma unroll
+    for (int r = 0; r < VI_COLS; r++) {
+      if (!live[r]) continue;
+      double lower, upper;
+      vi::cell_samples<ORD, int>(u[r], tab + lane, tab + NLO * 64 + lane, 64, idl, lower, upper);
+      edges[(IDX)k * lev + at[r]] = (k == 0) ? vi::bottom_edge(bc_lower, lower) : vi::edge_average(prev_upper[r], lower);
+      prev_upper[r] = upper;
+#pragma unroll
+      for (int kk = 0; kk < ORD - 1; kk++) u[r][kk] = u[r][kk + 1];
+      u[r][ORD - 1] = (k + hs + 1 < nz) ? incoming[r] : vi::ghost_value(bc_upper, u[r][ORD - 2]);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < VI_COLS; r++)
+    if (live[r]) edges[(IDX)nz * lev + at[r]] = vi::top_edge(bc_upper, prev_upper[r]);
+}
+
+// One shared table: lanes run along the flattened (column, member) index, a thread per column of one member.  The level's matrices
+// are the same for every lane: uniform addresses, fetched through the scalar cache.
+template <int ORD, class IDX>
+__global__ void __launch_bounds__(VI_FLAT) vertical_interp_shared_kernel(int nz, long long ncolens, const double *__restrict__ data,
+                                                                         const double *__restrict__ tab_lo,
+                                                                         const double *__restrict__ tab_hi, int bc_lower, int bc_upper,
+                                                                         double *__restrict__ edges) {
+  using D = vi::Dims<ORD>;
+  constexpr int hs = D::hs;
+  const long long c = (long long)blockIdx.x * VI_FLAT + (long long)threadIdx.x;
+  if (c >= ncolens) return;
+  const IDX lev = (IDX)ncolens, at = (IDX)c;
+  double idl[hs + 2];
+  vi::ideal_weights<ORD>(idl);
+  double u[ORD];
+  u[hs] = data[at];
+#pragma unroll
+  for (int kk = 0; kk < hs; kk++) u[kk] = vi::ghost_value(bc_lower, u[hs]);
+#pragma unroll
+  for (int kk = hs + 1; kk < ORD; kk++) u[kk] = (kk - hs < nz) ? data[(IDX)(kk - hs) * lev + at] : vi::ghost_value(bc_upper, u[kk - 1]);
+  double prev_upper = 0.0;
+  for (int k = 0; k < nz; k++) {
+    const double incoming = (k + hs + 1 < nz) ? data[(IDX)(k + hs + 1) * lev + at] : 0.0;
+    double lower, upper;
+    vi::cell_samples<ORD, int>(u, tab_lo + (long long)k * D::NLO, tab_hi + (long long)k * D::NHI, 1, idl, lower, upper);
+    edges[(IDX)k * lev + at] = (k == 0) ? vi::bottom_edge(bc_lower, lower) : vi::edge_average(prev_upper, lower);
+    prev_upper = upper;
+#pragma unroll
+    for (int kk = 0; kk < ORD - 1; kk++) u[kk] = u[kk + 1];
+    u[ORD - 1] = (k + hs + 1 < nz) ? incoming : vi::ghost_value(bc_upper, u[ORD - 2]);
+  }
+  edges[(IDX)nz * lev + at] = vi::top_edge(bc_upper, prev_upper);
+}
+
+constexpr unsigned VI_MAGIC = 0x56494e54u;   // "VINT"
+struct VerticalInterpHandle {
+  unsigned magic;
+  int ord, nz, nens, device;
+  bool identical;                 // every member has member 0's interfaces
+  bool shared;                    // cells_to_edges uses the one shared table
+  std::vector<double> h_lo, h_hi; // host tables as built: (nz,NLO,T), (nz,NHI,T), T = identical ? 1 : nens
+  double *d_shared;               // device: recon_lo then recon_hi, T = 1 (identical columns only)
+  double *d_member;               // device: recon_lo then recon_hi, T = nens (distinct columns, or sharing switched off)
+};
+
+int vi_error(int code, const char *who, const std::string &what) {
+  return pam_amd_set_last_error_(code, (std::string(who) + ": " + what).c_str());
+}
+
+template <int ORD>
+void vi_build_tables(VerticalInterpHandle &h, const double *zint) {
+  using D = vi::Dims<ORD>;
+  const int T = h.identical ? 1 : h.nens;
+  h.h_lo.assign((size_t)h.nz * D::NLO * T, 0.0);
+  h.h_hi.assign((size_t)h.nz * D::NHI * T, 0.0);
+  for (int e = 0; e < T; e++)
+    for (int k = 0; k < h.nz; k++) {
+      double lo[D::NLO], hi[D::NHI];
+      vi::level_tables<ORD>(zint + e, h.nens, h.nz, k, lo, hi);
+      for (int m = 0; m < D::NLO; m++) h.h_lo[((size_t)k * D::NLO + m) * T + e] = lo[m];
+      for (int m = 0; m < D::NHI; m++) h.h_hi[((size_t)k * D::NHI + m) * T + e] = hi[m];
+    }
+}
+
+int vi_table_sizes(int ord, size_t *nlo, size_t *nhi) {
+  *nlo = ord == 3 ? vi::Dims<3>::NLO : vi::Dims<5>::NLO;
+  *nhi = ord == 3 ? vi::Dims<3>::NHI : vi::Dims<5>::NHI;
+  return 0;
+}
+
+// the device copy of the tables with T members: the host tables as they are, or the shared one repeated for every member
+int vi_upload(const char *who, VerticalInterpHandle &h, int T, hipStream_t s, double **out) {
+  size_t nlo, nhi;
+  vi_table_sizes(h.ord, &nlo, &nhi);
+  const int have = h.identical ? 1 : h.nens;
+  const size_t n_lo = (size_t)h.nz * nlo * T, n_hi = (size_t)h.nz * nhi * T;
+  std::vector<double> rep;
+  const double *src_lo = h.h_lo.data(), *src_hi = h.h_hi.data();
+  if (T != have) {   // 1 -> nens
+    rep.resize(n_lo + n_hi);
+    for (size_t i = 0; i < (size_t)h.nz * nlo; i++) std::fill_n(rep.begin() + i * T, T, h.h_lo[i]);
+    for (size_t i = 0; i < (size_t)h.nz * nhi; i++) std::fill_n(rep.begin() + n_lo + i * T, T, h.h_hi[i]);
+    src_lo = rep.data();
+    src_hi = rep.data() + n_lo;
+  }
+  double *d = nullptr;
+  if (hipMalloc((void **)&d, (n_lo + n_hi) * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    return vi_error(PAM_AMD_ENOMEM, who, "cannot allocate the reconstruction matrices on the device");
+  }
+  if (hipMemcpyAsync(d, src_lo, n_lo * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(d + n_lo, src_hi, n_hi * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    const std::string msg = hipGetErrorString(hipGetLastError());
+    (void)hipFree(d);
+    return vi_error(PAM_AMD_ENOGPU, who, msg);
+  }
+  *out = d;
+  return PAM_AMD_OK;
+}
+
+VerticalInterpHandle *vi_handle(void *handle) {
+  VerticalInterpHandle *h = (VerticalInterpHandle *)handle;
+  return (h && h->magic == VI_MAGIC) ? h : nullptr;
+}
+
+template <int ORD, class IDX>
+void vi_launch(const VerticalInterpHandle &h, int ncol, const double *data, int bc_lower, int bc_upper, double *edges, hipStream_t s) {
+  size_t nlo, nhi;
+  vi_table_sizes(h.ord, &nlo, &nhi);
+  if (h.shared) {
+    const long long ncolens = (long long)ncol * h.nens;
+    hipLaunchKernelGGL((vertical_interp_shared_kernel<ORD, IDX>), dim3((unsigned)((ncolens + VI_FLAT - 1) / VI_FLAT)), dim3(VI_FLAT), 0, s,
+                       h.nz, ncolens, data, h.d_shared, h.d_shared + (size_t)h.nz * nlo, bc_lower, bc_upper, edges);
+  } else {
+    const int per = VI_WAVES * VI_COLS;
+    const dim3 grid((unsigned)((ncol + per - 1) / per), (unsigned)((h.nens + 63) / 64)), block(64, VI_WAVES);
+    hipLaunchKernelGGL((vertical_interp_member_kernel<ORD, IDX>), grid, block, 0, s, h.nz, ncol, h.nens, data, h.d_member,
+                       h.d_member + (size_t)h.nz * nlo * h.nens, bc_lower, bc_upper, edges);
+  }
+}
+}  // namespace
+
+extern "C" int pam_amd_vertical_interp_init(int ord, int nz, int nens, const double *zint, void *stream, void **handle) {
+  const char *who = "vertical_interp_init";
+  if (handle) *handle = nullptr;
+  if (ord != 3 && ord != 5)
+    return vi_error(PAM_AMD_EINVAL, who, "ord must be 3 or 5 (the reference's sample_val for orders 7 and 9 is not an interpolation)");
+  if (nz < 1 || nens < 1) return vi_error(PAM_AMD_EINVAL, who, "nz and nens must be >= 1");
+  if (!zint || !handle) return vi_error(PAM_AMD_EINVAL, who, "null pointer");
+  if ((nens + 63) / 64 > 65535) return vi_error(PAM_AMD_EINVAL, who, "nens exceeds the grid (64 x 65535 members)");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<double> z((size_t)(nz + 1) * nens);
+  if (hipMemcpyAsync(z.data(), zint, z.size() * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return vi_error(PAM_AMD_ENOGPU, who, hipGetErrorString(hipGetLastError()));
+  for (int e = 0; e < nens; e++)
+    if (!vi::column_ok(z.data() + e, nens, nz))
+      return vi_error(PAM_AMD_EINVAL, who, "member " + std::to_string(e) + ": the interfaces must be finite and strictly increasing");
+  VerticalInterpHandle *h = new VerticalInterpHandle();
+  h->magic = VI_MAGIC;
+  h->ord = ord; h->nz = nz; h->nens = nens;
+  h->d_shared = h->d_member = nullptr;
+  (void)hipGetDevice(&h->device);
+  h->identical = true;
+  for (int k = 0; k <= nz && h->identical; k++)
+    for (int e = 1; e < nens; e++)
+      if (z[(size_t)k * nens + e] != z[(size_t)k * nens]) { h->identical = false; break; }
+  h->shared = h->identical;
+  if (ord == 3) vi_build_tables<3>(*h, z.data());
+  else vi_build_tables<5>(*h, z.data());
+  if (int rc = vi_upload(who, *h, h->identical ? 1 : nens, s, h->identical ? &h->d_shared : &h->d_member)) {
+    h->magic = 0;
+    delete h;
+    return rc;
+  }
+  *handle = h;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_vertical_interp_set_table_sharing(void *handle, int shared, void *stream) {
+  const char *who = "vertical_interp_set_table_sharing";
+  VerticalInterpHandle *h = vi_handle(handle);
+  if (!h) return vi_error(PAM_AMD_EINVAL, who, "not a handle of vertical_interp_init");
+  if (shared != 0 && shared != 1) return vi_error(PAM_AMD_EINVAL, who, "shared must be 0 or 1");
+  if (shared && !h->identical) return vi_error(PAM_AMD_EINVAL, who, "the members' interfaces differ: there is no shared table");
+  if (!shared && !h->d_member)
+    if (int rc = vi_upload(who, *h, h->nens, (hipStream_t)stream, &h->d_member)) return rc;
+  h->shared = shared != 0;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_vertical_interp_cells_to_edges(void *handle, int ny, int nx, const double *data, int bc_lower, int bc_upper,
+                                                      double *edges, void *stream) {
+  const char *who = "vertical_interp_cells_to_edges";
+  if (!handle) return vi_error(PAM_AMD_EINVAL, who, "null handle");
+  if (ny < 1 || nx < 1) return vi_error(PAM_AMD_EINVAL, who, "ny and nx must be >= 1");
+  if (!data || !edges) return vi_error(PAM_AMD_EINVAL, who, "null pointer");
+  if (data == edges) return vi_error(PAM_AMD_EINVAL, who, "data and edges must be different arrays");
+  if ((bc_lower != vi::BC_ZERO_GRADIENT && bc_lower != vi::BC_ZERO_VALUE) || (bc_upper != vi::BC_ZERO_GRADIENT && bc_upper != vi::BC_ZERO_VALUE))
+    return vi_error(PAM_AMD_EINVAL, who, "bc_lower and bc_upper must be 0 (zero gradient) or 1 (zero value)");
+  VerticalInterpHandle *h = vi_handle(handle);
+  if (!h) return vi_error(PAM_AMD_EINVAL, who, "not a handle of vertical_interp_init");
+  const long long ncol = (long long)ny * nx;
+  if (ncol > 0x7fffff00LL || (ncol * h->nens + VI_FLAT - 1) / VI_FLAT > 0x7fffffffLL)
+    return vi_error(PAM_AMD_EINVAL, who, "ny x nx x nens exceeds the grid");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  const bool narrow = (long long)(h->nz + 1) * ncol * h->nens < IDX32_LIMIT;
+  hipStream_t s = (hipStream_t)stream;
+  if (h->ord == 3 && narrow) vi_launch<3, unsigned>(*h, (int)ncol, data, bc_lower, bc_upper, edges, s);
+  else if (h->ord == 3) vi_launch<3, long long>(*h, (int)ncol, data, bc_lower, bc_upper, edges, s);
+  else if (narrow) vi_launch<5, unsigned>(*h, (int)ncol, data, bc_lower, bc_upper, edges, s);
+  else vi_launch<5, long long>(*h, (int)ncol, data, bc_lower, bc_upper, edges, s);
+  return stats_launch_check(who);
+}
+
+extern "C" int pam_amd_vertical_interp_tables(void *handle, const double **recon_lo, const double **recon_hi, int *shared) {
+  const char *who = "vertical_interp_tables";
+  VerticalInterpHandle *h = vi_handle(handle);
+  if (!h) return vi_error(PAM_AMD_EINVAL, who, "not a handle of vertical_interp_init");
+  if (!recon_lo || !recon_hi || !shared) return vi_error(PAM_AMD_EINVAL, who, "null pointer");
+  size_t nlo, nhi;
+  vi_table_sizes(h->ord, &nlo, &nhi);
+  const double *base = h->shared ? h->d_shared : h->d_member;
+  *recon_lo = base;
+  *recon_hi = base + (size_t)h->nz * nlo * (h->shared ? 1 : h->nens);
+  *shared = h->shared ? 1 : 0;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_vertical_interp_finalize(void *handle) {
+  if (!handle) return PAM_AMD_OK;
+  VerticalInterpHandle *h = vi_handle(handle);
+  if (!h) return vi_error(PAM_AMD_EINVAL, "vertical_interp_finalize", "not a handle of vertical_interp_init");
+  if (h->d_shared) (void)hipFree(h->d_shared);
+  if (h->d_member) (void)hipFree(h->d_member);
+  h->magic = 0;
+  delete h;
+  return PAM_AMD_OK;
 }

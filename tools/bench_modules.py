@@ -1,7 +1,8 @@
 """The coupler-module timings of bench.py alone (Kessler, sponge layer, GCM forcing at the C2 grid), then saturation_adjustment and
 surface_friction_init / compute_surface_friction and the statistics modules (time_average_*, horizontal_average) at the same grid:
+then pam::VerticalInterp's cells_to_edges (order 5 with per-member tables and with the shared table, order 3 with per-member tables):
 one JSON object on stdout.
-Run on the GPU box:  python tools/bench_modules.py"""
+Run on the GPU box:  python tools/bench_modules.py            (--only vertical_interp: that row alone)"""
 import json
 import os
 import sys
@@ -15,6 +16,10 @@ import bench  # noqa: E402
 LANE_ISSUE_PER_S = bench.FP64_VALU_PEAK_TFLOPS * 1e12 / 2
 SATADJ_VALU_PER_ITER = 117      # VALU instructions of one bisection iteration (gfx950 ISA: 103 FP64 -- five divisions, one exp)
 SFC_VALU_PER_COLUMN = 113 + 8 * 288   # compute_surface_friction per column with a buoyancy flux: 8 diag_ustar iterations, both branches
+# VerticalInterp, per cell, from the gfx950 ISA of the level loop: FP64 VALU instructions (order 5: 13 divisions of ~13 instructions
+# each among them; order 3: 9) and all instructions of the loop body
+VINTERP_FP64_PER_CELL = {5: 345, 3: 176}
+VINTERP_INSTR_PER_CELL = {5: 435, 3: 225}
 
 
 def _events(fn, restore=None, n=5):
@@ -146,9 +151,50 @@ def statistics_timing(dev):
     return out
 
 
+def vertical_interp_timing(dev, n=11):
+    """pam_amd.VerticalInterp.cells_to_edges at the C2 grid on the L60 interfaces: one launch.  Algorithmic bytes: every cell read
+    once, every edge written once -- 8 (2 nz + 1) per (column, member) -- plus the tables once.  per-member tables: the members'
+    columns differ by a per-member stretch, so every member has its own 52 (order 5) or 17 (order 3) doubles per level."""
+    from pam_amd import VerticalInterp
+    from pam_amd import idealized as idz
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    ncolens = nens * nx * ny
+    z = torch.from_numpy(idz.l60_interfaces()).to(dev)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    stretch = 1.0 + 0.1 * torch.rand(nens, generator=gen, dtype=torch.float64, device=dev)
+    grids = {"per_member": (z[:, None] * stretch[None, :]).contiguous(), "shared": z[:, None].repeat(1, nens).contiguous()}
+    data = 280.0 + 20.0 * torch.rand((nz, ny, nx, nens), generator=gen, dtype=torch.float64, device=dev)
+    edges = torch.empty((nz + 1, ny, nx, nens), dtype=torch.float64, device=dev)
+    out = {}
+    for label, ord, tables in (("vertical_interp_ord5_per_member", 5, "per_member"), ("vertical_interp_ord5_shared", 5, "shared"),
+                               ("vertical_interp_ord3_per_member", 3, "per_member")):
+        v = VerticalInterp(ord)
+        v.init(grids[tables])
+        assert v.shared_table == (tables == "shared")
+        ntab = {5: 52, 3: 17}[ord] * nz * (1 if v.shared_table else nens)
+        for _ in range(3):
+            v.cells_to_edges(data, 0, 0, out=edges)      # warm-up
+        t = _events(lambda: v.cells_to_edges(data, 0, 0, out=edges), n=n)
+        nbytes = 8.0 * (2 * nz + 1) * ncolens + 8.0 * ntab
+        fp64_s = nz * ncolens * VINTERP_FP64_PER_CELL[ord] / LANE_ISSUE_PER_S
+        all_s = nz * ncolens * VINTERP_INSTR_PER_CELL[ord] / LANE_ISSUE_PER_S
+        hbm_frac, fp64_frac = nbytes / t / 1e6 / bench.HBM_PEAK_GBS, fp64_s * 1e3 / t
+        out[label] = {"ms": t, "calls": n, "bytes": nbytes, "table_bytes": 8.0 * ntab, "GBps": nbytes / t / 1e6, "hbm_frac": hbm_frac,
+                      "fp64_issue_floor_ms": fp64_s * 1e3, "fp64_issue_frac": fp64_frac, "all_issue_floor_ms": all_s * 1e3,
+                      "all_issue_frac": all_s * 1e3 / t, "binds": "fp64 issue" if fp64_frac > hbm_frac else "hbm"}
+        v.finalize()
+    del data, edges
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "vertical_interp"]:
+        print(json.dumps(vertical_interp_timing(dev)))
+        sys.exit(0)
     out = bench.modules_timing(torch, dev)
     out.update(moist_surface_timing(dev))
     out.update(statistics_timing(dev))
+    out.update(vertical_interp_timing(dev))
     print(json.dumps({k: ({kk: vv for kk, vv in v.items() if kk != "note"} if isinstance(v, dict) else v) for k, v in out.items()}))
