@@ -48,6 +48,8 @@
 #include "modules/time_average.h"
 #include "vertical_interp.h"
 #include "physics/micro/kessler_amd/Microphysics.h"
+#include "physics/sgs/none/SGS.h"
+#include "physics/radiation/forced_amd/radiation.h"
 
 #include <map>
 #include <sstream>
@@ -235,15 +237,15 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--stats PATH] [--edges PATH]
-//          <output.bin | ->
+//          [--radiation RAD_NX RAD_NY PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
 // out_freq, vcoords [, crm_nz, zlen, idealized, apply_sponge, initData].  What runs, in the reference's order:
-//   allocate_coupler_state -> set_grid -> micro.init -> dycore.init [-> initData on the device when `idealized`] ->
+//   allocate_coupler_state -> set_grid -> micro.init -> sgs.init -> dycore.init [-> initData on the device when `idealized`] ->
 //   initialize_from_supercell_column (driver.cpp:19-77: supercell_init column -> gcm_* columns -> broadcast_initial_gcm_column ->
 //   perturb_temperature, all on the device) when not idealized -> per GCM step { declare_current_profile_as_hydrostatic (what E3SM's
 //   MMF driver does once per GCM step; the standalone reference never calls it and runs on uninitialised variable_gravity);
-//   per CRM step { dycore -> sponge_layer -> micro } }.
+//   per CRM step { [radiation ->] dycore -> sponge_layer -> micro } }.
 // Not run: P3 and SHOC (the CI build's micro / sgs; external SCREAM code, out of scope) -- Kessler stands in as the microphysics -- and
 // modules::*_gcm_forcing_tendencies, whose field list is P3's tracer set (pam_core/modules/gcm_forcing.h:33-42).
 // vcoords: "uniform" (driver.cpp:135-153, with crm_nz and zlen) or the reference's file name `vcoords_equal_<N>_<H>km.nc` -- netCDF-4,
@@ -312,7 +314,16 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              printed with %.17g (exact round trip); nothing else of the run changes.
 //   --edges PATH               at the end of the run: "temp" on the nz+1 vertical interfaces (pam::VerticalInterp<5>, zero gradient at
 //                              both ends), (nz+1,ny,nx,nens) raw fp64 to PATH; nothing else of the run changes.
-struct YamlModules { bool sat_adjust = false, surface_friction = false; double tau = 0, bflx = 0; std::string stats, edges; };
+//   --radiation RAD_NX RAD_NY PATH  the forced Radiation plug-in: PATH holds "rad_enthalpy_tend", raw fp64 (nz,rad_ny,rad_nx,nens), read
+//                              once after the init; Radiation::timeStep runs FIRST in every CRM step, before the dycore, so that the
+//                              dynamics see the heated state (no driver of the reference calls Radiation: the position is this
+//                              project's decision).
+struct YamlModules {
+  bool sat_adjust = false, surface_friction = false, radiation = false;
+  double tau = 0, bflx = 0;
+  int rad_nx = 0, rad_ny = 0;
+  std::string stats, edges, rad_path;
+};
 
 // one JSON number that Python's json module reads back exactly (NaN / Infinity for the non-finite)
 static void stats_json_number(std::string &o, double v) {
@@ -373,8 +384,23 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     coupler.set_grid(xlen, ylen, zint);                                      // driver.cpp:180
     Dycore dycore;
     Microphysics micro;
-    micro.init(coupler);                                                     // driver.cpp:189 (sgs: SHOC, out of scope)
+    SGS sgs;
+    Radiation rad;
+    micro.init(coupler);                                                     // driver.cpp:189
+    sgs.init(coupler);                                                       // driver.cpp:190 (the reference's CI build: SHOC, out of scope)
     dycore.init(coupler);                                                    // driver.cpp:191
+    if (mods.radiation) {
+      coupler.set_option<int>("rad_nx", mods.rad_nx);
+      coupler.set_option<int>("rad_ny", mods.rad_ny);
+      rad.init(coupler);
+      auto tend = coupler.get_data_manager_device_readwrite().get<real, 4>("rad_enthalpy_tend");
+      std::vector<real> h(tend.size());
+      std::ifstream rin(mods.rad_path, std::ios::binary);
+      if (!rin) endrun("cannot open the --radiation file");
+      rin.read((char *)h.data(), h.size() * sizeof(real));
+      if (!rin || rin.peek() != std::ifstream::traits_type::eof()) endrun("the --radiation file is not (nz,rad_ny,rad_nx,nens) fp64");
+      if (hipMemcpy(tend.data(), h.data(), h.size() * sizeof(real), hipMemcpyHostToDevice) != hipSuccess) endrun("memcpy");
+    }
     std::printf("Dycore: %s\nMicro : %s\nSGS   : none (SHOC is out of scope)\n\n", dycore.dycore_name(), micro.micro_name().c_str());   // driver.cpp:203-205
     std::printf("crm_nx:   %d\ncrm_ny:   %d\ncrm_nz:   %d\nxlen (m): %g\nylen (m): %g\n", crm_nx, crm_ny, crm_nz, xlen, ylen);
     if (apply_gcm_forcing) std::printf("apply_gcm_forcing: not run (modules::gcm_forcing works on P3's tracer set; P3 is out of scope)\n");
@@ -413,6 +439,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       dycore.declare_current_profile_as_hydrostatic(coupler);               // (E3SM's MMF driver: once per GCM step)
       int crm_steps_gcm = 0;
       for (int step_crm_phys = 0; step_crm_phys < nsteps_crm_phys && !stop; ++step_crm_phys) {
+        if (mods.radiation) coupler.run_module("radiation", [&](pam::PamCoupler &c) { rad.timeStep(c); });
         coupler.run_module("dycore", [&](pam::PamCoupler &c) { dycore.timeStep(c); });       // driver.cpp:248
         substeps += dycore.last_ncycles();
         if (check) {
@@ -578,8 +605,14 @@ int main(int argc, char **argv) {
       }
       else if (o == "--stats" && b + 1 < argc - 1) mods.stats = argv[++b];
       else if (o == "--edges" && b + 1 < argc - 1) mods.edges = argv[++b];
+      else if (o == "--radiation" && b + 3 < argc - 1) {
+        mods.radiation = true;
+        mods.rad_nx = std::atoi(argv[++b]);
+        mods.rad_ny = std::atoi(argv[++b]);
+        mods.rad_path = argv[++b];
+      }
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
-               "[--stats PATH] [--edges PATH] <output.bin | ->");
+               "[--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] <output.bin | ->");
     }
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }

@@ -178,6 +178,27 @@ int pam_amd_vertical_interp_set_table_sharing(void *handle, int shared, void *st
 /* Frees the handle and its tables (NULL: nothing to do). */
 int pam_amd_vertical_interp_finalize(void *handle);
 
+/* Radiation::timeStep(coupler) of the "forced" plug-in  (physics/radiation/forced/radiation.h:27-45; every CRM step): the GCM's
+ * radiative heating, given on rad_ny x rad_nx groups of CRM columns, applied to the CRM temperature:
+ *   temp(k,j,i,e) += rad_enthalpy_tend(k, j / (ny/rad_ny), i / (nx/rad_nx), e) / cp_d * crm_dt
+ * evaluated left to right with the IEEE division, every operation rounded (no fma): the reference's bits.
+ *   temp               DEVICE "temp" (nz,ny,nx,nens), in/out
+ *   rad_enthalpy_tend  DEVICE (nz,rad_ny,rad_nx,nens); must not overlap temp
+ *   rad_nx, rad_ny     >= 1 and divisors of nx, ny (the reference divides by zero for rad_nx > nx and reads past the tendency where
+ *                      a remainder is left: both are EINVAL here)
+ *   cp_d               finite and positive; crm_dt finite
+ * Every argument is checked before the first HIP call, so an EINVAL return has written nothing.  One launch on `stream`, no
+ * scratch, no synchronisation. */
+int pam_amd_radiation_forced(int nens, int nx, int ny, int nz, int rad_nx, int rad_ny, double *temp,
+                             const double *rad_enthalpy_tend, double cp_d, double crm_dt, void *stream);
+
+/* PamCoupler::compute_pressure_array()  (pam_core/pam_coupler.h:360-393): pressure = rho_d*R_d*T + rho_v*R_v*T in every cell,
+ * evaluated left to right, every operation rounded (no fma): the reference's bits.  DEVICE arrays (nz,ny,nx,nens): rho_d
+ * "density_dry", rho_v "water_vapor", temp "temp" (in); pressure (out), which must not overlap an input.  R_d, R_v finite.
+ * Checked, launched and ordered as above. */
+int pam_amd_compute_pressure(int nens, int nx, int ny, int nz, const double *rho_d, const double *rho_v,
+                             const double *temp, double R_d, double R_v, double *pressure, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

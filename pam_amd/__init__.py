@@ -10,3 +10,4 @@ from . import parallel  # noqa: F401
 from . import modules  # noqa: F401
 from .micro import Microphysics  # noqa: F401
 from .vertical_interp import VerticalInterp  # noqa: F401
+from .physics import Radiation, RadiationNone, SGSNone, MicrophysicsNone  # noqa: F401

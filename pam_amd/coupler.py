@@ -202,6 +202,24 @@ class PamCoupler:
         f(self)
         return self.dm.get_dirty_entries()
 
+    def compute_pressure_array(self):
+        """pam_coupler.h:360-393: rho_d*R_d*T + rho_v*R_v*T of "density_dry", "water_vapor" and "temp", (nz,ny,nx,nens), one launch
+        on the current stream.  The coupler keeps the array and reuses it: a later call of the same shape overwrites the earlier
+        result (the reference returns a fresh array every time); clone() what has to outlive the next call."""
+        from . import capi
+        nz, ny, nx, nens = self.get_nz(), self.get_ny(), self.get_nx(), self.get_nens()
+        if min(nz, ny, nx, nens) < 1:
+            endrun("ERROR: compute_pressure_array: the coupler state is not allocated")
+        rho_d, rho_v, temp = (self.dm.get(n, readonly=True) for n in ("density_dry", "water_vapor", "temp"))
+        R_d, R_v = float(self.get_option("R_d")), float(self.get_option("R_v"))
+        p = getattr(self, "_pressure", None)
+        if p is None or tuple(p.shape) != (nz, ny, nx, nens) or p.device != rho_d.device:
+            p = self._pressure = torch.empty((nz, ny, nx, nens), dtype=torch.float64, device=rho_d.device)
+        with torch.cuda.device(self.device):
+            capi.check(capi.load().pam_amd_compute_pressure(nens, nx, ny, nz, rho_d.data_ptr(), rho_v.data_ptr(), temp.data_ptr(), R_d, R_v,
+                                                            p.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+        return p
+
     # ---- convenience for tests / bench: load numpy coupler fields into HBM and read them back
     def load_fields(self, fields):
         for k in ("density_dry", "uvel", "vvel", "wvel", "temp"):

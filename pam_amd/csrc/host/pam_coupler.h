@@ -7,6 +7,11 @@
 //   pam::DataManager   pam_core/DataManager.h:90-312   name -> device array + dims, dirty flags, ownership
 //   pam::PamCoupler    pam_core/pam_coupler.h:59-293   grid getters, options facade, tracer registry, run_module
 //   endrun             pam_core/pam_const.h:249-252    print to stderr and throw
+//
+// OWNERSHIP of compute_pressure_array().  The reference returns a freshly allocated, reference-counted real4d.  The arrays here are
+// non-owning views, so THE COUPLER owns the storage of the returned pressure: it is allocated on the first call, reused by every
+// later call of the same shape (the earlier result is overwritten), replaced when the shape changes, and freed with the coupler.  A
+// caller that needs two results at once copies the first.  The work runs on the default stream, unsynchronised, like the modules.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +21,9 @@
 #include <string>
 #include <variant>
 #include <vector>
+
+#include "pam_amd_awfl.h"
+#include "pam_amd_modules.h"
 
 typedef double real;
 
@@ -196,8 +204,11 @@ class PamCoupler {
   DataManager dm;
   struct Tracer { std::string name, desc; bool positive, adds_mass; };
   std::vector<Tracer> tracers;
+  mutable real *pressure_store = nullptr;      // compute_pressure_array()'s result (see OWNERSHIP above)
+  mutable std::vector<int> pressure_dims;
  public:
   PamCoupler() {}
+  ~PamCoupler() { if (pressure_store) (void)hipFree(pressure_store); }
   PamCoupler(PamCoupler const &) = delete;
   PamCoupler &operator=(PamCoupler const &) = delete;
 
@@ -282,6 +293,32 @@ class PamCoupler {
       if (t.name == name) { desc = t.desc; positive = t.positive; adds_mass = t.adds_mass; found = true; return; }
     found = false;
   }
+
+  // pam_coupler.h:360-386: the pressure of every cell, DEVICE (nz,ny,nx,nens), owned by the coupler and reused between calls
+  real4d compute_pressure_array() const {
+    auto dens_dry = dm.get<real const, 4>("density_dry");
+    auto dens_wv = dm.get<real const, 4>("water_vapor");
+    auto temp = dm.get<real const, 4>("temp");
+    int nz = get_nz(), ny = get_ny(), nx = get_nx(), nens = get_nens();
+    if (nz < 1 || ny < 1 || nx < 1 || nens < 1) endrun("ERROR: compute_pressure_array: the coupler state is not allocated");
+    auto R_d = get_option<real>("R_d");
+    auto R_v = get_option<real>("R_v");
+    std::vector<int> dims = {nz, ny, nx, nens};
+    if (dims != pressure_dims) {
+      if (pressure_store) (void)hipFree(pressure_store);
+      pressure_store = nullptr;
+      pressure_dims.clear();
+      if (hipMalloc((void **)&pressure_store, (size_t)nz * ny * nx * nens * sizeof(real)) != hipSuccess)
+        endrun("ERROR: device allocation failed for the pressure array");
+      pressure_dims = dims;
+    }
+    int rc = pam_amd_compute_pressure(nens, nx, ny, nz, dens_dry.data(), dens_wv.data(), temp.data(), R_d, R_v, pressure_store, nullptr);
+    if (rc) endrun(pam_amd_awfl_last_error());
+    return real4d(pressure_store, dims);
+  }
+
+  // pam_coupler.h:389-391
+  static real compute_pressure(real rho_d, real rho_v, real T, real R_d, real R_v) { return rho_d * R_d * T + rho_v * R_v * T; }
 };
 
 }  // namespace pam

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -18,6 +19,7 @@
 #include "moist_surface_device.h"  // saturation adjustment, surface friction: per-cell bodies shared with the host emulation
 #include "statistics_device.h"     // horizontal_average, time_average_*: the same, for the statistics modules
 #include "vertical_interp_device.h"  // pam::VerticalInterp: the same, for the cell-to-edge interpolation
+#include "plugins_device.h"          // forced radiation, the coupler's pressure array: the same
 
 namespace {
 
@@ -1552,4 +1554,142 @@ extern "C" int pam_amd_vertical_interp_finalize(void *handle) {
   h->magic = 0;
   delete h;
   return PAM_AMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The forced radiation plug-in (physics/radiation/forced/radiation.h:27-45) and PamCoupler::compute_pressure_array
+// (pam_core/pam_coupler.h:360-393).  Both are one pass over (nz,ny,nx,nens) fields, one launch, no LDS, no scratch, no atomics; the
+// arithmetic lives in plugins_device.h.  IDX: unsigned while a field is below 2^29 doubles (every byte offset fits 32 bits).
+namespace {
+namespace pl = pama::plugins;
+constexpr long long PLUGINS_NARROW_CELLS = 1ll << 29;   // fields from this size on take the long long instances
+constexpr int RAD_WAVES = 4;     // wavefronts of a workgroup
+constexpr int RAD_ROWS = 8;      // consecutive rows (k,j,i) per wavefront: their loads are in flight together
+constexpr int PRES_UNROLL = 4;   // elements per thread and pass
+
+// A row is the nens members of one cell (k,j,i); lane = member, so every access is a coalesced row of up to 64 members.  A
+// wavefront owns RAD_ROWS consecutive rows of one block of 64 members: it splits its first row into (k,j,i) and the rad cell with
+// 32-bit divisions, wave-uniform, and steps both along the rows with compares -- no division per element, none of 64 bits.
+// The rad cell's row is read once per CRM row; its fx*fy re-reads hit the caches.  FULL: all RAD_ROWS rows exist (every wavefront
+// but the field's last).
+template <class IDX, bool FULL>
+__device__ __forceinline__ void radiation_forced_rows(int r0, int e, int nens, int nx, int ny, int nrows, int rad_nx, int rad_ny,
+                                                      double *__restrict__ temp, const double *__restrict__ tend, double cp_d,
+                                                      double dt) {
+  const int fx = nx / rad_nx, fy = ny / rad_ny;
+  int i = r0 % nx;
+  const int kj = r0 / nx;
+  int j = kj % ny, k = kj / ny;
+  int ir = pl::rad_index(i, nx, rad_nx), jr = pl::rad_index(j, ny, rad_ny);
+  int irem = i - ir * fx, jrem = j - jr * fy;
+  const IDX stride = (IDX)nens;
+  double *__restrict__ tp = temp + ((IDX)r0 * stride + (IDX)e);
+  const double *__restrict__ qp = tend + (IDX)e;
+  double t[RAD_ROWS], q[RAD_ROWS];
+#pragma unroll
+  for (int u = 0; u < RAD_ROWS; u++) {
+    if (FULL || r0 + u < nrows) {
+      t[u] = tp[(IDX)u * stride];
+      q[u] = qp[(IDX)((k * rad_ny + jr) * rad_nx + ir) * stride];
+    }
+    if (++irem == fx) { irem = 0; ir++; }
+    if (++i == nx) {
+      i = 0; ir = 0; irem = 0;
+      if (++jrem == fy) { jrem = 0; jr++; }
+      if (++j == ny) { j = 0; jr = 0; jrem = 0; k++; }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < RAD_ROWS; u++)
+    if (FULL || r0 + u < nrows) tp[(IDX)u * stride] = pl::radiation_forced(t[u], q[u], cp_d, dt);
+}
+
+template <class IDX>
+__global__ void __launch_bounds__(64 * RAD_WAVES) radiation_forced_kernel(int nens, int nx, int ny, int nrows, int rad_nx, int rad_ny,
+                                                                          int nblk, double *__restrict__ temp,
+                                                                          const double *__restrict__ tend, double cp_d, double dt) {
+  const unsigned group = (unsigned)blockIdx.x / (unsigned)nblk;                   // row group; blockIdx.x % nblk: the member block
+  const int e = (int)((unsigned)blockIdx.x - group * (unsigned)nblk) * 64 + (int)(threadIdx.x & 63u);
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long long first = ((long long)group * RAD_WAVES + wave) * RAD_ROWS;
+  if (first >= nrows || e >= nens) return;
+  const int r0 = (int)first;
+  if (r0 + RAD_ROWS <= nrows) radiation_forced_rows<IDX, true>(r0, e, nens, nx, ny, nrows, rad_nx, rad_ny, temp, tend, cp_d, dt);
+  else radiation_forced_rows<IDX, false>(r0, e, nens, nx, ny, nrows, rad_nx, rad_ny, temp, tend, cp_d, dt);
+}
+
+// element-wise over the collapsed fields, each block striding in passes of 256 x PRES_UNROLL elements
+template <class IDX>
+__global__ void __launch_bounds__(256) coupler_pressure_kernel(long long ncell, const double *__restrict__ rho_d,
+                                                               const double *__restrict__ rho_v, const double *__restrict__ temp,
+                                                               double R_d, double R_v, double *__restrict__ pressure) {
+  const IDX n = (IDX)ncell;
+  const IDX step = (IDX)gridDim.x * (IDX)(256 * PRES_UNROLL);
+  for (IDX base = (IDX)blockIdx.x * (IDX)(256 * PRES_UNROLL) + (IDX)threadIdx.x; base < n; base += step) {
+    double a[PRES_UNROLL], b[PRES_UNROLL], c[PRES_UNROLL];
+#pragma unroll
+    for (int u = 0; u < PRES_UNROLL; u++) {
+      const IDX o = base + (IDX)(u * 256);
+      if (o < n) { a[u] = rho_d[o]; b[u] = rho_v[o]; c[u] = temp[o]; }
+    }
+#pragma unroll
+    for (int u = 0; u < PRES_UNROLL; u++) {
+      const IDX o = base + (IDX)(u * 256);
+      if (o < n) pressure[o] = pl::compute_pressure(a[u], b[u], c[u], R_d, R_v);
+    }
+  }
+}
+
+// [a, a + na) and [b, b + nb) doubles share an element
+bool plugins_overlap(const double *a, long long na, const double *b, long long nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + (uintptr_t)nb * sizeof(double) && b0 < a0 + (uintptr_t)na * sizeof(double);
+}
+}  // namespace
+
+extern "C" int pam_amd_radiation_forced(int nens, int nx, int ny, int nz, int rad_nx, int rad_ny, double *temp,
+                                        const double *rad_enthalpy_tend, double cp_d, double crm_dt, void *stream) {
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "radiation: nens, nx, ny and nz must be >= 1");
+  if (rad_nx < 1 || rad_ny < 1 || nx % rad_nx != 0 || ny % rad_ny != 0)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "radiation: rad_nx and rad_ny must be >= 1 and divide nx and ny");
+  if (!temp || !rad_enthalpy_tend) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "radiation: null pointer");
+  if (!std::isfinite(crm_dt)) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "radiation: crm_dt must be finite");
+  if (!std::isfinite(cp_d) || !(cp_d > 0)) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "radiation: cp_d must be finite and positive");
+  const long long nrows = (long long)nz * ny * nx, ncell = nrows * nens, nrad = (long long)nz * rad_ny * rad_nx * nens;
+  const long long nblk = (nens + 63) / 64, groups = (nrows + RAD_WAVES * RAD_ROWS - 1) / (RAD_WAVES * RAD_ROWS);
+  if (nrows > 0x7fffffffLL - RAD_WAVES * RAD_ROWS || groups * nblk > 0x7fffffffLL)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "radiation: nz x ny x nx x member blocks exceeds the grid");
+  if (plugins_overlap(temp, ncell, rad_enthalpy_tend, nrad))
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "radiation: temp overlaps rad_enthalpy_tend");
+  if (int rc = moist_surface_device_check("radiation")) return rc;
+  const dim3 grid((unsigned)(groups * nblk)), block(64 * RAD_WAVES);
+  if (ncell < PLUGINS_NARROW_CELLS)
+    hipLaunchKernelGGL((radiation_forced_kernel<unsigned>), grid, block, 0, (hipStream_t)stream, nens, nx, ny, (int)nrows, rad_nx, rad_ny,
+                       (int)nblk, temp, rad_enthalpy_tend, cp_d, crm_dt);
+  else
+    hipLaunchKernelGGL((radiation_forced_kernel<long long>), grid, block, 0, (hipStream_t)stream, nens, nx, ny, (int)nrows, rad_nx, rad_ny,
+                       (int)nblk, temp, rad_enthalpy_tend, cp_d, crm_dt);
+  return stats_launch_check("radiation");
+}
+
+extern "C" int pam_amd_compute_pressure(int nens, int nx, int ny, int nz, const double *rho_d, const double *rho_v, const double *temp,
+                                        double R_d, double R_v, double *pressure, void *stream) {
+  const char *who = "compute_pressure_array";
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": nens, nx, ny and nz must be >= 1").c_str());
+  if (!rho_d || !rho_v || !temp || !pressure) return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": null pointer").c_str());
+  if (!std::isfinite(R_d) || !std::isfinite(R_v))
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": R_d and R_v must be finite").c_str());
+  const long long ncell = (long long)nz * ny * nx * nens;
+  if (plugins_overlap(pressure, ncell, rho_d, ncell) || plugins_overlap(pressure, ncell, rho_v, ncell) || plugins_overlap(pressure, ncell, temp, ncell))
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": pressure overlaps an input").c_str());
+  if (int rc = moist_surface_device_check(who)) return rc;
+  // ~2048 workgroups of 256 (eight per CU), never more than the field needs
+  const long long per_blk = 256LL * PRES_UNROLL, need = (ncell + per_blk - 1) / per_blk;
+  const dim3 grid((unsigned)std::min(need, 2048LL)), block(256);
+  if (ncell < PLUGINS_NARROW_CELLS)
+    hipLaunchKernelGGL((coupler_pressure_kernel<unsigned>), grid, block, 0, (hipStream_t)stream, ncell, rho_d, rho_v, temp, R_d, R_v, pressure);
+  else
+    hipLaunchKernelGGL((coupler_pressure_kernel<long long>), grid, block, 0, (hipStream_t)stream, ncell, rho_d, rho_v, temp, R_d, R_v, pressure);
+  return stats_launch_check(who);
 }

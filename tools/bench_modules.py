@@ -1,8 +1,9 @@
 """The coupler-module timings of bench.py alone (Kessler, sponge layer, GCM forcing at the C2 grid), then saturation_adjustment and
 surface_friction_init / compute_surface_friction and the statistics modules (time_average_*, horizontal_average) at the same grid:
 then pam::VerticalInterp's cells_to_edges (order 5 with per-member tables and with the shared table, order 3 with per-member tables):
-one JSON object on stdout.
-Run on the GPU box:  python tools/bench_modules.py            (--only vertical_interp: that row alone)"""
+then the forced radiation plug-in at three rad grids and the coupler's pressure array, with time_average_accumulate and a device
+copy timed beside them as yardsticks, three repetitions: one JSON object on stdout.
+Run on the GPU box:  python tools/bench_modules.py            (--only vertical_interp, --only plugins: those rows alone)"""
 import json
 import os
 import sys
@@ -188,8 +189,82 @@ def vertical_interp_timing(dev, n=11):
     return out
 
 
+COPY_GBS = 6300.0      # what a device-to-device copy reaches on this part (the measured copy of the same run is reported beside it)
+
+
+def plugins_timing(dev, n=11, reps=3):
+    """Radiation.timeStep at rad grids 1x1, 8x8 and 32x32 and PamCoupler.compute_pressure_array at the C2 grid, 3 warm-up calls and the
+    median of n event-timed calls, `reps` repetitions.  Algorithmic bytes: temp read and written plus the tendency read once
+    (8 / (fx fy) B per cell); three reads and one write for the pressure.  The yardsticks of the same run: time_average_accumulate
+    on the nine fields statistics_timing averages (24 B per element: the traffic shape of radiation at the 32x32 rad grid) and a
+    copy of one field (16 B per element)."""
+    from pam_amd import PamCoupler, Microphysics, modules
+    from pam_amd import idealized as idz
+    from pam_amd.capi import check, load
+    lib, stream = load(), torch.cuda.current_stream(dev).cuda_stream
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    cells = nens * nx * ny * nz
+    c = PamCoupler(dev)
+    c.set_option("crm_dt", 20.0)
+    c.set_option("gcm_physics_dt", 900.0)
+    c.allocate_coupler_state(nz, ny, nx, nens)
+    c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+    micro = Microphysics()
+    micro.init(c)
+    dm = c.get_data_manager_device_readwrite()
+    names = ["density_dry", "uvel", "vvel", "wvel", "temp"] + c.get_tracer_names() + ["precl"]
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for name in names:
+        t = dm.get(name)
+        t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev))
+    dm.get("temp").mul_(100.0).add_(200.0)
+    elems = sum(dm.get(name, readonly=True).numel() for name in names)
+    modules.time_average_init(c, names)
+    spare = torch.empty_like(dm.get("temp"))
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        return _events(fn, n=n)
+
+    def row(ms, nbytes):
+        gbs = nbytes / ms / 1e6
+        return {"ms": ms, "bytes": nbytes, "GBps": gbs, "hbm_frac": gbs / bench.HBM_PEAK_GBS, "copy_frac": gbs / COPY_GBS}
+
+    out = {"plugins_grid": "1024 x 32x32x60 (C2)", "plugins_method": "3 warm-up calls, median of %d event-timed calls, %d repetitions" % (n, reps)}
+    runs = []
+    for _ in range(reps):
+        r = {}
+        for g in (1, 8, 32):
+            # the C ABI itself: a coupler keeps the rad grid of its first Radiation.init (the dimensions rad_x, rad_y)
+            q = torch.rand((nz, g, g, nens), generator=gen, dtype=torch.float64, device=dev) - 0.5
+            temp = dm.get("temp")
+            r["radiation_forced_rad%dx%d" % (g, g)] = row(timed(lambda: check(lib.pam_amd_radiation_forced(
+                nens, nx, ny, nz, g, g, temp.data_ptr(), q.data_ptr(), 1003.0, 20.0, stream))), cells * 16.0 + q.numel() * 8.0)
+        r["compute_pressure_array"] = row(timed(lambda: c.compute_pressure_array()), cells * 32.0)
+        r["time_average_accumulate"] = row(timed(lambda: modules.time_average_accumulate(c, names)), elems * 24.0)
+        r["copy_one_field"] = row(timed(lambda: spare.copy_(dm.get("temp", readonly=True))), cells * 16.0)
+        runs.append(r)
+    for k in runs[0]:
+        ms = sorted(r[k]["ms"] for r in runs)
+        fr = sorted(r[k]["hbm_frac"] for r in runs)
+        out[k] = dict(runs[0][k], ms=ms[len(ms) // 2], ms_repetitions=[r[k]["ms"] for r in runs], hbm_frac=fr[len(fr) // 2],
+                      hbm_frac_spread=fr[-1] - fr[0], GBps=runs[0][k]["bytes"] / ms[len(ms) // 2] / 1e6,
+                      copy_frac=runs[0][k]["bytes"] / ms[len(ms) // 2] / 1e6 / COPY_GBS)
+    y = out["time_average_accumulate"]
+    out["radiation_32x32_vs_time_average_accumulate"] = {
+        "hbm_frac_difference": out["radiation_forced_rad32x32"]["hbm_frac"] - y["hbm_frac"], "yardstick_spread": y["hbm_frac_spread"],
+        "holds": out["radiation_forced_rad32x32"]["hbm_frac"] >= y["hbm_frac"] - y["hbm_frac_spread"]}
+    del micro, dm, c, spare
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "plugins"]:
+        print(json.dumps(plugins_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "vertical_interp"]:
         print(json.dumps(vertical_interp_timing(dev)))
         sys.exit(0)
@@ -197,4 +272,5 @@ if __name__ == "__main__":
     out.update(moist_surface_timing(dev))
     out.update(statistics_timing(dev))
     out.update(vertical_interp_timing(dev))
+    out.update(plugins_timing(dev))
     print(json.dumps({k: ({kk: vv for kk, vv in v.items() if kk != "note"} if isinstance(v, dict) else v) for k, v in out.items()}))
