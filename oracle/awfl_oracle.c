@@ -1209,9 +1209,13 @@ void awfl_oracle_supercell_init(int nz, const double *zint, double Rd, double Rv
 /* Kessler microphysics, "next row" N4 (physics/micro/kessler/Microphysics.h:120-268 timeStep, :346-457 kessler()).
  * Arrays are the coupler's (nz, ncol) collapsed views, ncol = ny*nx*nens (get_lev_col); zmid (nz,nens); precl (ncol).
  * rainsplit_in > 0 overrides the sub-cycle count (ensemble shards must agree on the global minimum).  Returns rainsplit. */
-int awfl_oracle_kessler(int nens, int nx, int ny, int nz, double *rho_v, double *rho_c, double *rho_r, const double *rho_dry,
+/* census, if not NULL: KESSLER_CENSUS_N counters of the branches the run took, one count per cell and sub-cycle (the last per cell
+ * of the time-step limit); the counters only read what the scheme computes. */
+enum { KC_AUTOCONV_ON, KC_AUTOCONV_OFF_CLOUD, KC_QR_CLAMP, KC_RAINFREE_SED, KC_ERN_TMP1, KC_ERN_TMP2, KC_ERN_QR, KC_CONDENSATION,
+       KC_EVAP_PARTIAL, KC_EVAP_COMPLETE, KC_NO_CLOUD, KC_SLOW_FALL, KESSLER_CENSUS_N };
+static int kessler_body(int nens, int nx, int ny, int nz, double *rho_v, double *rho_c, double *rho_r, const double *rho_dry,
                         double *temp, double *precl, const double *zmid_in, double dt, double R_d, double R_v, double cp_d,
-                        double p0, int rainsplit_in) {
+                        double p0, int rainsplit_in, long long *census) {
   const size_t ncol = (size_t)ny * nx * nens;
   const size_t n = (size_t)nz * ncol;
 #define A2(a, k, i) a[(size_t)(k) * ncol + (i)]
@@ -1242,6 +1246,7 @@ int awfl_oracle_kessler(int nens, int nx, int ny, int nz, double *rho_v, double 
   for (int k = 0; k < nz - 1; k++) for (size_t i = 0; i < ncol; i++) {
     double d = (A2(velqr, k, i) > 1.e-10) ? 0.8 * (A2(z, k + 1, i) - A2(z, k, i)) / A2(velqr, k, i) : dt;
     if (d < dt_max) dt_max = d;
+    if (census && A2(velqr, k, i) > 0 && !(A2(velqr, k, i) > 1.e-10)) census[KC_SLOW_FALL]++;
   }
   int rainsplit = rainsplit_in > 0 ? rainsplit_in : (int)ceil(dt / dt_max);
   double dt0 = dt / (double)rainsplit;
@@ -1258,6 +1263,12 @@ int awfl_oracle_kessler(int nens, int nx, int ny, int nz, double *rho_v, double 
     for (int k = 0; k < nz; k++) for (size_t i = 0; i < ncol; i++) {
       double qrprod = A2(qc, k, i) - (A2(qc, k, i) - dt0 * fmax(0.001 * (A2(qc, k, i) - 0.001), 0.)) /
                                          (1 + dt0 * 2.2 * pow(A2(qr, k, i), 0.875));
+      if (census) {
+        if (0.001 * (A2(qc, k, i) - 0.001) > 0.) census[KC_AUTOCONV_ON]++;
+        else if (A2(qc, k, i) > 0.) census[KC_AUTOCONV_OFF_CLOUD]++;
+        if (A2(qr, k, i) + qrprod + A2(sed, k, i) < 0.) census[KC_QR_CLAMP]++;
+        if (A2(qr, k, i) == 0. && A2(sed, k, i) > 0.) census[KC_RAINFREE_SED]++;
+      }
       A2(qc, k, i) = fmax(A2(qc, k, i) - qrprod, 0.);
       A2(qr, k, i) = fmax(A2(qr, k, i) + qrprod + A2(sed, k, i), 0.);
       double tmp = A2(pk, k, i) * A2(theta, k, i) - 36.;
@@ -1269,6 +1280,14 @@ int awfl_oracle_kessler(int nens, int nx, int ny, int nz, double *rho_v, double 
       double tmp2 = fmax(-prod - A2(qc, k, i), 0.);
       double tmp3 = A2(qr, k, i);
       double ern = fmin(tmp1, fmin(tmp2, tmp3));
+      if (census) {
+        /* which of the three bounds set a NON-ZERO evaporation (ties go to the first) */
+        if (ern > 0.) census[tmp1 <= tmp2 && tmp1 <= tmp3 ? KC_ERN_TMP1 : tmp2 <= tmp3 ? KC_ERN_TMP2 : KC_ERN_QR]++;
+        if (prod > 0.) census[KC_CONDENSATION]++;
+        else if (!(A2(qc, k, i) > 0.)) census[KC_NO_CLOUD]++;
+        else if (prod > -A2(qc, k, i)) { if (prod < 0.) census[KC_EVAP_PARTIAL]++; }
+        else census[KC_EVAP_COMPLETE]++;
+      }
       A2(theta, k, i) = A2(theta, k, i) + lv / (cp * A2(pk, k, i)) * (fmax(prod, -A2(qc, k, i)) - ern);
       A2(qv, k, i) = fmax(A2(qv, k, i) - fmax(prod, -A2(qc, k, i)) + ern, 0.);
       A2(qc, k, i) = A2(qc, k, i) + fmax(prod, -A2(qc, k, i));
@@ -1287,6 +1306,20 @@ int awfl_oracle_kessler(int nens, int nx, int ny, int nz, double *rho_v, double 
   free(r); free(rhalf); free(pc); free(velqr); free(sed);
 #undef A2
   return rainsplit;
+}
+
+int awfl_oracle_kessler(int nens, int nx, int ny, int nz, double *rho_v, double *rho_c, double *rho_r, const double *rho_dry,
+                        double *temp, double *precl, const double *zmid_in, double dt, double R_d, double R_v, double cp_d,
+                        double p0, int rainsplit_in) {
+  return kessler_body(nens, nx, ny, nz, rho_v, rho_c, rho_r, rho_dry, temp, precl, zmid_in, dt, R_d, R_v, cp_d, p0, rainsplit_in, NULL);
+}
+
+/* the same run with its branch census: census[KESSLER_CENSUS_N] is zeroed, then counted into */
+int awfl_oracle_kessler_census(int nens, int nx, int ny, int nz, double *rho_v, double *rho_c, double *rho_r, const double *rho_dry,
+                               double *temp, double *precl, const double *zmid_in, double dt, double R_d, double R_v, double cp_d,
+                               double p0, int rainsplit_in, long long *census) {
+  for (int c = 0; c < KESSLER_CENSUS_N; c++) census[c] = 0;
+  return kessler_body(nens, nx, ny, nz, rho_v, rho_c, rho_r, rho_dry, temp, precl, zmid_in, dt, R_d, R_v, cp_d, p0, rainsplit_in, census);
 }
 
 /* ---------------------------------------------------------------------------------------------- */

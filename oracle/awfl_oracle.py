@@ -89,6 +89,8 @@ def load(path=None):
     lib.awfl_oracle_supercell_init.argtypes = [C.c_int, _DP] + [C.c_double] * 3 + [_DP] * 6
     lib.awfl_oracle_kessler.restype = C.c_int
     lib.awfl_oracle_kessler.argtypes = [C.c_int] * 4 + [_DP] * 7 + [C.c_double] * 5 + [C.c_int]
+    lib.awfl_oracle_kessler_census.restype = C.c_int
+    lib.awfl_oracle_kessler_census.argtypes = lib.awfl_oracle_kessler.argtypes + [C.POINTER(C.c_longlong)]
     lib.awfl_oracle_sponge_layer.argtypes = [C.c_int] * 5 + [C.POINTER(_DP), _DP, _DP, C.c_double, C.c_int, C.c_double]
     if path is None:
         _LIB = lib
@@ -292,6 +294,25 @@ def kessler(rho_v, rho_c, rho_r, rho_dry, temp, zmid, dt, consts, rainsplit=0, l
     n = lib.awfl_oracle_kessler(nens, nx, ny, nz, _p(rho_v), _p(rho_c), _p(rho_r), _p(rho_dry), _p(temp), _p(precl), _p(zm),
                                 float(dt), consts["R_d"], consts["R_v"], consts["cp_d"], consts["p0"], int(rainsplit))
     return precl, n
+
+
+KESSLER_CENSUS = ("autoconversion_on", "autoconversion_off_with_cloud", "qr_clamped", "rain_free_cell_receives_sediment",
+                  "ern_limited_by_tmp1", "ern_limited_by_tmp2", "ern_limited_by_qr", "condensation", "partial_cloud_evaporation",
+                  "complete_cloud_evaporation", "no_cloud", "slow_fall_speed")
+
+
+def kessler_census(rho_v, rho_c, rho_r, rho_dry, temp, zmid, dt, consts, rainsplit=0, lib=None):
+    """kessler() with the census of the branches the run took: returns (precl, rainsplit, {counter: cell-updates}).  A cell counts
+    once per sub-cycle; "slow_fall_speed" (a fall speed in (0, 1e-10], the dt2d = dt branch of the time-step limit) once per cell;
+    the three "ern_limited_by_*" count non-zero evaporation only."""
+    lib = lib or load()
+    nz, ny, nx, nens = temp.shape
+    precl = np.zeros((ny, nx, nens))
+    zm = np.ascontiguousarray(zmid, dtype=np.float64)
+    census = (C.c_longlong * len(KESSLER_CENSUS))()
+    n = lib.awfl_oracle_kessler_census(nens, nx, ny, nz, _p(rho_v), _p(rho_c), _p(rho_r), _p(rho_dry), _p(temp), _p(precl), _p(zm),
+                                       float(dt), consts["R_d"], consts["R_v"], consts["cp_d"], consts["p0"], int(rainsplit), census)
+    return precl, n, dict(zip(KESSLER_CENSUS, (int(c) for c in census)))
 
 
 GCM_FORCING_CRM = ("density_dry", "uvel", "vvel", "temp", "water_vapor", "cloud_water", "ice", "cloud_water_num", "ice_num",

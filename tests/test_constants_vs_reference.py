@@ -83,7 +83,7 @@ def test_kessler_and_module_literals_appear_in_reference_oracle_and_kernels():
     the arithmetic itself is covered by the oracle-vs-HIP parity tests)."""
     ref = _recorded()
     ora = open(os.path.join(ROOT, "oracle", "awfl_oracle.c")).read()
-    hip = open(os.path.join(ROOT, "pam_amd", "csrc", "modules_kernels.hip")).read()
+    hip = open(os.path.join(ROOT, "pam_amd", "csrc", "kessler_device.h")).read()      # the bodies of the Kessler kernels
     for lit in KESSLER_LITERALS:
         pat = re.escape(lit.rstrip(".")) + r"(?![\d])"
         assert lit in ref["kessler_literals_found"], ("reference", lit)

@@ -1,13 +1,16 @@
 """Kessler microphysics ("next row" N4; physics/micro/kessler/Microphysics.h): oracle properties
 on CPU, HIP-vs-oracle parity on the GPU.  The scheme is floating point with pow/exp; the device's libm differs from
-glibc in the last place, so the parity tolerance is 1e-12 relative (written in the test), not bit-exact."""
+glibc in the last place, so the parity tolerance is 1e-12 relative (written in the test), not bit-exact: of the field's maximum
+on the smooth case below, and cell by cell -- 1e-12 of the water that is in a cell or can fall into it -- on every case, the smooth
+one and the states of tests/kessler_cases.py that reach every branch (the host emulation of the same bodies: tests/test_kessler_emu.py)."""
 import numpy as np
 import pytest
 
+import kessler_cases as kc
 from oracle import awfl_oracle as ao
 from pam_amd import idealized as idz
 
-C0 = dict(idz.CONSTS_DEFAULT, cp_d=1003.0, cp_v=1859.0)   # the scheme's own constants (Microphysics.h:66-71)
+C0 = kc.C0   # the scheme's own constants (Microphysics.h:66-71)
 
 
 def _case(nens=3, nx=6, ny=2, nz=30, heavy_rain=False):
@@ -60,7 +63,12 @@ def test_oracle_kessler_subcycles_when_rain_is_fast():
     assert n2 == n and np.array_equal(precl, precl2) and np.array_equal(s["temp"], s2["temp"])
 
 
-def _gpu_run(s, zi, nens, nx, ny, nz, dt, rainsplit=0):
+COUPLER_NAMES = (("water_vapor", "rho_v"), ("cloud_liquid", "rho_c"), ("precip_liquid", "rho_r"), ("density_dry", "rho_dry"),
+                 ("temp", "temp"))
+
+
+def _gpu_setup(s, zi, nens, nx, ny, nz, dt):
+    """a coupler on the GPU that holds the state `s`, and the plug-in initialised on it"""
     import torch
     from pam_amd import PamCoupler, Microphysics
     coupler = PamCoupler("cuda:0")
@@ -73,9 +81,14 @@ def _gpu_run(s, zi, nens, nx, ny, nz, dt, rainsplit=0):
     assert coupler.get_option("micro") == "kessler" and coupler.get_option("cp_d") == 1003.0
     dm = coupler.get_data_manager_device_readwrite()
     assert float(dm.get("water_vapor").abs().max()) == 0.0
-    for name, key in (("water_vapor", "rho_v"), ("cloud_liquid", "rho_c"), ("precip_liquid", "rho_r"),
-                      ("density_dry", "rho_dry"), ("temp", "temp")):
+    for name, key in COUPLER_NAMES:
         dm.get(name).copy_(torch.from_numpy(s[key]))
+    return coupler, micro, dm
+
+
+def _gpu_run(s, zi, nens, nx, ny, nz, dt, rainsplit=0):
+    import torch
+    coupler, micro, dm = _gpu_setup(s, zi, nens, nx, ny, nz, dt)
     dt_max = micro.max_stable_dt(coupler)
     out = {}
     dirty = coupler.run_module("micro", lambda c: out.setdefault("n", micro.timeStep(c, rainsplit)))
@@ -91,6 +104,7 @@ def _gpu_run(s, zi, nens, nx, ny, nz, dt, rainsplit=0):
 def test_gpu_kessler_matches_oracle(heavy, dt, ny):
     nens, nx, nz = 70, 6, 30
     zint, zi, zm, s = _case(nens=nens, nx=nx, ny=ny, nz=nz, heavy_rain=heavy)
+    s_in = {k: v.copy() for k, v in s.items()}
     got, n, dt_max, micro = _gpu_run(s, zi, nens, nx, ny, nz, dt)
     precl, n_ref = ao.kessler(s["rho_v"], s["rho_c"], s["rho_r"], s["rho_dry"], s["temp"], zm, dt, C0)
     assert n == n_ref and n == micro.rainsplit_for(dt, dt_max)
@@ -100,6 +114,60 @@ def test_gpu_kessler_matches_oracle(heavy, dt, ny):
     tol = 1e-12   # relative to the field's maximum: device pow/exp differ from glibc in the last place
     for k in got:
         assert np.abs(got[k] - s[k]).max() <= tol * np.abs(s[k]).max(), k
+    # and cell by cell (tests/kessler_cases.py)
+    kc.gate_against_oracle(got, s_in, zm, dt, n, "smooth", case="kessler_gpu_smooth_heavy%d_dt%g_ny%d" % (heavy, dt, ny))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("i", range(len(kc.NAMED)), ids=kc.NAMED_IDS)
+def test_gpu_kessler_named_cases_match_oracle_cell_by_cell(i):
+    """the states that reach every branch of the scheme and mix rainy and rain-free lanes in every wavefront (kessler_cases.NAMED:
+    1 .. 200 members, 2-D / 3-D, one sub-cycle, sub-cycled, and one forced sub-cycle of an unstable step) through the per-cell gate"""
+    name, (nens, nx, ny, nz, _), _ = kc.NAMED[i]
+    zi, zm, s, dt, forced = kc.named_state(kc.NAMED[i])
+    assert s["temp"].size <= 150000
+    got, n, dt_max, micro = _gpu_run(s, zi, nens, nx, ny, nz, dt, rainsplit=forced)
+    _, n_ref = kc.run_oracle(s, zm, dt, rainsplit=forced)
+    assert n == n_ref, (n, n_ref)
+    _, n_free = kc.run_oracle(s, zm, dt)
+    assert n_free == micro.rainsplit_for(dt, dt_max)
+    if not forced:
+        assert n == n_free
+    kc.gate_against_oracle(got, s, zm, dt, n, name, case="kessler_gpu_" + name)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.int64)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bad", ["nan_rain", "negative_rain", "nan_density"])
+def test_gpu_kessler_refuses_an_unusable_state_and_touches_nothing(bad):
+    """a NaN or negative rain cell, or a NaN dry density, below the top level: the time-step limit is not positive, timeStep returns
+    PAM_AMD_ESTATE before the column kernel runs, and every coupler array is bit for bit what it was"""
+    import torch
+    from pam_amd.capi import PamAmdError
+    nens, nx, ny, nz = 70, 5, 2, 20
+    zi, zm, s = kc.state(nens, nx, ny, nz, 21)
+    cell = (nz - 2, 1, 3, 66) if bad != "nan_density" else (7, 0, 2, 5)
+    if bad == "nan_rain":
+        s["rho_r"][cell] = np.nan
+    elif bad == "negative_rain":
+        s["rho_r"][cell] = -1e-6
+    else:
+        s["rho_dry"][cell] = np.nan
+    coupler, micro, dm = _gpu_setup(s, zi, nens, nx, ny, nz, 5.0)
+    names = [n for n, _ in COUPLER_NAMES] + ["precl"]
+    before = {n: dm.get(n).cpu().numpy().copy() for n in names}
+    for n, key in COUPLER_NAMES:
+        assert np.array_equal(_bits(before[n]), _bits(s[key])), n
+    for call in (lambda: micro.timeStep(coupler), lambda: micro.max_stable_dt(coupler)):
+        with pytest.raises(PamAmdError, match="sedimentation time-step limit is not positive") as err:
+            call()
+        assert "[code -4]" in str(err.value)      # PAM_AMD_ESTATE
+        torch.cuda.synchronize()
+        for n in names:
+            assert np.array_equal(_bits(dm.get(n).cpu().numpy()), _bits(before[n])), n
 
 
 @pytest.mark.gpu
@@ -128,7 +196,9 @@ FUZZ_SEEDS = int(__import__("os").environ.get("PAM_AMD_FUZZ_SEEDS", "12"))
 @pytest.mark.parametrize("seed", range(FUZZ_SEEDS))
 def test_gpu_kessler_random_shapes_match_oracle(seed):
     """seeded random shapes (1 .. 200 members, 2-D / 3-D, 4 .. 60 levels, light / heavy rain, short / long steps): the column kernel's
-    staging of the pow tables, its member / column indexing and the sub-cycle count against the oracle (PAM_AMD_FUZZ_SEEDS=N: N seeds)"""
+    staging of the pow tables, its member / column indexing and the sub-cycle count against the oracle (PAM_AMD_FUZZ_SEEDS=N: N seeds).
+    Odd seeds draw their state from kessler_cases.state() (every cell its own categories) instead of the smooth case; every seed
+    passes the per-cell gate as well."""
     rng = np.random.default_rng(90001 * seed + 3)
     while True:
         nens = int(rng.choice([1, 2, 3, 7, 16, 33, 64, 65, 70, 128, 200]))
@@ -137,7 +207,11 @@ def test_gpu_kessler_random_shapes_match_oracle(seed):
             break
     heavy = bool(rng.random() < 0.5)
     dt = float(rng.choice([1.0, 5.0, 30.0, 60.0]))
-    zint, zi, zm, s = _case(nens=nens, nx=nx, ny=ny, nz=nz, heavy_rain=heavy)
+    if seed % 2:
+        zi, zm, s = kc.state(nens, nx, ny, nz, 1000 + seed)
+    else:
+        zint, zi, zm, s = _case(nens=nens, nx=nx, ny=ny, nz=nz, heavy_rain=heavy)
+    s_in = {k: v.copy() for k, v in s.items()}
     got, n, dt_max, micro = _gpu_run(s, zi, nens, nx, ny, nz, dt)
     precl, n_ref = ao.kessler(s["rho_v"], s["rho_c"], s["rho_r"], s["rho_dry"], s["temp"], zm, dt, C0)
     what = "seed %d: nens %d, %dx%dx%d, heavy %d, dt %g, rainsplit %d" % (seed, nens, nx, ny, nz, heavy, dt, n_ref)
@@ -146,3 +220,4 @@ def test_gpu_kessler_random_shapes_match_oracle(seed):
     for k in got:
         assert np.isfinite(s[k]).all(), (what, k)
         assert np.abs(got[k] - s[k]).max() <= 1e-12 * max(np.abs(s[k]).max(), 1e-300), (what, k)
+    kc.gate_against_oracle(got, s_in, zm, dt, n, what)
