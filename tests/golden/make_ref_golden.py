@@ -85,6 +85,10 @@ GCM_KW = {"plain": {}, "starve_level": {"starve_level": True}, "starve_liquid": 
 MODULE_CASES = {
     "sponge": ("sponge", dict(nens=3, nx=5, ny=4, nz=12)),
     **{"gcm_" + k: ("gcm", dict(nens=3, nx=5, ny=2, nz=8, **v)) for k, v in GCM_KW.items()},
+    # states of tests/gcm_forcing_cases.py: every species through the level pass and the whole-CRM fallback in one call, and the
+    # cloud-free cells beside cloudy ones that send the level pass off on every application
+    "gcm_mixed": ("gcm", dict(nens=10, nx=3, ny=2, nz=6, seed=3, scenarios="mixed")),
+    "gcm_cloudfree_plain": ("gcm", dict(nens=3, nx=5, ny=2, nz=8, seed=3, scenarios="plain")),
     "broadcast": ("broadcast", dict(nens=3, nx=4, ny=2, nz=6)),
     "satadj_kessler": ("satadj", dict(micro="kessler", nens=3, nx=3, ny=2, nz=5)),
     "satadj_p3": ("satadj", dict(micro="p3", nens=3, nx=3, ny=2, nz=5)),
@@ -107,6 +111,12 @@ def module_inputs(kind, kw):
         import test_modules as tm
         zint, zi, zm, f = tm._case(kw["nens"], kw["nx"], kw["ny"], kw["nz"])
         return dict({k: f[k] for k in FIELD5}, tracers=f["tracers"], zint=zi)
+    if kind == "gcm" and "scenarios" in kw:
+        import gcm_forcing_cases as gc
+        scenarios = gc.MIXED if kw["scenarios"] == "mixed" else (kw["scenarios"],)
+        crm, gcm, dz = gc.state(kw["nens"], kw["nx"], kw["ny"], kw["nz"], kw["seed"], scenarios)
+        zint = np.concatenate([np.zeros((1, kw["nens"])), np.cumsum(dz, axis=0)], axis=0)
+        return dict(crm, **gcm, zint=zint)
     if kind == "gcm":
         import test_modules as tm
         extra = {k: v for k, v in kw.items() if k.startswith("starve")}

@@ -39,7 +39,8 @@ def test_oracle_sponge_layer_properties():
 @pytest.mark.parametrize("ny,nens,nx", [(1, 70, 5), (4, 70, 5), (6, 3, 11), (12, 1, 24)],
                          ids=["2d", "3d", "strips_small_ensemble", "strips_one_member"])
 def test_gpu_sponge_layer_matches_oracle(ny, nens, nx):
-    """the last two cases have ny*nx >= 16: the horizontal means are summed in STRIPS (sponge_mean_kernel + sponge_mean_finish_kernel)"""
+    """the horizontal means live in sponge_kernel's workgroup: each of a member's 16 slots sums its cells, slot_reduce adds the slot
+    sums.  The 2-D case has ny*nx = 5, so most slots own no cell; the last two have many cells per slot (66 and 288 columns)"""
     import torch
     from pam_amd import PamCoupler, modules
     tr = idz.TRACERS_KESSLER_SHOC

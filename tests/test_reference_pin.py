@@ -11,7 +11,7 @@ bodies (tests/emu) and the HIP path.
    every make_golden case, the D1 replay count, and a seeded sweep over test_fuzz_parity.draw_case (PAM_AMD_REF_SEEDS=N seeds,
    default 16).  All bit for bit.
  * Coupler modules: the oracle and tests/moist_surface_ref.py against the reference's sponge_layer, GCM forcing (three hole-filling
-   paths), broadcasts, saturation_adjustment (Kessler and P3 tracer sets), surface friction, Kessler (one and several sub-cycles)
+   paths of the liquid, and two states of tests/gcm_forcing_cases.py: every species in the level pass and the fallback), broadcasts, saturation_adjustment (Kessler and P3 tracer sets), surface friction, Kessler (one and several sub-cycles)
    and supercell_init on L60 -- bit for bit, through tests/golden/ref_mod_*.npz and live.
  * GPU (-m gpu): the HIP path against the fixtures through tests/parity_gate.py (at each case's noise floor) and the modules' own
    tolerances, and against the
