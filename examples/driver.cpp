@@ -236,7 +236,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-//   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--stats PATH] [--edges PATH]
+//   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
@@ -318,8 +318,12 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              once after the init; Radiation::timeStep runs FIRST in every CRM step, before the dycore, so that the
 //                              dynamics see the heated state (no driver of the reference calls Radiation: the position is this
 //                              project's decision).
+//   --validate                 dm.validate_all() (DataManager.h:411) after the last module of every CRM step: NaNs and infinities in
+//                              the double and float entries, negative values in the double, float, int and long long entries
+//                              registered positive-definite (every other type is not looked at), reported on stderr; one device scan and one synchronisation per step; stdout and the
+//                              output file are those of a run without it.
 struct YamlModules {
-  bool sat_adjust = false, surface_friction = false, radiation = false;
+  bool sat_adjust = false, surface_friction = false, radiation = false, validate = false;
   double tau = 0, bflx = 0;
   int rad_nx = 0, rad_ny = 0;
   std::string stats, edges, rad_path;
@@ -453,6 +457,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (!dbg.no_micro) coupler.run_module("micro", [&](pam::PamCoupler &c) { micro.timeStep(c); });         // driver.cpp:253
         if (mods.sat_adjust) coupler.run_module("saturation_adjustment", modules::saturation_adjustment);
         if (stats) coupler.run_module("time_average_accumulate", [&](pam::PamCoupler &c) { modules::time_average_accumulate(c, stat_names); });
+        if (mods.validate) dm.validate_all();
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         crm_steps++;
         crm_steps_gcm++;
@@ -603,6 +608,7 @@ int main(int argc, char **argv) {
         mods.tau = std::atof(argv[++b]);
         mods.bflx = std::atof(argv[++b]);
       }
+      else if (o == "--validate") mods.validate = true;
       else if (o == "--stats" && b + 1 < argc - 1) mods.stats = argv[++b];
       else if (o == "--edges" && b + 1 < argc - 1) mods.edges = argv[++b];
       else if (o == "--radiation" && b + 3 < argc - 1) {
@@ -612,7 +618,7 @@ int main(int argc, char **argv) {
         mods.rad_path = argv[++b];
       }
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
-               "[--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] <output.bin | ->");
+               "[--validate] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] <output.bin | ->");
     }
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }

@@ -199,6 +199,26 @@ int pam_amd_radiation_forced(int nens, int nx, int ny, int nz, int rad_nx, int r
 int pam_amd_compute_pressure(int nens, int nx, int ny, int nz, const double *rho_d, const double *rho_v,
                              const double *temp, double R_d, double R_v, double *pressure, void *stream);
 
+/* DataManager::validate(name) / validate_all()  (pam_core/DataManager.h:408-509): the state check a host model calls between modules
+ * while hunting a blow-up, as ONE read of the data on the device (the reference copies every array to the host and loops there).
+ * Takes a LIST of fields like the statistics above (32 per launch, a longer list split, the results independent of the split):
+ *   kind       per field: 0 double, 1 float, 2 int (4 bytes), 3 long long (8 bytes).  short, unsigned and long double entries are not
+ *              supported: nothing in PAM registers them, and the adaptors leave them unchecked like the reference leaves bool
+ *   size       per field, >= 1: number of elements; the element index is 64-bit throughout (the reference's int index wraps at 2^31)
+ *   data       DEVICE arrays, each aligned to its element size (a view offset by some elements is fine); never written
+ *   positive   per field: non-zero = positive-definite, negative values are offenders
+ *   count, first  HOST arrays of 3*num_fields, [3*f + class]: class 0 NaN (isnan; floating kinds), 1 inf (isinf, either sign; floating
+ *              kinds), 2 negative (x < 0; every kind, positive fields only).  -inf is inf and negative; -0.0 and a NaN with the sign
+ *              bit set are not negative.  count: number of offenders; first: lowest flat index of one, -1 where count is 0.  Integers
+ *              throughout: exact, and identical from run to run.
+ * Every argument is checked before the first HIP call; then every field must live on the CURRENT device, to which `stream` belongs
+ * (EINVAL otherwise: fields of two devices take two calls).  Launched on `stream`, which is synchronised once to bring back the 48 bytes
+ * per field.  Finding offenders is a result, not an error: the return value is 0.  The result scratch (48 bytes per field) is kept per
+ * device, grown on demand and freed by pam_amd_modules_finalize(); nothing is allocated per call once it is large enough.  A workgroup
+ * that finds nothing touches no global memory, so a clean state issues no atomics. */
+int pam_amd_validate_fields(int num_fields, const int *kind, const long long *size, const void *const *data,
+                            const int *positive, long long *count, long long *first, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,8 @@ MODULE_SYMBOLS = {
     "pam_amd_vertical_interp_finalize": (C.c_int, [C.c_void_p]),
     "pam_amd_radiation_forced": (C.c_int, [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "pam_amd_compute_pressure": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "pam_amd_validate_fields": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
 }
 
 

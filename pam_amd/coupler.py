@@ -14,6 +14,8 @@ Arrays live in HBM as torch.float64 CUDA tensors (torch is only the allocator / 
 DataManager hands out the tensors themselves (views, not copies) like `dm.get<T,N>` returns non-owning views
 (DataManager.h:285-312).  Errors raise PamAmdError where the reference calls endrun().
 """
+import sys
+
 import torch
 
 from .capi import PamAmdError
@@ -21,6 +23,12 @@ from .capi import PamAmdError
 
 def endrun(msg):
     raise PamAmdError(msg)
+
+
+# DataManager.h:475, :488, :503: the lines of validate, character for character
+_VALIDATE_LINES = ("WARNING: NaN discovered in: %s at global index: %d\n",
+                   "WARNING: inf discovered in: %s at global index: %d\n",
+                   "WARNING: negative value discovered in positive-definite entry: %s at global index: %d\n")
 
 
 class Options:
@@ -62,21 +70,21 @@ class DataManager:
                 endrun(f"ERROR: dimension {n} already exists with size {self._dims[n]} != {d}")   # DataManager.h:112-127
             self._dims[n] = d
 
-    def register_and_allocate(self, name, desc, dims, dim_names=None, dtype=torch.float64):
+    def register_and_allocate(self, name, desc, dims, dim_names=None, dtype=torch.float64, positive=False):
         if name in self._e:
             endrun(f"ERROR: Duplicate entry name {name}")                                           # DataManager.h:98-103
         if dim_names:
             self._check_dims(dims, dim_names)
         t = torch.zeros(tuple(dims), dtype=dtype, device=self.device)
-        self._e[name] = dict(data=t, desc=desc, dims=tuple(dims), dirty=False, owned=True)
+        self._e[name] = dict(data=t, desc=desc, dims=tuple(dims), dirty=False, owned=True, positive=bool(positive))
         return t
 
-    def register_existing(self, name, desc, tensor, dim_names=None):
+    def register_existing(self, name, desc, tensor, dim_names=None, positive=False):
         if name in self._e:
             endrun(f"ERROR: Duplicate entry name {name}")
         if dim_names:
             self._check_dims(tuple(tensor.shape), dim_names)
-        self._e[name] = dict(data=tensor, desc=desc, dims=tuple(tensor.shape), dirty=False, owned=False)
+        self._e[name] = dict(data=tensor, desc=desc, dims=tuple(tensor.shape), dirty=False, owned=False, positive=bool(positive))
 
     def unregister_and_deallocate(self, name):
         if name not in self._e:
@@ -105,6 +113,45 @@ class DataManager:
 
     def get_dimension_size(self, name):
         return self._dims.get(name, -1)
+
+    # ---- the state check (DataManager.h:408-509)
+    def _validate(self, names, die):
+        """One device scan (modules.validate_fields) over the named entries of a checked dtype -- float64, float32, int32, int64; any
+        other is skipped, as the reference skips bool -- and one synchronisation.  Only an entry with offenders is copied to the host,
+        where the reference's three loops write its lines to sys.stderr: every NaN line, then every inf line, then every negative
+        line (positive-definite entries).  With `die`, endrun("") follows the first line."""
+        import numpy as np
+        from . import modules
+        names = [n for n in names if self._e[n]["data"].dtype in modules.VALIDATE_KINDS and self._e[n]["data"].numel() > 0]
+        if not names:
+            return
+        tensors = [self._e[n]["data"] for n in names]
+        count, _ = modules.validate_fields(tensors, [self._e[n]["positive"] for n in names])
+        for name, t, c in zip(names, tensors, count):
+            if not c.any():
+                continue
+            a = t.detach().reshape(-1).cpu().numpy()
+            floating = a.dtype.kind == "f"
+            with np.errstate(invalid="ignore"):
+                masks = (np.isnan(a) if floating else None, np.isinf(a) if floating else None,
+                         (a < 0) if self._e[name]["positive"] else None)
+            for mask, line in zip(masks, _VALIDATE_LINES):
+                if mask is None:
+                    continue
+                for i in mask.nonzero()[0]:
+                    sys.stderr.write(line % (name, i))
+                    if die:
+                        endrun("")
+
+    def validate_all(self, die_on_failed_check=False):
+        """DataManager.h:411-413: every entry, in registration order"""
+        self._validate(list(self._e), die_on_failed_check)
+
+    def validate(self, name, die_on_failed_check=False):
+        """DataManager.h:419-423"""
+        if name not in self._e:
+            endrun(f"ERROR: Could not find entry {name}")
+        self._validate([name], die_on_failed_check)
 
     def clean_all_entries(self):
         for e in self._e.values():

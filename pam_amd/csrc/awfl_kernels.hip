@@ -2534,6 +2534,15 @@ int pam_amd_awfl_declare_current_profile_as_hydrostatic(pam_amd_awfl_t *h, const
     } else if (int rc = launch(h, nullptr, awfl_hydro_kernel, dim3(nblocks(n, 64)), dim3(64), 0, h->stream, h->P, h->prim0, h->act_hy_dens, h->act_hy_pres)) {
       return rc;
     }
+    // the arrays of the OTHER mode: no kernel reads them until the balance option changes, which asks for a new declare (time_step
+    // refuses without one), so their poison has done its work.  Zeroed, so that a state check of the coupler (DataManager::validate_all)
+    // finds no NaN in entries this mode never defines (the reference leaves them as allocated).
+    if (h->P.grav_balance) {
+      HIP_TRY(hipMemsetAsync(h->act_hy_dens, 0, (size_t)n * sizeof(double), h->stream));
+      HIP_TRY(hipMemsetAsync(h->act_hy_pres, 0, (size_t)n * sizeof(double), h->stream));
+    } else {
+      HIP_TRY(hipMemsetAsync(h->act_grav_var, 0, (size_t)n * sizeof(double), h->stream));
+    }
   }
   h->hydro_declared = true;
   return PAM_AMD_OK;

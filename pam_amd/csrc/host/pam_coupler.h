@@ -7,6 +7,7 @@
 //   pam::DataManager   pam_core/DataManager.h:90-312   name -> device array + dims, dirty flags, ownership
 //   pam::PamCoupler    pam_core/pam_coupler.h:59-293   grid getters, options facade, tracer registry, run_module
 //   endrun             pam_core/pam_const.h:249-252    print to stderr and throw
+//   DataManager::validate / validate_all   pam_core/DataManager.h:408-509   the state check, as one device scan (data_validation_*.h)
 //
 // OWNERSHIP of compute_pressure_array().  The reference returns a freshly allocated, reference-counted real4d.  The arrays here are
 // non-owning views, so THE COUPLER owns the storage of the returned pressure: it is allocated on the first call, reused by every
@@ -62,6 +63,8 @@ typedef pam::DeviceView<real const> realConst4d;
 typedef pam::DeviceView<real const> realConst5d;
 typedef pam::DeviceView<int> int1d;
 typedef pam::DeviceView<int const> intConst1d;
+#include "data_validation_helpers.h"   // the helpers of DataManager::validate (pam::validation)
+
 namespace pam {
 
 class Options {
@@ -83,9 +86,13 @@ class Options {
 class DataManager {
   struct Entry {
     void *ptr; std::string desc; std::vector<int> dims; size_t elem; bool owned; bool dirty;
+    int kind;        // element kind the state check reads (validation::kind_of<T>), -1: not checked (bool, ...)
+    bool positive;   // positive-definite: validate reports negative values (DataManager.h:25)
+    size_t seq;      // registration sequence number: validate_all walks the entries in registration order (DataManager.h:412)
   };
   std::map<std::string, Entry> entries;
   std::map<std::string, int> dimensions;
+  size_t next_seq = 0;
  public:
   DataManager() {}
   DataManager(DataManager const &) = delete;
@@ -106,14 +113,14 @@ class DataManager {
     void *p = nullptr;
     if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) endrun("ERROR: device allocation failed for " + name);
     (void)hipMemset(p, 0, n * sizeof(T));                       // allocate_coupler_state zero-fills (pam_coupler.h:325-355)
-    entries[name] = Entry{p, desc, dims, sizeof(T), true, false};
+    entries[name] = Entry{p, desc, dims, sizeof(T), true, false, validation::kind_of<T>(), positive, next_seq++};
   }
 
   template <class T>
   void register_existing(std::string name, std::string desc, std::vector<int> dims, T *ptr,
                          std::vector<std::string> dim_names = std::vector<std::string>(), bool positive = false) {       // DataManager.h:158-163
     if (entries.count(name)) endrun("ERROR: Duplicate entry name " + name);
-    entries[name] = Entry{(void *)ptr, desc, dims, sizeof(T), false, false};
+    entries[name] = Entry{(void *)ptr, desc, dims, sizeof(T), false, false, validation::kind_of<T>(), positive, next_seq++};
   }
 
   // DataManager.h:230-234: frees a managed entry's storage, only forgets a borrowed (register_existing) one
@@ -163,6 +170,16 @@ class DataManager {
     if (it == entries.end()) endrun("ERROR: Could not find entry " + name);
     return it->second.dims;
   }
+
+  // DataManager.h:408-509, defined in data_validation_members.h (included after the coupler below): NaNs and infinities in the double and
+  // float entries, negative values in the positive-definite double, float, int and long long entries; every other type is left
+  // unchecked.  ONE device scan and one synchronisation per call; only an entry with offenders is copied to the host, where the
+  // reference's loops write the reference's lines to stderr.  Nothing is allocated per entry.
+  void validate_all(bool die_on_failed_check = false) const;
+  void validate(std::string name, bool die_on_failed_check = false) const;
+  void validate_nan(std::string name, bool die_on_failed_check = false) const;
+  void validate_inf(std::string name, bool die_on_failed_check = false) const;
+  void validate_pos(std::string name, bool die_on_failed_check = false) const;
 
   int get_dimension_size(std::string name) const {
     auto it = dimensions.find(name);
@@ -322,3 +339,5 @@ class PamCoupler {
 };
 
 }  // namespace pam
+
+#include "data_validation_members.h"   // the definitions of DataManager::validate_all, validate, validate_nan/inf/pos

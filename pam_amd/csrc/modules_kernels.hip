@@ -21,6 +21,7 @@
 #include "vertical_interp_device.h"  // pam::VerticalInterp: the same, for the cell-to-edge interpolation
 #include "plugins_device.h"          // forced radiation, the coupler's pressure array: the same
 #include "kessler_device.h"          // Kessler microphysics: the per-column bodies, the same
+#include "validate_device.h"         // DataManager::validate: classification, a thread's walk and the fold, the same
 
 namespace {
 
@@ -481,9 +482,12 @@ int kessler_read_dt_max(const double *slot, hipStream_t s, double *out) {
   *out = v;
   return PAM_AMD_OK;
 }
+
+void validate_scratch_free();   // the result scratch of pam_amd_validate_fields, defined with it below
 }  // namespace
 
 extern "C" int pam_amd_modules_finalize(void) {
+  validate_scratch_free();
   std::lock_guard<std::mutex> lk(g_tab_mutex);
   int cur = -1;
   (void)hipGetDevice(&cur);
@@ -1111,6 +1115,150 @@ extern "C" int pam_amd_time_average_accumulate(int num_fields, const long long *
   if (!std::isfinite(factor)) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "time_average_accumulate: factor must be finite");
   if (int rc = moist_surface_device_check("time_average_accumulate")) return rc;
   return time_average_launch<false>("time_average_accumulate", num_fields, size, var, tavg, factor, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// DataManager::validate / validate_all (pam_core/DataManager.h:408-509) as one read of the data: per field the number of NaNs, of
+// infinities and (where the field is positive-definite) of negative values, and the lowest flat index of each.  The classification,
+// a thread's walk and the fold live in validate_device.h.  Like the statistics: a table of up to STATS_TABLE fields per launch,
+// grid.y = field, a longer list split (every field's six integers come from that field alone, so they do not depend on the split).
+// A workgroup folds its threads' findings by wavefront shuffles and through LDS, and touches global memory only if it found something:
+// then one atomicAdd and one atomicMin per class it found.  A clean field issues no atomics.
+namespace {
+namespace vd = pama::validate;
+
+struct ValidateTable { const void *data[STATS_TABLE]; long long size[STATS_TABLE]; int kind[STATS_TABLE]; int positive[STATS_TABLE]; };
+
+// count, first: 3 integers per field of the table (class 0 NaN, 1 inf, 2 negative); count starts at 0 and first at ~0, the "none" of
+// an unsigned minimum, which the host reads back as -1
+__global__ void __launch_bounds__(vd::THREADS) validate_kernel(ValidateTable T, unsigned long long *__restrict__ count,
+                                                               unsigned long long *__restrict__ first) {
+  const int f = (int)blockIdx.y;
+  const int tid = (int)threadIdx.x;
+  vd::Tally t;
+  vd::tally_clear(t);
+  vd::thread_scan_kind(T.kind[f], T.data[f], T.size[f], T.positive[f] != 0, (long long)blockIdx.x, (long long)gridDim.x, tid, t);
+  // the fold: inside the wavefront by shuffles, then the wavefronts' tallies through LDS
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    vd::Tally o;
+#pragma unroll
+    for (int c = 0; c < vd::NUM_CLASSES; c++) {
+      o.count[c] = __shfl_down(t.count[c], off, 64);
+      o.first[c] = __shfl_down(t.first[c], off, 64);
+    }
+    vd::tally_merge(t, o);
+  }
+  __shared__ vd::Tally waves[vd::THREADS / 64];
+  if ((tid & 63) == 0) waves[tid >> 6] = t;
+  __syncthreads();
+  if (tid != 0) return;
+  for (int w = 1; w < vd::THREADS / 64; w++) vd::tally_merge(t, waves[w]);
+  for (int c = 0; c < vd::NUM_CLASSES; c++)
+    if (t.count[c] != 0) {
+      atomicAdd(&count[3 * f + c], (unsigned long long)t.count[c]);
+      atomicMin(&first[3 * f + c], (unsigned long long)t.first[c]);
+    }
+}
+
+// the 48 bytes per field the kernel writes: per device, grown on demand, freed by pam_amd_modules_finalize().  A device's mutex is
+// held for a whole call on that device (which ends in a synchronisation anyway), so two host threads never share a scratch and
+// callers on different devices do not wait for each other.
+constexpr int VALIDATE_MAX_DEVICES = 64;
+struct ValidateScratch { std::mutex m; unsigned long long *p = nullptr; long long fields = 0; };
+ValidateScratch g_validate_scratch[VALIDATE_MAX_DEVICES];
+
+// the scratch `s` of the CURRENT device (its mutex held), at least `fields` fields large
+unsigned long long *validate_scratch(ValidateScratch &s, long long fields) {
+  if (s.fields < fields) {
+    long long want = 256;
+    while (want < fields) want *= 2;
+    if (s.p) (void)hipFree(s.p);
+    s.p = nullptr;
+    s.fields = 0;
+    if (hipMalloc((void **)&s.p, (size_t)want * 6 * sizeof(unsigned long long)) != hipSuccess) { s.p = nullptr; return nullptr; }
+    s.fields = want;
+  }
+  return s.p;
+}
+
+void validate_scratch_free() {
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  for (int d = 0; d < VALIDATE_MAX_DEVICES; d++) {
+    ValidateScratch &s = g_validate_scratch[d];
+    std::lock_guard<std::mutex> lk(s.m);
+    if (s.p) {
+      if (d != cur) (void)hipSetDevice(d);
+      (void)hipFree(s.p);
+      s.p = nullptr;
+      s.fields = 0;
+      if (d != cur && cur >= 0) (void)hipSetDevice(cur);
+    }
+  }
+}
+}  // namespace
+
+extern "C" int pam_amd_validate_fields(int num_fields, const int *kind, const long long *size, const void *const *data,
+                                       const int *positive, long long *count, long long *first, void *stream) {
+  if (num_fields < 1 || !kind || !size || !data || !positive)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "validate: bad num_fields or null table");
+  if (!count || !first) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "validate: null count or first");
+  for (int f = 0; f < num_fields; f++) {
+    if (kind[f] < 0 || kind[f] > 3) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "validate: kind must be 0 (double), 1 (float), 2 (int) or 3 (long long)");
+    if (size[f] < 1) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "validate: every size must be >= 1");
+    if (!data[f]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "validate: null field pointer");
+    if ((unsigned long long)(uintptr_t)data[f] % (unsigned)vd::kind_bytes(kind[f]) != 0)
+      return pam_amd_set_last_error_(PAM_AMD_EINVAL, "validate: field pointer not aligned to its element size");
+  }
+  if (int rc = moist_surface_device_check("validate")) return rc;
+  // the launches, the scratch and `stream` belong to the current device: every field must live there (memory whose device the
+  // runtime cannot name, such as host-registered memory, is taken as given)
+  int cur = -1;
+  if (hipGetDevice(&cur) != hipSuccess || cur < 0 || cur >= VALIDATE_MAX_DEVICES)
+    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "validate: no current HIP device");
+  for (int f = 0; f < num_fields; f++) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, data[f]) != hipSuccess) { (void)hipGetLastError(); continue; }
+    if (attr.type == hipMemoryTypeDevice && attr.device != cur)
+      return pam_amd_set_last_error_(PAM_AMD_EINVAL, "validate: every field must live on the current device (hipSetDevice to the fields' device first)");
+  }
+  ValidateScratch &scratch = g_validate_scratch[cur];
+  std::lock_guard<std::mutex> lk(scratch.m);
+  unsigned long long *res = validate_scratch(scratch, num_fields);
+  if (!res) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "validate: device allocation of the result scratch failed");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n3 = (size_t)num_fields * 3;
+  unsigned long long *d_count = res, *d_first = res + n3;
+  if (hipMemsetAsync(d_count, 0, n3 * sizeof(unsigned long long), s) != hipSuccess ||
+      hipMemsetAsync(d_first, 0xff, n3 * sizeof(unsigned long long), s) != hipSuccess)
+    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string("validate: ") + hipGetErrorString(hipGetLastError())).c_str());
+  for (int f0 = 0; f0 < num_fields; f0 += STATS_TABLE) {
+    const int nf = std::min(STATS_TABLE, num_fields - f0);
+    ValidateTable T;
+    long long need = 1;
+    for (int l = 0; l < STATS_TABLE; l++) {
+      const bool in = l < nf;
+      T.data[l] = in ? data[f0 + l] : nullptr;
+      T.size[l] = in ? size[f0 + l] : 0;
+      T.kind[l] = in ? kind[f0 + l] : 0;
+      T.positive[l] = in ? (positive[f0 + l] != 0) : 0;
+      if (in) need = std::max(need, vd::blocks_needed(T.kind[l], T.size[l]));
+    }
+    // ~2048 workgroups of 256 in all (eight per CU), never more than the largest field needs
+    const unsigned gx = (unsigned)std::max(1LL, std::min(need, (long long)std::max(1, 2048 / nf)));
+    hipLaunchKernelGGL(validate_kernel, dim3(gx, (unsigned)nf), dim3(vd::THREADS), 0, s, T, d_count + 3 * f0, d_first + 3 * f0);
+    if (int rc = stats_launch_check("validate")) return rc;
+  }
+  std::vector<unsigned long long> host(2 * n3);
+  if (hipMemcpyAsync(host.data(), res, 2 * n3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string("validate: ") + hipGetErrorString(hipGetLastError())).c_str());
+  for (size_t i = 0; i < n3; i++) {
+    count[i] = (long long)host[i];
+    first[i] = (long long)host[n3 + i];      // ~0 (nothing found) is -1
+  }
+  return PAM_AMD_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

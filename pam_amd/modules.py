@@ -321,3 +321,44 @@ def time_average_accumulate(coupler, names):
     with torch.cuda.device(coupler.device):
         check(lib.pam_amd_time_average_accumulate(len(names), _sizes(shapes), _ptr_table(var), _ptr_table(tavg), factor,
                                                   torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+VALIDATE_KINDS = {torch.float64: 0, torch.float32: 1, torch.int32: 2, torch.int64: 3}
+
+
+def validate_fields(tensors, positive):
+    """The state check of DataManager::validate / validate_all (pam_core/DataManager.h:408-509) as one device scan
+    (pam_amd_validate_fields): `tensors` is a list of contiguous float64, float32, int32 or int64 tensors on one device (a view offset
+    by some elements is fine), `positive` one flag per tensor (positive-definite: negative values are offenders).  Returns
+    (count, first), int64 numpy arrays of shape (len(tensors), 3): per tensor the number of NaNs, of infinities (either sign) and of
+    negative values, and the lowest flat index of each (-1 where the count is 0).  Reads only; launched on the current stream, which
+    is synchronised once."""
+    import numpy as np
+    from .coupler import endrun
+    tensors, positive = list(tensors), [bool(p) for p in positive]
+    if len(tensors) != len(positive):
+        endrun("ERROR: validate_fields: one positive flag per tensor")
+    count = np.zeros((len(tensors), 3), dtype=np.int64)
+    first = np.full((len(tensors), 3), -1, dtype=np.int64)
+    if not tensors:
+        return count, first
+    for t in tensors:
+        if t.dtype not in VALIDATE_KINDS:
+            endrun("ERROR: validate_fields: dtype %s is not float64, float32, int32 or int64" % t.dtype)
+        if not t.is_contiguous():
+            endrun("ERROR: validate_fields: contiguous tensors only")
+        if t.numel() < 1:
+            endrun("ERROR: validate_fields: empty tensor")
+        if t.device != tensors[0].device:
+            endrun("ERROR: validate_fields: the tensors must live on one device")
+    n = len(tensors)
+    kinds = (C.c_int * n)(*[VALIDATE_KINDS[t.dtype] for t in tensors])
+    sizes = (C.c_longlong * n)(*[t.numel() for t in tensors])
+    pos = (C.c_int * n)(*[int(p) for p in positive])
+    device = tensors[0].device
+    with torch.cuda.device(device):
+        check(capi.load().pam_amd_validate_fields(n, kinds, sizes, _ptr_table(tensors), pos,
+                                                  count.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                  first.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                  torch.cuda.current_stream(device).cuda_stream))
+    return count, first

@@ -3,7 +3,8 @@ surface_friction_init / compute_surface_friction and the statistics modules (tim
 then pam::VerticalInterp's cells_to_edges (order 5 with per-member tables and with the shared table, order 3 with per-member tables):
 then the forced radiation plug-in at three rad grids and the coupler's pressure array, with time_average_accumulate and a device
 copy timed beside them as yardsticks, three repetitions: one JSON object on stdout.
-Run on the GPU box:  python tools/bench_modules.py            (--only vertical_interp, --only plugins: those rows alone)"""
+Run on the GPU box:  python tools/bench_modules.py            (--only vertical_interp, --only plugins: those rows alone;
+--only validate: DataManager.validate_all's device scan with the two statistics rows of the same run beside it)"""
 import json
 import os
 import sys
@@ -189,6 +190,70 @@ def vertical_interp_timing(dev, n=11):
     return out
 
 
+def validate_timing(dev):
+    """DataManager.validate_all's device scan (pam_amd.validate_fields) at the C2 grid on the Kessler field set of statistics_timing
+    (4 GB), one warm-up call and the median of 5 like the statistics rows, which are timed beside it in the same run as yardsticks:
+    the clean state (no atomics), the same state with 1 % offenders of all three classes (every workgroup issues its atomics), and
+    once the reference-style path the scan replaces: one C2 field copied to the host and the three host loops, as validate takes
+    it for a dirty entry.  A call includes its one synchronisation and the 48 bytes per field it brings back."""
+    import time
+    from pam_amd import PamCoupler, Microphysics, modules
+    from pam_amd import idealized as idz
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    c = PamCoupler(dev)
+    c.set_option("crm_dt", 2.0)
+    c.set_option("gcm_physics_dt", 900.0)
+    c.allocate_coupler_state(nz, ny, nx, nens)
+    c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+    micro = Microphysics()
+    micro.init(c)
+    dm = c.get_data_manager_device_readwrite()
+    names = ["density_dry", "uvel", "vvel", "wvel", "temp"] + c.get_tracer_names() + ["precl"]
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for n in names:
+        t = dm.get(n)
+        t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev))
+    tens = [dm.get(n, readonly=True) for n in names]
+    positive = [True] * len(tens)
+    elems = sum(t.numel() for t in tens)
+    modules.time_average_init(c, names)
+    havg = [(n + "_time_average", n != "precl") for n in names]
+
+    def row(t, nbytes, **more):
+        return dict({"ms": t, "bytes": nbytes, "GBps": nbytes / t / 1e6, "hbm_frac": nbytes / t / 1e6 / bench.HBM_PEAK_GBS,
+                     "fields": len(names)}, **more)
+
+    out = {"validate_grid": "1024 x 32x32x60 (C2)", "validate_method": "one warm-up call, median of 5 event-timed calls"}
+    out["time_average_accumulate"] = row(_events(lambda: modules.time_average_accumulate(c, names)), elems * 24.0)
+    out["horizontal_average"] = row(_events(lambda: modules.horizontal_average(c, havg)), elems * 8.0)
+    count, _ = modules.validate_fields(tens, positive)
+    assert not count.any()
+    out["validate_clean"] = row(_events(lambda: modules.validate_fields(tens, positive)), elems * 8.0)
+    for t in tens:
+        r = torch.rand(t.shape, generator=gen, dtype=torch.float32, device=dev)
+        t.masked_fill_(r < 0.0033, float("nan"))
+        t.masked_fill_((r >= 0.0033) & (r < 0.0066), float("inf"))
+        t.masked_fill_((r >= 0.0066) & (r < 0.01), -1.0)
+        del r
+    count, _ = modules.validate_fields(tens, positive)
+    out["validate_1pct_offenders"] = row(_events(lambda: modules.validate_fields(tens, positive)), elems * 8.0,
+                                         offender_fraction=float(count.sum()) / elems)
+    # the reference-style path, once: one field to the host, then the reference's three loops (vectorised by numpy)
+    import numpy as np
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    host = tens[4].reshape(-1).cpu().numpy()
+    t1 = time.perf_counter()
+    found = [np.flatnonzero(np.isnan(host)).size, np.flatnonzero(np.isinf(host)).size, np.flatnonzero(host < 0).size]
+    t2 = time.perf_counter()
+    out["reference_style_one_field"] = {"copy_ms": (t1 - t0) * 1e3, "host_loops_ms": (t2 - t1) * 1e3, "ms": (t2 - t0) * 1e3,
+                                        "bytes": host.size * 8.0, "offenders": found, "calls": 1,
+                                        "note": "one sample, no warm-up; numpy's vectorised checks: a LOWER bound on the reference's scalar loops"}
+    del micro, dm, c, tens, host
+    torch.cuda.empty_cache()
+    return out
+
+
 COPY_GBS = 6300.0      # what a device-to-device copy reaches on this part (the measured copy of the same run is reported beside it)
 
 
@@ -264,6 +329,9 @@ if __name__ == "__main__":
     dev = torch.device("cuda:0")
     if sys.argv[1:] == ["--only", "plugins"]:
         print(json.dumps(plugins_timing(dev)))
+        sys.exit(0)
+    if sys.argv[1:] == ["--only", "validate"]:
+        print(json.dumps(validate_timing(dev)))
         sys.exit(0)
     if sys.argv[1:] == ["--only", "vertical_interp"]:
         print(json.dumps(vertical_interp_timing(dev)))
