@@ -236,7 +236,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-//   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--stats PATH] [--edges PATH]
+//   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
@@ -322,11 +322,16 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              the double and float entries, negative values in the double, float, int and long long entries
 //                              registered positive-definite (every other type is not looked at), reported on stderr; one device scan and one synchronisation per step; stdout and the
 //                              output file are those of a run without it.
+//   --diag PATH                one JSON line per OUTPUT step (where the "Etime , dtphys, maxw" line is printed) to PATH: for density_dry,
+//                              uvel, vvel, wvel, temp and every tracer the least and the greatest element with their flat indices, the
+//                              number of NaNs and the reproducible sum, of the whole field ("whole") and of every ensemble member
+//                              ("members"), taken on the device by two scans (pam_amd_field_diagnostics) without copying a field;
+//                              stdout and the output file are those of a run without it.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false;
   double tau = 0, bflx = 0;
   int rad_nx = 0, rad_ny = 0;
-  std::string stats, edges, rad_path;
+  std::string stats, edges, rad_path, diag;
 };
 
 // one JSON number that Python's json module reads back exactly (NaN / Infinity for the non-finite)
@@ -336,6 +341,27 @@ static void stats_json_number(std::string &o, double v) {
   else if (std::isinf(v)) std::snprintf(t, sizeof(t), v > 0 ? "Infinity" : "-Infinity");
   else std::snprintf(t, sizeof(t), "%.17g", v);
   o += t;
+}
+// --diag: one result set of pam::diagnostics::scan as JSON, scalars for the whole field (members = 0), lists per member
+static void diag_json(std::string &o, pam::diagnostics::FieldDiagnostics const &d) {
+  auto doubles = [&](char const *key, std::vector<double> const &v) {
+    o += std::string("\"") + key + "\": " + (d.members ? "[" : "");
+    for (size_t m = 0; m < v.size(); m++) { if (m) o += ", "; stats_json_number(o, v[m]); }
+    o += d.members ? "], " : ", ";
+  };
+  auto integers = [&](char const *key, std::vector<long long> const &v, bool last) {
+    o += std::string("\"") + key + "\": " + (d.members ? "[" : "");
+    for (size_t m = 0; m < v.size(); m++) o += (m ? ", " : "") + std::to_string(v[m]);
+    o += std::string(d.members ? "]" : "") + (last ? "" : ", ");
+  };
+  o += "{";
+  doubles("vmin", d.vmin);
+  doubles("vmax", d.vmax);
+  doubles("vsum", d.vsum);
+  integers("argmin", d.argmin, false);
+  integers("argmax", d.argmax, false);
+  integers("nan_count", d.nan_count, true);
+  o += "}";
 }
 static int run_yaml(const std::string &file, int nens_override, int steps_limit, bool check, const std::string &outfile, YamlDebug dbg = YamlDebug(),
                     YamlModules mods = YamlModules()) {
@@ -433,6 +459,14 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     std::vector<std::tuple<std::string, bool>> stat_havg;
     for (auto &n : stat_names) stat_havg.emplace_back(n + "_time_average", n != "precl");
     std::string stats_steps;
+    // --diag: the fields looked at, and the file
+    std::vector<std::string> diag_names = {"density_dry", "uvel", "vvel", "wvel", "temp"};
+    for (auto &n : coupler.get_tracer_names()) diag_names.push_back(n);
+    std::ofstream diag_out;
+    if (!mods.diag.empty()) {
+      diag_out.open(mods.diag);
+      if (!diag_out) endrun("cannot open the --diag file");
+    }
     double etime_gcm = 0, maxw_all = 0, cons_max_rel = 0;
     int num_out = 0, crm_steps = 0;
     long substeps = 0, cons_violations = 0;
@@ -473,6 +507,24 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
           std::snprintf(t, sizeof(t), "%s%.6g", maxw_series.empty() ? "" : ",", maxw);
           maxw_series += t;
           num_out++;
+          if (diag_out.is_open()) {
+            std::vector<pam::diagnostics::Item> items;
+            for (auto &n : diag_names) items.push_back({n, 0, dm.get<real const, 4>(n).data(), (long long)ncell, items.size()});
+            auto whole = pam::diagnostics::scan(items, 0), members = pam::diagnostics::scan(items, nens);
+            std::string o = "{\"crm_step\": " + std::to_string(crm_steps) + ", \"etime\": ";
+            stats_json_number(o, etime_gcm);
+            o += ", \"nens\": " + std::to_string(nens) + ", \"fields\": {";
+            for (size_t f = 0; f < items.size(); f++) {
+              o += (f ? ", \"" : "\"") + diag_names[f] + "\": {\"whole\": ";
+              diag_json(o, whole[f]);
+              o += ", \"members\": ";
+              diag_json(o, members[f]);
+              o += "}";
+            }
+            o += "}}\n";
+            diag_out << o << std::flush;
+            if (!diag_out) endrun("cannot write the --diag file");
+          }
         }
         if (steps_limit > 0 && crm_steps >= steps_limit) stop = true;
       }
@@ -609,6 +661,7 @@ int main(int argc, char **argv) {
         mods.bflx = std::atof(argv[++b]);
       }
       else if (o == "--validate") mods.validate = true;
+      else if (o == "--diag" && b + 1 < argc - 1) mods.diag = argv[++b];
       else if (o == "--stats" && b + 1 < argc - 1) mods.stats = argv[++b];
       else if (o == "--edges" && b + 1 < argc - 1) mods.edges = argv[++b];
       else if (o == "--radiation" && b + 3 < argc - 1) {
@@ -618,7 +671,7 @@ int main(int argc, char **argv) {
         mods.rad_path = argv[++b];
       }
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
-               "[--validate] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] <output.bin | ->");
+               "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] <output.bin | ->");
     }
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }

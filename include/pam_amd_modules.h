@@ -219,6 +219,36 @@ int pam_amd_compute_pressure(int nens, int nx, int ny, int nz, const double *rho
 int pam_amd_validate_fields(int num_fields, const int *kind, const long long *size, const void *const *data,
                             const int *positive, long long *count, long long *first, void *stream);
 
+/* Field diagnostics: what the state LOOKS like, as one read of the data on the device -- the counterpart of the reference's
+ * DEBUG_PRINT_SUM / AVG / MIN / MAX(var) (pam_core/pam_const.h:308-333; yakl::intrinsics::sum / minval / maxval).  Takes a LIST of
+ * fields like the validation above (32 per launch, a longer list split, the results independent of the split):
+ *   kind       per field: 0 double, 1 float; anything else is refused
+ *   size       per field, >= 1 and a multiple of max(members, 1): number of elements
+ *   data       DEVICE arrays, each aligned to its element size (a view offset by some elements is fine); never written
+ *   members    0: one result per field.  M >= 1: one result per ensemble member m of x[r*M + m], the member the fastest axis
+ *   vmin, vmax, vsum, argmin, argmax, nan_count
+ *              HOST arrays of num_fields * max(members, 1), [f*M + m]:
+ *     vmin, argmin   the least element that is not a NaN (infinities take part) and its flat index into the field (64-bit, in the
+ *                    per-member case too).  Among elements that compare equal the lowest index wins; the value is that element's
+ *                    own bits (a float converted exactly), so -0.0 and +0.0 are told apart by index
+ *     vmax, argmax   the same for the greatest element
+ *     nan_count      number of NaNs.  Where every element is a NaN: vmin = +inf, vmax = -inf, both indices -1
+ *     vsum           the IEEE double sum of all elements (floats converted exactly) BY A FIXED TREE, so the same bits from run to
+ *                    run, on every device, for every split of the list and, per member, however the ensemble is cut into member
+ *                    chunks.  A NaN or inf - inf propagates.  fold(v; W, K): v is cut into chunks of W*K consecutive entries; entry
+ *                    e of a chunk belongs to lane e % W, step e / W; a lane adds its K entries in ascending step order; the lanes
+ *                    fold by `for d = W/2 .. 1: lane[l] += lane[l + d]`; the chunk results are the next v, until one value is left
+ *                    (missing entries count as -0.0).  Whole field: W = 256, K = 8 over the flat index.  Per member: W = 4, K = 64
+ *                    over the row index r, separately for each m.  tests/diagnostics_ref.py restates it in numpy.
+ *              The host derives max|x| = max(-vmin, vmax) and mean = vsum / n.
+ * Every argument is checked before the first HIP call; then every field must live on the CURRENT device, to which `stream` belongs
+ * (EINVAL otherwise).  Two launches per 32 fields on `stream` -- the first stores the level-1 chunk sums and the workgroups' extremes,
+ * the second folds them; no floating-point atomics -- then ONE synchronisation to bring back 48 bytes per result.  The scratch (about
+ * 0.05 % of the data for whole fields, 1 to 2 % per member) is kept per device, grown on demand and freed by pam_amd_modules_finalize(). */
+int pam_amd_field_diagnostics(int num_fields, const int *kind, const long long *size, const void *const *data, int members,
+                              double *vmin, double *vmax, double *vsum, long long *argmin, long long *argmax,
+                              long long *nan_count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,8 @@ MODULE_SYMBOLS = {
     "pam_amd_compute_pressure": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "pam_amd_validate_fields": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_void_p), C.POINTER(C.c_int),
                                           C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
+    "pam_amd_field_diagnostics": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_void_p), C.c_int] +
+                                  [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_longlong)] * 3 + [C.c_void_p]),
 }
 
 

@@ -153,6 +153,28 @@ class DataManager:
             endrun(f"ERROR: Could not find entry {name}")
         self._validate([name], die_on_failed_check)
 
+    # ---- what the state looks like (the reference's DEBUG_PRINT_SUM / AVG / MIN / MAX, pam_const.h:308-333, for every entry at once)
+    def _diagnose(self, names, members):
+        from . import modules
+        out = modules.field_diagnostics([self._e[n]["data"] for n in names], members)
+        return {n: {k: v[f] for k, v in out.items()} for f, n in enumerate(names)}
+
+    def diagnose_all(self, members=0):
+        """One device scan (modules.field_diagnostics) over every float64 and float32 entry, in registration order; prints nothing.
+        Returns {name: {"vmin", "vmax", "vsum", "argmin", "argmax", "nan_count"}}: numpy scalars for members = 0, arrays of (members,)
+        for members = M >= 1 (the ensemble member is the fastest axis).  Entries of another dtype, empty entries and -- with members --
+        entries whose size is no multiple of it are skipped."""
+        from . import modules
+        names = [n for n, e in self._e.items() if e["data"].dtype in modules.DIAGNOSTIC_KINDS and e["data"].numel() > 0
+                 and e["data"].numel() % max(int(members), 1) == 0]
+        return self._diagnose(names, members)
+
+    def diagnose(self, name, members=0):
+        """diagnose_all's result for one entry, which must be float64 or float32"""
+        if name not in self._e:
+            endrun(f"ERROR: Could not find entry {name}")
+        return self._diagnose([name], members)[name]
+
     def clean_all_entries(self):
         for e in self._e.values():
             e["dirty"] = False

@@ -8,6 +8,8 @@
 //   pam::PamCoupler    pam_core/pam_coupler.h:59-293   grid getters, options facade, tracer registry, run_module
 //   endrun             pam_core/pam_const.h:249-252    print to stderr and throw
 //   DataManager::validate / validate_all   pam_core/DataManager.h:408-509   the state check, as one device scan (data_validation_*.h)
+//   DataManager::diagnose / diagnose_all, DEBUG_PRINT_SUM / AVG / MIN / MAX   pam_core/pam_const.h:308-333   min, max, their indices, the
+//                      NaN count and a reproducible sum per entry or per ensemble member, as one device scan (data_diagnostics.h)
 //
 // OWNERSHIP of compute_pressure_array().  The reference returns a freshly allocated, reference-counted real4d.  The arrays here are
 // non-owning views, so THE COUPLER owns the storage of the returned pressure: it is allocated on the first call, reused by every
@@ -66,6 +68,8 @@ typedef pam::DeviceView<int const> intConst1d;
 #include "data_validation_helpers.h"   // the helpers of DataManager::validate (pam::validation)
 
 namespace pam {
+
+namespace diagnostics { struct FieldDiagnostics; }   // data_diagnostics.h
 
 class Options {
   std::map<std::string, std::variant<int, real, bool, std::string>> opts;
@@ -180,6 +184,13 @@ class DataManager {
   void validate_nan(std::string name, bool die_on_failed_check = false) const;
   void validate_inf(std::string name, bool die_on_failed_check = false) const;
   void validate_pos(std::string name, bool die_on_failed_check = false) const;
+
+  // What the state looks like (the companion of validate; not in the reference, whose DEBUG_PRINT_* macros look at one array each):
+  // per double or float entry -- members = 0 -- or per ensemble member of it -- members = nens, the fastest axis -- the least and the
+  // greatest element with their flat indices, the number of NaNs and a sum that is the same bits from run to run.  ONE device scan and
+  // one synchronisation per call; prints nothing.  Defined in data_diagnostics.h (included after the coupler below).
+  std::vector<diagnostics::FieldDiagnostics> diagnose_all(int members = 0) const;
+  diagnostics::FieldDiagnostics diagnose(std::string name, int members = 0) const;
 
   int get_dimension_size(std::string name) const {
     auto it = dimensions.find(name);
@@ -341,3 +352,4 @@ class PamCoupler {
 }  // namespace pam
 
 #include "data_validation_members.h"   // the definitions of DataManager::validate_all, validate, validate_nan/inf/pos
+#include "data_diagnostics.h"          // DataManager::diagnose_all, diagnose; DEBUG_PRINT_SUM / AVG / MIN / MAX

@@ -22,6 +22,7 @@
 #include "plugins_device.h"          // forced radiation, the coupler's pressure array: the same
 #include "kessler_device.h"          // Kessler microphysics: the per-column bodies, the same
 #include "validate_device.h"         // DataManager::validate: classification, a thread's walk and the fold, the same
+#include "diagnostics_device.h"      // field diagnostics: the per-element update, a thread's share of a chunk and the folds, the same
 
 namespace {
 
@@ -484,10 +485,12 @@ int kessler_read_dt_max(const double *slot, hipStream_t s, double *out) {
 }
 
 void validate_scratch_free();   // the result scratch of pam_amd_validate_fields, defined with it below
+void diagnostics_scratch_free();   // the scratch of pam_amd_field_diagnostics, the same
 }  // namespace
 
 extern "C" int pam_amd_modules_finalize(void) {
   validate_scratch_free();
+  diagnostics_scratch_free();
   std::lock_guard<std::mutex> lk(g_tab_mutex);
   int cur = -1;
   (void)hipGetDevice(&cur);
@@ -1257,6 +1260,324 @@ extern "C" int pam_amd_validate_fields(int num_fields, const int *kind, const lo
   for (size_t i = 0; i < n3; i++) {
     count[i] = (long long)host[i];
     first[i] = (long long)host[n3 + i];      // ~0 (nothing found) is -1
+  }
+  return PAM_AMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Field diagnostics (the reference's DEBUG_PRINT_SUM / AVG / MIN / MAX, pam_core/pam_const.h:308-333, as one read of the data): per
+// field, or per ensemble member of a field, the least and the greatest element with their flat indices, the number of NaNs, and a sum
+// whose tree is fixed (diagnostics_device.h), so that it is the same bits from run to run, for every grid and every split of the list.
+// No floating-point atomics and no "last workgroup" scheme: the first launch stores the level-1 chunk sums and its wavefronts' (or
+// workgroups') extremes in a per-device scratch, the second launch -- one workgroup per field, or per (field, tile of 64 members) --
+// folds the remaining levels and the extremes and writes one Result.  The bodies live in diagnostics_device.h; what is here is the
+// wavefront shuffles, the LDS hand-off and the launch code.
+namespace {
+namespace dg = pama::diagnostics;
+
+struct DiagTable {
+  const void *data[STATS_TABLE];
+  long long size[STATS_TABLE];
+  long long n1[STATS_TABLE];         // level-1 chunk results (per member)
+  long long sums_off[STATS_TABLE];   // byte offsets into the scratch
+  long long ext_off[STATS_TABLE];
+  int kind[STATS_TABLE];
+};
+
+__device__ __forceinline__ double diag_shfl_down(double v, int off) { return __shfl_down(v, off, dg::WAVE); }
+
+// lanes 4t .. 4t+3 of thread t folded over the wavefront: the steps d = 128 .. 4 of the lane fold, then d = 2, 1 (valid in lane 0)
+__device__ __forceinline__ double diag_wave_fold(double acc[dg::FIELD_OWN]) {
+#pragma unroll
+  for (int off = dg::WAVE / 2; off > 0; off >>= 1) {
+#pragma unroll
+    for (int j = 0; j < dg::FIELD_OWN; j++) acc[j] += diag_shfl_down(acc[j], off);
+  }
+  return dg::fold4(acc[0], acc[1], acc[2], acc[3]);
+}
+
+__device__ __forceinline__ void diag_wave_merge(dg::Extreme &e) {
+#pragma unroll
+  for (int off = dg::WAVE / 2; off > 0; off >>= 1) {
+    dg::Extreme o;
+    o.vmin = __shfl_down(e.vmin, off, dg::WAVE);
+    o.vmax = __shfl_down(e.vmax, off, dg::WAVE);
+    o.imin = __shfl_down(e.imin, off, dg::WAVE);
+    o.imax = __shfl_down(e.imax, off, dg::WAVE);
+    o.nans = __shfl_down(e.nans, off, dg::WAVE);
+    dg::extreme_merge(e, o);
+  }
+}
+
+// whole field, first launch: wavefront gw of the field's gridDim.x * 4 takes the chunks gw, gw + nwaves, ...
+template <class T>
+__device__ __forceinline__ void diag_field_scan(const T *p, long long n, long long gw, long long nwaves, int ln, double *s1, dg::Extreme *ext) {
+  dg::Running<T> r;
+  dg::running_clear(r);
+  const long long nchunks = dg::ceil_div(n, dg::FIELD_CHUNK);
+  int pass = 0;
+  for (long long c = gw; c < nchunks; c += nwaves, pass++) {
+    double acc[dg::FIELD_OWN];
+    dg::field_chunk_thread<T, true>(p, n, c, ln, pass, acc, r);
+    const double sum = diag_wave_fold(acc);
+    if (ln == 0) s1[c] = sum;
+  }
+  dg::Extreme e;
+  dg::field_finish(r, gw, nwaves, ln, e);
+  diag_wave_merge(e);
+  if (ln == 0) dg::extreme_copy(ext[gw], e);
+}
+
+__global__ void __launch_bounds__(dg::THREADS) diag_field_kernel(DiagTable T, char *__restrict__ scratch) {
+  const int f = (int)blockIdx.y;
+  const int tid = (int)threadIdx.x;
+  const long long gw = (long long)blockIdx.x * dg::WAVES + (tid >> 6), nwaves = (long long)gridDim.x * dg::WAVES;
+  double *s1 = (double *)(scratch + T.sums_off[f]);
+  dg::Extreme *ext = (dg::Extreme *)(scratch + T.ext_off[f]);
+  if (T.kind[f] == dg::KIND_DOUBLE) diag_field_scan((const double *)T.data[f], T.size[f], gw, nwaves, tid & 63, s1, ext);
+  else diag_field_scan((const float *)T.data[f], T.size[f], gw, nwaves, tid & 63, s1, ext);
+}
+
+// whole field, second launch: one workgroup per field folds the levels 2, 3, ... (its four wavefronts take the chunks of a level in
+// turn) and the `next` extremes of the first launch
+__global__ void __launch_bounds__(dg::THREADS) diag_field_finish_kernel(DiagTable T, char *__restrict__ scratch, long long next,
+                                                                        dg::Result *__restrict__ result) {
+  const int f = (int)blockIdx.x;
+  const int tid = (int)threadIdx.x, wave = tid >> 6, ln = tid & 63;
+  double *sums = (double *)(scratch + T.sums_off[f]);
+  long long cnt = T.n1[f];
+  while (cnt > 1) {
+    const long long more = dg::ceil_div(cnt, dg::FIELD_CHUNK);
+    dg::Running<double> unused;
+    for (long long c = wave; c < more; c += dg::WAVES) {
+      double acc[dg::FIELD_OWN];
+      dg::field_chunk_thread<double, false>(sums, cnt, c, ln, 0, acc, unused);
+      const double sum = diag_wave_fold(acc);
+      if (ln == 0) sums[cnt + c] = sum;
+    }
+    __threadfence();
+    __syncthreads();
+    sums += cnt;
+    cnt = more;
+  }
+  const dg::Extreme *ext = (const dg::Extreme *)(scratch + T.ext_off[f]);
+  dg::Extreme e;
+  dg::extreme_clear(e);
+  for (long long w = tid; w < next; w += dg::THREADS) dg::extreme_merge(e, ext[w]);
+  diag_wave_merge(e);
+  __shared__ dg::Extreme waves[dg::WAVES];
+  if (ln == 0) dg::extreme_copy(waves[wave], e);
+  __syncthreads();
+  if (tid != 0) return;
+  for (int w = 1; w < dg::WAVES; w++) dg::extreme_merge(e, waves[w]);
+  result[f] = dg::Result{e.vmin, e.vmax, sums[0], e.imin, e.imax, e.nans};
+}
+
+// per member, first launch: workgroup (group of four row chunks, tile of 64 members, field); wavefront p holds lane p of the tree.
+// A thread's extremes run over the four chunks; each chunk's four lanes go through LDS, and wavefront k folds those of chunk k.
+template <class T>
+__device__ __forceinline__ void diag_member_scan(const T *p, long long rows, long long M, long long chunk0, long long nchunks, long long m,
+                                                 int phase, int ml, double (*lane)[dg::MEMBER_W][dg::MEMBER_TILE], dg::Extreme &e) {
+  dg::Running<T> r;
+  dg::running_clear(r);
+  for (int k = 0; k < dg::MEMBER_GROUP && chunk0 + k < nchunks; k++) {
+    double acc;
+    dg::member_chunk_thread<T, true>(p, rows, M, chunk0 + k, m, phase, k * dg::MEMBER_K, acc, r);
+    lane[k][phase][ml] = acc;
+  }
+  dg::member_finish(r, M, chunk0, m, phase, e);
+}
+
+__global__ void __launch_bounds__(dg::THREADS) diag_member_kernel(DiagTable T, char *__restrict__ scratch, long long M) {
+  const int f = (int)blockIdx.z;
+  const long long group = (long long)blockIdx.x, chunk0 = group * dg::MEMBER_GROUP, nchunks = T.n1[f];
+  if (chunk0 >= nchunks) return;
+  const int tid = (int)threadIdx.x, phase = tid >> 6, ml = tid & 63;
+  const long long m = (long long)blockIdx.y * dg::MEMBER_TILE + ml, rows = T.size[f] / M;
+  const bool active = m < M;
+  __shared__ double lane[dg::MEMBER_GROUP][dg::MEMBER_W][dg::MEMBER_TILE];
+  __shared__ dg::Extreme found[dg::MEMBER_W][dg::MEMBER_TILE];
+  dg::Extreme e;
+  dg::extreme_clear(e);
+  if (active) {
+    if (T.kind[f] == dg::KIND_DOUBLE) diag_member_scan((const double *)T.data[f], rows, M, chunk0, nchunks, m, phase, ml, lane, e);
+    else diag_member_scan((const float *)T.data[f], rows, M, chunk0, nchunks, m, phase, ml, lane, e);
+  }
+  dg::extreme_copy(found[phase][ml], e);
+  __syncthreads();
+  if (!active) return;
+  if (chunk0 + phase < nchunks)
+    ((double *)(scratch + T.sums_off[f]))[(chunk0 + phase) * M + m] = dg::fold4(lane[phase][0][ml], lane[phase][1][ml], lane[phase][2][ml], lane[phase][3][ml]);
+  if (phase != 0) return;
+  for (int w = 1; w < dg::MEMBER_W; w++) dg::extreme_merge(e, found[w][ml]);
+  dg::extreme_copy(((dg::Extreme *)(scratch + T.ext_off[f]))[group * M + m], e);
+}
+
+// per member, second launch: one workgroup per (tile of 64 members, field) folds the levels 2, 3, ... -- a level is rows x M like the
+// field -- and the extremes of the groups of row chunks
+__global__ void __launch_bounds__(dg::THREADS) diag_member_finish_kernel(DiagTable T, char *__restrict__ scratch, long long M,
+                                                                         dg::Result *__restrict__ result) {
+  const int f = (int)blockIdx.y;
+  const int tid = (int)threadIdx.x, phase = tid >> 6, ml = tid & 63;
+  const long long m = (long long)blockIdx.x * dg::MEMBER_TILE + ml;
+  const bool active = m < M;
+  __shared__ double lane[dg::MEMBER_W][dg::MEMBER_TILE];
+  __shared__ dg::Extreme found[dg::MEMBER_W][dg::MEMBER_TILE];
+  double *sums = (double *)(scratch + T.sums_off[f]);
+  long long cnt = T.n1[f];
+  while (cnt > 1) {
+    const long long more = dg::ceil_div(cnt, dg::MEMBER_CHUNK);
+    dg::Running<double> unused;
+    for (long long c = 0; c < more; c++) {
+      double acc = -0.0;
+      if (active) dg::member_chunk_thread<double, false>(sums, cnt, M, c, m, phase, 0, acc, unused);
+      lane[phase][ml] = acc;
+      __syncthreads();
+      if (phase == 0 && active) sums[(cnt + c) * M + m] = dg::fold4(lane[0][ml], lane[1][ml], lane[2][ml], lane[3][ml]);
+      __syncthreads();
+    }
+    __threadfence();
+    __syncthreads();
+    sums += cnt * M;
+    cnt = more;
+  }
+  const dg::Extreme *ext = (const dg::Extreme *)(scratch + T.ext_off[f]);
+  dg::Extreme e;
+  dg::extreme_clear(e);
+  if (active) {
+#pragma unroll 4
+    for (long long g = phase; g < dg::ceil_div(T.n1[f], dg::MEMBER_GROUP); g += dg::MEMBER_W) dg::extreme_merge(e, ext[g * M + m]);
+  }
+  dg::extreme_copy(found[phase][ml], e);
+  __syncthreads();
+  if (phase != 0 || !active) return;
+  for (int w = 1; w < dg::MEMBER_W; w++) dg::extreme_merge(e, found[w][ml]);
+  result[(long long)f * M + m] = dg::Result{e.vmin, e.vmax, sums[m], e.imin, e.imax, e.nans};
+}
+
+// the scratch: per device, grown on demand, freed by pam_amd_modules_finalize().  A device's mutex is held for a whole call on that
+// device (which ends in a synchronisation anyway), as for the validation scratch.
+constexpr int DIAG_MAX_DEVICES = 64;
+struct DiagScratch { std::mutex m; char *p = nullptr; long long bytes = 0; };
+DiagScratch g_diag_scratch[DIAG_MAX_DEVICES];
+
+char *diagnostics_scratch(DiagScratch &s, long long bytes) {
+  if (s.bytes < bytes) {
+    long long want = 1 << 16;
+    while (want < bytes) want *= 2;
+    if (s.p) (void)hipFree(s.p);
+    s.p = nullptr;
+    s.bytes = 0;
+    if (hipMalloc((void **)&s.p, (size_t)want) != hipSuccess) { (void)hipGetLastError(); s.p = nullptr; return nullptr; }
+    s.bytes = want;
+  }
+  return s.p;
+}
+
+void diagnostics_scratch_free() {
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  for (int d = 0; d < DIAG_MAX_DEVICES; d++) {
+    DiagScratch &s = g_diag_scratch[d];
+    std::lock_guard<std::mutex> lk(s.m);
+    if (s.p) {
+      if (d != cur) (void)hipSetDevice(d);
+      (void)hipFree(s.p);
+      s.p = nullptr;
+      s.bytes = 0;
+      if (d != cur && cur >= 0) (void)hipSetDevice(cur);
+    }
+  }
+}
+}  // namespace
+
+extern "C" int pam_amd_field_diagnostics(int num_fields, const int *kind, const long long *size, const void *const *data, int members,
+                                         double *vmin, double *vmax, double *vsum, long long *argmin, long long *argmax,
+                                         long long *nan_count, void *stream) {
+  if (num_fields < 1 || !kind || !size || !data)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "field_diagnostics: bad num_fields or null table");
+  if (!vmin || !vmax || !vsum || !argmin || !argmax || !nan_count)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "field_diagnostics: null result array");
+  if (members < 0 || members > dg::MEMBER_TILE * 65535)
+    return pam_amd_set_last_error_(PAM_AMD_EINVAL, "field_diagnostics: members must be 0 (whole field) or 1 .. 4194240");
+  const long long M = std::max(members, 1);
+  for (int f = 0; f < num_fields; f++) {
+    if (kind[f] != dg::KIND_DOUBLE && kind[f] != dg::KIND_FLOAT)
+      return pam_amd_set_last_error_(PAM_AMD_EINVAL, "field_diagnostics: kind must be 0 (double) or 1 (float)");
+    if (size[f] < 1) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "field_diagnostics: every size must be >= 1");
+    if (size[f] % M != 0) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "field_diagnostics: every size must be a multiple of members");
+    if (members > 0 && dg::ceil_div(size[f] / M, dg::MEMBER_CHUNK * dg::MEMBER_GROUP) > 0x7fffffffLL / dg::THREADS * 2)
+      return pam_amd_set_last_error_(PAM_AMD_EINVAL, "field_diagnostics: more than 2^34 rows per member");
+    if (!data[f]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "field_diagnostics: null field pointer");
+    if ((unsigned long long)(uintptr_t)data[f] % (kind[f] == dg::KIND_DOUBLE ? 8u : 4u) != 0)
+      return pam_amd_set_last_error_(PAM_AMD_EINVAL, "field_diagnostics: field pointer not aligned to its element size");
+  }
+  if (int rc = moist_surface_device_check("field_diagnostics")) return rc;
+  int cur = -1;
+  if (hipGetDevice(&cur) != hipSuccess || cur < 0 || cur >= DIAG_MAX_DEVICES)
+    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "field_diagnostics: no current HIP device");
+  for (int f = 0; f < num_fields; f++) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, data[f]) != hipSuccess) { (void)hipGetLastError(); continue; }
+    if (attr.type == hipMemoryTypeDevice && attr.device != cur)
+      return pam_amd_set_last_error_(PAM_AMD_EINVAL, "field_diagnostics: every field must live on the current device (hipSetDevice to the fields' device first)");
+  }
+  // the plan of the whole call: per launch table its grid, per field its regions of the scratch, then the results
+  const int ngroups = (num_fields + STATS_TABLE - 1) / STATS_TABLE;
+  std::vector<dg::FieldPlan> plan(num_fields);
+  std::vector<long long> grid(ngroups);
+  long long bytes = 0;
+  for (int g = 0; g < ngroups; g++) {
+    const int f0 = g * STATS_TABLE, nf = std::min(STATS_TABLE, num_fields - f0);
+    long long nmax = 1;
+    for (int l = 0; l < nf; l++) nmax = std::max(nmax, size[f0 + l]);
+    grid[g] = dg::field_grid(nmax, nf);
+    for (int l = 0; l < nf; l++) bytes = dg::plan_field(size[f0 + l], members, grid[g] * dg::WAVES, bytes, plan[f0 + l]);
+  }
+  const long long result_off = bytes;
+  const size_t nres = (size_t)num_fields * (size_t)M;
+  bytes += (long long)(nres * sizeof(dg::Result));
+  DiagScratch &scratch = g_diag_scratch[cur];
+  std::lock_guard<std::mutex> lk(scratch.m);
+  char *base = diagnostics_scratch(scratch, bytes);
+  if (!base) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "field_diagnostics: device allocation of the scratch failed");
+  dg::Result *d_result = (dg::Result *)(base + result_off);
+  hipStream_t s = (hipStream_t)stream;
+  for (int g = 0; g < ngroups; g++) {
+    const int f0 = g * STATS_TABLE, nf = std::min(STATS_TABLE, num_fields - f0);
+    DiagTable T;
+    long long chunks = 1;
+    for (int l = 0; l < STATS_TABLE; l++) {
+      const bool in = l < nf;
+      T.data[l] = in ? data[f0 + l] : nullptr;
+      T.size[l] = in ? size[f0 + l] : 0;
+      T.kind[l] = in ? kind[f0 + l] : 0;
+      T.n1[l] = in ? plan[f0 + l].n1 : 0;
+      T.sums_off[l] = in ? plan[f0 + l].sums_off : 0;
+      T.ext_off[l] = in ? plan[f0 + l].ext_off : 0;
+      chunks = std::max(chunks, T.n1[l]);
+    }
+    if (members < 1) {
+      hipLaunchKernelGGL(diag_field_kernel, dim3((unsigned)grid[g], (unsigned)nf), dim3(dg::THREADS), 0, s, T, base);
+      hipLaunchKernelGGL(diag_field_finish_kernel, dim3((unsigned)nf), dim3(dg::THREADS), 0, s, T, base, grid[g] * dg::WAVES, d_result + f0);
+    } else {
+      const unsigned tiles = (unsigned)dg::ceil_div(M, dg::MEMBER_TILE);
+      hipLaunchKernelGGL(diag_member_kernel, dim3((unsigned)dg::ceil_div(chunks, dg::MEMBER_GROUP), tiles, (unsigned)nf), dim3(dg::THREADS), 0, s, T, base, M);
+      hipLaunchKernelGGL(diag_member_finish_kernel, dim3(tiles, (unsigned)nf), dim3(dg::THREADS), 0, s, T, base, M, d_result + (size_t)f0 * M);
+    }
+    if (int rc = stats_launch_check("field_diagnostics")) return rc;
+  }
+  std::vector<dg::Result> host(nres);
+  if (hipMemcpyAsync(host.data(), d_result, nres * sizeof(dg::Result), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string("field_diagnostics: ") + hipGetErrorString(hipGetLastError())).c_str());
+  for (size_t i = 0; i < nres; i++) {
+    vmin[i] = host[i].vmin;
+    vmax[i] = host[i].vmax;
+    vsum[i] = host[i].vsum;
+    argmin[i] = host[i].imin == dg::NOT_FOUND ? -1 : host[i].imin;
+    argmax[i] = host[i].imax == dg::NOT_FOUND ? -1 : host[i].imax;
+    nan_count[i] = host[i].nans;
   }
   return PAM_AMD_OK;
 }

@@ -362,3 +362,50 @@ def validate_fields(tensors, positive):
                                                   first.ctypes.data_as(C.POINTER(C.c_longlong)),
                                                   torch.cuda.current_stream(device).cuda_stream))
     return count, first
+
+
+DIAGNOSTIC_KINDS = {torch.float64: 0, torch.float32: 1}
+
+
+def field_diagnostics(tensors, members=0):
+    """What the fields look like, as one device scan (pam_amd_field_diagnostics; the reference's DEBUG_PRINT_SUM / AVG / MIN / MAX,
+    pam_core/pam_const.h:308-333): `tensors` is a list of contiguous float64 or float32 tensors on one device (a view offset by some
+    elements is fine).  members = 0: one result per tensor; members = M >= 1: one per ensemble member, the member being the fastest
+    axis (numel % M == 0).  Returns a dict of numpy arrays of shape (len(tensors),) or (len(tensors), M): "vmin", "vmax" (float64, the
+    extreme element's own bits; NaNs take no part, +inf / -inf where every element is one), "argmin", "argmax" (int64 flat indices into
+    the tensor, the lowest among equal values, -1 where every element is a NaN), "nan_count" (int64) and "vsum" (float64, the sum by
+    the fixed tree of include/pam_amd_modules.h: the same bits from run to run and under member chunking).  max|x| is
+    max(-vmin, vmax), the mean vsum / n.  Reads only; launched on the current stream, which is synchronised once."""
+    import numpy as np
+    from .coupler import endrun
+    tensors, members = list(tensors), int(members)
+    if members < 0:
+        endrun("ERROR: field_diagnostics: members must be >= 0")
+    shape = (len(tensors),) if members == 0 else (len(tensors), members)
+    out = {k: np.zeros(shape, dtype=np.float64) for k in ("vmin", "vmax", "vsum")}
+    out.update({k: np.zeros(shape, dtype=np.int64) for k in ("argmin", "argmax", "nan_count")})
+    if not tensors:
+        return out
+    for t in tensors:
+        if t.dtype not in DIAGNOSTIC_KINDS:
+            endrun("ERROR: field_diagnostics: dtype %s is not float64 or float32" % t.dtype)
+        if not t.is_contiguous():
+            endrun("ERROR: field_diagnostics: contiguous tensors only")
+        if t.numel() < 1:
+            endrun("ERROR: field_diagnostics: empty tensor")
+        if t.numel() % max(members, 1):
+            endrun("ERROR: field_diagnostics: the number of elements must be a multiple of members")
+        if t.device != tensors[0].device:
+            endrun("ERROR: field_diagnostics: the tensors must live on one device")
+    n = len(tensors)
+    kinds = (C.c_int * n)(*[DIAGNOSTIC_KINDS[t.dtype] for t in tensors])
+    sizes = (C.c_longlong * n)(*[t.numel() for t in tensors])
+    device = tensors[0].device
+    dp, lp = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
+    with torch.cuda.device(device):
+        check(capi.load().pam_amd_field_diagnostics(n, kinds, sizes, _ptr_table(tensors), members,
+                                                    out["vmin"].ctypes.data_as(dp), out["vmax"].ctypes.data_as(dp),
+                                                    out["vsum"].ctypes.data_as(dp), out["argmin"].ctypes.data_as(lp),
+                                                    out["argmax"].ctypes.data_as(lp), out["nan_count"].ctypes.data_as(lp),
+                                                    torch.cuda.current_stream(device).cuda_stream))
+    return out

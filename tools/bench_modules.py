@@ -4,7 +4,8 @@ then pam::VerticalInterp's cells_to_edges (order 5 with per-member tables and wi
 then the forced radiation plug-in at three rad grids and the coupler's pressure array, with time_average_accumulate and a device
 copy timed beside them as yardsticks, three repetitions: one JSON object on stdout.
 Run on the GPU box:  python tools/bench_modules.py            (--only vertical_interp, --only plugins: those rows alone;
---only validate: DataManager.validate_all's device scan with the two statistics rows of the same run beside it)"""
+--only validate: DataManager.validate_all's device scan with the two statistics rows of the same run beside it;
+--only diagnostics: pam_amd.field_diagnostics whole-field and per-member, with the validation and time_average_accumulate rows)"""
 import json
 import os
 import sys
@@ -254,6 +255,52 @@ def validate_timing(dev):
     return out
 
 
+def diagnostics_timing(dev):
+    """pam_amd.field_diagnostics at the C2 grid on the clean Kessler field set of statistics_timing (4 GB): the whole-field call and the
+    per-member call (members = nens = 1024), 3 warm-up calls and the median of 11 event-timed calls each.  Beside them, timed in the
+    same run and the same way, the yardsticks: the validation scan of the same fields (the same bytes read, integer work only) and
+    time_average_accumulate.  A diagnostics or validation call includes its one synchronisation and the bytes it brings back."""
+    from pam_amd import PamCoupler, Microphysics, modules
+    from pam_amd import idealized as idz
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    c = PamCoupler(dev)
+    c.set_option("crm_dt", 2.0)
+    c.set_option("gcm_physics_dt", 900.0)
+    c.allocate_coupler_state(nz, ny, nx, nens)
+    c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+    micro = Microphysics()
+    micro.init(c)
+    dm = c.get_data_manager_device_readwrite()
+    names = ["density_dry", "uvel", "vvel", "wvel", "temp"] + c.get_tracer_names() + ["precl"]
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for n in names:
+        t = dm.get(n)
+        t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev))
+    tens = [dm.get(n, readonly=True) for n in names]
+    elems = sum(t.numel() for t in tens)
+    modules.time_average_init(c, names)
+
+    def row(fn, nbytes):
+        fn()
+        fn()                                # with _events' own: 3 warm-up calls
+        t = _events(fn, n=11)
+        return {"ms": t, "bytes": nbytes, "GBps": nbytes / t / 1e6, "hbm_frac": nbytes / t / 1e6 / bench.HBM_PEAK_GBS, "fields": len(names)}
+
+    out = {"diagnostics_grid": "1024 x 32x32x60 (C2)", "diagnostics_method": "3 warm-up calls, median of 11 event-timed calls"}
+    whole = modules.field_diagnostics(tens)
+    per = modules.field_diagnostics(tens, members=nens)
+    assert not whole["nan_count"].any() and (per["vmin"].min(axis=1) == whole["vmin"]).all()
+    out["diagnostics_whole_field"] = row(lambda: modules.field_diagnostics(tens), elems * 8.0)
+    out["diagnostics_per_member"] = row(lambda: modules.field_diagnostics(tens, members=nens), elems * 8.0)
+    out["validate_clean"] = row(lambda: modules.validate_fields(tens, [True] * len(tens)), elems * 8.0)
+    out["time_average_accumulate"] = row(lambda: modules.time_average_accumulate(c, names), elems * 24.0)
+    for k in ("diagnostics_whole_field", "diagnostics_per_member"):
+        out[k]["of_validate"] = out[k]["hbm_frac"] / out["validate_clean"]["hbm_frac"]
+    del micro, dm, c, tens
+    torch.cuda.empty_cache()
+    return out
+
+
 COPY_GBS = 6300.0      # what a device-to-device copy reaches on this part (the measured copy of the same run is reported beside it)
 
 
@@ -332,6 +379,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:] == ["--only", "validate"]:
         print(json.dumps(validate_timing(dev)))
+        sys.exit(0)
+    if sys.argv[1:] == ["--only", "diagnostics"]:
+        print(json.dumps(diagnostics_timing(dev)))
         sys.exit(0)
     if sys.argv[1:] == ["--only", "vertical_interp"]:
         print(json.dumps(vertical_interp_timing(dev)))
