@@ -274,6 +274,9 @@ int pam_amd_awfl_set_tracer_grouping(pam_amd_awfl_t *h, int tracers_per_wavefron
  * grid flat over every cell (0/1 each) and the x tile
  * geometry {lanes per row, member blocks per line, cells per tile, halo rows per side, tiles per line, lines per workgroup} */
 int pam_amd_awfl_get_lane_mapping(const pam_amd_awfl_t *h, int *yz_flat, int *x_tiles, int *flat_cells, int geom[6]);
+/* the resolved number of member ranges (pam_amd_awfl_set_ensemble_chunks asks; flat lanes, tile kernels and a flat grid over every cell
+ * take the whole ensemble as one).  With one range the CFL minimum is published by the reduction itself, with more it is copied. */
+int pam_amd_awfl_get_ensemble_ranges(const pam_amd_awfl_t *h, int *ranges);
 
 /* --- test hooks: read-only views of resident device buffers, and a single tendency stage ------------------------- */
 /* name: "prim0","prim1","prim2","flux_x","flux_y","flux_z","seed","mult". */

@@ -1386,7 +1386,10 @@ PAMA_D double cfl_body(const Params &P, const double *__restrict__ rho_d_c, cons
   double dtx = cfl * P.dx / (fabs(u_c[idx]) + cs);
   double dty = cfl * P.dy / (fabs(v_c[idx]) + cs);
   double dtz = cfl * P.dz[ke] / (fabs(w_c[idx]) + cs);
-  return fmin(fmin(dtx, dty), dtz);
+  // a dry density, a total density or a temperature that is not positive is no state to take a time step from, yet two wrong signs
+  // cancel in p / rho (rho_d < -rho_v R_v / R_d, or rho_v < -rho_d: p and rho both negative), cs comes out real and the cell would pass
+  // for a healthy one.  With all three positive a negative p gives a NaN cs by itself.  NaN: the caller's reduction keeps it and reports 0
+  return (rho_d > 0.0 && rho > 0.0 && temp > 0.0) ? fmin(fmin(dtx, dty), dtz) : NAN;
 }
 
 // ------------------------------------------------------------------------------------------------

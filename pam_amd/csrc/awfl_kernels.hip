@@ -2829,6 +2829,12 @@ int pam_amd_awfl_get_lane_mapping(const pam_amd_awfl_t *h, int *yz_flat, int *x_
   return PAM_AMD_OK;
 }
 
+int pam_amd_awfl_get_ensemble_ranges(const pam_amd_awfl_t *h, int *ranges) {
+  if (!h || !ranges) return fail(PAM_AMD_EINVAL, "get_ensemble_ranges: null argument");
+  *ranges = (int)h->chunks.size();
+  return PAM_AMD_OK;
+}
+
 int pam_amd_awfl_set_debug_conservation(pam_amd_awfl_t *h, int enable) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
   USE_DEVICE(h);

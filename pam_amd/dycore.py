@@ -329,6 +329,12 @@ class Dycore:
                 "flat_cells": bool(cells.value),
                 "tile": dict(zip(("W", "nmb", "tc", "halo", "ntl", "lpb"), list(g)))}
 
+    def get_ensemble_ranges(self):
+        """the resolved number of member ranges (set_ensemble_chunks asks; some lane mappings take the whole ensemble as one)"""
+        n = C.c_int()
+        check(self._lib.pam_amd_awfl_get_ensemble_ranges(self._h, C.byref(n)))
+        return n.value
+
     def debug_buffer(self, name):
         ptr, n = C.c_void_p(), C.c_size_t()
         check(self._lib.pam_amd_awfl_debug_get_buffer(self._h, name.encode(), C.byref(ptr), C.byref(n)))

@@ -493,8 +493,10 @@ void emu_declare_hydrostatic(Emu *h, double *rho_d, double *u, double *v, double
 
 double emu_compute_time_step(Emu *h, double *rho_d, double *u, double *v, double *w, double *T, double *tracers, double cfl) {
   double m = INFINITY;
-  for (long long idx = 0; idx < h->P.ncell; idx++)
-    m = std::fmin(m, cfl_body(h->P, rho_d, u, v, w, T, tracers + (long long)h->P.idWV * h->P.ncell, cfl, idx));
+  for (long long idx = 0; idx < h->P.ncell; idx++) {
+    const double dtc = cfl_body(h->P, rho_d, u, v, w, T, tracers + (long long)h->P.idWV * h->P.ncell, cfl, idx);
+    m = (dtc != dtc || m != m) ? NAN : std::fmin(m, dtc);     // as awfl_cfl_kernel: fmin() drops a NaN operand, the reduction keeps it
+  }
   return m;
 }
 
