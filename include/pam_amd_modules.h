@@ -249,6 +249,81 @@ int pam_amd_field_diagnostics(int num_fields, const int *kind, const long long *
                               double *vmin, double *vmax, double *vsum, long long *argmin, long long *argmax,
                               long long *nan_count, void *stream);
 
+/* The SHOC coupling layer: what SGS::timeStep of the reference does around shoc_main  (physics/sgs/shoc/SGS.h:150-779), as two fused
+ * launches with SHOC behind a function pointer.  SHOC itself (SCREAM's code) is not part of this library.
+ *
+ * pam_amd_shoc_args_t: the arguments of pam::shoc_main_cxx (SGS.h:487-537), in that order and under those names, plus `exner`, which
+ * the unpack step needs (SGS.h:728).  Every pointer is a DEVICE array of the workspace below.  s = SHOC's level, 0 at the model top.
+ *   layout 0   the reference's Fortran-call layout: (lev, col) with the column fastest; hwind (2, lev, col): u_wind then v_wind;
+ *              qtracers (tr, lev, col); wtracer_sfc (tr, col)
+ *   layout 1   SCREAM's C++ layout: (col, lev) with the level fastest; hwind (col, 2, lev); qtracers (col, tr, lev); wtracer_sfc (col, tr)
+ * Sizes: ncol for the per-column arrays, nlev*ncol, nlevi*ncol for the interface arrays (zi_grid, presi, thl_sec ... w3).
+ * In: host_dx ... phis.  In/out: host_dse ... cldfrac.  Out: pblh ... tkh. */
+typedef struct pam_amd_shoc_args_t {
+  int ncol, nlev, nlevi;
+  double dt;
+  int nadv, num_qtracers, layout;
+  void *stream;   /* hipStream_t the coupling steps were enqueued on; shoc_main must order its work after it */
+  double *host_dx, *host_dy, *thv, *zt_grid, *zi_grid, *pres, *presi, *pdel, *wthl_sfc, *wqw_sfc, *uw_sfc, *vw_sfc, *wtracer_sfc;
+  double *w_field, *inv_exner, *phis;
+  double *host_dse, *tke, *thetal, *qw, *hwind, *qtracers, *wthv_sec, *tk, *ql, *cldfrac;
+  double *pblh, *ustar, *obklen, *mix, *isotropy, *w_sec, *thl_sec, *qw_sec, *qwthl_sec, *wthl_sec, *wqw_sec, *wtke_sec, *uw_sec, *vw_sec,
+      *w3, *wqls_sec, *brunt, *ql2, *tkh;
+  double *exner;
+} pam_amd_shoc_args_t;
+
+/* What SGS::set_shoc_main takes: 0 = success.  `args->stream` carries the work of the pack step; the unpack step is enqueued on the same
+ * stream right after the call returns. */
+typedef int (*pam_amd_shoc_main_fn)(const pam_amd_shoc_args_t *args, void *user);
+
+/* The workspace: ONE device allocation that holds every array of pam_amd_shoc_args_t, made once; nothing is allocated per step.
+ *   nens, nx, ny, nz >= 1 (ncol = ny*nx*nens below 2^31), num_qtracers 0 ... 7, layout 0 or 1.
+ * The arrays lie in the order of the struct, each rounded up to a multiple of 8 doubles, with a guard of 8 doubles before the first,
+ * between any two and after the last: with N = ncol, Z = nz, T = num_qtracers and r(n) = n rounded up to a multiple of 8,
+ *   doubles = 10 r(N) + r(T N) + 22 r(Z N) + r(2 Z N) + r(T Z N) + 11 r((Z+1) N) + 47 * 8          bytes = 8 * doubles
+ * The guards and the roundings hold the canary word 0x7ff853484f435f5f (a quiet NaN) from creation on: a write outside an array shows. */
+int pam_amd_shoc_workspace_create(int nens, int nx, int ny, int nz, int num_qtracers, int layout, void **ws);
+/* Fills *args with the sizes, the layout and the pointers; dt = 0, nadv = 1, stream = NULL are the caller's to set. */
+int pam_amd_shoc_workspace_args(void *ws, pam_amd_shoc_args_t *args);
+int pam_amd_shoc_workspace_bytes(void *ws, long long *bytes);
+int pam_amd_shoc_workspace_destroy(void *ws);   /* NULL: nothing to do */
+
+/* SGS.h:254-411 in ONE launch: the coupler state to every input of shoc_main, the vertical axis flipped, in the workspace's layout;
+ * no pressure array, no broadcast of zint / zmid, no scratch.  DEVICE arrays, (nz,ny,nx,nens) unless noted, all read only:
+ *   rho_d, rho_v, rho_c   "density_dry", "water_vapor", the cloud condensate ("cloud_liquid" / "cloud_water")
+ *   uvel, vvel, wvel, temp, tke
+ *   qtracers              HOST array of num_qtracers DEVICE pointers (SGS.h:240-249); may be NULL where num_qtracers = 0
+ *   wthv_sec, tk, tkh, cldfrac
+ *   sfc_mom_flx_u/v       (ny,nx,nens);  zint (nz+1,nens), zmid (nz,nens): read as (k, col % nens)
+ *   xlen, ylen            the domain: host_dx = xlen/nx, host_dy = ylen/ny (host_dx where ny = 1); finite and positive
+ *   coupler_R_d, coupler_R_v           the COUPLER's options R_d, R_v (the microphysics sets them): pmid is compute_pressure_array's
+ *                         (SGS.h:265, pam_coupler.h:375-376); finite and positive
+ *   R_d, cp_d, p0, grav, latvap        the SGS class's constants (SGS.h:60-80; exner = (pmid/p0)^(R_d/cp_d)); finite and positive
+ * Writes host_dx ... cldfrac, tkh and exner of the workspace; wthl_sfc, wqw_sfc and wtracer_sfc are zero (SGS.h:330-351).
+ * The plain arguments are checked first, then the workspace, then the tracer pointers (their number is the workspace's), all before the
+ * first HIP call.  The FIRST pack on a device builds the 3.5 KB of pow tables the Kessler kernels share (one synchronous allocation and
+ * copy, freed by pam_amd_modules_finalize()); from then on a call allocates nothing. */
+int pam_amd_shoc_pack(void *ws, const double *rho_d, const double *rho_v, const double *rho_c, const double *uvel, const double *vvel,
+                      const double *wvel, const double *temp, const double *tke, const double *const *qtracers, const double *wthv_sec,
+                      const double *tk, const double *tkh, const double *cldfrac, const double *sfc_mom_flx_u, const double *sfc_mom_flx_v,
+                      const double *zint, const double *zmid, double xlen, double ylen, double coupler_R_d, double coupler_R_v, double R_d,
+                      double cp_d, double p0, double grav, double latvap, void *stream);
+
+/* SGS.h:718-756 in ONE launch: qw, ql, thetal, exner, hwind, tke, wthv_sec, tk, tkh, cldfrac, ql2 and qtracers of the workspace back to
+ * the coupler state.  rho_d: in.  temp: in/out.  rho_v, rho_c, uvel, vvel, tke, qtracers[], wthv_sec, tk, tkh, cldfrac, inv_qc_relvar: out.
+ * cp_d, cv_d, latvap finite and positive. */
+int pam_amd_shoc_unpack(void *ws, const double *rho_d, double *rho_v, double *rho_c, double *uvel, double *vvel, double *temp, double *tke,
+                        double *const *qtracers, double *wthv_sec, double *tk, double *tkh, double *cldfrac, double *inv_qc_relvar,
+                        double cp_d, double cv_d, double latvap, void *stream);
+
+/* A TEST DOUBLE for shoc_main, not physics (pam_amd/csrc/shoc_device.h: standin_column), as a pam_amd_shoc_main_fn: one launch on
+ * args->stream, both layouts.  `user` is ignored. */
+int pam_amd_shoc_main_standin(const pam_amd_shoc_args_t *args, void *user);
+
+/* For tests: on != 0 makes pack, unpack and the stand-in launch their 64-bit-index instances whatever the size (they are otherwise chosen
+ * from 2^29 elements in the largest array on); 0 restores the choice by size.  Process-wide; the results have the same bits either way. */
+int pam_amd_shoc_debug_wide_index(int on);
+
 #ifdef __cplusplus
 }
 #endif

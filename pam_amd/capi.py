@@ -34,6 +34,22 @@ class GcmColumns(C.Structure):
                 ("gcm_cloud_water", C.c_void_p), ("gcm_cloud_ice", C.c_void_p)]
 
 
+# pam_amd_shoc_args_t (include/pam_amd_modules.h): the arguments of pam::shoc_main_cxx, in its order, plus exner
+SHOC_ARRAYS = ("host_dx", "host_dy", "thv", "zt_grid", "zi_grid", "pres", "presi", "pdel", "wthl_sfc", "wqw_sfc", "uw_sfc", "vw_sfc",
+               "wtracer_sfc", "w_field", "inv_exner", "phis", "host_dse", "tke", "thetal", "qw", "hwind", "qtracers", "wthv_sec", "tk", "ql",
+               "cldfrac", "pblh", "ustar", "obklen", "mix", "isotropy", "w_sec", "thl_sec", "qw_sec", "qwthl_sec", "wthl_sec", "wqw_sec",
+               "wtke_sec", "uw_sec", "vw_sec", "w3", "wqls_sec", "brunt", "ql2", "tkh", "exner")
+
+
+class ShocArgs(C.Structure):
+    _fields_ = [("ncol", C.c_int), ("nlev", C.c_int), ("nlevi", C.c_int), ("dt", C.c_double), ("nadv", C.c_int),
+                ("num_qtracers", C.c_int), ("layout", C.c_int), ("stream", C.c_void_p)] + [(n, C.c_void_p) for n in SHOC_ARRAYS]
+
+
+# pam_amd_shoc_main_fn
+SHOC_MAIN_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ShocArgs), C.c_void_p)
+
+
 # every symbol include/pam_amd_awfl.h declares (tests/test_capi_symbols.py checks the header against this list)
 SYMBOLS = {
     "pam_amd_awfl_abi_version": (C.c_int, []),
@@ -126,6 +142,14 @@ MODULE_SYMBOLS = {
                                           C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
     "pam_amd_field_diagnostics": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_void_p), C.c_int] +
                                   [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_longlong)] * 3 + [C.c_void_p]),
+    "pam_amd_shoc_workspace_create": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_void_p)]),
+    "pam_amd_shoc_workspace_args": (C.c_int, [C.c_void_p, C.POINTER(ShocArgs)]),
+    "pam_amd_shoc_workspace_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "pam_amd_shoc_workspace_destroy": (C.c_int, [C.c_void_p]),
+    "pam_amd_shoc_pack": (C.c_int, [C.c_void_p] * 9 + [C.POINTER(C.c_void_p)] + [C.c_void_p] * 8 + [C.c_double] * 9 + [C.c_void_p]),
+    "pam_amd_shoc_unpack": (C.c_int, [C.c_void_p] * 8 + [C.POINTER(C.c_void_p)] + [C.c_void_p] * 5 + [C.c_double] * 3 + [C.c_void_p]),
+    "pam_amd_shoc_main_standin": (C.c_int, [C.POINTER(ShocArgs), C.c_void_p]),
+    "pam_amd_shoc_debug_wide_index": (C.c_int, [C.c_int]),
 }
 
 

@@ -23,6 +23,7 @@
 #include "kessler_device.h"          // Kessler microphysics: the per-column bodies, the same
 #include "validate_device.h"         // DataManager::validate: classification, a thread's walk and the fold, the same
 #include "diagnostics_device.h"      // field diagnostics: the per-element update, a thread's share of a chunk and the folds, the same
+#include "shoc_device.h"             // the SHOC coupling layer: pack, unpack, the index and the stand-in for shoc_main, the same
 
 namespace {
 
@@ -2043,5 +2044,430 @@ extern "C" int pam_amd_compute_pressure(int nens, int nx, int ny, int nz, const 
     hipLaunchKernelGGL((coupler_pressure_kernel<unsigned>), grid, block, 0, (hipStream_t)stream, ncell, rho_d, rho_v, temp, R_d, R_v, pressure);
   else
     hipLaunchKernelGGL((coupler_pressure_kernel<long long>), grid, block, 0, (hipStream_t)stream, ncell, rho_d, rho_v, temp, R_d, R_v, pressure);
+  return stats_launch_check(who);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The SHOC coupling layer (physics/sgs/shoc/SGS.h:150-779): pack = the coupler state to every input of shoc_main, unpack = its outputs back,
+// one launch each; the arithmetic lives in shoc_device.h.  A thread owns one cell (k, col), lanes run along col, so every access to the
+// coupler state is a coalesced row.
+//   layout 0 ((lev, col), column fastest): tiles of 64 columns x 4 levels, the SHOC arrays are written / read directly.
+//   layout 1 ((col, lev), level fastest): tiles of 16 columns x 16 levels.  A value goes through an LDS tile [col][lev] of pitch 17 doubles
+//   and leaves with lanes along lev: 16 consecutive doubles (128 B) per row on both sides of HBM.  Banks (MI355X: 8-byte stores are served in
+//   groups of 16 consecutive lanes over 32 banks of 4 B, 8-byte loads in halves of 32 lanes over 64 banks): a store group holds 16 columns of one
+//   level, 17 c mod 16 = c: conflict-free; a load half holds 2 columns x 16 levels, offsets [x, x+16) and [x+17, x+33): one bank pair is hit
+//   twice (one extra cycle in 32 lanes).  A pitch of 16 would put all 16 lanes of a store group on one bank pair.  SHOC_GROUP arrays cross per pair of
+//   barriers (17 KB of LDS).
+// The pack kernel walks the level tiles of its columns from the ground up: a cell's values are computed once; the interface pressure needs pmid
+// and pdel of the cells k-1 and k, which are STAGED in LDS inside a tile and carried in registers from one tile to the next (nothing is recomputed,
+// no halo is re-read).  The tables of pow_pos_fast are staged once per workgroup.
+namespace {
+namespace sh = pama::shoc;
+constexpr int SHOC_THREADS = 256;
+constexpr int SHOC_GROUP = 8;
+constexpr long long SHOC_NARROW = 1ll << 29;   // the largest array from this size on: the long long instances
+constexpr unsigned long long SHOC_CANARY = 0x7ff853484f435f5full;
+constexpr int SHOC_GUARD = 8;                  // doubles
+constexpr int SHOC_NARRAYS = 46;
+template <int LAYOUT> struct ShocTile { static constexpr int TC = LAYOUT ? 16 : 64, TL = SHOC_THREADS / TC, PITCH = TL + 1; };
+
+struct ShocState {
+  const double *rho_d, *rho_v, *rho_c, *uvel, *vvel, *wvel, *temp, *tke, *wthv_sec, *tk, *tkh, *cldfrac, *flx_u, *flx_v, *zint, *zmid;
+  const double *q[sh::MAX_QTRACERS];
+};
+// destination of every per-cell value of pack_cell (C_*), with its component in hwind / qtracers
+struct ShocCellDst { double *p[sh::C_MAX]; signed char comp[sh::C_MAX], ncomp[sh::C_MAX]; };
+struct ShocColDst { double *zi_grid, *presi, *host_dx, *host_dy, *wthl_sfc, *wqw_sfc, *uw_sfc, *vw_sfc, *phis, *wtracer_sfc; };
+struct ShocCellSrc { const double *p[sh::U_MAX]; signed char comp[sh::U_MAX], ncomp[sh::U_MAX]; };
+struct ShocStateOut { double *p[sh::S_MAX]; const double *rho_d; };
+
+template <int LAYOUT, class IDX>
+__global__ void __launch_bounds__(SHOC_THREADS) shoc_pack_kernel(ShocState S, ShocCellDst D, ShocColDst E, int ncol_, int nens, int nz, int ntr,
+                                                                 sh::Consts c, double dx, double dy, const PowTab *__restrict__ tab) {
+  using T = ShocTile<LAYOUT>;
+  constexpr int TC = T::TC, TL = T::TL, PITCH = T::PITCH;
+  __shared__ PowTab sh_tab;
+  __shared__ double sh_p[TL][TC], sh_d[TL][TC];
+  __shared__ double sh_t[LAYOUT ? SHOC_GROUP * TC * PITCH : 1];
+  kessler_stage_tab(tab, &sh_tab);
+  const int tc = (int)threadIdx.x % TC, tl = (int)threadIdx.x / TC;
+  const IDX ncol = (IDX)ncol_;
+  const long long col_ll = (long long)blockIdx.x * TC + tc;
+  const bool col_ok = col_ll < ncol_;
+  const IDX col = (IDX)(col_ok ? col_ll : ncol_ - 1);
+  const int e = (int)(col % (IDX)nens);
+  const double z0 = S.zint[e];
+  const int na = sh::C_QTRACER0 + ntr;
+  // the transposed role of a thread (layout 1): lanes along the level
+  const int tl2 = (int)threadIdx.x % TL, tc2 = (int)threadIdx.x / TL;
+  const long long col2_ll = (long long)blockIdx.x * TC + tc2;
+  const bool col2_ok = col2_ll < ncol_;
+  const IDX col2 = (IDX)(col2_ok ? col2_ll : ncol_ - 1);
+  if (tl == 0 && col_ok) {   // SGS.h:327-352
+    E.host_dx[col] = dx;
+    E.host_dy[col] = dy;
+    E.wthl_sfc[col] = 0;
+    E.wqw_sfc[col] = 0;
+    E.uw_sfc[col] = S.flx_u[col];
+    E.vw_sfc[col] = S.flx_v[col];
+    { PAMA_NO_CONTRACT E.phis[col] = z0 * c.grav; }
+    for (int tr = 0; tr < ntr; tr++) E.wtracer_sfc[sh::offset_t<IDX>(LAYOUT, col, 0, ncol, 1, tr, ntr)] = 0;
+  }
+  const int ntile = (nz + TL) / TL;   // tiles that cover the nz + 1 interfaces
+  double carry_p = 0, carry_d = 0;    // of the thread row TL-1: its cell of the previous tile
+  for (int kt = 0; kt < ntile; kt++) {
+    const int k = kt * TL + tl;
+    const bool cell_ok = col_ok && k < nz, edge_ok = col_ok && k <= nz;
+    double v[sh::C_MAX];
+#pragma unroll
+    for (int a = 0; a < sh::C_MAX; a++) v[a] = 0;
+    double zk = 0;
+    if (edge_ok) zk = S.zint[(IDX)k * (IDX)nens + (IDX)e];
+    if (cell_ok) {
+      const IDX o = (IDX)k * ncol + col;
+      sh::CellIn in;
+      in.rho_d = S.rho_d[o]; in.rho_v = S.rho_v[o]; in.rho_c = S.rho_c[o]; in.uvel = S.uvel[o]; in.vvel = S.vvel[o]; in.wvel = S.wvel[o];
+      in.temp = S.temp[o]; in.tke = S.tke[o]; in.wthv_sec = S.wthv_sec[o]; in.tk = S.tk[o]; in.tkh = S.tkh[o]; in.cldfrac = S.cldfrac[o];
+#pragma unroll
+      for (int tr = 0; tr < sh::MAX_QTRACERS; tr++) in.q[tr] = tr < ntr ? S.q[tr][o] : 0.0;
+      in.zmid = S.zmid[(IDX)k * (IDX)nens + (IDX)e];
+      in.zint_k = zk;
+      in.zint_k1 = S.zint[(IDX)(k + 1) * (IDX)nens + (IDX)e];
+      in.zint_0 = z0;
+      sh::pack_cell(in, ntr, c, &sh_tab, v);
+    }
+    __syncthreads();   // the previous tile's readers of sh_p / sh_d / sh_t are done
+    sh_p[tl][tc] = v[sh::C_PRES];
+    sh_d[tl][tc] = v[sh::C_PDEL];
+    __syncthreads();
+    double p_km1 = carry_p, d_km1 = carry_d;
+    if (tl > 0) { p_km1 = sh_p[tl - 1][tc]; d_km1 = sh_d[tl - 1][tc]; }
+    // row 0 of the next tile needs row TL-1 of this one: every thread keeps its column's
+    carry_p = sh_p[TL - 1][tc];
+    carry_d = sh_d[TL - 1][tc];
+    double zi = 0, pint = 0;
+    if (edge_ok) {
+      { PAMA_NO_CONTRACT zi = zk - z0; }
+      pint = sh::pack_edge(k, nz, p_km1, d_km1, v[sh::C_PRES], v[sh::C_PDEL]);
+    }
+    if constexpr (LAYOUT == 0) {
+      if (cell_ok) {
+#pragma unroll
+        for (int a = 0; a < sh::C_MAX; a++)
+          if (a < na) D.p[a][sh::offset_t<IDX>(0, col, nz - 1 - k, ncol, nz, D.comp[a], D.ncomp[a])] = v[a];
+      }
+      if (edge_ok) {
+        E.zi_grid[sh::offset_t<IDX>(0, col, nz - k, ncol, nz + 1)] = zi;
+        E.presi[sh::offset_t<IDX>(0, col, nz - k, ncol, nz + 1)] = pint;
+      }
+    } else {
+      const int k2 = kt * TL + tl2;
+#pragma unroll
+      for (int g = 0; g < (sh::C_MAX + SHOC_GROUP - 1) / SHOC_GROUP; g++) {
+        if (g * SHOC_GROUP < na) {   // uniform over the workgroup
+          __syncthreads();
+#pragma unroll
+          for (int j = 0; j < SHOC_GROUP; j++)
+            if (g * SHOC_GROUP + j < sh::C_MAX) sh_t[(j * TC + tc) * PITCH + tl] = v[g * SHOC_GROUP + j < sh::C_MAX ? g * SHOC_GROUP + j : 0];
+          __syncthreads();
+          if (col2_ok && k2 < nz) {
+#pragma unroll
+            for (int j = 0; j < SHOC_GROUP; j++) {
+              const int a = g * SHOC_GROUP + j;
+              if (a < na) D.p[a][sh::offset_t<IDX>(1, col2, nz - 1 - k2, ncol, nz, D.comp[a], D.ncomp[a])] = sh_t[(j * TC + tc2) * PITCH + tl2];
+            }
+          }
+        }
+      }
+      __syncthreads();
+      sh_t[tc * PITCH + tl] = zi;
+      sh_t[(TC + tc) * PITCH + tl] = pint;
+      __syncthreads();
+      if (col2_ok && k2 <= nz) {
+        E.zi_grid[sh::offset_t<IDX>(1, col2, nz - k2, ncol, nz + 1)] = sh_t[tc2 * PITCH + tl2];
+        E.presi[sh::offset_t<IDX>(1, col2, nz - k2, ncol, nz + 1)] = sh_t[(TC + tc2) * PITCH + tl2];
+      }
+    }
+  }
+}
+
+// grid (column tiles, level tiles)
+template <int LAYOUT, class IDX>
+__global__ void __launch_bounds__(SHOC_THREADS) shoc_unpack_kernel(ShocCellSrc R, ShocStateOut O, int ncol_, int nz, int ntr, sh::Consts c) {
+  using T = ShocTile<LAYOUT>;
+  constexpr int TC = T::TC, TL = T::TL, PITCH = T::PITCH;
+  __shared__ double sh_t[LAYOUT ? SHOC_GROUP * TC * PITCH : 1];
+  const int tc = (int)threadIdx.x % TC, tl = (int)threadIdx.x / TC;
+  const IDX ncol = (IDX)ncol_;
+  const long long col_ll = (long long)blockIdx.x * TC + tc;
+  const int k = (int)blockIdx.y * TL + tl;
+  const bool cell_ok = col_ll < ncol_ && k < nz;
+  const IDX col = (IDX)(col_ll < ncol_ ? col_ll : ncol_ - 1);
+  const int na = sh::U_QTRACER0 + ntr;
+  double in[sh::U_MAX];
+#pragma unroll
+  for (int a = 0; a < sh::U_MAX; a++) in[a] = 0;
+  if constexpr (LAYOUT == 0) {
+    if (cell_ok) {
+#pragma unroll
+      for (int a = 0; a < sh::U_MAX; a++)
+        if (a < na) in[a] = R.p[a][sh::offset_t<IDX>(0, col, nz - 1 - k, ncol, nz, R.comp[a], R.ncomp[a])];
+    }
+  } else {
+    const int tl2 = (int)threadIdx.x % TL, tc2 = (int)threadIdx.x / TL;
+    const long long col2_ll = (long long)blockIdx.x * TC + tc2;
+    const int k2 = (int)blockIdx.y * TL + tl2;
+    const bool ok2 = col2_ll < ncol_ && k2 < nz;
+    const IDX col2 = (IDX)(col2_ll < ncol_ ? col2_ll : ncol_ - 1);
+#pragma unroll
+    for (int g = 0; g < (sh::U_MAX + SHOC_GROUP - 1) / SHOC_GROUP; g++) {
+      if (g * SHOC_GROUP < na) {   // uniform over the workgroup
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SHOC_GROUP; j++) {
+          const int a = g * SHOC_GROUP + j;
+          if (a < na && ok2) sh_t[(j * TC + tc2) * PITCH + tl2] = R.p[a][sh::offset_t<IDX>(1, col2, nz - 1 - k2, ncol, nz, R.comp[a], R.ncomp[a])];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SHOC_GROUP; j++)
+          if (g * SHOC_GROUP + j < sh::U_MAX && g * SHOC_GROUP + j < na) in[g * SHOC_GROUP + j < sh::U_MAX ? g * SHOC_GROUP + j : 0] = sh_t[(j * TC + tc) * PITCH + tl];
+      }
+    }
+  }
+  if (!cell_ok) return;
+  const IDX o = (IDX)k * ncol + col;
+  double out[sh::S_MAX];
+  sh::unpack_cell(in, O.p[sh::S_TEMP][o], O.rho_d[o], ntr, c, out);
+  const int ns = sh::S_QTRACER0 + ntr;
+#pragma unroll
+  for (int a = 0; a < sh::S_MAX; a++)
+    if (a < ns) O.p[a][o] = out[a];
+}
+
+template <class IDX>
+__global__ void __launch_bounds__(64) shoc_standin_kernel(pam_amd_shoc_args_t A) {
+  const long long col = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (col < A.ncol) sh::standin_column<IDX>(A, (IDX)col);
+}
+
+__global__ void __launch_bounds__(256) shoc_canary_kernel(unsigned long long *p, long long n) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) p[i] = SHOC_CANARY;
+}
+
+struct ShocWorkspace {
+  unsigned long long magic;
+  int nens, nx, ny, nz, ntr, layout;
+  long long doubles;
+  double *base;
+  pam_amd_shoc_args_t args;
+};
+constexpr unsigned long long SHOC_MAGIC = 0x53484f4357533031ull;
+ShocWorkspace *shoc_ws(void *ws) {
+  ShocWorkspace *w = (ShocWorkspace *)ws;
+  return (w && w->magic == SHOC_MAGIC) ? w : nullptr;
+}
+bool g_shoc_force_wide = false;   // pam_amd_shoc_debug_wide_index: tests run the long long instances at small sizes
+long long shoc_round8(long long n) { return (n + 7) / 8 * 8; }
+int shoc_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
+bool shoc_pos(double x) { return std::isfinite(x) && x > 0; }
+// element count of the largest array of a workspace
+long long shoc_largest(const ShocWorkspace *w) {
+  const long long ncol = (long long)w->ny * w->nx * w->nens;
+  return std::max<long long>(std::max(2, w->ntr) * (long long)w->nz * ncol, (long long)(w->nz + 1) * ncol);
+}
+// the sizes of the arrays, in the order of the struct's pointers
+void shoc_sizes(long long N, long long Z, long long T, long long (&n)[SHOC_NARRAYS]) {
+  const long long zi = (Z + 1) * N, zn = Z * N;
+  const long long s[SHOC_NARRAYS] = {N, N, zn, zn, zi, zn, zi, zn, N, N, N, N, T * N, zn, zn, N, zn, zn, zn, zn, 2 * zn, T * zn, zn, zn, zn, zn,
+                                     N, N, N, zn, zn, zn, zi, zi, zi, zi, zi, zi, zi, zi, zi, zn, zn, zn, zn, zn};
+  for (int i = 0; i < SHOC_NARRAYS; i++) n[i] = s[i];
+}
+}  // namespace
+
+extern "C" int pam_amd_shoc_debug_wide_index(int on) {
+  g_shoc_force_wide = on != 0;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_shoc_workspace_create(int nens, int nx, int ny, int nz, int num_qtracers, int layout, void **ws) {
+  const char *who = "shoc_workspace_create";
+  if (!ws) return shoc_error(who, "null ws");
+  *ws = nullptr;
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return shoc_error(who, "nens, nx, ny and nz must be >= 1");
+  if (num_qtracers < 0 || num_qtracers > sh::MAX_QTRACERS) return shoc_error(who, "num_qtracers must be 0 ... 7");
+  if (layout != 0 && layout != 1) return shoc_error(who, "layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)");
+  const long long ncol = (long long)ny * nx * nens;
+  if (ncol > 0x7fffffffLL - 64 || nz > 0x7ffffff0) return shoc_error(who, "ny x nx x nens must stay below 2^31");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  long long n[SHOC_NARRAYS], total = SHOC_GUARD;
+  shoc_sizes(ncol, nz, num_qtracers, n);
+  for (int i = 0; i < SHOC_NARRAYS; i++) total += shoc_round8(n[i]) + SHOC_GUARD;
+  double *base = nullptr;
+  if (hipMalloc((void **)&base, (size_t)total * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "shoc_workspace_create: cannot allocate the workspace");
+  }
+  hipLaunchKernelGGL(shoc_canary_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, 0,
+                     (unsigned long long *)base, total);
+  if (hipDeviceSynchronize() != hipSuccess) {
+    (void)hipFree(base);
+    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": " + hipGetErrorString(hipGetLastError())).c_str());
+  }
+  ShocWorkspace *w = new ShocWorkspace();
+  w->magic = SHOC_MAGIC;
+  w->nens = nens; w->nx = nx; w->ny = ny; w->nz = nz; w->ntr = num_qtracers; w->layout = layout;
+  w->doubles = total;
+  w->base = base;
+  pam_amd_shoc_args_t &A = w->args;
+  A.ncol = (int)ncol; A.nlev = nz; A.nlevi = nz + 1; A.dt = 0; A.nadv = 1; A.num_qtracers = num_qtracers; A.layout = layout; A.stream = nullptr;
+  double **ptr[SHOC_NARRAYS] = {&A.host_dx, &A.host_dy, &A.thv, &A.zt_grid, &A.zi_grid, &A.pres, &A.presi, &A.pdel, &A.wthl_sfc, &A.wqw_sfc,
+                                &A.uw_sfc, &A.vw_sfc, &A.wtracer_sfc, &A.w_field, &A.inv_exner, &A.phis, &A.host_dse, &A.tke, &A.thetal, &A.qw,
+                                &A.hwind, &A.qtracers, &A.wthv_sec, &A.tk, &A.ql, &A.cldfrac, &A.pblh, &A.ustar, &A.obklen, &A.mix,
+                                &A.isotropy, &A.w_sec, &A.thl_sec, &A.qw_sec, &A.qwthl_sec, &A.wthl_sec, &A.wqw_sec, &A.wtke_sec, &A.uw_sec,
+                                &A.vw_sec, &A.w3, &A.wqls_sec, &A.brunt, &A.ql2, &A.tkh, &A.exner};
+  long long at = SHOC_GUARD;
+  for (int i = 0; i < SHOC_NARRAYS; i++) {
+    *ptr[i] = base + at;
+    at += shoc_round8(n[i]) + SHOC_GUARD;
+  }
+  *ws = w;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_shoc_workspace_args(void *ws, pam_amd_shoc_args_t *args) {
+  ShocWorkspace *w = shoc_ws(ws);
+  if (!w) return shoc_error("shoc_workspace_args", "not a workspace of shoc_workspace_create");
+  if (!args) return shoc_error("shoc_workspace_args", "null args");
+  *args = w->args;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_shoc_workspace_bytes(void *ws, long long *bytes) {
+  ShocWorkspace *w = shoc_ws(ws);
+  if (!w) return shoc_error("shoc_workspace_bytes", "not a workspace of shoc_workspace_create");
+  if (!bytes) return shoc_error("shoc_workspace_bytes", "null bytes");
+  *bytes = w->doubles * (long long)sizeof(double);
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_shoc_workspace_destroy(void *ws) {
+  if (!ws) return PAM_AMD_OK;
+  ShocWorkspace *w = shoc_ws(ws);
+  if (!w) return shoc_error("shoc_workspace_destroy", "not a workspace of shoc_workspace_create");
+  (void)hipFree(w->base);
+  w->magic = 0;
+  delete w;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_shoc_pack(void *ws, const double *rho_d, const double *rho_v, const double *rho_c, const double *uvel,
+                                 const double *vvel, const double *wvel, const double *temp, const double *tke,
+                                 const double *const *qtracers, const double *wthv_sec, const double *tk, const double *tkh,
+                                 const double *cldfrac, const double *sfc_mom_flx_u, const double *sfc_mom_flx_v, const double *zint,
+                                 const double *zmid, double xlen, double ylen, double coupler_R_d, double coupler_R_v, double R_d, double cp_d,
+                                 double p0, double grav, double latvap, void *stream) {
+  const char *who = "shoc_pack";
+  if (!rho_d || !rho_v || !rho_c || !uvel || !vvel || !wvel || !temp || !tke || !wthv_sec || !tk || !tkh || !cldfrac || !sfc_mom_flx_u ||
+      !sfc_mom_flx_v || !zint || !zmid)
+    return shoc_error(who, "null pointer");
+  if (!shoc_pos(xlen) || !shoc_pos(ylen)) return shoc_error(who, "xlen and ylen must be finite and positive");
+  if (!shoc_pos(coupler_R_d) || !shoc_pos(coupler_R_v) || !shoc_pos(R_d) || !shoc_pos(cp_d) || !shoc_pos(p0) || !shoc_pos(grav) || !shoc_pos(latvap))
+    return shoc_error(who, "coupler_R_d, coupler_R_v, R_d, cp_d, p0, grav and latvap must be finite and positive");
+  ShocWorkspace *w = shoc_ws(ws);
+  if (!w) return shoc_error(who, "not a workspace of shoc_workspace_create");
+  if (w->ntr > 0 && !qtracers) return shoc_error(who, "null qtracers");
+  for (int tr = 0; tr < w->ntr; tr++)
+    if (!qtracers[tr]) return shoc_error(who, "null pointer in qtracers");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  const PowTab *tab = kessler_pow_tab(w->base);
+  if (!tab) return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "shoc_pack: cannot allocate the pow tables");
+  const pam_amd_shoc_args_t &A = w->args;
+  ShocState S = {rho_d, rho_v, rho_c, uvel, vvel, wvel, temp, tke, wthv_sec, tk, tkh, cldfrac, sfc_mom_flx_u, sfc_mom_flx_v, zint, zmid, {}};
+  for (int tr = 0; tr < sh::MAX_QTRACERS; tr++) S.q[tr] = tr < w->ntr ? qtracers[tr] : nullptr;
+  ShocCellDst D = {};
+  for (int a = 0; a < sh::C_MAX; a++) { D.p[a] = nullptr; D.comp[a] = 0; D.ncomp[a] = 1; }
+  D.p[sh::C_THV] = A.thv; D.p[sh::C_ZT_GRID] = A.zt_grid; D.p[sh::C_PRES] = A.pres; D.p[sh::C_PDEL] = A.pdel; D.p[sh::C_W_FIELD] = A.w_field;
+  D.p[sh::C_INV_EXNER] = A.inv_exner; D.p[sh::C_HOST_DSE] = A.host_dse; D.p[sh::C_TKE] = A.tke; D.p[sh::C_THETAL] = A.thetal;
+  D.p[sh::C_QW] = A.qw; D.p[sh::C_U_WIND] = A.hwind; D.p[sh::C_V_WIND] = A.hwind; D.p[sh::C_WTHV_SEC] = A.wthv_sec; D.p[sh::C_TK] = A.tk;
+  D.p[sh::C_QL] = A.ql; D.p[sh::C_CLDFRAC] = A.cldfrac; D.p[sh::C_TKH] = A.tkh; D.p[sh::C_EXNER] = A.exner;
+  D.ncomp[sh::C_U_WIND] = D.ncomp[sh::C_V_WIND] = 2;
+  D.comp[sh::C_V_WIND] = 1;
+  for (int tr = 0; tr < w->ntr; tr++) { D.p[sh::C_QTRACER0 + tr] = A.qtracers; D.comp[sh::C_QTRACER0 + tr] = (signed char)tr; D.ncomp[sh::C_QTRACER0 + tr] = (signed char)w->ntr; }
+  ShocColDst E = {A.zi_grid, A.presi, A.host_dx, A.host_dy, A.wthl_sfc, A.wqw_sfc, A.uw_sfc, A.vw_sfc, A.phis, A.wtracer_sfc};
+  const sh::Consts c = {p0, grav, R_d, cp_d, 0.0, latvap, coupler_R_d, coupler_R_v};
+  const double dx = xlen / w->nx, dy = w->ny == 1 ? dx : ylen / w->ny;   // SGS.h:168-169
+  const bool narrow = !g_shoc_force_wide && shoc_largest(w) < SHOC_NARROW;
+  hipStream_t s = (hipStream_t)stream;
+#define SHOC_PACK(LAYOUT, IDX)                                                                                                            \
+  hipLaunchKernelGGL((shoc_pack_kernel<LAYOUT, IDX>), dim3((unsigned)((A.ncol + ShocTile<LAYOUT>::TC - 1) / ShocTile<LAYOUT>::TC)),       \
+                     dim3(SHOC_THREADS), 0, s, S, D, E, A.ncol, w->nens, w->nz, w->ntr, c, dx, dy, tab)
+  if (w->layout == 0) { if (narrow) SHOC_PACK(0, unsigned); else SHOC_PACK(0, long long); }
+  else { if (narrow) SHOC_PACK(1, unsigned); else SHOC_PACK(1, long long); }
+#undef SHOC_PACK
+  return stats_launch_check(who);
+}
+
+extern "C" int pam_amd_shoc_unpack(void *ws, const double *rho_d, double *rho_v, double *rho_c, double *uvel, double *vvel, double *temp,
+                                   double *tke, double *const *qtracers, double *wthv_sec, double *tk, double *tkh, double *cldfrac,
+                                   double *inv_qc_relvar, double cp_d, double cv_d, double latvap, void *stream) {
+  const char *who = "shoc_unpack";
+  if (!rho_d || !rho_v || !rho_c || !uvel || !vvel || !temp || !tke || !wthv_sec || !tk || !tkh || !cldfrac || !inv_qc_relvar)
+    return shoc_error(who, "null pointer");
+  if (!shoc_pos(cp_d) || !shoc_pos(cv_d) || !shoc_pos(latvap)) return shoc_error(who, "cp_d, cv_d and latvap must be finite and positive");
+  ShocWorkspace *w = shoc_ws(ws);
+  if (!w) return shoc_error(who, "not a workspace of shoc_workspace_create");
+  if (w->ntr > 0 && !qtracers) return shoc_error(who, "null qtracers");
+  for (int tr = 0; tr < w->ntr; tr++)
+    if (!qtracers[tr]) return shoc_error(who, "null pointer in qtracers");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  const pam_amd_shoc_args_t &A = w->args;
+  ShocCellSrc R = {};
+  for (int a = 0; a < sh::U_MAX; a++) { R.p[a] = nullptr; R.comp[a] = 0; R.ncomp[a] = 1; }
+  R.p[sh::U_QW] = A.qw; R.p[sh::U_QL] = A.ql; R.p[sh::U_THETAL] = A.thetal; R.p[sh::U_EXNER] = A.exner; R.p[sh::U_U_WIND] = A.hwind;
+  R.p[sh::U_V_WIND] = A.hwind; R.p[sh::U_TKE] = A.tke; R.p[sh::U_WTHV_SEC] = A.wthv_sec; R.p[sh::U_TK] = A.tk; R.p[sh::U_TKH] = A.tkh;
+  R.p[sh::U_CLDFRAC] = A.cldfrac; R.p[sh::U_QL2] = A.ql2;
+  R.ncomp[sh::U_U_WIND] = R.ncomp[sh::U_V_WIND] = 2;
+  R.comp[sh::U_V_WIND] = 1;
+  for (int tr = 0; tr < w->ntr; tr++) { R.p[sh::U_QTRACER0 + tr] = A.qtracers; R.comp[sh::U_QTRACER0 + tr] = (signed char)tr; R.ncomp[sh::U_QTRACER0 + tr] = (signed char)w->ntr; }
+  ShocStateOut O = {};
+  O.p[sh::S_TEMP] = temp; O.p[sh::S_RHO_V] = rho_v; O.p[sh::S_RHO_C] = rho_c; O.p[sh::S_UVEL] = uvel; O.p[sh::S_VVEL] = vvel; O.p[sh::S_TKE] = tke;
+  O.p[sh::S_WTHV_SEC] = wthv_sec; O.p[sh::S_TK] = tk; O.p[sh::S_TKH] = tkh; O.p[sh::S_CLDFRAC] = cldfrac; O.p[sh::S_INV_QC_RELVAR] = inv_qc_relvar;
+  for (int tr = 0; tr < w->ntr; tr++) O.p[sh::S_QTRACER0 + tr] = qtracers[tr];
+  O.rho_d = rho_d;
+  const sh::Consts c = {0.0, 0.0, 0.0, cp_d, cv_d, latvap, 0.0, 0.0};
+  const bool narrow = !g_shoc_force_wide && shoc_largest(w) < SHOC_NARROW;
+  hipStream_t s = (hipStream_t)stream;
+#define SHOC_UNPACK(LAYOUT, IDX)                                                                                                          \
+  hipLaunchKernelGGL((shoc_unpack_kernel<LAYOUT, IDX>), dim3((unsigned)((A.ncol + ShocTile<LAYOUT>::TC - 1) / ShocTile<LAYOUT>::TC),      \
+                                                            (unsigned)((w->nz + ShocTile<LAYOUT>::TL - 1) / ShocTile<LAYOUT>::TL)),       \
+                     dim3(SHOC_THREADS), 0, s, R, O, A.ncol, w->nz, w->ntr, c)
+  if (w->layout == 0) { if (narrow) SHOC_UNPACK(0, unsigned); else SHOC_UNPACK(0, long long); }
+  else { if (narrow) SHOC_UNPACK(1, unsigned); else SHOC_UNPACK(1, long long); }
+#undef SHOC_UNPACK
+  return stats_launch_check(who);
+}
+
+extern "C" int pam_amd_shoc_main_standin(const pam_amd_shoc_args_t *args, void *user) {
+  (void)user;
+  const char *who = "shoc_main_standin";
+  if (!args) return shoc_error(who, "null args");
+  const pam_amd_shoc_args_t &A = *args;
+  if (A.ncol < 1 || A.nlev < 1 || A.nlevi != A.nlev + 1) return shoc_error(who, "ncol, nlev must be >= 1 and nlevi = nlev + 1");
+  if (A.ncol > 0x7fffffff - 64 || A.nlev > 0x7ffffff0) return shoc_error(who, "ncol must stay below 2^31 - 64");
+  if (A.num_qtracers < 0 || A.num_qtracers > sh::MAX_QTRACERS) return shoc_error(who, "num_qtracers must be 0 ... 7");
+  if (A.layout != 0 && A.layout != 1) return shoc_error(who, "layout must be 0 or 1");
+  double *const all[SHOC_NARRAYS] = {A.host_dx, A.host_dy, A.thv, A.zt_grid, A.zi_grid, A.pres, A.presi, A.pdel, A.wthl_sfc, A.wqw_sfc, A.uw_sfc,
+                                     A.vw_sfc, A.wtracer_sfc, A.w_field, A.inv_exner, A.phis, A.host_dse, A.tke, A.thetal, A.qw, A.hwind,
+                                     A.qtracers, A.wthv_sec, A.tk, A.ql, A.cldfrac, A.pblh, A.ustar, A.obklen, A.mix, A.isotropy, A.w_sec,
+                                     A.thl_sec, A.qw_sec, A.qwthl_sec, A.wthl_sec, A.wqw_sec, A.wtke_sec, A.uw_sec, A.vw_sec, A.w3,
+                                     A.wqls_sec, A.brunt, A.ql2, A.tkh, A.exner};
+  for (int i = 0; i < SHOC_NARRAYS; i++)
+    if (!all[i]) return shoc_error(who, "null pointer in args");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  const long long largest = std::max<long long>(std::max(2, A.num_qtracers) * (long long)A.nlev * A.ncol, (long long)A.nlevi * A.ncol);
+  const dim3 grid((unsigned)((A.ncol + 63) / 64)), block(64);
+  if (!g_shoc_force_wide && largest < SHOC_NARROW) hipLaunchKernelGGL((shoc_standin_kernel<unsigned>), grid, block, 0, (hipStream_t)A.stream, A);
+  else hipLaunchKernelGGL((shoc_standin_kernel<long long>), grid, block, 0, (hipStream_t)A.stream, A);
   return stats_launch_check(who);
 }

@@ -3,6 +3,7 @@
   Radiation         physics/radiation/forced/radiation.h   the GCM's radiative heating applied to the CRM temperature
   RadiationNone     physics/radiation/none/radiation.h
   SGSNone           physics/sgs/none/SGS.h
+  SGSShoc           physics/sgs/shoc/SGS.h                 the coupling layer around shoc_main; SHOC itself is handed in by the caller
   MicrophysicsNone  physics/micro/none/Microphysics.h      registers and zeroes "water_vapor", sets the constants
 
 Arithmetic is in libpam_amd_awfl.so (pam_amd/csrc/modules_kernels.hip); there is no CPU path.  Deviations from the reference
@@ -110,6 +111,197 @@ class SGSNone:
 
     def finalize(self, coupler):
         pass
+
+
+class _DeviceArray:
+    """device memory of the library as something torch.as_tensor can wrap without a copy"""
+
+    def __init__(self, ptr, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f8", "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+def shoc_shapes(ncol, nz, ntr, layout):
+    """name -> shape of every array of pam_amd_shoc_args_t (include/pam_amd_modules.h) in layout 0 ((lev, col), column fastest) or
+    1 (SCREAM's (col, lev), level fastest)"""
+    cell = {"thv", "zt_grid", "pres", "pdel", "w_field", "inv_exner", "host_dse", "tke", "thetal", "qw", "wthv_sec", "tk", "ql", "cldfrac", "mix",
+            "isotropy", "w_sec", "wqls_sec", "brunt", "ql2", "tkh", "exner"}
+    edge = {"zi_grid", "presi", "thl_sec", "qw_sec", "qwthl_sec", "wthl_sec", "wqw_sec", "wtke_sec", "uw_sec", "vw_sec", "w3"}
+    out = {}
+    for n in capi.SHOC_ARRAYS:
+        if n in cell:
+            out[n] = (nz, ncol) if layout == 0 else (ncol, nz)
+        elif n in edge:
+            out[n] = (nz + 1, ncol) if layout == 0 else (ncol, nz + 1)
+        elif n == "hwind":
+            out[n] = (2, nz, ncol) if layout == 0 else (ncol, 2, nz)
+        elif n == "qtracers":
+            out[n] = (ntr, nz, ncol) if layout == 0 else (ncol, ntr, nz)
+        elif n == "wtracer_sfc":
+            out[n] = (ntr, ncol) if layout == 0 else (ncol, ntr)
+        else:
+            out[n] = (ncol,)
+    return out
+
+
+class SGSShoc:
+    """physics/sgs/shoc/SGS.h: the coupling layer around SHOC -- pack (SGS.h:254-411), shoc_main, unpack (:718-756) -- as two fused
+    launches on the current stream.  SHOC itself is not part of this library: `shoc_main` is
+
+      * a C function pointer of type pam_amd_shoc_main_fn (a ctypes function, e.g. SGSShoc.standin(), or an address), called with the
+        pam_amd_shoc_args_t of the workspace and `user`, or
+      * a Python callable f(arrays, args): arrays maps every name of pam_amd_shoc_args_t to a torch view of the workspace in `layout`
+        (shoc_shapes), args is the capi.ShocArgs; it works in place on the current stream.
+
+    layout 1 is SCREAM's C++ layout (col, lev), layout 0 the reference's Fortran-call layout (lev, col)."""
+    ID_TKE = 0
+    # SGS.h:60-80
+    R_d, cp_d, R_v, cp_v, p0, grav, cp_l = 287.042, 1004.64, 461.505, 1859.0, 1.0e5, 9.80616, 4218.0
+    cv_d = cp_d - R_d
+    gamma_d, kappa_d, cv_v = cp_d / cv_d, R_d / cp_d, R_v - cp_v
+    latvap, latice, karman = 2501000.0, 333700.0, 0.4
+    P3_TRACERS = ("cloud_water_num", "rain", "rain_num", "ice", "ice_num", "ice_rime", "ice_rime_vol")      # SGS.h:243-249
+
+    def __init__(self, shoc_main=None, layout=1, user=None):
+        if layout not in (0, 1):
+            endrun("ERROR: SHOC: layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)")
+        self.layout = layout
+        self.micro_kessler = self.micro_p3 = False
+        self.first_step = True
+        self.etime = 0.0
+        self.npbl = -1
+        self._ws = None
+        self._ws_key = None
+        self.set_shoc_main(shoc_main, user)
+
+    @staticmethod
+    def get_num_tracers():
+        return 1
+
+    @staticmethod
+    def sgs_name():
+        return "shoc"
+
+    @staticmethod
+    def standin():
+        """the library's test double for shoc_main (no physics): pam_amd_shoc_main_standin"""
+        return capi.load().pam_amd_shoc_main_standin
+
+    def set_shoc_main(self, fn, user=None):
+        import ctypes as C
+        if isinstance(fn, int):
+            fn = capi.SHOC_MAIN_FN(fn)
+        self._c_main = fn is not None and isinstance(fn, C._CFuncPtr)
+        self.shoc_main, self.user = fn, user
+
+    def init(self, coupler):
+        """SGS.h:92-146: the "tke" tracer (positive, adds no mass), five 4-D and four surface entries, all zero; option sgs = "shoc" """
+        nz, ny, nx, nens = coupler.get_nz(), coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+        coupler.add_tracer("tke", "Turbulent Kinetic Energy (m^2/s^2)", True, False)
+        dm = coupler.get_data_manager_device_readwrite()
+        for name, desc in (("wthv_sec", "Buoyancy flux [K m/s]"), ("tk", "Eddy coefficient for momentum [m2/s]"),
+                           ("tkh", "Eddy coefficent for heat [m2/s]"), ("cldfrac", "Cloud fraction [-]"),
+                           ("inv_qc_relvar", "Inverse relative cloud water variance")):
+            dm.register_and_allocate(name, desc, (nz, ny, nx, nens), ("z", "y", "x", "nens"))
+        for name, desc in (("sfc_shf", "input surface sensible heat flux"), ("sfc_lhf", "input surface latent heat flux"),
+                           ("sfc_mom_flx_u", "Surface flux of U-momentum"), ("sfc_mom_flx_v", "Surface flux of V-momentum")):
+            if not dm.entry_exists(name):           # surface_friction may have registered the momentum fluxes already
+                dm.register_and_allocate(name, desc, (ny, nx, nens), ("y", "x", "nens"))
+        for name in ("tke", "wthv_sec", "tk", "tkh", "cldfrac", "inv_qc_relvar", "sfc_mom_flx_u", "sfc_mom_flx_v"):
+            dm.get(name).zero_()
+        coupler.set_option("sgs", "shoc")
+
+    def _workspace(self, coupler, ntr):
+        import ctypes as C
+        lib = capi.load()
+        key = (coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), ntr, self.layout, str(coupler.device))
+        if self._ws is None or self._ws_key != key:
+            self._free()
+            ws = C.c_void_p()
+            with torch.cuda.device(coupler.device):
+                check(lib.pam_amd_shoc_workspace_create(*key[:6], C.byref(ws)))
+            self._ws, self._ws_key = ws, key
+            self._args = capi.ShocArgs()
+            check(lib.pam_amd_shoc_workspace_args(ws, C.byref(self._args)))
+            self._views = None
+        return self._ws
+
+    def workspace_bytes(self):
+        import ctypes as C
+        n = C.c_longlong()
+        check(capi.load().pam_amd_shoc_workspace_bytes(self._ws, C.byref(n)))
+        return n.value
+
+    def workspace_views(self, device):
+        """name -> torch view of the workspace array, in this object's layout"""
+        if self._views is None:
+            a = self._args
+            shapes = shoc_shapes(a.ncol, a.nlev, a.num_qtracers, self.layout)
+            self._views = {n: (torch.as_tensor(_DeviceArray(getattr(a, n), shp), device=device) if min(shp) > 0
+                               else torch.empty(shp, dtype=torch.float64, device=device)) for n, shp in shapes.items()}
+        return self._views
+
+    def _free(self):
+        if self._ws is not None:
+            check(capi.load().pam_amd_shoc_workspace_destroy(self._ws))
+        self._ws = self._ws_key = self._views = None
+
+    def timeStep(self, coupler):
+        """SGS.h:150-779.  Everything is checked before the first launch: a refused call leaves every field untouched"""
+        import ctypes as C
+        lib = capi.load()
+        if self.shoc_main is None:
+            endrun("ERROR: SHOC: no shoc_main is registered; call set_shoc_main(fn, user) before timeStep (SHOC itself is not part of "
+                   "this library)")
+        dt = float(coupler.get_option("crm_dt"))
+        # the pressure is compute_pressure_array's (SGS.h:265): the coupler's options R_d, R_v, which the microphysics sets
+        pres_R_d, pres_R_v = float(coupler.get_option("R_d")), float(coupler.get_option("R_v"))
+        if self.first_step:
+            if not coupler.option_exists("micro"):
+                endrun("ERROR: SHOC requires coupler.set_option<std::string>(\"micro\",...) to be set")
+            micro = coupler.get_option("micro")
+            if micro not in ("kessler", "p3"):
+                endrun("ERROR: SHOC only meant to run with kessler or p3 microphysics")
+            self.micro_kessler, self.micro_p3 = micro == "kessler", micro == "p3"
+        nz, ny, nx, nens = coupler.get_nz(), coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+        dm = coupler.get_data_manager_device_readwrite()
+        cloud, names = ("cloud_liquid", ("precip_liquid",)) if self.micro_kessler else ("cloud_water", self.P3_TRACERS)
+        ro = lambda n: dm.get(n, readonly=True)
+        rho_d, wvel, zint, zmid = ro("density_dry"), ro("wvel"), ro("vertical_interface_height"), ro("vertical_midpoint_height")
+        flx_u, flx_v = ro("sfc_mom_flx_u"), ro("sfc_mom_flx_v")
+        rho_v, rho_c, uvel, vvel, temp, tke = (dm.get(n) for n in ("water_vapor", cloud, "uvel", "vvel", "temp", "tke"))
+        wthv_sec, tk, tkh, cldfrac, relvar = (dm.get(n) for n in ("wthv_sec", "tk", "tkh", "cldfrac", "inv_qc_relvar"))
+        q = [dm.get(n) for n in names]
+        qp = (C.c_void_p * max(len(q), 1))(*[t.data_ptr() for t in q])
+        ws = self._workspace(coupler, len(q))
+        with torch.cuda.device(coupler.device):
+            stream = torch.cuda.current_stream(coupler.device).cuda_stream
+            check(lib.pam_amd_shoc_pack(ws, rho_d.data_ptr(), rho_v.data_ptr(), rho_c.data_ptr(), uvel.data_ptr(), vvel.data_ptr(),
+                                        wvel.data_ptr(), temp.data_ptr(), tke.data_ptr(), qp, wthv_sec.data_ptr(), tk.data_ptr(),
+                                        tkh.data_ptr(), cldfrac.data_ptr(), flx_u.data_ptr(), flx_v.data_ptr(), zint.data_ptr(),
+                                        zmid.data_ptr(), float(coupler.get_xlen()), float(coupler.get_ylen()), pres_R_d, pres_R_v, self.R_d,
+                                        self.cp_d, self.p0, self.grav, self.latvap, stream))
+            self._args.dt, self._args.nadv, self._args.stream = dt, 1, stream
+            if self._c_main:
+                rc = self.shoc_main(C.byref(self._args), self.user)
+            else:
+                rc = self.shoc_main(self.workspace_views(coupler.device), self._args)
+            if rc not in (0, None):
+                endrun(f"ERROR: SHOC: shoc_main returned {rc}")
+            check(lib.pam_amd_shoc_unpack(ws, rho_d.data_ptr(), rho_v.data_ptr(), rho_c.data_ptr(), uvel.data_ptr(), vvel.data_ptr(),
+                                          temp.data_ptr(), tke.data_ptr(), qp, wthv_sec.data_ptr(), tk.data_ptr(), tkh.data_ptr(),
+                                          cldfrac.data_ptr(), relvar.data_ptr(), self.cp_d, self.cv_d, self.latvap, stream))
+        self.first_step = False
+        self.etime += dt
+
+    def finalize(self, coupler):
+        self._free()
+
+    def __del__(self):
+        # an object dropped without finalize() must not keep its workspace (18 to 21 GB at 1024 x 32x32x60) for the life of the process
+        try:
+            self._free()
+        except Exception:
+            pass
 
 
 class MicrophysicsNone:

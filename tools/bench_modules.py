@@ -5,7 +5,8 @@ then the forced radiation plug-in at three rad grids and the coupler's pressure 
 copy timed beside them as yardsticks, three repetitions: one JSON object on stdout.
 Run on the GPU box:  python tools/bench_modules.py            (--only vertical_interp, --only plugins: those rows alone;
 --only validate: DataManager.validate_all's device scan with the two statistics rows of the same run beside it;
---only diagnostics: pam_amd.field_diagnostics whole-field and per-member, with the validation and time_average_accumulate rows)"""
+--only diagnostics: pam_amd.field_diagnostics whole-field and per-member, with the validation and time_average_accumulate rows;
+--only shoc: the SHOC coupling layer's pack and unpack in both layouts, both tracer sets, beside the composition the reference performs)"""
 import json
 import os
 import sys
@@ -372,8 +373,143 @@ def plugins_timing(dev, n=11, reps=3):
     return out
 
 
+def shoc_timing(dev, n=11):
+    """pam_amd_shoc_pack / pam_amd_shoc_unpack at the C2 grid in both layouts, with the Kessler (1 extra tracer) and the P3 (7) set: 3 warm-up
+    calls, median of n event-timed calls.  Algorithmic bytes with Z = nz, N = ncol, T = extra tracers, 8 B each:
+      pack    reads  (12 + T) Z N  (rho_d, rho_v, rho_c, u, v, w, temp, tke, wthv_sec, tk, tkh, cldfrac, tracers) + 2 N (surface fluxes)
+              writes (18 + T) Z N  (thv, zt_grid, pres, pdel, w_field, inv_exner, host_dse, tke, thetal, qw, hwind x 2, wthv_sec, tk, ql,
+                                    cldfrac, tkh, exner, qtracers) + 2 (Z + 1) N (zi_grid, presi) + (7 + T) N (per column)
+      unpack  reads  (12 + T) Z N  (qw, ql, thetal, exner, hwind x 2, tke, wthv_sec, tk, tkh, cldfrac, ql2, qtracers) + 2 Z N (temp, rho_d)
+              writes (11 + T) Z N  (temp, rho_v, rho_c, u, v, tke, wthv_sec, tk, tkh, cldfrac, inv_qc_relvar, tracers)
+    The comparison is what the reference performs for SCREAM's layout, built from what exists: pam_amd_compute_pressure, the layout-0
+    pack and one transpose().contiguous() per array shoc_main reads (and back: one per array the unpack step reads, then the layout-0
+    unpack).  time_average_accumulate runs beside them as the yardstick of the other rows."""
+    import ctypes as C
+    from pam_amd import PamCoupler, modules
+    from pam_amd import idealized as idz
+    from pam_amd.capi import ShocArgs, check, load
+    from pam_amd.physics import SGSShoc, _DeviceArray, shoc_shapes
+    lib, stream = load(), torch.cuda.current_stream(dev).cuda_stream
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    ncol = nens * nx * ny
+    cells = ncol * nz
+    out = {"shoc_grid": "1024 x 32x32x60 (C2)", "shoc_method": "3 warm-up calls, median of %d event-timed calls" % n}
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        return _events(fn, n=n)
+
+    def row(ms, nbytes):
+        gbs = nbytes / ms / 1e6
+        return {"ms": ms, "bytes": nbytes, "GBps": gbs, "hbm_frac": gbs / bench.HBM_PEAK_GBS}
+
+    for label, extra in (("kessler", ("precip_liquid",)), ("p3", SGSShoc.P3_TRACERS)):
+        T = len(extra)
+        c = PamCoupler(dev)
+        c.set_option("crm_dt", 20.0)
+        c.set_option("gcm_physics_dt", 900.0)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+        cloud = "cloud_liquid" if label == "kessler" else "cloud_water"
+        for name in ("water_vapor", cloud) + tuple(extra):
+            c.add_tracer(name, "", True, True)
+        c.set_option("R_d", SGSShoc.R_d)
+        c.set_option("R_v", SGSShoc.R_v)
+        SGSShoc().init(c)
+        dm = c.get_data_manager_device_readwrite()
+        gen = torch.Generator(device=dev).manual_seed(0)
+        fields = ["density_dry", "water_vapor", cloud, "uvel", "vvel", "wvel", "temp", "tke", "wthv_sec", "tk", "tkh", "cldfrac"] + list(extra)
+        for name in fields:
+            t = dm.get(name)
+            t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev))
+        dm.get("temp").mul_(100.0).add_(200.0)
+        dm.get("density_dry").add_(0.1)
+        for name in ("water_vapor", cloud) + tuple(extra):
+            dm.get(name).mul_(1e-3)
+        saved = {name: dm.get(name).clone() for name in ("temp", "water_vapor", cloud, "tke")}
+        g = lambda name: dm.get(name).data_ptr()
+        qp = (C.c_void_p * T)(*[g(name) for name in extra])
+        ws, args, views = {}, {}, {}
+        for layout in (0, 1):
+            w = C.c_void_p()
+            check(lib.pam_amd_shoc_workspace_create(nens, nx, ny, nz, T, layout, C.byref(w)))
+            a = ShocArgs()
+            check(lib.pam_amd_shoc_workspace_args(w, C.byref(a)))
+            nb = C.c_longlong()
+            check(lib.pam_amd_shoc_workspace_bytes(w, C.byref(nb)))
+            out["shoc_workspace_bytes_%s_layout%d" % (label, layout)] = nb.value
+            ws[layout], args[layout] = w, a
+            views[layout] = {k: torch.as_tensor(_DeviceArray(getattr(a, k), shp), device=dev) for k, shp in shoc_shapes(ncol, nz, T, layout).items()}
+
+        def pack(layout):
+            check(lib.pam_amd_shoc_pack(ws[layout], g("density_dry"), g("water_vapor"), g(cloud), g("uvel"), g("vvel"), g("wvel"), g("temp"),
+                                        g("tke"), qp, g("wthv_sec"), g("tk"), g("tkh"), g("cldfrac"), g("sfc_mom_flx_u"), g("sfc_mom_flx_v"),
+                                        g("vertical_interface_height"), g("vertical_midpoint_height"), nx * 1000.0, ny * 1000.0, 287.0, 461.0,
+                                        SGSShoc.R_d, SGSShoc.cp_d, SGSShoc.p0, SGSShoc.grav, SGSShoc.latvap, stream))
+
+        def unpack(layout):
+            check(lib.pam_amd_shoc_unpack(ws[layout], g("density_dry"), g("water_vapor"), g(cloud), g("uvel"), g("vvel"), g("temp"), g("tke"), qp,
+                                          g("wthv_sec"), g("tk"), g("tkh"), g("cldfrac"), g("inv_qc_relvar"), SGSShoc.cp_d, SGSShoc.cv_d,
+                                          SGSShoc.latvap, stream))
+
+        def restore():
+            for name, v in saved.items():
+                dm.get(name).copy_(v)
+
+        ins = ("thv", "zt_grid", "zi_grid", "pres", "presi", "pdel", "w_field", "inv_exner", "host_dse", "tke", "thetal", "qw", "wthv_sec", "tk",
+               "ql", "cldfrac", "wtracer_sfc")
+        outs = ("qw", "ql", "thetal", "exner", "tke", "wthv_sec", "tk", "tkh", "cldfrac", "ql2")
+
+        def composed_pack():
+            c.compute_pressure_array()
+            pack(0)
+            v = views[0]
+            keep = [v[k].t().contiguous() for k in ins]
+            keep.append(v["hwind"].permute(2, 0, 1).contiguous())
+            keep.append(v["qtracers"].permute(2, 0, 1).contiguous())
+            return keep
+
+        def composed_unpack():
+            v1, v0 = views[1], views[0]
+            for k in outs:
+                v0[k].copy_(v1[k].t())
+            v0["hwind"].copy_(v1["hwind"].permute(1, 2, 0))
+            v0["qtracers"].copy_(v1["qtracers"].permute(1, 2, 0))
+            unpack(0)
+
+        pack_bytes = 8.0 * ((12 + T) * cells + 2 * ncol + (18 + T) * cells + 2 * (nz + 1) * ncol + (7 + T) * ncol)
+        unpack_bytes = 8.0 * ((12 + T) * cells + 2 * cells + (11 + T) * cells)
+        for layout in (0, 1):
+            out["shoc_pack_%s_layout%d" % (label, layout)] = row(timed(lambda: pack(layout)), pack_bytes)
+        out["shoc_pack_%s_composition" % label] = row(timed(composed_pack), pack_bytes)
+        # the unpack step reads what a shoc_main left: the stand-in's outputs, in both workspaces
+        for layout in (0, 1):
+            pack(layout)
+            args[layout].stream = stream
+            check(lib.pam_amd_shoc_main_standin(C.byref(args[layout]), None))
+        for layout in (0, 1):
+            restore()
+            out["shoc_unpack_%s_layout%d" % (label, layout)] = row(timed(lambda: unpack(layout)), unpack_bytes)
+        restore()
+        out["shoc_unpack_%s_composition" % label] = row(timed(composed_unpack), unpack_bytes)
+        restore()
+        names = ["density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor", cloud, "tke"]
+        modules.time_average_init(c, names)
+        elems = sum(dm.get(name, readonly=True).numel() for name in names)
+        out["time_average_accumulate_%s" % label] = row(timed(lambda: modules.time_average_accumulate(c, names)), elems * 24.0)
+        for layout in (0, 1):
+            check(lib.pam_amd_shoc_workspace_destroy(ws[layout]))
+        del views, saved, dm, c
+        torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "shoc"]:
+        print(json.dumps(shoc_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "plugins"]:
         print(json.dumps(plugins_timing(dev)))
         sys.exit(0)
