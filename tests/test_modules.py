@@ -40,7 +40,9 @@ def test_oracle_sponge_layer_properties():
                          ids=["2d", "3d", "strips_small_ensemble", "strips_one_member"])
 def test_gpu_sponge_layer_matches_oracle(ny, nens, nx):
     """the horizontal means live in sponge_kernel's workgroup: each of a member's 16 slots sums its cells, slot_reduce adds the slot
-    sums.  The 2-D case has ny*nx = 5, so most slots own no cell; the last two have many cells per slot (66 and 288 columns)"""
+    sums.  The 2-D case has ny*nx = 5, so most slots own no cell; the last two have many cells per slot (66 and 288 columns).
+    This state is horizontally uniform in the sponge but for wvel, its other tracers are zero there and its members share one factor: the
+    means as relaxation targets, the per-member factor and the tracer entries are covered cell by cell in tests/test_n2_modules_cells.py"""
     import torch
     from pam_amd import PamCoupler, modules
     tr = idz.TRACERS_KESSLER_SHOC
