@@ -246,7 +246,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 //   perturb_temperature, all on the device) when not idealized -> per GCM step { declare_current_profile_as_hydrostatic (what E3SM's
 //   MMF driver does once per GCM step; the standalone reference never calls it and runs on uninitialised variable_gravity);
 //   per CRM step { [radiation ->] dycore -> sponge_layer -> micro } }.
-// Not run: P3 and SHOC (the CI build's micro / sgs; SCREAM's numerics are out of scope; SHOC's coupling layer is built: physics/sgs/shoc_amd/SGS.h) -- Kessler stands in as the microphysics -- and
+// Not run: P3 and SHOC (the CI build's micro / sgs; SCREAM's numerics are out of scope; their coupling layers are built: physics/micro/p3_amd/Microphysics.h, physics/sgs/shoc_amd/SGS.h) -- Kessler stands in as the microphysics here -- and
 // modules::*_gcm_forcing_tendencies, whose field list is P3's tracer set (pam_core/modules/gcm_forcing.h:33-42).
 // vcoords: "uniform" (driver.cpp:135-153, with crm_nz and zlen) or the reference's file name `vcoords_equal_<N>_<H>km.nc` -- netCDF-4,
 // unreadable here; its contents are what the name says (read from the raw bytes of the reference's copy: 51 interfaces 0, 400, ...,
@@ -417,7 +417,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     SGS sgs;
     Radiation rad;
     micro.init(coupler);                                                     // driver.cpp:189
-    sgs.init(coupler);                                                       // driver.cpp:190 (the reference's CI build: SHOC; its numerics are out of scope, its coupling layer is physics/sgs/shoc_amd)
+    sgs.init(coupler);                                                       // driver.cpp:190 (the reference's CI build: SHOC with P3; their numerics are out of scope, their coupling layers are physics/sgs/shoc_amd and physics/micro/p3_amd)
     dycore.init(coupler);                                                    // driver.cpp:191
     if (mods.radiation) {
       coupler.set_option<int>("rad_nx", mods.rad_nx);

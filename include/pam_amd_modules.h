@@ -324,6 +324,93 @@ int pam_amd_shoc_main_standin(const pam_amd_shoc_args_t *args, void *user);
  * from 2^29 elements in the largest array on); 0 restores the choice by size.  Process-wide; the results have the same bits either way. */
 int pam_amd_shoc_debug_wide_index(int on);
 
+/* The P3 coupling layer: what Microphysics::timeStep of the reference does around p3_main  (physics/micro/p3/Microphysics.h:214-741), as
+ * two fused launches with P3 behind a function pointer.  P3 itself (SCREAM's code), its lookup tables and micro_p3_utils_init are not
+ * part of this library: they belong to whoever supplies p3_main.
+ *
+ * pam_amd_p3_args_t: the arguments of p3_main_fortran / pam::p3_main_cxx (Microphysics.h:11-23, :491-537) under their names, plus
+ * `exner`, which the unpack step needs (:697).  Every pointer is a DEVICE array of the workspace below.  k = the physical level, 0 at
+ * the ground.
+ *   layout 0   the reference's Fortran-call layout (:568-669): (lev, col) with the column fastest, lev = k (NOT flipped);
+ *              col_location (3, col); p3_tend_out (num_tend_out, lev, col); it = its = kts = 1, ite = ncol, kte = nlev
+ *   layout 1   SCREAM's C++ layout (:415-564): (col, lev) with the level fastest, lev = nlev-1-k; the flux arrays (col, nlev+1) with
+ *              lev = nlev-k; col_location (col, 3), not flipped; no p3_tend_out (NULL); it = its = kts = 0, ite = ncol-1, kte = nlev-1
+ * Sizes: nlev*ncol; precip_liq_surf, precip_ice_surf ncol; precip_liq_flux, precip_ice_flux (nlev+1)*ncol; col_location 3*ncol.
+ * In/out: qc ... bm.  In: pres ... inv_qc_relvar, dpres, inv_exner, cld_frac_*, q_prev, t_prev, col_location.  Out: the rest.
+ * bulk_qi is the Fortran call's rho_qi, inv_exner its argument named exner; diag_eff_radius_qr and qr_evap_tend each exist in one of the
+ * two calls only.  do_predict_nc = do_prescribed_CCN = 1 (:412-413). */
+typedef struct pam_amd_p3_args_t {
+  int ncol, nlev;
+  double dt;
+  int it, its, ite, kts, kte;
+  int do_predict_nc, do_prescribed_CCN;
+  int layout, num_tend_out;
+  void *stream;   /* hipStream_t the coupling steps were enqueued on; p3_main must order its work after it */
+  double *qc, *nc, *qr, *nr, *th_atm, *qv, *qi, *qm, *ni, *bm, *pres, *dz, *nc_nuceat_tend, *nccn_prescribed, *ni_activated, *inv_qc_relvar;
+  double *precip_liq_surf, *precip_ice_surf, *diag_eff_radius_qc, *diag_eff_radius_qi, *diag_eff_radius_qr, *bulk_qi, *precip_total_tend,
+      *nevapr, *qr_evap_tend, *dpres, *inv_exner, *qv2qi_depos_tend, *precip_liq_flux, *precip_ice_flux, *cld_frac_r, *cld_frac_l,
+      *cld_frac_i, *p3_tend_out, *mu_c, *lamc, *liq_ice_exchange, *vap_liq_exchange, *vap_ice_exchange, *q_prev, *t_prev, *col_location;
+  double *exner;
+} pam_amd_p3_args_t;
+
+/* What Microphysics::set_p3_main takes: 0 = success.  `args->stream` carries the work of the pack step; the unpack step is enqueued on
+ * the same stream right after the call returns. */
+typedef int (*pam_amd_p3_main_fn)(const pam_amd_p3_args_t *args, void *user);
+
+/* The workspace: ONE device allocation that holds every array of pam_amd_p3_args_t, made once; nothing is allocated per step (the
+ * reference makes about 40 allocations and up to 36 device copies per step).
+ *   nens, nx, ny, nz >= 1 (ncol = ny*nx*nens below 2^31), layout 0 or 1, num_tend_out 0 ... 49 and 0 in layout 1 (0: p3_tend_out = NULL).
+ * The arrays lie in the order of the struct, each rounded up to a multiple of 8 doubles, with a guard of 8 doubles before the first,
+ * between any two and after the last: with N = ncol, Z = nz, T = num_tend_out and r(n) = n rounded up to a multiple of 8,
+ *   doubles = 37 r(Z N) + 2 r(N) + 2 r((Z+1) N) + r(3 N) + 43 * 8  [+ r(T Z N) + 8 where T > 0]          bytes = 8 * doubles
+ * The guards and the roundings hold the canary word 0x7ff850335f57535f (a quiet NaN) from creation on: a write outside an array shows. */
+int pam_amd_p3_workspace_create(int nens, int nx, int ny, int nz, int layout, int num_tend_out, void **ws);
+/* Fills *args with the sizes, the indices of the layout, the flags and the pointers; dt = 0 and stream = NULL are the caller's to set. */
+int pam_amd_p3_workspace_args(void *ws, pam_amd_p3_args_t *args);
+int pam_amd_p3_workspace_bytes(void *ws, long long *bytes);
+int pam_amd_p3_workspace_destroy(void *ws);   /* NULL: nothing to do */
+
+/* Microphysics.h:273-409 (and the transposing copy-in of :424-488 in layout 1) in ONE launch: the saturation adjustment where
+ * adjust != 0, the coupler state to every input of p3_main in the workspace's layout; no dz array, no scratch.  DEVICE arrays,
+ * (nz,ny,nx,nens) unless noted:
+ *   rho_d                 "density_dry", read only
+ *   rho_v, rho_c, temp    "water_vapor", "cloud_water", "temp": IN/OUT where adjust != 0 (the reference's `! sgs_shoc`): a cell in the
+ *                         condensation or the evaporation branch is adjusted, a cell in neither is NOT WRITTEN; read only otherwise.
+ *                         The bisection is the class's own copy (:769-852) with rho = rho_d + rho_v and std::max clamps; it is capped at
+ *                         2048 iterations like pam_amd_saturation_adjustment (never binds where the reference terminates)
+ *   tracers               HOST array of the seven DEVICE pointers cloud_water_num, rain, rain_num, ice, ice_num, ice_rime, ice_rime_vol
+ *   nccn_prescribed, nc_nuceat_tend, ni_activated, q_prev, t_prev        read only
+ *   zint                  (nz+1,nens), read as (k, col % nens)
+ *   first_step != 0       q_prev = qv, t_prev = temp (after the adjustment) in the workspace (:379-385)
+ *   R_d, R_v, cp_d, cp_l, p0, grav     the Microphysics class's constants (:75-87), finite and positive; cp_v finite
+ * Deviations, none with a consequence after a completed step: the coupler's q_prev / t_prev are READ ONLY here -- the reference
+ * overwrites q_prev with a mixing ratio between its two kernels (:384); only the workspace copy takes that value, so a p3_main that
+ * fails leaves the coupler state meaningful, and unpack writes both as the reference does.  All three rows of col_location are
+ * written as 1; the reference leaves rows >= nz uninitialised where nz < 3 (:377).  cld_frac_l/i/r and inv_qc_relvar are rewritten
+ * as 1 on every call (both branches of :388-409): p3_main is foreign code and gets what the reference gives it.
+ * The plain arguments are checked first, then the workspace, then the tracer pointers, all before the first HIP call.  The FIRST pack
+ * on a device builds the 3.5 KB of pow tables the Kessler kernels share; from then on a call allocates nothing. */
+int pam_amd_p3_pack(void *ws, const double *rho_d, double *rho_v, double *rho_c, double *temp, const double *const *tracers,
+                    const double *nccn_prescribed, const double *nc_nuceat_tend, const double *ni_activated, const double *q_prev,
+                    const double *t_prev, const double *zint, int adjust, int first_step, double R_d, double R_v, double cp_d, double cp_v,
+                    double cp_l, double p0, double grav, void *stream);
+
+/* Microphysics.h:680-717 (and the transposing copy-out of :540-564 in layout 1) in ONE launch: the ten in/out arrays, exner and the
+ * three exchange tendencies of the workspace back to the coupler state, and the (ny,nx,nens) precipitation rates.  rho_d: in.  temp:
+ * in/out (temp_old + (th_atm*exner - temp_old)*cv_d/cp_d).  rho_v, rho_c, tracers[7], q_prev, t_prev, *_exchange_out,
+ * precip_*_surf_out: out.  cp_d, cv_d finite and positive. */
+int pam_amd_p3_unpack(void *ws, const double *rho_d, double *rho_v, double *rho_c, double *const *tracers, double *temp, double *q_prev,
+                      double *t_prev, double *liq_ice_exchange_out, double *vap_liq_exchange_out, double *vap_ice_exchange_out,
+                      double *precip_liq_surf_out, double *precip_ice_surf_out, double cp_d, double cv_d, void *stream);
+
+/* A TEST DOUBLE for p3_main, not physics (pam_amd/csrc/p3_device.h: standin_column), as a pam_amd_p3_main_fn: one launch on
+ * args->stream, both layouts.  `user` is ignored. */
+int pam_amd_p3_main_standin(const pam_amd_p3_args_t *args, void *user);
+
+/* For tests: on != 0 makes pack, unpack and the stand-in launch their 64-bit-index instances whatever the size (they are otherwise chosen
+ * from 2^29 elements in the largest array, p3_tend_out included, on); 0 restores the choice by size.  Process-wide; same bits either way. */
+int pam_amd_p3_debug_wide_index(int on);
+
 #ifdef __cplusplus
 }
 #endif

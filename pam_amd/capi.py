@@ -50,6 +50,24 @@ class ShocArgs(C.Structure):
 SHOC_MAIN_FN = C.CFUNCTYPE(C.c_int, C.POINTER(ShocArgs), C.c_void_p)
 
 
+# pam_amd_p3_args_t (include/pam_amd_modules.h): the arguments of p3_main_fortran / pam::p3_main_cxx under their names, plus exner
+P3_ARRAYS = ("qc", "nc", "qr", "nr", "th_atm", "qv", "qi", "qm", "ni", "bm", "pres", "dz", "nc_nuceat_tend", "nccn_prescribed", "ni_activated",
+             "inv_qc_relvar", "precip_liq_surf", "precip_ice_surf", "diag_eff_radius_qc", "diag_eff_radius_qi", "diag_eff_radius_qr", "bulk_qi",
+             "precip_total_tend", "nevapr", "qr_evap_tend", "dpres", "inv_exner", "qv2qi_depos_tend", "precip_liq_flux", "precip_ice_flux",
+             "cld_frac_r", "cld_frac_l", "cld_frac_i", "p3_tend_out", "mu_c", "lamc", "liq_ice_exchange", "vap_liq_exchange", "vap_ice_exchange",
+             "q_prev", "t_prev", "col_location", "exner")
+
+
+class P3Args(C.Structure):
+    _fields_ = [("ncol", C.c_int), ("nlev", C.c_int), ("dt", C.c_double), ("it", C.c_int), ("its", C.c_int), ("ite", C.c_int),
+                ("kts", C.c_int), ("kte", C.c_int), ("do_predict_nc", C.c_int), ("do_prescribed_CCN", C.c_int), ("layout", C.c_int),
+                ("num_tend_out", C.c_int), ("stream", C.c_void_p)] + [(n, C.c_void_p) for n in P3_ARRAYS]
+
+
+# pam_amd_p3_main_fn
+P3_MAIN_FN = C.CFUNCTYPE(C.c_int, C.POINTER(P3Args), C.c_void_p)
+
+
 # every symbol include/pam_amd_awfl.h declares (tests/test_capi_symbols.py checks the header against this list)
 SYMBOLS = {
     "pam_amd_awfl_abi_version": (C.c_int, []),
@@ -150,6 +168,14 @@ MODULE_SYMBOLS = {
     "pam_amd_shoc_unpack": (C.c_int, [C.c_void_p] * 8 + [C.POINTER(C.c_void_p)] + [C.c_void_p] * 5 + [C.c_double] * 3 + [C.c_void_p]),
     "pam_amd_shoc_main_standin": (C.c_int, [C.POINTER(ShocArgs), C.c_void_p]),
     "pam_amd_shoc_debug_wide_index": (C.c_int, [C.c_int]),
+    "pam_amd_p3_workspace_create": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_void_p)]),
+    "pam_amd_p3_workspace_args": (C.c_int, [C.c_void_p, C.POINTER(P3Args)]),
+    "pam_amd_p3_workspace_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "pam_amd_p3_workspace_destroy": (C.c_int, [C.c_void_p]),
+    "pam_amd_p3_pack": (C.c_int, [C.c_void_p] * 5 + [C.POINTER(C.c_void_p)] + [C.c_void_p] * 6 + [C.c_int] * 2 + [C.c_double] * 7 + [C.c_void_p]),
+    "pam_amd_p3_unpack": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)] + [C.c_void_p] * 8 + [C.c_double] * 2 + [C.c_void_p]),
+    "pam_amd_p3_main_standin": (C.c_int, [C.POINTER(P3Args), C.c_void_p]),
+    "pam_amd_p3_debug_wide_index": (C.c_int, [C.c_int]),
 }
 
 

@@ -24,6 +24,7 @@
 #include "validate_device.h"         // DataManager::validate: classification, a thread's walk and the fold, the same
 #include "diagnostics_device.h"      // field diagnostics: the per-element update, a thread's share of a chunk and the folds, the same
 #include "shoc_device.h"             // the SHOC coupling layer: pack, unpack, the index and the stand-in for shoc_main, the same
+#include "p3_device.h"               // the P3 coupling layer: the adjustment, pack, unpack, the index and the stand-in for p3_main
 
 namespace {
 
@@ -2469,5 +2470,390 @@ extern "C" int pam_amd_shoc_main_standin(const pam_amd_shoc_args_t *args, void *
   const dim3 grid((unsigned)((A.ncol + 63) / 64)), block(64);
   if (!g_shoc_force_wide && largest < SHOC_NARROW) hipLaunchKernelGGL((shoc_standin_kernel<unsigned>), grid, block, 0, (hipStream_t)A.stream, A);
   else hipLaunchKernelGGL((shoc_standin_kernel<long long>), grid, block, 0, (hipStream_t)A.stream, A);
+  return stats_launch_check(who);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The P3 coupling layer (physics/micro/p3/Microphysics.h:214-741): pack = the saturation adjustment (where SHOC is not the SGS) and the
+// coupler state to every input of p3_main, unpack = its outputs back with the precipitation rates, one launch each; the arithmetic lives
+// in p3_device.h.  A thread owns one cell (k, col), lanes run along col, so every access to the coupler state is a coalesced row; no cell
+// needs another, so both kernels run on a grid of (column tiles, level tiles).
+//   layout 0 ((lev, col), column fastest, not flipped): tiles of 64 columns x 4 levels, the P3 arrays are written / read directly.
+//   layout 1 ((col, lev), level fastest, flipped): tiles of 16 columns x 16 levels through LDS tiles [col][lev] of pitch 17 doubles, P3_GROUP
+//   arrays per pair of barriers -- the scheme of the SHOC kernels above, with the bank reasoning given there (derived, not measured).  The four
+//   constant arrays need no LDS: the transposed role of a thread writes them as 128-byte rows.
+// The ADJUST = 0 instances of the pack kernel (SHOC as the SGS) carry none of the bisection.  The tables of pow_pos_fast are staged once per
+// workgroup.
+namespace {
+namespace p3 = pama::p3;
+constexpr int P3_THREADS = 256;
+constexpr int P3_GROUP = 8;
+constexpr long long P3_NARROW = 1ll << 29;   // the largest array from this size on: the long long instances
+constexpr unsigned long long P3_CANARY = 0x7ff850335f57535full;
+constexpr int P3_GUARD = 8;                  // doubles
+constexpr int P3_NARRAYS = 43;
+template <int LAYOUT> struct P3Tile { static constexpr int TC = LAYOUT ? 16 : 64, TL = P3_THREADS / TC, PITCH = TL + 1; };
+
+struct P3State {
+  const double *rho_d;
+  double *rho_v, *rho_c, *temp;   // written only by the ADJUST instances
+  const double *q[p3::NTRACERS];
+  const double *nccn_prescribed, *nc_nuceat_tend, *ni_activated, *q_prev, *t_prev, *zint;
+};
+struct P3CellDst { double *p[p3::C_MAX]; double *one[4]; double *col_location; };
+struct P3CellSrc { const double *p[p3::U_MAX]; const double *precip_liq_surf, *precip_ice_surf; };
+struct P3StateOut { double *p[p3::S_MAX]; const double *rho_d; double *precip_liq_surf_out, *precip_ice_surf_out; };
+
+// grid (column tiles, level tiles)
+template <int LAYOUT, class IDX, bool ADJUST>
+__global__ void __launch_bounds__(P3_THREADS) p3_pack_kernel(P3State S, P3CellDst D, int ncol_, int nens, int nz, int first_step, p3::Consts c,
+                                                             const PowTab *__restrict__ tab) {
+  using T = P3Tile<LAYOUT>;
+  constexpr int TC = T::TC, TL = T::TL, PITCH = T::PITCH;
+  __shared__ PowTab sh_tab;
+  __shared__ double sh_t[LAYOUT ? P3_GROUP * TC * PITCH : 1];
+  kessler_stage_tab(tab, &sh_tab);
+  const int tc = (int)threadIdx.x % TC, tl = (int)threadIdx.x / TC;
+  const IDX ncol = (IDX)ncol_;
+  const long long col_ll = (long long)blockIdx.x * TC + tc;
+  const bool col_ok = col_ll < ncol_;
+  const IDX col = (IDX)(col_ok ? col_ll : ncol_ - 1);
+  const int k = (int)blockIdx.y * TL + tl;
+  const bool cell_ok = col_ok && k < nz;
+  if (blockIdx.y == 0 && tl == 0 && col_ok) {   // Microphysics.h:377; every row, see the header
+#pragma unroll
+    for (int r = 0; r < 3; r++) D.col_location[p3::offset_t<IDX>(LAYOUT, col, 0, ncol, 1, r, 3)] = 1;
+  }
+  double v[p3::C_MAX];
+#pragma unroll
+  for (int a = 0; a < p3::C_MAX; a++) v[a] = 0;
+  if (cell_ok) {
+    const IDX o = (IDX)k * ncol + col;
+    const int e = (int)(col % (IDX)nens);
+    p3::CellIn in;
+    in.rho_d = S.rho_d[o]; in.rho_v = S.rho_v[o]; in.rho_c = S.rho_c[o]; in.temp = S.temp[o];
+#pragma unroll
+    for (int tr = 0; tr < p3::NTRACERS; tr++) in.q[tr] = S.q[tr][o];
+    in.nccn_prescribed = S.nccn_prescribed[o]; in.nc_nuceat_tend = S.nc_nuceat_tend[o]; in.ni_activated = S.ni_activated[o];
+    in.q_prev = S.q_prev[o]; in.t_prev = S.t_prev[o];
+    in.zint_k = S.zint[(IDX)k * (IDX)nens + (IDX)e];
+    in.zint_k1 = S.zint[(IDX)(k + 1) * (IDX)nens + (IDX)e];
+    const int it = p3::pack_cell<ADJUST>(in, first_step != 0, c, &sh_tab, v);
+    if (ADJUST && it > 0) { S.rho_v[o] = in.rho_v; S.rho_c[o] = in.rho_c; S.temp[o] = in.temp; }
+  }
+  if constexpr (LAYOUT == 0) {
+    if (cell_ok) {
+#pragma unroll
+      for (int a = 0; a < p3::C_MAX; a++) D.p[a][p3::offset_t<IDX>(0, col, k, ncol, nz)] = v[a];
+#pragma unroll
+      for (int a = 0; a < 4; a++) D.one[a][p3::offset_t<IDX>(0, col, k, ncol, nz)] = 1;
+    }
+  } else {
+    // the transposed role of a thread: lanes along the level
+    const int tl2 = (int)threadIdx.x % TL, tc2 = (int)threadIdx.x / TL;
+    const long long col2_ll = (long long)blockIdx.x * TC + tc2;
+    const int k2 = (int)blockIdx.y * TL + tl2;
+    const bool ok2 = col2_ll < ncol_ && k2 < nz;
+    const IDX col2 = (IDX)(col2_ll < ncol_ ? col2_ll : ncol_ - 1);
+    const IDX o2 = p3::offset_t<IDX>(1, col2, ok2 ? k2 : 0, ncol, nz);
+    if (ok2) {
+#pragma unroll
+      for (int a = 0; a < 4; a++) D.one[a][o2] = 1;
+    }
+#pragma unroll
+    for (int g = 0; g < (p3::C_MAX + P3_GROUP - 1) / P3_GROUP; g++) {
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < P3_GROUP; j++)
+        if (g * P3_GROUP + j < p3::C_MAX) sh_t[(j * TC + tc) * PITCH + tl] = v[g * P3_GROUP + j < p3::C_MAX ? g * P3_GROUP + j : 0];
+      __syncthreads();
+      if (ok2) {
+#pragma unroll
+        for (int j = 0; j < P3_GROUP; j++)
+          if (g * P3_GROUP + j < p3::C_MAX) D.p[g * P3_GROUP + j < p3::C_MAX ? g * P3_GROUP + j : 0][o2] = sh_t[(j * TC + tc2) * PITCH + tl2];
+      }
+    }
+  }
+}
+
+// grid (column tiles, level tiles)
+template <int LAYOUT, class IDX>
+__global__ void __launch_bounds__(P3_THREADS) p3_unpack_kernel(P3CellSrc R, P3StateOut O, int ncol_, int nz, p3::Consts c) {
+  using T = P3Tile<LAYOUT>;
+  constexpr int TC = T::TC, TL = T::TL, PITCH = T::PITCH;
+  __shared__ double sh_t[LAYOUT ? P3_GROUP * TC * PITCH : 1];
+  const int tc = (int)threadIdx.x % TC, tl = (int)threadIdx.x / TC;
+  const IDX ncol = (IDX)ncol_;
+  const long long col_ll = (long long)blockIdx.x * TC + tc;
+  const int k = (int)blockIdx.y * TL + tl;
+  const bool col_ok = col_ll < ncol_, cell_ok = col_ok && k < nz;
+  const IDX col = (IDX)(col_ok ? col_ll : ncol_ - 1);
+  if (blockIdx.y == 0 && tl == 0 && col_ok) {   // Microphysics.h:713-717
+    O.precip_liq_surf_out[col] = R.precip_liq_surf[col];
+    O.precip_ice_surf_out[col] = R.precip_ice_surf[col];
+  }
+  double in[p3::U_MAX];
+#pragma unroll
+  for (int a = 0; a < p3::U_MAX; a++) in[a] = 0;
+  if constexpr (LAYOUT == 0) {
+    if (cell_ok) {
+#pragma unroll
+      for (int a = 0; a < p3::U_MAX; a++) in[a] = R.p[a][p3::offset_t<IDX>(0, col, k, ncol, nz)];
+    }
+  } else {
+    const int tl2 = (int)threadIdx.x % TL, tc2 = (int)threadIdx.x / TL;
+    const long long col2_ll = (long long)blockIdx.x * TC + tc2;
+    const int k2 = (int)blockIdx.y * TL + tl2;
+    const bool ok2 = col2_ll < ncol_ && k2 < nz;
+    const IDX col2 = (IDX)(col2_ll < ncol_ ? col2_ll : ncol_ - 1);
+    const IDX o2 = p3::offset_t<IDX>(1, col2, ok2 ? k2 : 0, ncol, nz);
+#pragma unroll
+    for (int g = 0; g < (p3::U_MAX + P3_GROUP - 1) / P3_GROUP; g++) {
+      __syncthreads();
+      if (ok2) {
+#pragma unroll
+        for (int j = 0; j < P3_GROUP; j++)
+          if (g * P3_GROUP + j < p3::U_MAX) sh_t[(j * TC + tc2) * PITCH + tl2] = R.p[g * P3_GROUP + j < p3::U_MAX ? g * P3_GROUP + j : 0][o2];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < P3_GROUP; j++)
+        if (g * P3_GROUP + j < p3::U_MAX) in[g * P3_GROUP + j < p3::U_MAX ? g * P3_GROUP + j : 0] = sh_t[(j * TC + tc) * PITCH + tl];
+    }
+  }
+  if (!cell_ok) return;
+  const IDX o = (IDX)k * ncol + col;
+  double out[p3::S_MAX];
+  p3::unpack_cell(in, O.p[p3::S_TEMP][o], O.rho_d[o], c, out);
+#pragma unroll
+  for (int a = 0; a < p3::S_MAX; a++) O.p[a][o] = out[a];
+}
+
+template <class IDX>
+__global__ void __launch_bounds__(64) p3_standin_kernel(pam_amd_p3_args_t A) {
+  const long long col = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (col < A.ncol) p3::standin_column<IDX>(A, (IDX)col);
+}
+
+__global__ void __launch_bounds__(256) p3_canary_kernel(unsigned long long *p, long long n) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) p[i] = P3_CANARY;
+}
+
+struct P3Workspace {
+  unsigned long long magic;
+  int nens, nx, ny, nz, layout, nout;
+  long long doubles;
+  double *base;
+  pam_amd_p3_args_t args;
+};
+constexpr unsigned long long P3_MAGIC = 0x5033434f55504c31ull;
+P3Workspace *p3_ws(void *ws) {
+  P3Workspace *w = (P3Workspace *)ws;
+  return (w && w->magic == P3_MAGIC) ? w : nullptr;
+}
+bool g_p3_force_wide = false;   // pam_amd_p3_debug_wide_index: tests run the long long instances at small sizes
+int p3_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
+// element count of the largest array: p3_tend_out where there is one, a flux array otherwise
+long long p3_largest(long long ncol, long long nz, long long nout) { return std::max(std::max<long long>(nout, 1) * nz * ncol, (nz + 1) * ncol); }
+// every array of the struct, in its order
+void p3_pointers(pam_amd_p3_args_t &A, double **(&ptr)[P3_NARRAYS]) {
+  double **p[P3_NARRAYS] = {&A.qc, &A.nc, &A.qr, &A.nr, &A.th_atm, &A.qv, &A.qi, &A.qm, &A.ni, &A.bm, &A.pres, &A.dz, &A.nc_nuceat_tend,
+                            &A.nccn_prescribed, &A.ni_activated, &A.inv_qc_relvar, &A.precip_liq_surf, &A.precip_ice_surf, &A.diag_eff_radius_qc,
+                            &A.diag_eff_radius_qi, &A.diag_eff_radius_qr, &A.bulk_qi, &A.precip_total_tend, &A.nevapr, &A.qr_evap_tend, &A.dpres,
+                            &A.inv_exner, &A.qv2qi_depos_tend, &A.precip_liq_flux, &A.precip_ice_flux, &A.cld_frac_r, &A.cld_frac_l, &A.cld_frac_i,
+                            &A.p3_tend_out, &A.mu_c, &A.lamc, &A.liq_ice_exchange, &A.vap_liq_exchange, &A.vap_ice_exchange, &A.q_prev, &A.t_prev,
+                            &A.col_location, &A.exner};
+  for (int i = 0; i < P3_NARRAYS; i++) ptr[i] = p[i];
+}
+// the sizes of the arrays, in the order of the struct's pointers
+void p3_sizes(long long N, long long Z, long long T, long long (&n)[P3_NARRAYS]) {
+  for (int i = 0; i < P3_NARRAYS; i++) n[i] = Z * N;
+  n[16] = n[17] = N;              // precip_liq_surf, precip_ice_surf
+  n[28] = n[29] = (Z + 1) * N;    // precip_liq_flux, precip_ice_flux
+  n[33] = T * Z * N;              // p3_tend_out
+  n[41] = 3 * N;                  // col_location
+}
+}  // namespace
+
+extern "C" int pam_amd_p3_debug_wide_index(int on) {
+  g_p3_force_wide = on != 0;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_p3_workspace_create(int nens, int nx, int ny, int nz, int layout, int num_tend_out, void **ws) {
+  const char *who = "p3_workspace_create";
+  if (!ws) return p3_error(who, "null ws");
+  *ws = nullptr;
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return p3_error(who, "nens, nx, ny and nz must be >= 1");
+  if (layout != 0 && layout != 1) return p3_error(who, "layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)");
+  if (num_tend_out < 0 || num_tend_out > p3::MAX_TEND_OUT) return p3_error(who, "num_tend_out must be 0 ... 49");
+  if (layout == 1 && num_tend_out != 0) return p3_error(who, "num_tend_out must be 0 in layout 1 (pam::p3_main_cxx has no p3_tend_out)");
+  const long long ncol = (long long)ny * nx * nens;
+  if (ncol > 0x7fffffffLL - 64 || nz > 0x7ffffff0) return p3_error(who, "ny x nx x nens must stay below 2^31");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  long long n[P3_NARRAYS], total = P3_GUARD;
+  p3_sizes(ncol, nz, num_tend_out, n);
+  for (int i = 0; i < P3_NARRAYS; i++)
+    if (n[i] > 0) total += shoc_round8(n[i]) + P3_GUARD;
+  double *base = nullptr;
+  if (hipMalloc((void **)&base, (size_t)total * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "p3_workspace_create: cannot allocate the workspace");
+  }
+  hipLaunchKernelGGL(p3_canary_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, 0,
+                     (unsigned long long *)base, total);
+  if (hipDeviceSynchronize() != hipSuccess) {
+    (void)hipFree(base);
+    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": " + hipGetErrorString(hipGetLastError())).c_str());
+  }
+  P3Workspace *w = new P3Workspace();
+  w->magic = P3_MAGIC;
+  w->nens = nens; w->nx = nx; w->ny = ny; w->nz = nz; w->layout = layout; w->nout = num_tend_out;
+  w->doubles = total;
+  w->base = base;
+  pam_amd_p3_args_t &A = w->args;
+  A.ncol = (int)ncol; A.nlev = nz; A.dt = 0; A.layout = layout; A.num_tend_out = num_tend_out; A.stream = nullptr;
+  A.do_predict_nc = A.do_prescribed_CCN = 1;                        // Microphysics.h:412-413
+  if (layout == 0) { A.it = A.its = A.kts = 1; A.ite = (int)ncol; A.kte = nz; }               // :568-572
+  else { A.it = A.its = A.kts = 0; A.ite = (int)ncol - 1; A.kte = nz - 1; }                   // :417-421
+  double **ptr[P3_NARRAYS];
+  p3_pointers(A, ptr);
+  long long at = P3_GUARD;
+  for (int i = 0; i < P3_NARRAYS; i++) {
+    *ptr[i] = n[i] > 0 ? base + at : nullptr;
+    if (n[i] > 0) at += shoc_round8(n[i]) + P3_GUARD;
+  }
+  *ws = w;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_p3_workspace_args(void *ws, pam_amd_p3_args_t *args) {
+  P3Workspace *w = p3_ws(ws);
+  if (!w) return p3_error("p3_workspace_args", "not a workspace of p3_workspace_create");
+  if (!args) return p3_error("p3_workspace_args", "null args");
+  *args = w->args;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_p3_workspace_bytes(void *ws, long long *bytes) {
+  P3Workspace *w = p3_ws(ws);
+  if (!w) return p3_error("p3_workspace_bytes", "not a workspace of p3_workspace_create");
+  if (!bytes) return p3_error("p3_workspace_bytes", "null bytes");
+  *bytes = w->doubles * (long long)sizeof(double);
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_p3_workspace_destroy(void *ws) {
+  if (!ws) return PAM_AMD_OK;
+  P3Workspace *w = p3_ws(ws);
+  if (!w) return p3_error("p3_workspace_destroy", "not a workspace of p3_workspace_create");
+  (void)hipFree(w->base);
+  w->magic = 0;
+  delete w;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_p3_pack(void *ws, const double *rho_d, double *rho_v, double *rho_c, double *temp, const double *const *tracers,
+                               const double *nccn_prescribed, const double *nc_nuceat_tend, const double *ni_activated, const double *q_prev,
+                               const double *t_prev, const double *zint, int adjust, int first_step, double R_d, double R_v, double cp_d,
+                               double cp_v, double cp_l, double p0, double grav, void *stream) {
+  const char *who = "p3_pack";
+  if (!rho_d || !rho_v || !rho_c || !temp || !nccn_prescribed || !nc_nuceat_tend || !ni_activated || !q_prev || !t_prev || !zint)
+    return p3_error(who, "null pointer");
+  if (!shoc_pos(R_d) || !shoc_pos(R_v) || !shoc_pos(cp_d) || !shoc_pos(cp_l) || !shoc_pos(p0) || !shoc_pos(grav) || !std::isfinite(cp_v))
+    return p3_error(who, "R_d, R_v, cp_d, cp_l, p0 and grav must be finite and positive, cp_v finite");
+  P3Workspace *w = p3_ws(ws);
+  if (!w) return p3_error(who, "not a workspace of p3_workspace_create");
+  if (!tracers) return p3_error(who, "null tracers");
+  for (int tr = 0; tr < p3::NTRACERS; tr++)
+    if (!tracers[tr]) return p3_error(who, "null pointer in tracers");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  const PowTab *tab = kessler_pow_tab(w->base);
+  if (!tab) return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "p3_pack: cannot allocate the pow tables");
+  const pam_amd_p3_args_t &A = w->args;
+  P3State S = {rho_d, rho_v, rho_c, temp, {}, nccn_prescribed, nc_nuceat_tend, ni_activated, q_prev, t_prev, zint};
+  for (int tr = 0; tr < p3::NTRACERS; tr++) S.q[tr] = tracers[tr];
+  P3CellDst D = {};
+  D.p[p3::C_QC] = A.qc; D.p[p3::C_NC] = A.nc; D.p[p3::C_QR] = A.qr; D.p[p3::C_NR] = A.nr; D.p[p3::C_TH_ATM] = A.th_atm; D.p[p3::C_QV] = A.qv;
+  D.p[p3::C_QI] = A.qi; D.p[p3::C_QM] = A.qm; D.p[p3::C_NI] = A.ni; D.p[p3::C_BM] = A.bm; D.p[p3::C_PRES] = A.pres; D.p[p3::C_DZ] = A.dz;
+  D.p[p3::C_NC_NUCEAT_TEND] = A.nc_nuceat_tend; D.p[p3::C_NCCN_PRESCRIBED] = A.nccn_prescribed; D.p[p3::C_NI_ACTIVATED] = A.ni_activated;
+  D.p[p3::C_DPRES] = A.dpres; D.p[p3::C_INV_EXNER] = A.inv_exner; D.p[p3::C_Q_PREV] = A.q_prev; D.p[p3::C_T_PREV] = A.t_prev;
+  D.p[p3::C_EXNER] = A.exner;
+  D.one[0] = A.cld_frac_l; D.one[1] = A.cld_frac_i; D.one[2] = A.cld_frac_r; D.one[3] = A.inv_qc_relvar;
+  D.col_location = A.col_location;
+  const p3::Consts c = {R_d, R_v, cp_d, cp_v, cp_l, p0, grav, 0.0};
+  const bool narrow = !g_p3_force_wide && p3_largest(A.ncol, w->nz, w->nout) < P3_NARROW;
+  hipStream_t s = (hipStream_t)stream;
+#define P3_PACK(LAYOUT, IDX, ADJ)                                                                                                         \
+  hipLaunchKernelGGL((p3_pack_kernel<LAYOUT, IDX, ADJ>), dim3((unsigned)((A.ncol + P3Tile<LAYOUT>::TC - 1) / P3Tile<LAYOUT>::TC),          \
+                                                              (unsigned)((w->nz + P3Tile<LAYOUT>::TL - 1) / P3Tile<LAYOUT>::TL)),          \
+                     dim3(P3_THREADS), 0, s, S, D, A.ncol, w->nens, w->nz, first_step, c, tab)
+#define P3_PACK_I(LAYOUT, ADJ) do { if (narrow) P3_PACK(LAYOUT, unsigned, ADJ); else P3_PACK(LAYOUT, long long, ADJ); } while (0)
+  if (w->layout == 0) { if (adjust) P3_PACK_I(0, true); else P3_PACK_I(0, false); }
+  else { if (adjust) P3_PACK_I(1, true); else P3_PACK_I(1, false); }
+#undef P3_PACK_I
+#undef P3_PACK
+  return stats_launch_check(who);
+}
+
+extern "C" int pam_amd_p3_unpack(void *ws, const double *rho_d, double *rho_v, double *rho_c, double *const *tracers, double *temp,
+                                 double *q_prev, double *t_prev, double *liq_ice_exchange_out, double *vap_liq_exchange_out,
+                                 double *vap_ice_exchange_out, double *precip_liq_surf_out, double *precip_ice_surf_out, double cp_d,
+                                 double cv_d, void *stream) {
+  const char *who = "p3_unpack";
+  if (!rho_d || !rho_v || !rho_c || !temp || !q_prev || !t_prev || !liq_ice_exchange_out || !vap_liq_exchange_out || !vap_ice_exchange_out ||
+      !precip_liq_surf_out || !precip_ice_surf_out)
+    return p3_error(who, "null pointer");
+  if (!shoc_pos(cp_d) || !shoc_pos(cv_d)) return p3_error(who, "cp_d and cv_d must be finite and positive");
+  P3Workspace *w = p3_ws(ws);
+  if (!w) return p3_error(who, "not a workspace of p3_workspace_create");
+  if (!tracers) return p3_error(who, "null tracers");
+  for (int tr = 0; tr < p3::NTRACERS; tr++)
+    if (!tracers[tr]) return p3_error(who, "null pointer in tracers");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  const pam_amd_p3_args_t &A = w->args;
+  P3CellSrc R = {};
+  R.p[p3::U_QC] = A.qc; R.p[p3::U_NC] = A.nc; R.p[p3::U_QR] = A.qr; R.p[p3::U_NR] = A.nr; R.p[p3::U_QI] = A.qi; R.p[p3::U_NI] = A.ni;
+  R.p[p3::U_QM] = A.qm; R.p[p3::U_BM] = A.bm; R.p[p3::U_QV] = A.qv; R.p[p3::U_TH_ATM] = A.th_atm; R.p[p3::U_EXNER] = A.exner;
+  R.p[p3::U_LIQ_ICE] = A.liq_ice_exchange; R.p[p3::U_VAP_LIQ] = A.vap_liq_exchange; R.p[p3::U_VAP_ICE] = A.vap_ice_exchange;
+  R.precip_liq_surf = A.precip_liq_surf; R.precip_ice_surf = A.precip_ice_surf;
+  P3StateOut O = {};
+  // tracers: cloud_water_num, rain, rain_num, ice, ice_num, ice_rime, ice_rime_vol
+  O.p[p3::S_RHO_C] = rho_c; O.p[p3::S_RHO_NC] = tracers[0]; O.p[p3::S_RHO_R] = tracers[1]; O.p[p3::S_RHO_NR] = tracers[2];
+  O.p[p3::S_RHO_I] = tracers[3]; O.p[p3::S_RHO_NI] = tracers[4]; O.p[p3::S_RHO_M] = tracers[5]; O.p[p3::S_RHO_BM] = tracers[6];
+  O.p[p3::S_RHO_V] = rho_v; O.p[p3::S_TEMP] = temp; O.p[p3::S_Q_PREV] = q_prev; O.p[p3::S_T_PREV] = t_prev;
+  O.p[p3::S_LIQ_ICE] = liq_ice_exchange_out; O.p[p3::S_VAP_LIQ] = vap_liq_exchange_out; O.p[p3::S_VAP_ICE] = vap_ice_exchange_out;
+  O.rho_d = rho_d; O.precip_liq_surf_out = precip_liq_surf_out; O.precip_ice_surf_out = precip_ice_surf_out;
+  const p3::Consts c = {0.0, 0.0, cp_d, 0.0, 0.0, 0.0, 0.0, cv_d};
+  const bool narrow = !g_p3_force_wide && p3_largest(A.ncol, w->nz, w->nout) < P3_NARROW;
+  hipStream_t s = (hipStream_t)stream;
+#define P3_UNPACK(LAYOUT, IDX)                                                                                                            \
+  hipLaunchKernelGGL((p3_unpack_kernel<LAYOUT, IDX>), dim3((unsigned)((A.ncol + P3Tile<LAYOUT>::TC - 1) / P3Tile<LAYOUT>::TC),            \
+                                                          (unsigned)((w->nz + P3Tile<LAYOUT>::TL - 1) / P3Tile<LAYOUT>::TL)),             \
+                     dim3(P3_THREADS), 0, s, R, O, A.ncol, w->nz, c)
+  if (w->layout == 0) { if (narrow) P3_UNPACK(0, unsigned); else P3_UNPACK(0, long long); }
+  else { if (narrow) P3_UNPACK(1, unsigned); else P3_UNPACK(1, long long); }
+#undef P3_UNPACK
+  return stats_launch_check(who);
+}
+
+extern "C" int pam_amd_p3_main_standin(const pam_amd_p3_args_t *args, void *user) {
+  (void)user;
+  const char *who = "p3_main_standin";
+  if (!args) return p3_error(who, "null args");
+  pam_amd_p3_args_t A = *args;
+  if (A.ncol < 1 || A.nlev < 1) return p3_error(who, "ncol and nlev must be >= 1");
+  if (A.ncol > 0x7fffffff - 64 || A.nlev > 0x7ffffff0) return p3_error(who, "ncol must stay below 2^31 - 64");
+  if (A.layout != 0 && A.layout != 1) return p3_error(who, "layout must be 0 or 1");
+  if (A.num_tend_out < 0 || A.num_tend_out > p3::MAX_TEND_OUT || (A.layout == 1 && A.num_tend_out)) return p3_error(who, "num_tend_out must be 0 ... 49, 0 in layout 1");
+  double **ptr[P3_NARRAYS];
+  p3_pointers(A, ptr);
+  for (int i = 0; i < P3_NARRAYS; i++)
+    if (!*ptr[i] && !(i == 33 && A.num_tend_out == 0)) return p3_error(who, "null pointer in args");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  const dim3 grid((unsigned)((A.ncol + 63) / 64)), block(64);
+  if (!g_p3_force_wide && p3_largest(A.ncol, A.nlev, A.num_tend_out) < P3_NARROW)
+    hipLaunchKernelGGL((p3_standin_kernel<unsigned>), grid, block, 0, (hipStream_t)A.stream, A);
+  else hipLaunchKernelGGL((p3_standin_kernel<long long>), grid, block, 0, (hipStream_t)A.stream, A);
   return stats_launch_check(who);
 }

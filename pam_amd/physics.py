@@ -5,6 +5,7 @@
   SGSNone           physics/sgs/none/SGS.h
   SGSShoc           physics/sgs/shoc/SGS.h                 the coupling layer around shoc_main; SHOC itself is handed in by the caller
   MicrophysicsNone  physics/micro/none/Microphysics.h      registers and zeroes "water_vapor", sets the constants
+  MicrophysicsP3    physics/micro/p3/Microphysics.h        the coupling layer around p3_main; P3 itself is handed in by the caller
 
 Arithmetic is in libpam_amd_awfl.so (pam_amd/csrc/modules_kernels.hip); there is no CPU path.  Deviations from the reference
 (DESIGN.md section 8): the sizes come from the coupler's own getters (options ncrms / crm_nz / crm_nx / crm_ny must agree where they
@@ -344,3 +345,197 @@ class MicrophysicsNone:
 
     def finalize(self, coupler):
         pass
+
+
+def p3_shapes(ncol, nz, layout, num_tend_out=0):
+    """name -> shape of every array of pam_amd_p3_args_t (include/pam_amd_modules.h) in layout 0 ((lev, col), column fastest, not flipped)
+    or 1 (SCREAM's (col, lev), level fastest, flipped).  p3_tend_out has no elements where num_tend_out = 0 (its pointer is NULL)."""
+    out = {}
+    for n in capi.P3_ARRAYS:
+        if n in ("precip_liq_surf", "precip_ice_surf"):
+            out[n] = (ncol,)
+        elif n in ("precip_liq_flux", "precip_ice_flux"):
+            out[n] = (nz + 1, ncol) if layout == 0 else (ncol, nz + 1)
+        elif n == "col_location":
+            out[n] = (3, ncol) if layout == 0 else (ncol, 3)
+        elif n == "p3_tend_out":
+            out[n] = (num_tend_out, nz, ncol) if layout == 0 else (ncol, num_tend_out, nz)
+        else:
+            out[n] = (nz, ncol) if layout == 0 else (ncol, nz)
+    return out
+
+
+class MicrophysicsP3:
+    """physics/micro/p3/Microphysics.h: the coupling layer around P3 -- the saturation adjustment where SHOC is not the SGS and pack
+    (Microphysics.h:273-409), p3_main, unpack (:680-717) -- as two fused launches on the current stream.  P3 itself, its lookup tables and
+    micro_p3_utils_init are not part of this library (option p3_lookup_data_path is not read): `p3_main` is
+
+      * a C function pointer of type pam_amd_p3_main_fn (a ctypes function, e.g. MicrophysicsP3.standin(), or an address), called with
+        the pam_amd_p3_args_t of the workspace and `user`, or
+      * a Python callable f(arrays, args): arrays maps every name of pam_amd_p3_args_t to a torch view of the workspace in `layout`
+        (p3_shapes), args is the capi.P3Args; it works in place on the current stream.
+
+    layout 1 is SCREAM's C++ layout (col, lev), flipped; layout 0 the reference's Fortran-call layout (lev, col), where num_tend_out
+    (default 49) planes of p3_tend_out exist.  The PAM_DEBUG mass check and the unused get_cloud_fraction are not provided."""
+    ID_C, ID_NC, ID_R, ID_NR, ID_I, ID_M, ID_NI, ID_BM, ID_V = range(9)                                     # Microphysics.h:61-69
+    # Microphysics.h:75-87 (cv_v = R_v - cp_v as written there)
+    R_d, cp_d, R_v, cp_v, p0, grav, cp_l = 287.042, 1004.64, 461.505, 1859.0, 1.0e5, 9.80616, 4188.0
+    cv_d = cp_d - R_d
+    gamma_d, kappa_d, cv_v = cp_d / cv_d, R_d / cp_d, R_v - cp_v
+    latvap, latice = 2501000.0, 333700.0                                                                    # :175-176
+    TRACERS = (("cloud_water", "Cloud Water Mass", True, True), ("cloud_water_num", "Cloud Water Number", True, False),
+               ("rain", "Rain Water Mass", True, True), ("rain_num", "Rain Water Number", True, False),
+               ("ice", "Ice Mass", True, True), ("ice_num", "Ice Number", True, False), ("ice_rime", "Ice-Rime Mass", True, False),
+               ("ice_rime_vol", "Ice-Rime Volume", True, False), ("water_vapor", "Water Vapor", True, True))   # :119-127
+    ARRAYS_4D = (("nccn_prescribed", "prescribed cld nuclei concentration  [#/kg]"),
+                 ("nc_nuceat_tend", "activated cld nuclei number tendency [#/kg/s]"),
+                 ("ni_activated", "activated ice nuclei concentration   [#/kg]"), ("q_prev", "rho_v from prev step"),
+                 ("t_prev", "Temperature from prev step"), ("liq_ice_exchange_out", "p3 liq to ice phase change tendency"),
+                 ("vap_liq_exchange_out", "p3 vap to liq phase change tendency"),
+                 ("vap_ice_exchange_out", "p3 vap to ice phase change tendency"))                           # :131-143
+    ARRAYS_3D = (("precip_liq_surf_out", "liq surface precipitation rate"), ("precip_ice_surf_out", "ice surface precipitation rate"))
+    PACKED_TRACERS = ("cloud_water_num", "rain", "rain_num", "ice", "ice_num", "ice_rime", "ice_rime_vol")
+
+    def __init__(self, p3_main=None, layout=1, user=None, num_tend_out=None):
+        if layout not in (0, 1):
+            endrun("ERROR: P3: layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)")
+        self.layout = layout
+        self.num_tend_out = (49 if layout == 0 else 0) if num_tend_out is None else int(num_tend_out)
+        if not 0 <= self.num_tend_out <= 49 or (layout == 1 and self.num_tend_out):
+            endrun("ERROR: P3: num_tend_out must be 0 ... 49, and 0 in layout 1")
+        self.sgs_shoc = False
+        self.first_step = True
+        self.etime = 0.0
+        self._ws = None
+        self._ws_key = None
+        self.set_p3_main(p3_main, user)
+
+    @staticmethod
+    def get_num_tracers():
+        return 9
+
+    @classmethod
+    def get_diffused_tracers_indices(cls):
+        return [cls.ID_V, cls.ID_C, cls.ID_R, cls.ID_I]
+
+    @classmethod
+    def get_num_diffused_tracers(cls):
+        return 4
+
+    @staticmethod
+    def micro_name():
+        return "p3"
+
+    @staticmethod
+    def standin():
+        """the library's test double for p3_main (no physics): pam_amd_p3_main_standin"""
+        return capi.load().pam_amd_p3_main_standin
+
+    def set_p3_main(self, fn, user=None):
+        import ctypes as C
+        if isinstance(fn, int):
+            fn = capi.P3_MAIN_FN(fn)
+        self._c_main = fn is not None and isinstance(fn, C._CFuncPtr)
+        self.p3_main, self.user = fn, user
+
+    def init(self, coupler):
+        """Microphysics.h:108-210: nine tracers, eight 4-D and two surface entries, all zero; option micro = "p3" and the constants"""
+        nz, ny, nx, nens = coupler.get_nz(), coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+        for name, desc, positive, adds_mass in self.TRACERS:
+            coupler.add_tracer(name, desc, positive, adds_mass)
+        dm = coupler.get_data_manager_device_readwrite()
+        for name, desc in self.ARRAYS_4D[:5]:
+            dm.register_and_allocate(name, desc, (nz, ny, nx, nens), ("z", "y", "x", "nens"))
+        for name, desc in self.ARRAYS_3D:
+            dm.register_and_allocate(name, desc, (ny, nx, nens), ("y", "x", "nens"))
+        for name, desc in self.ARRAYS_4D[5:]:
+            dm.register_and_allocate(name, desc, (nz, ny, nx, nens), ("z", "y", "x", "nens"))
+        for name in [t[0] for t in self.TRACERS] + [a[0] for a in self.ARRAYS_4D + self.ARRAYS_3D]:
+            dm.get(name).zero_()
+        coupler.set_option("micro", "p3")
+        for k in ("latvap", "latice", "R_d", "R_v", "cp_d", "cp_v", "grav", "p0"):
+            coupler.set_option(k, getattr(self, k))
+        self.etime = 0.0
+
+    def _workspace(self, coupler):
+        import ctypes as C
+        lib = capi.load()
+        key = (coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), self.layout, self.num_tend_out, str(coupler.device))
+        if self._ws is None or self._ws_key != key:
+            self._free()
+            ws = C.c_void_p()
+            with torch.cuda.device(coupler.device):
+                check(lib.pam_amd_p3_workspace_create(*key[:6], C.byref(ws)))
+            self._ws, self._ws_key = ws, key
+            self._args = capi.P3Args()
+            check(lib.pam_amd_p3_workspace_args(ws, C.byref(self._args)))
+            self._views = None
+        return self._ws
+
+    def workspace_bytes(self):
+        import ctypes as C
+        n = C.c_longlong()
+        check(capi.load().pam_amd_p3_workspace_bytes(self._ws, C.byref(n)))
+        return n.value
+
+    def workspace_views(self, device):
+        """name -> torch view of the workspace array, in this object's layout"""
+        if self._views is None:
+            a = self._args
+            shapes = p3_shapes(a.ncol, a.nlev, self.layout, a.num_tend_out)
+            self._views = {n: (torch.as_tensor(_DeviceArray(getattr(a, n), shp), device=device) if min(shp) > 0
+                               else torch.empty(shp, dtype=torch.float64, device=device)) for n, shp in shapes.items()}
+        return self._views
+
+    def _free(self):
+        if self._ws is not None:
+            check(capi.load().pam_amd_p3_workspace_destroy(self._ws))
+        self._ws = self._ws_key = self._views = None
+
+    def timeStep(self, coupler):
+        """Microphysics.h:214-741.  Everything is checked before the first launch: a refused call leaves every field untouched"""
+        import ctypes as C
+        lib = capi.load()
+        if self.p3_main is None:
+            endrun("ERROR: P3: no p3_main is registered; call set_p3_main(fn, user) before timeStep (P3 itself is not part of this "
+                   "library)")
+        dt = float(coupler.get_option("crm_dt"))
+        sgs_shoc = self.sgs_shoc or (self.first_step and coupler.get_option("sgs") == "shoc")             # :220-222
+        dm = coupler.get_data_manager_device_readwrite()
+        ro = lambda n: dm.get(n, readonly=True)
+        rho_d, zint = ro("density_dry"), ro("vertical_interface_height")
+        nccn, nuceat, ni_act = ro("nccn_prescribed"), ro("nc_nuceat_tend"), ro("ni_activated")
+        rho_v, rho_c, temp, q_prev, t_prev = (dm.get(n) for n in ("water_vapor", "cloud_water", "temp", "q_prev", "t_prev"))
+        liq_ice, vap_liq, vap_ice = (dm.get(n) for n in ("liq_ice_exchange_out", "vap_liq_exchange_out", "vap_ice_exchange_out"))
+        p_liq, p_ice = dm.get("precip_liq_surf_out"), dm.get("precip_ice_surf_out")
+        q = [dm.get(n) for n in self.PACKED_TRACERS]
+        qp = (C.c_void_p * 7)(*[t.data_ptr() for t in q])
+        ws = self._workspace(coupler)
+        self.sgs_shoc = sgs_shoc
+        with torch.cuda.device(coupler.device):
+            stream = torch.cuda.current_stream(coupler.device).cuda_stream
+            check(lib.pam_amd_p3_pack(ws, rho_d.data_ptr(), rho_v.data_ptr(), rho_c.data_ptr(), temp.data_ptr(), qp, nccn.data_ptr(),
+                                      nuceat.data_ptr(), ni_act.data_ptr(), q_prev.data_ptr(), t_prev.data_ptr(), zint.data_ptr(),
+                                      0 if sgs_shoc else 1, int(self.first_step), self.R_d, self.R_v, self.cp_d, self.cp_v, self.cp_l,
+                                      self.p0, self.grav, stream))
+            self._args.dt, self._args.stream = dt, stream
+            if self._c_main:
+                rc = self.p3_main(C.byref(self._args), self.user)
+            else:
+                rc = self.p3_main(self.workspace_views(coupler.device), self._args)
+            if rc not in (0, None):
+                endrun(f"ERROR: P3: p3_main returned {rc}")
+            check(lib.pam_amd_p3_unpack(ws, rho_d.data_ptr(), rho_v.data_ptr(), rho_c.data_ptr(), qp, temp.data_ptr(), q_prev.data_ptr(),
+                                        t_prev.data_ptr(), liq_ice.data_ptr(), vap_liq.data_ptr(), vap_ice.data_ptr(), p_liq.data_ptr(),
+                                        p_ice.data_ptr(), self.cp_d, self.cv_d, stream))
+        self.first_step = False
+        self.etime += dt
+
+    def finalize(self, coupler):
+        self._free()
+
+    def __del__(self):
+        try:
+            self._free()
+        except Exception:
+            pass

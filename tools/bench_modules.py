@@ -6,7 +6,8 @@ copy timed beside them as yardsticks, three repetitions: one JSON object on stdo
 Run on the GPU box:  python tools/bench_modules.py            (--only vertical_interp, --only plugins: those rows alone;
 --only validate: DataManager.validate_all's device scan with the two statistics rows of the same run beside it;
 --only diagnostics: pam_amd.field_diagnostics whole-field and per-member, with the validation and time_average_accumulate rows;
---only shoc: the SHOC coupling layer's pack and unpack in both layouts, both tracer sets, beside the composition the reference performs)"""
+--only shoc: the SHOC coupling layer's pack and unpack in both layouts, both tracer sets, beside the composition the reference performs;
+--only p3: the P3 coupling layer's pack (with and without the saturation adjustment) and unpack in both layouts, beside its composition)"""
 import json
 import os
 import sys
@@ -505,10 +506,157 @@ def shoc_timing(dev, n=11):
     return out
 
 
+def p3_timing(dev, n=11):
+    """pam_amd_p3_pack / pam_amd_p3_unpack at the C2 grid in both layouts: 3 warm-up calls, median of n event-timed calls.  adjust = 0 (SHOC
+    is the SGS), and adjust = 1 on a state where no cell is in a branch of the adjustment ("idle") and on one where every cell iterates
+    ("busy": super-saturated; a repeated call finds the adjusted state, whose cells still enter a branch and bisect from the full bracket).
+    Algorithmic bytes with Z = nz, N = ncol, 8 B each:
+      pack    reads  16 Z N  (rho_d, rho_v, rho_c, temp, 7 tracers, 3 nuclei arrays, q_prev, t_prev) + the grid
+              writes 24 Z N  (10 in/out, pres, dz, 3 nuclei arrays, dpres, inv_exner, q_prev, t_prev, exner, 3 cloud fractions, inv_qc_relvar)
+                     + 3 N (col_location), + up to 3 Z N with adjust (not counted: the rows' fractions are lower bounds there)
+      unpack  reads  16 Z N + 2 N   writes 15 Z N + 2 N
+    The comparison is what the reference performs for SCREAM's layout, built from what exists: pam_amd_saturation_adjustment ahead for
+    adjust = 1, the layout-0 pack and one flipped transpose().contiguous() per array p3_main reads (and back: one per array the unpack step
+    reads, then the layout-0 unpack).  time_average_accumulate runs beside them as the yardstick of the other rows."""
+    import ctypes as C
+    from pam_amd import PamCoupler, modules
+    from pam_amd import idealized as idz
+    from pam_amd.capi import P3Args, check, load
+    from pam_amd.physics import MicrophysicsP3 as M, _DeviceArray, p3_shapes
+    lib, stream = load(), torch.cuda.current_stream(dev).cuda_stream
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    ncol = nens * nx * ny
+    cells = ncol * nz
+    out = {"p3_grid": "1024 x 32x32x60 (C2)", "p3_method": "3 warm-up calls, median of %d event-timed calls" % n}
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        return _events(fn, n=n)
+
+    def row(ms, nbytes):
+        gbs = nbytes / ms / 1e6
+        return {"ms": ms, "bytes": nbytes, "GBps": gbs, "hbm_frac": gbs / bench.HBM_PEAK_GBS}
+
+    c = PamCoupler(dev)
+    c.set_option("crm_dt", 20.0)
+    c.set_option("gcm_physics_dt", 900.0)
+    c.set_option("sgs", "none")
+    c.allocate_coupler_state(nz, ny, nx, nens)
+    c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+    M().init(c)
+    dm = c.get_data_manager_device_readwrite()
+    gen = torch.Generator(device=dev).manual_seed(0)
+    tracers = [t[0] for t in M.TRACERS]
+    fields = ["density_dry", "temp", "nccn_prescribed", "nc_nuceat_tend", "ni_activated", "q_prev", "t_prev"] + tracers
+    for name in fields:
+        t = dm.get(name)
+        t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev))
+    dm.get("temp").mul_(60.0).add_(240.0)
+    dm.get("t_prev").mul_(60.0).add_(240.0)
+    dm.get("density_dry").add_(0.1)
+    for name in tracers + ["q_prev"]:
+        dm.get(name).mul_(1e-3)
+    temp = dm.get("temp")
+    sat = 610.94 * torch.exp(17.625 * (temp - 273.15) / (243.04 + (temp - 273.15))) / (M.R_v * temp)
+    states = {"idle": (0.5 * sat, torch.zeros_like(sat)), "busy": (1.3 * sat, dm.get("cloud_water").clone())}
+    saved_temp = temp.clone()
+    g = lambda name: dm.get(name).data_ptr()
+    qp = (C.c_void_p * 7)(*[g(name) for name in M.PACKED_TRACERS])
+    ws, args, views = {}, {}, {}
+    for layout in (0, 1):
+        w = C.c_void_p()
+        check(lib.pam_amd_p3_workspace_create(nens, nx, ny, nz, layout, 0, C.byref(w)))
+        a = P3Args()
+        check(lib.pam_amd_p3_workspace_args(w, C.byref(a)))
+        nb = C.c_longlong()
+        check(lib.pam_amd_p3_workspace_bytes(w, C.byref(nb)))
+        out["p3_workspace_bytes_layout%d" % layout] = nb.value
+        ws[layout], args[layout] = w, a
+        views[layout] = {k: torch.as_tensor(_DeviceArray(getattr(a, k), shp), device=dev) for k, shp in p3_shapes(ncol, nz, layout).items()
+                         if min(shp) > 0}
+
+    def load_state(which):
+        rv, rc = states[which]
+        dm.get("water_vapor").copy_(rv)
+        dm.get("cloud_water").copy_(rc)
+        temp.copy_(saved_temp)
+
+    def pack(layout, adjust):
+        check(lib.pam_amd_p3_pack(ws[layout], g("density_dry"), g("water_vapor"), g("cloud_water"), g("temp"), qp, g("nccn_prescribed"),
+                                  g("nc_nuceat_tend"), g("ni_activated"), g("q_prev"), g("t_prev"), g("vertical_interface_height"), adjust, 0,
+                                  M.R_d, M.R_v, M.cp_d, M.cp_v, M.cp_l, M.p0, M.grav, stream))
+
+    def unpack(layout):
+        check(lib.pam_amd_p3_unpack(ws[layout], g("density_dry"), g("water_vapor"), g("cloud_water"), qp, g("temp"), g("q_prev"), g("t_prev"),
+                                    g("liq_ice_exchange_out"), g("vap_liq_exchange_out"), g("vap_ice_exchange_out"), g("precip_liq_surf_out"),
+                                    g("precip_ice_surf_out"), M.cp_d, M.cv_d, stream))
+
+    ins = ("qc", "nc", "qr", "nr", "th_atm", "qv", "qi", "qm", "ni", "bm", "pres", "dz", "nc_nuceat_tend", "nccn_prescribed", "ni_activated",
+           "inv_qc_relvar", "dpres", "inv_exner", "cld_frac_r", "cld_frac_l", "cld_frac_i", "q_prev", "t_prev")
+    outs = ("qc", "nc", "qr", "nr", "th_atm", "qv", "qi", "qm", "ni", "bm", "liq_ice_exchange", "vap_liq_exchange", "vap_ice_exchange")
+
+    def composed_pack(adjust):
+        if adjust:
+            modules.saturation_adjustment(c)
+        pack(0, 0)
+        v = views[0]
+        keep = [v[k].flip(0).t().contiguous() for k in ins]
+        keep.append(v["col_location"].t().contiguous())
+        return keep
+
+    def composed_unpack():
+        v1, v0 = views[1], views[0]
+        for k in outs:
+            v0[k].copy_(v1[k].t().flip(0))
+        unpack(0)
+
+    zi = (nz + 1) * nens
+    pack_bytes = 8.0 * (16 * cells + zi + 24 * cells + 3 * ncol)
+    unpack_bytes = 8.0 * (16 * cells + 2 * ncol + 15 * cells + 2 * ncol)
+    for which, adjust in (("idle", 0), ("idle", 1), ("busy", 1)):
+        tag = "adjust%d%s" % (adjust, "_" + which if adjust else "")
+        for layout in (0, 1):
+            load_state(which)
+            out["p3_pack_%s_layout%d" % (tag, layout)] = row(timed(lambda: pack(layout, adjust)), pack_bytes)
+        load_state(which)
+        out["p3_pack_%s_composition" % tag] = row(timed(lambda: composed_pack(adjust)), pack_bytes)
+    # the unpack step reads what a p3_main left: the stand-in's outputs, in both workspaces
+    load_state("idle")
+    saved = {name: dm.get(name).clone() for name in ("temp", "water_vapor", "cloud_water", "q_prev", "t_prev") + M.PACKED_TRACERS}
+    for layout in (0, 1):
+        pack(layout, 0)
+        args[layout].stream = stream
+        check(lib.pam_amd_p3_main_standin(C.byref(args[layout]), None))
+
+    def restore():
+        for name, v in saved.items():
+            dm.get(name).copy_(v)
+
+    for layout in (0, 1):
+        restore()
+        out["p3_unpack_layout%d" % layout] = row(timed(lambda: unpack(layout)), unpack_bytes)
+    restore()
+    out["p3_unpack_composition"] = row(timed(composed_unpack), unpack_bytes)
+    restore()
+    names = ["density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor", "cloud_water", "rain"]
+    modules.time_average_init(c, names)
+    elems = sum(dm.get(name, readonly=True).numel() for name in names)
+    out["time_average_accumulate_p3"] = row(timed(lambda: modules.time_average_accumulate(c, names)), elems * 24.0)
+    for layout in (0, 1):
+        check(lib.pam_amd_p3_workspace_destroy(ws[layout]))
+    del views, saved, states, dm, c
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
     if sys.argv[1:] == ["--only", "shoc"]:
         print(json.dumps(shoc_timing(dev)))
+        sys.exit(0)
+    if sys.argv[1:] == ["--only", "p3"]:
+        print(json.dumps(p3_timing(dev)))
         sys.exit(0)
     if sys.argv[1:] == ["--only", "plugins"]:
         print(json.dumps(plugins_timing(dev)))
