@@ -5,7 +5,7 @@
 //   -> (host model fills the coupler fields) -> dycore.declare_current_profile_as_hydrostatic
 //   -> N x { coupler.run_module("dycore", dycore.timeStep); [sponge_layer]; [micro.timeStep] } -> output
 //
-//   driver [--gpus N] [--tile R] [--bench K W] <input.bin> <output.bin>
+//   driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] <input.bin> <output.bin>
 //
 // --gpus N: the ensemble is sharded by member index over N devices of this node -- ONE host thread, ONE coupler and ONE dycore
 // handle per device (hipSetDevice before init), no inter-device halo and no collective library: the exchanges the reference
@@ -14,6 +14,9 @@
 // doubles behind a barrier (HostMin) and handed to Dycore::timeStep(coupler, dt_dyn) / Microphysics::timeStep(coupler, rainsplit).  With fewer devices than ranks the ranks share
 // devices (rehearsal on a 1-GPU box; bit-identical results, tests/test_cpp_driver.py).
 // --tile R: the input's members are repeated R times along nens (tile t gets +t mK on temp so that no two CRMs are equal).
+// --accelerate A: CRM mean-state acceleration (modules/mean_state_acceleration.h): the file's nsteps are the CRM steps of ONE GCM step,
+// run on modules::MsaClock; the cease flag is global over the members, so the ranks OR theirs on the host through the same HostMin
+// (the maximum of 0 / 1 is minus the minimum of their negatives).  Rank 0 prints the number of CRM steps that ran.
 // --bench K W: W untimed + K timed steps between barriers; rank 0 prints one JSON line with the wall time (bench.py --launcher cpp).
 //
 // Input/output are raw little-endian fp64 files written/read by tests/test_cpp_driver.py (the reference reads YAML and
@@ -46,6 +49,7 @@
 #include "modules/surface_friction.h"
 #include "modules/horizontal_average.h"
 #include "modules/time_average.h"
+#include "modules/mean_state_acceleration.h"
 #include "vertical_interp.h"
 #include "physics/micro/kessler_amd/Microphysics.h"
 #include "physics/sgs/none/SGS.h"
@@ -112,6 +116,9 @@ struct Job {
   std::vector<std::vector<real>> fields;     // the output, same order: (nz,ny,nx,nens) each (only when want_output)
   std::vector<real> precl;                   // (ny,nx,nens), Kessler only
   int bench_steps = 0, bench_warmup = 0;
+  bool accelerate = false, accel_uv = false;
+  double accel_factor = 0, accel_max_ttend = 5.0;
+  int accel_crm_steps = 0, accel_ceased = 0;   // out (rank 0)
 };
 
 struct BenchResult { double seconds = 0; long substeps = 0; };
@@ -218,6 +225,26 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
     if (hipDeviceSynchronize() != hipSuccess) endrun("device error");
     hmin.barrier(rank);
     bench.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  } else if (J.accelerate) {
+    coupler.set_option<real>("crm_accel_factor", J.accel_factor);
+    coupler.set_option<bool>("crm_accel_uv", J.accel_uv);
+    coupler.set_option<real>("crm_accel_max_ttend", J.accel_max_ttend);
+    modules::MsaClock clock(J.nsteps, J.accel_factor);
+    coupler.run_module("msa_init", modules::msa_init);
+    int steps = 0;
+    while (!clock.done()) {
+      const bool accel = clock.accelerating();                                           // the same on every rank: the flag is global
+      if (accel) coupler.run_module("msa_diagnose", modules::msa_diagnose);
+      one_step();
+      bool cease = false;
+      if (accel)
+        coupler.run_module("msa_accelerate", [&](pam::PamCoupler &c) {
+          cease = modules::msa_accelerate(c, [&](int mine) { return world == 1 ? mine : (int)-hmin(rank, -(double)mine); });
+        });
+      clock.advance(cease);
+      steps++;
+    }
+    if (rank == 0) { J.accel_crm_steps = steps; J.accel_ceased = clock.ceased() ? 1 : 0; }
   } else {
     for (int s = 0; s < J.nsteps; s++) one_step();
   }
@@ -237,7 +264,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
-//          [--radiation RAD_NX RAD_NY PATH] <output.bin | ->
+//          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
 // out_freq, vcoords [, crm_nz, zlen, idealized, apply_sponge, initData].  What runs, in the reference's order:
@@ -327,9 +354,14 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              number of NaNs and the reproducible sum, of the whole field ("whole") and of every ensemble member
 //                              ("members"), taken on the device by two scans (pam_amd_field_diagnostics) without copying a field;
 //                              stdout and the output file are those of a run without it.
+//   --accelerate A [--accel-uv] [--accel-max-ttend X]   CRM mean-state acceleration (modules/mean_state_acceleration.h) with
+//                              crm_accel_factor = A: modules::msa_init at the start of every GCM step, modules::msa_diagnose FIRST in
+//                              every CRM step, modules::msa_accelerate after its last module; the CRM loop runs on modules::MsaClock, so
+//                              a GCM step takes nsteps_crm_phys / (1 + A) CRM steps (1 + A must divide it) unless the acceleration ceases,
+//                              and --stats weighs every step by the clock's count.  Without it the loop is the one above.
 struct YamlModules {
-  bool sat_adjust = false, surface_friction = false, radiation = false, validate = false;
-  double tau = 0, bflx = 0;
+  bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
+  double tau = 0, bflx = 0, accel_factor = 0, accel_max_ttend = 5.0;
   int rad_nx = 0, rad_ny = 0;
   std::string stats, edges, rad_path, diag;
 };
@@ -436,6 +468,11 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     if (apply_gcm_forcing) std::printf("apply_gcm_forcing: not run (modules::gcm_forcing works on P3's tracer set; P3 is out of scope)\n");
     if (!idealized) initialize_from_supercell_column(zint, coupler);        // driver.cpp:220-222
     if (check) dycore.set_debug_conservation(true);
+    if (mods.accelerate) {
+      coupler.set_option<real>("crm_accel_factor", mods.accel_factor);
+      coupler.set_option<bool>("crm_accel_uv", mods.accel_uv);
+      coupler.set_option<real>("crm_accel_max_ttend", mods.accel_max_ttend);
+    }
     auto &dm = coupler.get_data_manager_device_readwrite();
     double *sf_in = nullptr;                                                 // tau_in, bflx_in of surface_friction_init: (2, nens)
     if (mods.surface_friction) {
@@ -468,7 +505,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       if (!diag_out) endrun("cannot open the --diag file");
     }
     double etime_gcm = 0, maxw_all = 0, cons_max_rel = 0;
-    int num_out = 0, crm_steps = 0;
+    int num_out = 0, crm_steps = 0, accel_steps = 0, accel_ceased_gcm_steps = 0;
     long substeps = 0, cons_violations = 0;
     bool stop = false;
     std::string maxw_series;
@@ -476,7 +513,12 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       if (stats) coupler.run_module("time_average_init", [&](pam::PamCoupler &c) { modules::time_average_init(c, stat_names); });
       dycore.declare_current_profile_as_hydrostatic(coupler);               // (E3SM's MMF driver: once per GCM step)
       int crm_steps_gcm = 0;
-      for (int step_crm_phys = 0; step_crm_phys < nsteps_crm_phys && !stop; ++step_crm_phys) {
+      // the CRM loop runs on the clock: without --accelerate every step counts 1 and the loop is step_crm_phys = 0 .. nsteps_crm_phys - 1
+      modules::MsaClock clock(nsteps_crm_phys, mods.accelerate ? mods.accel_factor : 0.0);
+      if (mods.accelerate) coupler.run_module("msa_init", modules::msa_init);
+      while (!clock.done() && !stop) {
+        const bool accel = clock.accelerating();
+        if (accel) coupler.run_module("msa_diagnose", modules::msa_diagnose);
         if (mods.radiation) coupler.run_module("radiation", [&](pam::PamCoupler &c) { rad.timeStep(c); });
         coupler.run_module("dycore", [&](pam::PamCoupler &c) { dycore.timeStep(c); });       // driver.cpp:248
         substeps += dycore.last_ncycles();
@@ -490,12 +532,16 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         if (!dbg.no_micro) coupler.run_module("micro", [&](pam::PamCoupler &c) { micro.timeStep(c); });         // driver.cpp:253
         if (mods.sat_adjust) coupler.run_module("saturation_adjustment", modules::saturation_adjustment);
-        if (stats) coupler.run_module("time_average_accumulate", [&](pam::PamCoupler &c) { modules::time_average_accumulate(c, stat_names); });
+        bool cease = false;
+        if (accel) coupler.run_module("msa_accelerate", [&](pam::PamCoupler &c) { cease = modules::msa_accelerate(c); });
+        const int weight = clock.advance(cease);
+        if (accel && !cease) accel_steps++;
+        if (stats) coupler.run_module("time_average_accumulate", [&](pam::PamCoupler &c) { modules::time_average_accumulate(c, stat_names, weight); });
         if (mods.validate) dm.validate_all();
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         crm_steps++;
         crm_steps_gcm++;
-        etime_gcm = step_gcm * dt_gcm + (step_crm_phys + 1) * dt_crm_phys;  // driver.cpp:255
+        etime_gcm = step_gcm * dt_gcm + clock.count() * dt_crm_phys;        // driver.cpp:255
         if (out_freq >= 0. && etime_gcm / out_freq >= num_out + 1) {        // driver.cpp:257-271 (the netCDF output itself: out of scope)
           fetch("wvel");
           double maxw = 0;
@@ -528,6 +574,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         }
         if (steps_limit > 0 && crm_steps >= steps_limit) stop = true;
       }
+      if (clock.ceased()) accel_ceased_gcm_steps++;
       if (stats) {                                                            // the GCM step's profiles
         coupler.run_module("horizontal_average", [&](pam::PamCoupler &c) { modules::horizontal_average(c, stat_havg); });
         char t[96];
@@ -623,6 +670,9 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
 #ifdef PAM_FUNCTION_TIMERS
     pam::function_timers::print();
 #endif
+    if (mods.accelerate)
+      std::printf("{\"accel_factor\": %.9g, \"accel_uv\": %s, \"accel_max_ttend\": %.9g, \"accelerated_steps\": %d, \"ceased_gcm_steps\": %d}\n",
+                  mods.accel_factor, mods.accel_uv ? "true" : "false", mods.accel_max_ttend, accel_steps, accel_ceased_gcm_steps);
     std::printf("{\"crm_steps\": %d, \"substeps\": %ld, \"etime\": %.9g, \"dt_crm_phys\": %.9g, \"nens\": %d, \"nx\": %d, \"ny\": %d, \"nz\": %d, "
                 "\"finite\": %s, \"rho_d_min\": %.9g, \"temp_min\": %.9g, \"temp_max\": %.9g, \"maxw_final\": %.9g, \"maxw_any_output\": %.9g, "
                 "\"temp_min_level\": %ld, \"tracer_min\": %.9g, \"maxw_series\": [%s], \"conservation_checked\": %s, \"conservation_violations\": %ld, "
@@ -670,8 +720,12 @@ int main(int argc, char **argv) {
         mods.rad_ny = std::atoi(argv[++b]);
         mods.rad_path = argv[++b];
       }
+      else if (o == "--accelerate" && b + 1 < argc - 1) { mods.accelerate = true; mods.accel_factor = std::atof(argv[++b]); }
+      else if (o == "--accel-uv") mods.accel_uv = true;
+      else if (o == "--accel-max-ttend" && b + 1 < argc - 1) mods.accel_max_ttend = std::atof(argv[++b]);
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
-               "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] <output.bin | ->");
+               "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] <output.bin | ->");
     }
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }
@@ -682,9 +736,13 @@ int main(int argc, char **argv) {
     if (o == "--gpus" && a + 1 < argc) gpus = std::atoi(argv[++a]);
     else if (o == "--tile" && a + 1 < argc) tile = std::atoi(argv[++a]);
     else if (o == "--bench" && a + 2 < argc) { J.bench_steps = std::atoi(argv[++a]); J.bench_warmup = std::atoi(argv[++a]); }
-    else die("usage: driver [--gpus N] [--tile R] [--bench K W] <input.bin> <output.bin>");
+    else if (o == "--accelerate" && a + 1 < argc) { J.accelerate = true; J.accel_factor = std::atof(argv[++a]); }
+    else if (o == "--accel-uv") J.accel_uv = true;
+    else if (o == "--accel-max-ttend" && a + 1 < argc) J.accel_max_ttend = std::atof(argv[++a]);
+    else die("usage: driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] <input.bin> <output.bin>");
   }
-  if (argc - a != 2 || gpus < 1 || tile < 1) die("usage: driver [--gpus N] [--tile R] [--bench K W] <input.bin> <output.bin>");
+  if (argc - a != 2 || gpus < 1 || tile < 1)
+    die("usage: driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] <input.bin> <output.bin>");
   std::ifstream in(argv[a], std::ios::binary);
   if (!in) die("cannot open input");
   int64_t hdr[8];
@@ -733,6 +791,8 @@ int main(int argc, char **argv) {
   for (int r = 0; r < gpus; r++)
     if (!errors[r].empty()) { std::fprintf(stderr, "driver: rank %d: endrun: %s\n", r, errors[r].c_str()); return 1; }
   std::printf("Dycore: %s\n", name.c_str());
+  if (J.accelerate && J.bench_steps == 0)
+    std::printf("{\"accel_factor\": %.9g, \"crm_steps\": %d, \"ceased\": %s}\n", J.accel_factor, J.accel_crm_steps, J.accel_ceased ? "true" : "false");
   if (J.bench_steps > 0) {
     double sec = 0;
     for (auto &b : bench) sec = std::max(sec, b.seconds);

@@ -411,6 +411,35 @@ int pam_amd_p3_main_standin(const pam_amd_p3_args_t *args, void *user);
  * from 2^29 elements in the largest array, p3_tend_out included, on); 0 restores the choice by size.  Process-wide; same bits either way. */
 int pam_amd_p3_debug_wide_index(int on);
 
+/* CRM mean-state acceleration (MSA; Jones, Bretherton and Pritchard 2015, the crm_accel_factor / crm_accel_uv option of E3SM-MMF's CRM
+ * loop): after a CRM step the change of the horizontal-mean state over that step is applied once more, multiplied by a =
+ * accel_factor, and the step counts as 1 + a steps of model time.  Not part of the reference tree; the contract is this project's
+ *  and is restated in numpy in tests/msa_ref.py, which the kernels match bit for bit.
+ *   fields[6]   HOST array of DEVICE pointers (nz,ny,nx,nens): temp, water_vapor, cloud or NULL, ice or NULL, uvel, vvel
+ *   save[4], tend[4]   HOST arrays of DEVICE pointers (nz,nens): temp, total water q = water_vapor + cloud + ice (left to right, an
+ *               absent species skipped), uvel, vvel
+ * Level mean M(f)(k,e), r = 1/(ny nx): cell c = j nx + i belongs to slot c % 16; a slot adds f(k,c,e) * r (the product rounded first,
+ * no fma) over its cells in ascending c from 0.0; the 16 slot sums are added in ascending slot order from 0.0.  Level sum S: the same
+ * without r.  No floating-point atomics and no scratch: the same bits from run to run and for any split of the members over calls.
+ *
+ * pam_amd_msa_diagnose    at the start of a CRM step: save_x = M(x).  Writes nothing else.
+ * pam_amd_msa_tendencies  after the last module of the step: tend_x = M(x) - save_x; *cease_dev (DEVICE int) is set to 1 when
+ *               !(|tend_T| <= max_ttend) holds for any (k,e) -- a NaN or an infinite tendency ceases -- and is left alone otherwise: the
+ *               word is sticky, the caller zeroes it once per GCM step.  Touches no state.  cease_host (HOST, may be NULL): where
+ *               given, the word is copied there and `stream` is synchronised once; where NULL nothing synchronises.
+ * pam_amd_msa_apply       d_x = a tend_x once per (k,e); temp += d_T; with accel_uv != 0 uvel += d_U and vvel += d_V (otherwise neither
+ *               is read or written, and both pointers may be NULL); v' = water_vapor + d_q, P = S(max(v',0)), N = S(min(v',0)):
+ *               no negative value (!(N < 0)): water_vapor = v'; else P + N > 0: water_vapor = max(v',0) (1 + N/P), the level's vapour
+ *               mass kept; else the member's whole level becomes 0.  Cloud, ice (fields[2], fields[3] are ignored) and everything else
+ *               are never written.  cease_dev (DEVICE, may be NULL): where *cease_dev != 0 the kernel writes nothing.  a == 0: no launch.
+ * Every argument is checked before the first HIP call (null tables, nens / nx / ny / nz < 1, a negative or not finite, max_ttend not a
+ * positive number): a PAM_AMD_EINVAL return has written nothing and needs no device. */
+int pam_amd_msa_diagnose(int nens, int nx, int ny, int nz, const double *const *fields, double *const *save, void *stream);
+int pam_amd_msa_tendencies(int nens, int nx, int ny, int nz, const double *const *fields, const double *const *save, double *const *tend,
+                           double max_ttend, int *cease_dev, int *cease_host, void *stream);
+int pam_amd_msa_apply(int nens, int nx, int ny, int nz, double *const *fields, const double *const *tend, double accel_factor,
+                      int accel_uv, const int *cease_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,10 @@ MODULE_SYMBOLS = {
     "pam_amd_p3_unpack": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)] + [C.c_void_p] * 8 + [C.c_double] * 2 + [C.c_void_p]),
     "pam_amd_p3_main_standin": (C.c_int, [C.POINTER(P3Args), C.c_void_p]),
     "pam_amd_p3_debug_wide_index": (C.c_int, [C.c_int]),
+    "pam_amd_msa_diagnose": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_void_p)] * 2 + [C.c_void_p]),
+    "pam_amd_msa_tendencies": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_void_p)] * 3 + [C.c_double, C.c_void_p, C.POINTER(C.c_int),
+                                                                                       C.c_void_p]),
+    "pam_amd_msa_apply": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_void_p)] * 2 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -1,0 +1,136 @@
+// modules/mean_state_acceleration.h -- CRM mean-state acceleration (Jones, Bretherton and Pritchard 2015; E3SM-MMF's crm_accel_factor,
+// crm_accel_uv) over pam_amd_msa_diagnose / pam_amd_msa_tendencies / pam_amd_msa_apply (include/pam_amd_modules.h).  The method is not
+// part of the reference tree; the contract is this project's.  In a CRM step:
+//   modules::msa_diagnose(coupler)      first, before GCM forcing: saves the level means of temp, total water, uvel and vvel
+//   ... the modules of the step ...
+//   modules::msa_accelerate(coupler)    after the last module: the means' change over the step, applied once more crm_accel_factor
+//                                       times; returns true where the acceleration ceased (a temperature tendency beyond
+//                                       crm_accel_max_ttend, or not a number) and nothing was applied
+//   modules::MsaClock                   how many steps of model time the CRM step counts: the loop's counter and the weight of the step
+//                                       in modules::time_average_accumulate
+// modules::msa_init(coupler) comes first in every GCM step: it registers "accel_save_{t,q,u,v}", "accel_tend_{t,q,u,v}" {nz,nens} and
+// the cease word on first use, zeroes the word and sets option "crm_accel_ceaseflag" = false.
+// Options: "crm_accel_factor" (real, >= 0, required), "crm_accel_uv" (bool, default false), "crm_accel_max_ttend" (real, default 5 K),
+// "micro" names the condensate of the total water: kessler: cloud_liquid; p3: cloud_water and ice; none (or absent): vapour alone.
+#pragma once
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "pam_coupler.h"
+#include "pam_amd_awfl.h"
+#include "pam_amd_modules.h"
+
+namespace modules {
+
+// The step clock of an accelerated CRM loop.  nstop: unaccelerated CRM steps per GCM step; 1 + accel_factor must be an integer that
+// divides it (as E3SM requires), otherwise the constructor calls endrun.  A step that was accelerated counts 1 + accel_factor steps; the
+// step that raised the cease flag counts 1, and so does every later step of the GCM step.  The count cannot overshoot nstop.
+class MsaClock {
+  int nstop_, per_step_, count_ = 0;
+  bool ceased_ = false;
+ public:
+  MsaClock(int nstop, real accel_factor) : nstop_(nstop), per_step_(1) {
+    if (nstop < 1) endrun("ERROR: mean-state acceleration: nstop must be >= 1");
+    if (!(accel_factor >= 0) || !std::isfinite(accel_factor)) endrun("ERROR: mean-state acceleration: crm_accel_factor must be finite and >= 0");
+    real steps = 1 + accel_factor;
+    if (steps != std::floor(steps) || steps > nstop || nstop % (int)steps != 0)
+      endrun("ERROR: mean-state acceleration: 1 + crm_accel_factor must be an integer that divides the number of CRM steps");
+    per_step_ = (int)steps;
+  }
+  bool done() const { return count_ >= nstop_; }
+  bool accelerating() const { return !ceased_ && per_step_ > 1; }     // does the next step run diagnose / accelerate?
+  bool ceased() const { return ceased_; }
+  int count() const { return count_; }
+  // closes a CRM step; cease: what msa_accelerate returned (false for a step that did not call it).  Returns the step's weight
+  int advance(bool cease) {
+    if (cease) ceased_ = true;
+    int weight = accelerating() ? per_step_ : 1;
+    count_ += weight;
+    return weight;
+  }
+};
+
+struct MsaArrays_ {
+  double *fields[6], *save[4], *tend[4];
+  int *cease;
+};
+
+inline MsaArrays_ msa_arrays_(pam::PamCoupler &coupler) {
+  auto &dm = coupler.get_data_manager_device_readwrite();
+  if (!dm.entry_exists("accel_ceaseflag")) endrun("ERROR: mean-state acceleration: call msa_init first");
+  MsaArrays_ A;
+  std::string micro_scheme = coupler.option_exists("micro") ? coupler.get_option<std::string>("micro") : std::string("none");
+  std::string cloud, ice;
+  if (micro_scheme == "kessler") cloud = "cloud_liquid";
+  else if (micro_scheme == "p3") { cloud = "cloud_water"; ice = "ice"; }
+  else if (micro_scheme != "none") endrun("ERROR: mean-state acceleration only knows the kessler, p3 and none microphysics");
+  A.fields[0] = dm.get<real, 4>("temp").data();
+  A.fields[1] = dm.get<real, 4>("water_vapor").data();
+  A.fields[2] = cloud.empty() ? nullptr : (double *)dm.get<real const, 4>(cloud).data();
+  A.fields[3] = ice.empty() ? nullptr : (double *)dm.get<real const, 4>(ice).data();
+  A.fields[4] = dm.get<real, 4>("uvel").data();
+  A.fields[5] = dm.get<real, 4>("vvel").data();
+  const char *q[4] = {"t", "q", "u", "v"};
+  for (int i = 0; i < 4; i++) {
+    A.save[i] = dm.get<real, 2>(std::string("accel_save_") + q[i]).data();
+    A.tend[i] = dm.get<real, 2>(std::string("accel_tend_") + q[i]).data();
+  }
+  A.cease = dm.get<int, 1>("accel_ceaseflag").data();
+  return A;
+}
+
+inline void msa_init(pam::PamCoupler &coupler) {
+  int nz = coupler.get_nz(), nens = coupler.get_nens();
+  auto &dm = coupler.get_data_manager_device_readwrite();
+  if (!coupler.option_exists("crm_accel_factor")) endrun("ERROR: mean-state acceleration: option crm_accel_factor is not set");
+  real a = coupler.get_option<real>("crm_accel_factor");
+  if (!(a >= 0) || !std::isfinite(a)) endrun("ERROR: mean-state acceleration: crm_accel_factor must be finite and >= 0");
+  if (!coupler.option_exists("crm_accel_uv")) coupler.set_option<bool>("crm_accel_uv", false);
+  if (!coupler.option_exists("crm_accel_max_ttend")) coupler.set_option<real>("crm_accel_max_ttend", 5.0);
+  if (!(coupler.get_option<real>("crm_accel_max_ttend") > 0)) endrun("ERROR: mean-state acceleration: crm_accel_max_ttend must be positive");
+  if (!dm.entry_exists("accel_ceaseflag")) {
+    const char *q[4] = {"t", "q", "u", "v"};
+    for (int i = 0; i < 4; i++) {
+      dm.register_and_allocate<real>(std::string("accel_save_") + q[i], "level mean at the start of the CRM step", {nz, nens}, {"z", "nens"});
+      dm.register_and_allocate<real>(std::string("accel_tend_") + q[i], "change of the level mean over the CRM step", {nz, nens}, {"z", "nens"});
+    }
+    dm.register_and_allocate<int>("accel_ceaseflag", "mean-state acceleration ceased in this GCM step", {1});
+  }
+  if (hipMemsetAsync(dm.get<int, 1>("accel_ceaseflag").data(), 0, sizeof(int), 0) != hipSuccess) endrun("ERROR: mean-state acceleration: memset failed");
+  coupler.set_option<bool>("crm_accel_ceaseflag", false);
+}
+
+inline void msa_diagnose(pam::PamCoupler &coupler) {
+  MsaArrays_ A = msa_arrays_(coupler);
+  int rc = pam_amd_msa_diagnose(coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), A.fields, A.save, nullptr);
+  if (rc) endrun(pam_amd_awfl_last_error());
+}
+
+// all_ranks_or(flag): the flag of the WHOLE ensemble where it is sharded over devices (the cease flag is global over all members,
+// like the dycore's time step); called once, between the tendencies and the apply
+template <class F>
+inline bool msa_accelerate(pam::PamCoupler &coupler, F const &all_ranks_or) {
+  MsaArrays_ A = msa_arrays_(coupler);
+  int nens = coupler.get_nens(), nx = coupler.get_nx(), ny = coupler.get_ny(), nz = coupler.get_nz();
+  int mine = 0;
+  int rc = pam_amd_msa_tendencies(nens, nx, ny, nz, A.fields, A.save, A.tend, coupler.get_option<real>("crm_accel_max_ttend"), A.cease,
+                                  &mine, nullptr);
+  if (rc) endrun(pam_amd_awfl_last_error());
+  int flag = all_ranks_or(mine);
+  if (flag && !mine && hipMemcpy(A.cease, &flag, sizeof(int), hipMemcpyHostToDevice) != hipSuccess) endrun("ERROR: mean-state acceleration: memcpy failed");
+  if (flag) {
+    coupler.set_option<bool>("crm_accel_ceaseflag", true);
+    return true;
+  }
+  rc = pam_amd_msa_apply(nens, nx, ny, nz, A.fields, A.tend, coupler.get_option<real>("crm_accel_factor"),
+                         coupler.get_option<bool>("crm_accel_uv") ? 1 : 0, A.cease, nullptr);
+  if (rc) endrun(pam_amd_awfl_last_error());
+  return false;
+}
+
+inline bool msa_accelerate(pam::PamCoupler &coupler) {
+  return msa_accelerate(coupler, [](int flag) { return flag; });
+}
+
+}  // namespace modules

@@ -44,13 +44,15 @@ inline void time_average_init(pam::PamCoupler &coupler, std::vector<std::string>
   if (rc) endrun(pam_amd_awfl_last_error());
 }
 
-inline void time_average_accumulate(pam::PamCoupler &coupler, std::vector<std::string> var_names) {
+// weight: how many steps of model time this CRM step counts (modules::MsaClock under mean-state acceleration); it multiplies the
+// factor.  The reference's two-argument form below is this one with weight 1, which leaves the factor as it is
+inline void time_average_accumulate(pam::PamCoupler &coupler, std::vector<std::string> var_names, real weight) {
   auto &dm = coupler.get_data_manager_device_readwrite();
   auto crm_dt = coupler.get_option<real>("crm_dt");
   auto gcm_dt = coupler.get_option<real>("gcm_physics_dt");
   if (!(gcm_dt > 0)) endrun("ERROR: time_average_accumulate: gcm_physics_dt must be positive");
-  real factor = crm_dt / gcm_dt;
-  if (!std::isfinite(factor)) endrun("ERROR: time_average_accumulate: crm_dt / gcm_physics_dt is not finite");
+  real factor = crm_dt / gcm_dt * weight;
+  if (!std::isfinite(factor)) endrun("ERROR: time_average_accumulate: crm_dt / gcm_physics_dt x weight is not finite");
   int num_vars = var_names.size();
   std::vector<long long> sizes(num_vars);
   for (int i = 0; i < num_vars; i++) {
@@ -70,6 +72,10 @@ inline void time_average_accumulate(pam::PamCoupler &coupler, std::vector<std::s
   }
   int rc = pam_amd_time_average_accumulate(num_vars, sizes.data(), var.data(), tavg.data(), factor, nullptr);
   if (rc) endrun(pam_amd_awfl_last_error());
+}
+
+inline void time_average_accumulate(pam::PamCoupler &coupler, std::vector<std::string> var_names) {
+  time_average_accumulate(coupler, var_names, 1);
 }
 
 }  // namespace modules

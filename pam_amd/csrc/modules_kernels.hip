@@ -2857,3 +2857,154 @@ extern "C" int pam_amd_p3_main_standin(const pam_amd_p3_args_t *args, void *user
   else hipLaunchKernelGGL((p3_standin_kernel<long long>), grid, block, 0, (hipStream_t)A.stream, A);
   return stats_launch_check(who);
 }
+
+// ------------------------------------------------------------------------------------------------
+// CRM mean-state acceleration (Jones, Bretherton and Pritchard 2015; E3SM-MMF's crm_accel_factor): after a CRM step the change of the
+// horizontal-mean temp, total water and (optionally) winds over that step is applied once more, `a` times, and the step counts as
+// 1 + a steps of model time.  The method is not in the reference tree; the contract is in include/pam_amd_modules.h and DESIGN.md
+// section 8, its arithmetic in msa_device.h.  The level means are built on the slot order of the sponge layer and the GCM forcing
+// (slot_reduce above): a workgroup = (level, block of up to 64 members) x 16 slots, lanes are consecutive members, every step of a walk
+// is one coalesced row per field.  No scratch, no floating-point atomics; every element offset is 64 bits wide (one instance).
+#include "msa_device.h"
+
+namespace {
+namespace ms = pama::msa;
+struct MsaFields { const double *p[ms::NF]; };
+struct MsaIn { const double *p[ms::NQ]; };
+struct MsaOut { double *p[ms::NQ]; };
+
+// one sweep over up to six fields -> M(temp), M(vapour + cloud + ice), M(uvel), M(vvel) of every (level, member).  SAVE: they are the
+// saved means of msa_diagnose; otherwise out = mean - save, and a lane whose temperature tendency is not within max_ttend raises the
+// (sticky, integer) cease word.  grid (member blocks, levels), block (members, 16 slots)
+template <bool SAVE>
+__global__ void __launch_bounds__(64 * MOD_NS) msa_mean_kernel(int nens, int ncol, MsaFields F, MsaIn save, MsaOut out, double max_ttend,
+                                                               int *cease) {
+  __shared__ double red[ms::NQ * MOD_NS * 64];
+  const int ME = blockDim.x, slot = threadIdx.y;
+  const int e0 = (int)blockIdx.x * ME + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1, k = (int)blockIdx.y;
+  const long long base = (long long)k * ncol * nens + e;
+  const double *f[ms::NF];
+#pragma unroll
+  for (int i = 0; i < ms::NF; i++) f[i] = F.p[i] ? F.p[i] + base : nullptr;
+  double acc[ms::NQ] = {0.0, 0.0, 0.0, 0.0};
+  if (ok) ms::mean_walk(f, (long long)nens, ncol, slot, acc);
+  slot_reduce<ms::NQ>(acc, red);
+  if (slot != 0 || !ok) return;
+  const long long t = (long long)k * nens + e;
+#pragma unroll
+  for (int q = 0; q < ms::NQ; q++) {
+    if constexpr (SAVE) {
+      out.p[q][t] = acc[q];
+    } else {
+      const double tend = ms::tendency(acc[q], save.p[q][t]);
+      out.p[q][t] = tend;
+      if (q == ms::Q_T && ms::ceases(tend, max_ttend)) atomicOr(cease, 1);
+    }
+  }
+}
+
+// two sweeps per (level, member): P and N of the incremented vapour (water_vapor alone is read), then every cell read and written
+// once -- the vapour's second read comes out of the caches where the workgroup's strip still sits there.  Writes nothing when the
+// cease word is set.  grid and block as above
+__global__ void __launch_bounds__(64 * MOD_NS) msa_apply_kernel(int nens, int ncol, double *temp, double *vapor, double *uvel, double *vvel,
+                                                                MsaIn tend, double accel_factor, int accel_uv, const int *cease) {
+  __shared__ double red[2 * MOD_NS * 64];
+  if (cease && *cease != 0) return;      // the same word for every lane of the grid
+  const int ME = blockDim.x, slot = threadIdx.y;
+  const int e0 = (int)blockIdx.x * ME + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1, k = (int)blockIdx.y;
+  const long long base = (long long)k * ncol * nens + e, t = (long long)k * nens + e, stride = nens;
+  const double d_t = ms::increment(accel_factor, tend.p[ms::Q_T][t]), d_q = ms::increment(accel_factor, tend.p[ms::Q_Q][t]);
+  double d_u = 0.0, d_v = 0.0;
+  if (accel_uv) {
+    d_u = ms::increment(accel_factor, tend.p[ms::Q_U][t]);
+    d_v = ms::increment(accel_factor, tend.p[ms::Q_V][t]);
+  }
+  double pn[2] = {0.0, 0.0};
+  if (ok) ms::vapor_walk(vapor + base, stride, ncol, slot, d_q, pn);
+  slot_reduce<2>(pn, red);
+  if (!ok) return;
+  double factor;
+  const int mode = ms::vapor_mode(pn[0], pn[1], factor);
+  ms::apply_walk(temp + base, vapor + base, accel_uv ? uvel + base : nullptr, accel_uv ? vvel + base : nullptr, stride, ncol, slot, d_t,
+                 d_q, d_u, d_v, accel_uv != 0, mode, factor);
+}
+
+int msa_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
+
+// the checks the three entry points share, all before the first HIP call
+int msa_check(const char *who, int nens, int nx, int ny, int nz, const double *const *fields, bool need_uv, const double *const *a,
+              const double *const *b) {
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return msa_error(who, "nens, nx, ny and nz must be >= 1");
+  if ((long long)nx * ny > 0x7fffffffLL) return msa_error(who, "ny x nx exceeds 2^31 - 1 columns");
+  if (nz > 65535) return msa_error(who, "nz exceeds the grid (65535 levels)");
+  if (!fields || !a || !b) return msa_error(who, "null pointer table");
+  if (!fields[ms::F_TEMP] || !fields[ms::F_VAPOR]) return msa_error(who, "null temp or water_vapor pointer");
+  if (need_uv && (!fields[ms::F_U] || !fields[ms::F_V])) return msa_error(who, "null uvel or vvel pointer");
+  for (int q = 0; q < ms::NQ; q++)
+    if (!a[q] || !b[q]) return msa_error(who, "null pointer in a table of (nz,nens) arrays");
+  return PAM_AMD_OK;
+}
+
+void msa_launch_shape(int nens, int nz, dim3 &grid, dim3 &block) {
+  const int ME = nens < 64 ? nens : 64;
+  grid = dim3((unsigned)((nens + ME - 1) / ME), (unsigned)nz);
+  block = dim3((unsigned)ME, (unsigned)MOD_NS);
+}
+
+template <bool SAVE>
+int msa_mean_launch(const char *who, int nens, int nx, int ny, int nz, const double *const *fields, const double *const *save,
+                    double *const *out, double max_ttend, int *cease, void *stream) {
+  MsaFields F;
+  MsaIn S;
+  MsaOut O;
+  for (int i = 0; i < ms::NF; i++) F.p[i] = fields[i];
+  for (int q = 0; q < ms::NQ; q++) { S.p[q] = save ? save[q] : nullptr; O.p[q] = out[q]; }
+  dim3 grid, block;
+  msa_launch_shape(nens, nz, grid, block);
+  hipLaunchKernelGGL((msa_mean_kernel<SAVE>), grid, block, 0, (hipStream_t)stream, nens, nx * ny, F, S, O, max_ttend, cease);
+  return stats_launch_check(who);
+}
+}  // namespace
+
+extern "C" int pam_amd_msa_diagnose(int nens, int nx, int ny, int nz, const double *const *fields, double *const *save, void *stream) {
+  const char *who = "msa_diagnose";
+  if (int rc = msa_check(who, nens, nx, ny, nz, fields, true, save, save)) return rc;
+  if (int rc = moist_surface_device_check(who)) return rc;
+  return msa_mean_launch<true>(who, nens, nx, ny, nz, fields, nullptr, save, 0.0, nullptr, stream);
+}
+
+extern "C" int pam_amd_msa_tendencies(int nens, int nx, int ny, int nz, const double *const *fields, const double *const *save,
+                                      double *const *tend, double max_ttend, int *cease_dev, int *cease_host, void *stream) {
+  const char *who = "msa_tendencies";
+  if (int rc = msa_check(who, nens, nx, ny, nz, fields, true, save, tend)) return rc;
+  if (!(max_ttend > 0)) return msa_error(who, "max_ttend must be a positive number");
+  if (!cease_dev) return msa_error(who, "null cease_dev");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  if (int rc = msa_mean_launch<false>(who, nens, nx, ny, nz, fields, save, tend, max_ttend, cease_dev, stream)) return rc;
+  if (cease_host) {      // the one synchronisation of the call, for 4 bytes
+    if (hipMemcpyAsync(cease_host, cease_dev, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+        hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+      return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "msa_tendencies: reading the cease word back failed");
+  }
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_msa_apply(int nens, int nx, int ny, int nz, double *const *fields, const double *const *tend, double accel_factor,
+                                 int accel_uv, const int *cease_dev, void *stream) {
+  const char *who = "msa_apply";
+  if (int rc = msa_check(who, nens, nx, ny, nz, fields, accel_uv != 0, tend, tend)) return rc;
+  if (!(accel_factor >= 0) || !std::isfinite(accel_factor)) return msa_error(who, "accel_factor must be finite and >= 0");
+  if (accel_factor == 0) return PAM_AMD_OK;      // nothing to apply: no launch
+  if (int rc = moist_surface_device_check(who)) return rc;
+  MsaIn T;
+  for (int q = 0; q < ms::NQ; q++) T.p[q] = tend[q];
+  dim3 grid, block;
+  msa_launch_shape(nens, nz, grid, block);
+  hipLaunchKernelGGL(msa_apply_kernel, grid, block, 0, (hipStream_t)stream, nens, nx * ny, fields[ms::F_TEMP], fields[ms::F_VAPOR],
+                     fields[ms::F_U], fields[ms::F_V], T, accel_factor, accel_uv != 0 ? 1 : 0, cease_dev);
+  return stats_launch_check(who);
+}

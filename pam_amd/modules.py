@@ -289,10 +289,11 @@ def time_average_init(coupler, names):
                                             torch.cuda.current_stream(coupler.device).cuda_stream))
 
 
-def time_average_accumulate(coupler, names):
+def time_average_accumulate(coupler, names, weight=1):
     """modules::time_average_accumulate(coupler, names)  (time_average.h:39-72; every CRM step): "<name>_time_average" +=
     name * (crm_dt / gcm_physics_dt), element by element.  Options "crm_dt", "gcm_physics_dt" (> 0).  The whole list is validated
-    first: a name without its time average (no init) raises and nothing is written."""
+    first: a name without its time average (no init) raises and nothing is written.  weight: how many steps of model time this CRM
+    step counts (MsaClock under mean-state acceleration); it multiplies the factor, and 1 leaves it as it is."""
     import math
     from .coupler import endrun
     lib = capi.load()
@@ -300,9 +301,9 @@ def time_average_accumulate(coupler, names):
     gcm_dt = float(coupler.get_option("gcm_physics_dt"))
     if not gcm_dt > 0:
         endrun("ERROR: time_average_accumulate: gcm_physics_dt must be positive")
-    factor = crm_dt / gcm_dt
+    factor = crm_dt / gcm_dt * float(weight)
     if not math.isfinite(factor):
-        endrun("ERROR: time_average_accumulate: crm_dt / gcm_physics_dt is not finite")
+        endrun("ERROR: time_average_accumulate: crm_dt / gcm_physics_dt x weight is not finite")
     dm = coupler.get_data_manager_device_readwrite()
     names = list(names)
     shapes = []
@@ -409,3 +410,134 @@ def field_diagnostics(tensors, members=0):
                                                     out["argmax"].ctypes.data_as(lp), out["nan_count"].ctypes.data_as(lp),
                                                     torch.cuda.current_stream(device).cuda_stream))
     return out
+
+
+# ---- CRM mean-state acceleration (Jones, Bretherton and Pritchard 2015; E3SM-MMF's crm_accel_factor, crm_accel_uv).  Not part of the
+# reference tree: the contract is this project's (include/pam_amd_modules.h; numpy restatement: tests/msa_ref.py)
+MSA_CONDENSATE = {"kessler": ("cloud_liquid", None), "p3": ("cloud_water", "ice"), "none": (None, None)}
+MSA_QUANTITIES = ("t", "q", "u", "v")
+
+
+class MsaClock:
+    """The step clock of an accelerated CRM loop (the twin of modules::MsaClock).  nstop: unaccelerated CRM steps per GCM step;
+    1 + accel_factor must be an integer that divides it (as E3SM requires), otherwise the constructor raises.  A step that was
+    accelerated counts 1 + accel_factor steps of model time; the step that raised the cease flag counts 1, and so does every later step
+    of the GCM step.  The count is an integer and cannot overshoot nstop; advance() returns the step's weight in
+    time_average_accumulate."""
+
+    def __init__(self, nstop, accel_factor):
+        import math
+        from .coupler import endrun
+        if int(nstop) != nstop or nstop < 1:
+            endrun("ERROR: mean-state acceleration: nstop must be >= 1")
+        a = float(accel_factor)
+        if not (a >= 0) or not math.isfinite(a):
+            endrun("ERROR: mean-state acceleration: crm_accel_factor must be finite and >= 0")
+        steps = 1 + a
+        if steps != math.floor(steps) or steps > nstop or int(nstop) % int(steps) != 0:
+            endrun("ERROR: mean-state acceleration: 1 + crm_accel_factor must be an integer that divides the number of CRM steps")
+        self.nstop, self.per_step, self.count, self.ceased = int(nstop), int(steps), 0, False
+
+    def done(self):
+        return self.count >= self.nstop
+
+    def accelerating(self):
+        """does the next step run msa_diagnose / msa_accelerate?"""
+        return not self.ceased and self.per_step > 1
+
+    def advance(self, cease):
+        """closes a CRM step; cease: what msa_accelerate returned (False for a step that did not call it)"""
+        if cease:
+            self.ceased = True
+        weight = self.per_step if self.accelerating() else 1
+        self.count += weight
+        return weight
+
+
+def _msa_arrays(coupler):
+    from .coupler import endrun
+    dm = coupler.get_data_manager_device_readwrite()
+    if not dm.entry_exists("accel_ceaseflag"):
+        endrun("ERROR: mean-state acceleration: call msa_init first")
+    micro = coupler.get_option("micro") if coupler.option_exists("micro") else "none"
+    if micro not in MSA_CONDENSATE:
+        endrun("ERROR: mean-state acceleration only knows the kessler, p3 and none microphysics")
+    cloud, ice = MSA_CONDENSATE[micro]
+    fields = [dm.get("temp"), dm.get("water_vapor"), dm.get(cloud, readonly=True) if cloud else None,
+              dm.get(ice, readonly=True) if ice else None, dm.get("uvel"), dm.get("vvel")]
+    save = [dm.get("accel_save_" + q) for q in MSA_QUANTITIES]
+    tend = [dm.get("accel_tend_" + q) for q in MSA_QUANTITIES]
+    return fields, save, tend, dm.get("accel_ceaseflag")
+
+
+def _msa_table(tensors):
+    return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def msa_init(coupler):
+    """First in every GCM step: registers "accel_save_{t,q,u,v}", "accel_tend_{t,q,u,v}" (nz,nens) and the cease word "accel_ceaseflag"
+    (int32) on first use, zeroes the word and sets option "crm_accel_ceaseflag" = False.  Options: "crm_accel_factor" (>= 0, required),
+    "crm_accel_uv" (default False), "crm_accel_max_ttend" (default 5 K)."""
+    import math
+    from .coupler import endrun
+    if not coupler.option_exists("crm_accel_factor"):
+        endrun("ERROR: mean-state acceleration: option crm_accel_factor is not set")
+    a = float(coupler.get_option("crm_accel_factor"))
+    if not (a >= 0) or not math.isfinite(a):
+        endrun("ERROR: mean-state acceleration: crm_accel_factor must be finite and >= 0")
+    if not coupler.option_exists("crm_accel_uv"):
+        coupler.set_option("crm_accel_uv", False)
+    if not coupler.option_exists("crm_accel_max_ttend"):
+        coupler.set_option("crm_accel_max_ttend", 5.0)
+    if not float(coupler.get_option("crm_accel_max_ttend")) > 0:
+        endrun("ERROR: mean-state acceleration: crm_accel_max_ttend must be positive")
+    nz, nens = coupler.get_nz(), coupler.get_nens()
+    dm = coupler.get_data_manager_device_readwrite()
+    if not dm.entry_exists("accel_ceaseflag"):
+        for q in MSA_QUANTITIES:
+            dm.register_and_allocate("accel_save_" + q, "level mean at the start of the CRM step", (nz, nens), ("z", "nens"))
+            dm.register_and_allocate("accel_tend_" + q, "change of the level mean over the CRM step", (nz, nens), ("z", "nens"))
+        dm.register_and_allocate("accel_ceaseflag", "mean-state acceleration ceased in this GCM step", (1,), dtype=torch.int32)
+    dm.get("accel_ceaseflag").zero_()
+    coupler.set_option("crm_accel_ceaseflag", False)
+
+
+def msa_diagnose(coupler):
+    """First in a CRM step, before GCM forcing: saves the level means of temp, total water (water_vapor + cloud + ice, by option
+    "micro"), uvel and vvel.  Writes nothing else."""
+    lib = capi.load()
+    fields, save, _, _ = _msa_arrays(coupler)
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_msa_diagnose(coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), _msa_table(fields),
+                                       _msa_table(save), torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+def msa_accelerate(coupler, group=None):
+    """After the last module of a CRM step: the change of the level means over the step, applied once more crm_accel_factor times
+    (temp, water vapour with its negative values filled from the level, and with crm_accel_uv the winds).  Returns True where the
+    acceleration ceased -- a temperature tendency beyond crm_accel_max_ttend, or not a number, in ANY member -- and nothing was applied;
+    the flag stays up until the next msa_init.  group: the ensemble is sharded over the ranks of this torch.distributed group; the
+    flag goes through one 4-byte all-reduce(MAX) between the tendencies and the apply, like the dycore's time step
+    (pam_amd/parallel.py).  One 4-byte read-back synchronises the stream."""
+    import torch.distributed as dist
+    lib = capi.load()
+    fields, save, tend, cease = _msa_arrays(coupler)
+    nens, nx, ny, nz = coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz()
+    mine = C.c_int(0)
+    with torch.cuda.device(coupler.device):
+        stream = torch.cuda.current_stream(coupler.device).cuda_stream
+        check(lib.pam_amd_msa_tendencies(nens, nx, ny, nz, _msa_table(fields), _msa_table(save), _msa_table(tend),
+                                         float(coupler.get_option("crm_accel_max_ttend")), cease.data_ptr(), C.byref(mine), stream))
+        flag = mine.value
+        if group is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            t = cease if dist.get_backend(group) == "nccl" else torch.tensor([flag], dtype=torch.int32)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+            flag = int(t.item())
+            if flag and not mine.value:
+                cease.fill_(1)
+        if flag:
+            coupler.set_option("crm_accel_ceaseflag", True)
+            return True
+        check(lib.pam_amd_msa_apply(nens, nx, ny, nz, _msa_table(fields), _msa_table(tend), float(coupler.get_option("crm_accel_factor")),
+                                    1 if coupler.get_option("crm_accel_uv") else 0, cease.data_ptr(), stream))
+    return False

@@ -7,7 +7,9 @@ Run on the GPU box:  python tools/bench_modules.py            (--only vertical_i
 --only validate: DataManager.validate_all's device scan with the two statistics rows of the same run beside it;
 --only diagnostics: pam_amd.field_diagnostics whole-field and per-member, with the validation and time_average_accumulate rows;
 --only shoc: the SHOC coupling layer's pack and unpack in both layouts, both tracer sets, beside the composition the reference performs;
---only p3: the P3 coupling layer's pack (with and without the saturation adjustment) and unpack in both layouts, beside its composition)"""
+--only p3: the P3 coupling layer's pack (with and without the saturation adjustment) and unpack in both layouts, beside its composition;
+--only msa: mean-state acceleration's diagnose, tendencies and apply (with and without the winds), beside horizontal_average and
+time_average_accumulate of the same run)"""
 import json
 import os
 import sys
@@ -650,8 +652,88 @@ def p3_timing(dev, n=11):
     return out
 
 
+def msa_timing(dev, warmup=3, n=11):
+    """CRM mean-state acceleration at the C2 grid on P3's names (temp, water_vapor, cloud_water, ice, uvel, vvel: all six fields of the
+    level means are read): pam_amd_msa_diagnose, pam_amd_msa_tendencies (no host flag: nothing synchronises) and pam_amd_msa_apply
+    with and without the winds, 3 warm-up calls and the median of 11 event-timed calls each.  Algorithmic bytes: six fields read for a
+    mean; temp, water_vapor (and uvel, vvel) read and written once for the apply -- its second read of the vapour is NOT counted, so
+    a sweep that misses the caches shows as a lower fraction.  horizontal_average and time_average_accumulate of the same eight fields
+    (the five state fields and the three tracers) run beside them as yardsticks."""
+    import ctypes as C
+    from pam_amd import PamCoupler, capi, modules
+    from pam_amd import idealized as idz
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    cells = nens * nx * ny * nz
+    c = PamCoupler(dev)
+    c.set_option("crm_dt", 2.0)
+    c.set_option("gcm_physics_dt", 900.0)
+    c.allocate_coupler_state(nz, ny, nx, nens)
+    c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+    for t in ("water_vapor", "cloud_water", "ice"):
+        c.add_tracer(t, "", True, True)
+    c.set_option("micro", "p3")
+    c.set_option("crm_accel_factor", 2.0)
+    c.set_option("crm_accel_uv", True)
+    dm = c.get_data_manager_device_readwrite()
+    names = ["density_dry", "uvel", "vvel", "wvel", "temp"] + c.get_tracer_names()
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for name in names:
+        t = dm.get(name)
+        t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev))
+    modules.msa_init(c)
+    modules.time_average_init(c, names)
+    havg = [(name, True) for name in names]
+    lib = capi.load()
+    fields, save, tend, cease = modules._msa_arrays(c)
+    F, S, T = modules._msa_table(fields), modules._msa_table(save), modules._msa_table(tend)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2]
+
+    def row(t, nbytes, **more):
+        return dict({"ms": t, "bytes": nbytes, "GBps": nbytes / t / 1e6, "hbm_frac": nbytes / t / 1e6 / bench.HBM_PEAK_GBS}, **more)
+
+    out = {"msa_grid": "1024 x 32x32x60 (C2)", "msa_method": "%d warm-up calls, median of %d event-timed calls" % (warmup, n)}
+    out["time_average_accumulate_8_fields"] = row(timed(lambda: modules.time_average_accumulate(c, names)), len(names) * cells * 24.0)
+    out["horizontal_average_8_fields"] = row(timed(lambda: modules.horizontal_average(c, havg)), len(names) * cells * 8.0)
+    out["msa_diagnose"] = row(timed(lambda: capi.check(lib.pam_amd_msa_diagnose(nens, nx, ny, nz, F, S, stream))), 6 * cells * 8.0)
+    for name in ("temp", "water_vapor", "uvel", "vvel"):            # a step's worth of change, so that the tendencies are not zero
+        dm.get(name).mul_(1.001)
+    out["msa_tendencies"] = row(timed(lambda: capi.check(lib.pam_amd_msa_tendencies(nens, nx, ny, nz, F, S, T, 5.0, cease.data_ptr(), None,
+                                                                                      stream))), 6 * cells * 8.0)
+    assert int(cease.item()) == 0
+    for uv, label, nf in ((1, "msa_apply_accel_uv", 4), (0, "msa_apply", 2)):
+        t = timed(lambda: capi.check(lib.pam_amd_msa_apply(nens, nx, ny, nz, F, T, 2.0, uv, cease.data_ptr(), stream)))
+        out[label] = row(t, nf * cells * 16.0, worst_case_bytes=(nf * 2 + 1) * cells * 8.0,
+                         worst_case_hbm_frac=(nf * 2 + 1) * cells * 8.0 / t / 1e6 / bench.HBM_PEAK_GBS)
+    out["msa_diagnose_vs_horizontal_average_frac"] = out["msa_diagnose"]["hbm_frac"] / out["horizontal_average_8_fields"]["hbm_frac"]
+    out["msa_tendencies_vs_horizontal_average_frac"] = out["msa_tendencies"]["hbm_frac"] / out["horizontal_average_8_fields"]["hbm_frac"]
+    out["msa_apply_accel_uv_vs_time_average_accumulate_frac"] = out["msa_apply_accel_uv"]["hbm_frac"] / out["time_average_accumulate_8_fields"]["hbm_frac"]
+    out["msa_apply_vs_time_average_accumulate_frac"] = out["msa_apply"]["hbm_frac"] / out["time_average_accumulate_8_fields"]["hbm_frac"]
+    out["msa_per_crm_step_ms"] = out["msa_diagnose"]["ms"] + out["msa_tendencies"]["ms"] + out["msa_apply_accel_uv"]["ms"]
+    assert bool(torch.isfinite(dm.get("temp", readonly=True)).all())
+    del dm, c, fields, save, tend
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "msa"]:
+        print(json.dumps(msa_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "shoc"]:
         print(json.dumps(shoc_timing(dev)))
         sys.exit(0)
