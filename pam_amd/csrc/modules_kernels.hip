@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -25,6 +26,7 @@
 #include "diagnostics_device.h"      // field diagnostics: the per-element update, a thread's share of a chunk and the folds, the same
 #include "shoc_device.h"             // the SHOC coupling layer: pack, unpack, the index and the stand-in for shoc_main, the same
 #include "p3_device.h"               // the P3 coupling layer: the adjustment, pack, unpack, the index and the stand-in for p3_main
+#include "coupling_workspace.h"      // where the arrays of the two layers' workspaces lie: host arithmetic only
 
 namespace {
 
@@ -2049,6 +2051,102 @@ extern "C" int pam_amd_compute_pressure(int nens, int nx, int ny, int nz, const 
 }
 
 // ------------------------------------------------------------------------------------------------
+// What the SHOC and the P3 coupling layer below share: the tile of their kernels, the choice of a kernel instance and the workspace -- ONE
+// device allocation per layer that holds every array of its args struct between canary words (coupling_workspace.h says where each lies).
+namespace {
+namespace cw = pama::coupling;
+constexpr int COUPLING_THREADS = 256;
+constexpr int COUPLING_GROUP = 8;                  // arrays that cross LDS per pair of barriers (layout 1)
+constexpr long long COUPLING_NARROW = 1ll << 29;   // the largest array from this size on: the long long instances
+template <int LAYOUT> struct CouplingTile { static constexpr int TC = LAYOUT ? 16 : 64, TL = COUPLING_THREADS / TC, PITCH = TL + 1; };
+
+int coupling_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
+bool coupling_pos(double x) { return std::isfinite(x) && x > 0; }
+// force_wide: the layer's debug_wide_index switch; largest: the element count of its largest array
+bool coupling_narrow(bool force_wide, long long largest) { return !force_wide && largest < COUPLING_NARROW; }
+// grid (column tiles, level tiles)
+template <int LAYOUT> dim3 coupling_grid(int ncol, int nlev) {
+  using T = CouplingTile<LAYOUT>;
+  return dim3((unsigned)((ncol + T::TC - 1) / T::TC), (unsigned)((nlev + T::TL - 1) / T::TL));
+}
+// f(the layout as a std::integral_constant, a value of the index type): the one choice among (layout 0 / 1) x (unsigned / long long)
+template <class F> void coupling_dispatch(int layout, bool narrow, F &&f) {
+  if (layout == 0) { if (narrow) f(std::integral_constant<int, 0>(), 0u); else f(std::integral_constant<int, 0>(), 0ll); }
+  else { if (narrow) f(std::integral_constant<int, 1>(), 0u); else f(std::integral_constant<int, 1>(), 0ll); }
+}
+
+template <unsigned long long VALUE>
+__global__ void __launch_bounds__(256) coupling_canary_kernel(unsigned long long *p, long long n) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) p[i] = VALUE;
+}
+
+// what a layer's workspace W begins with; W adds its sizes, its args, its MAGIC and NOT_ONE, the message for a handle that is none
+struct CouplingWorkspace {
+  unsigned long long magic;
+  long long doubles;
+  double *base;
+};
+template <class W> W *coupling_ws(void *ws) {
+  W *w = (W *)ws;
+  return (w && w->magic == W::MAGIC) ? w : nullptr;
+}
+
+// the device side of workspace_create: the arrays of `table` in one allocation filled with CANARY -> w->doubles, w->base, the pointers of args
+template <unsigned long long CANARY, class ARGS, int NA>
+int coupling_allocate(const char *who, const cw::Array<ARGS> (&table)[NA], long long N, long long Z, long long T, cw::ZeroSize policy,
+                      CouplingWorkspace *w, ARGS *args) {
+  long long offset[NA];
+  const long long total = cw::carve_table(table, N, Z, T, policy, offset);
+  double *base = nullptr;
+  if (hipMalloc((void **)&base, (size_t)total * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    return pam_amd_set_last_error_(PAM_AMD_ENOMEM, (std::string(who) + ": cannot allocate the workspace").c_str());
+  }
+  hipLaunchKernelGGL((coupling_canary_kernel<CANARY>), dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, 0,
+                     (unsigned long long *)base, total);
+  if (hipDeviceSynchronize() != hipSuccess) {
+    (void)hipFree(base);
+    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": " + hipGetErrorString(hipGetLastError())).c_str());
+  }
+  w->doubles = total;
+  w->base = base;
+  for (int i = 0; i < NA; i++) args->*table[i].ptr = offset[i] < 0 ? nullptr : base + offset[i];
+  return PAM_AMD_OK;
+}
+// true where a row of `table` is null in args that must not be
+template <class ARGS, int NA>
+bool coupling_null_array(const cw::Array<ARGS> (&table)[NA], const ARGS &args, long long N, long long Z, long long T, cw::ZeroSize policy) {
+  for (int i = 0; i < NA; i++)
+    if (!(args.*table[i].ptr) && !cw::may_be_null(table[i], N, Z, T, policy)) return true;
+  return false;
+}
+
+template <class W, class ARGS> int coupling_workspace_args(void *ws, const char *who, ARGS *args) {
+  W *w = coupling_ws<W>(ws);
+  if (!w) return coupling_error(who, W::NOT_ONE);
+  if (!args) return coupling_error(who, "null args");
+  *args = w->args;
+  return PAM_AMD_OK;
+}
+template <class W> int coupling_workspace_bytes(void *ws, const char *who, long long *bytes) {
+  W *w = coupling_ws<W>(ws);
+  if (!w) return coupling_error(who, W::NOT_ONE);
+  if (!bytes) return coupling_error(who, "null bytes");
+  *bytes = w->doubles * (long long)sizeof(double);
+  return PAM_AMD_OK;
+}
+template <class W> int coupling_workspace_destroy(void *ws, const char *who) {
+  if (!ws) return PAM_AMD_OK;
+  W *w = coupling_ws<W>(ws);
+  if (!w) return coupling_error(who, W::NOT_ONE);
+  (void)hipFree(w->base);
+  w->magic = 0;
+  delete w;
+  return PAM_AMD_OK;
+}
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
 // The SHOC coupling layer (physics/sgs/shoc/SGS.h:150-779): pack = the coupler state to every input of shoc_main, unpack = its outputs back,
 // one launch each; the arithmetic lives in shoc_device.h.  A thread owns one cell (k, col), lanes run along col, so every access to the
 // coupler state is a coalesced row.
@@ -2057,20 +2155,14 @@ extern "C" int pam_amd_compute_pressure(int nens, int nx, int ny, int nz, const 
 //   and leaves with lanes along lev: 16 consecutive doubles (128 B) per row on both sides of HBM.  Banks (MI355X: 8-byte stores are served in
 //   groups of 16 consecutive lanes over 32 banks of 4 B, 8-byte loads in halves of 32 lanes over 64 banks): a store group holds 16 columns of one
 //   level, 17 c mod 16 = c: conflict-free; a load half holds 2 columns x 16 levels, offsets [x, x+16) and [x+17, x+33): one bank pair is hit
-//   twice (one extra cycle in 32 lanes).  A pitch of 16 would put all 16 lanes of a store group on one bank pair.  SHOC_GROUP arrays cross per pair of
+//   twice (one extra cycle in 32 lanes).  A pitch of 16 would put all 16 lanes of a store group on one bank pair.  COUPLING_GROUP arrays cross per pair of
 //   barriers (17 KB of LDS).
 // The pack kernel walks the level tiles of its columns from the ground up: a cell's values are computed once; the interface pressure needs pmid
 // and pdel of the cells k-1 and k, which are STAGED in LDS inside a tile and carried in registers from one tile to the next (nothing is recomputed,
 // no halo is re-read).  The tables of pow_pos_fast are staged once per workgroup.
 namespace {
 namespace sh = pama::shoc;
-constexpr int SHOC_THREADS = 256;
-constexpr int SHOC_GROUP = 8;
-constexpr long long SHOC_NARROW = 1ll << 29;   // the largest array from this size on: the long long instances
 constexpr unsigned long long SHOC_CANARY = 0x7ff853484f435f5full;
-constexpr int SHOC_GUARD = 8;                  // doubles
-constexpr int SHOC_NARRAYS = 46;
-template <int LAYOUT> struct ShocTile { static constexpr int TC = LAYOUT ? 16 : 64, TL = SHOC_THREADS / TC, PITCH = TL + 1; };
 
 struct ShocState {
   const double *rho_d, *rho_v, *rho_c, *uvel, *vvel, *wvel, *temp, *tke, *wthv_sec, *tk, *tkh, *cldfrac, *flx_u, *flx_v, *zint, *zmid;
@@ -2083,13 +2175,13 @@ struct ShocCellSrc { const double *p[sh::U_MAX]; signed char comp[sh::U_MAX], nc
 struct ShocStateOut { double *p[sh::S_MAX]; const double *rho_d; };
 
 template <int LAYOUT, class IDX>
-__global__ void __launch_bounds__(SHOC_THREADS) shoc_pack_kernel(ShocState S, ShocCellDst D, ShocColDst E, int ncol_, int nens, int nz, int ntr,
+__global__ void __launch_bounds__(COUPLING_THREADS) shoc_pack_kernel(ShocState S, ShocCellDst D, ShocColDst E, int ncol_, int nens, int nz, int ntr,
                                                                  sh::Consts c, double dx, double dy, const PowTab *__restrict__ tab) {
-  using T = ShocTile<LAYOUT>;
+  using T = CouplingTile<LAYOUT>;
   constexpr int TC = T::TC, TL = T::TL, PITCH = T::PITCH;
   __shared__ PowTab sh_tab;
   __shared__ double sh_p[TL][TC], sh_d[TL][TC];
-  __shared__ double sh_t[LAYOUT ? SHOC_GROUP * TC * PITCH : 1];
+  __shared__ double sh_t[LAYOUT ? COUPLING_GROUP * TC * PITCH : 1];
   kessler_stage_tab(tab, &sh_tab);
   const int tc = (int)threadIdx.x % TC, tl = (int)threadIdx.x / TC;
   const IDX ncol = (IDX)ncol_;
@@ -2164,17 +2256,17 @@ __global__ void __launch_bounds__(SHOC_THREADS) shoc_pack_kernel(ShocState S, Sh
     } else {
       const int k2 = kt * TL + tl2;
 #pragma unroll
-      for (int g = 0; g < (sh::C_MAX + SHOC_GROUP - 1) / SHOC_GROUP; g++) {
-        if (g * SHOC_GROUP < na) {   // uniform over the workgroup
+      for (int g = 0; g < (sh::C_MAX + COUPLING_GROUP - 1) / COUPLING_GROUP; g++) {
+        if (g * COUPLING_GROUP < na) {   // uniform over the workgroup
           __syncthreads();
 #pragma unroll
-          for (int j = 0; j < SHOC_GROUP; j++)
-            if (g * SHOC_GROUP + j < sh::C_MAX) sh_t[(j * TC + tc) * PITCH + tl] = v[g * SHOC_GROUP + j < sh::C_MAX ? g * SHOC_GROUP + j : 0];
+          for (int j = 0; j < COUPLING_GROUP; j++)
+            if (g * COUPLING_GROUP + j < sh::C_MAX) sh_t[(j * TC + tc) * PITCH + tl] = v[g * COUPLING_GROUP + j < sh::C_MAX ? g * COUPLING_GROUP + j : 0];
           __syncthreads();
           if (col2_ok && k2 < nz) {
 #pragma unroll
-            for (int j = 0; j < SHOC_GROUP; j++) {
-              const int a = g * SHOC_GROUP + j;
+            for (int j = 0; j < COUPLING_GROUP; j++) {
+              const int a = g * COUPLING_GROUP + j;
               if (a < na) D.p[a][sh::offset_t<IDX>(1, col2, nz - 1 - k2, ncol, nz, D.comp[a], D.ncomp[a])] = sh_t[(j * TC + tc2) * PITCH + tl2];
             }
           }
@@ -2194,10 +2286,10 @@ __global__ void __launch_bounds__(SHOC_THREADS) shoc_pack_kernel(ShocState S, Sh
 
 // grid (column tiles, level tiles)
 template <int LAYOUT, class IDX>
-__global__ void __launch_bounds__(SHOC_THREADS) shoc_unpack_kernel(ShocCellSrc R, ShocStateOut O, int ncol_, int nz, int ntr, sh::Consts c) {
-  using T = ShocTile<LAYOUT>;
+__global__ void __launch_bounds__(COUPLING_THREADS) shoc_unpack_kernel(ShocCellSrc R, ShocStateOut O, int ncol_, int nz, int ntr, sh::Consts c) {
+  using T = CouplingTile<LAYOUT>;
   constexpr int TC = T::TC, TL = T::TL, PITCH = T::PITCH;
-  __shared__ double sh_t[LAYOUT ? SHOC_GROUP * TC * PITCH : 1];
+  __shared__ double sh_t[LAYOUT ? COUPLING_GROUP * TC * PITCH : 1];
   const int tc = (int)threadIdx.x % TC, tl = (int)threadIdx.x / TC;
   const IDX ncol = (IDX)ncol_;
   const long long col_ll = (long long)blockIdx.x * TC + tc;
@@ -2221,18 +2313,18 @@ __global__ void __launch_bounds__(SHOC_THREADS) shoc_unpack_kernel(ShocCellSrc R
     const bool ok2 = col2_ll < ncol_ && k2 < nz;
     const IDX col2 = (IDX)(col2_ll < ncol_ ? col2_ll : ncol_ - 1);
 #pragma unroll
-    for (int g = 0; g < (sh::U_MAX + SHOC_GROUP - 1) / SHOC_GROUP; g++) {
-      if (g * SHOC_GROUP < na) {   // uniform over the workgroup
+    for (int g = 0; g < (sh::U_MAX + COUPLING_GROUP - 1) / COUPLING_GROUP; g++) {
+      if (g * COUPLING_GROUP < na) {   // uniform over the workgroup
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < SHOC_GROUP; j++) {
-          const int a = g * SHOC_GROUP + j;
+        for (int j = 0; j < COUPLING_GROUP; j++) {
+          const int a = g * COUPLING_GROUP + j;
           if (a < na && ok2) sh_t[(j * TC + tc2) * PITCH + tl2] = R.p[a][sh::offset_t<IDX>(1, col2, nz - 1 - k2, ncol, nz, R.comp[a], R.ncomp[a])];
         }
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < SHOC_GROUP; j++)
-          if (g * SHOC_GROUP + j < sh::U_MAX && g * SHOC_GROUP + j < na) in[g * SHOC_GROUP + j < sh::U_MAX ? g * SHOC_GROUP + j : 0] = sh_t[(j * TC + tc) * PITCH + tl];
+        for (int j = 0; j < COUPLING_GROUP; j++)
+          if (g * COUPLING_GROUP + j < sh::U_MAX && g * COUPLING_GROUP + j < na) in[g * COUPLING_GROUP + j < sh::U_MAX ? g * COUPLING_GROUP + j : 0] = sh_t[(j * TC + tc) * PITCH + tl];
       }
     }
   }
@@ -2252,38 +2344,15 @@ __global__ void __launch_bounds__(64) shoc_standin_kernel(pam_amd_shoc_args_t A)
   if (col < A.ncol) sh::standin_column<IDX>(A, (IDX)col);
 }
 
-__global__ void __launch_bounds__(256) shoc_canary_kernel(unsigned long long *p, long long n) {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) p[i] = SHOC_CANARY;
-}
-
-struct ShocWorkspace {
-  unsigned long long magic;
+struct ShocWorkspace : CouplingWorkspace {
+  static constexpr unsigned long long MAGIC = 0x53484f4357533031ull;
+  static constexpr const char *NOT_ONE = "not a workspace of shoc_workspace_create";
   int nens, nx, ny, nz, ntr, layout;
-  long long doubles;
-  double *base;
   pam_amd_shoc_args_t args;
 };
-constexpr unsigned long long SHOC_MAGIC = 0x53484f4357533031ull;
-ShocWorkspace *shoc_ws(void *ws) {
-  ShocWorkspace *w = (ShocWorkspace *)ws;
-  return (w && w->magic == SHOC_MAGIC) ? w : nullptr;
-}
 bool g_shoc_force_wide = false;   // pam_amd_shoc_debug_wide_index: tests run the long long instances at small sizes
-long long shoc_round8(long long n) { return (n + 7) / 8 * 8; }
-int shoc_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
-bool shoc_pos(double x) { return std::isfinite(x) && x > 0; }
-// element count of the largest array of a workspace
-long long shoc_largest(const ShocWorkspace *w) {
-  const long long ncol = (long long)w->ny * w->nx * w->nens;
-  return std::max<long long>(std::max(2, w->ntr) * (long long)w->nz * ncol, (long long)(w->nz + 1) * ncol);
-}
-// the sizes of the arrays, in the order of the struct's pointers
-void shoc_sizes(long long N, long long Z, long long T, long long (&n)[SHOC_NARRAYS]) {
-  const long long zi = (Z + 1) * N, zn = Z * N;
-  const long long s[SHOC_NARRAYS] = {N, N, zn, zn, zi, zn, zi, zn, N, N, N, N, T * N, zn, zn, N, zn, zn, zn, zn, 2 * zn, T * zn, zn, zn, zn, zn,
-                                     N, N, N, zn, zn, zn, zi, zi, zi, zi, zi, zi, zi, zi, zi, zn, zn, zn, zn, zn};
-  for (int i = 0; i < SHOC_NARRAYS; i++) n[i] = s[i];
-}
+// element count of the largest array: hwind or qtracers, an interface array on a single level
+long long shoc_largest(long long ncol, long long nz, long long ntr) { return std::max(std::max(2ll, ntr) * nz * ncol, (nz + 1) * ncol); }
 }  // namespace
 
 extern "C" int pam_amd_shoc_debug_wide_index(int on) {
@@ -2293,74 +2362,31 @@ extern "C" int pam_amd_shoc_debug_wide_index(int on) {
 
 extern "C" int pam_amd_shoc_workspace_create(int nens, int nx, int ny, int nz, int num_qtracers, int layout, void **ws) {
   const char *who = "shoc_workspace_create";
-  if (!ws) return shoc_error(who, "null ws");
+  if (!ws) return coupling_error(who, "null ws");
   *ws = nullptr;
-  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return shoc_error(who, "nens, nx, ny and nz must be >= 1");
-  if (num_qtracers < 0 || num_qtracers > sh::MAX_QTRACERS) return shoc_error(who, "num_qtracers must be 0 ... 7");
-  if (layout != 0 && layout != 1) return shoc_error(who, "layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)");
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return coupling_error(who, "nens, nx, ny and nz must be >= 1");
+  if (num_qtracers < 0 || num_qtracers > sh::MAX_QTRACERS) return coupling_error(who, "num_qtracers must be 0 ... 7");
+  if (layout != 0 && layout != 1) return coupling_error(who, "layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)");
   const long long ncol = (long long)ny * nx * nens;
-  if (ncol > 0x7fffffffLL - 64 || nz > 0x7ffffff0) return shoc_error(who, "ny x nx x nens must stay below 2^31");
+  if (ncol > 0x7fffffffLL - 64 || nz > 0x7ffffff0) return coupling_error(who, "ny x nx x nens must stay below 2^31");
   if (int rc = moist_surface_device_check(who)) return rc;
-  long long n[SHOC_NARRAYS], total = SHOC_GUARD;
-  shoc_sizes(ncol, nz, num_qtracers, n);
-  for (int i = 0; i < SHOC_NARRAYS; i++) total += shoc_round8(n[i]) + SHOC_GUARD;
-  double *base = nullptr;
-  if (hipMalloc((void **)&base, (size_t)total * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "shoc_workspace_create: cannot allocate the workspace");
-  }
-  hipLaunchKernelGGL(shoc_canary_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, 0,
-                     (unsigned long long *)base, total);
-  if (hipDeviceSynchronize() != hipSuccess) {
-    (void)hipFree(base);
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": " + hipGetErrorString(hipGetLastError())).c_str());
-  }
-  ShocWorkspace *w = new ShocWorkspace();
-  w->magic = SHOC_MAGIC;
+  std::unique_ptr<ShocWorkspace> w(new ShocWorkspace());
   w->nens = nens; w->nx = nx; w->ny = ny; w->nz = nz; w->ntr = num_qtracers; w->layout = layout;
-  w->doubles = total;
-  w->base = base;
   pam_amd_shoc_args_t &A = w->args;
   A.ncol = (int)ncol; A.nlev = nz; A.nlevi = nz + 1; A.dt = 0; A.nadv = 1; A.num_qtracers = num_qtracers; A.layout = layout; A.stream = nullptr;
-  double **ptr[SHOC_NARRAYS] = {&A.host_dx, &A.host_dy, &A.thv, &A.zt_grid, &A.zi_grid, &A.pres, &A.presi, &A.pdel, &A.wthl_sfc, &A.wqw_sfc,
-                                &A.uw_sfc, &A.vw_sfc, &A.wtracer_sfc, &A.w_field, &A.inv_exner, &A.phis, &A.host_dse, &A.tke, &A.thetal, &A.qw,
-                                &A.hwind, &A.qtracers, &A.wthv_sec, &A.tk, &A.ql, &A.cldfrac, &A.pblh, &A.ustar, &A.obklen, &A.mix,
-                                &A.isotropy, &A.w_sec, &A.thl_sec, &A.qw_sec, &A.qwthl_sec, &A.wthl_sec, &A.wqw_sec, &A.wtke_sec, &A.uw_sec,
-                                &A.vw_sec, &A.w3, &A.wqls_sec, &A.brunt, &A.ql2, &A.tkh, &A.exner};
-  long long at = SHOC_GUARD;
-  for (int i = 0; i < SHOC_NARRAYS; i++) {
-    *ptr[i] = base + at;
-    at += shoc_round8(n[i]) + SHOC_GUARD;
-  }
-  *ws = w;
+  if (int rc = coupling_allocate<SHOC_CANARY>(who, cw::SHOC_TABLE, ncol, nz, num_qtracers, cw::SHOC_ZERO_SIZE, w.get(), &A)) return rc;
+  w->magic = ShocWorkspace::MAGIC;
+  *ws = w.release();
   return PAM_AMD_OK;
 }
 
 extern "C" int pam_amd_shoc_workspace_args(void *ws, pam_amd_shoc_args_t *args) {
-  ShocWorkspace *w = shoc_ws(ws);
-  if (!w) return shoc_error("shoc_workspace_args", "not a workspace of shoc_workspace_create");
-  if (!args) return shoc_error("shoc_workspace_args", "null args");
-  *args = w->args;
-  return PAM_AMD_OK;
+  return coupling_workspace_args<ShocWorkspace>(ws, "shoc_workspace_args", args);
 }
-
 extern "C" int pam_amd_shoc_workspace_bytes(void *ws, long long *bytes) {
-  ShocWorkspace *w = shoc_ws(ws);
-  if (!w) return shoc_error("shoc_workspace_bytes", "not a workspace of shoc_workspace_create");
-  if (!bytes) return shoc_error("shoc_workspace_bytes", "null bytes");
-  *bytes = w->doubles * (long long)sizeof(double);
-  return PAM_AMD_OK;
+  return coupling_workspace_bytes<ShocWorkspace>(ws, "shoc_workspace_bytes", bytes);
 }
-
-extern "C" int pam_amd_shoc_workspace_destroy(void *ws) {
-  if (!ws) return PAM_AMD_OK;
-  ShocWorkspace *w = shoc_ws(ws);
-  if (!w) return shoc_error("shoc_workspace_destroy", "not a workspace of shoc_workspace_create");
-  (void)hipFree(w->base);
-  w->magic = 0;
-  delete w;
-  return PAM_AMD_OK;
-}
+extern "C" int pam_amd_shoc_workspace_destroy(void *ws) { return coupling_workspace_destroy<ShocWorkspace>(ws, "shoc_workspace_destroy"); }
 
 extern "C" int pam_amd_shoc_pack(void *ws, const double *rho_d, const double *rho_v, const double *rho_c, const double *uvel,
                                  const double *vvel, const double *wvel, const double *temp, const double *tke,
@@ -2371,15 +2397,15 @@ extern "C" int pam_amd_shoc_pack(void *ws, const double *rho_d, const double *rh
   const char *who = "shoc_pack";
   if (!rho_d || !rho_v || !rho_c || !uvel || !vvel || !wvel || !temp || !tke || !wthv_sec || !tk || !tkh || !cldfrac || !sfc_mom_flx_u ||
       !sfc_mom_flx_v || !zint || !zmid)
-    return shoc_error(who, "null pointer");
-  if (!shoc_pos(xlen) || !shoc_pos(ylen)) return shoc_error(who, "xlen and ylen must be finite and positive");
-  if (!shoc_pos(coupler_R_d) || !shoc_pos(coupler_R_v) || !shoc_pos(R_d) || !shoc_pos(cp_d) || !shoc_pos(p0) || !shoc_pos(grav) || !shoc_pos(latvap))
-    return shoc_error(who, "coupler_R_d, coupler_R_v, R_d, cp_d, p0, grav and latvap must be finite and positive");
-  ShocWorkspace *w = shoc_ws(ws);
-  if (!w) return shoc_error(who, "not a workspace of shoc_workspace_create");
-  if (w->ntr > 0 && !qtracers) return shoc_error(who, "null qtracers");
+    return coupling_error(who, "null pointer");
+  if (!coupling_pos(xlen) || !coupling_pos(ylen)) return coupling_error(who, "xlen and ylen must be finite and positive");
+  if (!coupling_pos(coupler_R_d) || !coupling_pos(coupler_R_v) || !coupling_pos(R_d) || !coupling_pos(cp_d) || !coupling_pos(p0) || !coupling_pos(grav) || !coupling_pos(latvap))
+    return coupling_error(who, "coupler_R_d, coupler_R_v, R_d, cp_d, p0, grav and latvap must be finite and positive");
+  ShocWorkspace *w = coupling_ws<ShocWorkspace>(ws);
+  if (!w) return coupling_error(who, ShocWorkspace::NOT_ONE);
+  if (w->ntr > 0 && !qtracers) return coupling_error(who, "null qtracers");
   for (int tr = 0; tr < w->ntr; tr++)
-    if (!qtracers[tr]) return shoc_error(who, "null pointer in qtracers");
+    if (!qtracers[tr]) return coupling_error(who, "null pointer in qtracers");
   if (int rc = moist_surface_device_check(who)) return rc;
   const PowTab *tab = kessler_pow_tab(w->base);
   if (!tab) return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "shoc_pack: cannot allocate the pow tables");
@@ -2398,14 +2424,11 @@ extern "C" int pam_amd_shoc_pack(void *ws, const double *rho_d, const double *rh
   ShocColDst E = {A.zi_grid, A.presi, A.host_dx, A.host_dy, A.wthl_sfc, A.wqw_sfc, A.uw_sfc, A.vw_sfc, A.phis, A.wtracer_sfc};
   const sh::Consts c = {p0, grav, R_d, cp_d, 0.0, latvap, coupler_R_d, coupler_R_v};
   const double dx = xlen / w->nx, dy = w->ny == 1 ? dx : ylen / w->ny;   // SGS.h:168-169
-  const bool narrow = !g_shoc_force_wide && shoc_largest(w) < SHOC_NARROW;
-  hipStream_t s = (hipStream_t)stream;
-#define SHOC_PACK(LAYOUT, IDX)                                                                                                            \
-  hipLaunchKernelGGL((shoc_pack_kernel<LAYOUT, IDX>), dim3((unsigned)((A.ncol + ShocTile<LAYOUT>::TC - 1) / ShocTile<LAYOUT>::TC)),       \
-                     dim3(SHOC_THREADS), 0, s, S, D, E, A.ncol, w->nens, w->nz, w->ntr, c, dx, dy, tab)
-  if (w->layout == 0) { if (narrow) SHOC_PACK(0, unsigned); else SHOC_PACK(0, long long); }
-  else { if (narrow) SHOC_PACK(1, unsigned); else SHOC_PACK(1, long long); }
-#undef SHOC_PACK
+  // the kernel walks the levels itself: one level tile
+  coupling_dispatch(w->layout, coupling_narrow(g_shoc_force_wide, shoc_largest(A.ncol, w->nz, w->ntr)), [&](auto layout, auto idx) {
+    hipLaunchKernelGGL((shoc_pack_kernel<layout(), decltype(idx)>), coupling_grid<layout()>(A.ncol, 1), dim3(COUPLING_THREADS), 0,
+                       (hipStream_t)stream, S, D, E, A.ncol, w->nens, w->nz, w->ntr, c, dx, dy, tab);
+  });
   return stats_launch_check(who);
 }
 
@@ -2414,13 +2437,13 @@ extern "C" int pam_amd_shoc_unpack(void *ws, const double *rho_d, double *rho_v,
                                    double *inv_qc_relvar, double cp_d, double cv_d, double latvap, void *stream) {
   const char *who = "shoc_unpack";
   if (!rho_d || !rho_v || !rho_c || !uvel || !vvel || !temp || !tke || !wthv_sec || !tk || !tkh || !cldfrac || !inv_qc_relvar)
-    return shoc_error(who, "null pointer");
-  if (!shoc_pos(cp_d) || !shoc_pos(cv_d) || !shoc_pos(latvap)) return shoc_error(who, "cp_d, cv_d and latvap must be finite and positive");
-  ShocWorkspace *w = shoc_ws(ws);
-  if (!w) return shoc_error(who, "not a workspace of shoc_workspace_create");
-  if (w->ntr > 0 && !qtracers) return shoc_error(who, "null qtracers");
+    return coupling_error(who, "null pointer");
+  if (!coupling_pos(cp_d) || !coupling_pos(cv_d) || !coupling_pos(latvap)) return coupling_error(who, "cp_d, cv_d and latvap must be finite and positive");
+  ShocWorkspace *w = coupling_ws<ShocWorkspace>(ws);
+  if (!w) return coupling_error(who, ShocWorkspace::NOT_ONE);
+  if (w->ntr > 0 && !qtracers) return coupling_error(who, "null qtracers");
   for (int tr = 0; tr < w->ntr; tr++)
-    if (!qtracers[tr]) return shoc_error(who, "null pointer in qtracers");
+    if (!qtracers[tr]) return coupling_error(who, "null pointer in qtracers");
   if (int rc = moist_surface_device_check(who)) return rc;
   const pam_amd_shoc_args_t &A = w->args;
   ShocCellSrc R = {};
@@ -2437,39 +2460,27 @@ extern "C" int pam_amd_shoc_unpack(void *ws, const double *rho_d, double *rho_v,
   for (int tr = 0; tr < w->ntr; tr++) O.p[sh::S_QTRACER0 + tr] = qtracers[tr];
   O.rho_d = rho_d;
   const sh::Consts c = {0.0, 0.0, 0.0, cp_d, cv_d, latvap, 0.0, 0.0};
-  const bool narrow = !g_shoc_force_wide && shoc_largest(w) < SHOC_NARROW;
-  hipStream_t s = (hipStream_t)stream;
-#define SHOC_UNPACK(LAYOUT, IDX)                                                                                                          \
-  hipLaunchKernelGGL((shoc_unpack_kernel<LAYOUT, IDX>), dim3((unsigned)((A.ncol + ShocTile<LAYOUT>::TC - 1) / ShocTile<LAYOUT>::TC),      \
-                                                            (unsigned)((w->nz + ShocTile<LAYOUT>::TL - 1) / ShocTile<LAYOUT>::TL)),       \
-                     dim3(SHOC_THREADS), 0, s, R, O, A.ncol, w->nz, w->ntr, c)
-  if (w->layout == 0) { if (narrow) SHOC_UNPACK(0, unsigned); else SHOC_UNPACK(0, long long); }
-  else { if (narrow) SHOC_UNPACK(1, unsigned); else SHOC_UNPACK(1, long long); }
-#undef SHOC_UNPACK
+  coupling_dispatch(w->layout, coupling_narrow(g_shoc_force_wide, shoc_largest(A.ncol, w->nz, w->ntr)), [&](auto layout, auto idx) {
+    hipLaunchKernelGGL((shoc_unpack_kernel<layout(), decltype(idx)>), coupling_grid<layout()>(A.ncol, w->nz), dim3(COUPLING_THREADS), 0,
+                       (hipStream_t)stream, R, O, A.ncol, w->nz, w->ntr, c);
+  });
   return stats_launch_check(who);
 }
 
 extern "C" int pam_amd_shoc_main_standin(const pam_amd_shoc_args_t *args, void *user) {
   (void)user;
   const char *who = "shoc_main_standin";
-  if (!args) return shoc_error(who, "null args");
+  if (!args) return coupling_error(who, "null args");
   const pam_amd_shoc_args_t &A = *args;
-  if (A.ncol < 1 || A.nlev < 1 || A.nlevi != A.nlev + 1) return shoc_error(who, "ncol, nlev must be >= 1 and nlevi = nlev + 1");
-  if (A.ncol > 0x7fffffff - 64 || A.nlev > 0x7ffffff0) return shoc_error(who, "ncol must stay below 2^31 - 64");
-  if (A.num_qtracers < 0 || A.num_qtracers > sh::MAX_QTRACERS) return shoc_error(who, "num_qtracers must be 0 ... 7");
-  if (A.layout != 0 && A.layout != 1) return shoc_error(who, "layout must be 0 or 1");
-  double *const all[SHOC_NARRAYS] = {A.host_dx, A.host_dy, A.thv, A.zt_grid, A.zi_grid, A.pres, A.presi, A.pdel, A.wthl_sfc, A.wqw_sfc, A.uw_sfc,
-                                     A.vw_sfc, A.wtracer_sfc, A.w_field, A.inv_exner, A.phis, A.host_dse, A.tke, A.thetal, A.qw, A.hwind,
-                                     A.qtracers, A.wthv_sec, A.tk, A.ql, A.cldfrac, A.pblh, A.ustar, A.obklen, A.mix, A.isotropy, A.w_sec,
-                                     A.thl_sec, A.qw_sec, A.qwthl_sec, A.wthl_sec, A.wqw_sec, A.wtke_sec, A.uw_sec, A.vw_sec, A.w3,
-                                     A.wqls_sec, A.brunt, A.ql2, A.tkh, A.exner};
-  for (int i = 0; i < SHOC_NARRAYS; i++)
-    if (!all[i]) return shoc_error(who, "null pointer in args");
+  if (A.ncol < 1 || A.nlev < 1 || A.nlevi != A.nlev + 1) return coupling_error(who, "ncol, nlev must be >= 1 and nlevi = nlev + 1");
+  if (A.ncol > 0x7fffffff - 64 || A.nlev > 0x7ffffff0) return coupling_error(who, "ncol must stay below 2^31 - 64");
+  if (A.num_qtracers < 0 || A.num_qtracers > sh::MAX_QTRACERS) return coupling_error(who, "num_qtracers must be 0 ... 7");
+  if (A.layout != 0 && A.layout != 1) return coupling_error(who, "layout must be 0 or 1");
+  if (coupling_null_array(cw::SHOC_TABLE, A, A.ncol, A.nlev, A.num_qtracers, cw::SHOC_ZERO_SIZE)) return coupling_error(who, "null pointer in args");
   if (int rc = moist_surface_device_check(who)) return rc;
-  const long long largest = std::max<long long>(std::max(2, A.num_qtracers) * (long long)A.nlev * A.ncol, (long long)A.nlevi * A.ncol);
-  const dim3 grid((unsigned)((A.ncol + 63) / 64)), block(64);
-  if (!g_shoc_force_wide && largest < SHOC_NARROW) hipLaunchKernelGGL((shoc_standin_kernel<unsigned>), grid, block, 0, (hipStream_t)A.stream, A);
-  else hipLaunchKernelGGL((shoc_standin_kernel<long long>), grid, block, 0, (hipStream_t)A.stream, A);
+  coupling_dispatch(A.layout, coupling_narrow(g_shoc_force_wide, shoc_largest(A.ncol, A.nlev, A.num_qtracers)), [&](auto, auto idx) {
+    hipLaunchKernelGGL((shoc_standin_kernel<decltype(idx)>), dim3((unsigned)((A.ncol + 63) / 64)), dim3(64), 0, (hipStream_t)A.stream, A);
+  });
   return stats_launch_check(who);
 }
 
@@ -2479,20 +2490,14 @@ extern "C" int pam_amd_shoc_main_standin(const pam_amd_shoc_args_t *args, void *
 // in p3_device.h.  A thread owns one cell (k, col), lanes run along col, so every access to the coupler state is a coalesced row; no cell
 // needs another, so both kernels run on a grid of (column tiles, level tiles).
 //   layout 0 ((lev, col), column fastest, not flipped): tiles of 64 columns x 4 levels, the P3 arrays are written / read directly.
-//   layout 1 ((col, lev), level fastest, flipped): tiles of 16 columns x 16 levels through LDS tiles [col][lev] of pitch 17 doubles, P3_GROUP
+//   layout 1 ((col, lev), level fastest, flipped): tiles of 16 columns x 16 levels through LDS tiles [col][lev] of pitch 17 doubles, COUPLING_GROUP
 //   arrays per pair of barriers -- the scheme of the SHOC kernels above, with the bank reasoning given there (derived, not measured).  The four
 //   constant arrays need no LDS: the transposed role of a thread writes them as 128-byte rows.
 // The ADJUST = 0 instances of the pack kernel (SHOC as the SGS) carry none of the bisection.  The tables of pow_pos_fast are staged once per
 // workgroup.
 namespace {
 namespace p3 = pama::p3;
-constexpr int P3_THREADS = 256;
-constexpr int P3_GROUP = 8;
-constexpr long long P3_NARROW = 1ll << 29;   // the largest array from this size on: the long long instances
 constexpr unsigned long long P3_CANARY = 0x7ff850335f57535full;
-constexpr int P3_GUARD = 8;                  // doubles
-constexpr int P3_NARRAYS = 43;
-template <int LAYOUT> struct P3Tile { static constexpr int TC = LAYOUT ? 16 : 64, TL = P3_THREADS / TC, PITCH = TL + 1; };
 
 struct P3State {
   const double *rho_d;
@@ -2506,12 +2511,12 @@ struct P3StateOut { double *p[p3::S_MAX]; const double *rho_d; double *precip_li
 
 // grid (column tiles, level tiles)
 template <int LAYOUT, class IDX, bool ADJUST>
-__global__ void __launch_bounds__(P3_THREADS) p3_pack_kernel(P3State S, P3CellDst D, int ncol_, int nens, int nz, int first_step, p3::Consts c,
+__global__ void __launch_bounds__(COUPLING_THREADS) p3_pack_kernel(P3State S, P3CellDst D, int ncol_, int nens, int nz, int first_step, p3::Consts c,
                                                              const PowTab *__restrict__ tab) {
-  using T = P3Tile<LAYOUT>;
+  using T = CouplingTile<LAYOUT>;
   constexpr int TC = T::TC, TL = T::TL, PITCH = T::PITCH;
   __shared__ PowTab sh_tab;
-  __shared__ double sh_t[LAYOUT ? P3_GROUP * TC * PITCH : 1];
+  __shared__ double sh_t[LAYOUT ? COUPLING_GROUP * TC * PITCH : 1];
   kessler_stage_tab(tab, &sh_tab);
   const int tc = (int)threadIdx.x % TC, tl = (int)threadIdx.x / TC;
   const IDX ncol = (IDX)ncol_;
@@ -2561,16 +2566,16 @@ __global__ void __launch_bounds__(P3_THREADS) p3_pack_kernel(P3State S, P3CellDs
       for (int a = 0; a < 4; a++) D.one[a][o2] = 1;
     }
 #pragma unroll
-    for (int g = 0; g < (p3::C_MAX + P3_GROUP - 1) / P3_GROUP; g++) {
+    for (int g = 0; g < (p3::C_MAX + COUPLING_GROUP - 1) / COUPLING_GROUP; g++) {
       __syncthreads();
 #pragma unroll
-      for (int j = 0; j < P3_GROUP; j++)
-        if (g * P3_GROUP + j < p3::C_MAX) sh_t[(j * TC + tc) * PITCH + tl] = v[g * P3_GROUP + j < p3::C_MAX ? g * P3_GROUP + j : 0];
+      for (int j = 0; j < COUPLING_GROUP; j++)
+        if (g * COUPLING_GROUP + j < p3::C_MAX) sh_t[(j * TC + tc) * PITCH + tl] = v[g * COUPLING_GROUP + j < p3::C_MAX ? g * COUPLING_GROUP + j : 0];
       __syncthreads();
       if (ok2) {
 #pragma unroll
-        for (int j = 0; j < P3_GROUP; j++)
-          if (g * P3_GROUP + j < p3::C_MAX) D.p[g * P3_GROUP + j < p3::C_MAX ? g * P3_GROUP + j : 0][o2] = sh_t[(j * TC + tc2) * PITCH + tl2];
+        for (int j = 0; j < COUPLING_GROUP; j++)
+          if (g * COUPLING_GROUP + j < p3::C_MAX) D.p[g * COUPLING_GROUP + j < p3::C_MAX ? g * COUPLING_GROUP + j : 0][o2] = sh_t[(j * TC + tc2) * PITCH + tl2];
       }
     }
   }
@@ -2578,10 +2583,10 @@ __global__ void __launch_bounds__(P3_THREADS) p3_pack_kernel(P3State S, P3CellDs
 
 // grid (column tiles, level tiles)
 template <int LAYOUT, class IDX>
-__global__ void __launch_bounds__(P3_THREADS) p3_unpack_kernel(P3CellSrc R, P3StateOut O, int ncol_, int nz, p3::Consts c) {
-  using T = P3Tile<LAYOUT>;
+__global__ void __launch_bounds__(COUPLING_THREADS) p3_unpack_kernel(P3CellSrc R, P3StateOut O, int ncol_, int nz, p3::Consts c) {
+  using T = CouplingTile<LAYOUT>;
   constexpr int TC = T::TC, TL = T::TL, PITCH = T::PITCH;
-  __shared__ double sh_t[LAYOUT ? P3_GROUP * TC * PITCH : 1];
+  __shared__ double sh_t[LAYOUT ? COUPLING_GROUP * TC * PITCH : 1];
   const int tc = (int)threadIdx.x % TC, tl = (int)threadIdx.x / TC;
   const IDX ncol = (IDX)ncol_;
   const long long col_ll = (long long)blockIdx.x * TC + tc;
@@ -2608,17 +2613,17 @@ __global__ void __launch_bounds__(P3_THREADS) p3_unpack_kernel(P3CellSrc R, P3St
     const IDX col2 = (IDX)(col2_ll < ncol_ ? col2_ll : ncol_ - 1);
     const IDX o2 = p3::offset_t<IDX>(1, col2, ok2 ? k2 : 0, ncol, nz);
 #pragma unroll
-    for (int g = 0; g < (p3::U_MAX + P3_GROUP - 1) / P3_GROUP; g++) {
+    for (int g = 0; g < (p3::U_MAX + COUPLING_GROUP - 1) / COUPLING_GROUP; g++) {
       __syncthreads();
       if (ok2) {
 #pragma unroll
-        for (int j = 0; j < P3_GROUP; j++)
-          if (g * P3_GROUP + j < p3::U_MAX) sh_t[(j * TC + tc2) * PITCH + tl2] = R.p[g * P3_GROUP + j < p3::U_MAX ? g * P3_GROUP + j : 0][o2];
+        for (int j = 0; j < COUPLING_GROUP; j++)
+          if (g * COUPLING_GROUP + j < p3::U_MAX) sh_t[(j * TC + tc2) * PITCH + tl2] = R.p[g * COUPLING_GROUP + j < p3::U_MAX ? g * COUPLING_GROUP + j : 0][o2];
       }
       __syncthreads();
 #pragma unroll
-      for (int j = 0; j < P3_GROUP; j++)
-        if (g * P3_GROUP + j < p3::U_MAX) in[g * P3_GROUP + j < p3::U_MAX ? g * P3_GROUP + j : 0] = sh_t[(j * TC + tc) * PITCH + tl];
+      for (int j = 0; j < COUPLING_GROUP; j++)
+        if (g * COUPLING_GROUP + j < p3::U_MAX) in[g * COUPLING_GROUP + j < p3::U_MAX ? g * COUPLING_GROUP + j : 0] = sh_t[(j * TC + tc) * PITCH + tl];
     }
   }
   if (!cell_ok) return;
@@ -2635,44 +2640,15 @@ __global__ void __launch_bounds__(64) p3_standin_kernel(pam_amd_p3_args_t A) {
   if (col < A.ncol) p3::standin_column<IDX>(A, (IDX)col);
 }
 
-__global__ void __launch_bounds__(256) p3_canary_kernel(unsigned long long *p, long long n) {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) p[i] = P3_CANARY;
-}
-
-struct P3Workspace {
-  unsigned long long magic;
+struct P3Workspace : CouplingWorkspace {
+  static constexpr unsigned long long MAGIC = 0x5033434f55504c31ull;
+  static constexpr const char *NOT_ONE = "not a workspace of p3_workspace_create";
   int nens, nx, ny, nz, layout, nout;
-  long long doubles;
-  double *base;
   pam_amd_p3_args_t args;
 };
-constexpr unsigned long long P3_MAGIC = 0x5033434f55504c31ull;
-P3Workspace *p3_ws(void *ws) {
-  P3Workspace *w = (P3Workspace *)ws;
-  return (w && w->magic == P3_MAGIC) ? w : nullptr;
-}
 bool g_p3_force_wide = false;   // pam_amd_p3_debug_wide_index: tests run the long long instances at small sizes
-int p3_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
 // element count of the largest array: p3_tend_out where there is one, a flux array otherwise
 long long p3_largest(long long ncol, long long nz, long long nout) { return std::max(std::max<long long>(nout, 1) * nz * ncol, (nz + 1) * ncol); }
-// every array of the struct, in its order
-void p3_pointers(pam_amd_p3_args_t &A, double **(&ptr)[P3_NARRAYS]) {
-  double **p[P3_NARRAYS] = {&A.qc, &A.nc, &A.qr, &A.nr, &A.th_atm, &A.qv, &A.qi, &A.qm, &A.ni, &A.bm, &A.pres, &A.dz, &A.nc_nuceat_tend,
-                            &A.nccn_prescribed, &A.ni_activated, &A.inv_qc_relvar, &A.precip_liq_surf, &A.precip_ice_surf, &A.diag_eff_radius_qc,
-                            &A.diag_eff_radius_qi, &A.diag_eff_radius_qr, &A.bulk_qi, &A.precip_total_tend, &A.nevapr, &A.qr_evap_tend, &A.dpres,
-                            &A.inv_exner, &A.qv2qi_depos_tend, &A.precip_liq_flux, &A.precip_ice_flux, &A.cld_frac_r, &A.cld_frac_l, &A.cld_frac_i,
-                            &A.p3_tend_out, &A.mu_c, &A.lamc, &A.liq_ice_exchange, &A.vap_liq_exchange, &A.vap_ice_exchange, &A.q_prev, &A.t_prev,
-                            &A.col_location, &A.exner};
-  for (int i = 0; i < P3_NARRAYS; i++) ptr[i] = p[i];
-}
-// the sizes of the arrays, in the order of the struct's pointers
-void p3_sizes(long long N, long long Z, long long T, long long (&n)[P3_NARRAYS]) {
-  for (int i = 0; i < P3_NARRAYS; i++) n[i] = Z * N;
-  n[16] = n[17] = N;              // precip_liq_surf, precip_ice_surf
-  n[28] = n[29] = (Z + 1) * N;    // precip_liq_flux, precip_ice_flux
-  n[33] = T * Z * N;              // p3_tend_out
-  n[41] = 3 * N;                  // col_location
-}
 }  // namespace
 
 extern "C" int pam_amd_p3_debug_wide_index(int on) {
@@ -2682,76 +2658,33 @@ extern "C" int pam_amd_p3_debug_wide_index(int on) {
 
 extern "C" int pam_amd_p3_workspace_create(int nens, int nx, int ny, int nz, int layout, int num_tend_out, void **ws) {
   const char *who = "p3_workspace_create";
-  if (!ws) return p3_error(who, "null ws");
+  if (!ws) return coupling_error(who, "null ws");
   *ws = nullptr;
-  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return p3_error(who, "nens, nx, ny and nz must be >= 1");
-  if (layout != 0 && layout != 1) return p3_error(who, "layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)");
-  if (num_tend_out < 0 || num_tend_out > p3::MAX_TEND_OUT) return p3_error(who, "num_tend_out must be 0 ... 49");
-  if (layout == 1 && num_tend_out != 0) return p3_error(who, "num_tend_out must be 0 in layout 1 (pam::p3_main_cxx has no p3_tend_out)");
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return coupling_error(who, "nens, nx, ny and nz must be >= 1");
+  if (layout != 0 && layout != 1) return coupling_error(who, "layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)");
+  if (num_tend_out < 0 || num_tend_out > p3::MAX_TEND_OUT) return coupling_error(who, "num_tend_out must be 0 ... 49");
+  if (layout == 1 && num_tend_out != 0) return coupling_error(who, "num_tend_out must be 0 in layout 1 (pam::p3_main_cxx has no p3_tend_out)");
   const long long ncol = (long long)ny * nx * nens;
-  if (ncol > 0x7fffffffLL - 64 || nz > 0x7ffffff0) return p3_error(who, "ny x nx x nens must stay below 2^31");
+  if (ncol > 0x7fffffffLL - 64 || nz > 0x7ffffff0) return coupling_error(who, "ny x nx x nens must stay below 2^31");
   if (int rc = moist_surface_device_check(who)) return rc;
-  long long n[P3_NARRAYS], total = P3_GUARD;
-  p3_sizes(ncol, nz, num_tend_out, n);
-  for (int i = 0; i < P3_NARRAYS; i++)
-    if (n[i] > 0) total += shoc_round8(n[i]) + P3_GUARD;
-  double *base = nullptr;
-  if (hipMalloc((void **)&base, (size_t)total * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "p3_workspace_create: cannot allocate the workspace");
-  }
-  hipLaunchKernelGGL(p3_canary_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, 0,
-                     (unsigned long long *)base, total);
-  if (hipDeviceSynchronize() != hipSuccess) {
-    (void)hipFree(base);
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": " + hipGetErrorString(hipGetLastError())).c_str());
-  }
-  P3Workspace *w = new P3Workspace();
-  w->magic = P3_MAGIC;
+  std::unique_ptr<P3Workspace> w(new P3Workspace());
   w->nens = nens; w->nx = nx; w->ny = ny; w->nz = nz; w->layout = layout; w->nout = num_tend_out;
-  w->doubles = total;
-  w->base = base;
   pam_amd_p3_args_t &A = w->args;
   A.ncol = (int)ncol; A.nlev = nz; A.dt = 0; A.layout = layout; A.num_tend_out = num_tend_out; A.stream = nullptr;
   A.do_predict_nc = A.do_prescribed_CCN = 1;                        // Microphysics.h:412-413
   if (layout == 0) { A.it = A.its = A.kts = 1; A.ite = (int)ncol; A.kte = nz; }               // :568-572
   else { A.it = A.its = A.kts = 0; A.ite = (int)ncol - 1; A.kte = nz - 1; }                   // :417-421
-  double **ptr[P3_NARRAYS];
-  p3_pointers(A, ptr);
-  long long at = P3_GUARD;
-  for (int i = 0; i < P3_NARRAYS; i++) {
-    *ptr[i] = n[i] > 0 ? base + at : nullptr;
-    if (n[i] > 0) at += shoc_round8(n[i]) + P3_GUARD;
-  }
-  *ws = w;
+  if (int rc = coupling_allocate<P3_CANARY>(who, cw::P3_TABLE, ncol, nz, num_tend_out, cw::P3_ZERO_SIZE, w.get(), &A)) return rc;
+  w->magic = P3Workspace::MAGIC;
+  *ws = w.release();
   return PAM_AMD_OK;
 }
 
 extern "C" int pam_amd_p3_workspace_args(void *ws, pam_amd_p3_args_t *args) {
-  P3Workspace *w = p3_ws(ws);
-  if (!w) return p3_error("p3_workspace_args", "not a workspace of p3_workspace_create");
-  if (!args) return p3_error("p3_workspace_args", "null args");
-  *args = w->args;
-  return PAM_AMD_OK;
+  return coupling_workspace_args<P3Workspace>(ws, "p3_workspace_args", args);
 }
-
-extern "C" int pam_amd_p3_workspace_bytes(void *ws, long long *bytes) {
-  P3Workspace *w = p3_ws(ws);
-  if (!w) return p3_error("p3_workspace_bytes", "not a workspace of p3_workspace_create");
-  if (!bytes) return p3_error("p3_workspace_bytes", "null bytes");
-  *bytes = w->doubles * (long long)sizeof(double);
-  return PAM_AMD_OK;
-}
-
-extern "C" int pam_amd_p3_workspace_destroy(void *ws) {
-  if (!ws) return PAM_AMD_OK;
-  P3Workspace *w = p3_ws(ws);
-  if (!w) return p3_error("p3_workspace_destroy", "not a workspace of p3_workspace_create");
-  (void)hipFree(w->base);
-  w->magic = 0;
-  delete w;
-  return PAM_AMD_OK;
-}
+extern "C" int pam_amd_p3_workspace_bytes(void *ws, long long *bytes) { return coupling_workspace_bytes<P3Workspace>(ws, "p3_workspace_bytes", bytes); }
+extern "C" int pam_amd_p3_workspace_destroy(void *ws) { return coupling_workspace_destroy<P3Workspace>(ws, "p3_workspace_destroy"); }
 
 extern "C" int pam_amd_p3_pack(void *ws, const double *rho_d, double *rho_v, double *rho_c, double *temp, const double *const *tracers,
                                const double *nccn_prescribed, const double *nc_nuceat_tend, const double *ni_activated, const double *q_prev,
@@ -2759,14 +2692,14 @@ extern "C" int pam_amd_p3_pack(void *ws, const double *rho_d, double *rho_v, dou
                                double cp_v, double cp_l, double p0, double grav, void *stream) {
   const char *who = "p3_pack";
   if (!rho_d || !rho_v || !rho_c || !temp || !nccn_prescribed || !nc_nuceat_tend || !ni_activated || !q_prev || !t_prev || !zint)
-    return p3_error(who, "null pointer");
-  if (!shoc_pos(R_d) || !shoc_pos(R_v) || !shoc_pos(cp_d) || !shoc_pos(cp_l) || !shoc_pos(p0) || !shoc_pos(grav) || !std::isfinite(cp_v))
-    return p3_error(who, "R_d, R_v, cp_d, cp_l, p0 and grav must be finite and positive, cp_v finite");
-  P3Workspace *w = p3_ws(ws);
-  if (!w) return p3_error(who, "not a workspace of p3_workspace_create");
-  if (!tracers) return p3_error(who, "null tracers");
+    return coupling_error(who, "null pointer");
+  if (!coupling_pos(R_d) || !coupling_pos(R_v) || !coupling_pos(cp_d) || !coupling_pos(cp_l) || !coupling_pos(p0) || !coupling_pos(grav) || !std::isfinite(cp_v))
+    return coupling_error(who, "R_d, R_v, cp_d, cp_l, p0 and grav must be finite and positive, cp_v finite");
+  P3Workspace *w = coupling_ws<P3Workspace>(ws);
+  if (!w) return coupling_error(who, P3Workspace::NOT_ONE);
+  if (!tracers) return coupling_error(who, "null tracers");
   for (int tr = 0; tr < p3::NTRACERS; tr++)
-    if (!tracers[tr]) return p3_error(who, "null pointer in tracers");
+    if (!tracers[tr]) return coupling_error(who, "null pointer in tracers");
   if (int rc = moist_surface_device_check(who)) return rc;
   const PowTab *tab = kessler_pow_tab(w->base);
   if (!tab) return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "p3_pack: cannot allocate the pow tables");
@@ -2782,17 +2715,13 @@ extern "C" int pam_amd_p3_pack(void *ws, const double *rho_d, double *rho_v, dou
   D.one[0] = A.cld_frac_l; D.one[1] = A.cld_frac_i; D.one[2] = A.cld_frac_r; D.one[3] = A.inv_qc_relvar;
   D.col_location = A.col_location;
   const p3::Consts c = {R_d, R_v, cp_d, cp_v, cp_l, p0, grav, 0.0};
-  const bool narrow = !g_p3_force_wide && p3_largest(A.ncol, w->nz, w->nout) < P3_NARROW;
-  hipStream_t s = (hipStream_t)stream;
-#define P3_PACK(LAYOUT, IDX, ADJ)                                                                                                         \
-  hipLaunchKernelGGL((p3_pack_kernel<LAYOUT, IDX, ADJ>), dim3((unsigned)((A.ncol + P3Tile<LAYOUT>::TC - 1) / P3Tile<LAYOUT>::TC),          \
-                                                              (unsigned)((w->nz + P3Tile<LAYOUT>::TL - 1) / P3Tile<LAYOUT>::TL)),          \
-                     dim3(P3_THREADS), 0, s, S, D, A.ncol, w->nens, w->nz, first_step, c, tab)
-#define P3_PACK_I(LAYOUT, ADJ) do { if (narrow) P3_PACK(LAYOUT, unsigned, ADJ); else P3_PACK(LAYOUT, long long, ADJ); } while (0)
-  if (w->layout == 0) { if (adjust) P3_PACK_I(0, true); else P3_PACK_I(0, false); }
-  else { if (adjust) P3_PACK_I(1, true); else P3_PACK_I(1, false); }
-#undef P3_PACK_I
-#undef P3_PACK
+  coupling_dispatch(w->layout, coupling_narrow(g_p3_force_wide, p3_largest(A.ncol, w->nz, w->nout)), [&](auto layout, auto idx) {
+    const auto launch = [&](auto adj) {
+      hipLaunchKernelGGL((p3_pack_kernel<layout(), decltype(idx), adj()>), coupling_grid<layout()>(A.ncol, w->nz), dim3(COUPLING_THREADS), 0,
+                         (hipStream_t)stream, S, D, A.ncol, w->nens, w->nz, first_step, c, tab);
+    };
+    if (adjust) launch(std::true_type()); else launch(std::false_type());
+  });
   return stats_launch_check(who);
 }
 
@@ -2803,13 +2732,13 @@ extern "C" int pam_amd_p3_unpack(void *ws, const double *rho_d, double *rho_v, d
   const char *who = "p3_unpack";
   if (!rho_d || !rho_v || !rho_c || !temp || !q_prev || !t_prev || !liq_ice_exchange_out || !vap_liq_exchange_out || !vap_ice_exchange_out ||
       !precip_liq_surf_out || !precip_ice_surf_out)
-    return p3_error(who, "null pointer");
-  if (!shoc_pos(cp_d) || !shoc_pos(cv_d)) return p3_error(who, "cp_d and cv_d must be finite and positive");
-  P3Workspace *w = p3_ws(ws);
-  if (!w) return p3_error(who, "not a workspace of p3_workspace_create");
-  if (!tracers) return p3_error(who, "null tracers");
+    return coupling_error(who, "null pointer");
+  if (!coupling_pos(cp_d) || !coupling_pos(cv_d)) return coupling_error(who, "cp_d and cv_d must be finite and positive");
+  P3Workspace *w = coupling_ws<P3Workspace>(ws);
+  if (!w) return coupling_error(who, P3Workspace::NOT_ONE);
+  if (!tracers) return coupling_error(who, "null tracers");
   for (int tr = 0; tr < p3::NTRACERS; tr++)
-    if (!tracers[tr]) return p3_error(who, "null pointer in tracers");
+    if (!tracers[tr]) return coupling_error(who, "null pointer in tracers");
   if (int rc = moist_surface_device_check(who)) return rc;
   const pam_amd_p3_args_t &A = w->args;
   P3CellSrc R = {};
@@ -2825,36 +2754,27 @@ extern "C" int pam_amd_p3_unpack(void *ws, const double *rho_d, double *rho_v, d
   O.p[p3::S_LIQ_ICE] = liq_ice_exchange_out; O.p[p3::S_VAP_LIQ] = vap_liq_exchange_out; O.p[p3::S_VAP_ICE] = vap_ice_exchange_out;
   O.rho_d = rho_d; O.precip_liq_surf_out = precip_liq_surf_out; O.precip_ice_surf_out = precip_ice_surf_out;
   const p3::Consts c = {0.0, 0.0, cp_d, 0.0, 0.0, 0.0, 0.0, cv_d};
-  const bool narrow = !g_p3_force_wide && p3_largest(A.ncol, w->nz, w->nout) < P3_NARROW;
-  hipStream_t s = (hipStream_t)stream;
-#define P3_UNPACK(LAYOUT, IDX)                                                                                                            \
-  hipLaunchKernelGGL((p3_unpack_kernel<LAYOUT, IDX>), dim3((unsigned)((A.ncol + P3Tile<LAYOUT>::TC - 1) / P3Tile<LAYOUT>::TC),            \
-                                                          (unsigned)((w->nz + P3Tile<LAYOUT>::TL - 1) / P3Tile<LAYOUT>::TL)),             \
-                     dim3(P3_THREADS), 0, s, R, O, A.ncol, w->nz, c)
-  if (w->layout == 0) { if (narrow) P3_UNPACK(0, unsigned); else P3_UNPACK(0, long long); }
-  else { if (narrow) P3_UNPACK(1, unsigned); else P3_UNPACK(1, long long); }
-#undef P3_UNPACK
+  coupling_dispatch(w->layout, coupling_narrow(g_p3_force_wide, p3_largest(A.ncol, w->nz, w->nout)), [&](auto layout, auto idx) {
+    hipLaunchKernelGGL((p3_unpack_kernel<layout(), decltype(idx)>), coupling_grid<layout()>(A.ncol, w->nz), dim3(COUPLING_THREADS), 0,
+                       (hipStream_t)stream, R, O, A.ncol, w->nz, c);
+  });
   return stats_launch_check(who);
 }
 
 extern "C" int pam_amd_p3_main_standin(const pam_amd_p3_args_t *args, void *user) {
   (void)user;
   const char *who = "p3_main_standin";
-  if (!args) return p3_error(who, "null args");
-  pam_amd_p3_args_t A = *args;
-  if (A.ncol < 1 || A.nlev < 1) return p3_error(who, "ncol and nlev must be >= 1");
-  if (A.ncol > 0x7fffffff - 64 || A.nlev > 0x7ffffff0) return p3_error(who, "ncol must stay below 2^31 - 64");
-  if (A.layout != 0 && A.layout != 1) return p3_error(who, "layout must be 0 or 1");
-  if (A.num_tend_out < 0 || A.num_tend_out > p3::MAX_TEND_OUT || (A.layout == 1 && A.num_tend_out)) return p3_error(who, "num_tend_out must be 0 ... 49, 0 in layout 1");
-  double **ptr[P3_NARRAYS];
-  p3_pointers(A, ptr);
-  for (int i = 0; i < P3_NARRAYS; i++)
-    if (!*ptr[i] && !(i == 33 && A.num_tend_out == 0)) return p3_error(who, "null pointer in args");
+  if (!args) return coupling_error(who, "null args");
+  const pam_amd_p3_args_t &A = *args;
+  if (A.ncol < 1 || A.nlev < 1) return coupling_error(who, "ncol and nlev must be >= 1");
+  if (A.ncol > 0x7fffffff - 64 || A.nlev > 0x7ffffff0) return coupling_error(who, "ncol must stay below 2^31 - 64");
+  if (A.layout != 0 && A.layout != 1) return coupling_error(who, "layout must be 0 or 1");
+  if (A.num_tend_out < 0 || A.num_tend_out > p3::MAX_TEND_OUT || (A.layout == 1 && A.num_tend_out)) return coupling_error(who, "num_tend_out must be 0 ... 49, 0 in layout 1");
+  if (coupling_null_array(cw::P3_TABLE, A, A.ncol, A.nlev, A.num_tend_out, cw::P3_ZERO_SIZE)) return coupling_error(who, "null pointer in args");
   if (int rc = moist_surface_device_check(who)) return rc;
-  const dim3 grid((unsigned)((A.ncol + 63) / 64)), block(64);
-  if (!g_p3_force_wide && p3_largest(A.ncol, A.nlev, A.num_tend_out) < P3_NARROW)
-    hipLaunchKernelGGL((p3_standin_kernel<unsigned>), grid, block, 0, (hipStream_t)A.stream, A);
-  else hipLaunchKernelGGL((p3_standin_kernel<long long>), grid, block, 0, (hipStream_t)A.stream, A);
+  coupling_dispatch(A.layout, coupling_narrow(g_p3_force_wide, p3_largest(A.ncol, A.nlev, A.num_tend_out)), [&](auto, auto idx) {
+    hipLaunchKernelGGL((p3_standin_kernel<decltype(idx)>), dim3((unsigned)((A.ncol + 63) / 64)), dim3(64), 0, (hipStream_t)A.stream, A);
+  });
   return stats_launch_check(who);
 }
 

@@ -121,6 +121,86 @@ class _DeviceArray:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f8", "data": (int(ptr), False), "version": 2, "strides": None}
 
 
+class _CouplingLayer:
+    """What SGSShoc and MicrophysicsP3 share: the workspace of the C library (one device allocation, made by the first timeStep and again
+    when a size changes) and the handed-in main function.  A subclass names _PREFIX (the symbols pam_amd_<prefix>_workspace_* and
+    pam_amd_<prefix>_main_standin, the attribute <prefix>_main), _ARGS and _MAIN_FN (capi) and _shapes(args) -> name -> shape."""
+    _PREFIX = _ARGS = _MAIN_FN = None
+
+    def __init__(self, main, user):
+        self._ws = self._ws_key = self._views = None
+        self._set_main(main, user)
+
+    @classmethod
+    def _symbol(cls, name):
+        return getattr(capi.load(), f"pam_amd_{cls._PREFIX}_{name}")
+
+    @classmethod
+    def standin(cls):
+        """the library's test double for shoc_main / p3_main (no physics): pam_amd_shoc_main_standin / pam_amd_p3_main_standin"""
+        return cls._symbol("main_standin")
+
+    def _set_main(self, fn, user):
+        import ctypes as C
+        if isinstance(fn, int):
+            fn = self._MAIN_FN(fn)
+        self._c_main = fn is not None and isinstance(fn, C._CFuncPtr)
+        setattr(self, self._PREFIX + "_main", fn)
+        self.user = user
+
+    def _call_main(self, device):
+        """the registered main on the workspace, either way in; its return value"""
+        import ctypes as C
+        main = getattr(self, self._PREFIX + "_main")
+        if self._c_main:
+            return main(C.byref(self._args), self.user)
+        return main(self.workspace_views(device), self._args)
+
+    def _workspace(self, coupler, sizes):
+        """sizes: the six arguments of workspace_create after which the workspace is cached, with the device"""
+        import ctypes as C
+        key = tuple(sizes) + (str(coupler.device),)
+        if self._ws is None or self._ws_key != key:
+            self._free()
+            ws = C.c_void_p()
+            with torch.cuda.device(coupler.device):
+                check(self._symbol("workspace_create")(*sizes, C.byref(ws)))
+            self._ws, self._ws_key = ws, key
+            self._args = self._ARGS()
+            check(self._symbol("workspace_args")(ws, C.byref(self._args)))
+            self._views = None
+        return self._ws
+
+    def workspace_bytes(self):
+        import ctypes as C
+        n = C.c_longlong()
+        check(self._symbol("workspace_bytes")(self._ws, C.byref(n)))
+        return n.value
+
+    def workspace_views(self, device):
+        """name -> torch view of the workspace array, in this object's layout"""
+        if self._views is None:
+            a = self._args
+            self._views = {n: (torch.as_tensor(_DeviceArray(getattr(a, n), shp), device=device) if min(shp) > 0
+                               else torch.empty(shp, dtype=torch.float64, device=device)) for n, shp in self._shapes(a).items()}
+        return self._views
+
+    def _free(self):
+        if self._ws is not None:
+            check(self._symbol("workspace_destroy")(self._ws))
+        self._ws = self._ws_key = self._views = None
+
+    def finalize(self, coupler):
+        self._free()
+
+    def __del__(self):
+        # an object dropped without finalize() must not keep its workspace (18 to 21 GB at 1024 x 32x32x60) for the life of the process
+        try:
+            self._free()
+        except Exception:
+            pass
+
+
 def shoc_shapes(ncol, nz, ntr, layout):
     """name -> shape of every array of pam_amd_shoc_args_t (include/pam_amd_modules.h) in layout 0 ((lev, col), column fastest) or
     1 (SCREAM's (col, lev), level fastest)"""
@@ -144,7 +224,7 @@ def shoc_shapes(ncol, nz, ntr, layout):
     return out
 
 
-class SGSShoc:
+class SGSShoc(_CouplingLayer):
     """physics/sgs/shoc/SGS.h: the coupling layer around SHOC -- pack (SGS.h:254-411), shoc_main, unpack (:718-756) -- as two fused
     launches on the current stream.  SHOC itself is not part of this library: `shoc_main` is
 
@@ -161,6 +241,7 @@ class SGSShoc:
     gamma_d, kappa_d, cv_v = cp_d / cv_d, R_d / cp_d, R_v - cp_v
     latvap, latice, karman = 2501000.0, 333700.0, 0.4
     P3_TRACERS = ("cloud_water_num", "rain", "rain_num", "ice", "ice_num", "ice_rime", "ice_rime_vol")      # SGS.h:243-249
+    _PREFIX, _ARGS, _MAIN_FN = "shoc", capi.ShocArgs, capi.SHOC_MAIN_FN
 
     def __init__(self, shoc_main=None, layout=1, user=None):
         if layout not in (0, 1):
@@ -170,9 +251,7 @@ class SGSShoc:
         self.first_step = True
         self.etime = 0.0
         self.npbl = -1
-        self._ws = None
-        self._ws_key = None
-        self.set_shoc_main(shoc_main, user)
+        super().__init__(shoc_main, user)
 
     @staticmethod
     def get_num_tracers():
@@ -182,17 +261,11 @@ class SGSShoc:
     def sgs_name():
         return "shoc"
 
-    @staticmethod
-    def standin():
-        """the library's test double for shoc_main (no physics): pam_amd_shoc_main_standin"""
-        return capi.load().pam_amd_shoc_main_standin
-
     def set_shoc_main(self, fn, user=None):
-        import ctypes as C
-        if isinstance(fn, int):
-            fn = capi.SHOC_MAIN_FN(fn)
-        self._c_main = fn is not None and isinstance(fn, C._CFuncPtr)
-        self.shoc_main, self.user = fn, user
+        self._set_main(fn, user)
+
+    def _shapes(self, a):
+        return shoc_shapes(a.ncol, a.nlev, a.num_qtracers, self.layout)
 
     def init(self, coupler):
         """SGS.h:92-146: the "tke" tracer (positive, adds no mass), five 4-D and four surface entries, all zero; option sgs = "shoc" """
@@ -210,41 +283,6 @@ class SGSShoc:
         for name in ("tke", "wthv_sec", "tk", "tkh", "cldfrac", "inv_qc_relvar", "sfc_mom_flx_u", "sfc_mom_flx_v"):
             dm.get(name).zero_()
         coupler.set_option("sgs", "shoc")
-
-    def _workspace(self, coupler, ntr):
-        import ctypes as C
-        lib = capi.load()
-        key = (coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), ntr, self.layout, str(coupler.device))
-        if self._ws is None or self._ws_key != key:
-            self._free()
-            ws = C.c_void_p()
-            with torch.cuda.device(coupler.device):
-                check(lib.pam_amd_shoc_workspace_create(*key[:6], C.byref(ws)))
-            self._ws, self._ws_key = ws, key
-            self._args = capi.ShocArgs()
-            check(lib.pam_amd_shoc_workspace_args(ws, C.byref(self._args)))
-            self._views = None
-        return self._ws
-
-    def workspace_bytes(self):
-        import ctypes as C
-        n = C.c_longlong()
-        check(capi.load().pam_amd_shoc_workspace_bytes(self._ws, C.byref(n)))
-        return n.value
-
-    def workspace_views(self, device):
-        """name -> torch view of the workspace array, in this object's layout"""
-        if self._views is None:
-            a = self._args
-            shapes = shoc_shapes(a.ncol, a.nlev, a.num_qtracers, self.layout)
-            self._views = {n: (torch.as_tensor(_DeviceArray(getattr(a, n), shp), device=device) if min(shp) > 0
-                               else torch.empty(shp, dtype=torch.float64, device=device)) for n, shp in shapes.items()}
-        return self._views
-
-    def _free(self):
-        if self._ws is not None:
-            check(capi.load().pam_amd_shoc_workspace_destroy(self._ws))
-        self._ws = self._ws_key = self._views = None
 
     def timeStep(self, coupler):
         """SGS.h:150-779.  Everything is checked before the first launch: a refused call leaves every field untouched"""
@@ -273,7 +311,7 @@ class SGSShoc:
         wthv_sec, tk, tkh, cldfrac, relvar = (dm.get(n) for n in ("wthv_sec", "tk", "tkh", "cldfrac", "inv_qc_relvar"))
         q = [dm.get(n) for n in names]
         qp = (C.c_void_p * max(len(q), 1))(*[t.data_ptr() for t in q])
-        ws = self._workspace(coupler, len(q))
+        ws = self._workspace(coupler, (nens, nx, ny, nz, len(q), self.layout))
         with torch.cuda.device(coupler.device):
             stream = torch.cuda.current_stream(coupler.device).cuda_stream
             check(lib.pam_amd_shoc_pack(ws, rho_d.data_ptr(), rho_v.data_ptr(), rho_c.data_ptr(), uvel.data_ptr(), vvel.data_ptr(),
@@ -282,10 +320,7 @@ class SGSShoc:
                                         zmid.data_ptr(), float(coupler.get_xlen()), float(coupler.get_ylen()), pres_R_d, pres_R_v, self.R_d,
                                         self.cp_d, self.p0, self.grav, self.latvap, stream))
             self._args.dt, self._args.nadv, self._args.stream = dt, 1, stream
-            if self._c_main:
-                rc = self.shoc_main(C.byref(self._args), self.user)
-            else:
-                rc = self.shoc_main(self.workspace_views(coupler.device), self._args)
+            rc = self._call_main(coupler.device)
             if rc not in (0, None):
                 endrun(f"ERROR: SHOC: shoc_main returned {rc}")
             check(lib.pam_amd_shoc_unpack(ws, rho_d.data_ptr(), rho_v.data_ptr(), rho_c.data_ptr(), uvel.data_ptr(), vvel.data_ptr(),
@@ -293,16 +328,6 @@ class SGSShoc:
                                           cldfrac.data_ptr(), relvar.data_ptr(), self.cp_d, self.cv_d, self.latvap, stream))
         self.first_step = False
         self.etime += dt
-
-    def finalize(self, coupler):
-        self._free()
-
-    def __del__(self):
-        # an object dropped without finalize() must not keep its workspace (18 to 21 GB at 1024 x 32x32x60) for the life of the process
-        try:
-            self._free()
-        except Exception:
-            pass
 
 
 class MicrophysicsNone:
@@ -365,7 +390,7 @@ def p3_shapes(ncol, nz, layout, num_tend_out=0):
     return out
 
 
-class MicrophysicsP3:
+class MicrophysicsP3(_CouplingLayer):
     """physics/micro/p3/Microphysics.h: the coupling layer around P3 -- the saturation adjustment where SHOC is not the SGS and pack
     (Microphysics.h:273-409), p3_main, unpack (:680-717) -- as two fused launches on the current stream.  P3 itself, its lookup tables and
     micro_p3_utils_init are not part of this library (option p3_lookup_data_path is not read): `p3_main` is
@@ -395,6 +420,7 @@ class MicrophysicsP3:
                  ("vap_ice_exchange_out", "p3 vap to ice phase change tendency"))                           # :131-143
     ARRAYS_3D = (("precip_liq_surf_out", "liq surface precipitation rate"), ("precip_ice_surf_out", "ice surface precipitation rate"))
     PACKED_TRACERS = ("cloud_water_num", "rain", "rain_num", "ice", "ice_num", "ice_rime", "ice_rime_vol")
+    _PREFIX, _ARGS, _MAIN_FN = "p3", capi.P3Args, capi.P3_MAIN_FN
 
     def __init__(self, p3_main=None, layout=1, user=None, num_tend_out=None):
         if layout not in (0, 1):
@@ -406,9 +432,7 @@ class MicrophysicsP3:
         self.sgs_shoc = False
         self.first_step = True
         self.etime = 0.0
-        self._ws = None
-        self._ws_key = None
-        self.set_p3_main(p3_main, user)
+        super().__init__(p3_main, user)
 
     @staticmethod
     def get_num_tracers():
@@ -426,17 +450,11 @@ class MicrophysicsP3:
     def micro_name():
         return "p3"
 
-    @staticmethod
-    def standin():
-        """the library's test double for p3_main (no physics): pam_amd_p3_main_standin"""
-        return capi.load().pam_amd_p3_main_standin
-
     def set_p3_main(self, fn, user=None):
-        import ctypes as C
-        if isinstance(fn, int):
-            fn = capi.P3_MAIN_FN(fn)
-        self._c_main = fn is not None and isinstance(fn, C._CFuncPtr)
-        self.p3_main, self.user = fn, user
+        self._set_main(fn, user)
+
+    def _shapes(self, a):
+        return p3_shapes(a.ncol, a.nlev, self.layout, a.num_tend_out)
 
     def init(self, coupler):
         """Microphysics.h:108-210: nine tracers, eight 4-D and two surface entries, all zero; option micro = "p3" and the constants"""
@@ -457,41 +475,6 @@ class MicrophysicsP3:
             coupler.set_option(k, getattr(self, k))
         self.etime = 0.0
 
-    def _workspace(self, coupler):
-        import ctypes as C
-        lib = capi.load()
-        key = (coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), self.layout, self.num_tend_out, str(coupler.device))
-        if self._ws is None or self._ws_key != key:
-            self._free()
-            ws = C.c_void_p()
-            with torch.cuda.device(coupler.device):
-                check(lib.pam_amd_p3_workspace_create(*key[:6], C.byref(ws)))
-            self._ws, self._ws_key = ws, key
-            self._args = capi.P3Args()
-            check(lib.pam_amd_p3_workspace_args(ws, C.byref(self._args)))
-            self._views = None
-        return self._ws
-
-    def workspace_bytes(self):
-        import ctypes as C
-        n = C.c_longlong()
-        check(capi.load().pam_amd_p3_workspace_bytes(self._ws, C.byref(n)))
-        return n.value
-
-    def workspace_views(self, device):
-        """name -> torch view of the workspace array, in this object's layout"""
-        if self._views is None:
-            a = self._args
-            shapes = p3_shapes(a.ncol, a.nlev, self.layout, a.num_tend_out)
-            self._views = {n: (torch.as_tensor(_DeviceArray(getattr(a, n), shp), device=device) if min(shp) > 0
-                               else torch.empty(shp, dtype=torch.float64, device=device)) for n, shp in shapes.items()}
-        return self._views
-
-    def _free(self):
-        if self._ws is not None:
-            check(capi.load().pam_amd_p3_workspace_destroy(self._ws))
-        self._ws = self._ws_key = self._views = None
-
     def timeStep(self, coupler):
         """Microphysics.h:214-741.  Everything is checked before the first launch: a refused call leaves every field untouched"""
         import ctypes as C
@@ -510,7 +493,7 @@ class MicrophysicsP3:
         p_liq, p_ice = dm.get("precip_liq_surf_out"), dm.get("precip_ice_surf_out")
         q = [dm.get(n) for n in self.PACKED_TRACERS]
         qp = (C.c_void_p * 7)(*[t.data_ptr() for t in q])
-        ws = self._workspace(coupler)
+        ws = self._workspace(coupler, (coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), self.layout, self.num_tend_out))
         self.sgs_shoc = sgs_shoc
         with torch.cuda.device(coupler.device):
             stream = torch.cuda.current_stream(coupler.device).cuda_stream
@@ -519,10 +502,7 @@ class MicrophysicsP3:
                                       0 if sgs_shoc else 1, int(self.first_step), self.R_d, self.R_v, self.cp_d, self.cp_v, self.cp_l,
                                       self.p0, self.grav, stream))
             self._args.dt, self._args.stream = dt, stream
-            if self._c_main:
-                rc = self.p3_main(C.byref(self._args), self.user)
-            else:
-                rc = self.p3_main(self.workspace_views(coupler.device), self._args)
+            rc = self._call_main(coupler.device)
             if rc not in (0, None):
                 endrun(f"ERROR: P3: p3_main returned {rc}")
             check(lib.pam_amd_p3_unpack(ws, rho_d.data_ptr(), rho_v.data_ptr(), rho_c.data_ptr(), qp, temp.data_ptr(), q_prev.data_ptr(),
@@ -530,12 +510,3 @@ class MicrophysicsP3:
                                         p_ice.data_ptr(), self.cp_d, self.cv_d, stream))
         self.first_step = False
         self.etime += dt
-
-    def finalize(self, coupler):
-        self._free()
-
-    def __del__(self):
-        try:
-            self._free()
-        except Exception:
-            pass

@@ -350,9 +350,14 @@ def test_offset_by_value_past_2_to_the_31(layout):
 
 
 def test_the_library_picks_the_wide_instances_before_a_byte_offset_passes_32_bits():
-    """P3_NARROW in modules_kernels.hip: arrays of 2^29 doubles (4 GiB) and more take the long long kernels, p3_tend_out included"""
+    """COUPLING_NARROW in modules_kernels.hip, shared with the SHOC layer: arrays of 2^29 doubles (4 GiB) and more take the long long
+    kernels, p3_tend_out included"""
     text = open(os.path.join(pc.ROOT, "pam_amd", "csrc", "modules_kernels.hip")).read()
-    assert re.search(r"P3_NARROW = 1ll << 29;", text) and "std::max<long long>(nout, 1) * nz * ncol" in text
+    assert len(re.findall(r"COUPLING_NARROW = 1ll << 29;", text)) == 1 and "P3_NARROW" not in text
+    assert "std::max<long long>(nout, 1) * nz * ncol" in text
+    # one narrow expression on the one constant; pack, unpack and the stand-in hand it P3's largest array
+    assert len(re.findall(r"\bcoupling_narrow\(bool force_wide, long long largest\) \{ return !force_wide && largest < COUPLING_NARROW; \}", text)) == 1
+    assert len(re.findall(r"coupling_narrow\(g_p3_force_wide, p3_largest\(", text)) == 3
     assert (2 ** 29 - 1) * 8 + 7 < 2 ** 32
 
 

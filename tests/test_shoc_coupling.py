@@ -293,11 +293,14 @@ def test_offset_by_value_past_2_to_the_31(layout):
 
 
 def test_the_library_picks_the_wide_instances_before_a_byte_offset_passes_32_bits():
-    """SHOC_NARROW in modules_kernels.hip: arrays of 2^29 doubles (4 GiB) and more take the long long kernels"""
+    """COUPLING_NARROW in modules_kernels.hip, shared with the P3 layer: arrays of 2^29 doubles (4 GiB) and more take the long long kernels"""
     import os
     import re
     text = open(os.path.join(sc.ROOT, "pam_amd", "csrc", "modules_kernels.hip")).read()
-    assert re.search(r"SHOC_NARROW = 1ll << 29;", text)
+    assert len(re.findall(r"COUPLING_NARROW = 1ll << 29;", text)) == 1 and "SHOC_NARROW" not in text
+    # one narrow expression on the one constant; pack, unpack and the stand-in hand it SHOC's largest array
+    assert len(re.findall(r"\bcoupling_narrow\(bool force_wide, long long largest\) \{ return !force_wide && largest < COUPLING_NARROW; \}", text)) == 1
+    assert len(re.findall(r"coupling_narrow\(g_shoc_force_wide, shoc_largest\(", text)) == 3
     assert (2 ** 29 - 1) * 8 + 7 < 2 ** 32
 
 

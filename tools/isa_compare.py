@@ -4,7 +4,7 @@
 usage: python tools/isa_compare.py BASE NEW [KERNEL [LINES]] > profiles/rNN_isa_compare.txt
 BASE / NEW: a .hip source (compiled here: hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only) or its assembly (.s).
 Kernels are matched by demangled name after mapping the tracer-sweep families that were merged into one
-(awfl_xtr_kernel<S, P, A> -> <S, P, 2, A>, awfl_xtrn_kernel<S, P, G> -> awfl_xtr_kernel<S, P, G, false>); symbol names and local labels
+(awfl_xtr_kernel<S, P, A> -> <S, P, 2, A>, awfl_xtrn_kernel<S, P, G> -> awfl_xtr_kernel<S, P, G, false>) and the two canary kernels that became coupling_canary_kernel<word>; symbol names and local labels
 are normalised.  Per kernel: the resources the compiler reports (VGPRs, AGPRs, SGPRs, scratch, waves per SIMD, LDS) and the instruction
 stream -- `identical`, `registers renamed` (the same opcodes in the same order, other register numbers) or `DIFFERENT` (with the
 opcode-count deltas).  KERNEL: print a unified diff of that kernel's streams as well (LINES of it, default 80).
@@ -18,6 +18,8 @@ import sys
 import tempfile
 
 RES = ["TotalNumSgprs", "NumVgprs", "NumAgprs", "ScratchSize", "Occupancy", "LDSByteSize"]
+# the canary kernels of the SHOC and the P3 coupling layer, merged into one template over the word they write
+CANARY = {"shoc_canary_kernel": 0x7ff853484f435f5f, "p3_canary_kernel": 0x7ff850335f57535f}
 
 
 def assembly(path, tmp):
@@ -40,6 +42,8 @@ def canon(d):
     m = re.match(r"awfl_xtr_kernel<(\d+), (\d+), (false|true)>", d)
     if m:
         return "awfl_xtr_kernel<%s, %s, 2, %s>" % m.groups()
+    if d in CANARY:
+        return "coupling_canary_kernel<%dull>" % CANARY[d]
     return d
 
 
