@@ -5,7 +5,8 @@
 //   -> (host model fills the coupler fields) -> dycore.declare_current_profile_as_hydrostatic
 //   -> N x { coupler.run_module("dycore", dycore.timeStep); [sponge_layer]; [micro.timeStep] } -> output
 //
-//   driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] <input.bin> <output.bin>
+//   driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE [--vt-u] [--vt-limit L]]
+//          <input.bin> <output.bin>
 //
 // --gpus N: the ensemble is sharded by member index over N devices of this node -- ONE host thread, ONE coupler and ONE dycore
 // handle per device (hipSetDevice before init), no inter-device halo and no collective library: the exchanges the reference
@@ -17,6 +18,9 @@
 // --accelerate A: CRM mean-state acceleration (modules/mean_state_acceleration.h): the file's nsteps are the CRM steps of ONE GCM step,
 // run on modules::MsaClock; the cease flag is global over the members, so the ranks OR theirs on the host through the same HostMin
 // (the maximum of 0 / 1 is minus the minimum of their negatives).  Rank 0 prints the number of CRM steps that ran.
+// --vt RATE: CRM variance transport (modules/variance_transport.h): the file's nsteps are the CRM steps of ONE GCM step; there is no GCM
+// here, so the variance tendency is RATE (a relative growth rate per second) times the variance the step starts from.  Everything is
+// per member: no exchange between the ranks.
 // --bench K W: W untimed + K timed steps between barriers; rank 0 prints one JSON line with the wall time (bench.py --launcher cpp).
 //
 // Input/output are raw little-endian fp64 files written/read by tests/test_cpp_driver.py (the reference reads YAML and
@@ -50,6 +54,7 @@
 #include "modules/horizontal_average.h"
 #include "modules/time_average.h"
 #include "modules/mean_state_acceleration.h"
+#include "modules/variance_transport.h"
 #include "vertical_interp.h"
 #include "physics/micro/kessler_amd/Microphysics.h"
 #include "physics/sgs/none/SGS.h"
@@ -103,6 +108,19 @@ static void shard_range(int nens, int r, int n, int &lo, int &hi) {
   hi = lo + base + (r < rem ? 1 : 0);
 }
 
+// the stand-alone run has no GCM: after vt_init the variance tendency is a relative growth rate per second of the starting variance
+static void vt_set_growth_rate(pam::PamCoupler &coupler, double rate) {
+  auto &dm = coupler.get_data_manager_device_readwrite();
+  const size_t n = (size_t)coupler.get_nz() * coupler.get_nens();
+  std::vector<real> h(n);
+  const char *q[3] = {"t", "q", "u"};
+  for (int i = 0; i < (coupler.get_option<bool>("crm_vt_u") ? 3 : 2); i++) {
+    if (hipMemcpy(h.data(), dm.get<real const, 2>(std::string("vt_var_start_") + q[i]).data(), n * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess) endrun("memcpy");
+    for (auto &v : h) v = rate * v;
+    if (hipMemcpy(dm.get<real, 2>(std::string("vt_tend_") + q[i]).data(), h.data(), n * sizeof(real), hipMemcpyHostToDevice) != hipSuccess) endrun("memcpy");
+  }
+}
+
 struct Job {
   int nens, nx, ny, nz, nt, nsteps;
   bool mode_a, with_sponge, with_micro, halo_roundtrip, has_consts;
@@ -119,6 +137,8 @@ struct Job {
   bool accelerate = false, accel_uv = false;
   double accel_factor = 0, accel_max_ttend = 5.0;
   int accel_crm_steps = 0, accel_ceased = 0;   // out (rank 0)
+  bool vt = false, vt_u = false;
+  double vt_rate = 0, vt_limit = 0.05;
 };
 
 struct BenchResult { double seconds = 0; long substeps = 0; };
@@ -215,6 +235,18 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
       }
     }
   };
+  // --vt: the file's steps are ONE GCM step; the forcing closes every CRM step with the model time the step counts
+  const bool vt = J.vt && J.bench_steps == 0;
+  if (vt) {
+    coupler.set_option<real>("gcm_physics_dt", J.nsteps * J.geo[2]);
+    coupler.set_option<bool>("crm_vt_u", J.vt_u);
+    coupler.set_option<real>("crm_vt_scale_limit", J.vt_limit);
+    coupler.run_module("vt_init", modules::vt_init);
+    vt_set_growth_rate(coupler, J.vt_rate);
+  }
+  auto vt_step = [&](int weight) {
+    if (vt) coupler.run_module("vt_apply_forcing", [&](pam::PamCoupler &c) { modules::vt_apply_forcing(c, weight * J.geo[2]); });
+  };
   if (J.bench_steps > 0) {
     for (int s = 0; s < J.bench_warmup; s++) one_step();
     if (hipDeviceSynchronize() != hipSuccess) endrun("device error");
@@ -241,13 +273,14 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
         coupler.run_module("msa_accelerate", [&](pam::PamCoupler &c) {
           cease = modules::msa_accelerate(c, [&](int mine) { return world == 1 ? mine : (int)-hmin(rank, -(double)mine); });
         });
-      clock.advance(cease);
+      vt_step(clock.advance(cease));
       steps++;
     }
     if (rank == 0) { J.accel_crm_steps = steps; J.accel_ceased = clock.ceased() ? 1 : 0; }
   } else {
-    for (int s = 0; s < J.nsteps; s++) one_step();
+    for (int s = 0; s < J.nsteps; s++) { one_step(); vt_step(1); }
   }
+  if (vt) coupler.run_module("vt_compute_feedback", modules::vt_compute_feedback);
   if (hipDeviceSynchronize() != hipSuccess) endrun("device error");
   for (size_t f = 0; f < names.size() && J.want_output; f++) {
     if (hipMemcpy(buf.data(), dm.get<real, 4>(names[f]).data(), ncell * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess) endrun("memcpy");
@@ -264,7 +297,8 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
-//          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] <output.bin | ->
+//          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
+//          <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
 // out_freq, vcoords [, crm_nz, zlen, idealized, apply_sponge, initData].  What runs, in the reference's order:
@@ -359,11 +393,18 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              every CRM step, modules::msa_accelerate after its last module; the CRM loop runs on modules::MsaClock, so
 //                              a GCM step takes nsteps_crm_phys / (1 + A) CRM steps (1 + A must divide it) unless the acceleration ceases,
 //                              and --stats weighs every step by the clock's count.  Without it the loop is the one above.
+//   --vt RATE PATH [--vt-u] [--vt-limit L]   CRM variance transport (modules/variance_transport.h): modules::vt_init at the start of every GCM
+//                              step; there is no GCM here, so vt_tend_x = RATE vt_var_start_x (a relative growth rate per second) for
+//                              that GCM step; modules::vt_apply_forcing LAST in every CRM step, after the clock has advanced, with dt =
+//                              the step's weight times crm_dt, so that it composes with --accelerate; modules::vt_compute_feedback at the
+//                              end of the GCM step.  PATH receives one JSON line per GCM step with var_start, var and feedback of every
+//                              quantity as flat (nz,nens) lists, printed with %.17g.  RATE = 0 changes nothing of the run.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  double tau = 0, bflx = 0, accel_factor = 0, accel_max_ttend = 5.0;
+  bool vt = false, vt_u = false;
+  double tau = 0, bflx = 0, accel_factor = 0, accel_max_ttend = 5.0, vt_rate = 0, vt_limit = 0.05;
   int rad_nx = 0, rad_ny = 0;
-  std::string stats, edges, rad_path, diag;
+  std::string stats, edges, rad_path, diag, vt_path;
 };
 
 // one JSON number that Python's json module reads back exactly (NaN / Infinity for the non-finite)
@@ -473,6 +514,13 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       coupler.set_option<bool>("crm_accel_uv", mods.accel_uv);
       coupler.set_option<real>("crm_accel_max_ttend", mods.accel_max_ttend);
     }
+    std::ofstream vt_out;
+    if (mods.vt) {
+      coupler.set_option<bool>("crm_vt_u", mods.vt_u);
+      coupler.set_option<real>("crm_vt_scale_limit", mods.vt_limit);
+      vt_out.open(mods.vt_path);
+      if (!vt_out) endrun("cannot open the --vt file");
+    }
     auto &dm = coupler.get_data_manager_device_readwrite();
     double *sf_in = nullptr;                                                 // tau_in, bflx_in of surface_friction_init: (2, nens)
     if (mods.surface_friction) {
@@ -516,6 +564,10 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       // the CRM loop runs on the clock: without --accelerate every step counts 1 and the loop is step_crm_phys = 0 .. nsteps_crm_phys - 1
       modules::MsaClock clock(nsteps_crm_phys, mods.accelerate ? mods.accel_factor : 0.0);
       if (mods.accelerate) coupler.run_module("msa_init", modules::msa_init);
+      if (mods.vt) {
+        coupler.run_module("vt_init", modules::vt_init);
+        vt_set_growth_rate(coupler, mods.vt_rate);
+      }
       while (!clock.done() && !stop) {
         const bool accel = clock.accelerating();
         if (accel) coupler.run_module("msa_diagnose", modules::msa_diagnose);
@@ -536,6 +588,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (accel) coupler.run_module("msa_accelerate", [&](pam::PamCoupler &c) { cease = modules::msa_accelerate(c); });
         const int weight = clock.advance(cease);
         if (accel && !cease) accel_steps++;
+        if (mods.vt) coupler.run_module("vt_apply_forcing", [&](pam::PamCoupler &c) { modules::vt_apply_forcing(c, weight * dt_crm_phys); });
         if (stats) coupler.run_module("time_average_accumulate", [&](pam::PamCoupler &c) { modules::time_average_accumulate(c, stat_names, weight); });
         if (mods.validate) dm.validate_all();
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
@@ -575,6 +628,29 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (steps_limit > 0 && crm_steps >= steps_limit) stop = true;
       }
       if (clock.ceased()) accel_ceased_gcm_steps++;
+      if (mods.vt) {                                                          // the GCM step's variances
+        coupler.run_module("vt_compute_feedback", modules::vt_compute_feedback);
+        std::string o = "{\"gcm_step\": " + std::to_string(step_gcm);
+        std::vector<real> prof((size_t)crm_nz * nens);
+        for (const char *what : {"var_start", "var", "feedback"}) {
+          o += std::string(", \"") + what + "\": {";
+          const char *q[3] = {"t", "q", "u"};
+          for (int i = 0; i < (mods.vt_u ? 3 : 2); i++) {
+            if (hipMemcpy(prof.data(), dm.get<real const, 2>(std::string("vt_") + what + "_" + q[i]).data(), prof.size() * sizeof(real),
+                          hipMemcpyDeviceToHost) != hipSuccess) endrun("memcpy");
+            o += std::string(i ? ", \"" : "\"") + q[i] + "\": [";
+            for (size_t j = 0; j < prof.size(); j++) {
+              if (j) o += ", ";
+              stats_json_number(o, prof[j]);
+            }
+            o += "]";
+          }
+          o += "}";
+        }
+        o += "}\n";
+        vt_out << o << std::flush;
+        if (!vt_out) endrun("cannot write the --vt file");
+      }
       if (stats) {                                                            // the GCM step's profiles
         coupler.run_module("horizontal_average", [&](pam::PamCoupler &c) { modules::horizontal_average(c, stat_havg); });
         char t[96];
@@ -673,6 +749,8 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     if (mods.accelerate)
       std::printf("{\"accel_factor\": %.9g, \"accel_uv\": %s, \"accel_max_ttend\": %.9g, \"accelerated_steps\": %d, \"ceased_gcm_steps\": %d}\n",
                   mods.accel_factor, mods.accel_uv ? "true" : "false", mods.accel_max_ttend, accel_steps, accel_ceased_gcm_steps);
+    if (mods.vt)
+      std::printf("{\"vt_rate\": %.17g, \"vt_u\": %s, \"vt_limit\": %.17g}\n", mods.vt_rate, mods.vt_u ? "true" : "false", mods.vt_limit);
     std::printf("{\"crm_steps\": %d, \"substeps\": %ld, \"etime\": %.9g, \"dt_crm_phys\": %.9g, \"nens\": %d, \"nx\": %d, \"ny\": %d, \"nz\": %d, "
                 "\"finite\": %s, \"rho_d_min\": %.9g, \"temp_min\": %.9g, \"temp_max\": %.9g, \"maxw_final\": %.9g, \"maxw_any_output\": %.9g, "
                 "\"temp_min_level\": %ld, \"tracer_min\": %.9g, \"maxw_series\": [%s], \"conservation_checked\": %s, \"conservation_violations\": %ld, "
@@ -723,9 +801,12 @@ int main(int argc, char **argv) {
       else if (o == "--accelerate" && b + 1 < argc - 1) { mods.accelerate = true; mods.accel_factor = std::atof(argv[++b]); }
       else if (o == "--accel-uv") mods.accel_uv = true;
       else if (o == "--accel-max-ttend" && b + 1 < argc - 1) mods.accel_max_ttend = std::atof(argv[++b]);
+      else if (o == "--vt" && b + 2 < argc - 1) { mods.vt = true; mods.vt_rate = std::atof(argv[++b]); mods.vt_path = argv[++b]; }
+      else if (o == "--vt-u") mods.vt_u = true;
+      else if (o == "--vt-limit" && b + 1 < argc - 1) mods.vt_limit = std::atof(argv[++b]);
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] <output.bin | ->");
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] <output.bin | ->");
     }
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }
@@ -739,10 +820,13 @@ int main(int argc, char **argv) {
     else if (o == "--accelerate" && a + 1 < argc) { J.accelerate = true; J.accel_factor = std::atof(argv[++a]); }
     else if (o == "--accel-uv") J.accel_uv = true;
     else if (o == "--accel-max-ttend" && a + 1 < argc) J.accel_max_ttend = std::atof(argv[++a]);
-    else die("usage: driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] <input.bin> <output.bin>");
+    else if (o == "--vt" && a + 1 < argc) { J.vt = true; J.vt_rate = std::atof(argv[++a]); }
+    else if (o == "--vt-u") J.vt_u = true;
+    else if (o == "--vt-limit" && a + 1 < argc) J.vt_limit = std::atof(argv[++a]);
+    else die("usage: driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE [--vt-u] [--vt-limit L]] <input.bin> <output.bin>");
   }
   if (argc - a != 2 || gpus < 1 || tile < 1)
-    die("usage: driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] <input.bin> <output.bin>");
+    die("usage: driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE [--vt-u] [--vt-limit L]] <input.bin> <output.bin>");
   std::ifstream in(argv[a], std::ios::binary);
   if (!in) die("cannot open input");
   int64_t hdr[8];

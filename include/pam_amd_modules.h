@@ -440,6 +440,42 @@ int pam_amd_msa_tendencies(int nens, int nx, int ny, int nz, const double *const
 int pam_amd_msa_apply(int nens, int nx, int ny, int nz, double *const *fields, const double *const *tend, double accel_factor,
                       int accel_uv, const int *cease_dev, void *stream);
 
+/* CRM variance transport (VT; Hannah and Pressel 2022, E3SM-MMF's use_MMF_VT with MMF_VT_wn_max = 0, the bulk form): the GCM carries the
+ * CRM's horizontal variance of temp and total water (optionally uvel) as tracers and hands back a variance tendency; the CRM stretches or
+ * shrinks its anomalies about the level mean on every CRM step, and reports the variance it produced.  Not part of the reference tree;
+ * the contract is this project's and is restated in numpy in tests/vt_ref.py, which the kernels match bit for bit.
+ *   fields[5]   HOST array of DEVICE pointers (nz,ny,nx,nens): temp, water_vapor, cloud or NULL, ice or NULL, uvel
+ *   mean[3], var[3], scale[3], tend[3], var_start[3], feedback[3]   HOST arrays of DEVICE pointers (nz,nens): t = temp, q = total water
+ *               = water_vapor + cloud + ice (left to right, an absent species skipped), u = uvel
+ *   use_u == 0: fields[4] and entry [2] of every table are neither read nor written and may be NULL.
+ * Level statistics of x at (k,e), r = 1/(ny nx), ONE pass shifted by the level's first cell: c = x(k,0,e); d(i) = x(k,i,e) - c;
+ * A = M(d) with M the level mean of mean-state acceleration above (cell i in slot i % 16; a slot adds d r, the product rounded first,
+ * no fma, over its cells in ascending order from 0.0; the slot sums added in ascending order from 0.0); B = M(d d), d d rounded, then
+ * times r rounded, then added; mean = c + A; var = B - A A (A A rounded, no fma); var < 0 becomes 0.0, a NaN stays.  A level that is
+ * constant in a member has var == 0.0 exactly.
+ * Scale: ratio = 1 + (dt tend) / var (the product rounded, one true division, the add); s = 1 where !(var > 0) or ratio is a NaN;
+ * otherwise s = sqrt(max(ratio, 0)) clamped into [1 - scale_limit, 1 + scale_limit].  One root and one division per (k,e).
+ *
+ * pam_amd_vt_diagnose   mean_x, var_x.  Writes nothing else.
+ * pam_amd_vt_forcing    mean_x, var_x and scale_x from tend_x (units of x^2 per second), dt and scale_limit.  Touches no state.
+ * pam_amd_vt_apply      g = s - 1 per (k,e).  Where g_t != 0: temp += g_t (temp - mean_t), the product rounded first; uvel likewise with
+ *               use_u.  Where g_q != 0 the total-water anomaly is scaled through the vapour alone: v' = v + g_q (q - mean_q), then the
+ *               mass-keeping fill of pam_amd_msa_apply over the level (P = S(max(v',0)), N = S(min(v',0)): kept / max(v',0) (1 + N/P) /
+ *               zeroed).  A quantity whose g is 0 at (k,e) keeps the bits of its fields there, negative vapour included: a zero tendency,
+ *               a zero variance or a NaN statistic changes nothing at all.  Cloud, ice and everything else are never written.
+ * pam_amd_vt_feedback   mean_x, var_x and feedback_x = (var_x - var_start_x) / gcm_dt, one true division per (k,e).
+ * Every argument is checked before the first HIP call (null tables, null temp / water_vapor, null uvel with use_u, nens / nx / ny / nz
+ * < 1, ny nx beyond 2^31 - 1, dt or gcm_dt not finite and positive, scale_limit outside (0,1)): a PAM_AMD_EINVAL return has written
+ * nothing and needs no device. */
+int pam_amd_vt_diagnose(int nens, int nx, int ny, int nz, const double *const *fields, int use_u, double *const *mean, double *const *var,
+                        void *stream);
+int pam_amd_vt_forcing(int nens, int nx, int ny, int nz, const double *const *fields, int use_u, const double *const *tend, double dt,
+                       double scale_limit, double *const *mean, double *const *var, double *const *scale, void *stream);
+int pam_amd_vt_apply(int nens, int nx, int ny, int nz, double *const *fields, int use_u, const double *const *mean,
+                     const double *const *scale, void *stream);
+int pam_amd_vt_feedback(int nens, int nx, int ny, int nz, const double *const *fields, int use_u, const double *const *var_start,
+                        double gcm_dt, double *const *mean, double *const *var, double *const *feedback, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2928,3 +2928,174 @@ extern "C" int pam_amd_msa_apply(int nens, int nx, int ny, int nz, double *const
                      fields[ms::F_U], fields[ms::F_V], T, accel_factor, accel_uv != 0 ? 1 : 0, cease_dev);
   return stats_launch_check(who);
 }
+
+// ------------------------------------------------------------------------------------------------
+// CRM variance transport (Hannah and Pressel 2022; E3SM-MMF's use_MMF_VT, bulk form): the GCM carries the CRM's horizontal variance of
+// temp and total water (and, optionally, uvel) as tracers and hands back a variance tendency; the CRM stretches or shrinks its anomalies
+// about the level mean on every CRM step and reports the variance it produced.  The method is not in the reference tree; the contract is
+// in include/pam_amd_modules.h and DESIGN.md section 8, its arithmetic in vt_device.h.  Launch shape, slot order and LDS rows are those
+// of mean-state acceleration above.  No scratch, no floating-point atomics; every element offset is 64 bits wide.
+#include "vt_device.h"
+
+namespace {
+namespace vt = pama::vt;
+struct VtFields { double *p[vt::NF]; };
+struct VtIn { const double *p[vt::NQ]; };
+struct VtOut { double *p[vt::NQ]; };
+enum { VT_DIAGNOSE, VT_FORCING, VT_FEEDBACK };
+
+// ONE sweep over up to five fields -> mean and variance of temp, total water and (use_u) uvel of every (level, member), shifted by the
+// level's first cell.  Six slot sums in two rounds of three through slot_reduce: 24 KB of LDS, not 48.  The epilogue is chosen at compile
+// time: VT_DIAGNOSE writes mean and var; VT_FORCING also the scale from in = tend, p = dt, lim; VT_FEEDBACK also (var - in) / p with
+// in = var_start, p = gcm_dt.  grid (member blocks, levels), block (members, 16 slots)
+template <int EPI>
+__global__ void __launch_bounds__(64 * MOD_NS) vt_stats_kernel(int nens, int ncol, VtFields F, int use_u, VtIn in, double p, double lim,
+                                                               VtOut mean, VtOut var, VtOut out) {
+  __shared__ double red[vt::NQ * MOD_NS * 64];
+  const int ME = blockDim.x, slot = threadIdx.y;
+  const int e0 = (int)blockIdx.x * ME + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1, k = (int)blockIdx.y;
+  const long long base = (long long)k * ncol * nens + e;
+  const double *f[vt::NF];
+#pragma unroll
+  for (int i = 0; i < vt::NF; i++) f[i] = F.p[i] ? F.p[i] + base : nullptr;
+  double c[vt::NQ] = {0.0, 0.0, 0.0}, a[vt::NQ] = {0.0, 0.0, 0.0}, b[vt::NQ] = {0.0, 0.0, 0.0};
+  if (ok) {
+    vt::first_cell(f, use_u != 0, c);
+    vt::stats_walk(f, (long long)nens, ncol, slot, use_u != 0, c, a, b);
+  }
+  slot_reduce<vt::NQ>(a, red);
+  slot_reduce<vt::NQ>(b, red);
+  if (slot != 0 || !ok) return;
+  const long long t = (long long)k * nens + e;
+#pragma unroll
+  for (int q = 0; q < vt::NQ; q++) {
+    if (q == vt::Q_U && !use_u) continue;
+    double m, v;
+    vt::finish(c[q], a[q], b[q], m, v);
+    mean.p[q][t] = m;
+    var.p[q][t] = v;
+    if constexpr (EPI == VT_FORCING) out.p[q][t] = vt::scale(v, in.p[q][t], p, lim);
+    if constexpr (EPI == VT_FEEDBACK) out.p[q][t] = vt::feedback(v, in.p[q][t], p);
+  }
+}
+
+// two sweeps per (level, member): P and N of the stretched vapour (vapour, cloud and ice are read) where g_q != 0 -- skipped by a
+// workgroup none of whose members has one --, then every cell of every quantity with g != 0 read and written once.  grid and block as above
+__global__ void __launch_bounds__(64 * MOD_NS) vt_apply_kernel(int nens, int ncol, VtFields F, int use_u, VtIn mean, VtIn scale) {
+  __shared__ double red[2 * MOD_NS * 64];
+  const int ME = blockDim.x, slot = threadIdx.y;
+  const int e0 = (int)blockIdx.x * ME + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1, k = (int)blockIdx.y;
+  const long long base = (long long)k * ncol * nens + e, t = (long long)k * nens + e, stride = nens;
+  double g[vt::NQ] = {0.0, 0.0, 0.0}, m[vt::NQ] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < vt::NQ; q++) {
+    if (q == vt::Q_U && !use_u) continue;
+    g[q] = vt::gain(scale.p[q][t]);
+    m[q] = mean.p[q][t];
+  }
+  const double *f[vt::NF];
+#pragma unroll
+  for (int i = 0; i < vt::NF; i++) f[i] = F.p[i] ? F.p[i] + base : nullptr;
+  const bool do_q = ok && g[vt::Q_Q] != 0;
+  double pn[2] = {0.0, 0.0};
+  if (__syncthreads_or(do_q ? 1 : 0)) {      // the same answer in every lane of the workgroup
+    if (do_q) vt::vapor_walk(f, stride, ncol, slot, g[vt::Q_Q], m[vt::Q_Q], pn);
+    slot_reduce<2>(pn, red);
+  }
+  if (!ok) return;
+  double factor;
+  const int mode = ms::vapor_mode(pn[0], pn[1], factor);
+  vt::apply_walk(F.p[vt::F_TEMP] + base, F.p[vt::F_VAPOR] + base, f[vt::F_CLOUD], f[vt::F_ICE], use_u ? F.p[vt::F_U] + base : nullptr, stride,
+                 ncol, slot, g, m, use_u != 0, mode, factor);
+}
+
+int vt_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
+
+// the checks the four entry points share, all before the first HIP call; tables: the call's (nz,nens) tables, n of them
+int vt_check(const char *who, int nens, int nx, int ny, int nz, const double *const *fields, int use_u, const double *const *const *tables,
+             int n) {
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return vt_error(who, "nens, nx, ny and nz must be >= 1");
+  if ((long long)nx * ny > 0x7fffffffLL) return vt_error(who, "ny x nx exceeds 2^31 - 1 columns");
+  if (nz > 65535) return vt_error(who, "nz exceeds the grid (65535 levels)");
+  if (!fields) return vt_error(who, "null pointer table");
+  for (int i = 0; i < n; i++)
+    if (!tables[i]) return vt_error(who, "null pointer table");
+  if (!fields[vt::F_TEMP] || !fields[vt::F_VAPOR]) return vt_error(who, "null temp or water_vapor pointer");
+  if (use_u && !fields[vt::F_U]) return vt_error(who, "null uvel pointer");
+  for (int i = 0; i < n; i++)
+    for (int q = 0; q < (use_u ? vt::NQ : vt::NQ - 1); q++)
+      if (!tables[i][q]) return vt_error(who, "null pointer in a table of (nz,nens) arrays");
+  return PAM_AMD_OK;
+}
+
+VtFields vt_fields(const double *const *fields, int use_u) {
+  VtFields F;
+  for (int i = 0; i < vt::NF; i++) F.p[i] = (i == vt::F_U && !use_u) ? nullptr : const_cast<double *>(fields[i]);
+  return F;
+}
+template <class T, class P>
+T vt_table(P const *table, int use_u) {
+  T t;
+  for (int q = 0; q < vt::NQ; q++) t.p[q] = (!table || (q == vt::Q_U && !use_u)) ? nullptr : table[q];
+  return t;
+}
+
+template <int EPI>
+int vt_stats_launch(const char *who, int nens, int nx, int ny, int nz, const double *const *fields, int use_u, const double *const *in,
+                    double p, double lim, double *const *mean, double *const *var, double *const *out, void *stream) {
+  dim3 grid, block;
+  msa_launch_shape(nens, nz, grid, block);
+  hipLaunchKernelGGL((vt_stats_kernel<EPI>), grid, block, 0, (hipStream_t)stream, nens, nx * ny, vt_fields(fields, use_u), use_u ? 1 : 0,
+                     vt_table<VtIn>(in, use_u), p, lim, vt_table<VtOut>(mean, use_u), vt_table<VtOut>(var, use_u),
+                     vt_table<VtOut>(out, use_u));
+  return stats_launch_check(who);
+}
+}  // namespace
+
+extern "C" int pam_amd_vt_diagnose(int nens, int nx, int ny, int nz, const double *const *fields, int use_u, double *const *mean,
+                                   double *const *var, void *stream) {
+  const char *who = "vt_diagnose";
+  const double *const *tables[2] = {mean, var};
+  if (int rc = vt_check(who, nens, nx, ny, nz, fields, use_u, tables, 2)) return rc;
+  if (int rc = moist_surface_device_check(who)) return rc;
+  return vt_stats_launch<VT_DIAGNOSE>(who, nens, nx, ny, nz, fields, use_u, nullptr, 0.0, 0.0, mean, var, nullptr, stream);
+}
+
+extern "C" int pam_amd_vt_forcing(int nens, int nx, int ny, int nz, const double *const *fields, int use_u, const double *const *tend,
+                                  double dt, double scale_limit, double *const *mean, double *const *var, double *const *scale,
+                                  void *stream) {
+  const char *who = "vt_forcing";
+  const double *const *tables[4] = {tend, mean, var, scale};
+  if (int rc = vt_check(who, nens, nx, ny, nz, fields, use_u, tables, 4)) return rc;
+  if (!(dt > 0) || !std::isfinite(dt)) return vt_error(who, "dt must be finite and positive");
+  if (!(scale_limit > 0 && scale_limit < 1)) return vt_error(who, "scale_limit must lie in (0, 1)");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  return vt_stats_launch<VT_FORCING>(who, nens, nx, ny, nz, fields, use_u, tend, dt, scale_limit, mean, var, scale, stream);
+}
+
+extern "C" int pam_amd_vt_apply(int nens, int nx, int ny, int nz, double *const *fields, int use_u, const double *const *mean,
+                                const double *const *scale, void *stream) {
+  const char *who = "vt_apply";
+  const double *const *tables[2] = {mean, scale};
+  if (int rc = vt_check(who, nens, nx, ny, nz, fields, use_u, tables, 2)) return rc;
+  if (int rc = moist_surface_device_check(who)) return rc;
+  dim3 grid, block;
+  msa_launch_shape(nens, nz, grid, block);
+  hipLaunchKernelGGL(vt_apply_kernel, grid, block, 0, (hipStream_t)stream, nens, nx * ny, vt_fields(fields, use_u), use_u ? 1 : 0,
+                     vt_table<VtIn>(mean, use_u), vt_table<VtIn>(scale, use_u));
+  return stats_launch_check(who);
+}
+
+extern "C" int pam_amd_vt_feedback(int nens, int nx, int ny, int nz, const double *const *fields, int use_u, const double *const *var_start,
+                                   double gcm_dt, double *const *mean, double *const *var, double *const *feedback, void *stream) {
+  const char *who = "vt_feedback";
+  const double *const *tables[4] = {var_start, mean, var, feedback};
+  if (int rc = vt_check(who, nens, nx, ny, nz, fields, use_u, tables, 4)) return rc;
+  if (!(gcm_dt > 0) || !std::isfinite(gcm_dt)) return vt_error(who, "gcm_dt must be finite and positive");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  return vt_stats_launch<VT_FEEDBACK>(who, nens, nx, ny, nz, fields, use_u, var_start, gcm_dt, 0.0, mean, var, feedback, stream);
+}

@@ -541,3 +541,81 @@ def msa_accelerate(coupler, group=None):
         check(lib.pam_amd_msa_apply(nens, nx, ny, nz, _msa_table(fields), _msa_table(tend), float(coupler.get_option("crm_accel_factor")),
                                     1 if coupler.get_option("crm_accel_uv") else 0, cease.data_ptr(), stream))
     return False
+
+
+# ---- CRM variance transport (Hannah and Pressel 2022; E3SM-MMF's use_MMF_VT, bulk form).  Not part of the reference tree: the contract
+# is this project's (include/pam_amd_modules.h; numpy restatement: tests/vt_ref.py)
+VT_QUANTITIES = ("t", "q", "u")
+VT_ENTRIES = (("mean", "level mean"), ("var", "level variance"), ("var_start", "level variance at the start of the GCM step"),
+              ("scale", "factor of the anomalies in the last CRM step"), ("tend", "variance tendency from the GCM"),
+              ("feedback", "variance tendency of the CRM over the GCM step"))
+
+
+def _vt_arrays(coupler):
+    """-> fields[5], {entry: [t, q, u or None]}, use_u"""
+    from .coupler import endrun
+    dm = coupler.get_data_manager_device_readwrite()
+    if not dm.entry_exists("vt_var_start_t"):
+        endrun("ERROR: variance transport: call vt_init first")
+    use_u = bool(coupler.get_option("crm_vt_u"))
+    micro = coupler.get_option("micro") if coupler.option_exists("micro") else "none"
+    if micro not in MSA_CONDENSATE:
+        endrun("ERROR: variance transport only knows the kessler, p3 and none microphysics")
+    cloud, ice = MSA_CONDENSATE[micro]
+    fields = [dm.get("temp"), dm.get("water_vapor"), dm.get(cloud, readonly=True) if cloud else None,
+              dm.get(ice, readonly=True) if ice else None, dm.get("uvel") if use_u else None]
+    tables = {n: [dm.get("vt_%s_%s" % (n, q)) if (q != "u" or use_u) else None for q in VT_QUANTITIES] for n, _ in VT_ENTRIES}
+    return fields, tables, use_u
+
+
+def vt_init(coupler):
+    """First in every GCM step: registers "vt_mean_x", "vt_var_x", "vt_var_start_x", "vt_scale_x", "vt_tend_x" (the GCM's input, zero-filled
+    when registered) and "vt_feedback_x" (nz,nens), x = t, q and (with crm_vt_u) u, on first use, and fills "vt_var_start_x" with the
+    variances the CRM starts from.  Options: "crm_vt_u" (default False), "crm_vt_scale_limit" (in (0,1), default 0.05)."""
+    from .coupler import endrun
+    if not coupler.option_exists("crm_vt_u"):
+        coupler.set_option("crm_vt_u", False)
+    if not coupler.option_exists("crm_vt_scale_limit"):
+        coupler.set_option("crm_vt_scale_limit", 0.05)
+    lim = float(coupler.get_option("crm_vt_scale_limit"))
+    if not 0 < lim < 1:
+        endrun("ERROR: variance transport: crm_vt_scale_limit must lie in (0, 1)")
+    nz, nens = coupler.get_nz(), coupler.get_nens()
+    dm = coupler.get_data_manager_device_readwrite()
+    if not dm.entry_exists("vt_var_start_t"):
+        for q in VT_QUANTITIES[:3 if coupler.get_option("crm_vt_u") else 2]:
+            for n, desc in VT_ENTRIES:
+                dm.register_and_allocate("vt_%s_%s" % (n, q), desc, (nz, nens), ("z", "nens"))
+            dm.get("vt_tend_" + q).zero_()
+    lib = capi.load()
+    fields, tb, use_u = _vt_arrays(coupler)
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_vt_diagnose(nens, coupler.get_nx(), coupler.get_ny(), nz, _msa_table(fields), int(use_u), _msa_table(tb["mean"]),
+                                      _msa_table(tb["var_start"]), torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+def vt_apply_forcing(coupler, dt=None):
+    """Last in a CRM step: the level statistics, the scale sqrt(1 + dt tend / var) clamped to 1 +- crm_vt_scale_limit, and the anomalies of
+    temp, total water (through the vapour, its negative values filled from the level) and, with crm_vt_u, uvel stretched by it.
+    dt: the model time the step counts (default: option "crm_dt"; an accelerated step passes its weight times crm_dt)."""
+    lib = capi.load()
+    fields, tb, use_u = _vt_arrays(coupler)
+    nens, nx, ny, nz = coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz()
+    dt = float(coupler.get_option("crm_dt") if dt is None else dt)
+    with torch.cuda.device(coupler.device):
+        stream = torch.cuda.current_stream(coupler.device).cuda_stream
+        check(lib.pam_amd_vt_forcing(nens, nx, ny, nz, _msa_table(fields), int(use_u), _msa_table(tb["tend"]), dt,
+                                     float(coupler.get_option("crm_vt_scale_limit")), _msa_table(tb["mean"]), _msa_table(tb["var"]),
+                                     _msa_table(tb["scale"]), stream))
+        check(lib.pam_amd_vt_apply(nens, nx, ny, nz, _msa_table(fields), int(use_u), _msa_table(tb["mean"]), _msa_table(tb["scale"]), stream))
+
+
+def vt_compute_feedback(coupler):
+    """At the end of a GCM step: "vt_feedback_x" = ("vt_var_x" - "vt_var_start_x") / gcm_physics_dt, with "vt_var_x" taken now."""
+    lib = capi.load()
+    fields, tb, use_u = _vt_arrays(coupler)
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_vt_feedback(coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), _msa_table(fields), int(use_u),
+                                      _msa_table(tb["var_start"]), float(coupler.get_option("gcm_physics_dt")), _msa_table(tb["mean"]),
+                                      _msa_table(tb["var"]), _msa_table(tb["feedback"]),
+                                      torch.cuda.current_stream(coupler.device).cuda_stream))

@@ -8,6 +8,8 @@ Run on the GPU box:  python tools/bench_modules.py            (--only vertical_i
 --only diagnostics: pam_amd.field_diagnostics whole-field and per-member, with the validation and time_average_accumulate rows;
 --only shoc: the SHOC coupling layer's pack and unpack in both layouts, both tracer sets, beside the composition the reference performs;
 --only p3: the P3 coupling layer's pack (with and without the saturation adjustment) and unpack in both layouts, beside its composition;
+--only vt: variance transport's diagnose, forcing, feedback and apply (with and without uvel), beside msa_diagnose, msa_apply and
+time_average_accumulate of the same run;
 --only msa: mean-state acceleration's diagnose, tendencies and apply (with and without the winds), beside horizontal_average and
 time_average_accumulate of the same run)"""
 import json
@@ -729,8 +731,110 @@ def msa_timing(dev, warmup=3, n=11):
     return out
 
 
+def vt_timing(dev, warmup=3, n=11, reps=3):
+    """CRM variance transport at the C2 grid on P3's names (temp, water_vapor, cloud_water, ice, uvel: all five fields of the level
+    statistics are read): pam_amd_vt_diagnose, pam_amd_vt_forcing, pam_amd_vt_feedback, and pam_amd_vt_apply with and without uvel, 3
+    warm-up calls and the median of 11 event-timed calls each, three repetitions (the row is the median repetition, `reps_ms` has all
+    three).  Algorithmic bytes count every field once per read or write the contract requires: five fields read for the statistics;
+    temp, water_vapor (and uvel) read and written and cloud_water, ice read once for the apply -- the second read of water_vapor,
+    cloud_water and ice by its first sweep is NOT counted (`worst_case_bytes` has it), so a sweep that misses the caches shows as a lower
+    fraction.  msa_diagnose (one read of six fields on the same launch shape: the yardstick of the statistics), msa_apply and
+    time_average_accumulate run beside them."""
+    from pam_amd import PamCoupler, capi, modules
+    from pam_amd import idealized as idz
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    cells = nens * nx * ny * nz
+    c = PamCoupler(dev)
+    c.set_option("crm_dt", 2.0)
+    c.set_option("gcm_physics_dt", 900.0)
+    c.allocate_coupler_state(nz, ny, nx, nens)
+    c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+    for t in ("water_vapor", "cloud_water", "ice"):
+        c.add_tracer(t, "", True, True)
+    c.set_option("micro", "p3")
+    c.set_option("crm_accel_factor", 2.0)
+    c.set_option("crm_accel_uv", True)
+    c.set_option("crm_vt_u", True)
+    dm = c.get_data_manager_device_readwrite()
+    names = ["density_dry", "uvel", "vvel", "wvel", "temp"] + c.get_tracer_names()
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for name in names:
+        t = dm.get(name)
+        t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev))
+    modules.msa_init(c)
+    modules.vt_init(c)
+    modules.time_average_init(c, names)
+    lib = capi.load()
+    mfields, msave, mtend, cease = modules._msa_arrays(c)
+    MF, MS, MT = modules._msa_table(mfields), modules._msa_table(msave), modules._msa_table(mtend)
+    fields, tb, _ = modules._vt_arrays(c)
+    F = modules._msa_table(fields)
+    T = {k: modules._msa_table(v) for k, v in tb.items()}
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    for q in ("t", "q", "u"):                       # a growth of 1e-3 per second of the starting variance, and a scale table of its own
+        dm.get("vt_tend_" + q).copy_(dm.get("vt_var_start_" + q) * 1.0e-3)
+        dm.get("vt_scale_" + q).fill_(1.001)
+
+    def timed(fn):
+        meds = []
+        for _ in range(reps):
+            for _ in range(warmup):
+                fn()
+            ts = []
+            for _ in range(n):
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ts.append(e0.elapsed_time(e1))
+            meds.append(sorted(ts)[len(ts) // 2])
+        return meds
+
+    def row(meds, nbytes, **more):
+        t = sorted(meds)[len(meds) // 2]
+        frac = [nbytes / m / 1e6 / bench.HBM_PEAK_GBS for m in meds]
+        return dict({"ms": t, "reps_ms": meds, "bytes": nbytes, "GBps": nbytes / t / 1e6, "hbm_frac": nbytes / t / 1e6 / bench.HBM_PEAK_GBS,
+                     "hbm_frac_spread": max(frac) - min(frac)}, **more)
+
+    out = {"vt_grid": "1024 x 32x32x60 (C2)",
+           "vt_method": "%d warm-up calls, median of %d event-timed calls, %d repetitions" % (warmup, n, reps)}
+    out["time_average_accumulate_8_fields"] = row(timed(lambda: modules.time_average_accumulate(c, names)), len(names) * cells * 24.0)
+    out["msa_diagnose"] = row(timed(lambda: capi.check(lib.pam_amd_msa_diagnose(nens, nx, ny, nz, MF, MS, stream))), 6 * cells * 8.0)
+    dm.get("accel_tend_t").fill_(1.0e-6)
+    for q in ("q", "u", "v"):
+        dm.get("accel_tend_" + q).zero_()
+    out["msa_apply_accel_uv"] = row(timed(lambda: capi.check(lib.pam_amd_msa_apply(nens, nx, ny, nz, MF, MT, 2.0, 1, cease.data_ptr(), stream))),
+                                    4 * cells * 16.0)
+    out["vt_diagnose"] = row(timed(lambda: capi.check(lib.pam_amd_vt_diagnose(nens, nx, ny, nz, F, 1, T["mean"], T["var"], stream))),
+                             5 * cells * 8.0)
+    out["vt_forcing"] = row(timed(lambda: capi.check(lib.pam_amd_vt_forcing(nens, nx, ny, nz, F, 1, T["tend"], 2.0, 0.05, T["mean"], T["var"],
+                                                                            T["scale"], stream))), 5 * cells * 8.0)
+    out["vt_feedback"] = row(timed(lambda: capi.check(lib.pam_amd_vt_feedback(nens, nx, ny, nz, F, 1, T["var_start"], 900.0, T["mean"], T["var"],
+                                                                              T["feedback"], stream))), 5 * cells * 8.0)
+    capi.check(lib.pam_amd_vt_diagnose(nens, nx, ny, nz, F, 1, T["mean"], T["var"], stream))
+    for u, label, nbytes, worst in ((1, "vt_apply_u", 64.0, 88.0), (0, "vt_apply", 48.0, 72.0)):
+        t = timed(lambda: capi.check(lib.pam_amd_vt_apply(nens, nx, ny, nz, F, u, T["mean"], T["scale"], stream)))
+        r = row(t, nbytes * cells)
+        out[label] = dict(r, worst_case_bytes=worst * cells, worst_case_hbm_frac=worst * cells / r["ms"] / 1e6 / bench.HBM_PEAK_GBS)
+    for k in ("vt_diagnose", "vt_forcing", "vt_feedback"):
+        out[k + "_vs_msa_diagnose_frac"] = out[k]["hbm_frac"] / out["msa_diagnose"]["hbm_frac"]
+        out[k + "_below_msa_diagnose_by"] = out["msa_diagnose"]["hbm_frac"] - out[k]["hbm_frac"]
+    out["vt_apply_u_vs_msa_apply_frac"] = out["vt_apply_u"]["hbm_frac"] / out["msa_apply_accel_uv"]["hbm_frac"]
+    out["vt_apply_u_vs_time_average_accumulate_frac"] = out["vt_apply_u"]["hbm_frac"] / out["time_average_accumulate_8_fields"]["hbm_frac"]
+    out["vt_per_crm_step_ms"] = out["vt_forcing"]["ms"] + out["vt_apply_u"]["ms"]
+    assert bool(torch.isfinite(dm.get("temp", readonly=True)).all()) and bool(torch.isfinite(dm.get("water_vapor", readonly=True)).all())
+    del dm, c, fields, tb, mfields, msave, mtend
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "vt"]:
+        print(json.dumps(vt_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "msa"]:
         print(json.dumps(msa_timing(dev)))
         sys.exit(0)
