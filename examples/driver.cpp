@@ -18,6 +18,7 @@
 // --accelerate A: CRM mean-state acceleration (modules/mean_state_acceleration.h): the file's nsteps are the CRM steps of ONE GCM step,
 // run on modules::MsaClock; the cease flag is global over the members, so the ranks OR theirs on the host through the same HostMin
 // (the maximum of 0 / 1 is minus the minimum of their negatives).  Rank 0 prints the number of CRM steps that ran.
+// --hyperdiff TAU: horizontal hyperdiffusion (modules/hyperdiffusion.h) with the time scale TAU (seconds) every CRM step after the sponge layer.
 // --vt RATE: CRM variance transport (modules/variance_transport.h): the file's nsteps are the CRM steps of ONE GCM step; there is no GCM
 // here, so the variance tendency is RATE (a relative growth rate per second) times the variance the step starts from.  Everything is
 // per member: no exchange between the ranks.
@@ -55,6 +56,7 @@
 #include "modules/time_average.h"
 #include "modules/mean_state_acceleration.h"
 #include "modules/variance_transport.h"
+#include "modules/hyperdiffusion.h"
 #include "vertical_interp.h"
 #include "physics/micro/kessler_amd/Microphysics.h"
 #include "physics/sgs/none/SGS.h"
@@ -139,6 +141,8 @@ struct Job {
   int accel_crm_steps = 0, accel_ceased = 0;   // out (rank 0)
   bool vt = false, vt_u = false;
   double vt_rate = 0, vt_limit = 0.05;
+  bool hyperdiff = false;
+  double hyperdiff_tau = 0;
 };
 
 struct BenchResult { double seconds = 0; long substeps = 0; };
@@ -203,6 +207,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
     (void)hipFree(ps); (void)hipFree(pt);
   }
 #endif
+  if (J.hyperdiff) modules::hyperdiffusion_init(coupler, J.hyperdiff_tau);
   auto one_step = [&]() {
 #ifdef PAMC_DYCORE
     coupler.run_module("dycore", [&](pam::PamCoupler &c) { dycore.timeStep(c); });      // driver.cpp:248
@@ -220,6 +225,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
     bench.substeps += dycore.last_ncycles();
 #endif
     if (J.with_sponge) coupler.run_module("sponge_layer", modules::sponge_layer);       // driver.cpp:250
+    if (J.hyperdiff) coupler.run_module("hyperdiffusion", [](pam::PamCoupler &c) { modules::hyperdiffusion(c); });
     if (J.with_micro) {                                                                  // driver.cpp:253
       if (world == 1) {
         coupler.run_module("micro", [&](pam::PamCoupler &c) { micro.timeStep(c); });
@@ -393,6 +399,9 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              every CRM step, modules::msa_accelerate after its last module; the CRM loop runs on modules::MsaClock, so
 //                              a GCM step takes nsteps_crm_phys / (1 + A) CRM steps (1 + A must divide it) unless the acceleration ceases,
 //                              and --stats weighs every step by the clock's count.  Without it the loop is the one above.
+//   --hyperdiff TAU            horizontal hyperdiffusion (modules/hyperdiffusion.h): modules::hyperdiffusion_init(coupler, TAU) once, then
+//                              modules::hyperdiffusion every CRM step after the sponge layer and the surface friction and before the
+//                              physics; composes with --accelerate and --vt
 //   --vt RATE PATH [--vt-u] [--vt-limit L]   CRM variance transport (modules/variance_transport.h): modules::vt_init at the start of every GCM
 //                              step; there is no GCM here, so vt_tend_x = RATE vt_var_start_x (a relative growth rate per second) for
 //                              that GCM step; modules::vt_apply_forcing LAST in every CRM step, after the clock has advanced, with dt =
@@ -401,7 +410,8 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              quantity as flat (nz,nens) lists, printed with %.17g.  RATE = 0 changes nothing of the run.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  bool vt = false, vt_u = false;
+  bool vt = false, vt_u = false, hyperdiff = false;
+  double hyperdiff_tau = 0;
   double tau = 0, bflx = 0, accel_factor = 0, accel_max_ttend = 5.0, vt_rate = 0, vt_limit = 0.05;
   int rad_nx = 0, rad_ny = 0;
   std::string stats, edges, rad_path, diag, vt_path;
@@ -514,6 +524,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       coupler.set_option<bool>("crm_accel_uv", mods.accel_uv);
       coupler.set_option<real>("crm_accel_max_ttend", mods.accel_max_ttend);
     }
+    if (mods.hyperdiff) modules::hyperdiffusion_init(coupler, mods.hyperdiff_tau);
     std::ofstream vt_out;
     if (mods.vt) {
       coupler.set_option<bool>("crm_vt_u", mods.vt_u);
@@ -581,6 +592,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         if (apply_sponge && !dbg.no_sponge) coupler.run_module("sponge_layer", modules::sponge_layer);         // driver.cpp:249-251
         if (mods.surface_friction) coupler.run_module("surface_friction", modules::compute_surface_friction);
+        if (mods.hyperdiff) coupler.run_module("hyperdiffusion", [](pam::PamCoupler &c) { modules::hyperdiffusion(c); });
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         if (!dbg.no_micro) coupler.run_module("micro", [&](pam::PamCoupler &c) { micro.timeStep(c); });         // driver.cpp:253
         if (mods.sat_adjust) coupler.run_module("saturation_adjustment", modules::saturation_adjustment);
@@ -746,6 +758,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
 #ifdef PAM_FUNCTION_TIMERS
     pam::function_timers::print();
 #endif
+    if (mods.hyperdiff) std::printf("{\"hyperdiff_timescale\": %.17g}\n", mods.hyperdiff_tau);
     if (mods.accelerate)
       std::printf("{\"accel_factor\": %.9g, \"accel_uv\": %s, \"accel_max_ttend\": %.9g, \"accelerated_steps\": %d, \"ceased_gcm_steps\": %d}\n",
                   mods.accel_factor, mods.accel_uv ? "true" : "false", mods.accel_max_ttend, accel_steps, accel_ceased_gcm_steps);
@@ -804,9 +817,10 @@ int main(int argc, char **argv) {
       else if (o == "--vt" && b + 2 < argc - 1) { mods.vt = true; mods.vt_rate = std::atof(argv[++b]); mods.vt_path = argv[++b]; }
       else if (o == "--vt-u") mods.vt_u = true;
       else if (o == "--vt-limit" && b + 1 < argc - 1) mods.vt_limit = std::atof(argv[++b]);
+      else if (o == "--hyperdiff" && b + 1 < argc - 1) { mods.hyperdiff = true; mods.hyperdiff_tau = std::atof(argv[++b]); }
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] <output.bin | ->");
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] <output.bin | ->");
     }
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }
@@ -823,10 +837,11 @@ int main(int argc, char **argv) {
     else if (o == "--vt" && a + 1 < argc) { J.vt = true; J.vt_rate = std::atof(argv[++a]); }
     else if (o == "--vt-u") J.vt_u = true;
     else if (o == "--vt-limit" && a + 1 < argc) J.vt_limit = std::atof(argv[++a]);
-    else die("usage: driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE [--vt-u] [--vt-limit L]] <input.bin> <output.bin>");
+    else if (o == "--hyperdiff" && a + 1 < argc) { J.hyperdiff = true; J.hyperdiff_tau = std::atof(argv[++a]); }
+    else die("usage: driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE [--vt-u] [--vt-limit L]] [--hyperdiff TAU] <input.bin> <output.bin>");
   }
   if (argc - a != 2 || gpus < 1 || tile < 1)
-    die("usage: driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE [--vt-u] [--vt-limit L]] <input.bin> <output.bin>");
+    die("usage: driver [--gpus N] [--tile R] [--bench K W] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE [--vt-u] [--vt-limit L]] [--hyperdiff TAU] <input.bin> <output.bin>");
   std::ifstream in(argv[a], std::ios::binary);
   if (!in) die("cannot open input");
   int64_t hdr[8];

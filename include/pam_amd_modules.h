@@ -476,6 +476,35 @@ int pam_amd_vt_apply(int nens, int nx, int ny, int nz, double *const *fields, in
 int pam_amd_vt_feedback(int nens, int nx, int ny, int nz, const double *const *fields, int use_u, const double *const *var_start,
                         double gcm_dt, double *const *mean, double *const *var, double *const *feedback, void *stream);
 
+/* Horizontal hyperdiffusion: the scale-selective fourth-difference damping of the 2 dx mode that E3SM-MMF's CRM applies once per CRM
+ * step between the sponge layer and the physics.  Not part of the reference tree; the contract is this project's
+ * and is restated in numpy in tests/hd_ref.py, which the kernels match bit for bit.
+ *   fields[num_fields]    HOST array of DEVICE pointers (nz,ny,nx,nens), members fastest, x and y periodic; updated IN PLACE
+ *   positive[num_fields]  HOST array: non-zero where the field must stay non-negative
+ * For one line along x, indices modulo nx: e1 = f[i-1] - f[i-2], e2 = f[i] - f[i-1], e3 = f[i+1] - f[i], e4 = f[i+2] - f[i+1],
+ * D4x = (e4 - e1) - 3.0 (e3 - e2), every operation rounded separately, the product before the subtraction, no fma.  D4y is the same along
+ * y; D4 = D4x + D4y with ny > 1 (IEEE addition of two operands commutes bit for bit, so the order of this one sum is not observable and
+ * not part of the contract) and D4 = D4x with ny == 1 (the y term is not computed, no + 0.0).  c = dt / (16.0 tau), once on the
+ * host; f_new = f - c D4, the product rounded first, every D4 taken from the field as it was before the call.  A field constant along
+ * its lines keeps its bits; a +-1 checkerboard in x (even nx, ny == 1) becomes exactly 0.0 at dt == tau.  The mode (kx, ky) is
+ * multiplied by 1 - (dt/tau)(sin^4(kx/2) + sin^4(ky/2)): stable for dt <= tau.
+ * A field flagged positive then gets the level fill of pam_amd_msa_apply, unchanged, with no increment: P = S(max(f_new, 0)) and
+ * N = S(min(f_new, 0)) per (level, member) in the 16-slot order (cell c = j nx + i in slot c % 16, ascending cells from 0.0, the slots
+ * folded in ascending order); a (level, member) without a negative value keeps the bits of f_new and is not written; otherwise
+ * max(f_new, 0) (1 + N/P), or 0 where P + N > 0 does not hold.  A NaN spreads to the cells whose stencil holds it and nowhere else;
+ * nothing is refused because of a value.  The same bits come out from run to run, for any split of the members or of the field list
+ * over calls, and on every internal path.
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: a null table or entry, num_fields outside 1..64, nens /
+ * nx / ny / nz < 1, nx < 5, 1 < ny < 5, ny nx beyond 2^31 - 1, dt or tau not finite and positive, dt > tau.
+ * Internally: ny == 1 walks each line in registers; ny > 1 walks the rows of a level with the original rows in LDS; where a level's
+ * rows fit no LDS, two launches per field go through a workspace of one field (allocated on first need, released by
+ * pam_amd_modules_finalize; that path ends in a synchronisation of the stream).
+ * pam_amd_hyperdiffusion_debug_path is a test switch like pam_amd_shoc_debug_wide_index: 0 = automatic, 1 = in place, 2 = workspace,
+ * 3 = in place with a quarter of the member block. */
+int pam_amd_hyperdiffusion(int nens, int nx, int ny, int nz, int num_fields, double *const *fields, const unsigned char *positive,
+                           double dt, double tau, void *stream);
+int pam_amd_hyperdiffusion_debug_path(int path);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,8 @@ MODULE_SYMBOLS = {
     "pam_amd_vt_apply": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_void_p), C.c_int] + [C.POINTER(C.c_void_p)] * 2 + [C.c_void_p]),
     "pam_amd_vt_feedback": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_double]
                             + [C.POINTER(C.c_void_p)] * 3 + [C.c_void_p]),
+    "pam_amd_hyperdiffusion": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_void_p), C.POINTER(C.c_ubyte), C.c_double, C.c_double, C.c_void_p]),
+    "pam_amd_hyperdiffusion_debug_path": (C.c_int, [C.c_int]),
 }
 
 

@@ -490,11 +490,13 @@ int kessler_read_dt_max(const double *slot, hipStream_t s, double *out) {
 
 void validate_scratch_free();   // the result scratch of pam_amd_validate_fields, defined with it below
 void diagnostics_scratch_free();   // the scratch of pam_amd_field_diagnostics, the same
+void hd_workspace_free();          // the workspace of pam_amd_hyperdiffusion's two-launch path, the same
 }  // namespace
 
 extern "C" int pam_amd_modules_finalize(void) {
   validate_scratch_free();
   diagnostics_scratch_free();
+  hd_workspace_free();
   std::lock_guard<std::mutex> lk(g_tab_mutex);
   int cur = -1;
   (void)hipGetDevice(&cur);
@@ -3098,4 +3100,261 @@ extern "C" int pam_amd_vt_feedback(int nens, int nx, int ny, int nz, const doubl
   if (!(gcm_dt > 0) || !std::isfinite(gcm_dt)) return vt_error(who, "gcm_dt must be finite and positive");
   if (int rc = moist_surface_device_check(who)) return rc;
   return vt_stats_launch<VT_FEEDBACK>(who, nens, nx, ny, nz, fields, use_u, var_start, gcm_dt, 0.0, mean, var, feedback, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Horizontal hyperdiffusion: the scale-selective fourth-difference damping of the 2 dx mode that E3SM-MMF's CRM applies once per CRM
+// step between the sponge layer and the physics, on temp, the winds and the water species.  The method is not in the reference tree; the
+// contract is in include/pam_amd_modules.h and DESIGN.md section 8, its arithmetic in hd_device.h.  The first module kernel here that
+// reads a horizontal neighbour, and it works IN PLACE: a cell's new value must never reach a neighbour that has not been updated yet.
+//   line path (ny == 1)   one lane owns one (level, member) line and walks x with a register window (hd::line_walk): nobody else
+//                         touches the line, and the lane reads every value before it writes it.
+//   row ring (ny > 1)     one workgroup owns ALL rows of one level for a block of members and walks y; the ORIGINAL rows it still needs
+//                         lie in LDS (rows 0, 1 kept, rows ny-2, ny-1 read ahead, a ring of six in between), and every stencil value is
+//                         taken from LDS, never from the field.  Row j + 3 is requested from the field while only rows < j are written.
+//   workspace             launch 1 writes f_new of one field to a workspace of one field, launch 2 copies it back: for a level whose
+//                         ring fits no LDS, and as the row ring's measuring stick.
+// The positivity fill is one more launch over the flagged fields on mean-state acceleration's block shape.  No floating-point atomics;
+// every element offset is 64 bits wide.
+#include "hd_device.h"
+
+namespace {
+namespace hd = pama::hd;
+struct HdFields { double *p[hd::MAX_FIELDS]; };
+constexpr int HD_THREADS = 256;
+constexpr int HD_RING_THREADS = 256;
+constexpr int HD_LDS_BYTES = 64 * 1024;      // the ring's budget: no more than 64 KB per workgroup
+constexpr int HD_PRE = (HD_LDS_BYTES / (hd::RING_ROWS * 8) + HD_RING_THREADS - 1) / HD_RING_THREADS;      // cells of one row per thread, at most
+enum { HD_AUTO, HD_INPLACE, HD_WORKSPACE, HD_INPLACE_NARROW };
+
+// grid (blocks of 256 lines, fields): lanes are consecutive members of one level, so every step of the walk is a coalesced row
+__global__ void __launch_bounds__(HD_THREADS) hd_line_kernel(int nens, int nx, long long lines, HdFields F, double c) {
+  const long long t = (long long)blockIdx.x * HD_THREADS + threadIdx.x;
+  if (t >= lines) return;
+  const long long k = t / nens, e = t % nens;
+  hd::line_walk(F.p[blockIdx.y] + k * nx * nens + e, (long long)nens, nx, c);
+}
+
+// grid (levels x member blocks, fields), block 256; LDS: hd::RING_ROWS rows of nx << me_log2 doubles.  A row's cells are dealt to the
+// threads members fastest, so a wavefront's accesses to the field are runs of 1 << me_log2 consecutive members
+__global__ void __launch_bounds__(HD_RING_THREADS) hd_ring_kernel(int nens, int nx, int ny, int nblk, int me_log2, HdFields F, double c) {
+  extern __shared__ double hd_rows[];
+  const int ME = 1 << me_log2, rowlen = nx << me_log2, tid = (int)threadIdx.x;
+  const int k = (int)blockIdx.x / nblk, e0 = ((int)blockIdx.x % nblk) << me_log2;
+  const int mw = nens - e0 < ME ? nens - e0 : ME;                           // members of this block that exist
+  const long long rowstride = (long long)nx * nens;
+  double *f = F.p[blockIdx.y] + (long long)k * ny * rowstride + e0;      // (k, 0, 0, e0)
+  auto load = [&](int r) {
+    double *dst = hd_rows + hd::ring_slot(r, ny) * rowlen;
+    const double *src = f + (long long)r * rowstride;
+    for (int t = tid; t < rowlen; t += HD_RING_THREADS) {
+      const int m = t & (ME - 1), i = t >> me_log2;
+      if (m < mw) dst[t] = src[(long long)i * nens + m];
+    }
+  };
+  // a ring row on its way: requested from the field BEFORE the step's stores are issued and put into LDS after them, so the request is
+  // in flight during the step's arithmetic and waiting for it does not wait for those stores (the memory counter runs in issue order).
+  // HD_LDS_BYTES bounds a row to HD_PRE cells per thread
+  double pre[HD_PRE];
+  auto fetch = [&](int r) {
+    const double *src = f + (long long)r * rowstride;
+#pragma unroll
+    for (int q = 0; q < HD_PRE; q++) {
+      const int t = tid + q * HD_RING_THREADS, m = t & (ME - 1), i = t >> me_log2;
+      if (t < rowlen && m < mw) pre[q] = src[(long long)i * nens + m];
+    }
+  };
+  auto stash = [&](int r) {
+    double *dst = hd_rows + hd::ring_slot(r, ny) * rowlen;
+#pragma unroll
+    for (int q = 0; q < HD_PRE; q++) {
+      const int t = tid + q * HD_RING_THREADS, m = t & (ME - 1);
+      if (t < rowlen && m < mw) dst[t] = pre[q];
+    }
+  };
+  load(0); load(1); load(ny - 2); load(ny - 1);
+  if (hd::ring_row(2, ny)) load(2);
+  for (int j = 0; j < ny; j++) {
+    __syncthreads();      // rows up to j + 2 are in LDS
+    // row j + 3 is requested while only rows < j are written
+    if (hd::ring_row(j + 3, ny)) fetch(j + 3);
+    const double *rm2 = hd_rows + hd::ring_slot(hd::wrap(j - 2, ny), ny) * rowlen, *rm1 = hd_rows + hd::ring_slot(hd::wrap(j - 1, ny), ny) * rowlen;
+    const double *r0 = hd_rows + hd::ring_slot(j, ny) * rowlen;
+    const double *rp1 = hd_rows + hd::ring_slot(hd::wrap(j + 1, ny), ny) * rowlen, *rp2 = hd_rows + hd::ring_slot(hd::wrap(j + 2, ny), ny) * rowlen;
+    double *out = f + (long long)j * rowstride;
+#pragma unroll
+    for (int q = 0; q < HD_PRE; q++) {
+      const int t = tid + q * HD_RING_THREADS, m = t & (ME - 1), i = t >> me_log2;
+      if (t < rowlen && m < mw) out[(long long)i * nens + m] = hd::cell_new(rm2 + m, rm1 + m, r0 + m, rp1 + m, rp2 + m, (long long)ME, i, nx, true, c);
+    }
+    // it takes the slot of row j - 3, which nobody reads after step j - 1: every thread has passed the barrier of step j
+    if (hd::ring_row(j + 3, ny)) stash(j + 3);
+  }
+}
+
+// launch 1 of the workspace path: every cell of one field from the field itself, the result elsewhere.  A grid-stride loop over
+// (k, j, i, e), e fastest
+__global__ void __launch_bounds__(HD_THREADS) hd_workspace_kernel(int nens, int nx, int ny, long long total, const double *f, double *ws,
+                                                                  double c) {
+  const long long rowstride = (long long)nx * nens;
+  for (long long idx = (long long)blockIdx.x * HD_THREADS + threadIdx.x; idx < total; idx += (long long)gridDim.x * HD_THREADS) {
+    const long long cell = idx / nens, row = cell / nx;
+    const int e = (int)(idx - cell * nens), i = (int)(cell - row * nx);
+    const long long k = row / ny;
+    const int j = (int)(row - k * ny);
+    const double *lvl = f + k * ny * rowstride + e;
+    ws[idx] = hd::cell_at(lvl, (long long)nens, rowstride, nx, ny, i, j, c);
+  }
+}
+
+// the fill of the flagged fields: P and N of every (level, member) in one sweep, then the level written where it holds a negative value.
+// grid (levels x member blocks, flagged fields), block (members, 16 slots) as mean-state acceleration's
+__global__ void __launch_bounds__(64 * MOD_NS) hd_fill_kernel(int nens, int ncol, int nblk, HdFields F) {
+  __shared__ double red[2 * MOD_NS * 64];
+  const int ME = blockDim.x, slot = threadIdx.y;
+  const int k = (int)blockIdx.x / nblk, e0 = ((int)blockIdx.x % nblk) * ME + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1;
+  double *p = F.p[blockIdx.y] + (long long)k * ncol * nens + e;
+  double pn[2] = {0.0, 0.0};
+  if (ok) hd::fill_walk(p, (long long)nens, ncol, slot, pn);
+  slot_reduce<2>(pn, red);
+  if (!ok) return;
+  double factor;
+  const int mode = ms::vapor_mode(pn[0], pn[1], factor);
+  hd::fill_apply_walk(p, (long long)nens, ncol, slot, mode, factor);
+}
+
+int hd_error(const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string("hyperdiffusion: ") + msg).c_str()); }
+
+// the workspace of one field: per device, grown on demand, freed by pam_amd_modules_finalize().  A device's mutex is held for a whole
+// call on the workspace path, which ends in a synchronisation of its stream: two streams never share the workspace.
+constexpr int HD_MAX_DEVICES = 64;
+struct HdWorkspace { std::mutex m; double *p = nullptr; long long count = 0; };
+HdWorkspace g_hd_workspace[HD_MAX_DEVICES];
+
+double *hd_workspace(HdWorkspace &w, long long count) {
+  if (w.count < count) {
+    if (w.p) (void)hipFree(w.p);
+    w.p = nullptr;
+    w.count = 0;
+    if (hipMalloc((void **)&w.p, (size_t)count * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); w.p = nullptr; return nullptr; }
+    w.count = count;
+  }
+  return w.p;
+}
+
+void hd_workspace_free() {
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  for (int d = 0; d < HD_MAX_DEVICES; d++) {
+    HdWorkspace &w = g_hd_workspace[d];
+    std::lock_guard<std::mutex> lk(w.m);
+    if (w.p) {
+      if (d != cur) (void)hipSetDevice(d);
+      (void)hipFree(w.p);
+      w.p = nullptr;
+      w.count = 0;
+      if (d != cur && cur >= 0) (void)hipSetDevice(cur);
+    }
+  }
+}
+
+int g_hd_path = HD_AUTO;   // pam_amd_hyperdiffusion_debug_path: tests run every path at small shapes
+
+// the widest member block (as log2) whose ring fits the LDS budget, no wider than the ensemble needs; -1: no block fits
+int hd_ring_block(int nens, int nx) {
+  const long long row = (long long)hd::RING_ROWS * nx * (long long)sizeof(double);
+  if (row > HD_LDS_BYTES) return -1;
+  int lg = 0;
+  while (lg < 6 && (row << (lg + 1)) <= HD_LDS_BYTES && (1 << lg) < nens) lg++;
+  return lg;
+}
+}  // namespace
+
+extern "C" int pam_amd_hyperdiffusion_debug_path(int path) {
+  if (path < HD_AUTO || path > HD_INPLACE_NARROW) return hd_error("debug path must be 0 (automatic), 1 (in place), 2 (workspace) or 3 (in place, narrow member blocks)");
+  g_hd_path = path;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_hyperdiffusion(int nens, int nx, int ny, int nz, int num_fields, double *const *fields, const unsigned char *positive,
+                                      double dt, double tau, void *stream) {
+  const char *who = "hyperdiffusion";
+  if (!fields || !positive) return hd_error("null fields or positive table");
+  if (num_fields < 1 || num_fields > hd::MAX_FIELDS) return hd_error("num_fields must be in [1, 64]");
+  for (int i = 0; i < num_fields; i++)
+    if (!fields[i]) return hd_error("null field pointer");
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return hd_error("nens, nx, ny and nz must be >= 1");
+  if (nx < 5) return hd_error("nx must be >= 5 (a five-point periodic stencil)");
+  if (ny > 1 && ny < 5) return hd_error("ny must be 1 or >= 5 (a five-point periodic stencil)");
+  if ((long long)nx * ny > 0x7fffffffLL) return hd_error("ny x nx exceeds 2^31 - 1 columns");
+  if (!(dt > 0) || !std::isfinite(dt) || !(tau > 0) || !std::isfinite(tau)) return hd_error("dt and tau must be finite and positive");
+  if (dt > tau) return hd_error("dt must not exceed tau (the scheme is stable for dt <= tau)");
+  const int me_fill = nens < 64 ? nens : 64;
+  const long long fill_blocks = (long long)((nens + me_fill - 1) / me_fill) * nz;
+  const long long lines = (long long)nz * nens;
+  if (fill_blocks > 0x7fffffffLL || (lines + HD_THREADS - 1) / HD_THREADS > 0x7fffffffLL) return hd_error("nz x nens exceeds the grid");
+  const int path = g_hd_path;
+  int lg = ny > 1 ? hd_ring_block(nens, nx) : 0;
+  if (path == HD_INPLACE_NARROW && lg > 0) lg = lg > 2 ? lg - 2 : 0;
+  const bool in_place = path == HD_WORKSPACE ? false : (ny == 1 || lg >= 0);
+  if (!in_place && path != HD_AUTO && path != HD_WORKSPACE) return hd_error("the forced row ring does not fit LDS at this nx");
+  const int nblk = ny > 1 && lg >= 0 ? (nens + (1 << lg) - 1) >> lg : 1;
+  if ((long long)nblk * nz > 0x7fffffffLL) return hd_error("nz x nens exceeds the grid");
+  if (int rc = moist_surface_device_check(who)) return rc;
+
+  const double c = hd::coefficient(dt, tau);
+  hipStream_t s = (hipStream_t)stream;
+  HdFields F, P;
+  int npos = 0;
+  for (int i = 0; i < hd::MAX_FIELDS; i++) { F.p[i] = nullptr; P.p[i] = nullptr; }
+  for (int i = 0; i < num_fields; i++) {
+    F.p[i] = fields[i];
+    if (positive[i]) P.p[npos++] = fields[i];
+  }
+  if (in_place && ny == 1) {
+    hipLaunchKernelGGL(hd_line_kernel, dim3((unsigned)((lines + HD_THREADS - 1) / HD_THREADS), (unsigned)num_fields), dim3(HD_THREADS), 0, s, nens,
+                       nx, lines, F, c);
+    if (int rc = stats_launch_check(who)) return rc;
+  } else if (in_place) {
+    const size_t lds = (size_t)hd::RING_ROWS * ((size_t)nx << lg) * sizeof(double);
+    hipLaunchKernelGGL(hd_ring_kernel, dim3((unsigned)((long long)nblk * nz), (unsigned)num_fields), dim3(HD_RING_THREADS), lds, s, nens, nx, ny,
+                       nblk, lg, F, c);
+    if (int rc = stats_launch_check(who)) return rc;
+  } else {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= HD_MAX_DEVICES)
+      return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "hyperdiffusion: cannot tell the current device");
+    HdWorkspace &w = g_hd_workspace[dev];
+    std::lock_guard<std::mutex> lk(w.m);
+    const long long total = (long long)nz * ny * nx * nens;
+    double *ws = hd_workspace(w, total);
+    if (!ws) return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "hyperdiffusion: cannot allocate the workspace of one field");
+    const long long want = (total + HD_THREADS - 1) / HD_THREADS;
+    const unsigned blocks = (unsigned)(want < (1LL << 20) ? want : (1LL << 20));
+    // whatever happens, the stream is synchronised before the mutex lets the next call at the workspace: after a failure too, what
+    // was launched before it may still be writing there
+    int rc = PAM_AMD_OK;
+    for (int i = 0; i < num_fields && !rc; i++) {
+      hipLaunchKernelGGL(hd_workspace_kernel, dim3(blocks), dim3(HD_THREADS), 0, s, nens, nx, ny, total, (const double *)fields[i], ws, c);
+      rc = stats_launch_check(who);
+      if (!rc && hipMemcpyAsync(fields[i], ws, (size_t)total * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        rc = pam_amd_set_last_error_(PAM_AMD_ENOGPU, "hyperdiffusion: the copy back from the workspace failed");
+    }
+    if (npos > 0 && !rc) {
+      hipLaunchKernelGGL(hd_fill_kernel, dim3((unsigned)fill_blocks, (unsigned)npos), dim3((unsigned)me_fill, (unsigned)MOD_NS), 0, s, nens,
+                         nx * ny, (nens + me_fill - 1) / me_fill, P);
+      rc = stats_launch_check(who);
+    }
+    const hipError_t done = hipStreamSynchronize(s);
+    if (!rc && done != hipSuccess) rc = pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": " + hipGetErrorString(done)).c_str());
+    return rc;
+  }
+  if (npos > 0) {
+    hipLaunchKernelGGL(hd_fill_kernel, dim3((unsigned)fill_blocks, (unsigned)npos), dim3((unsigned)me_fill, (unsigned)MOD_NS), 0, s, nens, nx * ny,
+                       (nens + me_fill - 1) / me_fill, P);
+    return stats_launch_check(who);
+  }
+  return PAM_AMD_OK;
 }

@@ -619,3 +619,36 @@ def vt_compute_feedback(coupler):
                                       _msa_table(tb["var_start"]), float(coupler.get_option("gcm_physics_dt")), _msa_table(tb["mean"]),
                                       _msa_table(tb["var"]), _msa_table(tb["feedback"]),
                                       torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+# ---- horizontal hyperdiffusion (the fourth-difference damping of the 2 dx mode E3SM-MMF's CRM applies between the sponge layer and the
+# physics).  Not part of the reference tree: the contract is this project's (include/pam_amd_modules.h; numpy
+# restatement: tests/hd_ref.py)
+HYPERDIFFUSION_FIELDS = ("temp", "uvel", "vvel", "wvel")
+
+
+def hyperdiffusion_init(coupler, tau):
+    """Once: sets the option "crm_hyperdiff_timescale" (seconds; the 2 dx mode of one direction decays by dt / tau per call)."""
+    from .coupler import endrun
+    if not float(tau) > 0:
+        endrun("ERROR: hyperdiffusion: crm_hyperdiff_timescale must be positive")
+    coupler.set_option("crm_hyperdiff_timescale", float(tau))
+
+
+def hyperdiffusion(coupler, dt=None):
+    """Once per CRM step, after the sponge layer and the surface friction and before SGS and microphysics: temp, uvel, vvel, wvel and every
+    registered tracer, in place; a tracer registered as positive is handed on non-negative.  density_dry is never touched.
+    dt: default the option "crm_dt"."""
+    from .coupler import endrun
+    if not coupler.option_exists("crm_hyperdiff_timescale"):
+        endrun("ERROR: hyperdiffusion: call hyperdiffusion_init first")
+    lib = capi.load()
+    dm = coupler.get_data_manager_device_readwrite()
+    tracers = coupler.get_tracer_names()
+    tens = [dm.get(n) for n in HYPERDIFFUSION_FIELDS] + [dm.get(n) for n in tracers]
+    positive = [0] * len(HYPERDIFFUSION_FIELDS) + [1 if coupler.get_tracer_info(n)[2] else 0 for n in tracers]
+    dt = float(coupler.get_option("crm_dt") if dt is None else dt)
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_hyperdiffusion(coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), len(tens), _ptr_table(tens),
+                                         (C.c_ubyte * len(tens))(*positive), dt, float(coupler.get_option("crm_hyperdiff_timescale")),
+                                         torch.cuda.current_stream(coupler.device).cuda_stream))

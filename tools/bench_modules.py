@@ -10,6 +10,8 @@ Run on the GPU box:  python tools/bench_modules.py            (--only vertical_i
 --only p3: the P3 coupling layer's pack (with and without the saturation adjustment) and unpack in both layouts, beside its composition;
 --only vt: variance transport's diagnose, forcing, feedback and apply (with and without uvel), beside msa_diagnose, msa_apply and
 time_average_accumulate of the same run;
+--only hyperdiffusion: the horizontal hyperdiffusion on its automatic and on each forced path at the C2 grid and at C4's 32x1x60 grid
+with 8192 members, beside msa_apply and time_average_accumulate of the same run;
 --only msa: mean-state acceleration's diagnose, tendencies and apply (with and without the winds), beside horizontal_average and
 time_average_accumulate of the same run)"""
 import json
@@ -830,8 +832,106 @@ def vt_timing(dev, warmup=3, n=11, reps=3):
     return out
 
 
+def hyperdiffusion_timing(dev, warmup=3, n=11):
+    """Horizontal hyperdiffusion at the C2 grid on the Kessler field set (temp, the three winds, three positive tracers: seven fields in
+    place) and at C4's 32x1x60 grid with 8192 members: the automatic path, each forced path (pam_amd_hyperdiffusion_debug_path: 1 in
+    place, 2 workspace, 3 in place with a quarter of the member block), 3 warm-up calls and the median of 11 event-timed calls each.
+    Algorithmic bytes: 16 B per cell and field (one read, one write) plus 8 B per cell of a flagged field for the fill's read -- the
+    tracers stay positive here, so the fill writes nothing; the workspace path's second read and write are NOT counted, so it shows as
+    the lower fraction it is.  msa_apply (with the winds) and time_average_accumulate of the same run stand beside them."""
+    import ctypes as C
+    from pam_amd import PamCoupler, capi, modules
+    from pam_amd import idealized as idz
+    lib = capi.load()
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    def row(t, nbytes):
+        return {"ms": t[0], "min_ms": t[1], "max_ms": t[2], "bytes": nbytes, "GBps": nbytes / t[0] / 1e6,
+                "hbm_frac": nbytes / t[0] / 1e6 / bench.HBM_PEAK_GBS}
+
+    def coupler(nens, nx, ny, nz):
+        c = PamCoupler(dev)
+        c.set_option("crm_dt", 2.0)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+        for t in ("water_vapor", "cloud_liquid", "precip_liquid"):
+            c.add_tracer(t, "", True, True)
+        c.set_option("micro", "kessler")
+        dm = c.get_data_manager_device_readwrite()
+        gen = torch.Generator(device=dev).manual_seed(0)
+        for name in ["density_dry", "uvel", "vvel", "wvel", "temp"] + c.get_tracer_names():
+            t = dm.get(name)
+            t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) + 0.5)
+        modules.hyperdiffusion_init(c, 60.0)
+        return c
+
+    def paths(c, label, out, which):
+        cells = c.get_nens() * c.get_nx() * c.get_ny() * c.get_nz()
+        nbytes = 7 * cells * 16.0 + 3 * cells * 8.0
+        for path, name in which:
+            capi.check(lib.pam_amd_hyperdiffusion_debug_path(path))
+            try:
+                out["hyperdiffusion_%s%s" % (name, label)] = row(timed(lambda: modules.hyperdiffusion(c)), nbytes)
+            finally:
+                capi.check(lib.pam_amd_hyperdiffusion_debug_path(0))
+        dm = c.get_data_manager_device_readwrite()
+        assert all(bool(torch.isfinite(dm.get(t, readonly=True)).all()) and bool((dm.get(t, readonly=True) >= 0).all())
+                   for t in c.get_tracer_names())
+
+    out = {"hyperdiffusion_grid": "1024 x 32x32x60 (C2) and 8192 x 32x1x60 (C4)",
+           "hyperdiffusion_method": "%d warm-up calls, median of %d event-timed calls" % (warmup, n)}
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    cells = nens * nx * ny * nz
+    c = coupler(nens, nx, ny, nz)
+    names = ["density_dry", "uvel", "vvel", "wvel", "temp"] + c.get_tracer_names()
+    c.set_option("gcm_physics_dt", 900.0)
+    c.set_option("crm_accel_factor", 2.0)
+    c.set_option("crm_accel_uv", True)
+    modules.msa_init(c)
+    modules.time_average_init(c, names)
+    mfields, msave, mtend, cease = modules._msa_arrays(c)
+    MF, MT = modules._msa_table(mfields), modules._msa_table(mtend)
+    dm = c.get_data_manager_device_readwrite()
+    dm.get("accel_tend_t").fill_(1.0e-6)
+    for q in ("q", "u", "v"):
+        dm.get("accel_tend_" + q).zero_()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    out["time_average_accumulate_8_fields"] = row(timed(lambda: modules.time_average_accumulate(c, names)), len(names) * cells * 24.0)
+    out["msa_apply_accel_uv"] = row(timed(lambda: capi.check(lib.pam_amd_msa_apply(nens, nx, ny, nz, MF, MT, 2.0, 1, cease.data_ptr(), stream))),
+                                    4 * cells * 16.0)
+    paths(c, "", out, ((0, "automatic"), (1, "in_place"), (2, "workspace"), (3, "in_place_narrow")))
+    out["hyperdiffusion_automatic_vs_msa_apply_frac"] = out["hyperdiffusion_automatic"]["hbm_frac"] / out["msa_apply_accel_uv"]["hbm_frac"]
+    out["hyperdiffusion_automatic_vs_workspace_speedup"] = out["hyperdiffusion_workspace"]["ms"] / out["hyperdiffusion_automatic"]["ms"]
+    del dm, c, mfields, msave, mtend
+    lib.pam_amd_modules_finalize()
+    torch.cuda.empty_cache()
+    c = coupler(8192, 32, 1, 60)
+    paths(c, "_c4", out, ((0, "automatic"), (2, "workspace")))
+    out["hyperdiffusion_automatic_vs_workspace_speedup_c4"] = out["hyperdiffusion_workspace_c4"]["ms"] / out["hyperdiffusion_automatic_c4"]["ms"]
+    del c
+    lib.pam_amd_modules_finalize()
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "hyperdiffusion"]:
+        print(json.dumps(hyperdiffusion_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "vt"]:
         print(json.dumps(vt_timing(dev)))
         sys.exit(0)
