@@ -57,6 +57,8 @@
 #include "modules/mean_state_acceleration.h"
 #include "modules/variance_transport.h"
 #include "modules/hyperdiffusion.h"
+#include "modules/radiation_aggregate.h"
+#include "modules/crm_feedback.h"
 #include "vertical_interp.h"
 #include "physics/micro/kessler_amd/Microphysics.h"
 #include "physics/sgs/none/SGS.h"
@@ -304,7 +306,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
-//          <output.bin | ->
+//          [--hyperdiff TAU] [--gcm-handoff RAD_NX RAD_NY PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
 // out_freq, vcoords [, crm_nz, zlen, idealized, apply_sponge, initData].  What runs, in the reference's order:
@@ -408,10 +410,19 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              the step's weight times crm_dt, so that it composes with --accelerate; modules::vt_compute_feedback at the
 //                              end of the GCM step.  PATH receives one JSON line per GCM step with var_start, var and feedback of every
 //                              quantity as flat (nz,nens) lists, printed with %.17g.  RATE = 0 changes nothing of the run.
+//   --gcm-handoff RAD_NX RAD_NY PATH   what the GCM takes back from the CRM (modules/radiation_aggregate.h, modules/crm_feedback.h):
+//                              modules::rad_aggregate_init at the start of every GCM step, modules::rad_aggregate after the last module
+//                              of every CRM step with the clock's weight (so it composes with --accelerate, --vt and --hyperdiff),
+//                              modules::compute_crm_feedback at the end of every GCM step (and of a run cut short by --steps).  The
+//                              aggregates (nz,rad_ny,rad_nx,nens) and the feedback's means and tendencies (nz,nens) go to PATH as JSON in
+//                              the format of --stats, every value printed with %.17g; nothing else of the run changes.  With --radiation
+//                              the two rad grids must be the same.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  bool vt = false, vt_u = false, hyperdiff = false;
+  bool vt = false, vt_u = false, hyperdiff = false, handoff = false;
   double hyperdiff_tau = 0;
+  int handoff_rad_nx = 0, handoff_rad_ny = 0;
+  std::string handoff_path;
   double tau = 0, bflx = 0, accel_factor = 0, accel_max_ttend = 5.0, vt_rate = 0, vt_limit = 0.05;
   int rad_nx = 0, rad_ny = 0;
   std::string stats, edges, rad_path, diag, vt_path;
@@ -424,6 +435,23 @@ static void stats_json_number(std::string &o, double v) {
   else if (std::isinf(v)) std::snprintf(t, sizeof(t), v > 0 ? "Infinity" : "-Infinity");
   else std::snprintf(t, sizeof(t), "%.17g", v);
   o += t;
+}
+// --gcm-handoff: a device array as nested JSON lists, the last dimension innermost
+static void handoff_json_array(std::string &o, const real *dev, std::vector<int> const &dims) {
+  size_t n = 1;
+  for (int d : dims) n *= d;
+  std::vector<real> h(n);
+  if (hipMemcpy(h.data(), dev, n * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess) endrun("memcpy");
+  std::vector<size_t> inner(dims.size(), 1);      // elements below one index of dimension d
+  for (int d = (int)dims.size() - 2; d >= 0; d--) inner[d] = inner[d + 1] * dims[d + 1];
+  for (size_t j = 0; j < n; j++) {
+    for (size_t d = 0; d < dims.size(); d++)
+      if (j % (inner[d] * dims[d]) == 0) o += "[";
+    stats_json_number(o, h[j]);
+    for (int d = (int)dims.size() - 1; d >= 0; d--)
+      if ((j + 1) % (inner[d] * dims[d]) == 0) o += "]";
+    if (j + 1 < n) o += ", ";
+  }
 }
 // --diag: one result set of pam::diagnostics::scan as JSON, scalars for the whole field (members = 0), lists per member
 static void diag_json(std::string &o, pam::diagnostics::FieldDiagnostics const &d) {
@@ -525,6 +553,14 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       coupler.set_option<real>("crm_accel_max_ttend", mods.accel_max_ttend);
     }
     if (mods.hyperdiff) modules::hyperdiffusion_init(coupler, mods.hyperdiff_tau);
+    std::string handoff_steps;
+    if (mods.handoff) {
+      if (mods.radiation && (mods.rad_nx != mods.handoff_rad_nx || mods.rad_ny != mods.handoff_rad_ny))
+        endrun("--radiation and --gcm-handoff must name the same rad grid");
+      coupler.set_option<int>("rad_nx", mods.handoff_rad_nx);
+      coupler.set_option<int>("rad_ny", mods.handoff_rad_ny);
+      coupler.run_module("crm_feedback_init", modules::crm_feedback_init);
+    }
     std::ofstream vt_out;
     if (mods.vt) {
       coupler.set_option<bool>("crm_vt_u", mods.vt_u);
@@ -579,6 +615,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         coupler.run_module("vt_init", modules::vt_init);
         vt_set_growth_rate(coupler, mods.vt_rate);
       }
+      if (mods.handoff) coupler.run_module("rad_aggregate_init", modules::rad_aggregate_init);
       while (!clock.done() && !stop) {
         const bool accel = clock.accelerating();
         if (accel) coupler.run_module("msa_diagnose", modules::msa_diagnose);
@@ -602,6 +639,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (accel && !cease) accel_steps++;
         if (mods.vt) coupler.run_module("vt_apply_forcing", [&](pam::PamCoupler &c) { modules::vt_apply_forcing(c, weight * dt_crm_phys); });
         if (stats) coupler.run_module("time_average_accumulate", [&](pam::PamCoupler &c) { modules::time_average_accumulate(c, stat_names, weight); });
+        if (mods.handoff) coupler.run_module("rad_aggregate", [&](pam::PamCoupler &c) { modules::rad_aggregate(c, weight); });
         if (mods.validate) dm.validate_all();
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         crm_steps++;
@@ -663,6 +701,29 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         vt_out << o << std::flush;
         if (!vt_out) endrun("cannot write the --vt file");
       }
+      if (mods.handoff) {                                                     // the GCM step's aggregates and feedback
+        coupler.run_module("compute_crm_feedback", modules::compute_crm_feedback);
+        handoff_steps += std::string(handoff_steps.empty() ? "" : ", ") + "{\"gcm_step\": " + std::to_string(step_gcm) + ", \"crm_steps\": " +
+                         std::to_string(crm_steps_gcm) + ", \"aggregates\": {";
+        bool first = true;
+        for (const char *n : {"rad_temperature", "rad_qv", "rad_qc", "rad_qi", "rad_cld"}) {
+          if (!dm.entry_exists(n)) continue;
+          handoff_steps += std::string(first ? "\"" : ", \"") + n + "\": ";
+          handoff_json_array(handoff_steps, dm.get<real const, 4>(n).data(), {crm_nz, mods.handoff_rad_ny, mods.handoff_rad_nx, nens});
+          first = false;
+        }
+        handoff_steps += "}, \"feedback\": {";
+        first = true;
+        for (const char *what : {"mean", "tend"})
+          for (const char *q : {"t", "qv", "qc", "qi", "u", "v"}) {
+            std::string n = std::string("crm_feedback_") + what + "_" + q;
+            if (!dm.entry_exists(n)) continue;
+            handoff_steps += std::string(first ? "\"" : ", \"") + what + "_" + q + "\": ";
+            handoff_json_array(handoff_steps, dm.get<real const, 2>(n).data(), {crm_nz, nens});
+            first = false;
+          }
+        handoff_steps += "}}";
+      }
       if (stats) {                                                            // the GCM step's profiles
         coupler.run_module("horizontal_average", [&](pam::PamCoupler &c) { modules::horizontal_average(c, stat_havg); });
         char t[96];
@@ -700,6 +761,18 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       if (!so) endrun("cannot open the --stats file");
       so << o;
       if (!so) endrun("cannot write the --stats file");
+    }
+    if (mods.handoff) {
+      std::string o = "{\"nens\": " + std::to_string(nens) + ", \"nz\": " + std::to_string(crm_nz) + ", \"rad_nx\": " +
+                      std::to_string(mods.handoff_rad_nx) + ", \"rad_ny\": " + std::to_string(mods.handoff_rad_ny) + ", \"crm_dt\": ";
+      stats_json_number(o, dt_crm_phys);
+      o += ", \"gcm_physics_dt\": ";
+      stats_json_number(o, dt_gcm);
+      o += ", \"gcm_steps\": [" + handoff_steps + "]}\n";
+      std::ofstream ho(mods.handoff_path);
+      if (!ho) endrun("cannot open the --gcm-handoff file");
+      ho << o;
+      if (!ho) endrun("cannot write the --gcm-handoff file");
     }
     if (!mods.edges.empty()) {
       pam::VerticalInterp<5> vert_interp;
@@ -818,9 +891,16 @@ int main(int argc, char **argv) {
       else if (o == "--vt-u") mods.vt_u = true;
       else if (o == "--vt-limit" && b + 1 < argc - 1) mods.vt_limit = std::atof(argv[++b]);
       else if (o == "--hyperdiff" && b + 1 < argc - 1) { mods.hyperdiff = true; mods.hyperdiff_tau = std::atof(argv[++b]); }
+      else if (o == "--gcm-handoff" && b + 3 < argc - 1) {
+        mods.handoff = true;
+        mods.handoff_rad_nx = std::atoi(argv[++b]);
+        mods.handoff_rad_ny = std::atoi(argv[++b]);
+        mods.handoff_path = argv[++b];
+      }
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] <output.bin | ->");
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] "
+               "[--gcm-handoff RAD_NX RAD_NY PATH] <output.bin | ->");
     }
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }

@@ -505,6 +505,47 @@ int pam_amd_hyperdiffusion(int nens, int nx, int ny, int nz, int num_fields, dou
                            double dt, double tau, void *stream);
 int pam_amd_hyperdiffusion_debug_path(int path);
 
+/* The CRM-to-GCM handoff: what a host model takes from the CRM at the end of a GCM step.  pam_amd_radiation_aggregate builds the inputs of
+ * the external radiation calculation whose result the forced Radiation plug-in applies (pam_amd_radiation_forced), on the same rad_ny x
+ * rad_nx groups of CRM columns; pam_amd_crm_feedback is the converse of pam_amd_gcm_forcing_compute.  Neither is part of the reference
+ * tree (E3SM-MMF's driver sums the first with one atomicAdd per cell and field, in no fixed order); the contract is this project's
+ *  and is restated in numpy in tests/rad_ref.py, which the kernels match bit for bit.
+ * Fields are (nz,ny,nx,nens), members fastest.  gx = nx / rad_nx, gy = ny / rad_ny, r = 1.0 / (gx gy).
+ *   fields[6]   HOST array of DEVICE pointers: temp, rho_d (density_dry), rho_v (water_vapor), rho_c, rho_i, cldfrac.  rho_c, rho_i and
+ *               cldfrac may each be NULL (Kessler has no ice; a run without SHOC has no cloud fraction).  An absent species contributes
+ *               nothing (no + 0.0), its aggregate is neither read nor written, and its rad entry must be NULL as well.
+ *   rad[5]      HOST array of DEVICE pointers (nz,rad_ny,rad_nx,nens), in/out: rad_temperature, rad_qv, rad_qc, rad_qi, rad_cld
+ * Per-cell values, d = rho_d + rho_v (rounded), every operation rounded, no fma: T = temp; qv = rho_v / d, qc = rho_c / d, qi = rho_i / d
+ * as IEEE divisions (the mixing ratios of gcm_forcing.h:108-110; d == 0 is not special-cased); cld = cldfrac where given, otherwise 1.0
+ * where rho_c + rho_i > 0 (the sum rounded, an absent species skipped) and 0.0 where it is not: a NaN gives 0.0.
+ * Group mean A(v)(k,jr,ir,e): the cell at local row jj and local column ii of its group has g = jj gx + ii and belongs to slot g % 16; a
+ * slot adds v * r (the product rounded first) over its cells in ascending g from +0.0; the 16 slot sums are added in ascending slot order
+ * from +0.0, an empty slot adding +0.0 (a group of one cell holding -0.0 gives +0.0).  At rad_nx == rad_ny == 1 this is the level mean M
+ * of mean-state acceleration above.
+ * rad_x[o] = rad_x[o] + A(x) * factor, the product rounded, then the add, once per output element by the one thread that owns it.  No
+ * floating-point atomics and no scratch array: the same bits from run to run, for any split of the members over calls and whichever
+ * threads hold the slots.  One launch on `stream`, no synchronisation; every element offset is 64 bits wide.
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: nens / nx / ny / nz < 1 (ny nx beyond 2^31 - 1, nz beyond
+ * 65535); rad_nx, rad_ny not >= 1 or not divisors of nx, ny; a NULL table; a NULL among temp, rho_d, rho_v or among rad[0], rad[1],
+ * rad[4]; a rad[2] or rad[3] whose NULL-ness differs from its species'; a factor that is not finite; an output that overlaps an input or
+ * another output.
+ * pam_amd_radiation_aggregate_debug_mapping is a test switch like pam_amd_hyperdiffusion_debug_path: 0 = automatic (16 slot threads per
+ * group and member from 64 cells per group on, one thread per group and member below), 1 and 2 force the one and the other. */
+int pam_amd_radiation_aggregate(int nens, int nx, int ny, int nz, int rad_nx, int rad_ny, const double *const *fields, double *const *rad,
+                                double factor, void *stream);
+int pam_amd_radiation_aggregate_debug_mapping(int mapping);
+
+/*   fields[7]   HOST array of DEVICE pointers (nz,ny,nx,nens): temp, rho_d, rho_v, rho_c or NULL, rho_i or NULL, uvel, vvel
+ *   gcm[7]      HOST array of DEVICE pointers (nz,nens): gcm_temp, gcm_density_dry, gcm_water_vapor, gcm_cloud_water, gcm_cloud_ice,
+ *               gcm_uvel, gcm_vvel
+ *   mean[6], tend[6]   HOST arrays of DEVICE pointers (nz,nens): t, qv, qc, qi, u, v
+ * mean_x = M(x) over the per-cell values above (uvel and vvel as they are); x_gcm is gcm_temp, gcm_uvel, gcm_vvel or gcm_rho_x /
+ * (gcm_density_dry + gcm_water_vapor); tend_x = (mean_x - x_gcm) / gcm_dt, one true division per (k,e).  The entries of an absent species
+ * (gcm, mean, tend) are neither read nor written and may be NULL.  ONE read of the fields, one launch, no scratch, no atomics.
+ * PAM_AMD_EINVAL as above; also gcm_dt not finite or not positive, and a NULL entry of a species that is present. */
+int pam_amd_crm_feedback(int nens, int nx, int ny, int nz, const double *const *fields, const double *const *gcm, double gcm_dt,
+                         double *const *mean, double *const *tend, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,9 @@ MODULE_SYMBOLS = {
                             + [C.POINTER(C.c_void_p)] * 3 + [C.c_void_p]),
     "pam_amd_hyperdiffusion": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_void_p), C.POINTER(C.c_ubyte), C.c_double, C.c_double, C.c_void_p]),
     "pam_amd_hyperdiffusion_debug_path": (C.c_int, [C.c_int]),
+    "pam_amd_radiation_aggregate": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_void_p)] * 2 + [C.c_double, C.c_void_p]),
+    "pam_amd_radiation_aggregate_debug_mapping": (C.c_int, [C.c_int]),
+    "pam_amd_crm_feedback": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_void_p)] * 2 + [C.c_double] + [C.POINTER(C.c_void_p)] * 2 + [C.c_void_p]),
 }
 
 

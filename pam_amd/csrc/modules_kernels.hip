@@ -3358,3 +3358,228 @@ extern "C" int pam_amd_hyperdiffusion(int nens, int nx, int ny, int nz, int num_
   }
   return PAM_AMD_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The CRM-to-GCM handoff: the radiation inputs averaged over rad_ny x rad_nx groups of CRM columns (E3SM-MMF's crm_rad_temperature,
+// _qv, _qc, _qi, _cld, which its driver builds with one atomicAdd per cell and field) and the CRM feedback tendencies
+// (CRM level mean - GCM value) / gcm_dt that close the loop compute_gcm_forcing_tendencies opens.  Neither is in the reference tree; the
+// contract is in include/pam_amd_modules.h and DESIGN.md section 8, its arithmetic in rad_device.h.  A group mean is mean-state
+// acceleration's level mean over the group's cells, so the bits do not depend on which threads hold the 16 slots:
+//   block slots (a group of 64 cells or more; the feedback's whole level)   a workgroup = (level, group, block of up to 64 members) x 16
+//                         slots through slot_reduce, as msa_mean_kernel: every step of a walk is one coalesced row per field.
+//   thread slots (smaller groups, down to the single cell)   a workgroup = (level, 256 / members groups, block of up to 64 members); a
+//                         thread walks the 16 slots of its own group one after the other and folds them in registers: no LDS, no idle
+//                         slot, and at one cell per group a streaming transform plus accumulate.
+// One thread owns an output element and adds to it once.  No scratch, no floating-point atomics; every element offset is 64 bits wide.
+#include "rad_device.h"
+
+namespace {
+namespace rd = pama::rad;
+struct RadFields { const double *p[rd::NF]; };
+struct RadOut { double *p[rd::NA]; };
+struct FbGcm { const double *p[rd::NG]; };
+struct FbOut { double *p[rd::NB]; };
+constexpr int RAD_THREADS = 256;           // the thread-slots workgroup
+constexpr int RAD_BLOCK_CELLS = 64;        // groups of this many cells or more take the block-slots kernel
+enum { RAD_AUTO, RAD_BLOCK_SLOTS, RAD_THREAD_SLOTS };
+
+// the field pointers of one walker at the first cell of group (jr, ir) of level k, member e
+__device__ __forceinline__ void rad_group_origin(const RadFields &F, int nens, int nx, int ny, int gx, int gy, int k, int jr, int ir, int e,
+                                                 const double *(&f)[rd::NF]) {
+  const long long base = (((long long)k * ny + (long long)jr * gy) * nx + (long long)ir * gx) * nens + e;
+#pragma unroll
+  for (int i = 0; i < rd::NF; i++) f[i] = F.p[i] ? F.p[i] + base : nullptr;
+}
+
+// the group means of K's quantities in every thread of the member, 16 slot threads per (group, member); red: 3 * 16 * 64 doubles.
+// Two rounds of three through slot_reduce, as vt_stats_kernel: 24 KB of LDS
+template <class K>
+__device__ __forceinline__ void rad_block_means(const RadFields &F, int nens, int nx, int ny, int gx, int gy, int k, int jr, int ir, int e,
+                                                bool ok, double (&tot)[K::NQ], double *red) {
+  static_assert(K::NQ > 3 && K::NQ <= 6, "two rounds of three");
+  const int slot = threadIdx.y;
+  const double *f[rd::NF];
+  rad_group_origin(F, nens, nx, ny, gx, gy, k, jr, ir, e, f);
+#pragma unroll
+  for (int q = 0; q < K::NQ; q++) tot[q] = 0.0;
+  if (ok) rd::slot_walk<K, 4>(f, (long long)nens, (long long)nx * nens, gx, gx * gy, slot, rd::Cursor{slot / gx, slot % gx}, rd::r_cells(gx, gy), tot);
+  double a[3] = {tot[0], tot[1], tot[2]}, b[3] = {tot[3], tot[4], K::NQ > 5 ? tot[K::NQ - 1] : 0.0};
+  slot_reduce<3>(a, red);
+  slot_reduce<3>(b, red);
+#pragma unroll
+  for (int q = 0; q < 3; q++) { tot[q] = a[q]; if (q + 3 < K::NQ) tot[q + 3] = b[q]; }
+}
+
+__device__ __forceinline__ void rad_accumulate(const RadOut &out, int nens, int rad_nx, int rad_ny, int k, int jr, int ir, int e,
+                                               const double (&tot)[rd::NA], double factor) {
+  const long long o = (((long long)k * rad_ny + jr) * rad_nx + ir) * nens + e;
+#pragma unroll
+  for (int q = 0; q < rd::NA; q++)
+    if (out.p[q]) out.p[q][o] = rd::accumulate(out.p[q][o], tot[q], factor);
+}
+
+// grid (groups of a level x member blocks, levels), block (members, 16 slots)
+__global__ void __launch_bounds__(64 * MOD_NS) rad_aggregate_block_kernel(int nens, int nx, int ny, int rad_nx, int rad_ny, int nblk, RadFields F,
+                                                                          RadOut out, double factor) {
+  __shared__ double red[3 * MOD_NS * 64];
+  const int grp = (int)blockIdx.x / nblk, e0 = ((int)blockIdx.x % nblk) * (int)blockDim.x + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1, k = (int)blockIdx.y, jr = grp / rad_nx, ir = grp % rad_nx;
+  double tot[rd::NA];
+  rad_block_means<rd::Aggregate>(F, nens, nx, ny, nx / rad_nx, ny / rad_ny, k, jr, ir, e, ok, tot, red);
+  if (threadIdx.y != 0 || !ok) return;
+  rad_accumulate(out, nens, rad_nx, rad_ny, k, jr, ir, e, tot, factor);
+}
+
+// grid (chunks of blockDim.y groups of a level x member blocks, levels), block (members, groups): a thread owns one (group, member)
+__global__ void __launch_bounds__(RAD_THREADS) rad_aggregate_thread_kernel(int nens, int nx, int ny, int rad_nx, int rad_ny, int nblk, RadFields F,
+                                                                           RadOut out, double factor) {
+  const int grp = ((int)blockIdx.x / nblk) * (int)blockDim.y + (int)threadIdx.y;
+  const int e = ((int)blockIdx.x % nblk) * (int)blockDim.x + (int)threadIdx.x;
+  if (e >= nens || grp >= rad_nx * rad_ny) return;
+  const int k = (int)blockIdx.y, jr = grp / rad_nx, ir = grp % rad_nx, gx = nx / rad_nx, gy = ny / rad_ny;
+  const double *f[rd::NF];
+  rad_group_origin(F, nens, nx, ny, gx, gy, k, jr, ir, e, f);
+  double tot[rd::NA] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  rd::slots_walk<rd::Aggregate>(f, (long long)nens, (long long)nx * nens, gx, gx * gy, 0, rd::NS, rd::r_cells(gx, gy), tot);
+  rad_accumulate(out, nens, rad_nx, rad_ny, k, jr, ir, e, tot, factor);
+}
+
+// ONE read of up to seven fields -> the level means of temp, qv, qc, qi, uvel, vvel and their distance from the GCM's values over
+// gcm_dt.  grid (member blocks, levels), block (members, 16 slots)
+__global__ void __launch_bounds__(64 * MOD_NS) crm_feedback_kernel(int nens, int nx, int ny, RadFields F, FbGcm gcm, double gcm_dt, FbOut mean,
+                                                                   FbOut tend) {
+  __shared__ double red[3 * MOD_NS * 64];
+  const int e0 = (int)blockIdx.x * (int)blockDim.x + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1, k = (int)blockIdx.y;
+  double tot[rd::NB];
+  rad_block_means<rd::Feedback>(F, nens, nx, ny, nx, ny, k, 0, 0, e, ok, tot, red);
+  if (threadIdx.y != 0 || !ok) return;
+  const long long t = (long long)k * nens + e;
+  double g[rd::NG];
+#pragma unroll
+  for (int i = 0; i < rd::NG; i++) g[i] = gcm.p[i] ? gcm.p[i][t] : 0.0;
+#pragma unroll
+  for (int q = 0; q < rd::NB; q++) {
+    if (!mean.p[q]) continue;
+    mean.p[q][t] = tot[q];
+    tend.p[q][t] = rd::feedback_tendency(tot[q], rd::gcm_value(g, q), gcm_dt);
+  }
+}
+
+int rad_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
+
+// [p, p + n doubles) of every array of a call, to refuse an output that shares memory with an input or with another output
+struct RadSpan { const double *p; long long n; bool out; };
+bool rad_spans_overlap(const std::vector<RadSpan> &spans) {
+  for (size_t i = 0; i < spans.size(); i++)
+    for (size_t j = i + 1; j < spans.size(); j++) {
+      if (!spans[i].out && !spans[j].out) continue;
+      const uintptr_t a = (uintptr_t)spans[i].p, b = (uintptr_t)spans[j].p;
+      if (a < b + (uintptr_t)spans[j].n * sizeof(double) && b < a + (uintptr_t)spans[i].n * sizeof(double)) return true;
+    }
+  return false;
+}
+
+int rad_check_sizes(const char *who, int nens, int nx, int ny, int nz) {
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return rad_error(who, "nens, nx, ny and nz must be >= 1");
+  if ((long long)nx * ny > 0x7fffffffLL) return rad_error(who, "ny x nx exceeds 2^31 - 1 columns");
+  if (nz > 65535) return rad_error(who, "nz exceeds the grid (65535 levels)");
+  return PAM_AMD_OK;
+}
+
+int g_rad_mapping = RAD_AUTO;   // pam_amd_radiation_aggregate_debug_mapping: tests run both mappings at small shapes
+}  // namespace
+
+extern "C" int pam_amd_radiation_aggregate_debug_mapping(int mapping) {
+  if (mapping < RAD_AUTO || mapping > RAD_THREAD_SLOTS)
+    return rad_error("radiation_aggregate", "debug mapping must be 0 (automatic), 1 (block slots) or 2 (thread slots)");
+  g_rad_mapping = mapping;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_radiation_aggregate(int nens, int nx, int ny, int nz, int rad_nx, int rad_ny, const double *const *fields,
+                                           double *const *rad, double factor, void *stream) {
+  const char *who = "radiation_aggregate";
+  if (int rc = rad_check_sizes(who, nens, nx, ny, nz)) return rc;
+  if (rad_nx < 1 || rad_ny < 1 || nx % rad_nx != 0 || ny % rad_ny != 0) return rad_error(who, "rad_nx and rad_ny must be >= 1 and divide nx and ny");
+  if (!fields || !rad) return rad_error(who, "null pointer table");
+  if (!fields[0] || !fields[1] || !fields[2]) return rad_error(who, "null temp, rho_d or rho_v pointer");
+  if (!rad[rd::A_T] || !rad[rd::A_QV] || !rad[rd::A_CLD]) return rad_error(who, "null rad_temperature, rad_qv or rad_cld pointer");
+  if ((rad[rd::A_QC] == nullptr) != (fields[3] == nullptr)) return rad_error(who, "rad_qc must be given exactly when rho_c is");
+  if ((rad[rd::A_QI] == nullptr) != (fields[4] == nullptr)) return rad_error(who, "rad_qi must be given exactly when rho_i is");
+  if (!std::isfinite(factor)) return rad_error(who, "factor must be finite");
+  const long long cells = (long long)nz * ny * nx * nens, elems = (long long)nz * rad_ny * rad_nx * nens;
+  std::vector<RadSpan> spans;
+  for (int i = 0; i < 6; i++)
+    if (fields[i]) spans.push_back({fields[i], cells, false});
+  for (int q = 0; q < rd::NA; q++)
+    if (rad[q]) spans.push_back({rad[q], elems, true});
+  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
+  const int gx = nx / rad_nx, gy = ny / rad_ny, ME = nens < 64 ? nens : 64, nblk = (nens + ME - 1) / ME;
+  const long long ngroups = (long long)rad_nx * rad_ny;
+  const bool block_slots = g_rad_mapping == RAD_AUTO ? (long long)gx * gy >= RAD_BLOCK_CELLS : g_rad_mapping == RAD_BLOCK_SLOTS;
+  const int GB = RAD_THREADS / ME;
+  const long long blocks = (block_slots ? ngroups : (ngroups + GB - 1) / GB) * nblk;
+  if (blocks > 0x7fffffffLL) return rad_error(who, "rad_ny x rad_nx x nens exceeds the grid");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  RadFields F;
+  RadOut O;
+  for (int i = 0; i < rd::NF; i++) F.p[i] = i < 6 ? fields[i] : nullptr;
+  for (int q = 0; q < rd::NA; q++) O.p[q] = rad[q];
+  const dim3 grid((unsigned)blocks, (unsigned)nz);
+  if (block_slots)
+    hipLaunchKernelGGL(rad_aggregate_block_kernel, grid, dim3((unsigned)ME, (unsigned)MOD_NS), 0, (hipStream_t)stream, nens, nx, ny, rad_nx, rad_ny,
+                       nblk, F, O, factor);
+  else
+    hipLaunchKernelGGL(rad_aggregate_thread_kernel, grid, dim3((unsigned)ME, (unsigned)GB), 0, (hipStream_t)stream, nens, nx, ny, rad_nx, rad_ny,
+                       nblk, F, O, factor);
+  return stats_launch_check(who);
+}
+
+extern "C" int pam_amd_crm_feedback(int nens, int nx, int ny, int nz, const double *const *fields, const double *const *gcm, double gcm_dt,
+                                    double *const *mean, double *const *tend, void *stream) {
+  const char *who = "crm_feedback";
+  if (int rc = rad_check_sizes(who, nens, nx, ny, nz)) return rc;
+  if (!fields || !gcm || !mean || !tend) return rad_error(who, "null pointer table");
+  if (!fields[0] || !fields[1] || !fields[2] || !fields[5] || !fields[6]) return rad_error(who, "null temp, rho_d, rho_v, uvel or vvel pointer");
+  if (!(gcm_dt > 0) || !std::isfinite(gcm_dt)) return rad_error(who, "gcm_dt must be finite and positive");
+  // the field, the gcm entry and the quantity of the two species that may be absent
+  const int species[2][3] = {{3, rd::G_RHOC, rd::B_QC}, {4, rd::G_RHOI, rd::B_QI}};
+  for (int i = 0; i < rd::NG; i++)
+    if (i != rd::G_RHOC && i != rd::G_RHOI && !gcm[i]) return rad_error(who, "null pointer in the gcm table");
+  for (int q = 0; q < rd::NB; q++)
+    if (q != rd::B_QC && q != rd::B_QI && (!mean[q] || !tend[q])) return rad_error(who, "null pointer in the mean or tend table");
+  for (auto &s : species)
+    if (fields[s[0]] && (!gcm[s[1]] || !mean[s[2]] || !tend[s[2]])) return rad_error(who, "a species that is present needs its gcm, mean and tend entries");
+  const long long cells = (long long)nz * ny * nx * nens, cols = (long long)nz * nens;
+  const bool has[2] = {fields[3] != nullptr, fields[4] != nullptr};
+  std::vector<RadSpan> spans;
+  for (int i = 0; i < 7; i++)
+    if (fields[i]) spans.push_back({fields[i], cells, false});
+  for (int i = 0; i < rd::NG; i++)
+    if (gcm[i] && !((i == rd::G_RHOC && !has[0]) || (i == rd::G_RHOI && !has[1]))) spans.push_back({gcm[i], cols, false});
+  for (int q = 0; q < rd::NB; q++) {
+    if ((q == rd::B_QC && !has[0]) || (q == rd::B_QI && !has[1])) continue;
+    spans.push_back({mean[q], cols, true});
+    spans.push_back({tend[q], cols, true});
+  }
+  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  RadFields F;
+  FbGcm G;
+  FbOut M, T;
+  for (int i = 0; i < rd::NF; i++) F.p[i] = nullptr;
+  for (int i = 0; i < 5; i++) F.p[i] = fields[i];
+  F.p[rd::F_U] = fields[5];
+  F.p[rd::F_V] = fields[6];
+  for (int i = 0; i < rd::NG; i++) G.p[i] = gcm[i];
+  for (int q = 0; q < rd::NB; q++) { M.p[q] = mean[q]; T.p[q] = tend[q]; }
+  for (int j = 0; j < 2; j++)
+    if (!has[j]) { G.p[species[j][1]] = nullptr; M.p[species[j][2]] = nullptr; T.p[species[j][2]] = nullptr; }
+  dim3 grid, block;
+  msa_launch_shape(nens, nz, grid, block);
+  hipLaunchKernelGGL(crm_feedback_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, ny, F, G, gcm_dt, M, T);
+  return stats_launch_check(who);
+}

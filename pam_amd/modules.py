@@ -652,3 +652,141 @@ def hyperdiffusion(coupler, dt=None):
         check(lib.pam_amd_hyperdiffusion(coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), len(tens), _ptr_table(tens),
                                          (C.c_ubyte * len(tens))(*positive), dt, float(coupler.get_option("crm_hyperdiff_timescale")),
                                          torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+# ---- the CRM-to-GCM handoff: the radiation inputs on the rad column groups (E3SM-MMF's crm_rad_* arrays) and the CRM feedback tendencies.
+# Not part of the reference tree: the contract is this project's (include/pam_amd_modules.h; numpy restatement:
+# tests/rad_ref.py)
+RAD_AGGREGATES = ("rad_temperature", "rad_qv", "rad_qc", "rad_qi", "rad_cld")
+CRM_FEEDBACK_QUANTITIES = ("t", "qv", "qc", "qi", "u", "v")
+CRM_FEEDBACK_GCM = ("gcm_temp", "gcm_density_dry", "gcm_water_vapor", "gcm_cloud_water", "gcm_cloud_ice", "gcm_uvel", "gcm_vvel")
+
+
+def _handoff_condensate(coupler, who):
+    from .coupler import endrun
+    micro = coupler.get_option("micro") if coupler.option_exists("micro") else "none"
+    if micro not in MSA_CONDENSATE:
+        endrun("ERROR: %s only knows the kessler, p3 and none microphysics" % who)
+    return MSA_CONDENSATE[micro]
+
+
+def _rad_aggregate_names(coupler):
+    """-> the sizes of the forced radiation plug-in, (cloud, ice) and the names of the aggregates this microphysics has"""
+    from .coupler import endrun
+    from .physics import _forced_sizes
+    if not (coupler.option_exists("rad_nx") and coupler.option_exists("rad_ny")):
+        endrun("ERROR: rad_aggregate: options rad_nx and rad_ny are not set")
+    sizes = _forced_sizes(coupler)
+    cloud, ice = _handoff_condensate(coupler, "rad_aggregate")
+    names = [n for n in RAD_AGGREGATES if not (n == "rad_qc" and cloud is None) and not (n == "rad_qi" and ice is None)]
+    return sizes, cloud, ice, names
+
+
+def rad_aggregate_init(coupler):
+    """First in every GCM step: registers "rad_temperature", "rad_qv", "rad_qc", "rad_qi" and "rad_cld" (nz,rad_ny,rad_nx,nens) on first
+    use -- "rad_qc" / "rad_qi" only where the microphysics (option "micro") has the species -- and zeroes them.  Options "rad_nx",
+    "rad_ny": >= 1 and divisors of the CRM grid, as the forced Radiation plug-in reads them."""
+    from .coupler import endrun
+    (nens, nz, ny, nx, rad_ny, rad_nx), _, _, names = _rad_aggregate_names(coupler)
+    dm = coupler.get_data_manager_device_readwrite()
+    shape = [nz, rad_ny, rad_nx, nens]
+    for n in names:
+        if dm.entry_exists(n) and dm.get_shape(n) != shape:
+            endrun("ERROR: rad_aggregate: %s exists with a shape other than (nz,rad_ny,rad_nx,nens)" % n)
+    for n in names:
+        if not dm.entry_exists(n):
+            dm.register_and_allocate(n, "radiation input on the rad column groups, averaged over the GCM step", tuple(shape),
+                                     ("z", "rad_y", "rad_x", "nens"))
+    rad = [dm.get(n) for n in names]
+    with torch.cuda.device(coupler.device):
+        check(capi.load().pam_amd_time_average_zero(len(rad), _sizes([shape] * len(rad)), _ptr_table(rad),
+                                                    torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+def rad_aggregate(coupler, weight=1):
+    """After the last module of every CRM step: rad_x += A(x) * (crm_dt / gcm_physics_dt * weight) with A the mean over the rad column
+    group of temp, rho_v / (rho_d + rho_v), rho_c / (..), rho_i / (..) and the cloud fraction -- the entry "cldfrac" where the
+    DataManager has it, otherwise 1 where a cell's condensate is positive and 0 where it is not.  The factor is
+    time_average_accumulate's, so weight takes MsaClock's step weight.  Every misuse raises before the launch."""
+    import math
+    from .coupler import endrun
+    (nens, nz, ny, nx, rad_ny, rad_nx), cloud, ice, names = _rad_aggregate_names(coupler)
+    crm_dt = float(coupler.get_option("crm_dt"))
+    gcm_dt = float(coupler.get_option("gcm_physics_dt"))
+    if not gcm_dt > 0:
+        endrun("ERROR: rad_aggregate: gcm_physics_dt must be positive")
+    factor = crm_dt / gcm_dt * float(weight)
+    if not math.isfinite(factor):
+        endrun("ERROR: rad_aggregate: crm_dt / gcm_physics_dt x weight is not finite")
+    dm = coupler.get_data_manager_device_readwrite()
+    for n in names:
+        if not dm.entry_exists(n):
+            endrun("ERROR: %s does not exist: call rad_aggregate_init first" % n)
+        if dm.get_shape(n) != [nz, rad_ny, rad_nx, nens]:
+            endrun("ERROR: rad_aggregate: %s is %s, not (nz,rad_ny,rad_nx,nens) = %s" % (n, dm.get_shape(n), [nz, rad_ny, rad_nx, nens]))
+    has_cldfrac = dm.entry_exists("cldfrac")
+    if has_cldfrac and dm.get_shape("cldfrac") != [nz, ny, nx, nens]:
+        endrun("ERROR: rad_aggregate: cldfrac is %s, not (nz,ny,nx,nens)" % dm.get_shape("cldfrac"))
+    fields = [dm.get("temp", readonly=True), dm.get("density_dry", readonly=True), dm.get("water_vapor", readonly=True),
+              dm.get(cloud, readonly=True) if cloud else None, dm.get(ice, readonly=True) if ice else None,
+              dm.get("cldfrac", readonly=True) if has_cldfrac else None]
+    rad = [dm.get(n) if n in names else None for n in RAD_AGGREGATES]
+    with torch.cuda.device(coupler.device):
+        check(capi.load().pam_amd_radiation_aggregate(nens, nx, ny, nz, rad_nx, rad_ny, _msa_table(fields), _msa_table(rad), factor,
+                                                      torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+def _crm_feedback_quantities(coupler):
+    cloud, ice = _handoff_condensate(coupler, "crm_feedback")
+    return cloud, ice, [q for q in CRM_FEEDBACK_QUANTITIES if not (q == "qc" and cloud is None) and not (q == "qi" and ice is None)]
+
+
+def crm_feedback_init(coupler):
+    """Registers "crm_feedback_mean_{t,qv,qc,qi,u,v}" and "crm_feedback_tend_{t,qv,qc,qi,u,v}" (nz,nens) on first use; qc and qi only
+    where the microphysics (option "micro") has the species."""
+    from .coupler import endrun
+    nz, nens = coupler.get_nz(), coupler.get_nens()
+    if min(nz, nens) < 1:
+        endrun("ERROR: crm_feedback: the coupler state is not allocated")
+    _, _, quantities = _crm_feedback_quantities(coupler)
+    dm = coupler.get_data_manager_device_readwrite()
+    names = ["crm_feedback_%s_%s" % (what, q) for q in quantities for what in ("mean", "tend")]
+    for n in names:
+        if dm.entry_exists(n) and dm.get_shape(n) != [nz, nens]:
+            endrun("ERROR: crm_feedback: %s exists with a shape other than (nz,nens)" % n)
+    for n in names:
+        if not dm.entry_exists(n):
+            dm.register_and_allocate(n, "CRM level mean, and its distance from the GCM's value over the GCM step", (nz, nens), ("z", "nens"))
+
+
+def compute_crm_feedback(coupler):
+    """At the end of a GCM step: "crm_feedback_mean_x" = the level mean of temp, rho_v / (rho_d + rho_v), rho_c / (..), rho_i / (..), uvel,
+    vvel; "crm_feedback_tend_x" = (mean_x - the GCM's value from the "gcm_*" entries) / gcm_physics_dt: the converse of
+    compute_gcm_forcing_tendencies.  One read of the fields, one launch."""
+    import math
+    from .coupler import endrun
+    dm = coupler.get_data_manager_device_readwrite()
+    if not dm.entry_exists("crm_feedback_tend_t"):
+        endrun("ERROR: crm_feedback: call crm_feedback_init first")
+    cloud, ice, quantities = _crm_feedback_quantities(coupler)
+    gcm_dt = float(coupler.get_option("gcm_physics_dt"))
+    if not (gcm_dt > 0 and math.isfinite(gcm_dt)):
+        endrun("ERROR: crm_feedback: gcm_physics_dt must be finite and positive")
+    nz, nens = coupler.get_nz(), coupler.get_nens()
+    for q in quantities:
+        for what in ("mean", "tend"):
+            n = "crm_feedback_%s_%s" % (what, q)
+            if not dm.entry_exists(n):
+                endrun("ERROR: crm_feedback: %s does not exist: the microphysics changed since crm_feedback_init" % n)
+            if dm.get_shape(n) != [nz, nens]:
+                endrun("ERROR: crm_feedback: %s is %s, not (nz,nens)" % (n, dm.get_shape(n)))
+    fields = [dm.get("temp", readonly=True), dm.get("density_dry", readonly=True), dm.get("water_vapor", readonly=True),
+              dm.get(cloud, readonly=True) if cloud else None, dm.get(ice, readonly=True) if ice else None,
+              dm.get("uvel", readonly=True), dm.get("vvel", readonly=True)]
+    gcm = [None if (n == "gcm_cloud_water" and cloud is None) or (n == "gcm_cloud_ice" and ice is None) else dm.get(n, readonly=True)
+           for n in CRM_FEEDBACK_GCM]
+    mean = [dm.get("crm_feedback_mean_" + q) if q in quantities else None for q in CRM_FEEDBACK_QUANTITIES]
+    tend = [dm.get("crm_feedback_tend_" + q) if q in quantities else None for q in CRM_FEEDBACK_QUANTITIES]
+    with torch.cuda.device(coupler.device):
+        check(capi.load().pam_amd_crm_feedback(nens, coupler.get_nx(), coupler.get_ny(), nz, _msa_table(fields), _msa_table(gcm), gcm_dt,
+                                               _msa_table(mean), _msa_table(tend), torch.cuda.current_stream(coupler.device).cuda_stream))

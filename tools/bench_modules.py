@@ -12,6 +12,8 @@ Run on the GPU box:  python tools/bench_modules.py            (--only vertical_i
 time_average_accumulate of the same run;
 --only hyperdiffusion: the horizontal hyperdiffusion on its automatic and on each forced path at the C2 grid and at C4's 32x1x60 grid
 with 8192 members, beside msa_apply and time_average_accumulate of the same run;
+--only handoff: the radiation column aggregates at the C2 grid (rad grids 1x1, 8x8, 32x32) and at C4's 32x1x60 grid with 8192 members,
+and the CRM feedback, beside msa_diagnose, time_average_accumulate and radiation_forced of the same run;
 --only msa: mean-state acceleration's diagnose, tendencies and apply (with and without the winds), beside horizontal_average and
 time_average_accumulate of the same run)"""
 import json
@@ -927,8 +929,122 @@ def hyperdiffusion_timing(dev, warmup=3, n=11):
     return out
 
 
+def handoff_timing(dev, warmup=3, n=11):
+    """The CRM-to-GCM handoff on the P3 field set (cloud water and ice present, no cldfrac): pam_amd_radiation_aggregate at the C2 grid
+    for the rad grids 1x1 (16 slot threads per level and member), 8x8 and 32x32 (one thread per group and member; 32x32 is the streaming
+    transform), each also on the mapping the size does not choose, and at C4's 32x1x60 grid with 8192 members for the rad grids 1x1 and
+    8x1; pam_amd_crm_feedback at C2.  3 warm-up calls and the median of 11 event-timed calls each.  Algorithmic bytes: 8 B per cell and
+    input field read (five for the aggregate, seven for the feedback) plus 16 B per rad element and output (five), and for the feedback
+    8 B per gcm entry read (seven) and 8 B per mean and tend written (twelve) per (level, member).  The yardsticks of the same run:
+    msa_diagnose (one read of six fields on the block-slots launch shape) for the whole-level aggregate and the feedback;
+    time_average_accumulate on eight fields and radiation_forced at the 32x32 rad grid for the one-cell-group aggregate."""
+    import ctypes as C
+    from pam_amd import PamCoupler, capi, modules
+    from pam_amd import idealized as idz
+    from pam_amd.capi import check
+    lib = capi.load()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    def row(t, nbytes):
+        return {"ms": t[0], "min_ms": t[1], "max_ms": t[2], "bytes": nbytes, "GBps": nbytes / t[0] / 1e6,
+                "hbm_frac": nbytes / t[0] / 1e6 / bench.HBM_PEAK_GBS}
+
+    def coupler(nens, nx, ny, nz):
+        c = PamCoupler(dev)
+        c.set_option("crm_dt", 20.0)
+        c.set_option("gcm_physics_dt", 900.0)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+        for t in ("water_vapor", "cloud_water", "ice"):
+            c.add_tracer(t, "", True, True)
+        c.set_option("micro", "p3")
+        dm = c.get_data_manager_device_readwrite()
+        gen = torch.Generator(device=dev).manual_seed(0)
+        for name in ["density_dry", "uvel", "vvel", "wvel", "temp"] + c.get_tracer_names() + list(modules.CRM_FEEDBACK_GCM):
+            t = dm.get(name)
+            t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) + 0.5)
+        return c
+
+    def aggregates(c, label, grids, out):
+        nens, nx, ny, nz = c.get_nens(), c.get_nx(), c.get_ny(), c.get_nz()
+        cells = nens * nx * ny * nz
+        dm = c.get_data_manager_device_readwrite()
+        fields = [dm.get(name, readonly=True) for name in ("temp", "density_dry", "water_vapor", "cloud_water", "ice")] + [None]
+        F = modules._msa_table(fields)
+        for (gy, gx), mappings in grids:
+            rad = [torch.zeros((nz, gy, gx, nens), dtype=torch.float64, device=dev) for _ in range(5)]
+            R = modules._msa_table(rad)
+            nbytes = 5 * cells * 8.0 + 5 * rad[0].numel() * 16.0
+            for mapping, tag in mappings:
+                check(lib.pam_amd_radiation_aggregate_debug_mapping(mapping))
+                try:
+                    out["radiation_aggregate_rad%dx%d%s%s" % (gy, gx, tag, label)] = row(timed(lambda: check(lib.pam_amd_radiation_aggregate(
+                        nens, nx, ny, nz, gx, gy, F, R, 20.0 / 900.0, stream))), nbytes)
+                finally:
+                    check(lib.pam_amd_radiation_aggregate_debug_mapping(0))
+            assert all(bool(torch.isfinite(r).all()) for r in rad)
+
+    out = {"handoff_grid": "1024 x 32x32x60 (C2) and 8192 x 32x1x60 (C4)",
+           "handoff_method": "%d warm-up calls, median of %d event-timed calls" % (warmup, n)}
+    nens, nx, ny, nz = 1024, 32, 32, 60
+    cells = nens * nx * ny * nz
+    c = coupler(nens, nx, ny, nz)
+    dm = c.get_data_manager_device_readwrite()
+    names = ["density_dry", "uvel", "vvel", "wvel", "temp"] + c.get_tracer_names()
+    c.set_option("crm_accel_factor", 2.0)
+    modules.msa_init(c)
+    modules.time_average_init(c, names)
+    mfields, msave, _, _ = modules._msa_arrays(c)
+    MF, MS = modules._msa_table(mfields), modules._msa_table(msave)
+    out["msa_diagnose"] = row(timed(lambda: check(lib.pam_amd_msa_diagnose(nens, nx, ny, nz, MF, MS, stream))), 6 * cells * 8.0)
+    out["time_average_accumulate_8_fields"] = row(timed(lambda: modules.time_average_accumulate(c, names)), len(names) * cells * 24.0)
+    q = torch.rand((nz, 32, 32, nens), dtype=torch.float64, device=dev) - 0.5
+    temp = dm.get("temp")
+    out["radiation_forced_rad32x32"] = row(timed(lambda: check(lib.pam_amd_radiation_forced(nens, nx, ny, nz, 32, 32, temp.data_ptr(), q.data_ptr(),
+                                                                                            1003.0, 1.0e-3, stream))), cells * 16.0 + q.numel() * 8.0)
+    del q
+    aggregates(c, "", (((1, 1), ((0, ""), (2, "_thread_slots"))), ((8, 8), ((0, ""), (1, "_block_slots"))), ((32, 32), ((0, ""),))), out)
+    modules.crm_feedback_init(c)
+    modules.compute_crm_feedback(c)
+    out["crm_feedback"] = row(timed(lambda: modules.compute_crm_feedback(c)), 7 * cells * 8.0 + (7 + 12) * nz * nens * 8.0)
+    for k, y in (("radiation_aggregate_rad1x1", "msa_diagnose"), ("crm_feedback", "msa_diagnose"),
+                 ("radiation_aggregate_rad32x32", "time_average_accumulate_8_fields"), ("radiation_aggregate_rad32x32", "radiation_forced_rad32x32")):
+        out["%s_below_%s_by" % (k, y)] = out[y]["hbm_frac"] - out[k]["hbm_frac"]
+    del dm, c, mfields, msave, temp
+    lib.pam_amd_modules_finalize()
+    torch.cuda.empty_cache()
+    c = coupler(8192, 32, 1, 60)
+    c.set_option("crm_accel_factor", 2.0)
+    modules.msa_init(c)
+    mfields, msave, _, _ = modules._msa_arrays(c)
+    MF, MS = modules._msa_table(mfields), modules._msa_table(msave)
+    out["msa_diagnose_c4"] = row(timed(lambda: check(lib.pam_amd_msa_diagnose(8192, 32, 1, 60, MF, MS, stream))), 6 * 8192 * 32 * 60 * 8.0)
+    aggregates(c, "_c4", (((1, 1), ((0, ""), (1, "_block_slots"))), ((1, 8), ((0, ""),))), out)
+    out["radiation_aggregate_rad1x1_c4_below_msa_diagnose_c4_by"] = out["msa_diagnose_c4"]["hbm_frac"] - out["radiation_aggregate_rad1x1_c4"]["hbm_frac"]
+    del c, mfields, msave
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "handoff"]:
+        print(json.dumps(handoff_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "hyperdiffusion"]:
         print(json.dumps(hyperdiffusion_timing(dev)))
         sys.exit(0)
