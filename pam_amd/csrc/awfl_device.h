@@ -604,15 +604,29 @@ PAMA_D double mul_rn(double a, double b) {
 }
 
 // Acoustic characteristic flux at a face (Dycore.h:341-366, :477-496 for the vertical walls): face mass flux and pressure.
-PAMA_D void acoustic_face(double ru_L, double ru_R, double pp_L, double pp_R, bool wall, double &ruf, double &ppf) {
+// The two characteristic variables are each one cell's: w1 comes from the left-edge values of the cell on the right of the face, w2 from
+// the right-edge values of the cell on its left -- a sweep that meets the two cells far apart (the closing face of a periodic line)
+// keeps w1 instead of the two edge values.
+PAMA_D double acoustic_w1(double ru_R, double pp_R) {
 #pragma clang fp contract(off)
-  const double cs = 350.0, rcs = 1.0 / 350.0;               // Dycore.h:335
-  if (wall) { ru_L = 0.0; ru_R = 0.0; }                       // Dycore.h:477,482
-  const double w1 = 0.5 * fma(-cs, ru_R, pp_R);
-  const double w2 = 0.5 * fma(cs, ru_L, pp_L);
+  const double cs = 350.0;                                    // Dycore.h:335
+  return 0.5 * fma(-cs, ru_R, pp_R);
+}
+PAMA_D double acoustic_w2(double ru_L, double pp_L) {
+#pragma clang fp contract(off)
+  const double cs = 350.0;
+  return 0.5 * fma(cs, ru_L, pp_L);
+}
+PAMA_D void acoustic_face_w(double w1, double w2, bool wall, double &ruf, double &ppf) {
+#pragma clang fp contract(off)
+  const double rcs = 1.0 / 350.0;
   ppf = w1 + w2;
   ruf = (w2 - w1) * rcs;
   if (wall) ruf = 0.0;                                        // Dycore.h:496
+}
+PAMA_D void acoustic_face(double ru_L, double ru_R, double pp_L, double pp_R, bool wall, double &ruf, double &ppf) {
+  if (wall) { ru_L = 0.0; ru_R = 0.0; }                       // Dycore.h:477,482
+  acoustic_face_w(acoustic_w1(ru_R, pp_R), acoustic_w2(ru_L, pp_L), wall, ruf, ppf);
 }
 
 // -(dFx)/dx - (dFy)/dy - (dFz)/dz of one variable (Dycore.h:553-571), reciprocal multiplies (<= 1 ulp per term).  This association
@@ -931,11 +945,22 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
   // sweep also computes the face that closes its last cell: face fend, or the periodic face n == face 0 (same bits)
   const int cl = DIFF ? (fend < g.n ? fend : g.n) : fend - 1;          // last face needed (inclusive)
   const bool periodic = (DIR != 2);
-  // DIFF on a periodic line (swept whole: f0 = 0): the closing face n IS face 0 -- its fluxes are kept from the first trip and
-  // the last cell is closed after the loop, instead of reconstructing the same polynomials a second time (one trip in n + 1)
+  // DIFF on a periodic line (swept whole: f0 = 0): the closing face n IS face 0.  It is formed once, after the loops, from the right
+  // edges of cell n-1 (the last trip's) and the left edges of cell 0 (the prologue's, see cpro): n polynomial sets for n cells -- no
+  // polynomial of cell -1 == cell n-1 for its right edges only and no second trip over cell 0
   const bool reuse0 = DIFF && periodic && f0 == 0 && cl == g.n;
   const int cloop = reuse0 ? cl - 1 : cl;                               // last face the loops compute
   const int ncomp = (DIR == 0) ? P_U : (DIR == 1 ? P_V : P_W);         // normal velocity field
+  // z: faces 0 and nz are walls, the cells beyond them (-1: the prologue's; nz: the last trip's) are ghosts.  A wall face has no mass
+  // flux, so the only edge value of a ghost cell that a result needs is the pressure's.  The other polynomials of ghost cell -1, and
+  // those of ghost cell nz in the pair sweeps, are not built: wave-uniform branches outside the loops (f0, nz and the span are
+  // scalar); the loads, the stores and the table hooks of every trip stay
+  const bool wall_lo = (DIR == 2) && f0 == 0;
+  // last trip of the pair sweeps' loops: a span that ends at the top wall makes its last trip, the one of ghost cell nz, after them
+  const int cin = ((DIR == 2) && cloop == P.nz) ? cloop - 1 : cloop;
+  // the cell the prologue builds.  Normally f0-1, for its right edges (face f0).  A whole periodic line starts with cell 0 instead and
+  // keeps its LEFT edges for the closing face: the loops then run over the faces 1 .. n-1 like those of any other span
+  const int cpro = reuse0 ? 0 : f0 - 1;
 
   auto cell_off = [&](int c) -> long long {
     if (DIR == 2) return pbase + (long long)(c > P.nz + 2 ? P.nz + 2 : c) * g.cs;   // ghosts exist for c in [-3, nz+2]
@@ -964,8 +989,8 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
     double *fln = flux + (long long)(1 + ncomp - P_U) * g.fs_flux + fbase;
     double wm[5], wp[5], wn[5];   // windows: rho*u_n product, pressure, u_n
 #pragma unroll
-    for (int s = 0; s < 5; s++) {                          // cells f0-3..f0+1: the window of cell f0-1
-      const long long o = cell_off(f0 - 3 + s);
+    for (int s = 0; s < 5; s++) {                          // the window of the prologue's cell (f0-1: cells f0-3..f0+1)
+      const long long o = cell_off(cpro - 2 + s);
       wn[s] = uni(pn + o)[eu];
       wm[s] = mul_rn(uni(pr + o)[eu], wn[s]);
       wp[s] = uni(pp + o)[eu];
@@ -973,18 +998,34 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
     double prevR_m, prevR_p, prevR_n;
     if (DIR == 2) { zt.pass_begin(f0, cloop + 1); zt.trip_begin(f0); }     // (levels f0 .. cloop + 1, in this order)
     {                                                      // cell f0-1: only its right-edge values are needed (face f0)
-      double Lm, Lp, Ln;
-      weno(wm, f0 - 1, Lm, prevR_m);
-      weno(wp, f0 - 1, Lp, prevR_p);
-      weno(wn, f0 - 1, Ln, prevR_n);
-      const long long on = cell_off(f0 + 2);
+      double Lm0 = 0.0, Lp0, Ln0 = 0.0;                   // (cell 0 of a whole periodic line: both edges)
+      weno(wp, cpro, Lp0, prevR_p);
+      if (wall_lo) {
+        // face 0 of a column is a wall: acoustic_face() zeroes both rho*w arguments and returns ruf = +0.0, so of ghost cell -1 only
+        // the pressure's edge value reaches a result -- rho*w's is replaced by 0.0 and w's multiplied by +0.0 (fma(+0, ., ppf)):
+        // any finite value gives the same number (at most the sign of a zero differs)
+        prevR_m = 0.0; prevR_n = 0.0;
+      } else {
+        weno(wm, cpro, Lm0, prevR_m);
+        weno(wn, cpro, Ln0, prevR_n);
+      }
+      if (reuse0) {
+        // A whole periodic line: what face n == face 0 needs of cell 0 -- its characteristic variable w1 and the left edge of u_n --
+        // waits in memory, not in registers, in two output slots of this lane that no trip writes: the mass flux of face 0 and
+        // the difference of cell n-1 (both are stored after the loop, from these values)
+        uniw(fl0)[eu] = acoustic_w1(Lm0, Lp0);
+        uniw(fln + (long long)(g.n - 1) * g.cs)[eu] = Ln0;
+      }
+      const long long on = cell_off(cpro + 3);
       const double nn = uni(pn + on)[eu];
 #pragma unroll
       for (int s = 0; s < 4; s++) { wm[s] = wm[s + 1]; wp[s] = wp[s + 1]; wn[s] = wn[s + 1]; }
       wn[4] = nn; wm[4] = mul_rn(uni(pr + on)[eu], nn); wp[4] = uni(pp + on)[eu];
     }
     if (DIR == 2) zt.trip_end(f0);
-    double Fpn = 0.0, Fn0 = 0.0;                           // DIFF: the previous face's normal-momentum flux; face 0's
+    // DIFF: the previous face's normal-momentum flux.  A whole periodic line starts from 0.0: its first trip, face 1, then parks
+    // 0.0 - F[1] in cell 0's own output slot, where it waits for face 0 (after the loop)
+    double Fpn = 0.0;
     const double *fyn = FOLD ? fold_y + (long long)(1 + ncomp - P_U) * P.ncell + fbase : nullptr;
     // one trip: face c between cells c-1 and c, from the windows of cell c (cells c-2..c+2, in um / up / un)
     auto trip = [&](int c, const double (&um)[5], const double (&up)[5], const double (&un)[5]) __attribute__((always_inline)) {
@@ -1006,7 +1047,6 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
       if (!(DIFF && periodic && c == g.n)) uniw(fl0 + (long long)c * g.cs)[eu] = ruf;
       if (DIFF) {
         if (c > f0) uniw(fln + (long long)(c - 1) * g.cs)[eu] = FOLD ? folded(Fpn - fn, dyv, rdzv) : Fpn - fn;   // cell c-1 is closed by faces c-1 and c
-        else Fn0 = fn;
         Fpn = fn;
       } else {
         uniw(fln + (long long)c * g.cs)[eu] = fn;
@@ -1018,6 +1058,8 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
       // slot r with the cell that enters): no window is moved, and neighbouring cells of a round share their differences.  The y
       // sweep keeps moving windows: rotated, its three windows would also share second differences and their squares, and those
       // live ranges cost the 128-register budget 108 B of scratch (docs/experiments.md).
+      // (pass 1 builds ghost cell nz whole: making its last trip after the loop with the pressure polynomial alone costs every
+      // trip of the loop more scalar-register spills than the two polynomials are worth, and the kernel 8 B of scratch)
 #pragma clang loop unroll(disable)
       for (int c = f0; c <= cloop;) {
 #pragma unroll
@@ -1037,7 +1079,7 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
       }
     } else {
 #pragma clang loop unroll(disable)
-      for (int c = f0; c <= cloop; c++) {
+      for (int c = cpro + 1; c <= cloop; c++) {
         if (DIR == 2) zt.trip_begin(c + 1);
         const long long on = cell_off(c + 3);              // the next cell entering the window
         const double nn = uni(pn + on)[eu], nm = mul_rn(uni(pr + on)[eu], nn), np_ = uni(pp + on)[eu];
@@ -1048,7 +1090,19 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
         if (DIR == 2) zt.trip_end(c + 1);
       }
     }
-    if (reuse0) uniw(fln + (long long)(g.n - 1) * g.cs)[eu] = Fpn - Fn0;   // the last cell: closed by face n == face 0
+    if (reuse0) {
+      // face n == face 0, from the right edges of cell n-1 and what was kept of cell 0; its mass flux is stored here, before
+      // any pair sweep reads it.  It closes the last cell and, with the parked 0.0 - F[1] loaded back (this lane's own store), cell 0:
+      // F[0] + (0.0 - F[1]) is F[0] - F[1] rounded once (the negation is exact; only the sign of a zero can differ)
+      double ruf, ppf;
+      const double w1 = uni(fl0)[eu], Ln0 = uni(fln + (long long)(g.n - 1) * g.cs)[eu];
+      acoustic_face_w(w1, acoustic_w2(prevR_m, prevR_p), false, ruf, ppf);
+      const double fn = fma(ruf, (ruf > 0.0) ? prevR_n : Ln0, ppf);
+      uniw(fl0)[eu] = ruf;
+      uniw(fln + (long long)(g.n - 1) * g.cs)[eu] = Fpn - fn;
+      const double mF1 = uni(fln)[eu];
+      uniw(fln)[eu] = fn + mF1;
+    }
   }
   // ---------------- the other advected quantities (Dycore.h:367-385), FLUX_NF fields per sweep ------------------
   // One polynomial is a long dependent chain (differences -> coefficients -> TVs -> weights -> map -> blend); with few
@@ -1068,17 +1122,23 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
     }
 #pragma unroll
     for (int s = 0; s < 5; s++) {
-      const long long o = cell_off(f0 - 3 + s);
+      const long long o = cell_off(cpro - 2 + s);
 #pragma unroll
       for (int n = 0; n < NF; n++) w[n][s] = uni(q[n] + o)[eu];
     }
     if (DIR == 2) { zt.pass_begin(f0, cloop + 1); zt.trip_begin(f0); }
     {
-      const long long on = cell_off(f0 + 2);
+      const long long on = cell_off(cpro + 3);
 #pragma unroll
       for (int n = 0; n < NF; n++) {
-        double L;
-        weno(w[n], f0 - 1, L, prevR[n]);
+        // wall face 0: its mass flux is +0.0, never > 0, so the upwind value is cell 0's left edge and ghost cell -1 has no reader:
+        // its polynomials are not built
+        double L0 = 0.0;
+        if (wall_lo) prevR[n] = 0.0;
+        else weno(w[n], cpro, L0, prevR[n]);
+        // A whole periodic line: cell 0's left edge is what face n == face 0 needs of it.  It waits in memory, not in a register, in
+        // the output slot of this lane that no trip writes: the difference of cell n-1, or face 0 of a face-form field
+        if (reuse0) uniw(fl[n] + (n < NS ? (long long)(g.n - 1) * g.cs : 0))[eu] = L0;
 #pragma unroll
         for (int s = 0; s < 4; s++) w[n][s] = w[n][s + 1];
         w[n][4] = uni(q[n] + on)[eu];
@@ -1088,17 +1148,20 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
     const double *fyq[NF];
 #pragma unroll
     for (int n = 0; n < NF; n++) fyq[n] = (FOLD && n < NS) ? fold_y + (long long)(1 + fa[n]) * P.ncell + fbase : nullptr;
-    double Fp[NF], F0[NF];
+    // the previous face's flux.  A whole periodic line starts from 0.0: its first trip, face 1, then parks 0.0 - F[1] in cell 0's own
+    // output slot, where it waits for face 0 (after the loop)
+    double Fp[NF];
 #pragma unroll
-    for (int n = 0; n < NF; n++) Fp[n] = F0[n] = 0.0;
+    for (int n = 0; n < NF; n++) Fp[n] = 0.0;
     // The window does not move: trip r of five uses the slots (r, r+1, .. r+4) mod 5 and overwrites slot r -- the oldest cell --
     // with the cell that enters; after five trips the naming is back where it started.  (Shifting the window costs 4 v_mov_b64
     // per field and trip, 6 % of the vector instructions of a sweep.)
+    int c = cpro + 1;
 #pragma clang loop unroll(disable)
-    for (int c = f0; c <= cloop;) {
+    for (; c <= cin;) {
 #pragma unroll
       for (int r = 0; r < 5; r++) {
-        if (c > cloop) break;
+        if (c > cin) break;
         if (DIR == 2) zt.trip_begin(c + 1);
         const long long on = cell_off(c + 3);
         double nq[NF], L[NF], R[NF], dyv[NF], rdzv = 0.0;
@@ -1120,7 +1183,6 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
           const double F = mul_rn(ruf, up ? prevR[n] : L[n]);
           if (n < NS) {
             if (c > f0) uniw(fl[n] + (long long)(c - 1) * g.cs)[eu] = FOLD ? folded(Fp[n] - F, dyv[n], rdzv) : Fp[n] - F;
-            else F0[n] = F;
             Fp[n] = F;
           } else if (c < fend) {
             uniw(fl[n] + (long long)c * g.cs)[eu] = F;
@@ -1132,9 +1194,46 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
         c++;
       }
     }
-    if (reuse0) {
+    if (DIR == 2 && c <= cloop) {
+      // The last trip, face nz: a wall.  Its mass flux is +0.0, so the flux of every field is mul_rn(+0.0, left edge of ghost cell nz):
+      // a zero for any finite edge value.  No polynomial of the ghost cell is built and 0.0 stands in for the edge value.  Only the
+      // sign bit of that zero can differ from the built polynomial's (a face-form field stores it as it is), and it reaches an
+      // output only as the sign of a zero.  The trip's loads of the mass flux and the fold terms, its stores and its table hooks stay;
+      // the window has no cell left to take in.  (c == nz here: the loop's own counter)
+      zt.trip_begin(c + 1);
+      double dyv[NF], rdzv = 0.0;
 #pragma unroll
-      for (int n = 0; n < NS; n++) uniw(fl[n] + (long long)(g.n - 1) * g.cs)[eu] = Fp[n] - F0[n];   // closed by face n == face 0
+      for (int n = 0; n < NF; n++) dyv[n] = (FOLD && n < NS) ? uni(fyq[n] + (long long)fold_cell(c) * g.cs)[eu] : 0.0;
+      if (FOLD && NS > 0) rdzv = zt.rdz(P, fold_cell(c), e);
+      const double ruf = uni(fl0 + (long long)c * g.cs)[eu];
+#pragma unroll
+      for (int n = 0; n < NF; n++) {
+        const double F = mul_rn(ruf, 0.0);
+        if (n < NS) {
+          if (c > f0) uniw(fl[n] + (long long)(c - 1) * g.cs)[eu] = FOLD ? folded(Fp[n] - F, dyv[n], rdzv) : Fp[n] - F;
+        } else if (c < fend) {
+          uniw(fl[n] + (long long)c * g.cs)[eu] = F;
+        }
+      }
+      zt.trip_end(c + 1);
+    }
+    if (reuse0) {                                                // face n == face 0: upwinded by face 0's mass flux (pass 1's store)
+      const double ruf0 = uni(fl0)[eu];
+      const bool up0 = ruf0 > 0.0;
+#pragma unroll
+      for (int n = 0; n < NF; n++) {
+        const double L0 = uni(fl[n] + (n < NS ? (long long)(g.n - 1) * g.cs : 0))[eu];
+        const double Fc = mul_rn(ruf0, up0 ? prevR[n] : L0);
+        if (n < NS) {
+          // closes the last cell and, with the parked 0.0 - F[1] loaded back (this lane's own store), cell 0: F[0] + (0.0 - F[1]) is
+          // F[0] - F[1] rounded once (the negation is exact; only the sign of a zero can differ)
+          uniw(fl[n] + (long long)(g.n - 1) * g.cs)[eu] = Fp[n] - Fc;
+          const double mF1 = uni(fl[n])[eu];
+          uniw(fl[n])[eu] = Fc + mF1;
+        } else {
+          uniw(fl[n])[eu] = Fc;
+        }
+      }
     }
   };
   // dispatch: NF fields per sweep, of which the leading ns are state variables in difference form
