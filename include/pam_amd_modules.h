@@ -546,6 +546,45 @@ int pam_amd_radiation_aggregate_debug_mapping(int mapping);
 int pam_amd_crm_feedback(int nens, int nx, int ny, int nz, const double *const *fields, const double *const *gcm, double gcm_dt,
                          double *const *mean, double *const *tend, void *stream);
 
+/* The CRM column diagnostics: total, low, middle and high cloud cover, liquid and ice water path, precipitable water and surface
+ * precipitation per GCM column and member (the per-step aggregation of E3SM-MMF's pam_statistics and, before it, the column scan of SAM's
+ * crm_module, which sum with one atomicAdd per cell).  Not part of the reference tree; the contract is this project's
+ * and is restated in numpy in tests/coldiag_ref.py, which the kernels match bit for bit.
+ *   fields[6]   HOST array of DEVICE pointers (nz,ny,nx,nens), members fastest: temp, rho_d, rho_v, rho_c or NULL, rho_i or NULL, cldfrac
+ *               or NULL
+ *   zint        (nz+1,nens): the coupler's vertical_interface_height
+ *   precip[2]   HOST array of DEVICE pointers (ny,nx,nens): the liquid and the ice surface precipitation rate, each or both NULL (Kessler's
+ *               precl is the liquid one; P3's are precip_liq_surf_out and precip_ice_surf_out).  A NULL table: both absent
+ *   out[9]      HOST array of DEVICE pointers (nens), in/out: cldtot, cldlow, cldmed, cldhgh, lwp, iwp, pw, precip_liq, precip_ice
+ * Per column (j,i,e), top-down, k = nz-1 .. 0, every operation rounded on its own, no fma: dz = zint(k+1,e) - zint(k,e); w_v = rho_v dz,
+ * w_c = rho_c dz, w_i = rho_i dz; pw, lwp and iwp add their w in that order of levels from +0.0; cw = w_c + w_i (an absent species is
+ * skipped and adds no + 0.0); cld = cldfrac where given, otherwise the 1.0 / 0.0 flag of pam_amd_radiation_aggregate above; p =
+ * rho_d R_d temp + rho_v R_v temp as pam_amd_compute_pressure has it; the level's class is low where p >= p_low, high where p < p_high
+ * and middle otherwise (a NaN pressure: middle).  Each of four running pairs (cwp_X, cf_X), X = total, low, middle, high, is updated on
+ * the levels of its class, total on every level: cwp_X adds cw from +0.0; cf_X = cld > cf_X ? cld : cf_X from 0.0 (a NaN cld is ignored).
+ * The column's cldX is cwp_X > cwp_threshold ? cf_X : 0.0 (exactly at the threshold 0.0, and 0.0 for a NaN path); its precipitation values
+ * are the precip entries as they are.
+ * Per member: out_x(e) = out_x(e) + M(x)(e) * factor, the product rounded, then the add, by the one thread that owns the element; M is the
+ * 16-slot level mean of mean-state acceleration above over the ny nx columns (column c = j nx + i in slot c % 16, r = 1 / (ny nx)).
+ * factor is time_average_accumulate's weight.  The same bits from run to run and for any split of the members over calls.
+ * Absent parts: out[4] / out[5] must be NULL exactly where rho_c / rho_i is; out[7] / out[8] exactly where precip[0] / precip[1] is;
+ * out[0..3] all NULL where both condensates are absent and all given otherwise; out[6] is always required.  Nothing absent is read,
+ * computed or written.
+ * Two launches on `stream` (the column scan into a workspace of at most seven (ny,nx,nens) arrays, then the column mean), no
+ * synchronisation, no floating-point atomics, every element offset 64 bits wide.  The workspace is per device, allocated on first need,
+ * grown when a larger shape comes and released by pam_amd_modules_finalize: calls on one device must be ordered by the caller (one stream,
+ * or events between streams).
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: nens / nx / ny / nz < 1 (ny nx beyond 2^31 - 1, nz beyond
+ * 65535); a NULL fields, out or zint; a NULL temp, rho_d or rho_v; any violation of the NULL-ness rules; R_d, R_v, p_low, p_high or factor
+ * not finite; p_high > p_low; cwp_threshold negative or a NaN; an output that overlaps an input or another output.  No value in a field
+ * is ever refused.
+ * pam_amd_column_diagnostics_debug_mapping is a test switch like pam_amd_radiation_aggregate_debug_mapping, for the column mean: 0 =
+ * automatic (16 slot threads per member from 64 columns on, one thread per member below), 1 and 2 force the one and the other. */
+int pam_amd_column_diagnostics(int nens, int nx, int ny, int nz, const double *const *fields, const double *zint,
+                               const double *const *precip, double R_d, double R_v, double p_low, double p_high,
+                               double cwp_threshold, double *const *out, double factor, void *stream);
+int pam_amd_column_diagnostics_debug_mapping(int mapping);
+
 #ifdef __cplusplus
 }
 #endif

@@ -491,12 +491,14 @@ int kessler_read_dt_max(const double *slot, hipStream_t s, double *out) {
 void validate_scratch_free();   // the result scratch of pam_amd_validate_fields, defined with it below
 void diagnostics_scratch_free();   // the scratch of pam_amd_field_diagnostics, the same
 void hd_workspace_free();          // the workspace of pam_amd_hyperdiffusion's two-launch path, the same
+void cd_workspace_free();          // the workspace of pam_amd_column_diagnostics' column values, the same
 }  // namespace
 
 extern "C" int pam_amd_modules_finalize(void) {
   validate_scratch_free();
   diagnostics_scratch_free();
   hd_workspace_free();
+  cd_workspace_free();
   std::lock_guard<std::mutex> lk(g_tab_mutex);
   int cur = -1;
   (void)hipGetDevice(&cur);
@@ -3581,5 +3583,181 @@ extern "C" int pam_amd_crm_feedback(int nens, int nx, int ny, int nz, const doub
   dim3 grid, block;
   msa_launch_shape(nens, nz, grid, block);
   hipLaunchKernelGGL(crm_feedback_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, ny, F, G, gcm_dt, M, T);
+  return stats_launch_check(who);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The CRM column diagnostics: total, low, middle and high cloud cover, liquid and ice water path, precipitable water and surface
+// precipitation per GCM column (the per-step aggregation of E3SM-MMF's pam_statistics and the column scan of SAM's crm_module, which sum
+// with one atomicAdd per cell).  Not in the reference tree; the contract is in include/pam_amd_modules.h and DESIGN.md section 8, its
+// arithmetic in coldiag_device.h.  Two launches:
+//   the column scan   one thread per (column, member) -- its flat index inside a level IS the thread's, so a wavefront's loads are
+//                     contiguous whatever nens is -- walks the nz levels top-down, cd::SCAN_UNROLL levels' loads in flight per lane, and writes
+//                     the column's values to a workspace of at most seven (ny,nx,nens) arrays;
+//   the column mean   the 16-slot mean of the workspace arrays and the precipitation arrays over the ny nx columns and the accumulate: the
+//                     radiation aggregate's walk over one group of ny nx cells per member, one quantity per workgroup (grid.y = the nine
+//                     quantities), by 16 slot threads per member from 64 columns on and by one thread per member below.
+// A single fused launch (slot threads walking columns) would have about nens / 4 wavefronts at the C2 grid: too few to keep HBM busy
+// (DESIGN.md section 8).  No floating-point atomics; every element offset is 64 bits wide.
+#include "coldiag_device.h"
+
+namespace {
+namespace cd = pama::coldiag;
+struct CdFields { const double *p[cd::NF]; };
+struct CdWork { double *p[cd::NW]; };
+struct CdMeanIn { const double *p[cd::NO]; };
+struct CdOut { double *p[cd::NO]; };
+constexpr int CD_THREADS = 256;
+constexpr int CD_BLOCK_COLUMNS = 64;       // from this many columns on the mean takes 16 slot threads per member
+enum { CD_AUTO, CD_BLOCK_SLOTS, CD_THREAD_SLOTS };
+
+// grid (ceil(ny nx nens / 256)), block 256: thread t = c nens + e
+__global__ void __launch_bounds__(CD_THREADS) coldiag_scan_kernel(int nens, long long level, int nz, CdFields F, const double *__restrict__ zint,
+                                                                  CdWork W, cd::Params P) {
+  const long long t = (long long)blockIdx.x * CD_THREADS + (long long)threadIdx.x;
+  if (t >= level) return;
+  const double *f[cd::NF];
+#pragma unroll
+  for (int i = 0; i < cd::NF; i++) f[i] = F.p[i];
+  cd::Column c;
+  cd::column_scan<cd::SCAN_UNROLL>(f, zint, t, level, nens, (int)(t % nens), nz, P, c);
+  cd::column_store(c, W.p, t, P);
+}
+
+// grid (member blocks, the nine quantities), block (members, 16 slots): a workgroup takes ONE quantity of its members (with three per
+// workgroup the C2 grid has 48 workgroups instead of 144: measured in one run 0.480 and 0.501 ms per call against 0.468 and 0.483, and
+// 0.675 and 0.716 ms against 0.606 and 0.623 where the thread-slots kernel is forced)
+__global__ void __launch_bounds__(64 * MOD_NS) coldiag_mean_block_kernel(int nens, int ncol, CdMeanIn I, CdOut O, double factor) {
+  __shared__ double red[MOD_NS * 64];
+  const int q = (int)blockIdx.y, slot = (int)threadIdx.y, e0 = (int)blockIdx.x * (int)blockDim.x + (int)threadIdx.x;
+  if (!I.p[q]) return;                               // an absent quantity: the same for the whole workgroup
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1;
+  const double *f[1] = {I.p[q] + e};
+  double tot[1] = {0.0};
+  if (ok) rd::slot_walk<cd::Means, 4>(f, (long long)nens, (long long)ncol * nens, ncol, ncol, slot, rd::Cursor{slot / ncol, slot % ncol},
+                                      cd::r_columns(ncol), tot);
+  slot_reduce<1>(tot, red);
+  if (slot != 0 || !ok) return;
+  O.p[q][e] = rd::accumulate(O.p[q][e], tot[0], factor);
+}
+
+// grid (ceil(nens / 256), the nine quantities), block 256: a thread owns one quantity of one member
+__global__ void __launch_bounds__(CD_THREADS) coldiag_mean_thread_kernel(int nens, int ncol, CdMeanIn I, CdOut O, double factor) {
+  const int q = (int)blockIdx.y, e = (int)blockIdx.x * CD_THREADS + (int)threadIdx.x;
+  if (e >= nens || !I.p[q]) return;
+  const double *f[1] = {I.p[q] + e};
+  double tot[1] = {0.0};
+  rd::slots_walk<cd::Means>(f, (long long)nens, (long long)ncol * nens, ncol, ncol, 0, rd::NS, cd::r_columns(ncol), tot);
+  O.p[q][e] = rd::accumulate(O.p[q][e], tot[0], factor);
+}
+
+// the workspace of the column values: per device, grown on demand, freed by pam_amd_modules_finalize().  Both launches of a call go to
+// the caller's stream and nothing synchronises, so calls on ONE device must be ordered by the caller (one stream, or events between
+// streams) -- as they are for any two calls that write the same outputs.  Growing frees the old array, which waits for the device.
+constexpr int CD_MAX_DEVICES = 64;
+struct CdWorkspace { std::mutex m; double *p = nullptr; long long count = 0; };
+CdWorkspace g_cd_workspace[CD_MAX_DEVICES];
+
+void cd_workspace_free() {
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  for (int d = 0; d < CD_MAX_DEVICES; d++) {
+    CdWorkspace &w = g_cd_workspace[d];
+    std::lock_guard<std::mutex> lk(w.m);
+    if (w.p) {
+      if (d != cur) (void)hipSetDevice(d);
+      (void)hipFree(w.p);
+      w.p = nullptr;
+      w.count = 0;
+      if (d != cur && cur >= 0) (void)hipSetDevice(cur);
+    }
+  }
+}
+
+int g_cd_mapping = CD_AUTO;   // pam_amd_column_diagnostics_debug_mapping: tests run both mean mappings at small shapes
+}  // namespace
+
+extern "C" int pam_amd_column_diagnostics_debug_mapping(int mapping) {
+  if (mapping < CD_AUTO || mapping > CD_THREAD_SLOTS)
+    return rad_error("column_diagnostics", "debug mapping must be 0 (automatic), 1 (block slots) or 2 (thread slots)");
+  g_cd_mapping = mapping;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_column_diagnostics(int nens, int nx, int ny, int nz, const double *const *fields, const double *zint,
+                                          const double *const *precip, double R_d, double R_v, double p_low, double p_high,
+                                          double cwp_threshold, double *const *out, double factor, void *stream) {
+  const char *who = "column_diagnostics";
+  if (int rc = rad_check_sizes(who, nens, nx, ny, nz)) return rc;
+  if (!fields || !out || !zint) return rad_error(who, "null fields, out or zint");
+  if (!fields[cd::F_TEMP] || !fields[cd::F_RHOD] || !fields[cd::F_RHOV]) return rad_error(who, "null temp, rho_d or rho_v pointer");
+  const bool has_c = fields[cd::F_RHOC] != nullptr, has_i = fields[cd::F_RHOI] != nullptr;
+  const double *pr[2] = {precip ? precip[0] : nullptr, precip ? precip[1] : nullptr};
+  if ((out[cd::O_LWP] != nullptr) != has_c) return rad_error(who, "lwp must be given exactly when rho_c is");
+  if ((out[cd::O_IWP] != nullptr) != has_i) return rad_error(who, "iwp must be given exactly when rho_i is");
+  if ((out[cd::O_PRECL] != nullptr) != (pr[0] != nullptr)) return rad_error(who, "precip_liq must be given exactly when its precipitation array is");
+  if ((out[cd::O_PRECI] != nullptr) != (pr[1] != nullptr)) return rad_error(who, "precip_ice must be given exactly when its precipitation array is");
+  for (int x = 0; x < cd::NC; x++)
+    if ((out[cd::O_CLDTOT + x] != nullptr) != (has_c || has_i))
+      return rad_error(who, "cldtot, cldlow, cldmed and cldhgh must all be given where a condensate is, and none of them where neither is");
+  if (!out[cd::O_PW]) return rad_error(who, "null pw pointer");
+  if (!std::isfinite(R_d) || !std::isfinite(R_v) || !std::isfinite(p_low) || !std::isfinite(p_high) || !std::isfinite(factor))
+    return rad_error(who, "R_d, R_v, p_low, p_high and factor must be finite");
+  if (p_high > p_low) return rad_error(who, "p_high must not exceed p_low");
+  if (!(cwp_threshold >= 0)) return rad_error(who, "cwp_threshold must be >= 0");
+  const long long ncol = (long long)nx * ny, level = ncol * nens, cells = level * nz;
+  std::vector<RadSpan> spans;
+  for (int i = 0; i < cd::NF; i++)
+    if (fields[i]) spans.push_back({fields[i], cells, false});
+  spans.push_back({zint, (long long)(nz + 1) * nens, false});
+  for (int i = 0; i < 2; i++)
+    if (pr[i]) spans.push_back({pr[i], level, false});
+  for (int q = 0; q < cd::NO; q++)
+    if (out[q]) spans.push_back({out[q], (long long)nens, true});
+  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
+  const long long scan_blocks = (level + CD_THREADS - 1) / CD_THREADS;
+  if (scan_blocks > 0x7fffffffLL) return rad_error(who, "ny x nx x nens exceeds the grid");
+  if (int rc = moist_surface_device_check(who)) return rc;
+
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= CD_MAX_DEVICES)
+    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "column_diagnostics: cannot tell the current device");
+  CdFields F;
+  CdWork W;
+  CdMeanIn I;
+  CdOut O;
+  for (int i = 0; i < cd::NF; i++) F.p[i] = fields[i];
+  int nws = 0;
+  for (int q = 0; q < cd::NW; q++) nws += out[q] != nullptr;
+  CdWorkspace &w = g_cd_workspace[dev];
+  std::lock_guard<std::mutex> lk(w.m);
+  if (w.count < nws * level) {
+    if (w.p) (void)hipFree(w.p);
+    w.p = nullptr;
+    w.count = 0;
+    if (hipMalloc((void **)&w.p, (size_t)(nws * level) * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
+      w.p = nullptr;
+      return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "column_diagnostics: cannot allocate the workspace of the column values");
+    }
+    w.count = nws * level;
+  }
+  int at = 0;
+  for (int q = 0; q < cd::NW; q++) W.p[q] = out[q] ? w.p + (long long)(at++) * level : nullptr;
+  for (int q = 0; q < cd::NO; q++) { I.p[q] = q < cd::NW ? W.p[q] : pr[q - cd::NW]; O.p[q] = out[q]; }
+  const cd::Params P{R_d, R_v, p_low, p_high, cwp_threshold};
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(coldiag_scan_kernel, dim3((unsigned)scan_blocks), dim3(CD_THREADS), 0, s, nens, level, nz, F, zint, W, P);
+  if (int rc = stats_launch_check(who)) return rc;
+  const bool block_slots = g_cd_mapping == CD_AUTO ? ncol >= CD_BLOCK_COLUMNS : g_cd_mapping == CD_BLOCK_SLOTS;
+  if (block_slots) {
+    const int ME = nens < 64 ? nens : 64;
+    hipLaunchKernelGGL(coldiag_mean_block_kernel, dim3((unsigned)((nens + ME - 1) / ME), (unsigned)cd::NO), dim3((unsigned)ME, (unsigned)MOD_NS), 0, s,
+                       nens, (int)ncol, I, O, factor);
+  } else {
+    hipLaunchKernelGGL(coldiag_mean_thread_kernel, dim3((unsigned)((nens + CD_THREADS - 1) / CD_THREADS), (unsigned)cd::NO), dim3(CD_THREADS), 0, s,
+                       nens, (int)ncol, I, O, factor);
+  }
   return stats_launch_check(who);
 }

@@ -790,3 +790,106 @@ def compute_crm_feedback(coupler):
     with torch.cuda.device(coupler.device):
         check(capi.load().pam_amd_crm_feedback(nens, coupler.get_nx(), coupler.get_ny(), nz, _msa_table(fields), _msa_table(gcm), gcm_dt,
                                                _msa_table(mean), _msa_table(tend), torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+# ---- the CRM column diagnostics: cloud cover, water paths, precipitable water and surface precipitation per GCM column (the per-step
+# aggregation of E3SM-MMF's pam_statistics).  Not part of the reference tree: the contract is this project's (include/pam_amd_modules.h,
+# DESIGN.md section 8; numpy restatement: tests/coldiag_ref.py)
+COLUMN_DIAGNOSTICS = ("diag_cldtot", "diag_cldlow", "diag_cldmed", "diag_cldhgh", "diag_lwp", "diag_iwp", "diag_pw", "diag_precip_liq",
+                      "diag_precip_ice")
+COLUMN_DIAGNOSTICS_DEFAULTS = (("crm_diag_p_low", 70000.0), ("crm_diag_p_high", 40000.0), ("crm_diag_cwp_threshold", 1.0e-3))
+
+
+def _column_diagnostics_names(coupler):
+    """-> (nens, nz, ny, nx), (cloud, ice), the two precipitation entries (None where the DataManager has none) and the nine outputs'
+    names in the order of the C ABI, None where the coupler lacks the inputs"""
+    from .coupler import endrun
+    nens, nz, ny, nx = coupler.get_nens(), coupler.get_nz(), coupler.get_ny(), coupler.get_nx()
+    if min(nens, nz, ny, nx) < 1:
+        endrun("ERROR: column_diagnostics: the coupler state is not allocated")
+    cloud, ice = _handoff_condensate(coupler, "column_diagnostics")
+    dm = coupler.get_data_manager_device_readwrite()
+    liq = "precl" if dm.entry_exists("precl") else ("precip_liq_surf_out" if dm.entry_exists("precip_liq_surf_out") else None)
+    pice = "precip_ice_surf_out" if dm.entry_exists("precip_ice_surf_out") else None
+    for n in (liq, pice):
+        if n is not None and dm.get_shape(n) != [ny, nx, nens]:
+            endrun("ERROR: column_diagnostics: %s is %s, not (ny,nx,nens)" % (n, dm.get_shape(n)))
+    there = [cloud is not None or ice is not None] * 4 + [cloud is not None, ice is not None, True, liq is not None, pice is not None]
+    return (nens, nz, ny, nx), (cloud, ice), (liq, pice), [n if t else None for n, t in zip(COLUMN_DIAGNOSTICS, there)]
+
+
+def column_diagnostics_init(coupler):
+    """First in every GCM step: registers "diag_cldtot", "diag_cldlow", "diag_cldmed", "diag_cldhgh", "diag_lwp", "diag_iwp", "diag_pw",
+    "diag_precip_liq" and "diag_precip_ice" (nens) on first use -- only those whose inputs the coupler has: no cloud cover without a
+    condensate (option "micro"), no path without its species, no precipitation without "precl" or "precip_liq_surf_out" /
+    "precip_ice_surf_out" -- and zeroes them.  Sets the options "crm_diag_p_low" = 70000, "crm_diag_p_high" = 40000 and
+    "crm_diag_cwp_threshold" = 1e-3 where they are unset."""
+    from .coupler import endrun
+    (nens, _, _, _), _, _, names = _column_diagnostics_names(coupler)
+    dm = coupler.get_data_manager_device_readwrite()
+    names = [n for n in names if n is not None]
+    for n in names:
+        if dm.entry_exists(n) and dm.get_shape(n) != [nens]:
+            endrun("ERROR: column_diagnostics: %s exists with a shape other than (nens)" % n)
+    for opt, value in COLUMN_DIAGNOSTICS_DEFAULTS:
+        if not coupler.option_exists(opt):
+            coupler.set_option(opt, value)
+    for n in names:
+        if not dm.entry_exists(n):
+            dm.register_and_allocate(n, "CRM column diagnostic, averaged over the columns and the GCM step", (nens,), ("nens",))
+    out = [dm.get(n) for n in names]
+    with torch.cuda.device(coupler.device):
+        check(capi.load().pam_amd_time_average_zero(len(out), _sizes([[nens]] * len(out)), _ptr_table(out),
+                                                    torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+def column_diagnostics(coupler, weight=1):
+    """After the last module of every CRM step: diag_x += M(x) * (crm_dt / gcm_physics_dt * weight) with M the mean over the CRM columns
+    of the column's cloud covers (the greatest cloud fraction of the levels of a pressure class where the class's condensed water path
+    exceeds crm_diag_cwp_threshold), water paths and surface precipitation.  The factor is time_average_accumulate's, so weight takes
+    MsaClock's step weight.  Every misuse raises before the launch."""
+    import math
+    from .coupler import endrun
+    (nens, nz, ny, nx), (cloud, ice), (liq, pice), names = _column_diagnostics_names(coupler)
+    dm = coupler.get_data_manager_device_readwrite()
+    if not dm.entry_exists("diag_pw"):
+        endrun("ERROR: diag_pw does not exist: call column_diagnostics_init first")
+    for opt in ("R_d", "R_v") + tuple(o for o, _ in COLUMN_DIAGNOSTICS_DEFAULTS):
+        if not coupler.option_exists(opt):
+            endrun("ERROR: column_diagnostics: option %s is not set" % opt)
+    R_d, R_v = float(coupler.get_option("R_d")), float(coupler.get_option("R_v"))
+    p_low, p_high = float(coupler.get_option("crm_diag_p_low")), float(coupler.get_option("crm_diag_p_high"))
+    threshold = float(coupler.get_option("crm_diag_cwp_threshold"))
+    if not all(math.isfinite(v) for v in (R_d, R_v, p_low, p_high)):
+        endrun("ERROR: column_diagnostics: R_d, R_v, crm_diag_p_low and crm_diag_p_high must be finite")
+    if p_high > p_low:
+        endrun("ERROR: column_diagnostics: crm_diag_p_high must not exceed crm_diag_p_low")
+    if not threshold >= 0:
+        endrun("ERROR: column_diagnostics: crm_diag_cwp_threshold must be >= 0")
+    crm_dt = float(coupler.get_option("crm_dt"))
+    gcm_dt = float(coupler.get_option("gcm_physics_dt"))
+    if not gcm_dt > 0:
+        endrun("ERROR: column_diagnostics: gcm_physics_dt must be positive")
+    factor = crm_dt / gcm_dt * float(weight)
+    if not math.isfinite(factor):
+        endrun("ERROR: column_diagnostics: crm_dt / gcm_physics_dt x weight is not finite")
+    for n in names:
+        if n is None:
+            continue
+        if not dm.entry_exists(n):
+            endrun("ERROR: %s does not exist: call column_diagnostics_init first" % n)
+        if dm.get_shape(n) != [nens]:
+            endrun("ERROR: column_diagnostics: %s is %s, not (nens)" % (n, dm.get_shape(n)))
+    has_cldfrac = dm.entry_exists("cldfrac")
+    if has_cldfrac and dm.get_shape("cldfrac") != [nz, ny, nx, nens]:
+        endrun("ERROR: column_diagnostics: cldfrac is %s, not (nz,ny,nx,nens)" % dm.get_shape("cldfrac"))
+    fields = [dm.get("temp", readonly=True), dm.get("density_dry", readonly=True), dm.get("water_vapor", readonly=True),
+              dm.get(cloud, readonly=True) if cloud else None, dm.get(ice, readonly=True) if ice else None,
+              dm.get("cldfrac", readonly=True) if has_cldfrac else None]
+    precip = [dm.get(n, readonly=True) if n else None for n in (liq, pice)]
+    out = [dm.get(n) if n else None for n in names]
+    with torch.cuda.device(coupler.device):
+        check(capi.load().pam_amd_column_diagnostics(nens, nx, ny, nz, _msa_table(fields),
+                                                     dm.get("vertical_interface_height", readonly=True).data_ptr(), _msa_table(precip),
+                                                     R_d, R_v, p_low, p_high, threshold, _msa_table(out), factor,
+                                                     torch.cuda.current_stream(coupler.device).cuda_stream))

@@ -14,6 +14,8 @@ time_average_accumulate of the same run;
 with 8192 members, beside msa_apply and time_average_accumulate of the same run;
 --only handoff: the radiation column aggregates at the C2 grid (rad grids 1x1, 8x8, 32x32) and at C4's 32x1x60 grid with 8192 members,
 and the CRM feedback, beside msa_diagnose, time_average_accumulate and radiation_forced of the same run;
+--only coldiag: the CRM column diagnostics on P3's field set at the C2 grid and at C4's 32x1x60 grid with 8192 members, beside the
+radiation aggregate at the 1x1 rad grid and msa_diagnose of the same run;
 --only msa: mean-state acceleration's diagnose, tendencies and apply (with and without the winds), beside horizontal_average and
 time_average_accumulate of the same run)"""
 import json
@@ -1040,8 +1042,99 @@ def handoff_timing(dev, warmup=3, n=11):
     return out
 
 
+def coldiag_timing(dev, warmup=3, n=11):
+    """The CRM column diagnostics on the P3 field set (cloud water and ice present, no cldfrac, both precipitation arrays):
+    pam_amd_column_diagnostics at the C2 grid and at C4's 32x1x60 grid with 8192 members, with the mean mapping the size chooses and with the
+    other one; both launches of a call are timed together.  3 warm-up calls and the median of 11 event-timed calls each.  Algorithmic bytes: 8 B per cell and present input field (five), 16 B per workspace element (seven arrays
+    written by the scan and read by the mean) and 8 B per precipitation element (two arrays).  The yardsticks of the same run:
+    pam_amd_radiation_aggregate at the 1x1 rad grid (six field streams) and msa_diagnose."""
+    from pam_amd import PamCoupler, capi, modules
+    from pam_amd import idealized as idz
+    from pam_amd.capi import check
+    lib = capi.load()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    def row(t, nbytes):
+        return {"ms": t[0], "min_ms": t[1], "max_ms": t[2], "bytes": nbytes, "GBps": nbytes / t[0] / 1e6,
+                "hbm_frac": nbytes / t[0] / 1e6 / bench.HBM_PEAK_GBS}
+
+    def grid(nens, nx, ny, nz, label, out):
+        c = PamCoupler(dev)
+        c.set_option("crm_dt", 20.0)
+        c.set_option("gcm_physics_dt", 900.0)
+        c.set_option("R_d", 287.042)
+        c.set_option("R_v", 461.505)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+        for t in ("water_vapor", "cloud_water", "ice"):
+            c.add_tracer(t, "", True, True)
+        c.set_option("micro", "p3")
+        dm = c.get_data_manager_device_readwrite()
+        for name in ("precip_liq_surf_out", "precip_ice_surf_out"):
+            dm.register_and_allocate(name, "surface precipitation rate", (ny, nx, nens), ("y", "x", "nens"))
+        gen = torch.Generator(device=dev).manual_seed(0)
+        # a troposphere of pressures across the three classes, and condensate in a third of the cells
+        k = torch.arange(nz, dtype=torch.float64, device=dev)[:, None, None, None]
+        for name, scale in (("temp", 290.0 - 1.2 * k), ("density_dry", 1.2 * torch.exp(-k / 25.0)), ("water_vapor", 1.0e-2 * torch.exp(-k / 10.0)),
+                            ("uvel", 10.0), ("vvel", 10.0)):
+            t = dm.get(name)
+            t.copy_((torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * 0.1 + 0.95) * scale)
+        for name, scale in (("cloud_water", 1.0e-4), ("ice", 3.0e-5), ("precip_liq_surf_out", 1.0e-4), ("precip_ice_surf_out", 3.0e-5)):
+            t = dm.get(name)
+            t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * scale)
+            t.mul_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) < 1.0 / 3.0)
+        cells, cols = nens * nx * ny * nz, nens * nx * ny
+        modules.column_diagnostics_init(c)
+        nbytes = 5 * cells * 8.0 + 7 * cols * 16.0 + 2 * cols * 8.0
+        for mapping, tag in ((0, ""), (2 if nx * ny >= 64 else 1, "_other_mean_mapping")):
+            check(lib.pam_amd_column_diagnostics_debug_mapping(mapping))
+            try:
+                out["column_diagnostics%s%s" % (tag, label)] = row(timed(lambda: modules.column_diagnostics(c)), nbytes)
+            finally:
+                check(lib.pam_amd_column_diagnostics_debug_mapping(0))
+        assert all(bool(torch.isfinite(dm.get(name, readonly=True)).all()) for name in modules.COLUMN_DIAGNOSTICS)
+        c.set_option("crm_accel_factor", 2.0)
+        modules.msa_init(c)
+        mfields, msave, _, _ = modules._msa_arrays(c)
+        MF, MS = modules._msa_table(mfields), modules._msa_table(msave)
+        out["msa_diagnose" + label] = row(timed(lambda: check(lib.pam_amd_msa_diagnose(nens, nx, ny, nz, MF, MS, stream))), 6 * cells * 8.0)
+        fields = [dm.get(name, readonly=True) for name in ("temp", "density_dry", "water_vapor", "cloud_water", "ice")] + [None]
+        rad = [torch.zeros((nz, 1, 1, nens), dtype=torch.float64, device=dev) for _ in range(5)]
+        F, R = modules._msa_table(fields), modules._msa_table(rad)
+        out["radiation_aggregate_rad1x1" + label] = row(timed(lambda: check(lib.pam_amd_radiation_aggregate(
+            nens, nx, ny, nz, 1, 1, F, R, 20.0 / 900.0, stream))), 5 * cells * 8.0 + 5 * rad[0].numel() * 16.0)
+        for y in ("radiation_aggregate_rad1x1", "msa_diagnose"):
+            out["column_diagnostics%s_below_%s%s_by" % (label, y, label)] = out[y + label]["hbm_frac"] - out["column_diagnostics" + label]["hbm_frac"]
+        del c, dm, mfields, msave, fields, rad
+        lib.pam_amd_modules_finalize()
+        torch.cuda.empty_cache()
+
+    out = {"coldiag_grid": "1024 x 32x32x60 (C2) and 8192 x 32x1x60 (C4)",
+           "coldiag_method": "%d warm-up calls, median of %d event-timed calls" % (warmup, n)}
+    grid(1024, 32, 32, 60, "", out)
+    grid(8192, 32, 1, 60, "_c4", out)
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "coldiag"]:
+        print(json.dumps(coldiag_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "handoff"]:
         print(json.dumps(handoff_timing(dev)))
         sys.exit(0)
