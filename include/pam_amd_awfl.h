@@ -185,7 +185,10 @@ int pam_amd_awfl_set_range_schedule(pam_amd_awfl_t *h, int independent);
 /* Member-lane sweeps with further tracers (NT > 1): the last three launches of a stage -- phase 2 of the further tracers' x sweeps, the
  * pressure pass, water vapour's fix-up; they read what earlier launches wrote and write disjoint things -- as ONE launch (mode 2;
  * automatic: while the phase-2 launch is less than about two rounds of wavefronts, e.g. one GPU's shard of C4) or three (mode 1).
- * Same bits (ABI 5). */
+ * Same bits (ABI 5).
+ * Water vapour alone (NT = 1), member-lane sweeps whose spans are at most 32 cells: mode 2 forms the next stage's pressure inside the
+ * fused x-sweep (no pressure-pass launch; rho*theta stays in the CU's LDS); mode 1 keeps the separate pass; automatic: mode 2
+ * (measured, docs/experiments.md).  Longer spans, flat lanes and tile kernels keep the separate pass whatever the mode.  Same bits. */
 int pam_amd_awfl_set_tail_fusion(pam_amd_awfl_t *h, int mode);
 /* Fused stage, 3-D grids swept with member lanes: the momentum components and rho*theta take their divergence as x + (y + z)
  * (Dycore.h:553-571 sums the three directions; the density and the tracers keep (x + y) + z).  mode 2: the z sweep runs in a launch

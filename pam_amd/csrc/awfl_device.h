@@ -2086,6 +2086,46 @@ PAMA_D void x_tracer_sweep(const Params &P, const double *__restrict__ prim_in, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// In-sweep pressure of the fused x-sweep (NT = 1).  The sweep loop has no register left for the pow that turns a cell's new rho*theta
+// into the next stage's pressure, so a lane parks the rho*theta of every cell it completes in a slot of its own (on the device: LDS,
+// XSTASH_CELLS x XSTASH_LANES doubles per wavefront; a lane reads only what it wrote, so nothing synchronises) and works the slots off
+// behind the loop, where nothing of the loop is live any more.  NoStash switches all of it off at compile time.
+constexpr int XSTASH_CELLS = 32;     // cells of a span that a stash holds: longer spans keep the separate pressure pass
+constexpr int XSTASH_LANES = 64;     // slots of one cell: a lane's cell n is slot[n * XSTASH_LANES]
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef __attribute__((address_space(3))) double *stash_ptr;
+#else
+typedef double *stash_ptr;
+#endif
+struct NoStash { static constexpr bool on = false; };
+// slot: the lane's slot of the span's first cell (one address register, advanced by one vector add per trip of the sweep loop; forming
+// the lane's part anew on every trip from the member offset costs no register but more scalar spills: measured, docs/experiments.md)
+struct LineStash { static constexpr bool on = true; stash_ptr slot; };
+
+// The pressure pass of the cells c0 .. c1-1 of line (k, j) by the lane that has just completed them: pressure_tail_body's values
+// (rho*theta from the stash instead of prim_out[P_PRES]; on the two boundary levels theta and the new density are the lane's own
+// stores to prim_out, read back in program order) through the same store_rho_pres<false>.  P.pw: on the device the caller's LDS copy.
+// The member comes as the offset `eu` the sweep addresses with, behind an opaque copy: whatever the epilogue derives from it per lane
+// (the addresses of dz and hy_pres, the cell's offset) is then formed here, behind the loop, instead of living across it in registers.
+PAMA_D void xsweep_pressure_epilogue(const Params &P, double *prim_out, const NoStash &, int, long long, unsigned, int, int) {}
+PAMA_D void xsweep_pressure_epilogue(const Params &P, double *prim_out, const LineStash &stash, int k, long long cu0, unsigned eu, int c0, int c1) {
+  const bool boundary = (k == 0 || k == P.nz - 1);
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(eu));
+#endif
+  const int e = (int)eu;
+#pragma clang loop unroll(disable)
+  for (int cc = c0; cc < c1; cc++) {
+    const long long cu = cu0 + (long long)cc * P.sx, c2 = cu + e;
+    const long long ou = (long long)(k + HS) * P.sz + cu;         // the cell of member 0 inside a prim field (uniform)
+    const double th = boundary ? uni(prim_out + P_THETA * P.prim_fs + ou)[eu] : 0.0;
+    const double rho_theta = stash.slot[(cc - c0) * XSTASH_LANES];
+    const double rho_new = boundary ? uni(prim_out + P_RHO * P.prim_fs + ou)[eu] : 0.0;
+    store_rho_pres<false>(P, prim_out, k, c2, e, rho_new, th, rho_theta, !P.grav_balance);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // FUSED x-sweep: reconstruction + fluxes in x (as flux_line_body<0>) AND, in the same pass, the stage update of the five
 // state variables of every cell of the line (as update_body), with the y and z flux differences of the cell read from the
 // arrays the y/z sweeps (flux_line_body<.., DIFF = true>) wrote earlier.  Reference: Dycore.h:334-386 (x fluxes), :553-571 (divergence, gravity), :162-221 (SSPRK3
@@ -2115,12 +2155,16 @@ PAMA_D void x_tracer_sweep(const Params &P, const double *__restrict__ prim_in, 
 //   tracers_inline   phase 1 of the further tracers here (else the caller launches awfl_xtr_kernel<., 1>)
 //   FOLD   the z sweep has folded the y differences of the state variables into the field it stores (flux_line_body_zt<., FOLD>;
 //          P.yz_fold, 3-D only): the z array holds the y+z part of each variable's divergence and the y differences are not loaded
-template <int STAGE, bool FOLD = false>
+//   stash  NoStash: the new rho*theta goes to prim_out[P_PRES] and pressure_tail_body follows in a pass of its own.  LineStash
+//          (NT = 1 -- no further tracers are swept and no mass flux is kept for them; spans of at most XSTASH_CELLS cells): the lane keeps the rho*theta of the cells it completes in slots of its
+//          own and, behind the sweep loop, makes the next stage's pressure of them itself (xsweep_pressure_epilogue: the arithmetic
+//          of pressure_tail_body on the same doubles -- same bits, no pressure pass, rho*theta never leaves the CU)
+template <int STAGE, bool FOLD = false, class Stash = NoStash>
 PAMA_D void flux_x_update_body(const Params &P, const double *__restrict__ prim_in, const double *__restrict__ prim0,
                                double *__restrict__ prim_out, double *__restrict__ fx, const double *__restrict__ fy,
                                const double *__restrict__ fz, double *__restrict__ seed, double *__restrict__ mult,
                                const FctRows &rows, int line, int e, int c0, int span, double dt_dyn, double dt_stage,
-                               bool tracers_inline) {
+                               bool tracers_inline, const Stash stash = Stash()) {
   const unsigned eu = member_offset(e);
   const WenoConsts wc = weno_consts();
   const int nx = P.nx;
@@ -2154,7 +2198,7 @@ PAMA_D void flux_x_update_body(const Params &P, const double *__restrict__ prim_
     const int tr = P.idWV;                                 // the tracer that rides with the state (water vapour)
     const double *pt = prim_in + (long long)(P_TR0 + tr) * P.prim_fs;
     double *flt = fx + (long long)(5 + tr) * P.ncell + fbase;   // its x flux
-    const bool more_tracers = P.nt > 1;                    // the tracer sweeps below need the mass flux
+    const bool more_tracers = !Stash::on && P.nt > 1;      // the tracer sweeps below need the mass flux (LineStash: NT = 1, none follow)
     auto load_cell = [&](long long o, double &m, double &p, double (&qv)[NQ]) {
 #pragma unroll
       for (int n = 0; n < NQ; n++) qv[n] = uni(prim_in + (long long)(P_U + n) * P.prim_fs + o)[eu];
@@ -2246,7 +2290,11 @@ PAMA_D void flux_x_update_body(const Params &P, const double *__restrict__ prim_
         store_adv_u(P, prim_out, P_U + n, k, cu0 + (long long)cc * P.sx, eu, v * rrho, (l == 3) ? 0.0 : v * rrho);
         // the new rho*theta goes where the pressure belongs: pressure_tail_body turns it into the next stage's pressure
         // (a pow per cell, kept out of this register-critical loop)
-        if (l == 4) uniw(out_rt + o)[eu] = v;
+        // (LineStash: it stays in the lane's own slot of this cell until the epilogue behind the loop)
+        if (l == 4) {
+          if constexpr (Stash::on) stash.slot[(cc - c0) * XSTASH_LANES] = v;
+          else uniw(out_rt + o)[eu] = v;
+        }
       }
       // Tracer 0 (Dycore.h:525-550, :572-584, :162-221): finished here like the further tracers in x_tracer_sweep
       finish_tracer_cell<STAGE>(P, tr, prim_out, seed, mult, rows, k, j, cc, e, eu, cu0 + (long long)cc * P.sx, fbase + (long long)cc * P.sx,
@@ -2308,10 +2356,12 @@ PAMA_D void flux_x_update_body(const Params &P, const double *__restrict__ prim_
       for (int n = 0; n < NQ; n++) wq[n][4] = nq[n];
     }
   }
+  // nothing of the loop is live here: the pow per cell that the loop has no register for
+  if constexpr (Stash::on) xsweep_pressure_epilogue(P, prim_out, stash, k, cu0, eu, c0, c1);
 
   // ---------------- the other tracers (Dycore.h:367-385): inline here, or -- small ensembles, where a wavefront per line is
   // too little parallelism for a chain this long -- by awfl_xtr_kernel, one wavefront per (line, pair of tracers)
-  if (tracers_inline) {
+  if (!Stash::on && tracers_inline) {
     for (int i = 0; i < P.nt - 1; i += FLUX_NF) {          // water vapour went with the state pass
       const int fa[2] = {4 + further_tracer(P, i), 4 + further_tracer(P, i + 1)};
       if (i + 1 < P.nt - 1) x_tracer_sweep<2, STAGE, 1>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, line, e, c0, span, fa, dt_dyn, dt_stage, true, ruf_close);

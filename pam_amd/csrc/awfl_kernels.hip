@@ -250,7 +250,14 @@ __global__ void __launch_bounds__(256) awfl_update_kernel(Params P, EnsRange R, 
 }
 // Fused x-sweep + state update (flux_x_update_body): wave unit u -> (x line, member block, span of cells); the 64 lanes are
 // 64 consecutive members of ONE line, so every address is a wave-uniform base + member (scalar addressing).
-template <int STAGE, bool FOLD>
+// PRESSURE (NT = 1, spans of at most XSTASH_CELLS cells): the next stage's pressure inside this kernel (LineStash: no awfl_ptail_kernel
+// launch).  Dynamic LDS of XUPD_STASH_LDS bytes: a stash per wavefront, then the tables of pow_pos_fast, staged before any wavefront
+// may leave (a ragged member block), so that every wavefront reaches the one barrier.  2 workgroups x 67.5 KB fit a CU's 160 KB.
+__device__ __forceinline__ void stage_pow_tab(Params &P, PowTab *sh_tab);
+constexpr size_t XUPD_STASH_DOUBLES = (size_t)FLUX_WAVES * XSTASH_CELLS * XSTASH_LANES;
+constexpr size_t XUPD_STASH_LDS = XUPD_STASH_DOUBLES * sizeof(double) + sizeof(PowTab);
+static_assert(XSTASH_LANES == 64, "a stash slot per lane of a wavefront");
+template <int STAGE, bool FOLD, bool PRESSURE = false>
 __global__ void __launch_bounds__(FLUX_THREADS, 2) awfl_xupd_kernel(Params P, EnsRange R, const double *__restrict__ prim_in,
                                                                      const double *__restrict__ prim0,
                                                                      double *__restrict__ prim_out, double *__restrict__ fx,
@@ -258,6 +265,8 @@ __global__ void __launch_bounds__(FLUX_THREADS, 2) awfl_xupd_kernel(Params P, En
                                                                      const double *__restrict__ fz, double *__restrict__ seed,
                                                                      double *__restrict__ mult, FctRows rows, double dt_dyn,
                                                                      double dt_stage, int tracers_inline, int span, int nspan) {
+  extern __shared__ double xupd_lds[];
+  if constexpr (PRESSURE) stage_pow_tab(P, reinterpret_cast<PowTab *>(xupd_lds + XUPD_STASH_DOUBLES));
   fct_rows_resolve(rows);
   const int u = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * FLUX_WAVES + (threadIdx.x >> 6)));
   const SweepUnits U = sweep_units(P.nz, P.ny, R.ne, nspan, 1);
@@ -265,9 +274,17 @@ __global__ void __launch_bounds__(FLUX_THREADS, 2) awfl_xupd_kernel(Params P, En
   const int sp = U.span(w);
   const SweepUnits::Lane m = U.place(w.grp);
   const int el = m.blk * 64 + (int)(threadIdx.x & 63);
-  if (U.holds(m, el))
-    flux_x_update_body<STAGE, FOLD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span,
-                                    dt_dyn, dt_stage, tracers_inline != 0);
+  if constexpr (PRESSURE) {
+    LineStash stash;     // (threadIdx.x = wavefront * 64 + lane: the lane's slot of cell 0 inside its wavefront's stash)
+    stash.slot = (stash_ptr)(xupd_lds + (size_t)(threadIdx.x >> 6) * (XSTASH_CELLS * XSTASH_LANES) + (threadIdx.x & 63));
+    if (U.holds(m, el))
+      flux_x_update_body<STAGE, FOLD, LineStash>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span,
+                                                 dt_dyn, dt_stage, tracers_inline != 0, stash);
+  } else {
+    if (U.holds(m, el))
+      flux_x_update_body<STAGE, FOLD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span,
+                                      dt_dyn, dt_stage, tracers_inline != 0);
+  }
 }
 // x sweeps of tracers 1.. (x_tracer_sweep): wave unit u -> (x line, member block, span, group of G tracers).  PHASE 1 (the cells' FCT
 // multipliers; only for small ensembles -- otherwise it runs inline in awfl_xupd_kernel) and PHASE 2 (the cells' complete update)
@@ -1143,6 +1160,7 @@ struct pam_amd_awfl {
     int xt_w = 0, xt_tc = 0, xt_lpb = 0;   // tile geometry overrides (0 = automatic)
     int xshuf = 0;             // x tile kernels, exchange between neighbouring cells: 0 automatic, 1 through LDS, 2 wavefront shuffles
     int tail_fuse = 0;         // NT > 1: phase 2 + pressure pass + vapour fix-up as one launch: 0 automatic (on), 1 off, 2 on
+                               // NT = 1: the pressure pass inside the x-sweep (xsweep_pressure): 0 automatic, 1 off, 2 on
     int fold = 0;              // y differences of the state folded into the z sweep's output (P.yz_fold): 0 automatic, 1 off, 2 on
     int tile_pressure = 0;     // 0 automatic, 1 separate pressure pass, 2 inside the x tile kernel
     int tile_state_parts = 0;  // 0 automatic, 1 one lane does the whole state pass, 2 three parts
@@ -1515,10 +1533,21 @@ inline size_t xtile_lds_bytes(const XTileGeom &G, int fields) { return (size_t)f
 inline bool xtile_lds_fits(const XTileGeom &G) { return xtile_lds_bytes(G, XT_NS) <= 160 * 1024; }
 
 // what launch_xupd reports: its status and whether the stage's tail went out inside its last launch (no launch_tail then)
+// pressure_done: the x-sweep has made the next stage's pressure itself (launch_tail then launches the fix-up only)
 struct XupdResult {
-  int rc; bool tail_fused;
-  XupdResult(int rc_, bool tail_fused_ = false) : rc(rc_), tail_fused(tail_fused_) {}
+  int rc; bool tail_fused; bool pressure_done;
+  XupdResult(int rc_, bool tail_fused_ = false, bool pressure_done_ = false) : rc(rc_), tail_fused(tail_fused_), pressure_done(pressure_done_) {}
 };
+
+// NT = 1, member-lane sweeps: the pressure pass inside awfl_xupd_kernel<., ., true> for spans that fit its stash.  pam_amd_awfl_set_tail_fusion:
+// 1 never, 2 wherever supported, 0 automatic = wherever supported (measured on MI355X, profiles/r13_ab_c2.txt: C2 2.671 -> 2.734 G, the
+// slowest of five runs above the parent's fastest).  Flat lanes, tile kernels, longer spans and NT > 1 keep awfl_ptail_kernel.
+constexpr bool XSWEEP_PRESSURE_AUTO = true;
+bool xsweep_pressure(const pam_amd_awfl *h, int span) {
+  const Params &P = h->P;
+  if (P.nt != 1 || h->use.flat || h->use.xtile || P.flat_cells || (span < P.nx ? span : P.nx) > XSTASH_CELLS) return false;
+  return h->want.tail_fuse == 2 || (h->want.tail_fuse == 0 && XSWEEP_PRESSURE_AUTO);
+}
 
 // x direction as tile kernels: a lane per cell, the whole ensemble in one launch (small ensembles; launches the sweeps cannot fill the chip with)
 int launch_xupd_tiles(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStream_t s) {
@@ -1611,14 +1640,18 @@ XupdResult launch_xupd_sweeps(pam_amd_awfl *h, const StageArgs &a, EnsRange r, h
   if (!sweep_units(P.nz, P.ny, r.ne, nspan, npairs > 0 ? npairs : 1).fits()) return fail(PAM_AMD_EINVAL, "x-sweep launch: more than 2^30 wavefronts");
   if (r.e0 % 64) return fail(PAM_AMD_EINVAL, "x-sweep launch: member ranges of the fused stage start at multiples of 64 (a wavefront is one row of FCT flags)");
   const dim3 block(FLUX_THREADS);
+  const bool pressure = xsweep_pressure(h, span);
   {
     // (fold: the z sweep has left the y+z part of the state's divergence in flux_z: no y differences to load)
-    const auto kernel = by_stage(a.st, [&](auto S) { return P.yz_fold ? awfl_xupd_kernel<S(), true> : awfl_xupd_kernel<S(), false>; });
-    if ((rc = launch(h, "xupd", kernel, dim3((unsigned)U.workgroups(FLUX_WAVES)), block, 0, s, P, r, a.in, a.base, a.out, h->flux_x, h->flux_y, h->flux_z,
-                     h->seed, h->mult, fct_rows(h, r, true), a.dt_dyn, a.dt_stage, split ? 0 : 1, span, nspan)))
+    const auto kernel = by_stage(a.st, [&](auto S) {
+      return pressure ? (P.yz_fold ? awfl_xupd_kernel<S(), true, true> : awfl_xupd_kernel<S(), false, true>)
+                      : (P.yz_fold ? awfl_xupd_kernel<S(), true> : awfl_xupd_kernel<S(), false>);
+    });
+    if ((rc = launch(h, "xupd", kernel, dim3((unsigned)U.workgroups(FLUX_WAVES)), block, pressure ? XUPD_STASH_LDS : 0, s, P, r, a.in, a.base, a.out,
+                     h->flux_x, h->flux_y, h->flux_z, h->seed, h->mult, fct_rows(h, r, true), a.dt_dyn, a.dt_stage, split ? 0 : 1, span, nspan)))
       return rc;
   }
-  if (npairs == 0) return PAM_AMD_OK;
+  if (npairs == 0) return XupdResult(PAM_AMD_OK, false, pressure);
   // the tracer launches have npairs wavefronts per (line, member block, span): their lines are cut less (or not at all)
   // Further tracers per wavefront of these launches (0 = automatic; measured on MI355X, round 5, profiles/r05_ab_experiments.txt):
   //   phase 1 -- ONE: 83 instead of 119 registers (5 instead of 4 wavefronts per SIMD), and only the face mass flux is loaded twice:
@@ -1666,11 +1699,11 @@ XupdResult launch_xupd(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStrea
   return launch_xupd_sweeps(h, a, r, s, allow_tail_fusion);
 }
 
-// the pointwise tail of the fused stage: pressure pass, then the tracers' fix-up pass
-int launch_tail(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStream_t s) {
+// the pointwise tail of the fused stage: pressure pass (unless the x-sweep has made the pressure: pressure_done), then the tracers' fix-up pass
+int launch_tail(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStream_t s, bool pressure_done) {
   const Params &P = h->P;
   const bool in_tile = h->use.xtile && h->use.tile_pressure;      // (small ensembles: the x tile kernel has already made the pressure)
-  if (!in_tile)
+  if (!in_tile && !pressure_done)
     if (int rc = launch(h, "ptail", awfl_ptail_kernel, cell_grid(P, r, (P.nz + TAIL_LEVELS - 1) / TAIL_LEVELS), dim3(256), 0, s, P, r, a.out)) return rc;
   if (in_tile && P.nt > 1) return PAM_AMD_OK;                      // (the last slice of the phase-2 tile launch has done the fix-up)
   if (P.flat_cells)      // small ensembles: a lane per cell
@@ -2093,7 +2126,7 @@ int stage_fused(pam_amd_awfl *h, Chunk &c, hipStream_t cs, const StageArgs &a, b
     HIP_TRY(hipEventRecord(c.flux_done, cs));
     HIP_TRY(hipStreamWaitEvent(c.stream, c.flux_done, 0));
   }
-  if (!x.tail_fused && (rc = launch_tail(h, a, c.r, c.stream))) return rc;
+  if (!x.tail_fused && (rc = launch_tail(h, a, c.r, c.stream, x.pressure_done))) return rc;
   if (forked) HIP_TRY(hipEventRecord(c.upd_done, c.stream));
   return PAM_AMD_OK;
 }
@@ -2418,7 +2451,10 @@ int pam_amd_awfl_init(const pam_amd_awfl_config_t *cfg, pam_amd_awfl_t **out) {
       (const void *)awfl_xtr_tile_kernel<1, 1, false>, (const void *)awfl_xtr_tile_kernel<1, 2, false>,
       (const void *)awfl_xtr_tile_kernel<2, 1, false>, (const void *)awfl_xtr_tile_kernel<2, 2, false>,
       (const void *)awfl_xtr_tile_kernel<3, 1, false>, (const void *)awfl_xtr_tile_kernel<3, 2, false>,
-      (const void *)awfl_flux_tile_kernel<false>, (const void *)awfl_flux_tile_kernel<true>};
+      (const void *)awfl_flux_tile_kernel<false>, (const void *)awfl_flux_tile_kernel<true>,
+      // (the x-sweeps with the pressure inside: XUPD_STASH_LDS = 67.5 KB)
+      (const void *)awfl_xupd_kernel<1, false, true>, (const void *)awfl_xupd_kernel<2, false, true>, (const void *)awfl_xupd_kernel<3, false, true>,
+      (const void *)awfl_xupd_kernel<1, true, true>, (const void *)awfl_xupd_kernel<2, true, true>, (const void *)awfl_xupd_kernel<3, true, true>};
   for (const void *kernel : big_lds_kernels) INIT_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #undef INIT_TRY
   h->flux_lds_floor = 0;   // no residency cap by default
@@ -2869,7 +2905,7 @@ int pam_amd_awfl_debug_inject_mass_fault(pam_amd_awfl_t *h, int variable, int k,
 
 int pam_amd_awfl_set_tail_fusion(pam_amd_awfl_t *h, int mode) {
   if (!h) return fail(PAM_AMD_EINVAL, "null handle");
-  if (mode < 0 || mode > 2) return fail(PAM_AMD_EINVAL, "set_tail_fusion: 0 = automatic, 1 = three launches, 2 = one launch");
+  if (mode < 0 || mode > 2) return fail(PAM_AMD_EINVAL, "set_tail_fusion: 0 = automatic, 1 = separate launches, 2 = fused where supported");
   drop_graphs(h);
   h->want.tail_fuse = mode;
   return PAM_AMD_OK;

@@ -261,7 +261,9 @@ class Dycore:
         check(self._lib.pam_amd_awfl_debug_fail_next_capture(self._h, int(which)))
 
     def set_tail_fusion(self, mode="auto"):
-        """NT > 1, member-lane sweeps: tracer phase 2 + pressure pass + vapour fix-up as one launch ("on" / "auto") or three ("off"); same bits"""
+        """NT > 1, member-lane sweeps: tracer phase 2 + pressure pass + vapour fix-up as one launch ("on" / "auto") or three ("off");
+        NT = 1, member-lane sweeps in spans of at most 32 cells: the pressure pass inside the fused x-sweep ("on" / "auto") or as a launch
+        of its own ("off"); same bits"""
         check(self._lib.pam_amd_awfl_set_tail_fusion(self._h, {"auto": 0, "off": 1, "on": 2}[mode]))
 
     FOLD = {"auto": 0, "off": 1, "on": 2}

@@ -1,0 +1,99 @@
+"""GPU: the next stage's pressure formed inside the fused x-sweep (NT = 1, member-lane sweeps, spans of at most 32 cells;
+set_tail_fusion("on")) against the separate pressure pass (set_tail_fusion("off")) and against the three-kernel stage: bit for bit,
+because the epilogue behind the sweep loop is pressure_tail_body's arithmetic on the same doubles (awfl_device.h:
+xsweep_pressure_epilogue).  The kernel timers tell which launches a stage made."""
+import numpy as np
+import pytest
+
+from pam_amd import idealized as idz
+
+pytestmark = pytest.mark.gpu
+
+NZ = 4          # both boundary levels (density / pressure ghosts) and interior ones
+WHOLE = 64      # set_flux_span: lines stay whole (up to 64 cells)
+CASES = {
+    # name: (nens, nx, ny, span, chunks, mode_a, per_member_grid, limited_vapour, in_sweep)
+    # the shortest periodic line, one full member block, 2-D
+    "nx3_2d_64": (64, 3, 1, WHOLE, 1, True, False, False, True),
+    # a line that fills the stash exactly; a ragged last block (6 members: its other lanes leave after the barrier); mode B; own grids
+    "nx32_3d_70_perens_B": (70, 32, 5, WHOLE, 1, False, True, False, True),
+    # spans with a recomputed closing face, two member ranges (128 + 2), the limiter at work: the fix-up follows a stage without a pressure launch
+    "nx32_3d_130_span4_chunks2_limited": (130, 32, 5, 4, 2, True, False, True, True),
+    # 2-D, spans, mode B, limited
+    "nx32_2d_64_span4_limited_B": (64, 32, 1, 4, 1, False, True, True, True),
+    # an uncut line longer than the stash: the separate pass stays
+    "nx33_3d_130_fallback_B": (130, 33, 5, WHOLE, 2, False, False, False, False),
+}
+FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor")
+
+
+def _run(case, fused, tail):
+    import torch
+    from pam_amd import Dycore, PamCoupler
+    nens, nx, ny, span, chunks, mode_a, per_ens, limited, _ = CASES[case]
+    tr, consts = idz.TRACERS_NONE, idz.CONSTS_DEFAULT
+    zint = idz.stretched_interfaces(NZ, 6000.0)
+    xlen = nx * 500.0
+    ylen = ny * 500.0 if ny > 1 else xlen
+    f = idz.supercell_fields(nens, nx, ny, NZ, zint, consts=consts, tracers=tr, magnitude=0.5)
+    idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
+    if limited:
+        f["uvel"] -= 25.0
+        f["vvel"] += 7.0
+        idz.carve_dry_air(f, tr)
+    zi = np.asarray(zint)[:, None] * np.ones((1, nens))
+    if per_ens:
+        zi = zi * (1 + 0.01 * (np.arange(nens) % 16) + 1.0e-4 * (np.arange(nens) // 16))[None, :]
+    coupler = PamCoupler("cuda:0")
+    coupler.set_option("crm_dt", 2.0)
+    for k, v in consts.items():
+        coupler.set_option(k, v)
+    coupler.allocate_coupler_state(NZ, ny, nx, nens)
+    coupler.set_grid(xlen, ylen, zi)
+    for n, p, m in tr:
+        coupler.add_tracer(n, "", p, m)
+    dycore = Dycore()
+    dycore.init(coupler)
+    dycore.set_fused_stage(fused)
+    dycore.set_lane_mapping("member", "sweep")
+    dycore.set_flux_span(span)
+    dycore.set_ensemble_chunks(chunks)
+    dycore.set_tail_fusion(tail)
+    dycore.set_kernel_timing(True)
+    coupler.load_fields(f)
+    if not mode_a:
+        coupler.set_option("balance_hydrostasis_with_gravity", False)
+    dycore.declare_current_profile_as_hydrostatic(coupler)
+    ncyc = []
+    for crm_dt in (2.0, 0.7, 2.0):        # odd and even sub-step counts: both parities of the three-buffer rotation
+        coupler.set_option("crm_dt", crm_dt)
+        ncyc.append(dycore.timeStep(coupler))
+    torch.cuda.synchronize()
+    out = coupler.dump_fields()
+    out["water_vapor"] = out["tracers"][0]
+    launches = {k: dycore.get_kernel_timing(k)[1] for k in ("xupd", "ptail", "trfix", "update")}
+    if not fused:       # FCT multipliers of the last stage (complete only in the three-kernel stage)
+        out["mult"] = dycore.debug_buffer("mult").cpu().numpy()
+    dycore.finalize(coupler)
+    return ncyc, out, launches
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_in_sweep_pressure_equals_separate_pass_and_three_kernel_stage(case):
+    in_sweep = CASES[case][-1]
+    n3, three, l3 = _run(case, fused=False, tail="off")
+    n0, off, l0 = _run(case, fused=True, tail="off")
+    n1, on, l1 = _run(case, fused=True, tail="on")
+    assert n3 == n0 == n1
+    # which launches the stages made: the three-kernel stage none of the fused stage's; "off" a pressure pass per x-sweep; "on" none
+    # where the stash holds a span and one per x-sweep where it does not; the fix-up follows every fused stage either way
+    assert l3["update"] > 0 and l3["xupd"] == 0 and l3["ptail"] == 0
+    assert l0["xupd"] > 0 and l0["ptail"] == l0["xupd"] and l0["trfix"] == l0["xupd"]
+    assert l1["xupd"] == l0["xupd"] and l1["trfix"] == l0["trfix"]
+    assert l1["ptail"] == (0 if in_sweep else l1["xupd"])
+    for k in FIELDS:
+        assert np.isfinite(three[k]).all(), k
+        assert np.array_equal(off[k], three[k]), (k, np.abs(off[k] - three[k]).max())
+        assert np.array_equal(on[k], off[k]), (k, np.abs(on[k] - off[k]).max())
+    if CASES[case][-2]:      # a limited case is only worth something if the limiter acted (multipliers of the last three-kernel stage)
+        assert np.isfinite(three["mult"]).all() and (three["mult"] < 1.0).any() and (three["mult"] == 1.0).any()
