@@ -60,6 +60,7 @@
 #include "modules/radiation_aggregate.h"
 #include "modules/crm_feedback.h"
 #include "modules/column_diagnostics.h"
+#include "modules/flux_profiles.h"
 #include "vertical_interp.h"
 #include "physics/micro/kessler_amd/Microphysics.h"
 #include "physics/sgs/none/SGS.h"
@@ -307,7 +308,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
-//          [--hyperdiff TAU] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] <output.bin | ->
+//          [--hyperdiff TAU] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
 // out_freq, vcoords [, crm_nz, zlen, idealized, apply_sponge, initData].  What runs, in the reference's order:
@@ -424,6 +425,12 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              receives one JSON record (a line) per GCM step with the (nens) lists of diag_cldtot, diag_cldlow,
 //                              diag_cldmed, diag_cldhgh, diag_lwp, diag_pw and diag_precip_liq (Kessler has no ice), printed with %.17g;
 //                              nothing else of the run changes.
+//   --flux-profiles PATH       the CRM flux profiles (modules/flux_profiles.h): modules::flux_profiles_init at the start of every GCM
+//                              step, modules::flux_profiles after the last module of every CRM step with the clock's weight (so it
+//                              composes with --accelerate, --vt, --hyperdiff, --gcm-handoff, --column-diag and --radiation).  PATH receives
+//                              one JSON record (a line) per GCM step: gcm_step, crm_steps, nens, nz and "profiles", name -> nz rows of nens
+//                              values of prof_mcup, prof_mcdn, prof_mcuup, prof_mcudn, prof_cld, prof_flux_t, prof_flux_qt, prof_flux_u,
+//                              prof_flux_v and prof_tke, printed with %.17g; nothing else of the run changes.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
   bool vt = false, vt_u = false, hyperdiff = false, handoff = false;
@@ -432,7 +439,7 @@ struct YamlModules {
   std::string handoff_path;
   double tau = 0, bflx = 0, accel_factor = 0, accel_max_ttend = 5.0, vt_rate = 0, vt_limit = 0.05;
   int rad_nx = 0, rad_ny = 0;
-  std::string stats, edges, rad_path, diag, vt_path, column_diag;
+  std::string stats, edges, rad_path, diag, vt_path, column_diag, flux_profiles;
 };
 
 // one JSON number that Python's json module reads back exactly (NaN / Infinity for the non-finite)
@@ -573,6 +580,11 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       coldiag_out.open(mods.column_diag);
       if (!coldiag_out) endrun("cannot open the --column-diag file");
     }
+    std::ofstream fluxprof_out;
+    if (!mods.flux_profiles.empty()) {
+      fluxprof_out.open(mods.flux_profiles);
+      if (!fluxprof_out) endrun("cannot open the --flux-profiles file");
+    }
     std::ofstream vt_out;
     if (mods.vt) {
       coupler.set_option<bool>("crm_vt_u", mods.vt_u);
@@ -629,6 +641,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       }
       if (mods.handoff) coupler.run_module("rad_aggregate_init", modules::rad_aggregate_init);
       if (coldiag_out.is_open()) coupler.run_module("column_diagnostics_init", modules::column_diagnostics_init);
+      if (fluxprof_out.is_open()) coupler.run_module("flux_profiles_init", modules::flux_profiles_init);
       while (!clock.done() && !stop) {
         const bool accel = clock.accelerating();
         if (accel) coupler.run_module("msa_diagnose", modules::msa_diagnose);
@@ -654,6 +667,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (stats) coupler.run_module("time_average_accumulate", [&](pam::PamCoupler &c) { modules::time_average_accumulate(c, stat_names, weight); });
         if (mods.handoff) coupler.run_module("rad_aggregate", [&](pam::PamCoupler &c) { modules::rad_aggregate(c, weight); });
         if (coldiag_out.is_open()) coupler.run_module("column_diagnostics", [&](pam::PamCoupler &c) { modules::column_diagnostics(c, weight); });
+        if (fluxprof_out.is_open()) coupler.run_module("flux_profiles", [&](pam::PamCoupler &c) { modules::flux_profiles(c, weight); });
         if (mods.validate) dm.validate_all();
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         crm_steps++;
@@ -729,6 +743,21 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         o += "}}\n";
         coldiag_out << o << std::flush;
         if (!coldiag_out) endrun("cannot write the --column-diag file");
+      }
+      if (fluxprof_out.is_open()) {                                           // the GCM step's flux profiles
+        std::string o = "{\"gcm_step\": " + std::to_string(step_gcm) + ", \"crm_steps\": " + std::to_string(crm_steps_gcm) + ", \"nens\": " +
+                        std::to_string(nens) + ", \"nz\": " + std::to_string(crm_nz) + ", \"profiles\": {";
+        bool first = true;
+        for (const char *n : {"prof_mcup", "prof_mcdn", "prof_mcuup", "prof_mcudn", "prof_cld", "prof_flux_t", "prof_flux_qt", "prof_flux_u",
+                              "prof_flux_v", "prof_tke"}) {
+          if (!dm.entry_exists(n)) continue;
+          o += std::string(first ? "\"" : ", \"") + n + "\": ";
+          handoff_json_array(o, dm.get<real const, 2>(n).data(), {crm_nz, nens});
+          first = false;
+        }
+        o += "}}\n";
+        fluxprof_out << o << std::flush;
+        if (!fluxprof_out) endrun("cannot write the --flux-profiles file");
       }
       if (mods.handoff) {                                                     // the GCM step's aggregates and feedback
         coupler.run_module("compute_crm_feedback", modules::compute_crm_feedback);
@@ -927,10 +956,11 @@ int main(int argc, char **argv) {
         mods.handoff_path = argv[++b];
       }
       else if (o == "--column-diag" && b + 1 < argc - 1) mods.column_diag = argv[++b];
+      else if (o == "--flux-profiles" && b + 1 < argc - 1) mods.flux_profiles = argv[++b];
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
                "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] "
-               "[--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] <output.bin | ->");
+               "[--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->");
     }
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }

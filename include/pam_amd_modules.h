@@ -585,6 +585,40 @@ int pam_amd_column_diagnostics(int nens, int nx, int ny, int nz, const double *c
                                double cwp_threshold, double *const *out, double factor, void *stream);
 int pam_amd_column_diagnostics_debug_mapping(int mapping);
 
+/* The CRM flux profiles: the convective mass fluxes by conditional sampling (SAM / E3SM-MMF's crm_output fields mcup, mcdn, mcuup,
+ * mcudn), the cloud fraction profile cld, the resolved vertical fluxes of heat, total water and horizontal momentum (their flux_qt, flux_u,
+ * flux_v, plus a heat flux) and the resolved turbulence kinetic energy, per level and member.  SAM and E3SM-MMF sum them with one atomicAdd
+ * per cell and quantity in several passes; here one launch reads the eight fields once.  Not part of the reference tree; the contract is
+ * this project's and is restated in numpy in tests/fluxprof_ref.py, which the kernel matches bit for bit.
+ *   fields[8]   HOST array of DEVICE pointers (nz,ny,nx,nens), members fastest: density_dry, water_vapor, cloud or NULL, ice or NULL, temp,
+ *               uvel, vvel, wvel (the dycore is an A-grid: wvel is cell-centred)
+ *   out[10]     HOST array of DEVICE pointers (nz,nens), in/out: mcup, mcdn, mcuup, mcudn, cld, flux_t, flux_qt, flux_u, flux_v, tke
+ * Per cell c = j nx + i of level k and member e, every operation rounded on its own, no fma: rho = rho_d + rho_v; m = rho w; wat = vapour +
+ * cloud + ice, left to right, an absent species skipped (mean-state acceleration's total water above); q = wat / rho, one true division;
+ * cond = rho_c + rho_i (an absent species skipped); the cell is cloudy where cond > qc_threshold rho (the product rounded; a NaN on either
+ * side: not cloudy; with both condensates absent no cell is cloudy and cond is not formed) and up where w > 0 (a NaN, 0.0 and -0.0: not up).
+ * Sampled sums, M the 16-slot level mean of mean-state acceleration above (cell c in slot c % 16; a slot adds x r over its cells in
+ * ascending c from 0.0, r = 1 / (ny nx), the product rounded first; the 16 slot sums are added in ascending slot order from 0.0).  A slot
+ * keeps one accumulator per class and a cell adds to the accumulator of its own class only: MCUP adds m r over the cloudy and up cells,
+ * MCDN over the cloudy and not-up cells, MCUUP over the not-cloudy and up cells, MCUDN over the not-cloudy and not-up cells; CLD adds
+ * 1.0 r for every cloudy cell.
+ * Shifted moments, variance transport's one-pass form above: c_x is x at the level's first cell (c = 0) for x in m, temp, q, uvel, vvel,
+ * wvel; d_x = x - c_x; A_x = M(d_x), six of them; B_mx = M(d_m d_x) for x in temp, q, uvel, vvel; B_xx = M(d_x d_x) for x in uvel, vvel,
+ * wvel; the product d d is rounded, then multiplied by r and rounded, then added.
+ * Finish, once per (k,e): flux_x = B_mx - A_m A_x (A A rounded, no fma); var_x = B_xx - A_x A_x as variance transport forms it (a negative
+ * value becomes 0.0, a NaN stays); tke = 0.5 * ((var_u + var_v) + var_w).  A level on which every input is constant in a member gives all
+ * four fluxes and tke exactly +0.0.
+ * Accumulate: out_x(k,e) = out_x(k,e) + value * factor, the product rounded, then the add, by the one thread that owns the element; factor
+ * is time_average_accumulate's weight.  The same bits from run to run and for any split of the members over calls.
+ * Absent parts: out[0], out[1] and out[4] (mcup, mcdn, cld) must be NULL exactly where both condensates are absent; the other seven outputs
+ * are always required.  Nothing absent is read, computed or written.
+ * One launch on `stream`, no synchronisation, no workspace, no floating-point atomics, every element offset 64 bits wide.
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: nens / nx / ny / nz < 1 (ny nx beyond 2^31 - 1, nz beyond
+ * 65535); a NULL table; a NULL density_dry, water_vapor, temp, uvel, vvel or wvel; any violation of the NULL-ness rules; qc_threshold
+ * negative or not finite; factor not finite; an output that overlaps an input or another output.  No value in a field is ever refused. */
+int pam_amd_flux_profiles(int nens, int nx, int ny, int nz, const double *const *fields, double qc_threshold, double *const *out,
+                          double factor, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

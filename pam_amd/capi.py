@@ -194,6 +194,7 @@ MODULE_SYMBOLS = {
     "pam_amd_column_diagnostics": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_double] * 5
                                    + [C.POINTER(C.c_void_p), C.c_double, C.c_void_p]),
     "pam_amd_column_diagnostics_debug_mapping": (C.c_int, [C.c_int]),
+    "pam_amd_flux_profiles": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_void_p), C.c_double, C.POINTER(C.c_void_p), C.c_double, C.c_void_p]),
 }
 
 

@@ -3761,3 +3761,88 @@ extern "C" int pam_amd_column_diagnostics(int nens, int nx, int ny, int nz, cons
   }
   return stats_launch_check(who);
 }
+
+// ------------------------------------------------------------------------------------------------
+// The CRM flux profiles: the convective mass fluxes by conditional sampling (mcup, mcdn, mcuup, mcudn), the cloud fraction profile, the
+// resolved vertical fluxes of heat, total water and horizontal momentum and the resolved turbulence kinetic energy per (level, member)
+// (SAM / E3SM-MMF's crm_output, summed there with one atomicAdd per cell and quantity in several passes).  Not in the reference tree; the
+// contract is in include/pam_amd_modules.h and DESIGN.md section 8, its arithmetic in fluxprof_device.h.  ONE launch reads the eight fields
+// once; launch shape, slot order and LDS rows are those of mean-state acceleration and variance transport above.  No scratch, no workspace,
+// no floating-point atomics; every element offset is 64 bits wide.
+#include "fluxprof_device.h"
+
+namespace {
+namespace fp = pama::fluxprof;
+struct FpFields { const double *p[fp::NF]; };
+struct FpOut { double *p[fp::NO]; };
+
+// ONE sweep over up to eight fields -> the 18 slot sums of every (level, member), shifted by the level's first cell, in six rounds of
+// three through slot_reduce: 24 KB of LDS, as vt_stats_kernel.  grid (member blocks, levels), block (members, 16 slots)
+__global__ void __launch_bounds__(64 * MOD_NS) flux_profiles_kernel(int nens, int ncol, FpFields F, double qc_threshold, FpOut O, double factor) {
+  static_assert(fp::NSUM % 3 == 0, "rounds of three");
+  __shared__ double red[3 * MOD_NS * 64];
+  const int ME = blockDim.x, slot = threadIdx.y;
+  const int e0 = (int)blockIdx.x * ME + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1, k = (int)blockIdx.y;
+  const long long base = (long long)k * ncol * nens + e;
+  const double *f[fp::NF];
+#pragma unroll
+  for (int i = 0; i < fp::NF; i++) f[i] = F.p[i] ? F.p[i] + base : nullptr;
+  double c[fp::NX], s[fp::NSUM];
+#pragma unroll
+  for (int i = 0; i < fp::NSUM; i++) s[i] = 0.0;
+  if (ok) {
+    fp::first_cell(f, c);
+    fp::slot_walk<fp::WALK_UNROLL>(f, (long long)nens, ncol, slot, qc_threshold, c, s);
+  }
+#pragma unroll
+  for (int g = 0; g < fp::NSUM; g += 3) {
+    double t[3] = {s[g], s[g + 1], s[g + 2]};
+    slot_reduce<3>(t, red);
+    s[g] = t[0]; s[g + 1] = t[1]; s[g + 2] = t[2];
+  }
+  if (slot != 0 || !ok) return;
+  double val[fp::NO];
+  fp::finish(s, val);
+  const long long t = (long long)k * nens + e;
+#pragma unroll
+  for (int q = 0; q < fp::NO; q++)
+    if (O.p[q]) O.p[q][t] = fp::accumulate(O.p[q][t], val[q], factor);
+}
+}  // namespace
+
+extern "C" int pam_amd_flux_profiles(int nens, int nx, int ny, int nz, const double *const *fields, double qc_threshold, double *const *out,
+                                     double factor, void *stream) {
+  const char *who = "flux_profiles";
+  if (int rc = rad_check_sizes(who, nens, nx, ny, nz)) return rc;
+  if (!fields || !out) return rad_error(who, "null fields or out");
+  for (int i = 0; i < fp::NF; i++)
+    if (i != fp::F_CLOUD && i != fp::F_ICE && !fields[i])
+      return rad_error(who, "null density_dry, water_vapor, temp, uvel, vvel or wvel pointer");
+  const bool has_cond = fields[fp::F_CLOUD] != nullptr || fields[fp::F_ICE] != nullptr;
+  for (int q = 0; q < fp::NO; q++) {
+    const bool sampled = q == fp::O_MCUP || q == fp::O_MCDN || q == fp::O_CLD;
+    if (sampled && (out[q] != nullptr) != has_cond)
+      return rad_error(who, "mcup, mcdn and cld must all be given where a condensate is, and none of them where neither is");
+    if (!sampled && !out[q]) return rad_error(who, "null mcuup, mcudn, flux_t, flux_qt, flux_u, flux_v or tke pointer");
+  }
+  if (!(qc_threshold >= 0) || !std::isfinite(qc_threshold)) return rad_error(who, "qc_threshold must be finite and >= 0");
+  if (!std::isfinite(factor)) return rad_error(who, "factor must be finite");
+  const long long cells = (long long)nz * ny * nx * nens, cols = (long long)nz * nens;
+  std::vector<RadSpan> spans;
+  for (int i = 0; i < fp::NF; i++)
+    if (fields[i]) spans.push_back({fields[i], cells, false});
+  for (int q = 0; q < fp::NO; q++)
+    if (out[q]) spans.push_back({out[q], cols, true});
+  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  FpFields F;
+  FpOut O;
+  for (int i = 0; i < fp::NF; i++) F.p[i] = fields[i];
+  for (int q = 0; q < fp::NO; q++) O.p[q] = out[q];
+  dim3 grid, block;
+  msa_launch_shape(nens, nz, grid, block);
+  hipLaunchKernelGGL(flux_profiles_kernel, grid, block, 0, (hipStream_t)stream, nens, nx * ny, F, qc_threshold, O, factor);
+  return stats_launch_check(who);
+}

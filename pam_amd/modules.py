@@ -893,3 +893,91 @@ def column_diagnostics(coupler, weight=1):
                                                      dm.get("vertical_interface_height", readonly=True).data_ptr(), _msa_table(precip),
                                                      R_d, R_v, p_low, p_high, threshold, _msa_table(out), factor,
                                                      torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+# ---- the CRM flux profiles: the convective mass fluxes by conditional sampling (SAM / E3SM-MMF's mcup, mcdn, mcuup, mcudn), the cloud
+# fraction profile, the resolved vertical fluxes of heat, total water and horizontal momentum and the resolved turbulence kinetic energy.
+# Not part of the reference tree: the contract is this project's (include/pam_amd_modules.h; numpy restatement:
+# tests/fluxprof_ref.py)
+FLUX_PROFILES = ("prof_mcup", "prof_mcdn", "prof_mcuup", "prof_mcudn", "prof_cld", "prof_flux_t", "prof_flux_qt", "prof_flux_u", "prof_flux_v",
+                 "prof_tke")
+FLUX_PROFILES_DEFAULTS = (("crm_prof_qc_threshold", 1.0e-5),)
+
+
+def _flux_profiles_names(coupler):
+    """-> (nens, nz, ny, nx), (cloud, ice) and the ten outputs' names in the order of the C ABI, None where the microphysics lacks the
+    inputs (no condensate: no prof_mcup, prof_mcdn, prof_cld)"""
+    from .coupler import endrun
+    nens, nz, ny, nx = coupler.get_nens(), coupler.get_nz(), coupler.get_ny(), coupler.get_nx()
+    if min(nens, nz, ny, nx) < 1:
+        endrun("ERROR: flux_profiles: the coupler state is not allocated")
+    cloud, ice = _handoff_condensate(coupler, "flux_profiles")
+    cloudy = cloud is not None or ice is not None
+    return (nens, nz, ny, nx), (cloud, ice), [n if (cloudy or n not in ("prof_mcup", "prof_mcdn", "prof_cld")) else None for n in FLUX_PROFILES]
+
+
+def flux_profiles_init(coupler):
+    """First in every GCM step: registers "prof_mcup", "prof_mcdn", "prof_mcuup", "prof_mcudn", "prof_cld", "prof_flux_t", "prof_flux_qt",
+    "prof_flux_u", "prof_flux_v" and "prof_tke" (nz,nens) on first use -- only those whose inputs the microphysics (option "micro") has:
+    no prof_mcup, prof_mcdn and prof_cld without a condensate -- and zeroes them.  Sets the option "crm_prof_qc_threshold" = 1e-5 where it
+    is unset."""
+    from .coupler import endrun
+    (nens, nz, _, _), _, names = _flux_profiles_names(coupler)
+    dm = coupler.get_data_manager_device_readwrite()
+    names = [n for n in names if n is not None]
+    for n in names:
+        if dm.entry_exists(n) and dm.get_shape(n) != [nz, nens]:
+            endrun("ERROR: flux_profiles: %s exists with a shape other than (nz,nens)" % n)
+    for opt, value in FLUX_PROFILES_DEFAULTS:
+        if not coupler.option_exists(opt):
+            coupler.set_option(opt, value)
+    for n in names:
+        if not dm.entry_exists(n):
+            dm.register_and_allocate(n, "CRM flux profile, averaged over the columns and the GCM step", (nz, nens), ("z", "nens"))
+    out = [dm.get(n) for n in names]
+    with torch.cuda.device(coupler.device):
+        check(capi.load().pam_amd_time_average_zero(len(out), _sizes([[nz, nens]] * len(out)), _ptr_table(out),
+                                                    torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+def flux_profiles(coupler, weight=1):
+    """After the last module of every CRM step: prof_x += value * (crm_dt / gcm_physics_dt * weight) with, per level and member, the mass
+    flux rho w averaged over the CRM columns of each class (cloudy where the condensate exceeds crm_prof_qc_threshold x rho, up where
+    w > 0), the cloudy fraction, the resolved fluxes of temp, total water, uvel and vvel and the resolved turbulence kinetic energy.  The
+    factor is time_average_accumulate's, so weight takes MsaClock's step weight.  Every misuse raises before the launch."""
+    import math
+    from .coupler import endrun
+    (nens, nz, ny, nx), (cloud, ice), names = _flux_profiles_names(coupler)
+    dm = coupler.get_data_manager_device_readwrite()
+    if not dm.entry_exists("prof_tke"):
+        endrun("ERROR: prof_tke does not exist: call flux_profiles_init first")
+    for opt, _ in FLUX_PROFILES_DEFAULTS:
+        if not coupler.option_exists(opt):
+            endrun("ERROR: flux_profiles: option %s is not set" % opt)
+    threshold = float(coupler.get_option("crm_prof_qc_threshold"))
+    if not (threshold >= 0 and math.isfinite(threshold)):
+        endrun("ERROR: flux_profiles: crm_prof_qc_threshold must be finite and >= 0")
+    crm_dt = float(coupler.get_option("crm_dt"))
+    gcm_dt = float(coupler.get_option("gcm_physics_dt"))
+    if not gcm_dt > 0:
+        endrun("ERROR: flux_profiles: gcm_physics_dt must be positive")
+    factor = crm_dt / gcm_dt * float(weight)
+    if not math.isfinite(factor):
+        endrun("ERROR: flux_profiles: crm_dt / gcm_physics_dt x weight is not finite")
+    for n in FLUX_PROFILES:
+        if n not in names and dm.entry_exists(n):
+            endrun("ERROR: flux_profiles: %s exists, but this microphysics has no condensate: it changed since flux_profiles_init" % n)
+    for n in names:
+        if n is None:
+            continue
+        if not dm.entry_exists(n):
+            endrun("ERROR: %s does not exist: call flux_profiles_init first" % n)
+        if dm.get_shape(n) != [nz, nens]:
+            endrun("ERROR: flux_profiles: %s is %s, not (nz,nens)" % (n, dm.get_shape(n)))
+    fields = [dm.get("density_dry", readonly=True), dm.get("water_vapor", readonly=True),
+              dm.get(cloud, readonly=True) if cloud else None, dm.get(ice, readonly=True) if ice else None,
+              dm.get("temp", readonly=True), dm.get("uvel", readonly=True), dm.get("vvel", readonly=True), dm.get("wvel", readonly=True)]
+    out = [dm.get(n) if n else None for n in names]
+    with torch.cuda.device(coupler.device):
+        check(capi.load().pam_amd_flux_profiles(nens, nx, ny, nz, _msa_table(fields), threshold, _msa_table(out), factor,
+                                                torch.cuda.current_stream(coupler.device).cuda_stream))

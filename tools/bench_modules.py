@@ -16,6 +16,8 @@ with 8192 members, beside msa_apply and time_average_accumulate of the same run;
 and the CRM feedback, beside msa_diagnose, time_average_accumulate and radiation_forced of the same run;
 --only coldiag: the CRM column diagnostics on P3's field set at the C2 grid and at C4's 32x1x60 grid with 8192 members, beside the
 radiation aggregate at the 1x1 rad grid and msa_diagnose of the same run;
+--only fluxprof: the CRM flux profiles on P3's field set at the C2 grid and at C4's 32x1x60 grid with 8192 members, beside vt_diagnose
+and msa_diagnose of the same run;
 --only msa: mean-state acceleration's diagnose, tendencies and apply (with and without the winds), beside horizontal_average and
 time_average_accumulate of the same run)"""
 import json
@@ -1130,8 +1132,95 @@ def coldiag_timing(dev, warmup=3, n=11):
     return out
 
 
+def fluxprof_timing(dev, warmup=3, n=11, reps=3):
+    """The CRM flux profiles on the P3 field set (cloud water and ice present: all eight fields are read, all ten profiles written):
+    pam_amd_flux_profiles at the C2 grid and at C4's 32x1x60 grid with 8192 members, 3 warm-up calls and the median of 11 event-timed
+    calls each, three repetitions (the row is the median repetition, `reps_ms` has all three).  Algorithmic bytes: 8 B per cell and
+    input field (eight) plus 16 B per output element (ten (nz,nens) arrays read and written).  The yardsticks of the same run:
+    vt_diagnose (the same launch shape over five fields, no division) and msa_diagnose (six fields)."""
+    from pam_amd import PamCoupler, capi, modules
+    from pam_amd import idealized as idz
+    from pam_amd.capi import check
+    lib = capi.load()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def timed(fn):
+        meds = []
+        for _ in range(reps):
+            for _ in range(warmup):
+                fn()
+            ts = []
+            for _ in range(n):
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ts.append(e0.elapsed_time(e1))
+            meds.append(sorted(ts)[len(ts) // 2])
+        return meds
+
+    def row(meds, nbytes):
+        t = sorted(meds)[len(meds) // 2]
+        frac = [nbytes / m / 1e6 / bench.HBM_PEAK_GBS for m in meds]
+        return {"ms": t, "reps_ms": meds, "bytes": nbytes, "GBps": nbytes / t / 1e6, "hbm_frac": nbytes / t / 1e6 / bench.HBM_PEAK_GBS,
+                "hbm_frac_spread": max(frac) - min(frac)}
+
+    def grid(nens, nx, ny, nz, label, out):
+        c = PamCoupler(dev)
+        c.set_option("crm_dt", 20.0)
+        c.set_option("gcm_physics_dt", 900.0)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+        for t in ("water_vapor", "cloud_water", "ice"):
+            c.add_tracer(t, "", True, True)
+        c.set_option("micro", "p3")
+        c.set_option("crm_accel_factor", 2.0)
+        c.set_option("crm_vt_u", True)
+        dm = c.get_data_manager_device_readwrite()
+        gen = torch.Generator(device=dev).manual_seed(0)
+        # a troposphere with condensate in a third of the cells and vertical velocities of both signs
+        k = torch.arange(nz, dtype=torch.float64, device=dev)[:, None, None, None]
+        for name, scale in (("temp", 290.0 - 1.2 * k), ("density_dry", 1.2 * torch.exp(-k / 25.0)), ("water_vapor", 1.0e-2 * torch.exp(-k / 10.0)),
+                            ("uvel", 10.0), ("vvel", 10.0)):
+            t = dm.get(name)
+            t.copy_((torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * 0.1 + 0.95) * scale)
+        t = dm.get("wvel")
+        t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * 2.0 - 1.0)
+        for name, scale in (("cloud_water", 1.0e-4), ("ice", 3.0e-5)):
+            t = dm.get(name)
+            t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * scale)
+            t.mul_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) < 1.0 / 3.0)
+        cells, cols = nens * nx * ny * nz, nens * nz
+        modules.flux_profiles_init(c)
+        out["flux_profiles" + label] = row(timed(lambda: modules.flux_profiles(c)), 8 * cells * 8.0 + 10 * cols * 16.0)
+        assert all(bool(torch.isfinite(dm.get(name, readonly=True)).all()) for name in modules.FLUX_PROFILES)
+        modules.msa_init(c)
+        modules.vt_init(c)
+        mfields, msave, _, _ = modules._msa_arrays(c)
+        MF, MS = modules._msa_table(mfields), modules._msa_table(msave)
+        out["msa_diagnose" + label] = row(timed(lambda: check(lib.pam_amd_msa_diagnose(nens, nx, ny, nz, MF, MS, stream))), 6 * cells * 8.0)
+        fields, tb, _ = modules._vt_arrays(c)
+        F, TM, TV = modules._msa_table(fields), modules._msa_table(tb["mean"]), modules._msa_table(tb["var"])
+        out["vt_diagnose" + label] = row(timed(lambda: check(lib.pam_amd_vt_diagnose(nens, nx, ny, nz, F, 1, TM, TV, stream))), 5 * cells * 8.0)
+        for y in ("vt_diagnose", "msa_diagnose"):
+            out["flux_profiles%s_vs_%s_frac" % (label, y)] = out["flux_profiles" + label]["hbm_frac"] / out[y + label]["hbm_frac"]
+        del c, dm, mfields, msave, fields, tb
+        torch.cuda.empty_cache()
+
+    out = {"fluxprof_grid": "1024 x 32x32x60 (C2) and 8192 x 32x1x60 (C4)",
+           "fluxprof_method": "%d warm-up calls, median of %d event-timed calls, %d repetitions" % (warmup, n, reps)}
+    grid(1024, 32, 32, 60, "", out)
+    grid(8192, 32, 1, 60, "_c4", out)
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "fluxprof"]:
+        print(json.dumps(fluxprof_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "coldiag"]:
         print(json.dumps(coldiag_timing(dev)))
         sys.exit(0)
