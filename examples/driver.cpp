@@ -64,6 +64,9 @@
 #include "vertical_interp.h"
 #include "physics/micro/kessler_amd/Microphysics.h"
 #include "physics/sgs/none/SGS.h"
+#define PAM_SGS_CLASS SGSSmagorinsky      // the driver holds both SGS classes and picks at run time (--sgs-smag)
+#include "physics/sgs/smag_amd/SGS.h"
+#undef PAM_SGS_CLASS
 #include "physics/radiation/forced_amd/radiation.h"
 
 #include <map>
@@ -308,7 +311,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
-//          [--hyperdiff TAU] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->
+//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
 // out_freq, vcoords [, crm_nz, zlen, idealized, apply_sponge, initData].  What runs, in the reference's order:
@@ -406,6 +409,10 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //   --hyperdiff TAU            horizontal hyperdiffusion (modules/hyperdiffusion.h): modules::hyperdiffusion_init(coupler, TAU) once, then
 //                              modules::hyperdiffusion every CRM step after the sponge layer and the surface friction and before the
 //                              physics; composes with --accelerate and --vt
+//   --sgs-smag CS PRANDTL      the native Smagorinsky SGS closure (physics/sgs/smag_amd/SGS.h) in the SGS slot of the CRM loop: its init in
+//                              place of the none class's, its timeStep every CRM step after the sponge layer, the surface friction and the
+//                              hyperdiffusion and before the microphysics.  With --surface-friction the fluxes that module computes are
+//                              the lower boundary condition of uvel and vvel; composes with every other flag
 //   --vt RATE PATH [--vt-u] [--vt-limit L]   CRM variance transport (modules/variance_transport.h): modules::vt_init at the start of every GCM
 //                              step; there is no GCM here, so vt_tend_x = RATE vt_var_start_x (a relative growth rate per second) for
 //                              that GCM step; modules::vt_apply_forcing LAST in every CRM step, after the clock has advanced, with dt =
@@ -433,8 +440,8 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              prof_flux_v and prof_tke, printed with %.17g; nothing else of the run changes.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  bool vt = false, vt_u = false, hyperdiff = false, handoff = false;
-  double hyperdiff_tau = 0;
+  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false;
+  double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0;
   int handoff_rad_nx = 0, handoff_rad_ny = 0;
   std::string handoff_path;
   double tau = 0, bflx = 0, accel_factor = 0, accel_max_ttend = 5.0, vt_rate = 0, vt_limit = 0.05;
@@ -540,9 +547,14 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     Dycore dycore;
     Microphysics micro;
     SGS sgs;
+    SGSSmagorinsky sgs_smag;
     Radiation rad;
     micro.init(coupler);                                                     // driver.cpp:189
-    sgs.init(coupler);                                                       // driver.cpp:190 (the reference's CI build: SHOC with P3; their numerics are out of scope, their coupling layers are physics/sgs/shoc_amd and physics/micro/p3_amd)
+    if (mods.sgs_smag) {                                                     // --sgs-smag: the native closure in the SGS slot
+      coupler.set_option<real>("sgs_smag_cs", mods.sgs_cs);
+      coupler.set_option<real>("sgs_smag_prandtl", mods.sgs_prandtl);
+      sgs_smag.init(coupler);
+    } else sgs.init(coupler);                                                // driver.cpp:190 (the reference's CI build: SHOC with P3; their numerics are out of scope, their coupling layers are physics/sgs/shoc_amd and physics/micro/p3_amd)
     dycore.init(coupler);                                                    // driver.cpp:191
     if (mods.radiation) {
       coupler.set_option<int>("rad_nx", mods.rad_nx);
@@ -556,7 +568,8 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       if (!rin || rin.peek() != std::ifstream::traits_type::eof()) endrun("the --radiation file is not (nz,rad_ny,rad_nx,nens) fp64");
       if (hipMemcpy(tend.data(), h.data(), h.size() * sizeof(real), hipMemcpyHostToDevice) != hipSuccess) endrun("memcpy");
     }
-    std::printf("Dycore: %s\nMicro : %s\nSGS   : none (SHOC is out of scope)\n\n", dycore.dycore_name(), micro.micro_name().c_str());   // driver.cpp:203-205
+    std::printf("Dycore: %s\nMicro : %s\nSGS   : %s\n\n", dycore.dycore_name(), micro.micro_name().c_str(),
+                mods.sgs_smag ? sgs_smag.sgs_name().c_str() : "none (SHOC is out of scope)");   // driver.cpp:203-205
     std::printf("crm_nx:   %d\ncrm_ny:   %d\ncrm_nz:   %d\nxlen (m): %g\nylen (m): %g\n", crm_nx, crm_ny, crm_nz, xlen, ylen);
     if (apply_gcm_forcing) std::printf("apply_gcm_forcing: not run (modules::gcm_forcing works on P3's tracer set; P3 is out of scope)\n");
     if (!idealized) initialize_from_supercell_column(zint, coupler);        // driver.cpp:220-222
@@ -656,6 +669,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (apply_sponge && !dbg.no_sponge) coupler.run_module("sponge_layer", modules::sponge_layer);         // driver.cpp:249-251
         if (mods.surface_friction) coupler.run_module("surface_friction", modules::compute_surface_friction);
         if (mods.hyperdiff) coupler.run_module("hyperdiffusion", [](pam::PamCoupler &c) { modules::hyperdiffusion(c); });
+        if (mods.sgs_smag) coupler.run_module("sgs", [&](pam::PamCoupler &c) { sgs_smag.timeStep(c); });
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         if (!dbg.no_micro) coupler.run_module("micro", [&](pam::PamCoupler &c) { micro.timeStep(c); });         // driver.cpp:253
         if (mods.sat_adjust) coupler.run_module("saturation_adjustment", modules::saturation_adjustment);
@@ -846,7 +860,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     if (hipDeviceSynchronize() != hipSuccess) endrun("device error");
     if (sf_in) (void)hipFree(sf_in);
     std::printf("Simulation Time: %g\n", etime_gcm);
-    if (mods.surface_friction) {                                             // the fluxes SHOC would read (not consumed here)
+    if (mods.surface_friction) {                                             // the fluxes an SGS scheme reads (--sgs-smag consumes them)
       const size_t n2 = (size_t)crm_ny * crm_nx * nens;
       std::vector<real> fu(n2), fv(n2), z0(nens);
       if (hipMemcpy(fu.data(), dm.get<real const, 3>("sfc_mom_flx_u").data(), n2 * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess ||
@@ -889,6 +903,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
 #ifdef PAM_FUNCTION_TIMERS
     pam::function_timers::print();
 #endif
+    if (mods.sgs_smag) std::printf("{\"sgs_smag_cs\": %.17g, \"sgs_smag_prandtl\": %.17g}\n", mods.sgs_cs, mods.sgs_prandtl);
     if (mods.hyperdiff) std::printf("{\"hyperdiff_timescale\": %.17g}\n", mods.hyperdiff_tau);
     if (mods.accelerate)
       std::printf("{\"accel_factor\": %.9g, \"accel_uv\": %s, \"accel_max_ttend\": %.9g, \"accelerated_steps\": %d, \"ceased_gcm_steps\": %d}\n",
@@ -949,6 +964,7 @@ int main(int argc, char **argv) {
       else if (o == "--vt-u") mods.vt_u = true;
       else if (o == "--vt-limit" && b + 1 < argc - 1) mods.vt_limit = std::atof(argv[++b]);
       else if (o == "--hyperdiff" && b + 1 < argc - 1) { mods.hyperdiff = true; mods.hyperdiff_tau = std::atof(argv[++b]); }
+      else if (o == "--sgs-smag" && b + 2 < argc - 1) { mods.sgs_smag = true; mods.sgs_cs = std::atof(argv[++b]); mods.sgs_prandtl = std::atof(argv[++b]); }
       else if (o == "--gcm-handoff" && b + 3 < argc - 1) {
         mods.handoff = true;
         mods.handoff_rad_nx = std::atoi(argv[++b]);
@@ -959,7 +975,7 @@ int main(int argc, char **argv) {
       else if (o == "--flux-profiles" && b + 1 < argc - 1) mods.flux_profiles = argv[++b];
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] "
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] "
                "[--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->");
     }
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);

@@ -619,6 +619,66 @@ int pam_amd_column_diagnostics_debug_mapping(int mapping);
 int pam_amd_flux_profiles(int nens, int nx, int ny, int nz, const double *const *fields, double qc_threshold, double *const *out,
                           double factor, void *stream);
 
+/* The native SGS closure: a first-order Smagorinsky-Lilly scheme with an implicit vertical solve, the turbulence closure that needs no
+ * external library (as Kessler is the microphysics that needs none).  A column scheme, as SHOC is in PAM: at CRM grids the horizontal SGS
+ * fluxes are about (dz/dx)^2 of the vertical ones, and horizontal scale-selective mixing is pam_amd_hyperdiffusion's job.  It consumes the
+ * surface momentum fluxes of pam_amd_surface_friction_compute.  Not part of the reference tree; the contract is this project's (DESIGN.md
+ * section 8) and is restated in numpy in tests/sgs_ref.py, which the kernels match bit for bit.
+ * Fields are (nz,ny,nx,nens), members fastest, x and y periodic, every variable cell-centred.  zint (nz+1,nens) and zmid (nz,nens) are the
+ * coupler's vertical_interface_height and vertical_midpoint_height; dz(k) = zint(k+1) - zint(k), dzf(k+1/2) = zmid(k+1) - zmid(k).
+ * rho = rho_d + rho_v (density_dry + water_vapor) as the fields are at entry.  Every operation is rounded on its own, no fma; every
+ * division is a true IEEE division and the root the IEEE root; no pow, cbrt or exp.
+ *
+ * pam_amd_sgs_smag_coefficients   tk, tkh (nz,ny,nx,nens) from uvel, vvel, wvel, temp, rho_d, rho_v.  One launch; writes only tk and tkh.
+ *   d/dx f = (f[i+1] - f[i-1]) / (2.0 dx), indices modulo nx (nx of 1 or 2 gives a zero difference); d/dy likewise, and with ny == 1 no y
+ *   derivative is formed and its terms are absent (no + 0.0).  d/dz f = (f[ku] - f[kd]) / (zmid[ku] - zmid[kd]) with ku = min(k+1, nz-1), kd
+ *   = max(k-1, 0): centred inside, one-sided over the one neighbouring midpoint at k = 0 and k = nz-1.
+ *   Def2 = 2 (ux^2 + vy^2 + wz^2) + (uy + vx)^2 + (uz + wx)^2 + (vz + wy)^2, summed left to right as written: a = ux ux; a = a + vy vy;
+ *   a = a + wz wz; d = 2 a; then d = d + s s for s = uy + vx, uz + wx, vz + wy in that order (ny == 1: s = vx, uz + wx, vz).
+ *   Tv = temp (1 + 0.608 (rho_v / rho)); N2 = (grav / Tv(k)) (dTv/dz + grav / cp_d), grav / cp_d formed once.  This is the UNSATURATED
+ *   frequency: there is no saturated branch and no condensate loading -- a known simplification; a moist N2 is left for later.
+ *   l = cs dz(k); arg = Def2 - N2 / prandtl; tk = (l l) sqrt(arg < 0 ? 0 : arg), so a NaN argument gives a NaN, not 0; tkh = tk / prandtl.
+ *   The mixing length is the level thickness, SAM's choice on anisotropic CRM grids.
+ *
+ * pam_amd_sgs_smag_diffuse   backward Euler of the vertical diffusion, IN PLACE on uvel, vvel, wvel, temp and tracers[num_tracers] (a HOST
+ *   array of DEVICE pointers to tracer densities).  Read only: rho_d, rho_v, tk, tkh, zint, zmid and sfc_flx_u, sfc_flx_v (ny,nx,nens), each
+ *   of which may be NULL.  rho stays frozen for the whole call, also while water_vapor itself is diffused: rho_v may be an entry of the
+ *   tracer table (found by pointer equality, in any position), and every field comes out with the same bits wherever it stands.
+ *   Faces k+1/2, k = 0 .. nz-2, for K = tk (momentum) or tkh (heat, tracers): rho_f = 0.5 (rho(k) + rho(k+1)); K_f = 0.5 (K(k) + K(k+1));
+ *   g = ((dt rho_f) K_f) / dzf; g = 0.0 at the ground and at the top.
+ *   Row k: -lower x(k-1) + diag x(k) - upper x(k+1) = r, diag = 1 + (g(k-1/2) + g(k+1/2)) / (rho(k) dz(k)); lower(0) = upper(nz-1) = 0.0.
+ *     momentum (uvel, vvel, wvel; K = tk)   lower = g(k-1/2) / (rho(k) dz(k)), upper = g(k+1/2) / (rho(k) dz(k)), r = f_old; at k = 0 uvel and
+ *                    vvel add (dt sfc_flx) / dz(0) to r where the flux is given: SHOC's uw_sfc, a kinematic flux in m2/s2, positive upward.
+ *     heat (temp; K = tkh)   the same lower and upper.  What is diffused is temp + (grav/cp_d) zmid; the solve is for temp itself with the
+ *                    linear term on the right: r = temp + (grav/cp_d) (upper dzf(k+1/2) - lower dzf(k-1/2)), a dzf beyond the column 0.0.
+ *     tracers (K = tkh)   what is diffused is the mixing ratio rho_x / rho, the solve is for rho_x: lower = g(k-1/2) / (rho(k-1) dz(k)),
+ *                    upper = g(k+1/2) / (rho(k+1) dz(k)), the same diag, r = rho_x.
+ *   Thomas algorithm, ascending elimination and descending substitution, no pivoting (an M-matrix): den = diag - lower c'(k-1); c'(k) =
+ *   upper / den; d'(k) = (r + lower d'(k-1)) / den with c'(-1) = d'(-1) = 0.0; x(nz-1) = d'(nz-1); x(k) = d'(k) + c'(k) x(k+1).
+ *   For finite columns: a level whose two faces have K_f == 0 keeps its value in every class (a -0.0 may come out as +0.0); without surface
+ *   flux S rho dz f over a column is kept to rounding for the three winds and temp, and S dz rho_x for every tracer; a non-negative
+ *   tracer stays non-negative.  Nothing is refused because of a value; a NaN goes where the restatement puts it.
+ *   One launch: a thread owns a (column, member) and solves the momentum, the heat and the tracer class of it in turn, d' in the field
+ *   itself, c' of the class in LDS (nz x 64 doubles per one-wavefront workgroup) where nz x 512 B <= 32 KB, in a device workspace of one
+ *   field otherwise (per device, allocated on first need, released by pam_amd_modules_finalize; calls on one device must then be ordered by
+ *   the caller).  No floating-point atomics; the same bits from run to run, for any split of the members over calls and on both paths.
+ *
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: a NULL required pointer, a NULL tracer table with
+ * num_tracers > 0 or a NULL entry; num_tracers outside 0..64; nens, nx or ny < 1; nz < 2; ny nx beyond 2^31 - 1 (ny nx nens beyond the
+ * launch grid); dt, dx, dy, grav, cp_d, cs or prandtl not finite and positive; an output that overlaps a read-only input or another
+ * output, except rho_v standing once in the tracer table.
+ * pam_amd_sgs_smag_debug_path is a test switch like pam_amd_hyperdiffusion_debug_path: 0 = automatic, 1 = c' in LDS (refused
+ * beyond its 32 KB), 2 = c' in the workspace. */
+int pam_amd_sgs_smag_coefficients(int nens, int nx, int ny, int nz, const double *uvel, const double *vvel, const double *wvel,
+                                  const double *temp, const double *rho_d, const double *rho_v, const double *zint, const double *zmid,
+                                  double dx, double dy, double grav, double cp_d, double cs, double prandtl, double *tk, double *tkh,
+                                  void *stream);
+int pam_amd_sgs_smag_diffuse(int nens, int nx, int ny, int nz, double *uvel, double *vvel, double *wvel, double *temp, int num_tracers,
+                             double *const *tracers, const double *rho_d, const double *rho_v, const double *tk, const double *tkh,
+                             const double *zint, const double *zmid, const double *sfc_flx_u, const double *sfc_flx_v, double dt, double grav,
+                             double cp_d, void *stream);
+int pam_amd_sgs_smag_debug_path(int path);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,9 @@
 // modules/surface_friction.h -- modules::surface_friction_init(coupler, tau_in, bflx_in) and modules::compute_surface_friction(coupler)
 // with the reference's signatures (pam_core/modules/surface_friction.h:66, :107), forwarding to the C ABI (include/pam_amd_modules.h).
 // The init registers "z0" and "sfc_bflx" {nens} as the reference does (:75-76).  "sfc_mom_flx_u/v" {ny,nx,nens} belong to the SGS
-// scheme in PAM (SHOC registers them, physics/sgs/shoc/SGS.h:119-120); no SGS scheme is ported here, so the init registers them
-// when they are absent.
+// scheme in PAM (SHOC registers them, physics/sgs/shoc/SGS.h:119-120), and here to physics/sgs/smag_amd/SGS.h, which reads them as the
+// lower boundary condition of uvel and vvel, and to physics/sgs/shoc_amd/SGS.h; the init registers them when they are absent (the SGS
+// plug-in is `none`, or its init has not run yet).
 #pragma once
 #include "pam_coupler.h"
 #include "pam_amd_awfl.h"

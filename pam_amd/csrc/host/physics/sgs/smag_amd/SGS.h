@@ -1,0 +1,63 @@
+// physics/sgs/smag_amd/SGS.h -- the native `SGS` plug-in (-DPAM_SGS=smag_amd): a first-order Smagorinsky-Lilly closure with an implicit
+// vertical solve, the turbulence scheme that needs no external library (as kessler_amd is the microphysics that needs none), with the
+// duck-typed members of the reference's physics/sgs/*/SGS.h.  The method is not part of the reference tree; the contract is this project's
+// (include/pam_amd_modules.h).  Two calls of libpam_amd_awfl.so per step: pam_amd_sgs_smag_coefficients fills "tk"
+// and "tkh", pam_amd_sgs_smag_diffuse mixes uvel, vvel, wvel, temp and EVERY registered tracer along the column (the reference's SHOC
+// layer diffuses every tracer too) and takes "sfc_mom_flx_u/v", which modules::compute_surface_friction fills, as the lower boundary
+// condition of the horizontal winds.  density_dry is never written.
+//   options read:  crm_dt, grav, cp_d (the microphysics sets the constants), sgs_smag_cs, sgs_smag_prandtl
+//   options set by init:  "sgs" = "smagorinsky"; sgs_smag_cs = 0.2 and sgs_smag_prandtl = 1/3 unless present
+#pragma once
+#include <string>
+#include <vector>
+
+#include "pam_coupler.h"
+#include "pam_amd_awfl.h"
+#include "pam_amd_modules.h"
+
+#ifndef PAM_SGS_CLASS
+#define PAM_SGS_CLASS SGS      // a driver that holds several SGS classes names each of them before the include
+#endif
+
+class PAM_SGS_CLASS {
+  static void chk(int rc) { if (rc) endrun(pam_amd_awfl_last_error()); }
+
+ public:
+  PAM_SGS_CLASS() {}
+  static int constexpr get_num_tracers() { return 0; }
+
+  void init(pam::PamCoupler &coupler) {
+    int nx = coupler.get_nx(), ny = coupler.get_ny(), nz = coupler.get_nz(), nens = coupler.get_nens();
+    auto &dm = coupler.get_data_manager_device_readwrite();
+    // allocations are zero-filled
+    if (!dm.entry_exists("tk")) dm.register_and_allocate<real>("tk", "Eddy coefficient for momentum [m2/s]", {nz, ny, nx, nens}, {"z", "y", "x", "nens"});
+    if (!dm.entry_exists("tkh")) dm.register_and_allocate<real>("tkh", "Eddy coefficent for heat [m2/s]", {nz, ny, nx, nens}, {"z", "y", "x", "nens"});
+    if (!dm.entry_exists("sfc_mom_flx_u")) dm.register_and_allocate<real>("sfc_mom_flx_u", "Surface flux of U-momentum", {ny, nx, nens}, {"y", "x", "nens"});
+    if (!dm.entry_exists("sfc_mom_flx_v")) dm.register_and_allocate<real>("sfc_mom_flx_v", "Surface flux of V-momentum", {ny, nx, nens}, {"y", "x", "nens"});
+    coupler.set_option<std::string>("sgs", "smagorinsky");
+    if (!coupler.option_exists("sgs_smag_cs")) coupler.set_option<real>("sgs_smag_cs", 0.2);
+    if (!coupler.option_exists("sgs_smag_prandtl")) coupler.set_option<real>("sgs_smag_prandtl", 1.0 / 3.0);
+  }
+
+  void timeStep(pam::PamCoupler &coupler) {
+    int nx = coupler.get_nx(), ny = coupler.get_ny(), nz = coupler.get_nz(), nens = coupler.get_nens();
+    real dt = coupler.get_option<real>("crm_dt"), grav = coupler.get_option<real>("grav"), cp_d = coupler.get_option<real>("cp_d");
+    real cs = coupler.get_option<real>("sgs_smag_cs"), prandtl = coupler.get_option<real>("sgs_smag_prandtl");
+    auto &dm = coupler.get_data_manager_device_readwrite();
+    real *uvel = dm.get<real, 4>("uvel").data(), *vvel = dm.get<real, 4>("vvel").data(), *wvel = dm.get<real, 4>("wvel").data();
+    real *temp = dm.get<real, 4>("temp").data(), *tk = dm.get<real, 4>("tk").data(), *tkh = dm.get<real, 4>("tkh").data();
+    real const *rho_d = dm.get<real const, 4>("density_dry").data(), *rho_v = dm.get<real const, 4>("water_vapor").data();
+    real const *zint = dm.get<real const, 2>("vertical_interface_height").data();
+    real const *zmid = dm.get<real const, 2>("vertical_midpoint_height").data();
+    real const *flx_u = dm.get<real const, 3>("sfc_mom_flx_u").data(), *flx_v = dm.get<real const, 3>("sfc_mom_flx_v").data();
+    std::vector<double *> tracers;
+    for (auto &n : coupler.get_tracer_names()) tracers.push_back(dm.get<real, 4>(n).data());
+    chk(pam_amd_sgs_smag_coefficients(nens, nx, ny, nz, uvel, vvel, wvel, temp, rho_d, rho_v, zint, zmid, coupler.get_dx(), coupler.get_dy(), grav,
+                                      cp_d, cs, prandtl, tk, tkh, nullptr));
+    chk(pam_amd_sgs_smag_diffuse(nens, nx, ny, nz, uvel, vvel, wvel, temp, (int)tracers.size(), tracers.data(), rho_d, rho_v, tk, tkh, zint, zmid,
+                                 flx_u, flx_v, dt, grav, cp_d, nullptr));
+  }
+
+  std::string sgs_name() const { return "smagorinsky"; }
+  void finalize(pam::PamCoupler &coupler) {}
+};

@@ -492,6 +492,7 @@ void validate_scratch_free();   // the result scratch of pam_amd_validate_fields
 void diagnostics_scratch_free();   // the scratch of pam_amd_field_diagnostics, the same
 void hd_workspace_free();          // the workspace of pam_amd_hyperdiffusion's two-launch path, the same
 void cd_workspace_free();          // the workspace of pam_amd_column_diagnostics' column values, the same
+void sgs_workspace_free();         // the workspace of pam_amd_sgs_smag_diffuse's c' on the path without LDS, the same
 }  // namespace
 
 extern "C" int pam_amd_modules_finalize(void) {
@@ -499,6 +500,7 @@ extern "C" int pam_amd_modules_finalize(void) {
   diagnostics_scratch_free();
   hd_workspace_free();
   cd_workspace_free();
+  sgs_workspace_free();
   std::lock_guard<std::mutex> lk(g_tab_mutex);
   int cur = -1;
   (void)hipGetDevice(&cur);
@@ -3844,5 +3846,192 @@ extern "C" int pam_amd_flux_profiles(int nens, int nx, int ny, int nz, const dou
   dim3 grid, block;
   msa_launch_shape(nens, nz, grid, block);
   hipLaunchKernelGGL(flux_profiles_kernel, grid, block, 0, (hipStream_t)stream, nens, nx * ny, F, qc_threshold, O, factor);
+  return stats_launch_check(who);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The native SGS closure: first-order Smagorinsky-Lilly eddy coefficients and the implicit vertical diffusion of the winds, temp and
+// every tracer, with the surface momentum fluxes of compute_surface_friction as the lower boundary condition of uvel and vvel.  Not in
+// the reference tree; the contract is in include/pam_amd_modules.h and DESIGN.md section 8, its arithmetic in sgs_device.h.  Both
+// launches give one thread a (column, member), members across the lanes, so every load and store is a coalesced row of members:
+//   coefficients   the thread walks its column upward with the centre values of three levels in registers; tk and tkh only are written.
+//   solve          ONE launch: the thread solves the momentum class, then the heat class, then the tracer table of its own column, each
+//                  by the Thomas algorithm with d' in the field itself.  No other thread ever reads this column's rho_v, and the thread
+//                  itself has read rho_v(k) before the vapour's own d'(k) takes its place, so the vapour may stand anywhere in the table.
+//                  c' of the class in flight lies in LDS (one wavefront per workgroup, nz x 64 doubles) where that leaves five
+//                  workgroups or more on a compute unit, and in a device workspace of one field otherwise.
+// No floating-point atomics; every element offset is 64 bits wide.
+#include "sgs_device.h"
+
+namespace {
+namespace sg = pama::sgs;
+struct SgsCoefFields { const double *p[6]; };
+struct SgsSolveArgs { double *mom[3]; const double *sfc[3]; double *heat[1]; double *tr[sg::MAX_TRACERS]; };
+constexpr int SGS_THREADS = 256;
+constexpr int SGS_LDS_THREADS = 64;                  // the LDS path: one wavefront per workgroup
+constexpr int SGS_LDS_BYTES = 32 * 1024;             // its budget: five workgroups on a compute unit's 160 KB
+enum { SGS_AUTO, SGS_LDS, SGS_WORKSPACE };
+
+// grid (ceil(ny nx nens / 256)), block 256: thread t = (j nx + i) nens + e
+__global__ void __launch_bounds__(SGS_THREADS) sgs_coef_kernel(int nens, int nx, int ny, int nz, long long level, SgsCoefFields F,
+                                                               const double *__restrict__ zint, const double *__restrict__ zmid,
+                                                               sg::CoefParams P, double *__restrict__ tk, double *__restrict__ tkh) {
+  const long long t = (long long)blockIdx.x * SGS_THREADS + (long long)threadIdx.x;
+  if (t >= level) return;
+  const long long c = t / nens;
+  const int e = (int)(t - c * nens), j = (int)(c / nx), i = (int)(c - (long long)j * nx);
+  const double *f[6];
+#pragma unroll
+  for (int q = 0; q < 6; q++) f[q] = F.p[q];
+  sg::coef_column(f, zint + e, zmid + e, level, nens, nx, ny, nz, j, i, e, P, tk, tkh);
+}
+
+// grid (ceil(ny nx nens / block)), block 64 (LDS: nz x 64 doubles of dynamic LDS) or 256 (workspace: ws is (nz,ny,nx,nens))
+template <bool LDS>
+__global__ void __launch_bounds__(LDS ? SGS_LDS_THREADS : SGS_THREADS) sgs_solve_kernel(int nens, long long level, int nz, int num_tracers,
+                                                                                        SgsSolveArgs A, const double *rd, const double *rv,
+                                                                                        const double *tk, const double *tkh, const double *zint,
+                                                                                        const double *zmid, double dt, double gc, double *ws) {
+  extern __shared__ double sgs_cp[];
+  constexpr int T = LDS ? SGS_LDS_THREADS : SGS_THREADS;
+  const long long t = (long long)blockIdx.x * T + (long long)threadIdx.x;
+  if (t >= level) return;                                   // no barrier below: a thread's c' is its own
+  const int e = (int)(t % nens);
+  double *cp = LDS ? sgs_cp + threadIdx.x : ws + t;
+  const long long cs = LDS ? (long long)T : level;
+  const double *zi = zint + e, *zm = zmid + e;
+  sg::solve_class(sg::C_MOMENTUM, A.mom, 3, A.sfc, t, rd, rv, tk, zi, zm, level, (long long)nens, nz, dt, gc, cp, cs);
+  sg::solve_class(sg::C_HEAT, A.heat, 1, nullptr, t, rd, rv, tkh, zi, zm, level, (long long)nens, nz, dt, gc, cp, cs);
+  if (num_tracers > 0) sg::solve_class(sg::C_TRACER, A.tr, num_tracers, nullptr, t, rd, rv, tkh, zi, zm, level, (long long)nens, nz, dt, gc, cp, cs);
+}
+
+// the workspace of c' on the path without LDS: per device, grown on demand, freed by pam_amd_modules_finalize().  The launch goes to the
+// caller's stream and nothing synchronises, so calls on ONE device must be ordered by the caller, as for column_diagnostics
+constexpr int SGS_MAX_DEVICES = 64;
+struct SgsWorkspace { std::mutex m; double *p = nullptr; long long count = 0; };
+SgsWorkspace g_sgs_workspace[SGS_MAX_DEVICES];
+
+void sgs_workspace_free() {
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  for (int d = 0; d < SGS_MAX_DEVICES; d++) {
+    SgsWorkspace &w = g_sgs_workspace[d];
+    std::lock_guard<std::mutex> lk(w.m);
+    if (w.p) {
+      if (d != cur) (void)hipSetDevice(d);
+      (void)hipFree(w.p);
+      w.p = nullptr;
+      w.count = 0;
+      if (d != cur && cur >= 0) (void)hipSetDevice(cur);
+    }
+  }
+}
+
+int g_sgs_path = SGS_AUTO;   // pam_amd_sgs_smag_debug_path: tests run both placements of c' at small shapes
+
+bool sgs_positive(double v) { return std::isfinite(v) && v > 0; }
+
+int sgs_check_sizes(const char *who, int nens, int nx, int ny, int nz) {
+  if (nens < 1 || nx < 1 || ny < 1) return rad_error(who, "nens, nx and ny must be >= 1");
+  if (nz < 2) return rad_error(who, "nz must be >= 2");
+  if ((long long)nx * ny > 0x7fffffffLL) return rad_error(who, "ny x nx exceeds 2^31 - 1 columns");
+  if (((long long)nx * ny * nens + SGS_LDS_THREADS - 1) / SGS_LDS_THREADS > 0x7fffffffLL) return rad_error(who, "ny x nx x nens exceeds the grid");
+  return PAM_AMD_OK;
+}
+}  // namespace
+
+extern "C" int pam_amd_sgs_smag_debug_path(int path) {
+  if (path < SGS_AUTO || path > SGS_WORKSPACE) return rad_error("sgs_smag", "debug path must be 0 (automatic), 1 (LDS) or 2 (workspace)");
+  g_sgs_path = path;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_sgs_smag_coefficients(int nens, int nx, int ny, int nz, const double *uvel, const double *vvel, const double *wvel,
+                                             const double *temp, const double *rho_d, const double *rho_v, const double *zint,
+                                             const double *zmid, double dx, double dy, double grav, double cp_d, double cs, double prandtl,
+                                             double *tk, double *tkh, void *stream) {
+  const char *who = "sgs_smag_coefficients";
+  if (int rc = sgs_check_sizes(who, nens, nx, ny, nz)) return rc;
+  if (!uvel || !vvel || !wvel || !temp || !rho_d || !rho_v || !zint || !zmid || !tk || !tkh) return rad_error(who, "null pointer");
+  if (!sgs_positive(dx) || !sgs_positive(dy) || !sgs_positive(grav) || !sgs_positive(cp_d) || !sgs_positive(cs) || !sgs_positive(prandtl))
+    return rad_error(who, "dx, dy, grav, cp_d, cs and prandtl must be finite and positive");
+  const long long level = (long long)nx * ny * nens, cells = level * nz;
+  std::vector<RadSpan> spans;
+  for (const double *p : {uvel, vvel, wvel, temp, rho_d, rho_v}) spans.push_back({p, cells, false});
+  spans.push_back({zint, (long long)(nz + 1) * nens, false});
+  spans.push_back({zmid, (long long)nz * nens, false});
+  spans.push_back({tk, cells, true});
+  spans.push_back({tkh, cells, true});
+  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
+  if (int rc = moist_surface_device_check(who)) return rc;
+  const SgsCoefFields F{{uvel, vvel, wvel, temp, rho_d, rho_v}};
+  const sg::CoefParams P{sg::twice(dx), sg::twice(dy), grav, sg::lapse(grav, cp_d), cs, prandtl};
+  hipLaunchKernelGGL(sgs_coef_kernel, dim3((unsigned)((level + SGS_THREADS - 1) / SGS_THREADS)), dim3(SGS_THREADS), 0, (hipStream_t)stream, nens,
+                     nx, ny, nz, level, F, zint, zmid, P, tk, tkh);
+  return stats_launch_check(who);
+}
+
+extern "C" int pam_amd_sgs_smag_diffuse(int nens, int nx, int ny, int nz, double *uvel, double *vvel, double *wvel, double *temp,
+                                        int num_tracers, double *const *tracers, const double *rho_d, const double *rho_v, const double *tk,
+                                        const double *tkh, const double *zint, const double *zmid, const double *sfc_flx_u,
+                                        const double *sfc_flx_v, double dt, double grav, double cp_d, void *stream) {
+  const char *who = "sgs_smag_diffuse";
+  if (int rc = sgs_check_sizes(who, nens, nx, ny, nz)) return rc;
+  if (num_tracers < 0 || num_tracers > sg::MAX_TRACERS) return rad_error(who, "num_tracers must be in [0, 64]");
+  if (num_tracers > 0 && !tracers) return rad_error(who, "null tracer table");
+  if (!uvel || !vvel || !wvel || !temp || !rho_d || !rho_v || !tk || !tkh || !zint || !zmid) return rad_error(who, "null pointer");
+  for (int i = 0; i < num_tracers; i++)
+    if (!tracers[i]) return rad_error(who, "null tracer pointer");
+  if (!sgs_positive(dt) || !sgs_positive(grav) || !sgs_positive(cp_d)) return rad_error(who, "dt, grav and cp_d must be finite and positive");
+  const long long level = (long long)nx * ny * nens, cells = level * nz;
+  std::vector<RadSpan> spans;
+  for (const double *p : {rho_d, tk, tkh}) spans.push_back({p, cells, false});
+  spans.push_back({zint, (long long)(nz + 1) * nens, false});
+  spans.push_back({zmid, (long long)nz * nens, false});
+  if (sfc_flx_u) spans.push_back({sfc_flx_u, level, false});
+  if (sfc_flx_v) spans.push_back({sfc_flx_v, level, false});
+  for (double *p : {uvel, vvel, wvel, temp}) spans.push_back({p, cells, true});
+  bool vapour_in_table = false;
+  for (int i = 0; i < num_tracers; i++) {
+    if (tracers[i] == rho_v && !vapour_in_table) { vapour_in_table = true; continue; }      // the one allowed alias: rho_v itself, once
+    spans.push_back({tracers[i], cells, true});
+  }
+  spans.push_back({rho_v, cells, vapour_in_table});       // as an output where it is solved: it overlaps nothing else
+  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
+  const bool lds = g_sgs_path == SGS_AUTO ? (long long)nz * SGS_LDS_THREADS * (long long)sizeof(double) <= SGS_LDS_BYTES : g_sgs_path == SGS_LDS;
+  if (lds && (long long)nz * SGS_LDS_THREADS * (long long)sizeof(double) > SGS_LDS_BYTES) return rad_error(who, "the forced LDS path does not fit its 32 KB at this nz");
+  if (int rc = moist_surface_device_check(who)) return rc;
+
+  SgsSolveArgs A;
+  A.mom[0] = uvel; A.mom[1] = vvel; A.mom[2] = wvel;
+  A.sfc[0] = sfc_flx_u; A.sfc[1] = sfc_flx_v; A.sfc[2] = nullptr;
+  A.heat[0] = temp;
+  for (int i = 0; i < sg::MAX_TRACERS; i++) A.tr[i] = i < num_tracers ? tracers[i] : nullptr;
+  const double gc = sg::lapse(grav, cp_d);
+  hipStream_t s = (hipStream_t)stream;
+  if (lds) {
+    hipLaunchKernelGGL(sgs_solve_kernel<true>, dim3((unsigned)((level + SGS_LDS_THREADS - 1) / SGS_LDS_THREADS)), dim3(SGS_LDS_THREADS),
+                       (size_t)nz * SGS_LDS_THREADS * sizeof(double), s, nens, level, nz, num_tracers, A, rho_d, rho_v, tk, tkh, zint, zmid, dt, gc,
+                       (double *)nullptr);
+    return stats_launch_check(who);
+  }
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SGS_MAX_DEVICES)
+    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "sgs_smag_diffuse: cannot tell the current device");
+  SgsWorkspace &w = g_sgs_workspace[dev];
+  std::lock_guard<std::mutex> lk(w.m);
+  if (w.count < cells) {
+    if (w.p) (void)hipFree(w.p);
+    w.p = nullptr;
+    w.count = 0;
+    if (hipMalloc((void **)&w.p, (size_t)cells * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
+      w.p = nullptr;
+      return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "sgs_smag_diffuse: cannot allocate the workspace of one field");
+    }
+    w.count = cells;
+  }
+  hipLaunchKernelGGL(sgs_solve_kernel<false>, dim3((unsigned)((level + SGS_THREADS - 1) / SGS_THREADS)), dim3(SGS_THREADS), 0, s, nens, level, nz,
+                     num_tracers, A, rho_d, rho_v, tk, tkh, zint, zmid, dt, gc, w.p);
   return stats_launch_check(who);
 }

@@ -1,0 +1,269 @@
+// sgs_device.h -- the arithmetic of the native Smagorinsky-Lilly SGS closure (a first-order column scheme: eddy coefficients from the
+// resolved deformation and the dry stability, then an implicit vertical diffusion of the winds, temp and every tracer), as device
+// functions that are plain inline C++ outside hipcc: the HIP kernels in modules_kernels.hip call them, and tests/emu/sgs_emu.cpp compiles
+// the same bodies with g++ (-ffp-contract=off).  The method is not part of the reference tree; the yardstick is the numpy restatement of
+// the contract in tests/sgs_ref.py, held bit for bit (include/pam_amd_modules.h).
+// Fields are (nz, ny, nx, nens), members fastest; inside a level a (column, member) has the flat index t = (j nx + i) nens + e, and every
+// element offset is 64 bits wide.  zint (nz+1, nens) and zmid (nz, nens) are per member.
+// Contraction into fma is switched off inside each body, so the device and the host give the same bits.
+#pragma once
+
+#include <cmath>
+
+#include "msa_device.h"      // PAMA_D, PAMA_NO_CONTRACT
+
+namespace pama {
+namespace sgs {
+
+constexpr int MAX_TRACERS = 64;          // tracers per call
+constexpr int NREG = 4;                  // fields of a class whose running values a thread keeps in registers
+constexpr int AHEAD = 4;                 // levels whose loads are requested before the first of them is used
+enum { C_MOMENTUM, C_HEAT, C_TRACER };   // the three classes of rows
+
+struct CoefParams {
+  double two_dx, two_dy, grav, gc, cs, prandtl;      // gc = grav / cp_d
+};
+
+// host functions, once per call
+inline double twice(double d) {
+  PAMA_NO_CONTRACT
+  return 2.0 * d;
+}
+inline double lapse(double grav, double cp_d) {
+  PAMA_NO_CONTRACT
+  return grav / cp_d;
+}
+
+PAMA_D double centred(double hi, double lo, double span) {
+  PAMA_NO_CONTRACT
+  const double d = hi - lo;
+  return d / span;
+}
+
+// Tv = temp (1 + 0.608 rho_v / rho), rho = rho_d + rho_v
+PAMA_D double virtual_temp(double temp, double rho_d, double rho_v) {
+  PAMA_NO_CONTRACT
+  const double rho = rho_d + rho_v;
+  const double q = rho_v / rho;
+  const double t = 0.608 * q;
+  const double f = 1.0 + t;
+  return temp * f;
+}
+
+// Def2 = 2 (ux^2 + vy^2 + wz^2) + (uy + vx)^2 + (uz + wx)^2 + (vz + wy)^2, left to right; without y the y derivatives are absent
+PAMA_D double deformation(bool with_y, double ux, double uy, double uz, double vx, double vy, double vz, double wx, double wy, double wz) {
+  PAMA_NO_CONTRACT
+  double a = ux * ux;
+  if (with_y) a = a + vy * vy;
+  a = a + wz * wz;
+  double d = 2.0 * a;
+  double s = with_y ? uy + vx : vx;
+  d = d + s * s;
+  s = uz + wx;
+  d = d + s * s;
+  s = with_y ? vz + wy : vz;
+  d = d + s * s;
+  return d;
+}
+
+// N2 = grav / Tv_k * (dTv/dz + grav / cp_d): the unsaturated frequency
+PAMA_D double stability(double grav, double gc, double tv, double dtvdz) {
+  PAMA_NO_CONTRACT
+  const double a = grav / tv;
+  const double b = dtvdz + gc;
+  return a * b;
+}
+
+// tk = (cs dz)^2 sqrt(max(Def2 - N2 / prandtl, 0)), a NaN argument staying a NaN; tkh = tk / prandtl
+PAMA_D void eddy(double def2, double n2, double dz, double cs, double prandtl, double &tk, double &tkh) {
+  PAMA_NO_CONTRACT
+  const double l = cs * dz;
+  const double l2 = l * l;
+  const double arg = def2 - n2 / prandtl;
+  const double m = arg < 0.0 ? 0.0 : arg;
+  tk = l2 * std::sqrt(m);
+  tkh = tk / prandtl;
+}
+
+PAMA_D int wrap_up(int i, int n) { return i + 1 == n ? 0 : i + 1; }
+PAMA_D int wrap_down(int i, int n) { return i == 0 ? n - 1 : i - 1; }
+
+// the eddy coefficients of one column (j, i) of member e, bottom to top.  f: uvel, vvel, wvel, temp, rho_d, rho_v, each pointing at
+// element 0; zint, zmid point at (0, e).  The centre values of levels k-1, k, k+1 ride along in registers; the horizontal neighbours of
+// level k are read from the fields.  tk and tkh overlap nothing that is read (the entry point refuses it)
+PAMA_D void coef_column(const double *const *f, const double *zint, const double *zmid, long long level, int nens, int nx, int ny, int nz, int j,
+                        int i, int e, const CoefParams &P, double *__restrict__ tk, double *__restrict__ tkh) {
+  const bool with_y = ny > 1;
+  const long long row = (long long)j * nx;
+  const long long c0 = (row + i) * nens + e;
+  const long long xp = (row + wrap_up(i, nx)) * nens + e, xm = (row + wrap_down(i, nx)) * nens + e;
+  const long long yp = ((long long)wrap_up(j, ny) * nx + i) * nens + e, ym = ((long long)wrap_down(j, ny) * nx + i) * nens + e;
+  const double *u = f[0], *v = f[1], *w = f[2], *T = f[3], *rd = f[4], *rv = f[5];
+  double u_k = u[c0], v_k = v[c0], w_k = w[c0], tv_k = virtual_temp(T[c0], rd[c0], rv[c0]), zm_k = zmid[0];
+  double u_m = u_k, v_m = v_k, w_m = w_k, tv_m = tv_k, zm_m = zm_k;      // the one-sided difference at the ground
+  double zi_k = zint[0];
+  for (int k = 0; k < nz; k++) {
+    const int ku = k + 1 < nz ? k + 1 : k;                               // the one-sided difference at the top
+    const long long lu = (long long)ku * level + c0, lk = (long long)k * level;
+    const double u_p = u[lu], v_p = v[lu], w_p = w[lu], tv_p = virtual_temp(T[lu], rd[lu], rv[lu]), zm_p = zmid[(long long)ku * nens];
+    const double zi_p = zint[(long long)(k + 1) * nens];
+    const double span = zm_p - zm_m;
+    const double uz = centred(u_p, u_m, span), vz = centred(v_p, v_m, span), wz = centred(w_p, w_m, span);
+    const double ux = centred(u[lk + xp], u[lk + xm], P.two_dx), vx = centred(v[lk + xp], v[lk + xm], P.two_dx);
+    const double wx = centred(w[lk + xp], w[lk + xm], P.two_dx);
+    double uy = 0.0, vy = 0.0, wy = 0.0;
+    if (with_y) {
+      uy = centred(u[lk + yp], u[lk + ym], P.two_dy);
+      vy = centred(v[lk + yp], v[lk + ym], P.two_dy);
+      wy = centred(w[lk + yp], w[lk + ym], P.two_dy);
+    }
+    const double def2 = deformation(with_y, ux, uy, uz, vx, vy, vz, wx, wy, wz);
+    const double n2 = stability(P.grav, P.gc, tv_k, centred(tv_p, tv_m, span));
+    double a, b;
+    eddy(def2, n2, zi_p - zi_k, P.cs, P.prandtl, a, b);
+    tk[lk + c0] = a;
+    tkh[lk + c0] = b;
+    u_m = u_k; v_m = v_k; w_m = w_k; tv_m = tv_k; zm_m = zm_k;
+    u_k = u_p; v_k = v_p; w_k = w_p; tv_k = tv_p; zm_k = zm_p;
+    zi_k = zi_p;
+  }
+}
+
+// g at the face between levels k and k+1: dt rho_f K_f / dzf with rho_f and K_f the means of the two levels, left to right
+PAMA_D double face_g(double dt, double rho_k, double rho_p, double K_k, double K_p, double dzf) {
+  PAMA_NO_CONTRACT
+  const double rf = 0.5 * (rho_k + rho_p);
+  const double kf = 0.5 * (K_k + K_p);
+  const double a = dt * rf;
+  const double b = a * kf;
+  return b / dzf;
+}
+
+// backward Euler of one class over one (column, member): nf fields, IN PLACE, by the Thomas algorithm (ascending elimination, descending
+// substitution, no pivoting).  Row k: -lower x(k-1) + diag x(k) - upper x(k+1) = r, lower(0) = upper(nz-1) = 0.0.
+//   den = diag - lower c'(k-1); c'(k) = upper / den; d'(k) = (r + lower d'(k-1)) / den, c'(-1) = d'(-1) = 0.0;
+//   x(nz-1) = d'(nz-1); x(k) = d'(k) + c'(k) x(k+1).
+// d' lives in the field itself; c', common to the fields of the class, in cp (cp[k cs]: LDS or a device workspace).  f[t] and sfc[t]
+// point at element 0 and get `off` (the flat index inside a level); rd, rv, K likewise; zint, zmid point at (0, e) with stride zs.
+// rho is read one level ahead of the level being written and carried in registers, so a field of the table may be rho_v itself: every
+// rho_v(k) is read before d'(k) takes its place.  The loads of AHEAD levels are requested before the first of them is used; the first
+// NREG fields keep d'(k-1) and x(k+1) in registers, a longer table reads them back from the field
+PAMA_D void solve_class(int cls, double *const *f, int nf, const double *const *sfc, long long off, const double *rd, const double *rv,
+                        const double *K, const double *zint, const double *zmid, long long level, long long zs, int nz, double dt, double gc,
+                        double *cp, long long cs) {
+  PAMA_NO_CONTRACT
+  double prev[NREG];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int t = 0; t < NREG; t++) prev[t] = 0.0;
+  rd += off; rv += off; K += off;
+  double rho_m = 0.0, rho_k = rd[0] + rv[0], K_k = K[0], zi_k = zint[0], zm_k = zmid[0], g_m = 0.0, dzf_m = 0.0, cprev = 0.0;
+  for (int k0 = 0; k0 < nz; k0 += AHEAD) {
+    double a_rd[AHEAD], a_rv[AHEAD], a_K[AHEAD], a_zi[AHEAD], a_zm[AHEAD], a_f[AHEAD][NREG];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int b = 0; b < AHEAD; b++) {
+      const int kk = k0 + b;
+      const long long kc = kk < nz ? kk : nz - 1, kp = kk + 1 < nz ? kk + 1 : nz - 1, ki = kk + 1 < nz ? kk + 1 : nz;
+      a_rd[b] = rd[kp * level]; a_rv[b] = rv[kp * level]; a_K[b] = K[kp * level];
+      a_zm[b] = zmid[kp * zs]; a_zi[b] = zint[ki * zs];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int t = 0; t < NREG; t++)
+        if (t < nf) a_f[b][t] = f[t][off + kc * level];
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int b = 0; b < AHEAD; b++) {
+      const int k = k0 + b;
+      if (k >= nz) break;
+      const bool first = k == 0, last = k == nz - 1;
+      const long long o = off + (long long)k * level;
+      const double rho_p = a_rd[b] + a_rv[b];
+      const double dz = a_zi[b] - zi_k;
+      const double dzf_p = last ? 0.0 : a_zm[b] - zm_k;
+      const double g_p = last ? 0.0 : face_g(dt, rho_k, rho_p, K_k, a_K[b], dzf_p);
+      const double rdz = rho_k * dz;
+      const double gs = g_m + g_p;
+      const double diag = 1.0 + gs / rdz;
+      double lower, upper;
+      if (cls == C_TRACER) {
+        lower = first ? 0.0 : g_m / (rho_m * dz);
+        upper = last ? 0.0 : g_p / (rho_p * dz);
+      } else {
+        lower = first ? 0.0 : g_m / rdz;
+        upper = last ? 0.0 : g_p / rdz;
+      }
+      const double den = diag - lower * cprev;
+      const double c = upper / den;
+      if (!last) cp[(long long)k * cs] = c;
+      double heat = 0.0;
+      if (cls == C_HEAT) {
+        const double hu = upper * dzf_p;
+        const double hl = lower * dzf_m;
+        heat = gc * (hu - hl);
+      }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int t = 0; t < NREG; t++)
+        if (t < nf) {
+          double r = a_f[b][t];
+          if (cls == C_HEAT) r = r + heat;
+          if (first && sfc && sfc[t]) r = r + (dt * sfc[t][off]) / dz;
+          const double d = (r + lower * prev[t]) / den;
+          f[t][o] = d;
+          prev[t] = d;
+        }
+      for (int t = NREG; t < nf; t++) {
+        double r = f[t][o];
+        if (cls == C_HEAT) r = r + heat;
+        if (first && sfc && sfc[t]) r = r + (dt * sfc[t][off]) / dz;
+        const double p = first ? 0.0 : f[t][o - level];
+        f[t][o] = (r + lower * p) / den;
+      }
+      rho_m = rho_k; rho_k = rho_p; K_k = a_K[b]; zi_k = a_zi[b]; zm_k = a_zm[b]; g_m = g_p; dzf_m = dzf_p; cprev = c;
+    }
+  }
+  // prev[t] is x(nz-1) = d'(nz-1) of the first NREG fields
+  for (int k0 = nz - 2; k0 >= 0; k0 -= AHEAD) {
+    double a_c[AHEAD], a_f[AHEAD][NREG];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int b = 0; b < AHEAD; b++) {
+      const long long kc = k0 - b > 0 ? k0 - b : 0;
+      a_c[b] = cp[kc * cs];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int t = 0; t < NREG; t++)
+        if (t < nf) a_f[b][t] = f[t][off + kc * level];
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int b = 0; b < AHEAD; b++) {
+      const int k = k0 - b;
+      if (k < 0) break;
+      const long long o = off + (long long)k * level;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int t = 0; t < NREG; t++)
+        if (t < nf) {
+          const double x = a_f[b][t] + a_c[b] * prev[t];
+          f[t][o] = x;
+          prev[t] = x;
+        }
+      for (int t = NREG; t < nf; t++) f[t][o] = f[t][o] + a_c[b] * f[t][o + level];
+    }
+  }
+}
+
+}  // namespace sgs
+}  // namespace pama

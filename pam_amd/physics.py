@@ -4,12 +4,14 @@
   RadiationNone     physics/radiation/none/radiation.h
   SGSNone           physics/sgs/none/SGS.h
   SGSShoc           physics/sgs/shoc/SGS.h                 the coupling layer around shoc_main; SHOC itself is handed in by the caller
+  SGSSmagorinsky    (this project's)                       the native Smagorinsky-Lilly closure with an implicit vertical solve
   MicrophysicsNone  physics/micro/none/Microphysics.h      registers and zeroes "water_vapor", sets the constants
   MicrophysicsP3    physics/micro/p3/Microphysics.h        the coupling layer around p3_main; P3 itself is handed in by the caller
 
 Arithmetic is in libpam_amd_awfl.so (pam_amd/csrc/modules_kernels.hip); there is no CPU path.  Deviations from the reference
 (DESIGN.md section 8): the sizes come from the coupler's own getters (options ncrms / crm_nz / crm_nx / crm_ny must agree where they
 exist), the rad grid must divide the CRM grid, and missing options or bad constants raise before anything is written."""
+import ctypes as C
 import math
 
 import torch
@@ -109,6 +111,71 @@ class SGSNone:
 
     def timeStep(self, coupler):
         pass
+
+    def finalize(self, coupler):
+        pass
+
+
+class SGSSmagorinsky:
+    """physics/sgs/smag_amd/SGS.h: the native first-order Smagorinsky-Lilly closure with an implicit vertical solve.  Not part of the
+    reference tree; the contract is this project's (include/pam_amd_modules.h).  timeStep fills "tk" and "tkh"
+    and mixes uvel, vvel, wvel, temp and every registered tracer along the column, with "sfc_mom_flx_u/v" (compute_surface_friction
+    fills them) as the lower boundary condition of the horizontal winds.  density_dry is never written."""
+    FIELDS = (("tk", 4), ("tkh", 4), ("sfc_mom_flx_u", 3), ("sfc_mom_flx_v", 3))
+    OPTIONS = ("sgs", "sgs_smag_cs", "sgs_smag_prandtl")
+    OPTIONS_READ = ("crm_dt", "grav", "cp_d", "sgs_smag_cs", "sgs_smag_prandtl")
+
+    def __init__(self, cs=0.2, prandtl=1.0 / 3.0):
+        self.cs, self.prandtl = float(cs), float(prandtl)
+
+    @staticmethod
+    def get_num_tracers():
+        return 0
+
+    @staticmethod
+    def sgs_name():
+        return "smagorinsky"
+
+    def init(self, coupler):
+        """registers "tk", "tkh" and "sfc_mom_flx_u/v" where absent, zero-filled; option "sgs" = "smagorinsky"; the options sgs_smag_cs
+        and sgs_smag_prandtl unless present"""
+        nens, nz, ny, nx = coupler.get_nens(), coupler.get_nz(), coupler.get_ny(), coupler.get_nx()
+        if min(nens, nz, ny, nx) < 1:
+            endrun("ERROR: sgs: the coupler state is not allocated")
+        dm = coupler.get_data_manager_device_readwrite()
+        for name, rank in self.FIELDS:
+            if not dm.entry_exists(name):
+                if rank == 4:
+                    dm.register_and_allocate(name, "Eddy coefficient [m2/s]", (nz, ny, nx, nens), ("z", "y", "x", "nens"))
+                else:
+                    dm.register_and_allocate(name, "Surface momentum flux", (ny, nx, nens), ("y", "x", "nens"))
+        coupler.set_option("sgs", "smagorinsky")
+        if not coupler.option_exists("sgs_smag_cs"):
+            coupler.set_option("sgs_smag_cs", self.cs)
+        if not coupler.option_exists("sgs_smag_prandtl"):
+            coupler.set_option("sgs_smag_prandtl", self.prandtl)
+
+    def timeStep(self, coupler):
+        """the coefficient launch, then the solve, on the current stream"""
+        lib = capi.load()
+        nens, nz, ny, nx = coupler.get_nens(), coupler.get_nz(), coupler.get_ny(), coupler.get_nx()
+        dt, grav, cp_d, cs, prandtl = (float(coupler.get_option(n)) for n in self.OPTIONS_READ)
+        dm = coupler.get_data_manager_device_readwrite()
+        u, v, w, temp, tk, tkh = (dm.get(n) for n in ("uvel", "vvel", "wvel", "temp", "tk", "tkh"))
+        rho_d, rho_v = dm.get("density_dry", readonly=True), dm.get("water_vapor", readonly=True)
+        zint, zmid = dm.get("vertical_interface_height", readonly=True), dm.get("vertical_midpoint_height", readonly=True)
+        flx_u, flx_v = dm.get("sfc_mom_flx_u", readonly=True), dm.get("sfc_mom_flx_v", readonly=True)
+        tracers = [dm.get(n) for n in coupler.get_tracer_names()]
+        table = (C.c_void_p * max(len(tracers), 1))(*[t.data_ptr() for t in tracers])
+        with torch.cuda.device(coupler.device):
+            stream = torch.cuda.current_stream(coupler.device).cuda_stream
+            check(lib.pam_amd_sgs_smag_coefficients(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(),
+                                                    rho_d.data_ptr(), rho_v.data_ptr(), zint.data_ptr(), zmid.data_ptr(),
+                                                    float(coupler.get_dx()), float(coupler.get_dy()), grav, cp_d, cs, prandtl,
+                                                    tk.data_ptr(), tkh.data_ptr(), stream))
+            check(lib.pam_amd_sgs_smag_diffuse(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(), len(tracers),
+                                               table, rho_d.data_ptr(), rho_v.data_ptr(), tk.data_ptr(), tkh.data_ptr(), zint.data_ptr(),
+                                               zmid.data_ptr(), flx_u.data_ptr(), flx_v.data_ptr(), dt, grav, cp_d, stream))
 
     def finalize(self, coupler):
         pass

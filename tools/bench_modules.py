@@ -18,6 +18,8 @@ and the CRM feedback, beside msa_diagnose, time_average_accumulate and radiation
 radiation aggregate at the 1x1 rad grid and msa_diagnose of the same run;
 --only fluxprof: the CRM flux profiles on P3's field set at the C2 grid and at C4's 32x1x60 grid with 8192 members, beside vt_diagnose
 and msa_diagnose of the same run;
+--only sgs: the native Smagorinsky SGS closure's coefficient launch and its solve (c' in LDS and in the workspace) on Kessler's field set
+at the C2 grid and at C4's 32x1x60 grid with 8192 members, beside hyperdiffusion and msa_apply of the same run;
 --only msa: mean-state acceleration's diagnose, tendencies and apply (with and without the winds), beside horizontal_average and
 time_average_accumulate of the same run)"""
 import json
@@ -1216,8 +1218,118 @@ def fluxprof_timing(dev, warmup=3, n=11, reps=3):
     return out
 
 
+def sgs_timing(dev, warmup=3, n=11):
+    """The native Smagorinsky SGS closure at the C2 grid on the Kessler field set (the three winds, temp and three tracers, the vapour among
+    them: seven solved fields) and at C4's 32x1x60 grid with 8192 members: the coefficient launch and the solve on its automatic path and
+    with c' forced into LDS (1) and into the workspace (2), 3 warm-up calls and the median of 11 event-timed calls each.  Algorithmic
+    bytes: 64 B per cell for the coefficients (six fields read, tk and tkh written); for the solve 16 B per cell and solved field (one
+    read, one write) plus the coefficient inputs rho_d, rho_v and K once per class (3 x 24 B per cell): the second touch of a field by the
+    substitution and the workspace's own traffic are NOT counted, so they show as the lower fraction they are.  hyperdiffusion (automatic
+    path) and msa_apply (with the winds) of the same run stand beside them."""
+    from pam_amd import PamCoupler, SGSSmagorinsky, capi, modules
+    from pam_amd import idealized as idz
+    lib = capi.load()
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    def row(t, nbytes):
+        return {"ms": t[0], "min_ms": t[1], "max_ms": t[2], "bytes": nbytes, "GBps": nbytes / t[0] / 1e6,
+                "hbm_frac": nbytes / t[0] / 1e6 / bench.HBM_PEAK_GBS}
+
+    def grid(nens, nx, ny, nz, label, out, beside):
+        cells = nens * nx * ny * nz
+        c = PamCoupler(dev)
+        c.set_option("crm_dt", 2.0)
+        c.set_option("grav", 9.80616)
+        c.set_option("cp_d", 1004.64)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+        for t in ("water_vapor", "cloud_liquid", "precip_liquid"):
+            c.add_tracer(t, "", True, True)
+        c.set_option("micro", "kessler")
+        dm = c.get_data_manager_device_readwrite()
+        gen = torch.Generator(device=dev).manual_seed(0)
+        for name, lo, span in (("density_dry", 0.5, 0.7), ("uvel", -5.0, 10.0), ("vvel", -5.0, 10.0), ("wvel", -1.0, 2.0), ("temp", 250.0, 50.0),
+                               ("water_vapor", 0.0, 0.01), ("cloud_liquid", 0.0, 0.001), ("precip_liquid", 0.0, 0.001)):
+            t = dm.get(name)
+            t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * span + lo)
+        sgs = SGSSmagorinsky()
+        sgs.init(c)
+        dm.get("sfc_mom_flx_u").fill_(-0.01)
+        dm.get("sfc_mom_flx_v").fill_(0.01)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        P = lambda name: dm.get(name).data_ptr()
+        tr = c.get_tracer_names()
+        table = (C.c_void_p * len(tr))(*[P(t) for t in tr])
+
+        def coef():
+            capi.check(lib.pam_amd_sgs_smag_coefficients(nens, nx, ny, nz, P("uvel"), P("vvel"), P("wvel"), P("temp"), P("density_dry"),
+                                                         P("water_vapor"), P("vertical_interface_height"), P("vertical_midpoint_height"), 1000.0,
+                                                         1000.0, 9.80616, 1004.64, 0.2, 1.0 / 3.0, P("tk"), P("tkh"), stream))
+
+        def solve():
+            capi.check(lib.pam_amd_sgs_smag_diffuse(nens, nx, ny, nz, P("uvel"), P("vvel"), P("wvel"), P("temp"), len(tr), table, P("density_dry"),
+                                                    P("water_vapor"), P("tk"), P("tkh"), P("vertical_interface_height"),
+                                                    P("vertical_midpoint_height"), P("sfc_mom_flx_u"), P("sfc_mom_flx_v"), 2.0, 9.80616, 1004.64,
+                                                    stream))
+
+        out["sgs_coefficients" + label] = row(timed(coef), cells * 64.0)
+        assert bool(torch.isfinite(dm.get("tk", readonly=True)).all()) and float(dm.get("tk", readonly=True).max()) > 0
+        nbytes = cells * (7 * 16.0 + 3 * 24.0)
+        for path, name in ((0, "automatic"), (1, "lds"), (2, "workspace")):
+            capi.check(lib.pam_amd_sgs_smag_debug_path(path))
+            try:
+                out["sgs_diffuse_%s%s" % (name, label)] = row(timed(solve), nbytes)
+            finally:
+                capi.check(lib.pam_amd_sgs_smag_debug_path(0))
+        assert all(bool(torch.isfinite(dm.get(t, readonly=True)).all()) for t in ["uvel", "vvel", "wvel", "temp"] + tr)
+        out["sgs_time_step_ms" + label] = out["sgs_coefficients" + label]["ms"] + out["sgs_diffuse_automatic" + label]["ms"]
+        if beside:
+            modules.hyperdiffusion_init(c, 60.0)
+            out["hyperdiffusion_automatic" + label] = row(timed(lambda: modules.hyperdiffusion(c)), 7 * cells * 16.0 + 3 * cells * 8.0)
+            c.set_option("gcm_physics_dt", 900.0)
+            c.set_option("crm_accel_factor", 2.0)
+            c.set_option("crm_accel_uv", True)
+            modules.msa_init(c)
+            mfields, msave, mtend, cease = modules._msa_arrays(c)
+            MF, MT = modules._msa_table(mfields), modules._msa_table(mtend)
+            dm.get("accel_tend_t").fill_(1.0e-6)
+            for q in ("q", "u", "v"):
+                dm.get("accel_tend_" + q).zero_()
+            out["msa_apply_accel_uv" + label] = row(timed(lambda: capi.check(lib.pam_amd_msa_apply(nens, nx, ny, nz, MF, MT, 2.0, 1, cease.data_ptr(),
+                                                                                                   stream))), 4 * cells * 16.0)
+            for k in ("sgs_coefficients", "sgs_diffuse_automatic"):
+                out["%s%s_vs_hyperdiffusion_frac" % (k, label)] = out[k + label]["hbm_frac"] / out["hyperdiffusion_automatic" + label]["hbm_frac"]
+            del mfields, msave, mtend
+        del c, dm, sgs
+        lib.pam_amd_modules_finalize()
+        torch.cuda.empty_cache()
+
+    import ctypes as C
+    out = {"sgs_grid": "1024 x 32x32x60 (C2) and 8192 x 32x1x60 (C4)",
+           "sgs_method": "%d warm-up calls, median of %d event-timed calls" % (warmup, n)}
+    grid(1024, 32, 32, 60, "", out, True)
+    grid(8192, 32, 1, 60, "_c4", out, True)
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "sgs"]:
+        print(json.dumps(sgs_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "fluxprof"]:
         print(json.dumps(fluxprof_timing(dev)))
         sys.exit(0)
