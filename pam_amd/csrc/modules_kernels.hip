@@ -400,6 +400,109 @@ __global__ void __launch_bounds__(64) perturb_temperature_kernel(int nens, int n
 
 extern "C" int pam_amd_set_last_error_(int code, const char *msg);   // defined in awfl_kernels.hip
 
+// ------------------------------------------------------------------------------------------------
+// What the entry points below share on the host: how an error is reported, the checks several modules make in the same words, the
+// shape of the (members, slots) workgroup, and the per-device scratch.  No device code.
+namespace {
+// "<who>: <msg>" becomes the last error; the code (PAM_AMD_EINVAL where none is given) is returned
+int module_error(int code, const char *who, const char *msg) { return pam_amd_set_last_error_(code, (std::string(who) + ": " + msg).c_str()); }
+int module_error(const char *who, const char *msg) { return module_error(PAM_AMD_EINVAL, who, msg); }
+
+// an error the runtime holds after a launch
+int stats_launch_check(const char *who) {
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return module_error(PAM_AMD_ENOGPU, who, hipGetErrorString(err));
+  return PAM_AMD_OK;
+}
+
+// the first HIP call of an entry point: every check of the arguments alone comes before it
+int require_device(const char *who) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+    return module_error(PAM_AMD_ENOGPU, who, "no HIP device available (this library has no CPU path)");
+  return PAM_AMD_OK;
+}
+
+// the sizes of a module whose grid is (member blocks, levels) and whose column index is an int
+int check_level_grid(const char *who, int nens, int nx, int ny, int nz) {
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return module_error(who, "nens, nx, ny and nz must be >= 1");
+  if ((long long)nx * ny > 0x7fffffffLL) return module_error(who, "ny x nx exceeds 2^31 - 1 columns");
+  if (nz > 65535) return module_error(who, "nz exceeds the grid (65535 levels)");
+  return PAM_AMD_OK;
+}
+
+// [p, p + n doubles) of every array of a call, to refuse an output that shares memory with an input or with another output
+struct Span { const double *p; long long n; bool out; };
+bool spans_overlap(const std::vector<Span> &spans) {
+  for (size_t i = 0; i < spans.size(); i++)
+    for (size_t j = i + 1; j < spans.size(); j++) {
+      if (!spans[i].out && !spans[j].out) continue;
+      const uintptr_t a = (uintptr_t)spans[i].p, b = (uintptr_t)spans[j].p;
+      if (a < b + (uintptr_t)spans[j].n * sizeof(double) && b < a + (uintptr_t)spans[i].n * sizeof(double)) return true;
+    }
+  return false;
+}
+
+// the workgroup of the slot kernels (the comment at MOD_NS): block = (ME members, slots), ME = min(nens, 64); grid = (blocks of ME
+// members, rows).  block.x is ME and grid.x the number of member blocks for a caller that builds its own grid.
+struct SlotShape { dim3 grid, block; };
+SlotShape slot_block_shape(int nens, int rows, int slots = MOD_NS) {
+  const int ME = nens < 64 ? nens : 64;
+  return {dim3((unsigned)((nens + ME - 1) / ME), (unsigned)rows), dim3((unsigned)ME, (unsigned)slots)};
+}
+
+// The per-device scratch: one slot per (user, device), grown on demand, freed by pam_amd_modules_finalize().  The slot of the CURRENT
+// device serves a call, and its mutex is held by the caller while the slot may change or its memory is handed to launches: for the
+// whole call by the users whose call ends in a synchronisation (validate, diagnostics, hyperdiffusion's workspace path), so that two
+// host threads never share a scratch; over the launches only by column diagnostics and SGS, which synchronise nothing, so that calls
+// on ONE device must be ordered by the caller (one stream, or events between streams) -- as they are for any two calls that write
+// the same outputs.  Callers on different devices never wait for each other.  Growing frees the old array, which waits for the device.
+constexpr int MAX_DEVICES = 64;
+enum ScratchUser { SCRATCH_VALIDATE, SCRATCH_DIAGNOSTICS, SCRATCH_HYPERDIFFUSION, SCRATCH_COLUMN_DIAGNOSTICS, SCRATCH_SGS, SCRATCH_USERS };
+struct DeviceScratch { std::mutex m; void *p = nullptr; size_t bytes = 0; };
+DeviceScratch g_scratch[SCRATCH_USERS][MAX_DEVICES];
+
+// the slot of `user` on the current device (-> *device where asked); null where the runtime names none, or one past MAX_DEVICES
+DeviceScratch *scratch_slot(ScratchUser user, int *device = nullptr) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return nullptr;
+  if (device) *device = dev;
+  return &g_scratch[user][dev];
+}
+
+// at least `bytes` in the slot, its mutex held: a smaller slot is freed and allocated anew, at exactly `bytes` (floor == 0) or at the
+// smallest floor * 2^k that holds them.  Null after a failed allocation, which leaves the slot empty and the runtime's error cleared.
+void *scratch_reserve(DeviceScratch &s, size_t bytes, size_t floor) {
+  if (s.bytes < bytes) {
+    size_t want = floor ? floor : bytes;
+    while (want < bytes) want *= 2;
+    if (s.p) (void)hipFree(s.p);
+    s.p = nullptr;
+    s.bytes = 0;
+    if (hipMalloc(&s.p, want) != hipSuccess) { (void)hipGetLastError(); s.p = nullptr; return nullptr; }
+    s.bytes = want;
+  }
+  return s.p;
+}
+
+void scratch_free_all() {
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  for (auto &user : g_scratch)
+    for (int d = 0; d < MAX_DEVICES; d++) {
+      DeviceScratch &s = user[d];
+      std::lock_guard lk(s.m);
+      if (s.p) {
+        if (d != cur) (void)hipSetDevice(d);
+        (void)hipFree(s.p);
+        s.p = nullptr;
+        s.bytes = 0;
+        if (d != cur && cur >= 0) (void)hipSetDevice(cur);
+      }
+    }
+}
+}  // namespace
+
 extern "C" int pam_amd_sponge_layer(int nens, int nx, int ny, int nz, int num_fields, double *const *fields,
                                     const double *zint, const double *zmid, double crm_dt, int num_layers, double time_scale,
                                     double *workspace, void *stream) {
@@ -410,9 +513,7 @@ extern "C" int pam_amd_sponge_layer(int nens, int nx, int ny, int nz, int num_fi
   if (num_layers < 1 || num_layers > nz)
     return pam_amd_set_last_error_(PAM_AMD_EINVAL, "sponge_layer: sponge_num_layers must be in [1, nz]");
   if (!(time_scale > 0)) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "sponge_layer: sponge_time_scale must be positive");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "sponge_layer: no HIP device available (this library has no CPU path)");
+  if (int rc = require_device("sponge_layer")) return rc;
   FieldPtrs F;
   for (int i = 0; i < MAX_FIELDS; i++) F.p[i] = nullptr;
   for (int i = 0; i < num_fields; i++) {
@@ -421,8 +522,8 @@ extern "C" int pam_amd_sponge_layer(int nens, int nx, int ny, int nz, int num_fi
   }
   hipStream_t s = (hipStream_t)stream;
   (void)workspace;      // (the horizontal means live in the workgroups since ABI 5; the argument is kept for callers of ABI <= 4)
-  const int ME = nens < 64 ? nens : 64;
-  const dim3 grid((unsigned)((nens + ME - 1) / ME), (unsigned)num_layers, (unsigned)num_fields), block((unsigned)ME, (unsigned)MOD_NS);
+  const SlotShape shape = slot_block_shape(nens, num_layers);
+  const dim3 grid(shape.grid.x, shape.grid.y, (unsigned)num_fields), block = shape.block;
   hipLaunchKernelGGL(sponge_kernel, grid, block, 0, s, F, nens, nx * ny, nz, num_layers, zint, zmid, crm_dt / time_scale);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, hipGetErrorString(err));
@@ -436,10 +537,7 @@ int kessler_check(int nens, int nx, int ny, int nz, const void *a, const void *b
   if (!a || !b || !c || !d || !e || !f || !g) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "kessler: null pointer");
   if (!(dt > 0) || !(R_d > 0) || !(R_v > 0) || !(cp_d > 0) || !(p0 > 0))
     return pam_amd_set_last_error_(PAM_AMD_EINVAL, "kessler: dt and the constants must be positive");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "kessler: no HIP device available (this library has no CPU path)");
-  return PAM_AMD_OK;
+  return require_device("kessler");
 }
 
 // the tables of pow_pos_fast on the device that holds the caller's arrays (`ref`: any of them; built once per device and process, 3.5 KB;
@@ -454,7 +552,7 @@ const PowTab *kessler_pow_tab(const void *ref) {
   else (void)hipGetLastError();
   if (hipGetDevice(&cur) != hipSuccess) return nullptr;
   if (dev < 0) dev = cur;
-  std::lock_guard<std::mutex> lk(g_tab_mutex);
+  std::lock_guard lk(g_tab_mutex);
   if ((int)g_tabs.size() <= dev) g_tabs.resize(dev + 1, nullptr);
   if (!g_tabs[dev]) {
     PowTab host;
@@ -488,20 +586,11 @@ int kessler_read_dt_max(const double *slot, hipStream_t s, double *out) {
   return PAM_AMD_OK;
 }
 
-void validate_scratch_free();   // the result scratch of pam_amd_validate_fields, defined with it below
-void diagnostics_scratch_free();   // the scratch of pam_amd_field_diagnostics, the same
-void hd_workspace_free();          // the workspace of pam_amd_hyperdiffusion's two-launch path, the same
-void cd_workspace_free();          // the workspace of pam_amd_column_diagnostics' column values, the same
-void sgs_workspace_free();         // the workspace of pam_amd_sgs_smag_diffuse's c' on the path without LDS, the same
 }  // namespace
 
 extern "C" int pam_amd_modules_finalize(void) {
-  validate_scratch_free();
-  diagnostics_scratch_free();
-  hd_workspace_free();
-  cd_workspace_free();
-  sgs_workspace_free();
-  std::lock_guard<std::mutex> lk(g_tab_mutex);
+  scratch_free_all();
+  std::lock_guard lk(g_tab_mutex);
   int cur = -1;
   (void)hipGetDevice(&cur);
   for (size_t d = 0; d < g_tabs.size(); d++)
@@ -573,14 +662,11 @@ namespace {
 int gcm_check(const char *who, int nens, int nx, int ny, int nz, const void *const *a, int na, const void *const *b, int nb,
               const void *const *c, int nc) {
   if (nens < 1 || nx < 1 || ny < 1 || nz < 1 || !a || !b || !c)
-    return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": bad dimensions or null pointer table").c_str());
-  for (int i = 0; i < na; i++) if (!a[i]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": null CRM field pointer").c_str());
-  for (int i = 0; i < nb; i++) if (!b[i]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": null GCM column pointer").c_str());
-  for (int i = 0; i < nc; i++) if (!c[i]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": null tendency pointer").c_str());
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": no HIP device available (this library has no CPU path)").c_str());
-  return PAM_AMD_OK;
+    return module_error(who, "bad dimensions or null pointer table");
+  for (int i = 0; i < na; i++) if (!a[i]) return module_error(who, "null CRM field pointer");
+  for (int i = 0; i < nb; i++) if (!b[i]) return module_error(who, "null GCM column pointer");
+  for (int i = 0; i < nc; i++) if (!c[i]) return module_error(who, "null tendency pointer");
+  return require_device(who);
 }
 }  // namespace
 
@@ -593,8 +679,7 @@ extern "C" int pam_amd_gcm_forcing_compute(int nens, int nx, int ny, int nz, con
   for (int i = 0; i < 10; i++) { C.p[i] = const_cast<double *>(crm[i]); G.p[i] = const_cast<double *>(gcm[i]); }
   for (int i = 0; i < 14; i++) T.p[i] = tend[i];
   hipStream_t s = (hipStream_t)stream;
-  const int ME = nens < 64 ? nens : 64;
-  const dim3 grid((unsigned)((nens + ME - 1) / ME), (unsigned)nz), block((unsigned)ME, (unsigned)GCM_NS);
+  const auto [grid, block] = slot_block_shape(nens, nz, GCM_NS);
   const bool small = (long long)nz * ny * nx * nens < (1ll << 29);
   if (small) hipLaunchKernelGGL(gcm_forcing_compute_kernel<unsigned>, grid, block, 0, s, nens, nx * ny, nz, C, G, T, 1.0 / gcm_physics_dt);
   else hipLaunchKernelGGL(gcm_forcing_compute_kernel<long long>, grid, block, 0, s, nens, nx * ny, nz, C, G, T, 1.0 / gcm_physics_dt);
@@ -618,8 +703,7 @@ extern "C" int pam_amd_gcm_forcing_apply(int nens, int nx, int ny, int nz, doubl
   double *glob = workspace + 6 * n2;
   int *flags = (int *)(glob + 2 * (long long)nens);
   if (hipMemsetAsync(flags, 0, 8 * sizeof(int), s) != hipSuccess) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, hipGetErrorString(hipGetLastError()));
-  const int ME = nens < 64 ? nens : 64;
-  const dim3 grid((unsigned)((nens + ME - 1) / ME), (unsigned)nz), block((unsigned)ME, (unsigned)GCM_NS_APPLY);
+  const auto [grid, block] = slot_block_shape(nens, nz, GCM_NS_APPLY);
   if (ncell < (1ll << 29))
     hipLaunchKernelGGL(gcm_forcing_apply_kernel<unsigned>, grid, block, 0, s, nens, nx * ny, nz, C, G, T, dz, crm_dt, 1.0 / gcm_physics_dt,
                        workspace, flags);
@@ -664,9 +748,7 @@ extern "C" int pam_amd_broadcast_initial_gcm_column(int nens, int nx, int ny, in
     if (!gcm[f] || !crm[f]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "broadcast_initial_gcm_column: null field pointer");
     F.crm[f] = crm[f]; F.gcm[f] = gcm[f];
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "broadcast_initial_gcm_column: no HIP device available (this library has no CPU path)");
+  if (int rc = require_device("broadcast_initial_gcm_column")) return rc;
   const long long per_level = (long long)ny * nx * nens, ncell = per_level * nz;
   hipLaunchKernelGGL(broadcast_gcm_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nens, per_level,
                      ncell, num_fields, F);
@@ -679,9 +761,7 @@ extern "C" int pam_amd_perturb_temperature(int nens, int nx, int ny, int nz, dou
                                            void *stream) {
   if (nens < 1 || nx < 1 || ny < 1 || nz < 1 || !temp || !id)
     return pam_amd_set_last_error_(PAM_AMD_EINVAL, "perturb_temperature: bad dimensions or null pointer");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "perturb_temperature: no HIP device available (this library has no CPU path)");
+  if (int rc = require_device("perturb_temperature")) return rc;
   const int num_levels = nz / 4;
   if (num_levels == 0) return PAM_AMD_OK;
   const long long n = (long long)num_levels * nens;
@@ -772,9 +852,7 @@ extern "C" int pam_amd_supercell_init(int nz, const double *vert_interface, doub
     return pam_amd_set_last_error_(PAM_AMD_EINVAL, "supercell_init: bad nz or null pointer");
   const size_t lds = (size_t)nz * 9 * sizeof(double);
   if (lds > 160 * 1024) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "supercell_init: more than 2275 levels");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "supercell_init: no HIP device available (this library has no CPU path)");
+  if (int rc = require_device("supercell_init")) return rc;
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute((const void *)supercell_init_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "supercell_init: cannot raise the LDS limit");
@@ -883,12 +961,6 @@ __global__ void __launch_bounds__(64 * MOD_NS) surface_friction_kernel(int nens,
   }
 }
 
-int moist_surface_device_check(const char *who) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": no HIP device available (this library has no CPU path)").c_str());
-  return PAM_AMD_OK;
-}
 }  // namespace
 
 extern "C" int pam_amd_saturation_adjustment(int nens, int nx, int ny, int nz, const double *rho_d, double *rho_v, double *rho_c,
@@ -906,7 +978,7 @@ extern "C" int pam_amd_saturation_adjustment(int nens, int nx, int ny, int nz, c
     if (!massy[i]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "saturation_adjustment: null tracer pointer");
     M.p[i] = massy[i];
   }
-  if (int rc = moist_surface_device_check("saturation_adjustment")) return rc;
+  if (int rc = require_device("saturation_adjustment")) return rc;
   const long long ncell = (long long)nz * ny * nx * nens;
   hipLaunchKernelGGL(saturation_adjustment_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ncell, rho_d,
                      rho_v, rho_c, temp, num_massy, M, R_v, cp_d, cp_v, cp_l);
@@ -922,8 +994,8 @@ extern "C" int pam_amd_surface_friction_init(int nens, int nx, int ny, int nz, c
   if (nens < 1 || nx < 1 || ny < 1 || nz < 1 || !rho_d || !rho_v || !zmid || !gcm_uvel || !gcm_vvel || !tau_in || !bflx_in || !z0 ||
       !sfc_bflx || !sfc_mom_flx_u || !sfc_mom_flx_v)
     return pam_amd_set_last_error_(PAM_AMD_EINVAL, "surface_friction_init: bad dimensions or null pointer");
-  if (int rc = moist_surface_device_check("surface_friction_init")) return rc;
-  const int ME = nens < 64 ? nens : 64;
+  if (int rc = require_device("surface_friction_init")) return rc;
+  const int ME = (int)slot_block_shape(nens, 1).block.x;
   hipLaunchKernelGGL(surface_friction_init_kernel, dim3((unsigned)((nens + ME - 1) / ME)), dim3((unsigned)ME, (unsigned)MOD_NS), 0,
                      (hipStream_t)stream, nens, nx * ny, rho_d, rho_v, zmid, gcm_uvel, gcm_vvel, tau_in, bflx_in, z0, sfc_bflx,
                      sfc_mom_flx_u, sfc_mom_flx_v);
@@ -941,8 +1013,9 @@ extern "C" int pam_amd_surface_friction_compute(int nens, int nx, int ny, int nz
     return pam_amd_set_last_error_(PAM_AMD_EINVAL, "compute_surface_friction: bad dimensions or null pointer");
   if (nz < 3)
     return pam_amd_set_last_error_(PAM_AMD_EINVAL, "compute_surface_friction: nz >= 3 required (the surface density is extrapolated from levels 0-2)");
-  if (int rc = moist_surface_device_check("compute_surface_friction")) return rc;
-  const int ME = nens < 64 ? nens : 64, nblk = (nens + ME - 1) / ME, ncol = nx * ny;
+  if (int rc = require_device("compute_surface_friction")) return rc;
+  const SlotShape shape = slot_block_shape(nens, 1);
+  const int ME = (int)shape.block.x, nblk = (int)shape.grid.x, ncol = nx * ny;
   // column chunks: ~512 workgroups in all (two per CU), each chunk at least 64 columns (four per slot)
   int nchunk = (512 + nblk - 1) / nblk;
   if (nchunk > (ncol + 63) / 64) nchunk = (ncol + 63) / 64;
@@ -1031,12 +1104,6 @@ __global__ void __launch_bounds__(256) time_average_kernel(TavgTable T, double f
 
 constexpr long long IDX32_LIMIT = 1LL << 31;
 
-int stats_launch_check(const char *who) {
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": " + hipGetErrorString(err)).c_str());
-  return PAM_AMD_OK;
-}
-
 // the element-wise launches of time_average_zero / time_average_accumulate over an already validated list
 template <bool ZERO>
 int time_average_launch(const char *who, int num_fields, const long long *size, const double *const *var, double *const *tavg,
@@ -1067,10 +1134,10 @@ int time_average_launch(const char *who, int num_fields, const long long *size, 
 
 int time_average_check(const char *who, int num_fields, const long long *size, double *const *tavg) {
   if (num_fields < 1 || !size || !tavg)
-    return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": bad num_fields or null pointer table").c_str());
+    return module_error(who, "bad num_fields or null pointer table");
   for (int f = 0; f < num_fields; f++) {
-    if (size[f] < 1) return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": every size must be >= 1").c_str());
-    if (!tavg[f]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": null time-average pointer").c_str());
+    if (size[f] < 1) return module_error(who, "every size must be >= 1");
+    if (!tavg[f]) return module_error(who, "null time-average pointer");
   }
   return PAM_AMD_OK;
 }
@@ -1086,7 +1153,7 @@ extern "C" int pam_amd_horizontal_average(int nens, int num_fields, const int *n
     if (!in[f] || !out[f]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "horizontal_average: null field pointer");
     if (nblk * nz[f] > 0x7fffffffLL) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "horizontal_average: nz x member blocks exceeds the grid");
   }
-  if (int rc = moist_surface_device_check("horizontal_average")) return rc;
+  if (int rc = require_device("horizontal_average")) return rc;
   for (int f0 = 0; f0 < num_fields; f0 += STATS_TABLE) {
     const int nf = std::min(STATS_TABLE, num_fields - f0);
     HavgTable T;
@@ -1115,7 +1182,7 @@ extern "C" int pam_amd_horizontal_average(int nens, int num_fields, const int *n
 
 extern "C" int pam_amd_time_average_zero(int num_fields, const long long *size, double *const *tavg, void *stream) {
   if (int rc = time_average_check("time_average_zero", num_fields, size, tavg)) return rc;
-  if (int rc = moist_surface_device_check("time_average_zero")) return rc;
+  if (int rc = require_device("time_average_zero")) return rc;
   return time_average_launch<true>("time_average_zero", num_fields, size, nullptr, tavg, 0.0, stream);
 }
 
@@ -1126,7 +1193,7 @@ extern "C" int pam_amd_time_average_accumulate(int num_fields, const long long *
   for (int f = 0; f < num_fields; f++)
     if (!var[f]) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "time_average_accumulate: null field pointer");
   if (!std::isfinite(factor)) return pam_amd_set_last_error_(PAM_AMD_EINVAL, "time_average_accumulate: factor must be finite");
-  if (int rc = moist_surface_device_check("time_average_accumulate")) return rc;
+  if (int rc = require_device("time_average_accumulate")) return rc;
   return time_average_launch<false>("time_average_accumulate", num_fields, size, var, tavg, factor, stream);
 }
 
@@ -1174,42 +1241,9 @@ __global__ void __launch_bounds__(vd::THREADS) validate_kernel(ValidateTable T, 
     }
 }
 
-// the 48 bytes per field the kernel writes: per device, grown on demand, freed by pam_amd_modules_finalize().  A device's mutex is
-// held for a whole call on that device (which ends in a synchronisation anyway), so two host threads never share a scratch and
-// callers on different devices do not wait for each other.
-constexpr int VALIDATE_MAX_DEVICES = 64;
-struct ValidateScratch { std::mutex m; unsigned long long *p = nullptr; long long fields = 0; };
-ValidateScratch g_validate_scratch[VALIDATE_MAX_DEVICES];
-
-// the scratch `s` of the CURRENT device (its mutex held), at least `fields` fields large
-unsigned long long *validate_scratch(ValidateScratch &s, long long fields) {
-  if (s.fields < fields) {
-    long long want = 256;
-    while (want < fields) want *= 2;
-    if (s.p) (void)hipFree(s.p);
-    s.p = nullptr;
-    s.fields = 0;
-    if (hipMalloc((void **)&s.p, (size_t)want * 6 * sizeof(unsigned long long)) != hipSuccess) { s.p = nullptr; return nullptr; }
-    s.fields = want;
-  }
-  return s.p;
-}
-
-void validate_scratch_free() {
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  for (int d = 0; d < VALIDATE_MAX_DEVICES; d++) {
-    ValidateScratch &s = g_validate_scratch[d];
-    std::lock_guard<std::mutex> lk(s.m);
-    if (s.p) {
-      if (d != cur) (void)hipSetDevice(d);
-      (void)hipFree(s.p);
-      s.p = nullptr;
-      s.fields = 0;
-      if (d != cur && cur >= 0) (void)hipSetDevice(cur);
-    }
-  }
-}
+// the 48 bytes per field the kernel writes lie in the per-device scratch (above), its mutex held for the whole call; the scratch grows
+// from 256 fields by doubling
+constexpr size_t VALIDATE_FIELD_BYTES = 6 * sizeof(unsigned long long);
 }  // namespace
 
 extern "C" int pam_amd_validate_fields(int num_fields, const int *kind, const long long *size, const void *const *data,
@@ -1224,28 +1258,27 @@ extern "C" int pam_amd_validate_fields(int num_fields, const int *kind, const lo
     if ((unsigned long long)(uintptr_t)data[f] % (unsigned)vd::kind_bytes(kind[f]) != 0)
       return pam_amd_set_last_error_(PAM_AMD_EINVAL, "validate: field pointer not aligned to its element size");
   }
-  if (int rc = moist_surface_device_check("validate")) return rc;
+  if (int rc = require_device("validate")) return rc;
   // the launches, the scratch and `stream` belong to the current device: every field must live there (memory whose device the
   // runtime cannot name, such as host-registered memory, is taken as given)
   int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess || cur < 0 || cur >= VALIDATE_MAX_DEVICES)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "validate: no current HIP device");
+  DeviceScratch *scratch = scratch_slot(SCRATCH_VALIDATE, &cur);
+  if (!scratch) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "validate: no current HIP device");
   for (int f = 0; f < num_fields; f++) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, data[f]) != hipSuccess) { (void)hipGetLastError(); continue; }
     if (attr.type == hipMemoryTypeDevice && attr.device != cur)
       return pam_amd_set_last_error_(PAM_AMD_EINVAL, "validate: every field must live on the current device (hipSetDevice to the fields' device first)");
   }
-  ValidateScratch &scratch = g_validate_scratch[cur];
-  std::lock_guard<std::mutex> lk(scratch.m);
-  unsigned long long *res = validate_scratch(scratch, num_fields);
+  std::lock_guard lk(scratch->m);
+  unsigned long long *res = (unsigned long long *)scratch_reserve(*scratch, num_fields * VALIDATE_FIELD_BYTES, 256 * VALIDATE_FIELD_BYTES);
   if (!res) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "validate: device allocation of the result scratch failed");
   hipStream_t s = (hipStream_t)stream;
   const size_t n3 = (size_t)num_fields * 3;
   unsigned long long *d_count = res, *d_first = res + n3;
   if (hipMemsetAsync(d_count, 0, n3 * sizeof(unsigned long long), s) != hipSuccess ||
       hipMemsetAsync(d_first, 0xff, n3 * sizeof(unsigned long long), s) != hipSuccess)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string("validate: ") + hipGetErrorString(hipGetLastError())).c_str());
+    return module_error(PAM_AMD_ENOGPU, "validate", hipGetErrorString(hipGetLastError()));
   for (int f0 = 0; f0 < num_fields; f0 += STATS_TABLE) {
     const int nf = std::min(STATS_TABLE, num_fields - f0);
     ValidateTable T;
@@ -1266,7 +1299,7 @@ extern "C" int pam_amd_validate_fields(int num_fields, const int *kind, const lo
   std::vector<unsigned long long> host(2 * n3);
   if (hipMemcpyAsync(host.data(), res, 2 * n3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string("validate: ") + hipGetErrorString(hipGetLastError())).c_str());
+    return module_error(PAM_AMD_ENOGPU, "validate", hipGetErrorString(hipGetLastError()));
   for (size_t i = 0; i < n3; i++) {
     count[i] = (long long)host[i];
     first[i] = (long long)host[n3 + i];      // ~0 (nothing found) is -1
@@ -1465,40 +1498,7 @@ __global__ void __launch_bounds__(dg::THREADS) diag_member_finish_kernel(DiagTab
   result[(long long)f * M + m] = dg::Result{e.vmin, e.vmax, sums[m], e.imin, e.imax, e.nans};
 }
 
-// the scratch: per device, grown on demand, freed by pam_amd_modules_finalize().  A device's mutex is held for a whole call on that
-// device (which ends in a synchronisation anyway), as for the validation scratch.
-constexpr int DIAG_MAX_DEVICES = 64;
-struct DiagScratch { std::mutex m; char *p = nullptr; long long bytes = 0; };
-DiagScratch g_diag_scratch[DIAG_MAX_DEVICES];
-
-char *diagnostics_scratch(DiagScratch &s, long long bytes) {
-  if (s.bytes < bytes) {
-    long long want = 1 << 16;
-    while (want < bytes) want *= 2;
-    if (s.p) (void)hipFree(s.p);
-    s.p = nullptr;
-    s.bytes = 0;
-    if (hipMalloc((void **)&s.p, (size_t)want) != hipSuccess) { (void)hipGetLastError(); s.p = nullptr; return nullptr; }
-    s.bytes = want;
-  }
-  return s.p;
-}
-
-void diagnostics_scratch_free() {
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  for (int d = 0; d < DIAG_MAX_DEVICES; d++) {
-    DiagScratch &s = g_diag_scratch[d];
-    std::lock_guard<std::mutex> lk(s.m);
-    if (s.p) {
-      if (d != cur) (void)hipSetDevice(d);
-      (void)hipFree(s.p);
-      s.p = nullptr;
-      s.bytes = 0;
-      if (d != cur && cur >= 0) (void)hipSetDevice(cur);
-    }
-  }
-}
+// the scratch is the per-device one (above), its mutex held for the whole call; it grows from 64 KB by doubling
 }  // namespace
 
 extern "C" int pam_amd_field_diagnostics(int num_fields, const int *kind, const long long *size, const void *const *data, int members,
@@ -1522,10 +1522,10 @@ extern "C" int pam_amd_field_diagnostics(int num_fields, const int *kind, const 
     if ((unsigned long long)(uintptr_t)data[f] % (kind[f] == dg::KIND_DOUBLE ? 8u : 4u) != 0)
       return pam_amd_set_last_error_(PAM_AMD_EINVAL, "field_diagnostics: field pointer not aligned to its element size");
   }
-  if (int rc = moist_surface_device_check("field_diagnostics")) return rc;
+  if (int rc = require_device("field_diagnostics")) return rc;
   int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess || cur < 0 || cur >= DIAG_MAX_DEVICES)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "field_diagnostics: no current HIP device");
+  DeviceScratch *scratch = scratch_slot(SCRATCH_DIAGNOSTICS, &cur);
+  if (!scratch) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "field_diagnostics: no current HIP device");
   for (int f = 0; f < num_fields; f++) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, data[f]) != hipSuccess) { (void)hipGetLastError(); continue; }
@@ -1547,9 +1547,8 @@ extern "C" int pam_amd_field_diagnostics(int num_fields, const int *kind, const 
   const long long result_off = bytes;
   const size_t nres = (size_t)num_fields * (size_t)M;
   bytes += (long long)(nres * sizeof(dg::Result));
-  DiagScratch &scratch = g_diag_scratch[cur];
-  std::lock_guard<std::mutex> lk(scratch.m);
-  char *base = diagnostics_scratch(scratch, bytes);
+  std::lock_guard lk(scratch->m);
+  char *base = (char *)scratch_reserve(*scratch, (size_t)bytes, 1 << 16);
   if (!base) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "field_diagnostics: device allocation of the scratch failed");
   dg::Result *d_result = (dg::Result *)(base + result_off);
   hipStream_t s = (hipStream_t)stream;
@@ -1580,7 +1579,7 @@ extern "C" int pam_amd_field_diagnostics(int num_fields, const int *kind, const 
   std::vector<dg::Result> host(nres);
   if (hipMemcpyAsync(host.data(), d_result, nres * sizeof(dg::Result), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string("field_diagnostics: ") + hipGetErrorString(hipGetLastError())).c_str());
+    return module_error(PAM_AMD_ENOGPU, "field_diagnostics", hipGetErrorString(hipGetLastError()));
   for (size_t i = 0; i < nres; i++) {
     vmin[i] = host[i].vmin;
     vmax[i] = host[i].vmax;
@@ -1742,10 +1741,6 @@ struct VerticalInterpHandle {
   double *d_member;               // device: recon_lo then recon_hi, T = nens (distinct columns, or sharing switched off)
 };
 
-int vi_error(int code, const char *who, const std::string &what) {
-  return pam_amd_set_last_error_(code, (std::string(who) + ": " + what).c_str());
-}
-
 template <int ORD>
 void vi_build_tables(VerticalInterpHandle &h, const double *zint) {
   using D = vi::Dims<ORD>;
@@ -1785,14 +1780,14 @@ int vi_upload(const char *who, VerticalInterpHandle &h, int T, hipStream_t s, do
   double *d = nullptr;
   if (hipMalloc((void **)&d, (n_lo + n_hi) * sizeof(double)) != hipSuccess) {
     (void)hipGetLastError();
-    return vi_error(PAM_AMD_ENOMEM, who, "cannot allocate the reconstruction matrices on the device");
+    return module_error(PAM_AMD_ENOMEM, who, "cannot allocate the reconstruction matrices on the device");
   }
   if (hipMemcpyAsync(d, src_lo, n_lo * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(d + n_lo, src_hi, n_hi * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess) {
     const std::string msg = hipGetErrorString(hipGetLastError());
     (void)hipFree(d);
-    return vi_error(PAM_AMD_ENOGPU, who, msg);
+    return module_error(PAM_AMD_ENOGPU, who, msg.c_str());
   }
   *out = d;
   return PAM_AMD_OK;
@@ -1824,18 +1819,18 @@ extern "C" int pam_amd_vertical_interp_init(int ord, int nz, int nens, const dou
   const char *who = "vertical_interp_init";
   if (handle) *handle = nullptr;
   if (ord != 3 && ord != 5)
-    return vi_error(PAM_AMD_EINVAL, who, "ord must be 3 or 5 (the reference's sample_val for orders 7 and 9 is not an interpolation)");
-  if (nz < 1 || nens < 1) return vi_error(PAM_AMD_EINVAL, who, "nz and nens must be >= 1");
-  if (!zint || !handle) return vi_error(PAM_AMD_EINVAL, who, "null pointer");
-  if ((nens + 63) / 64 > 65535) return vi_error(PAM_AMD_EINVAL, who, "nens exceeds the grid (64 x 65535 members)");
-  if (int rc = moist_surface_device_check(who)) return rc;
+    return module_error(who, "ord must be 3 or 5 (the reference's sample_val for orders 7 and 9 is not an interpolation)");
+  if (nz < 1 || nens < 1) return module_error(who, "nz and nens must be >= 1");
+  if (!zint || !handle) return module_error(who, "null pointer");
+  if ((nens + 63) / 64 > 65535) return module_error(who, "nens exceeds the grid (64 x 65535 members)");
+  if (int rc = require_device(who)) return rc;
   hipStream_t s = (hipStream_t)stream;
   std::vector<double> z((size_t)(nz + 1) * nens);
   if (hipMemcpyAsync(z.data(), zint, z.size() * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return vi_error(PAM_AMD_ENOGPU, who, hipGetErrorString(hipGetLastError()));
+    return module_error(PAM_AMD_ENOGPU, who, hipGetErrorString(hipGetLastError()));
   for (int e = 0; e < nens; e++)
     if (!vi::column_ok(z.data() + e, nens, nz))
-      return vi_error(PAM_AMD_EINVAL, who, "member " + std::to_string(e) + ": the interfaces must be finite and strictly increasing");
+      return module_error(who, ("member " + std::to_string(e) + ": the interfaces must be finite and strictly increasing").c_str());
   VerticalInterpHandle *h = new VerticalInterpHandle();
   h->magic = VI_MAGIC;
   h->ord = ord; h->nz = nz; h->nens = nens;
@@ -1860,9 +1855,9 @@ extern "C" int pam_amd_vertical_interp_init(int ord, int nz, int nens, const dou
 extern "C" int pam_amd_vertical_interp_set_table_sharing(void *handle, int shared, void *stream) {
   const char *who = "vertical_interp_set_table_sharing";
   VerticalInterpHandle *h = vi_handle(handle);
-  if (!h) return vi_error(PAM_AMD_EINVAL, who, "not a handle of vertical_interp_init");
-  if (shared != 0 && shared != 1) return vi_error(PAM_AMD_EINVAL, who, "shared must be 0 or 1");
-  if (shared && !h->identical) return vi_error(PAM_AMD_EINVAL, who, "the members' interfaces differ: there is no shared table");
+  if (!h) return module_error(who, "not a handle of vertical_interp_init");
+  if (shared != 0 && shared != 1) return module_error(who, "shared must be 0 or 1");
+  if (shared && !h->identical) return module_error(who, "the members' interfaces differ: there is no shared table");
   if (!shared && !h->d_member)
     if (int rc = vi_upload(who, *h, h->nens, (hipStream_t)stream, &h->d_member)) return rc;
   h->shared = shared != 0;
@@ -1872,18 +1867,18 @@ extern "C" int pam_amd_vertical_interp_set_table_sharing(void *handle, int share
 extern "C" int pam_amd_vertical_interp_cells_to_edges(void *handle, int ny, int nx, const double *data, int bc_lower, int bc_upper,
                                                       double *edges, void *stream) {
   const char *who = "vertical_interp_cells_to_edges";
-  if (!handle) return vi_error(PAM_AMD_EINVAL, who, "null handle");
-  if (ny < 1 || nx < 1) return vi_error(PAM_AMD_EINVAL, who, "ny and nx must be >= 1");
-  if (!data || !edges) return vi_error(PAM_AMD_EINVAL, who, "null pointer");
-  if (data == edges) return vi_error(PAM_AMD_EINVAL, who, "data and edges must be different arrays");
+  if (!handle) return module_error(who, "null handle");
+  if (ny < 1 || nx < 1) return module_error(who, "ny and nx must be >= 1");
+  if (!data || !edges) return module_error(who, "null pointer");
+  if (data == edges) return module_error(who, "data and edges must be different arrays");
   if ((bc_lower != vi::BC_ZERO_GRADIENT && bc_lower != vi::BC_ZERO_VALUE) || (bc_upper != vi::BC_ZERO_GRADIENT && bc_upper != vi::BC_ZERO_VALUE))
-    return vi_error(PAM_AMD_EINVAL, who, "bc_lower and bc_upper must be 0 (zero gradient) or 1 (zero value)");
+    return module_error(who, "bc_lower and bc_upper must be 0 (zero gradient) or 1 (zero value)");
   VerticalInterpHandle *h = vi_handle(handle);
-  if (!h) return vi_error(PAM_AMD_EINVAL, who, "not a handle of vertical_interp_init");
+  if (!h) return module_error(who, "not a handle of vertical_interp_init");
   const long long ncol = (long long)ny * nx;
   if (ncol > 0x7fffff00LL || (ncol * h->nens + VI_FLAT - 1) / VI_FLAT > 0x7fffffffLL)
-    return vi_error(PAM_AMD_EINVAL, who, "ny x nx x nens exceeds the grid");
-  if (int rc = moist_surface_device_check(who)) return rc;
+    return module_error(who, "ny x nx x nens exceeds the grid");
+  if (int rc = require_device(who)) return rc;
   const bool narrow = (long long)(h->nz + 1) * ncol * h->nens < IDX32_LIMIT;
   hipStream_t s = (hipStream_t)stream;
   if (h->ord == 3 && narrow) vi_launch<3, unsigned>(*h, (int)ncol, data, bc_lower, bc_upper, edges, s);
@@ -1896,8 +1891,8 @@ extern "C" int pam_amd_vertical_interp_cells_to_edges(void *handle, int ny, int 
 extern "C" int pam_amd_vertical_interp_tables(void *handle, const double **recon_lo, const double **recon_hi, int *shared) {
   const char *who = "vertical_interp_tables";
   VerticalInterpHandle *h = vi_handle(handle);
-  if (!h) return vi_error(PAM_AMD_EINVAL, who, "not a handle of vertical_interp_init");
-  if (!recon_lo || !recon_hi || !shared) return vi_error(PAM_AMD_EINVAL, who, "null pointer");
+  if (!h) return module_error(who, "not a handle of vertical_interp_init");
+  if (!recon_lo || !recon_hi || !shared) return module_error(who, "null pointer");
   size_t nlo, nhi;
   vi_table_sizes(h->ord, &nlo, &nhi);
   const double *base = h->shared ? h->d_shared : h->d_member;
@@ -1910,7 +1905,7 @@ extern "C" int pam_amd_vertical_interp_tables(void *handle, const double **recon
 extern "C" int pam_amd_vertical_interp_finalize(void *handle) {
   if (!handle) return PAM_AMD_OK;
   VerticalInterpHandle *h = vi_handle(handle);
-  if (!h) return vi_error(PAM_AMD_EINVAL, "vertical_interp_finalize", "not a handle of vertical_interp_init");
+  if (!h) return module_error("vertical_interp_finalize", "not a handle of vertical_interp_init");
   if (h->d_shared) (void)hipFree(h->d_shared);
   if (h->d_member) (void)hipFree(h->d_member);
   h->magic = 0;
@@ -2023,7 +2018,7 @@ extern "C" int pam_amd_radiation_forced(int nens, int nx, int ny, int nz, int ra
     return pam_amd_set_last_error_(PAM_AMD_EINVAL, "radiation: nz x ny x nx x member blocks exceeds the grid");
   if (plugins_overlap(temp, ncell, rad_enthalpy_tend, nrad))
     return pam_amd_set_last_error_(PAM_AMD_EINVAL, "radiation: temp overlaps rad_enthalpy_tend");
-  if (int rc = moist_surface_device_check("radiation")) return rc;
+  if (int rc = require_device("radiation")) return rc;
   const dim3 grid((unsigned)(groups * nblk)), block(64 * RAD_WAVES);
   if (ncell < PLUGINS_NARROW_CELLS)
     hipLaunchKernelGGL((radiation_forced_kernel<unsigned>), grid, block, 0, (hipStream_t)stream, nens, nx, ny, (int)nrows, rad_nx, rad_ny,
@@ -2038,14 +2033,14 @@ extern "C" int pam_amd_compute_pressure(int nens, int nx, int ny, int nz, const 
                                         double R_d, double R_v, double *pressure, void *stream) {
   const char *who = "compute_pressure_array";
   if (nens < 1 || nx < 1 || ny < 1 || nz < 1)
-    return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": nens, nx, ny and nz must be >= 1").c_str());
-  if (!rho_d || !rho_v || !temp || !pressure) return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": null pointer").c_str());
+    return module_error(who, "nens, nx, ny and nz must be >= 1");
+  if (!rho_d || !rho_v || !temp || !pressure) return module_error(who, "null pointer");
   if (!std::isfinite(R_d) || !std::isfinite(R_v))
-    return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": R_d and R_v must be finite").c_str());
+    return module_error(who, "R_d and R_v must be finite");
   const long long ncell = (long long)nz * ny * nx * nens;
   if (plugins_overlap(pressure, ncell, rho_d, ncell) || plugins_overlap(pressure, ncell, rho_v, ncell) || plugins_overlap(pressure, ncell, temp, ncell))
-    return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": pressure overlaps an input").c_str());
-  if (int rc = moist_surface_device_check(who)) return rc;
+    return module_error(who, "pressure overlaps an input");
+  if (int rc = require_device(who)) return rc;
   // ~2048 workgroups of 256 (eight per CU), never more than the field needs
   const long long per_blk = 256LL * PRES_UNROLL, need = (ncell + per_blk - 1) / per_blk;
   const dim3 grid((unsigned)std::min(need, 2048LL)), block(256);
@@ -2066,7 +2061,6 @@ constexpr int COUPLING_GROUP = 8;                  // arrays that cross LDS per 
 constexpr long long COUPLING_NARROW = 1ll << 29;   // the largest array from this size on: the long long instances
 template <int LAYOUT> struct CouplingTile { static constexpr int TC = LAYOUT ? 16 : 64, TL = COUPLING_THREADS / TC, PITCH = TL + 1; };
 
-int coupling_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
 bool coupling_pos(double x) { return std::isfinite(x) && x > 0; }
 // force_wide: the layer's debug_wide_index switch; largest: the element count of its largest array
 bool coupling_narrow(bool force_wide, long long largest) { return !force_wide && largest < COUPLING_NARROW; }
@@ -2106,13 +2100,13 @@ int coupling_allocate(const char *who, const cw::Array<ARGS> (&table)[NA], long 
   double *base = nullptr;
   if (hipMalloc((void **)&base, (size_t)total * sizeof(double)) != hipSuccess) {
     (void)hipGetLastError();
-    return pam_amd_set_last_error_(PAM_AMD_ENOMEM, (std::string(who) + ": cannot allocate the workspace").c_str());
+    return module_error(PAM_AMD_ENOMEM, who, "cannot allocate the workspace");
   }
   hipLaunchKernelGGL((coupling_canary_kernel<CANARY>), dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, 0,
                      (unsigned long long *)base, total);
   if (hipDeviceSynchronize() != hipSuccess) {
     (void)hipFree(base);
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": " + hipGetErrorString(hipGetLastError())).c_str());
+    return module_error(PAM_AMD_ENOGPU, who, hipGetErrorString(hipGetLastError()));
   }
   w->doubles = total;
   w->base = base;
@@ -2129,22 +2123,22 @@ bool coupling_null_array(const cw::Array<ARGS> (&table)[NA], const ARGS &args, l
 
 template <class W, class ARGS> int coupling_workspace_args(void *ws, const char *who, ARGS *args) {
   W *w = coupling_ws<W>(ws);
-  if (!w) return coupling_error(who, W::NOT_ONE);
-  if (!args) return coupling_error(who, "null args");
+  if (!w) return module_error(who, W::NOT_ONE);
+  if (!args) return module_error(who, "null args");
   *args = w->args;
   return PAM_AMD_OK;
 }
 template <class W> int coupling_workspace_bytes(void *ws, const char *who, long long *bytes) {
   W *w = coupling_ws<W>(ws);
-  if (!w) return coupling_error(who, W::NOT_ONE);
-  if (!bytes) return coupling_error(who, "null bytes");
+  if (!w) return module_error(who, W::NOT_ONE);
+  if (!bytes) return module_error(who, "null bytes");
   *bytes = w->doubles * (long long)sizeof(double);
   return PAM_AMD_OK;
 }
 template <class W> int coupling_workspace_destroy(void *ws, const char *who) {
   if (!ws) return PAM_AMD_OK;
   W *w = coupling_ws<W>(ws);
-  if (!w) return coupling_error(who, W::NOT_ONE);
+  if (!w) return module_error(who, W::NOT_ONE);
   (void)hipFree(w->base);
   w->magic = 0;
   delete w;
@@ -2368,14 +2362,14 @@ extern "C" int pam_amd_shoc_debug_wide_index(int on) {
 
 extern "C" int pam_amd_shoc_workspace_create(int nens, int nx, int ny, int nz, int num_qtracers, int layout, void **ws) {
   const char *who = "shoc_workspace_create";
-  if (!ws) return coupling_error(who, "null ws");
+  if (!ws) return module_error(who, "null ws");
   *ws = nullptr;
-  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return coupling_error(who, "nens, nx, ny and nz must be >= 1");
-  if (num_qtracers < 0 || num_qtracers > sh::MAX_QTRACERS) return coupling_error(who, "num_qtracers must be 0 ... 7");
-  if (layout != 0 && layout != 1) return coupling_error(who, "layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)");
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return module_error(who, "nens, nx, ny and nz must be >= 1");
+  if (num_qtracers < 0 || num_qtracers > sh::MAX_QTRACERS) return module_error(who, "num_qtracers must be 0 ... 7");
+  if (layout != 0 && layout != 1) return module_error(who, "layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)");
   const long long ncol = (long long)ny * nx * nens;
-  if (ncol > 0x7fffffffLL - 64 || nz > 0x7ffffff0) return coupling_error(who, "ny x nx x nens must stay below 2^31");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (ncol > 0x7fffffffLL - 64 || nz > 0x7ffffff0) return module_error(who, "ny x nx x nens must stay below 2^31");
+  if (int rc = require_device(who)) return rc;
   std::unique_ptr<ShocWorkspace> w(new ShocWorkspace());
   w->nens = nens; w->nx = nx; w->ny = ny; w->nz = nz; w->ntr = num_qtracers; w->layout = layout;
   pam_amd_shoc_args_t &A = w->args;
@@ -2403,16 +2397,16 @@ extern "C" int pam_amd_shoc_pack(void *ws, const double *rho_d, const double *rh
   const char *who = "shoc_pack";
   if (!rho_d || !rho_v || !rho_c || !uvel || !vvel || !wvel || !temp || !tke || !wthv_sec || !tk || !tkh || !cldfrac || !sfc_mom_flx_u ||
       !sfc_mom_flx_v || !zint || !zmid)
-    return coupling_error(who, "null pointer");
-  if (!coupling_pos(xlen) || !coupling_pos(ylen)) return coupling_error(who, "xlen and ylen must be finite and positive");
+    return module_error(who, "null pointer");
+  if (!coupling_pos(xlen) || !coupling_pos(ylen)) return module_error(who, "xlen and ylen must be finite and positive");
   if (!coupling_pos(coupler_R_d) || !coupling_pos(coupler_R_v) || !coupling_pos(R_d) || !coupling_pos(cp_d) || !coupling_pos(p0) || !coupling_pos(grav) || !coupling_pos(latvap))
-    return coupling_error(who, "coupler_R_d, coupler_R_v, R_d, cp_d, p0, grav and latvap must be finite and positive");
+    return module_error(who, "coupler_R_d, coupler_R_v, R_d, cp_d, p0, grav and latvap must be finite and positive");
   ShocWorkspace *w = coupling_ws<ShocWorkspace>(ws);
-  if (!w) return coupling_error(who, ShocWorkspace::NOT_ONE);
-  if (w->ntr > 0 && !qtracers) return coupling_error(who, "null qtracers");
+  if (!w) return module_error(who, ShocWorkspace::NOT_ONE);
+  if (w->ntr > 0 && !qtracers) return module_error(who, "null qtracers");
   for (int tr = 0; tr < w->ntr; tr++)
-    if (!qtracers[tr]) return coupling_error(who, "null pointer in qtracers");
-  if (int rc = moist_surface_device_check(who)) return rc;
+    if (!qtracers[tr]) return module_error(who, "null pointer in qtracers");
+  if (int rc = require_device(who)) return rc;
   const PowTab *tab = kessler_pow_tab(w->base);
   if (!tab) return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "shoc_pack: cannot allocate the pow tables");
   const pam_amd_shoc_args_t &A = w->args;
@@ -2443,14 +2437,14 @@ extern "C" int pam_amd_shoc_unpack(void *ws, const double *rho_d, double *rho_v,
                                    double *inv_qc_relvar, double cp_d, double cv_d, double latvap, void *stream) {
   const char *who = "shoc_unpack";
   if (!rho_d || !rho_v || !rho_c || !uvel || !vvel || !temp || !tke || !wthv_sec || !tk || !tkh || !cldfrac || !inv_qc_relvar)
-    return coupling_error(who, "null pointer");
-  if (!coupling_pos(cp_d) || !coupling_pos(cv_d) || !coupling_pos(latvap)) return coupling_error(who, "cp_d, cv_d and latvap must be finite and positive");
+    return module_error(who, "null pointer");
+  if (!coupling_pos(cp_d) || !coupling_pos(cv_d) || !coupling_pos(latvap)) return module_error(who, "cp_d, cv_d and latvap must be finite and positive");
   ShocWorkspace *w = coupling_ws<ShocWorkspace>(ws);
-  if (!w) return coupling_error(who, ShocWorkspace::NOT_ONE);
-  if (w->ntr > 0 && !qtracers) return coupling_error(who, "null qtracers");
+  if (!w) return module_error(who, ShocWorkspace::NOT_ONE);
+  if (w->ntr > 0 && !qtracers) return module_error(who, "null qtracers");
   for (int tr = 0; tr < w->ntr; tr++)
-    if (!qtracers[tr]) return coupling_error(who, "null pointer in qtracers");
-  if (int rc = moist_surface_device_check(who)) return rc;
+    if (!qtracers[tr]) return module_error(who, "null pointer in qtracers");
+  if (int rc = require_device(who)) return rc;
   const pam_amd_shoc_args_t &A = w->args;
   ShocCellSrc R = {};
   for (int a = 0; a < sh::U_MAX; a++) { R.p[a] = nullptr; R.comp[a] = 0; R.ncomp[a] = 1; }
@@ -2476,14 +2470,14 @@ extern "C" int pam_amd_shoc_unpack(void *ws, const double *rho_d, double *rho_v,
 extern "C" int pam_amd_shoc_main_standin(const pam_amd_shoc_args_t *args, void *user) {
   (void)user;
   const char *who = "shoc_main_standin";
-  if (!args) return coupling_error(who, "null args");
+  if (!args) return module_error(who, "null args");
   const pam_amd_shoc_args_t &A = *args;
-  if (A.ncol < 1 || A.nlev < 1 || A.nlevi != A.nlev + 1) return coupling_error(who, "ncol, nlev must be >= 1 and nlevi = nlev + 1");
-  if (A.ncol > 0x7fffffff - 64 || A.nlev > 0x7ffffff0) return coupling_error(who, "ncol must stay below 2^31 - 64");
-  if (A.num_qtracers < 0 || A.num_qtracers > sh::MAX_QTRACERS) return coupling_error(who, "num_qtracers must be 0 ... 7");
-  if (A.layout != 0 && A.layout != 1) return coupling_error(who, "layout must be 0 or 1");
-  if (coupling_null_array(cw::SHOC_TABLE, A, A.ncol, A.nlev, A.num_qtracers, cw::SHOC_ZERO_SIZE)) return coupling_error(who, "null pointer in args");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (A.ncol < 1 || A.nlev < 1 || A.nlevi != A.nlev + 1) return module_error(who, "ncol, nlev must be >= 1 and nlevi = nlev + 1");
+  if (A.ncol > 0x7fffffff - 64 || A.nlev > 0x7ffffff0) return module_error(who, "ncol must stay below 2^31 - 64");
+  if (A.num_qtracers < 0 || A.num_qtracers > sh::MAX_QTRACERS) return module_error(who, "num_qtracers must be 0 ... 7");
+  if (A.layout != 0 && A.layout != 1) return module_error(who, "layout must be 0 or 1");
+  if (coupling_null_array(cw::SHOC_TABLE, A, A.ncol, A.nlev, A.num_qtracers, cw::SHOC_ZERO_SIZE)) return module_error(who, "null pointer in args");
+  if (int rc = require_device(who)) return rc;
   coupling_dispatch(A.layout, coupling_narrow(g_shoc_force_wide, shoc_largest(A.ncol, A.nlev, A.num_qtracers)), [&](auto, auto idx) {
     hipLaunchKernelGGL((shoc_standin_kernel<decltype(idx)>), dim3((unsigned)((A.ncol + 63) / 64)), dim3(64), 0, (hipStream_t)A.stream, A);
   });
@@ -2664,15 +2658,15 @@ extern "C" int pam_amd_p3_debug_wide_index(int on) {
 
 extern "C" int pam_amd_p3_workspace_create(int nens, int nx, int ny, int nz, int layout, int num_tend_out, void **ws) {
   const char *who = "p3_workspace_create";
-  if (!ws) return coupling_error(who, "null ws");
+  if (!ws) return module_error(who, "null ws");
   *ws = nullptr;
-  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return coupling_error(who, "nens, nx, ny and nz must be >= 1");
-  if (layout != 0 && layout != 1) return coupling_error(who, "layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)");
-  if (num_tend_out < 0 || num_tend_out > p3::MAX_TEND_OUT) return coupling_error(who, "num_tend_out must be 0 ... 49");
-  if (layout == 1 && num_tend_out != 0) return coupling_error(who, "num_tend_out must be 0 in layout 1 (pam::p3_main_cxx has no p3_tend_out)");
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return module_error(who, "nens, nx, ny and nz must be >= 1");
+  if (layout != 0 && layout != 1) return module_error(who, "layout must be 0 ((lev, col), column fastest) or 1 ((col, lev), level fastest)");
+  if (num_tend_out < 0 || num_tend_out > p3::MAX_TEND_OUT) return module_error(who, "num_tend_out must be 0 ... 49");
+  if (layout == 1 && num_tend_out != 0) return module_error(who, "num_tend_out must be 0 in layout 1 (pam::p3_main_cxx has no p3_tend_out)");
   const long long ncol = (long long)ny * nx * nens;
-  if (ncol > 0x7fffffffLL - 64 || nz > 0x7ffffff0) return coupling_error(who, "ny x nx x nens must stay below 2^31");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (ncol > 0x7fffffffLL - 64 || nz > 0x7ffffff0) return module_error(who, "ny x nx x nens must stay below 2^31");
+  if (int rc = require_device(who)) return rc;
   std::unique_ptr<P3Workspace> w(new P3Workspace());
   w->nens = nens; w->nx = nx; w->ny = ny; w->nz = nz; w->layout = layout; w->nout = num_tend_out;
   pam_amd_p3_args_t &A = w->args;
@@ -2698,15 +2692,15 @@ extern "C" int pam_amd_p3_pack(void *ws, const double *rho_d, double *rho_v, dou
                                double cp_v, double cp_l, double p0, double grav, void *stream) {
   const char *who = "p3_pack";
   if (!rho_d || !rho_v || !rho_c || !temp || !nccn_prescribed || !nc_nuceat_tend || !ni_activated || !q_prev || !t_prev || !zint)
-    return coupling_error(who, "null pointer");
+    return module_error(who, "null pointer");
   if (!coupling_pos(R_d) || !coupling_pos(R_v) || !coupling_pos(cp_d) || !coupling_pos(cp_l) || !coupling_pos(p0) || !coupling_pos(grav) || !std::isfinite(cp_v))
-    return coupling_error(who, "R_d, R_v, cp_d, cp_l, p0 and grav must be finite and positive, cp_v finite");
+    return module_error(who, "R_d, R_v, cp_d, cp_l, p0 and grav must be finite and positive, cp_v finite");
   P3Workspace *w = coupling_ws<P3Workspace>(ws);
-  if (!w) return coupling_error(who, P3Workspace::NOT_ONE);
-  if (!tracers) return coupling_error(who, "null tracers");
+  if (!w) return module_error(who, P3Workspace::NOT_ONE);
+  if (!tracers) return module_error(who, "null tracers");
   for (int tr = 0; tr < p3::NTRACERS; tr++)
-    if (!tracers[tr]) return coupling_error(who, "null pointer in tracers");
-  if (int rc = moist_surface_device_check(who)) return rc;
+    if (!tracers[tr]) return module_error(who, "null pointer in tracers");
+  if (int rc = require_device(who)) return rc;
   const PowTab *tab = kessler_pow_tab(w->base);
   if (!tab) return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "p3_pack: cannot allocate the pow tables");
   const pam_amd_p3_args_t &A = w->args;
@@ -2738,14 +2732,14 @@ extern "C" int pam_amd_p3_unpack(void *ws, const double *rho_d, double *rho_v, d
   const char *who = "p3_unpack";
   if (!rho_d || !rho_v || !rho_c || !temp || !q_prev || !t_prev || !liq_ice_exchange_out || !vap_liq_exchange_out || !vap_ice_exchange_out ||
       !precip_liq_surf_out || !precip_ice_surf_out)
-    return coupling_error(who, "null pointer");
-  if (!coupling_pos(cp_d) || !coupling_pos(cv_d)) return coupling_error(who, "cp_d and cv_d must be finite and positive");
+    return module_error(who, "null pointer");
+  if (!coupling_pos(cp_d) || !coupling_pos(cv_d)) return module_error(who, "cp_d and cv_d must be finite and positive");
   P3Workspace *w = coupling_ws<P3Workspace>(ws);
-  if (!w) return coupling_error(who, P3Workspace::NOT_ONE);
-  if (!tracers) return coupling_error(who, "null tracers");
+  if (!w) return module_error(who, P3Workspace::NOT_ONE);
+  if (!tracers) return module_error(who, "null tracers");
   for (int tr = 0; tr < p3::NTRACERS; tr++)
-    if (!tracers[tr]) return coupling_error(who, "null pointer in tracers");
-  if (int rc = moist_surface_device_check(who)) return rc;
+    if (!tracers[tr]) return module_error(who, "null pointer in tracers");
+  if (int rc = require_device(who)) return rc;
   const pam_amd_p3_args_t &A = w->args;
   P3CellSrc R = {};
   R.p[p3::U_QC] = A.qc; R.p[p3::U_NC] = A.nc; R.p[p3::U_QR] = A.qr; R.p[p3::U_NR] = A.nr; R.p[p3::U_QI] = A.qi; R.p[p3::U_NI] = A.ni;
@@ -2770,14 +2764,14 @@ extern "C" int pam_amd_p3_unpack(void *ws, const double *rho_d, double *rho_v, d
 extern "C" int pam_amd_p3_main_standin(const pam_amd_p3_args_t *args, void *user) {
   (void)user;
   const char *who = "p3_main_standin";
-  if (!args) return coupling_error(who, "null args");
+  if (!args) return module_error(who, "null args");
   const pam_amd_p3_args_t &A = *args;
-  if (A.ncol < 1 || A.nlev < 1) return coupling_error(who, "ncol and nlev must be >= 1");
-  if (A.ncol > 0x7fffffff - 64 || A.nlev > 0x7ffffff0) return coupling_error(who, "ncol must stay below 2^31 - 64");
-  if (A.layout != 0 && A.layout != 1) return coupling_error(who, "layout must be 0 or 1");
-  if (A.num_tend_out < 0 || A.num_tend_out > p3::MAX_TEND_OUT || (A.layout == 1 && A.num_tend_out)) return coupling_error(who, "num_tend_out must be 0 ... 49, 0 in layout 1");
-  if (coupling_null_array(cw::P3_TABLE, A, A.ncol, A.nlev, A.num_tend_out, cw::P3_ZERO_SIZE)) return coupling_error(who, "null pointer in args");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (A.ncol < 1 || A.nlev < 1) return module_error(who, "ncol and nlev must be >= 1");
+  if (A.ncol > 0x7fffffff - 64 || A.nlev > 0x7ffffff0) return module_error(who, "ncol must stay below 2^31 - 64");
+  if (A.layout != 0 && A.layout != 1) return module_error(who, "layout must be 0 or 1");
+  if (A.num_tend_out < 0 || A.num_tend_out > p3::MAX_TEND_OUT || (A.layout == 1 && A.num_tend_out)) return module_error(who, "num_tend_out must be 0 ... 49, 0 in layout 1");
+  if (coupling_null_array(cw::P3_TABLE, A, A.ncol, A.nlev, A.num_tend_out, cw::P3_ZERO_SIZE)) return module_error(who, "null pointer in args");
+  if (int rc = require_device(who)) return rc;
   coupling_dispatch(A.layout, coupling_narrow(g_p3_force_wide, p3_largest(A.ncol, A.nlev, A.num_tend_out)), [&](auto, auto idx) {
     hipLaunchKernelGGL((p3_standin_kernel<decltype(idx)>), dim3((unsigned)((A.ncol + 63) / 64)), dim3(64), 0, (hipStream_t)A.stream, A);
   });
@@ -2859,26 +2853,17 @@ __global__ void __launch_bounds__(64 * MOD_NS) msa_apply_kernel(int nens, int nc
                  d_q, d_u, d_v, accel_uv != 0, mode, factor);
 }
 
-int msa_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
 
 // the checks the three entry points share, all before the first HIP call
 int msa_check(const char *who, int nens, int nx, int ny, int nz, const double *const *fields, bool need_uv, const double *const *a,
               const double *const *b) {
-  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return msa_error(who, "nens, nx, ny and nz must be >= 1");
-  if ((long long)nx * ny > 0x7fffffffLL) return msa_error(who, "ny x nx exceeds 2^31 - 1 columns");
-  if (nz > 65535) return msa_error(who, "nz exceeds the grid (65535 levels)");
-  if (!fields || !a || !b) return msa_error(who, "null pointer table");
-  if (!fields[ms::F_TEMP] || !fields[ms::F_VAPOR]) return msa_error(who, "null temp or water_vapor pointer");
-  if (need_uv && (!fields[ms::F_U] || !fields[ms::F_V])) return msa_error(who, "null uvel or vvel pointer");
+  if (int rc = check_level_grid(who, nens, nx, ny, nz)) return rc;
+  if (!fields || !a || !b) return module_error(who, "null pointer table");
+  if (!fields[ms::F_TEMP] || !fields[ms::F_VAPOR]) return module_error(who, "null temp or water_vapor pointer");
+  if (need_uv && (!fields[ms::F_U] || !fields[ms::F_V])) return module_error(who, "null uvel or vvel pointer");
   for (int q = 0; q < ms::NQ; q++)
-    if (!a[q] || !b[q]) return msa_error(who, "null pointer in a table of (nz,nens) arrays");
+    if (!a[q] || !b[q]) return module_error(who, "null pointer in a table of (nz,nens) arrays");
   return PAM_AMD_OK;
-}
-
-void msa_launch_shape(int nens, int nz, dim3 &grid, dim3 &block) {
-  const int ME = nens < 64 ? nens : 64;
-  grid = dim3((unsigned)((nens + ME - 1) / ME), (unsigned)nz);
-  block = dim3((unsigned)ME, (unsigned)MOD_NS);
 }
 
 template <bool SAVE>
@@ -2889,8 +2874,7 @@ int msa_mean_launch(const char *who, int nens, int nx, int ny, int nz, const dou
   MsaOut O;
   for (int i = 0; i < ms::NF; i++) F.p[i] = fields[i];
   for (int q = 0; q < ms::NQ; q++) { S.p[q] = save ? save[q] : nullptr; O.p[q] = out[q]; }
-  dim3 grid, block;
-  msa_launch_shape(nens, nz, grid, block);
+  const auto [grid, block] = slot_block_shape(nens, nz);
   hipLaunchKernelGGL((msa_mean_kernel<SAVE>), grid, block, 0, (hipStream_t)stream, nens, nx * ny, F, S, O, max_ttend, cease);
   return stats_launch_check(who);
 }
@@ -2899,7 +2883,7 @@ int msa_mean_launch(const char *who, int nens, int nx, int ny, int nz, const dou
 extern "C" int pam_amd_msa_diagnose(int nens, int nx, int ny, int nz, const double *const *fields, double *const *save, void *stream) {
   const char *who = "msa_diagnose";
   if (int rc = msa_check(who, nens, nx, ny, nz, fields, true, save, save)) return rc;
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (int rc = require_device(who)) return rc;
   return msa_mean_launch<true>(who, nens, nx, ny, nz, fields, nullptr, save, 0.0, nullptr, stream);
 }
 
@@ -2907,9 +2891,9 @@ extern "C" int pam_amd_msa_tendencies(int nens, int nx, int ny, int nz, const do
                                       double *const *tend, double max_ttend, int *cease_dev, int *cease_host, void *stream) {
   const char *who = "msa_tendencies";
   if (int rc = msa_check(who, nens, nx, ny, nz, fields, true, save, tend)) return rc;
-  if (!(max_ttend > 0)) return msa_error(who, "max_ttend must be a positive number");
-  if (!cease_dev) return msa_error(who, "null cease_dev");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (!(max_ttend > 0)) return module_error(who, "max_ttend must be a positive number");
+  if (!cease_dev) return module_error(who, "null cease_dev");
+  if (int rc = require_device(who)) return rc;
   if (int rc = msa_mean_launch<false>(who, nens, nx, ny, nz, fields, save, tend, max_ttend, cease_dev, stream)) return rc;
   if (cease_host) {      // the one synchronisation of the call, for 4 bytes
     if (hipMemcpyAsync(cease_host, cease_dev, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
@@ -2923,13 +2907,12 @@ extern "C" int pam_amd_msa_apply(int nens, int nx, int ny, int nz, double *const
                                  int accel_uv, const int *cease_dev, void *stream) {
   const char *who = "msa_apply";
   if (int rc = msa_check(who, nens, nx, ny, nz, fields, accel_uv != 0, tend, tend)) return rc;
-  if (!(accel_factor >= 0) || !std::isfinite(accel_factor)) return msa_error(who, "accel_factor must be finite and >= 0");
+  if (!(accel_factor >= 0) || !std::isfinite(accel_factor)) return module_error(who, "accel_factor must be finite and >= 0");
   if (accel_factor == 0) return PAM_AMD_OK;      // nothing to apply: no launch
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (int rc = require_device(who)) return rc;
   MsaIn T;
   for (int q = 0; q < ms::NQ; q++) T.p[q] = tend[q];
-  dim3 grid, block;
-  msa_launch_shape(nens, nz, grid, block);
+  const auto [grid, block] = slot_block_shape(nens, nz);
   hipLaunchKernelGGL(msa_apply_kernel, grid, block, 0, (hipStream_t)stream, nens, nx * ny, fields[ms::F_TEMP], fields[ms::F_VAPOR],
                      fields[ms::F_U], fields[ms::F_V], T, accel_factor, accel_uv != 0 ? 1 : 0, cease_dev);
   return stats_launch_check(who);
@@ -3019,22 +3002,19 @@ __global__ void __launch_bounds__(64 * MOD_NS) vt_apply_kernel(int nens, int nco
                  ncol, slot, g, m, use_u != 0, mode, factor);
 }
 
-int vt_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
 
 // the checks the four entry points share, all before the first HIP call; tables: the call's (nz,nens) tables, n of them
 int vt_check(const char *who, int nens, int nx, int ny, int nz, const double *const *fields, int use_u, const double *const *const *tables,
              int n) {
-  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return vt_error(who, "nens, nx, ny and nz must be >= 1");
-  if ((long long)nx * ny > 0x7fffffffLL) return vt_error(who, "ny x nx exceeds 2^31 - 1 columns");
-  if (nz > 65535) return vt_error(who, "nz exceeds the grid (65535 levels)");
-  if (!fields) return vt_error(who, "null pointer table");
+  if (int rc = check_level_grid(who, nens, nx, ny, nz)) return rc;
+  if (!fields) return module_error(who, "null pointer table");
   for (int i = 0; i < n; i++)
-    if (!tables[i]) return vt_error(who, "null pointer table");
-  if (!fields[vt::F_TEMP] || !fields[vt::F_VAPOR]) return vt_error(who, "null temp or water_vapor pointer");
-  if (use_u && !fields[vt::F_U]) return vt_error(who, "null uvel pointer");
+    if (!tables[i]) return module_error(who, "null pointer table");
+  if (!fields[vt::F_TEMP] || !fields[vt::F_VAPOR]) return module_error(who, "null temp or water_vapor pointer");
+  if (use_u && !fields[vt::F_U]) return module_error(who, "null uvel pointer");
   for (int i = 0; i < n; i++)
     for (int q = 0; q < (use_u ? vt::NQ : vt::NQ - 1); q++)
-      if (!tables[i][q]) return vt_error(who, "null pointer in a table of (nz,nens) arrays");
+      if (!tables[i][q]) return module_error(who, "null pointer in a table of (nz,nens) arrays");
   return PAM_AMD_OK;
 }
 
@@ -3053,8 +3033,7 @@ T vt_table(P const *table, int use_u) {
 template <int EPI>
 int vt_stats_launch(const char *who, int nens, int nx, int ny, int nz, const double *const *fields, int use_u, const double *const *in,
                     double p, double lim, double *const *mean, double *const *var, double *const *out, void *stream) {
-  dim3 grid, block;
-  msa_launch_shape(nens, nz, grid, block);
+  const auto [grid, block] = slot_block_shape(nens, nz);
   hipLaunchKernelGGL((vt_stats_kernel<EPI>), grid, block, 0, (hipStream_t)stream, nens, nx * ny, vt_fields(fields, use_u), use_u ? 1 : 0,
                      vt_table<VtIn>(in, use_u), p, lim, vt_table<VtOut>(mean, use_u), vt_table<VtOut>(var, use_u),
                      vt_table<VtOut>(out, use_u));
@@ -3067,7 +3046,7 @@ extern "C" int pam_amd_vt_diagnose(int nens, int nx, int ny, int nz, const doubl
   const char *who = "vt_diagnose";
   const double *const *tables[2] = {mean, var};
   if (int rc = vt_check(who, nens, nx, ny, nz, fields, use_u, tables, 2)) return rc;
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (int rc = require_device(who)) return rc;
   return vt_stats_launch<VT_DIAGNOSE>(who, nens, nx, ny, nz, fields, use_u, nullptr, 0.0, 0.0, mean, var, nullptr, stream);
 }
 
@@ -3077,9 +3056,9 @@ extern "C" int pam_amd_vt_forcing(int nens, int nx, int ny, int nz, const double
   const char *who = "vt_forcing";
   const double *const *tables[4] = {tend, mean, var, scale};
   if (int rc = vt_check(who, nens, nx, ny, nz, fields, use_u, tables, 4)) return rc;
-  if (!(dt > 0) || !std::isfinite(dt)) return vt_error(who, "dt must be finite and positive");
-  if (!(scale_limit > 0 && scale_limit < 1)) return vt_error(who, "scale_limit must lie in (0, 1)");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (!(dt > 0) || !std::isfinite(dt)) return module_error(who, "dt must be finite and positive");
+  if (!(scale_limit > 0 && scale_limit < 1)) return module_error(who, "scale_limit must lie in (0, 1)");
+  if (int rc = require_device(who)) return rc;
   return vt_stats_launch<VT_FORCING>(who, nens, nx, ny, nz, fields, use_u, tend, dt, scale_limit, mean, var, scale, stream);
 }
 
@@ -3088,9 +3067,8 @@ extern "C" int pam_amd_vt_apply(int nens, int nx, int ny, int nz, double *const 
   const char *who = "vt_apply";
   const double *const *tables[2] = {mean, scale};
   if (int rc = vt_check(who, nens, nx, ny, nz, fields, use_u, tables, 2)) return rc;
-  if (int rc = moist_surface_device_check(who)) return rc;
-  dim3 grid, block;
-  msa_launch_shape(nens, nz, grid, block);
+  if (int rc = require_device(who)) return rc;
+  const auto [grid, block] = slot_block_shape(nens, nz);
   hipLaunchKernelGGL(vt_apply_kernel, grid, block, 0, (hipStream_t)stream, nens, nx * ny, vt_fields(fields, use_u), use_u ? 1 : 0,
                      vt_table<VtIn>(mean, use_u), vt_table<VtIn>(scale, use_u));
   return stats_launch_check(who);
@@ -3101,8 +3079,8 @@ extern "C" int pam_amd_vt_feedback(int nens, int nx, int ny, int nz, const doubl
   const char *who = "vt_feedback";
   const double *const *tables[4] = {var_start, mean, var, feedback};
   if (int rc = vt_check(who, nens, nx, ny, nz, fields, use_u, tables, 4)) return rc;
-  if (!(gcm_dt > 0) || !std::isfinite(gcm_dt)) return vt_error(who, "gcm_dt must be finite and positive");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (!(gcm_dt > 0) || !std::isfinite(gcm_dt)) return module_error(who, "gcm_dt must be finite and positive");
+  if (int rc = require_device(who)) return rc;
   return vt_stats_launch<VT_FEEDBACK>(who, nens, nx, ny, nz, fields, use_u, var_start, gcm_dt, 0.0, mean, var, feedback, stream);
 }
 
@@ -3229,41 +3207,9 @@ __global__ void __launch_bounds__(64 * MOD_NS) hd_fill_kernel(int nens, int ncol
   hd::fill_apply_walk(p, (long long)nens, ncol, slot, mode, factor);
 }
 
-int hd_error(const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string("hyperdiffusion: ") + msg).c_str()); }
 
-// the workspace of one field: per device, grown on demand, freed by pam_amd_modules_finalize().  A device's mutex is held for a whole
-// call on the workspace path, which ends in a synchronisation of its stream: two streams never share the workspace.
-constexpr int HD_MAX_DEVICES = 64;
-struct HdWorkspace { std::mutex m; double *p = nullptr; long long count = 0; };
-HdWorkspace g_hd_workspace[HD_MAX_DEVICES];
-
-double *hd_workspace(HdWorkspace &w, long long count) {
-  if (w.count < count) {
-    if (w.p) (void)hipFree(w.p);
-    w.p = nullptr;
-    w.count = 0;
-    if (hipMalloc((void **)&w.p, (size_t)count * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); w.p = nullptr; return nullptr; }
-    w.count = count;
-  }
-  return w.p;
-}
-
-void hd_workspace_free() {
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  for (int d = 0; d < HD_MAX_DEVICES; d++) {
-    HdWorkspace &w = g_hd_workspace[d];
-    std::lock_guard<std::mutex> lk(w.m);
-    if (w.p) {
-      if (d != cur) (void)hipSetDevice(d);
-      (void)hipFree(w.p);
-      w.p = nullptr;
-      w.count = 0;
-      if (d != cur && cur >= 0) (void)hipSetDevice(cur);
-    }
-  }
-}
-
+// the workspace of one field is the per-device scratch (above), at exactly the size the largest call needed; its mutex is held for a
+// whole call on the workspace path, which ends in a synchronisation of its stream: two streams never share the workspace.
 int g_hd_path = HD_AUTO;   // pam_amd_hyperdiffusion_debug_path: tests run every path at small shapes
 
 // the widest member block (as log2) whose ring fits the LDS budget, no wider than the ensemble needs; -1: no block fits
@@ -3277,7 +3223,7 @@ int hd_ring_block(int nens, int nx) {
 }  // namespace
 
 extern "C" int pam_amd_hyperdiffusion_debug_path(int path) {
-  if (path < HD_AUTO || path > HD_INPLACE_NARROW) return hd_error("debug path must be 0 (automatic), 1 (in place), 2 (workspace) or 3 (in place, narrow member blocks)");
+  if (path < HD_AUTO || path > HD_INPLACE_NARROW) return module_error("hyperdiffusion", "debug path must be 0 (automatic), 1 (in place), 2 (workspace) or 3 (in place, narrow member blocks)");
   g_hd_path = path;
   return PAM_AMD_OK;
 }
@@ -3285,28 +3231,29 @@ extern "C" int pam_amd_hyperdiffusion_debug_path(int path) {
 extern "C" int pam_amd_hyperdiffusion(int nens, int nx, int ny, int nz, int num_fields, double *const *fields, const unsigned char *positive,
                                       double dt, double tau, void *stream) {
   const char *who = "hyperdiffusion";
-  if (!fields || !positive) return hd_error("null fields or positive table");
-  if (num_fields < 1 || num_fields > hd::MAX_FIELDS) return hd_error("num_fields must be in [1, 64]");
+  if (!fields || !positive) return module_error("hyperdiffusion", "null fields or positive table");
+  if (num_fields < 1 || num_fields > hd::MAX_FIELDS) return module_error("hyperdiffusion", "num_fields must be in [1, 64]");
   for (int i = 0; i < num_fields; i++)
-    if (!fields[i]) return hd_error("null field pointer");
-  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return hd_error("nens, nx, ny and nz must be >= 1");
-  if (nx < 5) return hd_error("nx must be >= 5 (a five-point periodic stencil)");
-  if (ny > 1 && ny < 5) return hd_error("ny must be 1 or >= 5 (a five-point periodic stencil)");
-  if ((long long)nx * ny > 0x7fffffffLL) return hd_error("ny x nx exceeds 2^31 - 1 columns");
-  if (!(dt > 0) || !std::isfinite(dt) || !(tau > 0) || !std::isfinite(tau)) return hd_error("dt and tau must be finite and positive");
-  if (dt > tau) return hd_error("dt must not exceed tau (the scheme is stable for dt <= tau)");
-  const int me_fill = nens < 64 ? nens : 64;
-  const long long fill_blocks = (long long)((nens + me_fill - 1) / me_fill) * nz;
+    if (!fields[i]) return module_error("hyperdiffusion", "null field pointer");
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return module_error("hyperdiffusion", "nens, nx, ny and nz must be >= 1");
+  if (nx < 5) return module_error("hyperdiffusion", "nx must be >= 5 (a five-point periodic stencil)");
+  if (ny > 1 && ny < 5) return module_error("hyperdiffusion", "ny must be 1 or >= 5 (a five-point periodic stencil)");
+  if ((long long)nx * ny > 0x7fffffffLL) return module_error("hyperdiffusion", "ny x nx exceeds 2^31 - 1 columns");
+  if (!(dt > 0) || !std::isfinite(dt) || !(tau > 0) || !std::isfinite(tau)) return module_error("hyperdiffusion", "dt and tau must be finite and positive");
+  if (dt > tau) return module_error("hyperdiffusion", "dt must not exceed tau (the scheme is stable for dt <= tau)");
+  const SlotShape fill = slot_block_shape(nens, nz);
+  const int me_fill = (int)fill.block.x;
+  const long long fill_blocks = (long long)fill.grid.x * nz;
   const long long lines = (long long)nz * nens;
-  if (fill_blocks > 0x7fffffffLL || (lines + HD_THREADS - 1) / HD_THREADS > 0x7fffffffLL) return hd_error("nz x nens exceeds the grid");
+  if (fill_blocks > 0x7fffffffLL || (lines + HD_THREADS - 1) / HD_THREADS > 0x7fffffffLL) return module_error("hyperdiffusion", "nz x nens exceeds the grid");
   const int path = g_hd_path;
   int lg = ny > 1 ? hd_ring_block(nens, nx) : 0;
   if (path == HD_INPLACE_NARROW && lg > 0) lg = lg > 2 ? lg - 2 : 0;
   const bool in_place = path == HD_WORKSPACE ? false : (ny == 1 || lg >= 0);
-  if (!in_place && path != HD_AUTO && path != HD_WORKSPACE) return hd_error("the forced row ring does not fit LDS at this nx");
+  if (!in_place && path != HD_AUTO && path != HD_WORKSPACE) return module_error("hyperdiffusion", "the forced row ring does not fit LDS at this nx");
   const int nblk = ny > 1 && lg >= 0 ? (nens + (1 << lg) - 1) >> lg : 1;
-  if ((long long)nblk * nz > 0x7fffffffLL) return hd_error("nz x nens exceeds the grid");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if ((long long)nblk * nz > 0x7fffffffLL) return module_error("hyperdiffusion", "nz x nens exceeds the grid");
+  if (int rc = require_device(who)) return rc;
 
   const double c = hd::coefficient(dt, tau);
   hipStream_t s = (hipStream_t)stream;
@@ -3327,13 +3274,11 @@ extern "C" int pam_amd_hyperdiffusion(int nens, int nx, int ny, int nz, int num_
                        nblk, lg, F, c);
     if (int rc = stats_launch_check(who)) return rc;
   } else {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= HD_MAX_DEVICES)
-      return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "hyperdiffusion: cannot tell the current device");
-    HdWorkspace &w = g_hd_workspace[dev];
-    std::lock_guard<std::mutex> lk(w.m);
+    DeviceScratch *w = scratch_slot(SCRATCH_HYPERDIFFUSION);
+    if (!w) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "hyperdiffusion: cannot tell the current device");
+    std::lock_guard lk(w->m);
     const long long total = (long long)nz * ny * nx * nens;
-    double *ws = hd_workspace(w, total);
+    double *ws = (double *)scratch_reserve(*w, (size_t)total * sizeof(double), 0);
     if (!ws) return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "hyperdiffusion: cannot allocate the workspace of one field");
     const long long want = (total + HD_THREADS - 1) / HD_THREADS;
     const unsigned blocks = (unsigned)(want < (1LL << 20) ? want : (1LL << 20));
@@ -3352,7 +3297,7 @@ extern "C" int pam_amd_hyperdiffusion(int nens, int nx, int ny, int nz, int num_
       rc = stats_launch_check(who);
     }
     const hipError_t done = hipStreamSynchronize(s);
-    if (!rc && done != hipSuccess) rc = pam_amd_set_last_error_(PAM_AMD_ENOGPU, (std::string(who) + ": " + hipGetErrorString(done)).c_str());
+    if (!rc && done != hipSuccess) rc = module_error(PAM_AMD_ENOGPU, who, hipGetErrorString(done));
     return rc;
   }
   if (npos > 0) {
@@ -3472,33 +3417,14 @@ __global__ void __launch_bounds__(64 * MOD_NS) crm_feedback_kernel(int nens, int
   }
 }
 
-int rad_error(const char *who, const char *msg) { return pam_amd_set_last_error_(PAM_AMD_EINVAL, (std::string(who) + ": " + msg).c_str()); }
 
-// [p, p + n doubles) of every array of a call, to refuse an output that shares memory with an input or with another output
-struct RadSpan { const double *p; long long n; bool out; };
-bool rad_spans_overlap(const std::vector<RadSpan> &spans) {
-  for (size_t i = 0; i < spans.size(); i++)
-    for (size_t j = i + 1; j < spans.size(); j++) {
-      if (!spans[i].out && !spans[j].out) continue;
-      const uintptr_t a = (uintptr_t)spans[i].p, b = (uintptr_t)spans[j].p;
-      if (a < b + (uintptr_t)spans[j].n * sizeof(double) && b < a + (uintptr_t)spans[i].n * sizeof(double)) return true;
-    }
-  return false;
-}
-
-int rad_check_sizes(const char *who, int nens, int nx, int ny, int nz) {
-  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return rad_error(who, "nens, nx, ny and nz must be >= 1");
-  if ((long long)nx * ny > 0x7fffffffLL) return rad_error(who, "ny x nx exceeds 2^31 - 1 columns");
-  if (nz > 65535) return rad_error(who, "nz exceeds the grid (65535 levels)");
-  return PAM_AMD_OK;
-}
 
 int g_rad_mapping = RAD_AUTO;   // pam_amd_radiation_aggregate_debug_mapping: tests run both mappings at small shapes
 }  // namespace
 
 extern "C" int pam_amd_radiation_aggregate_debug_mapping(int mapping) {
   if (mapping < RAD_AUTO || mapping > RAD_THREAD_SLOTS)
-    return rad_error("radiation_aggregate", "debug mapping must be 0 (automatic), 1 (block slots) or 2 (thread slots)");
+    return module_error("radiation_aggregate", "debug mapping must be 0 (automatic), 1 (block slots) or 2 (thread slots)");
   g_rad_mapping = mapping;
   return PAM_AMD_OK;
 }
@@ -3506,28 +3432,29 @@ extern "C" int pam_amd_radiation_aggregate_debug_mapping(int mapping) {
 extern "C" int pam_amd_radiation_aggregate(int nens, int nx, int ny, int nz, int rad_nx, int rad_ny, const double *const *fields,
                                            double *const *rad, double factor, void *stream) {
   const char *who = "radiation_aggregate";
-  if (int rc = rad_check_sizes(who, nens, nx, ny, nz)) return rc;
-  if (rad_nx < 1 || rad_ny < 1 || nx % rad_nx != 0 || ny % rad_ny != 0) return rad_error(who, "rad_nx and rad_ny must be >= 1 and divide nx and ny");
-  if (!fields || !rad) return rad_error(who, "null pointer table");
-  if (!fields[0] || !fields[1] || !fields[2]) return rad_error(who, "null temp, rho_d or rho_v pointer");
-  if (!rad[rd::A_T] || !rad[rd::A_QV] || !rad[rd::A_CLD]) return rad_error(who, "null rad_temperature, rad_qv or rad_cld pointer");
-  if ((rad[rd::A_QC] == nullptr) != (fields[3] == nullptr)) return rad_error(who, "rad_qc must be given exactly when rho_c is");
-  if ((rad[rd::A_QI] == nullptr) != (fields[4] == nullptr)) return rad_error(who, "rad_qi must be given exactly when rho_i is");
-  if (!std::isfinite(factor)) return rad_error(who, "factor must be finite");
+  if (int rc = check_level_grid(who, nens, nx, ny, nz)) return rc;
+  if (rad_nx < 1 || rad_ny < 1 || nx % rad_nx != 0 || ny % rad_ny != 0) return module_error(who, "rad_nx and rad_ny must be >= 1 and divide nx and ny");
+  if (!fields || !rad) return module_error(who, "null pointer table");
+  if (!fields[0] || !fields[1] || !fields[2]) return module_error(who, "null temp, rho_d or rho_v pointer");
+  if (!rad[rd::A_T] || !rad[rd::A_QV] || !rad[rd::A_CLD]) return module_error(who, "null rad_temperature, rad_qv or rad_cld pointer");
+  if ((rad[rd::A_QC] == nullptr) != (fields[3] == nullptr)) return module_error(who, "rad_qc must be given exactly when rho_c is");
+  if ((rad[rd::A_QI] == nullptr) != (fields[4] == nullptr)) return module_error(who, "rad_qi must be given exactly when rho_i is");
+  if (!std::isfinite(factor)) return module_error(who, "factor must be finite");
   const long long cells = (long long)nz * ny * nx * nens, elems = (long long)nz * rad_ny * rad_nx * nens;
-  std::vector<RadSpan> spans;
+  std::vector<Span> spans;
   for (int i = 0; i < 6; i++)
     if (fields[i]) spans.push_back({fields[i], cells, false});
   for (int q = 0; q < rd::NA; q++)
     if (rad[q]) spans.push_back({rad[q], elems, true});
-  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
-  const int gx = nx / rad_nx, gy = ny / rad_ny, ME = nens < 64 ? nens : 64, nblk = (nens + ME - 1) / ME;
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  const SlotShape shape = slot_block_shape(nens, nz);
+  const int gx = nx / rad_nx, gy = ny / rad_ny, ME = (int)shape.block.x, nblk = (int)shape.grid.x;
   const long long ngroups = (long long)rad_nx * rad_ny;
   const bool block_slots = g_rad_mapping == RAD_AUTO ? (long long)gx * gy >= RAD_BLOCK_CELLS : g_rad_mapping == RAD_BLOCK_SLOTS;
   const int GB = RAD_THREADS / ME;
   const long long blocks = (block_slots ? ngroups : (ngroups + GB - 1) / GB) * nblk;
-  if (blocks > 0x7fffffffLL) return rad_error(who, "rad_ny x rad_nx x nens exceeds the grid");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (blocks > 0x7fffffffLL) return module_error(who, "rad_ny x rad_nx x nens exceeds the grid");
+  if (int rc = require_device(who)) return rc;
   RadFields F;
   RadOut O;
   for (int i = 0; i < rd::NF; i++) F.p[i] = i < 6 ? fields[i] : nullptr;
@@ -3545,21 +3472,21 @@ extern "C" int pam_amd_radiation_aggregate(int nens, int nx, int ny, int nz, int
 extern "C" int pam_amd_crm_feedback(int nens, int nx, int ny, int nz, const double *const *fields, const double *const *gcm, double gcm_dt,
                                     double *const *mean, double *const *tend, void *stream) {
   const char *who = "crm_feedback";
-  if (int rc = rad_check_sizes(who, nens, nx, ny, nz)) return rc;
-  if (!fields || !gcm || !mean || !tend) return rad_error(who, "null pointer table");
-  if (!fields[0] || !fields[1] || !fields[2] || !fields[5] || !fields[6]) return rad_error(who, "null temp, rho_d, rho_v, uvel or vvel pointer");
-  if (!(gcm_dt > 0) || !std::isfinite(gcm_dt)) return rad_error(who, "gcm_dt must be finite and positive");
+  if (int rc = check_level_grid(who, nens, nx, ny, nz)) return rc;
+  if (!fields || !gcm || !mean || !tend) return module_error(who, "null pointer table");
+  if (!fields[0] || !fields[1] || !fields[2] || !fields[5] || !fields[6]) return module_error(who, "null temp, rho_d, rho_v, uvel or vvel pointer");
+  if (!(gcm_dt > 0) || !std::isfinite(gcm_dt)) return module_error(who, "gcm_dt must be finite and positive");
   // the field, the gcm entry and the quantity of the two species that may be absent
   const int species[2][3] = {{3, rd::G_RHOC, rd::B_QC}, {4, rd::G_RHOI, rd::B_QI}};
   for (int i = 0; i < rd::NG; i++)
-    if (i != rd::G_RHOC && i != rd::G_RHOI && !gcm[i]) return rad_error(who, "null pointer in the gcm table");
+    if (i != rd::G_RHOC && i != rd::G_RHOI && !gcm[i]) return module_error(who, "null pointer in the gcm table");
   for (int q = 0; q < rd::NB; q++)
-    if (q != rd::B_QC && q != rd::B_QI && (!mean[q] || !tend[q])) return rad_error(who, "null pointer in the mean or tend table");
+    if (q != rd::B_QC && q != rd::B_QI && (!mean[q] || !tend[q])) return module_error(who, "null pointer in the mean or tend table");
   for (auto &s : species)
-    if (fields[s[0]] && (!gcm[s[1]] || !mean[s[2]] || !tend[s[2]])) return rad_error(who, "a species that is present needs its gcm, mean and tend entries");
+    if (fields[s[0]] && (!gcm[s[1]] || !mean[s[2]] || !tend[s[2]])) return module_error(who, "a species that is present needs its gcm, mean and tend entries");
   const long long cells = (long long)nz * ny * nx * nens, cols = (long long)nz * nens;
   const bool has[2] = {fields[3] != nullptr, fields[4] != nullptr};
-  std::vector<RadSpan> spans;
+  std::vector<Span> spans;
   for (int i = 0; i < 7; i++)
     if (fields[i]) spans.push_back({fields[i], cells, false});
   for (int i = 0; i < rd::NG; i++)
@@ -3569,8 +3496,8 @@ extern "C" int pam_amd_crm_feedback(int nens, int nx, int ny, int nz, const doub
     spans.push_back({mean[q], cols, true});
     spans.push_back({tend[q], cols, true});
   }
-  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if (int rc = require_device(who)) return rc;
   RadFields F;
   FbGcm G;
   FbOut M, T;
@@ -3582,8 +3509,7 @@ extern "C" int pam_amd_crm_feedback(int nens, int nx, int ny, int nz, const doub
   for (int q = 0; q < rd::NB; q++) { M.p[q] = mean[q]; T.p[q] = tend[q]; }
   for (int j = 0; j < 2; j++)
     if (!has[j]) { G.p[species[j][1]] = nullptr; M.p[species[j][2]] = nullptr; T.p[species[j][2]] = nullptr; }
-  dim3 grid, block;
-  msa_launch_shape(nens, nz, grid, block);
+  const auto [grid, block] = slot_block_shape(nens, nz);
   hipLaunchKernelGGL(crm_feedback_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, ny, F, G, gcm_dt, M, T);
   return stats_launch_check(who);
 }
@@ -3654,35 +3580,14 @@ __global__ void __launch_bounds__(CD_THREADS) coldiag_mean_thread_kernel(int nen
   O.p[q][e] = rd::accumulate(O.p[q][e], tot[0], factor);
 }
 
-// the workspace of the column values: per device, grown on demand, freed by pam_amd_modules_finalize().  Both launches of a call go to
-// the caller's stream and nothing synchronises, so calls on ONE device must be ordered by the caller (one stream, or events between
-// streams) -- as they are for any two calls that write the same outputs.  Growing frees the old array, which waits for the device.
-constexpr int CD_MAX_DEVICES = 64;
-struct CdWorkspace { std::mutex m; double *p = nullptr; long long count = 0; };
-CdWorkspace g_cd_workspace[CD_MAX_DEVICES];
-
-void cd_workspace_free() {
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  for (int d = 0; d < CD_MAX_DEVICES; d++) {
-    CdWorkspace &w = g_cd_workspace[d];
-    std::lock_guard<std::mutex> lk(w.m);
-    if (w.p) {
-      if (d != cur) (void)hipSetDevice(d);
-      (void)hipFree(w.p);
-      w.p = nullptr;
-      w.count = 0;
-      if (d != cur && cur >= 0) (void)hipSetDevice(cur);
-    }
-  }
-}
-
+// the workspace of the column values is the per-device scratch (above), at exactly the size the largest call needed.  Both launches
+// of a call go to the caller's stream and nothing synchronises: its mutex is held over the launches only.
 int g_cd_mapping = CD_AUTO;   // pam_amd_column_diagnostics_debug_mapping: tests run both mean mappings at small shapes
 }  // namespace
 
 extern "C" int pam_amd_column_diagnostics_debug_mapping(int mapping) {
   if (mapping < CD_AUTO || mapping > CD_THREAD_SLOTS)
-    return rad_error("column_diagnostics", "debug mapping must be 0 (automatic), 1 (block slots) or 2 (thread slots)");
+    return module_error("column_diagnostics", "debug mapping must be 0 (automatic), 1 (block slots) or 2 (thread slots)");
   g_cd_mapping = mapping;
   return PAM_AMD_OK;
 }
@@ -3691,25 +3596,25 @@ extern "C" int pam_amd_column_diagnostics(int nens, int nx, int ny, int nz, cons
                                           const double *const *precip, double R_d, double R_v, double p_low, double p_high,
                                           double cwp_threshold, double *const *out, double factor, void *stream) {
   const char *who = "column_diagnostics";
-  if (int rc = rad_check_sizes(who, nens, nx, ny, nz)) return rc;
-  if (!fields || !out || !zint) return rad_error(who, "null fields, out or zint");
-  if (!fields[cd::F_TEMP] || !fields[cd::F_RHOD] || !fields[cd::F_RHOV]) return rad_error(who, "null temp, rho_d or rho_v pointer");
+  if (int rc = check_level_grid(who, nens, nx, ny, nz)) return rc;
+  if (!fields || !out || !zint) return module_error(who, "null fields, out or zint");
+  if (!fields[cd::F_TEMP] || !fields[cd::F_RHOD] || !fields[cd::F_RHOV]) return module_error(who, "null temp, rho_d or rho_v pointer");
   const bool has_c = fields[cd::F_RHOC] != nullptr, has_i = fields[cd::F_RHOI] != nullptr;
   const double *pr[2] = {precip ? precip[0] : nullptr, precip ? precip[1] : nullptr};
-  if ((out[cd::O_LWP] != nullptr) != has_c) return rad_error(who, "lwp must be given exactly when rho_c is");
-  if ((out[cd::O_IWP] != nullptr) != has_i) return rad_error(who, "iwp must be given exactly when rho_i is");
-  if ((out[cd::O_PRECL] != nullptr) != (pr[0] != nullptr)) return rad_error(who, "precip_liq must be given exactly when its precipitation array is");
-  if ((out[cd::O_PRECI] != nullptr) != (pr[1] != nullptr)) return rad_error(who, "precip_ice must be given exactly when its precipitation array is");
+  if ((out[cd::O_LWP] != nullptr) != has_c) return module_error(who, "lwp must be given exactly when rho_c is");
+  if ((out[cd::O_IWP] != nullptr) != has_i) return module_error(who, "iwp must be given exactly when rho_i is");
+  if ((out[cd::O_PRECL] != nullptr) != (pr[0] != nullptr)) return module_error(who, "precip_liq must be given exactly when its precipitation array is");
+  if ((out[cd::O_PRECI] != nullptr) != (pr[1] != nullptr)) return module_error(who, "precip_ice must be given exactly when its precipitation array is");
   for (int x = 0; x < cd::NC; x++)
     if ((out[cd::O_CLDTOT + x] != nullptr) != (has_c || has_i))
-      return rad_error(who, "cldtot, cldlow, cldmed and cldhgh must all be given where a condensate is, and none of them where neither is");
-  if (!out[cd::O_PW]) return rad_error(who, "null pw pointer");
+      return module_error(who, "cldtot, cldlow, cldmed and cldhgh must all be given where a condensate is, and none of them where neither is");
+  if (!out[cd::O_PW]) return module_error(who, "null pw pointer");
   if (!std::isfinite(R_d) || !std::isfinite(R_v) || !std::isfinite(p_low) || !std::isfinite(p_high) || !std::isfinite(factor))
-    return rad_error(who, "R_d, R_v, p_low, p_high and factor must be finite");
-  if (p_high > p_low) return rad_error(who, "p_high must not exceed p_low");
-  if (!(cwp_threshold >= 0)) return rad_error(who, "cwp_threshold must be >= 0");
+    return module_error(who, "R_d, R_v, p_low, p_high and factor must be finite");
+  if (p_high > p_low) return module_error(who, "p_high must not exceed p_low");
+  if (!(cwp_threshold >= 0)) return module_error(who, "cwp_threshold must be >= 0");
   const long long ncol = (long long)nx * ny, level = ncol * nens, cells = level * nz;
-  std::vector<RadSpan> spans;
+  std::vector<Span> spans;
   for (int i = 0; i < cd::NF; i++)
     if (fields[i]) spans.push_back({fields[i], cells, false});
   spans.push_back({zint, (long long)(nz + 1) * nens, false});
@@ -3717,14 +3622,13 @@ extern "C" int pam_amd_column_diagnostics(int nens, int nx, int ny, int nz, cons
     if (pr[i]) spans.push_back({pr[i], level, false});
   for (int q = 0; q < cd::NO; q++)
     if (out[q]) spans.push_back({out[q], (long long)nens, true});
-  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
   const long long scan_blocks = (level + CD_THREADS - 1) / CD_THREADS;
-  if (scan_blocks > 0x7fffffffLL) return rad_error(who, "ny x nx x nens exceeds the grid");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (scan_blocks > 0x7fffffffLL) return module_error(who, "ny x nx x nens exceeds the grid");
+  if (int rc = require_device(who)) return rc;
 
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= CD_MAX_DEVICES)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "column_diagnostics: cannot tell the current device");
+  DeviceScratch *w = scratch_slot(SCRATCH_COLUMN_DIAGNOSTICS);
+  if (!w) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "column_diagnostics: cannot tell the current device");
   CdFields F;
   CdWork W;
   CdMeanIn I;
@@ -3732,21 +3636,11 @@ extern "C" int pam_amd_column_diagnostics(int nens, int nx, int ny, int nz, cons
   for (int i = 0; i < cd::NF; i++) F.p[i] = fields[i];
   int nws = 0;
   for (int q = 0; q < cd::NW; q++) nws += out[q] != nullptr;
-  CdWorkspace &w = g_cd_workspace[dev];
-  std::lock_guard<std::mutex> lk(w.m);
-  if (w.count < nws * level) {
-    if (w.p) (void)hipFree(w.p);
-    w.p = nullptr;
-    w.count = 0;
-    if (hipMalloc((void **)&w.p, (size_t)(nws * level) * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();
-      w.p = nullptr;
-      return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "column_diagnostics: cannot allocate the workspace of the column values");
-    }
-    w.count = nws * level;
-  }
+  std::lock_guard lk(w->m);
+  double *ws = (double *)scratch_reserve(*w, (size_t)(nws * level) * sizeof(double), 0);
+  if (!ws) return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "column_diagnostics: cannot allocate the workspace of the column values");
   int at = 0;
-  for (int q = 0; q < cd::NW; q++) W.p[q] = out[q] ? w.p + (long long)(at++) * level : nullptr;
+  for (int q = 0; q < cd::NW; q++) W.p[q] = out[q] ? ws + (long long)(at++) * level : nullptr;
   for (int q = 0; q < cd::NO; q++) { I.p[q] = q < cd::NW ? W.p[q] : pr[q - cd::NW]; O.p[q] = out[q]; }
   const cd::Params P{R_d, R_v, p_low, p_high, cwp_threshold};
   hipStream_t s = (hipStream_t)stream;
@@ -3754,7 +3648,7 @@ extern "C" int pam_amd_column_diagnostics(int nens, int nx, int ny, int nz, cons
   if (int rc = stats_launch_check(who)) return rc;
   const bool block_slots = g_cd_mapping == CD_AUTO ? ncol >= CD_BLOCK_COLUMNS : g_cd_mapping == CD_BLOCK_SLOTS;
   if (block_slots) {
-    const int ME = nens < 64 ? nens : 64;
+    const int ME = (int)slot_block_shape(nens, cd::NO).block.x;
     hipLaunchKernelGGL(coldiag_mean_block_kernel, dim3((unsigned)((nens + ME - 1) / ME), (unsigned)cd::NO), dim3((unsigned)ME, (unsigned)MOD_NS), 0, s,
                        nens, (int)ncol, I, O, factor);
   } else {
@@ -3817,34 +3711,33 @@ __global__ void __launch_bounds__(64 * MOD_NS) flux_profiles_kernel(int nens, in
 extern "C" int pam_amd_flux_profiles(int nens, int nx, int ny, int nz, const double *const *fields, double qc_threshold, double *const *out,
                                      double factor, void *stream) {
   const char *who = "flux_profiles";
-  if (int rc = rad_check_sizes(who, nens, nx, ny, nz)) return rc;
-  if (!fields || !out) return rad_error(who, "null fields or out");
+  if (int rc = check_level_grid(who, nens, nx, ny, nz)) return rc;
+  if (!fields || !out) return module_error(who, "null fields or out");
   for (int i = 0; i < fp::NF; i++)
     if (i != fp::F_CLOUD && i != fp::F_ICE && !fields[i])
-      return rad_error(who, "null density_dry, water_vapor, temp, uvel, vvel or wvel pointer");
+      return module_error(who, "null density_dry, water_vapor, temp, uvel, vvel or wvel pointer");
   const bool has_cond = fields[fp::F_CLOUD] != nullptr || fields[fp::F_ICE] != nullptr;
   for (int q = 0; q < fp::NO; q++) {
     const bool sampled = q == fp::O_MCUP || q == fp::O_MCDN || q == fp::O_CLD;
     if (sampled && (out[q] != nullptr) != has_cond)
-      return rad_error(who, "mcup, mcdn and cld must all be given where a condensate is, and none of them where neither is");
-    if (!sampled && !out[q]) return rad_error(who, "null mcuup, mcudn, flux_t, flux_qt, flux_u, flux_v or tke pointer");
+      return module_error(who, "mcup, mcdn and cld must all be given where a condensate is, and none of them where neither is");
+    if (!sampled && !out[q]) return module_error(who, "null mcuup, mcudn, flux_t, flux_qt, flux_u, flux_v or tke pointer");
   }
-  if (!(qc_threshold >= 0) || !std::isfinite(qc_threshold)) return rad_error(who, "qc_threshold must be finite and >= 0");
-  if (!std::isfinite(factor)) return rad_error(who, "factor must be finite");
+  if (!(qc_threshold >= 0) || !std::isfinite(qc_threshold)) return module_error(who, "qc_threshold must be finite and >= 0");
+  if (!std::isfinite(factor)) return module_error(who, "factor must be finite");
   const long long cells = (long long)nz * ny * nx * nens, cols = (long long)nz * nens;
-  std::vector<RadSpan> spans;
+  std::vector<Span> spans;
   for (int i = 0; i < fp::NF; i++)
     if (fields[i]) spans.push_back({fields[i], cells, false});
   for (int q = 0; q < fp::NO; q++)
     if (out[q]) spans.push_back({out[q], cols, true});
-  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if (int rc = require_device(who)) return rc;
   FpFields F;
   FpOut O;
   for (int i = 0; i < fp::NF; i++) F.p[i] = fields[i];
   for (int q = 0; q < fp::NO; q++) O.p[q] = out[q];
-  dim3 grid, block;
-  msa_launch_shape(nens, nz, grid, block);
+  const auto [grid, block] = slot_block_shape(nens, nz);
   hipLaunchKernelGGL(flux_profiles_kernel, grid, block, 0, (hipStream_t)stream, nens, nx * ny, F, qc_threshold, O, factor);
   return stats_launch_check(who);
 }
@@ -3905,43 +3798,23 @@ __global__ void __launch_bounds__(LDS ? SGS_LDS_THREADS : SGS_THREADS) sgs_solve
   if (num_tracers > 0) sg::solve_class(sg::C_TRACER, A.tr, num_tracers, nullptr, t, rd, rv, tkh, zi, zm, level, (long long)nens, nz, dt, gc, cp, cs);
 }
 
-// the workspace of c' on the path without LDS: per device, grown on demand, freed by pam_amd_modules_finalize().  The launch goes to the
-// caller's stream and nothing synchronises, so calls on ONE device must be ordered by the caller, as for column_diagnostics
-constexpr int SGS_MAX_DEVICES = 64;
-struct SgsWorkspace { std::mutex m; double *p = nullptr; long long count = 0; };
-SgsWorkspace g_sgs_workspace[SGS_MAX_DEVICES];
-
-void sgs_workspace_free() {
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  for (int d = 0; d < SGS_MAX_DEVICES; d++) {
-    SgsWorkspace &w = g_sgs_workspace[d];
-    std::lock_guard<std::mutex> lk(w.m);
-    if (w.p) {
-      if (d != cur) (void)hipSetDevice(d);
-      (void)hipFree(w.p);
-      w.p = nullptr;
-      w.count = 0;
-      if (d != cur && cur >= 0) (void)hipSetDevice(cur);
-    }
-  }
-}
-
+// the workspace of c' on the path without LDS is the per-device scratch (above), at exactly the size the largest call needed.  The
+// launch goes to the caller's stream and nothing synchronises: its mutex is held over the launch only, as for column_diagnostics.
 int g_sgs_path = SGS_AUTO;   // pam_amd_sgs_smag_debug_path: tests run both placements of c' at small shapes
 
 bool sgs_positive(double v) { return std::isfinite(v) && v > 0; }
 
 int sgs_check_sizes(const char *who, int nens, int nx, int ny, int nz) {
-  if (nens < 1 || nx < 1 || ny < 1) return rad_error(who, "nens, nx and ny must be >= 1");
-  if (nz < 2) return rad_error(who, "nz must be >= 2");
-  if ((long long)nx * ny > 0x7fffffffLL) return rad_error(who, "ny x nx exceeds 2^31 - 1 columns");
-  if (((long long)nx * ny * nens + SGS_LDS_THREADS - 1) / SGS_LDS_THREADS > 0x7fffffffLL) return rad_error(who, "ny x nx x nens exceeds the grid");
+  if (nens < 1 || nx < 1 || ny < 1) return module_error(who, "nens, nx and ny must be >= 1");
+  if (nz < 2) return module_error(who, "nz must be >= 2");
+  if ((long long)nx * ny > 0x7fffffffLL) return module_error(who, "ny x nx exceeds 2^31 - 1 columns");
+  if (((long long)nx * ny * nens + SGS_LDS_THREADS - 1) / SGS_LDS_THREADS > 0x7fffffffLL) return module_error(who, "ny x nx x nens exceeds the grid");
   return PAM_AMD_OK;
 }
 }  // namespace
 
 extern "C" int pam_amd_sgs_smag_debug_path(int path) {
-  if (path < SGS_AUTO || path > SGS_WORKSPACE) return rad_error("sgs_smag", "debug path must be 0 (automatic), 1 (LDS) or 2 (workspace)");
+  if (path < SGS_AUTO || path > SGS_WORKSPACE) return module_error("sgs_smag", "debug path must be 0 (automatic), 1 (LDS) or 2 (workspace)");
   g_sgs_path = path;
   return PAM_AMD_OK;
 }
@@ -3952,18 +3825,18 @@ extern "C" int pam_amd_sgs_smag_coefficients(int nens, int nx, int ny, int nz, c
                                              double *tk, double *tkh, void *stream) {
   const char *who = "sgs_smag_coefficients";
   if (int rc = sgs_check_sizes(who, nens, nx, ny, nz)) return rc;
-  if (!uvel || !vvel || !wvel || !temp || !rho_d || !rho_v || !zint || !zmid || !tk || !tkh) return rad_error(who, "null pointer");
+  if (!uvel || !vvel || !wvel || !temp || !rho_d || !rho_v || !zint || !zmid || !tk || !tkh) return module_error(who, "null pointer");
   if (!sgs_positive(dx) || !sgs_positive(dy) || !sgs_positive(grav) || !sgs_positive(cp_d) || !sgs_positive(cs) || !sgs_positive(prandtl))
-    return rad_error(who, "dx, dy, grav, cp_d, cs and prandtl must be finite and positive");
+    return module_error(who, "dx, dy, grav, cp_d, cs and prandtl must be finite and positive");
   const long long level = (long long)nx * ny * nens, cells = level * nz;
-  std::vector<RadSpan> spans;
+  std::vector<Span> spans;
   for (const double *p : {uvel, vvel, wvel, temp, rho_d, rho_v}) spans.push_back({p, cells, false});
   spans.push_back({zint, (long long)(nz + 1) * nens, false});
   spans.push_back({zmid, (long long)nz * nens, false});
   spans.push_back({tk, cells, true});
   spans.push_back({tkh, cells, true});
-  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if (int rc = require_device(who)) return rc;
   const SgsCoefFields F{{uvel, vvel, wvel, temp, rho_d, rho_v}};
   const sg::CoefParams P{sg::twice(dx), sg::twice(dy), grav, sg::lapse(grav, cp_d), cs, prandtl};
   hipLaunchKernelGGL(sgs_coef_kernel, dim3((unsigned)((level + SGS_THREADS - 1) / SGS_THREADS)), dim3(SGS_THREADS), 0, (hipStream_t)stream, nens,
@@ -3977,14 +3850,14 @@ extern "C" int pam_amd_sgs_smag_diffuse(int nens, int nx, int ny, int nz, double
                                         const double *sfc_flx_v, double dt, double grav, double cp_d, void *stream) {
   const char *who = "sgs_smag_diffuse";
   if (int rc = sgs_check_sizes(who, nens, nx, ny, nz)) return rc;
-  if (num_tracers < 0 || num_tracers > sg::MAX_TRACERS) return rad_error(who, "num_tracers must be in [0, 64]");
-  if (num_tracers > 0 && !tracers) return rad_error(who, "null tracer table");
-  if (!uvel || !vvel || !wvel || !temp || !rho_d || !rho_v || !tk || !tkh || !zint || !zmid) return rad_error(who, "null pointer");
+  if (num_tracers < 0 || num_tracers > sg::MAX_TRACERS) return module_error(who, "num_tracers must be in [0, 64]");
+  if (num_tracers > 0 && !tracers) return module_error(who, "null tracer table");
+  if (!uvel || !vvel || !wvel || !temp || !rho_d || !rho_v || !tk || !tkh || !zint || !zmid) return module_error(who, "null pointer");
   for (int i = 0; i < num_tracers; i++)
-    if (!tracers[i]) return rad_error(who, "null tracer pointer");
-  if (!sgs_positive(dt) || !sgs_positive(grav) || !sgs_positive(cp_d)) return rad_error(who, "dt, grav and cp_d must be finite and positive");
+    if (!tracers[i]) return module_error(who, "null tracer pointer");
+  if (!sgs_positive(dt) || !sgs_positive(grav) || !sgs_positive(cp_d)) return module_error(who, "dt, grav and cp_d must be finite and positive");
   const long long level = (long long)nx * ny * nens, cells = level * nz;
-  std::vector<RadSpan> spans;
+  std::vector<Span> spans;
   for (const double *p : {rho_d, tk, tkh}) spans.push_back({p, cells, false});
   spans.push_back({zint, (long long)(nz + 1) * nens, false});
   spans.push_back({zmid, (long long)nz * nens, false});
@@ -3997,10 +3870,10 @@ extern "C" int pam_amd_sgs_smag_diffuse(int nens, int nx, int ny, int nz, double
     spans.push_back({tracers[i], cells, true});
   }
   spans.push_back({rho_v, cells, vapour_in_table});       // as an output where it is solved: it overlaps nothing else
-  if (rad_spans_overlap(spans)) return rad_error(who, "an output overlaps an input or another output");
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
   const bool lds = g_sgs_path == SGS_AUTO ? (long long)nz * SGS_LDS_THREADS * (long long)sizeof(double) <= SGS_LDS_BYTES : g_sgs_path == SGS_LDS;
-  if (lds && (long long)nz * SGS_LDS_THREADS * (long long)sizeof(double) > SGS_LDS_BYTES) return rad_error(who, "the forced LDS path does not fit its 32 KB at this nz");
-  if (int rc = moist_surface_device_check(who)) return rc;
+  if (lds && (long long)nz * SGS_LDS_THREADS * (long long)sizeof(double) > SGS_LDS_BYTES) return module_error(who, "the forced LDS path does not fit its 32 KB at this nz");
+  if (int rc = require_device(who)) return rc;
 
   SgsSolveArgs A;
   A.mom[0] = uvel; A.mom[1] = vvel; A.mom[2] = wvel;
@@ -4015,23 +3888,12 @@ extern "C" int pam_amd_sgs_smag_diffuse(int nens, int nx, int ny, int nz, double
                        (double *)nullptr);
     return stats_launch_check(who);
   }
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SGS_MAX_DEVICES)
-    return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "sgs_smag_diffuse: cannot tell the current device");
-  SgsWorkspace &w = g_sgs_workspace[dev];
-  std::lock_guard<std::mutex> lk(w.m);
-  if (w.count < cells) {
-    if (w.p) (void)hipFree(w.p);
-    w.p = nullptr;
-    w.count = 0;
-    if (hipMalloc((void **)&w.p, (size_t)cells * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();
-      w.p = nullptr;
-      return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "sgs_smag_diffuse: cannot allocate the workspace of one field");
-    }
-    w.count = cells;
-  }
+  DeviceScratch *w = scratch_slot(SCRATCH_SGS);
+  if (!w) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "sgs_smag_diffuse: cannot tell the current device");
+  std::lock_guard lk(w->m);
+  double *ws = (double *)scratch_reserve(*w, (size_t)cells * sizeof(double), 0);
+  if (!ws) return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "sgs_smag_diffuse: cannot allocate the workspace of one field");
   hipLaunchKernelGGL(sgs_solve_kernel<false>, dim3((unsigned)((level + SGS_THREADS - 1) / SGS_THREADS)), dim3(SGS_THREADS), 0, s, nens, level, nz,
-                     num_tracers, A, rho_d, rho_v, tk, tkh, zint, zmid, dt, gc, w.p);
+                     num_tracers, A, rho_d, rho_v, tk, tkh, zint, zmid, dt, gc, ws);
   return stats_launch_check(who);
 }

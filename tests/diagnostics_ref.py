@@ -77,6 +77,24 @@ def diagnose(a, members=0):
 
 KEYS = ("vmin", "vmax", "vsum", "argmin", "argmax", "nan_count")
 
+MEMBER_GROUP, EXTREME_BYTES, RESULT_BYTES = 4, 40, 48
+
+
+def member_plan_bytes(sizes, members):
+    """bytes of scratch a per-member call (members >= 1) of fields of these sizes plans: per field the level buffers of its sums and
+    one extreme per (group of MEMBER_GROUP row chunks, member), every region 16-byte aligned, then one result per (field, member)
+    (plan_field of diagnostics_device.h and the entry point's own sum over the list)"""
+    chunk, at = MEMBER_W * MEMBER_K, 0
+    for size in sizes:
+        n1 = -(-(size // members) // chunk)
+        entries, n = n1, n1
+        while n > 1:
+            n = -(-n // chunk)
+            entries += n
+        at = -(-(at + entries * members * 8) // 16) * 16
+        at = -(-(at + -(-n1 // MEMBER_GROUP) * members * EXTREME_BYTES) // 16) * 16
+    return at + len(sizes) * members * RESULT_BYTES
+
 
 def bits(d):
     """a result as comparable bytes: the bit patterns of the values, except that every NaN sum is one NaN"""

@@ -398,6 +398,32 @@ def test_gpu_lists_equal_per_field_calls(num, members):
 
 
 @pytest.mark.gpu
+def test_gpu_scratch_grows_with_the_plan():
+    """from no scratch at all: a small whole-field call (the scratch starts at 64 KB), then a per-member call whose plan exceeds 64 KB
+    (it grows) -- the fewest members of 5 rows that do --, then a per-member call of half the members and the whole-field call again on
+    the scratch the large one left, then the large one again from nothing after pam_amd_modules_finalize"""
+    import torch
+    import pam_amd
+    rows, floor = 5, 1 << 16
+    M = next(m for m in range(1, 1 << 16) if ref.member_plan_bytes([rows * m], m) > floor)
+    assert ref.member_plan_bytes([rows * (M - 1)], M - 1) <= floor < ref.member_plan_bytes([rows * M], M) and rows * M * 8 < (16 << 20)
+    rng = np.random.default_rng(909)
+    large, small = ref.mixed(rng, rows * M), ref.mixed(rng, 300)
+    large[rng.integers(0, large.size, 7)] = np.nan
+    half = np.ascontiguousarray(large[:rows * (M // 2)])
+    calls = {"small": (small, 0), "large": (large, M), "half": (half, M // 2)}
+    want = {k: ref.diagnose(a, m) for k, (a, m) in calls.items()}
+    dev = {k: torch.from_numpy(a).to("cuda:0") for k, (a, _) in calls.items()}
+    lib = capi.load()
+    capi.check(lib.pam_amd_modules_finalize())
+    for k in ("small", "large", "half", "small", None, "large"):
+        if k is None:
+            capi.check(lib.pam_amd_modules_finalize())
+            continue
+        assert same(_rows(pam_amd.field_diagnostics([dev[k]], calls[k][1]), 0), want[k]), k
+
+
+@pytest.mark.gpu
 def test_gpu_member_results_do_not_depend_on_member_chunking():
     import torch
     import pam_amd

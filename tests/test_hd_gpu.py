@@ -99,6 +99,24 @@ def test_gpu_field_outside_the_table_and_a_side_stream():
         assert ref.same_bits(bystander.cpu().numpy(), case["fields"][2])
 
 
+@pytest.mark.gpu
+def test_gpu_workspace_grows_with_the_shape():
+    """the workspace path from no workspace at all: the smallest shape with ny >= 5, then the largest, then one between them on the
+    workspace the largest left, then the largest again from nothing after pam_amd_modules_finalize"""
+    from pam_amd import capi
+    lib = capi.load()
+    with_y = sorted((s for s in ref.SHAPES if s[1] >= 5), key=lambda s: s[0] * s[1] * s[2] * s[3])
+    smallest, between, largest = with_y[0], with_y[len(with_y) // 2], with_y[-1]
+    capi.check(lib.pam_amd_modules_finalize())
+    be = GpuBackend(WORKSPACE)
+    for shape in (smallest, largest, between):
+        got = ref.run_case(be, ref.cases(shape)["base"])
+        assert ref.results_differ(got, ref.reference(shape, "base"), nan_by_place=True) == [], shape
+    capi.check(lib.pam_amd_modules_finalize())
+    got = ref.run_case(be, ref.cases(largest)["edge"])
+    assert ref.results_differ(got, ref.reference(largest, "edge"), nan_by_place=True) == []
+
+
 def _coupler(shape, tracers):
     from pam_amd import PamCoupler
     nz, ny, nx, nens = shape

@@ -143,6 +143,24 @@ def test_gpu_bystander_tensor_and_a_side_stream():
 
 
 @pytest.mark.gpu
+def test_gpu_workspace_grows_with_the_shape():
+    """the workspace path from no workspace at all: the smallest shape, then the largest, then one between them on the workspace the
+    largest left, then the largest again from nothing after pam_amd_modules_finalize"""
+    from pam_amd import capi
+    lib = capi.load()
+    by_size = sorted(ref.SHAPES, key=lambda s: s[0] * s[1] * s[2] * s[3])
+    smallest, between, largest = by_size[0], by_size[len(by_size) // 2], by_size[-1]
+    capi.check(lib.pam_amd_modules_finalize())
+    be = GpuBackend(WORKSPACE)
+    for shape in (smallest, largest, between):
+        got = ref.run_case(be, ref.cases(shape)["base"])
+        assert ref.results_differ(got, ref.reference(shape, "base"), nan_by_place=True) == [], shape
+    capi.check(lib.pam_amd_modules_finalize())
+    got = ref.run_case(be, ref.cases(largest)["vapour_last"])
+    assert ref.results_differ(got, ref.reference(largest, "vapour_last"), nan_by_place=True) == []
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(3, 1, 2, 65), (7, 3, 5, 130)], ids=ref.shape_id)
 def test_gpu_python_class_through_a_coupler(shape):
     """SGSSmagorinsky.init / timeStep: tk, tkh, the winds, temp and every registered tracer equal the restatement; density_dry keeps its

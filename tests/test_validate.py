@@ -415,6 +415,35 @@ def test_gpu_lists_equal_per_field_calls(num):
 
 
 @pytest.mark.gpu
+def test_gpu_result_scratch_grows_with_the_list():
+    """from no scratch at all: a list of 1 field, then of 300 (past the 256 fields the scratch starts with: it grows), then of 2 on the
+    scratch the 300 left, then the 300 again from nothing after pam_amd_modules_finalize.  Fields of a few hundred elements of mixed
+    kinds, an offender of the kind's last class at f % n in every third field"""
+    import torch
+    import pam_amd
+    rng = np.random.default_rng(4242)
+    arrays = []
+    for f in range(300):
+        a = _clean(f % 4, 200 + f, rng)
+        if f % 3 == 0:
+            a[f % a.size] = [c for c in _offenders(f % 4) if c is not None][-1][0]
+        arrays.append(a)
+    want = [ref.scan(a, True) for a in arrays]
+    tens = [torch.from_numpy(a).to("cuda:0") for a in arrays]
+    lib = capi.load()
+    capi.check(lib.pam_amd_modules_finalize())
+    for num in (1, 300, 2, None, 300):
+        if num is None:
+            capi.check(lib.pam_amd_modules_finalize())
+            continue
+        count, first = pam_amd.validate_fields(tens[:num], [True] * num)
+        assert count.shape == (num, 3) and first.shape == (num, 3)
+        for f in range(num):
+            assert np.array_equal(count[f], want[f][0]) and np.array_equal(first[f], want[f][1]), (num, f)
+    assert sum(int(w[0].any()) for w in want) == 100
+
+
+@pytest.mark.gpu
 def test_gpu_positive_off_ignores_negatives():
     import torch
     import pam_amd
