@@ -311,7 +311,8 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
-//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->
+//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
+//          [--flux-profiles PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
 // out_freq, vcoords [, crm_nz, zlen, idealized, apply_sponge, initData].  What runs, in the reference's order:
@@ -413,6 +414,11 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              place of the none class's, its timeStep every CRM step after the sponge layer, the surface friction and the
 //                              hyperdiffusion and before the microphysics.  With --surface-friction the fluxes that module computes are
 //                              the lower boundary condition of uvel and vvel; composes with every other flag
+//   --sgs-moist                with --sgs-smag: option sgs_smag_moist, so the closure's stability carries the condensate loading and is
+//                              the saturated one inside cloud (the species of option "micro")
+//   --sfc-fluxes SHF LHF       with --sgs-smag: option sgs_smag_surface_fluxes; "sfc_shf" and "sfc_lhf" are filled uniformly, once, with
+//                              SHF and LHF (W/m2, positive upward) and enter row 0 of temp and of the vapour in every SGS step.  Both
+//                              compose with every other flag
 //   --vt RATE PATH [--vt-u] [--vt-limit L]   CRM variance transport (modules/variance_transport.h): modules::vt_init at the start of every GCM
 //                              step; there is no GCM here, so vt_tend_x = RATE vt_var_start_x (a relative growth rate per second) for
 //                              that GCM step; modules::vt_apply_forcing LAST in every CRM step, after the clock has advanced, with dt =
@@ -440,8 +446,8 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              prof_flux_v and prof_tke, printed with %.17g; nothing else of the run changes.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false;
-  double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0;
+  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false;
+  double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0, sfc_shf = 0, sfc_lhf = 0;
   int handoff_rad_nx = 0, handoff_rad_ny = 0;
   std::string handoff_path;
   double tau = 0, bflx = 0, accel_factor = 0, accel_max_ttend = 5.0, vt_rate = 0, vt_limit = 0.05;
@@ -553,7 +559,18 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     if (mods.sgs_smag) {                                                     // --sgs-smag: the native closure in the SGS slot
       coupler.set_option<real>("sgs_smag_cs", mods.sgs_cs);
       coupler.set_option<real>("sgs_smag_prandtl", mods.sgs_prandtl);
+      coupler.set_option<bool>("sgs_smag_moist", mods.sgs_moist);
+      coupler.set_option<bool>("sgs_smag_surface_fluxes", mods.sfc_fluxes);
       sgs_smag.init(coupler);
+      if (mods.sfc_fluxes) {                                                 // --sfc-fluxes: the two entries, uniformly, once
+        auto &sdm = coupler.get_data_manager_device_readwrite();
+        std::vector<real> h((size_t)crm_ny * crm_nx * nens);
+        for (int q = 0; q < 2; q++) {
+          std::fill(h.begin(), h.end(), (real)(q == 0 ? mods.sfc_shf : mods.sfc_lhf));
+          if (hipMemcpy(sdm.get<real, 3>(q == 0 ? "sfc_shf" : "sfc_lhf").data(), h.data(), h.size() * sizeof(real), hipMemcpyHostToDevice) != hipSuccess)
+            endrun("memcpy");
+        }
+      }
     } else sgs.init(coupler);                                                // driver.cpp:190 (the reference's CI build: SHOC with P3; their numerics are out of scope, their coupling layers are physics/sgs/shoc_amd and physics/micro/p3_amd)
     dycore.init(coupler);                                                    // driver.cpp:191
     if (mods.radiation) {
@@ -903,6 +920,9 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
 #ifdef PAM_FUNCTION_TIMERS
     pam::function_timers::print();
 #endif
+    if (mods.sgs_moist || mods.sfc_fluxes)
+      std::printf("{\"sgs_smag_moist\": %s, \"sgs_smag_surface_fluxes\": %s, \"sfc_shf\": %.17g, \"sfc_lhf\": %.17g}\n",
+                  mods.sgs_moist ? "true" : "false", mods.sfc_fluxes ? "true" : "false", mods.sfc_shf, mods.sfc_lhf);
     if (mods.sgs_smag) std::printf("{\"sgs_smag_cs\": %.17g, \"sgs_smag_prandtl\": %.17g}\n", mods.sgs_cs, mods.sgs_prandtl);
     if (mods.hyperdiff) std::printf("{\"hyperdiff_timescale\": %.17g}\n", mods.hyperdiff_tau);
     if (mods.accelerate)
@@ -965,6 +985,8 @@ int main(int argc, char **argv) {
       else if (o == "--vt-limit" && b + 1 < argc - 1) mods.vt_limit = std::atof(argv[++b]);
       else if (o == "--hyperdiff" && b + 1 < argc - 1) { mods.hyperdiff = true; mods.hyperdiff_tau = std::atof(argv[++b]); }
       else if (o == "--sgs-smag" && b + 2 < argc - 1) { mods.sgs_smag = true; mods.sgs_cs = std::atof(argv[++b]); mods.sgs_prandtl = std::atof(argv[++b]); }
+      else if (o == "--sgs-moist") mods.sgs_moist = true;
+      else if (o == "--sfc-fluxes" && b + 2 < argc - 1) { mods.sfc_fluxes = true; mods.sfc_shf = std::atof(argv[++b]); mods.sfc_lhf = std::atof(argv[++b]); }
       else if (o == "--gcm-handoff" && b + 3 < argc - 1) {
         mods.handoff = true;
         mods.handoff_rad_nx = std::atoi(argv[++b]);
@@ -975,9 +997,10 @@ int main(int argc, char **argv) {
       else if (o == "--flux-profiles" && b + 1 < argc - 1) mods.flux_profiles = argv[++b];
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] "
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] "
                "[--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->");
     }
+    if ((mods.sgs_moist || mods.sfc_fluxes) && !mods.sgs_smag) die("--sgs-moist and --sfc-fluxes need --sgs-smag CS PRANDTL");
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }
 #endif

@@ -636,7 +636,7 @@ int pam_amd_flux_profiles(int nens, int nx, int ny, int nz, const double *const 
  *   Def2 = 2 (ux^2 + vy^2 + wz^2) + (uy + vx)^2 + (uz + wx)^2 + (vz + wy)^2, summed left to right as written: a = ux ux; a = a + vy vy;
  *   a = a + wz wz; d = 2 a; then d = d + s s for s = uy + vx, uz + wx, vz + wy in that order (ny == 1: s = vx, uz + wx, vz).
  *   Tv = temp (1 + 0.608 (rho_v / rho)); N2 = (grav / Tv(k)) (dTv/dz + grav / cp_d), grav / cp_d formed once.  This is the UNSATURATED
- *   frequency: there is no saturated branch and no condensate loading -- a known simplification; a moist N2 is left for later.
+ *   frequency: there is no saturated branch and no condensate loading here; pam_amd_sgs_smag_coefficients_moist (below) has both.
  *   l = cs dz(k); arg = Def2 - N2 / prandtl; tk = (l l) sqrt(arg < 0 ? 0 : arg), so a NaN argument gives a NaN, not 0; tkh = tk / prandtl.
  *   The mixing length is the level thickness, SAM's choice on anisotropic CRM grids.
  *
@@ -678,6 +678,57 @@ int pam_amd_sgs_smag_diffuse(int nens, int nx, int ny, int nz, double *uvel, dou
                              const double *zint, const double *zmid, const double *sfc_flx_u, const double *sfc_flx_v, double dt, double grav,
                              double cp_d, void *stream);
 int pam_amd_sgs_smag_debug_path(int path);
+
+/* The moist branch of the closure's stability, and the surface fluxes of heat and vapour in its solve.  Both are further instances of the
+ * two kernels above; the dry entry points, their bits and their compiled code are unchanged.  Restated in tests/sgs_moist_ref.py.
+ *
+ * pam_amd_sgs_smag_coefficients_moist   as pam_amd_sgs_smag_coefficients, with condensate loading everywhere and the saturated frequency
+ *   inside cloud.  cloud[num_cloud] and precip[num_precip] are HOST tables of DEVICE (nz,ny,nx,nens) densities: the cloud condensate
+ *   (Kessler's cloud_liquid; P3's cloud_water and ice) and the precipitating species (precip_liquid; rain); num_cloud in 0..4, num_precip in
+ *   0..8.  cloud_threshold is a mixing ratio.  Every operation is rounded on its own, no fma, IEEE divisions and root; parentheses give
+ *   the order.  Per cell, from the fields at entry:
+ *     rho = rho_d + rho_v; qv = rho_v / rho.  c = the cloud entries summed in table order from the first entry (no 0.0 +); load = c, then +
+ *     the precip entries in table order (num_cloud == 0: from the first precip entry).  With both tables empty there is no loading and
+ *     its terms are absent (no - 0.0), as the y terms are absent at ny == 1.
+ *     ql = load / rho; f = (1.0 + 0.608 qv) - ql; Trho = temp f; qt = qv + ql (without loading qt = qv).
+ *     sat = c > cloud_threshold rho: strict, so equality is unsaturated and a NaN compares false; never saturated with num_cloud == 0.
+ *     tc = temp - 273.15; es = 610.94 exp_c((17.625 tc) / (243.04 + tc)) (the reference's saturation_vapor_pressure over the exponential
+ *     below); qs = (es / (R_v temp)) / rho.  Lv = (2500.8 - 2.36 tc + 0.0016 tc tc - 0.00006 tc tc tc) 1000, left to right (the
+ *     reference's latent_heat_condensation).
+ *   The vertical differences of Trho, temp, qs and qt are the d/dz above.  With gc = grav / cp_d and eps = R_d / R_v, each formed once:
+ *     unsaturated   N2 = (grav / Trho(k)) (dTrho/dz + gc)
+ *     saturated     (Durran and Klemp 1982, eq. 36, in temperature form)  a1 = 1.0 + (Lv qs) / (R_d temp);
+ *                   a2 = 1.0 + (((eps Lv) Lv) qs) / (((cp_d R_d) temp) temp); b = (dT/dz + gc) / temp + (Lv / (cp_d temp)) dqs/dz;
+ *                   N2 = grav ((a1 / a2) b - dqt/dz), Lv, qs and temp those of level k.
+ *   N2 of level k is the saturated value where sat(k) and the unsaturated one elsewhere: level k alone decides, not its neighbours.
+ *   Def2, l, arg, tk and tkh are as in the dry entry point, and with both tables empty the result has the bits of the dry entry point.
+ *   Simplifications: Lv of liquid water is used for ice as well, and the branch is chosen per cell centre.
+ *   exp_c(x), part of the contract (so the closure stays bit for bit without libm; a last-place difference would be amplified without
+ *   bound by the root near arg = 0): n = floor(x 1.44269504088896338700 + 0.5); r = (x - n 6.93147180369123816490e-01) -
+ *   n 1.90821492927058770002e-10; p = c13; p = p r + c(k) for k = 12 .. 0 with c(k) = 1.0 / k! (an IEEE quotient, k! exact); the result is
+ *   ldexp(p, n).  A NaN gives a NaN, x < -700 gives 0.0, x > 700 gives +inf, before any integer conversion.  Within 1 ulp of glibc's exp for
+ *   150 K <= temp <= 350 K.
+ *
+ * pam_amd_sgs_smag_diffuse_fluxes   as pam_amd_sgs_smag_diffuse, with sfc_shf and sfc_lhf (ny,nx,nens), the surface sensible and latent
+ *   heat flux in W/m2, positive upward; either may be NULL.  Only row 0 of two fields changes:
+ *     temp         after the right-hand side above (lapse term included), r = r + (dt (sfc_shf / (cp_d rho(0)))) / dz(0);
+ *     the vapour   r = rho_v(0) + (dt (sfc_lhf / latvap)) / dz(0): a mass flux, not divided by rho.  sfc_lhf needs rho_v in the tracer table.
+ *   rho is the frozen rho_d + rho_v at entry.  S rho dz temp over a column grows by dt sfc_shf / cp_d and S dz rho_v by dt sfc_lhf / latvap,
+ *   to rounding.  A downward latent flux can make the vapour negative: it is not clamped, and nothing is refused because of a value.
+ *   One launch, both placements of c' as above; with both fluxes NULL the bits are those of pam_amd_sgs_smag_diffuse.
+ *
+ * PAM_AMD_EINVAL before the first HIP call, as above, and: num_cloud outside 0..4 or num_precip outside 0..8; a NULL table with a positive
+ * count or a NULL entry; R_d, R_v or latvap not finite and positive; cloud_threshold negative or not finite; sfc_lhf without rho_v in the
+ * tracer table; an output that overlaps a condensate density or a flux. */
+int pam_amd_sgs_smag_coefficients_moist(int nens, int nx, int ny, int nz, const double *uvel, const double *vvel, const double *wvel,
+                                        const double *temp, const double *rho_d, const double *rho_v, int num_cloud,
+                                        const double *const *cloud, int num_precip, const double *const *precip, const double *zint,
+                                        const double *zmid, double dx, double dy, double grav, double cp_d, double R_d, double R_v,
+                                        double cloud_threshold, double cs, double prandtl, double *tk, double *tkh, void *stream);
+int pam_amd_sgs_smag_diffuse_fluxes(int nens, int nx, int ny, int nz, double *uvel, double *vvel, double *wvel, double *temp, int num_tracers,
+                                    double *const *tracers, const double *rho_d, const double *rho_v, const double *tk, const double *tkh,
+                                    const double *zint, const double *zmid, const double *sfc_flx_u, const double *sfc_flx_v, double dt,
+                                    double grav, double cp_d, const double *sfc_shf, const double *sfc_lhf, double latvap, void *stream);
 
 #ifdef __cplusplus
 }

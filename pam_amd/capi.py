@@ -199,6 +199,10 @@ MODULE_SYMBOLS = {
     "pam_amd_sgs_smag_diffuse": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.POINTER(C.c_void_p)] + [C.c_void_p] * 8
                                  + [C.c_double] * 3 + [C.c_void_p]),
     "pam_amd_sgs_smag_debug_path": (C.c_int, [C.c_int]),
+    "pam_amd_sgs_smag_coefficients_moist": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 6 + [C.c_int, C.POINTER(C.c_void_p)] * 2 + [C.c_void_p] * 2
+                                            + [C.c_double] * 9 + [C.c_void_p] * 3),
+    "pam_amd_sgs_smag_diffuse_fluxes": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.POINTER(C.c_void_p)] + [C.c_void_p] * 8
+                                        + [C.c_double] * 3 + [C.c_void_p] * 2 + [C.c_double, C.c_void_p]),
 }
 
 

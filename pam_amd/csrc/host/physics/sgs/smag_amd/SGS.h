@@ -5,8 +5,16 @@
 // and "tkh", pam_amd_sgs_smag_diffuse mixes uvel, vvel, wvel, temp and EVERY registered tracer along the column (the reference's SHOC
 // layer diffuses every tracer too) and takes "sfc_mom_flx_u/v", which modules::compute_surface_friction fills, as the lower boundary
 // condition of the horizontal winds.  density_dry is never written.
-//   options read:  crm_dt, grav, cp_d (the microphysics sets the constants), sgs_smag_cs, sgs_smag_prandtl
-//   options set by init:  "sgs" = "smagorinsky"; sgs_smag_cs = 0.2 and sgs_smag_prandtl = 1/3 unless present
+// With option sgs_smag_moist the coefficients come from pam_amd_sgs_smag_coefficients_moist: the loading of every condensate, and the
+// saturated frequency inside cloud; the species follow option "micro" (kessler: cloud_liquid / precip_liquid; p3: cloud_water, ice /
+// rain; none: no species).  With option sgs_smag_surface_fluxes the solve is pam_amd_sgs_smag_diffuse_fluxes, which takes "sfc_shf" and
+// "sfc_lhf" (W/m2, positive upward; whoever drives the run fills them) into row 0 of temp and of the vapour.  With both off the calls
+// are the two above.
+//   options read:  crm_dt, grav, cp_d (the microphysics sets the constants), sgs_smag_cs, sgs_smag_prandtl, sgs_smag_moist,
+//                  sgs_smag_surface_fluxes; moist: micro, R_d, R_v, sgs_smag_cloud_threshold; surface fluxes: latvap where it exists
+//                  (2501000.0 otherwise)
+//   options set by init:  "sgs" = "smagorinsky"; sgs_smag_cs = 0.2, sgs_smag_prandtl = 1/3, sgs_smag_moist = false,
+//                  sgs_smag_surface_fluxes = false and sgs_smag_cloud_threshold = 0.0 unless present
 #pragma once
 #include <string>
 #include <vector>
@@ -37,12 +45,20 @@ class PAM_SGS_CLASS {
     coupler.set_option<std::string>("sgs", "smagorinsky");
     if (!coupler.option_exists("sgs_smag_cs")) coupler.set_option<real>("sgs_smag_cs", 0.2);
     if (!coupler.option_exists("sgs_smag_prandtl")) coupler.set_option<real>("sgs_smag_prandtl", 1.0 / 3.0);
+    if (!coupler.option_exists("sgs_smag_moist")) coupler.set_option<bool>("sgs_smag_moist", false);
+    if (!coupler.option_exists("sgs_smag_surface_fluxes")) coupler.set_option<bool>("sgs_smag_surface_fluxes", false);
+    if (!coupler.option_exists("sgs_smag_cloud_threshold")) coupler.set_option<real>("sgs_smag_cloud_threshold", 0.0);
+    if (coupler.get_option<bool>("sgs_smag_surface_fluxes")) {             // the reference's names and descriptions (shoc/SGS.h:115-116)
+      if (!dm.entry_exists("sfc_shf")) dm.register_and_allocate<real>("sfc_shf", "input surface sensible heat flux [W/m2]", {ny, nx, nens}, {"y", "x", "nens"});
+      if (!dm.entry_exists("sfc_lhf")) dm.register_and_allocate<real>("sfc_lhf", "input surface latent heat flux [W/m2]", {ny, nx, nens}, {"y", "x", "nens"});
+    }
   }
 
   void timeStep(pam::PamCoupler &coupler) {
     int nx = coupler.get_nx(), ny = coupler.get_ny(), nz = coupler.get_nz(), nens = coupler.get_nens();
     real dt = coupler.get_option<real>("crm_dt"), grav = coupler.get_option<real>("grav"), cp_d = coupler.get_option<real>("cp_d");
     real cs = coupler.get_option<real>("sgs_smag_cs"), prandtl = coupler.get_option<real>("sgs_smag_prandtl");
+    bool moist = coupler.get_option<bool>("sgs_smag_moist"), fluxes = coupler.get_option<bool>("sgs_smag_surface_fluxes");
     auto &dm = coupler.get_data_manager_device_readwrite();
     real *uvel = dm.get<real, 4>("uvel").data(), *vvel = dm.get<real, 4>("vvel").data(), *wvel = dm.get<real, 4>("wvel").data();
     real *temp = dm.get<real, 4>("temp").data(), *tk = dm.get<real, 4>("tk").data(), *tkh = dm.get<real, 4>("tkh").data();
@@ -52,10 +68,32 @@ class PAM_SGS_CLASS {
     real const *flx_u = dm.get<real const, 3>("sfc_mom_flx_u").data(), *flx_v = dm.get<real const, 3>("sfc_mom_flx_v").data();
     std::vector<double *> tracers;
     for (auto &n : coupler.get_tracer_names()) tracers.push_back(dm.get<real, 4>(n).data());
-    chk(pam_amd_sgs_smag_coefficients(nens, nx, ny, nz, uvel, vvel, wvel, temp, rho_d, rho_v, zint, zmid, coupler.get_dx(), coupler.get_dy(), grav,
-                                      cp_d, cs, prandtl, tk, tkh, nullptr));
-    chk(pam_amd_sgs_smag_diffuse(nens, nx, ny, nz, uvel, vvel, wvel, temp, (int)tracers.size(), tracers.data(), rho_d, rho_v, tk, tkh, zint, zmid,
-                                 flx_u, flx_v, dt, grav, cp_d, nullptr));
+    if (moist) {
+      std::string micro = coupler.option_exists("micro") ? coupler.get_option<std::string>("micro") : std::string("none");
+      std::vector<std::string> cloud_names, precip_names;
+      if (micro == "kessler") { cloud_names = {"cloud_liquid"}; precip_names = {"precip_liquid"}; }
+      else if (micro == "p3") { cloud_names = {"cloud_water", "ice"}; precip_names = {"rain"}; }
+      else if (micro != "none") endrun("ERROR: sgs: the moist branch knows the species of micro = kessler, p3 and none");
+      std::vector<const double *> cloud, precip;
+      for (auto &n : cloud_names) cloud.push_back(dm.get<real const, 4>(n).data());
+      for (auto &n : precip_names) precip.push_back(dm.get<real const, 4>(n).data());
+      chk(pam_amd_sgs_smag_coefficients_moist(nens, nx, ny, nz, uvel, vvel, wvel, temp, rho_d, rho_v, (int)cloud.size(), cloud.data(),
+                                              (int)precip.size(), precip.data(), zint, zmid, coupler.get_dx(), coupler.get_dy(), grav, cp_d,
+                                              coupler.get_option<real>("R_d"), coupler.get_option<real>("R_v"),
+                                              coupler.get_option<real>("sgs_smag_cloud_threshold"), cs, prandtl, tk, tkh, nullptr));
+    } else {
+      chk(pam_amd_sgs_smag_coefficients(nens, nx, ny, nz, uvel, vvel, wvel, temp, rho_d, rho_v, zint, zmid, coupler.get_dx(), coupler.get_dy(), grav,
+                                        cp_d, cs, prandtl, tk, tkh, nullptr));
+    }
+    if (fluxes) {
+      real const *shf = dm.get<real const, 3>("sfc_shf").data(), *lhf = dm.get<real const, 3>("sfc_lhf").data();
+      real latvap = coupler.option_exists("latvap") ? coupler.get_option<real>("latvap") : 2501000.0;
+      chk(pam_amd_sgs_smag_diffuse_fluxes(nens, nx, ny, nz, uvel, vvel, wvel, temp, (int)tracers.size(), tracers.data(), rho_d, rho_v, tk, tkh, zint,
+                                          zmid, flx_u, flx_v, dt, grav, cp_d, shf, lhf, latvap, nullptr));
+    } else {
+      chk(pam_amd_sgs_smag_diffuse(nens, nx, ny, nz, uvel, vvel, wvel, temp, (int)tracers.size(), tracers.data(), rho_d, rho_v, tk, tkh, zint, zmid,
+                                   flx_u, flx_v, dt, grav, cp_d, nullptr));
+    }
   }
 
   std::string sgs_name() const { return "smagorinsky"; }

@@ -3760,6 +3760,8 @@ namespace {
 namespace sg = pama::sgs;
 struct SgsCoefFields { const double *p[6]; };
 struct SgsSolveArgs { double *mom[3]; const double *sfc[3]; double *heat[1]; double *tr[sg::MAX_TRACERS]; };
+struct SgsMoistTables { const double *cloud[sg::MAX_CLOUD]; const double *precip[sg::MAX_PRECIP]; };      // unused entries are NULL
+struct SgsFluxArgs { const double *heat[1]; const double *tr[sg::MAX_TRACERS]; };     // sfc_shf; sfc_lhf at the vapour's index, NULL elsewhere
 constexpr int SGS_THREADS = 256;
 constexpr int SGS_LDS_THREADS = 64;                  // the LDS path: one wavefront per workgroup
 constexpr int SGS_LDS_BYTES = 32 * 1024;             // its budget: five workgroups on a compute unit's 160 KB
@@ -3777,6 +3779,25 @@ __global__ void __launch_bounds__(SGS_THREADS) sgs_coef_kernel(int nens, int nx,
 #pragma unroll
   for (int q = 0; q < 6; q++) f[q] = F.p[q];
   sg::coef_column(f, zint + e, zmid + e, level, nens, nx, ny, nz, j, i, e, P, tk, tkh);
+}
+
+// the moist instance of the same walk: the condensate tables ride along, and a cloudy cell takes the saturated frequency
+__global__ void __launch_bounds__(SGS_THREADS) sgs_coef_moist_kernel(int nens, int nx, int ny, int nz, long long level, SgsCoefFields F,
+                                                                     SgsMoistTables W, const double *__restrict__ zint,
+                                                                     const double *__restrict__ zmid, sg::CoefParams P, sg::MoistParams M,
+                                                                     double *__restrict__ tk, double *__restrict__ tkh) {
+  const long long t = (long long)blockIdx.x * SGS_THREADS + (long long)threadIdx.x;
+  if (t >= level) return;
+  const long long c = t / nens;
+  const int e = (int)(t - c * nens), j = (int)(c / nx), i = (int)(c - (long long)j * nx);
+  const double *f[6], *cloud[sg::MAX_CLOUD], *precip[sg::MAX_PRECIP];
+#pragma unroll
+  for (int q = 0; q < 6; q++) f[q] = F.p[q];
+#pragma unroll
+  for (int q = 0; q < sg::MAX_CLOUD; q++) cloud[q] = W.cloud[q];
+#pragma unroll
+  for (int q = 0; q < sg::MAX_PRECIP; q++) precip[q] = W.precip[q];
+  sg::coef_column_t<true>(f, cloud, precip, M, zint + e, zmid + e, level, nens, nx, ny, nz, j, i, e, P, tk, tkh);
 }
 
 // grid (ceil(ny nx nens / block)), block 64 (LDS: nz x 64 doubles of dynamic LDS) or 256 (workspace: ws is (nz,ny,nx,nens))
@@ -3798,6 +3819,27 @@ __global__ void __launch_bounds__(LDS ? SGS_LDS_THREADS : SGS_THREADS) sgs_solve
   if (num_tracers > 0) sg::solve_class(sg::C_TRACER, A.tr, num_tracers, nullptr, t, rd, rv, tkh, zi, zm, level, (long long)nens, nz, dt, gc, cp, cs);
 }
 
+// the same launch with the surface fluxes of heat (W/m2, scaled by cp_d rho(0)) and of vapour (W/m2, scaled by latvap) in row 0
+template <bool LDS>
+__global__ void __launch_bounds__(LDS ? SGS_LDS_THREADS : SGS_THREADS) sgs_solve_flux_kernel(int nens, long long level, int nz, int num_tracers,
+                                                                                             SgsSolveArgs A, SgsFluxArgs X, const double *rd,
+                                                                                             const double *rv, const double *tk, const double *tkh,
+                                                                                             const double *zint, const double *zmid, double dt,
+                                                                                             double gc, double cp_d, double latvap, double *ws) {
+  extern __shared__ double sgs_cp[];
+  constexpr int T = LDS ? SGS_LDS_THREADS : SGS_THREADS;
+  const long long t = (long long)blockIdx.x * T + (long long)threadIdx.x;
+  if (t >= level) return;                                   // no barrier below: a thread's c' is its own
+  const int e = (int)(t % nens);
+  double *cp = LDS ? sgs_cp + threadIdx.x : ws + t;
+  const long long cs = LDS ? (long long)T : level;
+  const double *zi = zint + e, *zm = zmid + e;
+  sg::solve_class_t<true>(sg::C_MOMENTUM, A.mom, 3, A.sfc, t, rd, rv, tk, zi, zm, level, (long long)nens, nz, dt, gc, cp, cs, 0.0);
+  sg::solve_class_t<true>(sg::C_HEAT, A.heat, 1, X.heat, t, rd, rv, tkh, zi, zm, level, (long long)nens, nz, dt, gc, cp, cs, cp_d);
+  if (num_tracers > 0)
+    sg::solve_class_t<true>(sg::C_TRACER, A.tr, num_tracers, X.tr, t, rd, rv, tkh, zi, zm, level, (long long)nens, nz, dt, gc, cp, cs, latvap);
+}
+
 // the workspace of c' on the path without LDS is the per-device scratch (above), at exactly the size the largest call needed.  The
 // launch goes to the caller's stream and nothing synchronises: its mutex is held over the launch only, as for column_diagnostics.
 int g_sgs_path = SGS_AUTO;   // pam_amd_sgs_smag_debug_path: tests run both placements of c' at small shapes
@@ -3811,6 +3853,122 @@ int sgs_check_sizes(const char *who, int nens, int nx, int ny, int nz) {
   if (((long long)nx * ny * nens + SGS_LDS_THREADS - 1) / SGS_LDS_THREADS > 0x7fffffffLL) return module_error(who, "ny x nx x nens exceeds the grid");
   return PAM_AMD_OK;
 }
+// the checks and the launch both coefficient entry points share; moist: the tables and the gas constants take part
+int sgs_coefficients(const char *who, bool moist, int nens, int nx, int ny, int nz, const double *uvel, const double *vvel, const double *wvel,
+                     const double *temp, const double *rho_d, const double *rho_v, int num_cloud, const double *const *cloud, int num_precip,
+                     const double *const *precip, const double *zint, const double *zmid, double dx, double dy, double grav, double cp_d, double R_d,
+                     double R_v, double cloud_threshold, double cs, double prandtl, double *tk, double *tkh, void *stream) {
+  if (int rc = sgs_check_sizes(who, nens, nx, ny, nz)) return rc;
+  if (!uvel || !vvel || !wvel || !temp || !rho_d || !rho_v || !zint || !zmid || !tk || !tkh) return module_error(who, "null pointer");
+  if (!sgs_positive(dx) || !sgs_positive(dy) || !sgs_positive(grav) || !sgs_positive(cp_d) || !sgs_positive(cs) || !sgs_positive(prandtl))
+    return module_error(who, "dx, dy, grav, cp_d, cs and prandtl must be finite and positive");
+  if (moist) {
+    if (num_cloud < 0 || num_cloud > sg::MAX_CLOUD) return module_error(who, "num_cloud must be in [0, 4]");
+    if (num_precip < 0 || num_precip > sg::MAX_PRECIP) return module_error(who, "num_precip must be in [0, 8]");
+    if ((num_cloud > 0 && !cloud) || (num_precip > 0 && !precip)) return module_error(who, "null condensate table");
+    for (int i = 0; i < num_cloud; i++)
+      if (!cloud[i]) return module_error(who, "null cloud pointer");
+    for (int i = 0; i < num_precip; i++)
+      if (!precip[i]) return module_error(who, "null precip pointer");
+    if (!sgs_positive(R_d) || !sgs_positive(R_v)) return module_error(who, "R_d and R_v must be finite and positive");
+    if (!std::isfinite(cloud_threshold) || cloud_threshold < 0) return module_error(who, "cloud_threshold must be finite and >= 0");
+  }
+  const long long level = (long long)nx * ny * nens, cells = level * nz;
+  std::vector<Span> spans;
+  for (const double *p : {uvel, vvel, wvel, temp, rho_d, rho_v}) spans.push_back({p, cells, false});
+  spans.push_back({zint, (long long)(nz + 1) * nens, false});
+  spans.push_back({zmid, (long long)nz * nens, false});
+  if (moist) {
+    for (int i = 0; i < num_cloud; i++) spans.push_back({cloud[i], cells, false});
+    for (int i = 0; i < num_precip; i++) spans.push_back({precip[i], cells, false});
+  }
+  spans.push_back({tk, cells, true});
+  spans.push_back({tkh, cells, true});
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if (int rc = require_device(who)) return rc;
+  const SgsCoefFields F{{uvel, vvel, wvel, temp, rho_d, rho_v}};
+  const sg::CoefParams P{sg::twice(dx), sg::twice(dy), grav, sg::lapse(grav, cp_d), cs, prandtl};
+  const dim3 grid((unsigned)((level + SGS_THREADS - 1) / SGS_THREADS)), block(SGS_THREADS);
+  if (!moist) {
+    hipLaunchKernelGGL(sgs_coef_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, ny, nz, level, F, zint, zmid, P, tk, tkh);
+    return stats_launch_check(who);
+  }
+  SgsMoistTables W;
+  for (int i = 0; i < sg::MAX_CLOUD; i++) W.cloud[i] = i < num_cloud ? cloud[i] : nullptr;
+  for (int i = 0; i < sg::MAX_PRECIP; i++) W.precip[i] = i < num_precip ? precip[i] : nullptr;
+  const sg::MoistParams M{R_d, R_v, cp_d, sg::ratio(R_d, R_v), cloud_threshold, num_cloud, num_precip};
+  hipLaunchKernelGGL(sgs_coef_moist_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, ny, nz, level, F, W, zint, zmid, P, M, tk, tkh);
+  return stats_launch_check(who);
+}
+
+// the checks and the launch both solve entry points share; fluxes: sfc_shf, sfc_lhf and latvap take part, and the launch is the flux
+// instance of the kernel even where both are NULL (the same bits)
+int sgs_diffuse(const char *who, bool fluxes, int nens, int nx, int ny, int nz, double *uvel, double *vvel, double *wvel, double *temp,
+                int num_tracers, double *const *tracers, const double *rho_d, const double *rho_v, const double *tk, const double *tkh,
+                const double *zint, const double *zmid, const double *sfc_flx_u, const double *sfc_flx_v, double dt, double grav, double cp_d,
+                const double *sfc_shf, const double *sfc_lhf, double latvap, void *stream) {
+  if (int rc = sgs_check_sizes(who, nens, nx, ny, nz)) return rc;
+  if (num_tracers < 0 || num_tracers > sg::MAX_TRACERS) return module_error(who, "num_tracers must be in [0, 64]");
+  if (num_tracers > 0 && !tracers) return module_error(who, "null tracer table");
+  if (!uvel || !vvel || !wvel || !temp || !rho_d || !rho_v || !tk || !tkh || !zint || !zmid) return module_error(who, "null pointer");
+  for (int i = 0; i < num_tracers; i++)
+    if (!tracers[i]) return module_error(who, "null tracer pointer");
+  if (!sgs_positive(dt) || !sgs_positive(grav) || !sgs_positive(cp_d)) return module_error(who, "dt, grav and cp_d must be finite and positive");
+  if (fluxes && !sgs_positive(latvap)) return module_error(who, "latvap must be finite and positive");
+  const long long level = (long long)nx * ny * nens, cells = level * nz;
+  std::vector<Span> spans;
+  for (const double *p : {rho_d, tk, tkh}) spans.push_back({p, cells, false});
+  spans.push_back({zint, (long long)(nz + 1) * nens, false});
+  spans.push_back({zmid, (long long)nz * nens, false});
+  for (const double *p : {sfc_flx_u, sfc_flx_v, sfc_shf, sfc_lhf})
+    if (p) spans.push_back({p, level, false});
+  for (double *p : {uvel, vvel, wvel, temp}) spans.push_back({p, cells, true});
+  int vapour = -1;
+  for (int i = 0; i < num_tracers; i++) {
+    if (tracers[i] == rho_v && vapour < 0) { vapour = i; continue; }      // the one allowed alias: rho_v itself, once
+    spans.push_back({tracers[i], cells, true});
+  }
+  spans.push_back({rho_v, cells, vapour >= 0});           // as an output where it is solved: it overlaps nothing else
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if (sfc_lhf && vapour < 0) return module_error(who, "sfc_lhf needs rho_v itself in the tracer table");
+  const bool lds = g_sgs_path == SGS_AUTO ? (long long)nz * SGS_LDS_THREADS * (long long)sizeof(double) <= SGS_LDS_BYTES : g_sgs_path == SGS_LDS;
+  if (lds && (long long)nz * SGS_LDS_THREADS * (long long)sizeof(double) > SGS_LDS_BYTES) return module_error(who, "the forced LDS path does not fit its 32 KB at this nz");
+  if (int rc = require_device(who)) return rc;
+
+  SgsSolveArgs A;
+  A.mom[0] = uvel; A.mom[1] = vvel; A.mom[2] = wvel;
+  A.sfc[0] = sfc_flx_u; A.sfc[1] = sfc_flx_v; A.sfc[2] = nullptr;
+  A.heat[0] = temp;
+  for (int i = 0; i < sg::MAX_TRACERS; i++) A.tr[i] = i < num_tracers ? tracers[i] : nullptr;
+  SgsFluxArgs X;
+  X.heat[0] = sfc_shf;
+  for (int i = 0; i < sg::MAX_TRACERS; i++) X.tr[i] = sfc_lhf && i == vapour ? sfc_lhf : nullptr;
+  const double gc = sg::lapse(grav, cp_d);
+  hipStream_t s = (hipStream_t)stream;
+  if (lds) {
+    const dim3 grid((unsigned)((level + SGS_LDS_THREADS - 1) / SGS_LDS_THREADS)), block(SGS_LDS_THREADS);
+    const size_t bytes = (size_t)nz * SGS_LDS_THREADS * sizeof(double);
+    if (fluxes)
+      hipLaunchKernelGGL(sgs_solve_flux_kernel<true>, grid, block, bytes, s, nens, level, nz, num_tracers, A, X, rho_d, rho_v, tk, tkh, zint, zmid, dt,
+                         gc, cp_d, latvap, (double *)nullptr);
+    else
+      hipLaunchKernelGGL(sgs_solve_kernel<true>, grid, block, bytes, s, nens, level, nz, num_tracers, A, rho_d, rho_v, tk, tkh, zint, zmid, dt, gc,
+                         (double *)nullptr);
+    return stats_launch_check(who);
+  }
+  DeviceScratch *w = scratch_slot(SCRATCH_SGS);
+  if (!w) return module_error(PAM_AMD_ENOGPU, who, "cannot tell the current device");
+  std::lock_guard lk(w->m);
+  double *ws = (double *)scratch_reserve(*w, (size_t)cells * sizeof(double), 0);
+  if (!ws) return module_error(PAM_AMD_ENOMEM, who, "cannot allocate the workspace of one field");
+  const dim3 grid((unsigned)((level + SGS_THREADS - 1) / SGS_THREADS)), block(SGS_THREADS);
+  if (fluxes)
+    hipLaunchKernelGGL(sgs_solve_flux_kernel<false>, grid, block, 0, s, nens, level, nz, num_tracers, A, X, rho_d, rho_v, tk, tkh, zint, zmid, dt, gc,
+                       cp_d, latvap, ws);
+  else
+    hipLaunchKernelGGL(sgs_solve_kernel<false>, grid, block, 0, s, nens, level, nz, num_tracers, A, rho_d, rho_v, tk, tkh, zint, zmid, dt, gc, ws);
+  return stats_launch_check(who);
+}
 }  // namespace
 
 extern "C" int pam_amd_sgs_smag_debug_path(int path) {
@@ -3823,77 +3981,32 @@ extern "C" int pam_amd_sgs_smag_coefficients(int nens, int nx, int ny, int nz, c
                                              const double *temp, const double *rho_d, const double *rho_v, const double *zint,
                                              const double *zmid, double dx, double dy, double grav, double cp_d, double cs, double prandtl,
                                              double *tk, double *tkh, void *stream) {
-  const char *who = "sgs_smag_coefficients";
-  if (int rc = sgs_check_sizes(who, nens, nx, ny, nz)) return rc;
-  if (!uvel || !vvel || !wvel || !temp || !rho_d || !rho_v || !zint || !zmid || !tk || !tkh) return module_error(who, "null pointer");
-  if (!sgs_positive(dx) || !sgs_positive(dy) || !sgs_positive(grav) || !sgs_positive(cp_d) || !sgs_positive(cs) || !sgs_positive(prandtl))
-    return module_error(who, "dx, dy, grav, cp_d, cs and prandtl must be finite and positive");
-  const long long level = (long long)nx * ny * nens, cells = level * nz;
-  std::vector<Span> spans;
-  for (const double *p : {uvel, vvel, wvel, temp, rho_d, rho_v}) spans.push_back({p, cells, false});
-  spans.push_back({zint, (long long)(nz + 1) * nens, false});
-  spans.push_back({zmid, (long long)nz * nens, false});
-  spans.push_back({tk, cells, true});
-  spans.push_back({tkh, cells, true});
-  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
-  if (int rc = require_device(who)) return rc;
-  const SgsCoefFields F{{uvel, vvel, wvel, temp, rho_d, rho_v}};
-  const sg::CoefParams P{sg::twice(dx), sg::twice(dy), grav, sg::lapse(grav, cp_d), cs, prandtl};
-  hipLaunchKernelGGL(sgs_coef_kernel, dim3((unsigned)((level + SGS_THREADS - 1) / SGS_THREADS)), dim3(SGS_THREADS), 0, (hipStream_t)stream, nens,
-                     nx, ny, nz, level, F, zint, zmid, P, tk, tkh);
-  return stats_launch_check(who);
+  return sgs_coefficients("sgs_smag_coefficients", false, nens, nx, ny, nz, uvel, vvel, wvel, temp, rho_d, rho_v, 0, nullptr, 0, nullptr, zint, zmid,
+                          dx, dy, grav, cp_d, 0.0, 0.0, 0.0, cs, prandtl, tk, tkh, stream);
+}
+
+extern "C" int pam_amd_sgs_smag_coefficients_moist(int nens, int nx, int ny, int nz, const double *uvel, const double *vvel, const double *wvel,
+                                                   const double *temp, const double *rho_d, const double *rho_v, int num_cloud,
+                                                   const double *const *cloud, int num_precip, const double *const *precip, const double *zint,
+                                                   const double *zmid, double dx, double dy, double grav, double cp_d, double R_d, double R_v,
+                                                   double cloud_threshold, double cs, double prandtl, double *tk, double *tkh, void *stream) {
+  return sgs_coefficients("sgs_smag_coefficients_moist", true, nens, nx, ny, nz, uvel, vvel, wvel, temp, rho_d, rho_v, num_cloud, cloud, num_precip,
+                          precip, zint, zmid, dx, dy, grav, cp_d, R_d, R_v, cloud_threshold, cs, prandtl, tk, tkh, stream);
 }
 
 extern "C" int pam_amd_sgs_smag_diffuse(int nens, int nx, int ny, int nz, double *uvel, double *vvel, double *wvel, double *temp,
                                         int num_tracers, double *const *tracers, const double *rho_d, const double *rho_v, const double *tk,
                                         const double *tkh, const double *zint, const double *zmid, const double *sfc_flx_u,
                                         const double *sfc_flx_v, double dt, double grav, double cp_d, void *stream) {
-  const char *who = "sgs_smag_diffuse";
-  if (int rc = sgs_check_sizes(who, nens, nx, ny, nz)) return rc;
-  if (num_tracers < 0 || num_tracers > sg::MAX_TRACERS) return module_error(who, "num_tracers must be in [0, 64]");
-  if (num_tracers > 0 && !tracers) return module_error(who, "null tracer table");
-  if (!uvel || !vvel || !wvel || !temp || !rho_d || !rho_v || !tk || !tkh || !zint || !zmid) return module_error(who, "null pointer");
-  for (int i = 0; i < num_tracers; i++)
-    if (!tracers[i]) return module_error(who, "null tracer pointer");
-  if (!sgs_positive(dt) || !sgs_positive(grav) || !sgs_positive(cp_d)) return module_error(who, "dt, grav and cp_d must be finite and positive");
-  const long long level = (long long)nx * ny * nens, cells = level * nz;
-  std::vector<Span> spans;
-  for (const double *p : {rho_d, tk, tkh}) spans.push_back({p, cells, false});
-  spans.push_back({zint, (long long)(nz + 1) * nens, false});
-  spans.push_back({zmid, (long long)nz * nens, false});
-  if (sfc_flx_u) spans.push_back({sfc_flx_u, level, false});
-  if (sfc_flx_v) spans.push_back({sfc_flx_v, level, false});
-  for (double *p : {uvel, vvel, wvel, temp}) spans.push_back({p, cells, true});
-  bool vapour_in_table = false;
-  for (int i = 0; i < num_tracers; i++) {
-    if (tracers[i] == rho_v && !vapour_in_table) { vapour_in_table = true; continue; }      // the one allowed alias: rho_v itself, once
-    spans.push_back({tracers[i], cells, true});
-  }
-  spans.push_back({rho_v, cells, vapour_in_table});       // as an output where it is solved: it overlaps nothing else
-  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
-  const bool lds = g_sgs_path == SGS_AUTO ? (long long)nz * SGS_LDS_THREADS * (long long)sizeof(double) <= SGS_LDS_BYTES : g_sgs_path == SGS_LDS;
-  if (lds && (long long)nz * SGS_LDS_THREADS * (long long)sizeof(double) > SGS_LDS_BYTES) return module_error(who, "the forced LDS path does not fit its 32 KB at this nz");
-  if (int rc = require_device(who)) return rc;
+  return sgs_diffuse("sgs_smag_diffuse", false, nens, nx, ny, nz, uvel, vvel, wvel, temp, num_tracers, tracers, rho_d, rho_v, tk, tkh, zint, zmid,
+                     sfc_flx_u, sfc_flx_v, dt, grav, cp_d, nullptr, nullptr, 0.0, stream);
+}
 
-  SgsSolveArgs A;
-  A.mom[0] = uvel; A.mom[1] = vvel; A.mom[2] = wvel;
-  A.sfc[0] = sfc_flx_u; A.sfc[1] = sfc_flx_v; A.sfc[2] = nullptr;
-  A.heat[0] = temp;
-  for (int i = 0; i < sg::MAX_TRACERS; i++) A.tr[i] = i < num_tracers ? tracers[i] : nullptr;
-  const double gc = sg::lapse(grav, cp_d);
-  hipStream_t s = (hipStream_t)stream;
-  if (lds) {
-    hipLaunchKernelGGL(sgs_solve_kernel<true>, dim3((unsigned)((level + SGS_LDS_THREADS - 1) / SGS_LDS_THREADS)), dim3(SGS_LDS_THREADS),
-                       (size_t)nz * SGS_LDS_THREADS * sizeof(double), s, nens, level, nz, num_tracers, A, rho_d, rho_v, tk, tkh, zint, zmid, dt, gc,
-                       (double *)nullptr);
-    return stats_launch_check(who);
-  }
-  DeviceScratch *w = scratch_slot(SCRATCH_SGS);
-  if (!w) return pam_amd_set_last_error_(PAM_AMD_ENOGPU, "sgs_smag_diffuse: cannot tell the current device");
-  std::lock_guard lk(w->m);
-  double *ws = (double *)scratch_reserve(*w, (size_t)cells * sizeof(double), 0);
-  if (!ws) return pam_amd_set_last_error_(PAM_AMD_ENOMEM, "sgs_smag_diffuse: cannot allocate the workspace of one field");
-  hipLaunchKernelGGL(sgs_solve_kernel<false>, dim3((unsigned)((level + SGS_THREADS - 1) / SGS_THREADS)), dim3(SGS_THREADS), 0, s, nens, level, nz,
-                     num_tracers, A, rho_d, rho_v, tk, tkh, zint, zmid, dt, gc, ws);
-  return stats_launch_check(who);
+extern "C" int pam_amd_sgs_smag_diffuse_fluxes(int nens, int nx, int ny, int nz, double *uvel, double *vvel, double *wvel, double *temp,
+                                               int num_tracers, double *const *tracers, const double *rho_d, const double *rho_v,
+                                               const double *tk, const double *tkh, const double *zint, const double *zmid,
+                                               const double *sfc_flx_u, const double *sfc_flx_v, double dt, double grav, double cp_d,
+                                               const double *sfc_shf, const double *sfc_lhf, double latvap, void *stream) {
+  return sgs_diffuse("sgs_smag_diffuse_fluxes", true, nens, nx, ny, nz, uvel, vvel, wvel, temp, num_tracers, tracers, rho_d, rho_v, tk, tkh, zint,
+                     zmid, sfc_flx_u, sfc_flx_v, dt, grav, cp_d, sfc_shf, sfc_lhf, latvap, stream);
 }

@@ -6,6 +6,10 @@
 // Fields are (nz, ny, nx, nens), members fastest; inside a level a (column, member) has the flat index t = (j nx + i) nens + e, and every
 // element offset is 64 bits wide.  zint (nz+1, nens) and zmid (nz, nens) are per member.
 // Contraction into fma is switched off inside each body, so the device and the host give the same bits.
+// The moist branch (coef_column_t<true>: condensate loading, a saturated N2 where cloud stands, with an exponential of its own, exp_c)
+// and the surface fluxes of heat and vapour (solve_class_t<true>) are further instances of the same two bodies; the instances the dry
+// entry points use (coef_column, solve_class) are the <false> ones.  tests/emu/sgs_moist_emu.cpp compiles the new ones under g++ and
+// tests/sgs_moist_ref.py restates them.
 #pragma once
 
 #include <cmath>
@@ -85,27 +89,158 @@ PAMA_D void eddy(double def2, double n2, double dz, double cs, double prandtl, d
   tkh = tk / prandtl;
 }
 
+// ---- the moist branch of the coefficients
+constexpr int MAX_CLOUD = 4, MAX_PRECIP = 8;          // entries of the two tables of condensate densities
+
+struct MoistParams {
+  double R_d, R_v, cp_d, eps, threshold;              // eps = R_d / R_v, formed once; threshold: a mixing ratio
+  int num_cloud, num_precip;
+};
+
+inline double ratio(double a, double b) {             // host, once per call
+  PAMA_NO_CONTRACT
+  return a / b;
+}
+
+// the exponential of the contract: n = floor(x log2(e) + 0.5); r = (x - n ln2_hi) - n ln2_lo; Horner of degree 13 with 1 / k!; ldexp.
+// Within 1 ulp of a correctly rounded exp over the arguments the saturation pressure sees; NaN -> NaN, x < -700 -> 0, x > 700 -> +inf
+PAMA_D double exp_c(double x) {
+  PAMA_NO_CONTRACT
+  if (x != x) return x;
+  if (x < -700.0) return 0.0;
+  if (x > 700.0) return HUGE_VAL;
+  const double n = std::floor(x * 1.44269504088896338700 + 0.5);
+  const double r = (x - n * 6.93147180369123816490e-01) - n * 1.90821492927058770002e-10;
+  double p = 1.0 / 6227020800.0;
+  p = p * r + 1.0 / 479001600.0;
+  p = p * r + 1.0 / 39916800.0;
+  p = p * r + 1.0 / 3628800.0;
+  p = p * r + 1.0 / 362880.0;
+  p = p * r + 1.0 / 40320.0;
+  p = p * r + 1.0 / 5040.0;
+  p = p * r + 1.0 / 720.0;
+  p = p * r + 1.0 / 120.0;
+  p = p * r + 1.0 / 24.0;
+  p = p * r + 1.0 / 6.0;
+  p = p * r + 1.0 / 2.0;
+  p = p * r + 1.0;
+  p = p * r + 1.0;
+  return std::ldexp(p, (int)n);                        // |n| <= 1010: the result is a normal number, so the scaling is exact
+}
+
+// Lv(T) of liquid water, the reference's latent_heat_condensation, left to right as it is written there
+PAMA_D double latent_heat(double temp) {
+  PAMA_NO_CONTRACT
+  const double tc = temp - 273.15;
+  return (2500.8 - 2.36 * tc + 0.0016 * tc * tc - 0.00006 * tc * tc * tc) * 1000.0;
+}
+
+// qs = (es / (R_v temp)) / rho with es the reference's saturation_vapor_pressure over exp_c
+PAMA_D double saturation_ratio(double temp, double rho, double R_v) {
+  PAMA_NO_CONTRACT
+  const double tc = temp - 273.15;
+  const double x = (17.625 * tc) / (243.04 + tc);
+  const double es = 610.94 * exp_c(x);
+  const double a = es / (R_v * temp);
+  return a / rho;
+}
+
+// what the stability needs of one cell.  Dry: trho = Tv only.  Moist: trho = temp ((1 + 0.608 qv) - ql), ql the loading of every
+// condensate; qt = qv + ql; qs; sat = the cloud condensate exceeds threshold rho (strictly; never without a cloud table)
+struct Thermo {
+  double trho, temp, qs, qt;
+  bool sat;
+};
+
+template <bool MOIST>
+PAMA_D Thermo thermo(double temp, double rho_d, double rho_v, const double *const *cloud, const double *const *precip, long long o,
+                     const MoistParams &M) {
+  PAMA_NO_CONTRACT
+  Thermo c;
+  if constexpr (!MOIST) {
+    c.trho = virtual_temp(temp, rho_d, rho_v);
+    c.temp = 0.0; c.qs = 0.0; c.qt = 0.0; c.sat = false;
+  } else {
+    const double rho = rho_d + rho_v;
+    const double qv = rho_v / rho;
+    const double t = 0.608 * qv;
+    double f = 1.0 + t;
+    double cl = 0.0, load = 0.0;
+    if (M.num_cloud > 0) cl = cloud[0][o];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int q = 1; q < MAX_CLOUD; q++)
+      if (q < M.num_cloud) cl = cl + cloud[q][o];
+    load = M.num_cloud > 0 ? cl : (M.num_precip > 0 ? precip[0][o] : 0.0);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int q = 0; q < MAX_PRECIP; q++)
+      if (q < M.num_precip && (q > 0 || M.num_cloud > 0)) load = load + precip[q][o];
+    c.qt = qv;
+    if (M.num_cloud > 0 || M.num_precip > 0) {
+      const double ql = load / rho;
+      f = f - ql;
+      c.qt = qv + ql;
+    }
+    c.trho = temp * f;
+    c.temp = temp;
+    c.sat = false;
+    c.qs = 0.0;
+    if (M.num_cloud > 0) {                             // without a cloud table no cell is saturated and qs is never used
+      c.sat = cl > M.threshold * rho;
+      c.qs = saturation_ratio(temp, rho, M.R_v);
+    }
+  }
+  return c;
+}
+
+// the saturated frequency (Durran and Klemp 1982, eq. 36, in temperature form):
+//   N2 = grav ((a1 / a2) ((dT/dz + gc) / T + (Lv / (cp_d T)) dqs/dz) - dqt/dz),
+//   a1 = 1 + (Lv qs) / (R_d T), a2 = 1 + (((eps Lv) Lv) qs) / (((cp_d R_d) T) T)
+PAMA_D double stability_saturated(double grav, double gc, const MoistParams &M, double temp, double qs, double dtdz, double dqsdz, double dqtdz) {
+  PAMA_NO_CONTRACT
+  const double lv = latent_heat(temp);
+  const double a1 = 1.0 + (lv * qs) / (M.R_d * temp);
+  const double a2 = 1.0 + (((M.eps * lv) * lv) * qs) / (((M.cp_d * M.R_d) * temp) * temp);
+  const double b1 = (dtdz + gc) / temp;
+  const double b2 = (lv / (M.cp_d * temp)) * dqsdz;
+  const double b = b1 + b2;
+  const double m = (a1 / a2) * b;
+  return grav * (m - dqtdz);
+}
+
 PAMA_D int wrap_up(int i, int n) { return i + 1 == n ? 0 : i + 1; }
 PAMA_D int wrap_down(int i, int n) { return i == 0 ? n - 1 : i - 1; }
 
 // the eddy coefficients of one column (j, i) of member e, bottom to top.  f: uvel, vvel, wvel, temp, rho_d, rho_v, each pointing at
 // element 0; zint, zmid point at (0, e).  The centre values of levels k-1, k, k+1 ride along in registers; the horizontal neighbours of
 // level k are read from the fields.  tk and tkh overlap nothing that is read (the entry point refuses it)
-PAMA_D void coef_column(const double *const *f, const double *zint, const double *zmid, long long level, int nens, int nx, int ny, int nz, int j,
-                        int i, int e, const CoefParams &P, double *__restrict__ tk, double *__restrict__ tkh) {
+// MOIST: cloud[M.num_cloud] and precip[M.num_precip] point at element 0 of the condensate densities, and a saturated level k takes
+// stability_saturated; without it the two tables and M are never read
+template <bool MOIST>
+PAMA_D void coef_column_t(const double *const *f, const double *const *cloud, const double *const *precip, const MoistParams &M, const double *zint,
+                          const double *zmid, long long level, int nens, int nx, int ny, int nz, int j, int i, int e, const CoefParams &P,
+                          double *__restrict__ tk, double *__restrict__ tkh) {
   const bool with_y = ny > 1;
   const long long row = (long long)j * nx;
   const long long c0 = (row + i) * nens + e;
   const long long xp = (row + wrap_up(i, nx)) * nens + e, xm = (row + wrap_down(i, nx)) * nens + e;
   const long long yp = ((long long)wrap_up(j, ny) * nx + i) * nens + e, ym = ((long long)wrap_down(j, ny) * nx + i) * nens + e;
   const double *u = f[0], *v = f[1], *w = f[2], *T = f[3], *rd = f[4], *rv = f[5];
-  double u_k = u[c0], v_k = v[c0], w_k = w[c0], tv_k = virtual_temp(T[c0], rd[c0], rv[c0]), zm_k = zmid[0];
-  double u_m = u_k, v_m = v_k, w_m = w_k, tv_m = tv_k, zm_m = zm_k;      // the one-sided difference at the ground
+  double u_k = u[c0], v_k = v[c0], w_k = w[c0];
+  Thermo a_k = thermo<MOIST>(T[c0], rd[c0], rv[c0], cloud, precip, c0, M);
+  double zm_k = zmid[0];
+  double u_m = u_k, v_m = v_k, w_m = w_k, zm_m = zm_k;      // the one-sided difference at the ground
+  Thermo a_m = a_k;
   double zi_k = zint[0];
   for (int k = 0; k < nz; k++) {
     const int ku = k + 1 < nz ? k + 1 : k;                               // the one-sided difference at the top
     const long long lu = (long long)ku * level + c0, lk = (long long)k * level;
-    const double u_p = u[lu], v_p = v[lu], w_p = w[lu], tv_p = virtual_temp(T[lu], rd[lu], rv[lu]), zm_p = zmid[(long long)ku * nens];
+    const double u_p = u[lu], v_p = v[lu], w_p = w[lu];
+    const Thermo a_p = thermo<MOIST>(T[lu], rd[lu], rv[lu], cloud, precip, lu, M);
+    const double zm_p = zmid[(long long)ku * nens];
     const double zi_p = zint[(long long)(k + 1) * nens];
     const double span = zm_p - zm_m;
     const double uz = centred(u_p, u_m, span), vz = centred(v_p, v_m, span), wz = centred(w_p, w_m, span);
@@ -118,15 +253,27 @@ PAMA_D void coef_column(const double *const *f, const double *zint, const double
       wy = centred(w[lk + yp], w[lk + ym], P.two_dy);
     }
     const double def2 = deformation(with_y, ux, uy, uz, vx, vy, vz, wx, wy, wz);
-    const double n2 = stability(P.grav, P.gc, tv_k, centred(tv_p, tv_m, span));
+    double n2 = stability(P.grav, P.gc, a_k.trho, centred(a_p.trho, a_m.trho, span));
+    if constexpr (MOIST) {
+      if (a_k.sat)                                                         // level k alone decides, not its neighbours
+        n2 = stability_saturated(P.grav, P.gc, M, a_k.temp, a_k.qs, centred(a_p.temp, a_m.temp, span), centred(a_p.qs, a_m.qs, span),
+                                 centred(a_p.qt, a_m.qt, span));
+    }
     double a, b;
     eddy(def2, n2, zi_p - zi_k, P.cs, P.prandtl, a, b);
     tk[lk + c0] = a;
     tkh[lk + c0] = b;
-    u_m = u_k; v_m = v_k; w_m = w_k; tv_m = tv_k; zm_m = zm_k;
-    u_k = u_p; v_k = v_p; w_k = w_p; tv_k = tv_p; zm_k = zm_p;
+    u_m = u_k; v_m = v_k; w_m = w_k; a_m = a_k; zm_m = zm_k;
+    u_k = u_p; v_k = v_p; w_k = w_p; a_k = a_p; zm_k = zm_p;
     zi_k = zi_p;
   }
+}
+
+// the dry instance, as pam_amd_sgs_smag_coefficients runs it
+PAMA_D void coef_column(const double *const *f, const double *zint, const double *zmid, long long level, int nens, int nx, int ny, int nz, int j,
+                        int i, int e, const CoefParams &P, double *__restrict__ tk, double *__restrict__ tkh) {
+  const MoistParams none{};
+  coef_column_t<false>(f, nullptr, nullptr, none, zint, zmid, level, nens, nx, ny, nz, j, i, e, P, tk, tkh);
 }
 
 // g at the face between levels k and k+1: dt rho_f K_f / dzf with rho_f and K_f the means of the two levels, left to right
@@ -139,6 +286,17 @@ PAMA_D double face_g(double dt, double rho_k, double rho_p, double K_k, double K
   return b / dzf;
 }
 
+// the flux as the row takes it: kinematic as given, or (FLUX) scaled by the class
+template <bool FLUX>
+PAMA_D double surface_term(int cls, double flux, double scale, double rho0) {
+  PAMA_NO_CONTRACT
+  if constexpr (FLUX) {
+    if (cls == C_HEAT) return flux / (scale * rho0);
+    if (cls == C_TRACER) return flux / scale;
+  }
+  return flux;
+}
+
 // backward Euler of one class over one (column, member): nf fields, IN PLACE, by the Thomas algorithm (ascending elimination, descending
 // substitution, no pivoting).  Row k: -lower x(k-1) + diag x(k) - upper x(k+1) = r, lower(0) = upper(nz-1) = 0.0.
 //   den = diag - lower c'(k-1); c'(k) = upper / den; d'(k) = (r + lower d'(k-1)) / den, c'(-1) = d'(-1) = 0.0;
@@ -148,9 +306,12 @@ PAMA_D double face_g(double dt, double rho_k, double rho_p, double K_k, double K
 // rho is read one level ahead of the level being written and carried in registers, so a field of the table may be rho_v itself: every
 // rho_v(k) is read before d'(k) takes its place.  The loads of AHEAD levels are requested before the first of them is used; the first
 // NREG fields keep d'(k-1) and x(k+1) in registers, a longer table reads them back from the field
-PAMA_D void solve_class(int cls, double *const *f, int nf, const double *const *sfc, long long off, const double *rd, const double *rv,
-                        const double *K, const double *zint, const double *zmid, long long level, long long zs, int nz, double dt, double gc,
-                        double *cp, long long cs) {
+// FLUX: the surface flux of the heat class is a heat flux in W/m2, r += (dt (sfc / (scale rho(0)))) / dz(0) with scale = cp_d, and that
+// of the tracer class a mass flux of latent heat, r += (dt (sfc / scale)) / dz(0) with scale = the latent heat; momentum is as without
+template <bool FLUX>
+PAMA_D void solve_class_t(int cls, double *const *f, int nf, const double *const *sfc, long long off, const double *rd, const double *rv,
+                          const double *K, const double *zint, const double *zmid, long long level, long long zs, int nz, double dt, double gc,
+                          double *cp, long long cs, double scale) {
   PAMA_NO_CONTRACT
   double prev[NREG];
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -214,7 +375,7 @@ PAMA_D void solve_class(int cls, double *const *f, int nf, const double *const *
         if (t < nf) {
           double r = a_f[b][t];
           if (cls == C_HEAT) r = r + heat;
-          if (first && sfc && sfc[t]) r = r + (dt * sfc[t][off]) / dz;
+          if (first && sfc && sfc[t]) r = r + (dt * surface_term<FLUX>(cls, sfc[t][off], scale, rho_k)) / dz;
           const double d = (r + lower * prev[t]) / den;
           f[t][o] = d;
           prev[t] = d;
@@ -222,7 +383,7 @@ PAMA_D void solve_class(int cls, double *const *f, int nf, const double *const *
       for (int t = NREG; t < nf; t++) {
         double r = f[t][o];
         if (cls == C_HEAT) r = r + heat;
-        if (first && sfc && sfc[t]) r = r + (dt * sfc[t][off]) / dz;
+        if (first && sfc && sfc[t]) r = r + (dt * surface_term<FLUX>(cls, sfc[t][off], scale, rho_k)) / dz;
         const double p = first ? 0.0 : f[t][o - level];
         f[t][o] = (r + lower * p) / den;
       }
@@ -263,6 +424,13 @@ PAMA_D void solve_class(int cls, double *const *f, int nf, const double *const *
       for (int t = NREG; t < nf; t++) f[t][o] = f[t][o] + a_c[b] * f[t][o + level];
     }
   }
+}
+
+// the instance without fluxes of heat and vapour, as pam_amd_sgs_smag_diffuse runs it
+PAMA_D void solve_class(int cls, double *const *f, int nf, const double *const *sfc, long long off, const double *rd, const double *rv,
+                        const double *K, const double *zint, const double *zmid, long long level, long long zs, int nz, double dt, double gc,
+                        double *cp, long long cs) {
+  solve_class_t<false>(cls, f, nf, sfc, off, rd, rv, K, zint, zmid, level, zs, nz, dt, gc, cp, cs, 0.0);
 }
 
 }  // namespace sgs

@@ -120,13 +120,21 @@ class SGSSmagorinsky:
     """physics/sgs/smag_amd/SGS.h: the native first-order Smagorinsky-Lilly closure with an implicit vertical solve.  Not part of the
     reference tree; the contract is this project's (include/pam_amd_modules.h).  timeStep fills "tk" and "tkh"
     and mixes uvel, vvel, wvel, temp and every registered tracer along the column, with "sfc_mom_flx_u/v" (compute_surface_friction
-    fills them) as the lower boundary condition of the horizontal winds.  density_dry is never written."""
+    fills them) as the lower boundary condition of the horizontal winds.  density_dry is never written.
+    moist: the stability carries the loading of every condensate and is the saturated one inside cloud (the species by option "micro";
+    options "R_d" and "R_v" are read).  surface_fluxes: "sfc_shf" and "sfc_lhf" (W/m2, positive upward; whoever drives the run fills them)
+    enter row 0 of temp and of the vapour, with option "latvap" where it exists.  With both off the two dry entry points are called."""
     FIELDS = (("tk", 4), ("tkh", 4), ("sfc_mom_flx_u", 3), ("sfc_mom_flx_v", 3))
-    OPTIONS = ("sgs", "sgs_smag_cs", "sgs_smag_prandtl")
+    FLUX_FIELDS = (("sfc_shf", "input surface sensible heat flux [W/m2]"), ("sfc_lhf", "input surface latent heat flux [W/m2]"))
+    OPTIONS = ("sgs", "sgs_smag_cs", "sgs_smag_prandtl", "sgs_smag_moist", "sgs_smag_surface_fluxes", "sgs_smag_cloud_threshold")
     OPTIONS_READ = ("crm_dt", "grav", "cp_d", "sgs_smag_cs", "sgs_smag_prandtl")
+    # option "micro" -> the cloud condensate and the precipitating species of the moist branch
+    CONDENSATE = {"kessler": (("cloud_liquid",), ("precip_liquid",)), "p3": (("cloud_water", "ice"), ("rain",)), "none": ((), ())}
+    LATVAP = 2501000.0          # where the option "latvap" is absent
 
-    def __init__(self, cs=0.2, prandtl=1.0 / 3.0):
+    def __init__(self, cs=0.2, prandtl=1.0 / 3.0, moist=False, surface_fluxes=False, cloud_threshold=0.0):
         self.cs, self.prandtl = float(cs), float(prandtl)
+        self.moist, self.surface_fluxes, self.cloud_threshold = bool(moist), bool(surface_fluxes), float(cloud_threshold)
 
     @staticmethod
     def get_num_tracers():
@@ -138,7 +146,8 @@ class SGSSmagorinsky:
 
     def init(self, coupler):
         """registers "tk", "tkh" and "sfc_mom_flx_u/v" where absent, zero-filled; option "sgs" = "smagorinsky"; the options sgs_smag_cs
-        and sgs_smag_prandtl unless present"""
+        sgs_smag_prandtl, sgs_smag_moist, sgs_smag_surface_fluxes and sgs_smag_cloud_threshold unless present; with surface fluxes
+        "sfc_shf" and "sfc_lhf" where absent, zero-filled, under the reference's names and descriptions"""
         nens, nz, ny, nx = coupler.get_nens(), coupler.get_nz(), coupler.get_ny(), coupler.get_nx()
         if min(nens, nz, ny, nx) < 1:
             endrun("ERROR: sgs: the coupler state is not allocated")
@@ -154,12 +163,23 @@ class SGSSmagorinsky:
             coupler.set_option("sgs_smag_cs", self.cs)
         if not coupler.option_exists("sgs_smag_prandtl"):
             coupler.set_option("sgs_smag_prandtl", self.prandtl)
+        if not coupler.option_exists("sgs_smag_moist"):
+            coupler.set_option("sgs_smag_moist", self.moist)
+        if not coupler.option_exists("sgs_smag_surface_fluxes"):
+            coupler.set_option("sgs_smag_surface_fluxes", self.surface_fluxes)
+        if not coupler.option_exists("sgs_smag_cloud_threshold"):
+            coupler.set_option("sgs_smag_cloud_threshold", self.cloud_threshold)
+        if coupler.get_option("sgs_smag_surface_fluxes"):
+            for name, desc in self.FLUX_FIELDS:
+                if not dm.entry_exists(name):
+                    dm.register_and_allocate(name, desc, (ny, nx, nens), ("y", "x", "nens"))
 
     def timeStep(self, coupler):
         """the coefficient launch, then the solve, on the current stream"""
         lib = capi.load()
         nens, nz, ny, nx = coupler.get_nens(), coupler.get_nz(), coupler.get_ny(), coupler.get_nx()
         dt, grav, cp_d, cs, prandtl = (float(coupler.get_option(n)) for n in self.OPTIONS_READ)
+        moist, fluxes = bool(coupler.get_option("sgs_smag_moist")), bool(coupler.get_option("sgs_smag_surface_fluxes"))
         dm = coupler.get_data_manager_device_readwrite()
         u, v, w, temp, tk, tkh = (dm.get(n) for n in ("uvel", "vvel", "wvel", "temp", "tk", "tkh"))
         rho_d, rho_v = dm.get("density_dry", readonly=True), dm.get("water_vapor", readonly=True)
@@ -169,13 +189,35 @@ class SGSSmagorinsky:
         table = (C.c_void_p * max(len(tracers), 1))(*[t.data_ptr() for t in tracers])
         with torch.cuda.device(coupler.device):
             stream = torch.cuda.current_stream(coupler.device).cuda_stream
-            check(lib.pam_amd_sgs_smag_coefficients(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(),
-                                                    rho_d.data_ptr(), rho_v.data_ptr(), zint.data_ptr(), zmid.data_ptr(),
-                                                    float(coupler.get_dx()), float(coupler.get_dy()), grav, cp_d, cs, prandtl,
-                                                    tk.data_ptr(), tkh.data_ptr(), stream))
-            check(lib.pam_amd_sgs_smag_diffuse(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(), len(tracers),
-                                               table, rho_d.data_ptr(), rho_v.data_ptr(), tk.data_ptr(), tkh.data_ptr(), zint.data_ptr(),
-                                               zmid.data_ptr(), flx_u.data_ptr(), flx_v.data_ptr(), dt, grav, cp_d, stream))
+            if moist:
+                micro = coupler.get_option("micro") if coupler.option_exists("micro") else "none"
+                if micro not in self.CONDENSATE:
+                    endrun("ERROR: sgs: the moist branch knows the species of micro = kessler, p3 and none, not of " + str(micro))
+                cloud, precip = ([dm.get(n, readonly=True) for n in names] for names in self.CONDENSATE[micro])
+                ctab = (C.c_void_p * 4)(*[t.data_ptr() for t in cloud])
+                ptab = (C.c_void_p * 8)(*[t.data_ptr() for t in precip])
+                check(lib.pam_amd_sgs_smag_coefficients_moist(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(),
+                                                              rho_d.data_ptr(), rho_v.data_ptr(), len(cloud), ctab, len(precip), ptab,
+                                                              zint.data_ptr(), zmid.data_ptr(), float(coupler.get_dx()), float(coupler.get_dy()),
+                                                              grav, cp_d, float(coupler.get_option("R_d")), float(coupler.get_option("R_v")),
+                                                              float(coupler.get_option("sgs_smag_cloud_threshold")), cs, prandtl,
+                                                              tk.data_ptr(), tkh.data_ptr(), stream))
+            else:
+                check(lib.pam_amd_sgs_smag_coefficients(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(),
+                                                        rho_d.data_ptr(), rho_v.data_ptr(), zint.data_ptr(), zmid.data_ptr(),
+                                                        float(coupler.get_dx()), float(coupler.get_dy()), grav, cp_d, cs, prandtl,
+                                                        tk.data_ptr(), tkh.data_ptr(), stream))
+            if fluxes:
+                shf, lhf = dm.get("sfc_shf", readonly=True), dm.get("sfc_lhf", readonly=True)
+                latvap = float(coupler.get_option("latvap")) if coupler.option_exists("latvap") else self.LATVAP
+                check(lib.pam_amd_sgs_smag_diffuse_fluxes(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(),
+                                                          len(tracers), table, rho_d.data_ptr(), rho_v.data_ptr(), tk.data_ptr(), tkh.data_ptr(),
+                                                          zint.data_ptr(), zmid.data_ptr(), flx_u.data_ptr(), flx_v.data_ptr(), dt, grav, cp_d,
+                                                          shf.data_ptr(), lhf.data_ptr(), latvap, stream))
+            else:
+                check(lib.pam_amd_sgs_smag_diffuse(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(), len(tracers),
+                                                   table, rho_d.data_ptr(), rho_v.data_ptr(), tk.data_ptr(), tkh.data_ptr(), zint.data_ptr(),
+                                                   zmid.data_ptr(), flx_u.data_ptr(), flx_v.data_ptr(), dt, grav, cp_d, stream))
 
     def finalize(self, coupler):
         pass

@@ -18,8 +18,9 @@ and the CRM feedback, beside msa_diagnose, time_average_accumulate and radiation
 radiation aggregate at the 1x1 rad grid and msa_diagnose of the same run;
 --only fluxprof: the CRM flux profiles on P3's field set at the C2 grid and at C4's 32x1x60 grid with 8192 members, beside vt_diagnose
 and msa_diagnose of the same run;
---only sgs: the native Smagorinsky SGS closure's coefficient launch and its solve (c' in LDS and in the workspace) on Kessler's field set
-at the C2 grid and at C4's 32x1x60 grid with 8192 members, beside hyperdiffusion and msa_apply of the same run;
+--only sgs: the native Smagorinsky SGS closure's coefficient launch (dry and moist) and its solve (c' in LDS and in the workspace, and
+with the surface fluxes of heat and vapour) on Kessler's field set at the C2 grid and at C4's 32x1x60 grid with 8192 members, beside
+hyperdiffusion and msa_apply of the same run;
 --only msa: mean-state acceleration's diagnose, tendencies and apply (with and without the winds), beside horizontal_average and
 time_average_accumulate of the same run)"""
 import json
@@ -1285,8 +1286,29 @@ def sgs_timing(dev, warmup=3, n=11):
                                                     P("vertical_midpoint_height"), P("sfc_mom_flx_u"), P("sfc_mom_flx_v"), 2.0, 9.80616, 1004.64,
                                                     stream))
 
+        ctab, ptab = (C.c_void_p * 4)(P("cloud_liquid")), (C.c_void_p * 8)(P("precip_liquid"))
+        shf = torch.full((ny, nx, nens), 50.0, dtype=torch.float64, device=dev)
+        lhf = torch.full((ny, nx, nens), 200.0, dtype=torch.float64, device=dev)
+
+        def coef_moist():
+            capi.check(lib.pam_amd_sgs_smag_coefficients_moist(nens, nx, ny, nz, P("uvel"), P("vvel"), P("wvel"), P("temp"), P("density_dry"),
+                                                               P("water_vapor"), 1, ctab, 1, ptab, P("vertical_interface_height"),
+                                                               P("vertical_midpoint_height"), 1000.0, 1000.0, 9.80616, 1004.64, 287.042, 461.505,
+                                                               0.0, 0.2, 1.0 / 3.0, P("tk"), P("tkh"), stream))
+
+        def solve_fluxes():
+            capi.check(lib.pam_amd_sgs_smag_diffuse_fluxes(nens, nx, ny, nz, P("uvel"), P("vvel"), P("wvel"), P("temp"), len(tr), table,
+                                                           P("density_dry"), P("water_vapor"), P("tk"), P("tkh"), P("vertical_interface_height"),
+                                                           P("vertical_midpoint_height"), P("sfc_mom_flx_u"), P("sfc_mom_flx_v"), 2.0, 9.80616,
+                                                           1004.64, shf.data_ptr(), lhf.data_ptr(), 2501000.0, stream))
+
         out["sgs_coefficients" + label] = row(timed(coef), cells * 64.0)
         assert bool(torch.isfinite(dm.get("tk", readonly=True)).all()) and float(dm.get("tk", readonly=True).max()) > 0
+        # the moist launch: 8 B per cell and input field (the six above, one cloud and one precip species) plus 16 B per cell written.
+        # Every cell of this state is cloudy, so every lane takes the saturated branch: its dearer side
+        out["sgs_coefficients_moist" + label] = row(timed(coef_moist), cells * (8 * 8.0 + 16.0))
+        assert bool(torch.isfinite(dm.get("tk", readonly=True)).all())
+        coef()                                               # the solves below run on the dry coefficients, as before
         nbytes = cells * (7 * 16.0 + 3 * 24.0)
         for path, name in ((0, "automatic"), (1, "lds"), (2, "workspace")):
             capi.check(lib.pam_amd_sgs_smag_debug_path(path))
@@ -1294,6 +1316,7 @@ def sgs_timing(dev, warmup=3, n=11):
                 out["sgs_diffuse_%s%s" % (name, label)] = row(timed(solve), nbytes)
             finally:
                 capi.check(lib.pam_amd_sgs_smag_debug_path(0))
+        out["sgs_diffuse_fluxes" + label] = row(timed(solve_fluxes), nbytes + 2 * 8.0 * nens * nx * ny)      # the automatic path, two fluxes more
         assert all(bool(torch.isfinite(dm.get(t, readonly=True)).all()) for t in ["uvel", "vvel", "wvel", "temp"] + tr)
         out["sgs_time_step_ms" + label] = out["sgs_coefficients" + label]["ms"] + out["sgs_diffuse_automatic" + label]["ms"]
         if beside:
