@@ -10,6 +10,7 @@ import copy
 import numpy as np
 
 from pam_amd import idealized as idz
+from parity_cases import build_inputs
 
 NENS = 2            # member lanes need two members; flat lanes run on the same fields
 DT = 0.5            # one sub-step: crm_dt == dt_dyn
@@ -27,6 +28,11 @@ GRIDS = {
     (5, 1, 8): [(1, 1, 1), (4, 0, 0), (1, 0, 1), (4, 1, 0)],
 }
 PHYSICS = [(g, v) for g in GRIDS for v in GRIDS[g]]
+# dx != dy with the sounding's shear along y (a third element: options of parity_cases.build_inputs).  The golden file has none of
+# these: tests/test_flux_unused_polys.py holds their plain schedule to the oracle and every other schedule to the plain one's bits.
+ANISO_PHYSICS = [((5, 7, 9), (4, 1, 1), dict(dxy=500.0, dy=800.0, flow="y")),
+                 ((6, 5, 8), (1, 1, 0), dict(dxy=800.0, dy=500.0, flow="y")),
+                 ((5, 6, 10), (4, 0, 0), dict(dxy=1000.0, dy=250.0, flow="y"))]
 # (lanes, z spans, fold, fused)
 SCHEDULES = [(lanes, spans, fold, fused) for fused in (True, False) for lanes in ("member", "flat") for spans in (1, 2) for fold in (False, True)
              if not (fold and (lanes == "flat" or not fused)) and not (lanes == "flat" and not fused)]
@@ -35,8 +41,9 @@ FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "tracers")
 
 
 def physics_id(p):
-    (nx, ny, nz), (nt, carve, perens) = p
-    return "%dx%dx%d_nt%d%s%s" % (nx, ny, nz, nt, "_carved" if carve else "", "_perens" if perens else "")
+    (nx, ny, nz), (nt, carve, perens) = p[:2]
+    return "%dx%dx%d_nt%d%s%s" % (nx, ny, nz, nt, "_carved" if carve else "", "_perens" if perens else "") + (
+        "_dx%g_dy%g_flow%s" % (p[2]["dxy"], p[2]["dy"], p[2]["flow"]) if len(p) > 2 else "")
 
 
 def schedule_id(s):
@@ -45,19 +52,16 @@ def schedule_id(s):
 
 
 def applies(p, s):
-    (nx, ny, nz), _ = p
+    (nx, ny, nz) = p[0]
     return not (s[2] and ny == 1)          # nothing to fold on a 2-D grid
 
 
 def make_fields(p):
-    (nx, ny, nz), (nt, carve, perens) = p
+    (nx, ny, nz), (nt, carve, perens) = p[:2]
     tr = idz.TRACERS_NONE if nt == 1 else idz.TRACERS_KESSLER_SHOC
     assert len(tr) == nt
     zint = idz.stretched_interfaces(nz, 12000.0)
-    xlen = nx * 500.0
-    ylen = ny * 500.0 if ny > 1 else xlen
-    f = idz.supercell_fields(NENS, nx, ny, nz, zint, tracers=tr, magnitude=0.5)
-    idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
+    f, xlen, ylen, _, _ = build_inputs(NENS, nx, ny, nz, tr, zint, mag=0.5, **(p[2] if len(p) > 2 else {}))
     # wind through every face, vertical motion next to both walls, and members that differ
     k, j, i, e = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), np.arange(NENS), indexing="ij")
     f["uvel"] = f["uvel"] - 25.0 + 3.0 * np.sin(1.3 * i + 0.7 * k + e)
@@ -73,7 +77,7 @@ def make_fields(p):
 
 def written(p, name, fused):
     """mask of the entries of a flux array that the stage writes (the rest keeps what the buffer held before)"""
-    (nx, ny, nz), (nt, _, _) = p
+    (nx, ny, nz), (nt, _, _) = p[:2]
     if name == "flux_y":
         m = np.ones((5 + nt, nz, ny, nx, NENS), dtype=bool)
     else:
@@ -87,7 +91,7 @@ def written(p, name, fused):
 
 def run(emu_harness, p, s):
     """one sub-step of schedule s on physics case p -> {name: 1-D array of the written entries}"""
-    (nx, ny, nz), (nt, carve, perens) = p
+    (nx, ny, nz), (nt, carve, perens) = p[:2]
     lanes, spans, fold, fused = s
     f, tr, zi, xlen, ylen = make_fields(p)
     f = copy.deepcopy(f)

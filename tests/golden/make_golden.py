@@ -20,9 +20,12 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+if os.path.dirname(HERE) not in sys.path:
+    sys.path.insert(0, os.path.dirname(HERE))      # tests/: the shared input builder
 
 from oracle import awfl_oracle as ao          # noqa: E402
 from pam_amd import idealized as idz          # noqa: E402
+from parity_cases import build_inputs         # noqa: E402
 
 SURVEY_KAT = {
     "source": "SURVEY.md Appendix B (reference headers, serial run during the survey)",
@@ -44,6 +47,15 @@ CASES = {
                                     mode_a=False, nsteps=2, crm_dt=2.0, consts="default", per_ens=False),
     "case_3d_nt10_perens_A_p3": dict(nens=3, nx=6, ny=4, nz=8, tr="p3_shoc", grid=("stretched", 12000.0), mode_a=True,
                                      nsteps=2, crm_dt=2.0, consts="p3", per_ens=True),
+    # dx != dy in both orders of the ratio and a strong one, nx != ny, the sounding's shear along y or along both
+    # (optional keys dxy, dy, flow, dry_air: tests/parity_cases.py build_inputs)
+    "case_3d_aniso_500x800_nt1_A_flowy": dict(nens=2, nx=6, ny=5, nz=8, tr="none", grid=("stretched", 12000.0), mode_a=True,
+                                              nsteps=2, crm_dt=2.0, consts="default", per_ens=False, dxy=500.0, dy=800.0, flow="y"),
+    "case_3d_aniso_800x500_nt4_B_flowy": dict(nens=2, nx=5, ny=7, nz=8, tr="kessler_shoc", grid=("stretched", 12000.0), mode_a=False,
+                                              nsteps=2, crm_dt=2.0, consts="default", per_ens=False, dxy=800.0, dy=500.0, flow="y"),
+    "case_3d_aniso_1000x250_nt1_limited_A_diag": dict(nens=4, nx=7, ny=5, nz=8, tr="none", grid=("stretched", 12000.0), mode_a=True,
+                                                      nsteps=2, crm_dt=2.0, consts="default", per_ens=False, dxy=1000.0, dy=250.0,
+                                                      flow="diag", dry_air=True),
 }
 TRACERS = {"none": idz.TRACERS_NONE, "kessler_shoc": idz.TRACERS_KESSLER_SHOC, "p3_shoc": idz.TRACERS_P3_SHOC}
 CONSTS = {"default": idz.CONSTS_DEFAULT, "p3": idz.CONSTS_P3}
@@ -54,13 +66,9 @@ def build_case(c):
     tr, consts = TRACERS[c["tr"]], CONSTS[c["consts"]]
     nens, nx, ny, nz = c["nens"], c["nx"], c["ny"], c["nz"]
     zint = idz.uniform_interfaces(nz, c["grid"][1]) if c["grid"][0] == "uniform" else idz.stretched_interfaces(nz, c["grid"][1])
-    xlen = nx * 500.0
-    ylen = ny * 500.0 if ny > 1 else xlen
-    f = idz.supercell_fields(nens, nx, ny, nz, zint, consts=consts, tracers=tr, magnitude=0.5)
-    idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
-    zi = np.asarray(zint)[:, None] * np.ones((1, nens))
-    if c["per_ens"]:
-        zi = zi * (1 + 0.01 * np.arange(nens))[None, :]
+    f, xlen, ylen, zi, _ = build_inputs(nens, nx, ny, nz, tr, zint, consts=consts, per_ens=c["per_ens"], mag=0.5,
+                                        dxy=c.get("dxy", 500.0), dy=c.get("dy"), flow=c.get("flow", "x"),
+                                        dry_air=c.get("dry_air", False))
     return tr, consts, zi, xlen, ylen, f
 
 

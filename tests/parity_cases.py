@@ -50,20 +50,98 @@ CASES = {
                             [("water_vapor", True, True)] + [("u%02d" % i, i % 2 == 0, False) for i in range(29)],
                             idz.stretched_interfaces(6, 9000.0), {}, True, 1),
 }
+# every case above has dx == dy, and apart from the noise and the 7 m/s of the dry_air cases no flow along y
+# (tests/test_anisotropy_census.py keeps the record).  The cases below have dx != dy in both orders of the ratio, nx != ny, and the
+# sounding's shear along y or along both: one per kernel family, at the smallest shape that selects it.
+ISOTROPIC_CASES = tuple(sorted(CASES))
+_Z8 = idz.stretched_interfaces(8, 12000.0)
+CASES.update({
+    # flat lanes + tile kernels: 2 x 8 x 5 (a row of 8 cells x 2 members: the shuffle exchange is possible) and 5 x 6 x 7 (LDS exchange)
+    "aniso_500x800_flat_2x8x5_nt1_A_flowy": (2, 8, 5, 8, idz.TRACERS_NONE, _Z8, dict(dxy=500.0, dy=800.0, flow="y"), True, 2),
+    "aniso_800x500_flat_2x8x5_nt4_B_diag": (2, 8, 5, 8, idz.TRACERS_KESSLER_SHOC, _Z8, dict(dxy=800.0, dy=500.0, flow="diag"), False, 2),
+    "aniso_1000x250_flat_5x6x7_nt1_B_flowy": (5, 6, 7, 8, idz.TRACERS_NONE, _Z8, dict(dxy=1000.0, dy=250.0, flow="y"), False, 2),
+    "aniso_500x800_flat_5x6x7_nt4_A_diag": (5, 6, 7, 8, idz.TRACERS_KESSLER_SHOC, _Z8, dict(dxy=500.0, dy=800.0, flow="diag"), True, 2),
+    # member lanes, a whole block and a ragged one, the limiter acting on vapour across the dry rows in y: NT = 1 (tail fusion), NT = 4
+    "aniso_800x500_nens64_nt1_vapour_limited_flowy": (64, 6, 5, 8, idz.TRACERS_NONE, _Z8,
+                                                      dict(dxy=800.0, dy=500.0, flow="y", dry_air=True), True, 2),
+    "aniso_500x800_nens70_ragged_nt4_vapour_limited_flowy_B": (70, 5, 7, 8, idz.TRACERS_KESSLER_SHOC, _Z8,
+                                                               dict(dxy=500.0, dy=800.0, flow="y", dry_air=True), False, 2),
+    # per-member vertical grids with member lanes
+    "aniso_500x800_perens_nens64_nt4_diag": (64, 6, 5, 8, idz.TRACERS_KESSLER_SHOC, _Z8,
+                                             dict(dxy=500.0, dy=800.0, flow="diag", per_ens="mod16"), True, 2),
+    # NT = 10
+    "aniso_800x500_nt10_p3_flowy": (3, 6, 5, 8, idz.TRACERS_P3_SHOC, _Z8,
+                                    dict(dxy=800.0, dy=500.0, flow="y", consts=idz.CONSTS_P3), True, 2),
+})
+ANISOTROPIC_CASES = tuple(sorted(set(CASES) - set(ISOTROPIC_CASES)))
 FLOOR_SEED = 0             # the seed of the named cases' twins
 
 
-def build_inputs(nens, nx, ny, nz, tr, zint, consts=idz.CONSTS_DEFAULT, supercell=True, per_ens=False, mag=0.5, dxy=500.0,
-                 dry_air=False):
-    """the seeded input fields of a case and its grid: (fields, xlen, ylen, interfaces (nz+1, nens), dz (nz, nens))"""
-    xlen = nx * dxy
-    ylen = ny * dxy if ny > 1 else xlen
-    if supercell:
-        f = idz.supercell_fields(nens, nx, ny, nz, zint, consts=consts, tracers=tr, magnitude=mag)
-        idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
-        if dry_air:      # exact zeros in the vapour beside moist air + a mean wind across the edges: the limiter acts on water_vapor
+FLOWS = ("x", "y", "diag")
+
+
+def _turn_wind(f, flow, dry_air, ny):
+    """the sounding's shear (u(z), v = 0: idealized.supercell_column) along x (today's inputs), along y, or along both at once with
+    different values and signs; with dry_air, the mean wind that carries the vapour across the carved edges"""
+    su = f["uvel"].copy()
+    if flow == "y":          # the shear along y, a fifth of it left along x
+        f["vvel"] = su
+        f["uvel"] = 0.2 * su
+    elif flow == "diag":     # u in [-9, 15], v in [-14, 4] m/s
+        f["uvel"] = 0.8 * su + 3.0
+        f["vvel"] = -0.6 * su - 5.0
+    elif flow != "x":
+        raise ValueError("flow must be one of %s" % (FLOWS,))
+    if dry_air:
+        if flow == "x":
             f["uvel"] -= 25.0
             f["vvel"] += 7.0 if ny > 1 else 0.0
+        elif flow == "y":    # the x case turned: 25 m/s across the dry rows in y, 7 m/s across the slabs in x
+            f["vvel"] -= 25.0
+            f["uvel"] += 7.0
+        else:                # as strong along y as along x
+            f["uvel"] -= 20.0
+            f["vvel"] += 20.0
+
+
+def _add_turned_tracer_blobs(f, tracers, xlen, ylen, zint, rel=1.0e-3):
+    """idealized.add_tracer_blobs turned into y: the blob centres spread along y (off the y centre line, where that one puts every
+    blob) at one x off the x centre line, and the two horizontal half-widths swapped.  No half-width is less than 0.75 cells (of the thickest
+    level, in z), so that at any dx/dy and on the coarsest grids every blob still holds a cell centre."""
+    nt, nz, ny, nx, nens = f["tracers"].shape
+    zmid = 0.5 * (zint[:-1] + zint[1:])
+    dx, dy = xlen / nx, ylen / ny
+    Z, Y, X = np.meshgrid(zmid, (np.arange(ny) + 0.5) * dy, (np.arange(nx) + 0.5) * dx, indexing="ij")
+    ztop = zint[-1]
+    rho = f["density_dry"]
+    for t, (name, _, _) in enumerate(tracers):
+        if name == "water_vapor":
+            continue
+        y0 = ylen * (0.2 + 0.6 * ((t * 0.37) % 1.0))
+        z0 = ztop * (0.05 + 0.25 * ((t * 0.61) % 1.0))
+        blob = idz.sample_ellipse_cosine(1.0, X, Y, Z, xlen * 0.35, y0, z0, max(ylen * 0.15, 0.75 * dx), max(xlen * 0.15, 0.75 * dy),
+                                         max(ztop * 0.06, 0.75 * np.diff(zint).max()))
+        if name == "tke":
+            f["tracers"][t] = rho * (0.1 * blob[..., None] + 0.0)
+        else:
+            f["tracers"][t] = rho * (rel * (1.0 + 0.1 * t)) * blob[..., None] * (1.0 + 0.01 * np.arange(nens))
+    return f
+
+
+def build_inputs(nens, nx, ny, nz, tr, zint, consts=idz.CONSTS_DEFAULT, supercell=True, per_ens=False, mag=0.5, dxy=500.0,
+                 dry_air=False, dy=None, flow="x", id0=0):
+    """the seeded input fields of a case and its grid: (fields, xlen, ylen, interfaces (nz+1, nens), dz (nz, nens)).  `dxy` is the
+    spacing in x and, unless `dy` is given, in y; `flow` is the direction of the sounding's shear and of the tracer blobs' spread
+    (FLOWS; "x" is the supercell state as pam_amd.idealized builds it); `id0` is the seed offset of the temperature noise."""
+    if flow != "x" and (ny == 1 or not supercell):
+        raise ValueError("flow=%r needs a 3-D supercell case" % flow)
+    xlen = nx * dxy
+    ylen = ny * (dxy if dy is None else dy) if ny > 1 else xlen
+    if supercell:
+        f = idz.supercell_fields(nens, nx, ny, nz, zint, consts=consts, tracers=tr, magnitude=mag, id0=id0)
+        (idz.add_tracer_blobs if flow == "x" else _add_turned_tracer_blobs)(f, tr, xlen, ylen, zint)
+        _turn_wind(f, flow, dry_air, ny)
+        if dry_air:      # exact zeros in the vapour beside moist air + a mean wind across the edges: the limiter acts on water_vapor
             idz.carve_dry_air(f, tr)
     else:
         f = idz.dry_bubble_fields(nens, nx, ny, nz, xlen, ylen, zint, consts=consts, tracers=tr)
@@ -80,23 +158,26 @@ class OracleCase:
     timeSteps of `crm_dt`, in place; returns the sub-step count) and `floor()` (parity_gate.noise_floor of that run)"""
 
     def __init__(self, nens, nx, ny, nz, tr, zint, consts=idz.CONSTS_DEFAULT, supercell=True, per_ens=False, mag=0.5, crm_dt=2.0,
-                 dxy=500.0, dry_air=False, mode_a=True, nsteps=1, gate_factor=1.0):
+                 dxy=500.0, dry_air=False, mode_a=True, nsteps=1, gate_factor=1.0, dy=None, flow="x"):
         self.dims = (nens, nx, ny, nz)
+        self.flow, self.dry_air = flow, dry_air
         self.tracers, self.consts, self.crm_dt, self.mode_a, self.nsteps, self.gate_factor = tr, consts, crm_dt, mode_a, nsteps, gate_factor
         self.names, self.pos, self.mass, self.idwv = idz.tracer_flags(tr)
         self.fields, self.xlen, self.ylen, self.zi, self.dz = build_inputs(nens, nx, ny, nz, tr, zint, consts, supercell, per_ens,
-                                                                           mag, dxy, dry_air)
+                                                                           mag, dxy, dry_air, dy, flow)
+        self.dx, self.dy = self.xlen / nx, self.ylen / ny
 
-    def oracle(self, consts=None):
+    def oracle(self, consts=None, ylen=None):
+        """the case's oracle; `ylen` replaces the case's own (tests/test_anisotropy_census.py: the grid a dy -> dx slip would see)"""
         nens, nx, ny, nz = self.dims
-        o = ao.OracleDycore(nens, nx, ny, nz, self.xlen, self.ylen, self.dz, self.pos, self.mass, self.idwv,
+        o = ao.OracleDycore(nens, nx, ny, nz, self.xlen, self.ylen if ylen is None else ylen, self.dz, self.pos, self.mass, self.idwv,
                             consts=self.consts if consts is None else consts)
         if not self.mode_a:
             o.set_grav_balance(False)
         return o
 
-    def run(self, f, consts=None):
-        o = self.oracle(consts)
+    def run(self, f, consts=None, ylen=None):
+        o = self.oracle(consts, ylen)
         o.declare_current_profile_as_hydrostatic(f)
         return sum(o.time_step(f, self.crm_dt)[0] for _ in range(self.nsteps))
 

@@ -10,37 +10,24 @@ import numpy as np
 import pytest
 
 from pam_amd import idealized as idz
+from parity_cases import build_inputs
 from parity_gate import compare, floor_gate, gates, noise_floor, record, worst_errors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "examples", "driver")
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("mode_a", [True, False])
-def test_cpp_driver_matches_oracle(tmp_path, mode_a):
+def _driver_matches_oracle(tmp_path, mode_a, nx=7, ny=4, **grid):
+    """examples/driver on a seeded case against the oracle through the parity gate; `grid`: dxy, dy, flow of build_inputs"""
     from oracle import awfl_oracle as ao
     assert os.path.exists(DRIVER), "examples/driver missing: run __graft_entry__.build()"
-    nens, nx, ny, nz, nsteps, crm_dt = 5, 7, 4, 9, 2, 2.0
+    nens, nz, nsteps, crm_dt = 5, 9, 2, 2.0
     tr = idz.TRACERS_KESSLER_SHOC
     names, pos, mass, idwv = idz.tracer_flags(tr)
     zint = idz.stretched_interfaces(nz, 12000.0)
-    xlen, ylen = nx * 500.0, ny * 500.0
-    f = idz.supercell_fields(nens, nx, ny, nz, zint, tracers=tr, magnitude=0.5)
-    idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
-    c = idz.CONSTS_DEFAULT
+    f, xlen, ylen, _, _ = build_inputs(nens, nx, ny, nz, tr, zint, mag=0.5, **grid)
     inp, outp = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-    with open(inp, "wb") as fh:
-        fh.write(struct.pack("<8q", nens, nx, ny, nz, len(tr), nsteps, int(mode_a), 1))
-        fh.write(struct.pack("<3d", xlen, ylen, crm_dt))
-        fh.write(struct.pack("<6d", c["R_d"], c["cp_d"], c["R_v"], c["cp_v"], c["p0"], c["grav"]))
-        fh.write(np.asarray(zint, dtype="<f8").tobytes())
-        fh.write(bytes(bytearray(v for t in range(len(tr)) for v in (int(pos[t]), int(mass[t])))))
-        fh.write(struct.pack("<q", idwv))
-        for k in ("density_dry", "uvel", "vvel", "wvel", "temp"):
-            fh.write(f[k].astype("<f8").tobytes())
-        for t in range(len(tr)):
-            fh.write(f["tracers"][t].astype("<f8").tobytes())
+    _write_input(inp, f, tr, zint, xlen, ylen, crm_dt, nsteps, int(mode_a))
     r = subprocess.run([DRIVER, inp, outp], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     assert "SSPRK3+WENO+FV A-grid" in r.stdout
@@ -55,6 +42,21 @@ def test_cpp_driver_matches_oracle(tmp_path, mode_a):
     nsub = run(f)
     got = {"density_dry": raw[0], "uvel": raw[1], "vvel": raw[2], "wvel": raw[3], "temp": raw[4], "tracers": raw[5:]}
     compare(got, f, names, nsub, floor=noise_floor(run, f0, names, 0, base=f))      # tests/parity_gate.py: the floor gate
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode_a", [True, False])
+def test_cpp_driver_matches_oracle(tmp_path, mode_a):
+    _driver_matches_oracle(tmp_path, mode_a)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode_a", [True, False])
+def test_cpp_driver_matches_oracle_on_an_anisotropic_grid(tmp_path, mode_a):
+    """ylen reaches the handle on a path of its own (host/dynamics/awfl_amd/Dycore.h: cfg.ylen): dx = 800 m, dy = 500 m with the
+    shear along y in mode A, dx = 500 m, dy = 800 m in mode B"""
+    grid = dict(dxy=800.0, dy=500.0, flow="y") if mode_a else dict(dxy=500.0, dy=800.0, flow="y")
+    _driver_matches_oracle(tmp_path, mode_a, nx=7, ny=5, **grid)
 
 
 @pytest.mark.gpu
@@ -255,6 +257,28 @@ def test_cpp_driver_sharded_over_handles_equals_unsharded_bit_for_bit(tmp_path, 
     assert np.isfinite(outs[0]).all() and not np.array_equal(outs[0][:f["density_dry"].size], f["density_dry"].ravel())
     for o in outs[1:]:
         assert np.array_equal(outs[0], o)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nens,ranks", [(70, 2), (6, 3)], ids=["member_and_flat_lane_shards", "flat_lane_shards"])
+def test_cpp_driver_sharded_over_handles_on_an_anisotropic_grid_equals_unsharded_bit_for_bit(tmp_path, nens, ranks):
+    """the test above with dx = 500 m, dy = 800 m and the shear along both x and y; the CFL-limiting member is fast along y"""
+    assert os.path.exists(DRIVER), "examples/driver missing: run __graft_entry__.build()"
+    nx, ny, nz, nsteps, crm_dt = 6, 5, 8, 2, 2.0
+    tr = idz.TRACERS_KESSLER_SHOC
+    zint = idz.stretched_interfaces(nz, 12000.0)
+    f, xlen, ylen, _, _ = build_inputs(nens, nx, ny, nz, tr, zint, mag=0.5, dxy=500.0, dy=800.0, flow="diag")
+    f["vvel"][..., 1] -= 60.0                      # member 1 alone sets the ensemble's CFL step
+    inp = str(tmp_path / "in.bin")
+    _write_input(inp, f, tr, zint, xlen, ylen, crm_dt, nsteps, 1)
+    outs = []
+    for n in (1, ranks):
+        outp = str(tmp_path / ("out%d.bin" % n))
+        r = subprocess.run([DRIVER, "--gpus", str(n), inp, outp], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr
+        outs.append(np.fromfile(outp, dtype="<f8"))
+    assert np.isfinite(outs[0]).all() and not np.array_equal(outs[0][:f["density_dry"].size], f["density_dry"].ravel())
+    assert np.array_equal(outs[0], outs[1])
 
 
 @pytest.mark.gpu

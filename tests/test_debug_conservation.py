@@ -5,16 +5,16 @@ import numpy as np
 import pytest
 
 from pam_amd import idealized as idz
+from parity_cases import build_inputs
 
 pytestmark = pytest.mark.gpu
 
 
-def _setup(nens, nx, ny, nz, tr):
+def _setup(nens, nx, ny, nz, tr, **grid):
+    """`grid`: dxy, dy, flow of parity_cases.build_inputs (default: 500 m x 500 m, the shear along x)"""
     from pam_amd import Dycore, PamCoupler
     zint = idz.stretched_interfaces(nz, 12000.0)
-    xlen, ylen = nx * 500.0, (ny if ny > 1 else nx) * 500.0
-    f = idz.supercell_fields(nens, nx, ny, nz, zint, tracers=tr, magnitude=0.5)
-    idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
+    f, xlen, ylen, _, _ = build_inputs(nens, nx, ny, nz, tr, zint, mag=0.5, **grid)
     coupler = PamCoupler("cuda:0")
     coupler.set_option("crm_dt", 2.0)
     coupler.allocate_coupler_state(nz, ny, nx, nens)
@@ -63,6 +63,20 @@ def test_conservation_check_is_silent_on_a_clean_run_and_fires_where_mass_was_ch
     with pytest.raises(PamAmdError):
         dycore.conservation()
     dycore.finalize(coupler)
+
+
+@pytest.mark.parametrize("dxy,dy", [(500.0, 800.0), (1000.0, 250.0)])
+def test_conservation_check_is_silent_on_an_anisotropic_grid(dxy, dy):
+    """the masses are sums of q dz over the cells of a member (Dycore.h:36-58: every cell has the same dx dy): with dx != dy and
+    the shear along y the y flux differences still telescope, so a clean run reports nothing, member lanes and flat lanes alike"""
+    for nens in (70, 3):
+        coupler, dycore = _setup(nens, 6, 5, 8, idz.TRACERS_NONE, dxy=dxy, dy=dy, flow="y")
+        dycore.set_debug_conservation(True)
+        for _ in range(3):
+            dycore.timeStep(coupler)
+            n, max_rel, _, _, report = dycore.conservation()
+            assert n == 0 and report == "" and max_rel <= 1.0e-10, (nens, n, max_rel, report)
+        dycore.finalize(coupler)
 
 
 def test_blob_tracers_are_reported_as_the_reference_would_report_them():

@@ -14,7 +14,7 @@ from oracle import awfl_oracle as ao
 from pam_amd import idealized as idz
 import emu_harness as eh
 from parity_gate import noise_floor
-from test_emu_parity import _inputs, _rel, assert_within_floor
+from test_emu_parity import _case_inputs, _rel, assert_within_floor
 
 # name: (nens, nx, ny, nz, tracers, zint, kw, mode_a, tile overrides (W, tc, lpb) to try besides the automatic geometry)
 CASES = {
@@ -28,6 +28,13 @@ CASES = {
                                [(0, 5, 0), (3, 3, 0)]),
     "nens4_vapour_limited_2d_B": (4, 10, 1, 8, idz.TRACERS_NONE, idz.stretched_interfaces(8, 12000.0), dict(dry_air=True), False,
                                   [(0, 1, 0)]),
+    # dx != dy with the sounding's shear along y: the flat-lane y/z sweeps and the y/z tile kernels, each with its own y indexing
+    "aniso_500x800_nens2_3d_flowy": (2, 8, 5, 9, idz.TRACERS_NONE, idz.stretched_interfaces(9, 12000.0),
+                                     dict(dxy=500.0, dy=800.0, flow="y"), True, [(0, 3, 0), (1, 0, 0)]),
+    "aniso_800x500_nens3_perens_nt4_B_flowy": (3, 6, 5, 8, idz.TRACERS_KESSLER_SHOC, idz.stretched_interfaces(8, 12000.0),
+                                               dict(per_ens=True, dxy=800.0, dy=500.0, flow="y"), False, [(2, 0, 0), (2, 4, 0)]),
+    "aniso_1000x250_nens5_vapour_limited_A_flowy": (5, 8, 5, 9, idz.TRACERS_NONE, idz.stretched_interfaces(9, 12000.0),
+                                                    dict(dry_air=True, dxy=1000.0, dy=250.0, flow="y"), True, [(0, 5, 0), (3, 3, 0)]),
 }
 
 
@@ -35,12 +42,9 @@ def _setup(case):
     nens, nx, ny, nz, tr, zint, kw, mode_a, tiles = CASES[case]
     consts = kw.get("consts", idz.CONSTS_DEFAULT)
     names, pos, mass, idwv = idz.tracer_flags(tr)
-    xlen = nx * 500.0
-    ylen = ny * 500.0 if ny > 1 else xlen
-    f = _inputs(nens, nx, ny, nz, tr, zint, kw, consts, xlen, ylen)
-    dz = np.diff(zint)[:, None] * np.ones((1, nens))
-    if kw.get("per_ens"):
-        dz = dz * (1 + 0.01 * np.arange(nens))[None, :]
+    f, xlen, ylen, dz = _case_inputs(nens, nx, ny, nz, tr, zint, kw)
+    if kw.get("dry_air") and ny == 1:
+        f["vvel"] += 7.0      # (the 2-D limited case has always carried the 3-D cases' 7 m/s in its inert v)
     return (nens, nx, ny, nz, xlen, ylen, dz, pos, mass, idwv, consts, mode_a), f, tiles
 
 
@@ -78,7 +82,7 @@ def test_flat_lanes_and_tile_kernels_equal_member_lane_sweeps_bit_for_bit(case):
             assert np.array_equal(ref[k], got[k]), (name, k, g.x_tile_geometry(), np.abs(ref[k] - got[k]).max())
 
 
-@pytest.mark.parametrize("case", ["c1_like_nens2_3d", "nens1_3d_nt4_B", "nens5_vapour_limited_A"])
+@pytest.mark.parametrize("case", ["c1_like_nens2_3d", "nens1_3d_nt4_B", "nens5_vapour_limited_A"] + sorted(c for c in CASES if "aniso" in c))
 def test_flat_and_tile_mapping_matches_oracle(case):
     args, f, _ = _setup(case)
     nens, nx, ny, nz, xlen, ylen, dz, pos, mass, idwv, consts, mode_a = args

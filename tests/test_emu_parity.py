@@ -14,6 +14,7 @@ import pytest
 from oracle import awfl_oracle as ao
 from pam_amd import idealized as idz
 import emu_harness as eh
+from parity_cases import build_inputs
 from parity_gate import gates, noise_floor, worst_errors
 
 
@@ -49,17 +50,28 @@ CASES = {
     "3d_nt1_vapour_limited_A": (6, 8, 5, 9, idz.TRACERS_NONE, idz.stretched_interfaces(9, 12000.0), dict(dry_air=True), True, 8),
     "3d_nt1_vapour_limited_B": (5, 6, 4, 8, idz.TRACERS_NONE, idz.stretched_interfaces(8, 12000.0), dict(dry_air=True), False, 3),
     "3d_nt1_stretched_B": (2, 7, 5, 9, idz.TRACERS_NONE, idz.stretched_interfaces(9, 12000.0), {}, False, 8),
+    # dx != dy (both orders of the ratio, nx != ny) with the sounding's shear along y: a y difference divided by dx, or a y sweep
+    # that is right only where nothing flows along y, fails here before any GPU run.  One per shape class above: NT = 1 in mode A,
+    # NT = 4 in mode B, per-member grids with NT = 10, and vapour limited across the dry rows in y
+    "aniso_500x800_nt1_A_flowy_seg3": (2, 7, 5, 9, idz.TRACERS_NONE, idz.stretched_interfaces(9, 12000.0),
+                                       dict(dxy=500.0, dy=800.0, flow="y"), True, 3),
+    "aniso_800x500_nt4_B_flowy": (2, 6, 5, 8, idz.TRACERS_KESSLER_SHOC, idz.stretched_interfaces(8, 12000.0),
+                                  dict(dxy=800.0, dy=500.0, flow="y"), False, 8),
+    "aniso_1200x300_nt10_perens_A_p3_flowy": (3, 6, 5, 8, idz.TRACERS_P3_SHOC, idz.stretched_interfaces(8, 12000.0),
+                                              dict(per_ens=True, consts=idz.CONSTS_P3, dxy=1200.0, dy=300.0, flow="y"), True, 5),
+    "aniso_500x800_nt1_vapour_limited_A_flowy": (6, 8, 5, 9, idz.TRACERS_NONE, idz.stretched_interfaces(9, 12000.0),
+                                                 dict(dry_air=True, dxy=500.0, dy=800.0, flow="y"), True, 8),
 }
 
 
-def _inputs(nens, nx, ny, nz, tr, zint, kw, consts, xlen, ylen):
-    f = idz.supercell_fields(nens, nx, ny, nz, zint, consts=consts, tracers=tr, magnitude=1.0)
-    idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
-    if kw.get("dry_air"):
-        f["uvel"] -= 25.0
-        f["vvel"] += 7.0
-        idz.carve_dry_air(f, tr)
-    return f
+def _case_inputs(nens, nx, ny, nz, tr, zint, kw):
+    """(fields, xlen, ylen, dz) of a case: tests/parity_cases.py build_inputs at this file's noise magnitude"""
+    f, xlen, ylen, _, _ = build_inputs(nens, nx, ny, nz, tr, zint, kw.get("consts", idz.CONSTS_DEFAULT), mag=1.0, dxy=kw.get("dxy", 500.0),
+                                       dry_air=bool(kw.get("dry_air")), dy=kw.get("dy"), flow=kw.get("flow", "x"))
+    dz = np.diff(zint)[:, None] * np.ones((1, nens))          # (the thicknesses scaled, not the interfaces: these cases' own grids)
+    if kw.get("per_ens"):
+        dz = dz * (1 + 0.01 * np.arange(nens))[None, :]
+    return f, xlen, ylen, dz
 
 
 @pytest.mark.parametrize("fused", [False, True], ids=["three_kernel_stage", "fused_x_stage"])
@@ -68,12 +80,7 @@ def test_emulated_kernels_match_oracle(case, fused):
     nens, nx, ny, nz, tr, zint, kw, mode_a, seg = CASES[case]
     consts = kw.get("consts", idz.CONSTS_DEFAULT)
     names, pos, mass, idwv = idz.tracer_flags(tr)
-    xlen = nx * 500.0
-    ylen = ny * 500.0 if ny > 1 else xlen
-    f = _inputs(nens, nx, ny, nz, tr, zint, kw, consts, xlen, ylen)
-    dz = np.diff(zint)[:, None] * np.ones((1, nens))
-    if kw.get("per_ens"):
-        dz = dz * (1 + 0.01 * np.arange(nens))[None, :]
+    f, xlen, ylen, dz = _case_inputs(nens, nx, ny, nz, tr, zint, kw)
     f1, f2 = copy.deepcopy(f), copy.deepcopy(f)
     o = ao.OracleDycore(nens, nx, ny, nz, xlen, ylen, dz, pos, mass, idwv, consts=consts)
     g = eh.EmuDycore(nens, nx, ny, nz, xlen, ylen, dz, pos, mass, idwv, consts=consts, seg=seg)
@@ -115,12 +122,7 @@ def test_fused_stage_equals_three_kernel_stage_bit_for_bit(case, span, split):
     nens, nx, ny, nz, tr, zint, kw, mode_a, seg = CASES[case]
     consts = kw.get("consts", idz.CONSTS_DEFAULT)
     names, pos, mass, idwv = idz.tracer_flags(tr)
-    xlen = nx * 500.0
-    ylen = ny * 500.0 if ny > 1 else xlen
-    f = _inputs(nens, nx, ny, nz, tr, zint, kw, consts, xlen, ylen)
-    dz = np.diff(zint)[:, None] * np.ones((1, nens))
-    if kw.get("per_ens"):
-        dz = dz * (1 + 0.01 * np.arange(nens))[None, :]
+    f, xlen, ylen, dz = _case_inputs(nens, nx, ny, nz, tr, zint, kw)
     out = []
     # three-kernel stage; fused stage; fused stage with the y differences of the state folded into the z sweep's output (3-D: the z
     # sweep stores yz_divergence(), the x-sweep loads that one field -- the schedule of large 3-D ensembles on the device)

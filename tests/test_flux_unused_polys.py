@@ -5,7 +5,11 @@ The host emulation of the kernel bodies runs one sub-step (three stages; the flu
 is compared, with numpy.array_equal (-0 equals +0, NaN equals nothing), with arrays recorded from the emulation of the commit before the
 skips: tests/golden/flux_unused_polys_parent.npz, written by tests/golden/make_flux_unused_polys_golden.py.  Every schedule of a physics
 case -- member or flat lanes, the z sweep whole or cut into two spans (one starts at a wall, the other ends at one), the y differences
-folded into the z sweep, the fused or the three-kernel stage -- is held to the same recorded arrays (tests/flux_unused_polys_cases.py)."""
+folded into the z sweep, the fused or the three-kernel stage -- is held to the same recorded arrays (tests/flux_unused_polys_cases.py).
+
+The recorded cases have dx == dy.  The anisotropic cases with the shear along y (fc.ANISO_PHYSICS) have no recorded arrays: their plain
+schedule is held to the oracle through the parity gate (tests/parity_gate.py), every other schedule to the plain one's bits."""
+import copy
 import os
 
 import numpy as np
@@ -13,6 +17,9 @@ import pytest
 
 import emu_harness
 import flux_unused_polys_cases as fc
+from oracle import awfl_oracle as ao
+from pam_amd import idealized as idz
+from parity_gate import compare, noise_floor
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "flux_unused_polys_parent.npz")
 
@@ -54,3 +61,34 @@ def test_every_schedule_reproduces_the_parent_commit(p, gold):
                 assert np.array_equal(a[1:5], gold[fc.key(p, False, name)]), where + (name,)
                 for fld in [0] + list(range(5, a.shape[0])):
                     assert np.array_equal(a[fld], gold[fc.key(p, True, name)][fld]), where + (name, fld)
+
+
+@pytest.mark.parametrize("p", fc.ANISO_PHYSICS, ids=fc.physics_id)
+def test_anisotropic_y_flow_case_matches_the_oracle_in_every_schedule(p):
+    (nx, ny, nz), (nt, carve, perens) = p[:2]
+    plain = {fused: fc.run(emu_harness, p, ("member", 1, False, fused)) for fused in (True, False)}
+    f, tr, zi, xlen, ylen = fc.make_fields(p)
+    assert ylen / ny != xlen / nx and np.abs(f["vvel"]).max() >= 0.5 * np.abs(f["uvel"]).max()
+    names, pos, mass, idwv = idz.tracer_flags(tr)
+
+    def run_oracle(ff):
+        o = ao.OracleDycore(fc.NENS, nx, ny, nz, xlen, ylen, np.diff(zi, axis=0), pos, mass, idwv)
+        o.declare_current_profile_as_hydrostatic(ff)
+        assert o.time_step(ff, fc.DT, fc.DT) == (1, fc.DT)
+    exp = copy.deepcopy(f)
+    run_oracle(exp)
+    got = {k: plain[True][k][0] for k in fc.FIELDS}
+    compare(got, exp, names, 1, floor=noise_floor(run_oracle, f, names, 0, base=exp))
+    for s in fc.SCHEDULES:
+        got = fc.run(emu_harness, p, s)
+        where = (fc.physics_id(p), fc.schedule_id(s))
+        for name, (a, m) in got.items():
+            if name in fc.FIELDS:
+                assert np.array_equal(a, plain[True][name][0]), where + (name,)
+            elif s[3]:
+                assert np.array_equal(a[m], plain[True][name][0][m]), where + (name,)
+            else:
+                assert m.all()
+                assert np.array_equal(a, plain[False][name][0]), where + (name,)
+                for fld in [0] + list(range(5, a.shape[0])):
+                    assert np.array_equal(a[fld], plain[True][name][0][fld]), where + (name, fld)

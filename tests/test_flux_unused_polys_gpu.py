@@ -22,22 +22,22 @@ LIMIT = 120          # seconds per case (a case takes a few)
 GRIDS = [(6, 5, 10, 4), (6, 1, 9, 1)]
 NENS = [64, 130, 8]
 CASES = [(g, nens, perens) for g in GRIDS for nens in NENS for perens in (0, 1)]
+# dx = 500 m, dy = 800 m with the sounding's shear along y (a fourth element): member lanes on per-member grids, and flat lanes
+ANISO_CASES = [((6, 5, 10, 4), 64, 1, 1), ((6, 7, 8, 1), 8, 0, 1)]
 
 
 def _id(c):
-    (nx, ny, nz, nt), nens, perens = c
-    return "%dx%dx%d_nt%d_nens%d_%s" % (nx, ny, nz, nt, nens, "perens" if perens else "shared")
+    (nx, ny, nz, nt), nens, perens = c[:3]
+    return "%dx%dx%d_nt%d_nens%d_%s" % (nx, ny, nz, nt, nens, "perens" if perens else "shared") + ("_dx500_dy800_flowy" if len(c) > 3 else "")
 
 
-def _inputs(nx, ny, nz, nt, nens, perens):
+def _inputs(nx, ny, nz, nt, nens, perens, aniso=0):
     import numpy as np
     from pam_amd import idealized as idz
+    from parity_cases import build_inputs
     tr = idz.TRACERS_NONE if nt == 1 else idz.TRACERS_KESSLER_SHOC
     zint = idz.stretched_interfaces(nz, 12000.0)
-    xlen = nx * 500.0
-    ylen = ny * 500.0 if ny > 1 else xlen
-    f = idz.supercell_fields(nens, nx, ny, nz, zint, tracers=tr, magnitude=0.5)
-    idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
+    f, xlen, ylen, _, _ = build_inputs(nens, nx, ny, nz, tr, zint, mag=0.5, **(dict(dxy=500.0, dy=800.0, flow="y") if aniso else {}))
     # smooth periodic waves on the wind: both signs of the mass flux at the faces of every line, motion next to both walls
     k, j, i, e = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), np.arange(nens), indexing="ij")
     px, py = 2.0 * np.pi * i / nx, 2.0 * np.pi * j / ny
@@ -77,7 +77,7 @@ def _run(inp, nx, ny, nz, nens, fused, lanes=None):
     return ncyc, out
 
 
-def _worker(nx, ny, nz, nt, nens, perens):
+def _worker(nx, ny, nz, nt, nens, perens, aniso=0):
     import copy
     import numpy as np
     sys.path.insert(0, ROOT)
@@ -85,7 +85,7 @@ def _worker(nx, ny, nz, nt, nens, perens):
     from pam_amd import idealized as idz
     from oracle import awfl_oracle as ao
     from parity_gate import compare
-    inp = _inputs(nx, ny, nz, nt, nens, perens)
+    inp = _inputs(nx, ny, nz, nt, nens, perens, aniso)
     f, tr, zi, xlen, ylen = inp
     names, pos, mass, idwv = idz.tracer_flags(tr)
     keys = ("density_dry", "uvel", "vvel", "wvel", "temp", "tracers")
@@ -111,14 +111,14 @@ def _worker(nx, ny, nz, nt, nens, perens):
     print("CASE OK")
 
 
-@pytest.mark.parametrize("case", CASES, ids=_id)
+@pytest.mark.parametrize("case", CASES + ANISO_CASES, ids=_id)
 def test_walls_and_periodic_closing_on_the_device(case):
-    (nx, ny, nz, nt), nens, perens = case
-    r = subprocess.run([sys.executable, os.path.abspath(__file__)] + [str(v) for v in (nx, ny, nz, nt, nens, perens)],
+    (nx, ny, nz, nt), nens, perens = case[:3]
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)] + [str(v) for v in (nx, ny, nz, nt, nens, perens) + case[3:]],
                        capture_output=True, text=True, timeout=LIMIT, cwd=ROOT)
     print(r.stdout[-2000:])
     assert r.returncode == 0 and "CASE OK" in r.stdout, (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
 
 
 if __name__ == "__main__":
-    _worker(*[int(v) for v in sys.argv[1:7]])
+    _worker(*[int(v) for v in sys.argv[1:8]])

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from pam_amd import idealized as idz
+from parity_cases import build_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -35,21 +36,24 @@ CASES = {
     "3d_nt4_perens_member_lanes": (128, 6, 5, 9, idz.TRACERS_KESSLER_SHOC, idz.stretched_interfaces(9, 12000.0), "mod16", True, idz.CONSTS_DEFAULT),
     "3d_nt1_perens_ragged_130_B": (130, 5, 3, 7, idz.TRACERS_NONE, idz.stretched_interfaces(7, 9000.0), "mod16", False, idz.CONSTS_DEFAULT),
     "2d_nt10_perens_member_lanes": (192, 32, 1, 12, idz.TRACERS_P3_SHOC, idz.stretched_interfaces(12, 12000.0), "mod16", True, idz.CONSTS_P3),
+    # dx != dy (ANISO below) with the sounding's shear along y or along both: member lanes (a whole block with per-member grids and
+    # NT = 4, a ragged one with vapour limited across the dry rows in y) and flat lanes
+    "aniso_3d_nt4_perens_member_lanes_flowy": (64, 6, 5, 8, idz.TRACERS_KESSLER_SHOC, idz.stretched_interfaces(8, 12000.0), "mod16", True, idz.CONSTS_DEFAULT),
+    "aniso_3d_nt1_vapour_limited_ragged_B_diag": (70, 5, 7, 8, idz.TRACERS_NONE, idz.stretched_interfaces(8, 12000.0), False, False, idz.CONSTS_DEFAULT),
+    "aniso_3d_nt4_flat_lanes_B_diag": (3, 6, 7, 8, idz.TRACERS_KESSLER_SHOC, idz.stretched_interfaces(8, 12000.0), False, False, idz.CONSTS_DEFAULT),
 }
+# options of parity_cases.build_inputs for the cases that are not on the 500 m x 500 m grid with the shear along x
+ANISO = {"aniso_3d_nt4_perens_member_lanes_flowy": dict(dxy=500.0, dy=800.0, flow="y"),
+         "aniso_3d_nt1_vapour_limited_ragged_B_diag": dict(dxy=800.0, dy=500.0, flow="diag"),
+         "aniso_3d_nt4_flat_lanes_B_diag": dict(dxy=1000.0, dy=250.0, flow="diag")}
 
 
 def _run(case, fused, chunks=0, want_mult=False, fold=None, lanes=None, tail=None):
     import torch
     from pam_amd import Dycore, PamCoupler
     nens, nx, ny, nz, tr, zint, per_ens, mode_a, consts = CASES[case]
-    xlen = nx * 500.0
-    ylen = ny * 500.0 if ny > 1 else xlen
-    f = idz.supercell_fields(nens, nx, ny, nz, zint, consts=consts, tracers=tr, magnitude=0.5)
-    idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
-    if "vapour_limited" in case:
-        f["uvel"] -= 25.0
-        f["vvel"] += 7.0
-        idz.carve_dry_air(f, tr)
+    f, xlen, ylen, zi, _ = build_inputs(nens, nx, ny, nz, tr, zint, consts, per_ens=per_ens, mag=0.5, dry_air="vapour_limited" in case,
+                                        **ANISO.get(case, {}))
     if nens >= 64:      # every third member: blobs on a positive floor (the limiter stays idle there); every fifth: none at all
         for t, (name, _, _) in enumerate(tr):
             if name == "water_vapor":
@@ -57,11 +61,6 @@ def _run(case, fused, chunks=0, want_mult=False, fold=None, lanes=None, tail=Non
             q = f["tracers"][t]
             q[..., 1::3] = q[..., 1::3] + 2.0e-4 * f["density_dry"][..., 1::3]
             q[..., 2::5] = 0.0
-    zi = np.asarray(zint)[:, None] * np.ones((1, nens))
-    if per_ens == "mod16":
-        zi = zi * (1 + 0.01 * (np.arange(nens) % 16) + 1.0e-4 * (np.arange(nens) // 16))[None, :]
-    elif per_ens:
-        zi = zi * (1 + 0.01 * np.arange(nens))[None, :]
     coupler = PamCoupler("cuda:0")
     coupler.set_option("crm_dt", 2.0)
     for k, v in consts.items():
@@ -81,6 +80,8 @@ def _run(case, fused, chunks=0, want_mult=False, fold=None, lanes=None, tail=Non
         dycore.set_yz_fold(fold)
     if tail is not None:
         dycore.set_tail_fusion(tail)
+    if case in ANISO:
+        print(case, ANISO[case], dict(fused=fused, chunks=chunks, fold=fold, lanes=lanes, tail=tail), "->", dycore.get_lane_mapping())
     coupler.load_fields(f)
     if not mode_a:
         coupler.set_option("balance_hydrostasis_with_gravity", False)
@@ -121,7 +122,7 @@ def test_flag_row_cases_exercise_the_limiter(case):
 
 
 @pytest.mark.parametrize("case", ["3d_nt4_whole_flag_rows", "3d_nt1_vapour_limited_rows", "3d_nt4_perens_member_lanes", "3d_nt1_perens_ragged_130_B",
-                                  "3d_nt4_many_lines_inline_tracers"])
+                                  "3d_nt4_many_lines_inline_tracers", "aniso_3d_nt4_perens_member_lanes_flowy"])
 def test_yz_fold_is_a_schedule_not_an_arithmetic(case):
     """3-D member lanes: the z sweep storing the y+z part of the state's divergence (one field per variable for the x-sweep; the
     default) == the z sweep storing its own differences and the x-sweep loading both (pam_amd_awfl_set_yz_fold), bit for bit"""
@@ -134,7 +135,7 @@ def test_yz_fold_is_a_schedule_not_an_arithmetic(case):
 
 
 @pytest.mark.parametrize("case", ["3d_nt4_whole_flag_rows", "2d_nt10_whole_flag_rows", "3d_nt4_many_lines_inline_tracers",
-                                  "2d_nt10_perens_member_lanes", "3d_nt4_perens_member_lanes"])
+                                  "2d_nt10_perens_member_lanes", "3d_nt4_perens_member_lanes", "aniso_3d_nt4_perens_member_lanes_flowy"])
 @pytest.mark.parametrize("chunks", [1, 2])
 def test_tail_fusion_is_a_schedule_not_an_arithmetic(case, chunks):
     """NT > 1, member-lane sweeps: phase 2 of the further tracers + the pressure pass + water vapour's fix-up as ONE launch
@@ -167,7 +168,8 @@ def test_yz_fold_is_refused_where_it_does_not_exist():
         dycore.finalize(coupler)
 
 
-@pytest.mark.parametrize("case", ["3d_nt4_perens_member_lanes", "3d_nt1_perens_ragged_130_B", "2d_nt10_perens_member_lanes"])
+@pytest.mark.parametrize("case", ["3d_nt4_perens_member_lanes", "3d_nt1_perens_ragged_130_B", "2d_nt10_perens_member_lanes",
+                                  "aniso_3d_nt4_perens_member_lanes_flowy"])
 def test_per_member_grids_member_lanes_equal_flat_lanes_bit_for_bit(case):
     """per-member vertical grids: the LDS-staged tables of the member-lane z sweep (awfl_fluxz_pe_kernel) against flat lanes, where
     every lane reads its member's table from global memory (ZTabLane) -- the same weno5_table on the same 31 values"""

@@ -17,10 +17,13 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))     # (for `python tests/test_fuzz_mappings.py`)
 from pam_amd import idealized as idz   # noqa: E402
+from parity_cases import build_inputs   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 NSEEDS = int(os.environ.get("PAM_AMD_FUZZ_SEEDS", "12"))
+NSEEDS_ANISO = int(os.environ.get("PAM_AMD_FUZZ_SEEDS", "8"))      # the second family: the same draws on grids with dx != dy
+ANISO_RATIOS = (0.4, 0.625, 1.6, 2.5)      # dy / dx
 NVARIANTS = 5
 MAX_CELLS = 400000
 
@@ -92,10 +95,26 @@ def draw_case(seed):
     return s
 
 
+def draw_aniso_case(seed):
+    """draw_case(seed), unchanged, on a grid with dx != dy and with the sounding's shear along y or along both (parity_cases.
+    build_inputs): 3-D draws only (a 2-D seed is drawn again 100000 further on), dy/dx and the flow from a generator of their own"""
+    sd = seed
+    while True:
+        s = draw_case(sd)
+        if s["ny"] > 1:
+            break
+        sd += 100000
+    rng = np.random.default_rng(9000011 * seed + 31)
+    s["dy"] = s["dxy"] * float(rng.choice(ANISO_RATIOS))
+    s["flow"] = str(rng.choice(["y", "diag"]))
+    return s
+
+
 def describe(s):
     return ("seed %d: nens %d, %dx%dx%d, nt %d (vapour at %d), %s%s, mode %s, dry_air %d"
             % (s["seed"], s["nens"], s["nx"], s["ny"], s["nz"], len(s["tracers"]), [t[0] for t in s["tracers"]].index("water_vapor"),
-               s["grid"], "+per-member" if s["per_ens"] else "", "A" if s["mode_a"] else "B", s["dry_air"]))
+               s["grid"], "+per-member" if s["per_ens"] else "", "A" if s["mode_a"] else "B", s["dry_air"])
+            + (", dx %g, dy %g, flow %s" % (s["dxy"], s["dy"], s["flow"]) if "dy" in s else ""))
 
 
 # (order matters where one knob's validity depends on another: the lane mapping first)
@@ -145,14 +164,8 @@ def run(s, f, xlen, ylen, knobs):
 
 def run_case(s):
     nens, nx, ny, nz, tr = s["nens"], s["nx"], s["ny"], s["nz"], s["tracers"]
-    xlen = nx * s["dxy"]
-    ylen = ny * s["dxy"] if ny > 1 else xlen
-    f = idz.supercell_fields(nens, nx, ny, nz, s["zint"], consts=s["consts"], tracers=tr, magnitude=0.5, id0=s["seed"])
-    idz.add_tracer_blobs(f, tr, xlen, ylen, s["zint"])
-    if s["dry_air"]:
-        f["uvel"] -= 25.0
-        f["vvel"] += 7.0 if ny > 1 else 0.0
-        idz.carve_dry_air(f, tr)
+    f, xlen, ylen, _, _ = build_inputs(nens, nx, ny, nz, tr, s["zint"], s["consts"], mag=0.5, dxy=s["dxy"], dry_air=s["dry_air"],
+                                       dy=s.get("dy"), flow=s.get("flow", "x"), id0=s["seed"])
     n0, ref, _, _ = run(s, f, xlen, ylen, {"lane_mapping": ("member", "sweep"), "ensemble_chunks": (1,), "graph_replay": ("off",)})
     for k in ("density_dry", "uvel", "wvel", "temp"):
         assert np.isfinite(ref[k]).all(), k
@@ -174,6 +187,15 @@ def test_random_schedules_give_the_same_bits(seed):
     s = draw_case(seed)
     try:
         run_case(s)
+    except AssertionError as e:
+        raise AssertionError(describe(s) + "\n" + str(e)[:2000]) from e
+
+
+@pytest.mark.parametrize("seed", range(NSEEDS_ANISO))
+def test_random_schedules_give_the_same_bits_on_an_anisotropic_grid(seed):
+    s = draw_aniso_case(seed)
+    try:
+        print(describe(s), "|", " ".join(run_case(s)))
     except AssertionError as e:
         raise AssertionError(describe(s) + "\n" + str(e)[:2000]) from e
 

@@ -22,9 +22,11 @@ from pam_amd import idealized as idz   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
+from parity_cases import build_inputs   # noqa: E402
 from parity_gate import FLOOR_K, compare, is_tight, noise_floor, tol_noise_fields   # noqa: E402
 
 NSEEDS = int(os.environ.get("PAM_AMD_FUZZ_SEEDS", "16"))
+NSEEDS_ANISO = int(os.environ.get("PAM_AMD_FUZZ_SEEDS", "8"))      # the second family: the same draws on grids with dx != dy
 MAX_CELLS = 24000          # the oracle runs ~2e5 cell-updates/s on one core
 
 
@@ -56,11 +58,31 @@ def draw_case(seed):
     return c
 
 
+ANISO_RATIOS = (0.4, 0.625, 1.6, 2.5)      # dy / dx
+
+
+def draw_aniso_case(seed):
+    """draw_case(seed), unchanged, on a grid with dx != dy and with the sounding's shear along y or along both (parity_cases.
+    build_inputs): 3-D draws only (a 2-D seed is drawn again 100000 further on, as test_reference_pin._small_draw does), dy/dx and
+    the flow from a generator of their own, so that no draw of draw_case moves"""
+    s = seed
+    while True:
+        c = draw_case(s)
+        if c["ny"] > 1:
+            break
+        s += 100000
+    rng = np.random.default_rng(9000011 * seed + 29)
+    c["dy"] = c["dxy"] * float(rng.choice(ANISO_RATIOS))
+    c["flow"] = str(rng.choice(["y", "diag"]))
+    return c
+
+
 def describe(c):
     return ("seed %d: nens %d, %dx%dx%d, nt %d (vapour at %d), %s%s, mode %s, dry_air %d, crm_dt %g x%d, dxy %g, lanes %s/%s/%s/%s"
             % (c["seed"], c["nens"], c["nx"], c["ny"], c["nz"], len(c["tracers"]), [t[0] for t in c["tracers"]].index("water_vapor"),
                c["grid"], "+per-member" if c["per_ens"] else "", "A" if c["mode_a"] else "B", c["dry_air"], c["crm_dt"], c["nsteps"],
-               c["dxy"], c["lanes"], c["xkernels"], c["xexchange"], c["fusion"]))
+               c["dxy"], c["lanes"], c["xkernels"], c["xexchange"], c["fusion"])
+            + (", dy %g, flow %s" % (c["dy"], c["flow"]) if "dy" in c else ""))
 
 
 class IllPosedCase(Exception):
@@ -74,18 +96,8 @@ def run_case(c):
     from oracle import awfl_oracle as ao
     nens, nx, ny, nz, tr, consts = c["nens"], c["nx"], c["ny"], c["nz"], c["tracers"], c["consts"]
     names, pos, mass, idwv = idz.tracer_flags(tr)
-    xlen = nx * c["dxy"]
-    ylen = ny * c["dxy"] if ny > 1 else xlen
-    f = idz.supercell_fields(nens, nx, ny, nz, c["zint"], consts=consts, tracers=tr, magnitude=0.5, id0=c["seed"])
-    idz.add_tracer_blobs(f, tr, xlen, ylen, c["zint"])
-    if c["dry_air"]:
-        f["uvel"] -= 25.0
-        f["vvel"] += 7.0 if ny > 1 else 0.0
-        idz.carve_dry_air(f, tr)
-    zi = np.asarray(c["zint"])[:, None] * np.ones((1, nens))
-    if c["per_ens"]:
-        zi = zi * (1 + 0.01 * np.arange(nens))[None, :]
-    dz = np.diff(zi, axis=0)
+    f, xlen, ylen, zi, dz = build_inputs(nens, nx, ny, nz, tr, c["zint"], consts, per_ens=c["per_ens"], mag=0.5, dxy=c["dxy"],
+                                         dry_air=c["dry_air"], dy=c.get("dy"), flow=c.get("flow", "x"), id0=c["seed"])
     coupler = PamCoupler("cuda:0")
     coupler.set_option("crm_dt", c["crm_dt"])
     for k, v in consts.items():
@@ -199,6 +211,18 @@ def test_random_case_matches_oracle(seed):
     c = draw_case(seed)
     try:
         run_case(c)
+    except IllPosedCase as e:
+        pytest.skip(describe(c) + ": " + str(e))
+    except AssertionError as e:
+        raise AssertionError(describe(c) + "\n" + str(e)) from e
+
+
+@pytest.mark.parametrize("seed", range(NSEEDS_ANISO))
+def test_random_anisotropic_case_matches_oracle(seed):
+    c = draw_aniso_case(seed)
+    try:
+        nsub, mapping, applied, over = run_case(c)
+        print("%s | %d sub-steps, mapping %s, forced %s" % (describe(c), nsub, mapping, ",".join(applied) or "-"))
     except IllPosedCase as e:
         pytest.skip(describe(c) + ": " + str(e))
     except AssertionError as e:

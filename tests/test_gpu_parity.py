@@ -31,10 +31,10 @@ from parity_cases import CASES, OracleCase, build_inputs, named_case   # noqa: E
 
 
 def _setup(nens, nx, ny, nz, tr, zint, consts=idz.CONSTS_DEFAULT, supercell=True, per_ens=False, mag=0.5, crm_dt=2.0,
-           dxy=500.0, dry_air=False):
+           dxy=500.0, dry_air=False, dy=None, flow="x"):
     from pam_amd import Dycore, PamCoupler
     names, pos, mass, idwv = idz.tracer_flags(tr)
-    f, xlen, ylen, zi, dz = build_inputs(nens, nx, ny, nz, tr, zint, consts, supercell, per_ens, mag, dxy, dry_air)
+    f, xlen, ylen, zi, dz = build_inputs(nens, nx, ny, nz, tr, zint, consts, supercell, per_ens, mag, dxy, dry_air, dy=dy, flow=flow)
     coupler = PamCoupler("cuda:0")
     coupler.set_option("crm_dt", crm_dt)
     for k, v in consts.items():
@@ -141,12 +141,17 @@ def test_ensemble_chunking_does_not_change_results(chunks):
         assert np.array_equal(res[0][k], res[1][k]), k
 
 
-def test_raw_fluxes_match_oracle():
+# the kernel-level checks below on today's isotropic state and on dx != dy with the sounding's shear along y (build_inputs)
+GRIDS = {"isotropic": {}, "anisotropic_y_flow": dict(dxy=500.0, dy=800.0, flow="y")}
+
+
+@pytest.mark.parametrize("grid", sorted(GRIDS, reverse=True))
+def test_raw_fluxes_match_oracle(grid):
     """Kernel-level check of the reconstruction/flux kernel (Dycore.h:334-519) on its own."""
     import torch
     nens, nx, ny, nz = 2, 7, 5, 9
     tr = idz.TRACERS_NONE
-    coupler, dycore, oracle, fo, names = _setup(nens, nx, ny, nz, tr, idz.stretched_interfaces(nz, 12000.0), mag=1.0)
+    coupler, dycore, oracle, fo, names = _setup(nens, nx, ny, nz, tr, idz.stretched_interfaces(nz, 12000.0), mag=1.0, **GRIDS[grid])
     dycore.declare_current_profile_as_hydrostatic(coupler)
     oracle.declare_current_profile_as_hydrostatic(fo)
     st, trc = oracle.convert_coupler_to_dynamics(fo)
@@ -166,13 +171,14 @@ def test_raw_fluxes_match_oracle():
     dycore.finalize(coupler)
 
 
-def test_converts_with_halo_arrays_match_oracle():
+@pytest.mark.parametrize("grid", sorted(GRIDS, reverse=True))
+def test_converts_with_halo_arrays_match_oracle(grid):
     """Dycore::convert_coupler_to_dynamics(coupler, state, tracers) and convert_dynamics_to_coupler(coupler, state, tracers) with
     the reference's halo'd arrays (Dycore.h:1336-1388, :1281-1331) against the oracle's restatement of the same two kernels."""
     import torch
     nens, nx, ny, nz = 3, 6, 4, 8
     tr = idz.TRACERS_KESSLER_SHOC
-    coupler, dycore, oracle, fo, names = _setup(nens, nx, ny, nz, tr, idz.stretched_interfaces(nz, 12000.0))
+    coupler, dycore, oracle, fo, names = _setup(nens, nx, ny, nz, tr, idz.stretched_interfaces(nz, 12000.0), **GRIDS[grid])
     nt = len(tr)
     st_o, tr_o = oracle.convert_coupler_to_dynamics(fo)
     st = torch.full((5, nz + 6, ny + 6, nx + 6, nens), float("nan"), dtype=torch.float64, device="cuda:0")

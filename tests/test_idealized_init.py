@@ -53,15 +53,33 @@ def test_oracle_supercell_init_properties():
         o.init_idealized(f, "bogus", zint)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("kind,ny", [("thermal", 1), ("thermal", 5), ("supercell", 1), ("supercell", 4)])
-def test_gpu_idealized_init_matches_oracle(kind, ny, tmp_path):
+def test_oracle_thermal_init_on_an_anisotropic_grid():
+    """dx = 1000 m, dy = 2400 m: the bubble's centre (xlen/2, ylen/2) = (4000 m, 6000 m) is off the diagonal, and the quadrature
+    points of a cell are spread over dx in x and dy in y"""
+    nens, nx, ny, nz = 2, 8, 5, 16
+    zint = idz.uniform_interfaces(nz, 8000.0)
+    dx, dy = 1000.0, 2400.0
+    o, f = _oracle(nens, nx, ny, nz, zint, nx * dx, ny * dy)
+    o.init_idealized(f, "thermal", zint)
+    assert all(np.isfinite(v).all() for v in f.values())
+    dT = f["temp"] - f["temp"][:, :1, :1, :]
+    k, j, i, e = np.unravel_index(np.argmax(dT), dT.shape)
+    assert abs((j + 0.5) * dy - 0.5 * ny * dy) <= 0.5 * dy and abs((i + 0.5) * dx - 0.5 * nx * dx) <= dx
+    # the bubble (radius 2000 m) reaches two cells from its centre in x, and in y only the rows beside the centre row (their cells
+    # begin 1200 m from the centre): a dy taken for dx would spread it over every row
+    warm = dT[..., 0].max(axis=0) > 1e-6
+    assert warm[2].sum() == 4 and warm[1].any() and warm[3].any() and not warm[0].any() and not warm[4].any(), warm
+    o2, f2 = _oracle(nens, nx, ny, nz, zint, nx * dx, ny * dx)
+    o2.init_idealized(f2, "thermal", zint)
+    assert np.abs(f2["temp"] - f["temp"]).max() > 0.1
+
+
+def _gpu_init_matches_oracle(kind, nx, ny, xlen, ylen, tmp_path):
     import torch
     from pam_amd import Dycore, PamCoupler, PamAmdError
-    nens, nx, nz = 70, 7, 14
+    nens, nz = 70, 14
     tr = idz.TRACERS_KESSLER_SHOC
     zint = idz.stretched_interfaces(nz, 14000.0, ratio=1.1)
-    xlen, ylen = nx * 1000.0, (ny if ny > 1 else nx) * 1000.0
     yml = tmp_path / "input.yaml"
     yml.write_text("initData: %s\n" % kind)
     coupler = PamCoupler("cuda:0")
@@ -87,3 +105,18 @@ def test_gpu_idealized_init_matches_oracle(kind, ny, tmp_path):
     with pytest.raises(PamAmdError):
         dycore.init_idealized(coupler, "bogus")
     dycore.finalize(coupler)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,ny", [("thermal", 1), ("thermal", 5), ("supercell", 1), ("supercell", 4)])
+def test_gpu_idealized_init_matches_oracle(kind, ny, tmp_path):
+    nx = 7
+    _gpu_init_matches_oracle(kind, nx, ny, nx * 1000.0, (ny if ny > 1 else nx) * 1000.0, tmp_path)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,dx,dy", [("thermal", 1000.0, 1600.0), ("thermal", 1500.0, 600.0), ("supercell", 500.0, 800.0)])
+def test_gpu_idealized_init_matches_oracle_on_an_anisotropic_grid(kind, dx, dy, tmp_path):
+    """the device places its quadrature points with dx in x and dy in y, and the bubble at (xlen/2, ylen/2), off the diagonal"""
+    nx, ny = 7, 5
+    _gpu_init_matches_oracle(kind, nx, ny, nx * dx, ny * dy, tmp_path)

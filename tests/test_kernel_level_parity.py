@@ -73,30 +73,38 @@ def test_device_weno_known_answers(grid):
     dycore.finalize(coupler)
 
 
-def _fct_case():
+ANISO = dict(dxy=500.0, dy=800.0, flow="y")        # dx != dy, the sounding's shear along y (parity_cases.build_inputs)
+
+
+def _fct_case(aniso=False):
     """3-D, Kessler+SHOC tracer set (3 positive mass-carrying tracers + tke), blobs with exact zeros around them, a mean wind
-    against x so that the periodic-seam flux is negative, and a stage time step long enough for the limiter to act."""
+    against x so that the periodic-seam flux is negative, and a stage time step long enough for the limiter to act.  `aniso`: the
+    same on ANISO, turned: blobs spread along y, the mean wind against y, the negative seam flux at the y seam."""
     nens, nx, ny, nz = 3, 8, 5, 9
     tr = idz.TRACERS_KESSLER_SHOC
     zint = idz.stretched_interfaces(nz, 12000.0)
-    coupler, dycore, oracle, fo, names = _setup(nens, nx, ny, nz, tr, zint, mag=1.0)
+    coupler, dycore, oracle, fo, names = _setup(nens, nx, ny, nz, tr, zint, mag=1.0, **(ANISO if aniso else {}))
     for f in (fo,):
-        f["uvel"] -= 25.0
-        f["vvel"] += 7.0
+        f["vvel" if aniso else "uvel"] -= 25.0
+        f["uvel" if aniso else "vvel"] += 7.0
         for t in (1, 2, 3):
             f["tracers"][t] *= 50.0          # thin blobs of large amplitude: outflow exceeds the mass available at their edges
     coupler.load_fields(fo)
     return coupler, dycore, oracle, fo, names, (nens, nx, ny, nz, len(tr))
 
 
-def _nt1_limiter_case(nens=5):
+def _nt1_limiter_case(nens=5, aniso=False):
     """3-D, water_vapor as the ONLY tracer (micro `none`, physics/micro/none/Microphysics.h:60-61: positive, adds mass) with exact
     zeros: dry slabs in x, y and z at member-dependent places beside moist air, and a mean wind across them.  The limiter then
     acts on vapour itself in every stage (Dycore.h:533 limits every positive tracer), which on the HIP side is the x-sweep's
-    "own multiplier != 1" store + row flag and the work branch of awfl_trfix_kernel -- the headline config's kernels."""
+    "own multiplier != 1" store + row flag and the work branch of awfl_trfix_kernel -- the headline config's kernels.  `aniso`: on
+    ANISO, the 25 m/s across the dry rows in y (build_inputs' dry_air)."""
     nx, ny, nz = 8, 5, 9
     tr = idz.TRACERS_NONE
     zint = idz.stretched_interfaces(nz, 12000.0)
+    if aniso:
+        coupler, dycore, oracle, fo, names = _setup(nens, nx, ny, nz, tr, zint, mag=1.0, dry_air=True, **ANISO)
+        return coupler, dycore, oracle, fo, names, (nens, nx, ny, nz, len(tr))
     coupler, dycore, oracle, fo, names = _setup(nens, nx, ny, nz, tr, zint, mag=1.0)
     fo["uvel"] -= 25.0
     fo["vvel"] += 7.0
@@ -105,7 +113,9 @@ def _nt1_limiter_case(nens=5):
     return coupler, dycore, oracle, fo, names, (nens, nx, ny, nz, len(tr))
 
 
-LIMITER_CASES = {"nt4_blobs": (_fct_case, idz.TRACERS_KESSLER_SHOC), "nt1_vapour_limited": (_nt1_limiter_case, idz.TRACERS_NONE)}
+LIMITER_CASES = {"nt4_blobs": (_fct_case, idz.TRACERS_KESSLER_SHOC), "nt1_vapour_limited": (_nt1_limiter_case, idz.TRACERS_NONE),
+                 "nt4_blobs_aniso_flowy": (lambda: _fct_case(aniso=True), idz.TRACERS_KESSLER_SHOC),
+                 "nt1_vapour_limited_aniso_flowy": (lambda: _nt1_limiter_case(aniso=True), idz.TRACERS_NONE)}
 
 
 def _assert_limiter_ran(dycore, fused, nt, shape):
@@ -122,9 +132,10 @@ def _assert_limiter_ran(dycore, fused, nt, shape):
     return flagged, total
 
 
-def test_fct_limited_fluxes_of_all_fields_and_seed_match_oracle():
+@pytest.mark.parametrize("case", ["nt4_blobs", "nt4_blobs_aniso_flowy"])
+def test_fct_limited_fluxes_of_all_fields_and_seed_match_oracle(case):
     import torch
-    coupler, dycore, oracle, fo, names, (nens, nx, ny, nz, nt) = _fct_case()
+    coupler, dycore, oracle, fo, names, (nens, nx, ny, nz, nt) = LIMITER_CASES[case][0]()
     dycore.declare_current_profile_as_hydrostatic(coupler)
     oracle.declare_current_profile_as_hydrostatic(fo)
     dt = 6.0 * oracle.compute_time_step(fo)
@@ -142,7 +153,7 @@ def test_fct_limited_fluxes_of_all_fields_and_seed_match_oracle():
     pos = np.array([p for _, p, _ in idz.TRACERS_KESSLER_SHOC])
     assert (mult[pos] < 1.0).any() and (mult[pos] == 1.0).any(), "the case must exercise the limiter"
     assert (seed0 == 0.0).any(), "the case must contain exact zeros"
-    assert (gx[5:, :, :, 0] < 0).any(), "the case must have a negative flux at the periodic seam"
+    assert ((gy[5:, :, 0] if "aniso" in case else gx[5:, :, :, 0]) < 0).any(), "the case must have a negative flux at the periodic seam"
 
     def cmp(g, o, what):
         scale = max(np.abs(o).max(), 1.0 if what < 5 else 1e-300)
@@ -223,17 +234,19 @@ def test_single_stage_every_prognostic_field_1e12(case, fused, mode_a):
     dycore.finalize(coupler)
 
 
-@pytest.mark.parametrize("case", ["3d_nt4_fct", "2d_nt10_p3", "3d_nt1_vapour_limited", "3d_nt1_vapour_limited_modeB"])
+@pytest.mark.parametrize("case", ["3d_nt4_fct", "2d_nt10_p3", "3d_nt1_vapour_limited", "3d_nt1_vapour_limited_modeB",
+                                  "3d_nt4_fct_aniso_flowy", "3d_nt1_vapour_limited_aniso_flowy", "3d_nt1_vapour_limited_modeB_aniso_flowy"])
 def test_single_substep_every_prognostic_field_1e12(case):
     """ONE SSPRK3 sub-step (crm_dt just below the CFL step -> ncycles = 1) through Dycore::timeStep: every coupler field,
     every tracer, gated at the north_star tolerance.  Multi-step runs amplify last-bit differences of the small, noisy
     fields (v, w) through the flow's own sensitivity -- the growth is gated, step by step, by test_tolerance_vs_steps_c1_bubble_is_the_flows_own_sensitivity."""
     import torch
-    if case == "3d_nt4_fct":
-        coupler, dycore, oracle, fo, names, dims = _fct_case()
+    aniso = case.endswith("_aniso_flowy")
+    if case.startswith("3d_nt4_fct"):
+        coupler, dycore, oracle, fo, names, dims = _fct_case(aniso=aniso)
     elif case.startswith("3d_nt1_vapour_limited"):
-        coupler, dycore, oracle, fo, names, dims = _nt1_limiter_case()
-        if case.endswith("modeB"):
+        coupler, dycore, oracle, fo, names, dims = _nt1_limiter_case(aniso=aniso)
+        if "modeB" in case:
             coupler.set_option("balance_hydrostasis_with_gravity", False)
             oracle.set_grav_balance(False)
     else:

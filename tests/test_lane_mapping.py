@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from pam_amd import idealized as idz
+from parity_cases import build_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -35,20 +36,27 @@ CASES = {
     "nens1_nx16_nt4": (1, 16, 4, 10, idz.TRACERS_KESSLER_SHOC, idz.stretched_interfaces(10, 12000.0), False, True, idz.CONSTS_DEFAULT, False, [(0, 0, 1), (0, 0, 3)]),
     "nens4_nx16_nt10_2d_p3_B": (4, 16, 1, 12, idz.TRACERS_P3_SHOC, idz.stretched_interfaces(12, 12000.0), True, False, idz.CONSTS_P3, False, [(2, 0, 0)]),
     "nens2_nx32_vapour_limited": (2, 32, 5, 9, idz.TRACERS_NONE, idz.stretched_interfaces(9, 12000.0), False, True, idz.CONSTS_DEFAULT, True, [(1, 0, 0)]),
+    # dx != dy (ANISO below) with the sounding's shear along both x and y, one per 3-D shape class above: whole lines inside one
+    # wavefront (shuffles), tiles of cells, vapour limited, and the large ensembles with the small-ensemble mappings forced (ragged
+    # and limited, 64-aligned rows with per-member grids)
+    "aniso_nens2_nx16_diag": (2, 16, 5, 9, idz.TRACERS_NONE, idz.stretched_interfaces(9, 12000.0), False, True, idz.CONSTS_DEFAULT, False, [(1, 0, 0)]),
+    "aniso_nens8_nt4_B_diag": (8, 12, 5, 8, idz.TRACERS_KESSLER_SHOC, idz.stretched_interfaces(8, 12000.0), False, False, idz.CONSTS_DEFAULT, False, [(0, 4, 0), (4, 0, 0)]),
+    "aniso_nens5_vapour_limited_diag": (5, 16, 5, 9, idz.TRACERS_NONE, idz.stretched_interfaces(9, 12000.0), False, True, idz.CONSTS_DEFAULT, True, [(0, 3, 0)]),
+    "aniso_nens70_ragged_vapour_limited_diag": (70, 12, 5, 9, idz.TRACERS_NONE, idz.stretched_interfaces(9, 12000.0), False, True, idz.CONSTS_DEFAULT, True, [(35, 0, 0)]),
+    "aniso_nens128_nt4_rows_perens_diag": (128, 16, 5, 8, idz.TRACERS_KESSLER_SHOC, idz.stretched_interfaces(8, 12000.0), "mod16", True, idz.CONSTS_DEFAULT, False, [(32, 0, 0), (64, 6, 0)]),
 }
-SHUFFLE_CASES = ("nens1_c2grid_slab", "nens2_c1_like", "nens1_nx16_nt4", "nens4_nx16_nt10_2d_p3_B", "nens2_nx32_vapour_limited")
+# options of parity_cases.build_inputs for the cases that are not on the 500 m x 500 m grid with the shear along x
+ANISO = {"aniso_nens2_nx16_diag": dict(dxy=500.0, dy=800.0, flow="diag"), "aniso_nens8_nt4_B_diag": dict(dxy=800.0, dy=500.0, flow="diag"),
+         "aniso_nens5_vapour_limited_diag": dict(dxy=1240.0, dy=310.0, flow="diag"),
+         "aniso_nens70_ragged_vapour_limited_diag": dict(dxy=800.0, dy=500.0, flow="diag"),
+         "aniso_nens128_nt4_rows_perens_diag": dict(dxy=500.0, dy=800.0, flow="diag")}
+SHUFFLE_CASES = ("nens1_c2grid_slab", "nens2_c1_like", "nens1_nx16_nt4", "nens4_nx16_nt10_2d_p3_B", "nens2_nx32_vapour_limited",
+                 "aniso_nens2_nx16_diag")
 
 
 def _fields(case):
     nens, nx, ny, nz, tr, zint, per_ens, mode_a, consts, limiter, tiles = CASES[case]
-    xlen = nx * 500.0
-    ylen = ny * 500.0 if ny > 1 else xlen
-    f = idz.supercell_fields(nens, nx, ny, nz, zint, consts=consts, tracers=tr, magnitude=0.5)
-    idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
-    if limiter:
-        f["uvel"] -= 25.0
-        f["vvel"] += 7.0
-        idz.carve_dry_air(f, tr)
+    f, xlen, ylen, _, _ = build_inputs(nens, nx, ny, nz, tr, zint, consts, mag=0.5, dry_air=limiter, **ANISO.get(case, {}))
     return f, xlen, ylen
 
 
@@ -60,7 +68,9 @@ def _run(case, f, xlen, ylen, yz, xk, tile=(0, 0, 0), nens_override=None, ftile=
     if nens_override:
         nens = nens_override
     zi = np.asarray(zint)[:, None] * np.ones((1, nens))
-    if per_ens:
+    if per_ens == "mod16":      # (128 members: grids stretched by 1 + 0.01 e leave the sounding)
+        zi = zi * (1 + 0.01 * (np.arange(nens) % 16))[None, :]
+    elif per_ens:
         zi = zi * (1 + 0.01 * np.arange(nens))[None, :]
     coupler = PamCoupler("cuda:0")
     coupler.set_option("crm_dt", 2.0)
@@ -117,6 +127,8 @@ def test_flat_lanes_and_tile_kernels_equal_member_lanes_and_sweeps_bit_for_bit(c
     for yz, xk, tile, ftile, fusion in variants:
         n1, got, m1, _ = _run(case, f, xlen, ylen, yz, xk, tile, ftile=ftile, fusion=fusion, xex="lds" if fusion else "auto")
         assert m1["yz_flat"] == (yz == "flat") and m1["x_tiles"] == (xk == "tile"), m1
+        if case in ANISO:
+            print(case, ANISO[case], (yz, xk, tile, ftile, fusion), "->", m1)
         if yz == "flat" and ftile[0] != "auto":
             assert m1["yz_tile_kernel"] == (ftile[0] == "tile"), m1
         assert n0 == n1
@@ -144,6 +156,8 @@ def test_wavefront_shuffle_exchange_equals_the_lds_exchange_and_the_sweeps_bit_f
                 n1, got, m1, _ = _run(case, f, xlen, ylen, "flat", "tile", tile, ftile=ftile, xex=xex.split("+")[0],
                                       fusion="beside" if "+" in xex else None)
                 assert m1["x_tiles"] and m1["x_shuffles"] == (xex != "lds"), (xex, m1)
+                if case in ANISO:
+                    print(case, ANISO[case], (tile, ftile, xex), "->", m1)
                 assert n1 == n0
                 outs[xex] = got
             for xex, got in outs.items():
@@ -249,7 +263,8 @@ def test_tile_geometry_puts_one_workgroup_on_every_cu_when_the_grid_allows():
         assert g["lpb"] == want and g["halo"] == 0, (nens, g)
 
 
-@pytest.mark.parametrize("case", ["nens1_c2grid_slab", "nens1_ref_shape_nt4", "nens8_nt4_B", "nens5_vapour_limited", "nens40_vapour_limited_B"])
+@pytest.mark.parametrize("case", ["nens1_c2grid_slab", "nens1_ref_shape_nt4", "nens8_nt4_B", "nens5_vapour_limited", "nens40_vapour_limited_B",
+                                  "aniso_nens8_nt4_B_diag", "aniso_nens5_vapour_limited_diag"])
 def test_time_step_replayed_from_a_hip_graph_equals_eager_launches_bit_for_bit(case):
     """pam_amd_awfl_set_graph_replay: the whole timeStep captured once per (coupler arrays, sub-cycle count, buffer parity) and replayed.
     Seven steps with two crm_dt values: graphs are captured, reused, and both parities of the three-buffer rotation occur (odd and even

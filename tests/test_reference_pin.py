@@ -9,7 +9,8 @@ bodies (tests/emu) and the HIP path.
  * Live reference (when oracle/_ref/ was built): the oracle against the reference on the hydrostatic outputs of both balance
    modes and of the GCM column, the vertical matrices on uniform / stretched / per-member grids, compute_time_step, a timeStep of
    every make_golden case, the D1 replay count, and a seeded sweep over test_fuzz_parity.draw_case (PAM_AMD_REF_SEEDS=N seeds,
-   default 16).  All bit for bit.
+   default 16; the odd seeds that draw a 3-D grid run it with dx != dy and the sounding's shear along y or along both, as three of
+   the make_golden cases do).  All bit for bit.
  * Coupler modules: the oracle and tests/moist_surface_ref.py against the reference's sponge_layer, GCM forcing (three hole-filling
    paths of the liquid, and two states of tests/gcm_forcing_cases.py: every species in the level pass and the fallback), broadcasts, saturation_adjustment (Kessler and P3 tracer sets), surface friction, Kessler (one and several sub-cycles)
    and supercell_init on L60 -- bit for bit, through tests/golden/ref_mod_*.npz and live.
@@ -32,6 +33,7 @@ import pytest
 from oracle import awfl_oracle as ao
 from oracle import pam_ref
 from pam_amd import idealized as idz
+from parity_cases import build_inputs
 from parity_gate import compare, noise_floor
 from test_emu_parity import assert_within_floor
 
@@ -243,19 +245,10 @@ def test_oracle_matches_reference_vertical_matrices(grid):
 
 def _fuzz_inputs(c):
     """inputs of a test_fuzz_parity draw, exactly as test_fuzz_parity.run_case builds them"""
-    nens, nx, ny, nz, tr, consts = c["nens"], c["nx"], c["ny"], c["nz"], c["tracers"], c["consts"]
-    xlen = nx * c["dxy"]
-    ylen = ny * c["dxy"] if ny > 1 else xlen
-    f = idz.supercell_fields(nens, nx, ny, nz, c["zint"], consts=consts, tracers=tr, magnitude=0.5, id0=c["seed"])
-    idz.add_tracer_blobs(f, tr, xlen, ylen, c["zint"])
-    if c["dry_air"]:
-        f["uvel"] -= 25.0
-        f["vvel"] += 7.0 if ny > 1 else 0.0
-        idz.carve_dry_air(f, tr)
-    zi = np.asarray(c["zint"])[:, None] * np.ones((1, nens))
-    if c["per_ens"]:
-        zi = zi * (1 + 0.01 * np.arange(nens))[None, :]
-    return f, xlen, ylen, np.diff(zi, axis=0)
+    f, xlen, ylen, _, dz = build_inputs(c["nens"], c["nx"], c["ny"], c["nz"], c["tracers"], c["zint"], c["consts"], per_ens=c["per_ens"],
+                                        mag=0.5, dxy=c["dxy"], dry_air=c["dry_air"], dy=c.get("dy"), flow=c.get("flow", "x"),
+                                        id0=c["seed"])
+    return f, xlen, ylen, dz
 
 
 def _small_draw(seed):
@@ -264,8 +257,15 @@ def _small_draw(seed):
     while True:                # the same draws as the GPU sweep, those above MAX_CELLS left out (the next seed instead)
         c = tfp.draw_case(s)
         if c["nens"] * c["nx"] * c["ny"] * c["nz"] <= MAX_CELLS:
-            return c
+            break
         s += 100000
+    # every other seed: the same draw on a grid with dx != dy and with the shear along y or along both, where it is 3-D (from a
+    # generator of its own: the draws above stay what they were)
+    if seed % 2 and c["ny"] > 1:
+        rng = np.random.default_rng(9000011 * seed + 37)
+        c["dy"] = c["dxy"] * float(rng.choice(tfp.ANISO_RATIOS))
+        c["flow"] = str(rng.choice(["y", "diag"]))
+    return c
 
 
 def _run(cls, c, f, xlen, ylen, dz, **kw):

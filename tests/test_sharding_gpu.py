@@ -8,17 +8,18 @@ import numpy as np
 import pytest
 
 from pam_amd import idealized as idz
+from parity_cases import build_inputs
 
 pytestmark = pytest.mark.gpu
 
 
-def _mk(f, lo, hi, nx, ny, nz, zint, tr):
+def _mk(f, lo, hi, nx, ny, nz, zint, tr, xlen=None, ylen=None):
     from pam_amd import Dycore, PamCoupler
     nens = hi - lo
     c = PamCoupler("cuda:0")
     c.set_option("crm_dt", 1.0)
     c.allocate_coupler_state(nz, ny, nx, nens)
-    c.set_grid(nx * 500.0, (ny if ny > 1 else nx) * 500.0, zint)
+    c.set_grid(nx * 500.0 if xlen is None else xlen, (ny if ny > 1 else nx) * 500.0 if ylen is None else ylen, zint)
     for n, p, m in tr:
         c.add_tracer(n, "", p, m)
     d = Dycore()
@@ -228,4 +229,95 @@ def test_random_shards_equal_the_unsharded_run_bit_for_bit(seed):
         assert np.isfinite(w[k]).all(), (what, k)
         assert np.array_equal(np.concatenate([x[k] for x in s], axis=-1), w[k]), (what, k)
     for c, d in [(whole_c, whole_d)] + shards:
+        d.finalize(c)
+
+
+# ---- the same three checks on a grid with dx != dy and the sounding's shear along both x and y (parity_cases.build_inputs) ----------
+ANISO_SHAPE = (6, 5, 8)        # nx, ny, nz
+
+
+def _aniso_inputs(nens, tr, dxy, dy, dry_air=False):
+    nx, ny, nz = ANISO_SHAPE
+    zint = idz.stretched_interfaces(nz, 12000.0)
+    f, xlen, ylen, _, _ = build_inputs(nens, nx, ny, nz, tr, zint, mag=0.5, dxy=dxy, dy=dy, flow="diag", dry_air=dry_air)
+    assert xlen / nx != ylen / ny and np.abs(f["vvel"]).max() >= 0.5 * np.abs(f["uvel"]).max()
+    return f, zint, xlen, ylen
+
+
+def _mk_aniso(f, zint, xlen, ylen, tr, lo=0, hi=None):
+    nx, ny, nz = ANISO_SHAPE
+    c, d = _mk(f, lo, f["temp"].shape[-1] if hi is None else hi, nx, ny, nz, zint, tr, xlen, ylen)
+    print("members %d..%s, dx %g, dy %g ->" % (lo, hi, xlen / nx, ylen / ny), d.get_lane_mapping())
+    return c, d
+
+
+def test_anisotropic_shards_with_reduced_dt_equal_the_unsharded_run_bit_for_bit():
+    """70 members with vapour limited, cut into 6 + 64: the small shard resolves flat lanes and tile kernels, the other member lanes"""
+    import torch
+    tr = idz.TRACERS_KESSLER_SHOC
+    f, zint, xlen, ylen = _aniso_inputs(70, tr, 800.0, 500.0, dry_air=True)
+    f["vvel"][..., 3] += 40.0                      # member 3 (first shard) limits the CFL step of the whole ensemble, through dy
+    whole_c, whole_d = _mk_aniso(f, zint, xlen, ylen, tr)
+    ranges = [(0, 6), (6, 70)]
+    shards = [_mk_aniso(f, zint, xlen, ylen, tr, lo, hi) for lo, hi in ranges]
+    maps = [d.get_lane_mapping() for c, d in shards]
+    assert maps[0]["yz_flat"] and maps[0]["x_tiles"] and not maps[1]["yz_flat"] and not maps[1]["x_tiles"], maps
+    for _ in range(2):
+        n_whole = whole_d.timeStep(whole_c)
+        dts = [d.compute_time_step(c) for c, d in shards]
+        assert dts[0] < dts[1]
+        assert [d.timeStep(c, dt_dyn_hint=min(dts)) for c, d in shards] == [n_whole, n_whole]
+    torch.cuda.synchronize()
+    w = whole_c.dump_fields()
+    s = [c.dump_fields() for c, d in shards]
+    for k in ("density_dry", "uvel", "vvel", "wvel", "temp", "tracers"):
+        assert np.isfinite(w[k]).all(), k
+        assert np.array_equal(np.concatenate([x[k] for x in s], axis=-1), w[k]), k
+    for c, d in [(whole_c, whole_d)] + shards:
+        d.finalize(c)
+
+
+def test_anisotropic_tracer_groupings_equal_pairs_bit_for_bit():
+    """test_four_tracers_per_wavefront_equal_pairs_bit_for_bit on a 3-D grid with dx != dy: nine further tracers, 128 members"""
+    import torch
+    tr = idz.TRACERS_P3_SHOC
+    f, zint, xlen, ylen = _aniso_inputs(128, tr, 500.0, 800.0)
+    hs = [_mk_aniso(f, zint, xlen, ylen, tr) for _ in range(4)]
+    for c, d in hs:
+        d.set_launch_tuning(0, -1, 1 << 30)          # phase 1 of the tracer sweeps as a launch of its own
+    hs[0][1].set_tracer_grouping(2)
+    hs[1][1].set_tracer_grouping(4)
+    hs[2][1].set_tracer_grouping(2, prefetch=True)
+    hs[3][1].set_tracer_grouping(0)
+    for _ in range(2):
+        n = [d.timeStep(c) for c, d in hs]
+        assert n == [n[0]] * 4
+    torch.cuda.synchronize()
+    out = [c.dump_fields() for c, d in hs]
+    for k in ("density_dry", "uvel", "vvel", "wvel", "temp", "tracers"):
+        assert np.isfinite(out[0][k]).all(), k
+        for o in out[1:]:
+            assert np.array_equal(out[0][k], o[k]), k
+    for c, d in hs:
+        d.finalize(c)
+
+
+def test_anisotropic_results_do_not_depend_on_the_launch_tuning():
+    """the launch-shape thresholds of test_two_handles_in_one_process_tuned_differently_do_not_reshape_each_other, per handle, on a 3-D
+    grid with dx != dy: whole lines / one-phase sweeps / inline tracers, and shortest spans / two-phase sweeps / tracers apart"""
+    import torch
+    tr = idz.TRACERS_KESSLER_SHOC
+    f, zint, xlen, ylen = _aniso_inputs(128, tr, 1000.0, 250.0)
+    hs = [_mk_aniso(f, zint, xlen, ylen, tr) for _ in range(3)]
+    hs[1][1].set_launch_tuning(64, 0, 0)
+    hs[2][1].set_launch_tuning(1 << 20, 1 << 30, 1 << 30)
+    for _ in range(2):
+        n = [d.timeStep(c) for c, d in hs]
+        assert n == [n[0]] * 3
+    torch.cuda.synchronize()
+    out = [c.dump_fields() for c, d in hs]
+    for k in ("density_dry", "uvel", "vvel", "wvel", "temp", "tracers"):
+        assert np.isfinite(out[0][k]).all(), k
+        assert np.array_equal(out[1][k], out[0][k]) and np.array_equal(out[2][k], out[0][k]), k
+    for c, d in hs:
         d.finalize(c)

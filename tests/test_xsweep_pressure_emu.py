@@ -14,6 +14,7 @@ import pytest
 
 import emu_harness as eh
 from pam_amd import idealized as idz
+from parity_cases import build_inputs
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "emu", "xsweep_pressure_emu.cpp")
@@ -25,6 +26,9 @@ FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "tracers")
 SHAPES = {
     "nx32_3d_span4_limited": (3, 32, 5, 4, True, False, True),
     "nx3_2d_whole_perens_B": (2, 3, 1, 0, False, True, False),
+    # dx != dy with the sounding's shear along y (an eighth element: options of parity_cases.build_inputs)
+    "aniso_800x500_nx9_3d_span4_limited_flowy": (3, 9, 5, 4, True, False, True, dict(dxy=800.0, dy=500.0, flow="y")),
+    "aniso_500x800_nx6_3d_whole_perens_B_flowy": (2, 6, 5, 0, False, True, False, dict(dxy=500.0, dy=800.0, flow="y")),
 }
 
 
@@ -61,17 +65,11 @@ class _Emu(eh.EmuDycore):
 
 
 def _inputs(shape):
-    nens, nx, ny, span, mode_a, per_ens, limited = SHAPES[shape]
+    nens, nx, ny, span, mode_a, per_ens, limited = SHAPES[shape][:7]
     tr = idz.TRACERS_NONE
     zint = idz.stretched_interfaces(NZ, 6000.0)
-    xlen = nx * 500.0
-    ylen = ny * 500.0 if ny > 1 else xlen
-    f = idz.supercell_fields(nens, nx, ny, NZ, zint, tracers=tr, magnitude=0.5)
-    idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
-    if limited:
-        f["uvel"] -= 25.0
-        f["vvel"] += 7.0
-        idz.carve_dry_air(f, tr)
+    f, xlen, ylen, _, _ = build_inputs(nens, nx, ny, NZ, tr, zint, mag=0.5, dry_air=limited,
+                                       **(SHAPES[shape][7] if len(SHAPES[shape]) > 7 else {}))
     dz = np.diff(zint)[:, None] * np.ones((1, nens))
     if per_ens:
         dz = dz * (1 + 0.01 * np.arange(nens))[None, :]
@@ -109,6 +107,28 @@ def test_stash_parameter_leaves_the_emulation_unchanged_and_in_sweep_pressure_ha
     assert np.isfinite(pa[5, 3:-3]).all()
     assert np.array_equal(pa, pb, equal_nan=True)
     assert np.array_equal(pa, pc, equal_nan=True)
+
+
+@pytest.mark.parametrize("shape", sorted(k for k in SHAPES if len(SHAPES[k]) > 7))
+def test_in_sweep_pressure_matches_the_oracle_on_an_anisotropic_grid(lib, shape):
+    """the bit-equality above holds a y difference divided by dx too (every build has it); here the in-sweep form is held to the
+    oracle through the parity gate (tests/parity_gate.py) at dx != dy with the shear along y"""
+    from oracle import awfl_oracle as ao
+    from parity_gate import compare, noise_floor
+    args, f = _inputs(shape)
+    mode_a = SHAPES[shape][4]
+    assert args[5] / args[2] != args[4] / args[1] and np.abs(f["vvel"]).max() >= 0.5 * np.abs(f["uvel"]).max()
+    ncyc, got, _ = _run(lambda *x: _Emu(lib, *x), args, f, shape, True)
+
+    def run_oracle(ff):
+        o = ao.OracleDycore(*args)
+        o.set_grav_balance(mode_a)
+        o.declare_current_profile_as_hydrostatic(ff)
+        return [o.time_step(ff, crm_dt)[0] for crm_dt in (2.0, 0.7)]
+    exp = copy.deepcopy(f)
+    assert run_oracle(exp) == ncyc
+    names = idz.tracer_flags(idz.TRACERS_NONE)[0]
+    compare(got, exp, names, sum(ncyc), floor=noise_floor(run_oracle, f, names, 0, base=exp))
 
 
 def test_in_sweep_pressure_is_refused_where_the_device_keeps_the_separate_pass(lib):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from pam_amd import idealized as idz
+from parity_cases import build_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +24,14 @@ CASES = {
     "nx32_2d_64_span4_limited_B": (64, 32, 1, 4, 1, False, True, True, True),
     # an uncut line longer than the stash: the separate pass stays
     "nx33_3d_130_fallback_B": (130, 33, 5, WHOLE, 2, False, False, False, False),
+    # dx != dy (ANISO below) with the sounding's shear along y: spans and a ragged block with the limiter across the dry rows in y;
+    # whole lines, own grids, mode B
+    "aniso_nx8_3d_70_span4_limited_flowy": (70, 8, 5, 4, 1, True, False, True, True),
+    "aniso_nx6_3d_64_perens_B_flowy": (64, 6, 5, WHOLE, 1, False, True, False, True),
 }
+# options of parity_cases.build_inputs for the cases that are not on the 500 m x 500 m grid with the shear along x
+ANISO = {"aniso_nx8_3d_70_span4_limited_flowy": dict(dxy=800.0, dy=500.0, flow="y"),
+         "aniso_nx6_3d_64_perens_B_flowy": dict(dxy=500.0, dy=800.0, flow="y")}
 FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "water_vapor")
 
 
@@ -33,17 +41,10 @@ def _run(case, fused, tail):
     nens, nx, ny, span, chunks, mode_a, per_ens, limited, _ = CASES[case]
     tr, consts = idz.TRACERS_NONE, idz.CONSTS_DEFAULT
     zint = idz.stretched_interfaces(NZ, 6000.0)
-    xlen = nx * 500.0
-    ylen = ny * 500.0 if ny > 1 else xlen
-    f = idz.supercell_fields(nens, nx, ny, NZ, zint, consts=consts, tracers=tr, magnitude=0.5)
-    idz.add_tracer_blobs(f, tr, xlen, ylen, zint)
-    if limited:
-        f["uvel"] -= 25.0
-        f["vvel"] += 7.0
-        idz.carve_dry_air(f, tr)
-    zi = np.asarray(zint)[:, None] * np.ones((1, nens))
-    if per_ens:
-        zi = zi * (1 + 0.01 * (np.arange(nens) % 16) + 1.0e-4 * (np.arange(nens) // 16))[None, :]
+    f, xlen, ylen, zi, _ = build_inputs(nens, nx, ny, NZ, tr, zint, consts, per_ens="mod16" if per_ens else False, mag=0.5,
+                                        dry_air=limited, **ANISO.get(case, {}))
+    if limited and ny == 1:
+        f["vvel"] += 7.0      # (the 2-D limited case has always carried the 3-D cases' 7 m/s in its inert v)
     coupler = PamCoupler("cuda:0")
     coupler.set_option("crm_dt", 2.0)
     for k, v in consts.items():
