@@ -68,6 +68,9 @@
 #include "physics/sgs/smag_amd/SGS.h"
 #undef PAM_SGS_CLASS
 #include "physics/radiation/forced_amd/radiation.h"
+#define PAM_RAD_CLASS RadiationGray     // the driver holds both Radiation classes and picks at run time (--radiation-gray)
+#include "physics/radiation/gray_amd/radiation.h"
+#undef PAM_RAD_CLASS
 
 #include <map>
 #include <sstream>
@@ -311,7 +314,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
-//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
+//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--radiation-gray [EVERY]] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
 //          [--flux-profiles PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
@@ -419,6 +422,11 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //   --sfc-fluxes SHF LHF       with --sgs-smag: option sgs_smag_surface_fluxes; "sfc_shf" and "sfc_lhf" are filled uniformly, once, with
 //                              SHF and LHF (W/m2, positive upward) and enter row 0 of temp and of the vapour in every SGS step.  Both
 //                              compose with every other flag
+//   --radiation-gray [EVERY]   the native grey two-stream longwave scheme (physics/radiation/gray_amd/radiation.h) in the radiation slot of
+//                              the CRM loop, where --radiation puts the forced class: its timeStep every CRM step before the dycore, the
+//                              fluxes recomputed on every EVERY-th step (1 unless given) and the stored heating applied between.  One
+//                              "radiation gray:" line per output step with the ensemble-mean OLR and surface downward flux.  Composes
+//                              with every other flag but --radiation: there is one slot
 //   --vt RATE PATH [--vt-u] [--vt-limit L]   CRM variance transport (modules/variance_transport.h): modules::vt_init at the start of every GCM
 //                              step; there is no GCM here, so vt_tend_x = RATE vt_var_start_x (a relative growth rate per second) for
 //                              that GCM step; modules::vt_apply_forcing LAST in every CRM step, after the clock has advanced, with dt =
@@ -446,7 +454,8 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              prof_flux_v and prof_tke, printed with %.17g; nothing else of the run changes.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false;
+  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false;
+  int radiation_gray_every = 1;
   double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0, sfc_shf = 0, sfc_lhf = 0;
   int handoff_rad_nx = 0, handoff_rad_ny = 0;
   std::string handoff_path;
@@ -555,6 +564,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     SGS sgs;
     SGSSmagorinsky sgs_smag;
     Radiation rad;
+    RadiationGray rad_gray;
     micro.init(coupler);                                                     // driver.cpp:189
     if (mods.sgs_smag) {                                                     // --sgs-smag: the native closure in the SGS slot
       coupler.set_option<real>("sgs_smag_cs", mods.sgs_cs);
@@ -573,6 +583,10 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       }
     } else sgs.init(coupler);                                                // driver.cpp:190 (the reference's CI build: SHOC with P3; their numerics are out of scope, their coupling layers are physics/sgs/shoc_amd and physics/micro/p3_amd)
     dycore.init(coupler);                                                    // driver.cpp:191
+    if (mods.radiation_gray) {                                               // --radiation-gray: the native scheme in the radiation slot
+      coupler.set_option<int>("rad_gray_every", mods.radiation_gray_every);
+      rad_gray.init(coupler);
+    }
     if (mods.radiation) {
       coupler.set_option<int>("rad_nx", mods.rad_nx);
       coupler.set_option<int>("rad_ny", mods.rad_ny);
@@ -676,6 +690,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         const bool accel = clock.accelerating();
         if (accel) coupler.run_module("msa_diagnose", modules::msa_diagnose);
         if (mods.radiation) coupler.run_module("radiation", [&](pam::PamCoupler &c) { rad.timeStep(c); });
+        if (mods.radiation_gray) coupler.run_module("radiation", [&](pam::PamCoupler &c) { rad_gray.timeStep(c); });
         coupler.run_module("dycore", [&](pam::PamCoupler &c) { dycore.timeStep(c); });       // driver.cpp:248
         substeps += dycore.last_ncycles();
         if (check) {
@@ -711,6 +726,16 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
           if (!(maxw == maxw)) maxw = INFINITY;
           maxw_all = std::max(maxw_all, maxw);
           std::printf("Etime , dtphys, maxw: %g , %g , %10.6g\n", etime_gcm, dt_crm_phys, maxw);
+          if (mods.radiation_gray) {                                         // the ensemble-mean (and column-mean) fluxes of the last computation
+            const size_t n2 = (size_t)crm_ny * crm_nx * nens;
+            std::vector<real> olr(n2), down(n2);
+            if (hipMemcpy(olr.data(), dm.get<real const, 3>("rad_olr").data(), n2 * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(down.data(), dm.get<real const, 3>("rad_lw_down_sfc").data(), n2 * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess)
+              endrun("memcpy");
+            double so = 0, sd = 0;
+            for (size_t c = 0; c < n2; c++) { so += olr[c]; sd += down[c]; }
+            std::printf("radiation gray: etime %g , olr %.9g , lw_down_sfc %.9g\n", etime_gcm, so / n2, sd / n2);
+          }
           char t[64];
           std::snprintf(t, sizeof(t), "%s%.6g", maxw_series.empty() ? "" : ",", maxw);
           maxw_series += t;
@@ -985,6 +1010,11 @@ int main(int argc, char **argv) {
       else if (o == "--vt-limit" && b + 1 < argc - 1) mods.vt_limit = std::atof(argv[++b]);
       else if (o == "--hyperdiff" && b + 1 < argc - 1) { mods.hyperdiff = true; mods.hyperdiff_tau = std::atof(argv[++b]); }
       else if (o == "--sgs-smag" && b + 2 < argc - 1) { mods.sgs_smag = true; mods.sgs_cs = std::atof(argv[++b]); mods.sgs_prandtl = std::atof(argv[++b]); }
+      else if (o == "--radiation-gray") {
+        mods.radiation_gray = true;
+        const std::string n(b + 1 < argc - 1 ? argv[b + 1] : "");                // the optional EVERY: an argument of digits only
+        if (!n.empty() && n.find_first_not_of("0123456789") == std::string::npos) mods.radiation_gray_every = std::atoi(argv[++b]);
+      }
       else if (o == "--sgs-moist") mods.sgs_moist = true;
       else if (o == "--sfc-fluxes" && b + 2 < argc - 1) { mods.sfc_fluxes = true; mods.sfc_shf = std::atof(argv[++b]); mods.sfc_lhf = std::atof(argv[++b]); }
       else if (o == "--gcm-handoff" && b + 3 < argc - 1) {
@@ -997,9 +1027,11 @@ int main(int argc, char **argv) {
       else if (o == "--flux-profiles" && b + 1 < argc - 1) mods.flux_profiles = argv[++b];
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] "
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--radiation-gray [EVERY]] "
                "[--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->");
     }
+    if (mods.radiation_gray && mods.radiation) die("--radiation-gray and --radiation both fill the one radiation slot: give one of them");
+    if (mods.radiation_gray && mods.radiation_gray_every < 1) die("--radiation-gray EVERY must be >= 1");
     if ((mods.sgs_moist || mods.sfc_fluxes) && !mods.sgs_smag) die("--sgs-moist and --sfc-fluxes need --sgs-smag CS PRANDTL");
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }

@@ -730,6 +730,44 @@ int pam_amd_sgs_smag_diffuse_fluxes(int nens, int nx, int ny, int nz, double *uv
                                     const double *zint, const double *zmid, const double *sfc_flx_u, const double *sfc_flx_v, double dt,
                                     double grav, double cp_d, const double *sfc_shf, const double *sfc_lhf, double latvap, void *stream);
 
+/* The native radiation scheme: a grey two-stream longwave (Schwarzschild) solve along every column, as idealised GCMs use it (Frierson,
+ * Held and Zurita-Gotor 2006), with the optical depth built from the water the CRM carries -- the radiation that needs no external
+ * library (as Kessler is the microphysics and Smagorinsky the SGS closure that need none).  Longwave only, one band, no scattering.  Not
+ * part of the reference tree; the contract is this project's and is restated in numpy in tests/grayrad_ref.py,
+ * which the kernel matches bit for bit.
+ * temp, rho_d (density_dry), rho_v (water_vapor), liquid[num_liquid] and ice[num_ice] (HOST arrays of DEVICE pointers to the cloud-liquid
+ * and the cloud-ice densities, 0..2 entries each) are (nz,ny,nx,nens), members fastest; zint (nz+1,nens) is each member's own grid;
+ * sfc_temp (ny,nx,nens) may be NULL: the surface then radiates at the lowest level's temp as it is at entry.  k_d, k_v, k_l, k_i are mass
+ * absorption coefficients in m2/kg with the diffusivity factor folded in; lw_down_top is the downward flux at the model top in W/m2.
+ * Everything is fp64, every operation is rounded on its own (no fma), every division is a true IEEE division, and the association is
+ * as written.  Per cell, level k counted from the ground:
+ *   dz = zint(k+1) - zint(k); L = 0.0 for an empty liquid table, liquid[0], or liquid[0] + liquid[1]; I likewise from the ice table;
+ *   c = k_d rho_d + k_v rho_v; c = c + k_l L; c = c + k_i I; dtau = c dz;
+ *   t = exp_c(-dtau), the exponential of pam_amd_sgs_smag_coefficients_moist above: exactly 1.0 at dtau = 0 and exactly 0.0 beyond 700;
+ *   t2 = temp temp; B = sigma (t2 t2); e = B (1.0 - t).
+ * Downward: D(nz) = lw_down_top; D(k) = D(k+1) t(k) + e(k) for k = nz-1 .. 0.  Upward: Ts2 = Ts Ts; U(0) = sigma (Ts2 Ts2); U(k+1) =
+ * U(k) t(k) + e(k) for k = 0 .. nz-1.  rad_heating(k) = ((D(k+1) - D(k)) + (U(k) - U(k+1))) / ((cp_d (rho_d + rho_v)) dz) in K/s, and where
+ * dt != 0 temp(k) = temp(k) + rad_heating(k) dt; with dt == 0 the call diagnoses only and temp keeps its bits.  Every t, e and Ts is
+ * formed from temp as it is at entry.
+ * Outputs: temp in place; rad_heating (nz,ny,nx,nens); rad_olr = U(nz), rad_lw_down_sfc = D(0) and rad_lw_up_sfc = U(0), each
+ * (ny,nx,nens).  For a finite column S cp_d (rho_d + rho_v) dz rad_heating = (U(0) - D(0)) - (U(nz) - D(nz)) to rounding; with all four
+ * coefficients 0.0 rad_heating is 0.0 everywhere and rad_olr has the bits of rad_lw_up_sfc.  Nothing is refused because of a value in a
+ * field; a NaN goes where the two recurrences carry it and no further: no other column sees it.
+ * One launch: a thread owns a (column, member) and makes both sweeps; the downward sweep parks D(k+1) - D(k) in rad_heating(k) and the
+ * upward sweep finishes it, so there is no scratch and no second launch.  No atomics; the same bits from run to run and for any split
+ * of the members over calls (with the matching slices of zint).
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: nens, nx, ny or nz < 1; ny nx beyond 2^31 - 1 (ny nx nens
+ * beyond the launch grid); a NULL pointer other than sfc_temp; num_liquid or num_ice outside 0..2, a NULL table with a positive count or
+ * a NULL entry; k_d, k_v, k_l, k_i, sigma, lw_down_top or dt not finite or negative; cp_d not finite and positive; an output that
+ * overlaps an input or another output.  Without a device a call whose arguments pass returns PAM_AMD_ENOGPU.
+ * pam_amd_radiation_gray_debug_wide_index is a test switch like pam_amd_shoc_debug_wide_index: nonzero forces the instance with 64-bit
+ * element offsets, which is otherwise taken from 2^29 cells on. */
+int pam_amd_radiation_gray(int nens, int nx, int ny, int nz, double *temp, const double *rho_d, const double *rho_v, int num_liquid,
+                           const double *const *liquid, int num_ice, const double *const *ice, const double *zint, const double *sfc_temp,
+                           double k_d, double k_v, double k_l, double k_i, double sigma, double cp_d, double lw_down_top, double dt,
+                           double *rad_heating, double *rad_olr, double *rad_lw_down_sfc, double *rad_lw_up_sfc, void *stream);
+int pam_amd_radiation_gray_debug_wide_index(int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4010,3 +4010,90 @@ extern "C" int pam_amd_sgs_smag_diffuse_fluxes(int nens, int nx, int ny, int nz,
   return sgs_diffuse("sgs_smag_diffuse_fluxes", true, nens, nx, ny, nz, uvel, vvel, wvel, temp, num_tracers, tracers, rho_d, rho_v, tk, tkh, zint,
                      zmid, sfc_flx_u, sfc_flx_v, dt, grav, cp_d, sfc_shf, sfc_lhf, latvap, stream);
 }
+
+// ------------------------------------------------------------------------------------------------
+// The native grey two-stream longwave radiation scheme: the optical depth of every cell from the dry air, the vapour and the cloud
+// condensate the CRM carries, a downward and an upward Schwarzschild sweep along the column, the heating rate and its application to
+// temp.  Not in the reference tree; the contract is in include/pam_amd_modules.h and DESIGN.md section 8, its arithmetic in
+// grayrad_device.h.  ONE launch: a thread owns a (column, member), members and then x across the lanes, so every level's access is a
+// contiguous line whatever nens is.  The downward sweep parks D[k+1] - D[k] in rad_heating, the upward sweep forms t and e of the cell
+// again from the fields (temp(k) is replaced only after it has been read), finishes rad_heating(k) and updates temp(k): no scratch, no
+// LDS, no second launch, no atomics.  IDX: unsigned while a field is below 2^29 doubles (every byte offset fits 32 bits).
+#include "grayrad_device.h"
+
+namespace {
+namespace gr = pama::grayrad;
+constexpr int GRAYRAD_THREADS = 64;                      // one wavefront per workgroup: 4096 workgroups at C4's 32 x 8192 columns
+constexpr long long GRAYRAD_NARROW_CELLS = 1ll << 29;    // fields from this size on take the long long instance
+
+// grid (ceil(ny nx nens / 64)), block 64: thread t = (j nx + i) nens + e
+template <class IDX>
+__global__ void __launch_bounds__(GRAYRAD_THREADS) grayrad_kernel(int nens, long long level, int nz, double *temp, gr::Fields F,
+                                                                  const double *__restrict__ zint, const double *sfc_temp, gr::Params P,
+                                                                  double *heating, double *__restrict__ olr, double *__restrict__ down_sfc,
+                                                                  double *__restrict__ up_sfc) {
+  const long long t = (long long)blockIdx.x * GRAYRAD_THREADS + (long long)threadIdx.x;
+  if (t >= level) return;
+  const int e = (int)(t % nens);
+  gr::column<IDX>(temp, F, zint + e, sfc_temp, (IDX)t, (IDX)level, (IDX)nens, nz, P, heating, olr, down_sfc, up_sfc);
+}
+
+bool g_grayrad_force_wide = false;   // pam_amd_radiation_gray_debug_wide_index: tests run the long long instance at small sizes
+
+bool grayrad_coefficient(double v) { return std::isfinite(v) && v >= 0; }
+}  // namespace
+
+extern "C" int pam_amd_radiation_gray_debug_wide_index(int on) {
+  g_grayrad_force_wide = on != 0;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_radiation_gray(int nens, int nx, int ny, int nz, double *temp, const double *rho_d, const double *rho_v,
+                                      int num_liquid, const double *const *liquid, int num_ice, const double *const *ice, const double *zint,
+                                      const double *sfc_temp, double k_d, double k_v, double k_l, double k_i, double sigma, double cp_d,
+                                      double lw_down_top, double dt, double *rad_heating, double *rad_olr, double *rad_lw_down_sfc,
+                                      double *rad_lw_up_sfc, void *stream) {
+  const char *who = "radiation_gray";
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return module_error(who, "nens, nx, ny and nz must be >= 1");
+  if ((long long)nx * ny > 0x7fffffffLL) return module_error(who, "ny x nx exceeds 2^31 - 1 columns");
+  const long long level = (long long)nx * ny * nens, cells = level * nz;
+  if ((level + GRAYRAD_THREADS - 1) / GRAYRAD_THREADS > 0x7fffffffLL) return module_error(who, "ny x nx x nens exceeds the grid");
+  if (num_liquid < 0 || num_liquid > gr::MAX_SPECIES) return module_error(who, "num_liquid must be in [0, 2]");
+  if (num_ice < 0 || num_ice > gr::MAX_SPECIES) return module_error(who, "num_ice must be in [0, 2]");
+  if ((num_liquid > 0 && !liquid) || (num_ice > 0 && !ice)) return module_error(who, "null condensate table");
+  if (!temp || !rho_d || !rho_v || !zint || !rad_heating || !rad_olr || !rad_lw_down_sfc || !rad_lw_up_sfc) return module_error(who, "null pointer");
+  for (int i = 0; i < num_liquid; i++)
+    if (!liquid[i]) return module_error(who, "null liquid pointer");
+  for (int i = 0; i < num_ice; i++)
+    if (!ice[i]) return module_error(who, "null ice pointer");
+  if (!grayrad_coefficient(k_d) || !grayrad_coefficient(k_v) || !grayrad_coefficient(k_l) || !grayrad_coefficient(k_i) ||
+      !grayrad_coefficient(sigma) || !grayrad_coefficient(lw_down_top) || !grayrad_coefficient(dt))
+    return module_error(who, "k_d, k_v, k_l, k_i, sigma, lw_down_top and dt must be finite and >= 0");
+  if (!std::isfinite(cp_d) || !(cp_d > 0)) return module_error(who, "cp_d must be finite and positive");
+  std::vector<Span> spans;
+  for (const double *p : {rho_d, rho_v}) spans.push_back({p, cells, false});
+  for (int i = 0; i < num_liquid; i++) spans.push_back({liquid[i], cells, false});
+  for (int i = 0; i < num_ice; i++) spans.push_back({ice[i], cells, false});
+  spans.push_back({zint, (long long)(nz + 1) * nens, false});
+  if (sfc_temp) spans.push_back({sfc_temp, level, false});
+  for (double *p : {temp, rad_heating}) spans.push_back({p, cells, true});
+  for (double *p : {rad_olr, rad_lw_down_sfc, rad_lw_up_sfc}) spans.push_back({p, level, true});
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if (int rc = require_device(who)) return rc;
+
+  gr::Fields F;
+  F.rho_d = rho_d; F.rho_v = rho_v;
+  for (int i = 0; i < gr::MAX_SPECIES; i++) {
+    F.liquid[i] = i < num_liquid ? liquid[i] : nullptr;
+    F.ice[i] = i < num_ice ? ice[i] : nullptr;
+  }
+  const gr::Params P{k_d, k_v, k_l, k_i, sigma, cp_d, lw_down_top, dt, num_liquid, num_ice};
+  const dim3 grid((unsigned)((level + GRAYRAD_THREADS - 1) / GRAYRAD_THREADS)), block(GRAYRAD_THREADS);
+  if (!g_grayrad_force_wide && cells < GRAYRAD_NARROW_CELLS)
+    hipLaunchKernelGGL((grayrad_kernel<unsigned>), grid, block, 0, (hipStream_t)stream, nens, level, nz, temp, F, zint, sfc_temp, P, rad_heating,
+                       rad_olr, rad_lw_down_sfc, rad_lw_up_sfc);
+  else
+    hipLaunchKernelGGL((grayrad_kernel<long long>), grid, block, 0, (hipStream_t)stream, nens, level, nz, temp, F, zint, sfc_temp, P, rad_heating,
+                       rad_olr, rad_lw_down_sfc, rad_lw_up_sfc);
+  return stats_launch_check(who);
+}

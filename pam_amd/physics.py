@@ -2,6 +2,7 @@
 
   Radiation         physics/radiation/forced/radiation.h   the GCM's radiative heating applied to the CRM temperature
   RadiationNone     physics/radiation/none/radiation.h
+  RadiationGray     (this project's)                       the native grey two-stream longwave scheme
   SGSNone           physics/sgs/none/SGS.h
   SGSShoc           physics/sgs/shoc/SGS.h                 the coupling layer around shoc_main; SHOC itself is handed in by the caller
   SGSSmagorinsky    (this project's)                       the native Smagorinsky-Lilly closure with an implicit vertical solve
@@ -90,6 +91,86 @@ class RadiationNone:
 
     def timeStep(self, coupler):
         pass
+
+    def finalize(self, coupler):
+        pass
+
+
+class RadiationGray:
+    """physics/radiation/gray_amd/radiation.h: the native grey two-stream longwave scheme.  Not part of the reference tree; the contract is
+    this project's (include/pam_amd_modules.h at pam_amd_radiation_gray).  Every `every`-th timeStep is one call of
+    pam_amd_radiation_gray: it fills "rad_heating" (K/s), "rad_olr", "rad_lw_down_sfc" and "rad_lw_up_sfc" (W/m2) and applies the heating
+    to temp; the steps between apply the stored "rad_heating" through pam_amd_radiation_forced with rad_nx = nx, rad_ny = ny and
+    cp_d = 1.0 (temp += rad_heating / 1.0 * crm_dt, exact).  The cloud species come from option "micro"; the surface radiates at
+    "sfc_temp" (ny,nx,nens) where that entry exists, else at the lowest level's temp.  k_d, k_v, k_l, k_i: mass absorption coefficients of
+    dry air, vapour, cloud liquid and cloud ice in m2/kg with the diffusivity factor folded in; lw_down_top in W/m2.  The defaults are a
+    starting point (k_l is the GCSS DYCOMS-II value): they are untuned."""
+    FIELDS = (("rad_heating", "longwave heating rate [K/s]", 4), ("rad_olr", "outgoing longwave radiation [W/m2]", 3),
+              ("rad_lw_down_sfc", "downward longwave flux at the surface [W/m2]", 3),
+              ("rad_lw_up_sfc", "upward longwave flux at the surface [W/m2]", 3))
+    OPTIONS = ("rad_gray_k_d", "rad_gray_k_v", "rad_gray_k_l", "rad_gray_k_i", "rad_gray_lw_down_top", "rad_gray_every")
+    # option "micro" -> the cloud-liquid and the cloud-ice densities
+    CONDENSATE = {"kessler": (("cloud_liquid",), ()), "p3": (("cloud_water",), ("ice",)), "none": ((), ())}
+    SIGMA = 5.670374419e-8      # where the option "sigma" is absent
+
+    def __init__(self, k_d=1e-4, k_v=0.1, k_l=85.0, k_i=40.0, lw_down_top=0.0, every=1):
+        self.defaults = (float(k_d), float(k_v), float(k_l), float(k_i), float(lw_down_top), int(every))
+        self.calls = 0
+
+    @staticmethod
+    def radiation_name():
+        return "gray"
+
+    def init(self, coupler):
+        """option "radiation" = "gray"; the six rad_gray_* options, each only where absent; registers the four outputs where absent,
+        zero-filled"""
+        nens, nz, ny, nx = coupler.get_nens(), coupler.get_nz(), coupler.get_ny(), coupler.get_nx()
+        if min(nens, nz, ny, nx) < 1:
+            endrun("ERROR: radiation: the coupler state is not allocated")
+        coupler.set_option("radiation", "gray")
+        for name, value in zip(self.OPTIONS, self.defaults):
+            if not coupler.option_exists(name):
+                coupler.set_option(name, value)
+        dm = coupler.get_data_manager_device_readwrite()
+        for name, desc, rank in self.FIELDS:
+            if not dm.entry_exists(name):
+                if rank == 4:
+                    dm.register_and_allocate(name, desc, (nz, ny, nx, nens), ("z", "y", "x", "nens"))
+                else:
+                    dm.register_and_allocate(name, desc, (ny, nx, nens), ("y", "x", "nens"))
+        self.calls = 0
+
+    def timeStep(self, coupler):
+        """one launch on the current stream: the fluxes where calls % rad_gray_every == 0, the stored heating otherwise"""
+        lib = capi.load()
+        nens, nz, ny, nx = coupler.get_nens(), coupler.get_nz(), coupler.get_ny(), coupler.get_nx()
+        dt, cp_d = float(coupler.get_option("crm_dt")), float(coupler.get_option("cp_d"))
+        k_d, k_v, k_l, k_i, top = (float(coupler.get_option(n)) for n in self.OPTIONS[:5])
+        every = int(coupler.get_option("rad_gray_every"))
+        if every < 1:
+            endrun("ERROR: radiation: rad_gray_every must be >= 1")
+        dm = coupler.get_data_manager_device_readwrite()
+        temp, heating = dm.get("temp"), dm.get("rad_heating")
+        recompute = self.calls % every == 0
+        self.calls += 1
+        with torch.cuda.device(coupler.device):
+            stream = torch.cuda.current_stream(coupler.device).cuda_stream
+            if not recompute:       # temp += rad_heating / 1.0 * crm_dt
+                check(lib.pam_amd_radiation_forced(nens, nx, ny, nz, nx, ny, temp.data_ptr(), heating.data_ptr(), 1.0, dt, stream))
+                return
+            micro = coupler.get_option("micro") if coupler.option_exists("micro") else "none"
+            if micro not in self.CONDENSATE:
+                endrun("ERROR: radiation: the gray scheme knows the species of micro = kessler, p3 and none, not of " + str(micro))
+            liquid, ice = ([dm.get(n, readonly=True) for n in names] for names in self.CONDENSATE[micro])
+            ltab = (C.c_void_p * 2)(*[t.data_ptr() for t in liquid])
+            itab = (C.c_void_p * 2)(*[t.data_ptr() for t in ice])
+            sigma = float(coupler.get_option("sigma")) if coupler.option_exists("sigma") else self.SIGMA
+            sfc = dm.get("sfc_temp", readonly=True).data_ptr() if dm.entry_exists("sfc_temp") else None
+            check(lib.pam_amd_radiation_gray(nens, nx, ny, nz, temp.data_ptr(), dm.get("density_dry", readonly=True).data_ptr(),
+                                             dm.get("water_vapor", readonly=True).data_ptr(), len(liquid), ltab, len(ice), itab,
+                                             dm.get("vertical_interface_height", readonly=True).data_ptr(), sfc, k_d, k_v, k_l, k_i, sigma,
+                                             cp_d, top, dt, heating.data_ptr(), dm.get("rad_olr").data_ptr(),
+                                             dm.get("rad_lw_down_sfc").data_ptr(), dm.get("rad_lw_up_sfc").data_ptr(), stream))
 
     def finalize(self, coupler):
         pass

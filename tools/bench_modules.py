@@ -21,6 +21,8 @@ and msa_diagnose of the same run;
 --only sgs: the native Smagorinsky SGS closure's coefficient launch (dry and moist) and its solve (c' in LDS and in the workspace, and
 with the surface fluxes of heat and vapour) on Kessler's field set at the C2 grid and at C4's 32x1x60 grid with 8192 members, beside
 hyperdiffusion and msa_apply of the same run;
+--only grayrad: the native grey two-stream longwave scheme (pam_amd_radiation_gray) at the C2 grid and at C4's 32x1x60 grid with 8192
+members on Kessler's and on P3's field set, beside column_diagnostics and pam_amd_sgs_smag_coefficients of the same run;
 --only msa: mean-state acceleration's diagnose, tendencies and apply (with and without the winds), beside horizontal_average and
 time_average_accumulate of the same run)"""
 import json
@@ -1348,8 +1350,96 @@ def sgs_timing(dev, warmup=3, n=11):
     return out
 
 
+def grayrad_timing(dev, warmup=3, n=11):
+    """The native grey two-stream longwave scheme (pam_amd_radiation_gray) at the C2 grid and at C4's 32x1x60 grid with 8192 members, with
+    Kessler's field set (one liquid species) and with P3's (one liquid, one ice), 3 warm-up calls and the median of 11 event-timed calls
+    each.  Algorithmic bytes per cell, counted as the two sweeps touch them: every input field (temp, rho_d, rho_v and the species: four
+    with Kessler, five with P3) read twice, rad_heating written, read and written, temp written: 12 x 8 B and 14 x 8 B; plus zint and
+    the three surface outputs.  pam_amd_column_diagnostics (P3's field set) and pam_amd_sgs_smag_coefficients of the same run stand
+    beside them as the yardsticks."""
+    import ctypes as C
+    from pam_amd import PamCoupler, RadiationGray, SGSSmagorinsky, capi, modules
+    from pam_amd import idealized as idz
+    lib = capi.load()
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    def row(t, nbytes):
+        return {"ms": t[0], "min_ms": t[1], "max_ms": t[2], "bytes": nbytes, "GBps": nbytes / t[0] / 1e6,
+                "hbm_frac": nbytes / t[0] / 1e6 / bench.HBM_PEAK_GBS}
+
+    def grid(nens, nx, ny, nz, label, out):
+        cells, cols = nens * nx * ny * nz, nens * nx * ny
+        c = PamCoupler(dev)
+        for name, v in (("crm_dt", 2.0), ("gcm_physics_dt", 900.0), ("grav", 9.80616), ("cp_d", 1004.64), ("R_d", 287.042), ("R_v", 461.505)):
+            c.set_option(name, v)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+        for t in ("water_vapor", "cloud_liquid", "cloud_water", "ice"):
+            c.add_tracer(t, "", True, True)
+        dm = c.get_data_manager_device_readwrite()
+        for name in ("precip_liq_surf_out", "precip_ice_surf_out"):
+            dm.register_and_allocate(name, "surface precipitation rate", (ny, nx, nens), ("y", "x", "nens"))
+        gen = torch.Generator(device=dev).manual_seed(0)
+        k = torch.arange(nz, dtype=torch.float64, device=dev)[:, None, None, None]
+        for name, scale in (("temp", 290.0 - 1.2 * k), ("density_dry", 1.2 * torch.exp(-k / 25.0)), ("water_vapor", 1.0e-2 * torch.exp(-k / 10.0)),
+                            ("uvel", 10.0), ("vvel", 10.0), ("wvel", 1.0)):
+            t = dm.get(name)
+            t.copy_((torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * 0.1 + 0.95) * scale)
+        for name, scale in (("cloud_liquid", 1.0e-4), ("cloud_water", 1.0e-4), ("ice", 3.0e-5)):      # condensate in a third of the cells
+            t = dm.get(name)
+            t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * scale)
+            t.mul_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) < 1.0 / 3.0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for micro, nin in (("kessler", 4), ("p3", 5)):
+            c.set_option("micro", micro)
+            rad = RadiationGray()
+            rad.init(c)
+            nbytes = cells * 8.0 * (2 * nin + 4) + (nz + 1) * nens * 8.0 + 3 * cols * 8.0
+            out["grayrad_%s%s" % (micro, label)] = row(timed(lambda: rad.timeStep(c)), nbytes)
+            assert bool(torch.isfinite(dm.get("rad_heating", readonly=True)).all()) and float(dm.get("rad_olr", readonly=True).min()) > 0
+        # the stored heating applied on the steps between two flux computations (every > 1): pam_amd_radiation_forced on the CRM grid
+        P = lambda name: dm.get(name).data_ptr()
+        out["grayrad_apply_stored" + label] = row(timed(lambda: capi.check(lib.pam_amd_radiation_forced(
+            nens, nx, ny, nz, nx, ny, P("temp"), P("rad_heating"), 1.0, 2.0, stream))), cells * 24.0)
+        modules.column_diagnostics_init(c)                          # micro = p3
+        out["column_diagnostics" + label] = row(timed(lambda: modules.column_diagnostics(c)), 5 * cells * 8.0 + 7 * cols * 16.0 + 2 * cols * 8.0)
+        sgs = SGSSmagorinsky()
+        sgs.init(c)
+        out["sgs_coefficients" + label] = row(timed(lambda: capi.check(lib.pam_amd_sgs_smag_coefficients(
+            nens, nx, ny, nz, P("uvel"), P("vvel"), P("wvel"), P("temp"), P("density_dry"), P("water_vapor"), P("vertical_interface_height"),
+            P("vertical_midpoint_height"), 1000.0, 1000.0, 9.80616, 1004.64, 0.2, 1.0 / 3.0, P("tk"), P("tkh"), stream))), cells * 64.0)
+        for micro in ("kessler", "p3"):
+            for y in ("column_diagnostics", "sgs_coefficients"):
+                out["grayrad_%s%s_vs_%s_frac" % (micro, label, y)] = out["grayrad_%s%s" % (micro, label)]["hbm_frac"] / out[y + label]["hbm_frac"]
+        del c, dm, rad, sgs
+        lib.pam_amd_modules_finalize()
+        torch.cuda.empty_cache()
+
+    out = {"grayrad_grid": "1024 x 32x32x60 (C2) and 8192 x 32x1x60 (C4)",
+           "grayrad_method": "%d warm-up calls, median of %d event-timed calls" % (warmup, n)}
+    grid(1024, 32, 32, 60, "", out)
+    grid(8192, 32, 1, 60, "_c4", out)
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "grayrad"]:
+        print(json.dumps(grayrad_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "sgs"]:
         print(json.dumps(sgs_timing(dev)))
         sys.exit(0)
