@@ -314,7 +314,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
-//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--radiation-gray [EVERY]] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
+//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
 //          [--flux-profiles PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
@@ -427,6 +427,10 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              fluxes recomputed on every EVERY-th step (1 unless given) and the stored heating applied between.  One
 //                              "radiation gray:" line per output step with the ensemble-mean OLR and surface downward flux.  Composes
 //                              with every other flag but --radiation: there is one slot
+//   --shortwave COSZEN [ALBEDO]   with --radiation-gray: option rad_gray_shortwave, the scheme's grey two-stream shortwave under a sun
+//                              whose zenith angle has the cosine COSZEN for every member (rad_gray_sw_coszen) over a surface of albedo
+//                              ALBEDO (rad_gray_sw_albedo; 0.07 unless given).  The "radiation gray:" line then also carries the mean
+//                              rad_sw_down_sfc and rad_sw_up_top.  Refused without --radiation-gray
 //   --vt RATE PATH [--vt-u] [--vt-limit L]   CRM variance transport (modules/variance_transport.h): modules::vt_init at the start of every GCM
 //                              step; there is no GCM here, so vt_tend_x = RATE vt_var_start_x (a relative growth rate per second) for
 //                              that GCM step; modules::vt_apply_forcing LAST in every CRM step, after the clock has advanced, with dt =
@@ -454,8 +458,9 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              prof_flux_v and prof_tke, printed with %.17g; nothing else of the run changes.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false;
+  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false, shortwave = false;
   int radiation_gray_every = 1;
+  double sw_coszen = 1, sw_albedo = 0.07;
   double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0, sfc_shf = 0, sfc_lhf = 0;
   int handoff_rad_nx = 0, handoff_rad_ny = 0;
   std::string handoff_path;
@@ -585,6 +590,11 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     dycore.init(coupler);                                                    // driver.cpp:191
     if (mods.radiation_gray) {                                               // --radiation-gray: the native scheme in the radiation slot
       coupler.set_option<int>("rad_gray_every", mods.radiation_gray_every);
+      if (mods.shortwave) {                                                  // --shortwave: the sun on, the same for every member
+        coupler.set_option<bool>("rad_gray_shortwave", true);
+        coupler.set_option<real>("rad_gray_sw_coszen", mods.sw_coszen);
+        coupler.set_option<real>("rad_gray_sw_albedo", mods.sw_albedo);
+      }
       rad_gray.init(coupler);
     }
     if (mods.radiation) {
@@ -734,7 +744,16 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
               endrun("memcpy");
             double so = 0, sd = 0;
             for (size_t c = 0; c < n2; c++) { so += olr[c]; sd += down[c]; }
-            std::printf("radiation gray: etime %g , olr %.9g , lw_down_sfc %.9g\n", etime_gcm, so / n2, sd / n2);
+            if (!mods.shortwave) std::printf("radiation gray: etime %g , olr %.9g , lw_down_sfc %.9g\n", etime_gcm, so / n2, sd / n2);
+            else {
+              if (hipMemcpy(olr.data(), dm.get<real const, 3>("rad_sw_down_sfc").data(), n2 * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess ||
+                  hipMemcpy(down.data(), dm.get<real const, 3>("rad_sw_up_top").data(), n2 * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess)
+                endrun("memcpy");
+              double ss = 0, st = 0;
+              for (size_t c = 0; c < n2; c++) { ss += olr[c]; st += down[c]; }
+              std::printf("radiation gray: etime %g , olr %.9g , lw_down_sfc %.9g , sw_down_sfc %.9g , sw_up_top %.9g\n", etime_gcm, so / n2, sd / n2,
+                          ss / n2, st / n2);
+            }
           }
           char t[64];
           std::snprintf(t, sizeof(t), "%s%.6g", maxw_series.empty() ? "" : ",", maxw);
@@ -1015,6 +1034,12 @@ int main(int argc, char **argv) {
         const std::string n(b + 1 < argc - 1 ? argv[b + 1] : "");                // the optional EVERY: an argument of digits only
         if (!n.empty() && n.find_first_not_of("0123456789") == std::string::npos) mods.radiation_gray_every = std::atoi(argv[++b]);
       }
+      else if (o == "--shortwave" && b + 1 < argc - 1) {
+        mods.shortwave = true;
+        mods.sw_coszen = std::atof(argv[++b]);
+        const std::string n(b + 1 < argc - 1 ? argv[b + 1] : "");                // the optional ALBEDO: an argument that is a number
+        if (!n.empty() && n.find_first_not_of("0123456789.eE+") == std::string::npos) mods.sw_albedo = std::atof(argv[++b]);
+      }
       else if (o == "--sgs-moist") mods.sgs_moist = true;
       else if (o == "--sfc-fluxes" && b + 2 < argc - 1) { mods.sfc_fluxes = true; mods.sfc_shf = std::atof(argv[++b]); mods.sfc_lhf = std::atof(argv[++b]); }
       else if (o == "--gcm-handoff" && b + 3 < argc - 1) {
@@ -1027,11 +1052,12 @@ int main(int argc, char **argv) {
       else if (o == "--flux-profiles" && b + 1 < argc - 1) mods.flux_profiles = argv[++b];
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--radiation-gray [EVERY]] "
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] "
                "[--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->");
     }
     if (mods.radiation_gray && mods.radiation) die("--radiation-gray and --radiation both fill the one radiation slot: give one of them");
     if (mods.radiation_gray && mods.radiation_gray_every < 1) die("--radiation-gray EVERY must be >= 1");
+    if (mods.shortwave && !mods.radiation_gray) die("--shortwave COSZEN [ALBEDO] needs --radiation-gray [EVERY]: the sun belongs to the native scheme");
     if ((mods.sgs_moist || mods.sfc_fluxes) && !mods.sgs_smag) die("--sgs-moist and --sfc-fluxes need --sgs-smag CS PRANDTL");
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }

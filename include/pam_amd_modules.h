@@ -768,6 +768,56 @@ int pam_amd_radiation_gray(int nens, int nx, int ny, int nz, double *temp, const
                            double *rad_heating, double *rad_olr, double *rad_lw_down_sfc, double *rad_lw_up_sfc, void *stream);
 int pam_amd_radiation_gray_debug_wide_index(int on);
 
+/* The shortwave of the native radiation scheme: a grey two-stream solve of the sunlight along every column, with absorption by the dry
+ * air, the vapour and the cloud condensate, backscatter by the cloud condensate, a reflecting surface, and the layers combined by the
+ * adding method (as Lacis and Hansen 1974 combine theirs) -- the sun of a run that needs no external library.  One band; no split into
+ * a direct and a diffuse beam: the slant factor m = 1 / coszen is used for the sun's beam AND for the reflected, diffuse light, which is
+ * an approximation of this grey scheme (the diffuse light of a real atmosphere travels at a mean slant of about 5/3 whatever the sun
+ * does).  Not part of the reference tree; the contract is this project's and is restated in numpy in
+ * tests/grayrad_sw_ref.py, which the kernel matches bit for bit.
+ * temp, rho_d, rho_v, liquid[num_liquid], ice[num_ice] and zint (nz+1,nens) are those of pam_amd_radiation_gray above.  coszen (nens) is
+ * a DEVICE array: the cosine of the solar zenith angle of every member (in an MMF every member sits under another GCM column).
+ * sfc_albedo (ny,nx,nens) is a DEVICE array or NULL; NULL selects the scalar albedo.  solar_constant in W/m2; a_d, a_v, a_l, a_i are mass
+ * absorption coefficients in m2/kg; s_l, s_i are the mass backscatter coefficients of cloud liquid and cloud ice in m2/kg: the extinction
+ * times (1 - g) / 2, folded in as the longwave folds in its diffusivity factor.
+ * Everything is fp64, every operation is rounded on its own (no fma), every division is a true IEEE division, and the association is
+ * as written.  Per (column, member), mu0 = coszen(e):
+ * Night, mu0 <= 0.0 (so -0.0 too): rad_sw_heating is 0.0 at every level, the three flux outputs are 0.0, temp keeps its bits, and no
+ *   field of that column is read.  A NaN mu0 is NOT night: it takes the day branch and fills the columns of its own member with NaN,
+ *   and of no other member.
+ * Day: m = 1.0 / mu0, once per column.  Per cell, level k counted from the ground:
+ *   dz = zint(k+1) - zint(k); L = 0.0 for an empty liquid table, liquid[0], or liquid[0] + liquid[1]; I likewise from the ice table;
+ *   a = a_d rho_d + a_v rho_v; a = a + a_l L; a = a + a_i I; da = (a dz) m; ta = exp_c(-da), the exponential of
+ *   pam_amd_sgs_smag_coefficients_moist above: exactly 1.0 at da = 0 and exactly 0.0 beyond 700;
+ *   s = s_l L + s_i I; b = (s dz) m; tr = 1.0 / (1.0 + b); r = 1.0 - tr (so b = 0 gives r = 0.0 exactly and b = inf gives r = 1.0, no NaN);
+ *   R = r ta, the layer's reflectance, and T = tr ta, its transmittance, the same for light from above and from below.
+ * Upward (the adding method): Rb(0) = sfc_albedo or albedo; for k = 0 .. nz-1: q(k) = 1.0 - Rb(k) R(k); Rb(k+1) = R(k) + ((T(k) Rb(k)) T(k))
+ *   / q(k).  Rb(k) is the reflectance of everything below interface k.
+ * Downward: Fd(nz) = solar_constant mu0; Fu(nz) = Rb(nz) Fd(nz); for k = nz-1 .. 0: Fd(k) = (T(k) Fd(k+1)) / q(k); Fu(k) = Rb(k) Fd(k), with
+ *   R, T and q formed again from the same inputs.
+ * rad_sw_heating(k) = ((Fd(k+1) - Fd(k)) + (Fu(k) - Fu(k+1))) / ((cp_d (rho_d + rho_v)) dz) in K/s, and where dt != 0 temp(k) = temp(k) +
+ * rad_sw_heating(k) dt; with dt == 0 the call diagnoses only and temp keeps its bits (temp enters nothing else).
+ * Outputs: temp in place; rad_sw_heating (nz,ny,nx,nens); rad_sw_down_sfc = Fd(0), rad_sw_up_sfc = Fu(0) and rad_sw_up_top = Fu(nz), each
+ * (ny,nx,nens).  For a finite column S cp_d (rho_d + rho_v) dz rad_sw_heating = (Fd(nz) - Fu(nz)) - (Fd(0) - Fu(0)) to rounding; with all
+ * four a_* 0.0 (conservative scattering) Fd - Fu is the same at every interface to rounding; with s_l = s_i = 0 and albedo 0 Fd(0) is
+ * Beer's law and every Fu is 0.0; with every coefficient 0.0 Fu(k) = albedo Fd(nz) at every k and rad_sw_heating is 0.0 exactly.
+ * Nothing is refused because of a value in a field; a NaN stays in its column.
+ * One launch: a thread owns a (column, member) and makes both sweeps; the upward sweep parks Rb(k) in rad_sw_heating(k), the downward
+ * sweep reads it back and overwrites it with the heating, so there is no scratch and no second launch.  Five divisions and two exp_c
+ * per cell.  No atomics; the same bits from run to run, for any split of the members over calls (with the matching slices of zint and
+ * coszen), and for a day member whatever its neighbours in the wavefront are.
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: the size, pointer, table and overlap rules of
+ * pam_amd_radiation_gray (sfc_albedo is the pointer that may be NULL; coszen and sfc_albedo count as inputs); a NULL coszen;
+ * solar_constant, a_d, a_v, a_l, a_i, s_l, s_i or dt not finite or negative; albedo outside [0, 1] (a NaN included); cp_d not finite
+ * and positive.  Without a device a call whose arguments pass returns PAM_AMD_ENOGPU.
+ * pam_amd_radiation_gray_sw_debug_wide_index is the test switch of pam_amd_radiation_gray_debug_wide_index for this kernel. */
+int pam_amd_radiation_gray_sw(int nens, int nx, int ny, int nz, double *temp, const double *rho_d, const double *rho_v, int num_liquid,
+                              const double *const *liquid, int num_ice, const double *const *ice, const double *zint, const double *coszen,
+                              const double *sfc_albedo, double solar_constant, double a_d, double a_v, double a_l, double a_i, double s_l,
+                              double s_i, double albedo, double cp_d, double dt, double *rad_sw_heating, double *rad_sw_down_sfc,
+                              double *rad_sw_up_sfc, double *rad_sw_up_top, void *stream);
+int pam_amd_radiation_gray_sw_debug_wide_index(int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4097,3 +4097,90 @@ extern "C" int pam_amd_radiation_gray(int nens, int nx, int ny, int nz, double *
                        rad_olr, rad_lw_down_sfc, rad_lw_up_sfc);
   return stats_launch_check(who);
 }
+
+// ------------------------------------------------------------------------------------------------
+// The native grey two-stream shortwave radiation scheme: absorption by the dry air, the vapour and the cloud condensate, backscatter by
+// the cloud condensate, the layers combined by the adding method, under each member's own sun.  Not in the reference tree; the contract
+// is in include/pam_amd_modules.h and DESIGN.md section 8, its arithmetic in grayrad_sw_device.h.  The launch shape is the longwave
+// kernel's: ONE launch, a thread owns a (column, member), members and then x across the lanes.  The upward sweep parks the reflectance
+// of everything below a cell in rad_sw_heating, the downward sweep forms R and T of the cell again from the fields, reads the parked
+// value back, replaces it by the heating and updates temp: no scratch, no LDS, no second launch, no atomics.  A night member's thread
+// stores its zeros and returns before any load of a field; the day lanes of the same wavefront run as they would alone.
+#include "grayrad_sw_device.h"
+
+namespace {
+namespace gs = pama::grayrad_sw;
+
+// grid (ceil(ny nx nens / 64)), block 64: thread t = (j nx + i) nens + e
+template <class IDX>
+__global__ void __launch_bounds__(GRAYRAD_THREADS) grayrad_sw_kernel(int nens, long long level, int nz, double *temp, gr::Fields F,
+                                                                     const double *__restrict__ zint, const double *__restrict__ coszen,
+                                                                     const double *sfc_albedo, gs::Params P, double *heating,
+                                                                     double *__restrict__ down_sfc, double *__restrict__ up_sfc,
+                                                                     double *__restrict__ up_top) {
+  const long long t = (long long)blockIdx.x * GRAYRAD_THREADS + (long long)threadIdx.x;
+  if (t >= level) return;
+  const int e = (int)(t % nens);
+  gs::column<IDX>(temp, F, zint + e, coszen[e], sfc_albedo, (IDX)t, (IDX)level, (IDX)nens, nz, P, heating, down_sfc, up_sfc, up_top);
+}
+
+bool g_grayrad_sw_force_wide = false;   // pam_amd_radiation_gray_sw_debug_wide_index: tests run the long long instance at small sizes
+}  // namespace
+
+extern "C" int pam_amd_radiation_gray_sw_debug_wide_index(int on) {
+  g_grayrad_sw_force_wide = on != 0;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_radiation_gray_sw(int nens, int nx, int ny, int nz, double *temp, const double *rho_d, const double *rho_v,
+                                         int num_liquid, const double *const *liquid, int num_ice, const double *const *ice,
+                                         const double *zint, const double *coszen, const double *sfc_albedo, double solar_constant, double a_d,
+                                         double a_v, double a_l, double a_i, double s_l, double s_i, double albedo, double cp_d, double dt,
+                                         double *rad_sw_heating, double *rad_sw_down_sfc, double *rad_sw_up_sfc, double *rad_sw_up_top,
+                                         void *stream) {
+  const char *who = "radiation_gray_sw";
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return module_error(who, "nens, nx, ny and nz must be >= 1");
+  if ((long long)nx * ny > 0x7fffffffLL) return module_error(who, "ny x nx exceeds 2^31 - 1 columns");
+  const long long level = (long long)nx * ny * nens, cells = level * nz;
+  if ((level + GRAYRAD_THREADS - 1) / GRAYRAD_THREADS > 0x7fffffffLL) return module_error(who, "ny x nx x nens exceeds the grid");
+  if (num_liquid < 0 || num_liquid > gr::MAX_SPECIES) return module_error(who, "num_liquid must be in [0, 2]");
+  if (num_ice < 0 || num_ice > gr::MAX_SPECIES) return module_error(who, "num_ice must be in [0, 2]");
+  if ((num_liquid > 0 && !liquid) || (num_ice > 0 && !ice)) return module_error(who, "null condensate table");
+  if (!temp || !rho_d || !rho_v || !zint || !coszen || !rad_sw_heating || !rad_sw_down_sfc || !rad_sw_up_sfc || !rad_sw_up_top)
+    return module_error(who, "null pointer");
+  for (int i = 0; i < num_liquid; i++)
+    if (!liquid[i]) return module_error(who, "null liquid pointer");
+  for (int i = 0; i < num_ice; i++)
+    if (!ice[i]) return module_error(who, "null ice pointer");
+  for (double v : {solar_constant, a_d, a_v, a_l, a_i, s_l, s_i, dt})
+    if (!grayrad_coefficient(v)) return module_error(who, "solar_constant, a_d, a_v, a_l, a_i, s_l, s_i and dt must be finite and >= 0");
+  if (!(albedo >= 0 && albedo <= 1)) return module_error(who, "albedo must be in [0, 1]");
+  if (!std::isfinite(cp_d) || !(cp_d > 0)) return module_error(who, "cp_d must be finite and positive");
+  std::vector<Span> spans;
+  for (const double *p : {rho_d, rho_v}) spans.push_back({p, cells, false});
+  for (int i = 0; i < num_liquid; i++) spans.push_back({liquid[i], cells, false});
+  for (int i = 0; i < num_ice; i++) spans.push_back({ice[i], cells, false});
+  spans.push_back({zint, (long long)(nz + 1) * nens, false});
+  spans.push_back({coszen, (long long)nens, false});
+  if (sfc_albedo) spans.push_back({sfc_albedo, level, false});
+  for (double *p : {temp, rad_sw_heating}) spans.push_back({p, cells, true});
+  for (double *p : {rad_sw_down_sfc, rad_sw_up_sfc, rad_sw_up_top}) spans.push_back({p, level, true});
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if (int rc = require_device(who)) return rc;
+
+  gr::Fields F;
+  F.rho_d = rho_d; F.rho_v = rho_v;
+  for (int i = 0; i < gr::MAX_SPECIES; i++) {
+    F.liquid[i] = i < num_liquid ? liquid[i] : nullptr;
+    F.ice[i] = i < num_ice ? ice[i] : nullptr;
+  }
+  const gs::Params P{a_d, a_v, a_l, a_i, s_l, s_i, solar_constant, albedo, cp_d, dt, num_liquid, num_ice};
+  const dim3 grid((unsigned)((level + GRAYRAD_THREADS - 1) / GRAYRAD_THREADS)), block(GRAYRAD_THREADS);
+  if (!g_grayrad_sw_force_wide && cells < GRAYRAD_NARROW_CELLS)
+    hipLaunchKernelGGL((grayrad_sw_kernel<unsigned>), grid, block, 0, (hipStream_t)stream, nens, level, nz, temp, F, zint, coszen, sfc_albedo, P,
+                       rad_sw_heating, rad_sw_down_sfc, rad_sw_up_sfc, rad_sw_up_top);
+  else
+    hipLaunchKernelGGL((grayrad_sw_kernel<long long>), grid, block, 0, (hipStream_t)stream, nens, level, nz, temp, F, zint, coszen, sfc_albedo, P,
+                       rad_sw_heating, rad_sw_down_sfc, rad_sw_up_sfc, rad_sw_up_top);
+  return stats_launch_check(who);
+}

@@ -2,7 +2,7 @@
 
   Radiation         physics/radiation/forced/radiation.h   the GCM's radiative heating applied to the CRM temperature
   RadiationNone     physics/radiation/none/radiation.h
-  RadiationGray     (this project's)                       the native grey two-stream longwave scheme
+  RadiationGray     (this project's)                       the native grey two-stream longwave scheme, and its shortwave
   SGSNone           physics/sgs/none/SGS.h
   SGSShoc           physics/sgs/shoc/SGS.h                 the coupling layer around shoc_main; SHOC itself is handed in by the caller
   SGSSmagorinsky    (this project's)                       the native Smagorinsky-Lilly closure with an implicit vertical solve
@@ -104,7 +104,16 @@ class RadiationGray:
     cp_d = 1.0 (temp += rad_heating / 1.0 * crm_dt, exact).  The cloud species come from option "micro"; the surface radiates at
     "sfc_temp" (ny,nx,nens) where that entry exists, else at the lowest level's temp.  k_d, k_v, k_l, k_i: mass absorption coefficients of
     dry air, vapour, cloud liquid and cloud ice in m2/kg with the diffusivity factor folded in; lw_down_top in W/m2.  The defaults are a
-    starting point (k_l is the GCSS DYCOMS-II value): they are untuned."""
+    starting point (k_l is the GCSS DYCOMS-II value): they are untuned.
+    The sun is switched on by RadiationGray(...).shortwave(solar_constant=1361.0, coszen=1.0, albedo=0.07, a_d=1e-6, a_v=2e-3, a_l=0.1,
+    a_i=0.1, s_l=11.0, s_i=5.0), which returns the object, or by option "rad_gray_shortwave" = True before init; the constructor keeps the
+    six longwave arguments.  init then also registers "rad_sw_heating" (K/s), "rad_sw_down_sfc", "rad_sw_up_sfc", "rad_sw_up_top" (W/m2)
+    and "rad_coszen" (nens), filled from coszen (a float, or a length-nens sequence or tensor); a host model or a test overwrites
+    "rad_coszen" between steps, and that is the diurnal cycle.  A recompute step is then the longwave call followed by one call of
+    pam_amd_radiation_gray_sw (the surface reflects "sfc_albedo" (ny,nx,nens) where that entry exists, else the scalar albedo), and a
+    step between applies both stored heatings, two calls of pam_amd_radiation_forced.  Without the sun the class makes exactly the
+    calls described above.  a_d, a_v, a_l, a_i: shortwave mass absorption coefficients in m2/kg; s_l, s_i: mass backscatter coefficients
+    of cloud liquid and cloud ice in m2/kg (extinction x (1 - g) / 2).  These defaults too are untuned starting points."""
     FIELDS = (("rad_heating", "longwave heating rate [K/s]", 4), ("rad_olr", "outgoing longwave radiation [W/m2]", 3),
               ("rad_lw_down_sfc", "downward longwave flux at the surface [W/m2]", 3),
               ("rad_lw_up_sfc", "upward longwave flux at the surface [W/m2]", 3))
@@ -112,10 +121,22 @@ class RadiationGray:
     # option "micro" -> the cloud-liquid and the cloud-ice densities
     CONDENSATE = {"kessler": (("cloud_liquid",), ()), "p3": (("cloud_water",), ("ice",)), "none": ((), ())}
     SIGMA = 5.670374419e-8      # where the option "sigma" is absent
+    SW_FIELDS = (("rad_sw_heating", "shortwave heating rate [K/s]", 4), ("rad_sw_down_sfc", "downward shortwave flux at the surface [W/m2]", 3),
+                 ("rad_sw_up_sfc", "upward shortwave flux at the surface [W/m2]", 3),
+                 ("rad_sw_up_top", "upward shortwave flux at the model top [W/m2]", 3))
+    SW_OPTIONS = ("rad_gray_sw_solar_constant", "rad_gray_sw_albedo", "rad_gray_sw_a_d", "rad_gray_sw_a_v", "rad_gray_sw_a_l", "rad_gray_sw_a_i",
+                  "rad_gray_sw_s_l", "rad_gray_sw_s_i")
 
     def __init__(self, k_d=1e-4, k_v=0.1, k_l=85.0, k_i=40.0, lw_down_top=0.0, every=1):
         self.defaults = (float(k_d), float(k_v), float(k_l), float(k_i), float(lw_down_top), int(every))
         self.calls = 0
+        self.sun, self.coszen, self.sw_defaults = False, 1.0, (1361.0, 0.07, 1e-6, 2e-3, 0.1, 0.1, 11.0, 5.0)
+
+    def shortwave(self, shortwave=True, solar_constant=1361.0, coszen=1.0, albedo=0.07, a_d=1e-6, a_v=2e-3, a_l=0.1, a_i=0.1, s_l=11.0, s_i=5.0):
+        """the sun, before init: -> self.  coszen: a float, or a length-nens sequence or tensor"""
+        self.sun, self.coszen = bool(shortwave), coszen
+        self.sw_defaults = tuple(float(v) for v in (solar_constant, albedo, a_d, a_v, a_l, a_i, s_l, s_i))
+        return self
 
     @staticmethod
     def radiation_name():
@@ -139,9 +160,28 @@ class RadiationGray:
                 else:
                     dm.register_and_allocate(name, desc, (ny, nx, nens), ("y", "x", "nens"))
         self.calls = 0
+        if not coupler.option_exists("rad_gray_shortwave"):
+            coupler.set_option("rad_gray_shortwave", self.sun)
+        if not coupler.get_option("rad_gray_shortwave"):
+            return
+        for name, value in zip(self.SW_OPTIONS, self.sw_defaults):
+            if not coupler.option_exists(name):
+                coupler.set_option(name, value)
+        for name, desc, rank in self.SW_FIELDS:
+            if not dm.entry_exists(name):
+                if rank == 4:
+                    dm.register_and_allocate(name, desc, (nz, ny, nx, nens), ("z", "y", "x", "nens"))
+                else:
+                    dm.register_and_allocate(name, desc, (ny, nx, nens), ("y", "x", "nens"))
+        if not dm.entry_exists("rad_coszen"):
+            mu0 = torch.as_tensor(self.coszen, dtype=torch.float64).reshape(-1)
+            if mu0.numel() not in (1, nens):
+                endrun("ERROR: radiation: coszen must be a float or hold one value per member")
+            dm.register_and_allocate("rad_coszen", "cosine of the solar zenith angle of every member", (nens,), ("nens",)).copy_(mu0.expand(nens))
 
     def timeStep(self, coupler):
-        """one launch on the current stream: the fluxes where calls % rad_gray_every == 0, the stored heating otherwise"""
+        """on the current stream: the fluxes where calls % rad_gray_every == 0 (the longwave launch, then the shortwave one where the sun
+        is on), the stored heating otherwise"""
         lib = capi.load()
         nens, nz, ny, nx = coupler.get_nens(), coupler.get_nz(), coupler.get_ny(), coupler.get_nx()
         dt, cp_d = float(coupler.get_option("crm_dt")), float(coupler.get_option("cp_d"))
@@ -153,10 +193,14 @@ class RadiationGray:
         temp, heating = dm.get("temp"), dm.get("rad_heating")
         recompute = self.calls % every == 0
         self.calls += 1
+        sun = coupler.option_exists("rad_gray_shortwave") and bool(coupler.get_option("rad_gray_shortwave"))
         with torch.cuda.device(coupler.device):
             stream = torch.cuda.current_stream(coupler.device).cuda_stream
             if not recompute:       # temp += rad_heating / 1.0 * crm_dt
                 check(lib.pam_amd_radiation_forced(nens, nx, ny, nz, nx, ny, temp.data_ptr(), heating.data_ptr(), 1.0, dt, stream))
+                if sun:             # and temp += rad_sw_heating / 1.0 * crm_dt
+                    check(lib.pam_amd_radiation_forced(nens, nx, ny, nz, nx, ny, temp.data_ptr(), dm.get("rad_sw_heating", readonly=True).data_ptr(),
+                                                       1.0, dt, stream))
                 return
             micro = coupler.get_option("micro") if coupler.option_exists("micro") else "none"
             if micro not in self.CONDENSATE:
@@ -171,6 +215,16 @@ class RadiationGray:
                                              dm.get("vertical_interface_height", readonly=True).data_ptr(), sfc, k_d, k_v, k_l, k_i, sigma,
                                              cp_d, top, dt, heating.data_ptr(), dm.get("rad_olr").data_ptr(),
                                              dm.get("rad_lw_down_sfc").data_ptr(), dm.get("rad_lw_up_sfc").data_ptr(), stream))
+            if not sun:
+                return
+            solar, albedo, a_d, a_v, a_l, a_i, s_l, s_i = (float(coupler.get_option(n)) for n in self.SW_OPTIONS)
+            sfc_albedo = dm.get("sfc_albedo", readonly=True).data_ptr() if dm.entry_exists("sfc_albedo") else None
+            check(lib.pam_amd_radiation_gray_sw(nens, nx, ny, nz, temp.data_ptr(), dm.get("density_dry", readonly=True).data_ptr(),
+                                                dm.get("water_vapor", readonly=True).data_ptr(), len(liquid), ltab, len(ice), itab,
+                                                dm.get("vertical_interface_height", readonly=True).data_ptr(),
+                                                dm.get("rad_coszen", readonly=True).data_ptr(), sfc_albedo, solar, a_d, a_v, a_l, a_i, s_l, s_i,
+                                                albedo, cp_d, dt, dm.get("rad_sw_heating").data_ptr(), dm.get("rad_sw_down_sfc").data_ptr(),
+                                                dm.get("rad_sw_up_sfc").data_ptr(), dm.get("rad_sw_up_top").data_ptr(), stream))
 
     def finalize(self, coupler):
         pass

@@ -23,6 +23,9 @@ with the surface fluxes of heat and vapour) on Kessler's field set at the C2 gri
 hyperdiffusion and msa_apply of the same run;
 --only grayrad: the native grey two-stream longwave scheme (pam_amd_radiation_gray) at the C2 grid and at C4's 32x1x60 grid with 8192
 members on Kessler's and on P3's field set, beside column_diagnostics and pam_amd_sgs_smag_coefficients of the same run;
+--only grayrad_sw: the scheme's shortwave (pam_amd_radiation_gray_sw) on the same grids and field sets, with every member under the sun
+and with half of the members at night (interleaved with the day members inside every wavefront, and in blocks of whole wavefronts),
+beside pam_amd_radiation_gray and column_diagnostics of the same run;
 --only msa: mean-state acceleration's diagnose, tendencies and apply (with and without the winds), beside horizontal_average and
 time_average_accumulate of the same run)"""
 import json
@@ -1435,8 +1438,108 @@ def grayrad_timing(dev, warmup=3, n=11):
     return out
 
 
+def grayrad_sw_timing(dev, warmup=3, n=11):
+    """The native scheme's shortwave (pam_amd_radiation_gray_sw) at the C2 grid and at C4's 32x1x60 grid with 8192 members, with Kessler's
+    field set (one liquid species) and with P3's (one liquid, one ice): the method is grayrad_timing's, 3 warm-up calls and the median of
+    11 event-timed calls each.  Rows: every member under the sun (coszen 0.3 .. 1); half of the members at night, the odd ones, so that
+    every wavefront holds both; and half of the members at night, the upper half, so that a wavefront holds one kind.  Algorithmic bytes
+    per cell of a day column: every input field (rho_d, rho_v and the species: three with Kessler, four with P3) read twice,
+    rad_sw_heating written, read and written, temp read and written: 11 x 8 B and 13 x 8 B; a night column writes rad_sw_heating once;
+    plus zint, coszen and the three column outputs.  pam_amd_radiation_gray (Kessler's field set) and pam_amd_column_diagnostics (P3's) of
+    the same run stand beside them as the yardsticks."""
+    import ctypes as C
+    from pam_amd import PamCoupler, RadiationGray, capi, modules
+    from pam_amd import idealized as idz
+    lib = capi.load()
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    def row(t, nbytes):
+        return {"ms": t[0], "min_ms": t[1], "max_ms": t[2], "bytes": nbytes, "GBps": nbytes / t[0] / 1e6,
+                "hbm_frac": nbytes / t[0] / 1e6 / bench.HBM_PEAK_GBS}
+
+    def grid(nens, nx, ny, nz, label, out):
+        cells, cols = nens * nx * ny * nz, nens * nx * ny
+        c = PamCoupler(dev)
+        for name, v in (("crm_dt", 2.0), ("gcm_physics_dt", 900.0), ("grav", 9.80616), ("cp_d", 1004.64), ("R_d", 287.042), ("R_v", 461.505)):
+            c.set_option(name, v)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+        for t in ("water_vapor", "cloud_liquid", "cloud_water", "ice"):
+            c.add_tracer(t, "", True, True)
+        dm = c.get_data_manager_device_readwrite()
+        for name in ("precip_liq_surf_out", "precip_ice_surf_out"):
+            dm.register_and_allocate(name, "surface precipitation rate", (ny, nx, nens), ("y", "x", "nens"))
+        gen = torch.Generator(device=dev).manual_seed(0)
+        k = torch.arange(nz, dtype=torch.float64, device=dev)[:, None, None, None]
+        for name, scale in (("temp", 290.0 - 1.2 * k), ("density_dry", 1.2 * torch.exp(-k / 25.0)), ("water_vapor", 1.0e-2 * torch.exp(-k / 10.0))):
+            t = dm.get(name)
+            t.copy_((torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * 0.1 + 0.95) * scale)
+        for name, scale in (("cloud_liquid", 1.0e-4), ("cloud_water", 1.0e-4), ("ice", 3.0e-5)):      # condensate in a third of the cells
+            t = dm.get(name)
+            t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * scale)
+            t.mul_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) < 1.0 / 3.0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        c.set_option("micro", "kessler")
+        rad = RadiationGray().shortwave()
+        rad.init(c)
+        P = lambda name: dm.get(name).data_ptr()
+        e = torch.arange(nens, device=dev)
+        day = 0.3 + 0.7 * torch.rand(nens, generator=gen, dtype=torch.float64, device=dev)
+        suns = (("", day), ("_halfnight_interleaved", torch.where(e % 2 == 1, -day, day)), ("_halfnight_blocks", torch.where(e >= nens // 2, -day, day)))
+        for micro, liquid, ice, nin in (("kessler", ("cloud_liquid",), (), 3), ("p3", ("cloud_water",), ("ice",), 4)):
+            ltab, itab = (C.c_void_p * 2)(*[P(x) for x in liquid]), (C.c_void_p * 2)(*[P(x) for x in ice])
+            for tag, mu0 in suns:
+                dm.get("rad_coszen").copy_(mu0)
+                ncols_day = float((mu0 > 0).sum()) * nx * ny
+                nbytes = (ncols_day * nz * 8.0 * (2 * nin + 5) + (cols - ncols_day) * nz * 8.0 + (nz + 1) * nens * 8.0 + nens * 8.0 + 3 * cols * 8.0)
+                out["grayrad_sw_%s%s%s" % (micro, tag, label)] = row(timed(lambda: capi.check(lib.pam_amd_radiation_gray_sw(
+                    nens, nx, ny, nz, P("temp"), P("density_dry"), P("water_vapor"), len(liquid), ltab, len(ice), itab, P("vertical_interface_height"),
+                    P("rad_coszen"), None, 1361.0, 1e-6, 2e-3, 0.1, 0.1, 11.0, 5.0, 0.07, 1004.64, 2.0, P("rad_sw_heating"), P("rad_sw_down_sfc"),
+                    P("rad_sw_up_sfc"), P("rad_sw_up_top"), stream))), nbytes)
+                heat, down = dm.get("rad_sw_heating", readonly=True), dm.get("rad_sw_down_sfc", readonly=True)
+                assert bool(torch.isfinite(heat).all()) and bool((down[..., mu0 > 0] > 0).all()) and bool((down[..., mu0 <= 0] == 0).all())
+        lw = RadiationGray()
+        lw.init(c)                                                 # the options are there already: the longwave alone, Kessler's field set
+        c.set_option("rad_gray_shortwave", False)
+        out["grayrad_kessler" + label] = row(timed(lambda: lw.timeStep(c)), cells * 8.0 * 12 + (nz + 1) * nens * 8.0 + 3 * cols * 8.0)
+        c.set_option("micro", "p3")
+        modules.column_diagnostics_init(c)
+        out["column_diagnostics" + label] = row(timed(lambda: modules.column_diagnostics(c)), 5 * cells * 8.0 + 7 * cols * 16.0 + 2 * cols * 8.0)
+        for micro in ("kessler", "p3"):
+            out["grayrad_sw_%s%s_vs_grayrad_kessler_frac" % (micro, label)] = (out["grayrad_sw_%s%s" % (micro, label)]["hbm_frac"]
+                                                                             / out["grayrad_kessler" + label]["hbm_frac"])
+            for tag in ("_halfnight_interleaved", "_halfnight_blocks"):
+                out["grayrad_sw_%s%s%s_vs_day_time" % (micro, tag, label)] = (out["grayrad_sw_%s%s%s" % (micro, tag, label)]["ms"]
+                                                                            / out["grayrad_sw_%s%s" % (micro, label)]["ms"])
+        del c, dm, rad, lw
+        lib.pam_amd_modules_finalize()
+        torch.cuda.empty_cache()
+
+    out = {"grayrad_sw_grid": "1024 x 32x32x60 (C2) and 8192 x 32x1x60 (C4)",
+           "grayrad_sw_method": "%d warm-up calls, median of %d event-timed calls" % (warmup, n)}
+    grid(1024, 32, 32, 60, "", out)
+    grid(8192, 32, 1, 60, "_c4", out)
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "grayrad_sw"]:
+        print(json.dumps(grayrad_sw_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "grayrad"]:
         print(json.dumps(grayrad_timing(dev)))
         sys.exit(0)
