@@ -52,6 +52,7 @@
 #include "modules/perturb_temperature.h"
 #include "modules/saturation_adjustment.h"
 #include "modules/surface_friction.h"
+#include "modules/surface_fluxes.h"
 #include "modules/horizontal_average.h"
 #include "modules/time_average.h"
 #include "modules/mean_state_acceleration.h"
@@ -314,7 +315,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
-//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
+//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
 //          [--flux-profiles PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
@@ -419,6 +420,12 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              the lower boundary condition of uvel and vvel; composes with every other flag
 //   --sgs-moist                with --sgs-smag: option sgs_smag_moist, so the closure's stability carries the condensate loading and is
 //                              the saturated one inside cloud (the species of option "micro")
+//   --surface SST [DEPTH]      with --sgs-smag, and not with --sfc-fluxes: bulk surface fluxes over a slab ocean (modules/surface_fluxes.h).
+//                              modules::surface_fluxes_init(coupler, SST, DEPTH) once, option sgs_smag_surface_fluxes, then
+//                              modules::compute_surface_fluxes every CRM step after the sponge layer and before the surface friction and
+//                              the SGS: "sfc_shf" and "sfc_lhf" from the lowest level and "sfc_temp", which starts at SST [K] and, with
+//                              DEPTH > 0 [m of water], takes the net energy (with --radiation-gray [--shortwave] the radiation too).  One
+//                              "surface:" line per output step with the means of the three.  Composes with the rest.
 //   --sfc-fluxes SHF LHF       with --sgs-smag: option sgs_smag_surface_fluxes; "sfc_shf" and "sfc_lhf" are filled uniformly, once, with
 //                              SHF and LHF (W/m2, positive upward) and enter row 0 of temp and of the vapour in every SGS step.  Both
 //                              compose with every other flag
@@ -458,10 +465,10 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              prof_flux_v and prof_tke, printed with %.17g; nothing else of the run changes.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false, shortwave = false;
+  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false, shortwave = false, surface = false;
   int radiation_gray_every = 1;
   double sw_coszen = 1, sw_albedo = 0.07;
-  double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0, sfc_shf = 0, sfc_lhf = 0;
+  double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0, sfc_shf = 0, sfc_lhf = 0, surface_sst = 300, surface_depth = 0;
   int handoff_rad_nx = 0, handoff_rad_ny = 0;
   std::string handoff_path;
   double tau = 0, bflx = 0, accel_factor = 0, accel_max_ttend = 5.0, vt_rate = 0, vt_limit = 0.05;
@@ -575,7 +582,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       coupler.set_option<real>("sgs_smag_cs", mods.sgs_cs);
       coupler.set_option<real>("sgs_smag_prandtl", mods.sgs_prandtl);
       coupler.set_option<bool>("sgs_smag_moist", mods.sgs_moist);
-      coupler.set_option<bool>("sgs_smag_surface_fluxes", mods.sfc_fluxes);
+      coupler.set_option<bool>("sgs_smag_surface_fluxes", mods.sfc_fluxes || mods.surface);
       sgs_smag.init(coupler);
       if (mods.sfc_fluxes) {                                                 // --sfc-fluxes: the two entries, uniformly, once
         auto &sdm = coupler.get_data_manager_device_readwrite();
@@ -656,6 +663,8 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       realConst1d tau_in(sf_in, {nens}), bflx_in(sf_in + nens, {nens});
       coupler.run_module("surface_friction_init", [&](pam::PamCoupler &c) { modules::surface_friction_init(c, tau_in, bflx_in); });
     }
+    if (mods.surface)                                                        // --surface: after the friction's init, whose z0 it takes
+      coupler.run_module("surface_fluxes_init", [&](pam::PamCoupler &c) { modules::surface_fluxes_init(c, mods.surface_sst, mods.surface_depth); });
     const size_t ncell = (size_t)crm_nz * crm_ny * crm_nx * nens;
     std::vector<real> buf(ncell);
     auto fetch = [&](std::string const &name) {
@@ -709,6 +718,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         }
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         if (apply_sponge && !dbg.no_sponge) coupler.run_module("sponge_layer", modules::sponge_layer);         // driver.cpp:249-251
+        if (mods.surface) coupler.run_module("surface_fluxes", [](pam::PamCoupler &c) { modules::compute_surface_fluxes(c); });
         if (mods.surface_friction) coupler.run_module("surface_friction", modules::compute_surface_friction);
         if (mods.hyperdiff) coupler.run_module("hyperdiffusion", [](pam::PamCoupler &c) { modules::hyperdiffusion(c); });
         if (mods.sgs_smag) coupler.run_module("sgs", [&](pam::PamCoupler &c) { sgs_smag.timeStep(c); });
@@ -754,6 +764,13 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
               std::printf("radiation gray: etime %g , olr %.9g , lw_down_sfc %.9g , sw_down_sfc %.9g , sw_up_top %.9g\n", etime_gcm, so / n2, sd / n2,
                           ss / n2, st / n2);
             }
+          }
+          if (mods.surface) {                                                // the means over all columns and members, by the reproducible sum of
+            std::vector<pam::diagnostics::Item> items;                       // the scan behind DataManager::diagnose, one scan for the three
+            for (char const *n : {"sfc_shf", "sfc_lhf", "sfc_temp"})
+              items.push_back({n, 0, dm.get<real const, 3>(n).data(), (long long)crm_ny * crm_nx * nens, items.size()});
+            auto s3 = pam::diagnostics::scan(items, 0);
+            std::printf("surface: etime %g , shf %.9g , lhf %.9g , sfc_temp %.17g\n", etime_gcm, s3[0].mean(), s3[1].mean(), s3[2].mean());
           }
           char t[64];
           std::snprintf(t, sizeof(t), "%s%.6g", maxw_series.empty() ? "" : ",", maxw);
@@ -1042,6 +1059,12 @@ int main(int argc, char **argv) {
       }
       else if (o == "--sgs-moist") mods.sgs_moist = true;
       else if (o == "--sfc-fluxes" && b + 2 < argc - 1) { mods.sfc_fluxes = true; mods.sfc_shf = std::atof(argv[++b]); mods.sfc_lhf = std::atof(argv[++b]); }
+      else if (o == "--surface" && b + 1 < argc - 1) {
+        mods.surface = true;
+        mods.surface_sst = std::atof(argv[++b]);
+        const std::string n(b + 1 < argc - 1 ? argv[b + 1] : "");                // the optional DEPTH: an argument that is a number
+        if (!n.empty() && n.find_first_not_of("0123456789.eE+") == std::string::npos) mods.surface_depth = std::atof(argv[++b]);
+      }
       else if (o == "--gcm-handoff" && b + 3 < argc - 1) {
         mods.handoff = true;
         mods.handoff_rad_nx = std::atoi(argv[++b]);
@@ -1052,13 +1075,16 @@ int main(int argc, char **argv) {
       else if (o == "--flux-profiles" && b + 1 < argc - 1) mods.flux_profiles = argv[++b];
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] "
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] "
                "[--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->");
     }
     if (mods.radiation_gray && mods.radiation) die("--radiation-gray and --radiation both fill the one radiation slot: give one of them");
     if (mods.radiation_gray && mods.radiation_gray_every < 1) die("--radiation-gray EVERY must be >= 1");
     if (mods.shortwave && !mods.radiation_gray) die("--shortwave COSZEN [ALBEDO] needs --radiation-gray [EVERY]: the sun belongs to the native scheme");
     if ((mods.sgs_moist || mods.sfc_fluxes) && !mods.sgs_smag) die("--sgs-moist and --sfc-fluxes need --sgs-smag CS PRANDTL");
+    if (mods.surface && !mods.sgs_smag) die("--surface SST [DEPTH] needs --sgs-smag CS PRANDTL: the closure is what takes the fluxes up");
+    if (mods.surface && mods.sfc_fluxes) die("--surface and --sfc-fluxes both fill sfc_shf and sfc_lhf: give one of them");
+    if (mods.surface && (!(mods.surface_sst > 0) || mods.surface_depth < 0)) die("--surface SST [DEPTH] needs SST > 0 K and DEPTH >= 0 m");
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);
   }
 #endif

@@ -818,6 +818,51 @@ int pam_amd_radiation_gray_sw(int nens, int nx, int ny, int nz, double *temp, co
                               double *rad_sw_up_sfc, double *rad_sw_up_top, void *stream);
 int pam_amd_radiation_gray_sw_debug_wide_index(int on);
 
+/* Bulk surface fluxes over a slab ocean: the surface that pam_amd_sgs_smag_diffuse_fluxes and the two radiation kernels above name.  A
+ * bulk aerodynamic scheme with the stability functions of Louis 1979 in closed form turns the state of the lowest level into sfc_shf
+ * and sfc_lhf, and a slab of water takes the net energy: the four radiative fluxes at the surface minus the two turbulent ones.  With it
+ * the energy of column plus slab changes by what passes the model top and by nothing else.  Not part of the reference tree; the contract
+ * is this project's and is restated in numpy in tests/surface_ref.py, which the kernel matches bit for bit.
+ * temp, rho_d, rho_v, uvel, vvel (nz,ny,nx,nens): only level 0 is read.  zmid (nz,nens): only row 0 is read.  cn and cstar (nens) are
+ * DEVICE arrays, the neutral transfer coefficient and the coefficient of the unstable branch of every member, formed on the host once
+ * (pam_amd.modules.surface_fluxes_init, modules::surface_fluxes_init): lnz = log(zmid0 / z0), cn = (0.4 / lnz)^2, cstar = ((5.3 * 9.4)
+ * cn) sqrt(zmid0 / z0), so the device calls no logarithm.  sfc_temp (ny,nx,nens) is read, and written when the slab is stepped.
+ * lw_down, lw_up, sw_down, sw_up (ny,nx,nens) are DEVICE arrays or NULL, NULL in pairs (lw_down with lw_up, sw_down with sw_up); an absent
+ * pair contributes exactly 0.0.  gust in m/s enters the wind speed; wetness in [0, 1] scales the saturation ratio of the surface.
+ * slab_heat_capacity in J/m2/K is rho_w c_w depth; the layers above it use rho_w = 1000.0 and c_w = 4186.0.
+ * Everything is fp64, every operation is rounded on its own (no fma), every division is a true IEEE division, the square roots are
+ * IEEE, and the association is as written.  gc = grav / cp_d is formed once on the host.  Per (row, column, member), with the level-0
+ * values of the fields, Ts = sfc_temp at entry and z = zmid(0, e):
+ *   rho = rho_d + rho_v; qv = rho_v / rho;
+ *   w = sqrt((uvel uvel + vvel vvel) + gust gust);
+ *   sa = temp + gc z;
+ *   qs = wetness saturation_ratio(Ts, rho, R_v), the function of pam_amd_sgs_smag_coefficients_moist above over exp_c:
+ *     tc = Ts - 273.15; es = 610.94 exp_c((17.625 tc) / (243.04 + tc)); (es / (R_v Ts)) / rho;
+ *   tva = sa (1.0 + 0.608 qv); tvs = Ts (1.0 + 0.608 qs);
+ *   rib = ((grav z) (tva - tvs)) / (tvs (w w));
+ *   f = rib < 0 ? 1.0 - (9.4 rib) / (1.0 + cstar sqrt(-rib)) : 1.0 / ((1.0 + 4.7 rib) (1.0 + 4.7 rib)); a NaN rib takes the second
+ *     branch and stays a NaN;
+ *   ch = cn f;
+ *   sfc_shf = ((rho cp_d) (ch w)) (Ts - sa)        W/m2, positive upward;
+ *   sfc_lhf = ((rho latvap) (ch w)) (qs - qv)      W/m2, positive upward; dew (negative) is allowed and not clamped.
+ * The slab is stepped where slab_heat_capacity > 0 and dt != 0, after the fluxes, which come from Ts at entry:
+ *   net = ((sw_down - sw_up) + (lw_down - lw_up)) - (sfc_shf + sfc_lhf), an absent pair being 0.0 in place of its difference;
+ *   sfc_temp = Ts + (dt net) / slab_heat_capacity.
+ * With slab_heat_capacity == 0 or dt == 0 sfc_temp keeps its bits and no radiation input is read.
+ * Nothing is refused because of a value in a field; a NaN stays in its own (row, column, member).
+ * One launch, a thread per (row, column, member), members across the lanes; no scratch, no LDS, no atomics; only level 0 is addressed,
+ * so one index serves.  The same bits from run to run and for any split of the members over calls (with the matching slices of zmid, cn
+ * and cstar).  Momentum is not this scheme's: pam_amd_surface_friction_compute remains the source of sfc_mom_flx_u/v.
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: a size below 1; ny nx beyond 2^31 - 1; a NULL pointer
+ * other than the four radiation inputs; gust, dt or slab_heat_capacity negative or not finite; wetness outside [0, 1] (a NaN included);
+ * grav, cp_d, R_v or latvap not finite and positive; one of a radiation pair without the other; an output that overlaps an input or
+ * another output (sfc_temp counts as both).  Without a device a call whose arguments pass returns PAM_AMD_ENOGPU. */
+int pam_amd_surface_fluxes(int nens, int nx, int ny, int nz, const double *temp, const double *rho_d, const double *rho_v,
+                           const double *uvel, const double *vvel, const double *zmid, const double *cn, const double *cstar,
+                           double *sfc_temp, const double *lw_down, const double *lw_up, const double *sw_down, const double *sw_up,
+                           double gust, double wetness, double grav, double cp_d, double R_v, double latvap, double slab_heat_capacity,
+                           double dt, double *sfc_shf, double *sfc_lhf, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

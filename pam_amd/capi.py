@@ -209,6 +209,7 @@ MODULE_SYMBOLS = {
     "pam_amd_radiation_gray_sw": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int, C.POINTER(C.c_void_p)] * 2 + [C.c_void_p] * 3
                                   + [C.c_double] * 10 + [C.c_void_p] * 5),
     "pam_amd_radiation_gray_sw_debug_wide_index": (C.c_int, [C.c_int]),
+    "pam_amd_surface_fluxes": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 13 + [C.c_double] * 8 + [C.c_void_p] * 3),
 }
 
 

@@ -4184,3 +4184,75 @@ extern "C" int pam_amd_radiation_gray_sw(int nens, int nx, int ny, int nz, doubl
                        rad_sw_heating, rad_sw_down_sfc, rad_sw_up_sfc, rad_sw_up_top);
   return stats_launch_check(who);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Bulk surface fluxes over a slab ocean: sfc_shf and sfc_lhf from the state of the lowest level (Louis 1979 stability functions in closed
+// form), and sfc_temp from the net energy the slab takes.  Not in the reference tree; the contract is in include/pam_amd_modules.h and
+// DESIGN.md section 8, its arithmetic in surface_device.h.  ONE launch, a thread owns a (row, column, member), members and then x
+// across the lanes, so every access is a full line of level 0.  No scratch, no LDS, no atomics.  Only level 0 is addressed: the one
+// index is the thread's own t < ny nx nens, and there is no wide-index switch.  Whether the slab is stepped is a template argument and
+// whether a radiation pair is present a kernel argument: the same for every lane.
+#include "surface_device.h"
+
+namespace {
+namespace sf = pama::surface;
+constexpr int SURFACE_THREADS = 64;
+
+// grid (ceil(ny nx nens / 64)), block 64: thread t = (j nx + i) nens + e
+template <bool SLAB>
+__global__ void __launch_bounds__(SURFACE_THREADS) surface_fluxes_kernel(int nens, long long level, const double *__restrict__ temp,
+                                                                         const double *__restrict__ rho_d, const double *__restrict__ rho_v,
+                                                                         const double *__restrict__ uvel, const double *__restrict__ vvel,
+                                                                         const double *__restrict__ zmid, const double *__restrict__ cn,
+                                                                         const double *__restrict__ cstar, double *__restrict__ sfc_temp,
+                                                                         const double *__restrict__ lw_down, const double *__restrict__ lw_up,
+                                                                         const double *__restrict__ sw_down, const double *__restrict__ sw_up,
+                                                                         sf::Params P, double *__restrict__ sfc_shf,
+                                                                         double *__restrict__ sfc_lhf) {
+  const long long t = (long long)blockIdx.x * SURFACE_THREADS + (long long)threadIdx.x;
+  if (t >= level) return;
+  const int e = level <= 0x7fffffffLL ? (int)((unsigned)t % (unsigned)nens) : (int)(t % nens);
+  sf::column<SLAB>(temp + t, rho_d + t, rho_v + t, uvel + t, vvel + t, zmid + e, cn + e, cstar + e, sfc_temp + t, lw_down ? lw_down + t : nullptr,
+                   lw_up ? lw_up + t : nullptr, sw_down ? sw_down + t : nullptr, sw_up ? sw_up + t : nullptr, P, sfc_shf + t, sfc_lhf + t);
+}
+}  // namespace
+
+extern "C" int pam_amd_surface_fluxes(int nens, int nx, int ny, int nz, const double *temp, const double *rho_d, const double *rho_v,
+                                      const double *uvel, const double *vvel, const double *zmid, const double *cn, const double *cstar,
+                                      double *sfc_temp, const double *lw_down, const double *lw_up, const double *sw_down, const double *sw_up,
+                                      double gust, double wetness, double grav, double cp_d, double R_v, double latvap,
+                                      double slab_heat_capacity, double dt, double *sfc_shf, double *sfc_lhf, void *stream) {
+  const char *who = "surface_fluxes";
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return module_error(who, "nens, nx, ny and nz must be >= 1");
+  if ((long long)nx * ny > 0x7fffffffLL) return module_error(who, "ny x nx exceeds 2^31 - 1 columns");
+  const long long level = (long long)nx * ny * nens, cells = level * nz;
+  if ((level + SURFACE_THREADS - 1) / SURFACE_THREADS > 0x7fffffffLL) return module_error(who, "ny x nx x nens exceeds the grid");
+  if (!temp || !rho_d || !rho_v || !uvel || !vvel || !zmid || !cn || !cstar || !sfc_temp || !sfc_shf || !sfc_lhf)
+    return module_error(who, "null pointer");
+  for (double v : {gust, dt, slab_heat_capacity})
+    if (!grayrad_coefficient(v)) return module_error(who, "gust, dt and slab_heat_capacity must be finite and >= 0");
+  if (!(wetness >= 0 && wetness <= 1)) return module_error(who, "wetness must be in [0, 1]");
+  for (double v : {grav, cp_d, R_v, latvap})
+    if (!std::isfinite(v) || !(v > 0)) return module_error(who, "grav, cp_d, R_v and latvap must be finite and positive");
+  if (!lw_down != !lw_up) return module_error(who, "lw_down and lw_up come as a pair");
+  if (!sw_down != !sw_up) return module_error(who, "sw_down and sw_up come as a pair");
+  std::vector<Span> spans;
+  for (const double *p : {temp, rho_d, rho_v, uvel, vvel}) spans.push_back({p, cells, false});
+  spans.push_back({zmid, (long long)nz * nens, false});
+  for (const double *p : {cn, cstar}) spans.push_back({p, (long long)nens, false});
+  for (const double *p : {lw_down, lw_up, sw_down, sw_up})
+    if (p) spans.push_back({p, level, false});
+  for (double *p : {sfc_temp, sfc_shf, sfc_lhf}) spans.push_back({p, level, true});
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if (int rc = require_device(who)) return rc;
+
+  const sf::Params P{gust, wetness, grav, pama::sgs::ratio(grav, cp_d), cp_d, R_v, latvap, slab_heat_capacity, dt};
+  const dim3 grid((unsigned)((level + SURFACE_THREADS - 1) / SURFACE_THREADS)), block(SURFACE_THREADS);
+  if (slab_heat_capacity > 0 && dt != 0)
+    hipLaunchKernelGGL((surface_fluxes_kernel<true>), grid, block, 0, (hipStream_t)stream, nens, level, temp, rho_d, rho_v, uvel, vvel, zmid, cn, cstar,
+                       sfc_temp, lw_down, lw_up, sw_down, sw_up, P, sfc_shf, sfc_lhf);
+  else
+    hipLaunchKernelGGL((surface_fluxes_kernel<false>), grid, block, 0, (hipStream_t)stream, nens, level, temp, rho_d, rho_v, uvel, vvel, zmid, cn,
+                       cstar, sfc_temp, lw_down, lw_up, sw_down, sw_up, P, sfc_shf, sfc_lhf);
+  return stats_launch_check(who);
+}

@@ -981,3 +981,88 @@ def flux_profiles(coupler, weight=1):
     with torch.cuda.device(coupler.device):
         check(capi.load().pam_amd_flux_profiles(nens, nx, ny, nz, _msa_table(fields), threshold, _msa_table(out), factor,
                                                 torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+# ---- bulk surface fluxes over a slab ocean: the surface that SGSSmagorinsky(surface_fluxes=True) and RadiationGray name.  Not part of
+# the reference tree: the contract is this project's (include/pam_amd_modules.h at pam_amd_surface_fluxes; numpy
+# restatement: tests/surface_ref.py)
+SURFACE_FLUX_FIELDS = (("sfc_shf", "input surface sensible heat flux [W/m2]"), ("sfc_lhf", "input surface latent heat flux [W/m2]"))
+SURFACE_RADIATION = ("rad_lw_down_sfc", "rad_lw_up_sfc", "rad_sw_down_sfc", "rad_sw_up_sfc")
+SURFACE_Z0 = 1.0e-4                               # where neither the entry "z0" nor the argument gives one [m]
+SURFACE_RHO_W, SURFACE_C_W = 1000.0, 4186.0       # slab_heat_capacity = rho_w c_w depth
+SURFACE_LATVAP = 2501000.0                        # where the option "latvap" is absent, as SGSSmagorinsky has it
+
+
+def surface_transfer_parameters(zmid0, z0):
+    """host arithmetic, once: lnz = log(zmid0 / z0); cn = (0.4 / lnz)^2; cstar = ((5.3 * 9.4) cn) sqrt(zmid0 / z0); numpy arrays (nens)"""
+    import numpy as np
+    r = np.asarray(zmid0, dtype=np.float64) / np.asarray(z0, dtype=np.float64)
+    k = 0.4 / np.log(r)
+    cn = k * k
+    return cn, ((5.3 * 9.4) * cn) * np.sqrt(r)
+
+
+def surface_fluxes_init(coupler, sst=300.0, z0=None, slab_depth=0.0, gust=1.0, wetness=0.98):
+    """Once, after the grid is set: registers "sfc_temp" (ny,nx,nens) where absent and fills it with sst (a float or nens values; an
+    existing entry keeps its values), "sfc_shf" and "sfc_lhf" where absent under the names and descriptions SGSSmagorinsky uses, and
+    "sfc_cn" and "sfc_cstar" (nens), the transfer parameters of every member, formed on the host from row 0 of
+    "vertical_midpoint_height" and the roughness height: the entry "z0" where surface_friction_init has made one, else the argument z0 (a
+    float or nens values), else 1e-4 m.  Options "sfc_slab_depth" [m], "sfc_gust" [m/s] and "sfc_wetness" are set only where absent."""
+    import numpy as np
+    from .coupler import endrun
+    ny, nx, nens = coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+    dm = coupler.get_data_manager_device_readwrite()
+    if not dm.entry_exists("sfc_temp"):
+        dm.register_and_allocate("sfc_temp", "surface temperature [K]", (ny, nx, nens), ("y", "x", "nens"))
+        t = torch.as_tensor(sst, dtype=torch.float64, device=coupler.device)
+        if t.dim() > 1 or (t.dim() == 1 and t.numel() != nens):
+            endrun("ERROR: surface_fluxes_init: sst needs one value or nens values")
+        dm.get("sfc_temp").copy_(t.expand(ny, nx, nens))
+    for name, desc in SURFACE_FLUX_FIELDS:
+        if not dm.entry_exists(name):
+            dm.register_and_allocate(name, desc, (ny, nx, nens), ("y", "x", "nens"))
+    if dm.entry_exists("z0"):
+        z0 = dm.get("z0", readonly=True).cpu().numpy()
+    else:
+        z0 = np.broadcast_to(np.asarray(SURFACE_Z0 if z0 is None else z0, dtype=np.float64), (nens,))
+    if z0.shape != (nens,) or not (z0 > 0).all():
+        endrun("ERROR: surface_fluxes_init: z0 needs one positive value or nens positive values")
+    zmid0 = dm.get("vertical_midpoint_height", readonly=True)[0].cpu().numpy()
+    if not (zmid0 > z0).all():
+        endrun("ERROR: surface_fluxes_init: the lowest level must lie above the roughness height")
+    for name, desc, a in zip(("sfc_cn", "sfc_cstar"), ("neutral surface transfer coefficient [1]", "unstable-branch coefficient of the surface transfer [1]"),
+                             surface_transfer_parameters(zmid0, z0)):
+        if not dm.entry_exists(name):
+            dm.register_and_allocate(name, desc, (nens,), ("nens",))
+        dm.get(name).copy_(torch.as_tensor(a, dtype=torch.float64))
+    for name, value in (("sfc_slab_depth", float(slab_depth)), ("sfc_gust", float(gust)), ("sfc_wetness", float(wetness))):
+        if not coupler.option_exists(name):
+            coupler.set_option(name, value)
+
+
+def surface_fluxes(coupler, dt=None):
+    """Once per CRM step, before the surface friction and the SGS: "sfc_shf" and "sfc_lhf" from the lowest level and "sfc_temp", and, where
+    option "sfc_slab_depth" > 0, "sfc_temp" stepped by the net energy with slab_heat_capacity = 1000.0 * 4186.0 * slab_depth.  The entries
+    "rad_lw_down_sfc"/"rad_lw_up_sfc" and "rad_sw_down_sfc"/"rad_sw_up_sfc" are handed over by pairs where they exist.  Options "grav",
+    "cp_d", "R_v", and "latvap" where it exists.  dt: default the option "crm_dt"."""
+    from .coupler import endrun
+    dm = coupler.get_data_manager_device_readwrite()
+    if not dm.entry_exists("sfc_cn"):
+        endrun("ERROR: surface_fluxes: call surface_fluxes_init first")
+    lib = capi.load()
+    inputs = [dm.get(n, readonly=True) for n in ("temp", "density_dry", "water_vapor", "uvel", "vvel", "vertical_midpoint_height", "sfc_cn",
+                                                 "sfc_cstar")]
+    rad = []
+    for down, up in (SURFACE_RADIATION[:2], SURFACE_RADIATION[2:]):
+        both = dm.entry_exists(down) and dm.entry_exists(up)
+        rad += [dm.get(down, readonly=True).data_ptr(), dm.get(up, readonly=True).data_ptr()] if both else [None, None]
+    dt = float(coupler.get_option("crm_dt") if dt is None else dt)
+    latvap = float(coupler.get_option("latvap")) if coupler.option_exists("latvap") else SURFACE_LATVAP
+    cap = SURFACE_RHO_W * SURFACE_C_W * float(coupler.get_option("sfc_slab_depth"))
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_surface_fluxes(coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(),
+                                         *[a.data_ptr() for a in inputs], dm.get("sfc_temp").data_ptr(), *rad,
+                                         float(coupler.get_option("sfc_gust")), float(coupler.get_option("sfc_wetness")),
+                                         float(coupler.get_option("grav")), float(coupler.get_option("cp_d")), float(coupler.get_option("R_v")),
+                                         latvap, cap, dt, dm.get("sfc_shf").data_ptr(), dm.get("sfc_lhf").data_ptr(),
+                                         torch.cuda.current_stream(coupler.device).cuda_stream))

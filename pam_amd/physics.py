@@ -257,8 +257,9 @@ class SGSSmagorinsky:
     and mixes uvel, vvel, wvel, temp and every registered tracer along the column, with "sfc_mom_flx_u/v" (compute_surface_friction
     fills them) as the lower boundary condition of the horizontal winds.  density_dry is never written.
     moist: the stability carries the loading of every condensate and is the saturated one inside cloud (the species by option "micro";
-    options "R_d" and "R_v" are read).  surface_fluxes: "sfc_shf" and "sfc_lhf" (W/m2, positive upward; whoever drives the run fills them)
-    enter row 0 of temp and of the vapour, with option "latvap" where it exists.  With both off the two dry entry points are called."""
+    options "R_d" and "R_v" are read).  surface_fluxes: "sfc_shf" and "sfc_lhf" (W/m2, positive upward; pam_amd.modules.surface_fluxes
+    fills them, or whoever drives the run) enter row 0 of temp and of the vapour, with option "latvap" where it exists.  With both off
+    the two dry entry points are called."""
     FIELDS = (("tk", 4), ("tkh", 4), ("sfc_mom_flx_u", 3), ("sfc_mom_flx_v", 3))
     FLUX_FIELDS = (("sfc_shf", "input surface sensible heat flux [W/m2]"), ("sfc_lhf", "input surface latent heat flux [W/m2]"))
     OPTIONS = ("sgs", "sgs_smag_cs", "sgs_smag_prandtl", "sgs_smag_moist", "sgs_smag_surface_fluxes", "sgs_smag_cloud_threshold")

@@ -23,6 +23,8 @@ with the surface fluxes of heat and vapour) on Kessler's field set at the C2 gri
 hyperdiffusion and msa_apply of the same run;
 --only grayrad: the native grey two-stream longwave scheme (pam_amd_radiation_gray) at the C2 grid and at C4's 32x1x60 grid with 8192
 members on Kessler's and on P3's field set, beside column_diagnostics and pam_amd_sgs_smag_coefficients of the same run;
+--only surface: the bulk surface fluxes over a slab ocean (pam_amd_surface_fluxes) at the C2 grid and at C4's 32x1x60 grid with 8192
+members, with the slab and all four radiation inputs and without either, beside compute_surface_friction of the same run;
 --only grayrad_sw: the scheme's shortwave (pam_amd_radiation_gray_sw) on the same grids and field sets, with every member under the sun
 and with half of the members at night (interleaved with the day members inside every wavefront, and in blocks of whole wavefronts),
 beside pam_amd_radiation_gray and column_diagnostics of the same run;
@@ -1535,8 +1537,103 @@ def grayrad_sw_timing(dev, warmup=3, n=11):
     return out
 
 
+def surface_timing(dev, warmup=3, n=11):
+    """The bulk surface fluxes over a slab ocean (pam_amd_surface_fluxes) at the C2 grid and at C4's 32x1x60 grid with 8192 members: the
+    method is grayrad_sw_timing's, 3 warm-up calls and the median of 11 event-timed calls each.  Rows: the slab on with all four radiation
+    inputs, and the slab off with the radiation inputs NULL.  Algorithmic bytes per column: 8 B for each array touched (level 0 of temp,
+    rho_d, rho_v, uvel, vvel; sfc_shf and sfc_lhf; the four radiation inputs where given) and 16 B for sfc_temp when the slab is on (8 B
+    when it is only read): 104 B and 64 B; plus zmid row 0, cn and cstar.  compute_surface_friction of the same run stands beside them as
+    the yardstick, with the byte count moist_surface_timing gives it.  The call moves about 0.1 GB at C2, so the time of a launch is
+    part of every figure, and a repeated call finds its lines in the last-level cache: every row is given twice, as repeated and (_cold)
+    after 512 MiB written to another buffer before each timed call."""
+    from pam_amd import PamCoupler, capi, modules
+    from pam_amd import idealized as idz
+    lib = capi.load()
+
+    def timed(fn, evict=None):
+        for _ in range(warmup):
+            fn()
+        ts = []
+        for _ in range(n):
+            if evict is not None:
+                evict()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    def row(t, nbytes):
+        return {"ms": t[0], "min_ms": t[1], "max_ms": t[2], "bytes": nbytes, "GBps": nbytes / t[0] / 1e6,
+                "hbm_frac": nbytes / t[0] / 1e6 / bench.HBM_PEAK_GBS}
+
+    def grid(nens, nx, ny, nz, label, out):
+        cols = nens * nx * ny
+        c = PamCoupler(dev)
+        for name, v in (("crm_dt", 2.0), ("grav", 9.80616), ("cp_d", 1004.64), ("R_d", 287.042), ("R_v", 461.505)):
+            c.set_option(name, v)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+        c.add_tracer("water_vapor", "", True, True)
+        dm = c.get_data_manager_device_readwrite()
+        gen = torch.Generator(device=dev).manual_seed(0)
+        rand = lambda shape: torch.rand(shape, generator=gen, dtype=torch.float64, device=dev)
+        k = torch.arange(nz, dtype=torch.float64, device=dev)[:, None, None, None]
+        for name, scale in (("temp", 299.0 - 1.2 * k), ("density_dry", 1.15 * torch.exp(-k / 25.0)), ("water_vapor", 1.6e-2 * torch.exp(-k / 10.0))):
+            t = dm.get(name)
+            t.copy_((rand(t.shape) * 0.1 + 0.95) * scale)
+        for name in ("uvel", "vvel"):
+            t = dm.get(name)
+            t.copy_(rand(t.shape) * 16.0 - 8.0)
+        for name, lo, hi in (("rad_lw_down_sfc", 350.0, 420.0), ("rad_lw_up_sfc", 440.0, 470.0), ("rad_sw_down_sfc", 0.0, 900.0)):
+            dm.register_and_allocate(name, "surface radiative flux [W/m2]", (ny, nx, nens), ("y", "x", "nens"))
+            dm.get(name).copy_(lo + (hi - lo) * rand((ny, nx, nens)))
+        dm.register_and_allocate("rad_sw_up_sfc", "surface radiative flux [W/m2]", (ny, nx, nens), ("y", "x", "nens"))
+        dm.get("rad_sw_up_sfc").copy_(0.07 * dm.get("rad_sw_down_sfc"))
+        modules.surface_fluxes_init(c, sst=300.0, slab_depth=1.0)
+        # half of the surface warmer than the air, half colder: both branches of the stability function in every wavefront
+        dm.get("sfc_temp").copy_(dm.get("temp")[0] + 8.0 * rand((ny, nx, nens)) - 4.0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        P = lambda name: dm.get(name).data_ptr()
+        small = (nens + 2 * nens) * 8.0
+        # what a call touches (0.1 GB at C2) fits the 256 MiB last-level cache, and a repeated call finds it there: the plain rows are that
+        # case.  The _cold rows write 512 MiB to another buffer before every timed call, as a CRM step's other kernels would
+        scratch = torch.empty(64 * 1024 * 1024, dtype=torch.float64, device=dev)
+        for tag, rad, cap, per_col in (("_slab_radiation", [P(x) for x in modules.SURFACE_RADIATION], 4186000.0, 104.0), ("_fluxes_only", [None] * 4, 0.0, 64.0)):
+            call = lambda: capi.check(lib.pam_amd_surface_fluxes(
+                nens, nx, ny, nz, P("temp"), P("density_dry"), P("water_vapor"), P("uvel"), P("vvel"), P("vertical_midpoint_height"), P("sfc_cn"),
+                P("sfc_cstar"), P("sfc_temp"), *rad, 1.0, 0.98, 9.80616, 1004.64, 461.505, 2501000.0, cap, 2.0, P("sfc_shf"), P("sfc_lhf"), stream))
+            out["surface" + tag + label] = row(timed(call), cols * per_col + small)
+            out["surface" + tag + "_cold" + label] = row(timed(call, lambda: scratch.fill_(1.0)), cols * per_col + small)
+            assert bool(torch.isfinite(dm.get("sfc_shf", readonly=True)).all()) and bool(torch.isfinite(dm.get("sfc_temp", readonly=True)).all())
+        tau = torch.full((nens,), 0.1, dtype=torch.float64, device=dev)
+        bflx = torch.full((nens,), 0.01, dtype=torch.float64, device=dev)
+        dm.get("gcm_uvel").copy_(dm.get("uvel").mean(dim=(1, 2)))
+        dm.get("gcm_vvel").copy_(dm.get("vvel").mean(dim=(1, 2)))
+        modules.surface_friction_init(c, tau, bflx)
+        out["compute_surface_friction" + label] = row(timed(lambda: modules.compute_surface_friction(c)), cols * 10 * 8.0)
+        out["compute_surface_friction_cold" + label] = row(timed(lambda: modules.compute_surface_friction(c), lambda: scratch.fill_(1.0)), cols * 10 * 8.0)
+        for tag in ("_slab_radiation", "_fluxes_only"):
+            out["surface%s%s_vs_friction_time" % (tag, label)] = out["surface" + tag + label]["ms"] / out["compute_surface_friction" + label]["ms"]
+        del c, dm, scratch
+        lib.pam_amd_modules_finalize()
+        torch.cuda.empty_cache()
+
+    out = {"surface_grid": "1024 x 32x32x60 (C2) and 8192 x 32x1x60 (C4)",
+           "surface_method": "%d warm-up calls, median of %d event-timed calls" % (warmup, n), "hbm_peak_GBps": bench.HBM_PEAK_GBS}
+    grid(1024, 32, 32, 60, "", out)
+    grid(8192, 32, 1, 60, "_c4", out)
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "surface"]:
+        print(json.dumps(surface_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "grayrad_sw"]:
         print(json.dumps(grayrad_sw_timing(dev)))
         sys.exit(0)
