@@ -1,15 +1,11 @@
 """ctypes binding of tests/emu/coldiag_emu.cpp (host emulation of the CRM column diagnostics kernels).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tools.native_build import emu_library
 from coldiag_ref import FIELDS, OUT, PRECIP
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "coldiag_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libcoldiag_emu.so")
 _DP = C.POINTER(C.c_double)
 _LIB = None
 ASCENDING, REVERSED, ROLLED = 0, 1, 2                        # the order of the scan's threads; its levels one by one
@@ -19,11 +15,7 @@ BLOCK_SLOTS, THREAD_SLOTS, FOUR_WALKERS = 1, 2, 3            # who holds the 16 
 def load():
     global _LIB
     if _LIB is None:
-        deps = [_SRC] + [os.path.join(_HERE, "..", "pam_amd", "csrc", h) for h in ("coldiag_device.h", "rad_device.h", "msa_device.h",
-                                                                                "plugins_device.h")]
-        if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _SO, _SRC], check=True)
-        lib = C.CDLL(_SO)
+        lib = C.CDLL(emu_library("coldiag_emu"))
         lib.emu_column_diagnostics.restype = C.c_int
         lib.emu_column_diagnostics.argtypes = [C.c_int] * 4 + [C.POINTER(_DP), _DP, C.POINTER(_DP)] + [C.c_double] * 5 + [C.POINTER(_DP), C.c_double] + \
             [C.c_int] * 3

@@ -1,24 +1,16 @@
 """ctypes binding of tests/emu/awfl_emu.cpp (host emulation of the HIP kernel bodies).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "awfl_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libawfl_emu.so")
+from tools.native_build import emu_library
+
 _DP = C.POINTER(C.c_double)
 _LIB = None
 
 
 def build():
-    deps = [_SRC] + [os.path.join(_HERE, "..", "pam_amd", "csrc", f) for f in
-                     ("awfl_device.h", "awfl_vertical.h", "awfl_constants.h")]
-    if os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps):
-        return _SO
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _SO, _SRC], check=True)
-    return _SO
+    return emu_library("awfl_emu")
 
 
 def load():

@@ -1,15 +1,11 @@
 """ctypes binding of tests/emu/fluxprof_emu.cpp (host emulation of the CRM flux profiles kernel).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tools.native_build import emu_library
 from fluxprof_ref import FIELDS, OUT
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "fluxprof_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libfluxprof_emu.so")
 _DP = C.POINTER(C.c_double)
 _LIB = None
 KERNEL, REVERSED, ONE_WALKER = 0, 1, 2                      # who holds the 16 slots of a member, and in which order they run
@@ -18,10 +14,7 @@ KERNEL, REVERSED, ONE_WALKER = 0, 1, 2                      # who holds the 16 s
 def load():
     global _LIB
     if _LIB is None:
-        deps = [_SRC] + [os.path.join(_HERE, "..", "pam_amd", "csrc", h) for h in ("fluxprof_device.h", "vt_device.h", "msa_device.h")]
-        if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _SO, _SRC], check=True)
-        lib = C.CDLL(_SO)
+        lib = C.CDLL(emu_library("fluxprof_emu"))
         lib.emu_flux_profiles.restype = C.c_int
         lib.emu_flux_profiles.argtypes = [C.c_int] * 4 + [C.POINTER(_DP), C.c_double, C.POINTER(_DP), C.c_double] + [C.c_int] * 2
         _LIB = lib

@@ -1,13 +1,10 @@
 """ctypes binding of tests/emu/grayrad_emu.cpp (host emulation of the grey radiation kernel).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "grayrad_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libgrayrad_emu.so")
+from tools.native_build import emu_library
+
 _DP = C.POINTER(C.c_double)
 _TAB = C.POINTER(C.c_void_p)
 _LIB = None
@@ -17,13 +14,7 @@ SCALARS = ("k_d", "k_v", "k_l", "k_i", "sigma", "cp_d", "lw_down_top", "dt")
 def load():
     global _LIB
     if _LIB is None:
-        csrc = os.path.join(_HERE, "..", "pam_amd", "csrc")
-        deps = [_SRC] + [os.path.join(csrc, h) for h in ("grayrad_device.h", "sgs_device.h", "msa_device.h")]
-        if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-            tmp = "%s.%d.tmp" % (_SO, os.getpid())      # built beside it and moved into place: another process never loads half a file
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", tmp, _SRC], check=True)
-            os.replace(tmp, _SO)
-        lib = C.CDLL(_SO)
+        lib = C.CDLL(emu_library("grayrad_emu"))
         lib.emu_radiation_gray.restype = None
         lib.emu_radiation_gray.argtypes = [C.c_int] * 4 + [_DP] * 3 + [C.c_int, _TAB] * 2 + [_DP, C.c_void_p] + [C.c_double] * 8 + [_DP] * 4 + [C.c_int]
         _LIB = lib

@@ -1,15 +1,11 @@
 """ctypes binding of tests/emu/grayrad_sw_emu.cpp (host emulation of the grey shortwave kernel).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tools.native_build import emu_library
 from grayrad_sw_ref import SCALARS
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "grayrad_sw_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libgrayrad_sw_emu.so")
 _DP = C.POINTER(C.c_double)
 _TAB = C.POINTER(C.c_void_p)
 _LIB = None
@@ -19,13 +15,7 @@ POISON = -7.0e77
 def load():
     global _LIB
     if _LIB is None:
-        csrc = os.path.join(_HERE, "..", "pam_amd", "csrc")
-        deps = [_SRC] + [os.path.join(csrc, h) for h in ("grayrad_sw_device.h", "grayrad_device.h", "sgs_device.h", "msa_device.h")]
-        if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-            tmp = "%s.%d.tmp" % (_SO, os.getpid())      # built beside it and moved into place: another process never loads half a file
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", tmp, _SRC], check=True)
-            os.replace(tmp, _SO)
-        lib = C.CDLL(_SO)
+        lib = C.CDLL(emu_library("grayrad_sw_emu"))
         lib.emu_radiation_gray_sw.restype = None
         lib.emu_radiation_gray_sw.argtypes = ([C.c_int] * 4 + [_DP] * 3 + [C.c_int, _TAB] * 2 + [_DP, _DP, C.c_void_p] + [C.c_double] * 10 + [_DP] * 4
                                               + [C.c_int])

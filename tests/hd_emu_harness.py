@@ -1,13 +1,10 @@
 """ctypes binding of tests/emu/hd_emu.cpp (host emulation of the hyperdiffusion kernels).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "hd_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libhd_emu.so")
+from tools.native_build import emu_library
+
 _DP = C.POINTER(C.c_double)
 _LIB = None
 PATHS = ("in_place", "workspace", "narrow", "single")      # the entry point's paths; the ring also at member blocks of a quarter and of one
@@ -16,13 +13,7 @@ PATHS = ("in_place", "workspace", "narrow", "single")      # the entry point's p
 def load():
     global _LIB
     if _LIB is None:
-        csrc = os.path.join(_HERE, "..", "pam_amd", "csrc")
-        deps = [_SRC, os.path.join(csrc, "hd_device.h"), os.path.join(csrc, "msa_device.h")]
-        if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-            tmp = "%s.%d.tmp" % (_SO, os.getpid())      # built beside it and moved into place: another process never loads half a file
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", tmp, _SRC], check=True)
-            os.replace(tmp, _SO)
-        lib = C.CDLL(_SO)
+        lib = C.CDLL(emu_library("hd_emu"))
         lib.emu_hd_line.restype = None
         lib.emu_hd_line.argtypes = [C.c_int] * 3 + [_DP, C.c_double]
         lib.emu_hd_ring.restype = None

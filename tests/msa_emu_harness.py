@@ -1,15 +1,11 @@
 """ctypes binding of tests/emu/msa_emu.cpp (host emulation of the mean-state acceleration kernels).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tools.native_build import emu_library
 from msa_ref import FIELDS, QUANTITIES
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "msa_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libmsa_emu.so")
 _DP = C.POINTER(C.c_double)
 _LIB = None
 
@@ -17,10 +13,7 @@ _LIB = None
 def load():
     global _LIB
     if _LIB is None:
-        deps = [_SRC, os.path.join(_HERE, "..", "pam_amd", "csrc", "msa_device.h")]
-        if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _SO, _SRC], check=True)
-        lib = C.CDLL(_SO)
+        lib = C.CDLL(emu_library("msa_emu"))
         lib.emu_msa_mean.restype = None
         lib.emu_msa_mean.argtypes = [C.c_int] * 4 + [C.POINTER(_DP)] * 3 + [C.c_double, C.POINTER(C.c_int), C.c_int]
         lib.emu_msa_apply.restype = None

@@ -3,7 +3,6 @@ unpack, shared by tests/test_p3_coupling.py and tests/test_p3_coupling_gpu.py.  
 import ctypes as C
 import functools
 import os
-import subprocess
 
 import numpy as np
 
@@ -11,10 +10,9 @@ import emu_harness
 import p3_coupling_ref as ref
 from pam_amd import capi
 from pam_amd.physics import p3_shapes
+from tools.native_build import emu_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "p3_emu.cpp")
-EMU_SO = os.path.join(ROOT, "tests", "emu", "libp3_emu.so")
 _DP = C.POINTER(C.c_double)
 _PP = C.POINTER(C.c_void_p)
 # (nz, ny, nx, nens): the SHOC list -- a partial tile on the column and on the level axis, one and several wavefronts, nens around 64,
@@ -91,11 +89,7 @@ def restated_case(shape, adjust, first_step):
 # the host emulation
 
 def emu():
-    deps = [EMU_SRC, os.path.join(ROOT, "include", "pam_amd_modules.h")] + [os.path.join(ROOT, "pam_amd", "csrc", f) for f in
-                                                                            ("p3_device.h", "moist_surface_device.h", "awfl_device.h", "awfl_vertical.h")]
-    if not (os.path.exists(EMU_SO) and all(os.path.getmtime(EMU_SO) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", EMU_SO, EMU_SRC], check=True)
-    lib = C.CDLL(EMU_SO)
+    lib = C.CDLL(emu_library("p3_emu"))
     lib.emu_p3_offset.restype = C.c_longlong
     lib.emu_p3_offset.argtypes = [C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.emu_p3_pack.restype = None

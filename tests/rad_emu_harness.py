@@ -1,15 +1,11 @@
 """ctypes binding of tests/emu/rad_emu.cpp (host emulation of the CRM-to-GCM handoff kernels).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tools.native_build import emu_library
 from rad_ref import FB_FIELDS, FIELDS, GCM, QUANTITIES, RAD, SPECIES
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "rad_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "librad_emu.so")
 _DP = C.POINTER(C.c_double)
 _LIB = None
 BLOCK_SLOTS, THREAD_SLOTS, FOUR_WALKERS = 1, 2, 3
@@ -18,10 +14,7 @@ BLOCK_SLOTS, THREAD_SLOTS, FOUR_WALKERS = 1, 2, 3
 def load():
     global _LIB
     if _LIB is None:
-        deps = [_SRC] + [os.path.join(_HERE, "..", "pam_amd", "csrc", h) for h in ("rad_device.h", "msa_device.h")]
-        if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _SO, _SRC], check=True)
-        lib = C.CDLL(_SO)
+        lib = C.CDLL(emu_library("rad_emu"))
         lib.emu_rad_aggregate.restype = C.c_int
         lib.emu_rad_aggregate.argtypes = [C.c_int] * 6 + [C.POINTER(_DP)] * 2 + [C.c_double, C.c_int, C.c_int]
         lib.emu_crm_feedback.restype = C.c_int

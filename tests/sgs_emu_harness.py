@@ -1,15 +1,11 @@
 """ctypes binding of tests/emu/sgs_emu.cpp (host emulation of the Smagorinsky SGS kernels).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tools.native_build import emu_library
 import sgs_ref as ref
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "sgs_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libsgs_emu.so")
 _DP = C.POINTER(C.c_double)
 _LIB = None
 PATHS = ("lds", "workspace", "lds_narrow")      # c' in LDS rows of 64 lanes, in the workspace, and in LDS rows of 5 lanes
@@ -18,13 +14,7 @@ PATHS = ("lds", "workspace", "lds_narrow")      # c' in LDS rows of 64 lanes, in
 def load():
     global _LIB
     if _LIB is None:
-        csrc = os.path.join(_HERE, "..", "pam_amd", "csrc")
-        deps = [_SRC, os.path.join(csrc, "sgs_device.h"), os.path.join(csrc, "msa_device.h")]
-        if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-            tmp = "%s.%d.tmp" % (_SO, os.getpid())      # built beside it and moved into place: another process never loads half a file
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", tmp, _SRC], check=True)
-            os.replace(tmp, _SO)
-        lib = C.CDLL(_SO)
+        lib = C.CDLL(emu_library("sgs_emu"))
         lib.emu_sgs_coefficients.restype = None
         lib.emu_sgs_coefficients.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_void_p), _DP, _DP] + [C.c_double] * 6 + [_DP, _DP]
         lib.emu_sgs_diffuse.restype = None

@@ -1,16 +1,12 @@
 """ctypes binding of tests/emu/sgs_moist_emu.cpp (host emulation of the moist coefficient kernel and of the solve with surface fluxes of
 heat and vapour).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tools.native_build import emu_library
 import sgs_moist_ref as mref
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "sgs_moist_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libsgs_moist_emu.so")
 _DP = C.POINTER(C.c_double)
 _TAB = C.POINTER(C.c_void_p)
 _LIB = None
@@ -21,13 +17,7 @@ SIX = mref.WINDS + ("temp", "density_dry", "water_vapor")
 def load():
     global _LIB
     if _LIB is None:
-        csrc = os.path.join(_HERE, "..", "pam_amd", "csrc")
-        deps = [_SRC, os.path.join(csrc, "sgs_device.h"), os.path.join(csrc, "msa_device.h")]
-        if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-            tmp = "%s.%d.tmp" % (_SO, os.getpid())      # built beside it and moved into place: another process never loads half a file
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", tmp, _SRC], check=True)
-            os.replace(tmp, _SO)
-        lib = C.CDLL(_SO)
+        lib = C.CDLL(emu_library("sgs_moist_emu"))
         lib.emu_sgs_exp_c.restype = None
         lib.emu_sgs_exp_c.argtypes = [_DP, _DP, C.c_longlong]
         lib.emu_sgs_coefficients_moist.restype = None

@@ -1,15 +1,11 @@
 """ctypes binding of tests/emu/surface_emu.cpp (host emulation of the surface-flux kernel).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tools.native_build import emu_library
 from surface_ref import FIELDS, RADIATION, SCALARS
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "surface_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libsurface_emu.so")
 _DP = C.POINTER(C.c_double)
 _LIB = None
 POISON = -7.0e77
@@ -18,13 +14,7 @@ POISON = -7.0e77
 def load():
     global _LIB
     if _LIB is None:
-        csrc = os.path.join(_HERE, "..", "pam_amd", "csrc")
-        deps = [_SRC] + [os.path.join(csrc, h) for h in ("surface_device.h", "sgs_device.h", "msa_device.h")]
-        if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-            tmp = "%s.%d.tmp" % (_SO, os.getpid())      # built beside it and moved into place: another process never loads half a file
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", tmp, _SRC], check=True)
-            os.replace(tmp, _SO)
-        lib = C.CDLL(_SO)
+        lib = C.CDLL(emu_library("surface_emu"))
         lib.emu_surface_fluxes.restype = None
         lib.emu_surface_fluxes.argtypes = [C.c_int] * 4 + [_DP] * 9 + [C.c_void_p] * 4 + [C.c_double] * 8 + [_DP] * 2
         _LIB = lib

@@ -15,6 +15,7 @@ import coldiag_ref as ref
 import test_boundary_surface as tb
 from coldiag_emu_harness import ASCENDING, BLOCK_SLOTS, FOUR_WALKERS, REVERSED, ROLLED, THREAD_SLOTS, EmuBackend
 from pam_amd import capi
+from tools import native_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
@@ -369,19 +370,9 @@ def test_python_layer_has_the_signatures_of_the_contract():
     assert dict(modules.COLUMN_DIAGNOSTICS_DEFAULTS) == {"crm_diag_p_low": 70000.0, "crm_diag_p_high": 40000.0, "crm_diag_cwp_threshold": 1.0e-3}
 
 
-CXX_SRC = os.path.join(ROOT, "tests", "cxx", "column_diag.cpp")
-CXX_EXE = os.path.join(ROOT, "tests", "cxx", "column_diag")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
 def cxx_program():
     """tests/cxx/column_diag, built the way the examples' driver is built (no device is needed to build it)"""
-    deps = [CXX_SRC, HEADER, os.path.join(HOST, "pam_coupler.h"), os.path.join(ROOT, "include", "pam_amd_modules.h"), capi.LIB_PATH]
-    if not (os.path.exists(CXX_EXE) and all(os.path.getmtime(CXX_EXE) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + HOST, CXX_SRC, "-L" + os.path.join(ROOT, "pam_amd"), "-lpam_amd_awfl",
-                        "-Wl,-rpath,$ORIGIN/../../pam_amd", "-o", CXX_EXE], check=True)
-    return CXX_EXE
+    return native_build.cxx_program("column_diag")
 
 
 def test_header_compiles_into_a_host_program():

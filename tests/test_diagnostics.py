@@ -19,16 +19,11 @@ import pytest
 
 import diagnostics_ref as ref
 from pam_amd import capi
+from tools.native_build import cxx_program, emu_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "diagnostics_emu.cpp")
-EMU_SO = os.path.join(ROOT, "tests", "emu", "libdiagnostics_emu.so")
-CXX_SRC = os.path.join(ROOT, "tests", "cxx", "diagnose_dm.cpp")
-CXX_EXE = os.path.join(ROOT, "tests", "cxx", "diagnose_dm")
 DRIVER = os.path.join(ROOT, "examples", "driver")
 CI_YAML = os.path.join(ROOT, "tests", "golden", "ci_input_pama.yaml")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KIND_NAMES = ["double", "float"]
 OFFSETS = [(0, 0), (0, 1), (1, 0), (1, 1), (1, 2), (1, 3)]          # (kind, elements past a 16-byte boundary)
 OFFSET_IDS = ["%s_off%d" % (KIND_NAMES[k], o) for k, o in OFFSETS]
@@ -167,10 +162,7 @@ def test_member_results_do_not_depend_on_member_chunking():
 
 @functools.lru_cache(maxsize=None)
 def emu():
-    deps = [EMU_SRC, os.path.join(ROOT, "pam_amd", "csrc", "diagnostics_device.h")]
-    if not (os.path.exists(EMU_SO) and all(os.path.getmtime(EMU_SO) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", EMU_SO, EMU_SRC], check=True)
-    lib = C.CDLL(EMU_SO)
+    lib = C.CDLL(emu_library("diagnostics_emu"))
     lib.emu_field_diagnostics.restype = C.c_int
     lib.emu_field_diagnostics.argtypes = [C.c_int, C.POINTER(C.c_int), _LP, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_longlong, C.c_void_p]
     return lib
@@ -509,15 +501,6 @@ def test_gpu_python_datamanager_diagnoses_every_entry():
     assert same(dm.diagnose("ens", members=4), per["ens"])
 
 
-def _cxx_exe():
-    deps = [CXX_SRC, os.path.join(HOST, "pam_coupler.h"), os.path.join(HOST, "data_diagnostics.h"), capi.LIB_PATH]
-    if not (os.path.exists(CXX_EXE) and all(os.path.getmtime(CXX_EXE) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + HOST, CXX_SRC, "-L" + os.path.join(ROOT, "pam_amd"), "-lpam_amd_awfl",
-                        "-Wl,-rpath,$ORIGIN/../../pam_amd", "-o", CXX_EXE], check=True)
-    return CXX_EXE
-
-
 @pytest.mark.gpu
 def test_gpu_cxx_adaptor_prints_the_reference_lines_and_returns_the_values(tmp_path):
     """DEBUG_PRINT_SUM / AVG / MIN / MAX on the work-alike's arrays: the reference's lines (pam_const.h:308-322) with the restatement's
@@ -535,7 +518,7 @@ def test_gpu_cxx_adaptor_prints_the_reference_lines_and_returns_the_values(tmp_p
     script += ["diagnose %s 0" % n for n, _ in entries] + ["diagnose_all 0", "diagnose ens 4", "diagnose_all 4", "diagnose ints 0"]
     path = tmp_path / "script.txt"
     path.write_text("\n".join(script) + "\n")
-    r = subprocess.run([_cxx_exe(), str(path)], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([cxx_program("diagnose_dm"), str(path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     lines = re.findall(r"^\*\*\* DEBUG: (\S+): (\d+): (sum|avg|minval|maxval)\(var\)  -->  (\S+)$", r.stdout, flags=re.M)
     assert len(lines) == 4 * len(entries) and all(l[0].endswith("diagnose_dm.cpp") for l in lines)

@@ -15,6 +15,7 @@ import fluxprof_ref as ref
 import test_boundary_surface as tb
 from fluxprof_emu_harness import KERNEL, ONE_WALKER, REVERSED, EmuBackend
 from pam_amd import capi
+from tools import native_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
@@ -409,19 +410,9 @@ def test_python_layer_has_the_signatures_of_the_contract():
     assert modules.FLUX_PROFILES_DEFAULTS == (("crm_prof_qc_threshold", 1.0e-5),)
 
 
-CXX_SRC = os.path.join(ROOT, "tests", "cxx", "flux_profiles.cpp")
-CXX_EXE = os.path.join(ROOT, "tests", "cxx", "flux_profiles")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
 def cxx_program():
     """tests/cxx/flux_profiles, built the way the examples' driver is built (no device is needed to build it)"""
-    deps = [CXX_SRC, HEADER, os.path.join(HOST, "pam_coupler.h"), os.path.join(ROOT, "include", "pam_amd_modules.h"), capi.LIB_PATH]
-    if not (os.path.exists(CXX_EXE) and all(os.path.getmtime(CXX_EXE) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + HOST, CXX_SRC, "-L" + os.path.join(ROOT, "pam_amd"), "-lpam_amd_awfl",
-                        "-Wl,-rpath,$ORIGIN/../../pam_amd", "-o", CXX_EXE], check=True)
-    return CXX_EXE
+    return native_build.cxx_program("flux_profiles")
 
 
 def test_header_compiles_into_a_host_program():

@@ -7,7 +7,6 @@ import ctypes as C
 import inspect
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,10 +15,10 @@ import grayrad_ref as ref
 import grayrad_cases as gc
 from grayrad_emu_harness import EmuBackend
 from pam_amd import capi
+from tools.native_build import syntax_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 U = 2.0 ** -53
 FINITE_CASES = tuple(n for n in gc.CASE_NAMES if n != "nan_cell")
 DEEP = [s for s in gc.SHAPES if s[0] >= 5]          # shapes whose cloud layer lies inside the column
@@ -219,8 +218,7 @@ def test_cxx_class_compiles_in_one_translation_unit(tmp_path):
                    "int main() {\n  pam::PamCoupler coupler;\n  Microphysics micro;\n  Radiation rad;\n  micro.init(coupler);\n"
                    '  coupler.set_option<int>("rad_gray_every", 3);\n'
                    "  rad.init(coupler);\n  rad.timeStep(coupler);\n  rad.finalize(coupler);\n  return (int)rad.radiation_name().size();\n}\n")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + HOST, str(src)], capture_output=True, text=True)
+    r = syntax_check(src)
     assert r.returncode == 0, r.stderr[-3000:]
 
 

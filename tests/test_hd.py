@@ -14,6 +14,7 @@ import hd_ref as ref
 import test_boundary_surface as tb
 from hd_emu_harness import PATHS, EmuBackend, ring_block
 from pam_amd import capi
+from tools import native_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
@@ -477,8 +478,8 @@ def test_adaptor_and_python_mirror_name_the_same_fields_and_options():
 
 
 def test_build_depends_on_the_device_header_and_the_driver_has_the_option():
-    text = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert '"hd_device.h"' in text and '"hyperdiffusion.h"' in text
+    deps = native_build.dependencies(native_build.LIB_SOURCES)
+    assert os.path.join(native_build.CSRC, "hd_device.h") in deps and os.path.join(HOST, "modules", "hyperdiffusion.h") in deps
     assert '#include "hd_device.h"' in open(os.path.join(ROOT, "pam_amd", "csrc", "modules_kernels.hip")).read()
     drv = open(os.path.join(ROOT, "examples", "driver.cpp")).read()
     assert drv.count('"--hyperdiff"') == 2 and '#include "modules/hyperdiffusion.h"' in drv

@@ -10,8 +10,6 @@
   * the gate itself: 1e-10 relative in one trace-rain cell turns it red where 1e-12 x max|field| stays green."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,21 +17,15 @@ import pytest
 import kessler_cases as kc
 import test_micro_kessler as tk
 from pam_amd.micro import Microphysics
+from tools.native_build import emu_library
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "kessler_emu.cpp")
-EMU_SO = os.path.join(ROOT, "tests", "emu", "libkessler_emu.so")
 _DP = C.POINTER(C.c_double)
 INSTANCES = {"single_u32": (1, 0), "single_i64": (1, 1), "multi_u32": (0, 0), "multi_i64": (0, 1)}   # (single, wide)
 
 
 @functools.lru_cache(maxsize=None)
 def emu():
-    deps = [EMU_SRC] + [os.path.join(ROOT, "pam_amd", "csrc", f) for f in ("kessler_device.h", "awfl_device.h", "awfl_vertical.h",
-                                                                          "awfl_constants.h")]
-    if not (os.path.exists(EMU_SO) and all(os.path.getmtime(EMU_SO) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", EMU_SO, EMU_SRC], check=True)
-    lib = C.CDLL(EMU_SO)
+    lib = C.CDLL(emu_library("kessler_emu"))
     lib.emu_kessler_max_stable_dt.argtypes = [C.c_int] * 4 + [_DP] * 3 + [C.c_double, C.c_int, _DP]
     lib.emu_kessler_columns.argtypes = [C.c_int] * 4 + [_DP] * 8 + [C.c_double, C.c_int] + [C.c_double] * 4 + [C.c_int] * 2
     return lib

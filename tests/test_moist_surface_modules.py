@@ -15,11 +15,10 @@ import moist_surface_ref as ref
 import test_boundary_surface as tb
 from pam_amd import capi
 from pam_amd import idealized as idz
+from tools.native_build import emu_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "moist_surface_emu.cpp")
-EMU_SO = os.path.join(ROOT, "tests", "emu", "libmoist_surface_emu.so")
 R_V, CP_D, CP_V = 461.0, 1003.0, 1859.0            # the Kessler scheme's constants (pam_amd/micro.py)
 TRACER_SETS = {"kessler": idz.TRACERS_KESSLER_SHOC, "p3": idz.TRACERS_P3_SHOC}
 CONDENSATE = {"kessler": "cloud_liquid", "p3": "cloud_water"}
@@ -62,10 +61,7 @@ def moist_state(tracers, nens, nx, ny, nz, seed=0):
 # host emulation
 
 def emu():
-    deps = [EMU_SRC, os.path.join(ROOT, "pam_amd", "csrc", "moist_surface_device.h")]
-    if not (os.path.exists(EMU_SO) and all(os.path.getmtime(EMU_SO) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", EMU_SO, EMU_SRC], check=True)
-    lib = C.CDLL(EMU_SO)
+    lib = C.CDLL(emu_library("moist_surface_emu"))
     lib.emu_saturation_adjustment.argtypes = [C.c_longlong, C.c_int] + [_DP] * 5 + [C.c_double] * 4 + [C.POINTER(C.c_int)]
     lib.emu_saturation_max_iter.restype = C.c_int
     lib.emu_surface_friction_z0.argtypes = [C.c_int] + [_DP] * 7

@@ -18,13 +18,13 @@ import emu_harness
 import p3_cases as pc
 import p3_coupling_ref as ref
 from pam_amd import capi
+from tools.native_build import syntax_check
 
 GOLDEN = os.path.join(pc.ROOT, "tests", "golden", "p3_coupling_ref.npz")
 EXTRACT = os.path.join(pc.ROOT, "tests", "golden", "p3_extract.json")
 REFERENCE = os.environ.get("PAM_REF", os.path.join(os.path.dirname(pc.ROOT), "reference"))
 MICRO_H = os.path.join(pc.ROOT, "pam_amd", "csrc", "host", "physics", "micro", "p3_amd", "Microphysics.h")
 HOST = os.path.join(pc.ROOT, "pam_amd", "csrc", "host")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 # constants whose products and quotients are exact: kappa = 1/2, so exner = sqrt(pressure / p0); cv_d / cp_d = 1/2
 HAND = dict(R_d=2.0, cp_d=4.0, R_v=4.0, cp_v=8.0, cp_l=16.0, p0=80.0, grav=8.0, cv_d=2.0)
@@ -566,6 +566,5 @@ def test_plugin_header_compiles_with_the_shoc_plugin_and_the_workalike(tmp_path)
                    "  micro.timeStep(coupler);\n  static_assert(Microphysics::get_num_tracers() == 9 && Microphysics::ID_V == 8, \"\");\n"
                    "  static_assert(Microphysics::get_num_diffused_tracers() == 4 && Microphysics::get_diffused_tracers_indices()[0] == 8, \"\");\n"
                    "  micro.finalize(coupler);\n  return (int)micro.micro_name().size() + (int)micro.etime;\n}\n")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-Wno-unused-value", "-I" + os.path.join(pc.ROOT, "include"),
-                        "-I" + HOST, str(src)], capture_output=True, text=True)
+    r = syntax_check(src)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -13,6 +13,7 @@ import pytest
 import p3_cases as pc
 import p3_coupling_ref as ref
 from pam_amd import capi
+from tools.native_build import cxx_program
 
 pytestmark = pytest.mark.gpu
 
@@ -427,22 +428,7 @@ def test_pack_and_unpack_refusals_leave_the_workspace_and_the_fields_untouched()
 # ------------------------------------------------------------------------------------------------------------------------------
 # the C++ class
 
-ROOT = pc.ROOT
-HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-CXX_SRC = os.path.join(ROOT, "tests", "cxx", "p3_micro.cpp")
-CXX_EXE = os.path.join(ROOT, "tests", "cxx", "p3_micro")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXX_ORDER = ("rho_d", "rho_v", "rho_c", "temp", "nccn_prescribed", "nc_nuceat_tend", "ni_activated", "q_prev", "t_prev")
-
-
-def _cxx():
-    deps = [CXX_SRC, os.path.join(HOST, "pam_coupler.h"), os.path.join(HOST, "physics", "micro", "p3_amd", "Microphysics.h"),
-            os.path.join(ROOT, "include", "pam_amd_modules.h"), capi.LIB_PATH]
-    if not (os.path.exists(CXX_EXE) and all(os.path.getmtime(CXX_EXE) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + HOST, CXX_SRC, "-L" + os.path.join(ROOT, "pam_amd"), "-lpam_amd_awfl",
-                        "-Wl,-rpath,$ORIGIN/../../pam_amd", "-o", CXX_EXE], check=True)
-    return CXX_EXE
 
 
 def _cxx_run(tmp_path, state, shoc, layout, steps, mode):
@@ -453,7 +439,7 @@ def _cxx_run(tmp_path, state, shoc, layout, steps, mode):
         f.write(np.array(list(shape) + [int(shoc), layout, steps], dtype=np.int32).tobytes())
         for a in [state["zint"]] + [state[k] for k in CXX_ORDER] + list(state["q"]):
             f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
-    r = subprocess.run([_cxx(), str(src), str(dst), mode], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([cxx_program("p3_micro"), str(src), str(dst), mode], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     names = list(CXX_ORDER) + ["q%d" % t for t in range(7)] + list(OUT_4D)
     flat = np.fromfile(dst, dtype=np.float64)

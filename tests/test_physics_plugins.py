@@ -16,16 +16,14 @@ import pytest
 import plugins_ref as ref
 import test_boundary_surface as tb
 from pam_amd import capi
+from tools.native_build import emu_library, syntax_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "plugins_emu.cpp")
-EMU_SO = os.path.join(ROOT, "tests", "emu", "libplugins_emu.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "plugins_ref.npz")
 EXTRACT = os.path.join(ROOT, "tests", "golden", "plugins_extract.json")
 DRIVER = os.path.join(ROOT, "examples", "driver")
 CI_YAML = os.path.join(ROOT, "tests", "golden", "ci_input_pama.yaml")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 REFERENCE = os.environ.get("PAM_REF", os.path.join(os.path.dirname(ROOT), "reference"))
 _DP = C.POINTER(C.c_double)
 
@@ -176,10 +174,7 @@ def test_the_fixture_is_reproduced_from_the_reference_tree():
 # CPU: the host emulation of the device bodies
 
 def emu():
-    deps = [EMU_SRC, os.path.join(ROOT, "pam_amd", "csrc", "plugins_device.h")]
-    if not (os.path.exists(EMU_SO) and all(os.path.getmtime(EMU_SO) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", EMU_SO, EMU_SRC], check=True)
-    lib = C.CDLL(EMU_SO)
+    lib = C.CDLL(emu_library("plugins_emu"))
     lib.emu_radiation_forced.argtypes = [C.c_int] * 6 + [_DP, _DP, C.c_double, C.c_double]
     lib.emu_compute_pressure.argtypes = [C.c_longlong] + [_DP] * 3 + [C.c_double, C.c_double, _DP]
     return lib
@@ -355,8 +350,7 @@ def test_plugin_headers_compile_together_with_the_workalike(tmp_path, rad):
                    "  static_assert(Microphysics::get_num_diffused_tracers() == 1, \"\");\n"
                    "  micro.finalize(coupler);\n  sgs.finalize(coupler);\n  rad.finalize(coupler);\n"
                    "  return (int)p.size() + (int)(micro.micro_name() + sgs.sgs_name() + rad.radiation_name()).size();\n}\n" % rad)
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + HOST, str(src)], capture_output=True, text=True)
+    r = syntax_check(src)
     assert r.returncode == 0, r.stderr[-3000:]
 
 

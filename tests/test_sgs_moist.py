@@ -8,7 +8,6 @@ import inspect
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,10 +17,10 @@ import sgs_moist_ref as mref
 from sgs_emu_harness import EmuBackend as DryEmuBackend
 from sgs_moist_emu_harness import PATHS, EmuBackend, exp_c as emu_exp_c, load
 from pam_amd import capi
+from tools.native_build import syntax_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 U = 2.0 ** -53
 LD = np.longdouble
 COEF_CASES = ("kessler_set", "p3_set", "cloud_only", "threshold_positive")      # cases with a cloud table and finite fields
@@ -453,8 +452,7 @@ def test_cxx_class_compiles_in_one_translation_unit_with_the_moist_options(tmp_p
                    '  coupler.set_option<bool>("sgs_smag_moist", true);\n  coupler.set_option<bool>("sgs_smag_surface_fluxes", true);\n'
                    '  coupler.set_option<real>("sgs_smag_cloud_threshold", 1.0e-6);\n'
                    "  sgs.init(coupler);\n  sgs.timeStep(coupler);\n  sgs.finalize(coupler);\n  return (int)sgs.sgs_name().size();\n}\n")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + HOST, str(src)], capture_output=True, text=True)
+    r = syntax_check(src)
     assert r.returncode == 0, r.stderr[-3000:]
 
 

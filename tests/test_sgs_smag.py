@@ -7,7 +7,6 @@ import inspect
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,10 +14,11 @@ import pytest
 import sgs_ref as ref
 from sgs_emu_harness import PATHS, EmuBackend, load
 from pam_amd import capi
+from tools import native_build
+from tools.native_build import syntax_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 U = 2.0 ** -53
 LD = np.longdouble
 
@@ -449,8 +449,7 @@ def test_cxx_class_compiles_in_one_translation_unit_with_micro_none_and_a_radiat
                    "int main() {\n  pam::PamCoupler coupler;\n  Microphysics micro;\n  SGS sgs;\n  Radiation rad;\n  micro.init(coupler);\n"
                    "  sgs.init(coupler);\n  rad.init(coupler);\n  rad.timeStep(coupler);\n  sgs.timeStep(coupler);\n  micro.timeStep(coupler);\n"
                    "  static_assert(SGS::get_num_tracers() == 0, \"\");\n  sgs.finalize(coupler);\n  return (int)sgs.sgs_name().size();\n}\n")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + HOST, str(src)], capture_output=True, text=True)
+    r = syntax_check(src)
     assert r.returncode == 0, r.stderr[-3000:]
 
 
@@ -475,8 +474,8 @@ def test_cxx_class_and_python_class_name_the_same_fields_and_options():
 
 
 def test_build_depends_on_the_new_headers_and_the_driver_has_the_option():
-    text = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert '"sgs_device.h"' in text and '"smag_amd"' in text
+    deps = native_build.dependencies(native_build.LIB_SOURCES)
+    assert os.path.join(native_build.CSRC, "sgs_device.h") in deps and SGS_H in deps
     assert '#include "sgs_device.h"' in open(os.path.join(ROOT, "pam_amd", "csrc", "modules_kernels.hip")).read()
     drv = open(os.path.join(ROOT, "examples", "driver.cpp")).read()
     assert drv.count('"--sgs-smag"') == 1 and drv.count("[--sgs-smag CS PRANDTL]") >= 2 and '#include "physics/sgs/smag_amd/SGS.h"' in drv

@@ -14,6 +14,7 @@ import emu_harness
 import shoc_cases as sc
 import shoc_coupling_ref as ref
 from pam_amd import capi
+from tools.native_build import syntax_check
 
 # constants whose products and quotients are exact: kappa = 1/2, so exner = sqrt(pmid / p0)
 HAND = dict(R_d=2.0, cp_d=4.0, R_v=4.0, p0=80.0, grav=8.0, latvap=16.0, cv_d=2.0, pres_R_d=2.0, pres_R_v=4.0)
@@ -424,7 +425,6 @@ def test_standin_refuses_null_args():
 
 SGS_H = os.path.join(sc.ROOT, "pam_amd", "csrc", "host", "physics", "sgs", "shoc_amd", "SGS.h")
 HOST = os.path.join(sc.ROOT, "pam_amd", "csrc", "host")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 GOLDEN = os.path.join(sc.ROOT, "tests", "golden", "shoc_coupling_ref.npz")
 EXTRACT = os.path.join(sc.ROOT, "tests", "golden", "shoc_extract.json")
 REFERENCE = os.environ.get("PAM_REF", os.path.join(os.path.dirname(sc.ROOT), "reference"))
@@ -487,6 +487,5 @@ def test_plugin_header_compiles_with_a_microphysics_and_the_workalike(tmp_path):
                    "  sgs.set_shoc_main(pam_amd_shoc_main_standin);\n  sgs.timeStep(coupler);\n  micro.timeStep(coupler);\n"
                    "  static_assert(SGS::get_num_tracers() == 1 && SGS::ID_TKE == 0, \"\");\n  sgs.finalize(coupler);\n"
                    "  return (int)sgs.sgs_name().size() + (int)sgs.etime;\n}\n")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-Wno-unused-value", "-I" + os.path.join(sc.ROOT, "include"),
-                        "-I" + HOST, str(src)], capture_output=True, text=True)
+    r = syntax_check(src)
     assert r.returncode == 0, r.stderr[-3000:]

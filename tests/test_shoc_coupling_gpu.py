@@ -2,7 +2,6 @@
 in both layouts and with both tracer sets; the workspace's canary words; what must stay untouched; run-to-run and shard-to-whole
 identity; the Python class SGSShoc; three CRM steps with it; and the refusals."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -11,6 +10,7 @@ import pytest
 import shoc_cases as sc
 import shoc_coupling_ref as ref
 from pam_amd import capi
+from tools.native_build import cxx_program
 
 pytestmark = pytest.mark.gpu
 
@@ -344,23 +344,6 @@ def test_pack_and_unpack_refuse_a_missing_tracer_pointer():
 # ------------------------------------------------------------------------------------------------------------------------------
 # the C++ class
 
-ROOT = sc.ROOT
-HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-CXX_SRC = os.path.join(ROOT, "tests", "cxx", "shoc_sgs.cpp")
-CXX_EXE = os.path.join(ROOT, "tests", "cxx", "shoc_sgs")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
-def _cxx():
-    deps = [CXX_SRC, os.path.join(HOST, "pam_coupler.h"), os.path.join(HOST, "physics", "sgs", "shoc_amd", "SGS.h"),
-            os.path.join(ROOT, "include", "pam_amd_modules.h"), capi.LIB_PATH]
-    if not (os.path.exists(CXX_EXE) and all(os.path.getmtime(CXX_EXE) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + HOST, CXX_SRC, "-L" + os.path.join(ROOT, "pam_amd"), "-lpam_amd_awfl",
-                        "-Wl,-rpath,$ORIGIN/../../pam_amd", "-o", CXX_EXE], check=True)
-    return CXX_EXE
-
-
 def _cxx_run(tmp_path, state, p3, layout, mode):
     shape = state["rho_d"].shape
     order = ["rho_d", "rho_v", "rho_c", "uvel", "vvel", "wvel", "temp", "tke", "wthv_sec", "tk", "tkh", "cldfrac"]
@@ -369,7 +352,7 @@ def _cxx_run(tmp_path, state, p3, layout, mode):
         f.write(np.array(list(shape) + [int(p3), layout], dtype=np.int32).tobytes())
         for a in [state[k] for k in ("zint", "zmid", "flx_u", "flx_v")] + [state[k] for k in order] + list(state["q"]):
             f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
-    r = subprocess.run([_cxx(), str(src), str(dst), mode], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([cxx_program("shoc_sgs"), str(src), str(dst), mode], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     names = order + ["q%d" % t for t in range(len(state["q"]))] + ["inv_qc_relvar"]
     flat = np.fromfile(dst, dtype=np.float64).reshape(len(names), *shape)

@@ -13,11 +13,10 @@ import pytest
 import statistics_ref as ref
 import test_boundary_surface as tb
 from pam_amd import capi
+from tools.native_build import emu_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "statistics_emu.cpp")
-EMU_SO = os.path.join(ROOT, "tests", "emu", "libstatistics_emu.so")
 DRIVER = os.path.join(ROOT, "examples", "driver")
 CI_YAML = os.path.join(ROOT, "tests", "golden", "ci_input_pama.yaml")
 _DP = C.POINTER(C.c_double)
@@ -39,10 +38,7 @@ def field(shape, seed):
 # host emulation
 
 def emu():
-    deps = [EMU_SRC, os.path.join(ROOT, "pam_amd", "csrc", "statistics_device.h")]
-    if not (os.path.exists(EMU_SO) and all(os.path.getmtime(EMU_SO) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", EMU_SO, EMU_SRC], check=True)
-    lib = C.CDLL(EMU_SO)
+    lib = C.CDLL(emu_library("statistics_emu"))
     lib.emu_horizontal_average.argtypes = [C.c_int] * 3 + [_DP] * 2
     lib.emu_time_average_accumulate.argtypes = [C.c_longlong, _DP, _DP, C.c_double]
     return lib

@@ -5,7 +5,6 @@ of surface_fluxes_init; the C++ module, the driver, the tool and the documents."
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,10 +13,11 @@ import surface_ref as ref
 import surface_cases as sc
 from surface_emu_harness import EmuBackend
 from pam_amd import capi
+from tools import native_build
+from tools.native_build import syntax_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 _EMU = {}
 
 
@@ -277,8 +277,7 @@ def test_cxx_module_compiles(tmp_path):
     src.write_text('#include "pam_coupler.h"\n#include "modules/surface_fluxes.h"\n'
                    "int main() {\n  pam::PamCoupler coupler;\n  modules::surface_fluxes_init(coupler, 300.0, 1.0);\n"
                    "  modules::compute_surface_fluxes(coupler);\n  modules::compute_surface_fluxes(coupler, 5.0);\n  return 0;\n}\n")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + HOST, str(src)], capture_output=True, text=True)
+    r = syntax_check(src)
     assert r.returncode == 0, r.stderr[-3000:]
 
 
@@ -301,5 +300,5 @@ def test_driver_bench_tool_and_documents_know_the_surface():
     assert '"surface"' in tool and "pam_amd_surface_fluxes" in tool
     for doc in ("README.md", "DESIGN.md", "INTEGRATION.md"):
         assert "surface_fluxes" in open(os.path.join(ROOT, doc)).read(), doc
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert '"surface_device.h"' in entry and '"surface_fluxes.h"' in entry
+    deps = native_build.dependencies(native_build.LIB_SOURCES)
+    assert os.path.join(native_build.CSRC, "surface_device.h") in deps and os.path.join(HOST, "modules", "surface_fluxes.h") in deps

@@ -19,17 +19,13 @@ import pytest
 import test_boundary_surface as tb
 import validate_ref as ref
 from pam_amd import capi
+from tools.native_build import cxx_program, emu_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "validate_ref.json")
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "validate_emu.cpp")
-EMU_SO = os.path.join(ROOT, "tests", "emu", "libvalidate_emu.so")
-CXX_SRC = os.path.join(ROOT, "tests", "cxx", "validate_dm.cpp")
-CXX_EXE = os.path.join(ROOT, "tests", "cxx", "validate_dm")
 DRIVER = os.path.join(ROOT, "examples", "driver")
 CI_YAML = os.path.join(ROOT, "tests", "golden", "ci_input_pama.yaml")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 REFERENCE = os.environ.get("PAM_REF", os.path.join(os.path.dirname(ROOT), "reference"))
 _LP = C.POINTER(C.c_longlong)
 
@@ -183,10 +179,7 @@ def test_the_field_set_reaches_every_class_and_edge():
 # CPU: the host emulation of the device bodies
 
 def emu():
-    deps = [EMU_SRC, os.path.join(ROOT, "pam_amd", "csrc", "validate_device.h")]
-    if not (os.path.exists(EMU_SO) and all(os.path.getmtime(EMU_SO) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", EMU_SO, EMU_SRC], check=True)
-    lib = C.CDLL(EMU_SO)
+    lib = C.CDLL(emu_library("validate_emu"))
     lib.emu_validate.restype = C.c_longlong
     lib.emu_validate.argtypes = [C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_longlong, _LP]
     return lib
@@ -480,16 +473,6 @@ def test_gpu_python_requires_contiguous_tensors_of_a_checked_dtype():
         pam_amd.validate_fields([t.to(torch.float16)], [True])
 
 
-def _cxx_exe():
-    deps = [CXX_SRC, os.path.join(HOST, "pam_coupler.h"), os.path.join(HOST, "data_validation_helpers.h"),
-            os.path.join(HOST, "data_validation_members.h"), capi.LIB_PATH]
-    if not (os.path.exists(CXX_EXE) and all(os.path.getmtime(CXX_EXE) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + HOST, CXX_SRC, "-L" + os.path.join(ROOT, "pam_amd"), "-lpam_amd_awfl",
-                        "-Wl,-rpath,$ORIGIN/../../pam_amd", "-o", CXX_EXE], check=True)
-    return CXX_EXE
-
-
 def _filtered(case, name, which, die):
     """validate_nan / validate_inf / validate_pos: the restatement's lines of one class"""
     _, arr, pos = next(e for e in case_entries(case) if e[0] == name)
@@ -508,7 +491,7 @@ def _filtered(case, name, which, die):
 def test_gpu_cxx_adaptor_writes_the_reference_lines(tmp_path):
     """the work-alike's validate_all / validate (and validate_nan / validate_inf / validate_pos) on the golden's cases: its stderr is
     the reference's, character for character, in the reference's registration order; a clean validate_all prints nothing"""
-    exe = _cxx_exe()
+    exe = cxx_program("validate_dm")
     for case in golden():
         script, want = [], []
         for e in case["entries"]:

@@ -5,7 +5,6 @@ argument checks; the C++ adaptor against the work-alike.  The GPU tests are in t
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,11 +12,10 @@ import pytest
 import vertical_interp_ref as ref
 from pam_amd import capi
 from pam_amd import idealized as idz
+from tools.native_build import emu_library, syntax_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-EMU_SRC = os.path.join(ROOT, "tests", "emu", "vertical_interp_emu.cpp")
-EMU_SO = os.path.join(ROOT, "tests", "emu", "libvertical_interp_emu.so")
 _DP = C.POINTER(C.c_double)
 
 ORDERS = [3, 5]
@@ -152,11 +150,7 @@ def test_uniform_grid_tables_are_the_reference_constants():
 # the host emulation of the device bodies
 
 def emu():
-    csrc = os.path.join(ROOT, "pam_amd", "csrc")
-    deps = [EMU_SRC] + [os.path.join(csrc, f) for f in ("vertical_interp_device.h", "awfl_vertical.h", "awfl_device.h", "awfl_constants.h")]
-    if not (os.path.exists(EMU_SO) and all(os.path.getmtime(EMU_SO) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", EMU_SO, EMU_SRC], check=True)
-    lib = C.CDLL(EMU_SO)
+    lib = C.CDLL(emu_library("vertical_interp_emu"))
     lib.emu_vertical_interp_tables.argtypes = [C.c_int] * 3 + [_DP] * 3
     lib.emu_vertical_interp_cells_to_edges.argtypes = [C.c_int] * 5 + [_DP] * 3 + [C.c_int] * 2 + [_DP]
     return lib
@@ -288,14 +282,12 @@ def test_python_mirror_refuses_orders_7_and_9():
 # the C++ adaptor
 
 ADAPTOR = os.path.join(HOST, "vertical_interp.h")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _compile(tmp_path, body):
     src = tmp_path / "use.cpp"
     src.write_text('#include "vertical_interp.h"\n' + body)
-    return subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-Wno-unused-value", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + HOST, str(src)], capture_output=True, text=True)
+    return syntax_check(src)
 
 
 def test_adaptor_compiles_against_the_workalike(tmp_path):

@@ -7,7 +7,6 @@ pass inside the x-sweep (LineStash + xsweep_pressure_epilogue); three runs per s
 import copy
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,10 +14,9 @@ import pytest
 import emu_harness as eh
 from pam_amd import idealized as idz
 from parity_cases import build_inputs
+from tools.native_build import emu_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "xsweep_pressure_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libxsweep_pressure_emu.so")
 _DP = C.POINTER(C.c_double)
 NZ = 4
 FIELDS = ("density_dry", "uvel", "vvel", "wvel", "temp", "tracers")
@@ -34,11 +32,7 @@ SHAPES = {
 
 @pytest.fixture(scope="module")
 def lib():
-    deps = [_SRC, os.path.join(_HERE, "emu", "awfl_emu.cpp")] + [os.path.join(_HERE, "..", "pam_amd", "csrc", f) for f in
-                                                                  ("awfl_device.h", "awfl_vertical.h", "awfl_constants.h")]
-    if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _SO, _SRC], check=True)
-    so = C.CDLL(_SO)
+    so = C.CDLL(emu_library("xsweep_pressure_emu"))
     ref = eh.load()
     for name in ("emu_init", "emu_destroy", "emu_set_grav_balance", "emu_set_span", "emu_set_fused", "emu_buffer", "emu_declare_hydrostatic",
                  "emu_time_step"):

@@ -1,15 +1,11 @@
 """ctypes binding of tests/emu/vt_emu.cpp (host emulation of the variance transport kernels).  TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tools.native_build import emu_library
 from vt_ref import FIELDS, QUANTITIES, quantities
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "emu", "vt_emu.cpp")
-_SO = os.path.join(_HERE, "emu", "libvt_emu.so")
 _DP = C.POINTER(C.c_double)
 _LIB = None
 
@@ -17,13 +13,7 @@ _LIB = None
 def load():
     global _LIB
     if _LIB is None:
-        csrc = os.path.join(_HERE, "..", "pam_amd", "csrc")
-        deps = [_SRC, os.path.join(csrc, "vt_device.h"), os.path.join(csrc, "msa_device.h")]
-        if not (os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in deps)):
-            tmp = "%s.%d.tmp" % (_SO, os.getpid())      # built beside it and moved into place: another process never loads half a file
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", tmp, _SRC], check=True)
-            os.replace(tmp, _SO)
-        lib = C.CDLL(_SO)
+        lib = C.CDLL(emu_library("vt_emu"))
         lib.emu_vt_stats.restype = None
         lib.emu_vt_stats.argtypes = [C.c_int] * 4 + [C.POINTER(_DP), C.c_int, C.c_int, C.POINTER(_DP), C.c_double, C.c_double] + [C.POINTER(_DP)] * 3
         lib.emu_vt_apply.restype = None
