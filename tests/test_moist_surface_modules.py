@@ -11,80 +11,17 @@ import subprocess
 import numpy as np
 import pytest
 
+import moist_surface_cases as mc
 import moist_surface_ref as ref
 import test_boundary_surface as tb
+from moist_surface_cases import CONDENSATE, CP_D, CP_V, R_V, TRACER_SETS, _p, emu, emu_saturation_adjustment, moist_state  # noqa: F401
 from pam_amd import capi
 from pam_amd import idealized as idz
-from tools.native_build import emu_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "pam_amd", "csrc", "host")
-R_V, CP_D, CP_V = 461.0, 1003.0, 1859.0            # the Kessler scheme's constants (pam_amd/micro.py)
-TRACER_SETS = {"kessler": idz.TRACERS_KESSLER_SHOC, "p3": idz.TRACERS_P3_SHOC}
-CONDENSATE = {"kessler": "cloud_liquid", "p3": "cloud_water"}
-_DP = C.POINTER(C.c_double)
-
-
-# ------------------------------------------------------------------------------------------------------------------------------
-# states
-
-def moist_state(tracers, nens, nx, ny, nz, seed=0):
-    """(nz,ny,nx,nens) fields whose cells are, at random, super-saturated (condensation), unsaturated with plenty of cloud (partial
-    evaporation), unsaturated with a trace of cloud (complete evaporation) or unsaturated without cloud (untouched)"""
-    rng = np.random.default_rng(seed)
-    shape = (nz, ny, nx, nens)
-    f = {"density_dry": 1.1 * np.exp(-np.arange(nz) / 20.0)[:, None, None, None] * (1 + 0.02 * rng.random(shape)),
-         "temp": 250.0 + 50.0 * rng.random(shape)}
-    tc = f["temp"] - 273.15
-    rvs = 610.94 * np.exp(17.625 * tc / (243.04 + tc)) / (R_V * f["temp"])
-    kind = rng.integers(0, 4, shape)
-    ratio = np.choose(kind, [rng.uniform(1.02, 1.3, shape), rng.uniform(0.85, 0.99, shape), rng.uniform(0.3, 0.6, shape),
-                             rng.uniform(0.5, 0.95, shape)])
-    cloud = np.choose(kind, [rng.uniform(0, 1e-3, shape), rng.uniform(2e-2, 3e-2, shape), rng.uniform(1e-7, 1e-5, shape),
-                             np.zeros(shape)])
-    cond = {"kessler": "cloud_liquid", "p3": "cloud_water"}
-    for name, _, mass in tracers:
-        if name == "water_vapor":
-            f[name] = rvs * ratio
-        elif name in cond.values():
-            f[name] = cloud
-        elif mass:
-            f[name] = rng.uniform(0, 1e-3, shape)
-        else:
-            f[name] = rng.uniform(1e5, 1e7, shape)       # number concentrations, tke: do not add mass
-    for k in f:
-        f[k] = np.ascontiguousarray(f[k], dtype=np.float64)
-    return f
-
-
-# ------------------------------------------------------------------------------------------------------------------------------
-# host emulation
-
-def emu():
-    lib = C.CDLL(emu_library("moist_surface_emu"))
-    lib.emu_saturation_adjustment.argtypes = [C.c_longlong, C.c_int] + [_DP] * 5 + [C.c_double] * 4 + [C.POINTER(C.c_int)]
-    lib.emu_saturation_max_iter.restype = C.c_int
-    lib.emu_surface_friction_z0.argtypes = [C.c_int] + [_DP] * 7
-    lib.emu_surface_friction_cell.argtypes = [C.c_longlong] + [_DP] * 14
-    return lib
-
-
-def _p(a):
-    assert a.dtype == np.float64 and a.flags["C_CONTIGUOUS"]
-    return a.ctypes.data_as(_DP)
-
-
-def emu_saturation_adjustment(lib, f, tracers, micro):
-    """the device loop on the host: returns (rho_v, rho_c, temp, iterations) as flat arrays"""
-    rho_d = np.ascontiguousarray(f["density_dry"].ravel())
-    massy = np.ascontiguousarray(np.stack([f[n].ravel() for n, _, m in tracers if m]))
-    rv = np.array(f["water_vapor"].ravel())
-    rc = np.array(f[CONDENSATE[micro]].ravel())
-    t = np.array(f["temp"].ravel())
-    it = np.zeros(rv.size, dtype=np.int32)
-    lib.emu_saturation_adjustment(rv.size, massy.shape[0], _p(rho_d), _p(massy), _p(rv), _p(rc), _p(t), R_V, CP_D, CP_V, ref.CP_L,
-                                  it.ctypes.data_as(C.POINTER(C.c_int)))
-    return rv, rc, t, it
+# the states (moist_state), the binding of the host emulation (emu, emu_saturation_adjustment) and the gates of the GPU tests live in
+# tests/moist_surface_cases.py; the names above are kept here for the tests that import them from this module
 
 
 def _emu_cells(lib, rv, rc=None, t=None, rho_d=1.0):
@@ -334,24 +271,23 @@ def _dump(c, names):
     return {n: dm.get(n, readonly=True).cpu().numpy() for n in names}
 
 
-SHAPES = [(70, 5, 4, 4), (3, 3, 2, 5), (1, 6, 1, 4)]     # (nens, nx, ny, nz): ragged nens with nx*ny >= 16, nx*ny < 16, one member
+SHAPES = mc.MODULE_SHAPES     # (nens, nx, ny, nz): ragged nens with nx*ny >= 16, nx*ny < 16, one member
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("micro", ["kessler", "p3"])
-@pytest.mark.parametrize("shape", SHAPES, ids=["ragged_nens_16cols", "small", "one_member"])
+@pytest.mark.parametrize("shape", SHAPES, ids=mc.MODULE_SHAPE_IDS)
 def test_gpu_saturation_adjustment_matches_restatement(micro, shape):
     import torch
     from pam_amd import modules
-    tr = TRACER_SETS[micro]
-    nens, nx, ny, nz = shape
-    f = moist_state(tr, nens, nx, ny, nz, seed=10 + nens)
+    d = mc.saturation_case("%s_%s" % (micro, mc.MODULE_SHAPE_IDS[SHAPES.index(shape)]))
+    tr, f = d["tracers"], d["fields"]
     c = _coupler(tr, f, micro)
     dirty = c.run_module("saturation_adjustment", modules.saturation_adjustment)
     torch.cuda.synchronize()
     names = list(f)
     got = _dump(c, names)
-    want, info = ref.saturation_adjustment(f, tr, micro, R_V, CP_D, CP_V)
+    info = d["info"]
     cn = CONDENSATE[micro]
     # the reference hands out density_dry, temp, water vapour, the condensate and every tracer that adds mass non-const
     assert set(dirty) == {"density_dry", "temp", "water_vapor", cn} | {n for n, _, m in tr if m}, dirty
@@ -359,17 +295,13 @@ def test_gpu_saturation_adjustment_matches_restatement(micro, shape):
     for k in names:
         if k not in ("water_vapor", cn, "temp"):
             assert np.array_equal(got[k], f[k]), k
-    # the adjusted fields against the restatement: 1e-12 of the field maximum, except where a decision of the bisection was within
-    # 1e-12 of its root (there a last-place difference of exp may flip it: at most 2 tol in rho, the matching change in T)
-    exempt = info["margin"].reshape(f["temp"].shape) < 1e-12
-    dT = 2 * ref.TOL * 2.6e6 / (0.5 * CP_D)               # Lv / (rho cp) bounds the temperature change per unit of density moved
-    for k, allow in (("water_vapor", 2 * ref.TOL), (cn, 2 * ref.TOL), ("temp", dT)):
-        err = np.abs(got[k] - want[k])
-        tol = 1e-12 * np.abs(want[k]).max()
-        assert np.all(err[~exempt] <= tol), (k, err[~exempt].max(), tol)
-        assert np.all(err[exempt] <= allow + tol), k
+    # the adjusted fields against the restatement, bit for bit (tests/moist_surface_cases.py: assert_adjusted_bits): exp enters the
+    # bisection only through its decisions, none of which is within 1e-10 of a tie on these states, so no cell is exempt
+    exempt = mc.assert_adjusted_bits({"rho_v": got["water_vapor"], "rho_c": got[cn], "temp": got["temp"]}, d["want"], info, d["before"],
+                                     rho_min=0.5)
     print("saturation_adjustment %s %s: %d of %d cells adjusted, %d exempted (decision margin < 1e-12)"
-          % (micro, shape, int((info["branch"] > 0).sum()), info["branch"].size, int(exempt.sum())))
+          % (micro, shape, int((info["branch"] > 0).sum()), info["branch"].size, exempt))
+    assert exempt == 0
 
 
 @pytest.mark.gpu
@@ -383,23 +315,7 @@ def test_gpu_saturation_adjustment_rejects_an_unknown_micro():
     assert all(np.array_equal(v, f[k]) for k, v in _dump(c, list(f)).items())
 
 
-def _friction_state(nens, nx, ny, nz, seed):
-    rng = np.random.default_rng(seed)
-    tr = TRACER_SETS["kessler"]
-    f = moist_state(tr, nens, nx, ny, nz, seed)
-    shape = (nz, ny, nx, nens)
-    f["uvel"] = rng.normal(4, 4, shape)
-    f["vvel"] = rng.normal(-1, 4, shape)
-    f["uvel"][0, 0, 0], f["vvel"][0, 0, 0] = 0.2, -0.1        # calm cells: max(1, |u|)
-    f["water_vapor"] = rng.uniform(0.005, 0.015, shape)
-    f["gcm_uvel"] = rng.normal(5, 4, (nz, nens))
-    f["gcm_vvel"] = rng.normal(0, 4, (nz, nens))
-    tau = rng.uniform(1e-3, 0.4, nens)
-    bflx = np.where(np.arange(nens) % 3 == 0, 0.0, rng.uniform(-0.03, 0.03, nens))   # bflx = 0: diag_ustar does not iterate
-    zi = idz.stretched_interfaces(nz, 12000.0)[:, None] * (1 + 0.01 * np.arange(nens))[None, :]
-    for k in f:
-        f[k] = np.ascontiguousarray(f[k])
-    return tr, f, tau, bflx, zi
+_friction_state = mc.module_friction_state
 
 
 def _friction_run(tr, f, tau, bflx, zi, computes=1):
@@ -419,23 +335,26 @@ def _friction_run(tr, f, tau, bflx, zi, computes=1):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", SHAPES + [(5, 12, 12, 3)], ids=["ragged_nens_16cols", "small", "one_member", "column_chunks"])
+@pytest.mark.parametrize("shape", mc.MODULE_FRICTION_SHAPES, ids=mc.MODULE_FRICTION_IDS)
 def test_gpu_surface_friction_matches_restatement(shape):
-    """the last shape has 144 columns: the compute kernel splits them into three chunks, each summing the means itself"""
+    """the last shape has 144 columns: the compute kernel splits them into three chunks, each summing the means itself.  z0 per member
+    and the fluxes per cell against the longdouble reference at the slot-order means (tests/moist_surface_cases.py: assert_z0_within,
+    assert_fluxes_within); the fluxes' reference takes the z0 the device's init left, which has passed its own gate by then."""
     nens, nx, ny, nz = shape
     tr, f, tau, bflx, zi = _friction_state(nens, nx, ny, nz, seed=20 + nens)
     got = _friction_run(tr, f, tau, bflx, zi, computes=2)
-    zm = 0.5 * (zi[:-1] + zi[1:])
-    z0, sb, fu0, fv0 = ref.surface_friction_init(f["density_dry"], f["water_vapor"], zm, f["gcm_uvel"], f["gcm_vvel"], tau, bflx)
+    d = mc.friction_case("module_" + mc.MODULE_FRICTION_IDS[mc.MODULE_FRICTION_SHAPES.index(shape)])
+    assert all(np.array_equal(d[k], f[n]) for k, n in (("rho_d", "density_dry"), ("rho_v", "water_vapor"), ("uvel", "uvel"), ("vvel", "vvel")))
     gi = got["init"]
-    assert np.all(np.abs(gi["z0"] - z0) <= 1e-12 * np.abs(z0).max())
-    assert np.array_equal(gi["sfc_bflx"], sb)
+    raw, want = mc.z0_reference(d)
+    worst_z0 = mc.assert_z0_within(gi["z0"], raw, want)
+    assert np.array_equal(gi["sfc_bflx"], bflx)
     assert assert_zero_then_filled(gi, got)
-    fu, fv = ref.compute_surface_friction(f["density_dry"], f["water_vapor"], f["uvel"], f["vvel"], zm, zi, gi["z0"], gi["sfc_bflx"])
-    for k, want in (("sfc_mom_flx_u", fu), ("sfc_mom_flx_v", fv)):
-        g = got["compute"][0][k]
-        assert np.abs(g - want).max() <= 1e-12 * np.abs(want).max(), k
-        assert np.array_equal(g, got["compute"][1][k]), k          # two identical calls: identical bits
+    g = got["compute"][0]
+    worst = mc.assert_fluxes_within(g["sfc_mom_flx_u"], g["sfc_mom_flx_v"], mc.friction_reference(d, z0=gi["z0"]))
+    print("surface friction %s: z0 %.2f units at the worst (gate %g), fluxes %.2f (gate %g)" % (shape, worst_z0, mc.G_Z0, worst, mc.G_FLUX))
+    for k in ("sfc_mom_flx_u", "sfc_mom_flx_v"):
+        assert np.array_equal(g[k], got["compute"][1][k]), k          # two identical calls: identical bits
     assert got["dirty_init"] == {"z0", "sfc_bflx", "sfc_mom_flx_u", "sfc_mom_flx_v", "density_dry", "water_vapor",
                                  "vertical_midpoint_height", "gcm_uvel", "gcm_vvel"}, got["dirty_init"]
     assert got["dirty"] == {"z0", "sfc_bflx", "sfc_mom_flx_u", "sfc_mom_flx_v"}, got["dirty"]

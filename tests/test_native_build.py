@@ -17,7 +17,7 @@ EMU_FLAGS = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"
 # the test-side files that build through the helper: the harnesses, the two case modules and the tests with a build of their own
 ROUTED = sorted(glob.glob(os.path.join(ROOT, "tests", "*_emu_harness.py"))) + [os.path.join(ROOT, "tests", f + ".py") for f in (
     "emu_harness", "shoc_cases", "p3_cases", "test_diagnostics", "test_statistics_modules", "test_vertical_interp", "test_xsweep_pressure_emu",
-    "test_validate", "test_kessler_emu", "test_moist_surface_modules", "test_physics_plugins", "test_coldiag", "test_fluxprof",
+    "test_validate", "test_kessler_emu", "moist_surface_cases", "test_physics_plugins", "test_coldiag", "test_fluxprof",
     "test_shoc_coupling_gpu", "test_p3_coupling_gpu", "test_p3_coupling", "test_shoc_coupling", "test_grayrad", "test_grayrad_sw", "test_sgs_smag",
     "test_sgs_moist", "test_surface")]
 

@@ -59,10 +59,12 @@ def emu_sources():
     return sorted(glob.glob(os.path.join(EMU_DIR, "*_emu.cpp")))
 
 
-def emu_library(name):
-    """tests/emu/<name>.cpp -> tests/emu/lib<name>.so, the device bodies under g++ without contraction"""
+def emu_library(name, libs=()):
+    """tests/emu/<name>.cpp -> tests/emu/lib<name>.so, the device bodies under g++ without contraction.  libs: libraries the source needs
+    at link time (moist_surface_quad_emu: "quadmath", "pthread"), so that loading the result needs nothing loaded before it"""
     src = os.path.join(EMU_DIR, name + ".cpp")
-    return build(os.path.join(EMU_DIR, "lib%s.so" % name), emu_sources(), ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", src])
+    return build(os.path.join(EMU_DIR, "lib%s.so" % name), emu_sources(),
+                 ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", src] + ["-l" + x for x in libs])
 
 
 def cxx_program(name):
