@@ -197,6 +197,11 @@ int pam_amd_awfl_set_tail_fusion(pam_amd_awfl_t *h, int mode);
  * and the x-sweep loads both and forms the same sum (measured: the flux kernel pays back what the x-sweep gains).
  * Same bits either way (ABI 5). */
 int pam_amd_awfl_set_yz_fold(pam_amd_awfl_t *h, int mode);
+/* Fused stage, member-lane x-sweeps: water vapour's FCT seed is loaded only by wavefronts in which a lower bound of it, formed from
+ * values the update has anyway, does not already show that no member is limited (mode 2); mode 1: always loaded; automatic: as
+ * measured (docs/experiments.md).  The bound holds for seeds made inside the same timeStep; pam_amd_awfl_debug_stage always loads.
+ * Same bits either way. */
+int pam_amd_awfl_set_seed_skip(pam_amd_awfl_t *h, int mode);
 
 /* Stage structure.  1 (default): per stage  flux(y,z) -> fused x-sweep + update of the state and of the first tracer (incl.
  * its FCT multiplier) -> [FCT multiplier of further tracers] -> pointwise tail (further tracers, the first tracer where the

@@ -687,6 +687,36 @@ PAMA_D double next_seed(double m_0, double m_in, double v) {
   if (STAGE == 2) return fma(2.0 / 3.0, v, (1.0 / 3.0) * m_0);
   return v;
 }
+// A lower bound L <= seed of the FCT seed that stage STAGE of a positive-definite tracer READS in a cell, from what that stage has in
+// registers anyway: m_0 = mul_rn(q_0, rho_0) and m_in = mul_rn(q_in, rho_in), its own sub-step-start and stage-input masses (q_in, rho_in:
+// the stage-input mixing ratio and density as loaded).  The x-sweep compares the mass leaving the cell with fct_mass_available(L) first
+// and loads the seed only where that does not settle the answer (finish_tracer_cell); fct_mass_available is monotone, so
+// mass_out <= available(L) implies mass_out <= available(seed): multiplier exactly 1, no flag, the very bits of the loading path.
+// Holds for seeds made by THIS library's chain inside one timeStep: init_prim_body, then every stage's next_seed (state pass, fix-up
+// pass, tile kernels, one-kernel update -- all through tracer_new_value).  A stage run on buffers the caller may have written
+// (pam_amd_awfl_debug_stage) keeps the load.
+//   STAGE 2  reads next_seed<1> = fma(1/4, v, (3/4) m_in') of stage 1, whose input IS this sub-step's start: m_in' = mul_rn of the same two
+//            doubles as m_0, and (3/4) m_0 here is the very product there.  v = fmax(0, .) >= 0 (a NaN becomes 0), so the exact sum is
+//            >= (3/4) m_0, a double, and rounding to nearest cannot go below a double that the exact value is not below.  L = (3/4) m_0.
+//   STAGE 3  reads next_seed<2> = fma(2/3, v, (1/3) m_0) with the same m_0 (both stages combine with the sub-step's start): L = (1/3) m_0.
+//            (m_0 a NaN: seed and L are NaN, fmax(NaN, 0) = 0 on both sides -- and the comparison sends the row to the load.)
+//   STAGE 1  reads the conserved mass S >= 0 itself (init_prim_body: the clipped coupler value; next_seed<3>: the clipped v), while the
+//            producer stored q_in = rn(S y), y = fast_rcp(rho_in) = (1 + e) / rho_in, and rho_in.  |e| <= 2^-52: v_rcp_f64 is good to
+//            2^-23 at worst (measured 4.6e-8), a Newton step y(1 + rn(1 - x y)) squares the error and adds one rounding of the fma each
+//            way, 2^-46 + 2^-53 after the first, < 2^-52 after the second (the host's 1/x: 2^-53).  Without underflow
+//            m_in = S (1 + e)(1 + d1)(1 + d2), |d| <= 2^-53, so m_in < S (1 + 2^-50) and
+//            L = rn(m_in (1 - 2^-48)) <= S (1 + 2^-50)(1 - 2^-48)(1 + 2^-53) < S.
+//            "Without underflow" (or overflow) is checked, not assumed: 2^-900 <= q_in <= 2^900 and 2^-100 <= rho_in <= 2^100 put S y,
+//            q_in rho_in and L a hundred binades inside the normal range (and send NaNs, zeros and negative densities the other way);
+//            anything else gets L = 0 <= S -- a cell with no vapour at all, or a state no bound should be trusted on, loads its seed.
+template <int STAGE>
+PAMA_D double seed_lower_bound(double m_0, double m_in, double q_in, double rho_in) {
+#pragma clang fp contract(off)
+  if (STAGE == 2) return (3.0 / 4.0) * m_0;
+  if (STAGE == 3) return (1.0 / 3.0) * m_0;
+  const bool normal = (q_in >= 0x1p-900) & (q_in <= 0x1p900) & (rho_in >= 0x1p-100) & (rho_in <= 0x1p100);
+  return normal ? m_in * (1.0 - 0x1p-48) : 0.0;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Wave-uniform addressing.  In the fused x-sweep every lane of a wavefront works on the SAME x line (k, j) and differs only
@@ -724,6 +754,43 @@ typedef const double *const_ptr;
 PAMA_D const_ptr as_constant(const double *p) { return p; }
 PAMA_D int uni_int(int v) { return v; }
 #endif
+// Streaming policy.  A stage moves ~37 GB through a 256 MB last-level cache, and the few lines that ARE read twice (the cells of the
+// periodic wrap, the stage-input density, the j+1 / k+1 faces shared with the neighbouring line) have to survive there behind
+// some 25 streams per trip that are touched exactly once.  ld_once / st_once make the same `scalar base + lane offset` access
+// as uni(p)[e] / uniw(p)[e] and mark it non-temporal (the `nt` bit of global_load / global_store: the line is the first to be
+// evicted).  A hint only: values, ordering and addressing are those of the plain access, which is also what the host
+// emulation and a build with the group's macro at 0 make.  Measured (round 19, docs/experiments.md): the bytes the kernels fetch do
+// not change with it, the C2 step gains about 1 %, and only X1 and F1 together are ahead of the parent reliably; X2 lost and is off.
+// One macro per group of sites, so that each can be measured alone:
+//   PAMA_STREAM_X1   x-sweep state pass, loads: the y/z differences, the sub-step-start values, water vapour's seed
+//   PAMA_STREAM_F1   flux sweeps, stores: the per-cell flux differences of the state variables (DIFF), read once by the x-sweep
+//   PAMA_STREAM_X2   x-sweep state pass, stores: water vapour's x flux (read again only where the limiter acts)
+#ifndef PAMA_STREAM_POLICY
+#define PAMA_STREAM_POLICY 1
+#endif
+#ifndef PAMA_STREAM_X1
+#define PAMA_STREAM_X1 PAMA_STREAM_POLICY
+#endif
+#ifndef PAMA_STREAM_F1
+#define PAMA_STREAM_F1 PAMA_STREAM_POLICY
+#endif
+#ifndef PAMA_STREAM_X2
+#define PAMA_STREAM_X2 0
+#endif
+template <int NT>
+PAMA_D double ld_once(gc_ptr p, unsigned e) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (NT != 0) return __builtin_nontemporal_load(p + e);
+#endif
+  return p[e];
+}
+template <int NT>
+PAMA_D void st_once(g_ptr p, unsigned e, double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (NT != 0) { __builtin_nontemporal_store(v, p + e); return; }
+#endif
+  p[e] = v;
+}
 // The member index of a lane as the compiler must see it for `scalar base + 32-bit lane offset` addressing: an unsigned
 // value whose top bits are KNOWN to be zero (nens < 2^28), so that 8*e cannot wrap in 32 bits.
 PAMA_D unsigned member_offset(int e) { return (unsigned)e & 0x0fffffffu; }
@@ -976,6 +1043,12 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
   // (requested at the top of the trip that closes the cell, on EVERY trip: see flux_x_update_body on s_waitcnt counts)
   auto fold_cell = [&](int c) -> int { return c > 0 ? c - 1 : 0; };      // the cell trip c closes (clamped: trip f0 closes none)
   auto folded = [&](double dzv, double dyv, double rdzv) -> double { return yz_divergence(P, dyv, dzv, rdzv); };
+  // DIFF: the store of a closed cell's difference by the trips of the loops.  The x-sweep reads it once (PAMA_STREAM_F1).  Trip 1 of a
+  // whole periodic line goes through here too, although what it parks in cell 0's slot is loaded back by this lane behind the loop: one
+  // reload per line.  Telling that trip apart cost the loops of the y sweep 6 to 25 instructions each (a second copy of every store
+  // behind a scalar branch), which an FP64-issue-bound kernel pays for on every trip.  The values parked BEFORE the loops and the
+  // stores behind them (the closing face) stay plain accesses.
+  auto st_diff = [&](double *p, double val) __attribute__((always_inline)) { st_once<PAMA_STREAM_F1>(uniw(p), eu, val); };
   const int nadv = 4 + P.nt;
   double *fl0 = flux + fbase;                                          // flux field 0 of this line: the face mass flux
 
@@ -1046,7 +1119,7 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
       // the mass flux always leaves as FACES: the later passes upwind with it (face n of a periodic line is face 0)
       if (!(DIFF && periodic && c == g.n)) uniw(fl0 + (long long)c * g.cs)[eu] = ruf;
       if (DIFF) {
-        if (c > f0) uniw(fln + (long long)(c - 1) * g.cs)[eu] = FOLD ? folded(Fpn - fn, dyv, rdzv) : Fpn - fn;   // cell c-1 is closed by faces c-1 and c
+        if (c > f0) st_diff(fln + (long long)(c - 1) * g.cs, FOLD ? folded(Fpn - fn, dyv, rdzv) : Fpn - fn);   // cell c-1 is closed by faces c-1 and c
         Fpn = fn;
       } else {
         uniw(fln + (long long)c * g.cs)[eu] = fn;
@@ -1182,7 +1255,7 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
         for (int n = 0; n < NF; n++) {
           const double F = mul_rn(ruf, up ? prevR[n] : L[n]);
           if (n < NS) {
-            if (c > f0) uniw(fl[n] + (long long)(c - 1) * g.cs)[eu] = FOLD ? folded(Fp[n] - F, dyv[n], rdzv) : Fp[n] - F;
+            if (c > f0) st_diff(fl[n] + (long long)(c - 1) * g.cs, FOLD ? folded(Fp[n] - F, dyv[n], rdzv) : Fp[n] - F);
             Fp[n] = F;
           } else if (c < fend) {
             uniw(fl[n] + (long long)c * g.cs)[eu] = F;
@@ -1210,7 +1283,7 @@ PAMA_D void flux_line_body_zt(const Params &P, const double *__restrict__ prim, 
       for (int n = 0; n < NF; n++) {
         const double F = mul_rn(ruf, 0.0);
         if (n < NS) {
-          if (c > f0) uniw(fl[n] + (long long)(c - 1) * g.cs)[eu] = FOLD ? folded(Fp[n] - F, dyv[n], rdzv) : Fp[n] - F;
+          if (c > f0) st_diff(fl[n] + (long long)(c - 1) * g.cs, FOLD ? folded(Fp[n] - F, dyv[n], rdzv) : Fp[n] - F);
         } else if (c < fend) {
           uniw(fl[n] + (long long)c * g.cs)[eu] = F;
         }
@@ -1565,6 +1638,23 @@ PAMA_D double fct_multiplier(const Params &P, double seed_v, double xlo, double 
   if (wave_any_or_lane(limited)) m = limited ? mass_available / mass_out : 1.0;
   return m;
 }
+// Its two sides once more, as functions of their own: the x-sweep forms both before it has the seed (finish_tracer_cell, seed_lower_bound).
+// SPELLED A SECOND TIME on purpose -- fct_multiplier written in terms of these two changed the compiler's code for every kernel that
+// calls it (docs/experiments.md, "Kernel entry layer"); tests/test_seed_bound.py holds the two spellings to the same bits.
+// fct_mass_available is MONOTONE in the seed: fmax, then three rounded products by positive factors (init rejects xlen, ylen and
+// dz <= 0), and rounding to nearest preserves <=.
+PAMA_D double fct_mass_available(const Params &P, double seed_v, double dzk) {
+#pragma clang fp contract(off)
+  return fmax(seed_v, 0.0) * P.dx * P.dy * dzk;
+}
+PAMA_D double fct_mass_out(const Params &P, double xlo, double xhi, double ylo, double yhi, double zlo, double zhi, double dzk,
+                           double rdzk, double dt) {
+#pragma clang fp contract(off)
+  const double flux_out_x = (fmax(xhi, 0.0) - fmin(xlo, 0.0)) * P.rdx;
+  const double flux_out_y = P.sim2d ? 0.0 : (fmax(yhi, 0.0) - fmin(ylo, 0.0)) * P.rdy;
+  const double flux_out_z = (fmax(zhi, 0.0) - fmin(zlo, 0.0)) * rdzk;
+  return (flux_out_x + flux_out_y + flux_out_z) * dt * P.dx * P.dy * dzk;
+}
 
 // FCT multiplier of one cell and tracer (Dycore.h:533-540): 1 when the cell is not limited.
 //   t0   first tracer to do (test hook)
@@ -1891,18 +1981,59 @@ PAMA_D void own_multiplier_cell(const Params &P, int t, double *__restrict__ mul
     uniw(mt)[eu] = m_t;
   }
 }
+// ... its flag and store part for a multiplier the caller has formed (finish_tracer_cell<., true>; a second spelling, as fct_mass_out)
+template <bool DENSE>
+PAMA_D void own_multiplier_store(const Params &P, int t, double *__restrict__ mult, const FctRows &rows, int k, int j, int i, int e,
+                                 unsigned eu, long long ix, double m_t) {
+  const bool limited = (m_t != 1.0);
+  double *mt = mult + (long long)t * P.ncell + ix;
+  if (rows.flags) {
+    if (limited) {
+      rows.flags[(long long)t * fct_rows_per_tracer(P) + fct_row(P, k, j, i, e)] = rows.seq;
+      if (!DENSE && rows.lines) rows.lines[(long long)t * fct_lines_per_tracer(P) + fct_line(P, k, j, e)] = rows.seq;
+      if (!DENSE) rows.any[e >> 6] = rows.seq;  // ("some row of water vapour in this member block": the fix-up pass has work)
+    }
+    // (sparse: only where a wavefront IS a row -- 64 members of one cell.  In the tile kernels a row may be narrower than a
+    // wavefront and straddle two of them: the half without a limited member must still store its multipliers, the row is flagged)
+    if (DENSE || !rows.sparse_store || wave_any(limited)) uniw(mt)[eu] = m_t;
+  } else {
+    uniw(mt)[eu] = m_t;
+  }
+}
 
 // Tracer 0 of one cell finished inside the state pass of the fused x-sweep (Dycore.h:525-550, :572-584, :162-221): its own
 // multiplier (above), and the cell's update as it is unless the cell or a neighbour is limited -- tracer_fixup_line_body redoes
 // exactly those neighbourhoods afterwards.  (Water vapour: a smooth positive field, the limiter is idle almost everywhere.)
 //   cu: offset of (j, i, member 0) inside a level
-template <int STAGE>
+//   LAZY_SEED   the caller has NOT loaded the seed (seed_v is ignored).  The mass leaving the cell is compared with what a lower bound of
+//               the seed makes available (seed_lower_bound, from values the update needs anyway); only a wavefront in which that does
+//               not settle some member's answer loads the seed and runs fct_multiplier as it is.  Elsewhere the multiplier is exactly
+//               1, as fct_multiplier would have found: same stores, same flags.  `!(a <= b)`: a NaN on either side takes the load.
+//               A tracer that is not positive-definite never had a use for its seed.
+#ifndef PAMA_SEED_SKIP_NOTE
+#define PAMA_SEED_SKIP_NOTE(P, t, k, j, i, e, loaded)     // (the host emulation counts the rows of either path)
+#endif
+template <int STAGE, bool LAZY_SEED = false>
 PAMA_D void finish_tracer_cell(const Params &P, int t, double *prim_out, double *__restrict__ seed, double *__restrict__ mult,
                                const FctRows &rows, int k, int j, int i, int e, unsigned eu, long long cu, long long ix,
                                double F_lo, double F_hi, double yl, double yh, double zl, double zh, double seed_v, double q_in,
                                double q_0, double rho_in, double rho_0, double rrho, double dzk, double rdzk, double dt_dyn,
                                double dt_stage) {
-  own_multiplier_cell<false>(P, t, mult, rows, k, j, i, e, eu, ix, F_lo, F_hi, yl, yh, zl, zh, seed_v, dzk, rdzk, dt_stage);
+  if constexpr (LAZY_SEED) {
+    double m_t = 1.0;
+    if ((P.pos_mask >> t) & 1ull) {
+      const double m_in = mul_rn(q_in, rho_in), m_0 = (STAGE > 1) ? mul_rn(q_0, rho_0) : 0.0;
+      const double at_least = fct_mass_available(P, seed_lower_bound<STAGE>(m_0, m_in, q_in, rho_in), dzk);
+      const double mass_out = fct_mass_out(P, F_lo, F_hi, yl, yh, zl, zh, dzk, rdzk, dt_stage);
+      const bool open = !(mass_out <= at_least);
+      if (wave_any_or_lane(open))
+        m_t = fct_multiplier(P, ld_once<PAMA_STREAM_X1>(uni(seed + (long long)t * P.ncell + ix), eu), F_lo, F_hi, yl, yh, zl, zh, dzk, rdzk, dt_stage);
+      PAMA_SEED_SKIP_NOTE(P, t, k, j, i, e, open);
+    }
+    own_multiplier_store<false>(P, t, mult, rows, k, j, i, e, eu, ix, m_t);
+  } else {
+    own_multiplier_cell<false>(P, t, mult, rows, k, j, i, e, eu, ix, F_lo, F_hi, yl, yh, zl, zh, seed_v, dzk, rdzk, dt_stage);
+  }
   double v, new_seed;
   tracer_new_value<STAGE>(P, t, F_lo, F_hi, yl, yh, zl, zh, q_in, q_0, rho_in, rho_0, rdzk, dt_dyn, v, new_seed);
   uniw(seed + (long long)t * P.ncell + ix)[eu] = new_seed;
@@ -2159,7 +2290,9 @@ PAMA_D void xsweep_pressure_epilogue(const Params &P, double *prim_out, const Li
 //          (NT = 1 -- no further tracers are swept and no mass flux is kept for them; spans of at most XSTASH_CELLS cells): the lane keeps the rho*theta of the cells it completes in slots of its
 //          own and, behind the sweep loop, makes the next stage's pressure of them itself (xsweep_pressure_epilogue: the arithmetic
 //          of pressure_tail_body on the same doubles -- same bits, no pressure pass, rho*theta never leaves the CU)
-template <int STAGE, bool FOLD = false, class Stash = NoStash>
+//   LAZY_SEED  water vapour's FCT seed is loaded only by wavefronts that cannot tell without it (finish_tracer_cell; seeds of this
+//          library's own chain only: seed_lower_bound)
+template <int STAGE, bool FOLD = false, class Stash = NoStash, bool LAZY_SEED = false>
 PAMA_D void flux_x_update_body(const Params &P, const double *__restrict__ prim_in, const double *__restrict__ prim0,
                                double *__restrict__ prim_out, double *__restrict__ fx, const double *__restrict__ fy,
                                const double *__restrict__ fz, double *__restrict__ seed, double *__restrict__ mult,
@@ -2250,24 +2383,24 @@ PAMA_D void flux_x_update_body(const Params &P, const double *__restrict__ prim_
     auto load_in = [&](int cc, CellIn &ci) {
       const long long o = pbase + (long long)cc * P.sx, ix = fbase + (long long)cc * P.sx;
       ci.rho_in = uni(pr + o)[eu];
-      ci.rho_0 = (STAGE > 1) ? uni(r0 + o)[eu] : 0.0;
+      ci.rho_0 = (STAGE > 1) ? ld_once<PAMA_STREAM_X1>(uni(r0 + o), eu) : 0.0;
 #pragma unroll
-      for (int n = 0; n < NQ; n++) ci.q0[n] = (STAGE > 1) ? uni(prim0 + (long long)(P_U + n) * P.prim_fs + o)[eu] : 0.0;
+      for (int n = 0; n < NQ; n++) ci.q0[n] = (STAGE > 1) ? ld_once<PAMA_STREAM_X1>(uni(prim0 + (long long)(P_U + n) * P.prim_fs + o), eu) : 0.0;
       ci.y0l = have_y ? uni(fy + ix)[eu] : 0.0;
       ci.y0h = have_y ? uni(fy + ix + jp1)[eu] : 0.0;
       ci.z0l = uni(fz + ix)[eu];
       ci.z0h = uni(fz + ix + P.sz)[eu];
 #pragma unroll
       for (int l = 1; l <= NQ; l++) {
-        ci.dy[l] = (have_y && !FOLD) ? uni(fy + (long long)l * P.ncell + ix)[eu] : 0.0;
-        ci.dz[l] = (l == 2 && !have_y) ? 0.0 : uni(fz + (long long)l * P.fz_fs + ix)[eu];   // 2-D: no v tendency, nothing stored
+        ci.dy[l] = (have_y && !FOLD) ? ld_once<PAMA_STREAM_X1>(uni(fy + (long long)l * P.ncell + ix), eu) : 0.0;
+        ci.dz[l] = (l == 2 && !have_y) ? 0.0 : ld_once<PAMA_STREAM_X1>(uni(fz + (long long)l * P.fz_fs + ix), eu);   // 2-D: no v tendency, nothing stored
       }
       ci.tyl = have_y ? uni(fyt + ix)[eu] : 0.0;
       ci.tyh = have_y ? uni(fyt + ix + jp1)[eu] : 0.0;
       ci.tzl = uni(fzt + ix)[eu];
       ci.tzh = uni(fzt + ix + P.sz)[eu];
-      ci.tseed = uni(sdt + ix)[eu];
-      ci.tq0 = (STAGE > 1) ? uni(pt0 + o)[eu] : 0.0;
+      ci.tseed = LAZY_SEED ? 0.0 : ld_once<PAMA_STREAM_X1>(uni(sdt + ix), eu);
+      ci.tq0 = (STAGE > 1) ? ld_once<PAMA_STREAM_X1>(uni(pt0 + o), eu) : 0.0;
     };
     // finish cell cc: F_lo/F_hi = its two x faces; m_in_u = rho*u of the stage input (the product window), q_in = v, w, theta
     auto finish = [&](int cc, const CellIn &ci, const double (&Flo)[1 + NQ], const double (&Fhi)[1 + NQ], double m_in_u,
@@ -2297,9 +2430,9 @@ PAMA_D void flux_x_update_body(const Params &P, const double *__restrict__ prim_
         }
       }
       // Tracer 0 (Dycore.h:525-550, :572-584, :162-221): finished here like the further tracers in x_tracer_sweep
-      finish_tracer_cell<STAGE>(P, tr, prim_out, seed, mult, rows, k, j, cc, e, eu, cu0 + (long long)cc * P.sx, fbase + (long long)cc * P.sx,
-                                Ft_lo, Ft_hi, ci.tyl, ci.tyh, ci.tzl, ci.tzh, ci.tseed, qt_in, ci.tq0, ci.rho_in, ci.rho_0, rrho, dzk,
-                                rdzk, dt_dyn, dt_stage);
+      finish_tracer_cell<STAGE, LAZY_SEED>(P, tr, prim_out, seed, mult, rows, k, j, cc, e, eu, cu0 + (long long)cc * P.sx, fbase + (long long)cc * P.sx,
+                                           Ft_lo, Ft_hi, ci.tyl, ci.tyh, ci.tzl, ci.tzh, ci.tseed, qt_in, ci.tq0, ci.rho_in, ci.rho_0, rrho, dzk,
+                                           rdzk, dt_dyn, dt_stage);
     };
     // Faces c0 .. c1: the last one closes the last cell.  It belongs to the next span (or is the periodic face nx == face 0)
     // and is computed here a second time, with the same bits -- one polynomial set per span instead of a dependency.
@@ -2331,7 +2464,7 @@ PAMA_D void flux_x_update_body(const Params &P, const double *__restrict__ prim_
       const double Ft = mul_rn(ruf, up ? prevR_t : Lt);      // x flux of water vapour (Dycore.h:367-385)
       if (c < c1) {                                          // the faces this span owns
         if (more_tracers) uniw(ruf_line + (long long)c * P.sx)[eu] = ruf;   // for the tracer sweeps
-        uniw(flt + (long long)c * P.sx)[eu] = Ft;            // (read again where the limiter acts: tracer_fixup_line_body)
+        st_once<PAMA_STREAM_X2>(uniw(flt + (long long)c * P.sx), eu, Ft);   // (read again where the limiter acts: tracer_fixup_line_body)
       }
       ruf_close = ruf;                                       // (after the last trip: face c1)
       F[0] = ruf;

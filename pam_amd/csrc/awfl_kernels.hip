@@ -257,7 +257,8 @@ __device__ __forceinline__ void stage_pow_tab(Params &P, PowTab *sh_tab);
 constexpr size_t XUPD_STASH_DOUBLES = (size_t)FLUX_WAVES * XSTASH_CELLS * XSTASH_LANES;
 constexpr size_t XUPD_STASH_LDS = XUPD_STASH_DOUBLES * sizeof(double) + sizeof(PowTab);
 static_assert(XSTASH_LANES == 64, "a stash slot per lane of a wavefront");
-template <int STAGE, bool FOLD, bool PRESSURE = false>
+// LAZY_SEED: water vapour's FCT seed only where a bound of it does not settle the multiplier (flux_x_update_body; pam_amd_awfl_set_seed_skip)
+template <int STAGE, bool FOLD, bool PRESSURE = false, bool LAZY_SEED = false>
 __global__ void __launch_bounds__(FLUX_THREADS, 2) awfl_xupd_kernel(Params P, EnsRange R, const double *__restrict__ prim_in,
                                                                      const double *__restrict__ prim0,
                                                                      double *__restrict__ prim_out, double *__restrict__ fx,
@@ -278,12 +279,12 @@ __global__ void __launch_bounds__(FLUX_THREADS, 2) awfl_xupd_kernel(Params P, En
     LineStash stash;     // (threadIdx.x = wavefront * 64 + lane: the lane's slot of cell 0 inside its wavefront's stash)
     stash.slot = (stash_ptr)(xupd_lds + (size_t)(threadIdx.x >> 6) * (XSTASH_CELLS * XSTASH_LANES) + (threadIdx.x & 63));
     if (U.holds(m, el))
-      flux_x_update_body<STAGE, FOLD, LineStash>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span,
-                                                 dt_dyn, dt_stage, tracers_inline != 0, stash);
+      flux_x_update_body<STAGE, FOLD, LineStash, LAZY_SEED>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span,
+                                                            dt_dyn, dt_stage, tracers_inline != 0, stash);
   } else {
     if (U.holds(m, el))
-      flux_x_update_body<STAGE, FOLD>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span,
-                                      dt_dyn, dt_stage, tracers_inline != 0);
+      flux_x_update_body<STAGE, FOLD, NoStash, LAZY_SEED>(P, prim_in, prim0, prim_out, fx, fy, fz, seed, mult, rows, m.line, R.e0 + el, sp * span, span,
+                                                          dt_dyn, dt_stage, tracers_inline != 0);
   }
 }
 // x sweeps of tracers 1.. (x_tracer_sweep): wave unit u -> (x line, member block, span, group of G tracers).  PHASE 1 (the cells' FCT
@@ -1161,6 +1162,7 @@ struct pam_amd_awfl {
     int xshuf = 0;             // x tile kernels, exchange between neighbouring cells: 0 automatic, 1 through LDS, 2 wavefront shuffles
     int tail_fuse = 0;         // NT > 1: phase 2 + pressure pass + vapour fix-up as one launch: 0 automatic (on), 1 off, 2 on
                                // NT = 1: the pressure pass inside the x-sweep (xsweep_pressure): 0 automatic, 1 off, 2 on
+    int seed_skip = 0;         // member-lane x-sweeps: water vapour's FCT seed only where it can matter: 0 automatic, 1 off, 2 on
     int fold = 0;              // y differences of the state folded into the z sweep's output (P.yz_fold): 0 automatic, 1 off, 2 on
     int tile_pressure = 0;     // 0 automatic, 1 separate pressure pass, 2 inside the x tile kernel
     int tile_state_parts = 0;  // 0 automatic, 1 one lane does the whole state pass, 2 three parts
@@ -1326,8 +1328,9 @@ auto by_stage(int st, F &&f) {
 }
 
 // One tendency stage of one member range: its number, input, sub-step start (base) and output buffers (the output differs from both in
-// the fused stage), the sub-step length and the stage's share of it.
-struct StageArgs { int st; const double *in, *base; double *out; double dt_dyn, dt_stage; };
+// the fused stage), the sub-step length and the stage's share of it.  own_seeds: the FCT seeds the stage reads were made by this
+// timeStep's own chain (init_prim, then stage after stage) -- what seed_lower_bound's proof is about; not so in pam_amd_awfl_debug_stage
+struct StageArgs { int st; const double *in, *base; double *out; double dt_dyn, dt_stage; bool own_seeds = false; };
 
 // Launch shape of the y/z flux TILE kernel for (cells per y tile, levels per z tile; 0 = ftile_geometry's own choice): nby workgroups of
 // y tiles, then nbz of z tiles, all of T lanes -- the larger of the two tiles in whole wavefronts (at most ftile_max_threads(P))
@@ -1549,6 +1552,20 @@ bool xsweep_pressure(const pam_amd_awfl *h, int span) {
   return h->want.tail_fuse == 2 || (h->want.tail_fuse == 0 && XSWEEP_PRESSURE_AUTO);
 }
 
+// Member-lane sweeps: water vapour's FCT seed loaded only by the wavefronts that cannot tell without it (awfl_xupd_kernel<., ., ., true>;
+// seed_lower_bound holds the bound and its proof).  Same bits either way.  Only for stages whose seeds this timeStep's own chain has made
+// (StageArgs::own_seeds).  pam_amd_awfl_set_seed_skip: 1 never, 2 wherever that holds, 0 automatic = wherever that holds: measured on
+// MI355X (round 19, profiles/r19_ab_c2.txt) on top of the streaming policy C2 2.8101 -> 2.8310 G, ahead in nine of ten rounds, and
+// with the policy the slowest of five runs above the parent's fastest in two sessions of three (docs/experiments.md).
+#ifndef PAMA_SEED_SKIP_AUTO
+#define PAMA_SEED_SKIP_AUTO 1      // (a macro, like PAMA_STREAM_*: the A/B builds differ in one of them each)
+#endif
+constexpr bool SEED_SKIP_AUTO = PAMA_SEED_SKIP_AUTO != 0;
+bool seed_skip(const pam_amd_awfl *h, const StageArgs &a) {
+  if (!a.own_seeds) return false;
+  return h->want.seed_skip == 2 || (h->want.seed_skip == 0 && SEED_SKIP_AUTO);
+}
+
 // x direction as tile kernels: a lane per cell, the whole ensemble in one launch (small ensembles; launches the sweeps cannot fill the chip with)
 int launch_xupd_tiles(pam_amd_awfl *h, const StageArgs &a, EnsRange r, hipStream_t s) {
   const Params &P = h->P;
@@ -1643,7 +1660,10 @@ XupdResult launch_xupd_sweeps(pam_amd_awfl *h, const StageArgs &a, EnsRange r, h
   const bool pressure = xsweep_pressure(h, span);
   {
     // (fold: the z sweep has left the y+z part of the state's divergence in flux_z: no y differences to load)
-    const auto kernel = by_stage(a.st, [&](auto S) {
+    const auto kernel = seed_skip(h, a) ? by_stage(a.st, [&](auto S) {
+      return pressure ? (P.yz_fold ? awfl_xupd_kernel<S(), true, true, true> : awfl_xupd_kernel<S(), false, true, true>)
+                      : (P.yz_fold ? awfl_xupd_kernel<S(), true, false, true> : awfl_xupd_kernel<S(), false, false, true>);
+    }) : by_stage(a.st, [&](auto S) {
       return pressure ? (P.yz_fold ? awfl_xupd_kernel<S(), true, true> : awfl_xupd_kernel<S(), false, true>)
                       : (P.yz_fold ? awfl_xupd_kernel<S(), true> : awfl_xupd_kernel<S(), false>);
     });
@@ -2186,7 +2206,7 @@ int enqueue_step(pam_amd_awfl *h, StepCall &s) {
     double *const buf[3] = {h->prim0, h->prim1, h->prim2};
     for (int st = 1; st <= 3; st++) {
       const StageSpec &t = spec[st - 1];
-      const StageArgs a{st, buf[t.in], buf[t.base], buf[t.out], s.dt_dyn, t.dt_factor * s.dt_dyn};
+      const StageArgs a{st, buf[t.in], buf[t.base], buf[t.out], s.dt_dyn, t.dt_factor * s.dt_dyn, true};   // (init_prim made the first seeds)
       if ((rc = next_fct_stage(h))) return rc;
       for (auto &c : h->chunks)
         if ((rc = run_stage(h, c, a, s.forked, prev_flux))) return rc;
@@ -2454,7 +2474,10 @@ int pam_amd_awfl_init(const pam_amd_awfl_config_t *cfg, pam_amd_awfl_t **out) {
       (const void *)awfl_flux_tile_kernel<false>, (const void *)awfl_flux_tile_kernel<true>,
       // (the x-sweeps with the pressure inside: XUPD_STASH_LDS = 67.5 KB)
       (const void *)awfl_xupd_kernel<1, false, true>, (const void *)awfl_xupd_kernel<2, false, true>, (const void *)awfl_xupd_kernel<3, false, true>,
-      (const void *)awfl_xupd_kernel<1, true, true>, (const void *)awfl_xupd_kernel<2, true, true>, (const void *)awfl_xupd_kernel<3, true, true>};
+      (const void *)awfl_xupd_kernel<1, true, true>, (const void *)awfl_xupd_kernel<2, true, true>, (const void *)awfl_xupd_kernel<3, true, true>,
+      (const void *)awfl_xupd_kernel<1, false, true, true>, (const void *)awfl_xupd_kernel<2, false, true, true>,
+      (const void *)awfl_xupd_kernel<3, false, true, true>, (const void *)awfl_xupd_kernel<1, true, true, true>,
+      (const void *)awfl_xupd_kernel<2, true, true, true>, (const void *)awfl_xupd_kernel<3, true, true, true>};
   for (const void *kernel : big_lds_kernels) INIT_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #undef INIT_TRY
   h->flux_lds_floor = 0;   // no residency cap by default
@@ -2908,6 +2931,14 @@ int pam_amd_awfl_set_tail_fusion(pam_amd_awfl_t *h, int mode) {
   if (mode < 0 || mode > 2) return fail(PAM_AMD_EINVAL, "set_tail_fusion: 0 = automatic, 1 = separate launches, 2 = fused where supported");
   drop_graphs(h);
   h->want.tail_fuse = mode;
+  return PAM_AMD_OK;
+}
+
+int pam_amd_awfl_set_seed_skip(pam_amd_awfl_t *h, int mode) {
+  if (!h) return fail(PAM_AMD_EINVAL, "null handle");
+  if (mode < 0 || mode > 2) return fail(PAM_AMD_EINVAL, "set_seed_skip: 0 = automatic, 1 = the seed is always loaded, 2 = only where it can matter");
+  drop_graphs(h);
+  h->want.seed_skip = mode;
   return PAM_AMD_OK;
 }
 

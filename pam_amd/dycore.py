@@ -273,6 +273,11 @@ class Dycore:
         ("off": the x-sweep loads both); same bits (include/pam_amd_awfl.h)"""
         check(self._lib.pam_amd_awfl_set_yz_fold(self._h, self.FOLD[mode]))
 
+    def set_seed_skip(self, mode="auto"):
+        """member-lane x-sweeps: water vapour's FCT seed loaded only where a lower bound of it does not settle the multiplier ("on") or
+        always ("off"); same bits (include/pam_amd_awfl.h)"""
+        check(self._lib.pam_amd_awfl_set_seed_skip(self._h, {"auto": 0, "off": 1, "on": 2}[mode]))
+
     def set_launch_tuning(self, want_units=0, two_phase_below=-1, split_below=-1):
         """launch-shape thresholds of THIS handle's sweep kernels, in wavefronts (0 / -1 = leave as it is); same results"""
         check(self._lib.pam_amd_awfl_set_handle_launch_tuning(self._h, int(want_units), int(two_phase_below), int(split_below)))

@@ -4,7 +4,7 @@
 usage: python tools/isa_compare.py BASE NEW [KERNEL [LINES]] > profiles/rNN_isa_compare.txt
 BASE / NEW: a .hip source (compiled here: hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only) or its assembly (.s).
 Kernels are matched by demangled name after mapping the tracer-sweep families that were merged into one
-(awfl_xtr_kernel<S, P, A> -> <S, P, 2, A>, awfl_xtrn_kernel<S, P, G> -> awfl_xtr_kernel<S, P, G, false>) and the two canary kernels that became coupling_canary_kernel<word>; symbol names and local labels
+(awfl_xtr_kernel<S, P, A> -> <S, P, 2, A>, awfl_xtrn_kernel<S, P, G> -> awfl_xtr_kernel<S, P, G, false>, awfl_xupd_kernel<S, F[, P]> -> <S, F, P, false>) and the two canary kernels that became coupling_canary_kernel<word>; symbol names and local labels
 are normalised.  Per kernel: the resources the compiler reports (VGPRs, AGPRs, SGPRs, scratch, waves per SIMD, LDS) and the instruction
 stream -- `identical`, `registers renamed` (the same opcodes in the same order, other register numbers) or `DIFFERENT` (with the
 opcode-count deltas).  KERNEL: print a unified diff of that kernel's streams as well (LINES of it, default 80).
@@ -42,6 +42,9 @@ def canon(d):
     m = re.match(r"awfl_xtr_kernel<(\d+), (\d+), (false|true)>", d)
     if m:
         return "awfl_xtr_kernel<%s, %s, 2, %s>" % m.groups()
+    m = re.match(r"awfl_xupd_kernel<(\d+), (false|true)(?:, (false|true))?>$", d)      # (PRESSURE and LAZY_SEED default to false)
+    if m:
+        return "awfl_xupd_kernel<%s, %s, %s, false>" % (m.group(1), m.group(2), m.group(3) or "false")
     if d in CANARY:
         return "coupling_canary_kernel<%dull>" % CANARY[d]
     return d
