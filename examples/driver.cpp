@@ -53,6 +53,7 @@
 #include "modules/saturation_adjustment.h"
 #include "modules/surface_friction.h"
 #include "modules/surface_fluxes.h"
+#include "modules/large_scale_forcing.h"
 #include "modules/horizontal_average.h"
 #include "modules/time_average.h"
 #include "modules/mean_state_acceleration.h"
@@ -315,7 +316,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
-//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
+//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
 //          [--flux-profiles PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
@@ -426,6 +427,15 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              the SGS: "sfc_shf" and "sfc_lhf" from the lowest level and "sfc_temp", which starts at SST [K] and, with
 //                              DEPTH > 0 [m of water], takes the net energy (with --radiation-gray [--shortwave] the radiation too).  One
 //                              "surface:" line per output step with the means of the three.  Composes with the rest.
+//   --ls-forcing PATH [--coriolis F]  large-scale forcing (modules/large_scale_forcing.h).  PATH is a raw float64 file of (rows, crm_nz),
+//                              rows <= 12, every row one profile applied to every member, in this order: wsub [m/s], temp_tend [K/s],
+//                              qv_tend [1/s], ug, vg [m/s], nudge_temp [K], nudge_qv [1], nudge_u, nudge_v [m/s], nudge_rate_temp,
+//                              nudge_rate_qv, nudge_rate_uv [1/s].  A row that is all NaN, or missing at the end, means "absent".
+//                              --coriolis F sets "ls_fcor" of every member [1/s] and needs the rows ug and vg.
+//                              modules::ls_forcing_init once, then modules::ls_forcing every CRM step after the sponge layer and before
+//                              the surface fluxes.  One "ls forcing:" line per output step with the domain means of uvel and vvel and
+//                              the mean temp of level 0.  Composes with the rest (--surface, --sgs-smag, --radiation-gray, --hyperdiff,
+//                              --accelerate, --vt).
 //   --sfc-fluxes SHF LHF       with --sgs-smag: option sgs_smag_surface_fluxes; "sfc_shf" and "sfc_lhf" are filled uniformly, once, with
 //                              SHF and LHF (W/m2, positive upward) and enter row 0 of temp and of the vapour in every SGS step.  Both
 //                              compose with every other flag
@@ -465,15 +475,15 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              prof_flux_v and prof_tke, printed with %.17g; nothing else of the run changes.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false, shortwave = false, surface = false;
+  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false, shortwave = false, surface = false, ls_forcing = false, coriolis = false;
   int radiation_gray_every = 1;
   double sw_coszen = 1, sw_albedo = 0.07;
-  double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0, sfc_shf = 0, sfc_lhf = 0, surface_sst = 300, surface_depth = 0;
+  double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0, sfc_shf = 0, sfc_lhf = 0, surface_sst = 300, surface_depth = 0, ls_fcor = 0;
   int handoff_rad_nx = 0, handoff_rad_ny = 0;
   std::string handoff_path;
   double tau = 0, bflx = 0, accel_factor = 0, accel_max_ttend = 5.0, vt_rate = 0, vt_limit = 0.05;
   int rad_nx = 0, rad_ny = 0;
-  std::string stats, edges, rad_path, diag, vt_path, column_diag, flux_profiles;
+  std::string stats, edges, rad_path, diag, vt_path, column_diag, flux_profiles, ls_path;
 };
 
 // one JSON number that Python's json module reads back exactly (NaN / Infinity for the non-finite)
@@ -665,6 +675,26 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     }
     if (mods.surface)                                                        // --surface: after the friction's init, whose z0 it takes
       coupler.run_module("surface_fluxes_init", [&](pam::PamCoupler &c) { modules::surface_fluxes_init(c, mods.surface_sst, mods.surface_depth); });
+    if (mods.ls_forcing) {                                                   // --ls-forcing: the rows of the file, an all-NaN row absent
+      std::ifstream in(mods.ls_path, std::ios::binary);
+      if (!in) endrun("cannot open the --ls-forcing file");
+      in.seekg(0, std::ios::end);
+      const size_t bytes = (size_t)in.tellg(), row = (size_t)crm_nz * sizeof(double);
+      if (bytes == 0 || bytes % row != 0 || bytes / row > 12) endrun("the --ls-forcing file must hold 1 to 12 rows of crm_nz float64 values");
+      in.seekg(0);
+      modules::LsProfiles P;
+      std::vector<real> *slots[12] = {&P.wsub, &P.temp_tend, &P.qv_tend, &P.ug, &P.vg, &P.nudge_temp, &P.nudge_qv, &P.nudge_u, &P.nudge_v,
+                                      &P.nudge_rate_temp, &P.nudge_rate_qv, &P.nudge_rate_uv};
+      for (size_t r = 0; r < bytes / row; r++) {
+        std::vector<real> v(crm_nz);
+        in.read((char *)v.data(), row);
+        bool some = false;
+        for (real x : v) some = some || x == x;
+        if (some) *slots[r] = v;
+      }
+      if (mods.coriolis) P.fcor = {mods.ls_fcor};
+      coupler.run_module("ls_forcing_init", [&](pam::PamCoupler &c) { modules::ls_forcing_init(c, P); });
+    }
     const size_t ncell = (size_t)crm_nz * crm_ny * crm_nx * nens;
     std::vector<real> buf(ncell);
     auto fetch = [&](std::string const &name) {
@@ -718,6 +748,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         }
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         if (apply_sponge && !dbg.no_sponge) coupler.run_module("sponge_layer", modules::sponge_layer);         // driver.cpp:249-251
+        if (mods.ls_forcing) coupler.run_module("ls_forcing", [](pam::PamCoupler &c) { modules::ls_forcing(c); });
         if (mods.surface) coupler.run_module("surface_fluxes", [](pam::PamCoupler &c) { modules::compute_surface_fluxes(c); });
         if (mods.surface_friction) coupler.run_module("surface_friction", modules::compute_surface_friction);
         if (mods.hyperdiff) coupler.run_module("hyperdiffusion", [](pam::PamCoupler &c) { modules::hyperdiffusion(c); });
@@ -771,6 +802,14 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
               items.push_back({n, 0, dm.get<real const, 3>(n).data(), (long long)crm_ny * crm_nx * nens, items.size()});
             auto s3 = pam::diagnostics::scan(items, 0);
             std::printf("surface: etime %g , shf %.9g , lhf %.9g , sfc_temp %.17g\n", etime_gcm, s3[0].mean(), s3[1].mean(), s3[2].mean());
+          }
+          if (mods.ls_forcing) {                                             // the same scan: the domain means of the winds, and temp of level 0
+            const long long level = (long long)crm_ny * crm_nx * nens;
+            std::vector<pam::diagnostics::Item> items;
+            for (char const *n : {"uvel", "vvel"}) items.push_back({n, 0, dm.get<real const, 4>(n).data(), level * crm_nz, items.size()});
+            items.push_back({"temp", 0, dm.get<real const, 4>("temp").data(), level, items.size()});
+            auto s3 = pam::diagnostics::scan(items, 0);
+            std::printf("ls forcing: etime %g , uvel %.9g , vvel %.9g , temp0 %.9g\n", etime_gcm, s3[0].mean(), s3[1].mean(), s3[2].mean());
           }
           char t[64];
           std::snprintf(t, sizeof(t), "%s%.6g", maxw_series.empty() ? "" : ",", maxw);
@@ -1065,6 +1104,8 @@ int main(int argc, char **argv) {
         const std::string n(b + 1 < argc - 1 ? argv[b + 1] : "");                // the optional DEPTH: an argument that is a number
         if (!n.empty() && n.find_first_not_of("0123456789.eE+") == std::string::npos) mods.surface_depth = std::atof(argv[++b]);
       }
+      else if (o == "--ls-forcing" && b + 1 < argc - 1) { mods.ls_forcing = true; mods.ls_path = argv[++b]; }
+      else if (o == "--coriolis" && b + 1 < argc - 1) { mods.coriolis = true; mods.ls_fcor = std::atof(argv[++b]); }
       else if (o == "--gcm-handoff" && b + 3 < argc - 1) {
         mods.handoff = true;
         mods.handoff_rad_nx = std::atoi(argv[++b]);
@@ -1075,7 +1116,7 @@ int main(int argc, char **argv) {
       else if (o == "--flux-profiles" && b + 1 < argc - 1) mods.flux_profiles = argv[++b];
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] "
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] "
                "[--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->");
     }
     if (mods.radiation_gray && mods.radiation) die("--radiation-gray and --radiation both fill the one radiation slot: give one of them");
@@ -1083,6 +1124,7 @@ int main(int argc, char **argv) {
     if (mods.shortwave && !mods.radiation_gray) die("--shortwave COSZEN [ALBEDO] needs --radiation-gray [EVERY]: the sun belongs to the native scheme");
     if ((mods.sgs_moist || mods.sfc_fluxes) && !mods.sgs_smag) die("--sgs-moist and --sfc-fluxes need --sgs-smag CS PRANDTL");
     if (mods.surface && !mods.sgs_smag) die("--surface SST [DEPTH] needs --sgs-smag CS PRANDTL: the closure is what takes the fluxes up");
+    if (mods.coriolis && !mods.ls_forcing) die("--coriolis F needs --ls-forcing PATH with the rows ug and vg: the force acts about a geostrophic wind");
     if (mods.surface && mods.sfc_fluxes) die("--surface and --sfc-fluxes both fill sfc_shf and sfc_lhf: give one of them");
     if (mods.surface && (!(mods.surface_sst > 0) || mods.surface_depth < 0)) die("--surface SST [DEPTH] needs SST > 0 K and DEPTH >= 0 m");
     return run_yaml(argv[2], nens_override, steps_limit, check, argv[argc - 1], dbg, mods);

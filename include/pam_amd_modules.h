@@ -863,6 +863,73 @@ int pam_amd_surface_fluxes(int nens, int nx, int ny, int nz, const double *temp,
                            double gust, double wetness, double grav, double cp_d, double R_v, double latvap, double slab_heat_capacity,
                            double dt, double *sfc_shf, double *sfc_lhf, void *stream);
 
+/* Large-scale forcing: what a standalone CRM takes from outside its domain, once per CRM step (SAM's forcing + subsidence + nudging +
+ * coriolis): a prescribed large-scale vertical velocity that advects every column, horizontally uniform tendencies of temp and vapour,
+ * a relaxation of the LEVEL MEANS towards target profiles, and the Coriolis force about a geostrophic wind.  Not part of the reference
+ * tree; the contract is this project's and is restated in numpy in tests/lsforcing_ref.py, which the kernels
+ * match bit for bit.  Fields are (nz,ny,nx,nens); every profile is a DEVICE array (nz,nens), per member, and fcor is (nens).  A term
+ * whose profile is NULL is absent: nothing is read for it and no zero is added.
+ * Everything is fp64, every operation is rounded on its own (no fma), every division is a true IEEE division, and the association is
+ * as written.  rho = rho_d + rho_v as at entry, frozen for the whole call; rho_d is never written, wvel is not an argument.
+ *
+ * pam_amd_ls_nudging: the increments of the relaxation, launched by the layers above only where some target is given.
+ * fields[5] = temp, rho_d, rho_v, uvel, vvel; target[4], rate[4] and inc[4] are tables of (nz,nens) arrays in the order temp,
+ * qv = rho_v / rho, uvel, vvel (rate[2] and rate[3] may be the same array).  For every x whose target is not NULL:
+ *   inc_x(k,e) = (dt rate_x(k,e)) (target_x(k,e) - M(x)(k,e)),
+ * M the level mean of pam_amd_msa_diagnose: cell c belongs to slot c % 16, a slot adds x(k,c,e) r over its cells in ascending c from
+ * 0.0 with r = 1/(ny nx) and the product rounded first, and the 16 slot sums are added in ascending slot order from 0.0.  The quotient
+ * rho_v / (rho_d + rho_v) is formed per cell before it enters a slot.  It is the mean that is nudged, not each cell, so the turbulence
+ * is not damped.  A NULL target is not read, its rate is not read, its inc must be NULL, and only the fields a given target needs
+ * (temp; rho_d and rho_v; uvel; vvel) must be non-NULL and are read.  The call writes only inc.  No floating-point atomics, no scratch.
+ * With every target NULL the call returns PAM_AMD_OK and launches nothing.
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: a size below 1; ny nx beyond 2^31 - 1; nz beyond 65535;
+ * a NULL table; a target without its rate, its inc or one of its fields; an inc without its target; dt not finite and positive; an inc
+ * that overlaps anything read or another inc.
+ *
+ * pam_amd_ls_forcing works IN PLACE on uvel, vvel, temp and tracers[num_tracers], mass densities as in pam_amd_sgs_smag_diffuse, with
+ * the positive[num_tracers] flags of pam_amd_hyperdiffusion (HOST tables).  The vapour is the table's entry that IS rho_v (pointer
+ * equality; it may stand at any place, once).  zmid, wsub, temp_tend, qv_tend, ug, vg and the four inc[x] (the table itself may be
+ * NULL: no nudging) are (nz,nens).  Per (column, member), with every right-hand value taken from the state at entry, gc = grav / cp_d
+ * formed once on the host, w = wsub(k,e), z = zmid(.,e):
+ *   Subsidence (wsub given), first-order upwind in ADVECTIVE form on the carried quantity g: g = uvel; g = vvel; for temp
+ *   g = temp + gc z, the quantity the SGS diffuses, so an adiabat is left alone; for every tracer g = rho_x / rho.
+ *     w > 0 and k > 0:     adv = (w (g(k) - g(k-1))) / (z(k) - z(k-1));
+ *     w < 0 and k < nz-1:  adv = (w (g(k+1) - g(k))) / (z(k+1) - z(k));
+ *     dg = -(dt adv); otherwise the term is absent, except that a NaN w gives dg = w.
+ *   The subsiding air leaves sideways through the periodic walls: g at an extremum is never overshot (for |w| dt <= the level
+ *   spacing, which the layers above enforce), and column mass is deliberately not conserved.
+ *   Uniform increments: d_T = dt temp_tend + inc_T and d_q = dt qv_tend + inc_q, an absent addend absent; for the winds inc alone.
+ *   Update, as increments, an absent addend absent and a field with no addend at all neither read nor written:
+ *     temp += dg_T + d_T;   uvel += dg_u + inc_u;   vvel += dg_v + inc_v;
+ *     a tracer: rho_x += rho (dg_x [+ d_q for the vapour]); where positive[i] != 0 a result below 0.0 becomes 0.0 (a NaN stays).  The
+ *     clamp can only act through d_q or rounding, and it is the one place where vapour is created.
+ *   So a zero forcing keeps every bit of every field (x + 0.0 == x in bits for every x but -0.0).
+ *   Coriolis (fcor, ug, vg given), after the above, on the updated winds: the trapezoidal rotation of the ageostrophic wind, which is
+ *   neutral for any f dt (a forward step would amplify the inertial oscillation on every step):
+ *     a = 0.5 (fcor(e) dt); c1 = 1.0 - a a; c2 = 2.0 a; den = 1.0 + a a; du = u - ug; dv = v - vg;
+ *     u' = ug + ((c1 du) + (c2 dv)) / den;   v' = vg + ((c1 dv) - (c2 du)) / den.
+ * Nothing is refused because of a value in a field; a NaN stays in its own column (for M: in its own level and member).  The same bits
+ * from run to run and for any split of the members over calls, given the matching slices of the profiles.
+ * One launch: a thread owns a (column, member), members across the lanes, and walks k upward with the values of entry of the level
+ * below in registers; loads are requested AHEAD = 4 levels before use; rho of a level is formed once for up to four tracers; no
+ * scratch, no LDS, no atomics.  Flat offsets are 64 bits wide from 2^29 elements per field on;
+ * pam_amd_ls_forcing_debug_wide_index(1) forces those instances at any size (0: back to automatic).  With every term absent the call
+ * returns PAM_AMD_OK and launches nothing.
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: a size below 1; ny nx beyond 2^31 - 1; a NULL uvel,
+ * vvel, temp, rho_d, rho_v or zmid; num_tracers outside 0..64; a NULL tracer, or a NULL table with num_tracers > 0; ug without vg or
+ * vg without ug; fcor without the pair or the pair without fcor; dt, grav or cp_d not finite and positive; qv_tend or inc[1] without
+ * rho_v in the tracer table; an output that overlaps a read-only input or another output, except rho_v standing once in the tracer
+ * table.  The limits |wsub| dt <= min (z(k+1) - z(k)) and dt rate <= 1 are the business of the layers above
+ * (pam_amd.modules.ls_forcing, modules::ls_forcing), not of the C ABI.  Without a device a call that passes and has a term returns
+ * PAM_AMD_ENOGPU. */
+int pam_amd_ls_nudging(int nens, int nx, int ny, int nz, const double *const *fields, const double *const *target,
+                       const double *const *rate, double dt, double *const *inc, void *stream);
+int pam_amd_ls_forcing(int nens, int nx, int ny, int nz, double *uvel, double *vvel, double *temp, int num_tracers,
+                       double *const *tracers, const unsigned char *positive, const double *rho_d, const double *rho_v, const double *zmid,
+                       const double *wsub, const double *temp_tend, const double *qv_tend, const double *const *inc, const double *fcor,
+                       const double *ug, const double *vg, double dt, double grav, double cp_d, void *stream);
+int pam_amd_ls_forcing_debug_wide_index(int on);
+
 #ifdef __cplusplus
 }
 #endif

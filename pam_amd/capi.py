@@ -211,6 +211,9 @@ MODULE_SYMBOLS = {
                                   + [C.c_double] * 10 + [C.c_void_p] * 5),
     "pam_amd_radiation_gray_sw_debug_wide_index": (C.c_int, [C.c_int]),
     "pam_amd_surface_fluxes": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 13 + [C.c_double] * 8 + [C.c_void_p] * 3),
+    "pam_amd_ls_nudging": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 2),
+    "pam_amd_ls_forcing": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 12 + [C.c_double] * 3 + [C.c_void_p]),
+    "pam_amd_ls_forcing_debug_wide_index": (C.c_int, [C.c_int]),
 }
 
 

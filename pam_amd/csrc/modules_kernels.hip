@@ -4256,3 +4256,155 @@ extern "C" int pam_amd_surface_fluxes(int nens, int nx, int ny, int nz, const do
                        cstar, sfc_temp, lw_down, lw_up, sw_down, sw_up, P, sfc_shf, sfc_lhf);
   return stats_launch_check(who);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Large-scale forcing (SAM's forcing + subsidence + nudging + coriolis, once per CRM step): a prescribed large-scale vertical velocity
+// advects every column, horizontally uniform tendencies act on temp and vapour, the level means are relaxed towards target profiles,
+// and the ageostrophic wind is rotated.  Not in the reference tree; the contract is in include/pam_amd_modules.h and DESIGN.md
+// section 8, its arithmetic in lsforcing_device.h.  TWO launches at the most.  The nudging increments are level means on the slot order
+// of msa_mean_kernel (slot_reduce): a workgroup = (level, block of up to 64 members) x 16 slots, no scratch, no floating-point atomics.
+// The forcing is ONE launch: a thread owns a (column, member), members and then x across the lanes, and walks the column upward with
+// the level below kept in registers: in place, no scratch, no LDS, no atomics.  IDX: unsigned while a field is below 2^29 doubles.
+#include "lsforcing_device.h"
+
+namespace {
+namespace ls = pama::lsforcing;
+constexpr int LSFORCING_THREADS = 64;
+constexpr long long LSFORCING_NARROW_CELLS = 1ll << 29;    // fields from this size on take the long long instances
+
+struct LsNudgeFields { const double *p[ls::NFIELDS]; };
+struct LsNudgeIn { const double *p[ls::NX]; };
+struct LsNudgeOut { double *p[ls::NX]; };
+
+// grid (member blocks, levels), block (members, 16 slots): inc_x(k,e) = (dt rate_x) (target_x - M(x)) for every x with a target
+__global__ void __launch_bounds__(64 * MOD_NS) ls_nudging_kernel(int nens, int ncol, LsNudgeFields F, LsNudgeIn target, LsNudgeIn rate, double dt,
+                                                                 LsNudgeOut inc) {
+  __shared__ double red[ls::NX * MOD_NS * 64];
+  const int ME = blockDim.x, slot = threadIdx.y;
+  const int e0 = (int)blockIdx.x * ME + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1, k = (int)blockIdx.y;
+  const long long base = (long long)k * ncol * nens + e;
+  const double *f[ls::NFIELDS];
+#pragma unroll
+  for (int i = 0; i < ls::NFIELDS; i++) f[i] = F.p[i] ? F.p[i] + base : nullptr;
+  const bool want[ls::NX] = {target.p[ls::X_T] != nullptr, target.p[ls::X_Q] != nullptr, target.p[ls::X_U] != nullptr, target.p[ls::X_V] != nullptr};
+  double acc[ls::NX] = {0.0, 0.0, 0.0, 0.0};
+  if (ok) ls::mean_walk(f, (long long)nens, ncol, slot, want, acc);
+  slot_reduce<ls::NX>(acc, red);
+  if (slot != 0 || !ok) return;
+  const long long t = (long long)k * nens + e;
+#pragma unroll
+  for (int x = 0; x < ls::NX; x++)
+    if (want[x]) inc.p[x][t] = ls::increment(dt, rate.p[x][t], target.p[x][t], acc[x]);
+}
+
+// grid (ceil(ny nx nens / 64)), block 64: thread t = (j nx + i) nens + e
+template <class IDX, bool SUBS>
+__global__ void __launch_bounds__(LSFORCING_THREADS) ls_forcing_kernel(int nens, long long level, int nz, ls::Args A) {
+  const long long t = (long long)blockIdx.x * LSFORCING_THREADS + (long long)threadIdx.x;
+  if (t >= level) return;
+  const int e = (int)(t % nens);
+  ls::column<IDX, SUBS>(A, (IDX)t, (IDX)level, (IDX)nens, e, nz);
+}
+
+bool g_ls_forcing_force_wide = false;   // pam_amd_ls_forcing_debug_wide_index: tests run the long long instances at small sizes
+}  // namespace
+
+extern "C" int pam_amd_ls_forcing_debug_wide_index(int on) {
+  g_ls_forcing_force_wide = on != 0;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_ls_nudging(int nens, int nx, int ny, int nz, const double *const *fields, const double *const *target,
+                                  const double *const *rate, double dt, double *const *inc, void *stream) {
+  const char *who = "ls_nudging";
+  if (int rc = check_level_grid(who, nens, nx, ny, nz)) return rc;
+  if (!fields || !target || !rate || !inc) return module_error(who, "null pointer table");
+  if (!sgs_positive(dt)) return module_error(who, "dt must be finite and positive");
+  const int needs[ls::NX][2] = {{ls::N_TEMP, ls::N_TEMP}, {ls::N_RHO_D, ls::N_RHO_V}, {ls::N_U, ls::N_U}, {ls::N_V, ls::N_V}};
+  const long long cells = (long long)nx * ny * nens * nz, rows = (long long)nz * nens;
+  std::vector<Span> spans;
+  bool any = false, read[ls::NFIELDS] = {false, false, false, false, false};
+  for (int x = 0; x < ls::NX; x++) {
+    if (!target[x]) {
+      if (inc[x]) return module_error(who, "an inc without its target");
+      continue;
+    }
+    any = true;
+    if (!rate[x] || !inc[x]) return module_error(who, "a target needs its rate and its inc");
+    for (int i : needs[x]) {
+      if (!fields[i]) return module_error(who, "null pointer of a field a target needs");
+      read[i] = true;
+    }
+    spans.push_back({target[x], rows, false});
+    spans.push_back({rate[x], rows, false});
+    spans.push_back({inc[x], rows, true});
+  }
+  if (!any) return PAM_AMD_OK;      // nothing to nudge: no launch
+  for (int i = 0; i < ls::NFIELDS; i++)
+    if (read[i]) spans.push_back({fields[i], cells, false});
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if (int rc = require_device(who)) return rc;
+
+  LsNudgeFields F;
+  LsNudgeIn T, R;
+  LsNudgeOut O;
+  for (int i = 0; i < ls::NFIELDS; i++) F.p[i] = read[i] ? fields[i] : nullptr;
+  for (int x = 0; x < ls::NX; x++) { T.p[x] = target[x]; R.p[x] = target[x] ? rate[x] : nullptr; O.p[x] = target[x] ? inc[x] : nullptr; }
+  const auto [grid, block] = slot_block_shape(nens, nz);
+  hipLaunchKernelGGL(ls_nudging_kernel, grid, block, 0, (hipStream_t)stream, nens, nx * ny, F, T, R, dt, O);
+  return stats_launch_check(who);
+}
+
+extern "C" int pam_amd_ls_forcing(int nens, int nx, int ny, int nz, double *uvel, double *vvel, double *temp, int num_tracers,
+                                  double *const *tracers, const unsigned char *positive, const double *rho_d, const double *rho_v,
+                                  const double *zmid, const double *wsub, const double *temp_tend, const double *qv_tend,
+                                  const double *const *inc, const double *fcor, const double *ug, const double *vg, double dt, double grav,
+                                  double cp_d, void *stream) {
+  const char *who = "ls_forcing";
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return module_error(who, "nens, nx, ny and nz must be >= 1");
+  if ((long long)nx * ny > 0x7fffffffLL) return module_error(who, "ny x nx exceeds 2^31 - 1 columns");
+  const long long level = (long long)nx * ny * nens, cells = level * nz, rows = (long long)nz * nens;
+  if ((level + LSFORCING_THREADS - 1) / LSFORCING_THREADS > 0x7fffffffLL) return module_error(who, "ny x nx x nens exceeds the grid");
+  if (num_tracers < 0 || num_tracers > ls::MAX_TRACERS) return module_error(who, "num_tracers must be in [0, 64]");
+  if (num_tracers > 0 && (!tracers || !positive)) return module_error(who, "null tracer or positive table");
+  if (!uvel || !vvel || !temp || !rho_d || !rho_v || !zmid) return module_error(who, "null pointer");
+  for (int i = 0; i < num_tracers; i++)
+    if (!tracers[i]) return module_error(who, "null tracer pointer");
+  if (!ug != !vg) return module_error(who, "ug and vg come as a pair");
+  if (!fcor != !ug) return module_error(who, "fcor, ug and vg come together");
+  if (!sgs_positive(dt) || !sgs_positive(grav) || !sgs_positive(cp_d)) return module_error(who, "dt, grav and cp_d must be finite and positive");
+  std::vector<Span> spans;
+  spans.push_back({rho_d, cells, false});
+  spans.push_back({zmid, rows, false});
+  for (const double *p : {wsub, temp_tend, qv_tend, ug, vg})
+    if (p) spans.push_back({p, rows, false});
+  for (int x = 0; x < ls::NX; x++)
+    if (inc && inc[x]) spans.push_back({inc[x], rows, false});
+  if (fcor) spans.push_back({fcor, (long long)nens, false});
+  for (double *p : {uvel, vvel, temp}) spans.push_back({p, cells, true});
+  int vapour = -1;
+  for (int i = 0; i < num_tracers; i++) {
+    if (tracers[i] == rho_v && vapour < 0) { vapour = i; continue; }      // the one allowed alias: rho_v itself, once
+    spans.push_back({tracers[i], cells, true});
+  }
+  spans.push_back({rho_v, cells, vapour >= 0});
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if ((qv_tend || (inc && inc[ls::X_Q])) && vapour < 0) return module_error(who, "qv_tend and the vapour's inc need rho_v itself in the tracer table");
+  bool any = wsub || temp_tend || qv_tend || fcor;
+  for (int x = 0; x < ls::NX; x++) any = any || (inc && inc[x]);
+  if (!any) return PAM_AMD_OK;      // every term is absent: no launch
+  if (int rc = require_device(who)) return rc;
+
+  const ls::Args A = ls::make_args(uvel, vvel, temp, num_tracers, tracers, positive, rho_d, rho_v, zmid, wsub, temp_tend, qv_tend, inc, fcor, ug, vg,
+                                   dt, pama::sgs::ratio(grav, cp_d));
+  const dim3 grid((unsigned)((level + LSFORCING_THREADS - 1) / LSFORCING_THREADS)), block(LSFORCING_THREADS);
+  const bool narrow = !g_ls_forcing_force_wide && cells < LSFORCING_NARROW_CELLS;
+  hipStream_t s = (hipStream_t)stream;
+  if (wsub && narrow) hipLaunchKernelGGL((ls_forcing_kernel<unsigned, true>), grid, block, 0, s, nens, level, nz, A);
+  else if (wsub) hipLaunchKernelGGL((ls_forcing_kernel<long long, true>), grid, block, 0, s, nens, level, nz, A);
+  else if (narrow) hipLaunchKernelGGL((ls_forcing_kernel<unsigned, false>), grid, block, 0, s, nens, level, nz, A);
+  else hipLaunchKernelGGL((ls_forcing_kernel<long long, false>), grid, block, 0, s, nens, level, nz, A);
+  return stats_launch_check(who);
+}

@@ -1066,3 +1066,109 @@ def surface_fluxes(coupler, dt=None):
                                          float(coupler.get_option("grav")), float(coupler.get_option("cp_d")), float(coupler.get_option("R_v")),
                                          latvap, cap, dt, dm.get("sfc_shf").data_ptr(), dm.get("sfc_lhf").data_ptr(),
                                          torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+# ---- large-scale forcing: subsidence, horizontally uniform tendencies, nudging of the level means and the Coriolis force about a
+# geostrophic wind (SAM's forcing + subsidence + nudging + coriolis).  Not part of the reference tree: the contract is this project's
+# (include/pam_amd_modules.h at pam_amd_ls_forcing; numpy restatement: tests/lsforcing_ref.py)
+LS_PROFILES = (("ls_wsub", "large-scale vertical velocity [m/s]"), ("ls_temp_tend", "large-scale temperature tendency [K/s]"),
+               ("ls_qv_tend", "large-scale tendency of the vapour mixing ratio rho_v / rho [1/s]"),
+               ("ls_ug", "geostrophic wind, x [m/s]"), ("ls_vg", "geostrophic wind, y [m/s]"),
+               ("ls_nudge_temp", "nudging target of the level-mean temperature [K]"),
+               ("ls_nudge_qv", "nudging target of the level-mean rho_v / rho [1]"),
+               ("ls_nudge_u", "nudging target of the level-mean uvel [m/s]"), ("ls_nudge_v", "nudging target of the level-mean vvel [m/s]"),
+               ("ls_nudge_rate_temp", "nudging rate of temp [1/s]"), ("ls_nudge_rate_qv", "nudging rate of rho_v / rho [1/s]"),
+               ("ls_nudge_rate_uv", "nudging rate of uvel and vvel [1/s]"))
+LS_TARGETS = ("ls_nudge_temp", "ls_nudge_qv", "ls_nudge_u", "ls_nudge_v")                      # in the order of the C ABI's tables
+LS_RATES = ("ls_nudge_rate_temp", "ls_nudge_rate_qv", "ls_nudge_rate_uv", "ls_nudge_rate_uv")
+LS_INCREMENTS = ("ls_inc_temp", "ls_inc_qv", "ls_inc_u", "ls_inc_v")
+LS_NUDGE_FIELDS = ("temp", "density_dry", "water_vapor", "uvel", "vvel")
+
+
+def ls_forcing_init(coupler, wsub=None, temp_tend=None, qv_tend=None, ug=None, vg=None, nudge_temp=None, nudge_qv=None, nudge_u=None,
+                    nudge_v=None, nudge_rate_temp=None, nudge_rate_qv=None, nudge_rate_uv=None, fcor=None):
+    """Once, after the grid is set: registers the profiles that are given as DEVICE entries (nz,nens) under the names of LS_PROFILES
+    ("ls_wsub", ..., the argument's name behind "ls_"), each from nz values (every member alike) or (nz,nens) values, "ls_fcor" (nens)
+    from one value or nens values, and "ls_inc_*" (nz,nens) for every target.  A profile that is not given is not registered and its
+    term is absent from ls_forcing.  ug and vg come as a pair and with fcor; a target comes with its rate.  From the host copies it
+    holds here it sets the options "ls_courant_rate" = max |wsub| / min (zmid(k+1) - zmid(k)) over every member [1/s] and
+    "ls_nudge_rate_max" [1/s], by which ls_forcing refuses a step that is too long; a host model that overwrites an entry between
+    steps with values beyond them sets the two options again."""
+    import numpy as np
+    from .coupler import endrun
+    nz, nens = coupler.get_nz(), coupler.get_nens()
+    dm = coupler.get_data_manager_device_readwrite()
+    given = dict(ls_wsub=wsub, ls_temp_tend=temp_tend, ls_qv_tend=qv_tend, ls_ug=ug, ls_vg=vg, ls_nudge_temp=nudge_temp, ls_nudge_qv=nudge_qv,
+                 ls_nudge_u=nudge_u, ls_nudge_v=nudge_v, ls_nudge_rate_temp=nudge_rate_temp, ls_nudge_rate_qv=nudge_rate_qv,
+                 ls_nudge_rate_uv=nudge_rate_uv)
+    if (ug is None) != (vg is None) or (fcor is None) != (ug is None):
+        endrun("ERROR: ls_forcing_init: ug, vg and fcor come together")
+    for target, rate in zip(LS_TARGETS, LS_RATES):
+        if given[target] is not None and given[rate] is None:
+            endrun("ERROR: ls_forcing_init: %s needs %s" % (target, rate))
+    host = {}
+    for name, desc in LS_PROFILES:
+        if given[name] is None:
+            continue
+        a = np.asarray(given[name], dtype=np.float64)
+        if a.shape == (nz,):
+            a = np.broadcast_to(a[:, None], (nz, nens))
+        if a.shape != (nz, nens):
+            endrun("ERROR: ls_forcing_init: %s needs nz values or (nz,nens) values" % name)
+        host[name] = np.ascontiguousarray(a)
+        if not dm.entry_exists(name):
+            dm.register_and_allocate(name, desc, (nz, nens), ("z", "nens"))
+        dm.get(name).copy_(torch.from_numpy(host[name]))
+    if fcor is not None:
+        f = np.broadcast_to(np.asarray(fcor, dtype=np.float64), (nens,)) if np.ndim(fcor) == 0 else np.asarray(fcor, dtype=np.float64)
+        if f.shape != (nens,):
+            endrun("ERROR: ls_forcing_init: fcor needs one value or nens values")
+        if not dm.entry_exists("ls_fcor"):
+            dm.register_and_allocate("ls_fcor", "Coriolis parameter [1/s]", (nens,), ("nens",))
+        dm.get("ls_fcor").copy_(torch.from_numpy(np.ascontiguousarray(f)))
+    for target, inc in zip(LS_TARGETS, LS_INCREMENTS):
+        if target in host and not dm.entry_exists(inc):
+            dm.register_and_allocate(inc, "nudging increment of the level mean", (nz, nens), ("z", "nens"))
+    courant = 0.0
+    if "ls_wsub" in host and nz > 1:
+        zmid = dm.get("vertical_midpoint_height", readonly=True).cpu().numpy()
+        courant = float((np.abs(host["ls_wsub"]).max(axis=0) / (zmid[1:] - zmid[:-1]).min(axis=0)).max())
+    coupler.set_option("ls_courant_rate", courant)
+    coupler.set_option("ls_nudge_rate_max", max([float(host[r].max()) for r in set(LS_RATES) if r in host], default=0.0))
+
+
+def ls_forcing(coupler, dt=None):
+    """Once per CRM step, after the sponge layer and before surface_fluxes: one call of pam_amd_ls_nudging where a target is registered,
+    then one of pam_amd_ls_forcing, in place on uvel, vvel, temp and every registered tracer (the vapour is "water_vapor"; a tracer
+    registered as positive is handed on non-negative).  density_dry and wvel are never written.  Refuses, before anything is launched,
+    dt "ls_courant_rate" > 1 (the subsidence would overshoot) and dt "ls_nudge_rate_max" > 1.  Options "grav", "cp_d"; dt: default the
+    option "crm_dt"."""
+    from .coupler import endrun
+    if not coupler.option_exists("ls_courant_rate"):
+        endrun("ERROR: ls_forcing: call ls_forcing_init first")
+    dt = float(coupler.get_option("crm_dt") if dt is None else dt)
+    if not dt * float(coupler.get_option("ls_courant_rate")) <= 1.0:
+        endrun("ERROR: ls_forcing: max |ls_wsub| dt exceeds the thinnest layer (dt x ls_courant_rate > 1)")
+    if not dt * float(coupler.get_option("ls_nudge_rate_max")) <= 1.0:
+        endrun("ERROR: ls_forcing: dt x nudging rate exceeds 1 (dt x ls_nudge_rate_max > 1)")
+    lib = capi.load()
+    dm = coupler.get_data_manager_device_readwrite()
+    P = lambda name: dm.get(name, readonly=True).data_ptr() if dm.entry_exists(name) else None
+    nens, nx, ny, nz = coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz()
+    names = coupler.get_tracer_names()
+    tracers = [dm.get(n) for n in names]
+    positive = [1 if coupler.get_tracer_info(n)[2] else 0 for n in names]
+    nudged = [dm.entry_exists(t) for t in LS_TARGETS]
+    with torch.cuda.device(coupler.device):
+        stream = torch.cuda.current_stream(coupler.device).cuda_stream
+        inc = None
+        if any(nudged):
+            table = lambda entries: (C.c_void_p * 4)(*[P(n) if on else None for n, on in zip(entries, nudged)])
+            inc = (C.c_void_p * 4)(*[dm.get(n).data_ptr() if on else None for n, on in zip(LS_INCREMENTS, nudged)])
+            check(lib.pam_amd_ls_nudging(nens, nx, ny, nz, _msa_table([dm.get(n, readonly=True) for n in LS_NUDGE_FIELDS]), table(LS_TARGETS),
+                                         table(LS_RATES), dt, inc, stream))
+        check(lib.pam_amd_ls_forcing(nens, nx, ny, nz, dm.get("uvel").data_ptr(), dm.get("vvel").data_ptr(), dm.get("temp").data_ptr(),
+                                     len(tracers), _ptr_table(tracers) if tracers else None,
+                                     (C.c_ubyte * len(tracers))(*positive) if tracers else None, P("density_dry"), P("water_vapor"),
+                                     P("vertical_midpoint_height"), P("ls_wsub"), P("ls_temp_tend"), P("ls_qv_tend"), inc, P("ls_fcor"),
+                                     P("ls_ug"), P("ls_vg"), dt, float(coupler.get_option("grav")), float(coupler.get_option("cp_d")), stream))

@@ -23,6 +23,9 @@ with the surface fluxes of heat and vapour) on Kessler's field set at the C2 gri
 hyperdiffusion and msa_apply of the same run;
 --only grayrad: the native grey two-stream longwave scheme (pam_amd_radiation_gray) at the C2 grid and at C4's 32x1x60 grid with 8192
 members on Kessler's and on P3's field set, beside column_diagnostics and pam_amd_sgs_smag_coefficients of the same run;
+--only lsforcing: the large-scale forcing (pam_amd_ls_forcing with everything on, with the subsidence alone and without it, and
+pam_amd_ls_nudging) at the C2 grid and at C4's 32x1x60 grid with 8192 members on Kessler's field set, beside hyperdiffusion, msa_apply,
+msa_diagnose and one C2 dycore step of the same run;
 --only surface: the bulk surface fluxes over a slab ocean (pam_amd_surface_fluxes) at the C2 grid and at C4's 32x1x60 grid with 8192
 members, with the slab and all four radiation inputs and without either, beside compute_surface_friction of the same run;
 --only grayrad_sw: the scheme's shortwave (pam_amd_radiation_gray_sw) on the same grids and field sets, with every member under the sun
@@ -1629,8 +1632,128 @@ def surface_timing(dev, warmup=3, n=11):
     return out
 
 
+def lsforcing_timing(dev, warmup=3, n=11):
+    """The large-scale forcing (pam_amd_ls_forcing, pam_amd_ls_nudging) at the C2 grid and at C4's 32x1x60 grid with 8192 members on
+    Kessler's field set (uvel, vvel, temp and three positive tracers: six fields in place): the method is hyperdiffusion_timing's, 3
+    warm-up calls and the median of 11 event-timed calls each.  Rows: the forcing with everything on (subsidence, both tendencies, the
+    four nudging increments, Coriolis), the forcing with the subsidence alone, and the nudging launch (four targets).  Algorithmic
+    bytes: 16 B per cell and written field plus 8 B per cell for each of rho_d and rho_v (rho_v is a written field already: 8 B for
+    rho_d alone on top of the six fields; the nudging reads five fields, 8 B each); the profiles are (nz,nens) and are not counted.
+    hyperdiffusion, msa_apply (with the winds) and msa_diagnose of the same run stand beside them as the yardsticks, and one C2 dycore
+    step for the share of a CRM step."""
+    import ctypes as C
+    from pam_amd import PamCoupler, capi, modules
+    from pam_amd import idealized as idz
+    lib = capi.load()
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    def row(t, nbytes):
+        return {"ms": t[0], "min_ms": t[1], "max_ms": t[2], "bytes": nbytes, "GBps": nbytes / t[0] / 1e6,
+                "hbm_frac": nbytes / t[0] / 1e6 / bench.HBM_PEAK_GBS}
+
+    def grid(nens, nx, ny, nz, label, out, yardsticks):
+        cells = nens * nx * ny * nz
+        c = PamCoupler(dev)
+        for name, v in (("crm_dt", 2.0), ("grav", 9.80616), ("cp_d", 1004.64)):
+            c.set_option(name, v)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        zint = idz.l60_interfaces()
+        c.set_grid(nx * 1000.0, ny * 1000.0, zint)
+        for t in ("water_vapor", "cloud_liquid", "precip_liquid"):
+            c.add_tracer(t, "", True, True)
+        c.set_option("micro", "kessler")
+        dm = c.get_data_manager_device_readwrite()
+        gen = torch.Generator(device=dev).manual_seed(0)
+        k = torch.arange(nz, dtype=torch.float64, device=dev)[:, None, None, None]
+        for name, scale in (("temp", 299.0 - 1.2 * k), ("density_dry", 1.15 * torch.exp(-k / 25.0)), ("water_vapor", 1.6e-2 * torch.exp(-k / 10.0)),
+                            ("cloud_liquid", 1.0e-4 + 0 * k), ("precip_liquid", 1.0e-5 + 0 * k)):
+            t = dm.get(name)
+            t.copy_((torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * 0.1 + 0.95) * scale)
+        for name in ("uvel", "vvel", "wvel"):
+            t = dm.get(name)
+            t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * 16.0 - 8.0)
+        import numpy as np
+        zmid = 0.5 * (np.asarray(zint)[1:] + np.asarray(zint)[:-1])
+        kk = np.arange(nz)
+        wsub = -0.01 * np.sin(np.pi * (kk + 0.5) / nz)[:, None] * np.where(np.arange(nens) % 2 == 0, 1.0, -1.0)[None, :]      # both signs in every wavefront
+        rate = np.full(nz, 1.0 / 3600.0)
+        modules.ls_forcing_init(c, wsub=wsub, temp_tend=np.full(nz, -2.0e-5), qv_tend=np.full(nz, -1.0e-9), ug=np.full(nz, 7.0), vg=np.full(nz, -2.0),
+                                fcor=1.0e-4, nudge_temp=299.0 - 1.2 * kk, nudge_qv=1.4e-2 * np.exp(-kk / 10.0), nudge_u=np.zeros(nz),
+                                nudge_v=np.zeros(nz), nudge_rate_temp=rate, nudge_rate_qv=rate, nudge_rate_uv=rate)
+        assert float(c.get_option("ls_courant_rate")) * 2.0 < 1.0 and zmid.shape == (nz,)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        P = lambda name: dm.get(name).data_ptr()
+        tracers = [dm.get(t) for t in c.get_tracer_names()]
+        TR, POS = modules._ptr_table(tracers), (C.c_ubyte * 3)(1, 1, 1)
+        INC = (C.c_void_p * 4)(*[P(x) for x in modules.LS_INCREMENTS])
+        forcing = lambda wsub, tt, qt, inc, fcor, ug, vg: capi.check(lib.pam_amd_ls_forcing(
+            nens, nx, ny, nz, P("uvel"), P("vvel"), P("temp"), 3, TR, POS, P("density_dry"), P("water_vapor"), P("vertical_midpoint_height"), wsub, tt, qt,
+            inc, fcor, ug, vg, 2.0, 9.80616, 1004.64, stream))
+        nudging = lambda: capi.check(lib.pam_amd_ls_nudging(
+            nens, nx, ny, nz, modules._msa_table([dm.get(x) for x in modules.LS_NUDGE_FIELDS]), (C.c_void_p * 4)(*[P(x) for x in modules.LS_TARGETS]),
+            (C.c_void_p * 4)(*[P(x) for x in modules.LS_RATES]), 2.0, INC, stream))
+        out["ls_nudging" + label] = row(timed(nudging), 5 * cells * 8.0)
+        out["ls_forcing_everything" + label] = row(timed(lambda: forcing(P("ls_wsub"), P("ls_temp_tend"), P("ls_qv_tend"), INC, P("ls_fcor"), P("ls_ug"),
+                                                                        P("ls_vg"))), 6 * cells * 16.0 + cells * 8.0)
+        out["ls_forcing_subsidence_alone" + label] = row(timed(lambda: forcing(P("ls_wsub"), None, None, None, None, None, None)),
+                                                         6 * cells * 16.0 + cells * 8.0)
+        out["ls_forcing_without_subsidence" + label] = row(timed(lambda: forcing(None, P("ls_temp_tend"), P("ls_qv_tend"), INC, P("ls_fcor"), P("ls_ug"),
+                                                                                P("ls_vg"))), 4 * cells * 16.0 + cells * 8.0)
+        out["ls_per_crm_step_ms" + label] = out["ls_nudging" + label]["ms"] + out["ls_forcing_everything" + label]["ms"]
+        assert all(bool(torch.isfinite(dm.get(t, readonly=True)).all()) for t in ("uvel", "vvel", "temp", "water_vapor", "cloud_liquid", "precip_liquid"))
+        if yardsticks:
+            modules.hyperdiffusion_init(c, 60.0)
+            out["hyperdiffusion_automatic" + label] = row(timed(lambda: modules.hyperdiffusion(c)), 7 * cells * 16.0 + 3 * cells * 8.0)
+            c.set_option("gcm_physics_dt", 900.0)
+            c.set_option("crm_accel_factor", 2.0)
+            c.set_option("crm_accel_uv", True)
+            modules.msa_init(c)
+            mfields, msave, mtend, cease = modules._msa_arrays(c)
+            MF, MS, MT = modules._msa_table(mfields), modules._msa_table(msave), modules._msa_table(mtend)
+            dm.get("accel_tend_t").fill_(1.0e-6)
+            for q in ("q", "u", "v"):
+                dm.get("accel_tend_" + q).zero_()
+            nf = sum(1 for f in mfields if f is not None)
+            out["msa_diagnose" + label] = row(timed(lambda: capi.check(lib.pam_amd_msa_diagnose(nens, nx, ny, nz, MF, MS, stream))), nf * cells * 8.0)
+            out["msa_apply_accel_uv" + label] = row(timed(lambda: capi.check(lib.pam_amd_msa_apply(nens, nx, ny, nz, MF, MT, 2.0, 1, cease.data_ptr(), stream))),
+                                                    4 * cells * 16.0)
+            out["ls_forcing_everything_vs_hyperdiffusion_frac" + label] = (out["ls_forcing_everything" + label]["hbm_frac"]
+                                                                           / out["hyperdiffusion_automatic" + label]["hbm_frac"])
+            out["ls_nudging_vs_msa_diagnose_frac" + label] = out["ls_nudging" + label]["hbm_frac"] / out["msa_diagnose" + label]["hbm_frac"]
+            del mfields, msave, mtend, cease
+        del c, dm, tracers
+        lib.pam_amd_modules_finalize()
+        torch.cuda.empty_cache()
+
+    out = {"lsforcing_grid": "1024 x 32x32x60 (C2) and 8192 x 32x1x60 (C4)",
+           "lsforcing_method": "%d warm-up calls, median of %d event-timed calls" % (warmup, n), "hbm_peak_GBps": bench.HBM_PEAK_GBS}
+    grid(1024, 32, 32, 60, "", out, True)
+    grid(8192, 32, 1, 60, "_c4", out, True)
+    job = bench.Job("c2", bench.parse_args([]), dev, 0, 1)
+    _, elapsed, _ = job.timed(3, 2)
+    out["c2_dycore_step_ms"] = elapsed / 3 * 1e3
+    out["ls_per_crm_step_share_of_c2_dycore_step"] = out["ls_per_crm_step_ms"] / out["c2_dycore_step_ms"]
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "lsforcing"]:
+        print(json.dumps(lsforcing_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "surface"]:
         print(json.dumps(surface_timing(dev)))
         sys.exit(0)
