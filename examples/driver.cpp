@@ -65,6 +65,9 @@
 #include "modules/flux_profiles.h"
 #include "vertical_interp.h"
 #include "physics/micro/kessler_amd/Microphysics.h"
+#define PAM_MICRO_CLASS MicrophysicsIce   // the driver holds both Microphysics classes and picks at run time (--micro-ice)
+#include "physics/micro/ice_amd/Microphysics.h"
+#undef PAM_MICRO_CLASS
 #include "physics/sgs/none/SGS.h"
 #define PAM_SGS_CLASS SGSSmagorinsky      // the driver holds both SGS classes and picks at run time (--sgs-smag)
 #include "physics/sgs/smag_amd/SGS.h"
@@ -316,7 +319,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
-//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
+//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--micro-ice] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
 //          [--flux-profiles PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
@@ -448,6 +451,13 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              whose zenith angle has the cosine COSZEN for every member (rad_gray_sw_coszen) over a surface of albedo
 //                              ALBEDO (rad_gray_sw_albedo; 0.07 unless given).  The "radiation gray:" line then also carries the mean
 //                              rad_sw_down_sfc and rad_sw_up_top.  Refused without --radiation-gray
+//   --micro-ice                the native one-moment microphysics with ice (physics/micro/ice_amd/Microphysics.h, option micro = "ice1m") in the
+//                              microphysics slot of the CRM loop, where Kessler runs without the flag: its init registers five water
+//                              tracers, "precl" and "preci", and its timeStep runs where Kessler's does.  Every module that reads the
+//                              condensate takes cloud_liquid and cloud_ice.  One "micro ice:" line per output step with the mean ice water
+//                              path [kg/m2], the mean precl and preci [m/s] and the water budget [kg/m2 summed over the columns]: the
+//                              total water now, the total at the start and the accumulated surface precipitation.  Composes with every
+//                              flag that composes with Kessler
 //   --vt RATE PATH [--vt-u] [--vt-limit L]   CRM variance transport (modules/variance_transport.h): modules::vt_init at the start of every GCM
 //                              step; there is no GCM here, so vt_tend_x = RATE vt_var_start_x (a relative growth rate per second) for
 //                              that GCM step; modules::vt_apply_forcing LAST in every CRM step, after the clock has advanced, with dt =
@@ -475,7 +485,7 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              prof_flux_v and prof_tke, printed with %.17g; nothing else of the run changes.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  bool vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false, shortwave = false, surface = false, ls_forcing = false, coriolis = false;
+  bool micro_ice = false, vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false, shortwave = false, surface = false, ls_forcing = false, coriolis = false;
   int radiation_gray_every = 1;
   double sw_coszen = 1, sw_albedo = 0.07;
   double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0, sfc_shf = 0, sfc_lhf = 0, surface_sst = 300, surface_depth = 0, ls_fcor = 0;
@@ -583,11 +593,13 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     coupler.set_grid(xlen, ylen, zint);                                      // driver.cpp:180
     Dycore dycore;
     Microphysics micro;
+    MicrophysicsIce micro_ice;
     SGS sgs;
     SGSSmagorinsky sgs_smag;
     Radiation rad;
     RadiationGray rad_gray;
-    micro.init(coupler);                                                     // driver.cpp:189
+    if (mods.micro_ice) micro_ice.init(coupler);                             // --micro-ice: the native scheme with ice in the microphysics slot
+    else micro.init(coupler);                                                // driver.cpp:189
     if (mods.sgs_smag) {                                                     // --sgs-smag: the native closure in the SGS slot
       coupler.set_option<real>("sgs_smag_cs", mods.sgs_cs);
       coupler.set_option<real>("sgs_smag_prandtl", mods.sgs_prandtl);
@@ -626,7 +638,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       if (!rin || rin.peek() != std::ifstream::traits_type::eof()) endrun("the --radiation file is not (nz,rad_ny,rad_nx,nens) fp64");
       if (hipMemcpy(tend.data(), h.data(), h.size() * sizeof(real), hipMemcpyHostToDevice) != hipSuccess) endrun("memcpy");
     }
-    std::printf("Dycore: %s\nMicro : %s\nSGS   : %s\n\n", dycore.dycore_name(), micro.micro_name().c_str(),
+    std::printf("Dycore: %s\nMicro : %s\nSGS   : %s\n\n", dycore.dycore_name(), (mods.micro_ice ? micro_ice.micro_name() : micro.micro_name()).c_str(),
                 mods.sgs_smag ? sgs_smag.sgs_name().c_str() : "none (SHOC is out of scope)");   // driver.cpp:203-205
     std::printf("crm_nx:   %d\ncrm_ny:   %d\ncrm_nz:   %d\nxlen (m): %g\nylen (m): %g\n", crm_nx, crm_ny, crm_nz, xlen, ylen);
     if (apply_gcm_forcing) std::printf("apply_gcm_forcing: not run (modules::gcm_forcing works on P3's tracer set; P3 is out of scope)\n");
@@ -717,6 +729,17 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       if (!diag_out) endrun("cannot open the --diag file");
     }
     double etime_gcm = 0, maxw_all = 0, cons_max_rel = 0;
+    // --micro-ice: the water budget.  Total water [kg/m2 summed over the columns] at the start, and the surface precipitation since
+    long double ice_water_start = 0, ice_precip_sum = 0;
+    if (mods.micro_ice) ice_water_start = micro_ice.compute_total_mass(coupler);
+    auto mean2d = [&](char const *name) {                                    // the mean of a (ny,nx,nens) entry
+      const size_t n2 = (size_t)crm_ny * crm_nx * nens;
+      std::vector<real> h(n2);
+      if (hipMemcpy(h.data(), dm.get<real const, 3>(name).data(), n2 * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess) endrun("memcpy");
+      long double sum = 0;
+      for (real v : h) sum += v;
+      return (double)(sum / n2);
+    };
     int num_out = 0, crm_steps = 0, accel_steps = 0, accel_ceased_gcm_steps = 0;
     long substeps = 0, cons_violations = 0;
     bool stop = false;
@@ -754,6 +777,11 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (mods.hyperdiff) coupler.run_module("hyperdiffusion", [](pam::PamCoupler &c) { modules::hyperdiffusion(c); });
         if (mods.sgs_smag) coupler.run_module("sgs", [&](pam::PamCoupler &c) { sgs_smag.timeStep(c); });
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
+        if (!dbg.no_micro && mods.micro_ice) {
+          coupler.run_module("micro", [&](pam::PamCoupler &c) { micro_ice.timeStep(c); });
+          const double n2 = (double)crm_ny * crm_nx * nens;                  // 1000 dt (precl + preci) of every column, added up
+          ice_precip_sum += (long double)1000.0 * dt_crm_phys * ((long double)mean2d("precl") + (long double)mean2d("preci")) * n2;
+        } else
         if (!dbg.no_micro) coupler.run_module("micro", [&](pam::PamCoupler &c) { micro.timeStep(c); });         // driver.cpp:253
         if (mods.sat_adjust) coupler.run_module("saturation_adjustment", modules::saturation_adjustment);
         bool cease = false;
@@ -810,6 +838,19 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
             items.push_back({"temp", 0, dm.get<real const, 4>("temp").data(), level, items.size()});
             auto s3 = pam::diagnostics::scan(items, 0);
             std::printf("ls forcing: etime %g , uvel %.9g , vvel %.9g , temp0 %.9g\n", etime_gcm, s3[0].mean(), s3[1].mean(), s3[2].mean());
+          }
+          if (mods.micro_ice) {                                              // the ice water path, the two rates, and the water budget
+            fetch("cloud_ice");
+            long double iwp = 0;
+            const size_t level = (size_t)crm_ny * crm_nx * nens;
+            for (int k = 0; k < crm_nz; k++) {
+              long double row = 0;
+              for (size_t c = 0; c < level; c++) row += buf[(size_t)k * level + c];
+              iwp += row * (long double)(zint[k + 1] - zint[k]);
+            }
+            std::printf("micro ice: etime %g , iwp %.9g , precl %.9g , preci %.9g , water %.17g , water_start %.17g , precipitated %.17g\n", etime_gcm,
+                        (double)(iwp / level), mean2d("precl"), mean2d("preci"), (double)micro_ice.compute_total_mass(coupler),
+                        (double)ice_water_start, (double)ice_precip_sum);
           }
           char t[64];
           std::snprintf(t, sizeof(t), "%s%.6g", maxw_series.empty() ? "" : ",", maxw);
@@ -1097,6 +1138,7 @@ int main(int argc, char **argv) {
         if (!n.empty() && n.find_first_not_of("0123456789.eE+") == std::string::npos) mods.sw_albedo = std::atof(argv[++b]);
       }
       else if (o == "--sgs-moist") mods.sgs_moist = true;
+      else if (o == "--micro-ice") mods.micro_ice = true;
       else if (o == "--sfc-fluxes" && b + 2 < argc - 1) { mods.sfc_fluxes = true; mods.sfc_shf = std::atof(argv[++b]); mods.sfc_lhf = std::atof(argv[++b]); }
       else if (o == "--surface" && b + 1 < argc - 1) {
         mods.surface = true;
@@ -1116,7 +1158,7 @@ int main(int argc, char **argv) {
       else if (o == "--flux-profiles" && b + 1 < argc - 1) mods.flux_profiles = argv[++b];
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] "
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--micro-ice] "
                "[--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->");
     }
     if (mods.radiation_gray && mods.radiation) die("--radiation-gray and --radiation both fill the one radiation slot: give one of them");

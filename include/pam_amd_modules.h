@@ -930,6 +930,65 @@ int pam_amd_ls_forcing(int nens, int nx, int ny, int nz, double *uvel, double *v
                        const double *ug, const double *vg, double dt, double grav, double cp_d, void *stream);
 int pam_amd_ls_forcing_debug_wide_index(int on);
 
+/* One-moment ice microphysics (option micro = "ice1m"): a bulk scheme with five water species as mass densities, rv water_vapor,
+ * rc cloud_liquid, ri cloud_ice, rr precip_liquid, rs precip_ice (kg/m3), in the sense that Kessler is the warm scheme that needs no
+ * library.  Not part of the reference tree; the contract is this project's and is restated in numpy in
+ * tests/ice1m_ref.py, which the kernel matches bit for bit.  The coefficients are untuned starting points.
+ * Fields are (nz,ny,nx,nens), members fastest; zint is (nz+1,nens), per member; precl and preci are (ny,nx,nens), metres of water per
+ * second: precl the liquid surface rate as Kessler's is, preci the frozen one, snow plus cloud ice.  rd = rho_dry is read only.
+ * Everything is fp64, every operation is rounded on its own (no fma), divisions and sqrt are IEEE, the association is as written, and
+ * the only transcendental is exp_c of pam_amd_sgs_smag_coefficients_moist.  There is no pow: s8(x) = sqrt(sqrt(sqrt(x))), s16(x) =
+ * sqrt(s8(x)).  pos(x) = x < 0 ? 0 : x and least(a, b) = b < a ? b : a, so a NaN is never swallowed.
+ * Constants: T0 = 273.16, Th = 233.16, Lv = 2.5e6, Ls = 2.834e6, Lf = Ls - Lv; cprd = cp_d rd per cell; dz(k) = zint(k+1) - zint(k).
+ * With dt == 0 no field is read or written and precl = preci = +0.0.  Otherwise, per (column, member):
+ *  1. rho0 = rd(0) + rv(0) of entry, used for the whole call.  Speeds, from a level's own values: fac = sqrt(rho0 / (rd + rv));
+ *     v_r = (13.1 s8(rr)) fac; v_s = (1.7 s16(rs)) fac; v_i = 0.4 where ri > 0, else 0.0.
+ *  2. Sub-cycle count, from the state at entry, PER COLUMN: c = 0.0; over k upward and over r, s, i in that order, x = (v dt) / dz(k)
+ *     replaces c where x > c or x is a NaN (a NaN then stays).  nsub = 1 unless c > 0.8, else min(ceil(c / 0.8), 64).  There is no
+ *     global minimum: no read-back, no synchronisation, no all-reduce between member shards.  dts = dt / nsub.
+ *  3. nsub sub-cycles, each one upward pass in place.  The speeds are recomputed from the values the pass begins with, and each is
+ *     clipped: v > vmax ? vmax : v, vmax = ((0.8 dz(k)) nsub) / dt, so a sub-cycle never takes more than a cell holds.
+ *     F_x(k) = v_x(k) r_x(k), F_x(nz) = +0.0;  r_x(k) = r_x(k) + (dts / dz(k)) (F_x(k+1) - F_x(k)), F_x(k+1) from the still-old
+ *     level above.  precl = precl + (F_r(0) dts) / (1000 dt); preci = preci + ((F_s(0) + F_i(0)) dts) / (1000 dt); both from +0.0.
+ *  4. On the LAST sub-cycle, after a level's sedimentation, the local processes of that cell in this order (T = temp):
+ *     Melt, where T > T0: H = (cprd (T - T0)) / Lf; mi = least(ri, H): ri -= mi, rc += mi; ms = least(rs, H - mi): rs -= ms,
+ *       rr += ms; T = T - (Lf (mi + ms)) / cprd.
+ *     Freeze, where T < Th: H = (cprd (Th - T)) / Lf; fc = least(rc, H): rc -= fc, ri += fc; fr = least(rr, H - fc): rr -= fr,
+ *       rs += fr; T = T + (Lf (fc + fr)) / cprd.
+ *     Adjust, one Newton step: tc = T - 273.15; rsw = (610.94 exp_c((17.625 tc) / (243.04 + tc))) / (R_v T);
+ *       rsi = (611.21 exp_c((22.587 tc) / (273.86 + tc))) / (R_v T); w = (T - 253.16) / 20 clamped to [0, 1];
+ *       rsat = rsi + w (rsw - rsi); L = w Lv + (1 - w) Ls;
+ *       slope = (w rsw) ((17.625 * 243.04) / ((243.04 + tc) (243.04 + tc)) - 1 / T)
+ *             + ((1 - w) rsi) ((22.587 * 273.86) / ((273.86 + tc) (273.86 + tc)) - 1 / T)      (the dw/dT term is neglected);
+ *       x = (rv - rsat) / (1 + (L / cprd) slope).
+ *       x > 0: dc = w x, di = x - dc; rv -= x, rc += dc, ri += di; T = T + (Lv dc + Ls di) / cprd.
+ *       x < 0: e = least(-x, rc + ri); el = least(e, rc); ei = least(e - el, ri): liquid first, and never more ice than there is;
+ *              rc -= el, ri -= ei, rv = rv + (el + ei); T = T - (Lv el + Ls ei) / cprd.
+ *     Collect, Kessler's implicit form, with p875(q) = q / s8(q), p8125(q) = q / ((t t) t), t = s16(q), both 0 at q == 0, and
+ *       pr = p875(rr / rd), ps = p8125(rs / rd) formed once from rr and rs as collection begins:
+ *       rc' = pos(rc - (dt 1e-3) pos(rc - 1e-3 rd)) / (1 + (dt 2.2) pr); rr = rr + (rc - rc');
+ *       g = exp_c(0.025 (T - T0)); ri' = pos(ri - ((dt 1e-3) g) pos(ri - 1e-4 rd)) / (1 + (dt g) ps); rs = rs + (ri - ri');
+ *       riming, where T < T0: rc'' = rc' / (1 + (dt 2.0) ps); dr = rc' - rc''; rs = rs + dr; T = T + (Lf dr) / cprd.
+ *     Evaporate and sublimate, rsw and rsi evaluated anew at the T collection left:
+ *       where rv < rsw and rr > 0: l = least(least(rr, 0.5 (rsw - rv)), ((dt 1e-4) (1 - rv / rsw)) sqrt(rr)); rr -= l, rv += l,
+ *         T = T - (Lv l) / cprd;  then where rv < rsi and rs > 0 the same with rs, rsi, 5e-5 and Ls.
+ * Guaranteed for finite non-negative species, positive rd, T and dz, and dt <= 1000 s: no species goes negative; a column's
+ * sum_k dz (rv + rc + ri + rr + rs) falls by 1000 dt (precl + preci) and by nothing else; per cell the local part obeys
+ * cprd dT = Lv d(rc + rr) + Ls d(ri + rs), both to a rounding bound derived in tests/ice1m_ref.py.  rho_dry, zint and everything that
+ * is not an argument are never written.  Nothing is refused because of a value in a field; a NaN stays in its own column.  The same
+ * bits from run to run and for any split of the members over calls, by construction.
+ * One launch: a thread owns a (column, member), members across the lanes; a read-only pre-pass over rr, rs, ri, rd, rv gives nsub;
+ * loads are requested AHEAD = 4 levels before use; lanes of one wavefront may hold different nsub; the local processes are fused into
+ * the last pass; no workspace, no LDS, no atomics.  Flat offsets are 64 bits wide from 2^29 elements per field on;
+ * pam_amd_ice1m_debug_wide_index(1) forces that instance at any size (0: back to automatic).
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: a size below 1; ny nx beyond 2^31 - 1; a NULL
+ * pointer; dt negative or not finite; R_v or cp_d not finite and positive; an output (the five species, temp, precl, preci) that
+ * overlaps an input or another output.  Without a device a call whose arguments pass returns PAM_AMD_ENOGPU. */
+int pam_amd_ice1m_time_step(int nens, int nx, int ny, int nz, double *rho_v, double *rho_c, double *rho_i, double *rho_r,
+                            double *rho_s, const double *rho_dry, double *temp, double *precl, double *preci, const double *zint,
+                            double dt, double R_v, double cp_d, void *stream);
+int pam_amd_ice1m_debug_wide_index(int on);
+
 #ifdef __cplusplus
 }
 #endif

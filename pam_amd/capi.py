@@ -214,6 +214,8 @@ MODULE_SYMBOLS = {
     "pam_amd_ls_nudging": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 2),
     "pam_amd_ls_forcing": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 12 + [C.c_double] * 3 + [C.c_void_p]),
     "pam_amd_ls_forcing_debug_wide_index": (C.c_int, [C.c_int]),
+    "pam_amd_ice1m_time_step": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 10 + [C.c_double] * 3 + [C.c_void_p]),
+    "pam_amd_ice1m_debug_wide_index": (C.c_int, [C.c_int]),
 }
 
 

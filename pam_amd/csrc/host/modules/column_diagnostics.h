@@ -12,7 +12,7 @@
 // "crm_diag_cwp_threshold" (1e-3 kg/m2), set by the init where they are unset; "micro" names the condensate: kessler: cloud_liquid, no ice
 // (no "diag_iwp"); p3: cloud_water and ice; none (or absent): neither, and then no cloud cover.  "cldfrac" {nz,ny,nx,nens} is the cloud
 // fraction where the DataManager has it.  The liquid precipitation is "precl" (Kessler) or "precip_liq_surf_out" (P3), the ice
-// precipitation "precip_ice_surf_out", each where the DataManager has it.
+// precipitation "preci" (ice1m: cloud_liquid and cloud_ice) or "precip_ice_surf_out", each where the DataManager has it.
 #pragma once
 #include <cmath>
 #include <string>
@@ -37,10 +37,12 @@ inline ColumnDiagnostics_ column_diagnostics_sizes_(pam::PamCoupler &coupler) {
   std::string micro_scheme = coupler.option_exists("micro") ? coupler.get_option<std::string>("micro") : std::string("none");
   if (micro_scheme == "kessler") s.cloud = "cloud_liquid";
   else if (micro_scheme == "p3") { s.cloud = "cloud_water"; s.ice = "ice"; }
+  else if (micro_scheme == "ice1m") { s.cloud = "cloud_liquid"; s.ice = "cloud_ice"; }
   else if (micro_scheme != "none") endrun("ERROR: column_diagnostics only knows the kessler, p3 and none microphysics");
   if (dm.entry_exists("precl")) s.precip_liq = "precl";
   else if (dm.entry_exists("precip_liq_surf_out")) s.precip_liq = "precip_liq_surf_out";
-  if (dm.entry_exists("precip_ice_surf_out")) s.precip_ice = "precip_ice_surf_out";
+  if (dm.entry_exists("preci")) s.precip_ice = "preci";                                           // micro = ice1m
+  else if (dm.entry_exists("precip_ice_surf_out")) s.precip_ice = "precip_ice_surf_out";
   std::vector<int> columns = {s.ny, s.nx, s.nens};
   for (auto &n : {s.precip_liq, s.precip_ice})
     if (!n.empty() && dm.get_shape(n) != columns) endrun("ERROR: column_diagnostics: " + n + " is not {ny,nx,nens}");

@@ -28,6 +28,7 @@ inline CrmFeedback_ crm_feedback_species_(pam::PamCoupler &coupler) {
   std::string micro_scheme = coupler.option_exists("micro") ? coupler.get_option<std::string>("micro") : std::string("none");
   if (micro_scheme == "kessler") s.cloud = "cloud_liquid";
   else if (micro_scheme == "p3") { s.cloud = "cloud_water"; s.ice = "ice"; }
+  else if (micro_scheme == "ice1m") { s.cloud = "cloud_liquid"; s.ice = "cloud_ice"; }
   else if (micro_scheme != "none") endrun("ERROR: crm_feedback only knows the kessler, p3 and none microphysics");
   for (int q = 0; q < 6; q++) s.has[q] = true;
   s.has[2] = !s.cloud.empty();

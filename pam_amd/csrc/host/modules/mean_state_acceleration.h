@@ -64,6 +64,7 @@ inline MsaArrays_ msa_arrays_(pam::PamCoupler &coupler) {
   std::string cloud, ice;
   if (micro_scheme == "kessler") cloud = "cloud_liquid";
   else if (micro_scheme == "p3") { cloud = "cloud_water"; ice = "ice"; }
+  else if (micro_scheme == "ice1m") { cloud = "cloud_liquid"; ice = "cloud_ice"; }
   else if (micro_scheme != "none") endrun("ERROR: mean-state acceleration only knows the kessler, p3 and none microphysics");
   A.fields[0] = dm.get<real, 4>("temp").data();
   A.fields[1] = dm.get<real, 4>("water_vapor").data();

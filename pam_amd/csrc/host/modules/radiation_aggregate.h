@@ -37,6 +37,7 @@ inline RadAggregate_ rad_aggregate_sizes_(pam::PamCoupler &coupler) {
   std::string micro_scheme = coupler.option_exists("micro") ? coupler.get_option<std::string>("micro") : std::string("none");
   if (micro_scheme == "kessler") s.cloud = "cloud_liquid";
   else if (micro_scheme == "p3") { s.cloud = "cloud_water"; s.ice = "ice"; }
+  else if (micro_scheme == "ice1m") { s.cloud = "cloud_liquid"; s.ice = "cloud_ice"; }
   else if (micro_scheme != "none") endrun("ERROR: rad_aggregate only knows the kessler, p3 and none microphysics");
   return s;
 }

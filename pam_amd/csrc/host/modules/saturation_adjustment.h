@@ -21,6 +21,7 @@ inline void saturation_adjustment(pam::PamCoupler &coupler) {
   std::string micro_scheme = coupler.get_option<std::string>("micro");                         // :126-129
   if (micro_scheme == "kessler") rho_c = dm.get<real, 4>("cloud_liquid").data();
   else if (micro_scheme == "p3") rho_c = dm.get<real, 4>("cloud_water").data();
+  else if (micro_scheme == "ice1m") rho_c = dm.get<real, 4>("cloud_liquid").data();      // the liquid of the native scheme with ice (cloud_ice is not adjusted here)
   else endrun("ERROR: saturation_adjustment.h only currently supports kessler and p3 microphysics");
   std::vector<double const *> massy;                                                              // :130-137
   for (auto &name : coupler.get_tracer_names()) {

@@ -5,7 +5,7 @@
 // call of pam_amd_radiation_gray: it fills "rad_heating" (K/s), "rad_olr", "rad_lw_down_sfc" and "rad_lw_up_sfc" (W/m2) and applies the
 // heating to temp; the steps between apply the stored "rad_heating" through pam_amd_radiation_forced with rad_nx = nx, rad_ny = ny
 // and cp_d = 1.0, which is temp += rad_heating / 1.0 * crm_dt: exact, and no kernel of its own.  The cloud species come from option
-// "micro": "kessler" gives "cloud_liquid" as liquid and no ice, "p3" gives "cloud_water" and "ice", "none" (or no option) neither.
+// "micro": "kessler" gives "cloud_liquid" as liquid and no ice, "p3" gives "cloud_water" and "ice", "ice1m" gives "cloud_liquid" and "cloud_ice", "none" (or no option) neither.
 // The surface radiates at "sfc_temp" (ny,nx,nens) where that entry exists, else at the lowest level's temp.
 //   options read:  crm_dt, cp_d, micro, sigma (5.670374419e-8 where absent), rad_gray_k_d/k_v/k_l/k_i, rad_gray_lw_down_top, rad_gray_every
 //   options set by init:  "radiation" = "gray"; rad_gray_k_d = 1e-4, rad_gray_k_v = 0.1, rad_gray_k_l = 85 (the GCSS DYCOMS-II value),
@@ -101,6 +101,7 @@ class PAM_RAD_CLASS {
     std::vector<double const *> liquid, ice;
     if (micro == "kessler") liquid.push_back(dm.get<real const, 4>("cloud_liquid").data());
     else if (micro == "p3") { liquid.push_back(dm.get<real const, 4>("cloud_water").data()); ice.push_back(dm.get<real const, 4>("ice").data()); }
+    else if (micro == "ice1m") { liquid.push_back(dm.get<real const, 4>("cloud_liquid").data()); ice.push_back(dm.get<real const, 4>("cloud_ice").data()); }
     else if (micro != "none") endrun("ERROR: radiation: the gray scheme knows the species of micro = kessler, p3 and none, not of " + micro);
     real sigma = coupler.option_exists("sigma") ? coupler.get_option<real>("sigma") : 5.670374419e-8;
     real const *sfc_temp = dm.entry_exists("sfc_temp") ? dm.get<real const, 3>("sfc_temp").data() : nullptr;

@@ -7,7 +7,7 @@
 // condition of the horizontal winds.  density_dry is never written.
 // With option sgs_smag_moist the coefficients come from pam_amd_sgs_smag_coefficients_moist: the loading of every condensate, and the
 // saturated frequency inside cloud; the species follow option "micro" (kessler: cloud_liquid / precip_liquid; p3: cloud_water, ice /
-// rain; none: no species).  With option sgs_smag_surface_fluxes the solve is pam_amd_sgs_smag_diffuse_fluxes, which takes "sfc_shf" and
+// rain; ice1m: cloud_liquid, cloud_ice / precip_liquid, precip_ice; none: no species).  With option sgs_smag_surface_fluxes the solve is pam_amd_sgs_smag_diffuse_fluxes, which takes "sfc_shf" and
 // "sfc_lhf" (W/m2, positive upward; whoever drives the run fills them) into row 0 of temp and of the vapour.  With both off the calls
 // are the two above.
 //   options read:  crm_dt, grav, cp_d (the microphysics sets the constants), sgs_smag_cs, sgs_smag_prandtl, sgs_smag_moist,
@@ -73,6 +73,7 @@ class PAM_SGS_CLASS {
       std::vector<std::string> cloud_names, precip_names;
       if (micro == "kessler") { cloud_names = {"cloud_liquid"}; precip_names = {"precip_liquid"}; }
       else if (micro == "p3") { cloud_names = {"cloud_water", "ice"}; precip_names = {"rain"}; }
+      else if (micro == "ice1m") { cloud_names = {"cloud_liquid", "cloud_ice"}; precip_names = {"precip_liquid", "precip_ice"}; }
       else if (micro != "none") endrun("ERROR: sgs: the moist branch knows the species of micro = kessler, p3 and none");
       std::vector<const double *> cloud, precip;
       for (auto &n : cloud_names) cloud.push_back(dm.get<real const, 4>(n).data());

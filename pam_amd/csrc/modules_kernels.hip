@@ -4408,3 +4408,64 @@ extern "C" int pam_amd_ls_forcing(int nens, int nx, int ny, int nz, double *uvel
   else hipLaunchKernelGGL((ls_forcing_kernel<long long, false>), grid, block, 0, s, nens, level, nz, A);
   return stats_launch_check(who);
 }
+
+// ------------------------------------------------------------------------------------------------
+// One-moment ice microphysics (option micro = "ice1m"): vapour, cloud liquid, cloud ice, rain and snow; sedimentation in per-column
+// sub-cycles, then melting, freezing, a mixed-phase saturation adjustment, collection, riming, evaporation and sublimation per cell.
+// Not in the reference tree; the contract is in include/pam_amd_modules.h and DESIGN.md section 8, its arithmetic in ice1m_device.h.
+// ONE launch: a thread owns a (column, member), members and then x across the lanes; a read-only pre-pass gives the thread its own
+// sub-cycle count, every sub-cycle is one upward pass in place, and the local processes ride on the last.  Lanes of a wavefront may
+// hold different counts: the loop over the earlier passes is per lane, and the last pass is taken by all of them together.  No
+// workspace, no LDS, no atomics, no read-back.  IDX: unsigned while a field is below 2^29 doubles.
+#include "ice1m_device.h"
+
+namespace {
+namespace im = pama::ice1m;
+constexpr int ICE1M_THREADS = 64;
+constexpr long long ICE1M_NARROW_CELLS = 1ll << 29;    // fields from this size on take the long long instance
+
+// grid (ceil(ny nx nens / 64)), block 64: thread t = (j nx + i) nens + e
+template <class IDX>
+__global__ void __launch_bounds__(ICE1M_THREADS) ice1m_kernel(int nens, long long level, int nz, im::Args A) {
+  const long long t = (long long)blockIdx.x * ICE1M_THREADS + (long long)threadIdx.x;
+  if (t >= level) return;
+  const int e = (int)(t % nens);
+  im::column<IDX>(A, (IDX)t, (IDX)level, (IDX)nens, e, nz);
+}
+
+bool g_ice1m_force_wide = false;   // pam_amd_ice1m_debug_wide_index: tests run the long long instance at small sizes
+}  // namespace
+
+extern "C" int pam_amd_ice1m_debug_wide_index(int on) {
+  g_ice1m_force_wide = on != 0;
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_ice1m_time_step(int nens, int nx, int ny, int nz, double *rho_v, double *rho_c, double *rho_i, double *rho_r,
+                                       double *rho_s, const double *rho_dry, double *temp, double *precl, double *preci,
+                                       const double *zint, double dt, double R_v, double cp_d, void *stream) {
+  const char *who = "ice1m";
+  if (nens < 1 || nx < 1 || ny < 1 || nz < 1) return module_error(who, "nens, nx, ny and nz must be >= 1");
+  if ((long long)nx * ny > 0x7fffffffLL) return module_error(who, "ny x nx exceeds 2^31 - 1 columns");
+  const long long level = (long long)nx * ny * nens, cells = level * nz, rows = ((long long)nz + 1) * nens;
+  if ((level + ICE1M_THREADS - 1) / ICE1M_THREADS > 0x7fffffffLL) return module_error(who, "ny x nx x nens exceeds the grid");
+  if (!rho_v || !rho_c || !rho_i || !rho_r || !rho_s || !rho_dry || !temp || !precl || !preci || !zint) return module_error(who, "null pointer");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return module_error(who, "dt must be finite and not negative");
+  if (!sgs_positive(R_v) || !sgs_positive(cp_d)) return module_error(who, "R_v and cp_d must be finite and positive");
+  std::vector<Span> spans;
+  spans.push_back({rho_dry, cells, false});
+  spans.push_back({zint, rows, false});
+  for (double *p : {rho_v, rho_c, rho_i, rho_r, rho_s, temp}) spans.push_back({p, cells, true});
+  for (double *p : {precl, preci}) spans.push_back({p, level, true});
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if (int rc = require_device(who)) return rc;
+
+  im::Args A;
+  A.rv = rho_v; A.rc = rho_c; A.ri = rho_i; A.rr = rho_r; A.rs = rho_s; A.temp = temp; A.precl = precl; A.preci = preci;
+  A.rd = rho_dry; A.zint = zint; A.dt = dt; A.R_v = R_v; A.cp_d = cp_d;
+  const dim3 grid((unsigned)((level + ICE1M_THREADS - 1) / ICE1M_THREADS)), block(ICE1M_THREADS);
+  hipStream_t s = (hipStream_t)stream;
+  if (!g_ice1m_force_wide && cells < ICE1M_NARROW_CELLS) hipLaunchKernelGGL((ice1m_kernel<unsigned>), grid, block, 0, s, nens, level, nz, A);
+  else hipLaunchKernelGGL((ice1m_kernel<long long>), grid, block, 0, s, nens, level, nz, A);
+  return stats_launch_check(who);
+}

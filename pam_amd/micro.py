@@ -90,3 +90,63 @@ class Microphysics:
     @staticmethod
     def rainsplit_for(crm_dt, dt_max):
         return max(1, int(math.ceil(crm_dt / dt_max)))
+
+
+class MicrophysicsIce:
+    """A bulk one-moment scheme with ice, five tracers: option micro = "ice1m".  Not part of the reference tree; the contract is this
+    project's (include/pam_amd_modules.h at pam_amd_ice1m_time_step).  The same members as Microphysics.  Its
+    coefficients are untuned starting points."""
+    TRACERS = (("water_vapor", "Water Vapor"), ("cloud_liquid", "Cloud liquid"), ("cloud_ice", "Cloud ice"),
+               ("precip_liquid", "precip_liquid"), ("precip_ice", "precip_ice"))
+    DIAGNOSTICS = (("precl", "liquid surface precipitation rate"), ("preci", "frozen surface precipitation rate"))
+    # Kessler's values, written to the coupler options as Kessler writes them
+    R_d, cp_d, cp_v, R_v, p0, grav = Microphysics.R_d, Microphysics.cp_d, Microphysics.cp_v, Microphysics.R_v, Microphysics.p0, Microphysics.grav
+
+    @staticmethod
+    def get_num_tracers():
+        return 5
+
+    @staticmethod
+    def micro_name():
+        return "ice1m"
+
+    def init(self, coupler):
+        """registers the five water tracers (positive, add mass) and the diagnostics "precl" and "preci", zeroes them, and writes the
+        scheme's constants into the coupler options"""
+        for name, desc in self.TRACERS:
+            coupler.add_tracer(name, desc, True, True)
+        dm = coupler.get_data_manager_device_readwrite()
+        ny, nx, nens = coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+        for name, desc in self.DIAGNOSTICS:
+            dm.register_and_allocate(name, desc, (ny, nx, nens), ("y", "x", "nens"))
+        for name in [t[0] for t in self.TRACERS] + [d[0] for d in self.DIAGNOSTICS]:
+            dm.get(name).zero_()
+        coupler.set_option("micro", "ice1m")
+        for k in ("R_d", "R_v", "cp_d", "cp_v", "grav", "p0"):
+            coupler.set_option(k, getattr(self, k))
+
+    def timeStep(self, coupler):
+        """one call of pam_amd_ice1m_time_step over crm_dt: every column forms its own sub-cycle count, so nothing is read back"""
+        lib = capi.load()
+        dm = coupler.get_data_manager_device_readwrite()
+        species = [dm.get(t[0]) for t in self.TRACERS]
+        with torch.cuda.device(coupler.device):
+            check(lib.pam_amd_ice1m_time_step(coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(),
+                                              *[t.data_ptr() for t in species], dm.get("density_dry", readonly=True).data_ptr(),
+                                              dm.get("temp").data_ptr(), dm.get("precl").data_ptr(), dm.get("preci").data_ptr(),
+                                              dm.get("vertical_interface_height", readonly=True).data_ptr(),
+                                              float(coupler.get_option("crm_dt")), self.R_v, self.cp_d,
+                                              torch.cuda.current_stream(coupler.device).cuda_stream))
+
+    def compute_total_mass(self, coupler):
+        """sum of (rho_v + rho_c + rho_i + rho_r + rho_s) dz"""
+        dm = coupler.get_data_manager_device_readonly()
+        zint = dm.get("vertical_interface_height", readonly=True)
+        dz = (zint[1:] - zint[:-1])[:, None, None, :]
+        total = dm.get("water_vapor", readonly=True).clone()
+        for name, _ in self.TRACERS[1:]:
+            total += dm.get(name, readonly=True)
+        return float((total * dz).sum())
+
+    def finalize(self, coupler):
+        pass

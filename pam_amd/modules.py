@@ -137,7 +137,7 @@ def supercell_init(vert_interface, R_d, R_v, grav):
     return tuple(cols)
 
 
-SATURATION_CONDENSATE = {"kessler": "cloud_liquid", "p3": "cloud_water"}     # saturation_adjustment.h:126-129
+SATURATION_CONDENSATE = {"kessler": "cloud_liquid", "p3": "cloud_water", "ice1m": "cloud_liquid"}     # saturation_adjustment.h:126-129
 
 
 def saturation_adjustment(coupler):
@@ -414,7 +414,8 @@ def field_diagnostics(tensors, members=0):
 
 # ---- CRM mean-state acceleration (Jones, Bretherton and Pritchard 2015; E3SM-MMF's crm_accel_factor, crm_accel_uv).  Not part of the
 # reference tree: the contract is this project's (include/pam_amd_modules.h; numpy restatement: tests/msa_ref.py)
-MSA_CONDENSATE = {"kessler": ("cloud_liquid", None), "p3": ("cloud_water", "ice"), "none": (None, None)}
+MSA_CONDENSATE = {"kessler": ("cloud_liquid", None), "p3": ("cloud_water", "ice"), "none": (None, None),
+                  "ice1m": ("cloud_liquid", "cloud_ice")}
 MSA_QUANTITIES = ("t", "q", "u", "v")
 
 
@@ -810,7 +811,7 @@ def _column_diagnostics_names(coupler):
     cloud, ice = _handoff_condensate(coupler, "column_diagnostics")
     dm = coupler.get_data_manager_device_readwrite()
     liq = "precl" if dm.entry_exists("precl") else ("precip_liq_surf_out" if dm.entry_exists("precip_liq_surf_out") else None)
-    pice = "precip_ice_surf_out" if dm.entry_exists("precip_ice_surf_out") else None
+    pice = "preci" if dm.entry_exists("preci") else ("precip_ice_surf_out" if dm.entry_exists("precip_ice_surf_out") else None)
     for n in (liq, pice):
         if n is not None and dm.get_shape(n) != [ny, nx, nens]:
             endrun("ERROR: column_diagnostics: %s is %s, not (ny,nx,nens)" % (n, dm.get_shape(n)))

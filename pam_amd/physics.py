@@ -120,6 +120,7 @@ class RadiationGray:
     OPTIONS = ("rad_gray_k_d", "rad_gray_k_v", "rad_gray_k_l", "rad_gray_k_i", "rad_gray_lw_down_top", "rad_gray_every")
     # option "micro" -> the cloud-liquid and the cloud-ice densities
     CONDENSATE = {"kessler": (("cloud_liquid",), ()), "p3": (("cloud_water",), ("ice",)), "none": ((), ())}
+    CONDENSATE_ICE1M = {"ice1m": (("cloud_liquid",), ("cloud_ice",))}      # the row of MicrophysicsIce, read beside CONDENSATE
     SIGMA = 5.670374419e-8      # where the option "sigma" is absent
     SW_FIELDS = (("rad_sw_heating", "shortwave heating rate [K/s]", 4), ("rad_sw_down_sfc", "downward shortwave flux at the surface [W/m2]", 3),
                  ("rad_sw_up_sfc", "upward shortwave flux at the surface [W/m2]", 3),
@@ -203,9 +204,10 @@ class RadiationGray:
                                                        1.0, dt, stream))
                 return
             micro = coupler.get_option("micro") if coupler.option_exists("micro") else "none"
-            if micro not in self.CONDENSATE:
+            species = dict(self.CONDENSATE, **self.CONDENSATE_ICE1M)
+            if micro not in species:
                 endrun("ERROR: radiation: the gray scheme knows the species of micro = kessler, p3 and none, not of " + str(micro))
-            liquid, ice = ([dm.get(n, readonly=True) for n in names] for names in self.CONDENSATE[micro])
+            liquid, ice = ([dm.get(n, readonly=True) for n in names] for names in species[micro])
             ltab = (C.c_void_p * 2)(*[t.data_ptr() for t in liquid])
             itab = (C.c_void_p * 2)(*[t.data_ptr() for t in ice])
             sigma = float(coupler.get_option("sigma")) if coupler.option_exists("sigma") else self.SIGMA
@@ -266,6 +268,7 @@ class SGSSmagorinsky:
     OPTIONS_READ = ("crm_dt", "grav", "cp_d", "sgs_smag_cs", "sgs_smag_prandtl")
     # option "micro" -> the cloud condensate and the precipitating species of the moist branch
     CONDENSATE = {"kessler": (("cloud_liquid",), ("precip_liquid",)), "p3": (("cloud_water", "ice"), ("rain",)), "none": ((), ())}
+    CONDENSATE_ICE1M = {"ice1m": (("cloud_liquid", "cloud_ice"), ("precip_liquid", "precip_ice"))}      # the row of MicrophysicsIce
     LATVAP = 2501000.0          # where the option "latvap" is absent
 
     def __init__(self, cs=0.2, prandtl=1.0 / 3.0, moist=False, surface_fluxes=False, cloud_threshold=0.0):
@@ -327,9 +330,10 @@ class SGSSmagorinsky:
             stream = torch.cuda.current_stream(coupler.device).cuda_stream
             if moist:
                 micro = coupler.get_option("micro") if coupler.option_exists("micro") else "none"
-                if micro not in self.CONDENSATE:
+                species = dict(self.CONDENSATE, **self.CONDENSATE_ICE1M)
+                if micro not in species:
                     endrun("ERROR: sgs: the moist branch knows the species of micro = kessler, p3 and none, not of " + str(micro))
-                cloud, precip = ([dm.get(n, readonly=True) for n in names] for names in self.CONDENSATE[micro])
+                cloud, precip = ([dm.get(n, readonly=True) for n in names] for names in species[micro])
                 ctab = (C.c_void_p * 4)(*[t.data_ptr() for t in cloud])
                 ptab = (C.c_void_p * 8)(*[t.data_ptr() for t in precip])
                 check(lib.pam_amd_sgs_smag_coefficients_moist(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(),

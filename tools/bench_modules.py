@@ -23,6 +23,8 @@ with the surface fluxes of heat and vapour) on Kessler's field set at the C2 gri
 hyperdiffusion and msa_apply of the same run;
 --only grayrad: the native grey two-stream longwave scheme (pam_amd_radiation_gray) at the C2 grid and at C4's 32x1x60 grid with 8192
 members on Kessler's and on P3's field set, beside column_diagnostics and pam_amd_sgs_smag_coefficients of the same run;
+--only ice1m: the one-moment ice microphysics (pam_amd_ice1m_time_step) on a clear, a raining and snowing and a deep_fall state at the
+C2 grid and at C4's 32x1x60 grid with 8192 members, beside Kessler's timeStep and pam_amd_radiation_gray of the same run;
 --only lsforcing: the large-scale forcing (pam_amd_ls_forcing with everything on, with the subsidence alone and without it, and
 pam_amd_ls_nudging) at the C2 grid and at C4's 32x1x60 grid with 8192 members on Kessler's field set, beside hyperdiffusion, msa_apply,
 msa_diagnose and one C2 dycore step of the same run;
@@ -1749,8 +1751,123 @@ def lsforcing_timing(dev, warmup=3, n=11):
     return out
 
 
+def ice1m_timing(dev, warmup=3, n=11):
+    """The one-moment ice microphysics (pam_amd_ice1m_time_step through MicrophysicsIce.timeStep) at the C2 grid and at C4's 32x1x60 grid
+    with 8192 members, 3 warm-up calls and the median of 11 event-timed calls each.  The call works in place and precipitation leaves,
+    so the state is put back before every call, outside the timed interval.  States: clear (vapour and cloud liquid alone, nsub = 1
+    everywhere), raining and snowing (all five species on the L60 grid, crm_dt = 10 s), and deep_fall (the same species on layers of
+    200 m, about 15 m and 0.5 m by member, so that the lanes of every wavefront hold nsub = 1, a few, and the cap of 64).
+    Algorithmic bytes, for every state: 13 x 8 B per cell, the count at nsub = 1 -- six fields read and written, density_dry read once;
+    zint and the two rates are not counted.  On top of it the pre-pass re-reads five fields (5 x 8 B), and every sub-cycle beyond the
+    first reads five and writes three (8 x 8 B per cell of the columns that take it): the rows say what the device moved for the
+    algorithmic count, not that it moved no more.  Kessler's timeStep (11 x 8 B per cell at one sub-cycle, bench.py's count) and
+    pam_amd_radiation_gray on Kessler's field set (12 x 8 B) of the same run stand beside them, and one C2 dycore step for the share
+    of a CRM step."""
+    from pam_amd import Microphysics, MicrophysicsIce, PamCoupler, RadiationGray, capi
+    from pam_amd import idealized as idz
+    import numpy as np
+    lib = capi.load()
+
+    def timed(fn, reset=None):
+        for _ in range(warmup):
+            if reset:
+                reset()
+            fn()
+        ts = []
+        for _ in range(n):
+            if reset:
+                reset()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    def row(t, nbytes):
+        return {"ms": t[0], "min_ms": t[1], "max_ms": t[2], "bytes": nbytes, "GBps": nbytes / t[0] / 1e6,
+                "hbm_frac": nbytes / t[0] / 1e6 / bench.HBM_PEAK_GBS}
+
+    def grid(nens, nx, ny, nz, label, out):
+        cells, cols = nens * nx * ny * nz, nens * nx * ny
+        zint = np.asarray(idz.l60_interfaces(), dtype=np.float64)
+        e = np.arange(nens)
+        thin = np.arange(nz + 1)[:, None] * np.where(e % 3 == 0, 200.0, np.where(e % 3 == 1, 12.0 + (e % 7), 0.5))[None, :]
+        gen = torch.Generator(device=dev).manual_seed(0)
+        k = torch.arange(nz, dtype=torch.float64, device=dev)[:, None, None, None]
+        rnd = lambda: torch.rand((nz, ny, nx, nens), generator=gen, dtype=torch.float64, device=dev)
+        state = {"temp": (0.95 + 0.1 * rnd()) * (299.0 - 1.5 * k), "density_dry": (0.95 + 0.1 * rnd()) * 1.15 * torch.exp(-k / 25.0),
+                 "water_vapor": (0.95 + 0.1 * rnd()) * 1.6e-2 * torch.exp(-k / 10.0)}
+        third = lambda scale: rnd() * scale * (rnd() < 1.0 / 3.0)        # condensate in a third of the cells
+        wet = {"cloud_liquid": third(1.0e-3), "cloud_ice": third(3.0e-4), "precip_liquid": third(1.0e-3), "precip_ice": third(1.0e-3)}
+        zero = torch.zeros((nz, ny, nx, nens), dtype=torch.float64, device=dev)
+        states = {"clear": (dict(state, cloud_liquid=wet["cloud_liquid"], cloud_ice=zero, precip_liquid=zero, precip_ice=zero), zint, 2.0),
+                  "raining_snowing": (dict(state, **wet), zint, 10.0), "deep_fall": (dict(state, **wet), thin, 10.0)}
+        for tag, (fields, z, dt) in states.items():
+            c = PamCoupler(dev)
+            c.set_option("crm_dt", dt)
+            c.allocate_coupler_state(nz, ny, nx, nens)
+            c.set_grid(nx * 1000.0, ny * 1000.0, z)
+            micro = MicrophysicsIce()
+            micro.init(c)
+            dm = c.get_data_manager_device_readwrite()
+
+            def reset():
+                for name, t in fields.items():
+                    dm.get(name).copy_(t)
+            out["ice1m_%s%s" % (tag, label)] = row(timed(lambda: micro.timeStep(c), reset), cells * 8.0 * 13)
+            assert all(bool(torch.isfinite(dm.get(name, readonly=True)).all()) for name in list(fields) + ["precl", "preci"])
+            assert all(float(dm.get(name, readonly=True).min()) >= 0.0 for name in wet)
+            out["ice1m_%s%s" % (tag, label)]["mean_preci"] = float(dm.get("preci", readonly=True).mean())
+            del c, dm, micro
+        # the yardsticks on the same grid: Kessler on the raining state, the grey longwave on Kessler's field set
+        c = PamCoupler(dev)
+        c.set_option("crm_dt", 2.0)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        c.set_grid(nx * 1000.0, ny * 1000.0, zint)
+        kessler = Microphysics()
+        kessler.init(c)
+        dm = c.get_data_manager_device_readwrite()
+        kfields = dict(state, cloud_liquid=wet["cloud_liquid"], precip_liquid=zero)
+
+        def kreset():
+            for name, t in kfields.items():
+                dm.get(name).copy_(t)
+        kreset()
+        assert kessler.timeStep(c) == 1
+        out["kessler_time_step_no_rain" + label] = row(timed(lambda: kessler.timeStep(c), kreset), cells * 8.0 * 11)
+        kreset()
+        rad = RadiationGray()
+        rad.init(c)
+        out["grayrad_kessler" + label] = row(timed(lambda: rad.timeStep(c)), cells * 8.0 * 12 + (nz + 1) * nens * 8.0 + 3 * cols * 8.0)
+        for tag in states:
+            for y in ("kessler_time_step_no_rain", "grayrad_kessler"):
+                out["ice1m_%s%s_vs_%s_frac" % (tag, label, y)] = out["ice1m_%s%s" % (tag, label)]["hbm_frac"] / out[y + label]["hbm_frac"]
+        del c, dm, kessler, rad
+        lib.pam_amd_modules_finalize()
+        torch.cuda.empty_cache()
+
+    out = {"ice1m_grid": "1024 x 32x32x60 (C2) and 8192 x 32x1x60 (C4)",
+           "ice1m_method": "%d warm-up calls, median of %d event-timed calls, the state put back before each" % (warmup, n),
+           "ice1m_bytes": "13 x 8 B per cell (six fields read and written, density_dry read once): the count at nsub = 1, used for every state",
+           "hbm_peak_GBps": bench.HBM_PEAK_GBS}
+    grid(1024, 32, 32, 60, "", out)
+    grid(8192, 32, 1, 60, "_c4", out)
+    job = bench.Job("c2", bench.parse_args([]), dev, 0, 1)
+    _, elapsed, _ = job.timed(3, 2)
+    out["c2_dycore_step_ms"] = elapsed / 3 * 1e3
+    for tag in ("clear", "raining_snowing", "deep_fall"):
+        out["ice1m_%s_share_of_c2_dycore_step" % tag] = out["ice1m_" + tag]["ms"] / out["c2_dycore_step_ms"]
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "ice1m"]:
+        print(json.dumps(ice1m_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "lsforcing"]:
         print(json.dumps(lsforcing_timing(dev)))
         sys.exit(0)
