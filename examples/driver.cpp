@@ -54,6 +54,7 @@
 #include "modules/surface_friction.h"
 #include "modules/surface_fluxes.h"
 #include "modules/large_scale_forcing.h"
+#include "modules/scalar_momentum.h"
 #include "modules/horizontal_average.h"
 #include "modules/time_average.h"
 #include "modules/mean_state_acceleration.h"
@@ -319,7 +320,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
-//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--micro-ice] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
+//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--esmt [KMAX]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--micro-ice] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
 //          [--flux-profiles PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
@@ -442,6 +443,13 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //   --sfc-fluxes SHF LHF       with --sgs-smag: option sgs_smag_surface_fluxes; "sfc_shf" and "sfc_lhf" are filled uniformly, once, with
 //                              SHF and LHF (W/m2, positive upward) and enter row 0 of temp and of the vapour in every SGS step.  Both
 //                              compose with every other flag
+//   --esmt [KMAX]              explicit scalar momentum transport (modules/scalar_momentum.h) on a 2-D CRM (crm_ny == 1): modules::esmt_init
+//                              before dycore.init (two more tracers, "esmt_u" and "esmt_v"), the scalars set from the CRM's own level-mean
+//                              wind (modules::esmt_set "crm"), then modules::esmt_pgf every CRM step after the sponge layer and before the
+//                              SGS, with the wavenumbers 1 .. KMAX (default crm_nx / 2); there is no GCM, so there is no forcing.  Per
+//                              output step a line "esmt: etime <s> , u_s <m/s> , v_s <m/s> , max_T_dt <m/s>": the means of esmt_x / rho
+//                              over the domain and the largest |T| dt of the last step that was probed (the step before an output).
+//                              Composes with the rest.
 //   --radiation-gray [EVERY]   the native grey two-stream longwave scheme (physics/radiation/gray_amd/radiation.h) in the radiation slot of
 //                              the CRM loop, where --radiation puts the forced class: its timeStep every CRM step before the dycore, the
 //                              fluxes recomputed on every EVERY-th step (1 unless given) and the stored heating applied between.  One
@@ -485,8 +493,8 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              prof_flux_v and prof_tke, printed with %.17g; nothing else of the run changes.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  bool micro_ice = false, vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false, shortwave = false, surface = false, ls_forcing = false, coriolis = false;
-  int radiation_gray_every = 1;
+  bool micro_ice = false, vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false, shortwave = false, surface = false, ls_forcing = false, coriolis = false, esmt = false;
+  int radiation_gray_every = 1, esmt_kmax = -1;
   double sw_coszen = 1, sw_albedo = 0.07;
   double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0, sfc_shf = 0, sfc_lhf = 0, surface_sst = 300, surface_depth = 0, ls_fcor = 0;
   int handoff_rad_nx = 0, handoff_rad_ny = 0;
@@ -616,6 +624,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         }
       }
     } else sgs.init(coupler);                                                // driver.cpp:190 (the reference's CI build: SHOC with P3; their numerics are out of scope, their coupling layers are physics/sgs/shoc_amd and physics/micro/p3_amd)
+    if (mods.esmt) modules::esmt_init(coupler, mods.esmt_kmax);              // --esmt: two more tracers, before the dycore takes its table
     dycore.init(coupler);                                                    // driver.cpp:191
     if (mods.radiation_gray) {                                               // --radiation-gray: the native scheme in the radiation slot
       coupler.set_option<int>("rad_gray_every", mods.radiation_gray_every);
@@ -707,6 +716,8 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       if (mods.coriolis) P.fcor = {mods.ls_fcor};
       coupler.run_module("ls_forcing_init", [&](pam::PamCoupler &c) { modules::ls_forcing_init(c, P); });
     }
+    if (mods.esmt) coupler.run_module("esmt_set", [](pam::PamCoupler &c) { modules::esmt_set(c, "crm"); });   // from the CRM's own level-mean wind
+    double esmt_max_t_dt = 0;
     const size_t ncell = (size_t)crm_nz * crm_ny * crm_nx * nens;
     std::vector<real> buf(ncell);
     auto fetch = [&](std::string const &name) {
@@ -772,6 +783,29 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         if (apply_sponge && !dbg.no_sponge) coupler.run_module("sponge_layer", modules::sponge_layer);         // driver.cpp:249-251
         if (mods.ls_forcing) coupler.run_module("ls_forcing", [](pam::PamCoupler &c) { modules::ls_forcing(c); });
+        if (mods.esmt) {                                                     // --esmt: the pressure force on the two scalars; no GCM, no forcing
+          // probed on the step an output follows (any step of an accelerated run): the scalars before and after, for max |T| dt
+          const bool probe = out_freq >= 0. && (accel || (step_gcm * dt_gcm + (clock.count() + 1) * dt_crm_phys) / out_freq >= num_out + 1);
+          std::vector<real> before[2];
+          if (probe)
+            for (int x = 0; x < 2; x++) { fetch(x == 0 ? "esmt_u" : "esmt_v"); before[x] = buf; }
+          coupler.run_module("esmt_pgf", [](pam::PamCoupler &c) { modules::esmt_pgf(c, -1, false); });
+          if (probe) {
+            std::vector<real> rho(ncell);
+            fetch("density_dry");
+            rho = buf;
+            fetch("water_vapor");
+            for (size_t c = 0; c < ncell; c++) rho[c] += buf[c];
+            esmt_max_t_dt = 0;
+            for (int x = 0; x < 2; x++) {
+              fetch(x == 0 ? "esmt_u" : "esmt_v");
+              for (size_t c = 0; c < ncell; c++) {
+                const double d = std::fabs((buf[c] - before[x][c]) / rho[c]);
+                esmt_max_t_dt = d > esmt_max_t_dt || d != d ? d : esmt_max_t_dt;
+              }
+            }
+          }
+        }
         if (mods.surface) coupler.run_module("surface_fluxes", [](pam::PamCoupler &c) { modules::compute_surface_fluxes(c); });
         if (mods.surface_friction) coupler.run_module("surface_friction", modules::compute_surface_friction);
         if (mods.hyperdiff) coupler.run_module("hyperdiffusion", [](pam::PamCoupler &c) { modules::hyperdiffusion(c); });
@@ -838,6 +872,17 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
             items.push_back({"temp", 0, dm.get<real const, 4>("temp").data(), level, items.size()});
             auto s3 = pam::diagnostics::scan(items, 0);
             std::printf("ls forcing: etime %g , uvel %.9g , vvel %.9g , temp0 %.9g\n", etime_gcm, s3[0].mean(), s3[1].mean(), s3[2].mean());
+          }
+          if (mods.esmt) {                                                   // the level means of the scalars as they are now, averaged
+            modules::esmt_detail::diagnose(coupler, "driver", nullptr, nullptr, false);
+            const size_t n2 = (size_t)crm_nz * nens;
+            std::vector<real> um(n2), vm(n2);
+            if (hipMemcpy(um.data(), dm.get<real const, 2>("esmt_u_mean").data(), n2 * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(vm.data(), dm.get<real const, 2>("esmt_v_mean").data(), n2 * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess)
+              endrun("memcpy");
+            double su = 0, sv = 0;
+            for (size_t c = 0; c < n2; c++) { su += um[c]; sv += vm[c]; }
+            std::printf("esmt: etime %g , u_s %.9g , v_s %.9g , max_T_dt %.9g\n", etime_gcm, su / n2, sv / n2, esmt_max_t_dt);
           }
           if (mods.micro_ice) {                                              // the ice water path, the two rates, and the water budget
             fetch("cloud_ice");
@@ -1049,7 +1094,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (f == 0) rho_min = std::min(rho_min, (double)v);
         if (f == 3) w_max = std::max(w_max, (double)std::fabs(v));
         if (f == 4) { if (v < t_min) { t_min = v; t_min_at = (long)c; } t_max = std::max(t_max, (double)v); }
-        if (f >= 5) qmin = std::min(qmin, (double)v);
+        if (f >= 5 && names[f].rfind("esmt_", 0) != 0) qmin = std::min(qmin, (double)v);      // (the scalars of --esmt carry a wind: either sign)
       }
       if (out.is_open()) out.write((char *)buf.data(), ncell * sizeof(real));
     }
@@ -1148,6 +1193,11 @@ int main(int argc, char **argv) {
       }
       else if (o == "--ls-forcing" && b + 1 < argc - 1) { mods.ls_forcing = true; mods.ls_path = argv[++b]; }
       else if (o == "--coriolis" && b + 1 < argc - 1) { mods.coriolis = true; mods.ls_fcor = std::atof(argv[++b]); }
+      else if (o == "--esmt") {
+        mods.esmt = true;
+        const std::string n(b + 1 < argc - 1 ? argv[b + 1] : "");                // the optional KMAX: an argument of digits only
+        if (!n.empty() && n.find_first_not_of("0123456789") == std::string::npos) mods.esmt_kmax = std::atoi(argv[++b]);
+      }
       else if (o == "--gcm-handoff" && b + 3 < argc - 1) {
         mods.handoff = true;
         mods.handoff_rad_nx = std::atoi(argv[++b]);
@@ -1158,7 +1208,7 @@ int main(int argc, char **argv) {
       else if (o == "--flux-profiles" && b + 1 < argc - 1) mods.flux_profiles = argv[++b];
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--micro-ice] "
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--esmt [KMAX]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--micro-ice] "
                "[--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->");
     }
     if (mods.radiation_gray && mods.radiation) die("--radiation-gray and --radiation both fill the one radiation slot: give one of them");

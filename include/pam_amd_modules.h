@@ -989,6 +989,75 @@ int pam_amd_ice1m_time_step(int nens, int nx, int ny, int nz, double *rho_v, dou
                             double dt, double R_v, double cp_d, void *stream);
 int pam_amd_ice1m_debug_wide_index(int on);
 
+/* Explicit scalar momentum transport (ESMT) for 2-D CRMs (Tulich 2015, JAMES; E3SM-MMF's use_MMF_ESMT).  A 2-D CRM cannot transport the
+ * cross-plane wind and transports the in-plane wind with the wrong pressure-gradient force, so the large-scale u and v are carried as
+ * two passive scalars, the mass densities esmt_u and esmt_v with the carried quantity x_s = esmt_x / rho.  The dycore advects them as
+ * it does any tracer; each CRM step they take the linearised pressure-gradient force -(1/rho) dp'/dx with
+ * lap p' = -2 rho_mean (dU/dz) dw/dx, and the tendency of their level means goes back to the GCM.  Not part of the reference tree; the
+ * contract is this project's and is restated in numpy in tests/esmt_ref.py, which the kernels match bit for bit.
+ * Everything is fp64, every operation is rounded on its own (no fma), every division is a true IEEE division, and the association is
+ * as written.  Fields are (nz,ny,nx,nens) with ny == 1; profiles are DEVICE arrays (nz,nens).  rho = rho_d + rho_v as at entry, frozen
+ * for the call, as in pam_amd_sgs_smag_diffuse and pam_amd_ls_forcing.  M is the level mean of pam_amd_msa_diagnose: cell c belongs to
+ * slot c % 16, a slot adds x(k,c,e) r over its cells in ascending c from 0.0 with r = 1/nx and the product rounded first, and the 16
+ * slot sums are added in ascending slot order from 0.0.
+ *
+ * pam_amd_esmt_set: esmt_x(k,c,e) = rho(k,c,e) src_x(k,e), src_u and src_v (nz,nens) given by the caller.
+ *
+ * pam_amd_esmt_diagnose: rho_mean = M(rho), u_mean = M(esmt_u / rho), v_mean = M(esmt_v / rho), the quotient formed per cell before it
+ * enters a slot.  Where gcm_x is not NULL (tend_x then too, and the other way round) it also writes
+ * tend_x(k,e) = (gcm_x - x_mean) / gcm_dt, and with feedback != 0 (x_mean - gcm_x) / gcm_dt instead: one entry point serves the
+ * forcing that the GCM applies to the scalars, once per GCM step, and the momentum tendency handed back at the end of it.  No
+ * floating-point atomics, no scratch.
+ *
+ * pam_amd_esmt_pgf works IN PLACE on esmt_u and esmt_v.  zmid and dz are (nz,nens); cos_table and sin_table are DEVICE tables
+ * C[j] = cos((2 pi j) / nx), S[j] = sin((2 pi j) / nx), j = 0..nx-1, 2 pi = 6.283185307179586, formed once on the host
+ * (pam_amd_esmt_tables writes them into HOST arrays); the device calls no sine or cosine.  The entry point forms
+ * k1 = 2 pi / (nx dx), s = 2.0 / nx, s_nyq = 1.0 / nx.  A NULL force_x is absent: not read, and no zero added.  A NULL x_mean leaves
+ * its scalar without the pressure force.  Per member, with z = zmid(.,e), h = dz(.,e), X either mean:
+ *   G_X(0)    = (X(1) - X(0)) / (z(1) - z(0));   G_X(nz-1) = (X(nz-1) - X(nz-2)) / (z(nz-1) - z(nz-2));
+ *   G_X(k)    = (X(k+1) - X(k-1)) / (z(k+1) - z(k-1)) otherwise;
+ *   a(k) = 1.0 / (h(k) (z(k) - z(k-1))), a(0) = 0;   c(k) = 1.0 / (h(k) (z(k+1) - z(k))), c(nz-1) = 0;
+ *   for m = 1 .. kmax:  idx(i) = (m i) % nx;  kap = m k1;  k2 = kap kap;  b(k) = (a(k) + c(k)) + k2;
+ *     wc(k) = s_m sum_i (wvel(k,i) C[idx(i)]),  ws(k) = s_m sum_i (wvel(k,i) S[idx(i)]),  ascending i from 0.0;
+ *       s_m = s, but s_nyq and no sine component where 2 m == nx;
+ *     per scalar X and component:  R(k) = (rho_mean(k) G_X(k)) w?(k);
+ *       cp(0) = -c(0) / b(0);  d(0) = R(0) / b(0);
+ *       den = b(k) + a(k) cp(k-1);  cp(k) = -c(k) / den;  d(k) = (R(k) + a(k) d(k-1)) / den;
+ *       psi(nz-1) = d(nz-1);  psi(k) = d(k) - cp(k) psi(k+1);   That(k) = ((2.0 k2) / rho_mean(k)) psi(k);
+ *   T_X(k,i) = sum over ascending m from 0.0 of: + That_c(k) C[idx(i)], then + That_s(k) S[idx(i)];
+ *   inc = dt T_X(k,i);  where force_X is given: inc = inc + dt force_X(k,e);  with kmax == 0 or no X mean: inc = dt force_X(k,e);
+ *   esmt_X(k,i) = esmt_X(k,i) + rho(k,i) inc.
+ * The solve is (kap^2 - d_zz) psi = rho_mean U_z w^ with zero normal gradient at both ends; with p^ = -2 i kap phi^ the force
+ * -(i kap / rho_mean) p^ collapses to the real factor 2 kap^2 / rho_mean, which keeps the complex rotation out of the kernel.  The
+ * matrix is strictly diagonally dominant for m >= 1, so there is no pivoting, and cp and den do not depend on the data: one
+ * elimination serves the four right-hand sides of a wavenumber.
+ * So: with kmax == 0 (or both means NULL) and no force the call returns PAM_AMD_OK and launches nothing; with kmax == 0 only the
+ * uniform forcing is applied; where a member has no shear (G_X == 0 on every level) and no force every bit of esmt_X is kept (but a
+ * -0.0); a NaN stays in its own member; the same bits from run to run and for any split of the members over calls, given the
+ * matching slices of the profiles.
+ * Three launches: forward, a thread per (level, member, block of 8 wavenumbers); Thomas, a thread per (wavenumber, member), loads
+ * requested AHEAD = 4 levels before use; inverse with the update, a thread per (level, member, block of 8 x cells).  Members across
+ * the lanes; no scratch, no LDS, no atomics.  workspace: pam_amd_esmt_workspace_doubles(nens, nz, kmax) = 6 kmax nz nens doubles of
+ * DEVICE memory (at most three fields) that the caller owns; it may be NULL with kmax == 0.  Nothing is allocated per call.  Flat
+ * offsets are 64 bits wide from 2^29 elements per field on; pam_amd_esmt_debug_wide_index(1) forces those instances at any size.
+ * PAM_AMD_EINVAL before the first HIP call, nothing written, no device needed: ny != 1 (a 3-D CRM transports momentum itself); nz < 2;
+ * nx < 2; nens < 1; kmax outside 0..nx/2; a NULL required pointer; a force without its scalar's mean; a gcm profile without its tend
+ * or a tend without its gcm profile; dt, dx (and gcm_dt where a gcm profile is given) not finite and positive; outputs overlapping
+ * inputs or each other; a workspace smaller than the documented size.  Without a device a call that passes its checks returns
+ * PAM_AMD_ENOGPU. */
+int pam_amd_esmt_set(int nens, int nx, int ny, int nz, const double *rho_d, const double *rho_v, const double *src_u, const double *src_v,
+                     double *esmt_u, double *esmt_v, void *stream);
+int pam_amd_esmt_diagnose(int nens, int nx, int ny, int nz, const double *rho_d, const double *rho_v, const double *esmt_u,
+                          const double *esmt_v, double *rho_mean, double *u_mean, double *v_mean, const double *gcm_u, const double *gcm_v,
+                          double gcm_dt, int feedback, double *tend_u, double *tend_v, void *stream);
+int pam_amd_esmt_pgf(int nens, int nx, int ny, int nz, double *esmt_u, double *esmt_v, const double *wvel, const double *rho_d,
+                     const double *rho_v, const double *zmid, const double *dz, const double *rho_mean, const double *u_mean,
+                     const double *v_mean, const double *force_u, const double *force_v, const double *cos_table, const double *sin_table,
+                     double dx, double dt, int kmax, double *workspace, long long workspace_doubles, void *stream);
+long long pam_amd_esmt_workspace_doubles(int nens, int nz, int kmax);
+int pam_amd_esmt_tables(int nx, double *cos_table, double *sin_table);
+int pam_amd_esmt_debug_wide_index(int on);
+
 #ifdef __cplusplus
 }
 #endif

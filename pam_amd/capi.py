@@ -216,6 +216,12 @@ MODULE_SYMBOLS = {
     "pam_amd_ls_forcing_debug_wide_index": (C.c_int, [C.c_int]),
     "pam_amd_ice1m_time_step": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 10 + [C.c_double] * 3 + [C.c_void_p]),
     "pam_amd_ice1m_debug_wide_index": (C.c_int, [C.c_int]),
+    "pam_amd_esmt_set": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 7),
+    "pam_amd_esmt_diagnose": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 9 + [C.c_double, C.c_int] + [C.c_void_p] * 3),
+    "pam_amd_esmt_pgf": (C.c_int, [C.c_int] * 4 + [C.c_void_p] * 14 + [C.c_double] * 2 + [C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "pam_amd_esmt_workspace_doubles": (C.c_longlong, [C.c_int] * 3),
+    "pam_amd_esmt_tables": (C.c_int, [C.c_int] + [C.c_void_p] * 2),
+    "pam_amd_esmt_debug_wide_index": (C.c_int, [C.c_int]),
 }
 
 

@@ -4469,3 +4469,201 @@ extern "C" int pam_amd_ice1m_time_step(int nens, int nx, int ny, int nz, double 
   else hipLaunchKernelGGL((ice1m_kernel<long long>), grid, block, 0, s, nens, level, nz, A);
   return stats_launch_check(who);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Explicit scalar momentum transport for 2-D CRMs (Tulich 2015; E3SM-MMF's use_MMF_ESMT): the large-scale u and v ride as the passive
+// scalars esmt_u and esmt_v, and every CRM step they take the linearised pressure-gradient force.  Not in the reference tree; the
+// contract is in include/pam_amd_modules.h and DESIGN.md section 8, its arithmetic in esmt_device.h.  The level means are on the slot
+// order of msa_mean_kernel (slot_reduce).  The force is THREE launches over a workspace the caller owns: a forward pass, a thread per
+// (level, member, block of 8 wavenumbers); a Thomas pass, a thread per (wavenumber, member); the inverse transform with the update, a
+// thread per (level, member, block of 8 x cells).  Members across the lanes; the tables are read at lane-uniform indices.  No scratch,
+// no LDS, no atomics.  IDX: unsigned while a field is below 2^29 doubles (the workspace is at most three fields).
+#include "esmt_device.h"
+
+namespace {
+namespace es = pama::esmt;
+constexpr int ESMT_THREADS = 64;
+constexpr long long ESMT_NARROW_CELLS = 1ll << 29;    // fields from this size on take the long long instances
+constexpr double ESMT_TWO_PI = 6.283185307179586;
+
+// grid (ceil(nz nx nens / 64)), block 64: esmt_x = rho src_x
+__global__ void __launch_bounds__(ESMT_THREADS) esmt_set_kernel(long long cells, long long level, int nens, const double *__restrict__ rho_d,
+                                                                const double *__restrict__ rho_v, const double *__restrict__ src_u,
+                                                                const double *__restrict__ src_v, double *__restrict__ eu, double *__restrict__ ev) {
+  const long long t = (long long)blockIdx.x * ESMT_THREADS + (long long)threadIdx.x;
+  if (t >= cells) return;
+  const long long row = (t / level) * nens + t % nens;
+  const double rd = rho_d[t], rv = rho_v[t];
+  eu[t] = es::set_cell(rd, rv, src_u[row]);
+  ev[t] = es::set_cell(rd, rv, src_v[row]);
+}
+
+// grid (member blocks, levels), block (members, 16 slots): the three level means, and the tendencies where a gcm profile is given
+__global__ void __launch_bounds__(64 * MOD_NS) esmt_diagnose_kernel(int nens, int ncol, const double *__restrict__ rho_d, const double *__restrict__ rho_v,
+                                                                    const double *__restrict__ eu, const double *__restrict__ ev, double *rho_mean,
+                                                                    double *u_mean, double *v_mean, const double *gcm_u, const double *gcm_v,
+                                                                    double gcm_dt, int feedback, double *tend_u, double *tend_v) {
+  __shared__ double red[es::NM * MOD_NS * 64];
+  const int ME = blockDim.x, slot = threadIdx.y;
+  const int e0 = (int)blockIdx.x * ME + (int)threadIdx.x;
+  const bool ok = e0 < nens;
+  const int e = ok ? e0 : nens - 1, k = (int)blockIdx.y;
+  const long long base = (long long)k * ncol * nens + e;
+  double acc[es::NM] = {0.0, 0.0, 0.0};
+  if (ok) es::mean_walk(rho_d + base, rho_v + base, eu + base, ev + base, (long long)nens, ncol, slot, acc);
+  slot_reduce<es::NM>(acc, red);
+  if (slot != 0 || !ok) return;
+  const long long t = (long long)k * nens + e;
+  rho_mean[t] = acc[es::M_RHO];
+  u_mean[t] = acc[es::M_U];
+  v_mean[t] = acc[es::M_V];
+  if (gcm_u) tend_u[t] = es::tendency(acc[es::M_U], gcm_u[t], gcm_dt, feedback != 0);
+  if (gcm_v) tend_v[t] = es::tendency(acc[es::M_V], gcm_v[t], gcm_dt, feedback != 0);
+}
+
+// grid (member blocks, levels, blocks of wavenumbers), block 64
+template <class IDX>
+__global__ void __launch_bounds__(ESMT_THREADS) esmt_forward_kernel(es::Args A) {
+  const int e = (int)blockIdx.x * ESMT_THREADS + (int)threadIdx.x;
+  if (e >= A.nens) return;
+  es::forward<IDX>(A, (int)blockIdx.y, e, (int)blockIdx.z);
+}
+
+// grid (member blocks, wavenumbers), block 64
+template <class IDX>
+__global__ void __launch_bounds__(ESMT_THREADS) esmt_thomas_kernel(es::Args A) {
+  const int e = (int)blockIdx.x * ESMT_THREADS + (int)threadIdx.x;
+  if (e >= A.nens) return;
+  es::thomas<IDX>(A, 1 + (int)blockIdx.y, e);
+}
+
+// grid (member blocks, levels, blocks of x cells), block 64
+template <class IDX>
+__global__ void __launch_bounds__(ESMT_THREADS) esmt_inverse_kernel(es::Args A) {
+  const int e = (int)blockIdx.x * ESMT_THREADS + (int)threadIdx.x;
+  if (e >= A.nens) return;
+  es::inverse_update<IDX>(A, (int)blockIdx.y, e, (int)blockIdx.z);
+}
+
+bool g_esmt_force_wide = false;   // pam_amd_esmt_debug_wide_index: tests run the long long instances at small sizes
+
+int esmt_check_grid(const char *who, int nens, int nx, int ny, int nz) {
+  if (ny != 1) return module_error(who, "ny must be 1: a 3-D CRM transports momentum itself");
+  if (nens < 1) return module_error(who, "nens must be >= 1");
+  if (nx < 2 || nz < 2) return module_error(who, "nx and nz must be >= 2");
+  if (nz > 65535) return module_error(who, "nz exceeds the grid (65535 levels)");
+  if (nx > 65535 * es::XB) return module_error(who, "nx exceeds the grid");
+  return PAM_AMD_OK;
+}
+}  // namespace
+
+extern "C" int pam_amd_esmt_debug_wide_index(int on) {
+  g_esmt_force_wide = on != 0;
+  return PAM_AMD_OK;
+}
+
+extern "C" long long pam_amd_esmt_workspace_doubles(int nens, int nz, int kmax) {
+  if (nens < 1 || nz < 1 || kmax < 0) return 0;
+  return 6ll * kmax * nz * nens;
+}
+
+extern "C" int pam_amd_esmt_tables(int nx, double *cos_table, double *sin_table) {
+  const char *who = "esmt_tables";
+  if (nx < 2) return module_error(who, "nx must be >= 2");
+  if (!cos_table || !sin_table) return module_error(who, "null pointer");
+  for (int j = 0; j < nx; j++) {
+    const double x = (ESMT_TWO_PI * (double)j) / (double)nx;
+    cos_table[j] = std::cos(x);
+    sin_table[j] = std::sin(x);
+  }
+  return PAM_AMD_OK;
+}
+
+extern "C" int pam_amd_esmt_set(int nens, int nx, int ny, int nz, const double *rho_d, const double *rho_v, const double *src_u,
+                                const double *src_v, double *esmt_u, double *esmt_v, void *stream) {
+  const char *who = "esmt_set";
+  if (int rc = esmt_check_grid(who, nens, nx, ny, nz)) return rc;
+  if (!rho_d || !rho_v || !src_u || !src_v || !esmt_u || !esmt_v) return module_error(who, "null pointer");
+  const long long level = (long long)nx * nens, cells = level * nz, rows = (long long)nz * nens;
+  if ((cells + ESMT_THREADS - 1) / ESMT_THREADS > 0x7fffffffLL) return module_error(who, "nz x nx x nens exceeds the grid");
+  if (spans_overlap({{rho_d, cells, false}, {rho_v, cells, false}, {src_u, rows, false}, {src_v, rows, false}, {esmt_u, cells, true},
+                     {esmt_v, cells, true}}))
+    return module_error(who, "an output overlaps an input or another output");
+  if (int rc = require_device(who)) return rc;
+  hipLaunchKernelGGL(esmt_set_kernel, dim3((unsigned)((cells + ESMT_THREADS - 1) / ESMT_THREADS)), dim3(ESMT_THREADS), 0, (hipStream_t)stream, cells,
+                     level, nens, rho_d, rho_v, src_u, src_v, esmt_u, esmt_v);
+  return stats_launch_check(who);
+}
+
+extern "C" int pam_amd_esmt_diagnose(int nens, int nx, int ny, int nz, const double *rho_d, const double *rho_v, const double *esmt_u,
+                                     const double *esmt_v, double *rho_mean, double *u_mean, double *v_mean, const double *gcm_u,
+                                     const double *gcm_v, double gcm_dt, int feedback, double *tend_u, double *tend_v, void *stream) {
+  const char *who = "esmt_diagnose";
+  if (int rc = esmt_check_grid(who, nens, nx, ny, nz)) return rc;
+  if (!rho_d || !rho_v || !esmt_u || !esmt_v || !rho_mean || !u_mean || !v_mean) return module_error(who, "null pointer");
+  if (!gcm_u != !tend_u || !gcm_v != !tend_v) return module_error(who, "a gcm profile and its tend come together");
+  if ((gcm_u || gcm_v) && !sgs_positive(gcm_dt)) return module_error(who, "gcm_dt must be finite and positive");
+  const long long cells = (long long)nx * nens * nz, rows = (long long)nz * nens;
+  std::vector<Span> spans = {{rho_d, cells, false}, {rho_v, cells, false}, {esmt_u, cells, false}, {esmt_v, cells, false},
+                             {rho_mean, rows, true}, {u_mean, rows, true}, {v_mean, rows, true}};
+  if (gcm_u) { spans.push_back({gcm_u, rows, false}); spans.push_back({tend_u, rows, true}); }
+  if (gcm_v) { spans.push_back({gcm_v, rows, false}); spans.push_back({tend_v, rows, true}); }
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  if (int rc = require_device(who)) return rc;
+  const auto [grid, block] = slot_block_shape(nens, nz);
+  hipLaunchKernelGGL(esmt_diagnose_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, rho_d, rho_v, esmt_u, esmt_v, rho_mean, u_mean, v_mean,
+                     gcm_u, gcm_v, gcm_dt, feedback, tend_u, tend_v);
+  return stats_launch_check(who);
+}
+
+extern "C" int pam_amd_esmt_pgf(int nens, int nx, int ny, int nz, double *esmt_u, double *esmt_v, const double *wvel, const double *rho_d,
+                                const double *rho_v, const double *zmid, const double *dz, const double *rho_mean, const double *u_mean,
+                                const double *v_mean, const double *force_u, const double *force_v, const double *cos_table,
+                                const double *sin_table, double dx, double dt, int kmax, double *workspace, long long workspace_doubles,
+                                void *stream) {
+  const char *who = "esmt_pgf";
+  if (int rc = esmt_check_grid(who, nens, nx, ny, nz)) return rc;
+  if (kmax < 0 || kmax > nx / 2) return module_error(who, "kmax must be in [0, nx / 2]");
+  if (kmax > 65535) return module_error(who, "kmax exceeds the grid (65535 wavenumbers)");
+  if (!esmt_u || !esmt_v || !wvel || !rho_d || !rho_v || !zmid || !dz || !rho_mean || !cos_table || !sin_table) return module_error(who, "null pointer");
+  if ((force_u && !u_mean) || (force_v && !v_mean)) return module_error(who, "a force needs its scalar's mean");
+  if (!sgs_positive(dt) || !sgs_positive(dx)) return module_error(who, "dt and dx must be finite and positive");
+  const long long level = (long long)nx * nens, cells = level * nz, rows = (long long)nz * nens;
+  const long long need = pam_amd_esmt_workspace_doubles(nens, nz, kmax);
+  if (kmax > 0 && (!workspace || workspace_doubles < need)) return module_error(who, "the workspace is smaller than 6 kmax nz nens doubles");
+  std::vector<Span> spans = {{wvel, cells, false}, {rho_d, cells, false}, {rho_v, cells, false}, {zmid, rows, false}, {dz, rows, false},
+                             {rho_mean, rows, false}, {cos_table, nx, false}, {sin_table, nx, false}, {esmt_u, cells, true}, {esmt_v, cells, true}};
+  for (const double *p : {u_mean, v_mean, force_u, force_v})
+    if (p) spans.push_back({p, rows, false});
+  if (kmax > 0) spans.push_back({workspace, need, true});
+  if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
+  const bool solve = kmax > 0 && (u_mean || v_mean);
+  if (!solve && !force_u && !force_v) return PAM_AMD_OK;      // no force and nothing to add: no launch
+  if (int rc = require_device(who)) return rc;
+
+  es::Args A;
+  A.eu = esmt_u; A.ev = esmt_v; A.ws = workspace; A.w = wvel; A.rd = rho_d; A.rv = rho_v; A.zmid = zmid; A.dz = dz;
+  A.rho_mean = rho_mean; A.u_mean = u_mean; A.v_mean = v_mean; A.force_u = force_u; A.force_v = force_v; A.C = cos_table; A.S = sin_table;
+  A.k1 = ESMT_TWO_PI / ((double)nx * dx);
+  A.s = 2.0 / (double)nx;
+  A.s_nyq = 1.0 / (double)nx;
+  A.dt = dt; A.nx = nx; A.nz = nz; A.nens = nens; A.kmax = kmax;
+  const unsigned eb = (unsigned)((nens + ESMT_THREADS - 1) / ESMT_THREADS);
+  const bool narrow = !g_esmt_force_wide && cells < ESMT_NARROW_CELLS;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 block(ESMT_THREADS);
+  if (solve) {
+    const dim3 gf(eb, (unsigned)nz, (unsigned)((kmax + es::MODES - 1) / es::MODES)), gt(eb, (unsigned)kmax);
+    if (narrow) {
+      hipLaunchKernelGGL((esmt_forward_kernel<unsigned>), gf, block, 0, s, A);
+      hipLaunchKernelGGL((esmt_thomas_kernel<unsigned>), gt, block, 0, s, A);
+    } else {
+      hipLaunchKernelGGL((esmt_forward_kernel<long long>), gf, block, 0, s, A);
+      hipLaunchKernelGGL((esmt_thomas_kernel<long long>), gt, block, 0, s, A);
+    }
+  }
+  const dim3 gi(eb, (unsigned)nz, (unsigned)((nx + es::XB - 1) / es::XB));
+  if (narrow) hipLaunchKernelGGL((esmt_inverse_kernel<unsigned>), gi, block, 0, s, A);
+  else hipLaunchKernelGGL((esmt_inverse_kernel<long long>), gi, block, 0, s, A);
+  return stats_launch_check(who);
+}

@@ -1173,3 +1173,119 @@ def ls_forcing(coupler, dt=None):
                                      (C.c_ubyte * len(tracers))(*positive) if tracers else None, P("density_dry"), P("water_vapor"),
                                      P("vertical_midpoint_height"), P("ls_wsub"), P("ls_temp_tend"), P("ls_qv_tend"), inc, P("ls_fcor"),
                                      P("ls_ug"), P("ls_vg"), dt, float(coupler.get_option("grav")), float(coupler.get_option("cp_d")), stream))
+
+
+# ---- explicit scalar momentum transport for 2-D CRMs (Tulich 2015; E3SM-MMF's use_MMF_ESMT): the large-scale u and v ride as two
+# passive scalars that take the linearised pressure-gradient force every CRM step.  Not part of the reference tree: the contract is this
+# project's (include/pam_amd_modules.h at pam_amd_esmt_pgf; numpy restatement: tests/esmt_ref.py)
+ESMT_SCALARS = ("esmt_u", "esmt_v")
+ESMT_PROFILES = (("esmt_rho_mean", "level mean of the total density [kg/m3]"), ("esmt_u_mean", "level mean of esmt_u / rho [m/s]"),
+                 ("esmt_v_mean", "level mean of esmt_v / rho [m/s]"), ("esmt_u_forcing", "GCM forcing of the scalar u [m/s2]"),
+                 ("esmt_v_forcing", "GCM forcing of the scalar v [m/s2]"), ("esmt_u_tend", "scalar momentum feedback, u [m/s2]"),
+                 ("esmt_v_tend", "scalar momentum feedback, v [m/s2]"))
+
+
+def esmt_init(coupler, kmax=None):
+    """Once, BEFORE Dycore.init (the dycore takes its tracer table when it is initialised): registers the tracers "esmt_u" and "esmt_v"
+    (not positive, adding no mass), the profiles of ESMT_PROFILES (nz,nens) zeroed, the tables "esmt_cos" and "esmt_sin" (nx) formed
+    on the host, and the workspace "esmt_workspace" (6 kmax nz nens doubles), and sets the option "esmt_kmax" (default nx // 2: every
+    wavenumber).  Refuses ny != 1: a 3-D CRM transports momentum itself."""
+    import numpy as np
+    from .coupler import endrun
+    lib = capi.load()
+    nz, ny, nx, nens = coupler.get_nz(), coupler.get_ny(), coupler.get_nx(), coupler.get_nens()
+    if ny != 1:
+        endrun("ERROR: esmt_init: explicit scalar momentum transport is for 2-D CRMs (ny == 1)")
+    if nx < 2 or nz < 2:
+        endrun("ERROR: esmt_init: nx and nz must be >= 2")
+    kmax = nx // 2 if kmax is None else int(kmax)
+    if not 0 <= kmax <= nx // 2:
+        endrun("ERROR: esmt_init: kmax must be in [0, nx // 2]")
+    dm = coupler.get_data_manager_device_readwrite()
+    if dm.entry_exists("esmt_cos"):
+        endrun("ERROR: esmt_init: called twice")
+    for n, d in zip(ESMT_SCALARS, ("large-scale u carried as a scalar [kg/m3 m/s]", "large-scale v carried as a scalar [kg/m3 m/s]")):
+        coupler.add_tracer(n, d, False, False)
+    for n, d in ESMT_PROFILES:
+        dm.register_and_allocate(n, d, (nz, nens), ("z", "nens"))
+        dm.get(n).zero_()
+    cos, sin = np.empty(nx), np.empty(nx)
+    check(lib.pam_amd_esmt_tables(nx, cos.ctypes.data, sin.ctypes.data))
+    for n, a in (("esmt_cos", cos), ("esmt_sin", sin)):
+        dm.register_and_allocate(n, "table of the transform along x", (nx,), ("x",))
+        dm.get(n).copy_(torch.from_numpy(a))
+    words = max(int(lib.pam_amd_esmt_workspace_doubles(nens, nz, kmax)), 1)
+    dm.register_and_allocate("esmt_workspace", "spectral coefficients and right-hand sides of the pressure solve", (words,))
+    coupler.set_option("esmt_kmax", kmax)
+
+
+def _esmt_ready(coupler, who):
+    from .coupler import endrun
+    if not coupler.option_exists("esmt_kmax"):
+        endrun("ERROR: %s: call esmt_init first" % who)
+    return coupler.get_data_manager_device_readwrite()
+
+
+def esmt_set(coupler, source="gcm"):
+    """Sets both scalars to rho times a profile: source "gcm" takes "gcm_uvel" / "gcm_vvel"; source "crm" takes the level means of uvel
+    and vvel (pam_amd_msa_diagnose: the slot order every level mean of the project has)."""
+    from .coupler import endrun
+    dm = _esmt_ready(coupler, "esmt_set")
+    if source not in ("gcm", "crm"):
+        endrun("ERROR: esmt_set: source must be \"gcm\" or \"crm\"")
+    lib = capi.load()
+    nens, nx, ny, nz = coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz()
+    with torch.cuda.device(coupler.device):
+        stream = torch.cuda.current_stream(coupler.device).cuda_stream
+        if source == "gcm":
+            src = [dm.get("gcm_uvel", readonly=True), dm.get("gcm_vvel", readonly=True)]
+        else:
+            u, v = dm.get("uvel", readonly=True), dm.get("vvel", readonly=True)
+            # the first two means of the table are not wanted: the tendencies of the feedback take them, and are written anew before use
+            rest = [dm.get("esmt_u_tend"), dm.get("esmt_v_tend")]
+            src = [dm.get("esmt_u_mean"), dm.get("esmt_v_mean")]
+            check(lib.pam_amd_msa_diagnose(nens, nx, ny, nz, _msa_table([u, v, None, None, u, v]), _msa_table(rest + src), stream))
+        check(lib.pam_amd_esmt_set(nens, nx, ny, nz, dm.get("density_dry", readonly=True).data_ptr(), dm.get("water_vapor", readonly=True).data_ptr(),
+                                   src[0].data_ptr(), src[1].data_ptr(), dm.get("esmt_u").data_ptr(), dm.get("esmt_v").data_ptr(), stream))
+
+
+def _esmt_diagnose(coupler, dm, tend, feedback):
+    lib = capi.load()
+    P = lambda n: dm.get(n, readonly=True).data_ptr()
+    gcm = (P("gcm_uvel"), P("gcm_vvel")) if tend else (None, None)
+    out = (dm.get(tend[0]).data_ptr(), dm.get(tend[1]).data_ptr()) if tend else (None, None)
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_esmt_diagnose(coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), P("density_dry"), P("water_vapor"),
+                                        P("esmt_u"), P("esmt_v"), dm.get("esmt_rho_mean").data_ptr(), dm.get("esmt_u_mean").data_ptr(),
+                                        dm.get("esmt_v_mean").data_ptr(), gcm[0], gcm[1],
+                                        float(coupler.get_option("gcm_physics_dt")) if tend else 1.0, 1 if feedback else 0, out[0], out[1],
+                                        torch.cuda.current_stream(coupler.device).cuda_stream))
+
+
+def esmt_compute_forcing(coupler):
+    """Once per GCM step: "esmt_x_forcing" = (gcm_x - M(esmt_x / rho)) / gcm_physics_dt, what the GCM applies to the scalars."""
+    _esmt_diagnose(coupler, _esmt_ready(coupler, "esmt_compute_forcing"), ("esmt_u_forcing", "esmt_v_forcing"), False)
+
+
+def esmt_compute_feedback(coupler):
+    """At the end of a GCM step: "esmt_x_tend" = (M(esmt_x / rho) - gcm_x) / gcm_physics_dt, the momentum tendency handed back."""
+    _esmt_diagnose(coupler, _esmt_ready(coupler, "esmt_compute_feedback"), ("esmt_u_tend", "esmt_v_tend"), True)
+
+
+def esmt_pgf(coupler, dt=None, forcing=True):
+    """Every CRM step, after the dycore and the sponge layer and before the SGS: pam_amd_esmt_diagnose, then pam_amd_esmt_pgf in place
+    on esmt_u and esmt_v with the wavenumbers 1 .. "esmt_kmax"; forcing: "esmt_x_forcing" is applied as well.  Nothing else is
+    written.  dt: default the option "crm_dt"."""
+    dm = _esmt_ready(coupler, "esmt_pgf")
+    lib = capi.load()
+    dt = float(coupler.get_option("crm_dt") if dt is None else dt)
+    _esmt_diagnose(coupler, dm, None, False)
+    P = lambda n: dm.get(n, readonly=True).data_ptr()
+    work = dm.get("esmt_workspace")
+    with torch.cuda.device(coupler.device):
+        check(lib.pam_amd_esmt_pgf(coupler.get_nens(), coupler.get_nx(), coupler.get_ny(), coupler.get_nz(), dm.get("esmt_u").data_ptr(),
+                                   dm.get("esmt_v").data_ptr(), P("wvel"), P("density_dry"), P("water_vapor"), P("vertical_midpoint_height"),
+                                   P("vertical_cell_dz"), P("esmt_rho_mean"), P("esmt_u_mean"), P("esmt_v_mean"),
+                                   P("esmt_u_forcing") if forcing else None, P("esmt_v_forcing") if forcing else None, P("esmt_cos"),
+                                   P("esmt_sin"), float(coupler.get_dx()), dt, int(coupler.get_option("esmt_kmax")), work.data_ptr(),
+                                   work.numel(), torch.cuda.current_stream(coupler.device).cuda_stream))

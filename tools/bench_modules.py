@@ -25,6 +25,9 @@ hyperdiffusion and msa_apply of the same run;
 members on Kessler's and on P3's field set, beside column_diagnostics and pam_amd_sgs_smag_coefficients of the same run;
 --only ice1m: the one-moment ice microphysics (pam_amd_ice1m_time_step) on a clear, a raining and snowing and a deep_fall state at the
 C2 grid and at C4's 32x1x60 grid with 8192 members, beside Kessler's timeStep and pam_amd_radiation_gray of the same run;
+--only esmt: explicit scalar momentum transport (esmt_pgf with every wavenumber and the forcing, with kmax = nx / 4, and the diagnose
+launch alone) at C4's 32x1x60 grid with 8192 members and at the 250x1x50 line with 2048 members, beside pam_amd_ls_forcing, msa_diagnose
+and one C4 dycore step of the same run;
 --only lsforcing: the large-scale forcing (pam_amd_ls_forcing with everything on, with the subsidence alone and without it, and
 pam_amd_ls_nudging) at the C2 grid and at C4's 32x1x60 grid with 8192 members on Kessler's field set, beside hyperdiffusion, msa_apply,
 msa_diagnose and one C2 dycore step of the same run;
@@ -1863,8 +1866,127 @@ def ice1m_timing(dev, warmup=3, n=11):
     return out
 
 
+def esmt_timing(dev, warmup=3, n=11):
+    """Explicit scalar momentum transport (modules.esmt_pgf: pam_amd_esmt_diagnose, then the three launches of pam_amd_esmt_pgf) at C4's
+    32x1x60 grid with 8192 members and at the reference's 250x1x50 line with 2048 members (25.6 M cells, enough to fill the device), 3
+    warm-up calls and the median of 11 event-timed calls each.  Rows: esmt_pgf with everything on (every wavenumber and the forcing),
+    with kmax = nx / 4, and the diagnose launch alone.  Bytes, counted as the kernels request them, per cell of a field with K = kmax:
+    diagnose 4 x 8 B (rho_d, rho_v and the two scalars); forward 8 B of wvel per block of 8 wavenumbers and 2 K / nx x 8 B written;
+    Thomas 16 K / nx x 8 B (wc and ws read, cp written and read back, the four right-hand sides written, read back and written again
+    as That); inverse 4 K / 8 x 8 B of That (a thread carries 8 cells and reads the four coefficients of every wavenumber once),
+    rho_d and rho_v read and both scalars read and written, 6 x 8 B.  The profiles and the tables are not counted.
+    pam_amd_ls_forcing (everything on, Kessler's field set) and msa_diagnose of the same run stand beside them as the yardsticks, and
+    one C4 dycore step at the same 8192 members for the share of a CRM step."""
+    import ctypes as C
+    import numpy as np
+    from pam_amd import PamCoupler, capi, modules
+    from pam_amd import idealized as idz
+    lib = capi.load()
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    def row(t, nbytes):
+        return {"ms": t[0], "min_ms": t[1], "max_ms": t[2], "bytes": nbytes, "GBps": nbytes / t[0] / 1e6,
+                "hbm_frac": nbytes / t[0] / 1e6 / bench.HBM_PEAK_GBS}
+
+    def per_cell(nx, K):
+        blocks = (K + 7) // 8
+        return {"diagnose": 32.0, "forward": 8.0 * blocks + 16.0 * K / nx, "thomas": 128.0 * K / nx, "inverse": 4.0 * K + 48.0}
+
+    def grid(nens, nx, nz, zint, label, out):
+        cells = nens * nx * nz
+        c = PamCoupler(dev)
+        for name, v in (("crm_dt", 2.0), ("grav", 9.80616), ("cp_d", 1004.64), ("gcm_physics_dt", 900.0)):
+            c.set_option(name, v)
+        c.allocate_coupler_state(nz, 1, nx, nens)
+        c.set_grid(nx * 1000.0, 1000.0, zint)
+        for t in ("water_vapor", "cloud_liquid", "precip_liquid"):
+            c.add_tracer(t, "", True, True)
+        c.set_option("micro", "kessler")
+        modules.esmt_init(c)
+        dm = c.get_data_manager_device_readwrite()
+        gen = torch.Generator(device=dev).manual_seed(0)
+        k = torch.arange(nz, dtype=torch.float64, device=dev)[:, None, None, None]
+        for name, scale in (("temp", 299.0 - 1.2 * k), ("density_dry", 1.15 * torch.exp(-k / 25.0)), ("water_vapor", 1.6e-2 * torch.exp(-k / 10.0)),
+                            ("cloud_liquid", 1.0e-4 + 0 * k), ("precip_liquid", 1.0e-5 + 0 * k)):
+            t = dm.get(name)
+            t.copy_((torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * 0.1 + 0.95) * scale)
+        for name in ("uvel", "vvel", "wvel"):
+            t = dm.get(name)
+            t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * 16.0 - 8.0)
+        dm.get("gcm_uvel").copy_((10.0 * torch.tanh(k / 12.0))[:, 0, 0, :].expand(nz, nens))
+        dm.get("gcm_vvel").copy_((-3.0 + 0.1 * k)[:, 0, 0, :].expand(nz, nens))
+        modules.esmt_set(c, "gcm")
+        dm.get("esmt_u").mul_(1.0 + 0.01 * torch.rand(dm.get("esmt_u").shape, generator=gen, dtype=torch.float64, device=dev))
+        modules.esmt_compute_forcing(c)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for tag, K in (("everything", nx // 2), ("kmax_quarter", nx // 4)):
+            c.set_option("esmt_kmax", K)
+            b = per_cell(nx, K)
+            out["esmt_pgf_" + tag + label] = row(timed(lambda: modules.esmt_pgf(c)), cells * sum(b.values()))
+            out["esmt_pgf_" + tag + label]["bytes_per_cell"] = dict(b, total=sum(b.values()))
+        c.set_option("esmt_kmax", nx // 2)
+        out["esmt_diagnose" + label] = row(timed(lambda: modules._esmt_diagnose(c, dm, None, False)), cells * 32.0)
+        assert all(bool(torch.isfinite(dm.get(t, readonly=True)).all()) for t in modules.ESMT_SCALARS)
+        # the yardsticks on the same grid: the large-scale forcing with everything on, and msa_diagnose
+        kk = np.arange(nz)
+        wsub = -0.01 * np.sin(np.pi * (kk + 0.5) / nz)[:, None] * np.where(np.arange(nens) % 2 == 0, 1.0, -1.0)[None, :]
+        rate = np.full(nz, 1.0 / 3600.0)
+        modules.ls_forcing_init(c, wsub=wsub, temp_tend=np.full(nz, -2.0e-5), qv_tend=np.full(nz, -1.0e-9), ug=np.full(nz, 7.0), vg=np.full(nz, -2.0),
+                                fcor=1.0e-4, nudge_temp=299.0 - 1.2 * kk, nudge_qv=1.4e-2 * np.exp(-kk / 10.0), nudge_u=np.zeros(nz),
+                                nudge_v=np.zeros(nz), nudge_rate_temp=rate, nudge_rate_qv=rate, nudge_rate_uv=rate)
+        P = lambda name: dm.get(name).data_ptr()
+        kessler = [dm.get(t) for t in ("water_vapor", "cloud_liquid", "precip_liquid")]
+        TR, POS = modules._ptr_table(kessler), (C.c_ubyte * 3)(1, 1, 1)
+        INC = (C.c_void_p * 4)(*[P(x) for x in modules.LS_INCREMENTS])
+        capi.check(lib.pam_amd_ls_nudging(nens, nx, 1, nz, modules._msa_table([dm.get(x) for x in modules.LS_NUDGE_FIELDS]),
+                                          (C.c_void_p * 4)(*[P(x) for x in modules.LS_TARGETS]), (C.c_void_p * 4)(*[P(x) for x in modules.LS_RATES]), 2.0,
+                                          INC, stream))
+        out["ls_forcing_everything" + label] = row(timed(lambda: capi.check(lib.pam_amd_ls_forcing(
+            nens, nx, 1, nz, P("uvel"), P("vvel"), P("temp"), 3, TR, POS, P("density_dry"), P("water_vapor"), P("vertical_midpoint_height"), P("ls_wsub"),
+            P("ls_temp_tend"), P("ls_qv_tend"), INC, P("ls_fcor"), P("ls_ug"), P("ls_vg"), 2.0, 9.80616, 1004.64, stream))), 6 * cells * 16.0 + cells * 8.0)
+        c.set_option("crm_accel_factor", 2.0)
+        modules.msa_init(c)
+        mfields, msave, _, _ = modules._msa_arrays(c)
+        MF, MS = modules._msa_table(mfields), modules._msa_table(msave)
+        nf = sum(1 for f in mfields if f is not None)
+        out["msa_diagnose" + label] = row(timed(lambda: capi.check(lib.pam_amd_msa_diagnose(nens, nx, 1, nz, MF, MS, stream))), nf * cells * 8.0)
+        for tag in ("esmt_pgf_everything", "esmt_pgf_kmax_quarter", "esmt_diagnose"):
+            for y in ("ls_forcing_everything", "msa_diagnose"):
+                out["%s_vs_%s_frac%s" % (tag, y, label)] = out[tag + label]["hbm_frac"] / out[y + label]["hbm_frac"]
+        del c, dm, kessler, mfields, msave
+        lib.pam_amd_modules_finalize()
+        torch.cuda.empty_cache()
+
+    out = {"esmt_grid": "8192 x 32x1x60 (C4) and 2048 x 250x1x50 (the reference's line)",
+           "esmt_method": "%d warm-up calls, median of %d event-timed calls" % (warmup, n), "hbm_peak_GBps": bench.HBM_PEAK_GBS}
+    grid(8192, 32, 60, idz.l60_interfaces(), "_c4", out)
+    grid(2048, 250, 50, idz.uniform_interfaces(50, 20000.0), "_line", out)
+    job = bench.Job("c4", bench.parse_args(["--config", "c4"]), dev, 0, 1, nens_override=8192)
+    _, elapsed, _ = job.timed(3, 2)
+    out["c4_dycore_step_ms"] = elapsed / 3 * 1e3
+    for tag in ("esmt_pgf_everything", "esmt_pgf_kmax_quarter"):
+        out[tag + "_share_of_c4_dycore_step"] = out[tag + "_c4"]["ms"] / out["c4_dycore_step_ms"]
+    return out
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
+    if sys.argv[1:] == ["--only", "esmt"]:
+        print(json.dumps(esmt_timing(dev)))
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "ice1m"]:
         print(json.dumps(ice1m_timing(dev)))
         sys.exit(0)
