@@ -73,6 +73,9 @@
 #define PAM_SGS_CLASS SGSSmagorinsky      // the driver holds both SGS classes and picks at run time (--sgs-smag)
 #include "physics/sgs/smag_amd/SGS.h"
 #undef PAM_SGS_CLASS
+#define PAM_SGS_CLASS SGSTke              // the third: the prognostic-TKE closure (--sgs-tke)
+#include "physics/sgs/tke_amd/SGS.h"
+#undef PAM_SGS_CLASS
 #include "physics/radiation/forced_amd/radiation.h"
 #define PAM_RAD_CLASS RadiationGray     // the driver holds both Radiation classes and picks at run time (--radiation-gray)
 #include "physics/radiation/gray_amd/radiation.h"
@@ -320,7 +323,7 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // ------------------------------------------------------------------------------------------------------------------------------
 //   driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] [--validate] [--diag PATH] [--stats PATH] [--edges PATH]
 //          [--radiation RAD_NX RAD_NY PATH] [--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]]
-//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--esmt [KMAX]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--micro-ice] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
+//          [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-tke CS CK] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--esmt [KMAX]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--micro-ice] [--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH]
 //          [--flux-profiles PATH] <output.bin | ->
 // The reference driver's OWN flow from its own kind of input file (standalone/mmf_simplified/driver.cpp:79-297; the flat
 // `key : value` YAML files under standalone/mmf_simplified/inputs/): sim_time, crm_nx, crm_ny, nens, xlen, ylen, dt_gcm, dt_crm_phys,
@@ -423,6 +426,11 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              place of the none class's, its timeStep every CRM step after the sponge layer, the surface friction and the
 //                              hyperdiffusion and before the microphysics.  With --surface-friction the fluxes that module computes are
 //                              the lower boundary condition of uvel and vvel; composes with every other flag
+//   --sgs-tke CS CK            the native prognostic-TKE closure (physics/sgs/tke_amd/SGS.h) in the same slot, and not with --sgs-smag: its
+//                              init registers the tracer "tke" before the dycore's, so the dycore transports it; one "sgs tke:" line per
+//                              output step with the mass-weighted mean of tke / rho, the extremes of tke = rho e and the greatest tk, from
+//                              the field diagnostics' scan (nothing is copied to the host).  --sgs-moist, --sfc-fluxes and --surface
+//                              accept either closure (the options are then sgs_tke_moist and sgs_tke_surface_fluxes).
 //   --sgs-moist                with --sgs-smag: option sgs_smag_moist, so the closure's stability carries the condensate loading and is
 //                              the saturated one inside cloud (the species of option "micro")
 //   --surface SST [DEPTH]      with --sgs-smag, and not with --sfc-fluxes: bulk surface fluxes over a slab ocean (modules/surface_fluxes.h).
@@ -493,10 +501,10 @@ struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };   
 //                              prof_flux_v and prof_tke, printed with %.17g; nothing else of the run changes.
 struct YamlModules {
   bool sat_adjust = false, surface_friction = false, radiation = false, validate = false, accelerate = false, accel_uv = false;
-  bool micro_ice = false, vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false, shortwave = false, surface = false, ls_forcing = false, coriolis = false, esmt = false;
+  bool micro_ice = false, vt = false, vt_u = false, hyperdiff = false, handoff = false, sgs_smag = false, sgs_tke = false, sgs_moist = false, sfc_fluxes = false, radiation_gray = false, shortwave = false, surface = false, ls_forcing = false, coriolis = false, esmt = false;
   int radiation_gray_every = 1, esmt_kmax = -1;
   double sw_coszen = 1, sw_albedo = 0.07;
-  double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0, sfc_shf = 0, sfc_lhf = 0, surface_sst = 300, surface_depth = 0, ls_fcor = 0;
+  double hyperdiff_tau = 0, sgs_cs = 0, sgs_prandtl = 0, sgs_ck = 0, sfc_shf = 0, sfc_lhf = 0, surface_sst = 300, surface_depth = 0, ls_fcor = 0;
   int handoff_rad_nx = 0, handoff_rad_ny = 0;
   std::string handoff_path;
   double tau = 0, bflx = 0, accel_factor = 0, accel_max_ttend = 5.0, vt_rate = 0, vt_limit = 0.05;
@@ -604,16 +612,25 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     MicrophysicsIce micro_ice;
     SGS sgs;
     SGSSmagorinsky sgs_smag;
+    SGSTke sgs_tke;
     Radiation rad;
     RadiationGray rad_gray;
     if (mods.micro_ice) micro_ice.init(coupler);                             // --micro-ice: the native scheme with ice in the microphysics slot
     else micro.init(coupler);                                                // driver.cpp:189
-    if (mods.sgs_smag) {                                                     // --sgs-smag: the native closure in the SGS slot
-      coupler.set_option<real>("sgs_smag_cs", mods.sgs_cs);
-      coupler.set_option<real>("sgs_smag_prandtl", mods.sgs_prandtl);
-      coupler.set_option<bool>("sgs_smag_moist", mods.sgs_moist);
-      coupler.set_option<bool>("sgs_smag_surface_fluxes", mods.sfc_fluxes || mods.surface);
-      sgs_smag.init(coupler);
+    if (mods.sgs_smag || mods.sgs_tke) {                                     // --sgs-smag / --sgs-tke: a native closure in the SGS slot
+      if (mods.sgs_smag) {
+        coupler.set_option<real>("sgs_smag_cs", mods.sgs_cs);
+        coupler.set_option<real>("sgs_smag_prandtl", mods.sgs_prandtl);
+        coupler.set_option<bool>("sgs_smag_moist", mods.sgs_moist);
+        coupler.set_option<bool>("sgs_smag_surface_fluxes", mods.sfc_fluxes || mods.surface);
+        sgs_smag.init(coupler);
+      } else {                                                               // registers the tracer "tke" before the dycore takes its table
+        coupler.set_option<real>("sgs_tke_cs", mods.sgs_cs);
+        coupler.set_option<real>("sgs_tke_ck", mods.sgs_ck);
+        coupler.set_option<bool>("sgs_tke_moist", mods.sgs_moist);
+        coupler.set_option<bool>("sgs_tke_surface_fluxes", mods.sfc_fluxes || mods.surface);
+        sgs_tke.init(coupler);
+      }
       if (mods.sfc_fluxes) {                                                 // --sfc-fluxes: the two entries, uniformly, once
         auto &sdm = coupler.get_data_manager_device_readwrite();
         std::vector<real> h((size_t)crm_ny * crm_nx * nens);
@@ -648,7 +665,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       if (hipMemcpy(tend.data(), h.data(), h.size() * sizeof(real), hipMemcpyHostToDevice) != hipSuccess) endrun("memcpy");
     }
     std::printf("Dycore: %s\nMicro : %s\nSGS   : %s\n\n", dycore.dycore_name(), (mods.micro_ice ? micro_ice.micro_name() : micro.micro_name()).c_str(),
-                mods.sgs_smag ? sgs_smag.sgs_name().c_str() : "none (SHOC is out of scope)");   // driver.cpp:203-205
+                mods.sgs_smag ? sgs_smag.sgs_name().c_str() : mods.sgs_tke ? sgs_tke.sgs_name().c_str() : "none (SHOC is out of scope)");   // driver.cpp:203-205
     std::printf("crm_nx:   %d\ncrm_ny:   %d\ncrm_nz:   %d\nxlen (m): %g\nylen (m): %g\n", crm_nx, crm_ny, crm_nz, xlen, ylen);
     if (apply_gcm_forcing) std::printf("apply_gcm_forcing: not run (modules::gcm_forcing works on P3's tracer set; P3 is out of scope)\n");
     if (!idealized) initialize_from_supercell_column(zint, coupler);        // driver.cpp:220-222
@@ -810,6 +827,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
         if (mods.surface_friction) coupler.run_module("surface_friction", modules::compute_surface_friction);
         if (mods.hyperdiff) coupler.run_module("hyperdiffusion", [](pam::PamCoupler &c) { modules::hyperdiffusion(c); });
         if (mods.sgs_smag) coupler.run_module("sgs", [&](pam::PamCoupler &c) { sgs_smag.timeStep(c); });
+        if (mods.sgs_tke) coupler.run_module("sgs", [&](pam::PamCoupler &c) { sgs_tke.timeStep(c); });
         if (dbg.sync && hipDeviceSynchronize() != hipSuccess) endrun("device error");
         if (!dbg.no_micro && mods.micro_ice) {
           coupler.run_module("micro", [&](pam::PamCoupler &c) { micro_ice.timeStep(c); });
@@ -864,6 +882,14 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
               items.push_back({n, 0, dm.get<real const, 3>(n).data(), (long long)crm_ny * crm_nx * nens, items.size()});
             auto s3 = pam::diagnostics::scan(items, 0);
             std::printf("surface: etime %g , shf %.9g , lhf %.9g , sfc_temp %.17g\n", etime_gcm, s3[0].mean(), s3[1].mean(), s3[2].mean());
+          }
+          if (mods.sgs_tke) {                                                // the same scan, nothing copied to the host: e_mean = S tke / S rho (the
+            const long long cells = (long long)crm_ny * crm_nx * nens * crm_nz;   // mass-weighted mean of tke / rho), the extremes of tke = rho e, and of tk
+            std::vector<pam::diagnostics::Item> items;
+            for (char const *n : {"tke", "density_dry", "water_vapor", "tk"}) items.push_back({n, 0, dm.get<real const, 4>(n).data(), cells, items.size()});
+            auto s4 = pam::diagnostics::scan(items, 0);
+            std::printf("sgs tke: etime %g , e_mean %.9g , tke_min %.9g , tke_max %.9g , tk_max %.9g\n", etime_gcm,
+                        s4[0].mean() / (s4[1].mean() + s4[2].mean()), s4[0].vmin[0], s4[0].vmax[0], s4[3].vmax[0]);
           }
           if (mods.ls_forcing) {                                             // the same scan: the domain means of the winds, and temp of level 0
             const long long level = (long long)crm_ny * crm_nx * nens;
@@ -1110,6 +1136,7 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
       std::printf("{\"sgs_smag_moist\": %s, \"sgs_smag_surface_fluxes\": %s, \"sfc_shf\": %.17g, \"sfc_lhf\": %.17g}\n",
                   mods.sgs_moist ? "true" : "false", mods.sfc_fluxes ? "true" : "false", mods.sfc_shf, mods.sfc_lhf);
     if (mods.sgs_smag) std::printf("{\"sgs_smag_cs\": %.17g, \"sgs_smag_prandtl\": %.17g}\n", mods.sgs_cs, mods.sgs_prandtl);
+    if (mods.sgs_tke) std::printf("{\"sgs_tke_cs\": %.17g, \"sgs_tke_ck\": %.17g}\n", mods.sgs_cs, mods.sgs_ck);
     if (mods.hyperdiff) std::printf("{\"hyperdiff_timescale\": %.17g}\n", mods.hyperdiff_tau);
     if (mods.accelerate)
       std::printf("{\"accel_factor\": %.9g, \"accel_uv\": %s, \"accel_max_ttend\": %.9g, \"accelerated_steps\": %d, \"ceased_gcm_steps\": %d}\n",
@@ -1182,6 +1209,7 @@ int main(int argc, char **argv) {
         const std::string n(b + 1 < argc - 1 ? argv[b + 1] : "");                // the optional ALBEDO: an argument that is a number
         if (!n.empty() && n.find_first_not_of("0123456789.eE+") == std::string::npos) mods.sw_albedo = std::atof(argv[++b]);
       }
+      else if (o == "--sgs-tke" && b + 2 < argc - 1) { mods.sgs_tke = true; mods.sgs_cs = std::atof(argv[++b]); mods.sgs_ck = std::atof(argv[++b]); }
       else if (o == "--sgs-moist") mods.sgs_moist = true;
       else if (o == "--micro-ice") mods.micro_ice = true;
       else if (o == "--sfc-fluxes" && b + 2 < argc - 1) { mods.sfc_fluxes = true; mods.sfc_shf = std::atof(argv[++b]); mods.sfc_lhf = std::atof(argv[++b]); }
@@ -1208,14 +1236,16 @@ int main(int argc, char **argv) {
       else if (o == "--flux-profiles" && b + 1 < argc - 1) mods.flux_profiles = argv[++b];
       else die("usage: driver --yaml <input.yaml> [--nens N] [--steps S] [--check] [--sat-adjust] [--surface-friction TAU BFLX] "
                "[--validate] [--diag PATH] [--stats PATH] [--edges PATH] [--radiation RAD_NX RAD_NY PATH] "
-               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--esmt [KMAX]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--micro-ice] "
+               "[--accelerate A [--accel-uv] [--accel-max-ttend X]] [--vt RATE PATH [--vt-u] [--vt-limit L]] [--hyperdiff TAU] [--sgs-smag CS PRANDTL] [--sgs-tke CS CK] [--sgs-moist] [--sfc-fluxes SHF LHF] [--surface SST [DEPTH]] [--ls-forcing PATH [--coriolis F]] [--esmt [KMAX]] [--radiation-gray [EVERY]] [--shortwave COSZEN [ALBEDO]] [--micro-ice] "
                "[--gcm-handoff RAD_NX RAD_NY PATH] [--column-diag PATH] [--flux-profiles PATH] <output.bin | ->");
     }
     if (mods.radiation_gray && mods.radiation) die("--radiation-gray and --radiation both fill the one radiation slot: give one of them");
     if (mods.radiation_gray && mods.radiation_gray_every < 1) die("--radiation-gray EVERY must be >= 1");
     if (mods.shortwave && !mods.radiation_gray) die("--shortwave COSZEN [ALBEDO] needs --radiation-gray [EVERY]: the sun belongs to the native scheme");
-    if ((mods.sgs_moist || mods.sfc_fluxes) && !mods.sgs_smag) die("--sgs-moist and --sfc-fluxes need --sgs-smag CS PRANDTL");
-    if (mods.surface && !mods.sgs_smag) die("--surface SST [DEPTH] needs --sgs-smag CS PRANDTL: the closure is what takes the fluxes up");
+    if (mods.sgs_smag && mods.sgs_tke) die("--sgs-smag and --sgs-tke both stand in the SGS slot: give one of them");
+    if (mods.sgs_tke && (!(mods.sgs_cs > 0) || !(mods.sgs_ck > 0))) die("--sgs-tke CS CK needs CS > 0 and CK > 0");
+    if ((mods.sgs_moist || mods.sfc_fluxes) && !mods.sgs_smag && !mods.sgs_tke) die("--sgs-moist and --sfc-fluxes need --sgs-smag CS PRANDTL or --sgs-tke CS CK");
+    if (mods.surface && !mods.sgs_smag && !mods.sgs_tke) die("--surface SST [DEPTH] needs --sgs-smag CS PRANDTL or --sgs-tke CS CK: the closure is what takes the fluxes up");
     if (mods.coriolis && !mods.ls_forcing) die("--coriolis F needs --ls-forcing PATH with the rows ug and vg: the force acts about a geostrophic wind");
     if (mods.surface && mods.sfc_fluxes) die("--surface and --sfc-fluxes both fill sfc_shf and sfc_lhf: give one of them");
     if (mods.surface && (!(mods.surface_sst > 0) || mods.surface_depth < 0)) die("--surface SST [DEPTH] needs SST > 0 K and DEPTH >= 0 m");

@@ -730,6 +730,59 @@ int pam_amd_sgs_smag_diffuse_fluxes(int nens, int nx, int ny, int nz, double *uv
                                     const double *zint, const double *zmid, const double *sfc_flx_u, const double *sfc_flx_v, double dt,
                                     double grav, double cp_d, const double *sfc_shf, const double *sfc_lhf, double latvap, void *stream);
 
+/* The prognostic-TKE (1.5-order, Deardorff 1980) closure: a further instance of the coefficient walk above.  The SGS turbulence energy
+ * lives in the tracer "tke" as PAM stores it, rho e in (nz,ny,nx,nens) with rho = rho_d + rho_v, the frozen rho the solve uses.  The two
+ * entry points step it IN PLACE by shear production, buoyancy and dissipation and write tk and tkh; pam_amd_sgs_smag_diffuse /
+ * pam_amd_sgs_smag_diffuse_fluxes then run unchanged with tke standing in the tracer table like any tracer.  The four Smagorinsky entry
+ * points, their bits and their compiled code are unchanged.  Restated in tests/sgs_tke_ref.py and held bit for bit.
+ *
+ * Per cell, every operation rounded on its own, no fma, IEEE divisions and roots, parentheses give the order; every comparison is written
+ * so that a NaN takes the else arm and then goes on through the arithmetic:
+ *     rho = rho_d + rho_v;  x = tke / rho;  e0 = x < 0 ? 0 : x;  se = sqrt(e0);  delta = zint(k+1) - zint(k)
+ *     D  = Def2 of pam_amd_sgs_smag_coefficients, on the same centred / one-sided differences
+ *     N2 = pam_amd_sgs_tke_coefficients: that of pam_amd_sgs_smag_coefficients (on the virtual temperature);
+ *          pam_amd_sgs_tke_coefficients_moist: that of pam_amd_sgs_smag_coefficients_moist (loading everywhere, saturated inside cloud)
+ *     if (N2 > 0) { ls = (0.76 se) / sqrt(N2);  lo = 0.1 delta;  m = ls < lo ? lo : ls;  l = m > delta ? delta : m }  else  l = delta
+ *     r = l / delta;  pri = 1 + 2 r;  ckl = ck l
+ *     ks = ckl se + seed
+ *     P = ks D;  B = (ks pri) N2;  s = P - B
+ *     e1 = e0 + dt s;  e1 = e1 < 0 ? 0 : e1
+ *     c = ce1 + ce2 r
+ *     e2 = e1 / (1 + ((dt c) se) / l)
+ *     tke = (e2 == x) ? tke : rho e2
+ *     tk = ckl sqrt(e2);  tkh = pri tk
+ * The host constants, formed in double in this order by every wrapper (Python and C++ give the same bits):
+ *     ce = ((ck ck) ck) / ((cs cs) (cs cs));  ce1 = (ce / 0.7) 0.19;  ce2 = (ce / 0.7) 0.51.
+ * Design points:
+ *   - The dissipation is linearised about the TKE at entry: sqrt(e0) stands in the denominator, not sqrt(e1).  The step is positive and
+ *     stable for any dt, and its neutral fixed point is ce e^1.5 / l = tk D exactly: with seed = 0 and N2 = 0 the closure settles on
+ *     Smagorinsky's tk = (cs delta)^2 sqrt(Def2) with the same cs, whatever dt is.  With sqrt(e1) instead the fixed point drifts with dt
+ *     (0.6 % off at dt = 10 s and Def2 = 1e-4, 24 % off at 60 s and Def2 = 1e-2).
+ *   - pri = 1 + 2 l / delta is tkh / tk: 3 where the flow is unstable or neutral (the project's prandtl = 1/3), tending to 1.2 at the
+ *     length floor.
+ *   - seed (1e-3 m2/s by default, SAM's value) lets TKE grow from exactly zero.
+ *   - tke is mixed by the existing solve with tkh, the tracer class, under a zero-flux boundary at both ends.  SAM mixes it with tk; tkh
+ *     is this contract's choice.
+ *   - A cell reads only its own tke; the neighbours D and N2 need belong to the winds and temp, which are not written.  So the update is
+ *     in place with no scratch, no LDS, no atomics; every element offset is 64 bits wide.
+ *   - dt == 0 keeps every bit of a non-negative tke.  A negative tke at entry counts as zero and is replaced.  A NaN in tke stays in its
+ *     cell; a NaN in a wind or temp reaches the cells whose differences read it, as in the Smagorinsky closure.
+ * Out of scope: horizontal SGS fluxes, a surface-layer length scale, SAM's LES grid length (dx dy dz)^(1/3), an SGS row in flux_profiles.
+ *
+ * PAM_AMD_EINVAL before the first HIP call for everything the two Smagorinsky coefficient entry points refuse (cs and prandtl apart, which
+ * are not arguments), and: a NULL tke; tke overlapping any input or output; ck or ce1 not finite and positive; ce2, seed or dt negative
+ * or not finite. */
+int pam_amd_sgs_tke_coefficients(int nens, int nx, int ny, int nz, const double *uvel, const double *vvel, const double *wvel,
+                                 const double *temp, const double *rho_d, const double *rho_v, double *tke, const double *zint,
+                                 const double *zmid, double dx, double dy, double dt, double grav, double cp_d, double ck, double ce1,
+                                 double ce2, double seed, double *tk, double *tkh, void *stream);
+int pam_amd_sgs_tke_coefficients_moist(int nens, int nx, int ny, int nz, const double *uvel, const double *vvel, const double *wvel,
+                                       const double *temp, const double *rho_d, const double *rho_v, double *tke, int num_cloud,
+                                       const double *const *cloud, int num_precip, const double *const *precip, const double *zint,
+                                       const double *zmid, double dx, double dy, double dt, double grav, double cp_d, double R_d, double R_v,
+                                       double cloud_threshold, double ck, double ce1, double ce2, double seed, double *tk, double *tkh,
+                                       void *stream);
+
 /* The native radiation scheme: a grey two-stream longwave (Schwarzschild) solve along every column, as idealised GCMs use it (Frierson,
  * Held and Zurita-Gotor 2006), with the optical depth built from the water the CRM carries -- the radiation that needs no external
  * library (as Kessler is the microphysics and Smagorinsky the SGS closure that need none).  Longwave only, one band, no scattering.  Not

@@ -12,4 +12,4 @@ from .modules import validate_fields  # noqa: F401
 from .modules import field_diagnostics  # noqa: F401
 from .micro import Microphysics, MicrophysicsIce  # noqa: F401
 from .vertical_interp import VerticalInterp  # noqa: F401
-from .physics import Radiation, RadiationNone, RadiationGray, SGSNone, SGSShoc, SGSSmagorinsky, MicrophysicsNone, MicrophysicsP3  # noqa: F401
+from .physics import Radiation, RadiationNone, RadiationGray, SGSNone, SGSShoc, SGSSmagorinsky, SGSTke, MicrophysicsNone, MicrophysicsP3  # noqa: F401

@@ -1,0 +1,121 @@
+// physics/sgs/tke_amd/SGS.h -- the native `SGS` plug-in (-DPAM_SGS=tke_amd): a prognostic-TKE (1.5-order, Deardorff 1980) closure over
+// the implicit vertical solve of smag_amd, with the duck-typed members of the reference's physics/sgs/*/SGS.h.  The method is not part of
+// the reference tree; the contract is this project's (include/pam_amd_modules.h at pam_amd_sgs_tke_coefficients).
+// The SGS turbulence energy lives in the tracer "tke" (rho e; positive, adds no mass), registered the way the reference's SHOC layer
+// registers it, so init runs BEFORE the dycore's and the dycore transports it.  Two calls of libpam_amd_awfl.so per step:
+// pam_amd_sgs_tke_coefficients steps "tke" in place by shear production, buoyancy and dissipation and fills "tk" and "tkh";
+// pam_amd_sgs_smag_diffuse mixes uvel, vvel, wvel, temp and EVERY registered tracer, tke among them, along the column and takes
+// "sfc_mom_flx_u/v" as the lower boundary condition of the horizontal winds.  density_dry is never written.
+// With option sgs_tke_moist the coefficients come from pam_amd_sgs_tke_coefficients_moist (the species follow option "micro" as in
+// smag_amd: kessler: cloud_liquid / precip_liquid; p3: cloud_water, ice / rain; ice1m: cloud_liquid, cloud_ice / precip_liquid,
+// precip_ice; none: no species).  With option sgs_tke_surface_fluxes the solve is pam_amd_sgs_smag_diffuse_fluxes, which takes "sfc_shf"
+// and "sfc_lhf" (W/m2, positive upward) into row 0 of temp and of the vapour.
+//   options read:  crm_dt, grav, cp_d, sgs_tke_cs, sgs_tke_ck, sgs_tke_seed, sgs_tke_moist, sgs_tke_surface_fluxes; moist: micro, R_d,
+//                  R_v, sgs_tke_cloud_threshold; surface fluxes: latvap where it exists (2501000.0 otherwise)
+//   options set by init:  "sgs" = "tke"; sgs_tke_cs = 0.2, sgs_tke_ck = 0.1, sgs_tke_seed = 1e-3, sgs_tke_moist = false,
+//                  sgs_tke_surface_fluxes = false and sgs_tke_cloud_threshold = 0.0 unless present
+//   the dissipation constants: ce = ((ck ck) ck) / ((cs cs) (cs cs)), ce1 = (ce / 0.7) 0.19, ce2 = (ce / 0.7) 0.51, formed in this order
+#pragma once
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "pam_coupler.h"
+#include "pam_amd_awfl.h"
+#include "pam_amd_modules.h"
+
+#ifndef PAM_SGS_CLASS
+#define PAM_SGS_CLASS SGS      // a driver that holds several SGS classes names each of them before the include
+#endif
+
+class PAM_SGS_CLASS {
+  static void chk(int rc) { if (rc) endrun(pam_amd_awfl_last_error()); }
+
+ public:
+  PAM_SGS_CLASS() {}
+  static int constexpr get_num_tracers() { return 1; }
+
+  // each operation rounded on its own, whatever the compiler's contraction default is
+  static void constants(double cs, double ck, double &ce, double &ce1, double &ce2) {
+    volatile double k2 = ck * ck, s2 = cs * cs;
+    volatile double k3 = k2 * ck, s4 = s2 * s2;
+    volatile double c = k3 / s4;
+    volatile double q = c / 0.7;
+    ce = c;
+    ce1 = q * 0.19;
+    ce2 = q * 0.51;
+  }
+
+  void init(pam::PamCoupler &coupler) {
+    int nx = coupler.get_nx(), ny = coupler.get_ny(), nz = coupler.get_nz(), nens = coupler.get_nens();
+    auto &dm = coupler.get_data_manager_device_readwrite();
+    auto names = coupler.get_tracer_names();
+    if (std::find(names.begin(), names.end(), std::string("tke")) == names.end())     // positive, adds no mass; zero-filled
+      coupler.add_tracer("tke", "Turbulent Kinetic Energy (m^2/s^2)", true, false);
+    // allocations are zero-filled
+    if (!dm.entry_exists("tk")) dm.register_and_allocate<real>("tk", "Eddy coefficient for momentum [m2/s]", {nz, ny, nx, nens}, {"z", "y", "x", "nens"});
+    if (!dm.entry_exists("tkh")) dm.register_and_allocate<real>("tkh", "Eddy coefficent for heat [m2/s]", {nz, ny, nx, nens}, {"z", "y", "x", "nens"});
+    if (!dm.entry_exists("sfc_mom_flx_u")) dm.register_and_allocate<real>("sfc_mom_flx_u", "Surface flux of U-momentum", {ny, nx, nens}, {"y", "x", "nens"});
+    if (!dm.entry_exists("sfc_mom_flx_v")) dm.register_and_allocate<real>("sfc_mom_flx_v", "Surface flux of V-momentum", {ny, nx, nens}, {"y", "x", "nens"});
+    coupler.set_option<std::string>("sgs", "tke");
+    if (!coupler.option_exists("sgs_tke_cs")) coupler.set_option<real>("sgs_tke_cs", 0.2);
+    if (!coupler.option_exists("sgs_tke_ck")) coupler.set_option<real>("sgs_tke_ck", 0.1);
+    if (!coupler.option_exists("sgs_tke_seed")) coupler.set_option<real>("sgs_tke_seed", 1e-3);
+    if (!coupler.option_exists("sgs_tke_moist")) coupler.set_option<bool>("sgs_tke_moist", false);
+    if (!coupler.option_exists("sgs_tke_surface_fluxes")) coupler.set_option<bool>("sgs_tke_surface_fluxes", false);
+    if (!coupler.option_exists("sgs_tke_cloud_threshold")) coupler.set_option<real>("sgs_tke_cloud_threshold", 0.0);
+    if (coupler.get_option<bool>("sgs_tke_surface_fluxes")) {             // the reference's names and descriptions (shoc/SGS.h:115-116)
+      if (!dm.entry_exists("sfc_shf")) dm.register_and_allocate<real>("sfc_shf", "input surface sensible heat flux [W/m2]", {ny, nx, nens}, {"y", "x", "nens"});
+      if (!dm.entry_exists("sfc_lhf")) dm.register_and_allocate<real>("sfc_lhf", "input surface latent heat flux [W/m2]", {ny, nx, nens}, {"y", "x", "nens"});
+    }
+  }
+
+  void timeStep(pam::PamCoupler &coupler) {
+    int nx = coupler.get_nx(), ny = coupler.get_ny(), nz = coupler.get_nz(), nens = coupler.get_nens();
+    real dt = coupler.get_option<real>("crm_dt"), grav = coupler.get_option<real>("grav"), cp_d = coupler.get_option<real>("cp_d");
+    real cs = coupler.get_option<real>("sgs_tke_cs"), ck = coupler.get_option<real>("sgs_tke_ck"), seed = coupler.get_option<real>("sgs_tke_seed");
+    bool moist = coupler.get_option<bool>("sgs_tke_moist"), fluxes = coupler.get_option<bool>("sgs_tke_surface_fluxes");
+    double ce, ce1, ce2;
+    constants(cs, ck, ce, ce1, ce2);
+    auto &dm = coupler.get_data_manager_device_readwrite();
+    real *uvel = dm.get<real, 4>("uvel").data(), *vvel = dm.get<real, 4>("vvel").data(), *wvel = dm.get<real, 4>("wvel").data();
+    real *temp = dm.get<real, 4>("temp").data(), *tk = dm.get<real, 4>("tk").data(), *tkh = dm.get<real, 4>("tkh").data();
+    real *tke = dm.get<real, 4>("tke").data();
+    real const *rho_d = dm.get<real const, 4>("density_dry").data(), *rho_v = dm.get<real const, 4>("water_vapor").data();
+    real const *zint = dm.get<real const, 2>("vertical_interface_height").data();
+    real const *zmid = dm.get<real const, 2>("vertical_midpoint_height").data();
+    real const *flx_u = dm.get<real const, 3>("sfc_mom_flx_u").data(), *flx_v = dm.get<real const, 3>("sfc_mom_flx_v").data();
+    std::vector<double *> tracers;
+    for (auto &n : coupler.get_tracer_names()) tracers.push_back(dm.get<real, 4>(n).data());
+    if (moist) {
+      std::string micro = coupler.option_exists("micro") ? coupler.get_option<std::string>("micro") : std::string("none");
+      std::vector<std::string> cloud_names, precip_names;
+      if (micro == "kessler") { cloud_names = {"cloud_liquid"}; precip_names = {"precip_liquid"}; }
+      else if (micro == "p3") { cloud_names = {"cloud_water", "ice"}; precip_names = {"rain"}; }
+      else if (micro == "ice1m") { cloud_names = {"cloud_liquid", "cloud_ice"}; precip_names = {"precip_liquid", "precip_ice"}; }
+      else if (micro != "none") endrun("ERROR: sgs: the moist branch knows the species of micro = kessler, p3 and none");
+      std::vector<const double *> cloud, precip;
+      for (auto &n : cloud_names) cloud.push_back(dm.get<real const, 4>(n).data());
+      for (auto &n : precip_names) precip.push_back(dm.get<real const, 4>(n).data());
+      chk(pam_amd_sgs_tke_coefficients_moist(nens, nx, ny, nz, uvel, vvel, wvel, temp, rho_d, rho_v, tke, (int)cloud.size(), cloud.data(),
+                                             (int)precip.size(), precip.data(), zint, zmid, coupler.get_dx(), coupler.get_dy(), dt, grav, cp_d,
+                                             coupler.get_option<real>("R_d"), coupler.get_option<real>("R_v"),
+                                             coupler.get_option<real>("sgs_tke_cloud_threshold"), ck, ce1, ce2, seed, tk, tkh, nullptr));
+    } else {
+      chk(pam_amd_sgs_tke_coefficients(nens, nx, ny, nz, uvel, vvel, wvel, temp, rho_d, rho_v, tke, zint, zmid, coupler.get_dx(), coupler.get_dy(),
+                                       dt, grav, cp_d, ck, ce1, ce2, seed, tk, tkh, nullptr));
+    }
+    if (fluxes) {
+      real const *shf = dm.get<real const, 3>("sfc_shf").data(), *lhf = dm.get<real const, 3>("sfc_lhf").data();
+      real latvap = coupler.option_exists("latvap") ? coupler.get_option<real>("latvap") : 2501000.0;
+      chk(pam_amd_sgs_smag_diffuse_fluxes(nens, nx, ny, nz, uvel, vvel, wvel, temp, (int)tracers.size(), tracers.data(), rho_d, rho_v, tk, tkh, zint,
+                                          zmid, flx_u, flx_v, dt, grav, cp_d, shf, lhf, latvap, nullptr));
+    } else {
+      chk(pam_amd_sgs_smag_diffuse(nens, nx, ny, nz, uvel, vvel, wvel, temp, (int)tracers.size(), tracers.data(), rho_d, rho_v, tk, tkh, zint, zmid,
+                                   flx_u, flx_v, dt, grav, cp_d, nullptr));
+    }
+  }
+
+  std::string sgs_name() const { return "tke"; }
+  void finalize(pam::PamCoupler &coupler) {}
+};

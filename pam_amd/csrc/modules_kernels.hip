@@ -3748,6 +3748,8 @@ extern "C" int pam_amd_flux_profiles(int nens, int nx, int ny, int nz, const dou
 // the reference tree; the contract is in include/pam_amd_modules.h and DESIGN.md section 8, its arithmetic in sgs_device.h.  Both
 // launches give one thread a (column, member), members across the lanes, so every load and store is a coalesced row of members:
 //   coefficients   the thread walks its column upward with the centre values of three levels in registers; tk and tkh only are written.
+//                  The prognostic-TKE closure (pam_amd_sgs_tke_coefficients / _moist) is the same walk with one coalesced load and one
+//                  store of the tracer tke per level more: a cell reads only its own tke, so the update is in place without scratch.
 //   solve          ONE launch: the thread solves the momentum class, then the heat class, then the tracer table of its own column, each
 //                  by the Thomas algorithm with d' in the field itself.  No other thread ever reads this column's rho_v, and the thread
 //                  itself has read rho_v(k) before the vapour's own d'(k) takes its place, so the vapour may stand anywhere in the table.
@@ -3798,6 +3800,42 @@ __global__ void __launch_bounds__(SGS_THREADS) sgs_coef_moist_kernel(int nens, i
 #pragma unroll
   for (int q = 0; q < sg::MAX_PRECIP; q++) precip[q] = W.precip[q];
   sg::coef_column_t<true>(f, cloud, precip, M, zint + e, zmid + e, level, nens, nx, ny, nz, j, i, e, P, tk, tkh);
+}
+
+// the prognostic-TKE closure: the same walk with tke (rho e) read and written in the thread's own cell, level by level, in place of
+// eddy(); the dry and the moist instance.  tke overlaps nothing else (the entry point refuses it)
+__global__ void __launch_bounds__(SGS_THREADS) sgs_tke_coef_kernel(int nens, int nx, int ny, int nz, long long level, SgsCoefFields F,
+                                                                   const double *__restrict__ zint, const double *__restrict__ zmid,
+                                                                   sg::CoefParams P, sg::TkeParams Q, double *__restrict__ tke,
+                                                                   double *__restrict__ tk, double *__restrict__ tkh) {
+  const long long t = (long long)blockIdx.x * SGS_THREADS + (long long)threadIdx.x;
+  if (t >= level) return;
+  const long long c = t / nens;
+  const int e = (int)(t - c * nens), j = (int)(c / nx), i = (int)(c - (long long)j * nx);
+  const double *f[6];
+#pragma unroll
+  for (int q = 0; q < 6; q++) f[q] = F.p[q];
+  const sg::MoistParams none{};
+  sg::coef_column_t<false, true>(f, nullptr, nullptr, none, zint + e, zmid + e, level, nens, nx, ny, nz, j, i, e, P, tk, tkh, &Q, tke);
+}
+
+__global__ void __launch_bounds__(SGS_THREADS) sgs_tke_coef_moist_kernel(int nens, int nx, int ny, int nz, long long level, SgsCoefFields F,
+                                                                         SgsMoistTables W, const double *__restrict__ zint,
+                                                                         const double *__restrict__ zmid, sg::CoefParams P, sg::MoistParams M,
+                                                                         sg::TkeParams Q, double *__restrict__ tke, double *__restrict__ tk,
+                                                                         double *__restrict__ tkh) {
+  const long long t = (long long)blockIdx.x * SGS_THREADS + (long long)threadIdx.x;
+  if (t >= level) return;
+  const long long c = t / nens;
+  const int e = (int)(t - c * nens), j = (int)(c / nx), i = (int)(c - (long long)j * nx);
+  const double *f[6], *cloud[sg::MAX_CLOUD], *precip[sg::MAX_PRECIP];
+#pragma unroll
+  for (int q = 0; q < 6; q++) f[q] = F.p[q];
+#pragma unroll
+  for (int q = 0; q < sg::MAX_CLOUD; q++) cloud[q] = W.cloud[q];
+#pragma unroll
+  for (int q = 0; q < sg::MAX_PRECIP; q++) precip[q] = W.precip[q];
+  sg::coef_column_t<true, true>(f, cloud, precip, M, zint + e, zmid + e, level, nens, nx, ny, nz, j, i, e, P, tk, tkh, &Q, tke);
 }
 
 // grid (ceil(ny nx nens / block)), block 64 (LDS: nz x 64 doubles of dynamic LDS) or 256 (workspace: ws is (nz,ny,nx,nens))
@@ -3853,14 +3891,26 @@ int sgs_check_sizes(const char *who, int nens, int nx, int ny, int nz) {
   if (((long long)nx * ny * nens + SGS_LDS_THREADS - 1) / SGS_LDS_THREADS > 0x7fffffffLL) return module_error(who, "ny x nx x nens exceeds the grid");
   return PAM_AMD_OK;
 }
-// the checks and the launch both coefficient entry points share; moist: the tables and the gas constants take part
+// what the prognostic-TKE entry points add to a coefficient call: the tracer, updated in place, and the constants of its step
+struct SgsTkeCall { double *tke; double dt, ck, ce1, ce2, seed; };
+bool sgs_non_negative(double v) { return std::isfinite(v) && v >= 0; }
+
+// the checks and the launch the coefficient entry points share; moist: the tables and the gas constants take part; K: the TKE closure
+// (cs and prandtl are then not looked at)
 int sgs_coefficients(const char *who, bool moist, int nens, int nx, int ny, int nz, const double *uvel, const double *vvel, const double *wvel,
                      const double *temp, const double *rho_d, const double *rho_v, int num_cloud, const double *const *cloud, int num_precip,
                      const double *const *precip, const double *zint, const double *zmid, double dx, double dy, double grav, double cp_d, double R_d,
-                     double R_v, double cloud_threshold, double cs, double prandtl, double *tk, double *tkh, void *stream) {
+                     double R_v, double cloud_threshold, double cs, double prandtl, double *tk, double *tkh, void *stream, const SgsTkeCall *K = nullptr) {
   if (int rc = sgs_check_sizes(who, nens, nx, ny, nz)) return rc;
   if (!uvel || !vvel || !wvel || !temp || !rho_d || !rho_v || !zint || !zmid || !tk || !tkh) return module_error(who, "null pointer");
-  if (!sgs_positive(dx) || !sgs_positive(dy) || !sgs_positive(grav) || !sgs_positive(cp_d) || !sgs_positive(cs) || !sgs_positive(prandtl))
+  if (K) {
+    if (!K->tke) return module_error(who, "null pointer");
+    if (!sgs_positive(dx) || !sgs_positive(dy) || !sgs_positive(grav) || !sgs_positive(cp_d))
+      return module_error(who, "dx, dy, grav and cp_d must be finite and positive");
+    if (!sgs_positive(K->ck) || !sgs_positive(K->ce1)) return module_error(who, "ck and ce1 must be finite and positive");
+    if (!sgs_non_negative(K->ce2) || !sgs_non_negative(K->seed) || !sgs_non_negative(K->dt))
+      return module_error(who, "ce2, seed and dt must be finite and >= 0");
+  } else if (!sgs_positive(dx) || !sgs_positive(dy) || !sgs_positive(grav) || !sgs_positive(cp_d) || !sgs_positive(cs) || !sgs_positive(prandtl))
     return module_error(who, "dx, dy, grav, cp_d, cs and prandtl must be finite and positive");
   if (moist) {
     if (num_cloud < 0 || num_cloud > sg::MAX_CLOUD) return module_error(who, "num_cloud must be in [0, 4]");
@@ -3884,20 +3934,29 @@ int sgs_coefficients(const char *who, bool moist, int nens, int nx, int ny, int 
   }
   spans.push_back({tk, cells, true});
   spans.push_back({tkh, cells, true});
+  if (K) spans.push_back({K->tke, cells, true});
   if (spans_overlap(spans)) return module_error(who, "an output overlaps an input or another output");
   if (int rc = require_device(who)) return rc;
   const SgsCoefFields F{{uvel, vvel, wvel, temp, rho_d, rho_v}};
   const sg::CoefParams P{sg::twice(dx), sg::twice(dy), grav, sg::lapse(grav, cp_d), cs, prandtl};
+  const sg::TkeParams Q = K ? sg::TkeParams{K->dt, K->ck, K->ce1, K->ce2, K->seed} : sg::TkeParams{};
   const dim3 grid((unsigned)((level + SGS_THREADS - 1) / SGS_THREADS)), block(SGS_THREADS);
   if (!moist) {
-    hipLaunchKernelGGL(sgs_coef_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, ny, nz, level, F, zint, zmid, P, tk, tkh);
+    if (K)
+      hipLaunchKernelGGL(sgs_tke_coef_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, ny, nz, level, F, zint, zmid, P, Q, K->tke, tk, tkh);
+    else
+      hipLaunchKernelGGL(sgs_coef_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, ny, nz, level, F, zint, zmid, P, tk, tkh);
     return stats_launch_check(who);
   }
   SgsMoistTables W;
   for (int i = 0; i < sg::MAX_CLOUD; i++) W.cloud[i] = i < num_cloud ? cloud[i] : nullptr;
   for (int i = 0; i < sg::MAX_PRECIP; i++) W.precip[i] = i < num_precip ? precip[i] : nullptr;
   const sg::MoistParams M{R_d, R_v, cp_d, sg::ratio(R_d, R_v), cloud_threshold, num_cloud, num_precip};
-  hipLaunchKernelGGL(sgs_coef_moist_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, ny, nz, level, F, W, zint, zmid, P, M, tk, tkh);
+  if (K)
+    hipLaunchKernelGGL(sgs_tke_coef_moist_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, ny, nz, level, F, W, zint, zmid, P, M, Q, K->tke, tk,
+                       tkh);
+  else
+    hipLaunchKernelGGL(sgs_coef_moist_kernel, grid, block, 0, (hipStream_t)stream, nens, nx, ny, nz, level, F, W, zint, zmid, P, M, tk, tkh);
   return stats_launch_check(who);
 }
 
@@ -3992,6 +4051,26 @@ extern "C" int pam_amd_sgs_smag_coefficients_moist(int nens, int nx, int ny, int
                                                    double cloud_threshold, double cs, double prandtl, double *tk, double *tkh, void *stream) {
   return sgs_coefficients("sgs_smag_coefficients_moist", true, nens, nx, ny, nz, uvel, vvel, wvel, temp, rho_d, rho_v, num_cloud, cloud, num_precip,
                           precip, zint, zmid, dx, dy, grav, cp_d, R_d, R_v, cloud_threshold, cs, prandtl, tk, tkh, stream);
+}
+
+extern "C" int pam_amd_sgs_tke_coefficients(int nens, int nx, int ny, int nz, const double *uvel, const double *vvel, const double *wvel,
+                                            const double *temp, const double *rho_d, const double *rho_v, double *tke, const double *zint,
+                                            const double *zmid, double dx, double dy, double dt, double grav, double cp_d, double ck, double ce1,
+                                            double ce2, double seed, double *tk, double *tkh, void *stream) {
+  const SgsTkeCall K{tke, dt, ck, ce1, ce2, seed};
+  return sgs_coefficients("sgs_tke_coefficients", false, nens, nx, ny, nz, uvel, vvel, wvel, temp, rho_d, rho_v, 0, nullptr, 0, nullptr, zint, zmid,
+                          dx, dy, grav, cp_d, 0.0, 0.0, 0.0, 0.0, 0.0, tk, tkh, stream, &K);
+}
+
+extern "C" int pam_amd_sgs_tke_coefficients_moist(int nens, int nx, int ny, int nz, const double *uvel, const double *vvel, const double *wvel,
+                                                  const double *temp, const double *rho_d, const double *rho_v, double *tke, int num_cloud,
+                                                  const double *const *cloud, int num_precip, const double *const *precip, const double *zint,
+                                                  const double *zmid, double dx, double dy, double dt, double grav, double cp_d, double R_d,
+                                                  double R_v, double cloud_threshold, double ck, double ce1, double ce2, double seed, double *tk,
+                                                  double *tkh, void *stream) {
+  const SgsTkeCall K{tke, dt, ck, ce1, ce2, seed};
+  return sgs_coefficients("sgs_tke_coefficients_moist", true, nens, nx, ny, nz, uvel, vvel, wvel, temp, rho_d, rho_v, num_cloud, cloud, num_precip,
+                          precip, zint, zmid, dx, dy, grav, cp_d, R_d, R_v, cloud_threshold, 0.0, 0.0, tk, tkh, stream, &K);
 }
 
 extern "C" int pam_amd_sgs_smag_diffuse(int nens, int nx, int ny, int nz, double *uvel, double *vvel, double *wvel, double *temp,

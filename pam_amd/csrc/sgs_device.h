@@ -10,6 +10,10 @@
 // and the surface fluxes of heat and vapour (solve_class_t<true>) are further instances of the same two bodies; the instances the dry
 // entry points use (coef_column, solve_class) are the <false> ones.  tests/emu/sgs_moist_emu.cpp compiles the new ones under g++ and
 // tests/sgs_moist_ref.py restates them.
+// The prognostic-TKE (1.5-order) closure is one more instance of the coefficient walk (coef_column_t<MOIST, true>): tke_step() stands in
+// eddy()'s place, the thread reads and writes its own cell of the tracer tke (rho e) level by level, and rho of level k rides along with
+// the centre values.  The instances above are what they were (TKE defaults to false and its two arguments to nullptr).
+// tests/emu/sgs_tke_emu.cpp compiles the new ones under g++ and tests/sgs_tke_ref.py restates them.
 #pragma once
 
 #include <cmath>
@@ -87,6 +91,59 @@ PAMA_D void eddy(double def2, double n2, double dz, double cs, double prandtl, d
   const double m = arg < 0.0 ? 0.0 : arg;
   tk = l2 * std::sqrt(m);
   tkh = tk / prandtl;
+}
+
+// ---- the prognostic-TKE (1.5-order) closure: one cell's step of e = tke / rho and the coefficients it gives
+struct TkeParams {
+  double dt, ck, ce1, ce2, seed;
+};
+
+// host, once per class: ce = ck^3 / cs^4, so that the neutral fixed point is Smagorinsky's tk = (cs delta)^2 sqrt(Def2); ce1 and ce2 are
+// Deardorff's split of the dissipation constant (0.19 + 0.51 l / delta, which is 0.7 at l = delta)
+inline double tke_ce(double cs, double ck) {
+  PAMA_NO_CONTRACT
+  return ((ck * ck) * ck) / ((cs * cs) * (cs * cs));
+}
+inline double tke_ce1(double ce) {
+  PAMA_NO_CONTRACT
+  return (ce / 0.7) * 0.19;
+}
+inline double tke_ce2(double ce) {
+  PAMA_NO_CONTRACT
+  return (ce / 0.7) * 0.51;
+}
+
+// e0 = max(tke / rho, 0); l = delta where N2 <= 0, else 0.76 sqrt(e0 / N2) held inside [0.1 delta, delta]; pri = 1 + 2 l / delta;
+// e1 = max(e0 + dt (ks Def2 - ks pri N2), 0) with ks = ck l sqrt(e0) + seed; e2 = e1 / (1 + dt (ce1 + ce2 l / delta) sqrt(e0) / l): the
+// dissipation linearised about the TKE at entry; tk = ck l sqrt(e2), tkh = pri tk.  tke keeps its bits where e2 == tke / rho.  Every
+// comparison is written so that a NaN takes the else arm and goes on through the arithmetic
+PAMA_D void tke_step(double tke_in, double rho, double def2, double n2, double delta, const TkeParams &Q, double &tke_out, double &tk,
+                     double &tkh) {
+  PAMA_NO_CONTRACT
+  const double x = tke_in / rho;
+  const double e0 = x < 0.0 ? 0.0 : x;
+  const double se = std::sqrt(e0);
+  double l = delta;
+  if (n2 > 0.0) {
+    const double ls = (0.76 * se) / std::sqrt(n2);
+    const double lo = 0.1 * delta;
+    const double m = ls < lo ? lo : ls;
+    l = m > delta ? delta : m;
+  }
+  const double r = l / delta;
+  const double pri = 1.0 + 2.0 * r;
+  const double ckl = Q.ck * l;
+  const double ks = ckl * se + Q.seed;
+  const double p = ks * def2;
+  const double b = (ks * pri) * n2;
+  const double s = p - b;
+  double e1 = e0 + Q.dt * s;
+  e1 = e1 < 0.0 ? 0.0 : e1;
+  const double c = Q.ce1 + Q.ce2 * r;
+  const double e2 = e1 / (1.0 + ((Q.dt * c) * se) / l);
+  tke_out = e2 == x ? tke_in : rho * e2;
+  tk = ckl * std::sqrt(e2);
+  tkh = pri * tk;
 }
 
 // ---- the moist branch of the coefficients
@@ -211,6 +268,11 @@ PAMA_D double stability_saturated(double grav, double gc, const MoistParams &M, 
   return grav * (m - dqtdz);
 }
 
+PAMA_D double total_density(double rho_d, double rho_v) {
+  PAMA_NO_CONTRACT
+  return rho_d + rho_v;
+}
+
 PAMA_D int wrap_up(int i, int n) { return i + 1 == n ? 0 : i + 1; }
 PAMA_D int wrap_down(int i, int n) { return i == 0 ? n - 1 : i - 1; }
 
@@ -219,10 +281,12 @@ PAMA_D int wrap_down(int i, int n) { return i == 0 ? n - 1 : i - 1; }
 // level k are read from the fields.  tk and tkh overlap nothing that is read (the entry point refuses it)
 // MOIST: cloud[M.num_cloud] and precip[M.num_precip] point at element 0 of the condensate densities, and a saturated level k takes
 // stability_saturated; without it the two tables and M are never read
-template <bool MOIST>
+// TKE: the prognostic closure in place of eddy(): rho of level k rides along as well, tke (rho e, element 0) is read and written in the
+// thread's own cell only, and Q holds the constants; P.cs and P.prandtl are not read.  Without it Q and tke are never read
+template <bool MOIST, bool TKE = false>
 PAMA_D void coef_column_t(const double *const *f, const double *const *cloud, const double *const *precip, const MoistParams &M, const double *zint,
                           const double *zmid, long long level, int nens, int nx, int ny, int nz, int j, int i, int e, const CoefParams &P,
-                          double *__restrict__ tk, double *__restrict__ tkh) {
+                          double *__restrict__ tk, double *__restrict__ tkh, const TkeParams *Q = nullptr, double *__restrict__ tke = nullptr) {
   const bool with_y = ny > 1;
   const long long row = (long long)j * nx;
   const long long c0 = (row + i) * nens + e;
@@ -231,6 +295,8 @@ PAMA_D void coef_column_t(const double *const *f, const double *const *cloud, co
   const double *u = f[0], *v = f[1], *w = f[2], *T = f[3], *rd = f[4], *rv = f[5];
   double u_k = u[c0], v_k = v[c0], w_k = w[c0];
   Thermo a_k = thermo<MOIST>(T[c0], rd[c0], rv[c0], cloud, precip, c0, M);
+  [[maybe_unused]] double rho_k = 0.0;
+  if constexpr (TKE) rho_k = total_density(rd[c0], rv[c0]);
   double zm_k = zmid[0];
   double u_m = u_k, v_m = v_k, w_m = w_k, zm_m = zm_k;      // the one-sided difference at the ground
   Thermo a_m = a_k;
@@ -240,6 +306,11 @@ PAMA_D void coef_column_t(const double *const *f, const double *const *cloud, co
     const long long lu = (long long)ku * level + c0, lk = (long long)k * level;
     const double u_p = u[lu], v_p = v[lu], w_p = w[lu];
     const Thermo a_p = thermo<MOIST>(T[lu], rd[lu], rv[lu], cloud, precip, lu, M);
+    [[maybe_unused]] double rho_p = 0.0, e_k = 0.0;
+    if constexpr (TKE) {
+      rho_p = total_density(rd[lu], rv[lu]);
+      e_k = tke[lk + c0];
+    }
     const double zm_p = zmid[(long long)ku * nens];
     const double zi_p = zint[(long long)(k + 1) * nens];
     const double span = zm_p - zm_m;
@@ -260,7 +331,14 @@ PAMA_D void coef_column_t(const double *const *f, const double *const *cloud, co
                                  centred(a_p.qt, a_m.qt, span));
     }
     double a, b;
-    eddy(def2, n2, zi_p - zi_k, P.cs, P.prandtl, a, b);
+    if constexpr (TKE) {
+      double e_new;
+      tke_step(e_k, rho_k, def2, n2, zi_p - zi_k, *Q, e_new, a, b);
+      tke[lk + c0] = e_new;
+      rho_k = rho_p;
+    } else {
+      eddy(def2, n2, zi_p - zi_k, P.cs, P.prandtl, a, b);
+    }
     tk[lk + c0] = a;
     tkh[lk + c0] = b;
     u_m = u_k; v_m = v_k; w_m = w_k; a_m = a_k; zm_m = zm_k;

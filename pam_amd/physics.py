@@ -6,6 +6,7 @@
   SGSNone           physics/sgs/none/SGS.h
   SGSShoc           physics/sgs/shoc/SGS.h                 the coupling layer around shoc_main; SHOC itself is handed in by the caller
   SGSSmagorinsky    (this project's)                       the native Smagorinsky-Lilly closure with an implicit vertical solve
+  SGSTke            (this project's)                       the native prognostic-TKE (1.5-order) closure over the same solve
   MicrophysicsNone  physics/micro/none/Microphysics.h      registers and zeroes "water_vapor", sets the constants
   MicrophysicsP3    physics/micro/p3/Microphysics.h        the coupling layer around p3_main; P3 itself is handed in by the caller
 
@@ -347,6 +348,118 @@ class SGSSmagorinsky:
                                                         rho_d.data_ptr(), rho_v.data_ptr(), zint.data_ptr(), zmid.data_ptr(),
                                                         float(coupler.get_dx()), float(coupler.get_dy()), grav, cp_d, cs, prandtl,
                                                         tk.data_ptr(), tkh.data_ptr(), stream))
+            if fluxes:
+                shf, lhf = dm.get("sfc_shf", readonly=True), dm.get("sfc_lhf", readonly=True)
+                latvap = float(coupler.get_option("latvap")) if coupler.option_exists("latvap") else self.LATVAP
+                check(lib.pam_amd_sgs_smag_diffuse_fluxes(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(),
+                                                          len(tracers), table, rho_d.data_ptr(), rho_v.data_ptr(), tk.data_ptr(), tkh.data_ptr(),
+                                                          zint.data_ptr(), zmid.data_ptr(), flx_u.data_ptr(), flx_v.data_ptr(), dt, grav, cp_d,
+                                                          shf.data_ptr(), lhf.data_ptr(), latvap, stream))
+            else:
+                check(lib.pam_amd_sgs_smag_diffuse(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(), len(tracers),
+                                                   table, rho_d.data_ptr(), rho_v.data_ptr(), tk.data_ptr(), tkh.data_ptr(), zint.data_ptr(),
+                                                   zmid.data_ptr(), flx_u.data_ptr(), flx_v.data_ptr(), dt, grav, cp_d, stream))
+
+    def finalize(self, coupler):
+        pass
+
+
+class SGSTke:
+    """physics/sgs/tke_amd/SGS.h: the native prognostic-TKE (1.5-order, Deardorff 1980) closure.  Not part of the reference tree; the
+    contract is this project's (include/pam_amd_modules.h at pam_amd_sgs_tke_coefficients).  The turbulence energy
+    lives in the tracer "tke" (rho e), which the dycore transports like any tracer: so init runs BEFORE Dycore.init, as SGSShoc's does.
+    timeStep steps tke in place by shear production, buoyancy and dissipation and fills "tk" and "tkh" (one launch), then mixes uvel,
+    vvel, wvel, temp and every registered tracer, tke among them, with the Smagorinsky closure's solve (one launch, unchanged).
+    moist and surface_fluxes are SGSSmagorinsky's: the species by option "micro", "sfc_shf" and "sfc_lhf" into row 0."""
+    FIELDS = SGSSmagorinsky.FIELDS
+    FLUX_FIELDS = SGSSmagorinsky.FLUX_FIELDS
+    OPTIONS = ("sgs", "sgs_tke_cs", "sgs_tke_ck", "sgs_tke_seed", "sgs_tke_moist", "sgs_tke_surface_fluxes", "sgs_tke_cloud_threshold")
+    OPTIONS_READ = ("crm_dt", "grav", "cp_d", "sgs_tke_cs", "sgs_tke_ck", "sgs_tke_seed")
+    LATVAP = SGSSmagorinsky.LATVAP
+
+    def __init__(self, cs=0.2, ck=0.1, seed=1e-3, moist=False, surface_fluxes=False, cloud_threshold=0.0):
+        self.cs, self.ck, self.seed = float(cs), float(ck), float(seed)
+        self.moist, self.surface_fluxes, self.cloud_threshold = bool(moist), bool(surface_fluxes), float(cloud_threshold)
+
+    @staticmethod
+    def get_num_tracers():
+        return 1
+
+    @staticmethod
+    def sgs_name():
+        return "tke"
+
+    @staticmethod
+    def constants(cs, ck):
+        """ce, ce1, ce2 in the contract's order: the bits the C++ class forms (sgs_device.h: tke_ce, tke_ce1, tke_ce2)"""
+        cs, ck = float(cs), float(ck)
+        ce = ((ck * ck) * ck) / ((cs * cs) * (cs * cs))
+        return ce, (ce / 0.7) * 0.19, (ce / 0.7) * 0.51
+
+    def init(self, coupler):
+        """the tracer "tke" where absent (positive, adds no mass, zero-filled), as SGSShoc.init registers it; "tk", "tkh" and
+        "sfc_mom_flx_u/v" where absent, zero-filled; option "sgs" = "tke"; the options sgs_tke_cs, sgs_tke_ck, sgs_tke_seed,
+        sgs_tke_moist, sgs_tke_surface_fluxes and sgs_tke_cloud_threshold unless present; with surface fluxes "sfc_shf" and "sfc_lhf" where
+        absent, zero-filled"""
+        nens, nz, ny, nx = coupler.get_nens(), coupler.get_nz(), coupler.get_ny(), coupler.get_nx()
+        if min(nens, nz, ny, nx) < 1:
+            endrun("ERROR: sgs: the coupler state is not allocated")
+        dm = coupler.get_data_manager_device_readwrite()
+        if "tke" not in coupler.get_tracer_names():
+            coupler.add_tracer("tke", "Turbulent Kinetic Energy (m^2/s^2)", True, False)
+            dm.get("tke").zero_()
+        for name, rank in self.FIELDS:
+            if not dm.entry_exists(name):
+                if rank == 4:
+                    dm.register_and_allocate(name, "Eddy coefficient [m2/s]", (nz, ny, nx, nens), ("z", "y", "x", "nens"))
+                else:
+                    dm.register_and_allocate(name, "Surface momentum flux", (ny, nx, nens), ("y", "x", "nens"))
+        coupler.set_option("sgs", "tke")
+        for name, value in (("sgs_tke_cs", self.cs), ("sgs_tke_ck", self.ck), ("sgs_tke_seed", self.seed), ("sgs_tke_moist", self.moist),
+                            ("sgs_tke_surface_fluxes", self.surface_fluxes), ("sgs_tke_cloud_threshold", self.cloud_threshold)):
+            if not coupler.option_exists(name):
+                coupler.set_option(name, value)
+        if coupler.get_option("sgs_tke_surface_fluxes"):
+            for name, desc in self.FLUX_FIELDS:
+                if not dm.entry_exists(name):
+                    dm.register_and_allocate(name, desc, (ny, nx, nens), ("y", "x", "nens"))
+
+    def timeStep(self, coupler):
+        """the coefficient launch (tke in place), then the solve, on the current stream"""
+        lib = capi.load()
+        nens, nz, ny, nx = coupler.get_nens(), coupler.get_nz(), coupler.get_ny(), coupler.get_nx()
+        dt, grav, cp_d, cs, ck, seed = (float(coupler.get_option(n)) for n in self.OPTIONS_READ)
+        ce, ce1, ce2 = self.constants(cs, ck)
+        moist, fluxes = bool(coupler.get_option("sgs_tke_moist")), bool(coupler.get_option("sgs_tke_surface_fluxes"))
+        dm = coupler.get_data_manager_device_readwrite()
+        u, v, w, temp, tke, tk, tkh = (dm.get(n) for n in ("uvel", "vvel", "wvel", "temp", "tke", "tk", "tkh"))
+        rho_d, rho_v = dm.get("density_dry", readonly=True), dm.get("water_vapor", readonly=True)
+        zint, zmid = dm.get("vertical_interface_height", readonly=True), dm.get("vertical_midpoint_height", readonly=True)
+        flx_u, flx_v = dm.get("sfc_mom_flx_u", readonly=True), dm.get("sfc_mom_flx_v", readonly=True)
+        tracers = [dm.get(n) for n in coupler.get_tracer_names()]
+        table = (C.c_void_p * max(len(tracers), 1))(*[t.data_ptr() for t in tracers])
+        with torch.cuda.device(coupler.device):
+            stream = torch.cuda.current_stream(coupler.device).cuda_stream
+            if moist:
+                micro = coupler.get_option("micro") if coupler.option_exists("micro") else "none"
+                species = dict(SGSSmagorinsky.CONDENSATE, **SGSSmagorinsky.CONDENSATE_ICE1M)
+                if micro not in species:
+                    endrun("ERROR: sgs: the moist branch knows the species of micro = kessler, p3 and none, not of " + str(micro))
+                cloud, precip = ([dm.get(n, readonly=True) for n in names] for names in species[micro])
+                ctab = (C.c_void_p * 4)(*[t.data_ptr() for t in cloud])
+                ptab = (C.c_void_p * 8)(*[t.data_ptr() for t in precip])
+                check(lib.pam_amd_sgs_tke_coefficients_moist(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(),
+                                                             rho_d.data_ptr(), rho_v.data_ptr(), tke.data_ptr(), len(cloud), ctab, len(precip),
+                                                             ptab, zint.data_ptr(), zmid.data_ptr(), float(coupler.get_dx()),
+                                                             float(coupler.get_dy()), dt, grav, cp_d, float(coupler.get_option("R_d")),
+                                                             float(coupler.get_option("R_v")),
+                                                             float(coupler.get_option("sgs_tke_cloud_threshold")), ck, ce1, ce2, seed,
+                                                             tk.data_ptr(), tkh.data_ptr(), stream))
+            else:
+                check(lib.pam_amd_sgs_tke_coefficients(nens, nx, ny, nz, u.data_ptr(), v.data_ptr(), w.data_ptr(), temp.data_ptr(),
+                                                       rho_d.data_ptr(), rho_v.data_ptr(), tke.data_ptr(), zint.data_ptr(), zmid.data_ptr(),
+                                                       float(coupler.get_dx()), float(coupler.get_dy()), dt, grav, cp_d, ck, ce1, ce2, seed,
+                                                       tk.data_ptr(), tkh.data_ptr(), stream))
             if fluxes:
                 shf, lhf = dm.get("sfc_shf", readonly=True), dm.get("sfc_lhf", readonly=True)
                 latvap = float(coupler.get_option("latvap")) if coupler.option_exists("latvap") else self.LATVAP

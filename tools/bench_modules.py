@@ -21,6 +21,8 @@ and msa_diagnose of the same run;
 --only sgs: the native Smagorinsky SGS closure's coefficient launch (dry and moist) and its solve (c' in LDS and in the workspace, and
 with the surface fluxes of heat and vapour) on Kessler's field set at the C2 grid and at C4's 32x1x60 grid with 8192 members, beside
 hyperdiffusion and msa_apply of the same run;
+--only sgs_tke: the prognostic-TKE closure's coefficient launch (dry and moist) on the same field set and grids, beside the two Smagorinsky
+coefficient launches of the same run;
 --only grayrad: the native grey two-stream longwave scheme (pam_amd_radiation_gray) at the C2 grid and at C4's 32x1x60 grid with 8192
 members on Kessler's and on P3's field set, beside column_diagnostics and pam_amd_sgs_smag_coefficients of the same run;
 --only ice1m: the one-moment ice microphysics (pam_amd_ice1m_time_step) on a clear, a raining and snowing and a deep_fall state at the
@@ -1363,6 +1365,101 @@ def sgs_timing(dev, warmup=3, n=11):
     return out
 
 
+def sgs_tke_timing(dev, warmup=3, n=11):
+    """The prognostic-TKE closure's coefficient launch (pam_amd_sgs_tke_coefficients, dry and moist) on Kessler's field set at the C2 grid and
+    at C4's 32x1x60 grid with 8192 members, beside pam_amd_sgs_smag_coefficients of the same run: 3 warm-up calls and the median of 11
+    event-timed calls each.  Algorithmic bytes: 10 x 8 B per cell for the dry launch (six inputs, tke read and written, tk and tkh
+    written) against 8 x 8 B for the dry Smagorinsky launch; the moist launch reads one cloud and one precipitating species more.  tke is
+    stepped in place, so every call starts from what the call before it left (it stays finite and non-negative); every cell of this
+    state is cloudy, so every lane of the moist launch takes the saturated branch."""
+    import ctypes as C
+    from pam_amd import PamCoupler, SGSTke, capi
+    from pam_amd import idealized as idz
+    lib = capi.load()
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    def row(t, nbytes):
+        return {"ms": t[0], "min_ms": t[1], "max_ms": t[2], "bytes": nbytes, "GBps": nbytes / t[0] / 1e6,
+                "hbm_frac": nbytes / t[0] / 1e6 / bench.HBM_PEAK_GBS}
+
+    def grid(nens, nx, ny, nz, label, out):
+        cells = nens * nx * ny * nz
+        c = PamCoupler(dev)
+        c.set_option("crm_dt", 2.0)
+        c.set_option("grav", 9.80616)
+        c.set_option("cp_d", 1004.64)
+        c.allocate_coupler_state(nz, ny, nx, nens)
+        c.set_grid(nx * 1000.0, ny * 1000.0, idz.l60_interfaces())
+        for t in ("water_vapor", "cloud_liquid", "precip_liquid"):
+            c.add_tracer(t, "", True, True)
+        c.set_option("micro", "kessler")
+        sgs = SGSTke()
+        sgs.init(c)
+        dm = c.get_data_manager_device_readwrite()
+        gen = torch.Generator(device=dev).manual_seed(0)
+        for name, lo, span in (("density_dry", 0.5, 0.7), ("uvel", -5.0, 10.0), ("vvel", -5.0, 10.0), ("wvel", -1.0, 2.0), ("temp", 250.0, 50.0),
+                               ("water_vapor", 0.0, 0.01), ("cloud_liquid", 0.0, 0.001), ("precip_liquid", 0.0, 0.001), ("tke", 0.0, 1.0)):
+            t = dm.get(name)
+            t.copy_(torch.rand(t.shape, generator=gen, dtype=torch.float64, device=dev) * span + lo)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        P = lambda name: dm.get(name).data_ptr()
+        ce, ce1, ce2 = SGSTke.constants(0.2, 0.1)
+        ctab, ptab = (C.c_void_p * 4)(P("cloud_liquid")), (C.c_void_p * 8)(P("precip_liquid"))
+        six = ("uvel", "vvel", "wvel", "temp", "density_dry", "water_vapor")
+
+        def smag():
+            capi.check(lib.pam_amd_sgs_smag_coefficients(nens, nx, ny, nz, *[P(f) for f in six], P("vertical_interface_height"),
+                                                         P("vertical_midpoint_height"), 1000.0, 1000.0, 9.80616, 1004.64, 0.2, 1.0 / 3.0, P("tk"),
+                                                         P("tkh"), stream))
+
+        def smag_moist():
+            capi.check(lib.pam_amd_sgs_smag_coefficients_moist(nens, nx, ny, nz, *[P(f) for f in six], 1, ctab, 1, ptab,
+                                                               P("vertical_interface_height"), P("vertical_midpoint_height"), 1000.0, 1000.0,
+                                                               9.80616, 1004.64, 287.042, 461.505, 0.0, 0.2, 1.0 / 3.0, P("tk"), P("tkh"), stream))
+
+        def tke():
+            capi.check(lib.pam_amd_sgs_tke_coefficients(nens, nx, ny, nz, *[P(f) for f in six], P("tke"), P("vertical_interface_height"),
+                                                        P("vertical_midpoint_height"), 1000.0, 1000.0, 2.0, 9.80616, 1004.64, 0.1, ce1, ce2, 1e-3,
+                                                        P("tk"), P("tkh"), stream))
+
+        def tke_moist():
+            capi.check(lib.pam_amd_sgs_tke_coefficients_moist(nens, nx, ny, nz, *[P(f) for f in six], P("tke"), 1, ctab, 1, ptab,
+                                                              P("vertical_interface_height"), P("vertical_midpoint_height"), 1000.0, 1000.0, 2.0,
+                                                              9.80616, 1004.64, 287.042, 461.505, 0.0, 0.1, ce1, ce2, 1e-3, P("tk"), P("tkh"),
+                                                              stream))
+
+        out["sgs_smag_coefficients" + label] = row(timed(smag), cells * 64.0)
+        out["sgs_smag_coefficients_moist" + label] = row(timed(smag_moist), cells * 80.0)
+        out["sgs_tke_coefficients" + label] = row(timed(tke), cells * 80.0)
+        out["sgs_tke_coefficients_moist" + label] = row(timed(tke_moist), cells * 96.0)
+        for f in ("tke", "tk", "tkh"):
+            assert bool(torch.isfinite(dm.get(f, readonly=True)).all()) and float(dm.get(f, readonly=True).min()) >= 0, f
+        for a, b in (("sgs_tke_coefficients", "sgs_smag_coefficients"), ("sgs_tke_coefficients_moist", "sgs_smag_coefficients_moist")):
+            out["%s%s_vs_smag_time" % (a, label)] = out[a + label]["ms"] / out[b + label]["ms"]
+        del c, dm, sgs
+        lib.pam_amd_modules_finalize()
+        torch.cuda.empty_cache()
+
+    out = {"sgs_tke_grid": "1024 x 32x32x60 (C2) and 8192 x 32x1x60 (C4)",
+           "sgs_tke_method": "%d warm-up calls, median of %d event-timed calls" % (warmup, n)}
+    grid(1024, 32, 32, 60, "", out)
+    grid(8192, 32, 1, 60, "_c4", out)
+    return out
+
+
 def grayrad_timing(dev, warmup=3, n=11):
     """The native grey two-stream longwave scheme (pam_amd_radiation_gray) at the C2 grid and at C4's 32x1x60 grid with 8192 members, with
     Kessler's field set (one liquid species) and with P3's (one liquid, one ice), 3 warm-up calls and the median of 11 event-timed calls
@@ -2001,6 +2098,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:] == ["--only", "grayrad"]:
         print(json.dumps(grayrad_timing(dev)))
+        sys.exit(0)
+    if sys.argv[1:] == ["--only", "sgs_tke"]:
+        print(json.dumps(sgs_tke_timing(dev)))
         sys.exit(0)
     if sys.argv[1:] == ["--only", "sgs"]:
         print(json.dumps(sgs_timing(dev)))
