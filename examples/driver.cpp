@@ -339,7 +339,8 @@ static void run_rank(Job &J, int rank, int world, int ndev, HostMin &hmin, Bench
 // unreadable here; its contents are what the name says (read from the raw bytes of the reference's copy: 51 interfaces 0, 400, ...,
 // 20000 m for vcoords_equal_50_20km.nc): N equal levels up to H km.
 // --nens overrides the file's ensemble size, --steps stops after S CRM steps, --check switches the dycore's conservation check on
-// (Dycore.h:224-251) and the last stdout line is a JSON object with the run's statistics.
+// (Dycore.h:224-251) and the last stdout line is a JSON object with the run's statistics.  --dump-init PATH (a debug flag, like --sync)
+// writes the state the first CRM step starts from, after every init, to PATH: the fields of the output file in its order, without precl.
 static std::map<std::string, std::string> read_flat_yaml(const std::string &file) {
   std::ifstream in(file);
   if (!in) die("cannot open the YAML input");
@@ -389,7 +390,10 @@ static void initialize_from_supercell_column(std::vector<real> const &zint_in, p
 }
 
 #ifndef PAMC_DYCORE
-struct YamlDebug { bool no_micro = false, no_sponge = false, sync = false; };      // bisection switches (tools/repro_ci_run.py has the Python twin)
+struct YamlDebug {                                                                  // bisection switches (tools/repro_ci_run.py has the Python twin)
+  bool no_micro = false, no_sponge = false, sync = false;
+  std::string dump_init;      // --dump-init PATH: the state the first CRM step starts from, the fields in the output file's order
+};
 // opt-in modules of the CRM step (off: the run is the one above, byte for byte):
 //   --sat-adjust               modules::saturation_adjustment after micro
 //   --surface-friction TAU BFLX  modules::surface_friction_init once (every member: tau = TAU, bflx = BFLX), then
@@ -747,6 +751,17 @@ static int run_yaml(const std::string &file, int nens_override, int steps_limit,
     auto fetch = [&](std::string const &name) {
       if (hipMemcpy(buf.data(), dm.get<real const, 4>(name).data(), ncell * sizeof(real), hipMemcpyDeviceToHost) != hipSuccess) endrun("memcpy");
     };
+    if (!dbg.dump_init.empty()) {                                            // --dump-init: what the loop starts from, before the first step
+      std::ofstream di(dbg.dump_init, std::ios::binary);
+      if (!di) endrun("cannot open the --dump-init file");
+      std::vector<std::string> init_names = {"density_dry", "uvel", "vvel", "wvel", "temp"};
+      for (auto &n : coupler.get_tracer_names()) init_names.push_back(n);
+      for (auto &n : init_names) {
+        fetch(n);
+        di.write((char *)buf.data(), ncell * sizeof(real));
+      }
+      if (!di) endrun("cannot write the --dump-init file");
+    }
     // --stats: the fields averaged over each GCM step, and their profiles as JSON
     const bool stats = !mods.stats.empty();
     std::vector<std::string> stat_names = {"density_dry", "uvel", "vvel", "wvel", "temp"};
@@ -1191,6 +1206,7 @@ int main(int argc, char **argv) {
       else if (o == "--no-micro") dbg.no_micro = true;
       else if (o == "--no-sponge") dbg.no_sponge = true;
       else if (o == "--sync") dbg.sync = true;
+      else if (o == "--dump-init" && b + 1 < argc - 1) dbg.dump_init = argv[++b];
       else if (o == "--sat-adjust") mods.sat_adjust = true;
       else if (o == "--surface-friction" && b + 2 < argc - 1) {
         mods.surface_friction = true;
